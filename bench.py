@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- end-to-end mv.Super + mv.Analyse(x2*tr) + mv.DegrainN throughput on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3|cfg2|cfg1|cfg5] [--batch B] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3|cfg2|cfg1|cfg5] [--batch B] [--dump-outputs DIR] [--full [--no-cpu]]
 
 A "step" is one pass of the hot path over one batch of B synthetic frames already resident in HBM:
 Super of the B+2*tr frames (batch + temporal halo), 2*tr*B motion searches (one chain per frame and direction, all in
@@ -13,6 +13,10 @@ is one of N ranks and N must equal WORLD_SIZE; started directly with N > 1 it la
 torch.distributed.run on 127.0.0.1 and fails loudly when the node has fewer than N GPUs.  The ranks' frame ranges come
 from mvtools_amd.shard.RankPlan (the clip is N*B output frames plus a tr-frame lead-in / lead-out; rank r owns a
 contiguous range and holds its tr-frame halo, which it runs Super on itself).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else after the timed steps: the search launch
+alone, one batch in flight, the CPU baseline and the oracle comparison of the timed step, the HBM traffic of a search launch, and for cfg3 the
+other configurations and the VapourSynth filter shell.  --dump-outputs DIR writes the last timed step's output frames (dump_outputs).
 """
 import argparse
 import json
@@ -272,6 +276,50 @@ class PipelineFPS:
     level_grids = Pipeline.level_grids
 
 
+def _output_clips(pipe):
+    """{name: frames} of what one step delivers to its caller: DegrainN's output frames, or cfg4's compensated and interpolated frames"""
+    if isinstance(pipe, PipelineFPS):
+        return {"compensate": pipe.comp_out, "blockfps": pipe.fps_out}
+    return {"degrain%d" % pipe.tr: pipe.out}
+
+
+def dump_outputs(torch, pipe, out_dir, prefix="", budget=48 << 20, seed=20240601):
+    """--dump-outputs DIR: the output frames of `pipe`'s last step as DIR/<prefix><clip>_*.npy, so that two builds can be compared output for
+    output.  Per output clip, float64 `<clip>_sums` [frame, plane, (sum, position-weighted sum)] over the visible pixels of every frame, and per
+    plane a fixed, seeded sample of whole visible rows: float32 `<clip>_<plane>` [row, pixel] with float64 `<clip>_<plane>_rows` [row, (frame, line)].
+    The row samples of all clips share `budget` bytes.  Returns the files written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    clips = _output_clips(pipe)
+    bps = 2 if pipe.bits > 8 else 1
+    written = []
+    rows_each = max(1, budget // (len(clips) * 4 * 2 * pipe.w))   # (luma row + two chroma rows of half the width) x float32
+    for ci, (name, frames) in enumerate(clips.items()):
+        sums = []
+        for p, plane_name in enumerate(("y", "u", "v")):
+            h, w = pipe.h >> (1 if p else 0), pipe.w >> (1 if p else 0)
+            weight = (torch.arange(h * w, device=frames[0][p].device, dtype=torch.int64) % 251 + 1).view(h, w)
+
+            def pixels(t):
+                v = t[:, :w * bps].to(torch.int64)
+                return v[:, 0::2] | (v[:, 1::2] << 8) if bps == 2 else v
+            sums.append(torch.stack([torch.stack([x.sum(), (x * weight).sum()]) for x in map(pixels, (f[p] for f in frames))]))
+            rng = np.random.default_rng(seed + 16 * ci + p)
+            pick = np.sort(rng.choice(len(frames) * h, size=min(rows_each, len(frames) * h), replace=False))
+            fr, ln = pick // h, pick % h
+            rows = []
+            for f in np.unique(fr):
+                idx = torch.as_tensor(ln[fr == f], device=frames[f][p].device)
+                rows.append(pixels(frames[f][p].index_select(0, idx)))
+            written.append(os.path.join(out_dir, "%s%s_%s.npy" % (prefix, name, plane_name)))
+            np.save(written[-1], torch.cat(rows).cpu().numpy().astype(np.float32))
+            written.append(os.path.join(out_dir, "%s%s_%s_rows.npy" % (prefix, name, plane_name)))
+            np.save(written[-1], np.stack([fr, ln], axis=1).astype(np.float64))
+        written.append(os.path.join(out_dir, "%s%s_sums.npy" % (prefix, name)))
+        np.save(written[-1], torch.stack(sums, dim=1).cpu().numpy().astype(np.float64))
+    return written
+
+
 def _frame_to_numpy(mv, frame, w, h, bits):
     import numpy as np
     dt = np.uint16 if bits > 8 else np.uint8
@@ -451,7 +499,7 @@ def other_configs():
     import subprocess
     res = {}
     for c in ("cfg2", "cfg4", "cfg5", "hd16"):
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", c, "--steps", "4", "--warmup", "2", "--no-cpu", "--no-traffic", "--no-others"]
+        cmd = [sys.executable, os.path.abspath(__file__), "--config", c, "--steps", "4", "--warmup", "2", "--full", "--no-cpu", "--no-traffic", "--no-others"]
         try:
             p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=420)
             line = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")][-1]
@@ -616,7 +664,7 @@ def measure_traffic(args, B):
         # (counters for the search kernels only: with every torch kernel of the clip generator instrumented too, rocprofv3 7.2 crashed -- SIGSEGV inside a torch
         # multiply -- in two of two r5 runs; the bytes this function reports are the search launch's anyway)
         cmd = [exe, "--pmc", c, "--kernel-trace", "--kernel-include-regex", "analyse_", "--output-format", "csv", "-d", d, "-o", "p", "--", sys.executable, os.path.abspath(__file__),
-               "--no-cpu", "--no-parity", "--no-traffic", "--steps", "1", "--warmup", "0", "--config", args.config, "--batch", str(B), "--slots", str(args.slots)]
+               "--full", "--no-cpu", "--no-parity", "--no-traffic", "--steps", "1", "--warmup", "0", "--config", args.config, "--batch", str(B), "--slots", str(args.slots)]
         try:
             pr = subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=300)
             if pr.returncode != 0:
@@ -722,17 +770,24 @@ def main():
                     "the current one's finishing chains free.  Default: 2 (cfg3 +11 %%: profiles/r5_batches_in_flight_unchained.txt, 2 x 107 GB of the 288 GB; "
                     "cfg2 / cfg4 / hd16 +3 %%: their chains finish together, there is little tail to fill), 1 for cfg5 (no room).  Stream priorities change nothing "
                     "(profiles/r5_batches_in_flight_other_configs.txt)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline (a two-frame parity check of the timed step still runs)")
-    ap.add_argument("--no-parity", action="store_true", help="with --no-cpu: skip the oracle comparison of the timed step too")
-    ap.add_argument("--no-traffic", action="store_true", help="do not run the two rocprofv3 --pmc passes that measure the search launch's HBM traffic")
-    ap.add_argument("--no-others", action="store_true", help="default cfg3 run: do not add the short runs of cfg2 / cfg4 / cfg5 (`other_configs` of the JSON line)")
-    ap.add_argument("--no-vs", action="store_true", help="default cfg3 run: do not add the run of the graph through the VapourSynth filter shell (`vs_shell` of the JSON line)")
+    ap.add_argument("--full", action="store_true", help="after the headline figure, everything else the benchmark measures or checks: the search launch alone, "
+                    "one batch in flight, the CPU baseline and the oracle comparison of the timed step (the shard check at N > 1), the search launch's HBM "
+                    "traffic, and on cfg3 the other configurations and the VapourSynth filter shell.  The --no-* options below leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the output frames of the last step as DIR/*.npy "
+                    "(per-frame sums and a fixed, seeded sample of rows; see dump_outputs)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline (a two-frame parity check of the timed step still runs)")
+    ap.add_argument("--no-parity", action="store_true", help="--full, with --no-cpu: skip the oracle comparison of the timed step too")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: do not run the two rocprofv3 --pmc passes that measure the search launch's HBM traffic")
+    ap.add_argument("--no-others", action="store_true", help="--full cfg3 run: do not add the short runs of cfg2 / cfg4 / cfg5 (`other_configs` of the JSON line)")
+    ap.add_argument("--no-vs", action="store_true", help="--full cfg3 run: do not add the run of the graph through the VapourSynth filter shell (`vs_shell` of the JSON line)")
     ap.add_argument("--vs-shell-leg", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--vs-frames", type=int, default=640)
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--ingest", action="store_true", help="also measure the step with its source frames arriving from / its output frames leaving to pinned host memory "
                     "(secondary metric `ingest_inclusive` of the JSON line; `value` stays the resident-input number)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.vs_shell_leg:
         print(json.dumps(vs_shell_leg(args.vs_frames, int(os.environ.get("MVX_VS_BENCH_THREADS", str(max(8, min(os.cpu_count() or 48, 256))))))))
@@ -789,12 +844,15 @@ def main():
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    last = pipes[(args.steps - 1) % len(pipes)]  # the slot that ran the last timed step
+    if args.dump_outputs:
+        dump_outputs(torch, last, args.dump_outputs, prefix="rank%d_" % rank if world > 1 else "", budget=(48 << 20) // world)
 
     rc = 0
     shard = None
-    if dist is not None and not fpsconv and not args.no_parity:  # every rank takes part (control-plane gather, after the timed region)
+    if args.full and dist is not None and not fpsconv and not args.no_parity:  # every rank takes part (control-plane gather, after the timed region)
         try:
-            shard = shard_check(mv, torch, dist, cfg, pipes[(args.steps - 1) % len(pipes)] if args.steps else pipe, plan, rank, world, max(1, min((os.cpu_count() or 8) // world, 16)))
+            shard = shard_check(mv, torch, dist, cfg, last, plan, rank, world, max(1, min((os.cpu_count() or 8) // world, 16)))
         except Exception as e:
             shard = {"error": "%s: %s" % (type(e).__name__, e)} if rank == 0 else None
     if rank == 0:
@@ -840,9 +898,19 @@ def main():
                          # the search is a serial chain per (frame, direction) -- its own yardstick is block steps per second
                          "blocks_per_chain": nblk, "chain_steps_per_s": chains * nblk / (avg_launch_ms * 1e-3)},
         }
+        if args.ingest and world == 1 and not fpsconv:
+            sps, up_b, down_b = ingest_run(torch, pipe, max(2, min(args.steps, 4)), 1)
+            out["ingest_inclusive"] = {"value": units / sps, "unit": "fps", "ms_per_step": sps * 1e3, "h2d_bytes_per_step": up_b, "d2h_bytes_per_step": down_b,
+                                       "how": "source frames from pinned host memory (double-buffered on the device), output frames to pinned host memory, one copy stream, overlapped with compute"}
+        if not args.full:
+            out["roofline"]["traffic_source"] = "not measured (--full measures it)"
+            print(json.dumps(out))
+            if dist is not None:
+                dist.destroy_process_group()
+            return
         if len(pipes) > 1 and not fpsconv:
             # the launches of the timed steps ran beside the other slot's Super / Degrain kernels; the same launch with the GPU to itself (same clip, same result):
-            alone_ms = pipes[(args.steps - 1) % len(pipes)].search_alone()
+            alone_ms = last.search_alone()
             alone_gbs = bytes_chain * chains / (alone_ms * 1e-3) / 1e9
             out["roofline"]["launch_alone"] = {
                 "avg_launch_ms": alone_ms, "achieved": alone_gbs, "frac": alone_gbs / HBM_PEAK_GBS,
@@ -859,15 +927,11 @@ def main():
             d1 = (time.perf_counter() - t1) / 3
             out["one_batch_in_flight"] = {"value": world * units / d1, "unit": "fps", "ms_per_step": d1 * 1e3, "steps": 3,
                                           "note": "--slots 1 equivalent, measured after the timed region: comparable with the headline of rounds 1-4"}
-        if args.ingest and world == 1 and not fpsconv:
-            sps, up_b, down_b = ingest_run(torch, pipe, max(2, min(args.steps, 4)), 1)
-            out["ingest_inclusive"] = {"value": units / sps, "unit": "fps", "ms_per_step": sps * 1e3, "h2d_bytes_per_step": up_b, "d2h_bytes_per_step": down_b,
-                                       "how": "source frames from pinned host memory (double-buffered on the device), output frames to pinned host memory, one copy stream, overlapped with compute"}
         if world == 1 and not (args.no_cpu and args.no_parity):
             # the CPU leg doubles as the parity check of the timed step: the oracle runs on frames of the SAME clip
             th = args.cpu_threads or min(os.cpu_count() or 1, 64)   # min(host cores, 64)
             F = (8 * th if fpsconv else th) if not args.no_cpu else 2
-            base, parity = (oracle_leg_fps if fpsconv else oracle_leg)(mv, torch, cfg, pipes[(args.steps - 1) % len(pipes)] if args.steps else pipe, th, F)
+            base, parity = (oracle_leg_fps if fpsconv else oracle_leg)(mv, torch, cfg, last, th, F)
             if not args.no_cpu:
                 out["cpu_baseline"] = base
             out["parity_check"] = parity

@@ -31,10 +31,10 @@ while [ $# -gt 0 ]; do
     smoke)
       timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee $out/smoke_$TAG.txt ;;
     bench)
-      timeout 900 python bench.py $BENCH_ARGS > $out/bench_$TAG.json 2> $out/bench_$TAG.err || tail -5 $out/bench_$TAG.err
+      timeout 900 python bench.py --full $BENCH_ARGS > $out/bench_$TAG.json 2> $out/bench_$TAG.err || tail -5 $out/bench_$TAG.err
       cat $out/bench_$TAG.json | line default; head -c 3000 $out/bench_$TAG.json ;;
     configs)
-      for c in cfg5 cfg2 cfg4 cfg1; do timeout 400 python bench.py --no-cpu --no-traffic --steps 2 --warmup 1 --config $c 2>&1 | tail -1 | line $c; done 2>&1 | tee $out/configs_$TAG.txt ;;
+      for c in cfg5 cfg2 cfg4 cfg1; do timeout 400 python bench.py --full --no-cpu --no-traffic --steps 2 --warmup 1 --config $c 2>&1 | tail -1 | line $c; done 2>&1 | tee $out/configs_$TAG.txt ;;
     stats)
       (cd /tmp && rm -rf /tmp/kt && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -o kt -- python $root/bench.py --no-cpu --no-parity --no-traffic $BENCH_ARGS > /tmp/kt.log 2>&1)
       f=$(find /tmp/kt -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp $f $out/${TAG}_kernel_stats.csv && head -12 $out/${TAG}_kernel_stats.csv || tail -5 /tmp/kt.log ;;
@@ -53,7 +53,7 @@ while [ $# -gt 0 ]; do
       : > $out/ab_$TAG.txt
       while [ $# -gt 0 ] && [ -f "$1" ]; do
         lib=$1; shift
-        MVX_LIB=$PWD/$lib timeout 600 python bench.py --no-cpu --no-traffic $BENCH_ARGS 2>&1 | tail -1 | line $lib | tee -a $out/ab_$TAG.txt
+        MVX_LIB=$PWD/$lib timeout 600 python bench.py --full --no-cpu --no-traffic $BENCH_ARGS 2>&1 | tail -1 | line $lib | tee -a $out/ab_$TAG.txt
       done ;;
     vs)
       timeout 900 python tools/vs_4k_run.py $VS_ARGS 2>&1 | tail -25 | tee $out/${TAG}_vs_shell.txt ;;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Developer tool (CPU only): how the default motion search behaves on a clip, counted by the oracle built with -DMVO_STATS (a private
-copy of the library under /tmp; the test library carries no counters).  Per level of the hierarchy: which of the seven predictor
+copy of the library in a temporary directory; the test library carries no counters).  Per level of the hierarchy: which of the seven predictor
 candidates a block's predictor phase ends on, whether that vector equals the hierarchical predictor / the median / the left neighbour,
 how many DIFFERENT vectors the seven candidates are, how often a point of the first hexagon wins, how often the bad-block rescue runs.
 These are the probabilities a kernel that wants to overlap the passes of a block by speculation needs.
@@ -10,6 +10,7 @@ import ctypes as C
 import os
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
@@ -18,7 +19,8 @@ sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")]
 import mvoracle as mo  # noqa: E402
 import pipeline as pl  # noqa: E402
 
-so = os.path.join(os.environ.get("TMPDIR", "/tmp"), "libmvoracle_stats.so")
+_tmp = tempfile.TemporaryDirectory(prefix="mvo_stats_")  # (private to this process: a fixed name in a shared temporary directory may belong to another user)
+so = os.path.join(_tmp.name, "libmvoracle_stats.so")
 subprocess.check_call(["gcc", "-std=gnu99", "-O2", "-mavx2", "-fPIC", "-ffp-contract=off", "-fno-strict-aliasing", "-DMVO_STATS", "-shared", "-o", so]
                       + [os.path.join(ROOT, "oracle", f) for f in ("mvo_super.c", "mvo_analyse.c", "mvo_degrain.c", "mvo_blockfps.c")] + ["-lm"])
 mo.build = lambda force=False: so  # this process counts

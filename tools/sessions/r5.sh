@@ -17,10 +17,10 @@ r5_col() {
 if grep -q "failed\|error" $out/r5_col_tests.txt; then echo "not green: no timing"; exit 1; fi
     {
 for u in 1 0; do
-      MVX_SPEC_COL=$u timeout 300 python bench.py --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 | line "cfg3 column passes $u"
+      MVX_SPEC_COL=$u timeout 300 python bench.py --full --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 | line "cfg3 column passes $u"
     done
-    MVX_SPEC_COL=1 timeout 300 python bench.py --no-cpu --no-traffic --no-others --steps 2 --warmup 1 --batch 64 2>&1 | tail -1 | line "cfg3 batch 64 (team) column passes 1"
-    MVX_SPEC_COL=0 timeout 300 python bench.py --no-cpu --no-traffic --no-others --steps 2 --warmup 1 --batch 64 2>&1 | tail -1 | line "cfg3 batch 64 (team) column passes 0"
+    MVX_SPEC_COL=1 timeout 300 python bench.py --full --no-cpu --no-traffic --no-others --steps 2 --warmup 1 --batch 64 2>&1 | tail -1 | line "cfg3 batch 64 (team) column passes 1"
+    MVX_SPEC_COL=0 timeout 300 python bench.py --full --no-cpu --no-traffic --no-others --steps 2 --warmup 1 --batch 64 2>&1 | tail -1 | line "cfg3 batch 64 (team) column passes 0"
     } 2>&1 | tee $out/r5_column_passes_ab.txt
 }
 
@@ -30,7 +30,7 @@ r5_final_light() {
     timeout 1500 python -m pytest tests -q -m gpu -x 2>&1 | tail -12 | tee $out/r5_tests_gpu_final.txt
     timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $out/r5_smoke.txt
     t0=$(date +%s)
-    timeout 1500 python bench.py --steps 20 --warmup 5 > $out/r5_bench_default.json 2> $out/r5_bench_default.err || tail -5 $out/r5_bench_default.err
+    timeout 1500 python bench.py --full --steps 20 --warmup 5 > $out/r5_bench_default.json 2> $out/r5_bench_default.err || tail -5 $out/r5_bench_default.err
     echo "bench.py --steps 20 --warmup 5 wall: $(( $(date +%s) - t0 )) s"
     tail -1 $out/r5_bench_default.json | cut -c1-300
 }
@@ -41,7 +41,7 @@ r5_final() {
     timeout 1500 python -m pytest tests -q -m gpu -x 2>&1 | tail -12 | tee $out/r5_tests_gpu_final.txt
     timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $out/r5_smoke.txt
     t0=$(date +%s)
-    timeout 1500 python bench.py --steps 20 --warmup 5 > $out/r5_bench_default.json 2> $out/r5_bench_default.err || tail -5 $out/r5_bench_default.err
+    timeout 1500 python bench.py --full --steps 20 --warmup 5 > $out/r5_bench_default.json 2> $out/r5_bench_default.err || tail -5 $out/r5_bench_default.err
     echo "bench.py --steps 20 --warmup 5 wall: $(( $(date +%s) - t0 )) s"
     python - <<'PY'
 import json
@@ -65,7 +65,7 @@ r5_first() {
     # r5 call 1: the whole GPU suite on the commit with the stream-ordering fix, the sharding case 30x in one process, a short bench line
     timeout 1500 python -m pytest tests -q -m gpu 2>&1 | tail -15 | tee $out/r5_tests_gpu_first.txt
     timeout 600 python tools/stress_sharding.py 30 2>&1 | tail -8 | tee $out/r5_sharding_stress_30x.txt
-    timeout 600 python bench.py --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 > $out/r5_bench_first.json
+    timeout 600 python bench.py --full --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 > $out/r5_bench_first.json
     python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r5_bench_first.json'))
@@ -77,7 +77,7 @@ r5_full() {
     # r5: the whole GPU suite (team form as the library's choice for small launches), the driver's bench command (with the vs_shell leg), cfg2 team sweep
     timeout 1500 python -m pytest tests -q -m gpu -x 2>&1 | tail -12 | tee $out/r5_tests_gpu_team_default.txt
     t0=$(date +%s)
-    timeout 1500 python bench.py > $out/r5_bench_default.json 2> $out/r5_bench_default.err || tail -5 $out/r5_bench_default.err
+    timeout 1500 python bench.py --full > $out/r5_bench_default.json 2> $out/r5_bench_default.err || tail -5 $out/r5_bench_default.err
     echo "bench.py wall: $(( $(date +%s) - t0 )) s"
     cat $out/r5_bench_default.json | line default
     python - <<'PY'
@@ -88,7 +88,7 @@ print(json.dumps(d.get('other_configs'))[:1500])
 PY
     {
 for bt in "1024 0" "512 0" "512 2" "256 0" "256 2" "256 4" "64 0" "64 4" "64 8"; do set -- $bt
-      MVX_TEAM=$2 timeout 300 python bench.py --config cfg2 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 --batch $1 2>&1 | tail -1 | line "cfg2 batch $1 team $2"
+      MVX_TEAM=$2 timeout 300 python bench.py --full --config cfg2 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 --batch $1 2>&1 | tail -1 | line "cfg2 batch $1 team $2"
     done
     } 2>&1 | tee $out/r5_team_cfg2_sweep.txt
 }
@@ -97,7 +97,7 @@ r5_full2() {
     # r5: the whole GPU suite + the driver's bench command on the current tree
     timeout 1500 python -m pytest tests -q -m gpu -x 2>&1 | tail -12 | tee $out/r5_tests_gpu.txt
     t0=$(date +%s)
-    timeout 1500 python bench.py > $out/r5_bench_default.json 2> $out/r5_bench_default.err || tail -5 $out/r5_bench_default.err
+    timeout 1500 python bench.py --full > $out/r5_bench_default.json 2> $out/r5_bench_default.err || tail -5 $out/r5_bench_default.err
     echo "bench.py wall: $(( $(date +%s) - t0 )) s"
     python - <<'PY'
 import json
@@ -114,22 +114,22 @@ r5_hd16() {
     timeout 900 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "8bit_16x16 or speculative or analyse_parity or golden or full_size_parity_cfg2" 2>&1 | tail -8 | tee $out/r5_hd16_tests.txt
 if grep -q "failed\|error" $out/r5_hd16_tests.txt; then echo "not green: no timing"; exit 1; fi
     {
-    timeout 400 python bench.py --config hd16 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16 row passes, barrier every 128 blocks"
-    MVX_CPW_SYNC=0 timeout 400 python bench.py --config hd16 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16 row passes, no barrier"
-    MVX_SPEC=0 timeout 400 python bench.py --config hd16 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16 serial lean kernel"
-    timeout 400 python bench.py --config hd16 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 --batch 1024 2>&1 | tail -1 | line "hd16 batch 1024 (2048 chains) row passes"
-    timeout 400 python bench.py --config hd16 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 --batch 128 2>&1 | tail -1 | line "hd16 batch 128 (teams)"
+    timeout 400 python bench.py --full --config hd16 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16 row passes, barrier every 128 blocks"
+    MVX_CPW_SYNC=0 timeout 400 python bench.py --full --config hd16 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16 row passes, no barrier"
+    MVX_SPEC=0 timeout 400 python bench.py --full --config hd16 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16 serial lean kernel"
+    timeout 400 python bench.py --full --config hd16 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 --batch 1024 2>&1 | tail -1 | line "hd16 batch 1024 (2048 chains) row passes"
+    timeout 400 python bench.py --full --config hd16 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 --batch 128 2>&1 | tail -1 | line "hd16 batch 128 (teams)"
     } 2>&1 | tee $out/r5_hd16_bench.txt
 }
 
 r5_shadow_ab() {
     # r5: re-pricing the shifted luma copy (shadow plane 0) against the row-pass kernel: search + Degrain reading it / not reading it
     {
-    timeout 300 python bench.py --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 | line "cfg3 default (search and Degrain read odd-sample blocks from the shifted luma copy)"
-    MVX_SHADOW_PLANES=2 timeout 300 python bench.py --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 | line "cfg3 search reads the plain luma plane (UV plane kept)"
-    MVX_SHADOW_PLANES=2 MVX_DEGRAIN_SHADOW=0 timeout 300 python bench.py --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 | line "cfg3 search AND Degrain read the plain luma plane"
-    MVX_DEGRAIN_SHADOW=0 timeout 300 python bench.py --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 | line "cfg3 only Degrain reads the plain luma plane"
-    MVX_SHADOW_PLANES=2 timeout 300 python bench.py --config cfg5 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "cfg5 search reads the plain luma plane"
+    timeout 300 python bench.py --full --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 | line "cfg3 default (search and Degrain read odd-sample blocks from the shifted luma copy)"
+    MVX_SHADOW_PLANES=2 timeout 300 python bench.py --full --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 | line "cfg3 search reads the plain luma plane (UV plane kept)"
+    MVX_SHADOW_PLANES=2 MVX_DEGRAIN_SHADOW=0 timeout 300 python bench.py --full --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 | line "cfg3 search AND Degrain read the plain luma plane"
+    MVX_DEGRAIN_SHADOW=0 timeout 300 python bench.py --full --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 | line "cfg3 only Degrain reads the plain luma plane"
+    MVX_SHADOW_PLANES=2 timeout 300 python bench.py --full --config cfg5 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "cfg5 search reads the plain luma plane"
     } 2>&1 | tee $out/r5_shadow_ab.txt
 }
 
@@ -138,12 +138,12 @@ r5_slots() {
     # the current one frees.  (The first form of this chained the search launches by events -- profiles/r5_batches_in_flight_chained_searches.txt, 878 fps; not chaining
     # them is 922: profiles/r5_batches_in_flight_unchained.txt.)
     {
-    timeout 400 python bench.py --no-cpu --no-traffic --no-others --steps 8 --warmup 2 --slots 1 2>&1 | tail -1 | line "cfg3 one batch in flight"
-    timeout 400 python bench.py --no-cpu --no-traffic --no-others --steps 8 --warmup 2 --slots 2 2>&1 | tail -1 | line "cfg3 two batches in flight"
-    timeout 400 python bench.py --no-cpu --no-traffic --no-others --steps 9 --warmup 3 --slots 3 --batch 256 2>&1 | tail -1 | line "cfg3 three batches of 256 in flight"
-    timeout 400 python bench.py --no-cpu --no-traffic --no-others --steps 8 --warmup 4 --slots 4 --batch 170 2>&1 | tail -1 | line "cfg3 four batches of 170 in flight"
-    timeout 400 python bench.py --config cfg2 --no-cpu --no-traffic --no-others --steps 8 --warmup 2 --slots 2 2>&1 | tail -1 | line "cfg2 two batches in flight"
-    timeout 400 python bench.py --config cfg2 --no-cpu --no-traffic --no-others --steps 8 --warmup 2 --slots 1 2>&1 | tail -1 | line "cfg2 one batch in flight"
+    timeout 400 python bench.py --full --no-cpu --no-traffic --no-others --steps 8 --warmup 2 --slots 1 2>&1 | tail -1 | line "cfg3 one batch in flight"
+    timeout 400 python bench.py --full --no-cpu --no-traffic --no-others --steps 8 --warmup 2 --slots 2 2>&1 | tail -1 | line "cfg3 two batches in flight"
+    timeout 400 python bench.py --full --no-cpu --no-traffic --no-others --steps 9 --warmup 3 --slots 3 --batch 256 2>&1 | tail -1 | line "cfg3 three batches of 256 in flight"
+    timeout 400 python bench.py --full --no-cpu --no-traffic --no-others --steps 8 --warmup 4 --slots 4 --batch 170 2>&1 | tail -1 | line "cfg3 four batches of 170 in flight"
+    timeout 400 python bench.py --full --config cfg2 --no-cpu --no-traffic --no-others --steps 8 --warmup 2 --slots 2 2>&1 | tail -1 | line "cfg2 two batches in flight"
+    timeout 400 python bench.py --full --config cfg2 --no-cpu --no-traffic --no-others --steps 8 --warmup 2 --slots 1 2>&1 | tail -1 | line "cfg2 one batch in flight"
     } 2>&1 | tee $out/r5_batches_in_flight.txt
 }
 
@@ -152,8 +152,8 @@ r5_strip32() {
     export MVX_LIB=$PWD/tools/variants/strip32.so
     timeout 900 python -m pytest tests/test_gpu_parity.py -q -m gpu -k "full_size_parity_cfg5 or team_sizes or analyse_parity or properties_cfg5" 2>&1 | tail -15 | tee $out/r5_strip32_tests.txt
     {
-    timeout 600 python bench.py --config cfg5 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "cfg5 row passes (32x32)"
-    MVX_TEAM=0 MVX_LIB= timeout 600 python bench.py --config cfg5 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "cfg5 product build (serial lean kernel)"
+    timeout 600 python bench.py --full --config cfg5 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "cfg5 row passes (32x32)"
+    MVX_TEAM=0 MVX_LIB= timeout 600 python bench.py --full --config cfg5 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "cfg5 product build (serial lean kernel)"
     } 2>&1 | tee $out/r5_strip32_bench.txt
 }
 
@@ -163,10 +163,10 @@ r5_team() {
 if grep -q "failed\|error\|Timeout" $out/r5_team_tests.txt; then echo "team tests not green: no timing"; exit 1; fi
     {
 for t in 0 4 2 8 3; do
-      MVX_TEAM=$t timeout 300 python bench.py --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "cfg3 batch 341 team $t"
+      MVX_TEAM=$t timeout 300 python bench.py --full --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "cfg3 batch 341 team $t"
     done
 for b in 86 22; do for t in 0 4 8; do
-      MVX_TEAM=$t timeout 300 python bench.py --no-cpu --no-traffic --no-others --steps 2 --warmup 1 --batch $b 2>&1 | tail -1 | line "cfg3 batch $b team $t"
+      MVX_TEAM=$t timeout 300 python bench.py --full --no-cpu --no-traffic --no-others --steps 2 --warmup 1 --batch $b 2>&1 | tail -1 | line "cfg3 batch $b team $t"
     done; done
     } 2>&1 | tee $out/r5_team_bench.txt
 }
@@ -179,7 +179,7 @@ r5_team2() {
     timeout 300 python tools/stress_sharding.py 30 2>&1 | tail -3 | tee -a $out/r5_sharding_race_repro.txt
     {
 for bt in "170 0" "170 2" "170 3" "128 0" "128 2" "128 3" "128 4" "43 4" "43 8" "43 0" "341 5" "341 6"; do set -- $bt
-      MVX_TEAM=$2 timeout 300 python bench.py --no-cpu --no-traffic --no-others --steps 2 --warmup 1 --batch $1 2>&1 | tail -1 | line "cfg3 batch $1 team $2"
+      MVX_TEAM=$2 timeout 300 python bench.py --full --no-cpu --no-traffic --no-others --steps 2 --warmup 1 --batch $1 2>&1 | tail -1 | line "cfg3 batch $1 team $2"
     done
     } 2>&1 | tee $out/r5_team_batch_sweep.txt
 for t in 4 0; do
@@ -207,11 +207,11 @@ r5_team_shapes() {
     # r5: the team form for shapes WITHOUT row passes (one block at a time in phase A): small launches of cfg5 (32x32) and of 8-bit 16x16 blocks
     {
 for cb in "cfg5 11" "cfg5 43" "hd16 64" "hd16 256" "hd16 512"; do set -- $cb
-      timeout 400 python bench.py --config $1 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 --batch $2 2>&1 | tail -1 | line "$1 batch $2 library default"
-      for t in 4 8; do MVX_SPEC=5 MVX_TEAM=$t timeout 400 python bench.py --config $1 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 --batch $2 2>&1 | tail -1 | line "$1 batch $2 speculative kernel, teams of $t"; done
+      timeout 400 python bench.py --full --config $1 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 --batch $2 2>&1 | tail -1 | line "$1 batch $2 library default"
+      for t in 4 8; do MVX_SPEC=5 MVX_TEAM=$t timeout 400 python bench.py --full --config $1 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 --batch $2 2>&1 | tail -1 | line "$1 batch $2 speculative kernel, teams of $t"; done
     done
-    timeout 400 python bench.py --config hd16 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16 batch 2048 library default"
-    MVX_SPEC=5 MVX_TEAM=0 timeout 400 python bench.py --config hd16 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16 batch 2048 speculative kernel, one wave per chain"
+    timeout 400 python bench.py --full --config hd16 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16 batch 2048 library default"
+    MVX_SPEC=5 MVX_TEAM=0 timeout 400 python bench.py --full --config hd16 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16 batch 2048 speculative kernel, one wave per chain"
     } 2>&1 | tee $out/r5_team_other_shapes.txt
 }
 
@@ -221,7 +221,7 @@ r5_uni() {
 if grep -q "failed\|error" $out/r5_uni_tests.txt; then echo "not green: no timing"; exit 1; fi
     {
 for c in cfg3 cfg2 cfg4; do for u in 1 0; do
-      MVX_SPEC_UNI=$u timeout 300 python bench.py --config $c --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 | line "$c uniform windows $u"
+      MVX_SPEC_UNI=$u timeout 300 python bench.py --full --config $c --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 | line "$c uniform windows $u"
     done; done
     } 2>&1 | tee $out/r5_uniform_windows_ab.txt
 }
@@ -245,10 +245,10 @@ r5_side16() {
     timeout 900 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "speculative or analyse_parity or golden or team" 2>&1 | tail -8 | tee $out/r5_side16_tests.txt
     if grep -q "failed\|error" $out/r5_side16_tests.txt; then echo "not green: no timing"; return 1; fi
     {
-    timeout 400 python bench.py --config hd16s --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16s (1080p8 16x16 overlap 0) row passes"
-    MVX_SPEC=0 timeout 400 python bench.py --config hd16s --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16s serial lean kernel"
-    timeout 400 python bench.py --no-cpu --no-traffic --no-others --steps 3 --warmup 1 --slots 1 2>&1 | tail -1 | line "cfg3 one batch in flight (must not have moved: 345 ms)"
-    timeout 400 python bench.py --config hd16 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16 (must not have moved: 144 ms)"
+    timeout 400 python bench.py --full --config hd16s --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16s (1080p8 16x16 overlap 0) row passes"
+    MVX_SPEC=0 timeout 400 python bench.py --full --config hd16s --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16s serial lean kernel"
+    timeout 400 python bench.py --full --no-cpu --no-traffic --no-others --steps 3 --warmup 1 --slots 1 2>&1 | tail -1 | line "cfg3 one batch in flight (must not have moved: 345 ms)"
+    timeout 400 python bench.py --full --config hd16 --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16 (must not have moved: 144 ms)"
     } 2>&1 | tee $out/r5_side16_bench.txt
 }
 
@@ -257,9 +257,9 @@ r5_lumaonly() {
     timeout 900 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "speculative or analyse_parity or golden or team" 2>&1 | tail -8 | tee $out/r5_lumaonly_tests.txt
     if grep -q "failed\|error" $out/r5_lumaonly_tests.txt; then echo "not green: no timing"; return 1; fi
     {
-    timeout 400 python bench.py --config hd16l --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16l (1080p8 16x16 overlap 8, chroma=0) row passes"
-    MVX_SPEC=0 timeout 400 python bench.py --config hd16l --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16l serial lean kernel"
-    timeout 400 python bench.py --no-cpu --no-traffic --no-others --steps 3 --warmup 1 --slots 1 2>&1 | tail -1 | line "cfg3 one batch in flight (must not have moved: 345 ms)"
+    timeout 400 python bench.py --full --config hd16l --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16l (1080p8 16x16 overlap 8, chroma=0) row passes"
+    MVX_SPEC=0 timeout 400 python bench.py --full --config hd16l --no-cpu --no-traffic --no-others --steps 2 --warmup 1 2>&1 | tail -1 | line "hd16l serial lean kernel"
+    timeout 400 python bench.py --full --no-cpu --no-traffic --no-others --steps 3 --warmup 1 --slots 1 2>&1 | tail -1 | line "cfg3 one batch in flight (must not have moved: 345 ms)"
     } 2>&1 | tee $out/r5_lumaonly_bench.txt
 }
 
@@ -268,9 +268,9 @@ r5_degrain_side() {
     timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_vs_shim.py -x -q -m gpu -k "degrain or golden or full_size or device" 2>&1 | tail -8 | tee $out/r5_degrain_side_tests.txt
     if grep -q "failed\|error" $out/r5_degrain_side_tests.txt; then echo "not green: no timing"; return 1; fi
     {
-    timeout 400 python bench.py --config hd16s --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 | line "hd16s (was 135.0 ms/step, Degrain gather 42 ms)"
-    timeout 400 python bench.py --config cfg1 --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 | line "cfg1 (r4: 66 700 fps)"
-    timeout 400 python bench.py --config cfg4 --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 | line "cfg4 (unchanged path)"
+    timeout 400 python bench.py --full --config hd16s --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 | line "hd16s (was 135.0 ms/step, Degrain gather 42 ms)"
+    timeout 400 python bench.py --full --config cfg1 --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 | line "cfg1 (r4: 66 700 fps)"
+    timeout 400 python bench.py --full --config cfg4 --no-cpu --no-traffic --no-others --steps 3 --warmup 1 2>&1 | tail -1 | line "cfg4 (unchanged path)"
     } 2>&1 | tee $out/r5_degrain_side_bench.txt
 }
 

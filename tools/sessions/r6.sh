@@ -14,7 +14,7 @@ r6_formats() {
     # r6 first session: the new 4:4:4 / 4:2:2 / Gray cases and the overlap-0 Degrain cases, then the starting point of the round (unchanged library)
     timeout 900 python -m pytest tests/test_gpu_formats.py -q -m gpu 2>&1 | tail -40 | tee $out/r6_formats_tests.txt
     timeout 600 python -m pytest tests/test_gpu_parity.py -q -m gpu -k "degrain_parity" 2>&1 | tail -8 | tee $out/r6_degrain_side_tests.txt
-    timeout 600 python bench.py --no-cpu --no-traffic --no-others --no-vs --steps 5 --warmup 2 2>&1 | tail -1 | tee $out/r6_start_bench.json | line "cfg3 start of r6"
+    timeout 600 python bench.py --full --no-cpu --no-traffic --no-others --no-vs --steps 5 --warmup 2 2>&1 | tail -1 | tee $out/r6_start_bench.json | line "cfg3 start of r6"
 }
 
 r6_ab() {
@@ -23,7 +23,7 @@ r6_ab() {
     for lib in "$@"; do
         if [ "$lib" != default ]; then export MVX_LIB=$PWD/$lib; else unset MVX_LIB; fi
         if [ -n "$k" ]; then timeout 900 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "$k" 2>&1 | tail -3 | sed "s|^|$lib: |"; fi
-        timeout 600 python bench.py --no-cpu --no-others --no-vs --slots 1 --steps 3 --warmup 1 $BENCH_ARGS 2>/dev/null | tail -1 > $out/r6_ab_$(basename $lib .so).json
+        timeout 600 python bench.py --full --no-cpu --no-others --no-vs --slots 1 --steps 3 --warmup 1 $BENCH_ARGS 2>/dev/null | tail -1 > $out/r6_ab_$(basename $lib .so).json
         python - $out/r6_ab_$(basename $lib .so).json $lib <<'PY'
 import sys, json
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r = d['roofline']
@@ -53,7 +53,7 @@ r6_shadow8() {
     MVX_SHADOW8=1 timeout 900 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "speculative_kernel_8bit or analyse_parity or degrain_parity or golden or full_size_parity_cfg2" 2>&1 | tail -4
     for c in cfg2 cfg4 hd16; do
         for s8 in 0 1; do
-            MVX_SHADOW8=$s8 timeout 600 python bench.py --config $c --no-cpu --no-traffic --slots 1 --steps 3 --warmup 1 2>/dev/null | tail -1 | line "$c shadow8=$s8"
+            MVX_SHADOW8=$s8 timeout 600 python bench.py --full --config $c --no-cpu --no-traffic --slots 1 --steps 3 --warmup 1 2>/dev/null | tail -1 | line "$c shadow8=$s8"
         done
     done 2>&1 | tee $out/r6_shadow8_ab.txt
 }
@@ -68,7 +68,7 @@ r6_k34() {
     # chains per SIMD of the 8-bit row-pass builds: 2 (256 registers, the default), 3 (168), 4 (128)
     for c in cfg2 cfg4 hd16; do
         for k in 0 3 4; do
-            MVX_FAST_K=$k timeout 600 python bench.py --config $c --no-cpu --no-traffic --slots 1 --steps 3 --warmup 1 2>/dev/null | tail -1 | line "$c fast_k=$k"
+            MVX_FAST_K=$k timeout 600 python bench.py --full --config $c --no-cpu --no-traffic --slots 1 --steps 3 --warmup 1 2>/dev/null | tail -1 | line "$c fast_k=$k"
         done
     done 2>&1 | tee $out/r6_8bit_chains_per_simd.txt
 }
@@ -76,7 +76,7 @@ r6_k34() {
 r6_configs() {
     # every bench configuration, one batch in flight, 3 timed steps each (TAG names the state)
     for c in cfg3 cfg2 cfg4 hd16 hd16s cfg1 cfg5; do
-        timeout 600 python bench.py --config $c --no-cpu --no-traffic --no-others --no-vs --slots 1 --steps 3 --warmup 1 2>/dev/null | tail -1 | line "$c"
+        timeout 600 python bench.py --full --config $c --no-cpu --no-traffic --no-others --no-vs --slots 1 --steps 3 --warmup 1 2>/dev/null | tail -1 | line "$c"
     done 2>&1 | tee $out/r6_configs_${TAG:-last}.txt
 }
 
@@ -86,7 +86,7 @@ r6_final() {
     timeout 1500 python -m pytest tests -q -m gpu -x 2>&1 | tail -12 | tee $out/r6_tests_gpu_final.txt
     timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $out/r6_smoke.txt
     t0=$(date +%s)
-    timeout 1500 python bench.py --steps 20 --warmup 5 > $out/r6_bench_default.json 2> $out/r6_bench_default.err || tail -5 $out/r6_bench_default.err
+    timeout 1500 python bench.py --full --steps 20 --warmup 5 > $out/r6_bench_default.json 2> $out/r6_bench_default.err || tail -5 $out/r6_bench_default.err
     echo "bench.py --steps 20 --warmup 5 wall: $(( $(date +%s) - t0 )) s"
     python - <<'PY'
 import json
@@ -163,12 +163,12 @@ r6_halfslots() {
     # launches of HALF the wave slots (batch 512 = 1024 chains = one wave per SIMD, one wave per chain: MVX_TEAM=0) from three or four batches in flight -- two searches
     # resident, the other batches' Super / Degrain kernels in the registers a finished launch frees
     for c in cfg2 cfg4 hd16; do
-        timeout 600 python bench.py --config $c --no-cpu --no-traffic --no-others --no-vs --steps 8 --warmup 2 2>/dev/null | grep '^{' | tail -1 | line "$c default (2 x 2048)"
+        timeout 600 python bench.py --full --config $c --no-cpu --no-traffic --no-others --no-vs --steps 8 --warmup 2 2>/dev/null | grep '^{' | tail -1 | line "$c default (2 x 2048)"
         for v in "2 512" "3 512" "4 512" "6 512" "3 1024"; do  # (MVX_FAST_K=2: the two-waves-per-SIMD build -- the one-wave build takes more than 256 registers, two launches could not share a SIMD)
             set -- $v
-            MVX_TEAM=0 MVX_FAST_K=2 timeout 600 python bench.py --config $c --slots $1 --batch $2 --no-cpu --no-traffic --no-others --no-vs --steps $(( 16 * 2048 / $2 / $1 )) --warmup $1 2>/dev/null | grep '^{' | tail -1 | line "$c slots $1 batch $2 team 0"
+            MVX_TEAM=0 MVX_FAST_K=2 timeout 600 python bench.py --full --config $c --slots $1 --batch $2 --no-cpu --no-traffic --no-others --no-vs --steps $(( 16 * 2048 / $2 / $1 )) --warmup $1 2>/dev/null | grep '^{' | tail -1 | line "$c slots $1 batch $2 team 0"
         done
-        MVX_FAST_K=2 timeout 600 python bench.py --config $c --slots 4 --batch 512 --no-cpu --no-traffic --no-others --no-vs --steps 16 --warmup 4 2>/dev/null | grep '^{' | tail -1 | line "$c slots 4 batch 512 library team choice"
+        MVX_FAST_K=2 timeout 600 python bench.py --full --config $c --slots 4 --batch 512 --no-cpu --no-traffic --no-others --no-vs --steps 16 --warmup 4 2>/dev/null | grep '^{' | tail -1 | line "$c slots 4 batch 512 library team choice"
     done 2>&1 | tee $out/r6_half_occupancy_launches.txt
 }
 
@@ -196,7 +196,7 @@ r6_cfg5k3() {
     # cfg5 (8K16, 32x32 blocks, serial lean kernel): three chains per SIMD need a batch of 252 frames, which only fits without the shifted luma copies (MVX_SHADOW=0: 0.52 instead of 1.05 GB per super frame)
     for v in "1 168" "0 168" "0 252"; do
         set -- $v
-        MVX_SHADOW=$1 timeout 900 python bench.py --config cfg5 --batch $2 --no-cpu --no-traffic --no-others --no-vs --slots 1 --steps 2 --warmup 1 2>&1 | grep '^{' | tail -1 | line "cfg5 shadow=$1 batch $2"
+        MVX_SHADOW=$1 timeout 900 python bench.py --full --config cfg5 --batch $2 --no-cpu --no-traffic --no-others --no-vs --slots 1 --steps 2 --warmup 1 2>&1 | grep '^{' | tail -1 | line "cfg5 shadow=$1 batch $2"
     done 2>&1 | tee $out/r6_cfg5_three_per_simd.txt
 }
 
@@ -278,9 +278,9 @@ d=json.loads(sys.stdin.read().strip().splitlines()[-1]); l=d.get('lazy_super',{}
 print('$1: graph', d.get('graph_construction_s'), 'requests', d.get('request_phase_s'), 'all inclusive', round(d.get('fps_all_inclusive',0),1), '| lazy', round(l.get('fps_all_inclusive',0),1))"; }
     {
     leg "alone (fresh box)"
-    timeout 600 python bench.py --config hd16 --no-cpu --no-traffic --no-others --no-vs --steps 8 --warmup 2 > /dev/null 2>&1; leg "right after a hd16 child run"
-    timeout 600 python bench.py --config hd16 --no-cpu --no-traffic --no-others --no-vs --steps 8 --warmup 2 > /dev/null 2>&1; MVX_VS_SETTLE_S=20 leg "after a hd16 child run, 20 s pause before each host"
-    timeout 600 python bench.py --no-cpu --no-traffic --no-others --no-vs --steps 40 --warmup 5 > /dev/null 2>&1; leg "right after 45 cfg3 steps (hot GPU)"
+    timeout 600 python bench.py --full --config hd16 --no-cpu --no-traffic --no-others --no-vs --steps 8 --warmup 2 > /dev/null 2>&1; leg "right after a hd16 child run"
+    timeout 600 python bench.py --full --config hd16 --no-cpu --no-traffic --no-others --no-vs --steps 8 --warmup 2 > /dev/null 2>&1; MVX_VS_SETTLE_S=20 leg "after a hd16 child run, 20 s pause before each host"
+    timeout 600 python bench.py --full --no-cpu --no-traffic --no-others --no-vs --steps 40 --warmup 5 > /dev/null 2>&1; leg "right after 45 cfg3 steps (hot GPU)"
     leg "alone again"
     } 2>&1 | tee $out/r6_vs_leg_after_other_runs.txt
 }
@@ -288,7 +288,7 @@ print('$1: graph', d.get('graph_construction_s'), 'requests', d.get('request_pha
 r6_vs_order() {
     # (the MVX_BENCH_VS_FIRST switch was removed from bench.py after this run) the shell leg inside the full bench command: after the other configurations' child runs (the default order) against before them
     for v in "" 1; do
-        MVX_BENCH_VS_FIRST=$v timeout 1200 python bench.py --steps 5 --warmup 2 2>/dev/null | grep '^{' | tail -1 | python -c "import sys,json
+        MVX_BENCH_VS_FIRST=$v timeout 1200 python bench.py --full --steps 5 --warmup 2 2>/dev/null | grep '^{' | tail -1 | python -c "import sys,json
 d=json.loads(sys.stdin.read()); v=d.get('vs_shell',{}); l=v.get('lazy_super',{})
 print('vs first=${v:-0}:', round(d['value'],1), 'fps | shell graph', v.get('graph_construction_s'), 'requests', v.get('request_phase_s'), 'all inclusive', round(v.get('fps_all_inclusive',0),1), '| lazy', round(l.get('fps_all_inclusive',0),1), '| others', {k:round(x.get('fps',0),1) for k,x in d.get('other_configs',{}).items()})"
     done 2>&1 | tee $out/r6_vs_leg_order_in_bench.txt
@@ -297,7 +297,7 @@ print('vs first=${v:-0}:', round(d['value'],1), 'fps | shell graph', v.get('grap
 r6_vs_trim() {
     # (the malloc_trim / MVX_BENCH_NO_TRIM code was removed from bench.py after this run) the shell leg inside the full bench command with the parent's freed host memory returned to the kernel first (malloc_trim) against without
     for v in "" 1; do
-        MVX_BENCH_NO_TRIM=$v timeout 1200 python bench.py --steps 5 --warmup 2 2>/dev/null | grep '^{' | tail -1 | python -c "import sys,json
+        MVX_BENCH_NO_TRIM=$v timeout 1200 python bench.py --full --steps 5 --warmup 2 2>/dev/null | grep '^{' | tail -1 | python -c "import sys,json
 d=json.loads(sys.stdin.read()); v=d.get('vs_shell',{}); l=v.get('lazy_super',{})
 print('no trim=${v:-0}:', round(d['value'],1), 'fps | shell graph', v.get('graph_construction_s'), 'requests', v.get('request_phase_s'), 'all inclusive', round(v.get('fps_all_inclusive',0),1), '| lazy', round(l.get('fps_all_inclusive',0),1))"
         grep -E "MemFree|MemAvailable|^Cached" /proc/meminfo | tr '\n' ' '; echo; numactl --hardware 2>/dev/null | grep -E "available|free" | tr '\n' ' '; echo
