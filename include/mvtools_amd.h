@@ -299,9 +299,12 @@ void mvx_scale_thscd(int64_t *thscd1, int32_t *thscd2, const mvx_analysis_data *
  * GroupOfPlanes.c:127-148 array layout) */
 int mvx_vectors_size(const mvx_analysis_data *ad);
 
-/* ---- test / measurement hook: selects among kernel variants that compute identical results (e.g. "general" = 1 keeps the
- * default search out of its specialised kernel so that the parity suite can run both).  The library never reads the
- * environment; a production host never needs this call. */
+/* ---- test hook: selects among kernel variants that compute identical results, so that the parity suite can run its cases
+ * through each of them.  Options: "general" = 1 keeps the default search out of its lean and speculative kernels; "cpw1" = 1
+ * runs the general kernels one chain per workgroup; "spec" picks the default search's kernel (0 the lean serial one, 1 the
+ * library's choice, 2 speculative with every block live, 3 speculative without runs, 5 speculative wherever it can run);
+ * "team" = waves per chain of the speculative kernel's team form (0 never, 2..8 always, -1 the library's choice).  The
+ * library never reads the environment; a production host never needs this call. */
 int mvx_debug_option(const char *name, int value);
 /* the last search launch of this process: out[0] = chains per SIMD of the default-search kernel (0: the general kernel ran), out[1] = chains
  * per workgroup (team form: waves per chain), out[2] = barrier interval in blocks, out[3] = job-table entries, out[4] = which default-search kernel:

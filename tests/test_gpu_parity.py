@@ -184,7 +184,7 @@ def dbg(mv):
         used.append(name)
     yield set_
     for name in used:
-        mv.debug_option(name, -1 if name in ("cpw_sync", "lds_min", "team") else 1 if name == "spec" else 0)
+        mv.debug_option(name, -1 if name == "team" else 1 if name == "spec" else 0)
 
 
 ANALYSE_CASES = [

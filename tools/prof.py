@@ -1,5 +1,5 @@
 """developer tool: per-phase cycle counters of one chain of the search kernel (library built with MVX_PROFILE=1).
-usage: MVX_ABLATE=$((chain<<8)) python tools/prof.py [cfg] [batch]"""
+usage: python tools/prof.py [cfg] [batch]     (the counters are those of chain 0)"""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -26,16 +26,3 @@ ox, oy, osad = pl.blob_vectors(ob, oan.ad, lv); gx, gy, gsad = pl.blob_vectors(g
 for r in range(ox.shape[0]):
     print("row", r, "oracle", [(int(ox[r, c]), int(oy[r, c]), int(osad[r, c])) for c in range(50, ox.shape[1])])
     print("row", r, "gpu   ", [(int(gx[r, c]), int(gy[r, c]), int(gsad[r, c])) for c in range(50, ox.shape[1])])
-
-import ctypes as C
-if hasattr(mv.lib(), "mvx_debug_specdbg"):
-    buf = (C.c_int * (4 * 64 * 12))()
-    # (the dump holds whichever chain wrote last: run the single forward job again alone)
-    gan.run([(gsf[1], gsf[2])]); import torch; torch.cuda.synchronize()
-    mv.lib().mvx_debug_specdbg(buf)
-    a = np.array(buf[:]).reshape(4, 64, 12)
-    def up(v): return (int(np.int16(v & 0xffff)), int(v >> 16))
-    for r in range(2):
-        for c in range(50, 61):
-            o = a[r, c]
-            print("row", r + 1, "col", c, "U", up(o[0]), "Ah", up(o[1]), "G", up(o[2]), "H", up(o[3]), "W", up(o[4]), "best", o[5], "tots U/Ah/Z/G/H", o[6:11].tolist(), "lam", o[11])

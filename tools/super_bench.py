@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""mv.Super alone on resident frames: milliseconds per frame batch and HBM bytes/s by variant (sharp, shadow planes, rows kernels).
+"""mv.Super alone on resident frames: milliseconds per frame batch and HBM bytes/s by variant (sharp, shadow planes).
     python tools/super_bench.py [width height bits frames]"""
 import os
 import sys
@@ -20,8 +20,7 @@ for f in frames:
 src_bytes = (w * h + 2 * (w // 2) * (h // 2)) * bps
 
 
-def run(label, rows_off=0, **kw):
-    mv.debug_option("super_rows_off", rows_off)
+def run(label, **kw):
     sup = mv.Super(w, h, bits, **kw)
     out = sup.alloc(n)
     sup.build(frames, out=out)
@@ -39,12 +38,9 @@ def run(label, rows_off=0, **kw):
     del out
 
 
-run("sharp 2, shadows, rows kernels")
-run("sharp 2, shadows, tile kernels", rows_off=1)
-run("sharp 2, no shadows, rows", shadow=False)
-run("sharp 2, no shadows, tile", rows_off=1, shadow=False)
-run("sharp 0, shadows, rows", sharp=0)
-run("sharp 0, no shadows, rows", sharp=0, shadow=False)
-run("sharp 1, shadows, rows", sharp=1)
+run("sharp 2, shadows")
+run("sharp 2, no shadows", shadow=False)
+run("sharp 0, shadows", sharp=0)
+run("sharp 0, no shadows", sharp=0, shadow=False)
+run("sharp 1, shadows", sharp=1)
 run("pel 1, shadows", pel=1)
-mv.debug_option("super_rows_off", 0)

@@ -16,8 +16,6 @@ SOURCES = ["mvx_api.hip", "mvx_super.hip", "mvx_analyse.hip", "mvx_analyse_any.h
 # not be fused into FMAs; no fast-math anywhere.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-inline-asm",
          "-Wno-unused-function", "-Wno-unused-variable"]
-if os.environ.get("MVX_NT_REF"):  # developer-only experiment: non-temporal reference loads
-    FLAGS.append("-DMVX_NT_REF")
 if os.environ.get("MVX_DEFS"):  # developer-only: extra -D switches for A/B builds, e.g. MVX_DEFS="MVX_NO_EARLY"
     FLAGS += ["-D" + d for d in os.environ["MVX_DEFS"].split()]
 if os.environ.get("MVX_PROFILE"):  # developer-only: per-phase cycle counters inside the search kernel

@@ -21,38 +21,18 @@ void mvx_set_error(const char *fmt, ...) {
 }
 extern "C" __attribute__((visibility("default"))) const char *mvx_last_error(void) { return g_err; }
 
-// ---- developer / test options.  The library never reads the environment: kernel-variant choices that exist for A/B
-// measurements and for running the parity suite through every kernel are set through ONE entry point, mvx_debug_option
-// (the Python test binding forwards MVX_* environment variables to it; the VapourSynth shell never calls it).  None of them
-// changes results, except "ablate", which only exists in MVX_LAB builds.
+// ---- test options.  The library never reads the environment: the kernel-variant choices that the parity suite needs to run
+// its cases through every kernel are set through ONE entry point, mvx_debug_option (the Python test binding forwards MVX_*
+// environment variables to it; the VapourSynth shell never calls it).  None of them changes results.
 struct MvxDebug {
     int general = 0;   // 1: never use the lean kernel of the default search (mvx_analyse_fast.h)
-    int fast_wpe = 0;  // > 0: chains per SIMD the lean kernel is launched at (when such a build exists)
     int cpw1 = 0;      // one chain per workgroup (general kernels)
-    int no_wpe2 = 0, no_wpe3 = 0, wpe3_u16 = 0;
-    int fast_cpw = 0;  // lean kernel: chains per workgroup (<= 4 * chains per SIMD)
-    int fast_lds_min = 0; // lean kernel: LDS floor per workgroup in bytes (fewer workgroups per CU: a host that runs other kernels beside long search launches keeps registers free for them)
-    int fast_k = 0;    // lean kernel: build for exactly that many chains per SIMD whatever the launch carries (several launches sharing the GPU)
-    int fast_flags = -1; // lean kernel: MVX_FAST_* bits, -1 = default
-    int pad_runs = -1;   // lean kernel: 1 = pad the job table so that the chains of one reference frame never straddle two workgroups
-    int shadow_planes = 3; // 1 = luma only, 2 = chroma only uses the shadow copies
-    int degrain_xcd = -1;  // Degrain cell kernels: XCD-contiguous tile order (1 / 0), -1 = default
-    int degrain_shadow = 1; // Degrain: 0 = never read the shifted luma copies (takes effect at mvx_degrain_set_ref_shadow)
-    int cpw_sync = -1; // barrier interval inside a workgroup (power of two, 0 = none)
-    int lds_min = -1;  // LDS floor of the one-chain launches
     int spec = 1;      // default search: 1 = the speculative kernel (mvx_analyse_spec.h), 0 = the lean serial kernel (mvx_analyse_fast.h), 2 = the speculative kernel's code with speculation off (every block live), 3 = speculative without runs (every block's candidates loaded on their own), 5 = speculative for every shape it can run (by default only where its row passes apply)
     int team = -1;     // waves per chain of the speculative kernel's team form (mvx_analyse_spec.h: TEAM): 0 = never, 2..8 = always that many, -1 = the library's choice
-    int super_rows_off = 0; // 1: mv.Super level 0 / first reduction through the LDS-tile / per-sample kernels only
-    int shadow8 = 0;   // r6 experiment: 8-bit clips keep THREE byte-shifted copies of their luma planes too (takes effect at mvx_super_shadow_bytes / the Super calls / mvx_analyse_set_ref_shadow)
-    int ablate = 0;
 };
 static MvxDebug g_dbg;
 extern "C" __attribute__((visibility("default"))) int mvx_debug_option(const char *name, int value) {
-    struct { const char *n; int *p; } tab[] = { { "general", &g_dbg.general }, { "fast_wpe", &g_dbg.fast_wpe }, { "cpw1", &g_dbg.cpw1 }, { "no_wpe2", &g_dbg.no_wpe2 }, { "no_wpe3", &g_dbg.no_wpe3 }, { "wpe3_u16", &g_dbg.wpe3_u16 }, { "fast_cpw", &g_dbg.fast_cpw }, { "fast_k", &g_dbg.fast_k }, { "fast_lds_min", &g_dbg.fast_lds_min }, { "fast_flags", &g_dbg.fast_flags }, { "pad_runs", &g_dbg.pad_runs }, { "shadow_planes", &g_dbg.shadow_planes }, { "degrain_xcd", &g_dbg.degrain_xcd }, { "degrain_shadow", &g_dbg.degrain_shadow }, { "cpw_sync", &g_dbg.cpw_sync }, { "lds_min", &g_dbg.lds_min }, { "super_rows_off", &g_dbg.super_rows_off }, { "spec", &g_dbg.spec }, { "team", &g_dbg.team }, { "shadow8", &g_dbg.shadow8 },
-#ifdef MVX_LAB
-        { "ablate", &g_dbg.ablate },
-#endif
-    };
+    struct { const char *n; int *p; } tab[] = { { "general", &g_dbg.general }, { "cpw1", &g_dbg.cpw1 }, { "spec", &g_dbg.spec }, { "team", &g_dbg.team } };
     for (auto &t : tab) if (!strcmp(t.n, name)) { *t.p = value; return MVX_OK; }
     mvx_set_error("mvx_debug_option: unknown option %s", name);
     return MVX_E_ARG;
@@ -64,14 +44,6 @@ extern "C" __attribute__((visibility("default"))) int mvx_debug_option(const cha
 static std::atomic<int> g_lastLaunch[5];
 extern "C" __attribute__((visibility("default"))) void mvx_debug_last_launch(int out[5]) {
     for (int i = 0; i < 5; i++) out[i] = g_lastLaunch[i].load();
-}
-
-int mvx_debug_value(const char *name, int def) {
-    if (!strcmp(name, "degrain_xcd")) return g_dbg.degrain_xcd >= 0 ? g_dbg.degrain_xcd : def;
-    if (!strcmp(name, "super_rows_off")) return g_dbg.super_rows_off;
-    if (!strcmp(name, "shadow8")) return g_dbg.shadow8;
-    if (!strcmp(name, "degrain_shadow")) return g_dbg.degrain_shadow;
-    return def;
 }
 
 #define AFAIL(...) do { snprintf(err, MVX_ERRLEN, __VA_ARGS__); mvx_set_error("%s", err); return MVX_E_ARG; } while (0)
@@ -103,7 +75,7 @@ __device__ __forceinline__ void mvx_get_median(GVec &o, const GVec &v1, const GV
 __global__ __launch_bounds__(256) void analyse_divide_kernel(const AParams *Pp, const AJob *jobs) {
     const AParams &P = *Pp;
     unsigned char *blob = jobs[blockIdx.y].blob;
-    if (!blob) return; // padding entry of the job table
+    if (!blob) return; // (a job without a blob)
     const int valid = ((const int *)blob)[1];
     const int nBlkX = P.lv[0].nBlkX, nBlkY = P.lv[0].nBlkY, nBlk = nBlkX * nBlkY;
     unsigned char *rec0 = blob + P.lv[0].blobOff;
@@ -236,7 +208,6 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_create(const m
     P.lambda = nLambda; P.lsad = lsad; P.badSAD = badSAD;
     P.verybigSAD = (long long)P.blkX * P.blkY * (1 << si.bits);
     P.superHPad = si.hpad; P.superVPad = si.vpad;
-    P.ablate = g_dbg.ablate;
     for (int p = 0; p < 3; p++) P.pitch[p] = p < si.num_planes ? super_pitch[p] : 0;
     if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) AFAIL("Analyse: the U and V planes of the super clip must share one pitch.");
     int blobOff = 8;
@@ -283,8 +254,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_set_ref_shadow
     for (int p = 0; p < 3; p++) {
         const long long v = copy_stride ? (long long)copy_stride[p] : 0;
         if (v < 0 || v % 16) { mvx_set_error("mvx_analyse_set_ref_shadow: copy strides must be non-negative multiples of 16 bytes"); return MVX_E_ARG; }
-        a->P.shadow[p] = ((p == 0 && !(g_dbg.shadow_planes & 1)) || (p > 0 && !(g_dbg.shadow_planes & 2))) ? 0 : v;
-        if (p == 0 && a->P.bps == 1 && !g_dbg.shadow8) a->P.shadow[0] = 0; // (8-bit super frames carry the UV plane only)
+        a->P.shadow[p] = p == 0 && a->P.bps == 1 ? 0 : v; // (8-bit super frames carry the UV plane only)
     }
     std::lock_guard<std::mutex> lk(a->guard.mu);
     if (a->dP) HIP_CHECK(hipMemcpy(a->dP, &a->P, sizeof(AParams), hipMemcpyHostToDevice)); // (synchronous: no launch of this handle is reading it concurrently unless the caller races)
@@ -342,8 +312,8 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_frames(mvx_ana
     // SIMD of a CU, and the job table is sorted by reference frame first, so the waves of a workgroup share their reference
     // lines in the CU's L1 (+4.7 % at 4K16; measured r1: a barrier between them only costs -- per block -13 %, per 16 blocks 0 %,
     // per row +3.7 % -- and dealing the groups out so that each XCD gets a contiguous range of frames changes nothing).
-    const bool spec = P.dctmode == 0 && P.xr == 2 && P.yr == 2 && P.blkX == P.blkY && (P.blkX == 16 || P.blkX == 8 || (P.blkX == 32 && P.bps == 2)) &&
-                      !g_dbg.cpw1;
+    if (!g_dbg.cpw1) std::stable_sort(hj.begin(), hj.end(), [](const AJob &x, const AJob &y) { return (uintptr_t)x.ref[0] > (uintptr_t)y.ref[0]; }); // (no reference: last)
+    HIP_CHECK(hipMemcpyAsync(S.d, hj.data(), sizeof(AJob) * njobs, hipMemcpyHostToDevice, st));
     int simds = 0; // of the device this call runs on
     {
         int dev = 0, cus = 0;
@@ -351,6 +321,13 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_frames(mvx_ana
         HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
         simds = 4 * cus;
     }
+    // after a launch: what ran (mvx_debug_last_launch), then the extra array of half-size blocks
+    auto finish = [&](int fast, int cpw, int syncEvery, int kind) {
+        g_lastLaunch[0] = fast; g_lastLaunch[1] = cpw; g_lastLaunch[2] = syncEvery; g_lastLaunch[3] = njobs; g_lastLaunch[4] = kind;
+        if (P.divide) hipLaunchKernelGGL(analyse_divide_kernel, dim3((P.lv[0].nBlkX * P.lv[0].nBlkY + 255) / 256, njobs), dim3(256), 0, st, a->dP, S.d);
+        HIP_CHECK(hipGetLastError());
+        return MVX_OK;
+    };
     // A launch with more chains than SIMDs runs TWO chains per SIMD where a 256-register build of the kernel exists without
     // spills (8-bit 8x8, 16x16; 16-bit 8x8, 16x16, 32x32): 8-bit 1080p +53 %; 16-bit 4K +13 %, and there only as workgroups of EIGHT chains
     // that share a reference frame -- eight unrelated chains per CU thrash its L1 / the XCD's L2 and lose.
@@ -381,7 +358,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_frames(mvx_ana
         // (r6, ADVICE r5: whether a team FITS is decided here, before anything is sized for the speculative kernel -- a shape without row passes whose team
         // would not fit the CU's LDS (a very wide frame) stays on the serial kernel with the serial kernel's LDS sizing instead of running the one-wave
         // speculative kernel, which loses to it: cfg2, cfg4, cfg5 above)
-        const int sStrip = (P.bps == 2 && P.blkX == 16 && MVX_STRIP_DMA) ? 2 * 24 * 128 /* r6: two strip buffers, filled by LDS-direct loads */ : (P.bps == 2 && (P.blkX == 16 || (MVX_STRIP32 && P.blkX == 32))) ? (P.blkX + P.blkX / 2) * 128 : (P.bps == 1 && P.blkX == 16) ? 24 * 64 : 0; // the source strip of a window of blocks: 24 (48) rows x 8 columns (mvx_analyse_spec.h: STRIP_OK)
+        const int sStrip = (P.bps == 2 && P.blkX == 16) ? 2 * 24 * 128 /* r6: two strip buffers, filled by LDS-direct loads */ : (P.bps == 2 && MVX_STRIP32 && P.blkX == 32) ? (P.blkX + P.blkX / 2) * 128 : (P.bps == 1 && P.blkX == 16) ? 24 * 64 : 0; // the source strip of a window of blocks: 24 (48) rows x 8 columns (mvx_analyse_spec.h: STRIP_OK)
         const int sSrc = stripShape8 ? 16 + 768 : fRow < sStrip ? sStrip : fRow; // (8-bit 8x8: 16 bytes of slack + 12 rows x 64 bytes)
         int sNeed = 0, sTabMax = 0; // per level: row buffer (8 B per block of THAT level) + the table of its search type; the largest SAD table of any level
         for (int i = 0; i < P.nLevels; i++) {
@@ -420,41 +397,12 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_frames(mvx_ana
         int k = njobs > 3 * simds ? 4 : njobs > 2 * simds ? 3 : njobs > simds ? 2 : 1;
         // the row passes of the speculative kernel (16-bit 16x16) want the 256-register builds: 3072 chains take 878 ms at two per SIMD (in
         // two rounds) against 919 at three (profiles/r4_spec_loads_in_flight_and_batch.txt)
-        if (useSpecStrips && k > 2 && g_dbg.fast_k != 3) k = 2;
-        if (g_dbg.fast_wpe > 0 && g_dbg.fast_wpe < k) k = g_dbg.fast_wpe;
-        if (g_dbg.fast_k > 0) k = g_dbg.fast_k;
+        if (useSpecStrips && k > 2) k = 2;
         while (k > 1 && (!have(k) || (long long)perChain * 4 * k > 160 * 1024)) k--;
         if ((long long)perChain * 4 * k <= 160 * 1024) {
-            std::stable_sort(hj.begin(), hj.end(), [](const AJob &x, const AJob &y) { return (uintptr_t)x.ref[0] > (uintptr_t)y.ref[0]; }); // (no reference: last)
-            int cpw = 4 * k;
             // the speculative kernel's chains wait for each other less in workgroups of FOUR (two per CU) that meet every 128 blocks: 345 ms per
             // 2046-chain launch against 370 with eight and a barrier per group (profiles/r4_spec_twostage_workgroup_size.txt, ..._barrier_interval.txt)
-            if (useSpecStrips) cpw = 4;
-            if (g_dbg.fast_cpw > 0 && g_dbg.fast_cpw < 4 * k) cpw = g_dbg.fast_cpw;
-            // keep the chains that share a reference frame in one workgroup where they fit: a run of the sorted table that would
-            // straddle a workgroup boundary starts a new workgroup instead (the skipped slots become padding entries, blob == NULL)
-            std::vector<AJob> padded;
-            const std::vector<AJob> *table = &hj;
-            if (g_dbg.pad_runs == 1) {
-                AJob none;
-                memset(&none, 0, sizeof(none));
-                for (size_t i = 0; i < hj.size();) {
-                    size_t j = i;
-                    while (j < hj.size() && hj[j].ref[0] == hj[i].ref[0]) j++;
-                    const size_t len = j - i, used = padded.size() % cpw;
-                    if (used && len <= (size_t)cpw && used + len > (size_t)cpw) padded.resize(padded.size() + (cpw - used), none);
-                    padded.insert(padded.end(), hj.begin() + i, hj.begin() + j);
-                    i = j;
-                }
-                table = &padded;
-            }
-            const int ntab = (int)table->size();
-            if ((size_t)ntab > S.cap) {
-                if (S.d) (void)hipFree(S.d);
-                S.cap = (size_t)ntab * 2;
-                HIP_CHECK(hipMalloc((void **)&S.d, S.cap * sizeof(AJob)));
-            }
-            HIP_CHECK(hipMemcpyAsync(S.d, table->data(), sizeof(AJob) * ntab, hipMemcpyHostToDevice, st));
+            const int cpw = useSpecStrips ? 4 : 4 * k;
             // Barrier between the chains of a workgroup every that many blocks of a row.  16-bit clips (shadow layout: the kernel is
             // bound by what the XCD's L2 must re-fetch): the chains that share a reference frame have to stay within a few blocks of
             // each other to share its lines -- measured r2 at three chains per SIMD (4K16): 256 blocks 337 fps, 128: 378, 16-64: 389-390,
@@ -462,61 +410,38 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_frames(mvx_ana
             // 1953-1970 with 16-64).
             int syncEvery = k >= 2 ? (P.bps == 2 ? 32 : 256) : 0;
             if (useSpecStrips) syncEvery = (stripShape8 || stripShape16) ? 0 : 128; // (8-bit 16x16, 4096 chains: none 144 ms, every 128 blocks 147: profiles/r5_hd16_bench.txt) // (8-bit, 4096 chains: none 330 ms, every 512 blocks 337, 256: 344, 128: 366 -- profiles/r4_rows8_configs2.txt)
-            if (g_dbg.cpw_sync >= 0 && (g_dbg.cpw_sync & (g_dbg.cpw_sync - 1)) == 0) syncEvery = g_dbg.cpw_sync;
             // XCD-contiguous workgroup order: neighbours in the (reference-sorted) job table share an L2 (+0.5 %, 4K16)
-            const int flags = (g_dbg.fast_flags >= 0 ? g_dbg.fast_flags : MVX_FAST_XCD_REMAP) | ((P.shadow[1] != 0 && P.chroma) ? MVX_FAST_UV : 0) | (g_dbg.spec == 2 ? MVX_FAST_NOSPEC : 0) | (g_dbg.spec == 3 ? MVX_FAST_NOSTRIP : 0);
-            ALaunch L = { ntab, fNeed, useSpec ? sRow : fRow, useSpec ? sRow : fRow, fBins, fNeed, simds, cpw, k, syncEvery, k, flags, st, a->dP, S.d };
-            L.ldsBytes = g_dbg.fast_lds_min; // (floor of the workgroup's LDS request, 0 = none)
+            const int flags = MVX_FAST_XCD_REMAP | ((P.shadow[1] != 0 && P.chroma) ? MVX_FAST_UV : 0) | (g_dbg.spec == 2 ? MVX_FAST_NOSPEC : 0) | (g_dbg.spec == 3 ? MVX_FAST_NOSTRIP : 0);
+            const ALaunch L = { njobs, 0, useSpec ? sRow : fRow, useSpec ? sRow : fRow, fBins, fNeed, simds, cpw, k, syncEvery, k, flags, st, a->dP, S.d };
             int rc;
             // TEAM form (r5): the nw waves of a workgroup walk ONE chain.  A chain finishes ~nw times sooner and a launch keeps nw times fewer chains resident
             // per wave slot, so it is the form for launches that do not fill the GPU with one wave per chain (a frame server's look-ahead window); for
             // big batches the choice is measured.  LDS: [64 B control words | row buffer] shared + per wave [source strip | SAD table]
             const int specSide = (P.blkX == 16 && P.ovX == 0) ? 1 : 0; // 16x16 blocks side by side: the SIDE builds of the speculative kernel (their row passes step by a whole block)
-            int team = 0;
-            if (useSpec) {
-                team = g_dbg.team >= 0 ? g_dbg.team : mvx_team_default(njobs, simds, useSpecStrips, P.bps);
-                if (team == 1 || team > 8) team = 0;
-            }
-            team = teamThatFits(team);
+            const int team = useSpec ? teamThatFits(g_dbg.team >= 0 ? g_dbg.team : mvx_team_default(njobs, simds, useSpecStrips, P.bps)) : 0;
             if (team) {
-                const int shared = teamShared, perWave = teamPerWave;
-                if (team > 1) {
-                    ALaunch TL = L;
-                    TL.ldsRow = shared; TL.ldsNeed = perWave; TL.ldsHist = sRow; TL.syncEvery = 0; TL.fast = 2; TL.cpw = 1;
-                    // (the job table may carry padding entries, blob == NULL, from the run padding above: the kernel skips them, `!J.blob`)
-                    const ASpecLaunch SL = { TL, sRow, team, specSide };
-                    rc = P.bps == 1 ? mvx_analyse_launch_spec_u8(P, SL) : mvx_analyse_launch_spec_u16(P, SL);
-                    if (rc == MVX_OK) {
-                        g_lastLaunch[0] = 2; g_lastLaunch[1] = team; g_lastLaunch[2] = 0; g_lastLaunch[3] = ntab; g_lastLaunch[4] = 3;
-                        if (P.divide) hipLaunchKernelGGL(analyse_divide_kernel, dim3((P.lv[0].nBlkX * P.lv[0].nBlkY + 255) / 256, ntab), dim3(256), 0, st, a->dP, S.d);
-                        HIP_CHECK(hipGetLastError());
-                        return MVX_OK;
-                    }
-                    if (rc != 1) return rc;
-                }
+                ALaunch TL = L;
+                TL.ldsRow = teamShared; TL.ldsNeed = teamPerWave; TL.ldsHist = sRow; TL.syncEvery = 0; TL.fast = 2; TL.cpw = 1;
+                const ASpecLaunch SL = { TL, sRow, team, specSide };
+                rc = P.bps == 1 ? mvx_analyse_launch_spec_u8(P, SL) : mvx_analyse_launch_spec_u16(P, SL);
+                if (rc == MVX_OK) return finish(2, team, 0, 3);
+                if (rc != 1) return rc;
             }
             if (useSpec) { const ASpecLaunch SL = { L, sTab, 0, specSide }; rc = P.bps == 1 ? mvx_analyse_launch_spec_u8(P, SL) : mvx_analyse_launch_spec_u16(P, SL); }
             else rc = P.bps == 1 ? mvx_analyse_launch_fast_u8(P, L) : mvx_analyse_launch_fast_u16(P, L);
-            if (rc == MVX_OK) {
-                g_lastLaunch[0] = k; g_lastLaunch[1] = cpw; g_lastLaunch[2] = syncEvery; g_lastLaunch[3] = ntab; g_lastLaunch[4] = useSpec ? 2 : 0;
-                if (P.divide) hipLaunchKernelGGL(analyse_divide_kernel, dim3((P.lv[0].nBlkX * P.lv[0].nBlkY + 255) / 256, ntab), dim3(256), 0, st, a->dP, S.d);
-                HIP_CHECK(hipGetLastError());
-                return MVX_OK;
-            }
+            if (rc == MVX_OK) return finish(k, cpw, syncEvery, useSpec ? 2 : 0);
             if (rc != 1) return rc;
         }
     }
-    const bool oneChain = g_dbg.cpw1 != 0;
-    int cpw = oneChain ? 1 : 4, wpe = 1; // (the generic kernels have four-chain builds too)
-    if (spec && njobs > simds && !g_dbg.no_wpe2) {
+    // ---- the general kernels (they have four-chain builds too)
+    const bool specialised = P.dctmode == 0 && P.xr == 2 && P.yr == 2 && P.blkX == P.blkY && (P.blkX == 16 || P.blkX == 8 || (P.blkX == 32 && P.bps == 2));
+    int cpw = g_dbg.cpw1 ? 1 : 4, wpe = 1;
+    if (specialised && !g_dbg.cpw1 && njobs > simds) {
         if (P.bps == 1 && (P.blkX == 8 || P.blkX == 16)) wpe = 2;
         // three per SIMD for the lightest kernel: its 168-register build spills 72 registers and still gains 14 % (1080p 1642 -> 1867 fps)
-        if (P.bps == 1 && P.blkX == 8 && njobs > 2 * simds && !g_dbg.no_wpe3) wpe = 3;
+        if (P.bps == 1 && P.blkX == 8 && njobs > 2 * simds) wpe = 3;
         if (P.bps == 2 && (P.blkX == 16 || P.blkX == 8 || P.blkX == 32)) { wpe = 2; cpw = 8; }
-        if (P.bps == 2 && P.blkX == 16 && njobs > 2 * simds && g_dbg.wpe3_u16) { wpe = 3; cpw = 12; }
     }
-    if (cpw > 1) std::stable_sort(hj.begin(), hj.end(), [](const AJob &x, const AJob &y) { return (uintptr_t)x.ref[0] > (uintptr_t)y.ref[0]; }); // (no reference: last)
-    HIP_CHECK(hipMemcpyAsync(S.d, hj.data(), sizeof(AJob) * njobs, hipMemcpyHostToDevice, st));
     // LDS: [source block (Y,U,V) | previous-row vectors | predictor rows (this, below) | histogram]
     int srcBytes = P.blkX * P.blkY * P.bps;
     if (P.chroma) srcBytes += 2 * (P.blkX / P.xr) * (P.blkY / P.yr) * P.bps;
@@ -532,23 +457,18 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_frames(mvx_ana
     // the CU's 160 KiB of LDS makes the dispatcher spread the chains four per CU instead of stacking some CUs (+5 % at 1008 chains).
     // The multi-chain workgroups are sized from ldsNeed instead.
     const int ldsNeed = ldsBytes;
-    {
-        int v = 33 * 1024;
-        if (g_dbg.lds_min >= 0) v = g_dbg.lds_min; // developer override
-        if (v > ldsBytes && v <= 160 * 1024) ldsBytes = v;
-    }
+    if (ldsBytes < 33 * 1024) ldsBytes = 33 * 1024;
     // a workgroup's chains share the CU's 160 KiB of LDS: very wide frames (long row buffers) get fewer chains per workgroup
     while (cpw > 1 && (long long)((ldsNeed + 255) & ~255) * cpw > 160 * 1024) {
-        cpw = cpw == 12 ? 8 : cpw == 8 ? 4 : 1;
+        cpw = cpw == 8 ? 4 : 1;
         if (wpe == 3) wpe = 2;
         if (P.bps == 2) wpe = 1; // (the 16-bit two-per-SIMD builds exist for eight chains per workgroup only)
     }
     // barrier between the chains of a workgroup every that many blocks (power of two) and at every row start: keeps the chains
     // of a two-per-SIMD workgroup on neighbouring blocks (+2 % at 4K16 for any interval from 64 blocks to a row, +2.8 % at 1080p
     // 8-bit); with one chain per SIMD it costs 1 %
-    int syncEvery = wpe >= 2 ? 256 : 0;
-    if (g_dbg.cpw_sync >= 0 && (g_dbg.cpw_sync & (g_dbg.cpw_sync - 1)) == 0) syncEvery = g_dbg.cpw_sync;
-    ALaunch L = { njobs, ldsBytes, ldsRow, ldsHist, histBins, ldsNeed, simds, cpw, wpe, syncEvery, 0, 0, st, a->dP, S.d };
+    const int syncEvery = wpe >= 2 ? 256 : 0;
+    const ALaunch L = { njobs, ldsBytes, ldsRow, ldsHist, histBins, ldsNeed, simds, cpw, wpe, syncEvery, 0, 0, st, a->dP, S.d };
     // the specialised kernels address the reference as "64-bit base + 32-bit offset inside the level's plane set" (all sub-pel planes)
     bool off32 = true;
     for (int i = 0; i < P.nLevels; i++)
@@ -556,10 +476,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_frames(mvx_ana
     int rc = (P.dctmode != 0 || !off32) ? 1 : P.bps == 1 ? mvx_analyse_launch_u8(P, L) : mvx_analyse_launch_u16(P, L); // specialised 4:2:0 geometries (SAD cost only)
     if (rc == 1) rc = mvx_analyse_launch_any(P, L);                                     // everything else
     if (rc) return rc;
-    g_lastLaunch[0] = 0; g_lastLaunch[1] = cpw; g_lastLaunch[2] = syncEvery; g_lastLaunch[3] = njobs; g_lastLaunch[4] = 0;
-    if (P.divide) hipLaunchKernelGGL(analyse_divide_kernel, dim3((P.lv[0].nBlkX * P.lv[0].nBlkY + 255) / 256, njobs), dim3(256), 0, st, a->dP, S.d);
-    HIP_CHECK(hipGetLastError());
-    return MVX_OK;
+    return finish(0, cpw, syncEvery, 0);
 }
 
 // ================================================================================================ mv.Recalculate

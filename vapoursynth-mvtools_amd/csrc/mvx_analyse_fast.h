@@ -8,7 +8,7 @@
 // for the square block sizes 8 / 16 / 32, plus the bad-block rescue (:938-963: UMH / expanding rings around zero, then the
 // small-radius refinement) as a plain loop.  mvx_analyse_frames picks it whenever a parameter set qualifies
 // (fast_eligible); everything else still runs analyse_kernel.  Results are identical by construction and by test: the
-// parity suite runs the same cases through both (MVX_LAB builds can force either).
+// parity suite runs the same cases through both (the "general" debug option forces analyse_kernel).
 //
 // What is different from analyse_kernel's fast path:
 //   * one chain per wavefront as before, but the per-block data that lives in memory is handled 64 blocks at a time: the
@@ -26,9 +26,7 @@
 // profiles/r3_lean_kernel_trims_ab.txt, r3_lean_kernel_dedup_nospec_ab.txt.
 #define MVX_SRC_AHEAD 2 // the source block's LDS pieces are read this many pieces ahead of their use (a read right before its use costs the wave an LDS round trip per piece)
 #define MVX_STREAM_MAX 12 // a candidate's pieces per lane up to which luma + chroma are ONE stream of loads (the serial kernel: longer streams measured slower).  The default of FastSearcher's STREAM_MAX parameter; the speculative kernel instantiates its base class with 48
-#ifndef MVX_INFLIGHT
-#define MVX_INFLIGHT 12 // reference loads a lane keeps in flight while it evaluates a candidate: all twelve of a hexagon-pass candidate
-#endif
+constexpr int FAST_INFLIGHT = 12; // reference loads a lane keeps in flight while it evaluates a candidate: all twelve of a hexagon-pass candidate
 #include "mvx_analyse_kernel.h"
 
 // -DMVX_FAST_PROF (tools/build_variant.py; read back by tools/fastprof.py): cycles of ONE chain per phase of the block loop, stamped with
@@ -273,7 +271,7 @@ template <int BPS, int BW, bool UV, int STREAM_MAX = MVX_STREAM_MAX> struct Fast
     __device__ __forceinline__ void region2(int s, const lds_u8 *srcA, gl_u8 *baseA, unsigned offA, unsigned pitchA, unsigned &accA,
                                             const lds_u8 *srcB, gl_u8 *baseB, unsigned offB, unsigned pitchB, unsigned &accB) const {
         constexpr int GG = 1 << LOGG, CA = 1 << LOGCA, CB_ = 1 << LOGCB;
-        constexpr int NA = TA / GG, NBB = TB / GG, NT = NA + NBB, W = NT < MVX_INFLIGHT ? NT : MVX_INFLIGHT;
+        constexpr int NA = TA / GG, NBB = TB / GG, NT = NA + NBB, W = NT < FAST_INFLIGHT ? NT : FAST_INFLIGHT;
         const int rowA = s >> LOGCA, xbA = (s & (CA - 1)) * CBA, rowB = s >> LOGCB, xbB = (s & (CB_ - 1)) * CBB;
         unsigned poA = offA + (unsigned)rowA * pitchA + (unsigned)xbA, poB = offB + (unsigned)rowB * pitchB + (unsigned)xbB;
         const lds_u8 *spA = srcA + rowA * ROWBA + xbA, *spB = srcB + rowB * ROWBB + xbB;
@@ -917,7 +915,7 @@ __global__ __launch_bounds__(64 * MAXCPW, WPE) void analyse_fast_kernel(const AP
     const int chain = uni(wg * cpw + (int)(threadIdx.x >> 6));
     if (chain >= njobs) return; // (a finished wave no longer counts for the workgroup's barriers)
     const AJob &J = jobs[chain];
-    if (!J.blob) return;        // padding entry of the job table (the host keeps the chains of one reference frame in one workgroup)
+    if (!J.blob) return;        // (a job without a blob)
     const int l = lane_id();
     int *hdr = (int *)J.blob;
     if (!J.valid) { // gopWriteDefaultToArray GroupOfPlanes.c:150-164, pobWriteDefaultToArray PlaneOfBlocks.cpp:1529-1556
@@ -960,8 +958,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_debug_fastprof(unsigne
 template <int BPS, int BW, int WPE, int MAXCPW, bool UV> static int launch_analyse_fast_uv(const ALaunch &L) {
     const int perChain = (L.ldsNeed + 255) & ~255;
     const int cpw = L.cpw < MAXCPW ? L.cpw : MAXCPW;
-    int lds = perChain * cpw;
-    if (L.ldsBytes > lds && L.ldsBytes <= 160 * 1024) lds = L.ldsBytes; // developer / host option: fewer workgroups per CU
+    const int lds = perChain * cpw;
     if (lds > 64 * 1024)
         HIP_CHECK(hipFuncSetAttribute((const void *)analyse_fast_kernel<BPS, BW, WPE, MAXCPW, UV>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     hipLaunchKernelGGL((analyse_fast_kernel<BPS, BW, WPE, MAXCPW, UV>), dim3((L.njobs + cpw - 1) / cpw), dim3(64 * cpw), lds, L.st, L.dP, L.dJobs,

@@ -50,7 +50,6 @@ struct AParams {
     int blobSize;
     int superHPad, superVPad;
     long long shadow[3]; // byte distance between the shifted copies of a reference plane (mvx_analyse_set_ref_shadow), 0 = none
-    int ablate; // developer-only (MVX_ABLATE env): 1 = skip the search, 2 = predictor round only; results are then WRONG
     ALevel lv[MVX_MAX_LEVELS];
 };
 
@@ -322,6 +321,7 @@ __device__ unsigned long long g_prof[32];
 #define PROF_ADD(i, v) ((void)0)
 #endif
 #define PF_MAX 4 // source-block prefetch registers per lane (16 B each)
+constexpr int EV_NB = 4; // chunks in flight per region: four measured +2 % over eight at 4K16 (register pressure), and keeps the 8x8 / 16x16 kernels spill-free at 256 registers (two would do that for the 16-bit 32x32 kernel too, but costs it 17 %: 8K 48.2 -> 40.1 fps)
 // Compile-time block geometry for the specialised kernels (BW == 0: geometry only known at run time -> generic loops).
 constexpr int pow2c(int v, int r = 1) { return r >= v ? r : pow2c(v, r * 2); }
 // DCT: the SATD cost modes (dct 5..10) are compiled into their own generic kernel only -- their code costs the default
@@ -433,11 +433,7 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
     // All loads of a batch (<= EV_BATCH per lane) are issued before the first SAD so that they overlap: the wave pays
     // one memory latency per batch instead of one per chunk.
 #define EV_BATCH 8
-#ifdef MVX_NT_REF
-#define LDREF(p) __builtin_nontemporal_load(p)
-#else
 #define LDREF(p) (*(p))
-#endif
     template <int CB> __device__ __forceinline__ unsigned eval_region(int s, int logG, int T, int logC, int rowB, const lds_u8 *src,
                                                                        gl_u8 *ref, long long refPitch, unsigned acc) const {
         // T and G are powers of two: every lane owns exactly cnt = T/G items (or lanes s < T one item each when G > T),
@@ -508,10 +504,7 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
             return acc;
         }
         constexpr int N = T >= G ? T / G : 1;        // items per lane
-#ifndef MVX_NB
-#define MVX_NB 4 // chunks in flight per region: four measured +2 % over eight at 4K16 (register pressure), and keeps the 8x8 / 16x16 kernels spill-free at 256 registers (two would do that for the 16-bit 32x32 kernel too, but costs it 17 %: 8K 48.2 -> 40.1 fps)
-#endif
-        constexpr int NB = N < MVX_NB ? N : MVX_NB;  // loads in flight per batch
+        constexpr int NB = N < EV_NB ? N : EV_NB;  // loads in flight per batch
         if (G >= C) { // the chunk column is fixed per lane, rows advance by G / C per item
             const int row0 = s >> LOGC, xb = (s & (C - 1)) * CB;
             gl_u8 *p = ref + (long long)row0 * refPitch + xb;
@@ -586,10 +579,7 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
             return acc;
         }
         constexpr int N = T >= G ? T / G : 1;        // items per lane
-#ifndef MVX_NB
-#define MVX_NB 4 // chunks in flight per region: four measured +2 % over eight at 4K16 (register pressure), and keeps the 8x8 / 16x16 kernels spill-free at 256 registers (two would do that for the 16-bit 32x32 kernel too, but costs it 17 %: 8K 48.2 -> 40.1 fps)
-#endif
-        constexpr int NB = N < MVX_NB ? N : MVX_NB;  // loads in flight per batch
+        constexpr int NB = N < EV_NB ? N : EV_NB;  // loads in flight per batch
         if (G >= C) { // the chunk column is fixed per lane, rows advance by G / C per item
             const int row0 = s >> LOGC, xb = (s & (C - 1)) * CB;
             const unsigned p = off + (unsigned)row0 * refPitch + (unsigned)xb;
@@ -891,7 +881,7 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
             }
             unsigned aL = 0, aC = 0;
             const long long pt0 = PROF_T();
-            if (ok && ablate != 3) eval_cand(s, logG, vx, vy, vyc, aL, aC);
+            if (ok) eval_cand(s, logG, vx, vy, vyc, aL, aC);
             const long long pt1 = PROF_T();
             aL = group_sum(aL, logG);
             aC = group_sum(aC, logG);
@@ -949,7 +939,6 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
         nLambda = uni((long long)((double)nLambda * scale * scale));
     }
 
-    int ablate;                                        // developer switch ("ablate" debug option, LAB builds), copied once: never re-read from memory inside the block loop
     int blockSync;                                     // several chains per workgroup: barrier interval in blocks (analyse_kernel, CPW)
 
     // ---- fast path -----------------------------------------------------------------------------------------------
@@ -1275,7 +1264,7 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
             PROF_ADD(10, st1 - st0); PROF_ADD(11, st2 - st1);
 
             switch (post) {
-            case POST_ROUNDA: aCost = rCost; aTot = rTot; aVx = rVx; aVy = rVy; pc = tryMany ? PC_TRY_NEXT : PC_REFINE; if (ablate == 2) pc = PC_DONE; break;
+            case POST_ROUNDA: aCost = rCost; aTot = rTot; aVx = rVx; aVy = rVy; pc = tryMany ? PC_TRY_NEXT : PC_REFINE; break;
             case POST_HEX6:
                 if (w >= 0) dir = w;
                 if (dir != -2) { bmx += tab8(HEX2X, dir + 1); bmy += tab8(HEX2Y, dir + 1); it = 1; pc = PC_HEX3; }
@@ -1626,11 +1615,17 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
             __builtin_amdgcn_wave_barrier(); // single wave: DS ops are in order; keep the compiler from moving LDS reads above the staging writes
             if (GEO::DCT && (dctmode == 7 || dctmode == 8 || dctmode == 10)) srcLuma = src_luma(); // :829-830 (only these modes read it)
             const long long bt1 = PROF_T();
-            if (ablate == 1) { bestMV = predictor; bestMV.sad = 0; }
             // (the hints matter: the general state machine is an inner loop, which the register allocator would otherwise favour
             // over the straight-line path that actually runs; measured +2 % at 4K16)
-            else if (__builtin_expect(fast, 1)) { if (__builtin_expect(!search_block_fast<EARLY_K>(&preA), 0)) search_block(1); }
-            else search_block(0);
+            // (bestMV = predictor is a dead store -- round A of search_block(0) always writes all of bestMV -- that the compiler cannot prove
+            // dead.  It steers the register allocation: without it the builds with two or three chains per SIMD spill to scratch (8-bit 8x8 at
+            // three per SIMD 40 -> 86 VGPRs, 8-bit 16x16 and 16-bit 32x32 at two 0 -> 4 / 21); with it the DCT builds spill 21 VGPRs they
+            // otherwise do not.  tools/isa_report.py)
+            if (__builtin_expect(fast, 1)) { if (__builtin_expect(!search_block_fast<EARLY_K>(&preA), 0)) search_block(1); }
+            else {
+                if constexpr (!GEO::DCT) bestMV = predictor;
+                search_block(0);
+            }
             const long long bt2 = PROF_T();
             __builtin_amdgcn_wave_barrier();
 
@@ -1739,7 +1734,6 @@ __global__ __launch_bounds__(64 * CPW, WPE) void analyse_kernel(const AParams *P
     S.lds = (lds_u8 *)smem + (CPW == 1 ? 0 : uni((int)(threadIdx.x >> 6)) * ldsChain);
     S.ldsRow = ldsRow; S.ldsHist = ldsHist; S.histBins = histBins;
     S.blockSync = CPW > 1 ? syncEvery : 0;
-    S.ablate = uni(P.ablate) & 0xff;
 #ifdef MVX_PROFILE
     for (int i = 0; i < 16; i++) S.prof[i] = 0;
     const long long kt0 = PROF_T();
@@ -1755,7 +1749,7 @@ __global__ __launch_bounds__(64 * CPW, WPE) void analyse_kernel(const AParams *P
     }
 #ifdef MVX_PROFILE
     S.prof[9] = PROF_T() - kt0;
-    if (l == 0 && chain == (P.ablate >> 8)) for (int i = 0; i < 16; i++) g_prof[i] = (unsigned long long)S.prof[i]; // MVX_ABLATE = chain << 8
+    if (l == 0 && chain == 0) for (int i = 0; i < 16; i++) g_prof[i] = (unsigned long long)S.prof[i];
 #endif
 }
 
@@ -1781,7 +1775,7 @@ __global__ __launch_bounds__(64, 1) void recalc_kernel(const AParams *Pp, const 
     typedef Searcher<BPS, GeoAnyDct> S_t;
     S_t S(P, J);
     S.lds = (lds_u8 *)smem; S.ldsRow = ldsRow; S.ldsHist = ldsHist; S.histBins = histBins;
-    S.ablate = 0; S.blockSync = 0;
+    S.blockSync = 0;
     for (int i = 0; i < 16; i++) S.prof[i] = 0;
     const int l = lane_id();
     S.setup_geometry(0);

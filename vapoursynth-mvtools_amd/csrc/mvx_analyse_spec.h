@@ -35,17 +35,7 @@
 #define MVX_FAST_NOSTRIP 8                // flags: no runs in pass A (every block's candidates loaded on their own)
 #define MVX_FAST_NOSPEC 4                 // flags: verify nothing, search every block live (developer switch: the same kernel as a plain serial walk)
 
-// -DMVX_SPEC_ABL=n (tools/build_variant.py): timing-only ablations of pass A, results are WRONG -- 1: no zero / global / hierarchical pass on Hex2
-// levels, 2: every group of the pattern pass evaluates the centre (same lines for all lanes), 3: every speculative result is taken (no live blocks); row passes: 4: no LDS source reads, 5: no reference loads, 6: no SADs
-#ifndef MVX_SPEC_ABL
-#define MVX_SPEC_ABL 0
-#endif
-#ifndef MVX_STRIP_DMA
-#define MVX_STRIP_DMA 1 // r6: the source strip of a window of 16-bit 16x16 blocks goes from global memory straight into LDS (global_load_lds_dwordx4), two buffers
-#endif
-#ifndef MVX_SPEC_SW3
-#define MVX_SPEC_SW3 12 // row loads in flight per lane in the builds for three or more chains per SIMD (168 registers)
-#endif
+constexpr int SPEC_SW3 = 12; // row loads in flight per lane in the builds for three or more chains per SIMD (168 registers)
 // -DMVX_SPEC_PROF (tools/specprof.py): cycles of ONE chain per phase of the group loop (s_memtime; a stamp waits for the scalar counter only)
 #ifdef MVX_SPEC_PROF
 #define SPROF_N 20 // (16: TEAM, waiting for the previous block row; 17: TEAM, waiting for the token)
@@ -58,12 +48,6 @@ static __device__ unsigned long long g_specprof[SPROF_N];
 #define SPEC_PROF_DUMP_() do { if (l == 0 && chain == 5 && S.role == 1) for (int i = 0; i < SPROF_N; i++) g_specprof[i] = (unsigned long long)S.sprof[i]; } while (0)
 #else
 #define SPEC_PROF_DUMP_() ((void)0)
-#endif
-#if MVX_SPEC_ABL == 9 // debug build: what the kernel knew about the 64 columns at (level, block row, first column) = g_specdbgAt (mvx_debug_specdbg_at)
-#define SPECDBG_N 24
-static __device__ int g_specdbg[64 * SPECDBG_N];
-static __device__ int g_specdbgAt[3];
-#define SPECDBG_HERE() (lvl == g_specdbgAt[0] && blky == g_specdbgAt[1] && c0 == g_specdbgAt[2])
 #endif
 #ifdef MVX_SPEC_STATS
 static __device__ unsigned long long g_specstat[MVX_MAX_LEVELS][8]; // per level: blocks in speculated rows, of them searched live, live because the flag was clear, rescues; 16x16 row passes: windows of stage 2 in strip form, in block form, blocks of block-form windows whose centre differs from the window's first block, block-form windows because of the limits alone
@@ -276,15 +260,13 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
 #pragma unroll
         for (int k = 0; k < SNT; k++) {
             const v4u cur = a[k % D];
-            if (MVX_SPEC_ABL != 4 && k + D < SNT) a[k % D] = src_piece(k + D);
-            if (MVX_SPEC_ABL != 6) {
-                if (k < SNA) aL = F::template sad_regs<COLB>(cur, T.r[k % SW], aL);
-                else aC = F::template sad_regs<COLB>(cur, T.r[k % SW], aC);
-            } else { aL += cur[0] + T.r[k % SW][0]; }
+            if (k + D < SNT) a[k % D] = src_piece(k + D);
+            if (k < SNA) aL = F::template sad_regs<COLB>(cur, T.r[k % SW], aL);
+            else aC = F::template sad_regs<COLB>(cur, T.r[k % SW], aC);
             asm volatile("" : "+v"(aL), "+v"(aC) : : "memory");
             const int kk = k + SW;
             if (kk == SNT) { T.curA = nA; T.curB = nB; }
-            if (MVX_SPEC_ABL != 5 && (REFILL || kk < SNT)) T.r[k % SW] = strip_issue(T, kk % SNT);
+            if (REFILL || kk < SNT) T.r[k % SW] = strip_issue(T, kk % SNT);
         }
         T.aL = aL; T.aC = aC;
     }
@@ -292,11 +274,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
     // and the SAD of block m is the sum of the dword sums m and m + 1.  A window is 15 blocks = 16 dwords = FOUR lanes per candidate in strip form
     // (16 candidates per pass: the whole Hex2 pattern in one); in block form a lane is one (candidate, block) and uses the first two dwords of its
     // load.  12 rows per pass (8 luma + 4 of the UV plane), all in flight; the window's source strip is 12 rows x 64 B in LDS.
-    #ifndef MVX_NO_STRIP8
     static constexpr bool STRIP8_OK = UV && BPS == 1 && BW == 8;
-#else
-    static constexpr bool STRIP8_OK = false;
-#endif
     static constexpr int W8_BLOCKS = 15, R8A = 8, R8B = 4, R8T = R8A + R8B;
     struct Strip8 { v4u r[R8T]; unsigned curA, curB; unsigned aL[4], aC[4]; };
     __device__ __forceinline__ v4u strip8_issue(Strip8 &T, int piece) const { // (byte-aligned 16-byte loads: 8-bit samples sit anywhere)
@@ -721,7 +699,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                     // global_load_lds_dwordx4 puts it: the strip never passes through registers (twelve fewer live across the passes, no ds_write).  Two buffers: the next
                                     // window's strip arrives while this window's passes read theirs.  A strip is requested BEFORE the 24 row loads that follow it (the prime, or a pass's
                                     // refills), so "all but the 24 newest loads have returned" (vmcnt is in order) means it is there
-                                    constexpr bool SDMA = MVX_STRIP_DMA && COLB == 16 && HC == 1 && SW == 24 && SNT == 24;
+                                    constexpr bool SDMA = COLB == 16 && HC == 1 && SW == 24 && SNT == 24;
                                     constexpr int SBUF = SNT * ROWB; // bytes of one strip buffer (the host sizes the chain's LDS for two)
                                     int sbuf = 0;                    // the buffer of the window whose passes run
                                     A4x32 stg[SDMA ? 1 : SSTG]; // (rows gS, gS + 8, ...: the luma rows first, then the rows of the UV plane)
@@ -800,21 +778,13 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                     run_stage(1, 0, nw);
                                     a2_pred(pBest, pX_, pY_, pSad); // the predictor phase of every block of the group
                                     pkW = pk(pX_, pY_);
-#if MVX_SPEC_ABL == 9
-                                    if (SPECDBG_HERE() && act) { // the predictor phase of this lane's block
-                                        int *o = g_specdbg + l * SPECDBG_N;
-                                        const int sUp = hexLevel ? 14 : 24, sZ = hexLevel ? 16 : 26;
-                                        o[0] = pkU; o[1] = pkAh; o[2] = pkG; o[3] = pkH; o[4] = pkW; o[5] = pBest;
-                                        o[6] = tot(rd(sUp)); o[7] = tot(rd(sUp + 1)); o[8] = tot(rd(sZ)); o[9] = tot(rd(sZ + 1)); o[10] = tot(rd(sZ + 2)); o[11] = lam;
-                                    }
-#endif
                                     { // windows whose blocks share the centre and keep the whole pattern inside their limits
                                         const bool ok2 = (pX_ - 2 >= dxMin) & (pX_ + 2 <= dxMax1) & (pY_ - 2 >= nDyMin) & (pY_ + 2 < nDyMax);
                                         for (int w = 0; w < nw; w++) {
                                             const int f = lo + SWB * w, e = min(f + SWB, hiE);
                                             const bool inw = (l >= f) & (l < e);
                                             const int w0 = __builtin_amdgcn_readlane(pkW, f);
-                                            if (MVX_SPEC_ABL != 7 && e - f >= 2 && __ballot(inw & ((pkW != w0) | !ok2)) == 0) stripW |= 1u << w; // (ABL 7: block form only)
+                                            if (e - f >= 2 && __ballot(inw & ((pkW != w0) | !ok2)) == 0) stripW |= 1u << w;
 #ifdef MVX_SPEC_STATS
                                             if ((stripW >> w) & 1) st4 += 1;
                                             else { st5 += 1; st6 += __builtin_popcountll(__ballot(inw & (pkW != w0))); if (__ballot(inw & (pkW != w0)) == 0) st7 += 1; }
@@ -1134,7 +1104,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                     { // hexagon + square around up, up itself, ahead: 16 candidates, 4 lanes each
                                         const int g = l >> 2, s = l & 3;
                                         const int base = g == 15 ? sAh : sU;
-                                        const int vx = upx(base) + (MVX_SPEC_ABL == 2 ? 0 : rdx), vy = upy(base) + (MVX_SPEC_ABL == 2 ? 0 : rdy);
+                                        const int vx = upx(base) + rdx, vy = upy(base) + rdy;
                                         const bool ok = vok(vx, vy) & ((g >= 6) | (nSearchParam > 1));
                                         unsigned aL = 0, aC = 0;
                                         if (ok) this->template eval<2>(s, vx, vy, vy, aL, aC);
@@ -1147,7 +1117,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                         const int vx = upx(base), vy = upy(base);
                                         const int vyc = g == 0 ? 0 : vy; // the zero candidate's chroma ignores fieldShift (:836-839)
                                         unsigned aL = 0, aC = 0;
-                                        if (g < (MVX_SPEC_ABL == 1 ? 0 : 3)) this->template eval<4>(s, vx, vy, vyc, aL, aC);
+                                        if (g < 3) this->template eval<4>(s, vx, vy, vyc, aL, aC);
                                         group_sum2<4>(aL, aC);
                                         if ((s == 0) & (g < 3)) *(LDS_AS v2u *)(tab + (16 + g) * SPEC_STRIDE + ti8) = v2u{aL, aC};
                                     }
@@ -1177,7 +1147,6 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                 live = a2_refine(ux, uy, best, bx, by, bs) || live;
                             } else {
                                 live = a2_refine(pX_, pY_, best, bx, by, bs);
-                                if (MVX_SPEC_ABL == 8) live = live || !(pX_ == ux && pY_ == uy); // (debug: accept only blocks whose centre is up)
                             }
                             // TEAM: everything above was independent of the walk; from here on the group needs the walk's state behind its left neighbour
                             if constexpr (TEAM) { SPROF(4); team_acquire(myG, prevX, prevY, prevSad); teamHeld = true; SPROF(17); }
@@ -1192,10 +1161,6 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                             const bool rowStart = c == (fwd ? 0 : nBlkX - 1); // (no left neighbour: predictors[1] is the zero vector, :421-426)
                             flagmask = __ballot(act && !live && !rowStart);
                             okmask = flagmask & __ballot(hyp);
-                            if (MVX_SPEC_ABL == 3) okmask = flagmask = __ballot(act);
-#if MVX_SPEC_ABL == 9
-                            if (SPECDBG_HERE() && act) { int *o = g_specdbg + l * SPECDBG_N; o[12] = rX; o[13] = rY; o[14] = rSad; o[15] = (int)((flagmask >> l) & 1) | ((int)((okmask >> l) & 1) << 1) | (staged2 ? 4 : 0) | (live ? 8 : 0); o[16] = pk(prevX, prevY); o[17] = best; }
-#endif
                         }
                     }
 
@@ -1214,9 +1179,6 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                             bOut[0] = mine ? (unsigned)rX : bOut[0]; bOut[1] = mine ? (unsigned)rY : bOut[1]; bOut[2] = mine ? (unsigned)rSad : bOut[2];
                             const int last = fwd ? a + run - 1 : a;
                             prevX = __builtin_amdgcn_readlane(rX, last); prevY = __builtin_amdgcn_readlane(rY, last); prevSad = __builtin_amdgcn_readlane(rSad, last);
-#if MVX_SPEC_ABL == 9
-                            if (SPECDBG_HERE() && mine) g_specdbg[l * SPECDBG_N + 18] = 1;
-#endif
                             pos += dir * run;
 #ifdef MVX_SPEC_STATS
                             st0 += run;
@@ -1260,9 +1222,6 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                     const bool mine = l == li;
                                     bOut[0] = mine ? (unsigned)rX : bOut[0]; bOut[1] = mine ? (unsigned)rY : bOut[1]; bOut[2] = mine ? (unsigned)rSad : bOut[2];
                                     prevX = __builtin_amdgcn_readlane(rX, li); prevY = __builtin_amdgcn_readlane(rY, li); prevSad = __builtin_amdgcn_readlane(rSad, li);
-#if MVX_SPEC_ABL == 9
-                                    if (SPECDBG_HERE() && l == 0) { int *o = g_specdbg + li * SPECDBG_N; o[18] = 2; o[19] = pk(Lx, Ly); o[20] = pk(Mx, My); o[21] = fL | (fM << 8); o[22] = best; o[23] = pk(wx, wy); }
-#endif
 #ifdef MVX_SPEC_STATS
                                     st0 += 1; st3 += 1;
 #endif
@@ -1317,9 +1276,6 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                             __builtin_amdgcn_wave_barrier();
                             { const bool mine = l == li; bOut[0] = mine ? (unsigned)bestX : bOut[0]; bOut[1] = mine ? (unsigned)bestY : bOut[1]; bOut[2] = mine ? (unsigned)bestSad : bOut[2]; }
                             prevX = bestX; prevY = bestY; prevSad = bestSad;
-#if MVX_SPEC_ABL == 9
-                            if (SPECDBG_HERE() && l == 0) { int *o = g_specdbg + li * SPECDBG_N; o[18] = 3; o[19] = pk(pX[1], pY[1]); o[20] = pk(pX[0], pY[0]); o[22] = bestSad; o[23] = pk(bestX, bestY); }
-#endif
 #ifdef MVX_SPEC_STATS
                             if (specRow) { st0 += 1; st1 += 1; st2 += !((flagmask >> li) & 1); }
 #endif
@@ -1392,7 +1348,7 @@ __global__ __launch_bounds__(64 * MAXCPW, WPE) void analyse_spec_kernel(const AP
     const int chain = uni(TEAM ? wg : wg * cpw + wave);
     if (chain >= njobs) return; // (a finished wave no longer counts for the workgroup's barriers)
     const AJob &J = jobs[chain];
-    if (!J.blob) return;        // padding entry of the job table
+    if (!J.blob) return;        // (a job without a blob)
     const int l = lane_id();
     int *hdr = (int *)J.blob;
     if (TEAM && wave != 0 && !J.valid) return;
@@ -1409,7 +1365,7 @@ __global__ __launch_bounds__(64 * MAXCPW, WPE) void analyse_spec_kernel(const AP
         return;
     }
     if (l == 0 && (!TEAM || wave == 0)) { hdr[0] = P.blobSize; hdr[1] = 1; } // GroupOfPlanes.c:77-85
-    SpecSearcher<BPS, BW, UV, (WPE <= 2 ? 24 : MVX_SPEC_SW3), TEAM, SIDE> S(P, J);
+    SpecSearcher<BPS, BW, UV, (WPE <= 2 ? 24 : SPEC_SW3), TEAM, SIDE> S(P, J);
     S.lds = (lds_u8 *)smem + (TEAM ? ldsRow : 0) + wave * ldsChain;
     S.ldsRow = ldsRow; S.ldsHist = ldsHist; S.histBins = histBins; S.ldsTab = ldsTab;
     S.role = wave; S.nw = uni((int)(blockDim.x >> 6)); S.ctl = (LDS_AS int *)((lds_u8 *)smem); S.shRow = (lds_u8 *)smem + 64;
@@ -1437,10 +1393,6 @@ extern "C" __attribute__((visibility("default"))) int mvx_debug_specprof(unsigne
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_specprof), sizeof(unsigned long long) * SPROF_N) == hipSuccess ? 0 : -1;
 }
 #endif
-#if MVX_SPEC_ABL == 9 && defined(MVX_PROF_EXPORT)
-extern "C" __attribute__((visibility("default"))) int mvx_debug_specdbg(int *out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_specdbg), sizeof(int) * 64 * SPECDBG_N) == hipSuccess ? 0 : -1; }
-extern "C" __attribute__((visibility("default"))) int mvx_debug_specdbg_at(int lvl, int blky, int c0) { const int v[3] = { lvl, blky, c0 }; return hipMemcpyToSymbol(HIP_SYMBOL(g_specdbgAt), v, sizeof(v)) == hipSuccess ? 0 : -1; }
-#endif
 #if defined(MVX_SPEC_STATS) && defined(MVX_PROF_EXPORT)
 extern "C" __attribute__((visibility("default"))) int mvx_debug_specstats(unsigned long long *out, int reset) {
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_specstat), sizeof(unsigned long long) * MVX_MAX_LEVELS * 8) != hipSuccess) return -1;
@@ -1450,14 +1402,13 @@ extern "C" __attribute__((visibility("default"))) int mvx_debug_specstats(unsign
 #endif
 
 // L.ldsRow = offset of the row buffer (8 bytes per block), L.ldsHist = offset of the histogram (lies over row buffer and table: it is
-// only used between levels), L.ldsBytes = offset of the table when L.ldsNeed carries the chain's total
+// only used between levels), L.ldsNeed = the chain's total
 struct ASpecLaunch { ALaunch L; int ldsTab; int team; int side; }; // side: 16x16 blocks side by side (overlap 0): the SIDE builds // team: 0 = one wave per chain, n = the workgroup's n waves walk one chain
 template <int BPS, int BW, int WPE, int MAXCPW, bool UV, bool SIDE = false> static int launch_analyse_spec_uv(const ASpecLaunch &S) {
     const ALaunch &L = S.L;
     const int perChain = (L.ldsNeed + 255) & ~255;
     const int cpw = L.cpw < MAXCPW ? L.cpw : MAXCPW;
-    int lds = perChain * cpw;
-    if (L.ldsBytes > lds && L.ldsBytes <= 160 * 1024) lds = L.ldsBytes; // developer / host option: fewer workgroups per CU
+    const int lds = perChain * cpw;
     if (lds > 64 * 1024)
         HIP_CHECK(hipFuncSetAttribute((const void *)analyse_spec_kernel<BPS, BW, WPE, MAXCPW, UV, false, SIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     hipLaunchKernelGGL((analyse_spec_kernel<BPS, BW, WPE, MAXCPW, UV, false, SIDE>), dim3((L.njobs + cpw - 1) / cpw), dim3(64 * cpw), lds, L.st, L.dP, L.dJobs,
@@ -1474,8 +1425,7 @@ template <int BPS, int BW, int WPE, int MAXCPW, bool UV, bool SIDE = false> stat
     const ALaunch &L = S.L;
     const int nw = S.team < MAXCPW ? S.team : MAXCPW;
     const int perWave = (L.ldsNeed + 255) & ~255;
-    int lds = L.ldsRow + perWave * nw;
-    if (L.ldsBytes > lds && L.ldsBytes <= 160 * 1024) lds = L.ldsBytes;
+    const int lds = L.ldsRow + perWave * nw;
     if (lds > 64 * 1024)
         HIP_CHECK(hipFuncSetAttribute((const void *)analyse_spec_kernel<BPS, BW, WPE, MAXCPW, UV, true, SIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     hipLaunchKernelGGL((analyse_spec_kernel<BPS, BW, WPE, MAXCPW, UV, true, SIDE>), dim3(L.njobs), dim3(64 * nw), lds, L.st, L.dP, L.dJobs,

@@ -26,9 +26,6 @@ int mvx_analyse_launch_fast_u16(const AParams &P, const ALaunch &L) {
 int mvx_analyse_launch_u16(const AParams &P, const ALaunch &L) {
     if (P.xr != 2 || P.yr != 2) return 1;
     if (L.cpw >= 4) { // several chains per workgroup (mvx_analyse_frames sorted the job table by reference frame)
-        if (L.wpe == 3 && L.cpw == 12) { // three per SIMD, twelve per CU
-            if (P.blkX == 16 && P.blkY == 16) return launch_analyse_kernel<2, Geo<16, 16, 2, 2>, 3, 12>(L);
-        }
         if (L.wpe == 2 && L.cpw == 8) { // two per SIMD, eight per CU
             if (P.blkX == 16 && P.blkY == 16) return launch_analyse_kernel<2, Geo<16, 16, 2, 2>, 2, 8>(L);
             if (P.blkX == 8 && P.blkY == 8) return launch_analyse_kernel<2, Geo<8, 8, 2, 2>, 2, 8>(L);

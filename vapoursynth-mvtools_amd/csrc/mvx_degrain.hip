@@ -159,11 +159,9 @@ __device__ __forceinline__ unsigned sup_offset(const PlaneG &g, int pel, int log
 
 // (r6: left alone the register allocator takes 162 registers for six references -- three waves per SIMD; asked for six it needs 71 and spills nothing:
 // 4.41 -> 2.78 ms per 341 4K16 frames, profiles/r6_degrain_window_plan_ab.txt)
-#ifndef MVX_DG_PLAN_WAVES
-#define MVX_DG_PLAN_WAVES(NR) ((NR) <= 6 ? 6 : 4)
-#endif
+constexpr int dg_plan_waves(int nr) { return nr <= 6 ? 6 : 4; }
 template <int NR>
-__global__ __launch_bounds__(256, MVX_DG_PLAN_WAVES(NR)) void degrain_plan_kernel(const DGParams *Pp, const DGJob *jobs, const int *usable, PlanRecT<NR> *plan) {
+__global__ __launch_bounds__(256, dg_plan_waves(NR)) void degrain_plan_kernel(const DGParams *Pp, const DGJob *jobs, const int *usable, PlanRecT<NR> *plan) {
     typedef PlanRecT<NR> PlanRec;
     const DGParams &P = *Pp;
     const int f = blockIdx.y;
@@ -382,32 +380,21 @@ template <typename T, int W> __device__ __forceinline__ void dg_store(DG_GL unsi
     else *(DG_GL dg_uh1 *)p = (unsigned short)d[0];
 }
 
-#ifndef MVX_DG_TILE
-#define MVX_DG_TILE 1 // (developer A/B builds: 0 = every thread reads its plan records from global memory, the form of rounds 2-5)
-#endif
 #define DG_TILE_MAX (34 * 6) // plan records of a workgroup's tile (32 cells x 8 rows): 33 block columns x at most 6 block rows (2-sample cell rows: five)
 // blocks of blkW x blkH stepping by stepX x stepY: the records that cover 32 cells x 8 rows fit the tile (always, for the geometries the cell kernel is launched on:
 // a power-of-two step below the block size is half the block size)
 constexpr bool dg_tiled(int nrefs) { return nrefs >= 6; }
 static bool dg_tile_fits(int blkW, int blkH, int stepX, int stepY) { return (31 + (blkW + stepX - 1) / stepX) * (7 / stepY + (blkH + stepY - 1) / stepY + 1) <= DG_TILE_MAX; }
-#ifndef MVX_DG_W4_NR6_WAVES
-#define MVX_DG_W4_NR6_WAVES 7 // (eight needs six spilled registers with the tile: 12.1 against 9.8 ms per 341 4K16 chroma frame pairs, profiles/r6_degrain_tile_ab.txt)
-#endif
-template <int NR, int W> constexpr int dg_cell_waves() { return W <= 2 ? 7 : W == 4 ? (NR <= 4 ? 8 : NR <= 6 ? MVX_DG_W4_NR6_WAVES : 6) : W == 8 ? (NR <= 2 ? 6 : NR <= 6 ? 5 : 4) : (NR <= 8 ? 3 : 2); }
+// (4-sample cells, six references: seven waves -- eight needs six spilled registers with the tile: 12.1 against 9.8 ms per 341 4K16 chroma frame pairs,
+// profiles/r6_degrain_tile_ab.txt)
+template <int NR, int W> constexpr int dg_cell_waves() { return W <= 2 ? 7 : W == 4 ? (NR <= 4 ? 8 : NR <= 6 ? 7 : 6) : W == 8 ? (NR <= 2 ? 6 : NR <= 6 ? 5 : 4) : (NR <= 8 ? 3 : 2); }
 template <typename T, int NR, int W>
-__global__ __launch_bounds__(256, (dg_cell_waves<NR, W>())) void degrain_cell_kernel(const DGParams *Pp, const DGJob *jobs, const PlanRecT<NR> *plan, int planeFirst, int planesPerFrame, int xcdOrder) {
+__global__ __launch_bounds__(256, (dg_cell_waves<NR, W>())) void degrain_cell_kernel(const DGParams *Pp, const DGJob *jobs, const PlanRecT<NR> *plan, int planeFirst, int planesPerFrame) {
     typedef PlanRecT<NR> PlanRec;
     const DGParams &P = *Pp;
-    int bxi = blockIdx.x, byi = blockIdx.y, z = blockIdx.z;
-    if (xcdOrder) { // workgroup w runs on XCD w % 8: give every XCD a contiguous range of tiles, so that vertically adjacent tiles (which
-        // read the same reference rows) meet in one L2 instead of fetching those rows from HBM once per XCD
-        const unsigned gx = gridDim.x, gy = gridDim.y, n = gx * gy * gridDim.z;
-        const unsigned w = bxi + gx * (byi + gy * z), x8 = w & 7, slot = w >> 3;
-        const unsigned nl = x8 * (n >> 3) + min(x8, n & 7) + slot;
-        z = nl / (gx * gy);
-        const unsigned rem = nl - z * (gx * gy);
-        byi = rem / gx; bxi = rem - byi * gx;
-    }
+    const int bxi = blockIdx.x, byi = blockIdx.y, z = blockIdx.z;
+    // (an XCD-contiguous tile order, measured r2 on 4K16 Degrain3, 512 frames: HBM fetch 124 -> 88 GB (luma) and 75 -> 34 GB (chroma), but the
+    // launch gets 8 ms SLOWER -- 189 against 181 ms for everything but the search: the kernel is not HBM-bound)
     const int f = z / planesPerFrame, p = planeFirst + z % planesPerFrame;
     const PlaneG &g = P.pl[p];
     const int c = bxi * 32 + (threadIdx.x & 31), y = byi * 8 + (threadIdx.x >> 5);
@@ -419,7 +406,7 @@ __global__ __launch_bounds__(256, (dg_cell_waves<NR, W>())) void degrain_cell_ke
     // Measured (profiles/r6_degrain_tile_ab.txt, ms per batch, every thread for itself -> tile): six 16-bit references 15.9 -> 14.3 (8-sample cells) and 12.8 -> 9.8
     // (4-sample cells), twelve 47.2 -> 43.0 / 29.2 -> 25.2; TWO 8-bit references (16-byte records, two loads per visit) lose: 15.5 -> 16.6, 12.7 -> 15.6 -- the tile is
     // for filters with six or more references (Degrain3-6)
-    constexpr bool TILED = MVX_DG_TILE && dg_tiled(NR);
+    constexpr bool TILED = dg_tiled(NR);
     constexpr int RD = (int)sizeof(PlanRec) / 4;
     __shared__ __attribute__((aligned(16))) unsigned tileD[TILED ? DG_TILE_MAX * RD : 1];
     int tBx = 0, tBy = 0, tNbx = 0; // (wave-uniform: scalar registers)
@@ -846,7 +833,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_set_ref_shadow
     // (plan records hold 32-bit byte offsets into a super plane: the copy must lie inside that range)
     if (v && v + g0.supPlaneStride * d->P.pel * d->P.pel >= 0xffffffffLL) { mvx_set_error("mvx_degrain_set_ref_shadow: the shifted copy lies beyond 4 GiB of the plane"); return MVX_E_ARG; }
     std::lock_guard<std::mutex> lk(d->guard.mu);
-    d->P.pl[0].shadow = (d->P.bps == 2 && mvx_debug_value("degrain_shadow", 1)) ? v : 0;
+    d->P.pl[0].shadow = d->P.bps == 2 ? v : 0;
     if (d->dP) HIP_CHECK(hipMemcpy(d->dP, &d->P, sizeof(DGParams), hipMemcpyHostToDevice));
     return MVX_OK;
 }
@@ -858,10 +845,7 @@ template <typename T> static void launch_degrain(int nr, dim3 grid, hipStream_t 
 }
 
 template <typename T, int W> static void launch_degrain_cells_w(int nr, dim3 grid, hipStream_t st, const DGParams *dP, const DGJob *dJ, const void *plan, int p0, int npl) {
-    // XCD-contiguous tile order: measured r2 (4K16 Degrain3, 512 frames): HBM fetch 124 -> 88 GB (luma) and 75 -> 34 GB (chroma), but the
-    // launch gets 8 ms SLOWER (189 against 181 ms for everything but the search) -- the kernel is not HBM-bound.  Off.
-    const int xo = mvx_debug_value("degrain_xcd", 0);
-#define DGC(N) hipLaunchKernelGGL((degrain_cell_kernel<T, N, W>), grid, dim3(256), 0, st, dP, dJ, (const PlanRecT<N> *)plan, p0, npl, xo)
+#define DGC(N) hipLaunchKernelGGL((degrain_cell_kernel<T, N, W>), grid, dim3(256), 0, st, dP, dJ, (const PlanRecT<N> *)plan, p0, npl)
     switch (nr) { case 2: DGC(2); break; case 4: DGC(4); break; case 6: DGC(6); break; case 8: DGC(8); break; case 10: DGC(10); break; default: DGC(12); break; }
 #undef DGC
 }
@@ -903,7 +887,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_frames(mvx_deg
     // per-sample gather
     // (r5: blocks side by side take the cell kernel too -- a cell of 8 (4) samples inside one block)
     auto cellW = [&](int p) { const int w = P.pl[p].stepX; return P.overlap ? ((w == 2 || w == 4 || w == 8 || w == 16) ? w : 0) : (P.pl[p].blkW % 8 == 0 ? 8 : P.pl[p].blkW % 4 == 0 ? 4 : 0); };
-    auto tileOk = [&](int p) { return !MVX_DG_TILE || !dg_tiled(P.nRefs) || !P.overlap || dg_tile_fits(P.pl[p].blkW, P.pl[p].blkH, P.pl[p].stepX, P.pl[p].stepY); };
+    auto tileOk = [&](int p) { return !dg_tiled(P.nRefs) || !P.overlap || dg_tile_fits(P.pl[p].blkW, P.pl[p].blkH, P.pl[p].stepX, P.pl[p].stepY); };
     const bool cells = cellW(0) && tileOk(0) && (P.nplanes == 1 || (cellW(1) && P.pl[1].stepX == P.pl[2].stepX && tileOk(1) && tileOk(2)));
     if (cells) {
         for (int cls = 0; cls < (P.nplanes > 1 ? 2 : 1); cls++) {

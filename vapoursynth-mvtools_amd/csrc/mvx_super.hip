@@ -430,25 +430,16 @@ static int super_frames_impl(mvx_super *s, int nframes, const void *const *src, 
 // buffer shifted left by 1 .. n samples (copy k, byte i = plane byte i + k * bps).  A block at a sample position x with
 // x % (4 / bps) == k is then read from copy k at x - k: same samples, dword-aligned address.  mvx_analyse_set_ref_shadow tells
 // a search where the copies are.
-struct ShadowArgs { void *const *planes; long long size[3], stride[3], begin[3]; int nplanes, bps, copies8; };
+struct ShadowArgs { void *const *planes; long long size[3], stride[3], begin[3]; int nplanes, bps; };
 // blockIdx.y = frame * 2 + kind; kind 0: the luma plane shifted left by one sample; kind 1: U and V interleaved sample by sample
 __global__ __launch_bounds__(256) void super_shadow_kernel(ShadowArgs A) {
     const int f = blockIdx.y >> 1, kind = blockIdx.y & 1;
     const long long i = A.begin[kind] + ((long long)blockIdx.x * 256 + threadIdx.x) * 16; // begin: bytes before it were written by the Super kernels themselves
     if (kind == 0) {
-        if ((A.bps == 1 && !A.copies8) || i >= A.size[0]) return; // (8-bit clips keep no shifted luma copy, unless "shadow8" asks for the three)
+        if (A.bps == 1 || i >= A.size[0]) return; // (8-bit clips keep no shifted luma copy)
         unsigned char *base = (unsigned char *)A.planes[f * 3];
         const uint4 a = *(const uint4 *)(base + i);
         const unsigned b = i + 16 < A.size[0] ? *(const unsigned *)(base + i + 16) : 0u;
-        if (A.bps == 1) { // copy k = the plane shifted left by k bytes
-            for (unsigned k = 1; k < 4; k++) {
-                uint4 o;
-                o.x = __builtin_amdgcn_alignbit(a.y, a.x, 8 * k); o.y = __builtin_amdgcn_alignbit(a.z, a.y, 8 * k);
-                o.z = __builtin_amdgcn_alignbit(a.w, a.z, 8 * k); o.w = __builtin_amdgcn_alignbit(b, a.w, 8 * k);
-                *(uint4 *)(base + (long long)k * A.stride[0] + i) = o;
-            }
-            return;
-        }
         const unsigned sh = 8u * A.bps;
         uint4 o;
         o.x = __builtin_amdgcn_alignbit(a.y, a.x, sh); o.y = __builtin_amdgcn_alignbit(a.z, a.y, sh);
@@ -476,7 +467,7 @@ __global__ __launch_bounds__(256) void super_shadow_kernel(ShadowArgs A) {
 }
 // 16-bit clips: shadows exist (1).  8-bit clips: none (0) -- measured (r2, 1080p Degrain1): shifted copies of an 8-bit plane (three are
 // needed) quadruple the cache footprint of every chain and cost more than the aligned loads save (1250-1340 fps with copies, 2005
-// without); the search then simply loads from the planes themselves.
+// without); the search then simply loads from the planes themselves.  Measured again r6 (cfg2): the search -12 %, but the whole step +5.6 %.
 // r3: 8-bit 4:2:x clips get the UV-interleaved plane too (U and V of a chroma block in ONE row of twice the width: half the load
 // instructions and cache lines per candidate), still no luma copy.
 extern "C" __attribute__((visibility("default"))) int mvx_super_shadow_copies(const mvx_super *s) { return s->info.bits <= 8 ? (s->info.num_planes >= 3 ? 1 : 0) : 1; }
@@ -486,11 +477,10 @@ extern "C" __attribute__((visibility("default"))) void mvx_super_shadow_bytes(co
     extra[0] = extra[1] = extra[2] = 0;
     if (!mvx_super_shadow_copies(s)) return;
     if (s->info.bits > 8) extra[0] = (size_t)s->info.plane_height[0] * pitch[0];
-    else if (mvx_debug_value("shadow8", 0)) extra[0] = 3 * (((size_t)s->info.plane_height[0] * pitch[0] + 255) & ~(size_t)255); // (three copies, each at a multiple of the 256-byte rounded plane size)
     if (s->info.num_planes >= 3) extra[1] = 2 * (size_t)s->info.plane_height[1] * pitch[1];
 }
 static int shadow_check(const mvx_super_info &si, const ptrdiff_t pitch[3], const ptrdiff_t copy_stride[3]) {
-    for (int p = (si.bits > 8 || mvx_debug_value("shadow8", 0)) ? 0 : 1; p < si.num_planes && p < 2; p++) {
+    for (int p = si.bits > 8 ? 0 : 1; p < si.num_planes && p < 2; p++) {
         const long long size = (long long)si.plane_height[p] * pitch[p];
         if (pitch[p] % 16 || copy_stride[p] % 16 || copy_stride[p] < size) { mvx_set_error("mvx_super_shadow_frames: pitch and shadow offset must be multiples of 16 bytes, the offset at least one plane"); return MVX_E_ARG; }
     }
@@ -502,9 +492,9 @@ static int shadow_launch(const mvx_super_info &si, int nframes, void *const *dpl
                          const long long begin[2], hipStream_t st) {
     ShadowArgs A;
     memset(&A, 0, sizeof(A));
-    A.nplanes = si.num_planes; A.bps = si.bits > 8 ? 2 : 1; A.planes = dplanes; A.copies8 = A.bps == 1 && mvx_debug_value("shadow8", 0);
+    A.nplanes = si.num_planes; A.bps = si.bits > 8 ? 2 : 1; A.planes = dplanes;
     long long maxsize = 0;
-    for (int p = (A.bps == 1 && !A.copies8) ? 1 : 0; p < si.num_planes && p < 2; p++) {
+    for (int p = A.bps == 1 ? 1 : 0; p < si.num_planes && p < 2; p++) {
         A.size[p] = (long long)si.plane_height[p] * pitch[p]; A.stride[p] = copy_stride[p]; A.begin[p] = begin[p];
         if (A.size[p] - begin[p] > maxsize) maxsize = A.size[p] - begin[p];
     }
@@ -600,7 +590,7 @@ static int super_frames_impl(mvx_super *s, int nframes, const void *const *src, 
     const int l0pel = pelMode ? 1 : si.pel;
     // pel 2: the columns whose filter window lies inside the source row go to super_rows_kernel (mvx_super_rows.h), which also writes
     // the shadow data of level 0; it loads dword-aligned vectors, so the source rows and the left padding must keep that alignment
-    bool rows = l0pel == 2 && !mvx_debug_value("super_rows_off", 0);
+    bool rows = l0pel == 2;
     const int bps = u8 ? 1 : 2, NS = 16 / bps;
     for (int p = 0; rows && p < si.num_planes; p++) {
         if ((A.g[p].hpad * bps) % 4 || src_pitch[p] % 4) rows = false;
@@ -714,7 +704,7 @@ static int super_frames_impl(mvx_super *s, int nframes, const void *const *src, 
             SuperReduceRowsArgs Q;
             memset(&Q, 0, sizeof(Q));
             Q.src = R.src; Q.dst = R.dst; Q.modeYUV = R.modeYUV; Q.nplanes = R.nplanes;
-            bool ok = !mvx_debug_value("super_rows_off", 0);
+            bool ok = true;
             int qw = 0, qh = 0;
             for (int p = 0; ok && p < si.num_planes; p++) {
                 Q.src_pitch[p] = R.src_pitch[p]; Q.dst_pitch[p] = R.dst_pitch[p]; Q.in_off[p] = R.in_off[p]; Q.out_off[p] = R.out_off[p];

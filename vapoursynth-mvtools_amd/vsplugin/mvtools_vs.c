@@ -1402,11 +1402,6 @@ static void VS_CC analyseCreate(const VSMap *in, VSMap *out, void *user, VSCore 
     d->blobSize = mvx_analyse_blob_size(d->an);
     if (d->geo.copies > 1) mvx_analyse_set_ref_shadow(d->an, d->geo.shadowStride); /* every device super frame of this shell carries its copies */
     combiner_init(&d->cb);
-    { /* MVX_VS_SEARCH_LDS=<bytes>: LDS floor of a search workgroup (four chains): 54000 caps a CU at eight chains = two per SIMD, so that the
-       * per-frame kernels of the other request threads (Super, Degrain) find registers beside the long-running low-priority search waves */
-        const long f = env_long("MVX_VS_SEARCH_LDS", 0);
-        if (f > 0) mvx_debug_option("fast_lds_min", (int)f);
-    }
     /* before the first launch has been timed: a chain walks every block of every level, a few microseconds each */
     d->cb.lastUs = (long)((double)d->ad.nBlkX * d->ad.nBlkY * 4.0 / 3.0 * 2.5);
     VSFilterDependency deps[2] = { { node, rpGeneral }, { NULL, rpGeneral } };
