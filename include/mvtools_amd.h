@@ -286,6 +286,68 @@ typedef struct mvx_blockfps_job {
 
 int mvx_blockfps_frames(mvx_blockfps *b, int nframes, const mvx_blockfps_job *jobs, void *stream);
 
+/* ---- mv.FlowInter / mv.FlowFPS -------------------------------------------------------------------
+ * per-sample ("flow") interpolation between two frames; both filters share one handle type and one engine.
+ * mvx_flowinter_create replaces mvflowinterCreate, MVFlowInter.c:473-678 (arg string :697-710);
+ * mvx_flowfps_create replaces mvflowfpsCreate, MVFlowFPS.c:565-878 (arg string :889-903);
+ * mvx_flow_frames replaces mvflowinterGetFrame / mvflowfpsGetFrame + FlowFPSHelper, MVFlowInter.c:80-452,
+ * MVFlowFPS.c:86-524, MVFlowFPSHelper.c:49-93; masks and fields MaskFun.cpp:38-203, formulas MaskFun.cpp:349-555,
+ * upsizers SimpleResize.cpp:27-121.  The super clip is read directly: no mv.Finest frame is needed.
+ * Deliberate divergences: FlowFPS rejects vectors with absolute frame references (delta <= 0), which the reference
+ * accepts and then reads negative frame numbers with; both reject frames less than two blocks wide or high, where the
+ * reference's upsizer reads outside its buffers. */
+
+typedef struct mvx_flowinter_args {
+    double time;             /* percent of the way from frame n to n + delta, 0..100 (a float argument in the reference); pass 50.0 for the default */
+    double ml;               /* mask scale (a float argument in the reference); pass 100.0 for the default */
+    int32_t blend;           /* MVX_UNSET -> 1 */
+    int64_t thscd1; int32_t thscd2;
+} mvx_flowinter_args;
+
+typedef struct mvx_flowfps_args {
+    int64_t num, den;        /* MVX_UNSET -> 25 / 1; 0 -> double the input rate */
+    int32_t mask;            /* 0..2, MVX_UNSET -> 2 */
+    double ml;               /* pass 100.0 for the default */
+    int32_t blend;           /* MVX_UNSET -> 1 */
+    int64_t thscd1; int32_t thscd2;
+} mvx_flowfps_args;
+
+typedef struct mvx_flow_info { int32_t num_frames; int64_t fps_num, fps_den; } mvx_flow_info; /* of the output clip; FlowInter: 0 / 0 = the input's rate */
+
+typedef struct mvx_flow mvx_flow;
+
+int mvx_flowinter_create(const mvx_flowinter_args *args, const mvx_analysis_data *mvbw, const mvx_analysis_data *mvfw,
+                         const mvx_super *super_clip, int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3],
+                         const ptrdiff_t dst_pitch[3], mvx_flow **out, char *err);
+/* fps_num / fps_den: frame rate of the input clip (the reference refuses clips without one) */
+int mvx_flowfps_create(const mvx_flowfps_args *args, const mvx_analysis_data *mvbw, const mvx_analysis_data *mvfw,
+                       const mvx_super *super_clip, int num_frames, int64_t fps_num, int64_t fps_den,
+                       const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3],
+                       mvx_flow **out, char *err);
+void mvx_flow_destroy(mvx_flow *h);
+void mvx_flow_get_info(const mvx_flow *h, mvx_flow_info *info);
+/* output frame n -> the two input frames it lies between and its time position: FlowInter (n, n + delta, time256),
+ * MVFlowInter.c:86-100; FlowFPS as BlockFPS, MVFlowFPS.c:92-99,125-134 */
+void mvx_flow_map(const mvx_flow *h, int n, int *nleft, int *nright, int *time256);
+
+typedef struct mvx_flow_job {
+    int32_t time256;             /* from mvx_flow_map; FlowFPS copies clip_left / clip_right at 0 / 256 (MVFlowFPS.c:138-142) */
+    int32_t reserved;
+    const void *super_left[3];   /* super frame nleft  } all four NULL when nright lies outside the clip (then, or when the */
+    const void *super_right[3];  /* super frame nright }   vectors are unusable: Blend of clip_left and clip_right when */
+    const void *blob_fw;         /* mvfw at nright     }   blend = 1, else clip_left, MVFlowInter.c:403-446) */
+    const void *blob_bw;         /* mvbw at nleft      } */
+    const void *blob_fw_extra;   /* mvfw at nleft  (NULL = unusable); read by FlowInter and FlowFPS mask = 2 only */
+    const void *blob_bw_extra;   /* mvbw at nright (NULL = unusable) */
+    const void *clip_left[3];    /* clip frame min(nleft, last)  */
+    const void *clip_right[3];   /* clip frame min(nright, last) */
+    void *dst[3];
+} mvx_flow_job;
+
+/* nframes jobs of one handle in one batch on `stream`: three small per-job kernels and a memset, then two gather launches that cover
+ * all jobs: one for the luma planes, one for both chroma planes (Gray: the luma launch only) */
+int mvx_flow_frames(mvx_flow *h, int nframes, const mvx_flow_job *jobs, void *stream);
+
 /* ---- mv.SCDetection -------------------------------------------------------------------------------
  * replaces the decision of mvscdetectionGetFrame, MVSCDetection.c:43-73 (arg string :137-145): scene_change[i] (HOST array) =
  * !usable(blobs[i]) for n device blobs of one vector clip, i.e. the value of _SceneChangePrev (forward vectors) or

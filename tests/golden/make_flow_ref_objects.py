@@ -1,0 +1,21 @@
+"""Writes tests/golden/flow_ref_objects.json: digests of the reference's AVX2 int16 vector resizer (SimpleResize_AVX2.cpp, from oracle/_ref)
+on the geometries tests/test_flow_ref.py uses, so that the test also runs where oracle/_ref is absent.
+
+    python tests/golden/make_flow_ref_objects.py
+"""
+import json
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path[:0] = [os.path.dirname(HERE), os.path.join(os.path.dirname(os.path.dirname(HERE)), "oracle")]
+
+import test_flow_ref as t  # noqa: E402
+
+if __name__ == "__main__":
+    lib = t.ref_lib()
+    assert lib is not None, "needs oracle/_ref (make -C oracle ref)"
+    out = [t.digest(t.ref_resize_i16(lib, *g)) for g in t.GEOMETRIES]
+    with open(os.path.join(HERE, "flow_ref_objects.json"), "w") as f:
+        json.dump({"simpleResize_int16_t_avx2": out}, f, indent=1)
+    print("wrote %d digests" % len(out))

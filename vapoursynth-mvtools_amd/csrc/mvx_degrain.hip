@@ -8,23 +8,10 @@
 //   plan kernel   : per (frame, block) -> per-reference weights (fp64 exactly as MVDegrains.h:184-223) and the byte
 //                   offset of the motion-compensated block inside the reference super frame (MVDegrains.h:192-206)
 //   gather kernel : per output sample  -> blend + window + normalise + uncovered strips + LimitChanges.
-#include "mvx_common.h"
+#include "mvx_fps_shared.h"
 
 #define MOTION_USE_CHROMA_MOTION 8
 
-struct __attribute__((packed, aligned(4))) GVecD { int x, y; long long sad; };
-
-// level-0 vectors of a MVTools_vectors blob: skip size + validity, then every coarser plane by ITS OWN size header -- the
-// reference's reader does exactly this, which is what makes clips produced with divide (an extra array of half-size
-// blocks after the finest estimated plane, whose geometry the level formula does not describe) readable
-// pointers that come out of job tables are generic ("flat") to the compiler: loads through them are slower and each is waited for on its own
-#define DG_GL __attribute__((address_space(1)))
-__device__ __forceinline__ DG_GL const unsigned char *dg_gl(const void *p) { return (DG_GL const unsigned char *)(unsigned long long)p; }
-__device__ __forceinline__ const GVecD *mvx_level0(const unsigned char *blob, int nLvCount) {
-    const unsigned char *p = blob + 8;
-    for (int i = nLvCount - 1; i >= 1; i--) p += *(const int *)p;
-    return (const GVecD *)(p + 4);
-}
 
 // ------------------------------------------------------------------------------------------------ host helpers
 
@@ -79,17 +66,6 @@ extern "C" __attribute__((visibility("default"))) void mvx_scale_thscd(int64_t *
 
 // ------------------------------------------------------------------------------------------------ shared device structs
 
-struct PlaneG { // one plane of the clip / of level 0 of the super frame
-    int W, H, WB, HB;        // frame dims, block-covered dims
-    int blkW, blkH, ovX, ovY, stepX, stepY;
-    int hpadPel, vpadPel;    // super padding * pel, in sub-pel units
-    int subX, subY;          // log2 subsampling of this plane relative to luma
-    long long srcPitch, supPitch, dstPitch, supPlaneStride; // bytes
-    int thIdx;               // 0 luma threshold, 1 chroma threshold
-    int process;
-    int limit;
-    long long shadow;        // 16-bit luma: byte distance to the copy of the super plane shifted left by one sample (mvx_degrain_set_ref_shadow), 0 = none
-};
 
 struct DGParams {
     int nRefs, nBlkX, nBlkY, nBlk, pel, logPel, bits, bps, nplanes, overlap;
@@ -149,13 +125,6 @@ __device__ __forceinline__ int degrain_weight(long long thSAD, long long blockSA
     return (int)((double)((thSAD - blockSAD) * (thSAD + blockSAD) * 256) / (double)(thSAD * thSAD + blockSAD * blockSAD));
 }
 
-// MVFrame.cpp:1686-1704,1732-1734 mvpGetPointer as a byte offset inside the super plane (level 0)
-__device__ __forceinline__ unsigned sup_offset(const PlaneG &g, int pel, int logPel, int bps, int nX, int nY) {
-    nX += g.hpadPel; nY += g.vpadPel;
-    const int m = pel - 1;
-    const int idx = (nX & m) | ((nY & m) << logPel);
-    return (unsigned)(idx * g.supPlaneStride + (long long)(nY >> logPel) * g.supPitch + (long long)(nX >> logPel) * bps);
-}
 
 // (r6: left alone the register allocator takes 162 registers for six references -- three waves per SIMD; asked for six it needs 71 and spills nothing:
 // 4.41 -> 2.78 ms per 341 4K16 frames, profiles/r6_degrain_window_plan_ab.txt)
@@ -284,28 +253,6 @@ __global__ __launch_bounds__(256) void degrain_kernel(const DGParams *Pp, const 
 // Same arithmetic per sample as degrain_kernel (Degrain_C + overlaps_c + ToPixels + LimitChanges).
 // Pointers that come out of the job tables are generic ("flat") to the compiler; flat loads are slower and every one of them is waited
 // for with vmcnt(0) lgkmcnt(0).  The vector helpers therefore take global-address-space pointers (dg_gl casts).
-__device__ __forceinline__ DG_GL unsigned char *dg_glw(void *p) { return (DG_GL unsigned char *)(unsigned long long)p; }
-typedef unsigned dg_uv4 __attribute__((ext_vector_type(4), aligned(1)));
-typedef unsigned dg_uv2 __attribute__((ext_vector_type(2), aligned(1)));
-typedef unsigned dg_uv1 __attribute__((aligned(1)));
-typedef unsigned short dg_uh1 __attribute__((aligned(1)));
-
-// W samples of type T from an arbitrarily aligned address, widened to int
-template <typename T, int W> __device__ __forceinline__ void dg_load(DG_GL const unsigned char *p, int *o) {
-    constexpr int BYTES = W * (int)sizeof(T);
-    unsigned d[(BYTES + 3) / 4];
-    if (BYTES >= 16) {
-#pragma unroll
-        for (int k = 0; k < BYTES / 16; k++) { dg_uv4 t = *(DG_GL const dg_uv4 *)(p + 16 * k); d[4 * k] = t[0]; d[4 * k + 1] = t[1]; d[4 * k + 2] = t[2]; d[4 * k + 3] = t[3]; }
-    } else if (BYTES == 8) { dg_uv2 t = *(DG_GL const dg_uv2 *)p; d[0] = t[0]; d[1] = t[1]; }
-    else if (BYTES == 4) d[0] = *(DG_GL const dg_uv1 *)p;
-    else d[0] = *(DG_GL const dg_uh1 *)p;
-#pragma unroll
-    for (int i = 0; i < W; i++) {
-        if (sizeof(T) == 2) o[i] = (int)((d[i >> 1] >> (16 * (i & 1))) & 0xffffu);
-        else o[i] = (int)((d[i >> 2] >> (8 * (i & 3))) & 0xffu);
-    }
-}
 // the same in two steps, so that several loads can be in flight before the first one is unpacked
 template <typename T, int W> struct DgRaw { unsigned d[(W * (int)sizeof(T) + 3) / 4]; };
 template <typename T, int W> __device__ __forceinline__ DgRaw<T, W> dg_load_raw(DG_GL const unsigned char *p) {
@@ -351,33 +298,6 @@ template <typename T, int NR, int W, typename REC> __device__ __forceinline__ vo
             for (int i = 0; i < W; i++) sum[i] += dg_sample<T, W>(raw[r], i) * w;
         }
     }
-}
-// N consecutive ints (dword-aligned address)
-typedef int dg_iv4 __attribute__((ext_vector_type(4), aligned(4)));
-typedef int dg_iv2 __attribute__((ext_vector_type(2), aligned(4)));
-template <int N> __device__ __forceinline__ void dg_load_ints(DG_GL const unsigned char *p, int *o) {
-    if (N >= 4) {
-#pragma unroll
-        for (int k = 0; k < N / 4; k++) { const dg_iv4 t = *(DG_GL const dg_iv4 *)(p + 16 * k); o[4 * k] = t[0]; o[4 * k + 1] = t[1]; o[4 * k + 2] = t[2]; o[4 * k + 3] = t[3]; }
-    } else if (N == 2) { const dg_iv2 t = *(DG_GL const dg_iv2 *)p; o[0] = t[0]; o[1] = t[1]; }
-    else o[0] = *(DG_GL const int *)p;
-}
-template <typename T, int W> __device__ __forceinline__ void dg_store(DG_GL unsigned char *p, const int *v) {
-    constexpr int BYTES = W * (int)sizeof(T);
-    unsigned d[(BYTES + 3) / 4];
-#pragma unroll
-    for (int k = 0; k < (BYTES + 3) / 4; k++) d[k] = 0;
-#pragma unroll
-    for (int i = 0; i < W; i++) {
-        if (sizeof(T) == 2) d[i >> 1] |= (unsigned)v[i] << (16 * (i & 1));
-        else d[i >> 2] |= (unsigned)v[i] << (8 * (i & 3));
-    }
-    if (BYTES >= 16) {
-#pragma unroll
-        for (int k = 0; k < BYTES / 16; k++) { dg_uv4 t = { d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3] }; *(DG_GL dg_uv4 *)(p + 16 * k) = t; }
-    } else if (BYTES == 8) { dg_uv2 t = { d[0], d[1] }; *(DG_GL dg_uv2 *)p = t; }
-    else if (BYTES == 4) *(DG_GL dg_uv1 *)p = d[0];
-    else *(DG_GL dg_uh1 *)p = (unsigned short)d[0];
 }
 
 #define DG_TILE_MAX (34 * 6) // plan records of a workgroup's tile (32 cells x 8 rows): 33 block columns x at most 6 block rows (2-sample cell rows: five)
@@ -1028,12 +948,7 @@ __global__ __launch_bounds__(256) void bf_usable_kernel(const DGParams *Pp, cons
     __syncthreads();
     const BFJob &J = jobs[f];
     if (J.good) {
-        for (int d = 0; d < 2; d++) {
-            const GVecD *v = mvx_level0((d ? J.blobB : J.blobF), P.nLvCount);
-            int c = 0;
-            for (int i = threadIdx.x; i < P.nBlk; i += 256) c += v[i].sad > B.thscd1 ? 1 : 0;
-            atomicAdd(&cnt[d], c);
-        }
+        for (int d = 0; d < 2; d++) atomicAdd(&cnt[d], fps_count_over(d ? J.blobB : J.blobF, P.nLvCount, P.nBlk, B.thscd1));
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1058,29 +973,7 @@ __global__ __launch_bounds__(256) void bf_mask_kernel(const DGParams *Pp, const 
     const int stepX = P.pl[0].stepX, stepY = P.pl[0].stepY, nPel = P.pel;
     int *m = small + ((size_t)f * 2 + dir) * B.XP * B.YP;
     if (B.mode <= 5) {
-        const int tX = time256 * 16 / (stepX * nPel), tY = time256 * 16 / (stepY * nPel);
-        const double nX = 80.0 / (B.ml * stepX * nPel), nY = 80.0 / (B.ml * stepY * nPel);
-        const int vx = vec[i].x, vy = vec[i].y;
-        if (bx < nBlkX - 1) {
-            const int vx1 = vec[i + 1].x;
-            if (vx1 < vx) {
-                const int o = vx - vx1;
-                const int minb = dir ? max(0, bx + 1 - o * tX / 4096) : bx;
-                const int maxb = dir ? bx + 1 : min(bx + 1 - o * tX / 4096, nBlkX - 1);
-                const int val = min((int)(255 * o * nX), 255);
-                for (int b = minb; b <= maxb; b++) atomicMax(&m[b + by * B.XP], val);
-            }
-        }
-        if (by < nBlkY - 1) {
-            const int vy1 = vec[i + nBlkX].y;
-            if (vy1 < vy) {
-                const int o = vy - vy1;
-                const int minb = dir ? max(0, by + 1 - o * tY / 4096) : by;
-                const int maxb = dir ? by + 1 : min(by + 1 - o * tY / 4096, nBlkY - 1);
-                const int val = min((int)(255 * o * nY), 255);
-                for (int b = minb; b <= maxb; b++) atomicMax(&m[bx + b * B.XP], val);
-            }
-        }
+        fps_occlusion_block(vec, i, bx, by, nBlkX, nBlkY, dir, time256, stepX, stepY, nPel, B.ml, m, B.XP);
     } else {
         const int tX = (256 - time256) * 16 / (stepX * nPel), tY = (256 - time256) * 16 / (stepY * nPel);
         int bxi = bx - vec[i].x * tX / 4096, byi = by - vec[i].y * tY / 4096;
@@ -1099,9 +992,9 @@ __global__ __launch_bounds__(256) void bf_mask_finish_kernel(const DGParams *Pp,
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= B.XP * B.YP) return;
     const int y = i / B.XP, x = i - y * B.XP;
-    const int sx = min(x, P.nBlkX - 1), sy = min(y, P.nBlkY - 1); // right clone first, then bottom clone of the padded row
+    const int s = fps_pad_source(x, y, P.nBlkX, P.nBlkY, B.XP);
     const int *mF = small + ((size_t)f * 2 + 0) * B.XP * B.YP, *mB = small + ((size_t)f * 2 + 1) * B.XP * B.YP;
-    const int vF = mF[sx + sy * B.XP], vB = mB[sx + sy * B.XP];
+    const int vF = mF[s], vB = mB[s];
     unsigned char *o = masks + (size_t)f * 3 * B.XP * B.YP;
     o[i] = (unsigned char)vF;
     o[B.XP * B.YP + i] = (unsigned char)vB;
@@ -1129,13 +1022,6 @@ __global__ __launch_bounds__(256) void bf_plan_kernel(const DGParams *Pp, const 
     plan[(size_t)f * P.nBlk + i] = r;
 }
 
-// SimpleResize.cpp:62-121 at one output sample
-__device__ __forceinline__ int bf_upsize(const unsigned char *m, int XP, const int *hOff, const int *hW, const int *vOff, const int *vW, int x, int y) {
-    const int wb = vW[y], wt = 16384 - wb, o = hOff[x], wr = hW[x], wl = 16384 - wr;
-    const unsigned char *s1 = m + vOff[y] * XP, *s2 = s1 + XP;
-    const int a = (unsigned char)((s1[o] * wt + s2[o] * wb + 8192) >> 14), b = (unsigned char)((s1[o + 1] * wt + s2[o + 1] * wb + 8192) >> 14);
-    return (unsigned char)((a * wl + b * wr + 8192) >> 14);
-}
 __device__ __forceinline__ int bf_median(int a, int b, int c) { const int mn = min(a, b), mx = max(a, b); return max(mn, min(mx, c)); }
 
 template <typename T>
@@ -1339,21 +1225,6 @@ struct mvx_blockfps : DGCommon {
     }
 };
 
-// SimpleResize.cpp:27-57 InitTables (same float arithmetic)
-static void bf_tables(int *offsets, int *weights, int out, int in) {
-    const float leftmost = 0.5f, rightmost = in - 0.5f;
-    const int leftmost_idx = std::max((int)leftmost, 0), rightmost_idx = std::min((int)rightmost, in - 1);
-    for (int i = 0; i < out; i++) {
-        const float position = (i + 0.5f) * (float)in / (float)out;
-        float weight; int offset;
-        if (position <= leftmost) { offset = leftmost_idx; weight = 0.0f; }
-        else if (position >= rightmost) { offset = rightmost_idx - 1; weight = 1.0f; }
-        else { offset = (int)(position - leftmost); weight = position - leftmost - offset; }
-        offsets[i] = offset;
-        weights[i] = (int)(weight * 16384);
-    }
-}
-static long long bf_gcd(long long x, long long y) { while (y) { long long t = x % y; x = y; y = t; } return x; }
 
 extern "C" __attribute__((visibility("default"))) int mvx_blockfps_create(const mvx_blockfps_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
         const mvx_super *sup, int num_frames, int64_t fps_num, int64_t fps_den, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3],

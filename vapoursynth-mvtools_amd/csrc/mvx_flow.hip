@@ -1,0 +1,470 @@
+// mvx_flow.hip -- mv.FlowInter and mv.FlowFPS on gfx950.
+//
+// The reference builds, per output frame and plane class, full-resolution int16 vector planes (SimpleResize.cpp:60-121 on the
+// block-resolution fields of MaskFun.cpp:169-203) and full-resolution occlusion masks, then runs FlowInterSimple / FlowInter /
+// FlowInterExtra (MaskFun.cpp:374-555) over them against the Finest frame (MVFlowInter.c:80-452, MVFlowFPS.c:86-524,
+// MVFlowFPSHelper.c:49-93).  Here none of the full-resolution planes exists: per job, tiny kernels decide usability and compute the
+// padded small fields; ONE gather pass then upsizes the vectors and masks at each output sample with the reference's integer tables
+// and rounding, and fetches the compensated samples straight from the super frames (sup_offset interleaves the pel^2 sub-planes
+// exactly as mv.Finest does), so the Finest frame is never built either:
+//   flow_usable_kernel : per (job, blob) -> usable flags; fl_state turns a job's four flags into its formula (Simple / regular / Extra)
+//                        or the Blend / copy fallback
+//   flow_occ_kernel    : per (job, direction, block) -> occlusion scatter-max (BlockFPS's code, mvx_fps_shared.h)
+//   flow_cells_kernel  : per (job, padded cell) -> padded vector cells (CheckAndPadSmallY) and padded mask bytes (CheckAndPadMaskSmall)
+//   flow_kernel        : per CW consecutive output samples -> the interpolated samples, one wide store; one launch for the luma planes
+//                        of all jobs and one for both chroma planes of all jobs (the two classes differ in CW and in the upsizer tables)
+#include "mvx_fps_shared.h"
+
+enum { FL_SIMPLE = 0, FL_REGULAR = 1, FL_EXTRA = 2, FL_FALLBACK = -1 };
+
+struct FLParams {
+    int nplanes, pel, logPel, bits, bps;
+    int nBlkX, nBlkY, nBlk, nLvCount, stepX, stepY;
+    int XP, YP;                           // padded small-field grid (nBlkXP, nBlkYP)
+    int isFPS, maskmode, blend;
+    int halfX, halfY;                     // VectorSmallMaskYToHalfUV: chroma vector = luma >> 1 along an axis with ratio 2
+    long long thscd1; int thscd2;
+    double ml;
+    int limW[2], limH[2];                 // the int16 resizer's limit_width / limit_height: luma / chroma frame size
+    PlaneG pl[3];
+    const int *hOff[2], *hW[2], *vOff[2], *vW[2]; // SimpleResize tables, luma / chroma upsizer
+    long long clipPitch[3];
+};
+struct FLJob {
+    const unsigned char *supL[3], *supR[3];  // super frames nleft / nright (the reference's pSrc / pRef Finest frames)
+    const unsigned char *blobF, *blobB;      // mvfw at nright, mvbw at nleft
+    const unsigned char *blobFF, *blobBB;    // mvfw at nleft, mvbw at nright (Extra)
+    const unsigned char *clipL[3], *clipR[3];
+    unsigned char *dst[3];
+    int time256, copy;                       // copy: 1 / 2 = the clip frame left / right (FlowFPS at time256 0 / 256, MVFlowFPS.c:138-142)
+};
+// one padded small-field cell: the B, F, BB, FF vectors as int16 (MakeVectorSmallMasks stores them into int16_t planes), x in the low half
+struct FLCell { short bx, by, fx, fy, bbx, bby, ffx, ffy; };
+static_assert(sizeof(FLCell) == 16, "cell layout");
+__device__ __forceinline__ int fl_lo(int w) { return (int)(short)(w & 0xffff); }
+__device__ __forceinline__ int fl_hi(int w) { return w >> 16; }
+
+// the wide helpers move at least two bytes: a single 8-bit sample goes on its own
+template <typename T, int W> __device__ __forceinline__ void fl_load(DG_GL const unsigned char *p, int *o) {
+    if constexpr (W * sizeof(T) == 1) o[0] = *p; else dg_load<T, W>(p, o);
+}
+template <typename T, int W> __device__ __forceinline__ void fl_store(DG_GL unsigned char *p, const int *v) {
+    if constexpr (W * sizeof(T) == 1) *p = (unsigned char)v[0]; else dg_store<T, W>(p, v);
+}
+
+// per (job, blob): Fakery.c:52-58,103-107,144-146 fgopIsUsable of mvfw at nright, mvbw at nleft, mvfw at nleft, mvbw at nright -> flags[job][4];
+// 0 for a blob the job does not read (copies, frames outside the clip, the extra blobs of FlowFPS mask 0 / 1)
+__global__ __launch_bounds__(256) void flow_usable_kernel(const FLParams *Pp, const FLJob *jobs, int *flags) {
+    const FLParams &P = *Pp;
+    const int f = blockIdx.x, k = blockIdx.y;
+    const FLJob &J = jobs[f];
+    const unsigned char *blob = k == 0 ? J.blobF : k == 1 ? J.blobB : k == 2 ? J.blobFF : J.blobBB;
+    const bool want = !J.copy && J.supL[0] && J.supR[0] && blob && (k < 2 || !P.isFPS || P.maskmode == 2);
+    __shared__ int cnt;
+    if (threadIdx.x == 0) cnt = 0;
+    __syncthreads();
+    if (want) atomicAdd(&cnt, fps_count_over(blob, P.nLvCount, P.nBlk, P.thscd1));
+    __syncthreads();
+    if (threadIdx.x == 0) flags[f * 4 + k] = want && ((const int *)blob)[1] == 1 && !(cnt > P.thscd2);
+}
+// the job's formula (MVFlowInter.c:109-138,245-276 / MVFlowFPS.c:153-166,314-354,385-435): the masks and B / F come from the main vectors, the
+// extra blobs only pick the formula; FlowFPS mask 2 without usable extra vectors falls through to Simple (MVFlowFPS.c:435)
+__device__ __forceinline__ int fl_state(const FLParams &P, const int *fl) {
+    if (!fl[0] || !fl[1]) return FL_FALLBACK;
+    const bool extra = fl[2] && fl[3];
+    if (!P.isFPS) return extra ? FL_EXTRA : FL_REGULAR;
+    if (P.maskmode == 1) return FL_REGULAR;
+    return extra ? FL_EXTRA : FL_SIMPLE;
+}
+
+// MakeVectorOcclusionMaskTime for the B mask (isBackward, 256 - t) and the F mask (t) into int planes [job][F,B][YP*XP], zeroed before
+__global__ __launch_bounds__(256) void flow_occ_kernel(const FLParams *Pp, const FLJob *jobs, const int *flags, int *small) {
+    const FLParams &P = *Pp;
+    const int f = blockIdx.z, dir = blockIdx.y; // dir 0 = forward mask, 1 = backward mask
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (fl_state(P, flags + 4 * f) < 0 || i >= P.nBlk) return;
+    const FLJob &J = jobs[f];
+    const GVecD *vec = mvx_level0(dir ? J.blobB : J.blobF, P.nLvCount);
+    const int by = i / P.nBlkX, bx = i - by * P.nBlkX;
+    fps_occlusion_block(vec, i, bx, by, P.nBlkX, P.nBlkY, dir, dir ? 256 - J.time256 : J.time256, P.stepX, P.stepY, P.pel, P.ml,
+                        small + ((size_t)f * 2 + dir) * P.XP * P.YP, P.XP);
+}
+
+// MaskFun.cpp:38-60 CheckAndPadSmallY: cells right of the field take min(vx, 0) and the row's vy, cells below take the (padded) row's vx and min(vy, 0)
+__device__ __forceinline__ void fl_padded(const GVecD *v, int s, bool right, bool below, short &vx, short &vy) {
+    vx = (short)v[s].x; vy = (short)v[s].y;
+    if (right) vx = min(vx, (short)0);
+    if (below) vy = min(vy, (short)0);
+}
+__global__ __launch_bounds__(256) void flow_cells_kernel(const FLParams *Pp, const FLJob *jobs, const int *flags, const int *small, FLCell *cells, unsigned char *masks) {
+    const FLParams &P = *Pp;
+    const int f = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int st = fl_state(P, flags + 4 * f);
+    const int cellsN = P.XP * P.YP;
+    if (st < 0 || i >= cellsN) return;
+    const FLJob &J = jobs[f];
+    const int y = i / P.XP, x = i - y * P.XP;
+    const int s = fps_pad_source(x, y, P.nBlkX, P.nBlkY, P.XP), sb = min(x, P.nBlkX - 1) + min(y, P.nBlkY - 1) * P.nBlkX;
+    const bool right = x >= P.nBlkX, below = y >= P.nBlkY;
+    FLCell c;
+    fl_padded(mvx_level0(J.blobB, P.nLvCount), sb, right, below, c.bx, c.by);
+    fl_padded(mvx_level0(J.blobF, P.nLvCount), sb, right, below, c.fx, c.fy);
+    if (st == FL_EXTRA) {
+        fl_padded(mvx_level0(J.blobBB, P.nLvCount), sb, right, below, c.bbx, c.bby);
+        fl_padded(mvx_level0(J.blobFF, P.nLvCount), sb, right, below, c.ffx, c.ffy);
+    } else {
+        c.bbx = c.bby = c.ffx = c.ffy = 0;
+    }
+    cells[(size_t)f * cellsN + i] = c;
+    const int *mF = small + ((size_t)f * 2 + 0) * cellsN, *mB = small + ((size_t)f * 2 + 1) * cellsN;
+    unsigned char *o = masks + (size_t)f * 2 * cellsN;
+    o[i] = (unsigned char)mF[s];
+    o[cellsN + i] = (unsigned char)mB[s];
+}
+
+// SimpleResize.cpp:60-121 for int16 fields at one output sample: the vertical pass rounds per small-field column, then the horizontal
+// pass rounds and clamps to [lo, hi]
+__device__ __forceinline__ int fl_vup(int s1a, int s2a, int s1b, int s2b, int wt, int wb, int wl, int wr, int lo, int hi) {
+    const int a = (short)((s1a * wt + s2a * wb + 8192) >> 14), b = (short)((s1b * wt + s2b * wb + 8192) >> 14);
+    const int r = (a * wl + b * wr + 8192) >> 14;
+    return (short)max(lo, min(r, hi));
+}
+
+template <typename T>
+__device__ __forceinline__ int fl_fetch(const FLParams &P, const PlaneG &g, const unsigned char *sup, int X, int Y) {
+    return *(DG_GL const T *)dg_gl(sup + sup_offset(g, P.pel, P.logPel, (int)sizeof(T), X, Y));
+}
+
+// one thread per CW consecutive samples of one row of plane class p0 .. p0 + npl - 1
+template <typename T, int CW>
+__global__ __launch_bounds__(256) void flow_kernel(const FLParams *Pp, const FLJob *jobs, const int *flags, const FLCell *cells, const unsigned char *masks,
+                                                   int planeFirst, int planesPerFrame) {
+    const FLParams &P = *Pp;
+    const int z = blockIdx.z, f = z / planesPerFrame, p = planeFirst + z % planesPerFrame;
+    const PlaneG &g = P.pl[p];
+    const int x = (blockIdx.x * 64 + (threadIdx.x & 63)) * CW, y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= g.W || y >= g.H) return;
+    const FLJob &J = jobs[f];
+    DG_GL unsigned char *dptr = dg_glw(J.dst[p] + (long long)y * g.dstPitch + (long long)x * (long long)sizeof(T));
+    const int t = J.time256, st = fl_state(P, flags + 4 * f);
+    int out[CW];
+    if (st < 0) { // copy at FlowFPS's time256 0 / 256, else Blend or the left frame (MaskFun.cpp:349-371, MVFlowInter.c:403-446, MVFlowFPS.c:475-519)
+        const long long co = (long long)y * P.clipPitch[p] + (long long)x * (long long)sizeof(T);
+        int l[CW];
+        if (J.copy == 2) { fl_load<T, CW>(dg_gl(J.clipR[p] + co), l); fl_store<T, CW>(dptr, l); return; }
+        fl_load<T, CW>(dg_gl(J.clipL[p] + co), l);
+        if (J.copy == 1 || !P.blend) { fl_store<T, CW>(dptr, l); return; }
+        int r[CW];
+        fl_load<T, CW>(dg_gl(J.clipR[p] + co), r);
+#pragma unroll
+        for (int i = 0; i < CW; i++) out[i] = (int)(T)((l[i] * (256 - t) + r[i] * t) >> 8);
+        fl_store<T, CW>(dptr, out);
+        return;
+    }
+    const int c = p ? 1 : 0;
+    const int cellsN = P.XP * P.YP;
+    const int wb = *(DG_GL const int *)dg_gl(P.vW[c] + y), wt = 16384 - wb;
+    const int r0 = *(DG_GL const int *)dg_gl(P.vOff[c] + y) * P.XP, r1 = r0 + P.XP;
+    int hO[CW], hWr[CW];
+    dg_load_ints<CW>(dg_gl(P.hOff[c] + x), hO);
+    dg_load_ints<CW>(dg_gl(P.hW[c] + x), hWr);
+    DG_GL const unsigned char *cl = dg_gl(cells + (size_t)f * cellsN);
+    DG_GL const unsigned char *mFp = dg_gl(masks + (size_t)f * 2 * cellsN), *mBp = mFp + cellsN;
+    const int hx = c && P.halfX ? 1 : 0, hy = c && P.halfY ? 1 : 0;
+    const int pel = P.pel, lp = P.logPel;
+    const int yLo = -y * pel, yHi = (P.limH[c] - y) * pel - 1;
+    const int Y = y << lp;
+#pragma unroll
+    for (int i = 0; i < CW; i++) {
+        const int xi = x + i, o = hO[i], wr = hWr[i], wl = 16384 - wr;
+        const int xLo = -xi * pel, xHi = (P.limW[c] - xi) * pel - 1;
+        // the four cells around the sample: (row r0 / r1) x (column o / o + 1), B and F vectors as two dwords each
+        const dg_iv2 a0 = *(DG_GL const dg_iv2 *)(cl + 16 * (r0 + o)), b0 = *(DG_GL const dg_iv2 *)(cl + 16 * (r0 + o + 1));
+        const dg_iv2 a1 = *(DG_GL const dg_iv2 *)(cl + 16 * (r1 + o)), b1 = *(DG_GL const dg_iv2 *)(cl + 16 * (r1 + o + 1));
+        const int vxB = fl_vup(fl_lo(a0[0]) >> hx, fl_lo(a1[0]) >> hx, fl_lo(b0[0]) >> hx, fl_lo(b1[0]) >> hx, wt, wb, wl, wr, xLo, xHi);
+        const int vyB = fl_vup(fl_hi(a0[0]) >> hy, fl_hi(a1[0]) >> hy, fl_hi(b0[0]) >> hy, fl_hi(b1[0]) >> hy, wt, wb, wl, wr, yLo, yHi);
+        const int vxF = fl_vup(fl_lo(a0[1]) >> hx, fl_lo(a1[1]) >> hx, fl_lo(b0[1]) >> hx, fl_lo(b1[1]) >> hx, wt, wb, wl, wr, xLo, xHi);
+        const int vyF = fl_vup(fl_hi(a0[1]) >> hy, fl_hi(a1[1]) >> hy, fl_hi(b0[1]) >> hy, fl_hi(b1[1]) >> hy, wt, wb, wl, wr, yLo, yHi);
+        const int mF = fps_upsize_u8(mFp, r0, r1, o, wt, wb, wl, wr), mB = fps_upsize_u8(mBp, r0, r1, o, wt, wb, wl, wr);
+        const int X = xi << lp;
+        const int dF = fl_fetch<T>(P, g, J.supL[p], X + ((vxF * t) >> 8), Y + ((vyF * t) >> 8));
+        const int dB = fl_fetch<T>(P, g, J.supR[p], X + ((vxB * (256 - t)) >> 8), Y + ((vyB * (256 - t)) >> 8));
+        int v;
+        if (st == FL_SIMPLE) { // MaskFun.cpp:493-551 (time256 == 128 has its own formula; its vectors v >> 1 equal (v * 128) >> 8)
+            if (t == 128) v = (((dF + dB) << 8) + (dB - dF) * (mF - mB)) >> 9;
+            else v = (((dF * (255 - mF) + dB * mF + 255) >> 8) * (256 - t) + ((dB * (255 - mB) + dF * mB + 255) >> 8) * t) >> 8;
+        } else if (st == FL_REGULAR) { // MaskFun.cpp:374-414: the int64 products are non-negative and below 2^32
+            const unsigned dF0 = (unsigned)fl_fetch<T>(P, g, J.supL[p], X, Y), dB0 = (unsigned)fl_fetch<T>(P, g, J.supR[p], X, Y);
+            const unsigned uF = (unsigned)dF, uB = (unsigned)dB, kF = (unsigned)mF, kB = (unsigned)mB;
+            const unsigned a = (uF * (255 - kF) + ((kF * (uB * (255 - kB) + kB * dF0) + 255) >> 8) + 255) >> 8;
+            const unsigned b = (uB * (255 - kB) + ((kB * (uF * (255 - kF) + kF * dB0) + 255) >> 8) + 255) >> 8;
+            v = (int)((a * (unsigned)(256 - t) + b * (unsigned)t) >> 8);
+        } else { // MaskFun.cpp:417-490
+            const dg_iv2 c0 = *(DG_GL const dg_iv2 *)(cl + 16 * (r0 + o) + 8), d0 = *(DG_GL const dg_iv2 *)(cl + 16 * (r0 + o + 1) + 8);
+            const dg_iv2 c1 = *(DG_GL const dg_iv2 *)(cl + 16 * (r1 + o) + 8), d1 = *(DG_GL const dg_iv2 *)(cl + 16 * (r1 + o + 1) + 8);
+            const int vxBB = fl_vup(fl_lo(c0[0]) >> hx, fl_lo(c1[0]) >> hx, fl_lo(d0[0]) >> hx, fl_lo(d1[0]) >> hx, wt, wb, wl, wr, xLo, xHi);
+            const int vyBB = fl_vup(fl_hi(c0[0]) >> hy, fl_hi(c1[0]) >> hy, fl_hi(d0[0]) >> hy, fl_hi(d1[0]) >> hy, wt, wb, wl, wr, yLo, yHi);
+            const int vxFF = fl_vup(fl_lo(c0[1]) >> hx, fl_lo(c1[1]) >> hx, fl_lo(d0[1]) >> hx, fl_lo(d1[1]) >> hx, wt, wb, wl, wr, xLo, xHi);
+            const int vyFF = fl_vup(fl_hi(c0[1]) >> hy, fl_hi(c1[1]) >> hy, fl_hi(d0[1]) >> hy, fl_hi(d1[1]) >> hy, wt, wb, wl, wr, yLo, yHi);
+            const int dFF = fl_fetch<T>(P, g, J.supL[p], X + ((vxFF * t) >> 8), Y + ((vyFF * t) >> 8));
+            const int dBB = fl_fetch<T>(P, g, J.supR[p], X + ((vxBB * (256 - t)) >> 8), Y + ((vyBB * (256 - t)) >> 8));
+            const int mn = min(dB, dF), mx = max(dB, dF);
+            const int medBB = max(mn, min(dBB, mx)), medFF = max(mn, min(dFF, mx));
+            v = (((medBB * mF + dF * (255 - mF) + 255) >> 8) * (256 - t) + ((medFF * mB + dB * (255 - mB) + 255) >> 8) * t) >> 8;
+        }
+        out[i] = (int)(T)v;
+    }
+    fl_store<T, CW>(dptr, out);
+}
+
+// ------------------------------------------------------------------------------------------------ host object
+
+struct mvx_flow {
+    CallGuard guard;
+    FLParams P;
+    FLParams *dP = nullptr;
+    FLJob *dJobs = nullptr;
+    size_t jobsCap = 0;
+    int *dFlags = nullptr, *dSmall = nullptr;
+    FLCell *dCells = nullptr;
+    unsigned char *dMasks = nullptr;
+    int *dTables = nullptr;
+    int nWidthP[2], nHeightP[2];
+    int delta, inFrames, outFrames, time256;
+    long long fa, fb, outNum, outDen;
+    ~mvx_flow() {
+        if (dP) (void)hipFree(dP);
+        if (dJobs) (void)hipFree(dJobs);
+        if (dFlags) (void)hipFree(dFlags);
+        if (dSmall) (void)hipFree(dSmall);
+        if (dCells) (void)hipFree(dCells);
+        if (dMasks) (void)hipFree(dMasks);
+        if (dTables) (void)hipFree(dTables);
+    }
+};
+
+#define FFAIL(...) do { snprintf(err, MVX_ERRLEN, __VA_ARGS__); mvx_set_error("%s", err); return MVX_E_ARG; } while (0)
+
+// MVAnalysisData.c:68-98 adataCheckSimilarity: every mismatching field overwrites the message, so the LAST one is reported
+static bool flow_similarity(const mvx_analysis_data *a, const mvx_analysis_data *b, const char *name, char *err) {
+    bool bad = false;
+    auto msg = [&](const char *what) { snprintf(err, MVX_ERRLEN, "%s: mvbw and mvfw have different %s.", name, what); bad = true; };
+    if (a->nWidth != b->nWidth) msg("widths");
+    if (a->nHeight != b->nHeight) msg("heights");
+    if (a->nBlkSizeX != b->nBlkSizeX || a->nBlkSizeY != b->nBlkSizeY) msg("block sizes");
+    if (a->nPel != b->nPel) msg("pel precision");
+    if (a->nOverlapX != b->nOverlapX || a->nOverlapY != b->nOverlapY) msg("overlap");
+    if (a->xRatioUV != b->xRatioUV) msg("horizontal subsampling");
+    if (a->yRatioUV != b->yRatioUV) msg("vertical subsampling");
+    if (a->bitsPerSample != b->bitsPerSample) msg("bit depths");
+    return bad;
+}
+
+// the checks both filters share after their own argument checks (MVFlowInter.c:540-574 / MVFlowFPS.c:646-671), then the geometry
+// (MVFlowInter.c:651-678, MVFlowFPS.c:776-802)
+static int flow_common(mvx_flow *h, const char *name, int64_t thscd1, int32_t thscd2, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
+                       const mvx_super_info &si, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], char *err) {
+    if (thscd1 > 8 * 8 * 255) FFAIL("%s: thscd1 can be at most %d.", name, 8 * 8 * 255);
+    mvx_scale_thscd(&thscd1, &thscd2, bw);
+    if (flow_similarity(bw, fw, name, err)) { mvx_set_error("%s", err); return MVX_E_ARG; }
+    // FlowInter's check; FlowFPS lacks it in the reference and then reads negative frame numbers: rejected here on purpose
+    if (bw->nDeltaFrame <= 0 || fw->nDeltaFrame <= 0) FFAIL("%s: cannot use motion vectors with absolute frame references.", name);
+    if (bw->nDeltaFrame != fw->nDeltaFrame) FFAIL("%s: mvbw and mvfw must be generated with the same delta.", name);
+    if (!bw->isBackward) FFAIL("%s: mvbw must be generated with isb=True.", name);
+    if (fw->isBackward) FFAIL("%s: mvfw must be generated with isb=False.", name);
+    FLParams &P = h->P;
+    memset(&P, 0, sizeof(P));
+    P.thscd1 = thscd1; P.thscd2 = thscd2;
+    P.nplanes = (si.modeYUV & 6) && si.num_planes > 1 ? 3 : 1;
+    P.pel = bw->nPel; P.logPel = bw->nPel == 4 ? 2 : bw->nPel == 2 ? 1 : 0;
+    P.bits = si.bits; P.bps = (si.bits + 7) / 8;
+    P.nBlkX = bw->nBlkX; P.nBlkY = bw->nBlkY; P.nBlk = bw->nBlkX * bw->nBlkY; P.nLvCount = bw->nLvCount;
+    P.stepX = bw->nBlkSizeX - bw->nOverlapX; P.stepY = bw->nBlkSizeY - bw->nOverlapY;
+    P.XP = bw->nBlkX; P.YP = bw->nBlkY;
+    while (P.XP * P.stepX + bw->nOverlapX < bw->nWidth) P.XP++;
+    while (P.YP * P.stepY + bw->nOverlapY < bw->nHeight) P.YP++;
+    h->nWidthP[0] = P.XP * P.stepX + bw->nOverlapX; h->nHeightP[0] = P.YP * P.stepY + bw->nOverlapY;
+    h->nWidthP[1] = h->nWidthP[0] / bw->xRatioUV; h->nHeightP[1] = h->nHeightP[0] / bw->yRatioUV;
+    P.limW[0] = bw->nWidth; P.limH[0] = bw->nHeight;
+    P.limW[1] = bw->nWidth / bw->xRatioUV; P.limH[1] = bw->nHeight / bw->yRatioUV;
+    P.halfX = bw->xRatioUV == 2; P.halfY = bw->yRatioUV == 2;
+    // the upsizer interpolates between small-field cells o and o + 1: with a single padded column or row the reference reads outside its buffers
+    if (P.XP < 2 || P.YP < 2) FFAIL("%s: the frame must be at least two blocks wide and two blocks high.", name);
+    if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) FFAIL("%s: U and V super planes must share one pitch.", name);
+    const int xSub = mvx_ilog2(si.xRatioUV), ySub = mvx_ilog2(si.yRatioUV);
+    for (int p = 0; p < 3; p++) {
+        PlaneG &g = P.pl[p];
+        const int sx = p ? xSub : 0, sy = p ? ySub : 0, q = p < si.num_planes ? p : 0;
+        g.subX = sx; g.subY = sy;
+        g.W = bw->nWidth >> sx; g.H = bw->nHeight >> sy;
+        g.hpadPel = (si.hpad >> sx) * si.pel; g.vpadPel = (si.vpad >> sy) * si.pel; // the Finest frame's nOffsetY / nOffsetUV (MVFlowInter.c:218-219)
+        g.supPitch = super_pitch[q]; g.dstPitch = dst_pitch[q];
+        g.supPlaneStride = g.supPitch * (long long)((si.height >> sy) + 2 * (si.vpad >> sy));
+        P.clipPitch[p] = clip_pitch[q];
+    }
+    h->delta = bw->nDeltaFrame;
+    return MVX_OK;
+}
+
+// MVFlowInter.c:473-678 mvflowinterCreate.  time and ml are float arguments there: time256 is formed in float, ml reaches the mask as (double)(float)ml.
+extern "C" __attribute__((visibility("default"))) int mvx_flowinter_create(const mvx_flowinter_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
+        const mvx_super *sup, int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flow **out, char *err) {
+    char dummy[MVX_ERRLEN];
+    if (!err) err = dummy;
+    err[0] = 0;
+    *out = nullptr;
+    const mvx_super_info &si = sup->info;
+    const float time = (float)a->time, ml = (float)a->ml;
+    const int blend = a->blend == MVX_UNSET ? 1 : !!a->blend;
+    const int64_t thscd1 = a->thscd1 == MVX_UNSET ? 400 : a->thscd1;
+    const int32_t thscd2 = a->thscd2 == MVX_UNSET ? 130 : a->thscd2;
+    if (time < 0.0f || time > 100.0f) FFAIL("FlowInter: time must be between 0 and 100 %% (inclusive).");
+    if (ml <= 0.0f) FFAIL("FlowInter: ml must be greater than 0.");
+    mvx_flow *h = new mvx_flow();
+    int rc = flow_common(h, "FlowInter", thscd1, thscd2, bw, fw, si, super_pitch, clip_pitch, dst_pitch, err);
+    if (!rc && (bw->nHeight != si.height || bw->nWidth != si.super_width - si.hpad * 2 || bw->nPel != si.pel)) {
+        snprintf(err, MVX_ERRLEN, "FlowInter: wrong source or super clip frame size.");
+        mvx_set_error("%s", err);
+        rc = MVX_E_ARG;
+    }
+    if (rc) { delete h; return rc; }
+    FLParams &P = h->P;
+    P.isFPS = 0; P.blend = blend; P.ml = (double)ml;
+    h->time256 = (int)(time * 256.0f / 100.0f);
+    h->inFrames = h->outFrames = num_frames;
+    h->outNum = 0; h->outDen = 0;
+    *out = h;
+    return MVX_OK;
+}
+
+// MVFlowFPS.c:565-802 mvflowfpsCreate
+extern "C" __attribute__((visibility("default"))) int mvx_flowfps_create(const mvx_flowfps_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
+        const mvx_super *sup, int num_frames, int64_t fps_num, int64_t fps_den, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3],
+        const ptrdiff_t dst_pitch[3], mvx_flow **out, char *err) {
+    char dummy[MVX_ERRLEN];
+    if (!err) err = dummy;
+    err[0] = 0;
+    *out = nullptr;
+    const mvx_super_info &si = sup->info;
+    const long long num = a->num == MVX_UNSET ? 25 : a->num, den = a->den == MVX_UNSET ? 1 : a->den;
+    const int mask = a->mask == MVX_UNSET ? 2 : a->mask;
+    const int blend = a->blend == MVX_UNSET ? 1 : !!a->blend;
+    const int64_t thscd1 = a->thscd1 == MVX_UNSET ? 400 : a->thscd1;
+    const int32_t thscd2 = a->thscd2 == MVX_UNSET ? 130 : a->thscd2;
+    if (mask < 0 || mask > 2) FFAIL("FlowFPS: mask must be 0, 1, or 2.");
+    if (a->ml <= 0.0) FFAIL("FlowFPS: ml must be greater than 0.");
+    mvx_flow *h = new mvx_flow();
+    int rc = flow_common(h, "FlowFPS", thscd1, thscd2, bw, fw, si, super_pitch, clip_pitch, dst_pitch, err);
+    auto fail = [&](const char *m) { snprintf(err, MVX_ERRLEN, "%s", m); mvx_set_error("%s", err); rc = MVX_E_ARG; };
+    if (!rc && (fps_num == 0 || fps_den == 0)) fail("FlowFPS: The input clip must have a frame rate. Invoke AssumeFPS if necessary.");
+    if (!rc && (bw->nWidth != si.width || bw->nHeight != si.height)) fail("FlowFPS: inconsistent source and vector frame size.");
+    if (!rc && (bw->nHeight != si.height || bw->nWidth != si.super_width - si.hpad * 2 || bw->nPel != si.pel)) fail("FlowFPS: wrong source or super clip frame size.");
+    if (!rc && !(bw->nWidth + bw->nHPadding * 2 == si.super_width && bw->nHeight + bw->nVPadding * 2 <= si.super_height))
+        fail("FlowFPS: inconsistent clips frame size! Incomprehensible error messages are the best, right?");
+    if (rc) { delete h; return rc; }
+    FLParams &P = h->P;
+    P.isFPS = 1; P.maskmode = mask; P.blend = blend; P.ml = a->ml;
+    long long numerator, denominator;
+    if (num != 0 && den != 0) { numerator = num; denominator = den; } else { numerator = fps_num * 2; denominator = fps_den; }
+    h->fa = denominator * fps_num; h->fb = numerator * fps_den;
+    const long long g = bf_gcd(h->fa, h->fb);
+    h->fa /= g; h->fb /= g;
+    if (numerator <= 0 || denominator <= 0) { h->outNum = 0; h->outDen = 1; } // setFPS, MVFlowFPS.c:547-561
+    else { const long long x = bf_gcd(numerator, denominator); h->outNum = numerator / x; h->outDen = denominator / x; }
+    h->inFrames = num_frames;
+    h->outFrames = (int)(1 + (num_frames - 1) * h->fb / h->fa);
+    h->time256 = 0;
+    *out = h;
+    return MVX_OK;
+}
+
+extern "C" __attribute__((visibility("default"))) void mvx_flow_destroy(mvx_flow *h) { delete h; }
+extern "C" __attribute__((visibility("default"))) void mvx_flow_get_info(const mvx_flow *h, mvx_flow_info *info) {
+    info->num_frames = h->outFrames; info->fps_num = h->outNum; info->fps_den = h->outDen;
+}
+// FlowInter: n -> (n, n + delta, time256) (MVFlowInter.c:86-100); FlowFPS: MVFlowFPS.c:92-99,125-134 (BlockFPS's arithmetic)
+extern "C" __attribute__((visibility("default"))) void mvx_flow_map(const mvx_flow *h, int n, int *nleft, int *nright, int *time256) {
+    if (!h->P.isFPS) { *nleft = n; *nright = n + h->delta; *time256 = h->time256; return; }
+    *nleft = (int)(n * h->fa / h->fb);
+    int t = (int)(((double)n * h->fa / h->fb - *nleft) * 256 + 0.5);
+    if (h->delta > 1) t = t / h->delta;
+    *nright = *nleft + h->delta;
+    *time256 = t;
+}
+
+extern "C" __attribute__((visibility("default"))) int mvx_flow_frames(mvx_flow *h, int nframes, const mvx_flow_job *jobs, void *stream) {
+    if (nframes <= 0) return MVX_OK;
+    hipStream_t st = (hipStream_t)stream;
+    CallGuard::Scope scope(h->guard, st);
+    FLParams &P = h->P;
+    if (!h->dP) { // upsizer tables (SimpleResize.cpp:27-57, MVFlowInter.c:677-679) + parameter block
+        const int n = h->nWidthP[0] + h->nWidthP[1] + h->nHeightP[0] + h->nHeightP[1];
+        std::vector<int> t(2 * n);
+        int *o = t.data(), *w = t.data() + n, pos = 0;
+        HIP_CHECK(hipMalloc((void **)&h->dTables, sizeof(int) * 2 * n));
+        for (int c = 0; c < 2; c++) {
+            bf_tables(o + pos, w + pos, h->nWidthP[c], P.XP); P.hOff[c] = h->dTables + pos; P.hW[c] = h->dTables + n + pos; pos += h->nWidthP[c];
+            bf_tables(o + pos, w + pos, h->nHeightP[c], P.YP); P.vOff[c] = h->dTables + pos; P.vW[c] = h->dTables + n + pos; pos += h->nHeightP[c];
+        }
+        HIP_CHECK(hipMemcpy(h->dTables, t.data(), sizeof(int) * 2 * n, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMalloc((void **)&h->dP, sizeof(FLParams)));
+        HIP_CHECK(hipMemcpy(h->dP, &P, sizeof(FLParams), hipMemcpyHostToDevice));
+    }
+    const size_t cellsN = (size_t)P.XP * P.YP;
+    if ((size_t)nframes > h->jobsCap) { // exactly this call's size; the capacity is raised only once every buffer exists
+        if (h->dJobs) (void)hipFree(h->dJobs);
+        if (h->dFlags) (void)hipFree(h->dFlags);
+        if (h->dSmall) (void)hipFree(h->dSmall);
+        if (h->dCells) (void)hipFree(h->dCells);
+        if (h->dMasks) (void)hipFree(h->dMasks);
+        h->dJobs = nullptr; h->dFlags = nullptr; h->dSmall = nullptr; h->dCells = nullptr; h->dMasks = nullptr;
+        h->jobsCap = 0;
+        const size_t n = (size_t)nframes;
+        HIP_CHECK(hipMalloc((void **)&h->dJobs, n * sizeof(FLJob)));
+        HIP_CHECK(hipMalloc((void **)&h->dFlags, n * 4 * sizeof(int)));
+        HIP_CHECK(hipMalloc((void **)&h->dSmall, n * 2 * cellsN * sizeof(int)));
+        HIP_CHECK(hipMalloc((void **)&h->dCells, n * cellsN * sizeof(FLCell)));
+        HIP_CHECK(hipMalloc((void **)&h->dMasks, n * 2 * cellsN));
+        h->jobsCap = n;
+    }
+    std::vector<FLJob> hj(nframes);
+    for (int f = 0; f < nframes; f++) {
+        FLJob &j = hj[f];
+        const mvx_flow_job &s = jobs[f];
+        memset(&j, 0, sizeof(j));
+        for (int p = 0; p < 3; p++) {
+            j.supL[p] = (const unsigned char *)s.super_left[p]; j.supR[p] = (const unsigned char *)s.super_right[p];
+            j.clipL[p] = (const unsigned char *)s.clip_left[p]; j.clipR[p] = (const unsigned char *)s.clip_right[p];
+            j.dst[p] = (unsigned char *)s.dst[p];
+        }
+        j.blobF = (const unsigned char *)s.blob_fw; j.blobB = (const unsigned char *)s.blob_bw;
+        j.blobFF = (const unsigned char *)s.blob_fw_extra; j.blobBB = (const unsigned char *)s.blob_bw_extra;
+        j.time256 = s.time256;
+        if (P.isFPS && s.time256 <= 0) j.copy = 1;
+        else if (P.isFPS && s.time256 >= 256) j.copy = 2;
+        if (s.time256 < 0 || s.time256 > 256) { mvx_set_error("mvx_flow_frames: time256 must be between 0 and 256"); return MVX_E_ARG; }
+        if (!j.dst[0] || !j.clipL[0] || ((j.copy == 2 || (!j.copy && P.blend)) && !j.clipR[0])) {
+            mvx_set_error("mvx_flow_frames: dst / clip_left / clip_right are required"); return MVX_E_ARG;
+        }
+    }
+    HIP_CHECK(hipMemcpyAsync(h->dJobs, hj.data(), sizeof(FLJob) * nframes, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(flow_usable_kernel, dim3(nframes, 4), dim3(256), 0, st, h->dP, h->dJobs, h->dFlags);
+    HIP_CHECK(hipMemsetAsync(h->dSmall, 0, (size_t)nframes * 2 * cellsN * sizeof(int), st));
+    hipLaunchKernelGGL(flow_occ_kernel, dim3((P.nBlk + 255) / 256, 2, nframes), dim3(256), 0, st, h->dP, h->dJobs, h->dFlags, h->dSmall);
+    hipLaunchKernelGGL(flow_cells_kernel, dim3((unsigned)((cellsN + 255) / 256), nframes), dim3(256), 0, st, h->dP, h->dJobs, h->dFlags, h->dSmall, h->dCells, h->dMasks);
+    // CW consecutive samples per thread: the widest of 16 bytes that divides the plane width (the tables cover nWidthP >= the width)
+    for (int cls = 0; cls < (P.nplanes > 1 ? 2 : 1); cls++) {
+        const int p0 = cls, npl = cls ? 2 : 1;
+        const PlaneG &g = P.pl[p0];
+        int cw = 16 / P.bps;
+        while (cw > 1 && g.W % cw) cw >>= 1;
+        dim3 grid((unsigned)((g.W / cw + 63) / 64), (unsigned)((g.H + 3) / 4), (unsigned)(nframes * npl));
+#define FK(TT, W_) hipLaunchKernelGGL((flow_kernel<TT, W_>), grid, dim3(256), 0, st, h->dP, h->dJobs, h->dFlags, h->dCells, h->dMasks, p0, npl)
+        if (P.bps == 1) { if (cw == 16) FK(uint8_t, 16); else if (cw == 8) FK(uint8_t, 8); else if (cw == 4) FK(uint8_t, 4); else if (cw == 2) FK(uint8_t, 2); else FK(uint8_t, 1); }
+        else { if (cw == 8) FK(uint16_t, 8); else if (cw == 4) FK(uint16_t, 4); else if (cw == 2) FK(uint16_t, 2); else FK(uint16_t, 1); }
+#undef FK
+    }
+    HIP_CHECK(hipGetLastError());
+    return MVX_OK;
+}

@@ -4,6 +4,7 @@
     core.mv.Analyse(super, ...)         -> Analyse(super, num_frames, ...)       .run(jobs)
     core.mv.Degrain1..6(clip, super, mvbw, mvfw, ...) -> Degrain(radius, super, analysis_data, ...) .run(jobs)
     core.mv.Compensate(clip, super, vectors, ...)     -> Compensate(super, analysis_data, ...)      .run(jobs)
+    core.mv.FlowInter / FlowFPS(clip, super, mvbw, mvfw, ...) -> FlowInter / FlowFPS(super, bw_data, fw_data, ...) .run(ns, ...)
 
 Argument names, defaults and error strings are the reference's (MVSuper.c:279-291, MVAnalyse.c:639-671,
 MVDegrains.cpp:813-932, MVCompensate.c:579-592); they are resolved inside the library, not here.
@@ -101,6 +102,21 @@ class BlockFPSJob(C.Structure):
                 ("blob_bw", C.c_void_p), ("clip_left", C.c_void_p * 3), ("clip_right", C.c_void_p * 3), ("dst", C.c_void_p * 3)]
 
 
+class FlowInterArgs(C.Structure):
+    _fields_ = [("time", C.c_double), ("ml", C.c_double), ("blend", C.c_int32), ("thscd1", C.c_int64), ("thscd2", C.c_int32)]
+
+
+class FlowFPSArgs(C.Structure):
+    _fields_ = [("num", C.c_int64), ("den", C.c_int64), ("mask", C.c_int32), ("ml", C.c_double), ("blend", C.c_int32), ("thscd1", C.c_int64),
+                ("thscd2", C.c_int32)]
+
+
+class FlowJob(C.Structure):
+    _fields_ = [("time256", C.c_int32), ("reserved", C.c_int32), ("super_left", C.c_void_p * 3), ("super_right", C.c_void_p * 3), ("blob_fw", C.c_void_p),
+                ("blob_bw", C.c_void_p), ("blob_fw_extra", C.c_void_p), ("blob_bw_extra", C.c_void_p), ("clip_left", C.c_void_p * 3),
+                ("clip_right", C.c_void_p * 3), ("dst", C.c_void_p * 3)]
+
+
 _lib = None
 
 
@@ -164,6 +180,14 @@ def lib():
         L.mvx_blockfps_get_info.argtypes = [C.c_void_p, P(BlockFPSInfo)]
         L.mvx_blockfps_map.argtypes = [C.c_void_p, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int)]
         L.mvx_blockfps_frames.argtypes = [C.c_void_p, C.c_int, P(BlockFPSJob), C.c_void_p]
+        L.mvx_flowinter_create.argtypes = [P(FlowInterArgs), P(AnalysisData), P(AnalysisData), C.c_void_p, C.c_int, P(C.c_ssize_t), P(C.c_ssize_t),
+                                           P(C.c_ssize_t), P(C.c_void_p), C.c_char_p]
+        L.mvx_flowfps_create.argtypes = [P(FlowFPSArgs), P(AnalysisData), P(AnalysisData), C.c_void_p, C.c_int, C.c_int64, C.c_int64, P(C.c_ssize_t),
+                                         P(C.c_ssize_t), P(C.c_ssize_t), P(C.c_void_p), C.c_char_p]
+        L.mvx_flow_destroy.argtypes = [C.c_void_p]
+        L.mvx_flow_get_info.argtypes = [C.c_void_p, P(BlockFPSInfo)]
+        L.mvx_flow_map.argtypes = [C.c_void_p, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int)]
+        L.mvx_flow_frames.argtypes = [C.c_void_p, C.c_int, P(FlowJob), C.c_void_p]
         L.mvx_scale_thscd.argtypes = [P(C.c_int64), P(C.c_int32), P(AnalysisData)]
         L.mvx_vectors_size.argtypes = [P(AnalysisData)]
         L.mvx_vectors_size.restype = C.c_int
@@ -628,6 +652,99 @@ class BlockFPS:
                 arr[k].blob_bw = blobs_bw[nl].data_ptr()
         _check(lib().mvx_blockfps_frames(self.h, n, arr, _stream()))
         return out
+
+
+class _Flow:
+    """the engine both flow filters share (mvx_flow_*); subclasses create the handle"""
+
+    def __init__(self, sup, num_frames, create):
+        self.sup = sup
+        self.h = C.c_void_p()
+        err = C.create_string_buffer(ERRLEN)
+        _check(create(C.byref(self.h), err), err)
+        self.in_frames = int(num_frames)
+        info = BlockFPSInfo()
+        lib().mvx_flow_get_info(self.h, C.byref(info))
+        self.num_frames, self.fps_num, self.fps_den = info.num_frames, info.fps_num, info.fps_den
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().mvx_flow_destroy(self.h)
+        except Exception:
+            pass
+
+    def map(self, n):
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        lib().mvx_flow_map(self.h, n, C.byref(a), C.byref(b), C.byref(c))
+        return a.value, b.value, c.value
+
+    def run(self, ns, clip, supers, blobs_bw, blobs_fw, out=None):
+        """ns: output frame numbers, one job each, all in one call; clip / supers: device frames of the input clip and its super clip;
+        blobs_bw / blobs_fw: per input frame device blobs of the two vector clips (mvbw at n, mvfw at n).  The main vectors are mvbw at
+        nleft and mvfw at nright, the extra ones mvfw at nleft and mvbw at nright."""
+        arr, out = self.jobs(ns, clip, supers, blobs_bw, blobs_fw, out)
+        self.launch(arr)
+        return out
+
+    def launch(self, arr):
+        """enqueues a job table made by jobs()"""
+        _check(lib().mvx_flow_frames(self.h, len(arr), arr, _stream()))
+
+    def jobs(self, ns, clip, supers, blobs_bw, blobs_fw, out=None):
+        """the job table of run() and its output frames, without launching"""
+        _torch()
+        n = len(ns)
+        if out is None:
+            out = arena_frames(n, [tuple(p.shape) for p in clip[0]], clip[0][0].device, zero=False)
+        arr = (FlowJob * n)()
+        last = self.in_frames - 1
+        for k, fo in enumerate(ns):
+            nl, nr, t = self.map(fo)
+            arr[k].time256 = t
+            L, R = clip[min(nl, last)], clip[min(nr, last)]
+            for p in range(self.sup.nplanes):
+                arr[k].clip_left[p] = L[p].data_ptr()
+                arr[k].clip_right[p] = R[p].data_ptr()
+                arr[k].dst[p] = out[k][p].data_ptr()
+            if nl < self.in_frames and nr < self.in_frames:
+                for p in range(self.sup.nplanes):
+                    arr[k].super_left[p] = supers[nl][p].data_ptr()
+                    arr[k].super_right[p] = supers[nr][p].data_ptr()
+                arr[k].blob_fw = blobs_fw[nr].data_ptr()
+                arr[k].blob_bw = blobs_bw[nl].data_ptr()
+                arr[k].blob_fw_extra = blobs_fw[nl].data_ptr()
+                arr[k].blob_bw_extra = blobs_bw[nr].data_ptr()
+        return arr, out
+
+
+def _pad3(l):
+    return (C.c_ssize_t * 3)(*(list(l) + [0] * (3 - len(l))))
+
+
+class FlowInter(_Flow):
+    """mv.FlowInter(clip, super, mvbw, mvfw, time, ml, blend, thscd1, thscd2) -- MVFlowInter.c:473-678.  Output frame n lies `time` percent
+    of the way from input frame n to n + delta; `clip_pitch` is the row pitch of the clip's device planes (and of the output)."""
+
+    def __init__(self, sup, ad_bw, ad_fw, num_frames, clip_pitch, time=50.0, ml=100.0, blend=None, thscd1=None, thscd2=None):
+        a = FlowInterArgs(float(time), float(ml), _u(blend), _u(thscd1), _u(thscd2))
+        bw = AnalysisData.from_buffer_copy(bytes(ad_bw))
+        fw = AnalysisData.from_buffer_copy(bytes(ad_fw))
+        super().__init__(sup, num_frames, lambda h, err: lib().mvx_flowinter_create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, int(num_frames), _pad3(sup.pitch),
+                                                                                     _pad3(clip_pitch), _pad3(clip_pitch), h, err))
+
+
+class FlowFPS(_Flow):
+    """mv.FlowFPS(clip, super, mvbw, mvfw, num, den, mask, ml, blend, thscd1, thscd2) -- MVFlowFPS.c:565-878.  `fps_num / fps_den` is the
+    input clip's frame rate; `clip_pitch` the row pitch of its device planes (and of the output)."""
+
+    def __init__(self, sup, ad_bw, ad_fw, num_frames, clip_pitch, fps_num=24, fps_den=1, num=None, den=None, mask=None, ml=100.0, blend=None, thscd1=None,
+                 thscd2=None):
+        a = FlowFPSArgs(_u(num), _u(den), _u(mask), float(ml), _u(blend), _u(thscd1), _u(thscd2))
+        bw = AnalysisData.from_buffer_copy(bytes(ad_bw))
+        fw = AnalysisData.from_buffer_copy(bytes(ad_fw))
+        super().__init__(sup, num_frames, lambda h, err: lib().mvx_flowfps_create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, int(num_frames), int(fps_num),
+                                                                                   int(fps_den), _pad3(sup.pitch), _pad3(clip_pitch), _pad3(clip_pitch), h, err))
 
 
 class Recalculate:
