@@ -348,6 +348,68 @@ typedef struct mvx_flow_job {
  * all jobs: one for the luma planes, one for both chroma planes (Gray: the luma launch only) */
 int mvx_flow_frames(mvx_flow *h, int nframes, const mvx_flow_job *jobs, void *stream);
 
+/* ---- mv.Flow / mv.FlowBlur ------------------------------------------------------------------------
+ * per-sample motion compensation and motion blur on the flow machinery above (int16 vector upsizing per sample, the super clip
+ * read as the Finest frame).
+ * mvx_flowcomp_create replaces mvflowCreate, MVFlow.cpp:391-593; mvx_flowcomp_frames replaces mvflowGetFrame, MVFlow.cpp:163-370
+ * (fetch :93-116, shift :119-148).  mvx_flowblur_create replaces mvflowblurCreate, MVFlowBlur.c:346-552; mvx_flowblur_frames replaces
+ * mvflowblurGetFrame, MVFlowBlur.c:143-326 (RealFlowBlur :72-130).
+ * Deliberate divergence: both reject frames less than two blocks wide or high, where the reference's upsizer reads outside its buffers. */
+
+typedef struct mvx_flowcomp_args {
+    double time;             /* percent of the vector, 0..100 (a double argument in the reference: time256 is formed in double); pass 100.0 for the default */
+    int32_t mode;            /* 0 fetch, 1 shift; MVX_UNSET -> 0 */
+    int32_t fields;          /* MVX_UNSET -> 0; the caller computes each job's field_shift from it */
+    int64_t thscd1; int32_t thscd2;
+} mvx_flowcomp_args;
+
+typedef struct mvx_flowcomp mvx_flowcomp;
+
+/* accepts vectors with absolute frame references (delta <= 0) */
+int mvx_flowcomp_create(const mvx_flowcomp_args *args, const mvx_analysis_data *vectors, const mvx_super *super_clip, int num_frames,
+                        const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flowcomp **out, char *err);
+void mvx_flowcomp_destroy(mvx_flowcomp *h);
+/* the reference frame of output frame n: n +- delta by isb, or -delta for absolute references (MVFlow.cpp:170-176) */
+int mvx_flowcomp_ref(const mvx_flowcomp *h, int n);
+
+typedef struct mvx_flowcomp_job {
+    const void *ref_super[3];    /* super frame mvx_flowcomp_ref(n); NULL (nref outside the clip) = copy clip */
+    const void *blob;            /* vectors at n; NULL = copy clip; unusable vectors copy clip too (MVFlow.cpp:364-368) */
+    const void *clip[3];         /* clip frame n */
+    void *dst[3];
+    int32_t field_shift;         /* MVFlow.cpp:264-302: +-pel/2 when fields=1, pel>1, (nref-n) odd and the field parities differ; else 0 */
+    int32_t reserved;
+} mvx_flowcomp_job;
+
+/* nframes jobs of one handle in one batch on `stream`: two small per-job kernels, then one launch per kernel and plane class (luma / both
+ * chroma planes) over all jobs.  Mode 1 (shift) scatters into a winner buffer of 8 bytes per sample and job, held by the handle and grown
+ * to the largest call. */
+int mvx_flowcomp_frames(mvx_flowcomp *h, int nframes, const mvx_flowcomp_job *jobs, void *stream);
+
+typedef struct mvx_flowblur_args {
+    double blur;             /* percent, 0..200 (a float argument in the reference: blur256 is formed in float); pass 50.0 for the default */
+    int32_t prec;            /* >= 1; MVX_UNSET -> 1 */
+    int64_t thscd1; int32_t thscd2;
+} mvx_flowblur_args;
+
+typedef struct mvx_flowblur mvx_flowblur;
+
+int mvx_flowblur_create(const mvx_flowblur_args *args, const mvx_analysis_data *mvbw, const mvx_analysis_data *mvfw, const mvx_super *super_clip,
+                        int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flowblur **out,
+                        char *err);
+void mvx_flowblur_destroy(mvx_flowblur *h);
+
+typedef struct mvx_flowblur_job {
+    const void *super[3];        /* super frame n; NULL = copy clip */
+    const void *blob_bw;         /* mvbw at n - delta } NULL when n - delta < 0 or n + delta >= num_frames = copy clip; */
+    const void *blob_fw;         /* mvfw at n + delta }   unusable vectors copy clip too (MVFlowBlur.c:158-178,318-322) */
+    const void *clip[3];         /* clip frame n */
+    void *dst[3];
+} mvx_flowblur_job;
+
+/* nframes jobs in one batch on `stream`: two small per-job kernels, then one launch for the luma planes and one for both chroma planes */
+int mvx_flowblur_frames(mvx_flowblur *h, int nframes, const mvx_flowblur_job *jobs, void *stream);
+
 /* ---- mv.SCDetection -------------------------------------------------------------------------------
  * replaces the decision of mvscdetectionGetFrame, MVSCDetection.c:43-73 (arg string :137-145): scene_change[i] (HOST array) =
  * !usable(blobs[i]) for n device blobs of one vector clip, i.e. the value of _SceneChangePrev (forward vectors) or

@@ -1,0 +1,22 @@
+"""Writes tests/golden/flowblur_ref_objects.json: digests of the reference's AVX2 int16 vector resizer (SimpleResize_AVX2.cpp, from
+oracle/_ref) on FlowBlur's unpadded geometries that tests/test_flowmc_host.py uses, so that the test also runs where oracle/_ref is absent.
+
+    python tests/golden/make_flowblur_ref_objects.py
+"""
+import json
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path[:0] = [os.path.dirname(HERE), os.path.join(os.path.dirname(os.path.dirname(HERE)), "oracle")]
+
+import test_flow_ref as t  # noqa: E402
+import test_flowmc_host as m  # noqa: E402
+
+if __name__ == "__main__":
+    lib = t.ref_lib()
+    assert lib is not None, "needs oracle/_ref (make -C oracle ref)"
+    out = [t.digest(t.ref_resize_i16(lib, *g)) for g in m.GEOMETRIES]
+    with open(os.path.join(HERE, "flowblur_ref_objects.json"), "w") as f:
+        json.dump({"simpleResize_int16_t_avx2": out}, f, indent=1)
+    print("wrote %d digests" % len(out))

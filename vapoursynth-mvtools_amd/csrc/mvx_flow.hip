@@ -1,4 +1,4 @@
-// mvx_flow.hip -- mv.FlowInter and mv.FlowFPS on gfx950.
+// mvx_flow.hip -- mv.FlowInter and mv.FlowFPS on gfx950; mv.Flow and mv.FlowBlur on the same machinery (second half of the file).
 //
 // The reference builds, per output frame and plane class, full-resolution int16 vector planes (SimpleResize.cpp:60-121 on the
 // block-resolution fields of MaskFun.cpp:169-203) and full-resolution occlusion masks, then runs FlowInterSimple / FlowInter /
@@ -261,19 +261,32 @@ static bool flow_similarity(const mvx_analysis_data *a, const mvx_analysis_data 
     return bad;
 }
 
-// the checks both filters share after their own argument checks (MVFlowInter.c:540-574 / MVFlowFPS.c:646-671), then the geometry
-// (MVFlowInter.c:651-678, MVFlowFPS.c:776-802)
-static int flow_common(mvx_flow *h, const char *name, int64_t thscd1, int32_t thscd2, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
-                       const mvx_super_info &si, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], char *err) {
-    if (thscd1 > 8 * 8 * 255) FFAIL("%s: thscd1 can be at most %d.", name, 8 * 8 * 255);
-    mvx_scale_thscd(&thscd1, &thscd2, bw);
+// MVAnalysisData.c:7-31 scaleThSCD with its limit check
+static int flow_thscd(const char *name, int64_t *thscd1, int32_t *thscd2, const mvx_analysis_data *ad, char *err) {
+    if (*thscd1 > 8 * 8 * 255) FFAIL("%s: thscd1 can be at most %d.", name, 8 * 8 * 255);
+    mvx_scale_thscd(thscd1, thscd2, ad);
+    return MVX_OK;
+}
+
+// the two-clip checks FlowInter, FlowFPS and FlowBlur share after their own argument checks (MVFlowInter.c:540-574, MVFlowFPS.c:646-671,
+// MVFlowBlur.c:410-470)
+static int flow_pair_checks(const char *name, int64_t *thscd1, int32_t *thscd2, const mvx_analysis_data *bw, const mvx_analysis_data *fw, char *err) {
+    if (int rc = flow_thscd(name, thscd1, thscd2, bw, err)) return rc;
     if (flow_similarity(bw, fw, name, err)) { mvx_set_error("%s", err); return MVX_E_ARG; }
     // FlowInter's check; FlowFPS lacks it in the reference and then reads negative frame numbers: rejected here on purpose
     if (bw->nDeltaFrame <= 0 || fw->nDeltaFrame <= 0) FFAIL("%s: cannot use motion vectors with absolute frame references.", name);
     if (bw->nDeltaFrame != fw->nDeltaFrame) FFAIL("%s: mvbw and mvfw must be generated with the same delta.", name);
     if (!bw->isBackward) FFAIL("%s: mvbw must be generated with isb=True.", name);
     if (fw->isBackward) FFAIL("%s: mvfw must be generated with isb=False.", name);
-    FLParams &P = h->P;
+    return MVX_OK;
+}
+
+// the geometry of every flow filter: padded small fields and upsizer tables to nWidthP / nHeightP (MVFlowInter.c:651-678,
+// MVFlowFPS.c:776-802, MVFlow.cpp:535-562), or with padded = false FlowBlur's unpadded fields and tables that end at the frame
+// (MVFlowBlur.c:525-536), so that a frame the block grid does not cover gets a stretched grid
+static int flow_geometry(FLParams &P, int nWidthP[2], int nHeightP[2], const char *name, int64_t thscd1, int32_t thscd2, const mvx_analysis_data *bw,
+                         const mvx_super_info &si, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], bool padded,
+                         char *err) {
     memset(&P, 0, sizeof(P));
     P.thscd1 = thscd1; P.thscd2 = thscd2;
     P.nplanes = (si.modeYUV & 6) && si.num_planes > 1 ? 3 : 1;
@@ -282,14 +295,19 @@ static int flow_common(mvx_flow *h, const char *name, int64_t thscd1, int32_t th
     P.nBlkX = bw->nBlkX; P.nBlkY = bw->nBlkY; P.nBlk = bw->nBlkX * bw->nBlkY; P.nLvCount = bw->nLvCount;
     P.stepX = bw->nBlkSizeX - bw->nOverlapX; P.stepY = bw->nBlkSizeY - bw->nOverlapY;
     P.XP = bw->nBlkX; P.YP = bw->nBlkY;
-    while (P.XP * P.stepX + bw->nOverlapX < bw->nWidth) P.XP++;
-    while (P.YP * P.stepY + bw->nOverlapY < bw->nHeight) P.YP++;
-    h->nWidthP[0] = P.XP * P.stepX + bw->nOverlapX; h->nHeightP[0] = P.YP * P.stepY + bw->nOverlapY;
-    h->nWidthP[1] = h->nWidthP[0] / bw->xRatioUV; h->nHeightP[1] = h->nHeightP[0] / bw->yRatioUV;
+    if (padded) {
+        while (P.XP * P.stepX + bw->nOverlapX < bw->nWidth) P.XP++;
+        while (P.YP * P.stepY + bw->nOverlapY < bw->nHeight) P.YP++;
+        nWidthP[0] = P.XP * P.stepX + bw->nOverlapX; nHeightP[0] = P.YP * P.stepY + bw->nOverlapY;
+        nWidthP[1] = nWidthP[0] / bw->xRatioUV; nHeightP[1] = nHeightP[0] / bw->yRatioUV;
+    } else {
+        nWidthP[0] = bw->nWidth; nHeightP[0] = bw->nHeight;
+        nWidthP[1] = bw->nWidth / bw->xRatioUV; nHeightP[1] = bw->nHeight / bw->yRatioUV;
+    }
     P.limW[0] = bw->nWidth; P.limH[0] = bw->nHeight;
     P.limW[1] = bw->nWidth / bw->xRatioUV; P.limH[1] = bw->nHeight / bw->yRatioUV;
     P.halfX = bw->xRatioUV == 2; P.halfY = bw->yRatioUV == 2;
-    // the upsizer interpolates between small-field cells o and o + 1: with a single padded column or row the reference reads outside its buffers
+    // the upsizer interpolates between small-field cells o and o + 1: with a single (padded) column or row the reference reads outside its buffers
     if (P.XP < 2 || P.YP < 2) FFAIL("%s: the frame must be at least two blocks wide and two blocks high.", name);
     if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) FFAIL("%s: U and V super planes must share one pitch.", name);
     const int xSub = mvx_ilog2(si.xRatioUV), ySub = mvx_ilog2(si.yRatioUV);
@@ -303,7 +321,31 @@ static int flow_common(mvx_flow *h, const char *name, int64_t thscd1, int32_t th
         g.supPlaneStride = g.supPitch * (long long)((si.height >> sy) + 2 * (si.vpad >> sy));
         P.clipPitch[p] = clip_pitch[q];
     }
+    return MVX_OK;
+}
+
+// FlowInter / FlowFPS: the two-clip checks, then the padded geometry
+static int flow_common(mvx_flow *h, const char *name, int64_t thscd1, int32_t thscd2, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
+                       const mvx_super_info &si, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], char *err) {
+    if (int rc = flow_pair_checks(name, &thscd1, &thscd2, bw, fw, err)) return rc;
+    if (int rc = flow_geometry(h->P, h->nWidthP, h->nHeightP, name, thscd1, thscd2, bw, si, super_pitch, clip_pitch, dst_pitch, true, err)) return rc;
     h->delta = bw->nDeltaFrame;
+    return MVX_OK;
+}
+
+// upsizer tables (SimpleResize.cpp:27-57) from the XP x YP small fields to nWidthP / nHeightP (luma, chroma) and the parameter block, on the device
+static int flow_upload(FLParams &P, const int nWidthP[2], const int nHeightP[2], int **dTables, FLParams **dP) {
+    const int n = nWidthP[0] + nWidthP[1] + nHeightP[0] + nHeightP[1];
+    std::vector<int> t(2 * n);
+    int *o = t.data(), *w = t.data() + n, pos = 0;
+    HIP_CHECK(hipMalloc((void **)dTables, sizeof(int) * 2 * n));
+    for (int c = 0; c < 2; c++) {
+        bf_tables(o + pos, w + pos, nWidthP[c], P.XP); P.hOff[c] = *dTables + pos; P.hW[c] = *dTables + n + pos; pos += nWidthP[c];
+        bf_tables(o + pos, w + pos, nHeightP[c], P.YP); P.vOff[c] = *dTables + pos; P.vW[c] = *dTables + n + pos; pos += nHeightP[c];
+    }
+    HIP_CHECK(hipMemcpy(*dTables, t.data(), sizeof(int) * 2 * n, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMalloc((void **)dP, sizeof(FLParams)));
+    HIP_CHECK(hipMemcpy(*dP, &P, sizeof(FLParams), hipMemcpyHostToDevice));
     return MVX_OK;
 }
 
@@ -398,19 +440,8 @@ extern "C" __attribute__((visibility("default"))) int mvx_flow_frames(mvx_flow *
     hipStream_t st = (hipStream_t)stream;
     CallGuard::Scope scope(h->guard, st);
     FLParams &P = h->P;
-    if (!h->dP) { // upsizer tables (SimpleResize.cpp:27-57, MVFlowInter.c:677-679) + parameter block
-        const int n = h->nWidthP[0] + h->nWidthP[1] + h->nHeightP[0] + h->nHeightP[1];
-        std::vector<int> t(2 * n);
-        int *o = t.data(), *w = t.data() + n, pos = 0;
-        HIP_CHECK(hipMalloc((void **)&h->dTables, sizeof(int) * 2 * n));
-        for (int c = 0; c < 2; c++) {
-            bf_tables(o + pos, w + pos, h->nWidthP[c], P.XP); P.hOff[c] = h->dTables + pos; P.hW[c] = h->dTables + n + pos; pos += h->nWidthP[c];
-            bf_tables(o + pos, w + pos, h->nHeightP[c], P.YP); P.vOff[c] = h->dTables + pos; P.vW[c] = h->dTables + n + pos; pos += h->nHeightP[c];
-        }
-        HIP_CHECK(hipMemcpy(h->dTables, t.data(), sizeof(int) * 2 * n, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMalloc((void **)&h->dP, sizeof(FLParams)));
-        HIP_CHECK(hipMemcpy(h->dP, &P, sizeof(FLParams), hipMemcpyHostToDevice));
-    }
+    if (!h->dP) // MVFlowInter.c:677-679
+        if (int rc = flow_upload(P, h->nWidthP, h->nHeightP, &h->dTables, &h->dP)) return rc;
     const size_t cellsN = (size_t)P.XP * P.YP;
     if ((size_t)nframes > h->jobsCap) { // exactly this call's size; the capacity is raised only once every buffer exists
         if (h->dJobs) (void)hipFree(h->dJobs);
@@ -465,6 +496,440 @@ extern "C" __attribute__((visibility("default"))) int mvx_flow_frames(mvx_flow *
         else { if (cw == 8) FK(uint16_t, 8); else if (cw == 4) FK(uint16_t, 4); else if (cw == 2) FK(uint16_t, 2); else FK(uint16_t, 1); }
 #undef FK
     }
+    HIP_CHECK(hipGetLastError());
+    return MVX_OK;
+}
+
+// ================================================================================================ mv.Flow and mv.FlowBlur
+//
+// Both stand on the machinery above: usability per blob, int16 small-field cells, the int16 upsizer evaluated at each sample (fl_vup with
+// the upsizer tables of flow_upload) and reads from the super frame as if it were the Finest frame (fl_fetch).  Flow builds the padded
+// fields of FlowInter (MVFlow.cpp:535-562) with field_shift added to every VY cell before the chroma halving (:264-302); FlowBlur builds
+// unpadded fields and tables that end at the frame (MVFlowBlur.c:525-536).  A job whose vectors are unusable copies its clip frame.
+//   fm_usable_kernel   : per (job, blob) -> usable flags
+//   fm_cells_kernel    : per (job, cell) -> one packed int16 pair (vx low, vy high) per vector field
+//   flowcomp_kernel    : Flow mode 0 (fetch), per CW consecutive samples -> one fetch per sample, one wide store
+//   flowshift_scatter  : Flow mode 1 (shift), per CW consecutive source samples -> a 64-bit atomicMax of ((raster index + 1) << 16) | sample
+//                        into the destination's winner; the last writer in raster order has the largest key, whatever the arrival order
+//   flowshift_resolve  : per CW samples -> the winner's sample, or pixel_max where nobody wrote (the reference's memset)
+//   flowblur_kernel    : per sample -> the data-dependent F and B tap loops of RealFlowBlur
+// Each of the last four runs as one launch for the luma planes of all jobs and one for both chroma planes of all jobs.
+struct FMJob {
+    const unsigned char *sup[3];   // Flow: super frame nref; FlowBlur: super frame n; NULL = copy the clip frame
+    const unsigned char *blob[2];  // Flow: vectors at n; FlowBlur: mvbw at n - delta, mvfw at n + delta
+    const unsigned char *clip[3];
+    unsigned char *dst[3];
+    int fieldShift, pad;
+};
+struct FMWin { unsigned long long *win; long long job, off[3]; }; // Flow shift: winners per job and plane, W x H samples each
+
+// Fakery.c:52-58,103-107,144-146 fgopIsUsable per (job, blob) -> flags[job][2]; a blob past nb counts as usable
+__global__ __launch_bounds__(256) void fm_usable_kernel(const FLParams *Pp, const FMJob *jobs, int nb, int *flags) {
+    const FLParams &P = *Pp;
+    const int f = blockIdx.x, k = blockIdx.y;
+    const FMJob &J = jobs[f];
+    const unsigned char *blob = k < nb ? J.blob[k] : nullptr;
+    const bool want = J.sup[0] && blob;
+    __shared__ int cnt;
+    if (threadIdx.x == 0) cnt = 0;
+    __syncthreads();
+    if (want) atomicAdd(&cnt, fps_count_over(blob, P.nLvCount, P.nBlk, P.thscd1));
+    __syncthreads();
+    if (threadIdx.x == 0) flags[f * 2 + k] = k >= nb ? 1 : want && ((const int *)blob)[1] == 1 && !(cnt > P.thscd2);
+}
+__device__ __forceinline__ bool fm_ok(const int *flags, int f) { return flags[2 * f] && flags[2 * f + 1]; }
+
+// MakeVectorSmallMasks into the XP x YP grid (CheckAndPadSmallY where XP / YP exceed the block grid), then VY += fieldShift on every cell
+__global__ __launch_bounds__(256) void fm_cells_kernel(const FLParams *Pp, const FMJob *jobs, int nb, const int *flags, int *cells) {
+    const FLParams &P = *Pp;
+    const int f = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int cellsN = P.XP * P.YP;
+    if (!fm_ok(flags, f) || i >= cellsN) return;
+    const FMJob &J = jobs[f];
+    const int y = i / P.XP, x = i - y * P.XP;
+    const int sb = min(x, P.nBlkX - 1) + min(y, P.nBlkY - 1) * P.nBlkX;
+    for (int k = 0; k < nb; k++) {
+        short vx, vy;
+        fl_padded(mvx_level0(J.blob[k], P.nLvCount), sb, x >= P.nBlkX, y >= P.nBlkY, vx, vy);
+        vy = (short)(vy + J.fieldShift);
+        cells[((size_t)f * cellsN + i) * nb + k] = (int)(unsigned short)vx | ((int)vy << 16);
+    }
+}
+
+// the upsized vector of field k at one sample: vx, vy with the int16 resizer's limits, chroma halving by >> hx / hy on the cells
+struct FMAt {
+    int wt, wb, r0, r1, hx, hy, yLo, yHi;
+    __device__ __forceinline__ void vec(DG_GL const unsigned char *cl, int nb, int k, int o, int wl, int wr, int xLo, int xHi, int &vx, int &vy) const {
+        const int a0 = *(DG_GL const int *)(cl + 4 * ((r0 + o) * nb + k)), b0 = *(DG_GL const int *)(cl + 4 * ((r0 + o + 1) * nb + k));
+        const int a1 = *(DG_GL const int *)(cl + 4 * ((r1 + o) * nb + k)), b1 = *(DG_GL const int *)(cl + 4 * ((r1 + o + 1) * nb + k));
+        vx = fl_vup(fl_lo(a0) >> hx, fl_lo(a1) >> hx, fl_lo(b0) >> hx, fl_lo(b1) >> hx, wt, wb, wl, wr, xLo, xHi);
+        vy = fl_vup(fl_hi(a0) >> hy, fl_hi(a1) >> hy, fl_hi(b0) >> hy, fl_hi(b1) >> hy, wt, wb, wl, wr, yLo, yHi);
+    }
+};
+__device__ __forceinline__ FMAt fm_at(const FLParams &P, int c, int y) {
+    FMAt a;
+    a.wb = *(DG_GL const int *)dg_gl(P.vW[c] + y); a.wt = 16384 - a.wb;
+    a.r0 = *(DG_GL const int *)dg_gl(P.vOff[c] + y) * P.XP; a.r1 = a.r0 + P.XP;
+    a.hx = c && P.halfX ? 1 : 0; a.hy = c && P.halfY ? 1 : 0;
+    a.yLo = -y * P.pel; a.yHi = (P.limH[c] - y) * P.pel - 1;
+    return a;
+}
+
+// the output samples x .. x + CW - 1 of row y of job f, plane p: the clip frame's, when the job copies
+template <typename T, int CW>
+__device__ __forceinline__ bool fm_copy(const FLParams &P, const FMJob &J, const int *flags, int f, int p, int x, int y, DG_GL unsigned char *dptr) {
+    if (fm_ok(flags, f)) return false;
+    int l[CW];
+    fl_load<T, CW>(dg_gl(J.clip[p] + (long long)y * P.clipPitch[p] + (long long)x * (long long)sizeof(T)), l);
+    fl_store<T, CW>(dptr, l);
+    return true;
+}
+
+// MVFlow.cpp:93-116 flowFetch: v = (V * time256 + 128) >> 8, the sample Finest(nref)[(h << lp) + vy][(w << lp) + vx]
+template <typename T, int CW>
+__global__ __launch_bounds__(256) void flowcomp_kernel(const FLParams *Pp, const FMJob *jobs, const int *flags, const int *cells, int time256,
+                                                       int planeFirst, int planesPerFrame) {
+    const FLParams &P = *Pp;
+    const int z = blockIdx.z, f = z / planesPerFrame, p = planeFirst + z % planesPerFrame;
+    const PlaneG &g = P.pl[p];
+    const int x = (blockIdx.x * 64 + (threadIdx.x & 63)) * CW, y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= g.W || y >= g.H) return;
+    const FMJob &J = jobs[f];
+    DG_GL unsigned char *dptr = dg_glw(J.dst[p] + (long long)y * g.dstPitch + (long long)x * (long long)sizeof(T));
+    if (fm_copy<T, CW>(P, J, flags, f, p, x, y, dptr)) return;
+    const int c = p ? 1 : 0;
+    const FMAt at = fm_at(P, c, y);
+    int hO[CW], hWr[CW];
+    dg_load_ints<CW>(dg_gl(P.hOff[c] + x), hO);
+    dg_load_ints<CW>(dg_gl(P.hW[c] + x), hWr);
+    DG_GL const unsigned char *cl = dg_gl(cells + (size_t)f * P.XP * P.YP);
+    const int Y = y << P.logPel;
+    int out[CW];
+#pragma unroll
+    for (int i = 0; i < CW; i++) {
+        const int xi = x + i;
+        int vx, vy;
+        at.vec(cl, 1, 0, hO[i], 16384 - hWr[i], hWr[i], -xi * P.pel, (P.limW[c] - xi) * P.pel - 1, vx, vy);
+        out[i] = fl_fetch<T>(P, g, J.sup[p], (xi << P.logPel) + ((vx * time256 + 128) >> 8), Y + ((vy * time256 + 128) >> 8));
+    }
+    fl_store<T, CW>(dptr, out);
+}
+
+// MVFlow.cpp:119-148 flowShift, the scatter: source sample (y, x) = Finest(nref)[y << lp][x << lp] (sub-plane 0 of the super frame, so
+// CW of them are one wide load) goes to (y + vy, x + vx) with v = (-V * time256 + (128 << lp)) >> (8 + lp), when that lies inside the plane
+template <typename T, int CW>
+__global__ __launch_bounds__(256) void flowshift_scatter(const FLParams *Pp, const FMJob *jobs, const int *flags, const int *cells, int time256, FMWin w,
+                                                         int planeFirst, int planesPerFrame) {
+    const FLParams &P = *Pp;
+    const int z = blockIdx.z, f = z / planesPerFrame, p = planeFirst + z % planesPerFrame;
+    const PlaneG &g = P.pl[p];
+    const int x = (blockIdx.x * 64 + (threadIdx.x & 63)) * CW, y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= g.W || y >= g.H || !fm_ok(flags, f)) return;
+    const FMJob &J = jobs[f];
+    const int c = p ? 1 : 0;
+    const FMAt at = fm_at(P, c, y);
+    int hO[CW], hWr[CW], s[CW];
+    dg_load_ints<CW>(dg_gl(P.hOff[c] + x), hO);
+    dg_load_ints<CW>(dg_gl(P.hW[c] + x), hWr);
+    fl_load<T, CW>(dg_gl(J.sup[p] + sup_offset(g, P.pel, P.logPel, (int)sizeof(T), x << P.logPel, y << P.logPel)), s);
+    DG_GL const unsigned char *cl = dg_gl(cells + (size_t)f * P.XP * P.YP);
+    DG_GL unsigned long long *win = (DG_GL unsigned long long *)(unsigned long long)(w.win + f * w.job + w.off[p]);
+    const int lp = P.logPel, rounding = 128 << lp, shift = 8 + lp;
+#pragma unroll
+    for (int i = 0; i < CW; i++) {
+        const int xi = x + i;
+        int vx, vy;
+        at.vec(cl, 1, 0, hO[i], 16384 - hWr[i], hWr[i], -xi * P.pel, (P.limW[c] - xi) * P.pel - 1, vx, vy);
+        const int dx = xi + ((-vx * time256 + rounding) >> shift), dy = y + ((-vy * time256 + rounding) >> shift);
+        if (dx >= 0 && dx < g.W && dy >= 0 && dy < g.H) {
+            const unsigned long long key = ((unsigned long long)((long long)y * g.W + xi + 1) << 16) | (unsigned)s[i];
+            __hip_atomic_fetch_max(win + (long long)dy * g.W + dx, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// MVFlow.cpp:312,336-337 + the scatter's result: the low 16 bits of the winner, pixel_max where no source landed
+typedef unsigned long long fm_u64x2 __attribute__((ext_vector_type(2), aligned(8)));
+template <typename T, int CW>
+__global__ __launch_bounds__(256) void flowshift_resolve(const FLParams *Pp, const FMJob *jobs, const int *flags, FMWin w, int planeFirst, int planesPerFrame) {
+    const FLParams &P = *Pp;
+    const int z = blockIdx.z, f = z / planesPerFrame, p = planeFirst + z % planesPerFrame;
+    const PlaneG &g = P.pl[p];
+    const int x = (blockIdx.x * 64 + (threadIdx.x & 63)) * CW, y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= g.W || y >= g.H) return;
+    const FMJob &J = jobs[f];
+    DG_GL unsigned char *dptr = dg_glw(J.dst[p] + (long long)y * g.dstPitch + (long long)x * (long long)sizeof(T));
+    if (fm_copy<T, CW>(P, J, flags, f, p, x, y, dptr)) return;
+    DG_GL const unsigned long long *win = (DG_GL const unsigned long long *)(unsigned long long)(w.win + f * w.job + w.off[p] + (long long)y * g.W + x);
+    const int pixel_max = (1 << P.bits) - 1;
+    int out[CW];
+    if constexpr (CW == 1) {
+        const unsigned long long k = *win;
+        out[0] = k ? (int)(k & 0xffff) : pixel_max;
+    } else {
+#pragma unroll
+        for (int i = 0; i < CW; i += 2) {
+            const fm_u64x2 k = *(DG_GL const fm_u64x2 *)(win + i);
+            out[i] = k[0] ? (int)(k[0] & 0xffff) : pixel_max;
+            out[i + 1] = k[1] ? (int)(k[1] & 0xffff) : pixel_max;
+        }
+    }
+    fl_store<T, CW>(dptr, out);
+}
+
+// MVFlowBlur.c:72-130 RealFlowBlur at one sample, F then B: m = (max(|v0x|, |v0y|) / prec) >> 8 taps at ((i + 1) * v0 >> 8) with
+// v0 = V * blur256 / m (C's truncating division; >> is arithmetic), the mean of the sample and the taps.  Every tap lies inside the
+// frame: the upsizer limits |V| to the frame, and |(i + 1) * v0| <= |V * blur256| with blur256 <= 256.  The sum stays int32 as in the
+// reference: it holds 16-bit samples while mF + mB < 32767.
+template <typename T>
+__device__ __forceinline__ int fb_taps(const FLParams &P, const PlaneG &g, const unsigned char *sup, int X, int Y, int vx, int vy, int blur256, int prec,
+                                       int &sum) {
+    int vx0 = vx * blur256, vy0 = vy * blur256;
+    const int m = (max(abs(vx0), abs(vy0)) / prec) >> 8;
+    if (m > 0) {
+        vx0 /= m; vy0 /= m;
+        int ax = vx0, ay = vy0;
+        for (int i = 0; i < m; i++) {
+            sum += fl_fetch<T>(P, g, sup, X + (ax >> 8), Y + (ay >> 8));
+            ax += vx0; ay += vy0;
+        }
+    }
+    return m;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void flowblur_kernel(const FLParams *Pp, const FMJob *jobs, const int *flags, const int *cells, int blur256, int prec,
+                                                       int planeFirst, int planesPerFrame) {
+    const FLParams &P = *Pp;
+    const int z = blockIdx.z, f = z / planesPerFrame, p = planeFirst + z % planesPerFrame;
+    const PlaneG &g = P.pl[p];
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= g.W || y >= g.H) return;
+    const FMJob &J = jobs[f];
+    DG_GL unsigned char *dptr = dg_glw(J.dst[p] + (long long)y * g.dstPitch + (long long)x * (long long)sizeof(T));
+    if (fm_copy<T, 1>(P, J, flags, f, p, x, y, dptr)) return;
+    const int c = p ? 1 : 0;
+    const FMAt at = fm_at(P, c, y);
+    const int o = *(DG_GL const int *)dg_gl(P.hOff[c] + x), wr = *(DG_GL const int *)dg_gl(P.hW[c] + x);
+    DG_GL const unsigned char *cl = dg_gl(cells + (size_t)f * P.XP * P.YP * 2);
+    const int xLo = -x * P.pel, xHi = (P.limW[c] - x) * P.pel - 1;
+    int vxB, vyB, vxF, vyF;
+    at.vec(cl, 2, 0, o, 16384 - wr, wr, xLo, xHi, vxB, vyB);
+    at.vec(cl, 2, 1, o, 16384 - wr, wr, xLo, xHi, vxF, vyF);
+    const int X = x << P.logPel, Y = y << P.logPel;
+    int sum = fl_fetch<T>(P, g, J.sup[p], X, Y);
+    const int mF = fb_taps<T>(P, g, J.sup[p], X, Y, vxF, vyF, blur256, prec, sum);
+    const int mB = fb_taps<T>(P, g, J.sup[p], X, Y, vxB, vyB, blur256, prec, sum);
+    const int out = sum / (mF + mB + 1);
+    fl_store<T, 1>(dptr, &out);
+}
+
+// ------------------------------------------------------------------------------------------------ host objects
+
+struct FMEngine {
+    CallGuard guard;
+    FLParams P;
+    FLParams *dP = nullptr;
+    FMJob *dJobs = nullptr;
+    size_t jobsCap = 0;
+    int *dFlags = nullptr, *dCells = nullptr, *dTables = nullptr;
+    unsigned long long *dWin = nullptr;
+    int nWidthP[2], nHeightP[2];
+    int nb = 1;                                  // vector fields per job: Flow 1, FlowBlur 2 (B, F)
+    int numFrames = 0, delta = 0, isb = 0, mode = 0, fields = 0, time256 = 0, blur256 = 0, prec = 1;
+    long long winJob = 0, winOff[3] = {0, 0, 0}; // Flow shift: winner samples per job, per plane offsets
+    ~FMEngine() {
+        if (dP) (void)hipFree(dP);
+        if (dJobs) (void)hipFree(dJobs);
+        if (dFlags) (void)hipFree(dFlags);
+        if (dCells) (void)hipFree(dCells);
+        if (dTables) (void)hipFree(dTables);
+        if (dWin) (void)hipFree(dWin);
+    }
+};
+struct mvx_flowcomp : FMEngine {};
+struct mvx_flowblur : FMEngine {};
+
+// the luma / chroma launches of one per-sample kernel: CW consecutive samples per thread, the widest of at most 16 bytes that divides the
+// plane width (cw1: one sample per thread)
+template <typename F> static void fm_classes(const FLParams &P, int nframes, bool cw1, F &&launch) {
+    for (int cls = 0; cls < (P.nplanes > 1 ? 2 : 1); cls++) {
+        const int p0 = cls, npl = cls ? 2 : 1;
+        const PlaneG &g = P.pl[p0];
+        int cw = cw1 ? 1 : 16 / P.bps;
+        while (cw > 1 && g.W % cw) cw >>= 1;
+        launch(dim3((unsigned)((g.W / cw + 63) / 64), (unsigned)((g.H + 3) / 4), (unsigned)(nframes * npl)), cw, p0, npl);
+    }
+}
+
+// the per-call part both filters share: buffers for nframes jobs, the job table, usability and the cells
+static int fm_prologue(FMEngine *h, int nframes, const std::vector<FMJob> &hj, hipStream_t st) {
+    FLParams &P = h->P;
+    if (!h->dP)
+        if (int rc = flow_upload(P, h->nWidthP, h->nHeightP, &h->dTables, &h->dP)) return rc;
+    const size_t cellsN = (size_t)P.XP * P.YP;
+    const bool shift = h->nb == 1 && h->mode == 1;
+    if ((size_t)nframes > h->jobsCap) { // exactly this call's size; the capacity is raised only once every buffer exists
+        if (h->dJobs) (void)hipFree(h->dJobs);
+        if (h->dFlags) (void)hipFree(h->dFlags);
+        if (h->dCells) (void)hipFree(h->dCells);
+        if (h->dWin) (void)hipFree(h->dWin);
+        h->dJobs = nullptr; h->dFlags = nullptr; h->dCells = nullptr; h->dWin = nullptr;
+        h->jobsCap = 0;
+        const size_t n = (size_t)nframes;
+        HIP_CHECK(hipMalloc((void **)&h->dJobs, n * sizeof(FMJob)));
+        HIP_CHECK(hipMalloc((void **)&h->dFlags, n * 2 * sizeof(int)));
+        HIP_CHECK(hipMalloc((void **)&h->dCells, n * cellsN * h->nb * sizeof(int)));
+        if (shift) HIP_CHECK(hipMalloc((void **)&h->dWin, n * (size_t)h->winJob * sizeof(unsigned long long)));
+        h->jobsCap = n;
+    }
+    HIP_CHECK(hipMemcpyAsync(h->dJobs, hj.data(), sizeof(FMJob) * nframes, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(fm_usable_kernel, dim3(nframes, 2), dim3(256), 0, st, h->dP, h->dJobs, h->nb, h->dFlags);
+    hipLaunchKernelGGL(fm_cells_kernel, dim3((unsigned)((cellsN + 255) / 256), nframes), dim3(256), 0, st, h->dP, h->dJobs, h->nb, h->dFlags, h->dCells);
+    return MVX_OK;
+}
+
+// the geometry part of creation (after each filter's own checks): the size check, then the grid
+static int fm_create(FMEngine *h, const char *name, int64_t thscd1, int32_t thscd2, const mvx_analysis_data *ad, const mvx_super_info &si,
+                     const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], bool padded, char *err) {
+    if (ad->nHeight != si.height || ad->nWidth != si.super_width - si.hpad * 2 || ad->nPel != si.pel) FFAIL("%s: wrong source or super clip frame size.", name);
+    if (int rc = flow_geometry(h->P, h->nWidthP, h->nHeightP, name, thscd1, thscd2, ad, si, super_pitch, clip_pitch, dst_pitch, padded, err)) return rc;
+    long long o = 0;
+    for (int p = 0; p < 3; p++) {
+        h->winOff[p] = o;
+        if (p < h->P.nplanes) o += (long long)h->P.pl[p].W * h->P.pl[p].H;
+    }
+    h->winJob = o;
+    h->delta = ad->nDeltaFrame; h->isb = ad->isBackward;
+    return MVX_OK;
+}
+
+// MVFlow.cpp:391-593 mvflowCreate.  time is a double argument there: time256 is formed in double (FlowInter forms it in float).
+extern "C" __attribute__((visibility("default"))) int mvx_flowcomp_create(const mvx_flowcomp_args *a, const mvx_analysis_data *vectors, const mvx_super *sup,
+        int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flowcomp **out, char *err) {
+    char dummy[MVX_ERRLEN];
+    if (!err) err = dummy;
+    err[0] = 0;
+    *out = nullptr;
+    const double time = a->time;
+    const int mode = a->mode == MVX_UNSET ? 0 : a->mode;
+    int64_t thscd1 = a->thscd1 == MVX_UNSET ? 400 : a->thscd1;
+    int32_t thscd2 = a->thscd2 == MVX_UNSET ? 130 : a->thscd2;
+    if (time < 0.0 || time > 100.0) FFAIL("Flow: time must be between 0 and 100 %% (inclusive).");
+    if (mode < 0 || mode > 1) FFAIL("Flow: mode must be 0 or 1.");
+    if (int rc = flow_thscd("Flow", &thscd1, &thscd2, vectors, err)) return rc;
+    mvx_flowcomp *h = new mvx_flowcomp();
+    if (int rc = fm_create(h, "Flow", thscd1, thscd2, vectors, sup->info, super_pitch, clip_pitch, dst_pitch, true, err)) { delete h; return rc; }
+    h->nb = 1; h->mode = mode;
+    h->fields = a->fields == MVX_UNSET ? 0 : !!a->fields;
+    h->time256 = (int)(time * 256.0 / 100.0);
+    h->numFrames = num_frames;
+    *out = h;
+    return MVX_OK;
+}
+extern "C" __attribute__((visibility("default"))) void mvx_flowcomp_destroy(mvx_flowcomp *h) { delete h; }
+// MVFlow.cpp:170-176: the reference frame of output frame n
+extern "C" __attribute__((visibility("default"))) int mvx_flowcomp_ref(const mvx_flowcomp *h, int n) {
+    return h->delta > 0 ? (h->isb ? n + h->delta : n - h->delta) : -h->delta;
+}
+
+extern "C" __attribute__((visibility("default"))) int mvx_flowcomp_frames(mvx_flowcomp *h, int nframes, const mvx_flowcomp_job *jobs, void *stream) {
+    if (nframes <= 0) return MVX_OK;
+    hipStream_t st = (hipStream_t)stream;
+    CallGuard::Scope scope(h->guard, st);
+    FLParams &P = h->P;
+    std::vector<FMJob> hj(nframes);
+    for (int f = 0; f < nframes; f++) {
+        FMJob &j = hj[f];
+        const mvx_flowcomp_job &s = jobs[f];
+        memset(&j, 0, sizeof(j));
+        const bool comp = s.ref_super[0] && s.blob;
+        for (int p = 0; p < 3; p++) {
+            j.sup[p] = comp ? (const unsigned char *)s.ref_super[p] : nullptr;
+            j.clip[p] = (const unsigned char *)s.clip[p]; j.dst[p] = (unsigned char *)s.dst[p];
+        }
+        j.blob[0] = comp ? (const unsigned char *)s.blob : nullptr;
+        j.fieldShift = s.field_shift;
+        if (!j.dst[0] || !j.clip[0]) { mvx_set_error("mvx_flowcomp_frames: dst / clip are required"); return MVX_E_ARG; }
+    }
+    if (int rc = fm_prologue(h, nframes, hj, st)) return rc;
+    const bool wide = P.bps == 1;
+    if (h->mode == 0) {
+        fm_classes(P, nframes, false, [&](dim3 grid, int cw, int p0, int npl) {
+#define FK(TT, W_) hipLaunchKernelGGL((flowcomp_kernel<TT, W_>), grid, dim3(256), 0, st, h->dP, h->dJobs, h->dFlags, h->dCells, h->time256, p0, npl)
+            if (wide) { if (cw == 16) FK(uint8_t, 16); else if (cw == 8) FK(uint8_t, 8); else if (cw == 4) FK(uint8_t, 4); else if (cw == 2) FK(uint8_t, 2); else FK(uint8_t, 1); }
+            else { if (cw == 8) FK(uint16_t, 8); else if (cw == 4) FK(uint16_t, 4); else if (cw == 2) FK(uint16_t, 2); else FK(uint16_t, 1); }
+#undef FK
+        });
+    } else {
+        const FMWin w = { h->dWin, h->winJob, { h->winOff[0], h->winOff[1], h->winOff[2] } };
+        HIP_CHECK(hipMemsetAsync(h->dWin, 0, (size_t)nframes * h->winJob * sizeof(unsigned long long), st));
+        fm_classes(P, nframes, false, [&](dim3 grid, int cw, int p0, int npl) {
+#define FK(TT, W_) hipLaunchKernelGGL((flowshift_scatter<TT, W_>), grid, dim3(256), 0, st, h->dP, h->dJobs, h->dFlags, h->dCells, h->time256, w, p0, npl)
+            if (wide) { if (cw == 16) FK(uint8_t, 16); else if (cw == 8) FK(uint8_t, 8); else if (cw == 4) FK(uint8_t, 4); else if (cw == 2) FK(uint8_t, 2); else FK(uint8_t, 1); }
+            else { if (cw == 8) FK(uint16_t, 8); else if (cw == 4) FK(uint16_t, 4); else if (cw == 2) FK(uint16_t, 2); else FK(uint16_t, 1); }
+#undef FK
+        });
+        fm_classes(P, nframes, false, [&](dim3 grid, int cw, int p0, int npl) {
+#define FK(TT, W_) hipLaunchKernelGGL((flowshift_resolve<TT, W_>), grid, dim3(256), 0, st, h->dP, h->dJobs, h->dFlags, w, p0, npl)
+            if (wide) { if (cw == 16) FK(uint8_t, 16); else if (cw == 8) FK(uint8_t, 8); else if (cw == 4) FK(uint8_t, 4); else if (cw == 2) FK(uint8_t, 2); else FK(uint8_t, 1); }
+            else { if (cw == 8) FK(uint16_t, 8); else if (cw == 4) FK(uint16_t, 4); else if (cw == 2) FK(uint16_t, 2); else FK(uint16_t, 1); }
+#undef FK
+        });
+    }
+    HIP_CHECK(hipGetLastError());
+    return MVX_OK;
+}
+
+// MVFlowBlur.c:346-552 mvflowblurCreate.  blur is a float argument there: blur256 is formed in float.
+extern "C" __attribute__((visibility("default"))) int mvx_flowblur_create(const mvx_flowblur_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
+        const mvx_super *sup, int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flowblur **out,
+        char *err) {
+    char dummy[MVX_ERRLEN];
+    if (!err) err = dummy;
+    err[0] = 0;
+    *out = nullptr;
+    const float blur = (float)a->blur;
+    const int prec = a->prec == MVX_UNSET ? 1 : a->prec;
+    int64_t thscd1 = a->thscd1 == MVX_UNSET ? 400 : a->thscd1;
+    int32_t thscd2 = a->thscd2 == MVX_UNSET ? 130 : a->thscd2;
+    if (blur < 0.0f || blur > 200.0f) FFAIL("FlowBlur: blur must be between 0 and 200 %% (inclusive).");
+    if (prec < 1) FFAIL("FlowBlur: prec must be at least 1.");
+    if (int rc = flow_pair_checks("FlowBlur", &thscd1, &thscd2, bw, fw, err)) return rc;
+    mvx_flowblur *h = new mvx_flowblur();
+    if (int rc = fm_create(h, "FlowBlur", thscd1, thscd2, bw, sup->info, super_pitch, clip_pitch, dst_pitch, false, err)) { delete h; return rc; }
+    h->nb = 2; h->prec = prec;
+    h->blur256 = (int)(blur * 256.0f / 200.0f);
+    h->numFrames = num_frames;
+    *out = h;
+    return MVX_OK;
+}
+extern "C" __attribute__((visibility("default"))) void mvx_flowblur_destroy(mvx_flowblur *h) { delete h; }
+
+extern "C" __attribute__((visibility("default"))) int mvx_flowblur_frames(mvx_flowblur *h, int nframes, const mvx_flowblur_job *jobs, void *stream) {
+    if (nframes <= 0) return MVX_OK;
+    hipStream_t st = (hipStream_t)stream;
+    CallGuard::Scope scope(h->guard, st);
+    FLParams &P = h->P;
+    std::vector<FMJob> hj(nframes);
+    for (int f = 0; f < nframes; f++) {
+        FMJob &j = hj[f];
+        const mvx_flowblur_job &s = jobs[f];
+        memset(&j, 0, sizeof(j));
+        const bool comp = s.super[0] && s.blob_bw && s.blob_fw;
+        for (int p = 0; p < 3; p++) {
+            j.sup[p] = comp ? (const unsigned char *)s.super[p] : nullptr;
+            j.clip[p] = (const unsigned char *)s.clip[p]; j.dst[p] = (unsigned char *)s.dst[p];
+        }
+        j.blob[0] = comp ? (const unsigned char *)s.blob_bw : nullptr;
+        j.blob[1] = comp ? (const unsigned char *)s.blob_fw : nullptr;
+        if (!j.dst[0] || !j.clip[0]) { mvx_set_error("mvx_flowblur_frames: dst / clip are required"); return MVX_E_ARG; }
+    }
+    if (int rc = fm_prologue(h, nframes, hj, st)) return rc;
+    fm_classes(P, nframes, true, [&](dim3 grid, int, int p0, int npl) {
+        if (P.bps == 1) hipLaunchKernelGGL((flowblur_kernel<uint8_t>), grid, dim3(256), 0, st, h->dP, h->dJobs, h->dFlags, h->dCells, h->blur256, h->prec, p0, npl);
+        else hipLaunchKernelGGL((flowblur_kernel<uint16_t>), grid, dim3(256), 0, st, h->dP, h->dJobs, h->dFlags, h->dCells, h->blur256, h->prec, p0, npl);
+    });
     HIP_CHECK(hipGetLastError());
     return MVX_OK;
 }

@@ -5,6 +5,8 @@
     core.mv.Degrain1..6(clip, super, mvbw, mvfw, ...) -> Degrain(radius, super, analysis_data, ...) .run(jobs)
     core.mv.Compensate(clip, super, vectors, ...)     -> Compensate(super, analysis_data, ...)      .run(jobs)
     core.mv.FlowInter / FlowFPS(clip, super, mvbw, mvfw, ...) -> FlowInter / FlowFPS(super, bw_data, fw_data, ...) .run(ns, ...)
+    core.mv.Flow(clip, super, vectors, ...)           -> Flow(super, analysis_data, ...)          .run(jobs)
+    core.mv.FlowBlur(clip, super, mvbw, mvfw, ...)    -> FlowBlur(super, bw_data, fw_data, ...)   .run(ns, ...)
 
 Argument names, defaults and error strings are the reference's (MVSuper.c:279-291, MVAnalyse.c:639-671,
 MVDegrains.cpp:813-932, MVCompensate.c:579-592); they are resolved inside the library, not here.
@@ -117,6 +119,23 @@ class FlowJob(C.Structure):
                 ("clip_right", C.c_void_p * 3), ("dst", C.c_void_p * 3)]
 
 
+class FlowCompArgs(C.Structure):
+    _fields_ = [("time", C.c_double), ("mode", C.c_int32), ("fields", C.c_int32), ("thscd1", C.c_int64), ("thscd2", C.c_int32)]
+
+
+class FlowCompJob(C.Structure):
+    _fields_ = [("ref_super", C.c_void_p * 3), ("blob", C.c_void_p), ("clip", C.c_void_p * 3), ("dst", C.c_void_p * 3), ("field_shift", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class FlowBlurArgs(C.Structure):
+    _fields_ = [("blur", C.c_double), ("prec", C.c_int32), ("thscd1", C.c_int64), ("thscd2", C.c_int32)]
+
+
+class FlowBlurJob(C.Structure):
+    _fields_ = [("super", C.c_void_p * 3), ("blob_bw", C.c_void_p), ("blob_fw", C.c_void_p), ("clip", C.c_void_p * 3), ("dst", C.c_void_p * 3)]
+
+
 _lib = None
 
 
@@ -188,6 +207,15 @@ def lib():
         L.mvx_flow_get_info.argtypes = [C.c_void_p, P(BlockFPSInfo)]
         L.mvx_flow_map.argtypes = [C.c_void_p, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int)]
         L.mvx_flow_frames.argtypes = [C.c_void_p, C.c_int, P(FlowJob), C.c_void_p]
+        L.mvx_flowcomp_create.argtypes = [P(FlowCompArgs), P(AnalysisData), C.c_void_p, C.c_int, P(C.c_ssize_t), P(C.c_ssize_t), P(C.c_ssize_t),
+                                          P(C.c_void_p), C.c_char_p]
+        L.mvx_flowcomp_destroy.argtypes = [C.c_void_p]
+        L.mvx_flowcomp_ref.argtypes = [C.c_void_p, C.c_int]
+        L.mvx_flowcomp_frames.argtypes = [C.c_void_p, C.c_int, P(FlowCompJob), C.c_void_p]
+        L.mvx_flowblur_create.argtypes = [P(FlowBlurArgs), P(AnalysisData), P(AnalysisData), C.c_void_p, C.c_int, P(C.c_ssize_t), P(C.c_ssize_t),
+                                          P(C.c_ssize_t), P(C.c_void_p), C.c_char_p]
+        L.mvx_flowblur_destroy.argtypes = [C.c_void_p]
+        L.mvx_flowblur_frames.argtypes = [C.c_void_p, C.c_int, P(FlowBlurJob), C.c_void_p]
         L.mvx_scale_thscd.argtypes = [P(C.c_int64), P(C.c_int32), P(AnalysisData)]
         L.mvx_vectors_size.argtypes = [P(AnalysisData)]
         L.mvx_vectors_size.restype = C.c_int
@@ -745,6 +773,112 @@ class FlowFPS(_Flow):
         fw = AnalysisData.from_buffer_copy(bytes(ad_fw))
         super().__init__(sup, num_frames, lambda h, err: lib().mvx_flowfps_create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, int(num_frames), int(fps_num),
                                                                                    int(fps_den), _pad3(sup.pitch), _pad3(clip_pitch), _pad3(clip_pitch), h, err))
+
+
+class Flow:
+    """mv.Flow(clip, super, vectors, time, mode, fields, thscd1, thscd2, tff) -- MVFlow.cpp:391-593.  Output frame n is clip frame n compensated
+    per sample from the Finest frame of ref(n); `clip_pitch` is the row pitch of the clip's device planes (and of the output)."""
+
+    def __init__(self, sup, ad, num_frames, clip_pitch, time=100.0, mode=None, fields=None, thscd1=None, thscd2=None):
+        self.sup = sup
+        a = FlowCompArgs(float(time), _u(mode), _u(fields), _u(thscd1), _u(thscd2))
+        ad = AnalysisData.from_buffer_copy(bytes(ad))
+        self.h = C.c_void_p()
+        self.pitch = list(clip_pitch)
+        self.num_frames = int(num_frames)
+        err = C.create_string_buffer(ERRLEN)
+        _check(lib().mvx_flowcomp_create(C.byref(a), C.byref(ad), sup.h, self.num_frames, _pad3(sup.pitch), _pad3(clip_pitch), _pad3(clip_pitch),
+                                         C.byref(self.h), err), err)
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().mvx_flowcomp_destroy(self.h)
+        except Exception:
+            pass
+
+    def ref(self, n):
+        """the reference frame of output frame n (MVFlow.cpp:170-176); outside the clip the job passes no super frame"""
+        return lib().mvx_flowcomp_ref(self.h, int(n))
+
+    def run(self, jobs, out=None):
+        """jobs: list of (clip_frame, ref_super_or_None, blob[, field_shift]); None or a blob of None copies the clip frame"""
+        _torch()
+        n = len(jobs)
+        if out is None:
+            c = jobs[0][0]
+            out = arena_frames(n, [tuple(p.shape) for p in c], c[0].device, zero=False)
+        arr = (FlowCompJob * n)()
+        for k, job in enumerate(jobs):
+            clip, r, blob = job[:3]
+            for p in range(self.sup.nplanes):
+                arr[k].clip[p] = clip[p].data_ptr()
+                arr[k].dst[p] = out[k][p].data_ptr()
+                arr[k].ref_super[p] = r[p].data_ptr() if r is not None else None
+            arr[k].blob = blob.data_ptr() if blob is not None else None
+            arr[k].field_shift = int(job[3]) if len(job) > 3 else 0
+        self.launch(arr)
+        return out
+
+    def launch(self, arr):
+        """enqueues a job table (a ctypes array of FlowCompJob)"""
+        _check(lib().mvx_flowcomp_frames(self.h, len(arr), arr, _stream()))
+
+
+class FlowBlur:
+    """mv.FlowBlur(clip, super, mvbw, mvfw, blur, prec, thscd1, thscd2) -- MVFlowBlur.c:346-552.  `clip_pitch` is the row pitch of the clip's
+    device planes (and of the output)."""
+
+    def __init__(self, sup, ad_bw, ad_fw, num_frames, clip_pitch, blur=50.0, prec=None, thscd1=None, thscd2=None):
+        self.sup = sup
+        a = FlowBlurArgs(float(blur), _u(prec), _u(thscd1), _u(thscd2))
+        bw = AnalysisData.from_buffer_copy(bytes(ad_bw))
+        fw = AnalysisData.from_buffer_copy(bytes(ad_fw))
+        self.h = C.c_void_p()
+        self.pitch = list(clip_pitch)
+        self.num_frames = int(num_frames)
+        self.delta = bw.nDeltaFrame
+        err = C.create_string_buffer(ERRLEN)
+        _check(lib().mvx_flowblur_create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, self.num_frames, _pad3(sup.pitch), _pad3(clip_pitch),
+                                         _pad3(clip_pitch), C.byref(self.h), err), err)
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().mvx_flowblur_destroy(self.h)
+        except Exception:
+            pass
+
+    def run(self, ns, clip, supers, blobs_bw, blobs_fw, out=None):
+        """ns: output frame numbers, one job each, all in one call; clip / supers: device frames of the input clip and its super clip;
+        blobs_bw / blobs_fw: per input frame device blobs of the two vector clips (mvbw at n, mvfw at n).  Frame n reads mvbw at n - delta and
+        mvfw at n + delta (MVFlowBlur.c:158-178); where either lies outside the clip it copies clip frame n."""
+        arr, out = self.jobs(ns, clip, supers, blobs_bw, blobs_fw, out)
+        self.launch(arr)
+        return out
+
+    def launch(self, arr):
+        """enqueues a job table made by jobs()"""
+        _check(lib().mvx_flowblur_frames(self.h, len(arr), arr, _stream()))
+
+    def jobs(self, ns, clip, supers, blobs_bw, blobs_fw, out=None):
+        """the job table of run() and its output frames, without launching"""
+        _torch()
+        n = len(ns)
+        if out is None:
+            out = arena_frames(n, [tuple(p.shape) for p in clip[0]], clip[0][0].device, zero=False)
+        arr = (FlowBlurJob * n)()
+        d = self.delta
+        for k, fo in enumerate(ns):
+            for p in range(self.sup.nplanes):
+                arr[k].clip[p] = clip[fo][p].data_ptr()
+                arr[k].dst[p] = out[k][p].data_ptr()
+            if fo - d >= 0 and fo + d < self.num_frames:
+                for p in range(self.sup.nplanes):
+                    arr[k].super[p] = supers[fo][p].data_ptr()
+                arr[k].blob_bw = blobs_bw[fo - d].data_ptr()
+                arr[k].blob_fw = blobs_fw[fo + d].data_ptr()
+        return arr, out
 
 
 class Recalculate:
