@@ -58,9 +58,8 @@ def upsize_u8(small, dw, dh):
     return dst[:, :dw].copy()
 
 
-def upsize_i16(small, dw, dh, limit_w, limit_h, pel, horizontal):
-    """SimpleResize.cpp:60-121, int16_t form: vertical pass rounded into an int16 work row, horizontal pass rounded, then limited to
-    [-x * pel, (limit_w - x) * pel - 1] (horizontal vectors, :99-113) or [-y * pel, (limit_h - y) * pel - 1] (vertical vectors, :117-119)"""
+def upsize_i16_parts(small, dw, dh, limit_w, limit_h, pel, horizontal):
+    """SimpleResize.cpp:60-121, int16_t form, before the limiting: (the rounded result, its lower limits, its upper limits)"""
     sh, sw = small.shape
     vo, vw = resize_tables(dh, sh)
     ho, hw = resize_tables(dw, sw)
@@ -74,6 +73,13 @@ def upsize_i16(small, dw, dh, limit_w, limit_h, pel, horizontal):
     else:
         y = np.arange(dh, dtype=np.int64)[:, None]
         lo, hi = -y * pel, (limit_h - y) * pel - 1
+    return res, lo, hi
+
+
+def upsize_i16(small, dw, dh, limit_w, limit_h, pel, horizontal):
+    """SimpleResize.cpp:60-121, int16_t form: vertical pass rounded into an int16 work row, horizontal pass rounded, then limited to
+    [-x * pel, (limit_w - x) * pel - 1] (horizontal vectors, :99-113) or [-y * pel, (limit_h - y) * pel - 1] (vertical vectors, :117-119)"""
+    res, lo, hi = upsize_i16_parts(small, dw, dh, limit_w, limit_h, pel, horizontal)
     return np.maximum(lo, np.minimum(res, hi)).astype(np.int16)
 
 
@@ -128,6 +134,15 @@ def blend(l, r, t, dtype):
     return ((l.astype(np.int64) * (256 - t) + r.astype(np.int64) * t) >> 8).astype(dtype)
 
 
+def take(fin, rows, cols):
+    """fin[rows, cols] after checking that every index lies inside the plane: numpy wraps negative indices silently, which would let this
+    restatement agree with a kernel that reads the wrong sample (the reference would read outside its frame there)"""
+    rows, cols = np.broadcast_arrays(rows, cols)
+    assert rows.min() >= 0 and rows.max() < fin.shape[0] and cols.min() >= 0 and cols.max() < fin.shape[1], (
+        "fetch outside the Finest plane", int(rows.min()), int(rows.max()), int(cols.min()), int(cols.max()), fin.shape)
+    return fin[rows, cols]
+
+
 def flow_inter(kind, t, fin_b, fin_f, off, pel, vb, vf, mb, mf, w, h, dtype, vbb=None, vff=None):
     """kind 'simple' / 'regular' / 'extra': MaskFun.cpp:493-551 / :374-414 / :417-490 over one plane.  fin_b = the right Finest plane
     (prefB), fin_f = the left one (prefF); off = (row, column) of the unpadded sample (0, 0) in them; v* = (VX, VY) full planes."""
@@ -138,7 +153,7 @@ def flow_inter(kind, t, fin_b, fin_f, off, pel, vb, vf, mb, mf, w, h, dtype, vbb
     MF, MB = cut(mf), cut(mb)
 
     def fetch(fin, v, tt):
-        return fin[Y + ((cut(v[1]) * tt) >> 8), X + ((cut(v[0]) * tt) >> 8)].astype(np.int64)
+        return take(fin, Y + ((cut(v[1]) * tt) >> 8), X + ((cut(v[0]) * tt) >> 8)).astype(np.int64)
 
     dF, dB = fetch(fin_f, vf, t), fetch(fin_b, vb, 256 - t)
     if kind == "simple":
@@ -147,7 +162,7 @@ def flow_inter(kind, t, fin_b, fin_f, off, pel, vb, vf, mb, mf, w, h, dtype, vbb
         else:
             out = ((((dF * (255 - MF) + dB * MF + 255) >> 8) * (256 - t) + ((dB * (255 - MB) + dF * MB + 255) >> 8) * t) >> 8)
     elif kind == "regular":
-        dF0, dB0 = fin_f[Y, X].astype(np.int64), fin_b[Y, X].astype(np.int64)
+        dF0, dB0 = take(fin_f, Y, X).astype(np.int64), take(fin_b, Y, X).astype(np.int64)
         a = (dF * (255 - MF) + ((MF * (dB * (255 - MB) + MB * dF0) + 255) >> 8) + 255) >> 8
         b = (dB * (255 - MB) + ((MB * (dF * (255 - MF) + MF * dB0) + 255) >> 8) + 255) >> 8
         out = (a * (256 - t) + b * t) >> 8

@@ -19,7 +19,7 @@ import numpy as np
 
 import mvoracle
 import pipeline as pl
-from flow_ref import _lib, half_uv, small_fields, upsize_i16
+from flow_ref import _lib, half_uv, small_fields, take, upsize_i16
 
 
 def cdiv(a, b):
@@ -38,7 +38,7 @@ def fetch(fin, off, v, t, pel, w, h, dtype):
     fin = the Finest plane of nref, off = (row, column) of its unpadded sample (0, 0), v = (VX, VY) full planes."""
     Y, X, _ = _grid(h, w, pel, off)
     vx, vy = v[0][:h, :w].astype(np.int64), v[1][:h, :w].astype(np.int64)
-    return fin[Y + ((vy * t + 128) >> 8), X + ((vx * t + 128) >> 8)].astype(dtype)
+    return take(fin, Y + ((vy * t + 128) >> 8), X + ((vx * t + 128) >> 8)).astype(dtype)
 
 
 def shift_targets(v, t, pel, w, h):
@@ -64,7 +64,7 @@ def shift(fin, off, v, t, pel, w, h, bits, dtype, stats=None):
     goes to (h + vy, w + vx), v = (-V * time256 + (128 << lp)) >> (8 + lp).  stats (a dict) counts destinations that two or more sources
     with different samples reach ("collide") and destinations nobody reaches ("hole")."""
     Y, X, _ = _grid(h, w, pel, off)
-    src = fin[Y, X].astype(np.int64)
+    src = take(fin, Y, X).astype(np.int64)
     win = shift_winners(v, t, pel, w, h)
     out = np.full((h, w), (1 << bits) - 1, np.int64)
     has = win > 0
@@ -101,7 +101,7 @@ def blur(fin, off, vb, vf, blur256, prec, pel, w, h, dtype, stats=None):
     / prec) >> 8 with v0 = V * blur256; if m > 0, v0 /= m (truncating) and m taps at ((i + 1) * v0) >> 8; the mean of the sample and the
     taps.  stats counts samples with taps ("taps"), samples without ("notaps") and negative v0 with a remainder ("trunc")."""
     Y, X, _ = _grid(h, w, pel, off)
-    total = fin[Y, X].astype(np.int64)
+    total = take(fin, Y, X).astype(np.int64)
     count = np.ones((h, w), np.int64)
     for v in (vf, vb):
         vx0 = v[0][:h, :w].astype(np.int64) * blur256
@@ -115,7 +115,7 @@ def blur(fin, off, vb, vf, blur256, prec, pel, w, h, dtype, stats=None):
         ax, ay = vx0.copy(), vy0.copy()
         for i in range(int(m.max()) if m.size else 0):
             live = i < m
-            total += np.where(live, fin[np.where(live, Y + (ay >> 8), 0), np.where(live, X + (ax >> 8), 0)], 0)
+            total += np.where(live, take(fin, np.where(live, Y + (ay >> 8), 0), np.where(live, X + (ax >> 8), 0)), 0)
             ax += vx0
             ay += vy0
         count += m

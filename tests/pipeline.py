@@ -2,6 +2,8 @@
 through the product's C ABI (GPU), on identical inputs."""
 import numpy as np
 
+import vector_fields
+
 
 def moving_clip(width, height, bits, nframes, seed=7, noise=2, motion=(3, -1), sub=(1, 1)):
     """Textured 4:2:0 (or other subsampling) clip: band-limited texture translating by `motion` px/frame, a rectangle
@@ -54,20 +56,19 @@ def defined_equal(oracle_sup, oracle_frame, gpu_frame_np):
     return bad
 
 
+def first_diff(got, want):
+    """'' when the planes are equal, else the count of differing samples and the first of them"""
+    if np.array_equal(got, want):
+        return ""
+    ys, xs = np.nonzero(got != want)
+    return "%d samples differ, first (y=%d, x=%d) got %d want %d" % (len(ys), ys[0], xs[0], got[ys[0], xs[0]], want[ys[0], xs[0]])
+
+
 def blob_vectors(blob, ad, level=0):
     """numpy view (x, y, sad) of one level of a MVTools_vectors blob"""
     b = np.asarray(blob, dtype=np.uint8)
-    off = 8
-    nWB = (ad.nBlkSizeX - ad.nOverlapX) * ad.nBlkX + ad.nOverlapX
-    nHB = (ad.nBlkSizeY - ad.nOverlapY) * ad.nBlkY + ad.nOverlapY
-    for i in range(ad.nLvCount - 1, -1, -1):
-        bx = ((nWB >> i) - ad.nOverlapX) // (ad.nBlkSizeX - ad.nOverlapX)
-        by = ((nHB >> i) - ad.nOverlapY) // (ad.nBlkSizeY - ad.nOverlapY)
-        n = bx * by
-        if i == level:
-            rec = b[off + 4: off + 4 + n * 16]
-            xy = rec.view(np.int32).reshape(n, 4)[:, :2]
-            sad = rec.view(np.int64).reshape(n, 2)[:, 1]
-            return xy[:, 0].reshape(by, bx), xy[:, 1].reshape(by, bx), sad.reshape(by, bx)
-        off += 4 + n * 16
-    raise ValueError(level)
+    off, by, bx = vector_fields.level_span(b, ad, level)
+    rec = b[off: off + by * bx * 16]
+    xy = rec.view(np.int32).reshape(by * bx, 4)[:, :2]
+    sad = rec.view(np.int64).reshape(by * bx, 2)[:, 1]
+    return xy[:, 0].reshape(by, bx), xy[:, 1].reshape(by, bx), sad.reshape(by, bx)

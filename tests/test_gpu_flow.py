@@ -6,6 +6,7 @@ import pytest
 
 import flow_ref
 import pipeline as pl
+import vector_fields
 
 pytestmark = pytest.mark.gpu
 
@@ -109,7 +110,7 @@ def _run(mv, oracle, fmt, w, h, bits, skw, akw, fkw, nf, seed, outs=None, edit=N
         kinds.add(ref.last_kind)
         for p in range(gsup.nplanes):
             got = mv.plane_to_numpy(out[k][p], want[p].shape[1], want[p].dtype)
-            assert np.array_equal(got, want[p]), (n, p, g.map(n), ref.last_kind, int(np.count_nonzero(got != want[p])))
+            assert np.array_equal(got, want[p]), "frame %d plane %d %s (%s): %s" % (n, p, g.map(n), ref.last_kind, pl.first_diff(got, want[p]))
         if ref_d is not None:
             differs += sum(int(np.count_nonzero(a != b)) for a, b in zip(want, ref_d.frame(n, frames, fin, bbw, bfw)))
     if ref_d is not None:
@@ -139,17 +140,10 @@ def _alternating_vectors(o):
     """blob editor: level-0 vectors (0, 0) in even block columns and (-o, 0) in odd ones, SAD 0 -- an occlusion of o at every even column"""
     def edit(blob, ad):
         b = blob.copy()
-        off = 8
-        nwb = (ad.nBlkSizeX - ad.nOverlapX) * ad.nBlkX + ad.nOverlapX
-        nhb = (ad.nBlkSizeY - ad.nOverlapY) * ad.nBlkY + ad.nOverlapY
-        for i in range(ad.nLvCount - 1, -1, -1):
-            bx = ((nwb >> i) - ad.nOverlapX) // (ad.nBlkSizeX - ad.nOverlapX)
-            by = ((nhb >> i) - ad.nOverlapY) // (ad.nBlkSizeY - ad.nOverlapY)
-            if i == 0:
-                rec = b[off + 4:off + 4 + bx * by * 16].view(np.int32).reshape(by, bx, 4)
-                rec[:, :, 0] = np.where(np.arange(bx) % 2 == 1, -o, 0)[None, :]
-                rec[:, :, 1:] = 0
-            off += 4 + bx * by * 16
+        xy, sad = vector_fields.records(b, ad)
+        xy[:, :, 0] = np.where(np.arange(xy.shape[1]) % 2 == 1, -o, 0)[None, :]
+        xy[:, :, 1] = 0
+        sad[:, :] = 0
         return b
     return edit
 

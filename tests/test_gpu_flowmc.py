@@ -103,10 +103,10 @@ def _kinds(kinds, stats):
 def _compare(mv, out, want, k, n, kind):
     for p in range(len(want)):
         got = mv.plane_to_numpy(out[k][p], want[p].shape[1], want[p].dtype)
-        assert np.array_equal(got, want[p]), (n, p, kind, int(np.count_nonzero(got != want[p])))
+        assert np.array_equal(got, want[p]), "frame %d plane %d (%s): %s" % (n, p, kind, pl.first_diff(got, want[p]))
 
 
-def _run_flow(mv, oracle, fmt, w, h, bits, skw, akw, fkw, nf, seed, outs=None):
+def _run_flow(mv, oracle, fmt, w, h, bits, skw, akw, fkw, nf, seed, outs=None, edit=None):
     import torch
     frames, gsup, gsrc, gsf, fin = _clip(mv, oracle, fmt, w, h, bits, skw, nf, seed)
     akw, fkw = dict(akw), dict(fkw)
@@ -116,6 +116,8 @@ def _run_flow(mv, oracle, fmt, w, h, bits, skw, akw, fkw, nf, seed, outs=None):
     ref = flowmc_ref.Flow(ga.ad, nf, gsup.nplanes, gsup.info.hpad, gsup.info.vpad, bits, **fkw)
     inside = lambda k: 0 <= k < nf
     blobs = ga.run([(gsf[n], gsf[g.ref(n)] if inside(g.ref(n)) else None) for n in range(nf)])
+    if edit is not None:  # replace the vectors of every blob (device copies)
+        blobs = [torch.from_numpy(edit(b.cpu().numpy(), ga.ad)).to(b.device) for b in blobs]
     ns = list(range(nf)) if outs is None else outs
     for n in ns:
         assert g.ref(n) == ref.ref(n), n
@@ -129,7 +131,7 @@ def _run_flow(mv, oracle, fmt, w, h, bits, skw, akw, fkw, nf, seed, outs=None):
     return _kinds(kinds, stats)
 
 
-def _run_blur(mv, oracle, fmt, w, h, bits, skw, akw, fkw, nf, seed, outs=None):
+def _run_blur(mv, oracle, fmt, w, h, bits, skw, akw, fkw, nf, seed, outs=None, edit=None):
     import torch
     frames, gsup, gsrc, gsf, fin = _clip(mv, oracle, fmt, w, h, bits, skw, nf, seed)
     akw = dict(akw)
@@ -138,6 +140,9 @@ def _run_blur(mv, oracle, fmt, w, h, bits, skw, akw, fkw, nf, seed, outs=None):
     gafw = mv.Analyse(gsup, num_frames=nf, isb=0, delta=delta, **akw)
     gbbw = gabw.run([(gsf[n], gsf[n + delta] if n + delta < nf else None) for n in range(nf)])
     gbfw = gafw.run([(gsf[n], gsf[n - delta] if n - delta >= 0 else None) for n in range(nf)])
+    if edit is not None:
+        gbbw = [torch.from_numpy(edit(b.cpu().numpy(), gabw.ad)).to(b.device) for b in gbbw]
+        gbfw = [torch.from_numpy(edit(b.cpu().numpy(), gafw.ad)).to(b.device) for b in gbfw]
     g = mv.FlowBlur(gsup, gabw.ad, gafw.ad, nf, [p.stride(0) for p in gsrc[0]], **fkw)
     ref = flowmc_ref.FlowBlur(gabw.ad, gafw.ad, nf, gsup.nplanes, gsup.info.hpad, gsup.info.vpad, bits, **fkw)
     ns = list(range(nf)) if outs is None else outs
