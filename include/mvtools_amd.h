@@ -410,6 +410,64 @@ typedef struct mvx_flowblur_job {
 /* nframes jobs in one batch on `stream`: two small per-job kernels, then one launch for the luma planes and one for both chroma planes */
 int mvx_flowblur_frames(mvx_flowblur *h, int nframes, const mvx_flowblur_job *jobs, void *stream);
 
+/* ---- mv.Mask --------------------------------------------------------------------------------------
+ * motion, SAD and occlusion masks from one vector clip, as an 8-bit three-plane clip.
+ * mvx_mask_create replaces mvmaskCreate, MVMask.c:227-346 (arg string :349-363); mvx_mask_frames replaces mvmaskGetFrame,
+ * MVMask.c:75-211 (mvmaskLength :66-72); masks MaskFun.cpp:85-166 (ByteOccMask, MakeVectorOcclusionMaskTime, ByteNorm,
+ * MakeSADMaskTime), upsizer SimpleResize.cpp:27-121.  No super clip is needed; creation touches no device.
+ * kind: 0 vector length, 1 SAD, 2 occlusion, 3 / 4 the x / y component (+128), 5 x in U and y in V with the clip's luma kept.
+ * U and V are equal for kinds 0-4.  A frame whose vectors are unusable (scene change, invalid, NULL blob) is filled with ysc (kind 5:
+ * chroma only).  Only the samples of each plane are written: bytes between a plane's width and its pitch are never touched (the
+ * reference's memset / memcpy fallbacks write them).
+ * The reference's `opt` chooses between C and AVX2 forms that compute the same bytes; it has no counterpart here.
+ * 255 * pow(...) is the device's double-precision pow where the reference calls the C library's; the two may differ in the last
+ * places, which changes a byte only where the product lies within that distance of an integer.  An exponent of exactly 1 (kinds 1 and
+ * 2 at gamma 1, kind 0 at gamma 2) takes no pow at all, and is exact.
+ * Deliberate divergences, each rejected at creation with a message of the library's own unless stated otherwise:
+ *   1. fewer than two blocks wide or high: the reference's upsizer then reads before its buffer (as Flow);
+ *   2. a clip whose size or chroma ratios differ from the vector clip's nWidth / nHeight / xRatioUV / yRatioUV (Gray counts as
+ *      1 / 1): the reference does not check this, and then writes planes of the wrong size;
+ *   3. (not rejected) where 255 * pow(...) of the occlusion mask exceeds the int range the reference's cast is undefined -- on
+ *      x86 it yields INT_MIN, so the cell keeps its old value; the library saturates: the cell becomes 255. */
+
+typedef struct mvx_mask_args {
+    double ml, gamma;        /* pass 100.0 / 1.0 for the defaults; float arguments in the reference: every factor is formed in float */
+    int32_t kind;            /* 0..5, MVX_UNSET -> 0 */
+    double time;             /* 0..100 (a double argument in the reference: time256 is formed in double); pass 100.0 for the default */
+    int32_t ysc;             /* 0..255, MVX_UNSET -> 0 */
+    int64_t thscd1; int32_t thscd2;
+} mvx_mask_args;
+
+/* the format of the clip argument (VSVideoInfo) */
+typedef struct mvx_mask_clip { int32_t width, height, bits, subsampling_w, subsampling_h, gray; } mvx_mask_clip;
+
+/* the output clip: always 3 planes of 8 bits; a Gray input gives 4:4:4 (MVMask.c:328-329).  The remaining fields are what creation
+ * derived from the arguments (MVMask.c:304-307,334), for hosts and tests that want to see the rounding. */
+typedef struct mvx_mask_info {
+    int32_t width, height, subsampling_w, subsampling_h, num_planes;
+    int32_t plane_width[3], plane_height[3];
+    int32_t time256;
+    float fMaskNormFactor, fMaskNormFactor2, fHalfGamma;
+} mvx_mask_info;
+
+typedef struct mvx_mask mvx_mask;
+
+/* clip_pitch[0]: row pitch of the clip's luma plane (read by kind 5 only); dst_pitch: multiples of 16 bytes, U and V alike */
+int mvx_mask_create(const mvx_mask_args *args, const mvx_analysis_data *vectors, const mvx_mask_clip *clip, const ptrdiff_t clip_pitch[3],
+                    const ptrdiff_t dst_pitch[3], mvx_mask **out, char *err);
+void mvx_mask_destroy(mvx_mask *m);
+void mvx_mask_get_info(const mvx_mask *m, mvx_mask_info *info);
+
+typedef struct mvx_mask_job {
+    const void *blob;        /* vectors at n; NULL = unusable */
+    const void *clip_luma;   /* luma plane of clip frame n; read by kind 5 only */
+    void *dst[3];            /* 16-byte aligned */
+} mvx_mask_job;
+
+/* nframes jobs in one batch on `stream`: two or three small kernels over all jobs (usability, the block-resolution masks), then one
+ * launch for the luma planes of all jobs and one for both chroma planes of all jobs */
+int mvx_mask_frames(mvx_mask *m, int nframes, const mvx_mask_job *jobs, void *stream);
+
 /* ---- mv.SCDetection -------------------------------------------------------------------------------
  * replaces the decision of mvscdetectionGetFrame, MVSCDetection.c:43-73 (arg string :137-145): scene_change[i] (HOST array) =
  * !usable(blobs[i]) for n device blobs of one vector clip, i.e. the value of _SceneChangePrev (forward vectors) or

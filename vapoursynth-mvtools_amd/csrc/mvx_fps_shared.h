@@ -116,11 +116,19 @@ __device__ __forceinline__ int fps_count_over(const unsigned char *blob, int nLv
     return c;
 }
 
-// MaskFun.cpp:86-130 MakeVectorOcclusionMaskTime (fGamma 1) for block (bx, by) = i: the occlusion against its right and bottom
+// MaskFun.cpp:85-90 ByteOccMask, the value that is maxed into the mask.  fGamma 1 has no pow (the interpolating filters, which pass the
+// constant, keep exactly their expression); otherwise the device's double pow, and a product beyond the int range -- where the reference's
+// cast is undefined -- saturates to 255 (mv.Mask's divergence 3, mvtools_amd.h)
+__device__ __forceinline__ int fps_occlusion_value(int o, double norm, double gamma) {
+    if (gamma == 1.0) return min((int)(255 * o * norm), 255);
+    const double l = 255 * pow(o * norm, gamma);
+    return l >= 255.0 ? 255 : (int)l;
+}
+// MaskFun.cpp:86-130 MakeVectorOcclusionMaskTime for block (bx, by) = i: the occlusion against its right and bottom
 // neighbours, scatter-maxed into the int plane m (pitch XP; zeroed before).  dir 1 = isBackward; time256 is the mask's own time
-// (256 - t for the backward mask).  Only maxima are taken, so the order of the reference's loops does not matter.
+// (256 - t for the backward mask); ml is dMaskNormDivider.  Only maxima are taken, so the order of the reference's loops does not matter.
 __device__ __forceinline__ void fps_occlusion_block(const GVecD *vec, int i, int bx, int by, int nBlkX, int nBlkY, int dir, int time256, int stepX, int stepY,
-                                                    int nPel, double ml, int *m, int XP) {
+                                                    int nPel, double ml, int *m, int XP, double gamma = 1.0) {
     const int tX = time256 * 16 / (stepX * nPel), tY = time256 * 16 / (stepY * nPel);
     const double nX = 80.0 / (ml * stepX * nPel), nY = 80.0 / (ml * stepY * nPel);
     const int vx = vec[i].x, vy = vec[i].y;
@@ -130,7 +138,7 @@ __device__ __forceinline__ void fps_occlusion_block(const GVecD *vec, int i, int
             const int o = vx - vx1;
             const int minb = dir ? max(0, bx + 1 - o * tX / 4096) : bx;
             const int maxb = dir ? bx + 1 : min(bx + 1 - o * tX / 4096, nBlkX - 1);
-            const int val = min((int)(255 * o * nX), 255);
+            const int val = fps_occlusion_value(o, nX, gamma);
             for (int b = minb; b <= maxb; b++) atomicMax(&m[b + by * XP], val);
         }
     }
@@ -140,7 +148,7 @@ __device__ __forceinline__ void fps_occlusion_block(const GVecD *vec, int i, int
             const int o = vy - vy1;
             const int minb = dir ? max(0, by + 1 - o * tY / 4096) : by;
             const int maxb = dir ? by + 1 : min(by + 1 - o * tY / 4096, nBlkY - 1);
-            const int val = min((int)(255 * o * nY), 255);
+            const int val = fps_occlusion_value(o, nY, gamma);
             for (int b = minb; b <= maxb; b++) atomicMax(&m[bx + b * XP], val);
         }
     }

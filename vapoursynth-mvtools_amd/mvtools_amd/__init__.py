@@ -7,6 +7,7 @@
     core.mv.FlowInter / FlowFPS(clip, super, mvbw, mvfw, ...) -> FlowInter / FlowFPS(super, bw_data, fw_data, ...) .run(ns, ...)
     core.mv.Flow(clip, super, vectors, ...)           -> Flow(super, analysis_data, ...)          .run(jobs)
     core.mv.FlowBlur(clip, super, mvbw, mvfw, ...)    -> FlowBlur(super, bw_data, fw_data, ...)   .run(ns, ...)
+    core.mv.Mask(clip, vectors, ...)                  -> Mask(analysis_data, width, height, ...)  .run(blobs, clip)
 
 Argument names, defaults and error strings are the reference's (MVSuper.c:279-291, MVAnalyse.c:639-671,
 MVDegrains.cpp:813-932, MVCompensate.c:579-592); they are resolved inside the library, not here.
@@ -136,6 +137,25 @@ class FlowBlurJob(C.Structure):
     _fields_ = [("super", C.c_void_p * 3), ("blob_bw", C.c_void_p), ("blob_fw", C.c_void_p), ("clip", C.c_void_p * 3), ("dst", C.c_void_p * 3)]
 
 
+class MaskArgs(C.Structure):
+    _fields_ = [("ml", C.c_double), ("gamma", C.c_double), ("kind", C.c_int32), ("time", C.c_double), ("ysc", C.c_int32), ("thscd1", C.c_int64),
+                ("thscd2", C.c_int32)]
+
+
+class MaskClip(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "bits", "subsampling_w", "subsampling_h", "gray")]
+
+
+class MaskInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "subsampling_w", "subsampling_h", "num_planes")] + [
+        ("plane_width", C.c_int32 * 3), ("plane_height", C.c_int32 * 3), ("time256", C.c_int32), ("fMaskNormFactor", C.c_float),
+        ("fMaskNormFactor2", C.c_float), ("fHalfGamma", C.c_float)]
+
+
+class MaskJob(C.Structure):
+    _fields_ = [("blob", C.c_void_p), ("clip_luma", C.c_void_p), ("dst", C.c_void_p * 3)]
+
+
 _lib = None
 
 
@@ -216,6 +236,11 @@ def lib():
                                           P(C.c_ssize_t), P(C.c_void_p), C.c_char_p]
         L.mvx_flowblur_destroy.argtypes = [C.c_void_p]
         L.mvx_flowblur_frames.argtypes = [C.c_void_p, C.c_int, P(FlowBlurJob), C.c_void_p]
+        L.mvx_mask_create.argtypes = [P(MaskArgs), P(AnalysisData), P(MaskClip), P(C.c_ssize_t), P(C.c_ssize_t), P(C.c_void_p), C.c_char_p]
+        L.mvx_mask_destroy.argtypes = [C.c_void_p]
+        L.mvx_mask_get_info.argtypes = [C.c_void_p, P(MaskInfo)]
+        L.mvx_mask_get_info.restype = None
+        L.mvx_mask_frames.argtypes = [C.c_void_p, C.c_int, P(MaskJob), C.c_void_p]
         L.mvx_scale_thscd.argtypes = [P(C.c_int64), P(C.c_int32), P(AnalysisData)]
         L.mvx_vectors_size.argtypes = [P(AnalysisData)]
         L.mvx_vectors_size.restype = C.c_int
@@ -878,6 +903,68 @@ class FlowBlur:
                     arr[k].super[p] = supers[fo][p].data_ptr()
                 arr[k].blob_bw = blobs_bw[fo - d].data_ptr()
                 arr[k].blob_fw = blobs_fw[fo + d].data_ptr()
+        return arr, out
+
+
+class Mask:
+    """mv.Mask(clip, vectors, ml, gamma, kind, time, ysc, thscd1, thscd2) -- MVMask.c:227-346.  `width` / `height` / `subsampling` / `gray` /
+    `bits` describe the clip argument (which must have the vector clip's geometry); the output is always three 8-bit planes, 4:4:4 for a
+    Gray clip.  `clip_pitch` is the row pitch of the clip's device planes (only the luma plane is read, by kind 5); `dst_pitch` the row
+    pitches of the output planes (multiples of 16 bytes; default: the plane widths rounded up to 256)."""
+
+    def __init__(self, vectors_ad, width, height, subsampling=(1, 1), gray=False, clip_pitch=None, dst_pitch=None, bits=8, ml=100.0, gamma=1.0,
+                 kind=None, time=100.0, ysc=None, thscd1=None, thscd2=None):
+        a = MaskArgs(float(ml), float(gamma), _u(kind), float(time), _u(ysc), _u(thscd1), _u(thscd2))
+        ad = AnalysisData.from_buffer_copy(bytes(vectors_ad))
+        c = MaskClip(int(width), int(height), int(bits), int(subsampling[0]), int(subsampling[1]), int(bool(gray)))
+        sw, sh = (0, 0) if gray else subsampling
+        if dst_pitch is None:
+            dst_pitch = [((max(int(width) >> s, 1) + 255) // 256) * 256 for s in (0, sw, sw)]
+        if clip_pitch is None:
+            clip_pitch = [dst_pitch[0]]
+        self.h = C.c_void_p()
+        self.kind = 0 if kind is None else int(kind)
+        self.pitch = list(dst_pitch)
+        err = C.create_string_buffer(ERRLEN)
+        _check(lib().mvx_mask_create(C.byref(a), C.byref(ad), C.byref(c), _pad3(clip_pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
+        self.info = MaskInfo()
+        lib().mvx_mask_get_info(self.h, C.byref(self.info))
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().mvx_mask_destroy(self.h)
+        except Exception:
+            pass
+
+    def alloc(self, n, device="cuda"):
+        """n output frames of three planes with this filter's pitches (contents undefined)"""
+        return arena_frames(n, [(self.info.plane_height[p], self.pitch[p]) for p in range(3)], device, zero=False)
+
+    def run(self, blobs, clip=None, out=None):
+        """blobs: per output frame the device blob of the vector clip at that frame (None: unusable); clip: per output frame the clip
+        frame (a list of device planes, of which kind 5 reads the luma), or None for kinds 0-4; all frames in one call"""
+        arr, out = self.jobs(blobs, clip, out)
+        self.launch(arr)
+        return out
+
+    def launch(self, arr):
+        """enqueues a job table (a ctypes array of MaskJob, e.g. from jobs())"""
+        _check(lib().mvx_mask_frames(self.h, len(arr), arr, _stream()))
+
+    def jobs(self, blobs, clip=None, out=None):
+        """the job table of run() and its output frames, without launching"""
+        _torch()
+        n = len(blobs)
+        if out is None:
+            dev = next((b.device for b in blobs if b is not None), "cuda")
+            out = self.alloc(n, dev)
+        arr = (MaskJob * n)()
+        for k, blob in enumerate(blobs):
+            arr[k].blob = blob.data_ptr() if blob is not None else None
+            arr[k].clip_luma = clip[k][0].data_ptr() if clip is not None else None
+            for p in range(3):
+                arr[k].dst[p] = out[k][p].data_ptr()
         return arr, out
 
 
