@@ -14,6 +14,8 @@ import mvtools_amd as mv  # noqa: E402
 
 cfg = bench.CONFIGS[sys.argv[1] if len(sys.argv) > 1 else "cfg3"]
 batch = int(sys.argv[2]) if len(sys.argv) > 2 else 64
+blk, ov = cfg[4].get("blksize", 8), cfg[4].get("overlap", 0)
+nblkx0 = (cfg[0] - ov) // (blk - ov)  # blocks per row of the finest level
 p = bench.Pipeline(mv, torch, cfg, batch, torch.device("cuda", 0), 1)
 out = (C.c_ulonglong * (24 * 8))()  # MVX_MAX_LEVELS x 8
 p.step()
@@ -31,3 +33,6 @@ for lv in range(16):
         if ws + wb:
             print("       stage-2 windows (16x16 row passes): strip form %d (%.1f %%), block form %d -- %.2f blocks per block-form window whose centre differs from the window's first block, %d block-form windows for the limits alone" % (
                 ws, 100.0 * ws / (ws + wb), wb, dev / max(wb, 1), lim))
+            # a group is a whole number of windows (mvx_analyse_spec.h: GT): every window but the last one of a block row is full
+            bpw = b / (ws + wb)
+            print("       %.2f blocks per stage-2 window" % bpw + (" = %.1f windows per block row of %d blocks" % (nblkx0 / bpw, nblkx0) if lv == 0 else ""))

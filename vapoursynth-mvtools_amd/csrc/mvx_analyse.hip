@@ -343,7 +343,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_frames(mvx_ana
         const int fBins = 1024;
         int fNeed = fRow + fMaxBlkX * 16;
         if (fNeed < fRow + fBins * 4) fNeed = fRow + fBins * 4;
-        // the speculative kernel (mvx_analyse_spec.h): [source block | previous row's results, 8 B per block | SAD table of a 32-block group];
+        // the speculative kernel (mvx_analyse_spec.h): [source block | previous row's results, 8 B per block | SAD table of a group: SPEC_TB columns, of which a build uses its group length];
         // the histogram lies over row buffer and table
         // The speculative kernel runs where its row passes apply (16-bit 16x16 blocks overlapping by half, with chroma: cfg3 612 against 555 fps);
         // one block at a time it loses to the serial lean kernel (cfg2 2 557 / 2 894, cfg4 17 180 / 18 764, cfg5 76 / 92 fps:
@@ -417,7 +417,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_frames(mvx_ana
             // TEAM form (r5): the nw waves of a workgroup walk ONE chain.  A chain finishes ~nw times sooner and a launch keeps nw times fewer chains resident
             // per wave slot, so it is the form for launches that do not fill the GPU with one wave per chain (a frame server's look-ahead window); for
             // big batches the choice is measured.  LDS: [64 B control words | row buffer] shared + per wave [source strip | SAD table]
-            const int specSide = (P.blkX == 16 && P.ovX == 0) ? 1 : 0; // 16x16 blocks side by side: the SIDE builds of the speculative kernel (their row passes step by a whole block)
+            const int specSide = ((P.blkX == 16 || stripShape8) && P.ovX == 0) ? 1 : 0; // 16x16 / 8-bit 8x8 blocks side by side: the SIDE builds of the speculative kernel (their row passes step by a whole block, their groups are whole windows of 4 / 8 blocks)
             const int team = useSpec ? teamThatFits(g_dbg.team >= 0 ? g_dbg.team : mvx_team_default(njobs, simds, useSpecStrips, P.bps)) : 0;
             if (team) {
                 ALaunch TL = L;

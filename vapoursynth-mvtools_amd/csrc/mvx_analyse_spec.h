@@ -7,7 +7,7 @@
 // NOT depend on its left neighbour: the zero, global, hierarchical, up and ahead predictors (:834-915), every cost term (lambda and
 // the cost centre come from the interpolated predictor, :449-462) and -- when the predictor phase ends on the up neighbour's vector,
 // which it does whenever the motion field is locally smooth -- the whole refinement pattern around it (:667-724, :786-791).
-// So a chain is processed in GROUPS of 32 blocks of a row:
+// So a chain is processed in GROUPS of up to 32 blocks of a row (SpecSearcher::GT: a whole number of the build's row-pass windows):
 //
 //   A   for every block of the group, with all 64 lanes and nothing to wait for but memory: the SADs of the left-independent
 //       predictors and of the refinement pattern around the block's UP predictor, written to a table in LDS;
@@ -27,7 +27,7 @@
 #include <type_traits>
 #include "mvx_analyse_fast.h"
 
-#define SPEC_TB 32                        // blocks per group (one table column per block)
+#define SPEC_TB 32                        // columns of the SAD table: the most blocks a group may hold (a build's group is SpecSearcher::GT of them, in whole row-pass windows)
 #define SPEC_STRIDE (SPEC_TB * 8 + 8)     // bytes between the slots of the table: 66 dwords, so that the 16 (32) group leaders of a pass write different banks
 // slots: Hex2 levels: 0-5 hexagon, 6-13 square, 14 up, 15 ahead, 16 zero, 17 global, 18 hierarchical; exhaustive levels: 0-23 rings 1 and 2, 24 up, 25 ahead, 26 zero, 27 global, 28 hierarchical
 #define SPEC_SLOTS_HEX 19
@@ -83,7 +83,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
     int role, nw;
     lds_u8 *shRow;
     LDS_AS int *ctl;
-    // the running global predictor after the blocks lo..hiE-1 of the 64-column chunk at c0, in walk order (:859: every block clips the running value
+    // the running global predictor after the blocks lo..hiE-1 of the frame at c0, in walk order (:859: every block clips the running value
     // with its own limits).  The limits are monotonic along a row: a value that neither the first nor the last block of the group clips passes them all
     __device__ __forceinline__ int team_advance(int g, int c0, int lo, int hiE, bool fwd, int stepX, int hps) const {
         auto clampAt = [&](int v, int li) { const int xb = stepX * (c0 + li); return min(max(v, -((xb + hps) << logPel)), ((pw - xb - hpad - BW - hpad + hps) << logPel) - 1); };
@@ -234,7 +234,6 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
     // HC = 16-byte columns per half block (a 32x32 block row is four columns, blocks step by two); a window is eight columns: 7 (3) blocks;
     // block form: LPB lanes per block, LPC per candidate (four candidates: lanes 0..4 * LPC - 1; lanes 56-63 stay free for the zero vector's strip)
     static constexpr int HC = STRIP_OK ? BW / 16 : 1, SW_BLOCKS = 8 / HC - 1, LPB = 2 * HC, LPC = SW_BLOCKS * LPB;
-    static_assert(!SIDE || (STRIP_OK && HC == 1), "blocks side by side: 16x16 row passes only");
     static constexpr int pickSW(int nt, int w) { return w <= 1 ? 1 : (w <= nt && nt % w == 0) ? w : pickSW(nt, w - 1); } // rows in flight: a divisor of the rows of a pass
     static constexpr int SNA = BW, SNB = UV ? BW / 2 : 0, SNT = SNA + SNB, SW = pickSW(SNT, (BW == 32 && SWIN > 12) ? 12 : SWIN), S_UV = SNA * ROWB, SSTG = SNT / 8; // (32x32: 12 in flight -- 24 plus the six staging pieces spill) // rows of a pass, loads in flight, LDS offset of the UV rows, staging pieces per lane
     struct StripPass { v4u r[SW]; unsigned curA, curB, aL, aC; };
@@ -276,6 +275,15 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
     // load.  12 rows per pass (8 luma + 4 of the UV plane), all in flight; the window's source strip is 12 rows x 64 B in LDS.
     static constexpr bool STRIP8_OK = UV && BPS == 1 && BW == 8;
     static constexpr int W8_BLOCKS = 15, R8A = 8, R8B = 4, R8T = R8A + R8B;
+    static_assert(!SIDE || (STRIP_OK && HC == 1) || STRIP8_OK, "blocks side by side: the 16x16 and the 8-bit 8x8 row passes only");
+    // ---- the walk's geometry.  A row pass costs the same whatever its lanes do, so a group is a WHOLE number of the build's windows and a frame -- the columns
+    // whose predictors and results the lanes hold at a time, lane i <-> column c0 + i -- is two groups: every window but the last one of a block row is full.
+    // 16x16 overlapping: 4 windows of 7 = 28 blocks in a frame of 56 (groups of 32 ran windows of 7, 7, 7, 7, 4: a 4K row of 479 blocks took 75 windows, now
+    // ceil(479 / 7) = 69); 8-bit 8x8 overlapping: 2 windows of 15 = 30 in a frame of 60 (32 were cut into 11, 11, 10: 45 windows, now 32); side by side (4 / 8
+    // blocks per window) and the builds without row passes: 32 in 64 as before.  GT consecutive lanes are distinct modulo SPEC_TB: the table's ring stays valid.
+    static constexpr int WBLK = STRIP_OK ? (SIDE ? 4 : SW_BLOCKS) : STRIP8_OK ? (SIDE ? 8 : W8_BLOCKS) : SPEC_TB; // blocks of a full window
+    static constexpr int GT = SPEC_TB / WBLK * WBLK, FR = 2 * GT;                                                  // blocks of a group, columns of a frame
+    static_assert(GT >= 1 && GT <= SPEC_TB && FR <= 64, "a group fits the table, a frame the wave");
     struct Strip8 { v4u r[R8T]; unsigned curA, curB; unsigned aL[4], aC[4]; };
     __device__ __forceinline__ v4u strip8_issue(Strip8 &T, int piece) const { // (byte-aligned 16-byte loads: 8-bit samples sit anywhere)
         v4u v;
@@ -332,7 +340,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
         }
     }
 
-    // GroupOfPlanes.c:69-125 + PlaneOfBlocks.cpp:971-1131 for one level, in groups of SPEC_TB blocks
+    // GroupOfPlanes.c:69-125 + PlaneOfBlocks.cpp:971-1131 for one level, in groups of GT blocks
     __device__ __forceinline__ void search_level_spec(int lvl, int globalX, int globalY, GL_AS const GVec *coarse, int coarseBlkX, int coarseBlkY, int coarseLogPel, int syncEvery, bool specEnabled, bool stripEnabled) {
         const int l = lane_id();
         const ALevel &L = P.lv[lvl];
@@ -401,7 +409,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
         unsigned sPat = 0, bPat0 = 0, bPat1 = 0;
         {
             // (8-bit row passes: sixteen strip candidates of four lanes per pass, block candidates of fifteen lanes)
-            const bool side8 = STRIP8_OK && stepX == BW; // (blocks side by side: eight block candidates of eight lanes per pass)
+            constexpr bool side8 = STRIP8_OK && SIDE; // (blocks side by side: eight block candidates of eight lanes per pass)
             // (16-bit: LPC lanes per block-form candidate -- 14 for 16x16 blocks.  r4 had the 14 written out here, which made the block-form stage 2 of a 32x32 build
             // (LPC = 12) mix two pattern points in the blocks of lanes 12-13, 24-27 and 36-41: the "8K clip that disagreed with the oracle" of r4 -- one block in
             // 128 851, profiles/r5_strip32_mismatch_found.txt)
@@ -420,10 +428,11 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
 #endif
 
         int prevX = 0, prevY = 0, prevSad = 0;
-        int syncCount = 0;
-        if (syncEvery > 0 && syncEvery < 32) syncEvery = 32; // (a group is the unit)
+        const int syncGroups = syncEvery > 0 ? max(1, (syncEvery + GT / 2) / GT) : 0; // (a group is the unit: the whole number of groups nearest to syncEvery blocks)
+        int syncCount = syncGroups - 1;             // groups since the last barrier (the first group of a level meets one); counted up and reset -- counted down, this
+                                                    // costs the cfg3 build two more spilled registers
         int Gc = 0;                                 // groups of this level so far, in walk order (TEAM: the token's unit)
-        const int nGrpRow = (nBlkX + SPEC_TB - 1) / SPEC_TB;
+        const int nGrpRow = (nBlkX + GT - 1) / GT;  // (a frame is two groups: the frames of a row hold ceil(nBlkX / GT) of them)
         for (int blky = 0; blky < nBlkY; blky++) {
             const bool fwd = (blky & 1) == 0 || !meander;
             const int dir = fwd ? 1 : -1;
@@ -432,20 +441,19 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
             nDyMin = -((y0 - vpad + vps) << logPel);
             if constexpr (TEAM) gmvy = this->clipy(gmvy); // (every wave follows the running global predictor through the groups it does not own; the row's clip is idempotent)
             const bool specRow = specLevel && blky > 0;
-            const int ngrp = (nBlkX + 63) >> 6;
+            const int ngrp = (nBlkX + FR - 1) / FR;
             for (int gi = 0; gi < ngrp; gi++) {
                 const int grp = fwd ? gi : ngrp - 1 - gi;
-                const int c0 = grp << 6, c = c0 + l;
-                const bool in = c < nBlkX;
-                const int ncol = min(64, nBlkX - c0);
-                // ---- 64 columns at a time (lane i <-> column c0 + i): the interpolated predictors of this row and of the blocks "below-ahead",
-                // the previous row's results; lambda lane-parallel (:456-462)
-                // ---- 64 columns at a time (lane i <-> column c0 + i).  What a group keeps in registers across its passes is little: the results and,
+                const int c0 = grp * FR, c = c0 + l;
+                const int ncol = min(FR, nBlkX - c0);
+                const bool in = l < ncol; // (the lanes beyond the frame hold no column)
+                // ---- a frame of FR columns at a time (lane i <-> column c0 + i): the interpolated predictors of this row and of the blocks "below-ahead",
+                // the previous row's results; lambda lane-parallel (:456-462).  What a group keeps in registers across its passes is little: the results and,
                 // in speculated rows, four packed predictors and lambda per block; the live search of a single block reads its predictors itself.
                 v4u bOut = {0, 0, 0, 0};
                 for (int hi = 0; hi < 2; hi++) {
                     const int h = fwd ? hi : 1 - hi;
-                    const int lo = h * SPEC_TB, hiE = min(lo + SPEC_TB, ncol);
+                    const int lo = h * GT, hiE = min(lo + GT, ncol);
                     if (lo >= ncol) continue;
                     const int myG = Gc++;
                     bool teamHeld = false; // TEAM: this wave holds the token (prevX / prevY / prevSad / badcount are the walk's)
@@ -457,7 +465,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                         if (specRow) {
                             // phase A1 reads the previous block row's results of this group's columns (in the last block row also of the column ahead, :441-447):
                             // they are written when the token has passed the group(s) of the previous row that cover them
-                            const int j = (c0 >> 5) + h;
+                            const int j = 2 * grp + h; // this group's number in its row, left to right
                             const bool fwdPrev = ((blky - 1) & 1) == 0 || !meander;
                             auto idxPrev = [&](int jj) { return fwdPrev ? jj : nGrpRow - 1 - jj; };
                             int need = (blky - 1) * nGrpRow + idxPrev(j) + 1;
@@ -468,7 +476,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                         }
                     }
                     SPROF(7);
-                    if (syncEvery && (syncCount++ & ((syncEvery >> 5) - 1)) == 0) __builtin_amdgcn_s_barrier(); // keeps the chains of a workgroup on neighbouring blocks (shared reference lines): every syncEvery / 32 groups
+                    if (syncGroups && ++syncCount == syncGroups) { __builtin_amdgcn_s_barrier(); syncCount = 0; } // keeps the chains of a workgroup on neighbouring blocks (shared reference lines): every syncGroups groups, for every chain alike (the levels' geometry is the launch's)
                     SPROF(0);
                     const bool act = l >= lo && l < hiE;
                     unsigned long long okmask = 0, flagmask = 0;
@@ -484,7 +492,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                         const int dxMin = -((xs + hps) << logPel), dxMax1 = ((pw - xs - hpad - BW - hpad + hps) << logPel) - 1;
                         auto cx = [&](int v) { return min(max(v, dxMin), dxMax1); };
                         auto cy = [&](int v) { return min(max(v, nDyMin), nDyMax - 1); };
-                        // the interpolated predictors of this row and of the blocks "below-ahead", the previous row's results (one load each per 64 columns)
+                        // the interpolated predictors of this row and of the blocks "below-ahead", the previous row's results (one load each per frame)
                         v4u bSelf = {0, 0, 0, 0}, bBelow = {0, 0, 0, 0};
                         unsigned upPk = 0;
                         if (in) {
@@ -618,7 +626,8 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                 constexpr bool side = SIDE;
                                 if (stripEnabled && stepX == (side ? BW : BW / 2) && (UV ? chroma != 0 : chroma == 0)) {
                                     constexpr int TC = side ? 2 : HC, SWB = side ? 4 : SW_BLOCKS, LPCr = SWB * LPB; // columns per block step, blocks per window, lanes per block-form candidate
-                                    const int nw = (nb + SWB - 1) / SWB;
+                                    static_assert(SWB == WBLK, "the group length is counted in these windows");
+                                    const int nw = (nb + SWB - 1) / SWB; // (nb = GT: whole windows; fewer only in the last group of a block row)
                                     const int npat = hexLevel ? 14 : 24;
                                     pbMask = 0;
                                     staged2 = true;
@@ -801,7 +810,8 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                 auto rows8 = [&](auto DS2) {
                                     constexpr bool ds2 = decltype(DS2)::value;    // a block step is two dwords: blocks do not overlap (a compile-time copy each: as a run-time flag it cost cfg2 4 %)
                                     const int wmax = ds2 ? 8 : W8_BLOCKS;        // sixteen dwords: 15 blocks of two dwords overlapping by one / 8 blocks side by side
-                                    const int nw = (nb + wmax - 1) / wmax, WL = (nb + nw - 1) / nw; // windows of equal length (32 blocks overlapping: 11, 11, 10)
+                                    static_assert((ds2 ? 8 : W8_BLOCKS) == WBLK, "the group length is counted in these windows");
+                                    const int nw = (nb + wmax - 1) / wmax, WL = (nb + nw - 1) / nw; // windows of equal length (nb = GT: full ones; the last group of a block row: e.g. 29 blocks overlapping as 15, 14)
                                     const int npat = hexLevel ? 14 : 24;
                                     pbMask = 0;
                                     staged2 = true;
@@ -945,10 +955,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                     }
                                     run_stage(2);
                                 };
-                                if (stripEnabled && nb >= 3) {
-                                    if (stepX == BW / 2) rows8(std::false_type());
-                                    else if (stepX == BW) rows8(std::true_type());
-                                }
+                                if (stripEnabled && nb >= 3 && stepX == (SIDE ? BW : BW / 2)) rows8(std::integral_constant<bool, SIDE>());
                             }
 
                             SPROF(2);
@@ -1311,7 +1318,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                     sprof[9] += 1;
 #endif
                 }
-                // ---- results of the 64 columns (:967, :1106)
+                // ---- results of the frame's columns (:967, :1106)
                 if (!TEAM && in) {
                     typedef unsigned a4v __attribute__((ext_vector_type(4), aligned(4)));
                     const a4v t = {bOut[0], bOut[1], bOut[2], 0u}; // (block SADs are non-negative and < 2^31)
