@@ -46,7 +46,6 @@ extern "C" __attribute__((visibility("default"))) void mvx_debug_last_launch(int
     for (int i = 0; i < 5; i++) out[i] = g_lastLaunch[i].load();
 }
 
-#define AFAIL(...) do { snprintf(err, MVX_ERRLEN, __VA_ARGS__); mvx_set_error("%s", err); return MVX_E_ARG; } while (0)
 static int A(int v, int d) { return v == MVX_UNSET ? d : v; }
 
 // MVAnalyse.c:267-635 mvanalyseCreate
@@ -103,10 +102,7 @@ __global__ __launch_bounds__(256) void analyse_divide_kernel(const AParams *Pp, 
 
 extern "C" __attribute__((visibility("default"))) int mvx_analyse_create(const mvx_analyse_args *a, const mvx_super *sup, int num_frames, const ptrdiff_t super_pitch[3],
                                   mvx_analyse **out, char *err) {
-    char dummy[MVX_ERRLEN];
-    if (!err) err = dummy;
-    err[0] = 0;
-    *out = nullptr;
+    MVX_CREATE_BEGIN(out);
     const mvx_super_info &si = sup->info;
     mvx_analysis_data ad;
     memset(&ad, 0, sizeof(ad));
@@ -140,27 +136,27 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_create(const m
     P.meander = !!A(a->meander, 1);
     P.tryMany = !!A(a->trymany, 0);
 
-    if (P.searchType < 0 || P.searchType > 7) AFAIL("Analyse: search must be between 0 and 7 (inclusive).");
-    if (P.searchTypeCoarse < 0 || P.searchTypeCoarse > 7) AFAIL("Analyse: search_coarse must be between 0 and 7 (inclusive).");
-    if (P.dctmode < 0 || P.dctmode > 10) AFAIL("Analyse: dct must be between 0 and 10 (inclusive).");
-    if (P.dctmode >= 5 && ad.nBlkSizeX == 16 && ad.nBlkSizeY == 2) AFAIL("Analyse: dct 5..10 cannot work with 16x2 blocks.");
-    if (P.dctmode >= 1 && P.dctmode <= 4) AFAIL("Analyse: dct 1..4 (FFTW3 DCT cost) are not implemented on the GPU path.");
-    if (divide < 0 || divide > 2) AFAIL("Analyse: divide must be between 0 and 2 (inclusive).");
+    if (P.searchType < 0 || P.searchType > 7) MVX_FAIL("Analyse: search must be between 0 and 7 (inclusive).");
+    if (P.searchTypeCoarse < 0 || P.searchTypeCoarse > 7) MVX_FAIL("Analyse: search_coarse must be between 0 and 7 (inclusive).");
+    if (P.dctmode < 0 || P.dctmode > 10) MVX_FAIL("Analyse: dct must be between 0 and 10 (inclusive).");
+    if (P.dctmode >= 5 && ad.nBlkSizeX == 16 && ad.nBlkSizeY == 2) MVX_FAIL("Analyse: dct 5..10 cannot work with 16x2 blocks.");
+    if (P.dctmode >= 1 && P.dctmode <= 4) MVX_FAIL("Analyse: dct 1..4 (FFTW3 DCT cost) are not implemented on the GPU path.");
+    if (divide < 0 || divide > 2) MVX_FAIL("Analyse: divide must be between 0 and 2 (inclusive).");
     {
         static const int okb[12][2] = { { 4, 4 }, { 8, 4 }, { 8, 8 }, { 16, 2 }, { 16, 8 }, { 16, 16 }, { 32, 16 }, { 32, 32 }, { 64, 32 }, { 64, 64 }, { 128, 64 }, { 128, 128 } };
         bool found = false;
         for (auto &b : okb) found |= (ad.nBlkSizeX == b[0] && ad.nBlkSizeY == b[1]);
-        if (!found) AFAIL("Analyse: the block size must be 4x4, 8x4, 8x8, 16x2, 16x8, 16x16, 32x16, 32x32, 64x32, 64x64, 128x64, or 128x128.");
+        if (!found) MVX_FAIL("Analyse: the block size must be 4x4, 8x4, 8x8, 16x2, 16x8, 16x16, 32x16, 32x32, 64x32, 64x64, 128x64, or 128x128.");
     }
-    if (P.plevel < 0 || P.plevel > 2) AFAIL("Analyse: plevel must be between 0 and 2 (inclusive).");
-    if (P.pnew < 0 || P.pnew > 256) AFAIL("Analyse: pnew must be between 0 and 256 (inclusive).");
-    if (P.pzero < 0 || P.pzero > 256) AFAIL("Analyse: pzero must be between 0 and 256 (inclusive).");
-    if (P.pglobal < 0 || P.pglobal > 256) AFAIL("Analyse: pglobal must be between 0 and 256 (inclusive).");
+    if (P.plevel < 0 || P.plevel > 2) MVX_FAIL("Analyse: plevel must be between 0 and 2 (inclusive).");
+    if (P.pnew < 0 || P.pnew > 256) MVX_FAIL("Analyse: pnew must be between 0 and 256 (inclusive).");
+    if (P.pzero < 0 || P.pzero > 256) MVX_FAIL("Analyse: pzero must be between 0 and 256 (inclusive).");
+    if (P.pglobal < 0 || P.pglobal > 256) MVX_FAIL("Analyse: pglobal must be between 0 and 256 (inclusive).");
     if (ad.nOverlapX < 0 || ad.nOverlapX > ad.nBlkSizeX / 2 || ad.nOverlapY < 0 || ad.nOverlapY > ad.nBlkSizeY / 2)
-        AFAIL("Analyse: overlap must be at most half of blksize, overlapv must be at most half of blksizev, and they both need to be at least 0.");
-    if (divide && (ad.nBlkSizeX < 8 || ad.nBlkSizeY < 8)) AFAIL("Analyse: blksize and blksizev must be at least 8 when divide=True."); // :447
+        MVX_FAIL("Analyse: overlap must be at most half of blksize, overlapv must be at most half of blksizev, and they both need to be at least 0.");
+    if (divide && (ad.nBlkSizeX < 8 || ad.nBlkSizeY < 8)) MVX_FAIL("Analyse: blksize and blksizev must be at least 8 when divide=True."); // :447
     if (divide && (ad.nOverlapX % (2 * si.xRatioUV) || ad.nOverlapY % (2 * si.yRatioUV)))                                                    // :503-505
-        AFAIL("Analyse: overlap and overlapv must be multiples of 2 or 4 when divide=True, depending on the super clip's subsampling.");
+        MVX_FAIL("Analyse: overlap and overlapv must be multiples of 2 or 4 when divide=True, depending on the super clip's subsampling.");
     if (P.searchType == SearchNstep) P.nSearchParam = searchparam < 0 ? 0 : searchparam;
     else P.nSearchParam = searchparam < 1 ? 1 : searchparam;
 
@@ -177,10 +173,10 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_create(const m
     ad.nMotionFlags = (opt ? MOTION_USE_SIMD : 0) | (ad.isBackward ? MOTION_IS_BACKWARD : 0) | (chroma ? MOTION_USE_CHROMA_MOTION : 0);
     ad.nCPUFlags = 0; // host-dependent in the reference (g_cpuinfo, MVAnalyse.c:492-494); no CPU kernels here
     if (ad.nOverlapX % si.xRatioUV || ad.nOverlapY % si.yRatioUV)
-        AFAIL("Analyse: The requested overlap is incompatible with the super clip's subsampling.");
-    if (ad.nDeltaFrame <= 0 && (-ad.nDeltaFrame) >= num_frames) AFAIL("Analyse: delta points to frame past the input clip's end.");
+        MVX_FAIL("Analyse: The requested overlap is incompatible with the super clip's subsampling.");
+    if (ad.nDeltaFrame <= 0 && (-ad.nDeltaFrame) >= num_frames) MVX_FAIL("Analyse: delta points to frame past the input clip's end.");
     ad.yRatioUV = si.yRatioUV; ad.xRatioUV = si.xRatioUV;
-    if ((nModeYUV & si.modeYUV) != nModeYUV) AFAIL("Analyse: super clip does not contain needed colour data.");
+    if ((nModeYUV & si.modeYUV) != nModeYUV) MVX_FAIL("Analyse: super clip does not contain needed colour data.");
     ad.nWidth = si.super_width - si.hpad * 2;
     ad.nHeight = si.height;
     ad.nPel = si.pel;
@@ -195,9 +191,9 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_create(const m
            ((nHeight_B >> nLevelsMax) - ad.nOverlapY) / (ad.nBlkSizeY - ad.nOverlapY) > 0)
         nLevelsMax++;
     ad.nLvCount = levels > 0 ? levels : nLevelsMax + levels;
-    if (ad.nLvCount < 1 || ad.nLvCount > nLevelsMax) AFAIL("Analyse: invalid number of levels.");
-    if (ad.nLvCount > si.levels) AFAIL("Analyse: super clip has %d levels. Analyse needs %d levels.", si.levels, ad.nLvCount);
-    if (ad.nLvCount > MVX_MAX_LEVELS) AFAIL("Analyse: too many levels.");
+    if (ad.nLvCount < 1 || ad.nLvCount > nLevelsMax) MVX_FAIL("Analyse: invalid number of levels.");
+    if (ad.nLvCount > si.levels) MVX_FAIL("Analyse: super clip has %d levels. Analyse needs %d levels.", si.levels, ad.nLvCount);
+    if (ad.nLvCount > MVX_MAX_LEVELS) MVX_FAIL("Analyse: too many levels.");
     if (P.nPelSearch <= 0) P.nPelSearch = ad.nPel;
 
     // ---- device parameter block
@@ -209,7 +205,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_create(const m
     P.verybigSAD = (long long)P.blkX * P.blkY * (1 << si.bits);
     P.superHPad = si.hpad; P.superVPad = si.vpad;
     for (int p = 0; p < 3; p++) P.pitch[p] = p < si.num_planes ? super_pitch[p] : 0;
-    if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) AFAIL("Analyse: the U and V planes of the super clip must share one pitch.");
+    if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) MVX_FAIL("Analyse: the U and V planes of the super clip must share one pitch.");
     int blobOff = 8;
     for (int i = ad.nLvCount - 1; i >= 0; i--) { // GroupOfPlanes.c:25-56 (block grid per level), :167-174 (blob layout)
         ALevel &L = P.lv[i];
@@ -493,14 +489,10 @@ struct mvx_recalculate {
     CallGuard guard;
 };
 
-#define RFAIL(...) do { snprintf(err, MVX_ERRLEN, __VA_ARGS__); mvx_set_error("%s", err); return MVX_E_ARG; } while (0)
 
 extern "C" __attribute__((visibility("default"))) int mvx_recalculate_create(const mvx_recalculate_args *a, const mvx_super *sup, const mvx_analysis_data *vectors,
                                                                              const ptrdiff_t super_pitch[3], mvx_recalculate **out, char *err) {
-    char dummy[MVX_ERRLEN];
-    if (!err) err = dummy;
-    err[0] = 0;
-    *out = nullptr;
+    MVX_CREATE_BEGIN(out);
     const mvx_super_info &si = sup->info;
     auto A64 = [](int64_t v, int64_t d) { return v == MVX_UNSET ? d : v; };
     mvx_analysis_data ad;
@@ -524,29 +516,29 @@ extern "C" __attribute__((visibility("default"))) int mvx_recalculate_create(con
     P.meander = !!A64(a->meander, 1);
     // fields: the shift MVRecalculate.c:171-175 derives only feeds zeroMVfieldShifted / globalMVPredictor (PlaneOfBlocks.cpp:1167-1171),
     // which the recalculation never reads (ONLY_CHECK_NONDEFAULT_MV is not defined, PlaneOfBlocks.h:37): accepted, no effect on the blob.
-    if (P.searchType < 0 || P.searchType > 7) RFAIL("Recalculate: search must be between 0 and 7 (inclusive).");
-    if (P.dctmode < 0 || P.dctmode > 10) RFAIL("Recalculate: dct must be between 0 and 10 (inclusive).");
-    if (P.dctmode >= 5 && ad.nBlkSizeX == 16 && ad.nBlkSizeY == 2) RFAIL("Recalculate: dct 5..10 cannot work with 16x2 blocks.");
-    if (P.dctmode >= 1 && P.dctmode <= 4) RFAIL("Recalculate: dct 1..4 (FFTW3 DCT cost) are not implemented on the GPU path.");
-    if (divide < 0 || divide > 2) RFAIL("Recalculate: divide must be between 0 and 2 (inclusive).");
+    if (P.searchType < 0 || P.searchType > 7) MVX_FAIL("Recalculate: search must be between 0 and 7 (inclusive).");
+    if (P.dctmode < 0 || P.dctmode > 10) MVX_FAIL("Recalculate: dct must be between 0 and 10 (inclusive).");
+    if (P.dctmode >= 5 && ad.nBlkSizeX == 16 && ad.nBlkSizeY == 2) MVX_FAIL("Recalculate: dct 5..10 cannot work with 16x2 blocks.");
+    if (P.dctmode >= 1 && P.dctmode <= 4) MVX_FAIL("Recalculate: dct 1..4 (FFTW3 DCT cost) are not implemented on the GPU path.");
+    if (divide < 0 || divide > 2) MVX_FAIL("Recalculate: divide must be between 0 and 2 (inclusive).");
     {
         static const int okb[12][2] = { { 4, 4 }, { 8, 4 }, { 8, 8 }, { 16, 2 }, { 16, 8 }, { 16, 16 }, { 32, 16 }, { 32, 32 }, { 64, 32 }, { 64, 64 }, { 128, 64 }, { 128, 128 } };
         bool found = false;
         for (auto &b : okb) found |= (ad.nBlkSizeX == b[0] && ad.nBlkSizeY == b[1]);
-        if (!found) RFAIL("Recalculate: the block size must be 4x4, 8x4, 8x8, 16x2, 16x8, 16x16, 32x16, 32x32, 64x32, 64x64, 128x64, or 128x128.");
+        if (!found) MVX_FAIL("Recalculate: the block size must be 4x4, 8x4, 8x8, 16x2, 16x8, 16x16, 32x16, 32x32, 64x32, 64x64, 128x64, or 128x128.");
     }
-    if (P.pnew < 0 || P.pnew > 256) RFAIL("Recalculate: pnew must be between 0 and 256 (inclusive).");
+    if (P.pnew < 0 || P.pnew > 256) MVX_FAIL("Recalculate: pnew must be between 0 and 256 (inclusive).");
     if (ad.nOverlapX < 0 || ad.nOverlapX > ad.nBlkSizeX / 2 || ad.nOverlapY < 0 || ad.nOverlapY > ad.nBlkSizeY / 2)
-        RFAIL("Recalculate: overlap must be at most half of blksize, overlapv must be at most half of blksizev, and they both need to be at least 0.");
-    if (divide && (ad.nBlkSizeX < 8 || ad.nBlkSizeY < 8)) RFAIL("Recalculate: blksize and blksizev must be at least 8 when divide=True.");
+        MVX_FAIL("Recalculate: overlap must be at most half of blksize, overlapv must be at most half of blksizev, and they both need to be at least 0.");
+    if (divide && (ad.nBlkSizeX < 8 || ad.nBlkSizeY < 8)) MVX_FAIL("Recalculate: blksize and blksizev must be at least 8 when divide=True.");
     if (P.searchType == SearchNstep) P.nSearchParam = searchparam < 0 ? 0 : searchparam;
     else P.nSearchParam = searchparam < 1 ? 1 : searchparam;
-    if (ad.nOverlapX % si.xRatioUV || ad.nOverlapY % si.yRatioUV) RFAIL("Recalculate: The requested overlap is incompatible with the super clip's subsampling.");
+    if (ad.nOverlapX % si.xRatioUV || ad.nOverlapY % si.yRatioUV) MVX_FAIL("Recalculate: The requested overlap is incompatible with the super clip's subsampling.");
     if (divide && (ad.nOverlapX % (2 * si.xRatioUV) || ad.nOverlapY % (2 * si.yRatioUV)))
-        RFAIL("Recalculate: overlap and overlapv must be multiples of 2 or 4 when divide=True, depending on the super clip's subsampling.");
+        MVX_FAIL("Recalculate: overlap and overlapv must be multiples of 2 or 4 when divide=True, depending on the super clip's subsampling.");
     if (si.gray) chroma = 0;
     const int nModeYUV = chroma ? 7 : 1;
-    if ((nModeYUV & si.modeYUV) != nModeYUV) RFAIL("Recalculate: super clip does not contain needed colour data.");
+    if ((nModeYUV & si.modeYUV) != nModeYUV) MVX_FAIL("Recalculate: super clip does not contain needed colour data.");
     ad.yRatioUV = vectors->yRatioUV; ad.xRatioUV = vectors->xRatioUV;
     ad.nWidth = vectors->nWidth; ad.nHeight = vectors->nHeight;
     ad.nDeltaFrame = vectors->nDeltaFrame; ad.isBackward = vectors->isBackward;
@@ -558,8 +550,8 @@ extern "C" __attribute__((visibility("default"))) int mvx_recalculate_create(con
     if (chroma) thSAD += thSAD / (ad.xRatioUV * ad.yRatioUV) * 2;
     ad.nMotionFlags = MOTION_USE_SIMD | (ad.isBackward ? MOTION_IS_BACKWARD : 0) | (chroma ? MOTION_USE_CHROMA_MOTION : 0);
     ad.nPel = si.pel;
-    if (si.height != ad.nHeight || si.super_width - 2 * si.hpad != ad.nWidth) RFAIL("Recalculate: wrong frame size.");
-    if (ad.xRatioUV != si.xRatioUV || ad.yRatioUV != si.yRatioUV) RFAIL("Recalculate: wrong frame size.");
+    if (si.height != ad.nHeight || si.super_width - 2 * si.hpad != ad.nWidth) MVX_FAIL("Recalculate: wrong frame size.");
+    if (ad.xRatioUV != si.xRatioUV || ad.yRatioUV != si.yRatioUV) MVX_FAIL("Recalculate: wrong frame size.");
     ad.nHPadding = si.hpad; ad.nVPadding = si.vpad;
     ad.nBlkX = (ad.nWidth - ad.nOverlapX) / (ad.nBlkSizeX - ad.nOverlapX);
     ad.nBlkY = (ad.nHeight - ad.nOverlapY) / (ad.nBlkSizeY - ad.nOverlapY);
@@ -573,7 +565,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_recalculate_create(con
     P.verybigSAD = (long long)P.blkX * P.blkY * (1 << si.bits);
     P.superHPad = si.hpad; P.superVPad = si.vpad;
     for (int p = 0; p < 3; p++) P.pitch[p] = p < si.num_planes ? super_pitch[p] : 0;
-    if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) RFAIL("Recalculate: the U and V planes of the super clip must share one pitch.");
+    if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) MVX_FAIL("Recalculate: the U and V planes of the super clip must share one pitch.");
     {
         ALevel &L = P.lv[0];
         L.nBlkX = ad.nBlkX; L.nBlkY = ad.nBlkY; L.pel = ad.nPel; L.logPel = mvx_ilog2(L.pel);

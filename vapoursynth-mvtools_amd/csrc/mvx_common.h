@@ -24,6 +24,32 @@ void mvx_divided_data(const mvx_analysis_data *in, mvx_analysis_data *out);
         }                                                                                         \
     } while (0)
 
+// ---- functions that report through `char *err` (MVX_ERRLEN bytes, may be NULL).  They open with MVX_CREATE_BEGIN (MVX_ERR_BEGIN where
+// there is no handle to return); an argument error leaves through MVX_FAIL: the message in err and in mvx_last_error, MVX_E_ARG returned.
+#define MVX_ERR_BEGIN() char dummy[MVX_ERRLEN]; if (!err) err = dummy; err[0] = 0
+#define MVX_CREATE_BEGIN(out) MVX_ERR_BEGIN(); *(out) = nullptr
+#define MVX_FAIL(...) do { snprintf(err, MVX_ERRLEN, __VA_ARGS__); mvx_set_error("%s", err); return MVX_E_ARG; } while (0)
+
+// ---- device scratch that a handle owns: count elements of T, freed with the handle.  reserve() leaves a buffer that is large enough
+// alone; one that is too small is freed FIRST (hipFree synchronises the device: no earlier kernel still reads it) and replaced by one of
+// count + headroom elements.  On failure p == nullptr and cap == 0, so the next call starts over.
+template <typename T> struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    hipError_t reserve(size_t count, size_t headroom = 0) {
+        if (count <= cap) return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc((void **)&p, (count + headroom) * sizeof(T));
+        if (e == hipSuccess) cap = count + headroom; else p = nullptr;
+        return e;
+    }
+};
+
 // ---- thread / stream safety of the *_frames entry points.  A handle owns device scratch (job tables, plans, masks) that every
 // call overwrites.  VapourSynth calls a filter's getFrame concurrently (fmParallel), possibly with different streams, so each
 // call (a) holds the handle's mutex while it enqueues, and (b) makes its stream wait for the event the previous call on the same

@@ -1,4 +1,5 @@
-// mvx_degrain.hip -- mv.Degrain1..6 and mv.Compensate on gfx950.
+// mvx_degrain.hip -- the block filters on gfx950: mv.Degrain1..6 and mv.Compensate (first half), mv.BlockFPS and mv.SCDetection (second half,
+// each under its own heading).  What they share with the flow filters and mv.Mask is in mvx_fps_shared.h.
 //
 // The reference walks blocks, blends each block into a temp (Degrain_C, MVDegrains.h:30-53), scatters it times a
 // raised-cosine window into a 16/32-bit accumulator (overlaps_c, Overlap.cpp:143-158) and finally normalises
@@ -11,7 +12,6 @@
 #include "mvx_fps_shared.h"
 
 #define MOTION_USE_CHROMA_MOTION 8
-
 
 // ------------------------------------------------------------------------------------------------ host helpers
 
@@ -66,7 +66,6 @@ extern "C" __attribute__((visibility("default"))) void mvx_scale_thscd(int64_t *
 
 // ------------------------------------------------------------------------------------------------ shared device structs
 
-
 struct DGParams {
     int nRefs, nBlkX, nBlkY, nBlk, pel, logPel, bits, bps, nplanes, overlap;
     int nLvCount;            // levels in a blob; the level-0 record is found by walking the per-plane size headers like fgopUpdate (Fakery.c:112-123)
@@ -99,24 +98,12 @@ static_assert(sizeof(PlanRecT<6>) == 40 && sizeof(PlanRecT<12>) == 76 && sizeof(
 
 // ------------------------------------------------------------------------------------------------ kernels
 
-// Fakery.c:52-58,103-107,144-146: usable = validity==1 && !(count(sad > thscd1) > thscd2)
-__global__ __launch_bounds__(256) void usable_kernel(const DGParams *Pp, const DGJob *jobs, int *usable, int single) {
+// per (job, reference): fgopIsUsable of the reference's vectors, 0 for a reference frame outside the clip (which may have no blob at all)
+__global__ __launch_bounds__(256) void usable_kernel(const DGParams *Pp, const DGJob *jobs, int *usable) {
     const DGParams &P = *Pp;
     const int f = blockIdx.y, r = blockIdx.x;
-    const unsigned char *blob = single ? jobs[f].blobs[0] : jobs[f].blobs[r];
-    const bool haveRef = single ? true : jobs[f].refs[r][0] != nullptr;
-    __shared__ int cnt;
-    if (threadIdx.x == 0) cnt = 0;
-    __syncthreads();
-    int c = 0;
-    const GVecD *v = mvx_level0(blob, P.nLvCount);
-    for (int i = threadIdx.x; i < P.nBlk; i += 256) c += v[i].sad > P.thscd1 ? 1 : 0;
-    atomicAdd(&cnt, c);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int validity = ((const int *)blob)[1];
-        usable[f * 12 + r] = haveRef && validity == 1 && !(cnt > P.thscd2);
-    }
+    const bool ok = fps_block_usable(jobs[f].blobs[r], jobs[f].refs[r][0] != nullptr, P.nLvCount, P.nBlk, P.thscd1, P.thscd2);
+    if (threadIdx.x == 0) usable[f * 12 + r] = ok;
 }
 
 // MVDegrains.h:184-189
@@ -124,7 +111,6 @@ __device__ __forceinline__ int degrain_weight(long long thSAD, long long blockSA
     if (blockSAD >= thSAD) return 0;
     return (int)((double)((thSAD - blockSAD) * (thSAD + blockSAD) * 256) / (double)(thSAD * thSAD + blockSAD * blockSAD));
 }
-
 
 // (r6: left alone the register allocator takes 162 registers for six references -- three waves per SIMD; asked for six it needs 71 and spills nothing:
 // 4.41 -> 2.78 ms per 341 4K16 frames, profiles/r6_degrain_window_plan_ab.txt)
@@ -596,139 +582,101 @@ __global__ __launch_bounds__(256) void compensate_rows_kernel(const DGParams *Pp
 struct DGCommon {
     CallGuard guard;
     DGParams P;
-    DGParams *dP = nullptr;
-    DGJob *dJobs = nullptr;
-    size_t jobsCap = 0;
-    int *dUsable = nullptr;
-    void *dPlan = nullptr;
-    size_t planCap = 0;
-    int16_t *dWin[2] = { nullptr, nullptr };
+    DevBuf<DGParams> dP;
+    DevBuf<DGJob> dJobs;          // these two grow to twice the call's jobs
+    DevBuf<int> dUsable;
+    DevBuf<unsigned char> dPlan;  // grows to one and a half times the call's plan
+    DevBuf<int16_t> dWin[2];
     int nWinClasses = 1;
-    ~DGCommon() {
-        if (dP) (void)hipFree(dP);
-        if (dJobs) (void)hipFree(dJobs);
-        if (dUsable) (void)hipFree(dUsable);
-        if (dPlan) (void)hipFree(dPlan);
-        if (dWin[0]) (void)hipFree(dWin[0]);
-        if (dWin[1]) (void)hipFree(dWin[1]);
-    }
 };
 struct mvx_degrain : DGCommon { int radius; };
 struct mvx_compensate : DGCommon {};
 
-#define DFAIL(...) do { snprintf(err, MVX_ERRLEN, __VA_ARGS__); mvx_set_error("%s", err); return MVX_E_ARG; } while (0)
-
 static int fill_common(DGCommon *h, const mvx_analysis_data *ad, const mvx_super_info &si, const ptrdiff_t src_pitch[3],
                        const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], char *err) {
     DGParams &P = h->P;
+    memset(&P, 0, sizeof(P));
     P.nBlkX = ad->nBlkX; P.nBlkY = ad->nBlkY; P.nBlk = ad->nBlkX * ad->nBlkY;
     P.pel = ad->nPel; P.logPel = ad->nPel == 4 ? 2 : ad->nPel == 2 ? 1 : 0;
     P.bits = si.bits; P.bps = (si.bits + 7) / 8; P.nplanes = si.num_planes;
     P.overlap = ad->nOverlapX > 0 || ad->nOverlapY > 0;
-    if (P.overlap && (ad->nBlkX < 3 || ad->nBlkY < 3)) DFAIL("overlap needs at least 3x3 blocks (window selection divides by nBlk-2).");
+    if (P.overlap && (ad->nBlkX < 3 || ad->nBlkY < 3)) MVX_FAIL("overlap needs at least 3x3 blocks (window selection divides by nBlk-2).");
     P.nLvCount = ad->nLvCount;
-    const int xSub = mvx_ilog2(si.xRatioUV), ySub = mvx_ilog2(si.yRatioUV);
-    for (int p = 0; p < 3; p++) {
-        PlaneG &g = P.pl[p];
-        const int sx = p ? xSub : 0, sy = p ? ySub : 0;
-        g.subX = sx; g.subY = sy;
-        g.W = ad->nWidth >> sx; g.H = ad->nHeight >> sy;
-        g.blkW = ad->nBlkSizeX >> sx; g.blkH = ad->nBlkSizeY >> sy;
-        g.ovX = ad->nOverlapX >> sx; g.ovY = ad->nOverlapY >> sy;
-        g.stepX = g.blkW - g.ovX; g.stepY = g.blkH - g.ovY;
-        g.WB = (ad->nBlkX * (ad->nBlkSizeX - ad->nOverlapX) + ad->nOverlapX) >> sx;
-        g.HB = (ad->nBlkY * (ad->nBlkSizeY - ad->nOverlapY) + ad->nOverlapY) >> sy;
-        g.hpadPel = (si.hpad >> sx) * si.pel; g.vpadPel = (si.vpad >> sy) * si.pel; // MVFrame.cpp:1334-1335,1775-1779
-        g.srcPitch = src_pitch ? src_pitch[p < si.num_planes ? p : 0] : 0;
-        g.supPitch = super_pitch[p < si.num_planes ? p : 0];
-        g.dstPitch = dst_pitch[p < si.num_planes ? p : 0];
-        g.supPlaneStride = g.supPitch * (long long)((si.height >> sy) + 2 * (si.vpad >> sy));
-        g.thIdx = p ? 1 : 0;
-        g.process = 1; g.limit = (1 << si.bits) - 1;
-        g.shadow = 0;
-    }
-    if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) DFAIL("U and V super planes must share one pitch.");
+    fps_fill_planes(P.pl, ad, si, src_pitch, super_pitch, dst_pitch);
+    if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) MVX_FAIL("U and V super planes must share one pitch.");
     h->nWinClasses = si.num_planes > 1 ? 2 : 1;
     return MVX_OK;
 }
 
 // device state is created on first use so that argument validation works without a GPU
 static int finish_common(DGCommon *h) {
-    if (h->dP) return MVX_OK;
+    if (h->dP.p) return MVX_OK;
     DGParams &P = h->P;
     if (P.overlap) {
         for (int c = 0; c < h->nWinClasses; c++) {
             const PlaneG &g = P.pl[c];
             std::vector<int16_t> w(9 * g.blkW * g.blkH);
             mvx_over_windows(w.data(), g.blkW, g.blkH, g.ovX, g.ovY);
-            HIP_CHECK(hipMalloc((void **)&h->dWin[c], w.size() * 2));
-            HIP_CHECK(hipMemcpy(h->dWin[c], w.data(), w.size() * 2, hipMemcpyHostToDevice));
+            HIP_CHECK(h->dWin[c].reserve(w.size()));
+            HIP_CHECK(hipMemcpy(h->dWin[c].p, w.data(), w.size() * 2, hipMemcpyHostToDevice));
         }
-        P.win[0] = h->dWin[0]; P.win[1] = P.win[2] = h->dWin[1];
+        P.win[0] = h->dWin[0].p; P.win[1] = P.win[2] = h->dWin[1].p;
     }
-    HIP_CHECK(hipMalloc((void **)&h->dP, sizeof(DGParams)));
-    HIP_CHECK(hipMemcpy(h->dP, &h->P, sizeof(DGParams), hipMemcpyHostToDevice));
-    return MVX_OK;
+    return fps_upload_params(h->dP, P);
 }
 
 static int ensure_jobs(DGCommon *h, int nframes, size_t planBytesPerFrame) {
-    if ((size_t)nframes > h->jobsCap) {
-        if (h->dJobs) (void)hipFree(h->dJobs);
-        if (h->dUsable) (void)hipFree(h->dUsable);
-        h->jobsCap = (size_t)nframes * 2;
-        HIP_CHECK(hipMalloc((void **)&h->dJobs, h->jobsCap * sizeof(DGJob)));
-        HIP_CHECK(hipMalloc((void **)&h->dUsable, h->jobsCap * 12 * sizeof(int)));
-    }
-    size_t need = planBytesPerFrame * nframes;
-    if (need > h->planCap) {
-        if (h->dPlan) (void)hipFree(h->dPlan);
-        h->planCap = need + need / 2;
-        HIP_CHECK(hipMalloc(&h->dPlan, h->planCap));
-    }
+    const size_t n = (size_t)nframes, need = planBytesPerFrame * n;
+    HIP_CHECK(h->dJobs.reserve(n, n));
+    HIP_CHECK(h->dUsable.reserve(n * 12, n * 12));
+    HIP_CHECK(h->dPlan.reserve(need, need / 2));
     return MVX_OK;
+}
+
+// samples per thread of the row kernels of Compensate and BlockFPS: up to 16 bytes, dividing the block width and the frame width, so that a
+// segment is never split between cases (`covered`: and the covered width, where Compensate's uncovered strip starts; BlockFPS's starts at
+// nBlkX * blkW).  0: the blocks overlap or are not powers of two -- the per-sample gather
+static int dg_rows_cw(const DGParams &P, int p, bool covered) {
+    if (P.overlap) return 0;
+    const PlaneG &g = P.pl[p];
+    int cw = 16 / P.bps;
+    while (cw > 1 && (g.blkW % cw || g.W % cw || (covered && g.WB % cw))) cw >>= 1;
+    return (cw >= 2 && (g.blkW & (g.blkW - 1)) == 0 && (g.blkH & (g.blkH - 1)) == 0) ? cw : 0;
 }
 
 // MVDegrains.cpp:511-809 mvdegrainCreate
 extern "C" __attribute__((visibility("default"))) int mvx_degrain_create(const mvx_degrain_args *a, const mvx_analysis_data *ad, const mvx_super *sup, const ptrdiff_t src_pitch[3],
                                   const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_degrain **out, char *err) {
-    char dummy[MVX_ERRLEN];
-    if (!err) err = dummy;
-    err[0] = 0;
-    *out = nullptr;
+    MVX_CREATE_BEGIN(out);
     const mvx_super_info &si = sup->info;
     const int radius = a->radius;
-    if (radius < 1 || radius > 6) DFAIL("Degrain: radius must be between 1 and 6.");
+    if (radius < 1 || radius > 6) MVX_FAIL("Degrain: radius must be between 1 and 6.");
+    char name[16]; // the reference's filter name carries the radius
+    snprintf(name, sizeof(name), "Degrain%d", radius);
     long long thSAD0 = a->thsad == MVX_UNSET ? 400 : a->thsad;
     long long thSAD1 = a->thsadc == MVX_UNSET ? thSAD0 : a->thsadc;
     int plane = a->plane == MVX_UNSET ? 4 : a->plane;
-    long long nSCD1 = a->thscd1 == MVX_UNSET ? 400 : a->thscd1; // MV_DEFAULT_SCD1
-    int nSCD2 = a->thscd2 == MVX_UNSET ? 130 : a->thscd2;
-    if (plane < 0 || plane > 4) DFAIL("Degrain%d: plane must be between 0 and 4 (inclusive).", radius);
+    if (plane < 0 || plane > 4) MVX_FAIL("%s: plane must be between 0 and 4 (inclusive).", name);
     static const int planes[5] = { 1, 2, 4, 6, 7 };
     const int YUVplanes = planes[plane];
-    if (nSCD1 > 8 * 8 * 255) DFAIL("Degrain%d: thscd1 can be at most %d.", radius, 8 * 8 * 255);
-    const long long nSCD1_old = nSCD1;
-    int64_t s1 = nSCD1; int32_t s2 = nSCD2;
-    mvx_scale_thscd(&s1, &s2, ad);
-    nSCD1 = s1; nSCD2 = s2;
+    int64_t nSCD1, nSCD1_old; int32_t nSCD2;
+    if (int rc = mvx_resolve_thscd(name, a->thscd1, a->thscd2, ad, &nSCD1, &nSCD2, err, &nSCD1_old)) return rc;
     thSAD0 = thSAD0 * nSCD1 / nSCD1_old; // :658-659
     thSAD1 = thSAD1 * nSCD1 / nSCD1_old;
     if (thSAD0 >= 2147483647LL || thSAD1 >= 2147483647LL) {
         const bool c = thSAD0 < 2147483647LL;
-        DFAIL("Degrain%d: with this block size and video format, thsad%s must not exceed %lld or some calculations would overflow.", radius,
-              c ? "c" : "", (long long)(2147483647LL * nSCD1_old / nSCD1));
+        MVX_FAIL("%s: with this block size and video format, thsad%s must not exceed %lld or some calculations would overflow.", name, c ? "c" : "",
+                 (long long)(2147483647LL * nSCD1_old / nSCD1));
     }
-    if (ad->nHeight != si.height || ad->nWidth != si.super_width - si.hpad * 2 || ad->nWidth != si.width || ad->nPel != si.pel)
-        DFAIL("Degrain%d: wrong source or super clip frame size.", radius);
+    if (!mvx_super_fits(ad, si, true)) MVX_FAIL("%s: wrong source or super clip frame size.", name);
     const int pixelMax = (1 << si.bits) - 1;
     int limit = a->limit == MVX_UNSET ? pixelMax : a->limit;
     int limitc = a->limitc == MVX_UNSET ? limit : a->limitc;
-    if (limit < 0 || limit > pixelMax) DFAIL("Degrain%d: limit must be between 0 and %d (inclusive).", radius, pixelMax);
-    if (limitc < 0 || limitc > pixelMax) DFAIL("Degrain%d: limitc must be between 0 and %d (inclusive).", radius, pixelMax);
+    if (limit < 0 || limit > pixelMax) MVX_FAIL("%s: limit must be between 0 and %d (inclusive).", name, pixelMax);
+    if (limitc < 0 || limitc > pixelMax) MVX_FAIL("%s: limitc must be between 0 and %d (inclusive).", name, pixelMax);
 
     mvx_degrain *h = new mvx_degrain();
     h->radius = radius;
-    memset(&h->P, 0, sizeof(h->P));
     int rc = fill_common(h, ad, si, src_pitch, super_pitch, dst_pitch, err);
     if (rc) { delete h; return rc; }
     DGParams &P = h->P;
@@ -754,7 +702,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_set_ref_shadow
     if (v && v + g0.supPlaneStride * d->P.pel * d->P.pel >= 0xffffffffLL) { mvx_set_error("mvx_degrain_set_ref_shadow: the shifted copy lies beyond 4 GiB of the plane"); return MVX_E_ARG; }
     std::lock_guard<std::mutex> lk(d->guard.mu);
     d->P.pl[0].shadow = d->P.bps == 2 ? v : 0;
-    if (d->dP) HIP_CHECK(hipMemcpy(d->dP, &d->P, sizeof(DGParams), hipMemcpyHostToDevice));
+    if (d->dP.p) HIP_CHECK(hipMemcpy(d->dP.p, &d->P, sizeof(DGParams), hipMemcpyHostToDevice));
     return MVX_OK;
 }
 
@@ -795,11 +743,11 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_frames(mvx_deg
             hj[f].blobs[r] = (const unsigned char *)jobs[f].blobs[r];
         }
     }
-    HIP_CHECK(hipMemcpyAsync(d->dJobs, hj.data(), sizeof(DGJob) * nframes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(usable_kernel, dim3(P.nRefs, nframes), dim3(256), 0, st, d->dP, d->dJobs, d->dUsable, 0);
+    HIP_CHECK(hipMemcpyAsync(d->dJobs.p, hj.data(), sizeof(DGJob) * nframes, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(usable_kernel, dim3(P.nRefs, nframes), dim3(256), 0, st, d->dP.p, d->dJobs.p, d->dUsable.p);
     {
         const dim3 pg((P.nBlk + 255) / 256, nframes);
-#define DGP(N) hipLaunchKernelGGL(degrain_plan_kernel<N>, pg, dim3(256), 0, st, d->dP, d->dJobs, d->dUsable, (PlanRecT<N> *)d->dPlan)
+#define DGP(N) hipLaunchKernelGGL(degrain_plan_kernel<N>, pg, dim3(256), 0, st, d->dP.p, d->dJobs.p, d->dUsable.p, (PlanRecT<N> *)d->dPlan.p)
         switch (P.nRefs) { case 2: DGP(2); break; case 4: DGP(4); break; case 6: DGP(6); break; case 8: DGP(8); break; case 10: DGP(10); break; default: DGP(12); break; }
 #undef DGP
     }
@@ -813,13 +761,13 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_frames(mvx_deg
         for (int cls = 0; cls < (P.nplanes > 1 ? 2 : 1); cls++) {
             const int p0 = cls, npl = cls ? 2 : 1, W = cellW(p0);
             dim3 grid(((P.pl[p0].W + W - 1) / W + 31) / 32, (P.pl[p0].H + 7) / 8, nframes * npl);
-            if (P.bps == 1) launch_degrain_cells<uint8_t>(P.nRefs, W, grid, st, d->dP, d->dJobs, d->dPlan, p0, npl);
-            else launch_degrain_cells<uint16_t>(P.nRefs, W, grid, st, d->dP, d->dJobs, d->dPlan, p0, npl);
+            if (P.bps == 1) launch_degrain_cells<uint8_t>(P.nRefs, W, grid, st, d->dP.p, d->dJobs.p, d->dPlan.p, p0, npl);
+            else launch_degrain_cells<uint16_t>(P.nRefs, W, grid, st, d->dP.p, d->dJobs.p, d->dPlan.p, p0, npl);
         }
     } else {
         dim3 grid((P.pl[0].W + 63) / 64, (P.pl[0].H + 3) / 4, nframes * 3);
-        if (P.bps == 1) launch_degrain<uint8_t>(P.nRefs, grid, st, d->dP, d->dJobs, d->dPlan);
-        else launch_degrain<uint16_t>(P.nRefs, grid, st, d->dP, d->dJobs, d->dPlan);
+        if (P.bps == 1) launch_degrain<uint8_t>(P.nRefs, grid, st, d->dP.p, d->dJobs.p, d->dPlan.p);
+        else launch_degrain<uint16_t>(P.nRefs, grid, st, d->dP.p, d->dJobs.p, d->dPlan.p);
     }
     HIP_CHECK(hipGetLastError());
     return MVX_OK;
@@ -828,28 +776,18 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_frames(mvx_deg
 // MVCompensate.c:419-575 mvcompensateCreate
 extern "C" __attribute__((visibility("default"))) int mvx_compensate_create(const mvx_compensate_args *a, const mvx_analysis_data *ad, const mvx_super *sup,
                                      const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_compensate **out, char *err) {
-    char dummy[MVX_ERRLEN];
-    if (!err) err = dummy;
-    err[0] = 0;
-    *out = nullptr;
+    MVX_CREATE_BEGIN(out);
     const mvx_super_info &si = sup->info;
     const int scBehavior = a->scbehavior == MVX_UNSET ? 1 : !!a->scbehavior;
     long long thSAD = a->thsad == MVX_UNSET ? 10000 : a->thsad;
     const double time = a->time;
-    if (time < 0.0 || time > 100.0) DFAIL("Compensate: time must be between 0.0 and 100.0 (inclusive).");
-    long long nSCD1 = a->thscd1 == MVX_UNSET ? 400 : a->thscd1;
-    int nSCD2 = a->thscd2 == MVX_UNSET ? 130 : a->thscd2;
-    if (nSCD1 > 8 * 8 * 255) DFAIL("Compensate: thscd1 can be at most %d.", 8 * 8 * 255);
-    const long long nSCD1_old = nSCD1;
-    int64_t s1 = nSCD1; int32_t s2 = nSCD2;
-    mvx_scale_thscd(&s1, &s2, ad);
-    nSCD1 = s1; nSCD2 = s2;
+    if (time < 0.0 || time > 100.0) MVX_FAIL("Compensate: time must be between 0.0 and 100.0 (inclusive).");
+    int64_t nSCD1, nSCD1_old; int32_t nSCD2;
+    if (int rc = mvx_resolve_thscd("Compensate", a->thscd1, a->thscd2, ad, &nSCD1, &nSCD2, err, &nSCD1_old)) return rc;
     thSAD = thSAD * nSCD1 / nSCD1_old; // :521
-    if (ad->nHeight != si.height || ad->nWidth != si.super_width - si.hpad * 2 || ad->nWidth != si.width || ad->nPel != si.pel)
-        DFAIL("Compensate: wrong source or super clip frame size.");
-    if (a->fields != MVX_UNSET && a->fields && ad->nPel < 2) DFAIL("Compensate: fields option requires pel > 1."); // :514-517
+    if (!mvx_super_fits(ad, si, true)) MVX_FAIL("Compensate: wrong source or super clip frame size.");
+    if (a->fields != MVX_UNSET && a->fields && ad->nPel < 2) MVX_FAIL("Compensate: fields option requires pel > 1."); // :514-517
     mvx_compensate *h = new mvx_compensate();
-    memset(&h->P, 0, sizeof(h->P));
     int rc = fill_common(h, ad, si, nullptr, super_pitch, dst_pitch, err);
     if (rc) { delete h; return rc; }
     DGParams &P = h->P;
@@ -883,31 +821,22 @@ extern "C" __attribute__((visibility("default"))) int mvx_compensate_frames(mvx_
         hj[f].blobs[0] = (const unsigned char *)jobs[f].blob;
         hj[f].fieldShift = jobs[f].field_shift;
     }
-    HIP_CHECK(hipMemcpyAsync(c->dJobs, hj.data(), sizeof(DGJob) * nframes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(usable_kernel, dim3(1, nframes), dim3(256), 0, st, c->dP, c->dJobs, c->dUsable, 0);
-    hipLaunchKernelGGL(compensate_plan_kernel, dim3((P.nBlk + 255) / 256, nframes), dim3(256), 0, st, c->dP, c->dJobs, c->dUsable, (CPlanRec *)c->dPlan);
+    HIP_CHECK(hipMemcpyAsync(c->dJobs.p, hj.data(), sizeof(DGJob) * nframes, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(usable_kernel, dim3(1, nframes), dim3(256), 0, st, c->dP.p, c->dJobs.p, c->dUsable.p);
+    const CPlanRec *plan = (const CPlanRec *)c->dPlan.p;
+    hipLaunchKernelGGL(compensate_plan_kernel, dim3((P.nBlk + 255) / 256, nframes), dim3(256), 0, st, c->dP.p, c->dJobs.p, c->dUsable.p, (CPlanRec *)c->dPlan.p);
     // blocks without overlap: the vectorised row kernel (one launch per plane class); otherwise the per-sample gather
-    auto rowsCW = [&](int p) { // samples per thread: up to 16 bytes, dividing block, covered and frame width
-        if (P.overlap) return 0;
-        const PlaneG &g = P.pl[p];
-        int cw = 16 / P.bps;
-        while (cw > 1 && (g.blkW % cw || g.W % cw || g.WB % cw)) cw >>= 1;
-        return (cw >= 2 && (g.blkW & (g.blkW - 1)) == 0 && (g.blkH & (g.blkH - 1)) == 0) ? cw : 0;
-    };
-    const int cwY = rowsCW(0), cwC = P.nplanes > 1 ? rowsCW(1) : 1;
+    const int cwY = dg_rows_cw(P, 0, true), cwC = P.nplanes > 1 ? dg_rows_cw(P, 1, true) : 1;
     if (cwY && cwC && (P.nplanes == 1 || P.pl[1].W == P.pl[2].W)) {
-        for (int cls = 0; cls < (P.nplanes > 1 ? 2 : 1); cls++) {
-            const int p0 = cls, npl = cls ? 2 : 1, cw = cls ? cwC : cwY;
-            dim3 grid(((P.pl[p0].W / cw) + 63) / 64, (P.pl[p0].H + 3) / 4, nframes * npl);
-#define CR(TT, W_) hipLaunchKernelGGL((compensate_rows_kernel<TT, W_>), grid, dim3(256), 0, st, c->dP, c->dJobs, c->dUsable, (const CPlanRec *)c->dPlan, p0, npl)
-            if (P.bps == 1) { if (cw == 16) CR(uint8_t, 16); else if (cw == 8) CR(uint8_t, 8); else if (cw == 4) CR(uint8_t, 4); else CR(uint8_t, 2); }
-            else { if (cw == 8) CR(uint16_t, 8); else if (cw == 4) CR(uint16_t, 4); else CR(uint16_t, 2); }
-#undef CR
-        }
+        fps_classes(P.pl, P.nplanes, nframes, [&](int p) { return p ? cwC : cwY; }, [&](dim3 grid, int cw, int p0, int npl) {
+            fps_dispatch<2>(P.bps, cw, [&](auto t, auto w) {
+                hipLaunchKernelGGL((compensate_rows_kernel<typename decltype(t)::type, decltype(w)::value>), grid, dim3(256), 0, st, c->dP.p, c->dJobs.p, c->dUsable.p, plan, p0, npl);
+            });
+        });
     } else {
         dim3 grid((P.pl[0].W + 63) / 64, (P.pl[0].H + 3) / 4, nframes * 3);
-        if (P.bps == 1) hipLaunchKernelGGL(compensate_kernel<uint8_t>, grid, dim3(256), 0, st, c->dP, c->dJobs, c->dUsable, (const CPlanRec *)c->dPlan);
-        else hipLaunchKernelGGL(compensate_kernel<uint16_t>, grid, dim3(256), 0, st, c->dP, c->dJobs, c->dUsable, (const CPlanRec *)c->dPlan);
+        if (P.bps == 1) hipLaunchKernelGGL(compensate_kernel<uint8_t>, grid, dim3(256), 0, st, c->dP.p, c->dJobs.p, c->dUsable.p, plan);
+        else hipLaunchKernelGGL(compensate_kernel<uint16_t>, grid, dim3(256), 0, st, c->dP.p, c->dJobs.p, c->dUsable.p, plan);
     }
     HIP_CHECK(hipGetLastError());
     return MVX_OK;
@@ -942,20 +871,10 @@ struct BFPlan { unsigned offB[2], offF[2]; };    // luma / chroma offsets of the
 // per job: usable = both vector fields valid and no scene change (Fakery.c:144-146); 0 -> fallback
 __global__ __launch_bounds__(256) void bf_usable_kernel(const DGParams *Pp, const BFParams *Bp, const BFJob *jobs, int *usable) {
     const DGParams &P = *Pp; const BFParams &B = *Bp;
-    const int f = blockIdx.x;
-    __shared__ int cnt[2];
-    if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const BFJob &J = jobs[f];
-    if (J.good) {
-        for (int d = 0; d < 2; d++) atomicAdd(&cnt[d], fps_count_over(d ? J.blobB : J.blobF, P.nLvCount, P.nBlk, B.thscd1));
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int ok = J.good && J.time256 > 0 && J.time256 < 256;
-        if (ok) ok = ((const int *)J.blobF)[1] == 1 && ((const int *)J.blobB)[1] == 1 && !(cnt[0] > B.thscd2) && !(cnt[1] > B.thscd2);
-        usable[f] = ok;
-    }
+    const BFJob &J = jobs[blockIdx.x];
+    const unsigned char *const blobs[2] = { J.blobF, J.blobB };
+    const bool ok = fps_block_usable(blobs, J.good && J.time256 > 0 && J.time256 < 256, P.nLvCount, P.nBlk, B.thscd1, B.thscd2);
+    if (threadIdx.x == 0) usable[blockIdx.x] = ok;
 }
 
 // small masks, pass 1: scatter-max (occlusion, MaskFun.cpp:91-130) or direct (SAD mask, :139-166) into int planes
@@ -1208,78 +1127,45 @@ __global__ __launch_bounds__(256) void blockfps_rows_kernel(const DGParams *Pp, 
 
 struct mvx_blockfps : DGCommon {
     BFParams B;
-    BFParams *dB = nullptr;
-    BFJob *dBJobs = nullptr;
-    size_t bjobsCap = 0;
-    int *dSmall = nullptr; unsigned char *dMasks = nullptr; size_t maskCap = 0;
-    int *dTables = nullptr;
-    mvx_analysis_data bw, fw;
-    long long fa, fb, outNum, outDen;
-    int inFrames, outFrames;
-    ~mvx_blockfps() {
-        if (dB) (void)hipFree(dB);
-        if (dBJobs) (void)hipFree(dBJobs);
-        if (dSmall) (void)hipFree(dSmall);
-        if (dMasks) (void)hipFree(dMasks);
-        if (dTables) (void)hipFree(dTables);
-    }
+    DevBuf<BFParams> dB;
+    DevBuf<BFJob> dBJobs;         // grows to twice the call's jobs, as do the masks
+    DevBuf<int> dSmall, dTables;
+    DevBuf<unsigned char> dMasks;
+    FpsRate rate;
+    int delta;
 };
-
 
 extern "C" __attribute__((visibility("default"))) int mvx_blockfps_create(const mvx_blockfps_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
         const mvx_super *sup, int num_frames, int64_t fps_num, int64_t fps_den, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3],
         const ptrdiff_t dst_pitch[3], mvx_blockfps **out, char *err) {
-    char dummy[MVX_ERRLEN];
-    if (!err) err = dummy;
-    err[0] = 0;
-    *out = nullptr;
+    MVX_CREATE_BEGIN(out);
     const mvx_super_info &si = sup->info;
-    const long long num = a->num == MVX_UNSET ? 25 : a->num, den = a->den == MVX_UNSET ? 1 : a->den;
     const int mode = a->mode == MVX_UNSET ? 3 : a->mode;
     const int blend = a->blend == MVX_UNSET ? 1 : !!a->blend;
-    long long thscd1 = a->thscd1 == MVX_UNSET ? 400 : a->thscd1;
-    int thscd2 = a->thscd2 == MVX_UNSET ? 130 : a->thscd2;
-    if (mode < 0 || mode > 8) DFAIL("BlockFPS: mode must be between 0 and 8 (inclusive).");
-    if (thscd1 > 8 * 8 * 255) DFAIL("BlockFPS: thscd1 can be at most %d.", 8 * 8 * 255);
-    { int64_t s1 = thscd1; int32_t s2 = thscd2; mvx_scale_thscd(&s1, &s2, bw); thscd1 = s1; thscd2 = s2; }
-    if (bw->nWidth != fw->nWidth) DFAIL("BlockFPS: mvbw and mvfw have different widths.");
-    if (bw->nHeight != fw->nHeight) DFAIL("BlockFPS: mvbw and mvfw have different heights.");
-    if (bw->nBlkSizeX != fw->nBlkSizeX || bw->nBlkSizeY != fw->nBlkSizeY) DFAIL("BlockFPS: mvbw and mvfw have different block sizes.");
-    if (bw->nPel != fw->nPel) DFAIL("BlockFPS: mvbw and mvfw have different pel precision.");
-    if (bw->nOverlapX != fw->nOverlapX || bw->nOverlapY != fw->nOverlapY) DFAIL("BlockFPS: mvbw and mvfw have different overlap.");
-    if (bw->nDeltaFrame <= 0 || fw->nDeltaFrame <= 0) DFAIL("BlockFPS: cannot use motion vectors with absolute frame references.");
-    if (bw->nDeltaFrame != fw->nDeltaFrame) DFAIL("BlockFPS: mvbw and mvfw must be generated with the same delta.");
-    if (!bw->isBackward) DFAIL("BlockFPS: mvbw must be generated with isb=True.");
-    if (fw->isBackward) DFAIL("BlockFPS: mvfw must be generated with isb=False.");
-    if (fps_num == 0 || fps_den == 0) DFAIL("BlockFPS: The input clip must have a frame rate. Invoke AssumeFPS if necessary.");
-    long long numerator, denominator;
-    if (num != 0 && den != 0) { numerator = num; denominator = den; } else { numerator = fps_num * 2; denominator = fps_den; }
-    if (bw->nHeight != si.height || bw->nWidth != si.super_width - si.hpad * 2 || bw->nWidth != si.width || bw->nPel != si.pel)
-        DFAIL("BlockFPS: wrong source or super clip frame size.");
+    int64_t thscd1; int32_t thscd2;
+    if (mode < 0 || mode > 8) MVX_FAIL("BlockFPS: mode must be between 0 and 8 (inclusive).");
+    if (int rc = mvx_resolve_thscd("BlockFPS", a->thscd1, a->thscd2, bw, &thscd1, &thscd2, err)) return rc;
+    // (the first mismatch is reported, and subsampling and bit depth are not compared: unlike flow_similarity in mvx_flow.hip)
+    if (bw->nWidth != fw->nWidth) MVX_FAIL("BlockFPS: mvbw and mvfw have different widths.");
+    if (bw->nHeight != fw->nHeight) MVX_FAIL("BlockFPS: mvbw and mvfw have different heights.");
+    if (bw->nBlkSizeX != fw->nBlkSizeX || bw->nBlkSizeY != fw->nBlkSizeY) MVX_FAIL("BlockFPS: mvbw and mvfw have different block sizes.");
+    if (bw->nPel != fw->nPel) MVX_FAIL("BlockFPS: mvbw and mvfw have different pel precision.");
+    if (bw->nOverlapX != fw->nOverlapX || bw->nOverlapY != fw->nOverlapY) MVX_FAIL("BlockFPS: mvbw and mvfw have different overlap.");
+    if (int rc = mvx_pair_checks("BlockFPS", bw, fw, err)) return rc;
+    if (fps_num == 0 || fps_den == 0) MVX_FAIL("BlockFPS: The input clip must have a frame rate. Invoke AssumeFPS if necessary.");
+    if (!mvx_super_fits(bw, si, true)) MVX_FAIL("BlockFPS: wrong source or super clip frame size.");
     mvx_blockfps *h = new mvx_blockfps();
-    memset(&h->P, 0, sizeof(h->P));
-    memset(&h->B, 0, sizeof(h->B));
     int rc = fill_common(h, bw, si, clip_pitch, super_pitch, dst_pitch, err);
     if (rc) { delete h; return rc; }
     DGParams &P = h->P;
     if (!(si.modeYUV & 6)) P.nplanes = 1;
     P.nRefs = 2; P.thscd1 = thscd1; P.thscd2 = thscd2;
-    h->bw = *bw; h->fw = *fw;
-    h->fa = denominator * fps_num; h->fb = numerator * fps_den;
-    const long long g = bf_gcd(h->fa, h->fb);
-    h->fa /= g; h->fb /= g;
-    if (numerator <= 0 || denominator <= 0) { h->outNum = 0; h->outDen = 1; }
-    else { const long long x = bf_gcd(numerator, denominator); h->outNum = numerator / x; h->outDen = denominator / x; }
-    h->inFrames = num_frames;
-    h->outFrames = (int)(1 + (num_frames - 1) * h->fb / h->fa);
+    fps_rate_init(h->rate, a->num, a->den, fps_num, fps_den, num_frames);
+    h->delta = bw->nDeltaFrame;
     BFParams &B = h->B;
+    memset(&B, 0, sizeof(B));
     B.mode = mode; B.blend = blend; B.ml = a->ml; B.thscd1 = thscd1; B.thscd2 = thscd2;
-    B.XP = bw->nBlkX; B.YP = bw->nBlkY;
-    while (B.XP * (bw->nBlkSizeX - bw->nOverlapX) + bw->nOverlapX < bw->nWidth) B.XP++;
-    while (B.YP * (bw->nBlkSizeY - bw->nOverlapY) + bw->nOverlapY < bw->nHeight) B.YP++;
-    B.nWidthP[0] = B.XP * (bw->nBlkSizeX - bw->nOverlapX) + bw->nOverlapX;
-    B.nHeightP[0] = B.YP * (bw->nBlkSizeY - bw->nOverlapY) + bw->nOverlapY;
-    B.nWidthP[1] = B.nWidthP[0] / bw->xRatioUV; B.nHeightP[1] = B.nHeightP[0] / bw->yRatioUV;
+    fps_padded_grid(bw, &B.XP, &B.YP, B.nWidthP, B.nHeightP);
     const int bps = P.bps;
     B.supInterior[0] = si.hpad * bps + (int)super_pitch[0] * si.vpad;
     for (int p = 1; p < 3; p++) B.supInterior[p] = (si.hpad >> 1) * bps + (int)super_pitch[p < si.num_planes ? p : 0] * (si.vpad >> 1); // the reference's ">> 1" (:459-463)
@@ -1289,16 +1175,10 @@ extern "C" __attribute__((visibility("default"))) int mvx_blockfps_create(const 
 }
 extern "C" __attribute__((visibility("default"))) void mvx_blockfps_destroy(mvx_blockfps *b) { delete b; }
 extern "C" __attribute__((visibility("default"))) void mvx_blockfps_get_info(const mvx_blockfps *b, mvx_blockfps_info *info) {
-    info->num_frames = b->outFrames; info->fps_num = b->outNum; info->fps_den = b->outDen;
+    info->num_frames = b->rate.outFrames; info->fps_num = b->rate.outNum; info->fps_den = b->rate.outDen;
 }
-// MVBlockFPS.c:245-254,278-292
 extern "C" __attribute__((visibility("default"))) void mvx_blockfps_map(const mvx_blockfps *b, int n, int *nleft, int *nright, int *time256) {
-    const int off = b->bw.nDeltaFrame;
-    *nleft = (int)(n * b->fa / b->fb);
-    int t = (int)(((double)n * b->fa / b->fb - *nleft) * 256 + 0.5);
-    if (off > 1) t = t / off;
-    *nright = *nleft + off;
-    *time256 = t;
+    fps_rate_map(b->rate, b->delta, n, nleft, nright, time256);
 }
 
 extern "C" __attribute__((visibility("default"))) int mvx_blockfps_frames(mvx_blockfps *b, int nframes, const mvx_blockfps_job *jobs, void *stream) {
@@ -1309,33 +1189,12 @@ extern "C" __attribute__((visibility("default"))) int mvx_blockfps_frames(mvx_bl
     if (rc) return rc;
     const DGParams &P = b->P;
     BFParams &B = b->B;
-    if (!b->dB) { // upsizer tables + parameter block
-        const int n = B.nWidthP[0] + B.nWidthP[1] + B.nHeightP[0] + B.nHeightP[1];
-        std::vector<int> t(2 * n);
-        int *o = t.data(), *w = t.data() + n, pos = 0;
-        HIP_CHECK(hipMalloc((void **)&b->dTables, sizeof(int) * 2 * n));
-        for (int c = 0; c < 2; c++) {
-            bf_tables(o + pos, w + pos, B.nWidthP[c], B.XP); B.hOff[c] = b->dTables + pos; B.hW[c] = b->dTables + n + pos; pos += B.nWidthP[c];
-            bf_tables(o + pos, w + pos, B.nHeightP[c], B.YP); B.vOff[c] = b->dTables + pos; B.vW[c] = b->dTables + n + pos; pos += B.nHeightP[c];
-        }
-        HIP_CHECK(hipMemcpy(b->dTables, t.data(), sizeof(int) * 2 * n, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMalloc((void **)&b->dB, sizeof(BFParams)));
-        HIP_CHECK(hipMemcpy(b->dB, &B, sizeof(BFParams), hipMemcpyHostToDevice));
-    }
+    if (!b->dB.p && (rc = fps_upload_tables(b->dTables, b->dB, B, B.nWidthP, B.nHeightP))) return rc;
     if ((rc = ensure_jobs(b, nframes, sizeof(BFPlan) * (size_t)P.nBlk))) return rc;
-    if ((size_t)nframes > b->bjobsCap) {
-        if (b->dBJobs) (void)hipFree(b->dBJobs);
-        b->bjobsCap = (size_t)nframes * 2;
-        HIP_CHECK(hipMalloc((void **)&b->dBJobs, b->bjobsCap * sizeof(BFJob)));
-    }
-    const size_t cells = (size_t)B.XP * B.YP;
-    if ((size_t)nframes > b->maskCap) {
-        if (b->dSmall) (void)hipFree(b->dSmall);
-        if (b->dMasks) (void)hipFree(b->dMasks);
-        b->maskCap = (size_t)nframes * 2;
-        HIP_CHECK(hipMalloc((void **)&b->dSmall, b->maskCap * 2 * cells * sizeof(int)));
-        HIP_CHECK(hipMalloc((void **)&b->dMasks, b->maskCap * 3 * cells + 16)); // (+ slack: the row kernels read mask bytes four at a time)
-    }
+    const size_t n = (size_t)nframes, cells = (size_t)B.XP * B.YP;
+    HIP_CHECK(b->dBJobs.reserve(n, n));
+    HIP_CHECK(b->dSmall.reserve(n * 2 * cells, n * 2 * cells));
+    HIP_CHECK(b->dMasks.reserve(n * 3 * cells + 16, n * 3 * cells)); // (+ slack: the row kernels read mask bytes four at a time)
     std::vector<BFJob> hj(nframes);
     for (int f = 0; f < nframes; f++) {
         BFJob &j = hj[f];
@@ -1350,35 +1209,27 @@ extern "C" __attribute__((visibility("default"))) int mvx_blockfps_frames(mvx_bl
         j.good = j.srcSup[0] && j.refSup[0] && j.blobF && j.blobB;
         if (!j.clipL[0] || (j.time256 > 0 && !j.clipR[0])) { mvx_set_error("mvx_blockfps_frames: clip_left / clip_right are required"); return MVX_E_ARG; }
     }
-    HIP_CHECK(hipMemcpyAsync(b->dBJobs, hj.data(), sizeof(BFJob) * nframes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(bf_usable_kernel, dim3(nframes), dim3(256), 0, st, b->dP, b->dB, b->dBJobs, b->dUsable);
+    HIP_CHECK(hipMemcpyAsync(b->dBJobs.p, hj.data(), sizeof(BFJob) * nframes, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(bf_usable_kernel, dim3(nframes), dim3(256), 0, st, b->dP.p, b->dB.p, b->dBJobs.p, b->dUsable.p);
     if (B.mode >= 3) {
-        HIP_CHECK(hipMemsetAsync(b->dSmall, 0, (size_t)nframes * 2 * cells * sizeof(int), st));
-        hipLaunchKernelGGL(bf_mask_kernel, dim3((P.nBlk + 255) / 256, 2, nframes), dim3(256), 0, st, b->dP, b->dB, b->dBJobs, b->dUsable, b->dSmall);
-        hipLaunchKernelGGL(bf_mask_finish_kernel, dim3((unsigned)((cells + 255) / 256), nframes), dim3(256), 0, st, b->dP, b->dB, b->dUsable, b->dSmall, b->dMasks);
+        HIP_CHECK(hipMemsetAsync(b->dSmall.p, 0, n * 2 * cells * sizeof(int), st));
+        hipLaunchKernelGGL(bf_mask_kernel, dim3((P.nBlk + 255) / 256, 2, nframes), dim3(256), 0, st, b->dP.p, b->dB.p, b->dBJobs.p, b->dUsable.p, b->dSmall.p);
+        hipLaunchKernelGGL(bf_mask_finish_kernel, dim3((unsigned)((cells + 255) / 256), nframes), dim3(256), 0, st, b->dP.p, b->dB.p, b->dUsable.p, b->dSmall.p, b->dMasks.p);
     }
-    hipLaunchKernelGGL(bf_plan_kernel, dim3((P.nBlk + 255) / 256, nframes), dim3(256), 0, st, b->dP, b->dBJobs, b->dUsable, (BFPlan *)b->dPlan);
-    auto rowsCW = [&](int p) { // as in mvx_compensate_frames; the uncovered strips start at nBlkX * blkW here
-        if (P.overlap) return 0;
-        const PlaneG &g = P.pl[p];
-        int cw = 16 / P.bps;
-        while (cw > 1 && (g.blkW % cw || g.W % cw)) cw >>= 1;
-        return (cw >= 2 && (g.blkW & (g.blkW - 1)) == 0 && (g.blkH & (g.blkH - 1)) == 0) ? cw : 0;
-    };
-    const int cwY = rowsCW(0), cwC = P.nplanes > 1 ? rowsCW(1) : 1;
+    const BFPlan *plan = (const BFPlan *)b->dPlan.p;
+    hipLaunchKernelGGL(bf_plan_kernel, dim3((P.nBlk + 255) / 256, nframes), dim3(256), 0, st, b->dP.p, b->dBJobs.p, b->dUsable.p, (BFPlan *)b->dPlan.p);
+    const int cwY = dg_rows_cw(P, 0, false), cwC = P.nplanes > 1 ? dg_rows_cw(P, 1, false) : 1;
     if (cwY && cwC && (P.nplanes == 1 || P.pl[1].W == P.pl[2].W)) {
-        for (int cls = 0; cls < (P.nplanes > 1 ? 2 : 1); cls++) {
-            const int p0 = cls, npl = cls ? 2 : 1, cw = cls ? cwC : cwY;
-            dim3 grid(((P.pl[p0].W / cw) + 63) / 64, (P.pl[p0].H + 3) / 4, nframes * npl);
-#define BR(TT, W_) hipLaunchKernelGGL((blockfps_rows_kernel<TT, W_>), grid, dim3(256), 0, st, b->dP, b->dB, b->dBJobs, b->dUsable, (const BFPlan *)b->dPlan, b->dMasks, p0, npl)
-            if (P.bps == 1) { if (cw == 16) BR(uint8_t, 16); else if (cw == 8) BR(uint8_t, 8); else if (cw == 4) BR(uint8_t, 4); else BR(uint8_t, 2); }
-            else { if (cw == 8) BR(uint16_t, 8); else if (cw == 4) BR(uint16_t, 4); else BR(uint16_t, 2); }
-#undef BR
-        }
+        fps_classes(P.pl, P.nplanes, nframes, [&](int p) { return p ? cwC : cwY; }, [&](dim3 grid, int cw, int p0, int npl) {
+            fps_dispatch<2>(P.bps, cw, [&](auto t, auto w) {
+                hipLaunchKernelGGL((blockfps_rows_kernel<typename decltype(t)::type, decltype(w)::value>), grid, dim3(256), 0, st, b->dP.p, b->dB.p, b->dBJobs.p, b->dUsable.p, plan,
+                                   b->dMasks.p, p0, npl);
+            });
+        });
     } else {
         dim3 grid((P.pl[0].W + 63) / 64, (P.pl[0].H + 3) / 4, nframes * 3);
-        if (P.bps == 1) hipLaunchKernelGGL(blockfps_kernel<uint8_t>, grid, dim3(256), 0, st, b->dP, b->dB, b->dBJobs, b->dUsable, (const BFPlan *)b->dPlan, b->dMasks);
-        else hipLaunchKernelGGL(blockfps_kernel<uint16_t>, grid, dim3(256), 0, st, b->dP, b->dB, b->dBJobs, b->dUsable, (const BFPlan *)b->dPlan, b->dMasks);
+        if (P.bps == 1) hipLaunchKernelGGL(blockfps_kernel<uint8_t>, grid, dim3(256), 0, st, b->dP.p, b->dB.p, b->dBJobs.p, b->dUsable.p, plan, b->dMasks.p);
+        else hipLaunchKernelGGL(blockfps_kernel<uint16_t>, grid, dim3(256), 0, st, b->dP.p, b->dB.p, b->dBJobs.p, b->dUsable.p, plan, b->dMasks.p);
     }
     HIP_CHECK(hipGetLastError());
     return MVX_OK;
@@ -1387,39 +1238,27 @@ extern "C" __attribute__((visibility("default"))) int mvx_blockfps_frames(mvx_bl
 // ================================================================================================ mv.SCDetection
 // MVSCDetection.c:43-73: _SceneChangePrev / _SceneChangeNext = !fgopIsUsable(vectors at n) (Fakery.c:52-58,144-146)
 __global__ __launch_bounds__(256) void scdetect_kernel(const unsigned char *const *blobs, int nLvCount, int nBlk, long long thscd1, int thscd2, int *out) {
-    const unsigned char *blob = blobs[blockIdx.x];
-    __shared__ int cnt;
-    if (threadIdx.x == 0) cnt = 0;
-    __syncthreads();
-    const GVecD *v = mvx_level0(blob, nLvCount);
-    int c = 0;
-    for (int i = threadIdx.x; i < nBlk; i += 256) c += v[i].sad > thscd1 ? 1 : 0;
-    atomicAdd(&cnt, c);
-    __syncthreads();
-    if (threadIdx.x == 0) out[blockIdx.x] = !(((const int *)blob)[1] == 1 && !(cnt > thscd2));
+    const bool ok = fps_block_usable(blobs[blockIdx.x], true, nLvCount, nBlk, thscd1, thscd2);
+    if (threadIdx.x == 0) out[blockIdx.x] = !ok;
 }
 
 extern "C" __attribute__((visibility("default"))) int mvx_scdetect(const mvx_analysis_data *ad, int64_t thscd1, int32_t thscd2, int n, const void *const *blobs,
                                                                    int32_t *scene_change, void *stream, char *err) {
-    char dummy[MVX_ERRLEN];
-    if (!err) err = dummy;
-    err[0] = 0;
+    MVX_ERR_BEGIN();
     if (n <= 0) return MVX_OK;
     hipStream_t st = (hipStream_t)stream;
-    int64_t s1 = thscd1 == MVX_UNSET ? 400 : thscd1;
-    int32_t s2 = thscd2 == MVX_UNSET ? 130 : thscd2;
-    if (s1 > 8 * 8 * 255) DFAIL("SCDetection: thscd1 can be at most %d.", 8 * 8 * 255); // MVAnalysisData.c:11-14
-    mvx_scale_thscd(&s1, &s2, ad);
-    const unsigned char **dB = nullptr; int *dOut = nullptr;
-    HIP_CHECK(hipMalloc((void **)&dB, sizeof(void *) * n));
-    if (hipMalloc((void **)&dOut, sizeof(int) * n) != hipSuccess) { (void)hipFree(dB); mvx_set_error("mvx_scdetect: out of device memory"); return MVX_E_NOMEM; }
-    hipError_t e = hipMemcpyAsync(dB, blobs, sizeof(void *) * n, hipMemcpyHostToDevice, st);
+    int64_t s1; int32_t s2;
+    if (int rc = mvx_resolve_thscd("SCDetection", thscd1, thscd2, ad, &s1, &s2, err)) return rc;
+    DevBuf<const unsigned char *> dB; // (freed on return, after the stream has been waited for)
+    DevBuf<int> dOut;
+    HIP_CHECK(dB.reserve(n));
+    if (dOut.reserve(n) != hipSuccess) { mvx_set_error("mvx_scdetect: out of device memory"); return MVX_E_NOMEM; }
+    hipError_t e = hipMemcpyAsync(dB.p, blobs, sizeof(void *) * n, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(scdetect_kernel, dim3(n), dim3(256), 0, st, dB, ad->nLvCount, ad->nBlkX * ad->nBlkY, (long long)s1, (int)s2, dOut);
-        e = hipMemcpyAsync(scene_change, dOut, sizeof(int) * n, hipMemcpyDeviceToHost, st);
+        hipLaunchKernelGGL(scdetect_kernel, dim3(n), dim3(256), 0, st, dB.p, ad->nLvCount, ad->nBlkX * ad->nBlkY, (long long)s1, (int)s2, dOut.p);
+        e = hipMemcpyAsync(scene_change, dOut.p, sizeof(int) * n, hipMemcpyDeviceToHost, st);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(dB); (void)hipFree(dOut);
     if (e != hipSuccess) { mvx_set_error("mvx_scdetect: %s", hipGetErrorString(e)); return MVX_E_DEVICE; }
     return MVX_OK;
 }

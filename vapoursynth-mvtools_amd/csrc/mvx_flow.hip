@@ -60,12 +60,8 @@ __global__ __launch_bounds__(256) void flow_usable_kernel(const FLParams *Pp, co
     const FLJob &J = jobs[f];
     const unsigned char *blob = k == 0 ? J.blobF : k == 1 ? J.blobB : k == 2 ? J.blobFF : J.blobBB;
     const bool want = !J.copy && J.supL[0] && J.supR[0] && blob && (k < 2 || !P.isFPS || P.maskmode == 2);
-    __shared__ int cnt;
-    if (threadIdx.x == 0) cnt = 0;
-    __syncthreads();
-    if (want) atomicAdd(&cnt, fps_count_over(blob, P.nLvCount, P.nBlk, P.thscd1));
-    __syncthreads();
-    if (threadIdx.x == 0) flags[f * 4 + k] = want && ((const int *)blob)[1] == 1 && !(cnt > P.thscd2);
+    const bool ok = fps_block_usable(blob, want, P.nLvCount, P.nBlk, P.thscd1, P.thscd2);
+    if (threadIdx.x == 0) flags[f * 4 + k] = ok;
 }
 // the job's formula (MVFlowInter.c:109-138,245-276 / MVFlowFPS.c:153-166,314-354,385-435): the masks and B / F come from the main vectors, the
 // extra blobs only pick the formula; FlowFPS mask 2 without usable extra vectors falls through to Simple (MVFlowFPS.c:435)
@@ -223,28 +219,15 @@ __global__ __launch_bounds__(256) void flow_kernel(const FLParams *Pp, const FLJ
 struct mvx_flow {
     CallGuard guard;
     FLParams P;
-    FLParams *dP = nullptr;
-    FLJob *dJobs = nullptr;
-    size_t jobsCap = 0;
-    int *dFlags = nullptr, *dSmall = nullptr;
-    FLCell *dCells = nullptr;
-    unsigned char *dMasks = nullptr;
-    int *dTables = nullptr;
+    DevBuf<FLParams> dP;
+    DevBuf<FLJob> dJobs;              // the per-job buffers hold exactly the largest call's jobs
+    DevBuf<int> dFlags, dSmall, dTables;
+    DevBuf<FLCell> dCells;
+    DevBuf<unsigned char> dMasks;
     int nWidthP[2], nHeightP[2];
-    int delta, inFrames, outFrames, time256;
-    long long fa, fb, outNum, outDen;
-    ~mvx_flow() {
-        if (dP) (void)hipFree(dP);
-        if (dJobs) (void)hipFree(dJobs);
-        if (dFlags) (void)hipFree(dFlags);
-        if (dSmall) (void)hipFree(dSmall);
-        if (dCells) (void)hipFree(dCells);
-        if (dMasks) (void)hipFree(dMasks);
-        if (dTables) (void)hipFree(dTables);
-    }
+    int delta, time256;
+    FpsRate rate;                     // FlowFPS; FlowInter: the clip's frame count and no rate
 };
-
-#define FFAIL(...) do { snprintf(err, MVX_ERRLEN, __VA_ARGS__); mvx_set_error("%s", err); return MVX_E_ARG; } while (0)
 
 // MVAnalysisData.c:68-98 adataCheckSimilarity: every mismatching field overwrites the message, so the LAST one is reported
 static bool flow_similarity(const mvx_analysis_data *a, const mvx_analysis_data *b, const char *name, char *err) {
@@ -261,24 +244,13 @@ static bool flow_similarity(const mvx_analysis_data *a, const mvx_analysis_data 
     return bad;
 }
 
-// MVAnalysisData.c:7-31 scaleThSCD with its limit check
-static int flow_thscd(const char *name, int64_t *thscd1, int32_t *thscd2, const mvx_analysis_data *ad, char *err) {
-    if (*thscd1 > 8 * 8 * 255) FFAIL("%s: thscd1 can be at most %d.", name, 8 * 8 * 255);
-    mvx_scale_thscd(thscd1, thscd2, ad);
-    return MVX_OK;
-}
-
 // the two-clip checks FlowInter, FlowFPS and FlowBlur share after their own argument checks (MVFlowInter.c:540-574, MVFlowFPS.c:646-671,
 // MVFlowBlur.c:410-470)
-static int flow_pair_checks(const char *name, int64_t *thscd1, int32_t *thscd2, const mvx_analysis_data *bw, const mvx_analysis_data *fw, char *err) {
-    if (int rc = flow_thscd(name, thscd1, thscd2, bw, err)) return rc;
+static int flow_pair_checks(const char *name, int64_t arg1, int32_t arg2, int64_t *thscd1, int32_t *thscd2, const mvx_analysis_data *bw,
+                            const mvx_analysis_data *fw, char *err) {
+    if (int rc = mvx_resolve_thscd(name, arg1, arg2, bw, thscd1, thscd2, err)) return rc;
     if (flow_similarity(bw, fw, name, err)) { mvx_set_error("%s", err); return MVX_E_ARG; }
-    // FlowInter's check; FlowFPS lacks it in the reference and then reads negative frame numbers: rejected here on purpose
-    if (bw->nDeltaFrame <= 0 || fw->nDeltaFrame <= 0) FFAIL("%s: cannot use motion vectors with absolute frame references.", name);
-    if (bw->nDeltaFrame != fw->nDeltaFrame) FFAIL("%s: mvbw and mvfw must be generated with the same delta.", name);
-    if (!bw->isBackward) FFAIL("%s: mvbw must be generated with isb=True.", name);
-    if (fw->isBackward) FFAIL("%s: mvfw must be generated with isb=False.", name);
-    return MVX_OK;
+    return mvx_pair_checks(name, bw, fw, err);
 }
 
 // the geometry of every flow filter: padded small fields and upsizer tables to nWidthP / nHeightP (MVFlowInter.c:651-678,
@@ -295,12 +267,8 @@ static int flow_geometry(FLParams &P, int nWidthP[2], int nHeightP[2], const cha
     P.nBlkX = bw->nBlkX; P.nBlkY = bw->nBlkY; P.nBlk = bw->nBlkX * bw->nBlkY; P.nLvCount = bw->nLvCount;
     P.stepX = bw->nBlkSizeX - bw->nOverlapX; P.stepY = bw->nBlkSizeY - bw->nOverlapY;
     P.XP = bw->nBlkX; P.YP = bw->nBlkY;
-    if (padded) {
-        while (P.XP * P.stepX + bw->nOverlapX < bw->nWidth) P.XP++;
-        while (P.YP * P.stepY + bw->nOverlapY < bw->nHeight) P.YP++;
-        nWidthP[0] = P.XP * P.stepX + bw->nOverlapX; nHeightP[0] = P.YP * P.stepY + bw->nOverlapY;
-        nWidthP[1] = nWidthP[0] / bw->xRatioUV; nHeightP[1] = nHeightP[0] / bw->yRatioUV;
-    } else {
+    if (padded) fps_padded_grid(bw, &P.XP, &P.YP, nWidthP, nHeightP);
+    else {
         nWidthP[0] = bw->nWidth; nHeightP[0] = bw->nHeight;
         nWidthP[1] = bw->nWidth / bw->xRatioUV; nHeightP[1] = bw->nHeight / bw->yRatioUV;
     }
@@ -308,64 +276,43 @@ static int flow_geometry(FLParams &P, int nWidthP[2], int nHeightP[2], const cha
     P.limW[1] = bw->nWidth / bw->xRatioUV; P.limH[1] = bw->nHeight / bw->yRatioUV;
     P.halfX = bw->xRatioUV == 2; P.halfY = bw->yRatioUV == 2;
     // the upsizer interpolates between small-field cells o and o + 1: with a single (padded) column or row the reference reads outside its buffers
-    if (P.XP < 2 || P.YP < 2) FFAIL("%s: the frame must be at least two blocks wide and two blocks high.", name);
-    if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) FFAIL("%s: U and V super planes must share one pitch.", name);
-    const int xSub = mvx_ilog2(si.xRatioUV), ySub = mvx_ilog2(si.yRatioUV);
-    for (int p = 0; p < 3; p++) {
-        PlaneG &g = P.pl[p];
-        const int sx = p ? xSub : 0, sy = p ? ySub : 0, q = p < si.num_planes ? p : 0;
-        g.subX = sx; g.subY = sy;
-        g.W = bw->nWidth >> sx; g.H = bw->nHeight >> sy;
-        g.hpadPel = (si.hpad >> sx) * si.pel; g.vpadPel = (si.vpad >> sy) * si.pel; // the Finest frame's nOffsetY / nOffsetUV (MVFlowInter.c:218-219)
-        g.supPitch = super_pitch[q]; g.dstPitch = dst_pitch[q];
-        g.supPlaneStride = g.supPitch * (long long)((si.height >> sy) + 2 * (si.vpad >> sy));
-        P.clipPitch[p] = clip_pitch[q];
-    }
+    if (P.XP < 2 || P.YP < 2) MVX_FAIL("%s: the frame must be at least two blocks wide and two blocks high.", name);
+    if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) MVX_FAIL("%s: U and V super planes must share one pitch.", name);
+    fps_fill_planes(P.pl, bw, si, nullptr, super_pitch, dst_pitch);
+    for (int p = 0; p < 3; p++) P.clipPitch[p] = clip_pitch[p < si.num_planes ? p : 0];
     return MVX_OK;
 }
 
 // FlowInter / FlowFPS: the two-clip checks, then the padded geometry
-static int flow_common(mvx_flow *h, const char *name, int64_t thscd1, int32_t thscd2, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
+static int flow_common(mvx_flow *h, const char *name, int64_t arg1, int32_t arg2, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
                        const mvx_super_info &si, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], char *err) {
-    if (int rc = flow_pair_checks(name, &thscd1, &thscd2, bw, fw, err)) return rc;
+    int64_t thscd1; int32_t thscd2;
+    if (int rc = flow_pair_checks(name, arg1, arg2, &thscd1, &thscd2, bw, fw, err)) return rc;
     if (int rc = flow_geometry(h->P, h->nWidthP, h->nHeightP, name, thscd1, thscd2, bw, si, super_pitch, clip_pitch, dst_pitch, true, err)) return rc;
     h->delta = bw->nDeltaFrame;
     return MVX_OK;
 }
 
-// upsizer tables (SimpleResize.cpp:27-57) from the XP x YP small fields to nWidthP / nHeightP (luma, chroma) and the parameter block, on the device
-static int flow_upload(FLParams &P, const int nWidthP[2], const int nHeightP[2], int **dTables, FLParams **dP) {
-    const int n = nWidthP[0] + nWidthP[1] + nHeightP[0] + nHeightP[1];
-    std::vector<int> t(2 * n);
-    int *o = t.data(), *w = t.data() + n, pos = 0;
-    HIP_CHECK(hipMalloc((void **)dTables, sizeof(int) * 2 * n));
-    for (int c = 0; c < 2; c++) {
-        bf_tables(o + pos, w + pos, nWidthP[c], P.XP); P.hOff[c] = *dTables + pos; P.hW[c] = *dTables + n + pos; pos += nWidthP[c];
-        bf_tables(o + pos, w + pos, nHeightP[c], P.YP); P.vOff[c] = *dTables + pos; P.vW[c] = *dTables + n + pos; pos += nHeightP[c];
-    }
-    HIP_CHECK(hipMemcpy(*dTables, t.data(), sizeof(int) * 2 * n, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMalloc((void **)dP, sizeof(FLParams)));
-    HIP_CHECK(hipMemcpy(*dP, &P, sizeof(FLParams), hipMemcpyHostToDevice));
-    return MVX_OK;
+// the luma / chroma launches of a kernel that produces CW consecutive samples per thread, the widest segment that divides the plane width (the
+// tables cover nWidthP >= the width): go(grid, first plane, planes per job, fps_type<T>, integral constant CW)
+template <typename F> static void flow_launches(const FLParams &P, int nframes, F &&go) {
+    fps_classes(P.pl, P.nplanes, nframes, [&](int p) { return fps_segment(P.bps, P.pl[p].W); }, [&](dim3 grid, int cw, int p0, int npl) {
+        fps_dispatch<1>(P.bps, cw, [&](auto t, auto w) { go(grid, p0, npl, t, w); });
+    });
 }
 
 // MVFlowInter.c:473-678 mvflowinterCreate.  time and ml are float arguments there: time256 is formed in float, ml reaches the mask as (double)(float)ml.
 extern "C" __attribute__((visibility("default"))) int mvx_flowinter_create(const mvx_flowinter_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
         const mvx_super *sup, int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flow **out, char *err) {
-    char dummy[MVX_ERRLEN];
-    if (!err) err = dummy;
-    err[0] = 0;
-    *out = nullptr;
+    MVX_CREATE_BEGIN(out);
     const mvx_super_info &si = sup->info;
     const float time = (float)a->time, ml = (float)a->ml;
     const int blend = a->blend == MVX_UNSET ? 1 : !!a->blend;
-    const int64_t thscd1 = a->thscd1 == MVX_UNSET ? 400 : a->thscd1;
-    const int32_t thscd2 = a->thscd2 == MVX_UNSET ? 130 : a->thscd2;
-    if (time < 0.0f || time > 100.0f) FFAIL("FlowInter: time must be between 0 and 100 %% (inclusive).");
-    if (ml <= 0.0f) FFAIL("FlowInter: ml must be greater than 0.");
+    if (time < 0.0f || time > 100.0f) MVX_FAIL("FlowInter: time must be between 0 and 100 %% (inclusive).");
+    if (ml <= 0.0f) MVX_FAIL("FlowInter: ml must be greater than 0.");
     mvx_flow *h = new mvx_flow();
-    int rc = flow_common(h, "FlowInter", thscd1, thscd2, bw, fw, si, super_pitch, clip_pitch, dst_pitch, err);
-    if (!rc && (bw->nHeight != si.height || bw->nWidth != si.super_width - si.hpad * 2 || bw->nPel != si.pel)) {
+    int rc = flow_common(h, "FlowInter", a->thscd1, a->thscd2, bw, fw, si, super_pitch, clip_pitch, dst_pitch, err);
+    if (!rc && !mvx_super_fits(bw, si, false)) {
         snprintf(err, MVX_ERRLEN, "FlowInter: wrong source or super clip frame size.");
         mvx_set_error("%s", err);
         rc = MVX_E_ARG;
@@ -374,8 +321,8 @@ extern "C" __attribute__((visibility("default"))) int mvx_flowinter_create(const
     FLParams &P = h->P;
     P.isFPS = 0; P.blend = blend; P.ml = (double)ml;
     h->time256 = (int)(time * 256.0f / 100.0f);
-    h->inFrames = h->outFrames = num_frames;
-    h->outNum = 0; h->outDen = 0;
+    h->rate = FpsRate();
+    h->rate.outFrames = num_frames;
     *out = h;
     return MVX_OK;
 }
@@ -384,38 +331,24 @@ extern "C" __attribute__((visibility("default"))) int mvx_flowinter_create(const
 extern "C" __attribute__((visibility("default"))) int mvx_flowfps_create(const mvx_flowfps_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
         const mvx_super *sup, int num_frames, int64_t fps_num, int64_t fps_den, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3],
         const ptrdiff_t dst_pitch[3], mvx_flow **out, char *err) {
-    char dummy[MVX_ERRLEN];
-    if (!err) err = dummy;
-    err[0] = 0;
-    *out = nullptr;
+    MVX_CREATE_BEGIN(out);
     const mvx_super_info &si = sup->info;
-    const long long num = a->num == MVX_UNSET ? 25 : a->num, den = a->den == MVX_UNSET ? 1 : a->den;
     const int mask = a->mask == MVX_UNSET ? 2 : a->mask;
     const int blend = a->blend == MVX_UNSET ? 1 : !!a->blend;
-    const int64_t thscd1 = a->thscd1 == MVX_UNSET ? 400 : a->thscd1;
-    const int32_t thscd2 = a->thscd2 == MVX_UNSET ? 130 : a->thscd2;
-    if (mask < 0 || mask > 2) FFAIL("FlowFPS: mask must be 0, 1, or 2.");
-    if (a->ml <= 0.0) FFAIL("FlowFPS: ml must be greater than 0.");
+    if (mask < 0 || mask > 2) MVX_FAIL("FlowFPS: mask must be 0, 1, or 2.");
+    if (a->ml <= 0.0) MVX_FAIL("FlowFPS: ml must be greater than 0.");
     mvx_flow *h = new mvx_flow();
-    int rc = flow_common(h, "FlowFPS", thscd1, thscd2, bw, fw, si, super_pitch, clip_pitch, dst_pitch, err);
+    int rc = flow_common(h, "FlowFPS", a->thscd1, a->thscd2, bw, fw, si, super_pitch, clip_pitch, dst_pitch, err);
     auto fail = [&](const char *m) { snprintf(err, MVX_ERRLEN, "%s", m); mvx_set_error("%s", err); rc = MVX_E_ARG; };
     if (!rc && (fps_num == 0 || fps_den == 0)) fail("FlowFPS: The input clip must have a frame rate. Invoke AssumeFPS if necessary.");
     if (!rc && (bw->nWidth != si.width || bw->nHeight != si.height)) fail("FlowFPS: inconsistent source and vector frame size.");
-    if (!rc && (bw->nHeight != si.height || bw->nWidth != si.super_width - si.hpad * 2 || bw->nPel != si.pel)) fail("FlowFPS: wrong source or super clip frame size.");
+    if (!rc && !mvx_super_fits(bw, si, false)) fail("FlowFPS: wrong source or super clip frame size.");
     if (!rc && !(bw->nWidth + bw->nHPadding * 2 == si.super_width && bw->nHeight + bw->nVPadding * 2 <= si.super_height))
         fail("FlowFPS: inconsistent clips frame size! Incomprehensible error messages are the best, right?");
     if (rc) { delete h; return rc; }
     FLParams &P = h->P;
     P.isFPS = 1; P.maskmode = mask; P.blend = blend; P.ml = a->ml;
-    long long numerator, denominator;
-    if (num != 0 && den != 0) { numerator = num; denominator = den; } else { numerator = fps_num * 2; denominator = fps_den; }
-    h->fa = denominator * fps_num; h->fb = numerator * fps_den;
-    const long long g = bf_gcd(h->fa, h->fb);
-    h->fa /= g; h->fb /= g;
-    if (numerator <= 0 || denominator <= 0) { h->outNum = 0; h->outDen = 1; } // setFPS, MVFlowFPS.c:547-561
-    else { const long long x = bf_gcd(numerator, denominator); h->outNum = numerator / x; h->outDen = denominator / x; }
-    h->inFrames = num_frames;
-    h->outFrames = (int)(1 + (num_frames - 1) * h->fb / h->fa);
+    fps_rate_init(h->rate, a->num, a->den, fps_num, fps_den, num_frames);
     h->time256 = 0;
     *out = h;
     return MVX_OK;
@@ -423,16 +356,12 @@ extern "C" __attribute__((visibility("default"))) int mvx_flowfps_create(const m
 
 extern "C" __attribute__((visibility("default"))) void mvx_flow_destroy(mvx_flow *h) { delete h; }
 extern "C" __attribute__((visibility("default"))) void mvx_flow_get_info(const mvx_flow *h, mvx_flow_info *info) {
-    info->num_frames = h->outFrames; info->fps_num = h->outNum; info->fps_den = h->outDen;
+    info->num_frames = h->rate.outFrames; info->fps_num = h->rate.outNum; info->fps_den = h->rate.outDen;
 }
 // FlowInter: n -> (n, n + delta, time256) (MVFlowInter.c:86-100); FlowFPS: MVFlowFPS.c:92-99,125-134 (BlockFPS's arithmetic)
 extern "C" __attribute__((visibility("default"))) void mvx_flow_map(const mvx_flow *h, int n, int *nleft, int *nright, int *time256) {
     if (!h->P.isFPS) { *nleft = n; *nright = n + h->delta; *time256 = h->time256; return; }
-    *nleft = (int)(n * h->fa / h->fb);
-    int t = (int)(((double)n * h->fa / h->fb - *nleft) * 256 + 0.5);
-    if (h->delta > 1) t = t / h->delta;
-    *nright = *nleft + h->delta;
-    *time256 = t;
+    fps_rate_map(h->rate, h->delta, n, nleft, nright, time256);
 }
 
 extern "C" __attribute__((visibility("default"))) int mvx_flow_frames(mvx_flow *h, int nframes, const mvx_flow_job *jobs, void *stream) {
@@ -440,25 +369,14 @@ extern "C" __attribute__((visibility("default"))) int mvx_flow_frames(mvx_flow *
     hipStream_t st = (hipStream_t)stream;
     CallGuard::Scope scope(h->guard, st);
     FLParams &P = h->P;
-    if (!h->dP) // MVFlowInter.c:677-679
-        if (int rc = flow_upload(P, h->nWidthP, h->nHeightP, &h->dTables, &h->dP)) return rc;
-    const size_t cellsN = (size_t)P.XP * P.YP;
-    if ((size_t)nframes > h->jobsCap) { // exactly this call's size; the capacity is raised only once every buffer exists
-        if (h->dJobs) (void)hipFree(h->dJobs);
-        if (h->dFlags) (void)hipFree(h->dFlags);
-        if (h->dSmall) (void)hipFree(h->dSmall);
-        if (h->dCells) (void)hipFree(h->dCells);
-        if (h->dMasks) (void)hipFree(h->dMasks);
-        h->dJobs = nullptr; h->dFlags = nullptr; h->dSmall = nullptr; h->dCells = nullptr; h->dMasks = nullptr;
-        h->jobsCap = 0;
-        const size_t n = (size_t)nframes;
-        HIP_CHECK(hipMalloc((void **)&h->dJobs, n * sizeof(FLJob)));
-        HIP_CHECK(hipMalloc((void **)&h->dFlags, n * 4 * sizeof(int)));
-        HIP_CHECK(hipMalloc((void **)&h->dSmall, n * 2 * cellsN * sizeof(int)));
-        HIP_CHECK(hipMalloc((void **)&h->dCells, n * cellsN * sizeof(FLCell)));
-        HIP_CHECK(hipMalloc((void **)&h->dMasks, n * 2 * cellsN));
-        h->jobsCap = n;
-    }
+    if (!h->dP.p) // MVFlowInter.c:677-679
+        if (int rc = fps_upload_tables(h->dTables, h->dP, P, h->nWidthP, h->nHeightP)) return rc;
+    const size_t n = (size_t)nframes, cellsN = (size_t)P.XP * P.YP;
+    HIP_CHECK(h->dJobs.reserve(n));
+    HIP_CHECK(h->dFlags.reserve(n * 4));
+    HIP_CHECK(h->dSmall.reserve(n * 2 * cellsN));
+    HIP_CHECK(h->dCells.reserve(n * cellsN));
+    HIP_CHECK(h->dMasks.reserve(n * 2 * cellsN));
     std::vector<FLJob> hj(nframes);
     for (int f = 0; f < nframes; f++) {
         FLJob &j = hj[f];
@@ -479,23 +397,14 @@ extern "C" __attribute__((visibility("default"))) int mvx_flow_frames(mvx_flow *
             mvx_set_error("mvx_flow_frames: dst / clip_left / clip_right are required"); return MVX_E_ARG;
         }
     }
-    HIP_CHECK(hipMemcpyAsync(h->dJobs, hj.data(), sizeof(FLJob) * nframes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(flow_usable_kernel, dim3(nframes, 4), dim3(256), 0, st, h->dP, h->dJobs, h->dFlags);
-    HIP_CHECK(hipMemsetAsync(h->dSmall, 0, (size_t)nframes * 2 * cellsN * sizeof(int), st));
-    hipLaunchKernelGGL(flow_occ_kernel, dim3((P.nBlk + 255) / 256, 2, nframes), dim3(256), 0, st, h->dP, h->dJobs, h->dFlags, h->dSmall);
-    hipLaunchKernelGGL(flow_cells_kernel, dim3((unsigned)((cellsN + 255) / 256), nframes), dim3(256), 0, st, h->dP, h->dJobs, h->dFlags, h->dSmall, h->dCells, h->dMasks);
-    // CW consecutive samples per thread: the widest of 16 bytes that divides the plane width (the tables cover nWidthP >= the width)
-    for (int cls = 0; cls < (P.nplanes > 1 ? 2 : 1); cls++) {
-        const int p0 = cls, npl = cls ? 2 : 1;
-        const PlaneG &g = P.pl[p0];
-        int cw = 16 / P.bps;
-        while (cw > 1 && g.W % cw) cw >>= 1;
-        dim3 grid((unsigned)((g.W / cw + 63) / 64), (unsigned)((g.H + 3) / 4), (unsigned)(nframes * npl));
-#define FK(TT, W_) hipLaunchKernelGGL((flow_kernel<TT, W_>), grid, dim3(256), 0, st, h->dP, h->dJobs, h->dFlags, h->dCells, h->dMasks, p0, npl)
-        if (P.bps == 1) { if (cw == 16) FK(uint8_t, 16); else if (cw == 8) FK(uint8_t, 8); else if (cw == 4) FK(uint8_t, 4); else if (cw == 2) FK(uint8_t, 2); else FK(uint8_t, 1); }
-        else { if (cw == 8) FK(uint16_t, 8); else if (cw == 4) FK(uint16_t, 4); else if (cw == 2) FK(uint16_t, 2); else FK(uint16_t, 1); }
-#undef FK
-    }
+    HIP_CHECK(hipMemcpyAsync(h->dJobs.p, hj.data(), sizeof(FLJob) * nframes, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(flow_usable_kernel, dim3(nframes, 4), dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p);
+    HIP_CHECK(hipMemsetAsync(h->dSmall.p, 0, n * 2 * cellsN * sizeof(int), st));
+    hipLaunchKernelGGL(flow_occ_kernel, dim3((P.nBlk + 255) / 256, 2, nframes), dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p, h->dSmall.p);
+    hipLaunchKernelGGL(flow_cells_kernel, dim3((unsigned)((cellsN + 255) / 256), nframes), dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p, h->dSmall.p, h->dCells.p, h->dMasks.p);
+    flow_launches(P, nframes, [&](dim3 grid, int p0, int npl, auto t, auto w) {
+        hipLaunchKernelGGL((flow_kernel<typename decltype(t)::type, decltype(w)::value>), grid, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p, h->dCells.p, h->dMasks.p, p0, npl);
+    });
     HIP_CHECK(hipGetLastError());
     return MVX_OK;
 }
@@ -503,7 +412,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_flow_frames(mvx_flow *
 // ================================================================================================ mv.Flow and mv.FlowBlur
 //
 // Both stand on the machinery above: usability per blob, int16 small-field cells, the int16 upsizer evaluated at each sample (fl_vup with
-// the upsizer tables of flow_upload) and reads from the super frame as if it were the Finest frame (fl_fetch).  Flow builds the padded
+// the upsizer tables of fps_upload_tables) and reads from the super frame as if it were the Finest frame (fl_fetch).  Flow builds the padded
 // fields of FlowInter (MVFlow.cpp:535-562) with field_shift added to every VY cell before the chroma halving (:264-302); FlowBlur builds
 // unpadded fields and tables that end at the frame (MVFlowBlur.c:525-536).  A job whose vectors are unusable copies its clip frame.
 //   fm_usable_kernel   : per (job, blob) -> usable flags
@@ -529,13 +438,8 @@ __global__ __launch_bounds__(256) void fm_usable_kernel(const FLParams *Pp, cons
     const int f = blockIdx.x, k = blockIdx.y;
     const FMJob &J = jobs[f];
     const unsigned char *blob = k < nb ? J.blob[k] : nullptr;
-    const bool want = J.sup[0] && blob;
-    __shared__ int cnt;
-    if (threadIdx.x == 0) cnt = 0;
-    __syncthreads();
-    if (want) atomicAdd(&cnt, fps_count_over(blob, P.nLvCount, P.nBlk, P.thscd1));
-    __syncthreads();
-    if (threadIdx.x == 0) flags[f * 2 + k] = k >= nb ? 1 : want && ((const int *)blob)[1] == 1 && !(cnt > P.thscd2);
+    const bool ok = fps_block_usable(blob, J.sup[0] && blob, P.nLvCount, P.nBlk, P.thscd1, P.thscd2);
+    if (threadIdx.x == 0) flags[f * 2 + k] = k >= nb || ok;
 }
 __device__ __forceinline__ bool fm_ok(const int *flags, int f) { return flags[2 * f] && flags[2 * f + 1]; }
 
@@ -729,70 +633,38 @@ __global__ __launch_bounds__(256) void flowblur_kernel(const FLParams *Pp, const
 struct FMEngine {
     CallGuard guard;
     FLParams P;
-    FLParams *dP = nullptr;
-    FMJob *dJobs = nullptr;
-    size_t jobsCap = 0;
-    int *dFlags = nullptr, *dCells = nullptr, *dTables = nullptr;
-    unsigned long long *dWin = nullptr;
+    DevBuf<FLParams> dP;
+    DevBuf<FMJob> dJobs;                         // the per-job buffers hold exactly the largest call's jobs
+    DevBuf<int> dFlags, dCells, dTables;
+    DevBuf<unsigned long long> dWin;
     int nWidthP[2], nHeightP[2];
     int nb = 1;                                  // vector fields per job: Flow 1, FlowBlur 2 (B, F)
     int numFrames = 0, delta = 0, isb = 0, mode = 0, fields = 0, time256 = 0, blur256 = 0, prec = 1;
     long long winJob = 0, winOff[3] = {0, 0, 0}; // Flow shift: winner samples per job, per plane offsets
-    ~FMEngine() {
-        if (dP) (void)hipFree(dP);
-        if (dJobs) (void)hipFree(dJobs);
-        if (dFlags) (void)hipFree(dFlags);
-        if (dCells) (void)hipFree(dCells);
-        if (dTables) (void)hipFree(dTables);
-        if (dWin) (void)hipFree(dWin);
-    }
 };
 struct mvx_flowcomp : FMEngine {};
 struct mvx_flowblur : FMEngine {};
 
-// the luma / chroma launches of one per-sample kernel: CW consecutive samples per thread, the widest of at most 16 bytes that divides the
-// plane width (cw1: one sample per thread)
-template <typename F> static void fm_classes(const FLParams &P, int nframes, bool cw1, F &&launch) {
-    for (int cls = 0; cls < (P.nplanes > 1 ? 2 : 1); cls++) {
-        const int p0 = cls, npl = cls ? 2 : 1;
-        const PlaneG &g = P.pl[p0];
-        int cw = cw1 ? 1 : 16 / P.bps;
-        while (cw > 1 && g.W % cw) cw >>= 1;
-        launch(dim3((unsigned)((g.W / cw + 63) / 64), (unsigned)((g.H + 3) / 4), (unsigned)(nframes * npl)), cw, p0, npl);
-    }
-}
-
 // the per-call part both filters share: buffers for nframes jobs, the job table, usability and the cells
 static int fm_prologue(FMEngine *h, int nframes, const std::vector<FMJob> &hj, hipStream_t st) {
     FLParams &P = h->P;
-    if (!h->dP)
-        if (int rc = flow_upload(P, h->nWidthP, h->nHeightP, &h->dTables, &h->dP)) return rc;
-    const size_t cellsN = (size_t)P.XP * P.YP;
-    const bool shift = h->nb == 1 && h->mode == 1;
-    if ((size_t)nframes > h->jobsCap) { // exactly this call's size; the capacity is raised only once every buffer exists
-        if (h->dJobs) (void)hipFree(h->dJobs);
-        if (h->dFlags) (void)hipFree(h->dFlags);
-        if (h->dCells) (void)hipFree(h->dCells);
-        if (h->dWin) (void)hipFree(h->dWin);
-        h->dJobs = nullptr; h->dFlags = nullptr; h->dCells = nullptr; h->dWin = nullptr;
-        h->jobsCap = 0;
-        const size_t n = (size_t)nframes;
-        HIP_CHECK(hipMalloc((void **)&h->dJobs, n * sizeof(FMJob)));
-        HIP_CHECK(hipMalloc((void **)&h->dFlags, n * 2 * sizeof(int)));
-        HIP_CHECK(hipMalloc((void **)&h->dCells, n * cellsN * h->nb * sizeof(int)));
-        if (shift) HIP_CHECK(hipMalloc((void **)&h->dWin, n * (size_t)h->winJob * sizeof(unsigned long long)));
-        h->jobsCap = n;
-    }
-    HIP_CHECK(hipMemcpyAsync(h->dJobs, hj.data(), sizeof(FMJob) * nframes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(fm_usable_kernel, dim3(nframes, 2), dim3(256), 0, st, h->dP, h->dJobs, h->nb, h->dFlags);
-    hipLaunchKernelGGL(fm_cells_kernel, dim3((unsigned)((cellsN + 255) / 256), nframes), dim3(256), 0, st, h->dP, h->dJobs, h->nb, h->dFlags, h->dCells);
+    if (!h->dP.p)
+        if (int rc = fps_upload_tables(h->dTables, h->dP, P, h->nWidthP, h->nHeightP)) return rc;
+    const size_t n = (size_t)nframes, cellsN = (size_t)P.XP * P.YP;
+    HIP_CHECK(h->dJobs.reserve(n));
+    HIP_CHECK(h->dFlags.reserve(n * 2));
+    HIP_CHECK(h->dCells.reserve(n * cellsN * h->nb));
+    if (h->nb == 1 && h->mode == 1) HIP_CHECK(h->dWin.reserve(n * (size_t)h->winJob)); // Flow's shift mode
+    HIP_CHECK(hipMemcpyAsync(h->dJobs.p, hj.data(), sizeof(FMJob) * nframes, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(fm_usable_kernel, dim3(nframes, 2), dim3(256), 0, st, h->dP.p, h->dJobs.p, h->nb, h->dFlags.p);
+    hipLaunchKernelGGL(fm_cells_kernel, dim3((unsigned)((cellsN + 255) / 256), nframes), dim3(256), 0, st, h->dP.p, h->dJobs.p, h->nb, h->dFlags.p, h->dCells.p);
     return MVX_OK;
 }
 
 // the geometry part of creation (after each filter's own checks): the size check, then the grid
 static int fm_create(FMEngine *h, const char *name, int64_t thscd1, int32_t thscd2, const mvx_analysis_data *ad, const mvx_super_info &si,
                      const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], bool padded, char *err) {
-    if (ad->nHeight != si.height || ad->nWidth != si.super_width - si.hpad * 2 || ad->nPel != si.pel) FFAIL("%s: wrong source or super clip frame size.", name);
+    if (!mvx_super_fits(ad, si, false)) MVX_FAIL("%s: wrong source or super clip frame size.", name);
     if (int rc = flow_geometry(h->P, h->nWidthP, h->nHeightP, name, thscd1, thscd2, ad, si, super_pitch, clip_pitch, dst_pitch, padded, err)) return rc;
     long long o = 0;
     for (int p = 0; p < 3; p++) {
@@ -807,17 +679,13 @@ static int fm_create(FMEngine *h, const char *name, int64_t thscd1, int32_t thsc
 // MVFlow.cpp:391-593 mvflowCreate.  time is a double argument there: time256 is formed in double (FlowInter forms it in float).
 extern "C" __attribute__((visibility("default"))) int mvx_flowcomp_create(const mvx_flowcomp_args *a, const mvx_analysis_data *vectors, const mvx_super *sup,
         int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flowcomp **out, char *err) {
-    char dummy[MVX_ERRLEN];
-    if (!err) err = dummy;
-    err[0] = 0;
-    *out = nullptr;
+    MVX_CREATE_BEGIN(out);
     const double time = a->time;
     const int mode = a->mode == MVX_UNSET ? 0 : a->mode;
-    int64_t thscd1 = a->thscd1 == MVX_UNSET ? 400 : a->thscd1;
-    int32_t thscd2 = a->thscd2 == MVX_UNSET ? 130 : a->thscd2;
-    if (time < 0.0 || time > 100.0) FFAIL("Flow: time must be between 0 and 100 %% (inclusive).");
-    if (mode < 0 || mode > 1) FFAIL("Flow: mode must be 0 or 1.");
-    if (int rc = flow_thscd("Flow", &thscd1, &thscd2, vectors, err)) return rc;
+    int64_t thscd1; int32_t thscd2;
+    if (time < 0.0 || time > 100.0) MVX_FAIL("Flow: time must be between 0 and 100 %% (inclusive).");
+    if (mode < 0 || mode > 1) MVX_FAIL("Flow: mode must be 0 or 1.");
+    if (int rc = mvx_resolve_thscd("Flow", a->thscd1, a->thscd2, vectors, &thscd1, &thscd2, err)) return rc;
     mvx_flowcomp *h = new mvx_flowcomp();
     if (int rc = fm_create(h, "Flow", thscd1, thscd2, vectors, sup->info, super_pitch, clip_pitch, dst_pitch, true, err)) { delete h; return rc; }
     h->nb = 1; h->mode = mode;
@@ -853,28 +721,18 @@ extern "C" __attribute__((visibility("default"))) int mvx_flowcomp_frames(mvx_fl
         if (!j.dst[0] || !j.clip[0]) { mvx_set_error("mvx_flowcomp_frames: dst / clip are required"); return MVX_E_ARG; }
     }
     if (int rc = fm_prologue(h, nframes, hj, st)) return rc;
-    const bool wide = P.bps == 1;
     if (h->mode == 0) {
-        fm_classes(P, nframes, false, [&](dim3 grid, int cw, int p0, int npl) {
-#define FK(TT, W_) hipLaunchKernelGGL((flowcomp_kernel<TT, W_>), grid, dim3(256), 0, st, h->dP, h->dJobs, h->dFlags, h->dCells, h->time256, p0, npl)
-            if (wide) { if (cw == 16) FK(uint8_t, 16); else if (cw == 8) FK(uint8_t, 8); else if (cw == 4) FK(uint8_t, 4); else if (cw == 2) FK(uint8_t, 2); else FK(uint8_t, 1); }
-            else { if (cw == 8) FK(uint16_t, 8); else if (cw == 4) FK(uint16_t, 4); else if (cw == 2) FK(uint16_t, 2); else FK(uint16_t, 1); }
-#undef FK
+        flow_launches(P, nframes, [&](dim3 grid, int p0, int npl, auto t, auto w) {
+            hipLaunchKernelGGL((flowcomp_kernel<typename decltype(t)::type, decltype(w)::value>), grid, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p, h->dCells.p, h->time256, p0, npl);
         });
     } else {
-        const FMWin w = { h->dWin, h->winJob, { h->winOff[0], h->winOff[1], h->winOff[2] } };
-        HIP_CHECK(hipMemsetAsync(h->dWin, 0, (size_t)nframes * h->winJob * sizeof(unsigned long long), st));
-        fm_classes(P, nframes, false, [&](dim3 grid, int cw, int p0, int npl) {
-#define FK(TT, W_) hipLaunchKernelGGL((flowshift_scatter<TT, W_>), grid, dim3(256), 0, st, h->dP, h->dJobs, h->dFlags, h->dCells, h->time256, w, p0, npl)
-            if (wide) { if (cw == 16) FK(uint8_t, 16); else if (cw == 8) FK(uint8_t, 8); else if (cw == 4) FK(uint8_t, 4); else if (cw == 2) FK(uint8_t, 2); else FK(uint8_t, 1); }
-            else { if (cw == 8) FK(uint16_t, 8); else if (cw == 4) FK(uint16_t, 4); else if (cw == 2) FK(uint16_t, 2); else FK(uint16_t, 1); }
-#undef FK
+        const FMWin win = { h->dWin.p, h->winJob, { h->winOff[0], h->winOff[1], h->winOff[2] } };
+        HIP_CHECK(hipMemsetAsync(h->dWin.p, 0, (size_t)nframes * h->winJob * sizeof(unsigned long long), st));
+        flow_launches(P, nframes, [&](dim3 grid, int p0, int npl, auto t, auto w) {
+            hipLaunchKernelGGL((flowshift_scatter<typename decltype(t)::type, decltype(w)::value>), grid, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p, h->dCells.p, h->time256, win, p0, npl);
         });
-        fm_classes(P, nframes, false, [&](dim3 grid, int cw, int p0, int npl) {
-#define FK(TT, W_) hipLaunchKernelGGL((flowshift_resolve<TT, W_>), grid, dim3(256), 0, st, h->dP, h->dJobs, h->dFlags, w, p0, npl)
-            if (wide) { if (cw == 16) FK(uint8_t, 16); else if (cw == 8) FK(uint8_t, 8); else if (cw == 4) FK(uint8_t, 4); else if (cw == 2) FK(uint8_t, 2); else FK(uint8_t, 1); }
-            else { if (cw == 8) FK(uint16_t, 8); else if (cw == 4) FK(uint16_t, 4); else if (cw == 2) FK(uint16_t, 2); else FK(uint16_t, 1); }
-#undef FK
+        flow_launches(P, nframes, [&](dim3 grid, int p0, int npl, auto t, auto w) {
+            hipLaunchKernelGGL((flowshift_resolve<typename decltype(t)::type, decltype(w)::value>), grid, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p, win, p0, npl);
         });
     }
     HIP_CHECK(hipGetLastError());
@@ -885,17 +743,13 @@ extern "C" __attribute__((visibility("default"))) int mvx_flowcomp_frames(mvx_fl
 extern "C" __attribute__((visibility("default"))) int mvx_flowblur_create(const mvx_flowblur_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
         const mvx_super *sup, int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flowblur **out,
         char *err) {
-    char dummy[MVX_ERRLEN];
-    if (!err) err = dummy;
-    err[0] = 0;
-    *out = nullptr;
+    MVX_CREATE_BEGIN(out);
     const float blur = (float)a->blur;
     const int prec = a->prec == MVX_UNSET ? 1 : a->prec;
-    int64_t thscd1 = a->thscd1 == MVX_UNSET ? 400 : a->thscd1;
-    int32_t thscd2 = a->thscd2 == MVX_UNSET ? 130 : a->thscd2;
-    if (blur < 0.0f || blur > 200.0f) FFAIL("FlowBlur: blur must be between 0 and 200 %% (inclusive).");
-    if (prec < 1) FFAIL("FlowBlur: prec must be at least 1.");
-    if (int rc = flow_pair_checks("FlowBlur", &thscd1, &thscd2, bw, fw, err)) return rc;
+    int64_t thscd1; int32_t thscd2;
+    if (blur < 0.0f || blur > 200.0f) MVX_FAIL("FlowBlur: blur must be between 0 and 200 %% (inclusive).");
+    if (prec < 1) MVX_FAIL("FlowBlur: prec must be at least 1.");
+    if (int rc = flow_pair_checks("FlowBlur", a->thscd1, a->thscd2, &thscd1, &thscd2, bw, fw, err)) return rc;
     mvx_flowblur *h = new mvx_flowblur();
     if (int rc = fm_create(h, "FlowBlur", thscd1, thscd2, bw, sup->info, super_pitch, clip_pitch, dst_pitch, false, err)) { delete h; return rc; }
     h->nb = 2; h->prec = prec;
@@ -926,9 +780,9 @@ extern "C" __attribute__((visibility("default"))) int mvx_flowblur_frames(mvx_fl
         if (!j.dst[0] || !j.clip[0]) { mvx_set_error("mvx_flowblur_frames: dst / clip are required"); return MVX_E_ARG; }
     }
     if (int rc = fm_prologue(h, nframes, hj, st)) return rc;
-    fm_classes(P, nframes, true, [&](dim3 grid, int, int p0, int npl) {
-        if (P.bps == 1) hipLaunchKernelGGL((flowblur_kernel<uint8_t>), grid, dim3(256), 0, st, h->dP, h->dJobs, h->dFlags, h->dCells, h->blur256, h->prec, p0, npl);
-        else hipLaunchKernelGGL((flowblur_kernel<uint16_t>), grid, dim3(256), 0, st, h->dP, h->dJobs, h->dFlags, h->dCells, h->blur256, h->prec, p0, npl);
+    fps_classes(P.pl, P.nplanes, nframes, [](int) { return 1; }, [&](dim3 grid, int, int p0, int npl) { // one sample per thread
+        if (P.bps == 1) hipLaunchKernelGGL((flowblur_kernel<uint8_t>), grid, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p, h->dCells.p, h->blur256, h->prec, p0, npl);
+        else hipLaunchKernelGGL((flowblur_kernel<uint16_t>), grid, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p, h->dCells.p, h->blur256, h->prec, p0, npl);
     });
     HIP_CHECK(hipGetLastError());
     return MVX_OK;

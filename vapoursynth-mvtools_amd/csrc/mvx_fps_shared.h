@@ -1,8 +1,10 @@
-// mvx_fps_shared.h -- device and host helpers shared by the block filters (mvx_degrain.hip) and the flow filters (mvx_flow.hip):
-// the level-0 vector reader, the super-plane addressing, the wide sample loads / stores, the reference's bilinear upsizer tables and
-// the occlusion mask of MaskFun.cpp.  Internal; not part of the ABI.
+// mvx_fps_shared.h -- what the filters that consume vectors share (mvx_degrain.hip, mvx_flow.hip, mvx_mask.hip).  Device side: the level-0
+// vector reader, fgopIsUsable, the super-plane addressing, the wide sample loads / stores, the reference's bilinear upsizer and the occlusion
+// mask of MaskFun.cpp.  Host side: the scene-change thresholds, the checks on a pair of vector clips, the frame-rate conversion, the padded
+// small-field grid with its upsizer tables, the plane geometry and the launch dispatch by sample type and width.  Internal; not part of the ABI.
 #pragma once
 #include <algorithm>
+#include <type_traits>
 #include "mvx_common.h"
 
 struct __attribute__((packed, aligned(4))) GVecD { int x, y; long long sad; };
@@ -102,18 +104,34 @@ __device__ __forceinline__ int bf_upsize(const unsigned char *m, int XP, const i
     return fps_upsize_u8(m, r0, r0 + XP, hOff[x], 16384 - wb, wb, 16384 - wr, wr);
 }
 
-// Fakery.c:52-58,103-107,144-146 fgopIsUsable, the count part: this thread's share (stride 256) of the level-0 blocks whose SAD exceeds thscd1.
-// Global-address-space loads, four in flight, so that a wave does not wait for each 16-byte record on its own.
-__device__ __forceinline__ int fps_count_over(const unsigned char *blob, int nLvCount, int nBlk, long long thscd1) {
-    DG_GL const unsigned char *v = dg_gl(mvx_level0(blob, nLvCount));
+// Fakery.c:52-58,103-107,144-146 fgopIsUsable, the count part: this thread's share (stride 256) of the n level-0 blocks from `first` on whose SAD
+// exceeds thscd1.  Global-address-space loads, four in flight, so that a wave does not wait for each 16-byte record on its own.
+__device__ __forceinline__ int fps_count_over(const unsigned char *blob, int nLvCount, int first, int n, long long thscd1) {
+    DG_GL const unsigned char *v = dg_gl(mvx_level0(blob, nLvCount)) + 16 * (long long)first + 8;
     int c = 0, i = threadIdx.x;
-    for (; i + 768 < nBlk; i += 1024) {
-        const long long s0 = *(DG_GL const long long *)(v + 16 * i + 8), s1 = *(DG_GL const long long *)(v + 16 * (i + 256) + 8);
-        const long long s2 = *(DG_GL const long long *)(v + 16 * (i + 512) + 8), s3 = *(DG_GL const long long *)(v + 16 * (i + 768) + 8);
+    for (; i + 768 < n; i += 1024) {
+        const long long s0 = *(DG_GL const long long *)(v + 16 * i), s1 = *(DG_GL const long long *)(v + 16 * (i + 256));
+        const long long s2 = *(DG_GL const long long *)(v + 16 * (i + 512)), s3 = *(DG_GL const long long *)(v + 16 * (i + 768));
         c += (s0 > thscd1) + (s1 > thscd1) + (s2 > thscd1) + (s3 > thscd1);
     }
-    for (; i < nBlk; i += 256) c += *(DG_GL const long long *)(v + 16 * i + 8) > thscd1 ? 1 : 0;
+    for (; i < n; i += 256) c += *(DG_GL const long long *)(v + 16 * i) > thscd1 ? 1 : 0;
     return c;
+}
+// fgopIsUsable of N vector fields by one workgroup of 256 threads, all of which call: every field has validity == 1 && !(count(sad > thscd1) >
+// thscd2).  `want` (uniform) false: not usable, and no blob is dereferenced.  The decision is returned to thread 0 only (false elsewhere).
+template <int N> __device__ __forceinline__ bool fps_block_usable(const unsigned char *const (&blob)[N], bool want, int nLvCount, int nBlk, long long thscd1, int thscd2) {
+    __shared__ int cnt[N];
+    if (threadIdx.x < N) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    if (want) for (int d = 0; d < N; d++) atomicAdd(&cnt[d], fps_count_over(blob[d], nLvCount, 0, nBlk, thscd1));
+    __syncthreads();
+    bool ok = threadIdx.x == 0 && want;
+    for (int d = 0; d < N; d++) ok = ok && ((const int *)blob[d])[1] == 1 && !(cnt[d] > thscd2);
+    return ok;
+}
+__device__ __forceinline__ bool fps_block_usable(const unsigned char *blob, bool want, int nLvCount, int nBlk, long long thscd1, int thscd2) {
+    const unsigned char *const one[1] = { blob };
+    return fps_block_usable(one, want, nLvCount, nBlk, thscd1, thscd2);
 }
 
 // MaskFun.cpp:85-90 ByteOccMask, the value that is maxed into the mask.  fGamma 1 has no pow (the interpolating filters, which pass the
@@ -172,3 +190,135 @@ static void bf_tables(int *offsets, int *weights, int out, int in) {
     }
 }
 static long long bf_gcd(long long x, long long y) { while (y) { long long t = x % y; x = y; y = t; } return x; }
+
+// ------------------------------------------------------------------------------------------------ host helpers
+
+// the scene-change thresholds of a filter from its arguments: MV_DEFAULT_SCD1 / MV_DEFAULT_SCD2, then MVAnalysisData.c:7-31 scaleThSCD with
+// its limit check.  unscaled: thscd1 before the scaling (Degrain and Compensate scale thsad by the same ratio)
+static int mvx_resolve_thscd(const char *name, int64_t arg1, int32_t arg2, const mvx_analysis_data *ad, int64_t *thscd1, int32_t *thscd2, char *err,
+                             int64_t *unscaled = nullptr) {
+    const int maxSAD = 8 * 8 * 255;
+    *thscd1 = arg1 == MVX_UNSET ? 400 : arg1;
+    *thscd2 = arg2 == MVX_UNSET ? 130 : arg2;
+    if (*thscd1 > maxSAD) MVX_FAIL("%s: thscd1 can be at most %d.", name, maxSAD);
+    if (unscaled) *unscaled = *thscd1;
+    mvx_scale_thscd(thscd1, thscd2, ad);
+    return MVX_OK;
+}
+
+// the checks on mvbw / mvfw that every two-clip filter makes after comparing their geometry (MVBlockFPS.c:844-871, MVFlowInter.c:571-598,
+// MVFlowBlur.c:440-467; FlowFPS lacks the first in the reference and then reads negative frame numbers: rejected here on purpose)
+static int mvx_pair_checks(const char *name, const mvx_analysis_data *bw, const mvx_analysis_data *fw, char *err) {
+    if (bw->nDeltaFrame <= 0 || fw->nDeltaFrame <= 0) MVX_FAIL("%s: cannot use motion vectors with absolute frame references.", name);
+    if (bw->nDeltaFrame != fw->nDeltaFrame) MVX_FAIL("%s: mvbw and mvfw must be generated with the same delta.", name);
+    if (!bw->isBackward) MVX_FAIL("%s: mvbw must be generated with isb=True.", name);
+    if (fw->isBackward) MVX_FAIL("%s: mvfw must be generated with isb=False.", name);
+    return MVX_OK;
+}
+
+// "wrong source or super clip frame size": the vectors against the super clip, and with `width` also against the clip's own width
+static bool mvx_super_fits(const mvx_analysis_data *ad, const mvx_super_info &si, bool width) {
+    return ad->nHeight == si.height && ad->nWidth == si.super_width - si.hpad * 2 && (!width || ad->nWidth == si.width) && ad->nPel == si.pel;
+}
+
+// frame-rate conversion of BlockFPS and FlowFPS (MVBlockFPS.c:703-718,888-909, MVFlowFPS.c:547-561,714-744): fa / fb = input rate / output
+// rate in lowest terms, the output clip's rate and frame count.  num / den as passed: MVX_UNSET -> 25 / 1, 0 -> double the input rate
+struct FpsRate { long long fa, fb, outNum, outDen; int outFrames; };
+static void fps_rate_init(FpsRate &r, long long num, long long den, long long fps_num, long long fps_den, int num_frames) {
+    if (num == MVX_UNSET) num = 25;
+    if (den == MVX_UNSET) den = 1;
+    if (num == 0 || den == 0) { num = fps_num * 2; den = fps_den; }
+    r.fa = den * fps_num; r.fb = num * fps_den;
+    const long long g = bf_gcd(r.fa, r.fb);
+    r.fa /= g; r.fb /= g;
+    if (num <= 0 || den <= 0) { r.outNum = 0; r.outDen = 1; } // setFPS
+    else { const long long x = bf_gcd(num, den); r.outNum = num / x; r.outDen = den / x; }
+    r.outFrames = (int)(1 + (num_frames - 1) * r.fb / r.fa);
+}
+// output frame n -> the input frames it lies between and its time position (MVBlockFPS.c:245-254,278-292, MVFlowFPS.c:92-99,125-134)
+static void fps_rate_map(const FpsRate &r, int delta, int n, int *nleft, int *nright, int *time256) {
+    *nleft = (int)(n * r.fa / r.fb);
+    int t = (int)(((double)n * r.fa / r.fb - *nleft) * 256 + 0.5);
+    if (delta > 1) t = t / delta;
+    *nright = *nleft + delta;
+    *time256 = t;
+}
+
+// the small fields padded until they cover the frame, and the size the upsizer stretches them to, luma / chroma (MVBlockFPS.c:936-949,
+// MVFlowInter.c:651-665, MVFlowFPS.c:804-816, MVFlow.cpp:535-546)
+static void fps_padded_grid(const mvx_analysis_data *ad, int *XP, int *YP, int nWidthP[2], int nHeightP[2]) {
+    const int stepX = ad->nBlkSizeX - ad->nOverlapX, stepY = ad->nBlkSizeY - ad->nOverlapY;
+    *XP = ad->nBlkX; *YP = ad->nBlkY;
+    while (*XP * stepX + ad->nOverlapX < ad->nWidth) (*XP)++;
+    while (*YP * stepY + ad->nOverlapY < ad->nHeight) (*YP)++;
+    nWidthP[0] = *XP * stepX + ad->nOverlapX; nHeightP[0] = *YP * stepY + ad->nOverlapY;
+    nWidthP[1] = nWidthP[0] / ad->xRatioUV; nHeightP[1] = nHeightP[0] / ad->yRatioUV;
+}
+// a parameter block on the device
+template <typename PARAMS> static int fps_upload_params(DevBuf<PARAMS> &d, const PARAMS &P) {
+    HIP_CHECK(d.reserve(1));
+    const hipError_t e = hipMemcpy(d.p, &P, sizeof(PARAMS), hipMemcpyHostToDevice);
+    if (e != hipSuccess) d.release(); // (handles take an existing block for an uploaded one)
+    HIP_CHECK(e);
+    return MVX_OK;
+}
+// the upsizer tables from the P.XP x P.YP small fields to nWidthP / nHeightP (luma, chroma) on the device, then P, which points into them
+template <typename PARAMS> static int fps_upload_tables(DevBuf<int> &tables, DevBuf<PARAMS> &d, PARAMS &P, const int nWidthP[2], const int nHeightP[2]) {
+    const int n = nWidthP[0] + nWidthP[1] + nHeightP[0] + nHeightP[1];
+    std::vector<int> t(2 * n);
+    int *o = t.data(), *w = t.data() + n, pos = 0;
+    HIP_CHECK(tables.reserve(2 * (size_t)n));
+    for (int c = 0; c < 2; c++) {
+        bf_tables(o + pos, w + pos, nWidthP[c], P.XP); P.hOff[c] = tables.p + pos; P.hW[c] = tables.p + n + pos; pos += nWidthP[c];
+        bf_tables(o + pos, w + pos, nHeightP[c], P.YP); P.vOff[c] = tables.p + pos; P.vW[c] = tables.p + n + pos; pos += nHeightP[c];
+    }
+    HIP_CHECK(hipMemcpy(tables.p, t.data(), sizeof(int) * 2 * n, hipMemcpyHostToDevice));
+    return fps_upload_params(d, P);
+}
+
+// the three planes of the clip and of level 0 of its super clip; a clip with fewer planes repeats plane 0's pitches
+static void fps_fill_planes(PlaneG pl[3], const mvx_analysis_data *ad, const mvx_super_info &si, const ptrdiff_t src_pitch[3], const ptrdiff_t super_pitch[3],
+                            const ptrdiff_t dst_pitch[3]) {
+    const int xSub = mvx_ilog2(si.xRatioUV), ySub = mvx_ilog2(si.yRatioUV);
+    for (int p = 0; p < 3; p++) {
+        PlaneG &g = pl[p];
+        const int sx = p ? xSub : 0, sy = p ? ySub : 0, q = p < si.num_planes ? p : 0;
+        g.subX = sx; g.subY = sy;
+        g.W = ad->nWidth >> sx; g.H = ad->nHeight >> sy;
+        g.blkW = ad->nBlkSizeX >> sx; g.blkH = ad->nBlkSizeY >> sy;
+        g.ovX = ad->nOverlapX >> sx; g.ovY = ad->nOverlapY >> sy;
+        g.stepX = g.blkW - g.ovX; g.stepY = g.blkH - g.ovY;
+        g.WB = (ad->nBlkX * (ad->nBlkSizeX - ad->nOverlapX) + ad->nOverlapX) >> sx;
+        g.HB = (ad->nBlkY * (ad->nBlkSizeY - ad->nOverlapY) + ad->nOverlapY) >> sy;
+        g.hpadPel = (si.hpad >> sx) * si.pel; g.vpadPel = (si.vpad >> sy) * si.pel; // MVFrame.cpp:1334-1335,1775-1779; the Finest frame's nOffsetY / nOffsetUV (MVFlowInter.c:218-219)
+        g.srcPitch = src_pitch ? src_pitch[q] : 0;
+        g.supPitch = super_pitch[q];
+        g.dstPitch = dst_pitch[q];
+        g.supPlaneStride = g.supPitch * (long long)((si.height >> sy) + 2 * (si.vpad >> sy));
+        g.thIdx = p ? 1 : 0;
+        g.process = 1; g.limit = (1 << si.bits) - 1;
+        g.shadow = 0;
+    }
+}
+
+// ---- launches of the kernels that produce CW consecutive samples per thread, 64 x 4 threads per workgroup
+// the widest segment of at most 16 bytes that divides a plane of W samples
+static int fps_segment(int bps, int W) { int cw = 16 / bps; while (cw > 1 && W % cw) cw >>= 1; return cw; }
+// one launch for the luma planes of all jobs and one for both chroma planes of all jobs (the two classes differ in the segment and in the
+// upsizer tables): launch(grid, cw, first plane, planes per job) with cw = cwOf(first plane)
+template <typename CWOF, typename F> static void fps_classes(const PlaneG pl[3], int nplanes, int nframes, CWOF &&cwOf, F &&launch) {
+    for (int cls = 0; cls < (nplanes > 1 ? 2 : 1); cls++) {
+        const int p0 = cls, npl = cls ? 2 : 1, cw = cwOf(p0);
+        launch(dim3((unsigned)((pl[p0].W / cw + 63) / 64), (unsigned)((pl[p0].H + 3) / 4), (unsigned)(nframes * npl)), cw, p0, npl);
+    }
+}
+// (bytes per sample, segment) -> f(fps_type<T>(), std::integral_constant<int, CW>()) for the segments MINW .. 16 bytes of uint8_t / uint16_t; a
+// generic lambda launches kernel<typename decltype(t)::type, decltype(w)::value>.  Only these combinations are instantiated.
+template <typename T> struct fps_type { typedef T type; };
+template <int MINW, typename T, int W, typename F> static void fps_dispatch_width(int cw, F &f) {
+    if constexpr (W > MINW) { if (cw < W) return fps_dispatch_width<MINW, T, W / 2>(cw, f); }
+    f(fps_type<T>(), std::integral_constant<int, W>());
+}
+template <int MINW, typename F> static void fps_dispatch(int bps, int cw, F &&f) {
+    if (bps == 1) fps_dispatch_width<MINW, uint8_t, 16>(cw, f); else fps_dispatch_width<MINW, uint16_t, 8>(cw, f);
+}

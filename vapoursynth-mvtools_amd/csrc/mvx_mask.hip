@@ -44,15 +44,8 @@ __global__ __launch_bounds__(256) void mask_usable_kernel(const MKParams *Pp, co
     if (threadIdx.x == 0) cnt = 0;
     __syncthreads();
     if (blob) {
-        const int share = (P.nBlk + MK_SLICES - 1) / MK_SLICES, first = min(s * share, P.nBlk), n = min(share, P.nBlk - first);
-        DG_GL const unsigned char *v = dg_gl(mvx_level0(blob, P.nLvCount)) + 16 * (long long)first + 8;
-        int c = 0, i = threadIdx.x;
-        for (; i + 768 < n; i += 1024) { // four loads in flight, as fps_count_over
-            const long long s0 = *(DG_GL const long long *)(v + 16 * i), s1 = *(DG_GL const long long *)(v + 16 * (i + 256));
-            const long long s2 = *(DG_GL const long long *)(v + 16 * (i + 512)), s3 = *(DG_GL const long long *)(v + 16 * (i + 768));
-            c += (s0 > P.thscd1) + (s1 > P.thscd1) + (s2 > P.thscd1) + (s3 > P.thscd1);
-        }
-        for (; i < n; i += 256) c += *(DG_GL const long long *)(v + 16 * i) > P.thscd1 ? 1 : 0;
+        const int share = (P.nBlk + MK_SLICES - 1) / MK_SLICES, first = min(s * share, P.nBlk);
+        const int c = fps_count_over(blob, P.nLvCount, first, min(share, P.nBlk - first), P.thscd1);
         if (c) atomicAdd(&cnt, c);
     }
     __syncthreads();
@@ -310,23 +303,12 @@ struct mvx_mask {
     mvx_mask_info info;
     std::vector<unsigned> tables;        // hTab luma, vTab luma, hTab chroma, vTab chroma
     size_t tabOff[4];
-    MKParams *dP = nullptr;
-    unsigned *dTables = nullptr;
-    MKJob *dJobs = nullptr;
-    int *dOver = nullptr, *dOcc = nullptr;
-    unsigned char *dSmall = nullptr;
-    size_t jobsCap = 0;
-    ~mvx_mask() {
-        if (dP) (void)hipFree(dP);
-        if (dTables) (void)hipFree(dTables);
-        if (dJobs) (void)hipFree(dJobs);
-        if (dOver) (void)hipFree(dOver);
-        if (dOcc) (void)hipFree(dOcc);
-        if (dSmall) (void)hipFree(dSmall);
-    }
+    DevBuf<MKParams> dP;
+    DevBuf<unsigned> dTables;
+    DevBuf<MKJob> dJobs;                 // the per-job buffers hold exactly the largest call's jobs
+    DevBuf<int> dOver, dOcc;
+    DevBuf<unsigned char> dSmall;
 };
-
-#define MFAIL(...) do { snprintf(err, MVX_ERRLEN, __VA_ARGS__); mvx_set_error("%s", err); return MVX_E_ARG; } while (0)
 
 // SimpleResize.cpp:27-57 InitTables from `in` cells to `covered` samples, laid out for all `size` samples of the plane (and on to `padded`
 // entries): a sample beyond the covered rectangle takes the entry of the last covered one -- MVMask.c:164-169,180-189
@@ -342,30 +324,25 @@ static void mask_table(unsigned *t, int padded, int size, int covered, int in) {
 // MVMask.c:227-346 mvmaskCreate
 extern "C" __attribute__((visibility("default"))) int mvx_mask_create(const mvx_mask_args *a, const mvx_analysis_data *ad, const mvx_mask_clip *clip,
         const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_mask **out, char *err) {
-    char dummy[MVX_ERRLEN];
-    if (!err) err = dummy;
-    err[0] = 0;
-    *out = nullptr;
+    MVX_CREATE_BEGIN(out);
     const float ml = (float)a->ml, fGamma = (float)a->gamma;   // float arguments (MVMask.c:235-241)
     const int kind = a->kind == MVX_UNSET ? 0 : a->kind;
     const double time = a->time;
     const int ysc = a->ysc == MVX_UNSET ? 0 : a->ysc;
-    int64_t thscd1 = a->thscd1 == MVX_UNSET ? 400 : a->thscd1;
-    int32_t thscd2 = a->thscd2 == MVX_UNSET ? 130 : a->thscd2;
-    if (fGamma < 0.0f) MFAIL("Mask: gamma must not be negative.");
-    if (kind < 0 || kind > 5) MFAIL("Mask: kind must 0, 1, 2, 3, 4, or 5.");
-    if (time < 0.0 || time > 100.0) MFAIL("Mask: time must be between 0.0 and 100.0 (inclusive).");
-    if (ysc < 0 || ysc > 255) MFAIL("Mask: ysc must be between 0 and 255 (inclusive).");
-    if (thscd1 > 8 * 8 * 255) MFAIL("Mask: thscd1 can be at most %d.", 8 * 8 * 255); // MVAnalysisData.c:7-31 scaleThSCD
-    mvx_scale_thscd(&thscd1, &thscd2, ad);
+    int64_t thscd1; int32_t thscd2;
+    if (fGamma < 0.0f) MVX_FAIL("Mask: gamma must not be negative.");
+    if (kind < 0 || kind > 5) MVX_FAIL("Mask: kind must 0, 1, 2, 3, 4, or 5.");
+    if (time < 0.0 || time > 100.0) MVX_FAIL("Mask: time must be between 0.0 and 100.0 (inclusive).");
+    if (ysc < 0 || ysc > 255) MVX_FAIL("Mask: ysc must be between 0 and 255 (inclusive).");
+    if (int rc = mvx_resolve_thscd("Mask", a->thscd1, a->thscd2, ad, &thscd1, &thscd2, err)) return rc;
     if (clip->bits > 8 || clip->subsampling_w > 1 || clip->subsampling_h > 1 || clip->subsampling_w < 0 || clip->subsampling_h < 0)
-        MFAIL("Mask: input clip must be GRAY8, YUV420P8, YUV422P8, YUV440P8, or YUV444P8, with constant dimensions.");
+        MVX_FAIL("Mask: input clip must be GRAY8, YUV420P8, YUV422P8, YUV440P8, or YUV444P8, with constant dimensions.");
     // the library's own checks (divergences 1 and 2 of mvtools_amd.h)
-    if (ad->nBlkX < 2 || ad->nBlkY < 2) MFAIL("Mask: the frame must be at least two blocks wide and two blocks high.");
+    if (ad->nBlkX < 2 || ad->nBlkY < 2) MVX_FAIL("Mask: the frame must be at least two blocks wide and two blocks high.");
     const int xr = clip->gray ? 1 : 1 << clip->subsampling_w, yr = clip->gray ? 1 : 1 << clip->subsampling_h;
     if (clip->width != ad->nWidth || clip->height != ad->nHeight || xr != ad->xRatioUV || yr != ad->yRatioUV)
-        MFAIL("Mask: the clip's size and chroma subsampling must be those of the vector clip.");
-    if (dst_pitch[0] % 16 || dst_pitch[1] % 16 || dst_pitch[1] != dst_pitch[2]) MFAIL("Mask: dst pitches must be multiples of 16 bytes, U and V alike.");
+        MVX_FAIL("Mask: the clip's size and chroma subsampling must be those of the vector clip.");
+    if (dst_pitch[0] % 16 || dst_pitch[1] % 16 || dst_pitch[1] != dst_pitch[2]) MVX_FAIL("Mask: dst pitches must be multiples of 16 bytes, U and V alike.");
 
     mvx_mask *h = new mvx_mask();
     MKParams &P = h->P;
@@ -428,40 +405,29 @@ extern "C" __attribute__((visibility("default"))) int mvx_mask_frames(mvx_mask *
         }
         if (P.kind == 5 && !j.clip) { mvx_set_error("mvx_mask_frames: kind 5 needs clip_luma"); return MVX_E_ARG; }
     }
-    if (!h->dP) {
-        HIP_CHECK(hipMalloc((void **)&h->dTables, sizeof(unsigned) * h->tables.size()));
-        HIP_CHECK(hipMemcpy(h->dTables, h->tables.data(), sizeof(unsigned) * h->tables.size(), hipMemcpyHostToDevice));
-        for (int c = 0; c < 2; c++) { P.hTab[c] = h->dTables + h->tabOff[2 * c]; P.vTab[c] = h->dTables + h->tabOff[2 * c + 1]; }
-        MKParams *dP = nullptr;
-        HIP_CHECK(hipMalloc((void **)&dP, sizeof(MKParams)));
-        if (hipMemcpy(dP, &P, sizeof(MKParams), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(dP); mvx_set_error("mvx_mask_frames: parameter upload failed"); return MVX_E_DEVICE; }
-        h->dP = dP;
+    if (!h->dP.p) {
+        HIP_CHECK(h->dTables.reserve(h->tables.size()));
+        HIP_CHECK(hipMemcpy(h->dTables.p, h->tables.data(), sizeof(unsigned) * h->tables.size(), hipMemcpyHostToDevice));
+        for (int c = 0; c < 2; c++) { P.hTab[c] = h->dTables.p + h->tabOff[2 * c]; P.vTab[c] = h->dTables.p + h->tabOff[2 * c + 1]; }
+        HIP_CHECK(h->dP.reserve(1));
+        if (hipMemcpy(h->dP.p, &P, sizeof(MKParams), hipMemcpyHostToDevice) != hipSuccess) { h->dP.release(); mvx_set_error("mvx_mask_frames: parameter upload failed"); return MVX_E_DEVICE; }
     }
-    if ((size_t)nframes > h->jobsCap) { // exactly this call's size; the capacity is raised only once every buffer exists
-        if (h->dJobs) (void)hipFree(h->dJobs);
-        if (h->dOver) (void)hipFree(h->dOver);
-        if (h->dSmall) (void)hipFree(h->dSmall);
-        if (h->dOcc) (void)hipFree(h->dOcc);
-        h->dJobs = nullptr; h->dOver = nullptr; h->dSmall = nullptr; h->dOcc = nullptr;
-        h->jobsCap = 0;
-        const size_t n = (size_t)nframes;
-        HIP_CHECK(hipMalloc((void **)&h->dJobs, n * sizeof(MKJob)));
-        HIP_CHECK(hipMalloc((void **)&h->dOver, n * MK_SLICES * sizeof(int)));
-        HIP_CHECK(hipMalloc((void **)&h->dSmall, n * 2 * (size_t)P.stride + 32)); // + the slack mk_load16 may read
-        if (P.kind == 2) HIP_CHECK(hipMalloc((void **)&h->dOcc, n * (size_t)P.stride * sizeof(int)));
-        h->jobsCap = n;
-    }
-    HIP_CHECK(hipMemcpyAsync(h->dJobs, hj.data(), sizeof(MKJob) * nframes, hipMemcpyHostToDevice, st));
+    const size_t n = (size_t)nframes;
+    HIP_CHECK(h->dJobs.reserve(n));
+    HIP_CHECK(h->dOver.reserve(n * MK_SLICES));
+    HIP_CHECK(h->dSmall.reserve(n * 2 * (size_t)P.stride + 32)); // + the slack mk_load16 may read
+    if (P.kind == 2) HIP_CHECK(h->dOcc.reserve(n * (size_t)P.stride));
+    HIP_CHECK(hipMemcpyAsync(h->dJobs.p, hj.data(), sizeof(MKJob) * nframes, hipMemcpyHostToDevice, st));
     const dim3 perBlock((unsigned)(((P.nBlk + 3) / 4 + 255) / 256), (unsigned)nframes); // four blocks per lane
-    hipLaunchKernelGGL(mask_usable_kernel, dim3(MK_SLICES, (unsigned)nframes), dim3(256), 0, st, h->dP, h->dJobs, h->dOver);
-    if (P.kind == 2) HIP_CHECK(hipMemsetAsync(h->dOcc, 0, (size_t)nframes * P.stride * sizeof(int), st));
-    if (P.kind == 2) hipLaunchKernelGGL((mask_small_kernel<1>), dim3((unsigned)((P.nBlk + 255) / 256), (unsigned)nframes), dim3(256), 0, st, h->dP, h->dJobs, h->dOver, h->dSmall, h->dOcc);
-    else hipLaunchKernelGGL((mask_small_kernel<4>), perBlock, dim3(256), 0, st, h->dP, h->dJobs, h->dOver, h->dSmall, h->dOcc);
-    if (P.kind == 2) hipLaunchKernelGGL(mask_occ_finish_kernel, perBlock, dim3(256), 0, st, h->dP, h->dJobs, h->dOver, h->dOcc, h->dSmall);
+    hipLaunchKernelGGL(mask_usable_kernel, dim3(MK_SLICES, (unsigned)nframes), dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dOver.p);
+    if (P.kind == 2) HIP_CHECK(hipMemsetAsync(h->dOcc.p, 0, n * P.stride * sizeof(int), st));
+    if (P.kind == 2) hipLaunchKernelGGL((mask_small_kernel<1>), dim3((unsigned)((P.nBlk + 255) / 256), (unsigned)nframes), dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dOver.p, h->dSmall.p, h->dOcc.p);
+    else hipLaunchKernelGGL((mask_small_kernel<4>), perBlock, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dOver.p, h->dSmall.p, h->dOcc.p);
+    if (P.kind == 2) hipLaunchKernelGGL(mask_occ_finish_kernel, perBlock, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dOver.p, h->dOcc.p, h->dSmall.p);
     hipLaunchKernelGGL((mask_planes_kernel<0>), dim3((unsigned)(((long long)P.segs[0] * ((P.H[0] + MK_ROWS - 1) / MK_ROWS) + 255) / 256), (unsigned)nframes), dim3(256), 0, st,
-                       h->dP, h->dJobs, h->dOver, h->dSmall);
+                       h->dP.p, h->dJobs.p, h->dOver.p, h->dSmall.p);
     hipLaunchKernelGGL((mask_planes_kernel<1>), dim3((unsigned)(((long long)P.segs[1] * ((P.H[1] + MK_ROWS - 1) / MK_ROWS) + 255) / 256), (unsigned)nframes * 2), dim3(256), 0, st,
-                       h->dP, h->dJobs, h->dOver, h->dSmall);
+                       h->dP.p, h->dJobs.p, h->dOver.p, h->dSmall.p);
     HIP_CHECK(hipGetLastError());
     return MVX_OK;
 }

@@ -55,10 +55,7 @@ void mvx_level_plane(const mvx_super_info &si, int level, int plane, long long p
 static int argdef(int v, int d) { return v == MVX_UNSET ? d : v; }
 
 extern "C" __attribute__((visibility("default"))) int mvx_super_create(const mvx_super_args *a, mvx_super **out, char *err) { // MVSuper.c:140-264
-    char dummy[MVX_ERRLEN];
-    if (!err) err = dummy;
-    err[0] = 0;
-    *out = nullptr;
+    MVX_CREATE_BEGIN(out);
     mvx_super_info si;
     memset(&si, 0, sizeof(si));
     si.hpad = argdef(a->hpad, 16);
@@ -68,14 +65,13 @@ extern "C" __attribute__((visibility("default"))) int mvx_super_create(const mvx
     si.chroma = !!argdef(a->chroma, 1);
     si.sharp = argdef(a->sharp, 2);
     si.rfilter = argdef(a->rfilter, 2);
-#define SFAIL(msg) do { snprintf(err, MVX_ERRLEN, "%s", msg); mvx_set_error("%s", msg); return MVX_E_ARG; } while (0)
-    if (si.pel != 1 && si.pel != 2 && si.pel != 4) SFAIL("Super: pel must be 1, 2, or 4.");
-    if (si.sharp < 0 || si.sharp > 2) SFAIL("Super: sharp must be between 0 and 2 (inclusive).");
-    if (si.rfilter < 0 || si.rfilter > 4) SFAIL("Super: rfilter must be between 0 and 4 (inclusive).");
+    if (si.pel != 1 && si.pel != 2 && si.pel != 4) MVX_FAIL("Super: pel must be 1, 2, or 4.");
+    if (si.sharp < 0 || si.sharp > 2) MVX_FAIL("Super: sharp must be between 0 and 2 (inclusive).");
+    if (si.rfilter < 0 || si.rfilter > 4) MVX_FAIL("Super: rfilter must be between 0 and 4 (inclusive).");
     if (a->bits < 8 || a->bits > 16 || a->subsampling_w < 0 || a->subsampling_w > 1 || a->subsampling_h < 0 || a->subsampling_h > 1 ||
         a->width <= 0 || a->height <= 0)
-        SFAIL("Super: input clip must be GRAY, 420, 422, 440, or 444, up to 16 bits, with constant dimensions.");
-    if (si.hpad < 0 || si.vpad < 0) SFAIL("Super: hpad and vpad must not be negative.");
+        MVX_FAIL("Super: input clip must be GRAY, 420, 422, 440, or 444, up to 16 bits, with constant dimensions.");
+    if (si.hpad < 0 || si.vpad < 0) MVX_FAIL("Super: hpad and vpad must not be negative.");
     si.width = a->width; si.height = a->height; si.bits = a->bits; si.gray = !!a->gray;
     if (si.gray) si.chroma = 0;
     si.modeYUV = si.chroma ? 7 : 1;
@@ -86,7 +82,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_super_create(const mvx
            mvx_plane_width_luma(si.width, nLevelsMax, si.xRatioUV, si.hpad) >= si.xRatioUV * 2)
         nLevelsMax++;
     if (si.levels <= 0 || si.levels > nLevelsMax) si.levels = nLevelsMax;
-    if (si.levels > MVX_MAX_LEVELS) SFAIL("Super: too many levels.");
+    if (si.levels > MVX_MAX_LEVELS) MVX_FAIL("Super: too many levels.");
     si.super_width = si.width + 2 * si.hpad; // :257-264
     si.super_height = mvx_plane_super_offset(0, si.height, si.levels, si.pel, si.vpad, si.super_width, si.yRatioUV) / si.super_width;
     if (si.yRatioUV == 2 && (si.super_height & 1)) si.super_height++;
@@ -100,7 +96,6 @@ extern "C" __attribute__((visibility("default"))) int mvx_super_create(const mvx
     s->info = si;
     *out = s;
     return MVX_OK;
-#undef SFAIL
 }
 
 extern "C" __attribute__((visibility("default"))) void mvx_super_destroy(mvx_super *s) { delete s; }
