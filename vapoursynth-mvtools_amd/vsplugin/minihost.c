@@ -12,6 +12,8 @@
  *   mvx_vs_host <plugin.so> error  <Filter> <w> <h> <bits> [f.key=value ...]       -> prints the creation error (or OK)
  *   mvx_vs_host <plugin.so> run <pipeline> <in.raw> <w> <h> <bits> <nframes> <out.raw> [s.|a.|d.|c.key=value ...]
  *       pipeline: super | finest | analyse | scdetection (d.*) | recalculate (r.*) | degrainN | compensate | blockfps (b.*)
+ *                 | flowinter | flowfps | flow | flowblur | mask (f.*; the plugin registers these with MVX_VS_FLOW=1): on the vector pair of delta 1, or
+ *                 of x.delta=N; flow and mask take the backward clip as `vectors`, x.vectors=fw the forward one
  *       in.raw  : nframes x (Y, U, V planes, 4:2:0, tightly packed, little endian); x.format=422 | 444 | gray (one plane): other chroma formats
  *       out.raw : super      -> every super frame (planes tightly packed) ; props of frame 0 on stdout
  *                 analyse    -> per frame: 84-byte MVTools_MVAnalysisData + MVTools_vectors, backward (isb=1) then forward
@@ -196,6 +198,14 @@ static uint8_t *VS_CC getWritePtr(VSFrame *f, int p) {
     return f->data[p];
 }
 static const VSVideoFormat *VS_CC getVideoFrameFormat(const VSFrame *f) { return &f->fmt; }
+static int VS_CC queryVideoFormat(VSVideoFormat *fmt, int colorFamily, int sampleType, int bits, int ssw, int ssh, VSCore *core) { /* integer Gray / YUV of 8..16 bits, like the source clips */
+    (void)core;
+    if ((colorFamily != cfGray && colorFamily != cfYUV) || sampleType != stInteger || bits < 8 || bits > 16 || ssw < 0 || ssw > 4 || ssh < 0 || ssh > 4) return 0;
+    if (colorFamily == cfGray && (ssw || ssh)) return 0;
+    fmt->colorFamily = colorFamily; fmt->sampleType = sampleType; fmt->bitsPerSample = bits; fmt->bytesPerSample = bits > 8 ? 2 : 1;
+    fmt->subSamplingW = ssw; fmt->subSamplingH = ssh; fmt->numPlanes = colorFamily == cfGray ? 1 : 3;
+    return 1;
+}
 static int VS_CC getFrameWidth(const VSFrame *f, int p) { return plane_w(f, p); }
 static int VS_CC getFrameHeight(const VSFrame *f, int p) { return plane_h(f, p); }
 
@@ -369,7 +379,7 @@ static void init_api(void) {
     g_api.createVideoFilter = createVideoFilter; g_api.freeNode = freeNode; g_api.addNodeRef = addNodeRef; g_api.getVideoInfo = getVideoInfo;
     g_api.newVideoFrame = newVideoFrame; g_api.freeFrame = freeFrame; g_api.copyFrame = copyFrame;
     g_api.getFramePropertiesRO = getFramePropertiesRO; g_api.getFramePropertiesRW = getFramePropertiesRW;
-    g_api.getStride = getStride; g_api.getReadPtr = getReadPtr; g_api.getWritePtr = getWritePtr; g_api.getVideoFrameFormat = getVideoFrameFormat;
+    g_api.getStride = getStride; g_api.getReadPtr = getReadPtr; g_api.getWritePtr = getWritePtr; g_api.getVideoFrameFormat = getVideoFrameFormat; g_api.queryVideoFormat = queryVideoFormat;
     g_api.getFrameWidth = getFrameWidth; g_api.getFrameHeight = getFrameHeight;
     g_api.getFrame = getFrame; g_api.getFrameFilter = getFrameFilter; g_api.requestFrameFilter = requestFrameFilter; g_api.setFilterError = setFilterError;
     g_api.createMap = createMap; g_api.freeMap = freeMap; g_api.clearMap = clearMap; g_api.mapSetError = mapSetError; g_api.mapGetError = mapGetError;
@@ -512,6 +522,7 @@ int main(int argc, char **argv) {
     if (!strcmp(argv[2], "error")) { /* error <Filter> w h bits [f.key=value] : creation-time behaviour on a blank clip */
         const char *filter = argv[3];
         const int w = atoi(argv[4]), hh = atoi(argv[5]), bits = atoi(argv[6]);
+        format_from_args(argc - 7, argv + 7);
         VSNode *clip = source_clip(NULL, w, hh, bits, 4);
         VSMap *m = createMap();
         VSNode *out = NULL;
@@ -534,9 +545,10 @@ int main(int argc, char **argv) {
                 mapSetInt(a1, "isb", 1, maReplace); mapSetInt(a2, "isb", 0, maReplace);
                 VSNode *bw = invoke("Analyse", a1, err, sizeof(err)); if (!bw) die("Analyse", err);
                 VSNode *fw = invoke("Analyse", a2, err, sizeof(err)); if (!fw) die("Analyse", err);
-                mapSetNode(m, "clip", clip, maReplace); mapSetNode(m, "super", sup, maReplace);
+                mapSetNode(m, "clip", clip, maReplace);
+                if (strcmp(filter, "Mask")) mapSetNode(m, "super", sup, maReplace); /* (mv.Mask takes no super clip) */
                 add_args(m, 'f', argc - 7, argv + 7);
-                if (!strcmp(filter, "Compensate")) { mapSetNode(m, "vectors", bw, maReplace); out = invoke("Compensate", m, err, sizeof(err)); }
+                if (!strcmp(filter, "Compensate") || !strcmp(filter, "Flow") || !strcmp(filter, "Mask")) { mapSetNode(m, "vectors", bw, maReplace); out = invoke(filter, m, err, sizeof(err)); }
                 else if (!strcmp(filter, "Degrain1Swapped")) { mapSetNode(m, "mvbw", fw, maReplace); mapSetNode(m, "mvfw", bw, maReplace); out = invoke("Degrain1", m, err, sizeof(err)); }
                 else { mapSetNode(m, "mvbw", bw, maReplace); mapSetNode(m, "mvfw", fw, maReplace); out = invoke(filter, m, err, sizeof(err)); }
             }
@@ -580,18 +592,19 @@ int main(int argc, char **argv) {
         }
         fclose(fo); printf("DONE\n"); return 0;
     }
-    /* vector clips: delta 1..R, backward then forward */
-    int R = 1;
+    /* vector clips: delta 1..R (x.delta=N: N..N+R-1), backward then forward */
+    int R = 1, delta0 = 1;
+    for (int i = 0; i < nextra; i++) if (!strncmp(extra[i], "x.delta=", 8)) delta0 = atoi(extra[i] + 8);
     if (!strncmp(pipeline, "degrain", 7)) R = atoi(pipeline + 7);
     VSNode *vec[12];
     VSMap *amaps[12] = { NULL };
     for (int r = 0; r < R; r++)
         for (int isb = 1; isb >= 0; isb--) {
             VSMap *am = createMap(); mapSetNode(am, "super", sup, maReplace); add_args(am, 'a', nextra, extra);
-            mapSetInt(am, "isb", isb, maReplace); mapSetInt(am, "delta", r + 1, maReplace);
+            mapSetInt(am, "isb", isb, maReplace); mapSetInt(am, "delta", delta0 + r, maReplace);
             amaps[2 * r + (isb ? 0 : 1)] = am;
             vec[2 * r + (isb ? 0 : 1)] = invoke("Analyse", am, err, sizeof(err));
-            if (getenv("MVX_HOST_TIMES")) fprintf(stderr, "minihost: mv.Analyse delta %d isb %d created at %.2f s after start\n", r + 1, isb, now_s() - g_start);
+            if (getenv("MVX_HOST_TIMES")) fprintf(stderr, "minihost: mv.Analyse delta %d isb %d created at %.2f s after start\n", delta0 + r, isb, now_s() - g_start);
             if (!vec[2 * r + (isb ? 0 : 1)]) die("Analyse", err);
         }
     if (!strcmp(pipeline, "analyse")) {
@@ -666,7 +679,25 @@ int main(int argc, char **argv) {
         }
         fclose(fo); printf("DONE\n"); return 0;
     }
+    int outFrames = nframes, isFlowFps = 0; /* frames of the output clip */
+    static const struct { const char *pipeline, *filter; int pair; } flowFilters[] = { { "flowinter", "FlowInter", 1 }, { "flowfps", "FlowFPS", 1 }, { "flow", "Flow", 0 }, { "flowblur", "FlowBlur", 1 }, { "mask", "Mask", 0 } };
+    const char *flowFilter = NULL;
+    int flowPair = 0;
+    for (int i = 0; i < 5; i++) if (!strcmp(pipeline, flowFilters[i].pipeline)) { flowFilter = flowFilters[i].filter; flowPair = flowFilters[i].pair; }
     if (!strcmp(pipeline, "compensate")) { mapSetNode(m, "vectors", vec[0], maReplace); add_args(m, 'c', nextra, extra); out = invoke("Compensate", m, err, sizeof(err)); }
+    else if (flowFilter) { /* the per-sample filters (f.*): both vector clips, or one as `vectors` (x.vectors=fw: the forward one) */
+        int fwd = 0;
+        for (int i = 0; i < nextra; i++) if (!strcmp(extra[i], "x.vectors=fw")) fwd = 1;
+        if (!strcmp(flowFilter, "Mask")) { freeMap(m); m = createMap(); mapSetNode(m, "clip", clip, maReplace); } /* (mv.Mask takes no super clip) */
+        if (flowPair) { mapSetNode(m, "mvbw", vec[0], maReplace); mapSetNode(m, "mvfw", vec[1], maReplace); }
+        else mapSetNode(m, "vectors", vec[fwd], maReplace);
+        add_args(m, 'f', nextra, extra);
+        out = invoke(flowFilter, m, err, sizeof(err));
+        if (out && !strcmp(flowFilter, "FlowFPS")) {
+            isFlowFps = 1; outFrames = out->vi.numFrames;
+            printf("flowfps frames=%d fps=%lld/%lld\n", out->vi.numFrames, (long long)out->vi.fpsNum, (long long)out->vi.fpsDen);
+        }
+    }
     else {
         static const char *vn[] = { "mvbw", "mvfw", "mvbw2", "mvfw2", "mvbw3", "mvfw3", "mvbw4", "mvfw4", "mvbw5", "mvfw5", "mvbw6", "mvfw6" };
         for (int r = 0; r < 2 * R; r++) mapSetNode(m, vn[r], vec[r], maReplace);
@@ -682,19 +713,20 @@ int main(int argc, char **argv) {
     for (int i = 0; i < nextra; i++) if (!strcmp(extra[i], "x.order=frame")) frameOrder = 1;
     if (frameOrder) g_uncapped = out;
     if (threads > 1 && frameOrder) {
-        prefetch_parallel(threads, nframes, &out, 1);
+        prefetch_parallel(threads, outFrames, &out, 1);
         if (times) { fprintf(stderr, "minihost: output clip (frame order) %.2f s\n", now_s() - t0); t0 = now_s(); }
     } else if (threads > 1) { /* the vector clips first (all threads inside one Analyse instance at a time), then the output */
         prefetch_parallel(threads, nframes, vec, 2 * R < 4 ? 2 * R : 4);
         if (2 * R > 4) prefetch_parallel(threads, nframes, vec + 4, 2 * R - 4 < 4 ? 2 * R - 4 : 4);
         if (2 * R > 8) prefetch_parallel(threads, nframes, vec + 8, 2 * R - 8);
         if (times) { fprintf(stderr, "minihost: vector clips %.2f s\n", now_s() - t0); t0 = now_s(); }
-        prefetch_parallel(threads, nframes, &out, 1);
+        prefetch_parallel(threads, outFrames, &out, 1);
         if (times) { fprintf(stderr, "minihost: output clip %.2f s\n", now_s() - t0); t0 = now_s(); }
     }
-    for (int n = 0; n < nframes; n++) {
+    for (int n = 0; n < outFrames; n++) {
         const VSFrame *f = eval_frame(n, out, err, sizeof(err));
         if (!f) die("output frame", err);
+        if (isFlowFps && n == 1) { int e; printf("frame1 _DurationNum=%lld _DurationDen=%lld\n", (long long)mapGetInt(f->props, "_DurationNum", 0, &e), (long long)mapGetInt(f->props, "_DurationDen", 0, &e)); }
         dump_frame(fo, f); freeFrame(f);
     }
     fclose(fo);

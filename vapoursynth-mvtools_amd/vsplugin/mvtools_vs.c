@@ -6,6 +6,9 @@
  *     Super       (src/MVSuper.c:279-291)        Analyse   (src/MVAnalyse.c:639-671)
  *     Degrain1..6 (src/MVDegrains.cpp:813-932)   Compensate (src/MVCompensate.c:579-592)   BlockFPS (src/MVBlockFPS.c:1017-1033)
  *     Recalculate (src/MVRecalculate.c:549-572)   Finest (src/MVFinest.c:213-218)   SCDetection (src/MVSCDetection.c:137-145)
+ * and, when the host's environment has MVX_VS_FLOW=1 as the plugin is loaded, the per-sample filters
+ *     FlowInter (src/MVFlowInter.c:700-710)   FlowFPS (src/MVFlowFPS.c:913-925)   Flow (src/MVFlow.cpp:597-607)
+ *     FlowBlur  (src/MVFlowBlur.c:555-565)    Mask    (src/MVMask.c:350-360)
  * and keeps the reference's inter-filter data layout: super-frame geometry + Super_* props on frame 0
  * (src/MVSuper.c:111-120), vector clips = copyFrame(super[n]) + binary props MVTools_MVAnalysisData / MVTools_vectors
  * (src/MVAnalyse.c:224-239).  This file is the only code that touches VSAPI; all arithmetic happens on the GPU behind
@@ -2267,6 +2270,597 @@ static void VS_CC fpsCreate(const VSMap *in, VSMap *out, void *user, VSCore *cor
     vs->freeNode(node);
 }
 
+/* ------------------------------------------------------------------------------------------------ the per-sample filters: shared plumbing
+ * mv.FlowInter / mv.FlowFPS / mv.Flow / mv.FlowBlur / mv.Mask (registered with MVX_VS_FLOW=1, see the entry point).  Where the reference asks its
+ * mv.Finest node for a frame these filters ask the super clip: the library reads the sub-pel planes of the super frame directly (mvtools_amd.h), so
+ * no Finest node exists.  One mvx_*_frames call per output frame, on the thread's stream. */
+
+/* device pitches of clip and output planes: rows of 256 bytes */
+static void clip_pitches(ptrdiff_t pitch[3], const VSVideoInfo *vi, int bps) {
+    for (int p = 0; p < 3; p++) {
+        const int w = p ? vi->width >> vi->format.subSamplingW : vi->width;
+        pitch[p] = ((ptrdiff_t)w * bps + 255) / 256 * 256;
+    }
+}
+/* the clip check of MVFlowInter.c:644, MVFlowFPS.c:794, MVFlow.cpp:526, MVFlowBlur.c:514 */
+static int flow_clip_ok(const VSVideoInfo *vi) {
+    return mvx_vsh_is_constant_video_format(vi) && vi->format.bitsPerSample <= 16 && vi->format.sampleType == stInteger && vi->format.subSamplingW <= 1 &&
+           vi->format.subSamplingH <= 1 && (vi->format.colorFamily == cfYUV || vi->format.colorFamily == cfGray);
+}
+/* The kernels address the clip's planes with the vector clip's geometry, which creation ties to the super clip's: a clip of another size or format
+ * than the one the super clip was made from would be read outside its planes.  (The reference does not check this.) */
+static int flow_clip_is_supers(const VSVideoInfo *vi, const VSVideoInfo *svi, const SuperGeo *g) {
+    return g->si.width == vi->width && g->si.height == vi->height && vi->format.bitsPerSample == svi->format.bitsPerSample && vi->format.colorFamily == svi->format.colorFamily &&
+           vi->format.subSamplingW == svi->format.subSamplingW && vi->format.subSamplingH == svi->format.subSamplingH;
+}
+/* one arena for the planes of an output frame */
+static int dst_plane_set(void *dst[3], void **arena, const ptrdiff_t pitch[3], const int height[3], int nplanes) {
+    size_t off[3], total = 0;
+    for (int p = 0; p < nplanes; p++) { off[p] = total; total += (size_t)pitch[p] * (size_t)height[p]; }
+    for (int p = 0; p < 3; p++) dst[p] = NULL;
+    *arena = shell_alloc(total);
+    if (!*arena) return MVX_E_NOMEM;
+    for (int p = 0; p < nplanes; p++) dst[p] = (char *)*arena + off[p];
+    return 0;
+}
+/* the finished planes -> the host frame; complete on return */
+static int download_plane_set(VSFrame *dst, void *const src[3], const ptrdiff_t pitch[3], int nplanes, int bps, const VSAPI *vs) {
+    int rc = 0;
+    for (int p = 0; p < nplanes && !rc; p++)
+        rc = timed_download(vs->getWritePtr(dst, p), vs->getStride(dst, p), src[p], pitch[p], (size_t)vs->getFrameWidth(dst, p) * bps, (size_t)vs->getFrameHeight(dst, p));
+    if (!rc) rc = mvx_stream_sync(thread_stream());
+    return rc;
+}
+static void flow_frame_error(const char *name, int rc, VSFrameContext *ctx, const VSAPI *vs) {
+    char msg[96];
+    if (rc != MVX_E_ARG && rc != MVX_E_NOMEM) { vs->setFilterError(mvx_last_error(), ctx); return; }
+    snprintf(msg, sizeof(msg), "%s: %s", name, rc == MVX_E_ARG ? "vector clip frame without matching MVTools_vectors property." : "out of memory.");
+    vs->setFilterError(msg, ctx);
+}
+static double opt_float(const VSMap *in, const char *key, double def, const VSAPI *vs) {
+    int e = 0;
+    const double v = vs->mapGetFloat(in, key, 0, &e);
+    return e ? def : v;
+}
+/* MVTools_vectors of frame n of a vector clip -> device; 0 or an MVX_E_* code */
+static int clip_blob_to_device(void **dblob, int n, VSNode *vectors, const mvx_analysis_data *ad, VSFrameContext *ctx, const VSAPI *vs) {
+    const VSFrame *vf = vs->getFrameFilter(n, vectors, ctx);
+    const int rc = blob_to_device(dblob, NULL, ad, vf, vs);
+    vs->freeFrame(vf);
+    return rc;
+}
+static int clip_super_to_device(DevRef *r, int n, VSNode *super, const SuperGeo *g, VSFrameContext *ctx, const VSAPI *vs) {
+    const VSFrame *sf = vs->getFrameFilter(n, super, ctx);
+    const int rc = super_to_device(r, sf, g, vs);
+    vs->freeFrame(sf);
+    return rc;
+}
+
+/* ------------------------------------------------------------------------------------------------ mv.FlowInter / mv.FlowFPS (one engine, one shell) */
+
+typedef struct FlowData { VSNode *node, *super, *mvbw, *mvfw; const VSVideoInfo *oldvi; VSVideoInfo vi; mvx_super *sup; SuperGeo geo; mvx_flow *fl;
+                          mvx_analysis_data bw, fw; ptrdiff_t pitch[3]; int fps /* FlowFPS, else FlowInter */, extra /* the Extra formula's second pair of vectors is read */;
+                          const char *name; Gate gate; } FlowData;
+
+static const VSFrame *VS_CC flowGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    (void)fd;
+    FlowData *d = (FlowData *)inst;
+    int nleft, nright, time256;
+    mvx_flow_map(d->fl, n, &nleft, &nright, &time256);
+    const int last = d->oldvi->numFrames - 1;
+    const int good = nleft <= last && nright <= last;
+    const int ncl = fps_min(nleft, last), ncr = fps_min(nright, last);
+    const int copies = d->fps && (time256 == 0 || time256 == 256); /* MVFlowFPS.c:101-107,138-142; FlowInter has no such shortcut */
+    if (reason == arInitial) { /* src/MVFlowInter.c:86-102, src/MVFlowFPS.c:92-124 */
+        if (copies) { vs->requestFrameFilter(time256 ? ncr : ncl, d->node, ctx); return NULL; }
+        if (good) {
+            if (d->extra) vs->requestFrameFilter(nleft, d->mvfw, ctx);
+            vs->requestFrameFilter(nright, d->mvfw, ctx);
+            vs->requestFrameFilter(nleft, d->mvbw, ctx);
+            if (d->extra) vs->requestFrameFilter(nright, d->mvbw, ctx);
+            vs->requestFrameFilter(nleft, d->super, ctx);
+            vs->requestFrameFilter(nright, d->super, ctx);
+        }
+        vs->requestFrameFilter(ncl, d->node, ctx);
+        vs->requestFrameFilter(ncr, d->node, ctx); /* FlowFPS only asks for it when blend=1; harmless */
+        return NULL;
+    }
+    if (reason != arAllFramesReady) return NULL;
+    if (copies) return vs->getFrameFilter(time256 ? ncr : ncl, d->node, ctx); /* simply left / right */
+    const VSFrame *cl = vs->getFrameFilter(ncl, d->node, ctx);
+    const VSFrame *cr = vs->getFrameFilter(ncr, d->node, ctx);
+    const int np = d->vi.format.numPlanes, bps = d->vi.format.bytesPerSample;
+    mvx_flow_job job;
+    memset(&job, 0, sizeof(job));
+    job.time256 = time256;
+    void *arenaL = NULL, *arenaR = NULL, *dstArena = NULL, *dl[3], *dr[3], *ddst[3], *blob[4] = { NULL, NULL, NULL, NULL };
+    int height[3] = { 0, 0, 0 };
+    for (int p = 0; p < np; p++) height[p] = vs->getFrameHeight(cl, p);
+    int rc = upload_plane_set(dl, &arenaL, cl, d->pitch, np, bps, vs);
+    if (!rc) rc = upload_plane_set(dr, &arenaR, cr, d->pitch, np, bps, vs);
+    if (!rc) rc = dst_plane_set(ddst, &dstArena, d->pitch, height, np);
+    for (int p = 0; p < np && !rc; p++) { job.clip_left[p] = dl[p]; job.clip_right[p] = dr[p]; job.dst[p] = ddst[p]; }
+    DevRef sl, sr;
+    memset(&sl, 0, sizeof(sl)); memset(&sr, 0, sizeof(sr));
+    if (!rc && good) { /* (else all four stay NULL: Blend or the left frame) */
+        rc = clip_super_to_device(&sl, nleft, d->super, &d->geo, ctx, vs);
+        if (!rc) rc = clip_super_to_device(&sr, nright, d->super, &d->geo, ctx, vs);
+        if (!rc) rc = clip_blob_to_device(&blob[0], nright, d->mvfw, &d->fw, ctx, vs);
+        if (!rc) rc = clip_blob_to_device(&blob[1], nleft, d->mvbw, &d->bw, ctx, vs);
+        if (!rc && d->extra) rc = clip_blob_to_device(&blob[2], nleft, d->mvfw, &d->fw, ctx, vs);
+        if (!rc && d->extra) rc = clip_blob_to_device(&blob[3], nright, d->mvbw, &d->bw, ctx, vs);
+        for (int p = 0; p < 3; p++) { job.super_left[p] = sl.plane[p]; job.super_right[p] = sr.plane[p]; }
+        job.blob_fw = blob[0]; job.blob_bw = blob[1]; job.blob_fw_extra = blob[2]; job.blob_bw_extra = blob[3];
+    }
+    if (!rc) rc = mvx_flow_frames(d->fl, 1, &job, thread_stream());
+    VSFrame *dst = NULL;
+    if (!rc) {
+        dst = vs->newVideoFrame(&d->vi.format, d->vi.width, d->vi.height, cl, core);
+        rc = download_plane_set(dst, ddst, d->pitch, np, bps, vs);
+    }
+    shell_quiesce(rc);
+    dev_release(&sl); dev_release(&sr);
+    for (int i = 0; i < 4; i++) if (blob[i]) mvx_dev_free(blob[i]);
+    if (arenaL) mvx_dev_free(arenaL);
+    if (arenaR) mvx_dev_free(arenaR);
+    if (dstArena) mvx_dev_free(dstArena);
+    vs->freeFrame(cl); vs->freeFrame(cr);
+    if (rc) {
+        if (dst) vs->freeFrame(dst);
+        flow_frame_error(d->name, rc, ctx, vs);
+        return NULL;
+    }
+    return dst;
+}
+
+/* (the admission gate around the filter proper: arInitial takes the permit, whatever ends the request -- the frame, a filter error, arError -- returns it) */
+static const VSFrame *VS_CC flowGetFrame(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    FlowData *d = (FlowData *)inst;
+    if (reason == arInitial) gate_enter(&d->gate, n, fd);
+    const VSFrame *f = flowGetFrameUngated(n, reason, inst, fd, ctx, core, vs);
+    if (reason != arInitial || f) gate_leave(&d->gate, fd);
+    return f;
+}
+
+static void VS_CC flowFree(void *inst, VSCore *core, const VSAPI *vs) {
+    (void)core;
+    FlowData *d = (FlowData *)inst;
+    vs->freeNode(d->node); vs->freeNode(d->super); vs->freeNode(d->mvbw); vs->freeNode(d->mvfw);
+    mvx_flow_destroy(d->fl);
+    mvx_super_destroy(d->sup);
+    gate_free(&d->gate);
+    free(d);
+}
+
+/* user != NULL: mv.FlowFPS (src/MVFlowFPS.c:565-900), else mv.FlowInter (src/MVFlowInter.c:473-678) */
+static void VS_CC flowCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
+    warm_barrier();
+    FlowData *d = (FlowData *)calloc(1, sizeof(*d));
+    gate_init(&d->gate);
+    d->fps = user != NULL;
+    d->name = d->fps ? "FlowFPS" : "FlowInter";
+    char err[1400] = "";
+    mvx_flowinter_args ai;
+    mvx_flowfps_args af;
+    ai.time = opt_float(in, "time", 50.0, vs); ai.ml = af.ml = opt_float(in, "ml", 100.0, vs);
+    ai.blend = af.blend = opt_int(in, "blend", vs);
+    ai.thscd1 = af.thscd1 = opt_int64(in, "thscd1", vs); ai.thscd2 = af.thscd2 = opt_int(in, "thscd2", vs);
+    af.num = opt_int64(in, "num", vs); af.den = opt_int64(in, "den", vs); af.mask = opt_int(in, "mask", vs);
+    d->extra = d->fps ? (af.mask == MVX_UNSET || af.mask == 2) : 1;
+    d->super = vs->mapGetNode(in, "super", 0, NULL);
+    d->sup = super_from_props(d->super, d->name, err, sizeof(err), vs);
+    if (!err[0]) { d->mvbw = vs->mapGetNode(in, "mvbw", 0, NULL); adata_from_clip(&d->bw, d->mvbw, d->name, "mvbw", err, sizeof(err), vs); }
+    if (!err[0]) { d->mvfw = vs->mapGetNode(in, "mvfw", 0, NULL); adata_from_clip(&d->fw, d->mvfw, d->name, "mvfw", err, sizeof(err), vs); }
+    if (!err[0]) {
+        d->node = vs->mapGetNode(in, "clip", 0, NULL);
+        d->oldvi = vs->getVideoInfo(d->node);
+        d->vi = *d->oldvi;
+        super_geo(&d->geo, d->sup);
+        clip_pitches(d->pitch, &d->vi, d->vi.format.bytesPerSample);
+        char lerr[MVX_ERRLEN];
+        const int rc = d->fps ? mvx_flowfps_create(&af, &d->bw, &d->fw, d->sup, d->oldvi->numFrames, d->oldvi->fpsNum, d->oldvi->fpsDen, d->geo.pitch, d->pitch, d->pitch, &d->fl, lerr)
+                              : mvx_flowinter_create(&ai, &d->bw, &d->fw, d->sup, d->oldvi->numFrames, d->geo.pitch, d->pitch, d->pitch, &d->fl, lerr);
+        if (rc) snprintf(err, sizeof(err), "%s", lerr);
+        else if (!flow_clip_ok(&d->vi)) snprintf(err, sizeof(err), "%s: input clip must be GRAY, 420, 422, 440, or 444, up to 16 bits, with constant dimensions.", d->name);
+        else if (!flow_clip_is_supers(&d->vi, vs->getVideoInfo(d->super), &d->geo)) snprintf(err, sizeof(err), "%s: wrong source or super clip frame size.", d->name);
+    }
+    if (err[0]) {
+        vs->mapSetError(out, err);
+        if (d->node) vs->freeNode(d->node);
+        if (d->super) vs->freeNode(d->super);
+        if (d->mvbw) vs->freeNode(d->mvbw);
+        if (d->mvfw) vs->freeNode(d->mvfw);
+        if (d->fl) mvx_flow_destroy(d->fl);
+        if (d->sup) mvx_super_destroy(d->sup);
+        free(d);
+        return;
+    }
+    VSFilterDependency deps[4] = { { d->node, rpGeneral }, { d->super, rpGeneral }, { d->mvbw, rpGeneral }, { d->mvfw, rpGeneral } };
+    if (!d->fps) { /* the output clip is the input's */
+        vs->createVideoFilter(out, d->name, &d->vi, flowGetFrame, flowFree, fmParallel, deps, 4, d, core);
+        return;
+    }
+    mvx_flow_info info;
+    mvx_flow_get_info(d->fl, &info);
+    d->vi.numFrames = info.num_frames; d->vi.fpsNum = info.fps_num; d->vi.fpsDen = info.fps_den;
+    vs->createVideoFilter(out, d->name, &d->vi, flowGetFrame, flowFree, fmParallel, deps, 4, d, core);
+    /* AssumeFPS sets the _DurationNum / _DurationDen frame properties (src/MVFlowFPS.c:881-900) */
+    VSNode *node = vs->mapGetNode(out, "clip", 0, NULL);
+    VSMap *args = vs->createMap();
+    vs->mapSetNode(args, "clip", node, maReplace);
+    vs->freeNode(node);
+    vs->mapSetInt(args, "fpsnum", info.fps_num, maReplace);
+    vs->mapSetInt(args, "fpsden", info.fps_den, maReplace);
+    VSPlugin *std = vs->getPluginByID("com.vapoursynth.std", core);
+    VSMap *ret = vs->invoke(std, "AssumeFPS", args);
+    vs->freeMap(args);
+    if (vs->mapGetError(ret)) {
+        char msg[600];
+        snprintf(msg, sizeof(msg), "FlowFPS: Failed to invoke AssumeFPS. Error message: %s", vs->mapGetError(ret));
+        vs->mapSetError(out, msg);
+        vs->freeMap(ret);
+        return;
+    }
+    node = vs->mapGetNode(ret, "clip", 0, NULL);
+    vs->freeMap(ret);
+    vs->mapSetNode(out, "clip", node, maReplace);
+    vs->freeNode(node);
+}
+
+/* ------------------------------------------------------------------------------------------------ mv.Flow */
+
+typedef struct FlowCompData { VSNode *node, *super, *vectors; const VSVideoInfo *vi; mvx_super *sup; SuperGeo geo; mvx_flowcomp *fc; mvx_analysis_data ad; ptrdiff_t pitch[3];
+                              FieldOpt fo; Gate gate; } FlowCompData;
+
+static const VSFrame *VS_CC flowCompGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    (void)fd;
+    FlowCompData *d = (FlowCompData *)inst;
+    const int nref = mvx_flowcomp_ref(d->fc, n);
+    const int haveRef = nref >= 0 && nref < d->vi->numFrames;
+    /* the parities of frames n and nref decide the field shift (src/MVFlow.cpp:264-297): only then is super frame n needed at all -- the reference always asks
+     * for Finest frame n and reads nothing else from it */
+    const int parity = haveRef && d->fo.fields && d->ad.nPel > 1 && ((nref - n) % 2 != 0);
+    if (reason == arInitial) { /* src/MVFlow.cpp:170-192 */
+        vs->requestFrameFilter(n, d->vectors, ctx);
+        if (haveRef) {
+            if (nref < n) vs->requestFrameFilter(nref, d->super, ctx);
+            if (parity) vs->requestFrameFilter(n, d->super, ctx);
+            if (nref >= n) vs->requestFrameFilter(nref, d->super, ctx);
+        }
+        vs->requestFrameFilter(n, d->node, ctx);
+        return NULL;
+    }
+    if (reason != arAllFramesReady) return NULL;
+    const VSFrame *src = vs->getFrameFilter(n, d->node, ctx);
+    const VSFrame *rsup = haveRef ? vs->getFrameFilter(nref, d->super, ctx) : NULL;
+    const int np = d->vi->format.numPlanes, bps = d->vi->format.bytesPerSample;
+    int fieldShift = 0;
+    if (parity) { /* (as mv.Compensate here: usability is decided on the device, so a missing _Field is reported for scene-change frames too) */
+        const VSFrame *ssup = vs->getFrameFilter(n, d->super, ctx);
+        int missing = 0;
+        const int srcTop = frame_top_field(&d->fo, ssup, n, &missing, vs);
+        const int refTop = frame_top_field(&d->fo, rsup, nref, &missing, vs);
+        vs->freeFrame(ssup);
+        if (missing) {
+            vs->setFilterError("Flow: _Field property not found in super frame. Therefore, you must pass tff argument.", ctx);
+            vs->freeFrame(rsup); vs->freeFrame(src);
+            return NULL;
+        }
+        fieldShift = field_shift_of(srcTop, refTop, d->ad.nPel);
+    }
+    mvx_flowcomp_job job;
+    memset(&job, 0, sizeof(job));
+    job.field_shift = fieldShift;
+    void *srcArena = NULL, *dstArena = NULL, *dsrc[3], *ddst[3], *dblob = NULL;
+    int height[3] = { 0, 0, 0 };
+    for (int p = 0; p < np; p++) height[p] = vs->getFrameHeight(src, p);
+    int rc = upload_plane_set(dsrc, &srcArena, src, d->pitch, np, bps, vs);
+    if (!rc) rc = dst_plane_set(ddst, &dstArena, d->pitch, height, np);
+    for (int p = 0; p < np && !rc; p++) { job.clip[p] = dsrc[p]; job.dst[p] = ddst[p]; }
+    DevRef dr;
+    memset(&dr, 0, sizeof(dr));
+    if (!rc && rsup) rc = super_to_device(&dr, rsup, &d->geo, vs);
+    if (!rc) rc = clip_blob_to_device(&dblob, n, d->vectors, &d->ad, ctx, vs);
+    for (int p = 0; p < 3; p++) job.ref_super[p] = rsup ? dr.plane[p] : NULL; /* NULL: copy of the clip frame */
+    job.blob = dblob;
+    if (!rc) rc = mvx_flowcomp_frames(d->fc, 1, &job, thread_stream());
+    VSFrame *dst = NULL;
+    if (!rc) {
+        dst = vs->newVideoFrame(&d->vi->format, d->vi->width, d->vi->height, src, core);
+        rc = download_plane_set(dst, ddst, d->pitch, np, bps, vs);
+    }
+    shell_quiesce(rc);
+    dev_release(&dr);
+    if (dblob) mvx_dev_free(dblob);
+    if (srcArena) mvx_dev_free(srcArena);
+    if (dstArena) mvx_dev_free(dstArena);
+    if (rsup) vs->freeFrame(rsup);
+    vs->freeFrame(src);
+    if (rc) {
+        if (dst) vs->freeFrame(dst);
+        flow_frame_error("Flow", rc, ctx, vs);
+        return NULL;
+    }
+    return dst;
+}
+
+/* (the admission gate around the filter proper, as flowGetFrame) */
+static const VSFrame *VS_CC flowCompGetFrame(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    FlowCompData *d = (FlowCompData *)inst;
+    if (reason == arInitial) gate_enter(&d->gate, n, fd);
+    const VSFrame *f = flowCompGetFrameUngated(n, reason, inst, fd, ctx, core, vs);
+    if (reason != arInitial || f) gate_leave(&d->gate, fd);
+    return f;
+}
+
+static void VS_CC flowCompFree(void *inst, VSCore *core, const VSAPI *vs) {
+    (void)core;
+    FlowCompData *d = (FlowCompData *)inst;
+    vs->freeNode(d->node); vs->freeNode(d->super); vs->freeNode(d->vectors);
+    mvx_flowcomp_destroy(d->fc);
+    mvx_super_destroy(d->sup);
+    gate_free(&d->gate);
+    free(d);
+}
+
+/* src/MVFlow.cpp:391-593 (fields=1 with pel=1 is accepted there and shifts nothing: :265) */
+static void VS_CC flowCompCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
+    warm_barrier();
+    (void)user;
+    FlowCompData *d = (FlowCompData *)calloc(1, sizeof(*d));
+    gate_init(&d->gate);
+    char err[1400] = "";
+    mvx_flowcomp_args a;
+    a.time = opt_float(in, "time", 100.0, vs); a.mode = opt_int(in, "mode", vs);
+    a.thscd1 = opt_int64(in, "thscd1", vs); a.thscd2 = opt_int(in, "thscd2", vs);
+    field_opt(&d->fo, in, vs);
+    a.fields = d->fo.fields;
+    d->super = vs->mapGetNode(in, "super", 0, NULL);
+    d->sup = super_from_props(d->super, "Flow", err, sizeof(err), vs);
+    if (!err[0]) { d->vectors = vs->mapGetNode(in, "vectors", 0, NULL); adata_from_clip(&d->ad, d->vectors, "Flow", "vectors", err, sizeof(err), vs); }
+    if (!err[0]) {
+        d->node = vs->mapGetNode(in, "clip", 0, NULL);
+        d->vi = vs->getVideoInfo(d->node);
+        super_geo(&d->geo, d->sup);
+        clip_pitches(d->pitch, d->vi, d->vi->format.bytesPerSample);
+        char lerr[MVX_ERRLEN];
+        if (mvx_flowcomp_create(&a, &d->ad, d->sup, d->vi->numFrames, d->geo.pitch, d->pitch, d->pitch, &d->fc, lerr)) snprintf(err, sizeof(err), "%s", lerr);
+        else if (!flow_clip_ok(d->vi)) snprintf(err, sizeof(err), "Flow: input clip must be GRAY, 420, 422, 440, or 444, up to 16 bits, with constant dimensions.");
+        else if (!flow_clip_is_supers(d->vi, vs->getVideoInfo(d->super), &d->geo)) snprintf(err, sizeof(err), "Flow: wrong source or super clip frame size.");
+    }
+    if (err[0]) {
+        vs->mapSetError(out, err);
+        if (d->node) vs->freeNode(d->node);
+        if (d->super) vs->freeNode(d->super);
+        if (d->vectors) vs->freeNode(d->vectors);
+        if (d->fc) mvx_flowcomp_destroy(d->fc);
+        if (d->sup) mvx_super_destroy(d->sup);
+        free(d);
+        return;
+    }
+    VSFilterDependency deps[3] = { { d->node, rpStrictSpatial }, { d->super, rpGeneral }, { d->vectors, rpStrictSpatial } };
+    vs->createVideoFilter(out, "Flow", d->vi, flowCompGetFrame, flowCompFree, fmParallel, deps, 3, d, core);
+}
+
+/* ------------------------------------------------------------------------------------------------ mv.FlowBlur */
+
+typedef struct BlurData { VSNode *node, *super, *mvbw, *mvfw; const VSVideoInfo *vi; mvx_super *sup; SuperGeo geo; mvx_flowblur *fb; mvx_analysis_data bw, fw; ptrdiff_t pitch[3];
+                          Gate gate; } BlurData;
+
+static const VSFrame *VS_CC blurGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    (void)fd;
+    BlurData *d = (BlurData *)inst;
+    const int off = d->bw.nDeltaFrame;
+    const int both = n - off >= 0 && n + off < d->vi->numFrames;
+    if (reason == arInitial) { /* src/MVFlowBlur.c:148-157 */
+        if (both) {
+            vs->requestFrameFilter(n - off, d->mvbw, ctx);
+            vs->requestFrameFilter(n + off, d->mvfw, ctx);
+        }
+        vs->requestFrameFilter(n, d->super, ctx);
+        vs->requestFrameFilter(n, d->node, ctx);
+        return NULL;
+    }
+    if (reason != arAllFramesReady) return NULL;
+    const VSFrame *src = vs->getFrameFilter(n, d->node, ctx);
+    const int np = d->vi->format.numPlanes, bps = d->vi->format.bytesPerSample;
+    mvx_flowblur_job job;
+    memset(&job, 0, sizeof(job));
+    void *srcArena = NULL, *dstArena = NULL, *dsrc[3], *ddst[3], *blobB = NULL, *blobF = NULL;
+    int height[3] = { 0, 0, 0 };
+    for (int p = 0; p < np; p++) height[p] = vs->getFrameHeight(src, p);
+    int rc = upload_plane_set(dsrc, &srcArena, src, d->pitch, np, bps, vs);
+    if (!rc) rc = dst_plane_set(ddst, &dstArena, d->pitch, height, np);
+    for (int p = 0; p < np && !rc; p++) { job.clip[p] = dsrc[p]; job.dst[p] = ddst[p]; }
+    DevRef ds;
+    memset(&ds, 0, sizeof(ds));
+    if (!rc) rc = clip_super_to_device(&ds, n, d->super, &d->geo, ctx, vs);
+    if (!rc && both) rc = clip_blob_to_device(&blobB, n - off, d->mvbw, &d->bw, ctx, vs);
+    if (!rc && both) rc = clip_blob_to_device(&blobF, n + off, d->mvfw, &d->fw, ctx, vs);
+    for (int p = 0; p < 3; p++) job.super[p] = ds.plane[p];
+    job.blob_bw = blobB; job.blob_fw = blobF; /* both NULL: copy of the clip frame */
+    if (!rc) rc = mvx_flowblur_frames(d->fb, 1, &job, thread_stream());
+    VSFrame *dst = NULL;
+    if (!rc) {
+        dst = vs->newVideoFrame(&d->vi->format, d->vi->width, d->vi->height, src, core);
+        rc = download_plane_set(dst, ddst, d->pitch, np, bps, vs);
+    }
+    shell_quiesce(rc);
+    dev_release(&ds);
+    if (blobB) mvx_dev_free(blobB);
+    if (blobF) mvx_dev_free(blobF);
+    if (srcArena) mvx_dev_free(srcArena);
+    if (dstArena) mvx_dev_free(dstArena);
+    vs->freeFrame(src);
+    if (rc) {
+        if (dst) vs->freeFrame(dst);
+        flow_frame_error("FlowBlur", rc, ctx, vs);
+        return NULL;
+    }
+    return dst;
+}
+
+/* (the admission gate around the filter proper, as flowGetFrame) */
+static const VSFrame *VS_CC blurGetFrame(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    BlurData *d = (BlurData *)inst;
+    if (reason == arInitial) gate_enter(&d->gate, n, fd);
+    const VSFrame *f = blurGetFrameUngated(n, reason, inst, fd, ctx, core, vs);
+    if (reason != arInitial || f) gate_leave(&d->gate, fd);
+    return f;
+}
+
+static void VS_CC blurFree(void *inst, VSCore *core, const VSAPI *vs) {
+    (void)core;
+    BlurData *d = (BlurData *)inst;
+    vs->freeNode(d->node); vs->freeNode(d->super); vs->freeNode(d->mvbw); vs->freeNode(d->mvfw);
+    mvx_flowblur_destroy(d->fb);
+    mvx_super_destroy(d->sup);
+    gate_free(&d->gate);
+    free(d);
+}
+
+/* src/MVFlowBlur.c:346-552 */
+static void VS_CC blurCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
+    warm_barrier();
+    (void)user;
+    BlurData *d = (BlurData *)calloc(1, sizeof(*d));
+    gate_init(&d->gate);
+    char err[1400] = "";
+    mvx_flowblur_args a;
+    a.blur = opt_float(in, "blur", 50.0, vs); a.prec = opt_int(in, "prec", vs);
+    a.thscd1 = opt_int64(in, "thscd1", vs); a.thscd2 = opt_int(in, "thscd2", vs);
+    d->super = vs->mapGetNode(in, "super", 0, NULL);
+    d->sup = super_from_props(d->super, "FlowBlur", err, sizeof(err), vs);
+    if (!err[0]) { d->mvbw = vs->mapGetNode(in, "mvbw", 0, NULL); adata_from_clip(&d->bw, d->mvbw, "FlowBlur", "mvbw", err, sizeof(err), vs); }
+    if (!err[0]) { d->mvfw = vs->mapGetNode(in, "mvfw", 0, NULL); adata_from_clip(&d->fw, d->mvfw, "FlowBlur", "mvfw", err, sizeof(err), vs); }
+    if (!err[0]) {
+        d->node = vs->mapGetNode(in, "clip", 0, NULL);
+        d->vi = vs->getVideoInfo(d->node);
+        super_geo(&d->geo, d->sup);
+        clip_pitches(d->pitch, d->vi, d->vi->format.bytesPerSample);
+        char lerr[MVX_ERRLEN];
+        if (mvx_flowblur_create(&a, &d->bw, &d->fw, d->sup, d->vi->numFrames, d->geo.pitch, d->pitch, d->pitch, &d->fb, lerr)) snprintf(err, sizeof(err), "%s", lerr);
+        else if (!flow_clip_ok(d->vi)) snprintf(err, sizeof(err), "FlowBlur: input clip must be GRAY, 420, 422, 440, or 444, up to 16 bits, with constant dimensions.");
+        else if (!flow_clip_is_supers(d->vi, vs->getVideoInfo(d->super), &d->geo)) snprintf(err, sizeof(err), "FlowBlur: wrong source or super clip frame size.");
+    }
+    if (err[0]) {
+        vs->mapSetError(out, err);
+        if (d->node) vs->freeNode(d->node);
+        if (d->super) vs->freeNode(d->super);
+        if (d->mvbw) vs->freeNode(d->mvbw);
+        if (d->mvfw) vs->freeNode(d->mvfw);
+        if (d->fb) mvx_flowblur_destroy(d->fb);
+        if (d->sup) mvx_super_destroy(d->sup);
+        free(d);
+        return;
+    }
+    VSFilterDependency deps[4] = { { d->node, rpStrictSpatial }, { d->super, rpStrictSpatial }, { d->mvbw, rpGeneral }, { d->mvfw, rpGeneral } };
+    vs->createVideoFilter(out, "FlowBlur", d->vi, blurGetFrame, blurFree, fmParallel, deps, 4, d, core);
+}
+
+/* ------------------------------------------------------------------------------------------------ mv.Mask */
+
+typedef struct MaskData { VSNode *node, *vectors; const VSVideoInfo *clipvi; VSVideoInfo vi; mvx_mask *mk; mvx_mask_info info; mvx_analysis_data ad;
+                          ptrdiff_t pitch[3]; int kind; Gate gate; } MaskData;
+
+static const VSFrame *VS_CC maskGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    (void)fd;
+    MaskData *d = (MaskData *)inst;
+    if (reason == arInitial) { /* src/MVMask.c:80-82 */
+        vs->requestFrameFilter(n, d->vectors, ctx);
+        vs->requestFrameFilter(n, d->node, ctx);
+        return NULL;
+    }
+    if (reason != arAllFramesReady) return NULL;
+    const VSFrame *src = vs->getFrameFilter(n, d->node, ctx); /* the new frame's props; its luma is kind 5's plane 0 */
+    mvx_mask_job job;
+    memset(&job, 0, sizeof(job));
+    void *lumaArena = NULL, *dstArena = NULL, *dluma[3], *ddst[3], *dblob = NULL;
+    int rc = 0;
+    if (d->kind == 5) rc = upload_plane_set(dluma, &lumaArena, src, d->pitch, 1, 1, vs); /* (the clip is 8-bit: creation) */
+    if (!rc) rc = dst_plane_set(ddst, &dstArena, d->pitch, d->info.plane_height, 3);
+    if (!rc) rc = clip_blob_to_device(&dblob, n, d->vectors, &d->ad, ctx, vs);
+    for (int p = 0; p < 3 && !rc; p++) job.dst[p] = ddst[p];
+    job.blob = dblob;
+    job.clip_luma = d->kind == 5 && !rc ? dluma[0] : NULL;
+    if (!rc) rc = mvx_mask_frames(d->mk, 1, &job, thread_stream());
+    VSFrame *dst = NULL;
+    if (!rc) {
+        dst = vs->newVideoFrame(&d->vi.format, d->vi.width, d->vi.height, src, core);
+        rc = download_plane_set(dst, ddst, d->pitch, 3, 1, vs);
+    }
+    shell_quiesce(rc);
+    if (dblob) mvx_dev_free(dblob);
+    if (lumaArena) mvx_dev_free(lumaArena);
+    if (dstArena) mvx_dev_free(dstArena);
+    vs->freeFrame(src);
+    if (rc) {
+        if (dst) vs->freeFrame(dst);
+        flow_frame_error("Mask", rc, ctx, vs);
+        return NULL;
+    }
+    return dst;
+}
+
+/* (the admission gate around the filter proper, as flowGetFrame) */
+static const VSFrame *VS_CC maskGetFrame(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    MaskData *d = (MaskData *)inst;
+    if (reason == arInitial) gate_enter(&d->gate, n, fd);
+    const VSFrame *f = maskGetFrameUngated(n, reason, inst, fd, ctx, core, vs);
+    if (reason != arInitial || f) gate_leave(&d->gate, fd);
+    return f;
+}
+
+static void VS_CC maskFree(void *inst, VSCore *core, const VSAPI *vs) {
+    (void)core;
+    MaskData *d = (MaskData *)inst;
+    vs->freeNode(d->node); vs->freeNode(d->vectors);
+    mvx_mask_destroy(d->mk);
+    gate_free(&d->gate);
+    free(d);
+}
+
+/* src/MVMask.c:227-346 */
+static void VS_CC maskCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
+    warm_barrier();
+    (void)user;
+    MaskData *d = (MaskData *)calloc(1, sizeof(*d));
+    gate_init(&d->gate);
+    char err[1400] = "";
+    mvx_mask_args a;
+    a.ml = opt_float(in, "ml", 100.0, vs); a.gamma = opt_float(in, "gamma", 1.0, vs); a.kind = opt_int(in, "kind", vs); a.time = opt_float(in, "time", 100.0, vs);
+    a.ysc = opt_int(in, "ysc", vs); a.thscd1 = opt_int64(in, "thscd1", vs); a.thscd2 = opt_int(in, "thscd2", vs);
+    d->kind = a.kind == MVX_UNSET ? 0 : a.kind;
+    d->vectors = vs->mapGetNode(in, "vectors", 0, NULL);
+    adata_from_clip(&d->ad, d->vectors, "Mask", "vectors", err, sizeof(err), vs);
+    if (!err[0]) {
+        d->node = vs->mapGetNode(in, "clip", 0, NULL);
+        d->clipvi = vs->getVideoInfo(d->node);
+        d->vi = *d->clipvi;
+        const VSVideoFormat *f = &d->clipvi->format;
+        const mvx_mask_clip mc = { d->clipvi->width, d->clipvi->height, f->bitsPerSample, f->subSamplingW, f->subSamplingH, f->colorFamily == cfGray };
+        clip_pitches(d->pitch, d->clipvi, 1); /* of the clip's luma and of the mask's planes alike: 8-bit, the clip's subsampling (Gray: none, three full-size planes) */
+        char lerr[MVX_ERRLEN];
+        if (mvx_mask_create(&a, &d->ad, &mc, d->pitch, d->pitch, &d->mk, lerr)) snprintf(err, sizeof(err), "%s", lerr);
+        else if (!mvx_vsh_is_constant_video_format(d->clipvi) || f->sampleType != stInteger || (f->colorFamily != cfYUV && f->colorFamily != cfGray))
+            snprintf(err, sizeof(err), "Mask: input clip must be GRAY8, YUV420P8, YUV422P8, YUV440P8, or YUV444P8, with constant dimensions.");
+    }
+    if (!err[0]) { /* three 8-bit planes with the clip's subsampling; Gray -> 4:4:4 (src/MVMask.c:328-329) */
+        mvx_mask_get_info(d->mk, &d->info);
+        if (!vs->queryVideoFormat(&d->vi.format, cfYUV, stInteger, 8, d->info.subsampling_w, d->info.subsampling_h, core)) snprintf(err, sizeof(err), "Mask: the host has no 8-bit YUV format for the mask clip.");
+    }
+    if (err[0]) {
+        vs->mapSetError(out, err);
+        if (d->node) vs->freeNode(d->node);
+        if (d->vectors) vs->freeNode(d->vectors);
+        if (d->mk) mvx_mask_destroy(d->mk);
+        free(d);
+        return;
+    }
+    VSFilterDependency deps[2] = { { d->node, rpStrictSpatial }, { d->vectors, rpStrictSpatial } };
+    vs->createVideoFilter(out, "Mask", &d->vi, maskGetFrame, maskFree, fmParallel, deps, 2, d, core);
+}
+
 /* ------------------------------------------------------------------------------------------------ entry point */
 
 #define DEGRAIN_TAIL "thsad:int:opt;thsadc:int:opt;plane:int:opt;limit:int:opt;limitc:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;"
@@ -2321,4 +2915,22 @@ VS_EXTERNAL_API(void) VapourSynthPluginInit2(VSPlugin *plugin, const VSPLUGINAPI
     vspapi->registerFunction("Compensate",
                              "clip:vnode;super:vnode;vectors:vnode;scbehavior:int:opt;thsad:int:opt;fields:int:opt;time:float:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;tff:int:opt;",
                              "clip:vnode;", compCreate, NULL, plugin);
+    /* The per-sample filters are opt-in for now: MVX_VS_FLOW=1 in the host's environment when the plugin is loaded (read here, once).  Without it the
+     * plugin registers exactly the functions above.   */
+    if (!env_long("MVX_VS_FLOW", 0)) return;
+    vspapi->registerFunction("FlowInter",
+                             "clip:vnode;super:vnode;mvbw:vnode;mvfw:vnode;time:float:opt;ml:float:opt;blend:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;",
+                             "clip:vnode;", flowCreate, NULL, plugin);
+    vspapi->registerFunction("FlowFPS",
+                             "clip:vnode;super:vnode;mvbw:vnode;mvfw:vnode;num:int:opt;den:int:opt;mask:int:opt;ml:float:opt;blend:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;",
+                             "clip:vnode;", flowCreate, (void *)(intptr_t)1, plugin);
+    vspapi->registerFunction("Flow",
+                             "clip:vnode;super:vnode;vectors:vnode;time:float:opt;mode:int:opt;fields:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;tff:int:opt;",
+                             "clip:vnode;", flowCompCreate, NULL, plugin);
+    vspapi->registerFunction("FlowBlur",
+                             "clip:vnode;super:vnode;mvbw:vnode;mvfw:vnode;blur:float:opt;prec:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;",
+                             "clip:vnode;", blurCreate, NULL, plugin);
+    vspapi->registerFunction("Mask",
+                             "clip:vnode;vectors:vnode;ml:float:opt;gamma:float:opt;kind:int:opt;time:float:opt;ysc:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;",
+                             "clip:vnode;", maskCreate, NULL, plugin);
 }

@@ -8,7 +8,7 @@
  * only uses names that exist in the real header.  The in-repo mini host (minihost.c) shares this file, so the tests
  * are self-consistent either way.
  *
- * Only what the mvtools hot path uses is spelled out (27 VSAPI members + 2 VSPLUGINAPI members); the
+ * Only what the mvtools hot path uses is spelled out (27 VSAPI members + 2 VSPLUGINAPI members; queryVideoFormat for mv.Mask's output format); the
  * other slots are kept as untyped placeholders so that the offsets of the used members match the documented table.
  */
 #ifndef MVX_VS4_API_H
@@ -121,7 +121,9 @@ struct VSAPI {
     mvx_vs_slot getFrameLength;
 
     /* formats */
-    mvx_vs_slot getVideoFormatName, getAudioFormatName, queryVideoFormat, queryAudioFormat, queryVideoFormatID, getVideoFormatByID;
+    mvx_vs_slot getVideoFormatName, getAudioFormatName;
+    int (VS_CC *queryVideoFormat)(VSVideoFormat *format, int colorFamily, int sampleType, int bitsPerSample, int subSamplingW, int subSamplingH, VSCore *core); /* non-zero on success */
+    mvx_vs_slot queryAudioFormat, queryVideoFormatID, getVideoFormatByID;
 
     /* frame requests */
     const VSFrame *(VS_CC *getFrame)(int n, VSNode *node, char *errorMsg, int bufSize);

@@ -42,6 +42,7 @@ MVX_VSAPI_SLOT(mapSetError, 51);
 MVX_VSAPI_SLOT(mapSetInt, 62);
 MVX_VSAPI_SLOT(mapSetNode, 74);
 MVX_VSAPI_SLOT(newVideoFrame, 12);
+MVX_VSAPI_SLOT(queryVideoFormat, 32);
 MVX_VSAPI_SLOT(requestFrameFilter, 39);
 MVX_VSAPI_SLOT(setFilterError, 42);
 _Static_assert(offsetof(VSPLUGINAPI, configPlugin) == sizeof(void *) && offsetof(VSPLUGINAPI, registerFunction) == 2 * sizeof(void *), "VSPLUGINAPI layout differs from vs4_api.h");
