@@ -468,6 +468,119 @@ typedef struct mvx_mask_job {
  * launch for the luma planes of all jobs and one for both chroma planes of all jobs */
 int mvx_mask_frames(mvx_mask *m, int nframes, const mvx_mask_job *jobs, void *stream);
 
+/* ---- mv.DepanCompensate / mv.DepanAnalyse ----------------------------------------------------------
+ * global motion: DepanAnalyse fits a pan / zoom / rotation model to the block vectors of a delta-1 vector clip, DepanCompensate warps
+ * a frame by the model summed over the frames between source and destination.  Neither needs FFTW (only DepanEstimate does).
+ * mvx_depan_compensate_create replaces depanCompensateCreate, MVDepan.cpp:2750-2881; mvx_depan_compensate_map and
+ * mvx_depan_motion_to_transform replace the frame selection and the transform sum of depanCompensateGetFrame, :2594-2675;
+ * mvx_depan_compensate_frames replaces :2678-2715 with compensate_plane_nearest / _bilinear / _bicubic, :1626-2585.
+ * mvx_depan_analyse_create replaces depanAnalyseCreate, :473-615; mvx_depan_analyse_frames / _host replace depanAnalyseGetFrame,
+ * :237-430 (TrasformUpdate :145-199, RejectBadBlocks :203-234).  Creation touches no device.  Only the samples of each plane are written,
+ * never the bytes between a plane's width and its pitch.
+ * The estimator runs on the host (csrc/mvx_depan_host.h): each of its sums is a serial float chain in block order, and another order
+ * gives another result.  The GPU gathers what it reads: the verdict of fgopIsUsable, the level-0 vectors and the mask bytes.
+ * Deliberate divergences:
+ *   1. the sign of a near-zero dx: where |dx| < 0.01 the reference draws the sign of 0.011 from rand() (:397-398); the library always
+ *      returns +0.011f;
+ *   2. (not rejected) reads and writes outside a row.  Wherever the reference's own index falls outside [0, row_size) of its row the
+ *      library writes the plane's border value (0 for luma, half range for chroma), and it never writes outside the row:
+ *        a. translation and zoom forms of all three interpolators, left mirror (srcp[w0 - rowleft] and the blur run that ends there):
+ *           -rowleft >= row_size;
+ *        b. the same forms, right mirror (srcp[w0 + 2 * row_size - rowleft - 2] and the blur run that starts there):
+ *           rowleft > 2 * row_size - 2;
+ *        c. the translation form of bilinear: its tail loop starts at rowgoodendpaired - 1 (:1971), so with fewer than two "good"
+ *           columns (inttr0 >= row_size - 2, or inttr0 <= 1 - row_size) the reference reads before the row, writes dstp[-1], or runs its
+ *           "bad" loop past either end of the row.  Every sample inside the row ends with the value of the per-sample rule -- interpolate
+ *           where 0 <= rowleft < row_size - 1, else mirror (a, b), else border -- and that is what the library writes; nothing else;
+ *   3. plane sizes: every plane must be at least 2 x 2 samples, rejected at creation otherwise.  With one column bicubic's edge test
+ *      rowleft == row_size - 2 reads srcp[-1]; with one row its near-edge rows (hlow == 0) read the row below the plane and the zoom
+ *      form's bottom row reads the row above it;
+ *   4. a frame larger than 32767 x 32767 is rejected: a blur run is summed in int as in the reference, and stays exact up to there;
+ *   5. (not rejected) positions that are NaN or not inside (-2^30, 2^30): the reference's float -> int conversion or its mirror
+ *      arithmetic is undefined there.  The library writes the border value for such a sample (for the whole row where the row's ysrc
+ *      is such a value in the translation and zoom forms), and faults on none;
+ *   6. DepanAnalyse with a mask clip has no ignored border, and the reference's comparison of a vector with its eight neighbours
+ *      (blockDx[n - 1 - nBlkX] .. blockDx[n + 1 + nBlkX], :211-221) then reads before and after its arrays.  The library skips that
+ *      comparison for a block with a neighbour index outside the array.  (At the sides the indices wrap into the adjoining row, inside
+ *      the array: those reads are kept as they are.);
+ *   7. `info` overlays are the shell's business; the numbers they print are returned (mvx_depan_motion_to_transform's `motion`,
+ *      mvx_depan_motion's iter and error). */
+
+/* the format of a clip argument (VSVideoInfo) */
+typedef struct mvx_depan_clip { int32_t width, height, bits, subsampling_w, subsampling_h, gray; } mvx_depan_clip;
+
+typedef struct mvx_depan_compensate_args {
+    double offset;           /* -10..10; a float argument in the reference.  Required */
+    int32_t subpixel;        /* 0 nearest, 1 bilinear, 2 bicubic; MVX_UNSET -> 2 */
+    double pixaspect;        /* > 0; pass 1.0 for the default (a float argument in the reference) */
+    int32_t matchfields;     /* MVX_UNSET -> 1 */
+    int32_t mirror;          /* bits: 1 top, 2 bottom, 4 left, 8 right; MVX_UNSET -> 0 */
+    int32_t blur;            /* >= 0, MVX_UNSET -> 0; chroma planes of 4:2:0 and 4:2:2 take blur / 2 */
+    int32_t fields;          /* MVX_UNSET -> 0 */
+    int32_t tff;             /* MVX_UNSET = not passed */
+} mvx_depan_compensate_args;
+
+typedef struct mvx_depan_compensate_info {
+    int32_t width, height, bits, subsampling_w, subsampling_h, num_planes;
+    int32_t plane_width[3], plane_height[3];
+    int32_t intoffset;       /* ceilf(offset) for offset > 0, else floorf(offset), :2835-2838; 0: every frame passes through */
+    int32_t subpixel, mirror, pixel_max;
+    int32_t border[3], blur[3];
+    float xcenter, ycenter, offset, pixaspect;
+} mvx_depan_compensate_info;
+
+typedef struct mvx_depan_compensate mvx_depan_compensate;
+
+/* num_frames / data_frames: the lengths of clip and data.  Pitches in bytes, multiples of the sample size */
+int mvx_depan_compensate_create(const mvx_depan_compensate_args *args, const mvx_depan_clip *clip, int num_frames, int data_frames,
+                                const ptrdiff_t src_pitch[3], const ptrdiff_t dst_pitch[3], mvx_depan_compensate **out, char *err);
+void mvx_depan_compensate_destroy(mvx_depan_compensate *h);
+void mvx_depan_compensate_get_info(const mvx_depan_compensate *h, mvx_depan_compensate_info *info);
+/* output frame ndest: returns 1 with *nsrc = ndest - intoffset, the clip frame to warp, and the motions of data frames *start + 1 ..
+ * *end to sum; or 0 (intoffset == 0, or nsrc outside the clip): the caller returns clip frame ndest itself */
+int mvx_depan_compensate_map(const mvx_depan_compensate *h, int ndest, int *nsrc, int *start, int *end);
+/* the summed luma transform of output frame ndest from `count` motions (dx, dy, zoom, rot each: Depan_dx, Depan_dy, Depan_zoom, Depan_rot of
+ * data frames start + 1 .. end, in that order): trsum = dxc, dxx, dxy, dyc, dyx, dyy; motion = dx, dy, zoom, rot of the info string
+ * (transform2motion).  top_field: the _Field property of clip frame ndest, MVX_UNSET when absent; read with fields and matchfields only.
+ * Host arithmetic, no device. */
+int mvx_depan_motion_to_transform(const mvx_depan_compensate *h, int count, const float *motions, int ndest, int top_field,
+                                  float trsum[6], float motion[4], char *err);
+
+typedef struct mvx_depan_compensate_job {
+    const void *src[3];      /* planes of clip frame nsrc */
+    void *dst[3];
+    float tr[6];             /* trsum; the library derives each plane's transform, border value and blur, :2683-2700 */
+} mvx_depan_compensate_job;
+
+/* nframes jobs in one batch on `stream`: a small pre-pass for the rotation form of nearest and bilinear, then one launch for all planes of
+ * all jobs */
+int mvx_depan_compensate_frames(mvx_depan_compensate *h, int nframes, const mvx_depan_compensate_job *jobs, void *stream);
+
+typedef struct mvx_depan_analyse_args {
+    int32_t zoom, rot;       /* MVX_UNSET -> 1 */
+    double pixaspect, error, wrong, zerow; /* float arguments in the reference; pass 1.0 / 15.0 / 10.0 / 0.05 for the defaults */
+    int64_t thscd1; int32_t thscd2;
+    int32_t fields;          /* MVX_UNSET -> 0 */
+} mvx_depan_analyse_args;
+
+/* dx == 0.0f marks a frame without a result (scene change, unusable vectors, error too large), as in the reference */
+typedef struct mvx_depan_motion { float dx, dy, zoom, rot; int32_t iter; float error; } mvx_depan_motion;
+
+typedef struct mvx_depan_analyse mvx_depan_analyse;
+
+/* mask: the format of the optional mask clip, NULL = none; *_frames: the lengths of the three clips */
+int mvx_depan_analyse_create(const mvx_depan_analyse_args *args, const mvx_analysis_data *vectors, const mvx_depan_clip *clip,
+                             const mvx_depan_clip *mask, int num_frames, int vector_frames, int mask_frames, mvx_depan_analyse **out, char *err);
+void mvx_depan_analyse_destroy(mvx_depan_analyse *h);
+/* n frames: blobs[i] the DEVICE blob of the vector clip at frame i (backward vectors: at max(0, i - 1)), NULL = unusable; masks[i] the
+ * DEVICE luma plane of the mask clip (with a mask clip only); top_field[i] read with fields only (may be NULL otherwise).  One gather
+ * kernel for all frames, then the estimator on the host.  Synchronous. */
+int mvx_depan_analyse_frames(mvx_depan_analyse *h, int n, const void *const *blobs, const void *const *masks, ptrdiff_t mask_pitch,
+                             const int32_t *top_field, mvx_depan_motion *out, void *stream);
+/* the same from HOST blobs and HOST mask planes; touches no device */
+int mvx_depan_analyse_host(const mvx_depan_analyse *h, int n, const void *const *blobs, const void *const *masks, ptrdiff_t mask_pitch,
+                           const int32_t *top_field, mvx_depan_motion *out);
+
 /* ---- mv.SCDetection -------------------------------------------------------------------------------
  * replaces the decision of mvscdetectionGetFrame, MVSCDetection.c:43-73 (arg string :137-145): scene_change[i] (HOST array) =
  * !usable(blobs[i]) for n device blobs of one vector clip, i.e. the value of _SceneChangePrev (forward vectors) or

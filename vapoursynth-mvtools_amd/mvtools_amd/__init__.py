@@ -8,6 +8,8 @@
     core.mv.Flow(clip, super, vectors, ...)           -> Flow(super, analysis_data, ...)          .run(jobs)
     core.mv.FlowBlur(clip, super, mvbw, mvfw, ...)    -> FlowBlur(super, bw_data, fw_data, ...)   .run(ns, ...)
     core.mv.Mask(clip, vectors, ...)                  -> Mask(analysis_data, width, height, ...)  .run(blobs, clip)
+    core.mv.DepanAnalyse(clip, vectors, ...)          -> DepanAnalyse(analysis_data, width, height, ...) .run(blobs, masks)
+    core.mv.DepanCompensate(clip, data, offset, ...)  -> DepanCompensate(width, height, ..., offset=...) .map(n) .transform(motions) .run(frames, transforms)
 
 Argument names, defaults and error strings are the reference's (MVSuper.c:279-291, MVAnalyse.c:639-671,
 MVDegrains.cpp:813-932, MVCompensate.c:579-592); they are resolved inside the library, not here.
@@ -156,6 +158,35 @@ class MaskJob(C.Structure):
     _fields_ = [("blob", C.c_void_p), ("clip_luma", C.c_void_p), ("dst", C.c_void_p * 3)]
 
 
+class DepanClip(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "bits", "subsampling_w", "subsampling_h", "gray")]
+
+
+class DepanCompensateArgs(C.Structure):
+    _fields_ = [("offset", C.c_double), ("subpixel", C.c_int32), ("pixaspect", C.c_double), ("matchfields", C.c_int32), ("mirror", C.c_int32),
+                ("blur", C.c_int32), ("fields", C.c_int32), ("tff", C.c_int32)]
+
+
+class DepanCompensateInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "bits", "subsampling_w", "subsampling_h", "num_planes")] + [
+        ("plane_width", C.c_int32 * 3), ("plane_height", C.c_int32 * 3), ("intoffset", C.c_int32), ("subpixel", C.c_int32), ("mirror", C.c_int32),
+        ("pixel_max", C.c_int32), ("border", C.c_int32 * 3), ("blur", C.c_int32 * 3), ("xcenter", C.c_float), ("ycenter", C.c_float),
+        ("offset", C.c_float), ("pixaspect", C.c_float)]
+
+
+class DepanCompensateJob(C.Structure):
+    _fields_ = [("src", C.c_void_p * 3), ("dst", C.c_void_p * 3), ("tr", C.c_float * 6)]
+
+
+class DepanAnalyseArgs(C.Structure):
+    _fields_ = [("zoom", C.c_int32), ("rot", C.c_int32), ("pixaspect", C.c_double), ("error", C.c_double), ("wrong", C.c_double), ("zerow", C.c_double),
+                ("thscd1", C.c_int64), ("thscd2", C.c_int32), ("fields", C.c_int32)]
+
+
+class DepanMotion(C.Structure):
+    _fields_ = [("dx", C.c_float), ("dy", C.c_float), ("zoom", C.c_float), ("rot", C.c_float), ("iter", C.c_int32), ("error", C.c_float)]
+
+
 _lib = None
 
 
@@ -241,6 +272,17 @@ def lib():
         L.mvx_mask_get_info.argtypes = [C.c_void_p, P(MaskInfo)]
         L.mvx_mask_get_info.restype = None
         L.mvx_mask_frames.argtypes = [C.c_void_p, C.c_int, P(MaskJob), C.c_void_p]
+        L.mvx_depan_compensate_create.argtypes = [P(DepanCompensateArgs), P(DepanClip), C.c_int, C.c_int, P(C.c_ssize_t), P(C.c_ssize_t), P(C.c_void_p), C.c_char_p]
+        L.mvx_depan_compensate_destroy.argtypes = [C.c_void_p]
+        L.mvx_depan_compensate_get_info.argtypes = [C.c_void_p, P(DepanCompensateInfo)]
+        L.mvx_depan_compensate_get_info.restype = None
+        L.mvx_depan_compensate_map.argtypes = [C.c_void_p, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int)]
+        L.mvx_depan_motion_to_transform.argtypes = [C.c_void_p, C.c_int, P(C.c_float), C.c_int, C.c_int, P(C.c_float), P(C.c_float), C.c_char_p]
+        L.mvx_depan_compensate_frames.argtypes = [C.c_void_p, C.c_int, P(DepanCompensateJob), C.c_void_p]
+        L.mvx_depan_analyse_create.argtypes = [P(DepanAnalyseArgs), P(AnalysisData), P(DepanClip), P(DepanClip), C.c_int, C.c_int, C.c_int, P(C.c_void_p), C.c_char_p]
+        L.mvx_depan_analyse_destroy.argtypes = [C.c_void_p]
+        L.mvx_depan_analyse_frames.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), P(C.c_void_p), C.c_ssize_t, P(C.c_int32), P(DepanMotion), C.c_void_p]
+        L.mvx_depan_analyse_host.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), P(C.c_void_p), C.c_ssize_t, P(C.c_int32), P(DepanMotion)]
         L.mvx_scale_thscd.argtypes = [P(C.c_int64), P(C.c_int32), P(AnalysisData)]
         L.mvx_vectors_size.argtypes = [P(AnalysisData)]
         L.mvx_vectors_size.restype = C.c_int
@@ -965,6 +1007,141 @@ class Mask:
             arr[k].clip_luma = clip[k][0].data_ptr() if clip is not None else None
             for p in range(3):
                 arr[k].dst[p] = out[k][p].data_ptr()
+        return arr, out
+
+
+class DepanAnalyse:
+    """mv.DepanAnalyse(clip, vectors, mask, zoom, rot, pixaspect, error, info, wrong, zerow, thscd1, thscd2, fields, tff) -- MVDepan.cpp:473-615.
+    `width` / `height` describe the clip; `mask` = (bits,) or (bits, width, height) of the optional mask clip.  The vectors come from a delta-1
+    Analyse; for backward vectors the caller passes the blob of frame max(0, n - 1) for frame n (MVDepan.cpp:287).  The estimator runs on the
+    host in block order; run() gathers what it reads with one kernel, run_host() takes numpy blobs and mask planes and touches no device."""
+
+    def __init__(self, vectors_ad, width, height, bits=8, subsampling=(1, 1), gray=False, mask=None, zoom=None, rot=None, pixaspect=1.0, error=15.0,
+                 wrong=10.0, zerow=0.05, thscd1=None, thscd2=None, fields=None, num_frames=1, vector_frames=None, mask_frames=None):
+        a = DepanAnalyseArgs(_u(zoom), _u(rot), float(pixaspect), float(error), float(wrong), float(zerow), _u(thscd1), _u(thscd2), _u(fields))
+        ad = AnalysisData.from_buffer_copy(bytes(vectors_ad))
+        c = DepanClip(int(width), int(height), int(bits), int(subsampling[0]), int(subsampling[1]), int(bool(gray)))
+        m = None
+        if mask is not None:
+            mask = tuple(mask) + (width, height)[len(mask) - 1:] if len(mask) < 3 else tuple(mask)
+            m = C.byref(DepanClip(int(mask[1]), int(mask[2]), int(mask[0]), 0, 0, 1))
+        self.has_mask = mask is not None
+        self.nblk = ad.nBlkX * ad.nBlkY
+        self.h = C.c_void_p()
+        err = C.create_string_buffer(ERRLEN)
+        nf = int(num_frames)
+        _check(lib().mvx_depan_analyse_create(C.byref(a), C.byref(ad), C.byref(c), m, nf, nf if vector_frames is None else int(vector_frames),
+                                              nf if mask_frames is None else int(mask_frames), C.byref(self.h), err), err)
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().mvx_depan_analyse_destroy(self.h)
+        except Exception:
+            pass
+
+    @staticmethod
+    def _result(out):
+        return [dict(dx=m.dx, dy=m.dy, zoom=m.zoom, rot=m.rot, iter=m.iter, error=m.error) for m in out]
+
+    def _fields(self, n, top_field):
+        return None if top_field is None else (C.c_int32 * n)(*[int(bool(t)) for t in top_field])
+
+    def run(self, blobs, masks=None, top_field=None):
+        """blobs: device blobs (None: unusable); masks: device luma planes of the mask clip; -> one dict per frame"""
+        _torch()
+        n = len(blobs)
+        ptrs = (C.c_void_p * n)(*[b.data_ptr() if b is not None else None for b in blobs])
+        mp = (C.c_void_p * n)(*[m.data_ptr() for m in masks]) if masks is not None else None
+        out = (DepanMotion * n)()
+        _check(lib().mvx_depan_analyse_frames(self.h, n, ptrs, mp, masks[0].stride(0) if masks is not None else 0, self._fields(n, top_field), out, _stream()))
+        return self._result(out)
+
+    def run_host(self, blobs, masks=None, top_field=None):
+        """the same from numpy uint8 blobs and 2-D numpy uint8 mask planes of one shape; no device"""
+        n = len(blobs)
+        keep = [np.ascontiguousarray(b, dtype=np.uint8) if b is not None else None for b in blobs]
+        ptrs = (C.c_void_p * n)(*[b.ctypes.data if b is not None else None for b in keep])
+        mk = [np.ascontiguousarray(m, dtype=np.uint8) for m in masks] if masks is not None else None
+        mp = (C.c_void_p * n)(*[m.ctypes.data for m in mk]) if mk is not None else None
+        out = (DepanMotion * n)()
+        _check(lib().mvx_depan_analyse_host(self.h, n, ptrs, mp, mk[0].strides[0] if mk is not None else 0, self._fields(n, top_field), out))
+        return self._result(out)
+
+
+class DepanCompensate:
+    """mv.DepanCompensate(clip, data, offset, subpixel, pixaspect, matchfields, mirror, blur, info, fields, tff) -- MVDepan.cpp:2750-2881.
+    map(n) says which clip frame to warp and which data frames' motions to sum, transform(motions, ...) sums them (host arithmetic), and a
+    job is (src planes, summed transform).  `src_pitch` / `dst_pitch`: row pitches in bytes of the device planes."""
+
+    def __init__(self, width, height, bits=8, subsampling=(1, 1), gray=False, src_pitch=None, dst_pitch=None, offset=0.0, subpixel=None, pixaspect=1.0,
+                 matchfields=None, mirror=None, blur=None, fields=None, tff=None, num_frames=1 << 30, data_frames=None):
+        a = DepanCompensateArgs(float(offset), _u(subpixel), float(pixaspect), _u(matchfields), _u(mirror), _u(blur), _u(fields), _u(tff))
+        c = DepanClip(int(width), int(height), int(bits), int(subsampling[0]), int(subsampling[1]), int(bool(gray)))
+        sw = 0 if gray else subsampling[0]
+        bps = 2 if bits > 8 else 1
+        if dst_pitch is None:
+            dst_pitch = [((max(int(width) >> s, 1) * bps + 255) // 256) * 256 for s in (0, sw, sw)]
+        if src_pitch is None:
+            src_pitch = dst_pitch
+        self.h = C.c_void_p()
+        self.pitch = list(dst_pitch)
+        self.dtype = np.uint16 if bits > 8 else np.uint8
+        err = C.create_string_buffer(ERRLEN)
+        _check(lib().mvx_depan_compensate_create(C.byref(a), C.byref(c), int(num_frames), int(num_frames if data_frames is None else data_frames),
+                                                 _pad3(src_pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
+        self.info = DepanCompensateInfo()
+        lib().mvx_depan_compensate_get_info(self.h, C.byref(self.info))
+        self.nplanes = self.info.num_planes
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().mvx_depan_compensate_destroy(self.h)
+        except Exception:
+            pass
+
+    def map(self, n):
+        """(nsrc, start, end) of output frame n: warp clip frame nsrc by the motions of data frames start + 1 .. end; None: return clip frame n"""
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        if not lib().mvx_depan_compensate_map(self.h, int(n), C.byref(a), C.byref(b), C.byref(c)):
+            return None
+        return a.value, b.value, c.value
+
+    def transform(self, motions, top_field=None, ndest=0):
+        """motions: (dx, dy, zoom, rot) of data frames start + 1 .. end -> (trsum as six floats, (dx, dy, zoom, rot) of the info string)"""
+        flat = [float(v) for m in motions for v in m]
+        arr = (C.c_float * max(len(flat), 1))(*flat)
+        tr, mo = (C.c_float * 6)(), (C.c_float * 4)()
+        err = C.create_string_buffer(ERRLEN)
+        _check(lib().mvx_depan_motion_to_transform(self.h, len(motions), arr, int(ndest), UNSET if top_field is None else int(bool(top_field)), tr, mo, err), err)
+        return np.array(tr, dtype=np.float32), np.array(mo, dtype=np.float32)
+
+    def alloc(self, n, device="cuda"):
+        return arena_frames(n, [(self.info.plane_height[p], self.pitch[p]) for p in range(self.nplanes)], device, zero=False)
+
+    def run(self, frames, transforms, out=None):
+        """frames: per job the device planes of clip frame nsrc; transforms: per job trsum; all jobs in one call"""
+        arr, out = self.jobs(frames, transforms, out)
+        self.launch(arr)
+        return out
+
+    def launch(self, arr):
+        _check(lib().mvx_depan_compensate_frames(self.h, len(arr), arr, _stream()))
+
+    def jobs(self, frames, transforms, out=None):
+        _torch()
+        n = len(frames)
+        if out is None:
+            out = self.alloc(n, frames[0][0].device if n else "cuda")
+        arr = (DepanCompensateJob * n)()
+        for k in range(n):
+            for p in range(self.nplanes):
+                arr[k].src[p] = frames[k][p].data_ptr()
+                arr[k].dst[p] = out[k][p].data_ptr()
+            t = np.asarray(transforms[k], dtype=np.float32)
+            for i in range(6):
+                arr[k].tr[i] = t[i]
         return arr, out
 
 
