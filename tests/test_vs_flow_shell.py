@@ -87,6 +87,12 @@ def test_creation_errors(flow_on, double, args, msg):
     assert host("error", *args).strip() == "ERROR " + msg
 
 
+@pytest.mark.parametrize("mismatch", shim.CLIP_MISMATCHES)
+@pytest.mark.parametrize("filt", ["FlowInter", "FlowFPS", "Flow", "FlowBlur"])
+def test_clip_must_be_the_one_the_super_clip_was_made_from(flow_on, double, filt, mismatch):
+    assert host("error", filt, 128, 96, 8, mismatch).strip() == "ERROR %s: wrong source or super clip frame size." % filt
+
+
 def test_without_the_switch_the_filters_do_not_exist(monkeypatch, double):
     monkeypatch.delenv("MVX_VS_FLOW", raising=False)
     assert host("error", "FlowFPS", 128, 96, 8).strip() == "ERROR no function FlowFPS"

@@ -20,6 +20,7 @@ def _run(fakedev, args, out, extra, env):
     e.update(env)
     r = subprocess.run([HOST, PLUGIN] + [str(a) for a in args] + [out] + list(extra), capture_output=True, text=True, timeout=600, env=e)
     assert r.returncode == 0 and "DONE" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "permits out" not in r.stderr, r.stderr[-2000:]  # (x.free=1: the gate was freed with every permit returned)
     fk = [l for l in r.stderr.splitlines() if l.startswith("mvx_fakedev:")]
     assert len(fk) == 1, r.stderr[-2000:]  # the double was really in front of the library
     return {k: int(v) for k, v in (t.split("=") for t in fk[0].split()[2:])}

@@ -10,6 +10,7 @@ same mini host, the oracle's kernels: what that run tests is the shell's own log
 """
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -39,7 +40,6 @@ def proc_env(**extra):
 
 def host(*args, check=True):
     if not (os.path.exists(HOST) and os.path.exists(PLUGIN)):
-        import sys
         sys.path.insert(0, PKG)
         import build
         build.build()
@@ -112,6 +112,18 @@ def test_super_create_reports_geometry_without_gpu():
     assert host("error", "Super", 640, 360, 8, "f.pel=2", "x.pelw=1280", "x.pelh=720").strip().startswith("OK ")
     assert host("error", "Super", 640, 360, 8, "f.pel=2", "x.pelw=%d" % ((640 + 32) * 2), "x.pelh=%d" % ((360 + 32) * 2)).strip().startswith("OK ")
     assert host("error", "Super", 640, 360, 8, "f.pel=1", "x.pelw=100", "x.pelh=100").strip() == "OK 672x978 frames=4"
+
+
+CLIP_MISMATCHES = ["x.clip=144x96x8", "x.clip=128x96x16"]  # `clip` with another width, another depth than the super clip's source
+
+
+@pytest.mark.parametrize("mismatch", CLIP_MISMATCHES)
+@pytest.mark.parametrize("filt", ["Degrain1", "Compensate", "BlockFPS"])
+def test_clip_must_be_the_one_the_super_clip_was_made_from(fakedev, monkeypatch, filt, mismatch):
+    """The kernels address the clip's planes with the super clip's geometry and sample size: every filter that takes both refuses a `clip`
+    that is not the super clip's source, in the reference's words.  (CPU only: frame 0 of the super and vector clips comes from the test double.)"""
+    monkeypatch.setattr(sys.modules[__name__], "_PRELOAD", fakedev)
+    assert host("error", filt, 128, 96, 8, mismatch).strip() == "ERROR %s: wrong source or super clip frame size." % filt
 
 
 def _write_clip(path, frames):
@@ -381,6 +393,11 @@ def test_shell_fields_need_parity_information(shell):
         assert "Analyse: " + msg in out
         out = host("run", "compensate", os.path.join(d, "in.raw"), 128, 96, 8, 3, os.path.join(d, "o.raw"), "c.fields=1", check=False)
         assert "Compensate: " + msg in out
+        # the same request through the admission gate's error leg: the filter error returned the permit before the graph was freed
+        r = subprocess.run([HOST, PLUGIN, "run", "compensate", os.path.join(d, "in.raw"), "128", "96", "8", "3", os.path.join(d, "o.raw"), "c.fields=1", "x.free=1"],
+                           capture_output=True, text=True, timeout=600, env=proc_env())
+        assert "Compensate: " + msg in r.stdout and "FREED" in r.stdout, r.stdout + r.stderr
+        assert "permits out" not in r.stderr, r.stderr[-2000:]
         out = host("run", "recalculate", os.path.join(d, "in.raw"), 128, 96, 8, 3, os.path.join(d, "o.raw"), "r.fields=1", check=False)
         assert "Recalculate: " + msg in out
         out = host("run", "recalculate", os.path.join(d, "in.raw"), 128, 96, 8, 3, os.path.join(d, "o.raw"), "r.fields=1", "r.tff=1")

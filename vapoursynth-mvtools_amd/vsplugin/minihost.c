@@ -10,6 +10,7 @@
  *
  *   mvx_vs_host <plugin.so> list
  *   mvx_vs_host <plugin.so> error  <Filter> <w> <h> <bits> [f.key=value ...]       -> prints the creation error (or OK)
+ *       x.clip=WxHxBITS: the filter's `clip` argument is a second blank clip of that geometry; the super clip is still made from the first
  *   mvx_vs_host <plugin.so> run <pipeline> <in.raw> <w> <h> <bits> <nframes> <out.raw> [s.|a.|d.|c.key=value ...]
  *       pipeline: super | finest | analyse | scdetection (d.*) | recalculate (r.*) | degrainN | compensate | blockfps (b.*)
  *                 | flowinter | flowfps | flow | flowblur | mask (f.*; the plugin registers these with MVX_VS_FLOW=1): on the vector pair of delta 1, or
@@ -523,7 +524,11 @@ int main(int argc, char **argv) {
         const char *filter = argv[3];
         const int w = atoi(argv[4]), hh = atoi(argv[5]), bits = atoi(argv[6]);
         format_from_args(argc - 7, argv + 7);
-        VSNode *clip = source_clip(NULL, w, hh, bits, 4);
+        VSNode *clip = source_clip(NULL, w, hh, bits, 4), *fclip = clip; /* fclip: the consuming filter's `clip` argument (x.clip=WxHxBITS: a clip of its own) */
+        for (int i = 7; i < argc; i++) {
+            int cw, ch, cb;
+            if (!strncmp(argv[i], "x.clip=", 7) && sscanf(argv[i] + 7, "%dx%dx%d", &cw, &ch, &cb) == 3) fclip = source_clip(NULL, cw, ch, cb, 4);
+        }
         VSMap *m = createMap();
         VSNode *out = NULL;
         if (!strcmp(filter, "Super")) {
@@ -545,7 +550,7 @@ int main(int argc, char **argv) {
                 mapSetInt(a1, "isb", 1, maReplace); mapSetInt(a2, "isb", 0, maReplace);
                 VSNode *bw = invoke("Analyse", a1, err, sizeof(err)); if (!bw) die("Analyse", err);
                 VSNode *fw = invoke("Analyse", a2, err, sizeof(err)); if (!fw) die("Analyse", err);
-                mapSetNode(m, "clip", clip, maReplace);
+                mapSetNode(m, "clip", fclip, maReplace);
                 if (strcmp(filter, "Mask")) mapSetNode(m, "super", sup, maReplace); /* (mv.Mask takes no super clip) */
                 add_args(m, 'f', argc - 7, argv + 7);
                 if (!strcmp(filter, "Compensate") || !strcmp(filter, "Flow") || !strcmp(filter, "Mask")) { mapSetNode(m, "vectors", bw, maReplace); out = invoke(filter, m, err, sizeof(err)); }
@@ -723,9 +728,10 @@ int main(int argc, char **argv) {
         prefetch_parallel(threads, outFrames, &out, 1);
         if (times) { fprintf(stderr, "minihost: output clip %.2f s\n", now_s() - t0); t0 = now_s(); }
     }
+    int failed = 0; /* (with x.free=1 a failed output frame is reported after the teardown: the free callbacks of a graph whose request ended in an error run too) */
     for (int n = 0; n < outFrames; n++) {
         const VSFrame *f = eval_frame(n, out, err, sizeof(err));
-        if (!f) die("output frame", err);
+        if (!f) { failed = 1; break; }
         if (isFlowFps && n == 1) { int e; printf("frame1 _DurationNum=%lld _DurationDen=%lld\n", (long long)mapGetInt(f->props, "_DurationNum", 0, &e), (long long)mapGetInt(f->props, "_DurationDen", 0, &e)); }
         dump_frame(fo, f); freeFrame(f);
     }
@@ -742,6 +748,7 @@ int main(int argc, char **argv) {
             node_free(clip);
             printf("FREED\n");
         }
+    if (failed) die("output frame", err);
     printf("DONE\n");
     return 0;
 }

@@ -77,7 +77,6 @@ static void la_trace(const void *inst, int w, const char *what, double dur) {
     if (g_trace_on < 0) { g_trace_on = getenv("MVX_VS_TRACE") != NULL; g_trace_t0 = prof_now(); }
     if (g_trace_on) fprintf(stderr, "mvtools_vs trace %8.3f  analyse %p window %d %s (%.3f s)\n", prof_now() - g_trace_t0, inst, w, what, dur);
 }
-static void prof_add_locked_ok(int k, double t0) { prof_add(k, t0); } /* (g_lock is a different mutex than the callers hold) */
 /* The per-frame work of a worker thread (its uploads, its Super / Degrain / ... kernels) runs on ONE stream of a small pool
  * (MVX_VS_FRAME_STREAMS, default 4; r3 had ONE for all threads: a thread's kernel then waited behind every other thread's uploads), chosen per
  * thread the first time it asks.  Every getFrame waits for its own stream before it publishes or releases anything, so the streams need no
@@ -1151,7 +1150,7 @@ static int la_wait(AnalyseData *d, LaWindow *s) {
             pthread_cond_broadcast(&d->la.cv);
             continue;
         }
-        { const double tb = prof_now(); pthread_cond_wait(&d->la.cv, &d->la.mu); prof_add_locked_ok(PF_LA_BLOCKED, tb); } /* BUILDING / SYNCING: somebody is on it */
+        { const double tb = prof_now(); pthread_cond_wait(&d->la.cv, &d->la.mu); prof_add(PF_LA_BLOCKED, tb); } /* BUILDING / SYNCING: somebody is on it */
     }
     const int rc = s->state == LW_READY ? 0 : (s->rc ? s->rc : MVX_E_DEVICE);
     pthread_mutex_unlock(&d->la.mu);
@@ -1738,20 +1737,160 @@ static void gate_leave(Gate *g, void **fd) {
     pthread_mutex_unlock(&g->mu);
 }
 
+/* ------------------------------------------------------------------------------------------------ the consuming filters: one skeleton
+ * mv.Degrain1..6 / mv.Compensate / mv.BlockFPS and, registered with MVX_VS_FLOW=1 (see the entry point), mv.FlowInter / mv.FlowFPS / mv.Flow / mv.FlowBlur / mv.Mask
+ * take vectors and produce pictures behind the admission gate.  Each has a Consumer as the FIRST member of its data: what an instance owns, the gate around its
+ * getFrame and its free callback exist once.  Where the reference asks its mv.Finest node for a frame the per-sample filters ask the super clip: the library reads
+ * the sub-pel planes of the super frame directly (mvtools_amd.h), so no Finest node exists.  One mvx_*_frames call per output frame, on the thread's stream. */
+typedef struct Consumer {
+    const char *name;
+    Gate gate;
+    VSNode *nodes[14]; int nnodes;         /* every node the instance holds (the filters' own node members point into this) */
+    mvx_super *sup; SuperGeo geo;          /* of the super clip (mv.Mask takes none) */
+    void *engine; void (*destroy)(void *); /* the library's handle */
+    VSFilterGetFrame body;                 /* the filter proper */
+} Consumer;
+
+#define ENGINE_DESTROY(T) static void T##_destroy_engine(void *e) { T##_destroy((T *)e); }
+ENGINE_DESTROY(mvx_degrain) ENGINE_DESTROY(mvx_compensate) ENGINE_DESTROY(mvx_blockfps) ENGINE_DESTROY(mvx_flow) ENGINE_DESTROY(mvx_flowcomp) ENGINE_DESTROY(mvx_flowblur) ENGINE_DESTROY(mvx_mask)
+
+static void *consumer_new(size_t size, const char *name, VSFilterGetFrame body, void (*destroy)(void *)) {
+    Consumer *c = (Consumer *)calloc(1, size);
+    c->name = name; c->body = body; c->destroy = destroy;
+    gate_init(&c->gate);
+    return c;
+}
+static VSNode *consumer_node(Consumer *c, const VSMap *in, const char *key, const VSAPI *vs) {
+    return c->nodes[c->nnodes++] = vs->mapGetNode(in, key, 0, NULL);
+}
+static VSNode *consumer_super(Consumer *c, const VSMap *in, char *err, size_t esz, const VSAPI *vs) {
+    VSNode *super = consumer_node(c, in, "super", vs);
+    c->sup = super_from_props(super, c->name, err, esz, vs);
+    if (c->sup) super_geo(&c->geo, c->sup);
+    return super;
+}
+/* the admission gate around the filter proper: arInitial takes the permit, whatever ends the request -- the frame, a filter error, arError -- returns it */
+static const VSFrame *VS_CC consumerGetFrame(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    Consumer *c = (Consumer *)inst;
+    if (reason == arInitial) gate_enter(&c->gate, n, fd);
+    const VSFrame *f = c->body(n, reason, inst, fd, ctx, core, vs);
+    if (reason != arInitial || f) gate_leave(&c->gate, fd);
+    return f;
+}
+/* the free callback, and the teardown of an instance whose creation failed part of the way (no permit can be out then) */
+static void VS_CC consumerFree(void *inst, VSCore *core, const VSAPI *vs) {
+    (void)core;
+    Consumer *c = (Consumer *)inst;
+    for (int i = 0; i < c->nnodes; i++) if (c->nodes[i]) vs->freeNode(c->nodes[i]);
+    if (c->engine) c->destroy(c->engine);
+    if (c->sup) mvx_super_destroy(c->sup);
+    gate_free(&c->gate);
+    free(c);
+}
+static void consumer_fail(Consumer *c, const char *err, VSMap *out, const VSAPI *vs) {
+    vs->mapSetError(out, err);
+    consumerFree(c, NULL, vs);
+}
+
+/* device pitches of clip and output planes: rows of 256 bytes */
+static void clip_pitches(ptrdiff_t pitch[3], const VSVideoInfo *vi, int bps) {
+    for (int p = 0; p < 3; p++) {
+        const int w = p ? vi->width >> vi->format.subSamplingW : vi->width;
+        pitch[p] = ((ptrdiff_t)w * bps + 255) / 256 * 256;
+    }
+}
+/* The two tests of `clip` at creation; the first that fails writes its message.  The format test is the reference's (MVDegrains.cpp:693, MVCompensate.c:543,
+ * MVBlockFPS.c:928, MVFlowInter.c:644, MVFlowFPS.c:794, MVFlow.cpp:526, MVFlowBlur.c:514).  Of the other, the reference has the sizes only (MVDegrains.cpp:683,
+ * MVCompensate.c:535, MVBlockFPS.c:913-920): the kernels address the clip's planes with the vector clip's geometry and the super clip's sample size, which creation
+ * ties to the super clip's, so a clip of another size or format than the one the super clip was made from would be read or written outside its planes. */
+static void consumer_check_clip(const Consumer *c, const VSVideoInfo *vi, const VSVideoInfo *svi, int sizeFirst, char *err, size_t esz) {
+    const mvx_super_info *si = &c->geo.si;
+    const int formatOk = mvx_vsh_is_constant_video_format(vi) && vi->format.bitsPerSample <= 16 && vi->format.sampleType == stInteger && vi->format.subSamplingW <= 1 &&
+                         vi->format.subSamplingH <= 1 && (vi->format.colorFamily == cfYUV || vi->format.colorFamily == cfGray);
+    const int isSupers = si->width == vi->width && si->height == vi->height && si->super_width == svi->width && si->super_height == svi->height &&
+                         vi->format.bitsPerSample == svi->format.bitsPerSample && vi->format.colorFamily == svi->format.colorFamily &&
+                         vi->format.subSamplingW == svi->format.subSamplingW && vi->format.subSamplingH == svi->format.subSamplingH;
+    if (!isSupers && (sizeFirst || formatOk)) snprintf(err, esz, "%s: wrong source or super clip frame size.", c->name);
+    else if (!formatOk) snprintf(err, esz, "%s: input clip must be GRAY, 420, 422, 440, or 444, up to 16 bits, with constant dimensions.", c->name);
+}
+/* one arena for the planes of an output frame */
+static int dst_plane_set(void *dst[3], void **arena, const ptrdiff_t pitch[3], const int height[3], int nplanes) {
+    size_t off[3], total = 0;
+    for (int p = 0; p < nplanes; p++) { off[p] = total; total += (size_t)pitch[p] * (size_t)height[p]; }
+    for (int p = 0; p < 3; p++) dst[p] = NULL;
+    *arena = shell_alloc(total);
+    if (!*arena) return MVX_E_NOMEM;
+    for (int p = 0; p < nplanes; p++) dst[p] = (char *)*arena + off[p];
+    return 0;
+}
+/* the finished planes -> the host frame; complete on return */
+static int download_plane_set(VSFrame *dst, void *const src[3], const ptrdiff_t pitch[3], int nplanes, int bps, const VSAPI *vs) {
+    int rc = 0;
+    for (int p = 0; p < nplanes && !rc; p++)
+        rc = timed_download(vs->getWritePtr(dst, p), vs->getStride(dst, p), src[p], pitch[p], (size_t)vs->getFrameWidth(dst, p) * bps, (size_t)vs->getFrameHeight(dst, p));
+    if (!rc) rc = mvx_stream_sync(thread_stream());
+    return rc;
+}
+/* prefixAll: the library's own message gets the filter's name in front as well (mv.DegrainN's habit) */
+static void consumer_frame_error(const char *name, int rc, int prefixAll, VSFrameContext *ctx, const VSAPI *vs) {
+    char msg[MVX_ERRLEN + 64];
+    if (rc != MVX_E_ARG && rc != MVX_E_NOMEM && !prefixAll) { vs->setFilterError(mvx_last_error(), ctx); return; }
+    snprintf(msg, sizeof(msg), "%s: %s", name, rc == MVX_E_ARG ? "vector clip frame without matching MVTools_vectors property." : rc == MVX_E_NOMEM ? "out of memory." : mvx_last_error());
+    vs->setFilterError(msg, ctx);
+}
+static double opt_float(const VSMap *in, const char *key, double def, const VSAPI *vs) {
+    int e = 0;
+    const double v = vs->mapGetFloat(in, key, 0, &e);
+    return e ? def : v;
+}
+/* MVTools_vectors of frame n of a vector clip -> device; 0 or an MVX_E_* code */
+static int clip_blob_to_device(void **dblob, int n, VSNode *vectors, const mvx_analysis_data *ad, VSFrameContext *ctx, const VSAPI *vs) {
+    const VSFrame *vf = vs->getFrameFilter(n, vectors, ctx);
+    const int rc = blob_to_device(dblob, NULL, ad, vf, vs);
+    vs->freeFrame(vf);
+    return rc;
+}
+static int clip_super_to_device(DevRef *r, int n, VSNode *super, const SuperGeo *g, VSFrameContext *ctx, const VSAPI *vs) {
+    const VSFrame *sf = vs->getFrameFilter(n, super, ctx);
+    const int rc = super_to_device(r, sf, g, vs);
+    vs->freeFrame(sf);
+    return rc;
+}
+/* mv.BlockFPS / mv.FlowFPS: AssumeFPS sets the _DurationNum / _DurationDen frame properties (src/MVBlockFPS.c:989-1014, src/MVFlowFPS.c:881-900) */
+static void assume_fps(VSMap *out, const char *name, int64_t num, int64_t den, VSCore *core, const VSAPI *vs) {
+    VSNode *node = vs->mapGetNode(out, "clip", 0, NULL);
+    VSMap *args = vs->createMap();
+    vs->mapSetNode(args, "clip", node, maReplace);
+    vs->freeNode(node);
+    vs->mapSetInt(args, "fpsnum", num, maReplace);
+    vs->mapSetInt(args, "fpsden", den, maReplace);
+    VSPlugin *std = vs->getPluginByID("com.vapoursynth.std", core);
+    VSMap *ret = vs->invoke(std, "AssumeFPS", args);
+    vs->freeMap(args);
+    if (vs->mapGetError(ret)) {
+        char msg[600];
+        snprintf(msg, sizeof(msg), "%s: Failed to invoke AssumeFPS. Error message: %s", name, vs->mapGetError(ret));
+        vs->mapSetError(out, msg);
+        vs->freeMap(ret);
+        return;
+    }
+    node = vs->mapGetNode(ret, "clip", 0, NULL);
+    vs->freeMap(ret);
+    vs->mapSetNode(out, "clip", node, maReplace);
+    vs->freeNode(node);
+}
+
 /* ------------------------------------------------------------------------------------------------ mv.Degrain1..6 */
 
 typedef struct DegrainData {
+    Consumer c;
     VSNode *node, *super, *vectors[12];
     const VSVideoInfo *vi;
     int radius;
-    mvx_super *sup; SuperGeo geo;
     mvx_degrain *dg;
     mvx_analysis_data ad[12];
     AnalyseData *an[12]; /* the mv.Analyse instances behind the vector clips, where they are this plugin's (r6: their vectors are read on the device) */
     ptrdiff_t pitch[3]; /* device pitch of clip / output planes */
-    int blobSize;
-    char name[16];
-    Gate gate;
 } DegrainData;
 
 typedef struct FirstFrameReq { const VSAPI *vs; VSNode *node; } FirstFrameReq;
@@ -1788,28 +1927,22 @@ static const VSFrame *VS_CC degrainGetFrameUngated(int n, int reason, void *inst
     void *blobArena[12];
     LaWindow *blobHeld[12];
     memset(refs, 0, sizeof(refs)); memset(blobArena, 0, sizeof(blobArena)); memset(blobHeld, 0, sizeof(blobHeld));
-    int rc = 0;
-    void *srcArena = NULL, *dsrc[3];
-    rc = upload_plane_set(dsrc, &srcArena, src, d->pitch, np, bps, vs);
-    size_t dstOff[3], dstBytes = 0;
-    for (int p = 0; p < np; p++) { dstOff[p] = dstBytes; dstBytes += (size_t)d->pitch[p] * vs->getFrameHeight(src, p); }
-    void *dstArena = shell_alloc(dstBytes);
-    if (!rc && (!srcArena || !dstArena)) rc = MVX_E_NOMEM;
-    for (int p = 0; p < np && !rc; p++) { job.src[p] = dsrc[p]; job.dst[p] = (char *)dstArena + dstOff[p]; }
+    void *srcArena = NULL, *dstArena = NULL, *dsrc[3], *ddst[3];
+    int height[3] = { 0, 0, 0 };
+    for (int p = 0; p < np; p++) height[p] = vs->getFrameHeight(src, p);
+    int rc = upload_plane_set(dsrc, &srcArena, src, d->pitch, np, bps, vs);
+    if (!rc) rc = dst_plane_set(ddst, &dstArena, d->pitch, height, np);
+    for (int p = 0; p < np && !rc; p++) { job.src[p] = dsrc[p]; job.dst[p] = ddst[p]; }
     for (int r = 0; r < nr && !rc; r++) {
         const void *onDevice = la_device_blob(d->an[r], n, &blobHeld[r]);
         if (onDevice) job.blobs[r] = (void *)onDevice; /* (the window that made the frame's property: the same bytes) */
         else {
-            const VSFrame *vf = vs->getFrameFilter(n, d->vectors[r], ctx);
-            rc = blob_to_device(&blobArena[r], NULL, &d->ad[r], vf, vs);
+            rc = clip_blob_to_device(&blobArena[r], n, d->vectors[r], &d->ad[r], ctx, vs);
             job.blobs[r] = blobArena[r];
-            vs->freeFrame(vf);
         }
         const int nref = (r & 1) ? n - d->ad[r].nDeltaFrame : n + d->ad[r].nDeltaFrame;
         if (!rc && nref >= 0 && nref < d->vi->numFrames) {
-            const VSFrame *sf = vs->getFrameFilter(nref, d->super, ctx);
-            rc = super_to_device(&refs[r], sf, &d->geo, vs);
-            vs->freeFrame(sf);
+            rc = clip_super_to_device(&refs[r], nref, d->super, &d->c.geo, ctx, vs);
             for (int p = 0; p < 3; p++) job.refs[r][p] = refs[r].plane[p];
         }
     }
@@ -1829,10 +1962,8 @@ static const VSFrame *VS_CC degrainGetFrameUngated(int n, int reason, void *inst
     if (dstArena) mvx_dev_free(dstArena);
     vs->freeFrame(src);
     if (rc) {
-        char msg[MVX_ERRLEN + 64];
-        snprintf(msg, sizeof(msg), "%s: %s", d->name, rc == MVX_E_ARG ? "vector clip frame without matching MVTools_vectors property." : rc == MVX_E_NOMEM ? "out of memory." : mvx_last_error());
         if (dst) vs->freeFrame(dst);
-        vs->setFilterError(msg, ctx);
+        consumer_frame_error(d->c.name, rc, 1, ctx, vs);
         return NULL;
     }
     prof_add(PF_GF_DEGRAIN, tgf);
@@ -1840,45 +1971,22 @@ static const VSFrame *VS_CC degrainGetFrameUngated(int n, int reason, void *inst
     return dst;
 }
 
-/* (the admission gate around the filter proper: arInitial takes the permit, whatever ends the request -- the frame, a filter error, arError -- returns it) */
-static const VSFrame *VS_CC degrainGetFrame(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
-    DegrainData *d = (DegrainData *)inst;
-    if (reason == arInitial) gate_enter(&d->gate, n, fd);
-    const VSFrame *f = degrainGetFrameUngated(n, reason, inst, fd, ctx, core, vs);
-    if (reason != arInitial || f) gate_leave(&d->gate, fd);
-    return f;
-}
-
-static void VS_CC degrainFree(void *inst, VSCore *core, const VSAPI *vs) {
-    (void)core;
-    DegrainData *d = (DegrainData *)inst;
-    vs->freeNode(d->node); vs->freeNode(d->super);
-    for (int r = 0; r < 2 * d->radius; r++) vs->freeNode(d->vectors[r]);
-    mvx_degrain_destroy(d->dg);
-    mvx_super_destroy(d->sup);
-    gate_free(&d->gate);
-    free(d);
-}
-
 static void VS_CC degrainCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
     warm_barrier();
     const int radius = (int)(intptr_t)user;
+    static const char *const names[] = { "Degrain1", "Degrain2", "Degrain3", "Degrain4", "Degrain5", "Degrain6" };
     static const char *vnames[] = { "mvbw", "mvfw", "mvbw2", "mvfw2", "mvbw3", "mvfw3", "mvbw4", "mvfw4", "mvbw5", "mvfw5", "mvbw6", "mvfw6" };
-    DegrainData *d = (DegrainData *)calloc(1, sizeof(*d));
-    gate_init(&d->gate);
+    DegrainData *d = (DegrainData *)consumer_new(sizeof(*d), names[radius - 1], degrainGetFrameUngated, mvx_degrain_destroy_engine);
+    const char *name = d->c.name;
     d->radius = radius;
-    snprintf(d->name, sizeof(d->name), "Degrain%d", radius);
     char err[1400] = "";
     mvx_degrain_args a;
     a.radius = radius; a.thsad = opt_int64(in, "thsad", vs); a.thsadc = opt_int64(in, "thsadc", vs); a.plane = opt_int(in, "plane", vs);
     a.limit = opt_int(in, "limit", vs); a.limitc = opt_int(in, "limitc", vs); a.thscd1 = opt_int64(in, "thscd1", vs); a.thscd2 = opt_int(in, "thscd2", vs);
-    if (a.plane != MVX_UNSET && (a.plane < 0 || a.plane > 4)) snprintf(err, sizeof(err), "%s: plane must be between 0 and 4 (inclusive).", d->name);
-    if (!err[0]) {
-        d->super = vs->mapGetNode(in, "super", 0, NULL);
-        d->sup = super_from_props(d->super, d->name, err, sizeof(err), vs);
-    }
+    if (a.plane != MVX_UNSET && (a.plane < 0 || a.plane > 4)) snprintf(err, sizeof(err), "%s: plane must be between 0 and 4 (inclusive).", name);
+    if (!err[0]) d->super = consumer_super(&d->c, in, err, sizeof(err), vs);
     const int nr = 2 * radius;
-    for (int r = 0; r < nr && !err[0]; r++) d->vectors[r] = vs->mapGetNode(in, vnames[r], 0, NULL);
+    for (int r = 0; r < nr && !err[0]; r++) d->vectors[r] = consumer_node(&d->c, in, vnames[r], vs);
     if (!err[0] && env_long("MVX_VS_PARALLEL_FIRST", 1)) { /* r6: frame 0 of the vector clips is produced CONCURRENTLY (each is a whole look-ahead window of searches: six launches
                                                              * that share the GPU instead of queueing behind each other); the reads below then find the frames in the host's cache */
         pthread_t th[12];
@@ -1887,8 +1995,8 @@ static void VS_CC degrainCreate(const VSMap *in, VSMap *out, void *user, VSCore 
         for (int r = 0; r < nr; r++) { fr[r].vs = vs; fr[r].node = d->vectors[r]; started[r] = pthread_create(&th[r], NULL, first_frame_thread, &fr[r]) == 0; }
         for (int r = 0; r < nr; r++) if (started[r]) pthread_join(th[r], NULL);
     }
-    for (int r = 0; r < nr && !err[0]; r++) adata_from_clip(&d->ad[r], d->vectors[r], d->name, vnames[r], err, sizeof(err), vs);
-    for (int r = 1; r < nr && !err[0]; r++) adata_similar(&d->ad[0], &d->ad[r], d->name, vnames[0], vnames[r], err, sizeof(err));
+    for (int r = 0; r < nr && !err[0]; r++) adata_from_clip(&d->ad[r], d->vectors[r], name, vnames[r], err, sizeof(err), vs);
+    for (int r = 1; r < nr && !err[0]; r++) adata_similar(&d->ad[0], &d->ad[r], name, vnames[0], vnames[r], err, sizeof(err));
     if (!err[0]) { /* src/MVDegrains.cpp:606-640 */
         const char *m = NULL;
         for (int r = 0; r < nr; r++) if (d->ad[r].nDeltaFrame <= 0) m = "cannot use motion vectors with absolute frame references.";
@@ -1900,52 +2008,32 @@ static void VS_CC degrainCreate(const VSMap *in, VSMap *out, void *user, VSCore 
             if (d->ad[2 * k].nDeltaFrame <= d->ad[2 * k - 2].nDeltaFrame) m = "mvbwN must have greater delta than mvbwP.";
             if (d->ad[2 * k + 1].nDeltaFrame <= d->ad[2 * k - 1].nDeltaFrame) m = "mvfwN must have greater delta than mvfwP.";
         }
-        if (m) snprintf(err, sizeof(err), "%s: %s", d->name, m);
+        if (m) snprintf(err, sizeof(err), "%s: %s", name, m);
     }
     if (!err[0]) {
-        d->node = vs->mapGetNode(in, "clip", 0, NULL);
+        d->node = consumer_node(&d->c, in, "clip", vs);
         d->vi = vs->getVideoInfo(d->node);
-        const VSVideoInfo *svi = vs->getVideoInfo(d->super);
-        super_geo(&d->geo, d->sup);
-        if (!mvx_vsh_is_constant_video_format(d->vi) || d->vi->format.bitsPerSample > 16 || d->vi->format.sampleType != stInteger || d->vi->format.subSamplingW > 1 ||
-            d->vi->format.subSamplingH > 1 || (d->vi->format.colorFamily != cfYUV && d->vi->format.colorFamily != cfGray))
-            snprintf(err, sizeof(err), "%s: input clip must be GRAY, 420, 422, 440, or 444, up to 16 bits, with constant dimensions.", d->name);
-        else if (d->geo.si.height != d->vi->height || d->geo.si.super_width != svi->width || d->geo.si.super_height != svi->height || d->geo.si.width != d->vi->width ||
-                 d->vi->format.bitsPerSample != svi->format.bitsPerSample || d->vi->format.subSamplingW != svi->format.subSamplingW || d->vi->format.subSamplingH != svi->format.subSamplingH)
-            snprintf(err, sizeof(err), "%s: wrong source or super clip frame size.", d->name);
+        consumer_check_clip(&d->c, d->vi, vs->getVideoInfo(d->super), 0, err, sizeof(err));
     }
     if (!err[0]) {
-        const int bps = d->vi->format.bytesPerSample;
-        for (int p = 0; p < 3; p++) {
-            const int w = p ? d->vi->width >> d->vi->format.subSamplingW : d->vi->width;
-            d->pitch[p] = ((ptrdiff_t)w * bps + 255) / 256 * 256;
-        }
+        clip_pitches(d->pitch, d->vi, d->vi->format.bytesPerSample);
         char lerr[MVX_ERRLEN];
-        if (mvx_degrain_create(&a, &d->ad[0], d->sup, d->pitch, d->geo.pitch, d->pitch, &d->dg, lerr)) snprintf(err, sizeof(err), "%s", lerr);
-        else if (d->geo.copies > 1) mvx_degrain_set_ref_shadow(d->dg, d->geo.shadowStride); /* every device super frame of this shell carries its copies */
+        if (mvx_degrain_create(&a, &d->ad[0], d->c.sup, d->pitch, d->c.geo.pitch, d->pitch, &d->dg, lerr)) snprintf(err, sizeof(err), "%s", lerr);
+        else if (d->c.geo.copies > 1) mvx_degrain_set_ref_shadow(d->dg, d->c.geo.shadowStride); /* every device super frame of this shell carries its copies */
+        d->c.engine = d->dg;
     }
-    if (!err[0]) d->blobSize = mvx_vectors_size(&d->ad[0]);
     if (!err[0] && env_long("MVX_VS_DEVICE_VECTORS", 1)) for (int r = 0; r < nr; r++) d->an[r] = analyse_lookup(d->vectors[r]);
-    if (err[0]) {
-        vs->mapSetError(out, err);
-        if (d->node) vs->freeNode(d->node);
-        if (d->super) vs->freeNode(d->super);
-        for (int r = 0; r < nr; r++) if (d->vectors[r]) vs->freeNode(d->vectors[r]);
-        if (d->dg) mvx_degrain_destroy(d->dg);
-        if (d->sup) mvx_super_destroy(d->sup);
-        free(d);
-        return;
-    }
+    if (err[0]) { consumer_fail(&d->c, err, out, vs); return; }
     VSFilterDependency deps[14];
     deps[0].source = d->node; deps[0].requestPattern = rpStrictSpatial;
     deps[1].source = d->super; deps[1].requestPattern = rpGeneral;
     for (int r = 0; r < nr; r++) { deps[2 + r].source = d->vectors[r]; deps[2 + r].requestPattern = rpStrictSpatial; }
-    vs->createVideoFilter(out, d->name, d->vi, degrainGetFrame, degrainFree, fmParallel, deps, 2 + nr, d, core);
+    vs->createVideoFilter(out, name, d->vi, consumerGetFrame, consumerFree, fmParallel, deps, 2 + nr, d, core);
 }
 
 /* ------------------------------------------------------------------------------------------------ mv.Compensate */
 
-typedef struct CompData { VSNode *node, *super, *vectors; const VSVideoInfo *vi; mvx_super *sup; SuperGeo geo; mvx_compensate *cp; mvx_analysis_data ad; ptrdiff_t pitch[3]; int blobSize; FieldOpt fo; Gate gate; } CompData;
+typedef struct CompData { Consumer c; VSNode *node, *super, *vectors; const VSVideoInfo *vi; mvx_compensate *cp; mvx_analysis_data ad; ptrdiff_t pitch[3]; FieldOpt fo; } CompData;
 
 static int comp_nref(const CompData *d, int n) { /* src/MVCompensate.c:84-92 */
     if (d->ad.nDeltaFrame > 0) return n + (d->ad.isBackward ? d->ad.nDeltaFrame : -d->ad.nDeltaFrame);
@@ -1987,29 +2075,26 @@ static const VSFrame *VS_CC compGetFrameUngated(int n, int reason, void *inst, v
     }
     DevRef ds, dr;
     memset(&dr, 0, sizeof(dr));
-    int rc = super_to_device(&ds, ssup, &d->geo, vs);
-    if (!rc && rsup) rc = super_to_device(&dr, rsup, &d->geo, vs);
-    void *dblob = NULL;
+    int rc = super_to_device(&ds, ssup, &d->c.geo, vs);
+    if (!rc && rsup) rc = super_to_device(&dr, rsup, &d->c.geo, vs);
+    void *dblob = NULL, *dstArena = NULL, *ddst[3];
     if (!rc) rc = blob_to_device(&dblob, NULL, &d->ad, vf, vs);
-    size_t dstOff[3], dstBytes = 0;
-    for (int p = 0; p < np; p++) { dstOff[p] = dstBytes; dstBytes += (size_t)d->pitch[p] * vs->getFrameHeight(src, p); }
-    void *dstArena = rc ? NULL : mvx_dev_alloc(dstBytes);
-    if (!rc && !dstArena) rc = MVX_E_NOMEM;
+    int height[3] = { 0, 0, 0 };
+    for (int p = 0; p < np; p++) height[p] = vs->getFrameHeight(src, p);
+    if (!rc) rc = dst_plane_set(ddst, &dstArena, d->pitch, height, np);
     mvx_compensate_job job;
     memset(&job, 0, sizeof(job));
     if (!rc) {
         for (int p = 0; p < 3; p++) { job.src_super[p] = ds.plane[p]; job.ref_super[p] = rsup ? dr.plane[p] : NULL; }
-        for (int p = 0; p < np; p++) job.dst[p] = (char *)dstArena + dstOff[p];
+        for (int p = 0; p < np; p++) job.dst[p] = ddst[p];
         job.blob = dblob;
         job.field_shift = fieldShift;
-        if (!rc) rc = mvx_compensate_frames(d->cp, 1, &job, thread_stream());
+        rc = mvx_compensate_frames(d->cp, 1, &job, thread_stream());
     }
     VSFrame *dst = NULL;
     if (!rc) {
         dst = vs->newVideoFrame(&d->vi->format, d->vi->width, d->vi->height, src, core);
-        for (int p = 0; p < np && !rc; p++)
-            rc = timed_download(vs->getWritePtr(dst, p), vs->getStride(dst, p), job.dst[p], d->pitch[p], (size_t)vs->getFrameWidth(dst, p) * bps, (size_t)vs->getFrameHeight(dst, p));
-        if (!rc) rc = mvx_stream_sync(thread_stream());
+        rc = download_plane_set(dst, ddst, d->pitch, np, bps, vs);
     }
     shell_quiesce(rc);
     dev_release(&ds); dev_release(&dr);
@@ -2019,88 +2104,43 @@ static const VSFrame *VS_CC compGetFrameUngated(int n, int reason, void *inst, v
     vs->freeFrame(src);
     if (rc) {
         if (dst) vs->freeFrame(dst);
-        vs->setFilterError(rc == MVX_E_ARG ? "Compensate: vector clip frame without matching MVTools_vectors property." : rc == MVX_E_NOMEM ? "Compensate: out of memory." : mvx_last_error(), ctx);
+        consumer_frame_error("Compensate", rc, 0, ctx, vs);
         return NULL;
     }
     return dst;
 }
 
-/* (the admission gate around the filter proper: arInitial takes the permit, whatever ends the request -- the frame, a filter error, arError -- returns it) */
-static const VSFrame *VS_CC compGetFrame(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
-    CompData *d = (CompData *)inst;
-    if (reason == arInitial) gate_enter(&d->gate, n, fd);
-    const VSFrame *f = compGetFrameUngated(n, reason, inst, fd, ctx, core, vs);
-    if (reason != arInitial || f) gate_leave(&d->gate, fd);
-    return f;
-}
-
-static void VS_CC compFree(void *inst, VSCore *core, const VSAPI *vs) {
-    (void)core;
-    CompData *d = (CompData *)inst;
-    vs->freeNode(d->node); vs->freeNode(d->super); vs->freeNode(d->vectors);
-    mvx_compensate_destroy(d->cp);
-    mvx_super_destroy(d->sup);
-    gate_free(&d->gate);
-    free(d);
-}
-
 static void VS_CC compCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
     warm_barrier();
     (void)user;
-    CompData *d = (CompData *)calloc(1, sizeof(*d));
-    gate_init(&d->gate);
+    CompData *d = (CompData *)consumer_new(sizeof(*d), "Compensate", compGetFrameUngated, mvx_compensate_destroy_engine);
     char err[1400] = "";
     mvx_compensate_args a;
     a.scbehavior = opt_int(in, "scbehavior", vs); a.thsad = opt_int64(in, "thsad", vs); a.thscd1 = opt_int64(in, "thscd1", vs); a.thscd2 = opt_int(in, "thscd2", vs);
-    int e = 0;
-    a.time = vs->mapGetFloat(in, "time", 0, &e);
-    if (e) a.time = 100.0;
+    a.time = opt_float(in, "time", 100.0, vs);
     field_opt(&d->fo, in, vs);
     a.fields = d->fo.fields;
+    d->super = consumer_super(&d->c, in, err, sizeof(err), vs);
+    if (!err[0]) { d->vectors = consumer_node(&d->c, in, "vectors", vs); adata_from_clip(&d->ad, d->vectors, "Compensate", "vectors", err, sizeof(err), vs); }
     if (!err[0]) {
-        d->super = vs->mapGetNode(in, "super", 0, NULL);
-        d->sup = super_from_props(d->super, "Compensate", err, sizeof(err), vs);
-    }
-    if (!err[0]) {
-        d->vectors = vs->mapGetNode(in, "vectors", 0, NULL);
-        adata_from_clip(&d->ad, d->vectors, "Compensate", "vectors", err, sizeof(err), vs);
-    }
-    if (!err[0]) {
-        d->node = vs->mapGetNode(in, "clip", 0, NULL);
+        d->node = consumer_node(&d->c, in, "clip", vs);
         d->vi = vs->getVideoInfo(d->node);
-        super_geo(&d->geo, d->sup);
-        const VSVideoInfo *svi = vs->getVideoInfo(d->super);
-        if (d->geo.si.height != d->vi->height || d->geo.si.width != d->vi->width || d->geo.si.super_width != svi->width || d->geo.si.super_height != svi->height)
-            snprintf(err, sizeof(err), "Compensate: wrong source or super clip frame size.");
+        consumer_check_clip(&d->c, d->vi, vs->getVideoInfo(d->super), 1, err, sizeof(err)); /* (the size first, as MVCompensate.c:535-545) */
     }
     if (!err[0]) {
-        const int bps = d->vi->format.bytesPerSample;
-        for (int p = 0; p < 3; p++) {
-            const int w = p ? d->vi->width >> d->vi->format.subSamplingW : d->vi->width;
-            d->pitch[p] = ((ptrdiff_t)w * bps + 255) / 256 * 256;
-        }
+        clip_pitches(d->pitch, d->vi, d->vi->format.bytesPerSample);
         char lerr[MVX_ERRLEN];
-        if (mvx_compensate_create(&a, &d->ad, d->sup, d->geo.pitch, d->pitch, &d->cp, lerr)) snprintf(err, sizeof(err), "%s", lerr);
+        if (mvx_compensate_create(&a, &d->ad, d->c.sup, d->c.geo.pitch, d->pitch, &d->cp, lerr)) snprintf(err, sizeof(err), "%s", lerr);
+        d->c.engine = d->cp;
     }
-    if (!err[0]) d->blobSize = mvx_vectors_size(&d->ad);
-    if (err[0]) {
-        vs->mapSetError(out, err);
-        if (d->node) vs->freeNode(d->node);
-        if (d->super) vs->freeNode(d->super);
-        if (d->vectors) vs->freeNode(d->vectors);
-        if (d->cp) mvx_compensate_destroy(d->cp);
-        if (d->sup) mvx_super_destroy(d->sup);
-        free(d);
-        return;
-    }
+    if (err[0]) { consumer_fail(&d->c, err, out, vs); return; }
     VSFilterDependency deps[3] = { { d->node, rpStrictSpatial }, { d->super, rpGeneral }, { d->vectors, rpStrictSpatial } };
-    vs->createVideoFilter(out, "Compensate", d->vi, compGetFrame, compFree, fmParallel, deps, 3, d, core);
+    vs->createVideoFilter(out, "Compensate", d->vi, consumerGetFrame, consumerFree, fmParallel, deps, 3, d, core);
 }
 
 /* ------------------------------------------------------------------------------------------------ mv.BlockFPS */
 
-typedef struct FpsData { VSNode *node, *super, *mvbw, *mvfw; const VSVideoInfo *oldvi; VSVideoInfo vi; mvx_super *sup; SuperGeo geo; mvx_blockfps *bf;
-                         mvx_analysis_data bw, fw; ptrdiff_t pitch[3]; int blobSize; Gate gate; } FpsData;
+typedef struct FpsData { Consumer c; VSNode *node, *super, *mvbw, *mvfw; const VSVideoInfo *oldvi; VSVideoInfo vi; mvx_blockfps *bf; mvx_analysis_data bw, fw; ptrdiff_t pitch[3]; } FpsData;
 
 static int fps_min(int a, int b) { return a < b ? a : b; }
 
@@ -2133,37 +2173,31 @@ static const VSFrame *VS_CC fpsGetFrameUngated(int n, int reason, void *inst, vo
     mvx_blockfps_job job;
     memset(&job, 0, sizeof(job));
     job.time256 = time256;
-    void *arenaL = NULL, *arenaR = NULL, *dl[3], *dr[3], *blobF = NULL, *blobB = NULL;
+    void *arenaL = NULL, *arenaR = NULL, *dstArena = NULL, *dl[3], *dr[3], *ddst[3], *blobF = NULL, *blobB = NULL;
+    int height[3] = { 0, 0, 0 };
+    for (int p = 0; p < np; p++) height[p] = vs->getFrameHeight(cl, p);
     int rc = upload_plane_set(dl, &arenaL, cl, d->pitch, np, bps, vs);
     if (!rc) rc = upload_plane_set(dr, &arenaR, cr, d->pitch, np, bps, vs);
-    size_t dstOff[3], dstBytes = 0;
-    for (int p = 0; p < np; p++) { dstOff[p] = dstBytes; dstBytes += (size_t)d->pitch[p] * vs->getFrameHeight(cl, p); }
-    void *dstArena = shell_alloc(dstBytes);
-    if (!rc && (!arenaL || !arenaR || !dstArena)) rc = MVX_E_NOMEM;
-    for (int p = 0; p < np && !rc; p++) { job.clip_left[p] = dl[p]; job.clip_right[p] = dr[p]; job.dst[p] = (char *)dstArena + dstOff[p]; }
+    if (!rc) rc = dst_plane_set(ddst, &dstArena, d->pitch, height, np);
+    for (int p = 0; p < np && !rc; p++) { job.clip_left[p] = dl[p]; job.clip_right[p] = dr[p]; job.dst[p] = ddst[p]; }
     DevRef ds, dr2;
     memset(&ds, 0, sizeof(ds)); memset(&dr2, 0, sizeof(dr2));
     if (!rc && good) {
-        const VSFrame *sl = vs->getFrameFilter(nleft, d->super, ctx), *sr = vs->getFrameFilter(nright, d->super, ctx);
-        const VSFrame *vf = vs->getFrameFilter(nright, d->mvfw, ctx), *vb = vs->getFrameFilter(nleft, d->mvbw, ctx);
-        rc = super_to_device(&ds, sl, &d->geo, vs);
-        if (!rc) rc = super_to_device(&dr2, sr, &d->geo, vs);
-        if (!rc) rc = blob_to_device(&blobF, NULL, &d->fw, vf, vs);
-        if (!rc) rc = blob_to_device(&blobB, NULL, &d->bw, vb, vs);
+        rc = clip_super_to_device(&ds, nleft, d->super, &d->c.geo, ctx, vs);
+        if (!rc) rc = clip_super_to_device(&dr2, nright, d->super, &d->c.geo, ctx, vs);
+        if (!rc) rc = clip_blob_to_device(&blobF, nright, d->mvfw, &d->fw, ctx, vs);
+        if (!rc) rc = clip_blob_to_device(&blobB, nleft, d->mvbw, &d->bw, ctx, vs);
         for (int p = 0; p < 3; p++) { job.src_super[p] = ds.plane[p]; job.ref_super[p] = dr2.plane[p]; }
         job.blob_fw = blobF; job.blob_bw = blobB;
-        vs->freeFrame(sl); vs->freeFrame(sr); vs->freeFrame(vf); vs->freeFrame(vb);
     }
     if (!rc) rc = mvx_blockfps_frames(d->bf, 1, &job, thread_stream());
     VSFrame *dst = NULL;
     if (!rc) {
         dst = vs->newVideoFrame(&d->vi.format, d->vi.width, d->vi.height, cl, core);
-        for (int p = 0; p < np && !rc; p++)
-            rc = timed_download(vs->getWritePtr(dst, p), vs->getStride(dst, p), job.dst[p], d->pitch[p], (size_t)vs->getFrameWidth(dst, p) * bps, (size_t)vs->getFrameHeight(dst, p));
-        if (!rc) rc = mvx_stream_sync(thread_stream());
+        rc = download_plane_set(dst, ddst, d->pitch, np, bps, vs);
     }
-    dev_release(&ds); dev_release(&dr2);
     shell_quiesce(rc);
+    dev_release(&ds); dev_release(&dr2);
     if (blobF) mvx_dev_free(blobF);
     if (blobB) mvx_dev_free(blobB);
     if (arenaL) mvx_dev_free(arenaL);
@@ -2172,175 +2206,49 @@ static const VSFrame *VS_CC fpsGetFrameUngated(int n, int reason, void *inst, vo
     vs->freeFrame(cl); vs->freeFrame(cr);
     if (rc) {
         if (dst) vs->freeFrame(dst);
-        vs->setFilterError(rc == MVX_E_ARG ? "BlockFPS: vector clip frame without matching MVTools_vectors property." : rc == MVX_E_NOMEM ? "BlockFPS: out of memory." : mvx_last_error(), ctx);
+        consumer_frame_error("BlockFPS", rc, 0, ctx, vs);
         return NULL;
     }
     return dst;
 }
 
-/* (the admission gate around the filter proper: arInitial takes the permit, whatever ends the request -- the frame, a filter error, arError -- returns it) */
-static const VSFrame *VS_CC fpsGetFrame(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
-    FpsData *d = (FpsData *)inst;
-    if (reason == arInitial) gate_enter(&d->gate, n, fd);
-    const VSFrame *f = fpsGetFrameUngated(n, reason, inst, fd, ctx, core, vs);
-    if (reason != arInitial || f) gate_leave(&d->gate, fd);
-    return f;
-}
-
-static void VS_CC fpsFree(void *inst, VSCore *core, const VSAPI *vs) {
-    (void)core;
-    FpsData *d = (FpsData *)inst;
-    vs->freeNode(d->node); vs->freeNode(d->super); vs->freeNode(d->mvbw); vs->freeNode(d->mvfw);
-    mvx_blockfps_destroy(d->bf);
-    mvx_super_destroy(d->sup);
-    gate_free(&d->gate);
-    free(d);
-}
-
 static void VS_CC fpsCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
     warm_barrier();
     (void)user;
-    FpsData *d = (FpsData *)calloc(1, sizeof(*d));
-    gate_init(&d->gate);
+    FpsData *d = (FpsData *)consumer_new(sizeof(*d), "BlockFPS", fpsGetFrameUngated, mvx_blockfps_destroy_engine);
     char err[1400] = "";
     mvx_blockfps_args a;
     a.num = opt_int64(in, "num", vs); a.den = opt_int64(in, "den", vs); a.mode = opt_int(in, "mode", vs); a.blend = opt_int(in, "blend", vs);
     a.thscd1 = opt_int64(in, "thscd1", vs); a.thscd2 = opt_int(in, "thscd2", vs);
-    int e = 0;
-    a.ml = vs->mapGetFloat(in, "ml", 0, &e);
-    if (e) a.ml = 100.0;
+    a.ml = opt_float(in, "ml", 100.0, vs);
     if (a.mode != MVX_UNSET && (a.mode < 0 || a.mode > 8)) snprintf(err, sizeof(err), "BlockFPS: mode must be between 0 and 8 (inclusive).");
-    if (!err[0]) { d->super = vs->mapGetNode(in, "super", 0, NULL); d->sup = super_from_props(d->super, "BlockFPS", err, sizeof(err), vs); }
-    if (!err[0]) { d->mvbw = vs->mapGetNode(in, "mvbw", 0, NULL); adata_from_clip(&d->bw, d->mvbw, "BlockFPS", "mvbw", err, sizeof(err), vs); }
-    if (!err[0]) { d->mvfw = vs->mapGetNode(in, "mvfw", 0, NULL); adata_from_clip(&d->fw, d->mvfw, "BlockFPS", "mvfw", err, sizeof(err), vs); }
+    if (!err[0]) d->super = consumer_super(&d->c, in, err, sizeof(err), vs);
+    if (!err[0]) { d->mvbw = consumer_node(&d->c, in, "mvbw", vs); adata_from_clip(&d->bw, d->mvbw, "BlockFPS", "mvbw", err, sizeof(err), vs); }
+    if (!err[0]) { d->mvfw = consumer_node(&d->c, in, "mvfw", vs); adata_from_clip(&d->fw, d->mvfw, "BlockFPS", "mvfw", err, sizeof(err), vs); }
     if (!err[0]) {
-        d->node = vs->mapGetNode(in, "clip", 0, NULL);
+        d->node = consumer_node(&d->c, in, "clip", vs);
         d->oldvi = vs->getVideoInfo(d->node);
         d->vi = *d->oldvi;
-        super_geo(&d->geo, d->sup);
-        const int bps = d->vi.format.bytesPerSample;
-        for (int p = 0; p < 3; p++) {
-            const int w = p ? d->vi.width >> d->vi.format.subSamplingW : d->vi.width;
-            d->pitch[p] = ((ptrdiff_t)w * bps + 255) / 256 * 256;
-        }
+        clip_pitches(d->pitch, &d->vi, d->vi.format.bytesPerSample);
         char lerr[MVX_ERRLEN];
-        if (mvx_blockfps_create(&a, &d->bw, &d->fw, d->sup, d->oldvi->numFrames, d->oldvi->fpsNum, d->oldvi->fpsDen, d->geo.pitch, d->pitch, d->pitch, &d->bf, lerr))
+        if (mvx_blockfps_create(&a, &d->bw, &d->fw, d->c.sup, d->oldvi->numFrames, d->oldvi->fpsNum, d->oldvi->fpsDen, d->c.geo.pitch, d->pitch, d->pitch, &d->bf, lerr))
             snprintf(err, sizeof(err), "%s", lerr);
-        else if (!mvx_vsh_is_constant_video_format(&d->vi) || d->vi.format.bitsPerSample > 16 || d->vi.format.sampleType != stInteger || d->vi.format.subSamplingW > 1 ||
-                 d->vi.format.subSamplingH > 1 || (d->vi.format.colorFamily != cfYUV && d->vi.format.colorFamily != cfGray))
-            snprintf(err, sizeof(err), "BlockFPS: input clip must be GRAY, 420, 422, 440, or 444, up to 16 bits, with constant dimensions.");
+        else consumer_check_clip(&d->c, &d->vi, vs->getVideoInfo(d->super), 0, err, sizeof(err));
+        d->c.engine = d->bf;
     }
-    if (err[0]) {
-        vs->mapSetError(out, err);
-        if (d->node) vs->freeNode(d->node);
-        if (d->super) vs->freeNode(d->super);
-        if (d->mvbw) vs->freeNode(d->mvbw);
-        if (d->mvfw) vs->freeNode(d->mvfw);
-        if (d->bf) mvx_blockfps_destroy(d->bf);
-        if (d->sup) mvx_super_destroy(d->sup);
-        free(d);
-        return;
-    }
+    if (err[0]) { consumer_fail(&d->c, err, out, vs); return; }
     mvx_blockfps_info info;
     mvx_blockfps_get_info(d->bf, &info);
     d->vi.numFrames = info.num_frames; d->vi.fpsNum = info.fps_num; d->vi.fpsDen = info.fps_den;
-    d->blobSize = mvx_vectors_size(&d->bw);
     VSFilterDependency deps[4] = { { d->node, rpGeneral }, { d->super, rpGeneral }, { d->mvbw, rpGeneral }, { d->mvfw, rpGeneral } };
-    vs->createVideoFilter(out, "BlockFPS", &d->vi, fpsGetFrame, fpsFree, fmParallel, deps, 4, d, core);
-    /* AssumeFPS sets the _DurationNum / _DurationDen frame properties (src/MVBlockFPS.c:989-1014) */
-    VSNode *node = vs->mapGetNode(out, "clip", 0, NULL);
-    VSMap *args = vs->createMap();
-    vs->mapSetNode(args, "clip", node, maReplace);
-    vs->freeNode(node);
-    vs->mapSetInt(args, "fpsnum", info.fps_num, maReplace);
-    vs->mapSetInt(args, "fpsden", info.fps_den, maReplace);
-    VSPlugin *std = vs->getPluginByID("com.vapoursynth.std", core);
-    VSMap *ret = vs->invoke(std, "AssumeFPS", args);
-    vs->freeMap(args);
-    if (vs->mapGetError(ret)) {
-        char msg[600];
-        snprintf(msg, sizeof(msg), "BlockFPS: Failed to invoke AssumeFPS. Error message: %s", vs->mapGetError(ret));
-        vs->mapSetError(out, msg);
-        vs->freeMap(ret);
-        return;
-    }
-    node = vs->mapGetNode(ret, "clip", 0, NULL);
-    vs->freeMap(ret);
-    vs->mapSetNode(out, "clip", node, maReplace);
-    vs->freeNode(node);
-}
-
-/* ------------------------------------------------------------------------------------------------ the per-sample filters: shared plumbing
- * mv.FlowInter / mv.FlowFPS / mv.Flow / mv.FlowBlur / mv.Mask (registered with MVX_VS_FLOW=1, see the entry point).  Where the reference asks its
- * mv.Finest node for a frame these filters ask the super clip: the library reads the sub-pel planes of the super frame directly (mvtools_amd.h), so
- * no Finest node exists.  One mvx_*_frames call per output frame, on the thread's stream. */
-
-/* device pitches of clip and output planes: rows of 256 bytes */
-static void clip_pitches(ptrdiff_t pitch[3], const VSVideoInfo *vi, int bps) {
-    for (int p = 0; p < 3; p++) {
-        const int w = p ? vi->width >> vi->format.subSamplingW : vi->width;
-        pitch[p] = ((ptrdiff_t)w * bps + 255) / 256 * 256;
-    }
-}
-/* the clip check of MVFlowInter.c:644, MVFlowFPS.c:794, MVFlow.cpp:526, MVFlowBlur.c:514 */
-static int flow_clip_ok(const VSVideoInfo *vi) {
-    return mvx_vsh_is_constant_video_format(vi) && vi->format.bitsPerSample <= 16 && vi->format.sampleType == stInteger && vi->format.subSamplingW <= 1 &&
-           vi->format.subSamplingH <= 1 && (vi->format.colorFamily == cfYUV || vi->format.colorFamily == cfGray);
-}
-/* The kernels address the clip's planes with the vector clip's geometry, which creation ties to the super clip's: a clip of another size or format
- * than the one the super clip was made from would be read outside its planes.  (The reference does not check this.) */
-static int flow_clip_is_supers(const VSVideoInfo *vi, const VSVideoInfo *svi, const SuperGeo *g) {
-    return g->si.width == vi->width && g->si.height == vi->height && vi->format.bitsPerSample == svi->format.bitsPerSample && vi->format.colorFamily == svi->format.colorFamily &&
-           vi->format.subSamplingW == svi->format.subSamplingW && vi->format.subSamplingH == svi->format.subSamplingH;
-}
-/* one arena for the planes of an output frame */
-static int dst_plane_set(void *dst[3], void **arena, const ptrdiff_t pitch[3], const int height[3], int nplanes) {
-    size_t off[3], total = 0;
-    for (int p = 0; p < nplanes; p++) { off[p] = total; total += (size_t)pitch[p] * (size_t)height[p]; }
-    for (int p = 0; p < 3; p++) dst[p] = NULL;
-    *arena = shell_alloc(total);
-    if (!*arena) return MVX_E_NOMEM;
-    for (int p = 0; p < nplanes; p++) dst[p] = (char *)*arena + off[p];
-    return 0;
-}
-/* the finished planes -> the host frame; complete on return */
-static int download_plane_set(VSFrame *dst, void *const src[3], const ptrdiff_t pitch[3], int nplanes, int bps, const VSAPI *vs) {
-    int rc = 0;
-    for (int p = 0; p < nplanes && !rc; p++)
-        rc = timed_download(vs->getWritePtr(dst, p), vs->getStride(dst, p), src[p], pitch[p], (size_t)vs->getFrameWidth(dst, p) * bps, (size_t)vs->getFrameHeight(dst, p));
-    if (!rc) rc = mvx_stream_sync(thread_stream());
-    return rc;
-}
-static void flow_frame_error(const char *name, int rc, VSFrameContext *ctx, const VSAPI *vs) {
-    char msg[96];
-    if (rc != MVX_E_ARG && rc != MVX_E_NOMEM) { vs->setFilterError(mvx_last_error(), ctx); return; }
-    snprintf(msg, sizeof(msg), "%s: %s", name, rc == MVX_E_ARG ? "vector clip frame without matching MVTools_vectors property." : "out of memory.");
-    vs->setFilterError(msg, ctx);
-}
-static double opt_float(const VSMap *in, const char *key, double def, const VSAPI *vs) {
-    int e = 0;
-    const double v = vs->mapGetFloat(in, key, 0, &e);
-    return e ? def : v;
-}
-/* MVTools_vectors of frame n of a vector clip -> device; 0 or an MVX_E_* code */
-static int clip_blob_to_device(void **dblob, int n, VSNode *vectors, const mvx_analysis_data *ad, VSFrameContext *ctx, const VSAPI *vs) {
-    const VSFrame *vf = vs->getFrameFilter(n, vectors, ctx);
-    const int rc = blob_to_device(dblob, NULL, ad, vf, vs);
-    vs->freeFrame(vf);
-    return rc;
-}
-static int clip_super_to_device(DevRef *r, int n, VSNode *super, const SuperGeo *g, VSFrameContext *ctx, const VSAPI *vs) {
-    const VSFrame *sf = vs->getFrameFilter(n, super, ctx);
-    const int rc = super_to_device(r, sf, g, vs);
-    vs->freeFrame(sf);
-    return rc;
+    vs->createVideoFilter(out, "BlockFPS", &d->vi, consumerGetFrame, consumerFree, fmParallel, deps, 4, d, core);
+    assume_fps(out, "BlockFPS", info.fps_num, info.fps_den, core, vs);
 }
 
 /* ------------------------------------------------------------------------------------------------ mv.FlowInter / mv.FlowFPS (one engine, one shell) */
 
-typedef struct FlowData { VSNode *node, *super, *mvbw, *mvfw; const VSVideoInfo *oldvi; VSVideoInfo vi; mvx_super *sup; SuperGeo geo; mvx_flow *fl;
-                          mvx_analysis_data bw, fw; ptrdiff_t pitch[3]; int fps /* FlowFPS, else FlowInter */, extra /* the Extra formula's second pair of vectors is read */;
-                          const char *name; Gate gate; } FlowData;
+typedef struct FlowData { Consumer c; VSNode *node, *super, *mvbw, *mvfw; const VSVideoInfo *oldvi; VSVideoInfo vi; mvx_flow *fl; mvx_analysis_data bw, fw; ptrdiff_t pitch[3];
+                          int fps /* FlowFPS, else FlowInter */, extra /* the Extra formula's second pair of vectors is read */; } FlowData;
 
 static const VSFrame *VS_CC flowGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
     (void)fd;
@@ -2383,8 +2291,8 @@ static const VSFrame *VS_CC flowGetFrameUngated(int n, int reason, void *inst, v
     DevRef sl, sr;
     memset(&sl, 0, sizeof(sl)); memset(&sr, 0, sizeof(sr));
     if (!rc && good) { /* (else all four stay NULL: Blend or the left frame) */
-        rc = clip_super_to_device(&sl, nleft, d->super, &d->geo, ctx, vs);
-        if (!rc) rc = clip_super_to_device(&sr, nright, d->super, &d->geo, ctx, vs);
+        rc = clip_super_to_device(&sl, nleft, d->super, &d->c.geo, ctx, vs);
+        if (!rc) rc = clip_super_to_device(&sr, nright, d->super, &d->c.geo, ctx, vs);
         if (!rc) rc = clip_blob_to_device(&blob[0], nright, d->mvfw, &d->fw, ctx, vs);
         if (!rc) rc = clip_blob_to_device(&blob[1], nleft, d->mvbw, &d->bw, ctx, vs);
         if (!rc && d->extra) rc = clip_blob_to_device(&blob[2], nleft, d->mvfw, &d->fw, ctx, vs);
@@ -2407,38 +2315,18 @@ static const VSFrame *VS_CC flowGetFrameUngated(int n, int reason, void *inst, v
     vs->freeFrame(cl); vs->freeFrame(cr);
     if (rc) {
         if (dst) vs->freeFrame(dst);
-        flow_frame_error(d->name, rc, ctx, vs);
+        consumer_frame_error(d->c.name, rc, 0, ctx, vs);
         return NULL;
     }
     return dst;
 }
 
-/* (the admission gate around the filter proper: arInitial takes the permit, whatever ends the request -- the frame, a filter error, arError -- returns it) */
-static const VSFrame *VS_CC flowGetFrame(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
-    FlowData *d = (FlowData *)inst;
-    if (reason == arInitial) gate_enter(&d->gate, n, fd);
-    const VSFrame *f = flowGetFrameUngated(n, reason, inst, fd, ctx, core, vs);
-    if (reason != arInitial || f) gate_leave(&d->gate, fd);
-    return f;
-}
-
-static void VS_CC flowFree(void *inst, VSCore *core, const VSAPI *vs) {
-    (void)core;
-    FlowData *d = (FlowData *)inst;
-    vs->freeNode(d->node); vs->freeNode(d->super); vs->freeNode(d->mvbw); vs->freeNode(d->mvfw);
-    mvx_flow_destroy(d->fl);
-    mvx_super_destroy(d->sup);
-    gate_free(&d->gate);
-    free(d);
-}
-
 /* user != NULL: mv.FlowFPS (src/MVFlowFPS.c:565-900), else mv.FlowInter (src/MVFlowInter.c:473-678) */
 static void VS_CC flowCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
     warm_barrier();
-    FlowData *d = (FlowData *)calloc(1, sizeof(*d));
-    gate_init(&d->gate);
+    FlowData *d = (FlowData *)consumer_new(sizeof(*d), user ? "FlowFPS" : "FlowInter", flowGetFrameUngated, mvx_flow_destroy_engine);
+    const char *name = d->c.name;
     d->fps = user != NULL;
-    d->name = d->fps ? "FlowFPS" : "FlowInter";
     char err[1400] = "";
     mvx_flowinter_args ai;
     mvx_flowfps_args af;
@@ -2447,70 +2335,35 @@ static void VS_CC flowCreate(const VSMap *in, VSMap *out, void *user, VSCore *co
     ai.thscd1 = af.thscd1 = opt_int64(in, "thscd1", vs); ai.thscd2 = af.thscd2 = opt_int(in, "thscd2", vs);
     af.num = opt_int64(in, "num", vs); af.den = opt_int64(in, "den", vs); af.mask = opt_int(in, "mask", vs);
     d->extra = d->fps ? (af.mask == MVX_UNSET || af.mask == 2) : 1;
-    d->super = vs->mapGetNode(in, "super", 0, NULL);
-    d->sup = super_from_props(d->super, d->name, err, sizeof(err), vs);
-    if (!err[0]) { d->mvbw = vs->mapGetNode(in, "mvbw", 0, NULL); adata_from_clip(&d->bw, d->mvbw, d->name, "mvbw", err, sizeof(err), vs); }
-    if (!err[0]) { d->mvfw = vs->mapGetNode(in, "mvfw", 0, NULL); adata_from_clip(&d->fw, d->mvfw, d->name, "mvfw", err, sizeof(err), vs); }
+    d->super = consumer_super(&d->c, in, err, sizeof(err), vs);
+    if (!err[0]) { d->mvbw = consumer_node(&d->c, in, "mvbw", vs); adata_from_clip(&d->bw, d->mvbw, name, "mvbw", err, sizeof(err), vs); }
+    if (!err[0]) { d->mvfw = consumer_node(&d->c, in, "mvfw", vs); adata_from_clip(&d->fw, d->mvfw, name, "mvfw", err, sizeof(err), vs); }
     if (!err[0]) {
-        d->node = vs->mapGetNode(in, "clip", 0, NULL);
+        d->node = consumer_node(&d->c, in, "clip", vs);
         d->oldvi = vs->getVideoInfo(d->node);
         d->vi = *d->oldvi;
-        super_geo(&d->geo, d->sup);
         clip_pitches(d->pitch, &d->vi, d->vi.format.bytesPerSample);
         char lerr[MVX_ERRLEN];
-        const int rc = d->fps ? mvx_flowfps_create(&af, &d->bw, &d->fw, d->sup, d->oldvi->numFrames, d->oldvi->fpsNum, d->oldvi->fpsDen, d->geo.pitch, d->pitch, d->pitch, &d->fl, lerr)
-                              : mvx_flowinter_create(&ai, &d->bw, &d->fw, d->sup, d->oldvi->numFrames, d->geo.pitch, d->pitch, d->pitch, &d->fl, lerr);
+        const int rc = d->fps ? mvx_flowfps_create(&af, &d->bw, &d->fw, d->c.sup, d->oldvi->numFrames, d->oldvi->fpsNum, d->oldvi->fpsDen, d->c.geo.pitch, d->pitch, d->pitch, &d->fl, lerr)
+                              : mvx_flowinter_create(&ai, &d->bw, &d->fw, d->c.sup, d->oldvi->numFrames, d->c.geo.pitch, d->pitch, d->pitch, &d->fl, lerr);
         if (rc) snprintf(err, sizeof(err), "%s", lerr);
-        else if (!flow_clip_ok(&d->vi)) snprintf(err, sizeof(err), "%s: input clip must be GRAY, 420, 422, 440, or 444, up to 16 bits, with constant dimensions.", d->name);
-        else if (!flow_clip_is_supers(&d->vi, vs->getVideoInfo(d->super), &d->geo)) snprintf(err, sizeof(err), "%s: wrong source or super clip frame size.", d->name);
+        else consumer_check_clip(&d->c, &d->vi, vs->getVideoInfo(d->super), 0, err, sizeof(err));
+        d->c.engine = d->fl;
     }
-    if (err[0]) {
-        vs->mapSetError(out, err);
-        if (d->node) vs->freeNode(d->node);
-        if (d->super) vs->freeNode(d->super);
-        if (d->mvbw) vs->freeNode(d->mvbw);
-        if (d->mvfw) vs->freeNode(d->mvfw);
-        if (d->fl) mvx_flow_destroy(d->fl);
-        if (d->sup) mvx_super_destroy(d->sup);
-        free(d);
-        return;
-    }
+    if (err[0]) { consumer_fail(&d->c, err, out, vs); return; }
     VSFilterDependency deps[4] = { { d->node, rpGeneral }, { d->super, rpGeneral }, { d->mvbw, rpGeneral }, { d->mvfw, rpGeneral } };
-    if (!d->fps) { /* the output clip is the input's */
-        vs->createVideoFilter(out, d->name, &d->vi, flowGetFrame, flowFree, fmParallel, deps, 4, d, core);
-        return;
+    if (d->fps) { /* (mv.FlowInter's output clip is the input's) */
+        mvx_flow_info info;
+        mvx_flow_get_info(d->fl, &info);
+        d->vi.numFrames = info.num_frames; d->vi.fpsNum = info.fps_num; d->vi.fpsDen = info.fps_den;
     }
-    mvx_flow_info info;
-    mvx_flow_get_info(d->fl, &info);
-    d->vi.numFrames = info.num_frames; d->vi.fpsNum = info.fps_num; d->vi.fpsDen = info.fps_den;
-    vs->createVideoFilter(out, d->name, &d->vi, flowGetFrame, flowFree, fmParallel, deps, 4, d, core);
-    /* AssumeFPS sets the _DurationNum / _DurationDen frame properties (src/MVFlowFPS.c:881-900) */
-    VSNode *node = vs->mapGetNode(out, "clip", 0, NULL);
-    VSMap *args = vs->createMap();
-    vs->mapSetNode(args, "clip", node, maReplace);
-    vs->freeNode(node);
-    vs->mapSetInt(args, "fpsnum", info.fps_num, maReplace);
-    vs->mapSetInt(args, "fpsden", info.fps_den, maReplace);
-    VSPlugin *std = vs->getPluginByID("com.vapoursynth.std", core);
-    VSMap *ret = vs->invoke(std, "AssumeFPS", args);
-    vs->freeMap(args);
-    if (vs->mapGetError(ret)) {
-        char msg[600];
-        snprintf(msg, sizeof(msg), "FlowFPS: Failed to invoke AssumeFPS. Error message: %s", vs->mapGetError(ret));
-        vs->mapSetError(out, msg);
-        vs->freeMap(ret);
-        return;
-    }
-    node = vs->mapGetNode(ret, "clip", 0, NULL);
-    vs->freeMap(ret);
-    vs->mapSetNode(out, "clip", node, maReplace);
-    vs->freeNode(node);
+    vs->createVideoFilter(out, name, &d->vi, consumerGetFrame, consumerFree, fmParallel, deps, 4, d, core);
+    if (d->fps) assume_fps(out, name, d->vi.fpsNum, d->vi.fpsDen, core, vs);
 }
 
 /* ------------------------------------------------------------------------------------------------ mv.Flow */
 
-typedef struct FlowCompData { VSNode *node, *super, *vectors; const VSVideoInfo *vi; mvx_super *sup; SuperGeo geo; mvx_flowcomp *fc; mvx_analysis_data ad; ptrdiff_t pitch[3];
-                              FieldOpt fo; Gate gate; } FlowCompData;
+typedef struct FlowCompData { Consumer c; VSNode *node, *super, *vectors; const VSVideoInfo *vi; mvx_flowcomp *fc; mvx_analysis_data ad; ptrdiff_t pitch[3]; FieldOpt fo; } FlowCompData;
 
 static const VSFrame *VS_CC flowCompGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
     (void)fd;
@@ -2559,7 +2412,7 @@ static const VSFrame *VS_CC flowCompGetFrameUngated(int n, int reason, void *ins
     for (int p = 0; p < np && !rc; p++) { job.clip[p] = dsrc[p]; job.dst[p] = ddst[p]; }
     DevRef dr;
     memset(&dr, 0, sizeof(dr));
-    if (!rc && rsup) rc = super_to_device(&dr, rsup, &d->geo, vs);
+    if (!rc && rsup) rc = super_to_device(&dr, rsup, &d->c.geo, vs);
     if (!rc) rc = clip_blob_to_device(&dblob, n, d->vectors, &d->ad, ctx, vs);
     for (int p = 0; p < 3; p++) job.ref_super[p] = rsup ? dr.plane[p] : NULL; /* NULL: copy of the clip frame */
     job.blob = dblob;
@@ -2578,74 +2431,42 @@ static const VSFrame *VS_CC flowCompGetFrameUngated(int n, int reason, void *ins
     vs->freeFrame(src);
     if (rc) {
         if (dst) vs->freeFrame(dst);
-        flow_frame_error("Flow", rc, ctx, vs);
+        consumer_frame_error("Flow", rc, 0, ctx, vs);
         return NULL;
     }
     return dst;
-}
-
-/* (the admission gate around the filter proper, as flowGetFrame) */
-static const VSFrame *VS_CC flowCompGetFrame(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
-    FlowCompData *d = (FlowCompData *)inst;
-    if (reason == arInitial) gate_enter(&d->gate, n, fd);
-    const VSFrame *f = flowCompGetFrameUngated(n, reason, inst, fd, ctx, core, vs);
-    if (reason != arInitial || f) gate_leave(&d->gate, fd);
-    return f;
-}
-
-static void VS_CC flowCompFree(void *inst, VSCore *core, const VSAPI *vs) {
-    (void)core;
-    FlowCompData *d = (FlowCompData *)inst;
-    vs->freeNode(d->node); vs->freeNode(d->super); vs->freeNode(d->vectors);
-    mvx_flowcomp_destroy(d->fc);
-    mvx_super_destroy(d->sup);
-    gate_free(&d->gate);
-    free(d);
 }
 
 /* src/MVFlow.cpp:391-593 (fields=1 with pel=1 is accepted there and shifts nothing: :265) */
 static void VS_CC flowCompCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
     warm_barrier();
     (void)user;
-    FlowCompData *d = (FlowCompData *)calloc(1, sizeof(*d));
-    gate_init(&d->gate);
+    FlowCompData *d = (FlowCompData *)consumer_new(sizeof(*d), "Flow", flowCompGetFrameUngated, mvx_flowcomp_destroy_engine);
     char err[1400] = "";
     mvx_flowcomp_args a;
     a.time = opt_float(in, "time", 100.0, vs); a.mode = opt_int(in, "mode", vs);
     a.thscd1 = opt_int64(in, "thscd1", vs); a.thscd2 = opt_int(in, "thscd2", vs);
     field_opt(&d->fo, in, vs);
     a.fields = d->fo.fields;
-    d->super = vs->mapGetNode(in, "super", 0, NULL);
-    d->sup = super_from_props(d->super, "Flow", err, sizeof(err), vs);
-    if (!err[0]) { d->vectors = vs->mapGetNode(in, "vectors", 0, NULL); adata_from_clip(&d->ad, d->vectors, "Flow", "vectors", err, sizeof(err), vs); }
+    d->super = consumer_super(&d->c, in, err, sizeof(err), vs);
+    if (!err[0]) { d->vectors = consumer_node(&d->c, in, "vectors", vs); adata_from_clip(&d->ad, d->vectors, "Flow", "vectors", err, sizeof(err), vs); }
     if (!err[0]) {
-        d->node = vs->mapGetNode(in, "clip", 0, NULL);
+        d->node = consumer_node(&d->c, in, "clip", vs);
         d->vi = vs->getVideoInfo(d->node);
-        super_geo(&d->geo, d->sup);
         clip_pitches(d->pitch, d->vi, d->vi->format.bytesPerSample);
         char lerr[MVX_ERRLEN];
-        if (mvx_flowcomp_create(&a, &d->ad, d->sup, d->vi->numFrames, d->geo.pitch, d->pitch, d->pitch, &d->fc, lerr)) snprintf(err, sizeof(err), "%s", lerr);
-        else if (!flow_clip_ok(d->vi)) snprintf(err, sizeof(err), "Flow: input clip must be GRAY, 420, 422, 440, or 444, up to 16 bits, with constant dimensions.");
-        else if (!flow_clip_is_supers(d->vi, vs->getVideoInfo(d->super), &d->geo)) snprintf(err, sizeof(err), "Flow: wrong source or super clip frame size.");
+        if (mvx_flowcomp_create(&a, &d->ad, d->c.sup, d->vi->numFrames, d->c.geo.pitch, d->pitch, d->pitch, &d->fc, lerr)) snprintf(err, sizeof(err), "%s", lerr);
+        else consumer_check_clip(&d->c, d->vi, vs->getVideoInfo(d->super), 0, err, sizeof(err));
+        d->c.engine = d->fc;
     }
-    if (err[0]) {
-        vs->mapSetError(out, err);
-        if (d->node) vs->freeNode(d->node);
-        if (d->super) vs->freeNode(d->super);
-        if (d->vectors) vs->freeNode(d->vectors);
-        if (d->fc) mvx_flowcomp_destroy(d->fc);
-        if (d->sup) mvx_super_destroy(d->sup);
-        free(d);
-        return;
-    }
+    if (err[0]) { consumer_fail(&d->c, err, out, vs); return; }
     VSFilterDependency deps[3] = { { d->node, rpStrictSpatial }, { d->super, rpGeneral }, { d->vectors, rpStrictSpatial } };
-    vs->createVideoFilter(out, "Flow", d->vi, flowCompGetFrame, flowCompFree, fmParallel, deps, 3, d, core);
+    vs->createVideoFilter(out, "Flow", d->vi, consumerGetFrame, consumerFree, fmParallel, deps, 3, d, core);
 }
 
 /* ------------------------------------------------------------------------------------------------ mv.FlowBlur */
 
-typedef struct BlurData { VSNode *node, *super, *mvbw, *mvfw; const VSVideoInfo *vi; mvx_super *sup; SuperGeo geo; mvx_flowblur *fb; mvx_analysis_data bw, fw; ptrdiff_t pitch[3];
-                          Gate gate; } BlurData;
+typedef struct BlurData { Consumer c; VSNode *node, *super, *mvbw, *mvfw; const VSVideoInfo *vi; mvx_flowblur *fb; mvx_analysis_data bw, fw; ptrdiff_t pitch[3]; } BlurData;
 
 static const VSFrame *VS_CC blurGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
     (void)fd;
@@ -2674,7 +2495,7 @@ static const VSFrame *VS_CC blurGetFrameUngated(int n, int reason, void *inst, v
     for (int p = 0; p < np && !rc; p++) { job.clip[p] = dsrc[p]; job.dst[p] = ddst[p]; }
     DevRef ds;
     memset(&ds, 0, sizeof(ds));
-    if (!rc) rc = clip_super_to_device(&ds, n, d->super, &d->geo, ctx, vs);
+    if (!rc) rc = clip_super_to_device(&ds, n, d->super, &d->c.geo, ctx, vs);
     if (!rc && both) rc = clip_blob_to_device(&blobB, n - off, d->mvbw, &d->bw, ctx, vs);
     if (!rc && both) rc = clip_blob_to_device(&blobF, n + off, d->mvfw, &d->fw, ctx, vs);
     for (int p = 0; p < 3; p++) job.super[p] = ds.plane[p];
@@ -2694,74 +2515,41 @@ static const VSFrame *VS_CC blurGetFrameUngated(int n, int reason, void *inst, v
     vs->freeFrame(src);
     if (rc) {
         if (dst) vs->freeFrame(dst);
-        flow_frame_error("FlowBlur", rc, ctx, vs);
+        consumer_frame_error("FlowBlur", rc, 0, ctx, vs);
         return NULL;
     }
     return dst;
-}
-
-/* (the admission gate around the filter proper, as flowGetFrame) */
-static const VSFrame *VS_CC blurGetFrame(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
-    BlurData *d = (BlurData *)inst;
-    if (reason == arInitial) gate_enter(&d->gate, n, fd);
-    const VSFrame *f = blurGetFrameUngated(n, reason, inst, fd, ctx, core, vs);
-    if (reason != arInitial || f) gate_leave(&d->gate, fd);
-    return f;
-}
-
-static void VS_CC blurFree(void *inst, VSCore *core, const VSAPI *vs) {
-    (void)core;
-    BlurData *d = (BlurData *)inst;
-    vs->freeNode(d->node); vs->freeNode(d->super); vs->freeNode(d->mvbw); vs->freeNode(d->mvfw);
-    mvx_flowblur_destroy(d->fb);
-    mvx_super_destroy(d->sup);
-    gate_free(&d->gate);
-    free(d);
 }
 
 /* src/MVFlowBlur.c:346-552 */
 static void VS_CC blurCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
     warm_barrier();
     (void)user;
-    BlurData *d = (BlurData *)calloc(1, sizeof(*d));
-    gate_init(&d->gate);
+    BlurData *d = (BlurData *)consumer_new(sizeof(*d), "FlowBlur", blurGetFrameUngated, mvx_flowblur_destroy_engine);
     char err[1400] = "";
     mvx_flowblur_args a;
     a.blur = opt_float(in, "blur", 50.0, vs); a.prec = opt_int(in, "prec", vs);
     a.thscd1 = opt_int64(in, "thscd1", vs); a.thscd2 = opt_int(in, "thscd2", vs);
-    d->super = vs->mapGetNode(in, "super", 0, NULL);
-    d->sup = super_from_props(d->super, "FlowBlur", err, sizeof(err), vs);
-    if (!err[0]) { d->mvbw = vs->mapGetNode(in, "mvbw", 0, NULL); adata_from_clip(&d->bw, d->mvbw, "FlowBlur", "mvbw", err, sizeof(err), vs); }
-    if (!err[0]) { d->mvfw = vs->mapGetNode(in, "mvfw", 0, NULL); adata_from_clip(&d->fw, d->mvfw, "FlowBlur", "mvfw", err, sizeof(err), vs); }
+    d->super = consumer_super(&d->c, in, err, sizeof(err), vs);
+    if (!err[0]) { d->mvbw = consumer_node(&d->c, in, "mvbw", vs); adata_from_clip(&d->bw, d->mvbw, "FlowBlur", "mvbw", err, sizeof(err), vs); }
+    if (!err[0]) { d->mvfw = consumer_node(&d->c, in, "mvfw", vs); adata_from_clip(&d->fw, d->mvfw, "FlowBlur", "mvfw", err, sizeof(err), vs); }
     if (!err[0]) {
-        d->node = vs->mapGetNode(in, "clip", 0, NULL);
+        d->node = consumer_node(&d->c, in, "clip", vs);
         d->vi = vs->getVideoInfo(d->node);
-        super_geo(&d->geo, d->sup);
         clip_pitches(d->pitch, d->vi, d->vi->format.bytesPerSample);
         char lerr[MVX_ERRLEN];
-        if (mvx_flowblur_create(&a, &d->bw, &d->fw, d->sup, d->vi->numFrames, d->geo.pitch, d->pitch, d->pitch, &d->fb, lerr)) snprintf(err, sizeof(err), "%s", lerr);
-        else if (!flow_clip_ok(d->vi)) snprintf(err, sizeof(err), "FlowBlur: input clip must be GRAY, 420, 422, 440, or 444, up to 16 bits, with constant dimensions.");
-        else if (!flow_clip_is_supers(d->vi, vs->getVideoInfo(d->super), &d->geo)) snprintf(err, sizeof(err), "FlowBlur: wrong source or super clip frame size.");
+        if (mvx_flowblur_create(&a, &d->bw, &d->fw, d->c.sup, d->vi->numFrames, d->c.geo.pitch, d->pitch, d->pitch, &d->fb, lerr)) snprintf(err, sizeof(err), "%s", lerr);
+        else consumer_check_clip(&d->c, d->vi, vs->getVideoInfo(d->super), 0, err, sizeof(err));
+        d->c.engine = d->fb;
     }
-    if (err[0]) {
-        vs->mapSetError(out, err);
-        if (d->node) vs->freeNode(d->node);
-        if (d->super) vs->freeNode(d->super);
-        if (d->mvbw) vs->freeNode(d->mvbw);
-        if (d->mvfw) vs->freeNode(d->mvfw);
-        if (d->fb) mvx_flowblur_destroy(d->fb);
-        if (d->sup) mvx_super_destroy(d->sup);
-        free(d);
-        return;
-    }
+    if (err[0]) { consumer_fail(&d->c, err, out, vs); return; }
     VSFilterDependency deps[4] = { { d->node, rpStrictSpatial }, { d->super, rpStrictSpatial }, { d->mvbw, rpGeneral }, { d->mvfw, rpGeneral } };
-    vs->createVideoFilter(out, "FlowBlur", d->vi, blurGetFrame, blurFree, fmParallel, deps, 4, d, core);
+    vs->createVideoFilter(out, "FlowBlur", d->vi, consumerGetFrame, consumerFree, fmParallel, deps, 4, d, core);
 }
 
 /* ------------------------------------------------------------------------------------------------ mv.Mask */
 
-typedef struct MaskData { VSNode *node, *vectors; const VSVideoInfo *clipvi; VSVideoInfo vi; mvx_mask *mk; mvx_mask_info info; mvx_analysis_data ad;
-                          ptrdiff_t pitch[3]; int kind; Gate gate; } MaskData;
+typedef struct MaskData { Consumer c; VSNode *node, *vectors; const VSVideoInfo *clipvi; VSVideoInfo vi; mvx_mask *mk; mvx_mask_info info; mvx_analysis_data ad; ptrdiff_t pitch[3]; int kind; } MaskData;
 
 static const VSFrame *VS_CC maskGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
     (void)fd;
@@ -2796,45 +2584,26 @@ static const VSFrame *VS_CC maskGetFrameUngated(int n, int reason, void *inst, v
     vs->freeFrame(src);
     if (rc) {
         if (dst) vs->freeFrame(dst);
-        flow_frame_error("Mask", rc, ctx, vs);
+        consumer_frame_error("Mask", rc, 0, ctx, vs);
         return NULL;
     }
     return dst;
-}
-
-/* (the admission gate around the filter proper, as flowGetFrame) */
-static const VSFrame *VS_CC maskGetFrame(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
-    MaskData *d = (MaskData *)inst;
-    if (reason == arInitial) gate_enter(&d->gate, n, fd);
-    const VSFrame *f = maskGetFrameUngated(n, reason, inst, fd, ctx, core, vs);
-    if (reason != arInitial || f) gate_leave(&d->gate, fd);
-    return f;
-}
-
-static void VS_CC maskFree(void *inst, VSCore *core, const VSAPI *vs) {
-    (void)core;
-    MaskData *d = (MaskData *)inst;
-    vs->freeNode(d->node); vs->freeNode(d->vectors);
-    mvx_mask_destroy(d->mk);
-    gate_free(&d->gate);
-    free(d);
 }
 
 /* src/MVMask.c:227-346 */
 static void VS_CC maskCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
     warm_barrier();
     (void)user;
-    MaskData *d = (MaskData *)calloc(1, sizeof(*d));
-    gate_init(&d->gate);
+    MaskData *d = (MaskData *)consumer_new(sizeof(*d), "Mask", maskGetFrameUngated, mvx_mask_destroy_engine);
     char err[1400] = "";
     mvx_mask_args a;
     a.ml = opt_float(in, "ml", 100.0, vs); a.gamma = opt_float(in, "gamma", 1.0, vs); a.kind = opt_int(in, "kind", vs); a.time = opt_float(in, "time", 100.0, vs);
     a.ysc = opt_int(in, "ysc", vs); a.thscd1 = opt_int64(in, "thscd1", vs); a.thscd2 = opt_int(in, "thscd2", vs);
     d->kind = a.kind == MVX_UNSET ? 0 : a.kind;
-    d->vectors = vs->mapGetNode(in, "vectors", 0, NULL);
+    d->vectors = consumer_node(&d->c, in, "vectors", vs);
     adata_from_clip(&d->ad, d->vectors, "Mask", "vectors", err, sizeof(err), vs);
     if (!err[0]) {
-        d->node = vs->mapGetNode(in, "clip", 0, NULL);
+        d->node = consumer_node(&d->c, in, "clip", vs);
         d->clipvi = vs->getVideoInfo(d->node);
         d->vi = *d->clipvi;
         const VSVideoFormat *f = &d->clipvi->format;
@@ -2844,21 +2613,15 @@ static void VS_CC maskCreate(const VSMap *in, VSMap *out, void *user, VSCore *co
         if (mvx_mask_create(&a, &d->ad, &mc, d->pitch, d->pitch, &d->mk, lerr)) snprintf(err, sizeof(err), "%s", lerr);
         else if (!mvx_vsh_is_constant_video_format(d->clipvi) || f->sampleType != stInteger || (f->colorFamily != cfYUV && f->colorFamily != cfGray))
             snprintf(err, sizeof(err), "Mask: input clip must be GRAY8, YUV420P8, YUV422P8, YUV440P8, or YUV444P8, with constant dimensions.");
+        d->c.engine = d->mk;
     }
     if (!err[0]) { /* three 8-bit planes with the clip's subsampling; Gray -> 4:4:4 (src/MVMask.c:328-329) */
         mvx_mask_get_info(d->mk, &d->info);
         if (!vs->queryVideoFormat(&d->vi.format, cfYUV, stInteger, 8, d->info.subsampling_w, d->info.subsampling_h, core)) snprintf(err, sizeof(err), "Mask: the host has no 8-bit YUV format for the mask clip.");
     }
-    if (err[0]) {
-        vs->mapSetError(out, err);
-        if (d->node) vs->freeNode(d->node);
-        if (d->vectors) vs->freeNode(d->vectors);
-        if (d->mk) mvx_mask_destroy(d->mk);
-        free(d);
-        return;
-    }
+    if (err[0]) { consumer_fail(&d->c, err, out, vs); return; }
     VSFilterDependency deps[2] = { { d->node, rpStrictSpatial }, { d->vectors, rpStrictSpatial } };
-    vs->createVideoFilter(out, "Mask", &d->vi, maskGetFrame, maskFree, fmParallel, deps, 2, d, core);
+    vs->createVideoFilter(out, "Mask", &d->vi, consumerGetFrame, consumerFree, fmParallel, deps, 2, d, core);
 }
 
 /* ------------------------------------------------------------------------------------------------ entry point */
