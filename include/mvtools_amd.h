@@ -581,6 +581,79 @@ int mvx_depan_analyse_frames(mvx_depan_analyse *h, int n, const void *const *blo
 int mvx_depan_analyse_host(const mvx_depan_analyse *h, int n, const void *const *blobs, const void *const *masks, ptrdiff_t mask_pitch,
                            const int32_t *top_field, mvx_depan_motion *out);
 
+/* ---- mv.DepanEstimate -------------------------------------------------------------------------------
+ * global motion without a vector clip: pan (and zoom, from two windows) between frame n - 1 and frame n from the peak of the
+ * cross-correlation of a luma window, computed with a power-of-two real 2-D FFT in HIP (csrc/mvx_depan_fft.hip; no FFTW).  The three
+ * entry points mirror the reference's three chained filters: mvx_depan_estimate_spectra replaces depanEstimateStage1GetFrame,
+ * MVDepan.cpp:956-997 (frame_data2d :651-678 and the r2c transform); mvx_depan_estimate_correlate replaces depanEstimateStage2GetFrame,
+ * :1000-1151 (mult_conj_data2d :681-697, the c2r transform, get_motion_vector :700-883, the zoom of :1110-1121, the frame-0 rule);
+ * mvx_depan_estimate_finish replaces depanEstimateStage3GetFrame, :1154-1243.  mvx_depan_estimate_create replaces
+ * depanEstimateCreate, :1271-1433, and touches no device.
+ * The transforms cannot be byte-exact against FFTW, whose order of summation is its own: the spectrum is held to the error bound of a
+ * single-precision radix FFT against a double-precision one, the discrete results (peak position, scene-change decision, zoom branch) are
+ * exact on cases whose margins exceed that error, and dx, dy, zoom and trust are held to a measured multiple of the distance between two
+ * independent FFTs.  Everything after the scan of the correlation surface is host arithmetic in the reference's order
+ * (csrc/mvx_depan_estimate_host.h), bit-exact given the same scan results; the sum behind the mean of the search area is the reference's float
+ * chain in scan order, on the device.  No float atomics: results are identical from run to run and
+ * for any batch size.
+ * Deliberate divergences, continuing the list above:
+ *   8. samples are read in the clip's own type.  The reference passes bytesPerSample (1, 2, 4) to frame_data2d, which compares it with 8
+ *      and 32 (:657-668), so every clip goes through its uint16_t branch: right for 9..16 bits, but an 8-bit clip is read as pairs of
+ *      bytes over 2 * winx bytes per row, past the window and on the last rows past the frame.  The library reads bytes for 8 bits and
+ *      words for 9..16 bits;
+ *   9. float clips are refused at creation (no filter of this library has a float path);
+ *  10. winx (after the halving for zoom) and winy must be powers of two from 8 to 8192, refused at creation otherwise; the automatic
+ *      sizes always qualify on a frame of at least 8 x 8 (16 x 8 with zoom).  A window that leaves the frame -- the second window of
+ *      zoommax != 1 starts at wleft + width / 2, which the reference does not check -- is refused too;
+ *  11. a result with |dx| < 0.01 becomes +0.011f where the reference draws the sign from rand() (:878-879), as in divergence 1;
+ *  12. `show` and the `info` overlay are not built; the numbers of `info` are returned. */
+
+typedef struct mvx_depan_estimate_args {
+    double trust;            /* 0..100; float arguments in the reference: pass 4.0 / 1.0 / 1.0 / 1.0 for the defaults of trust, zoommax, stab, pixaspect */
+    double zoommax, stab, pixaspect;
+    int32_t winx, winy;      /* MVX_UNSET or 0 -> the largest power of two that fits, up to 8192 */
+    int32_t wleft, wtop;     /* MVX_UNSET or < 0 -> centred */
+    int32_t dxmax, dymax;    /* MVX_UNSET or < 0 -> winx / 4, winy / 4 */
+    int32_t fields;          /* MVX_UNSET -> 0 */
+    int32_t tff;             /* MVX_UNSET = not passed */
+    int32_t float_samples;   /* 1: the clip's sample type is float (refused after the reference's own checks) */
+} mvx_depan_estimate_args;
+
+typedef struct mvx_depan_estimate_info {
+    int32_t winx, winy, wleft, wtop, dxmax, dymax;
+    int32_t windows;         /* 1, or 2 with zoommax != 1 */
+    int64_t spectrum_bytes;  /* of one window: winy * (winx / 2 + 1) complex floats, the reference's padded layout */
+} mvx_depan_estimate_info;
+
+/* Depan_dx, Depan_dy, Depan_zoom of stage 2 and its trust; dx == 0.0f marks a scene change */
+typedef struct mvx_depan_estimate_result { float dx, dy, zoom, trust; } mvx_depan_estimate_result;
+
+/* what the scan of one correlation surface leaves (get_motion_vector :717-767): the first maximum in scan order and the sum over the four
+ * corners, both unnormalised, the position of the maximum, and the surface at (imax + 1, jmax), (imax - 1, jmax), (imax, jmax + 1),
+ * (imax, jmax - 1), wrapped */
+typedef struct mvx_depan_estimate_scan { float max, sum; int32_t imax, jmax; float xp, xm, yp, ym; } mvx_depan_estimate_scan;
+
+typedef struct mvx_depan_estimate mvx_depan_estimate;
+
+int mvx_depan_estimate_create(const mvx_depan_estimate_args *args, const mvx_depan_clip *clip, int num_frames, mvx_depan_estimate **out, char *err);
+void mvx_depan_estimate_destroy(mvx_depan_estimate *h);
+void mvx_depan_estimate_get_info(const mvx_depan_estimate *h, mvx_depan_estimate_info *info);
+/* stage 1: luma_planes[i] the DEVICE luma plane of frame i (pitch in bytes), spectra_out[i] DEVICE room for windows * spectrum_bytes
+ * (8-byte aligned; the second window's spectrum follows the first).  Two launches for all frames; asynchronous on `stream`. */
+int mvx_depan_estimate_spectra(mvx_depan_estimate *h, int nframes, const void *const *luma_planes, ptrdiff_t pitch, void *const *spectra_out, void *stream);
+/* stage 2: pair i is frame frame_numbers[i] (cur) against the frame before it (prev), both as written by stage 1.  top_field[i]: the
+ * _Field property of cur, MVX_UNSET when absent; read with fields only (NULL: absent everywhere).  frame_numbers NULL: no pair is
+ * frame 0.  scans_out: NULL, or room for npairs * windows scan results.  Three launches for all pairs, then the host tail.  Synchronous. */
+int mvx_depan_estimate_correlate(mvx_depan_estimate *h, int npairs, const void *const *prev_spectra, const void *const *cur_spectra,
+                                 const int32_t *top_field, const int32_t *frame_numbers, mvx_depan_estimate_result *out,
+                                 mvx_depan_estimate_scan *scans_out, void *stream);
+/* the host tail alone, from npairs * windows scan results of the caller; touches no device */
+int mvx_depan_estimate_host_tail(const mvx_depan_estimate *h, int npairs, const mvx_depan_estimate_scan *scans, const int32_t *top_field,
+                                 const int32_t *frame_numbers, mvx_depan_estimate_result *out);
+/* stage 3 for frame n: results of frames max(0, n - 1), n, min(n + 1, num_frames - 1) -> Depan_dx, Depan_dy, Depan_zoom, Depan_rot = 0
+ * (iter and error are 0).  Host arithmetic. */
+int mvx_depan_estimate_finish(const mvx_depan_estimate *h, int n, const mvx_depan_estimate_result results_prev_cur_next[3], mvx_depan_motion *motion);
+
 /* ---- mv.SCDetection -------------------------------------------------------------------------------
  * replaces the decision of mvscdetectionGetFrame, MVSCDetection.c:43-73 (arg string :137-145): scene_change[i] (HOST array) =
  * !usable(blobs[i]) for n device blobs of one vector clip, i.e. the value of _SceneChangePrev (forward vectors) or

@@ -9,6 +9,7 @@
     core.mv.FlowBlur(clip, super, mvbw, mvfw, ...)    -> FlowBlur(super, bw_data, fw_data, ...)   .run(ns, ...)
     core.mv.Mask(clip, vectors, ...)                  -> Mask(analysis_data, width, height, ...)  .run(blobs, clip)
     core.mv.DepanAnalyse(clip, vectors, ...)          -> DepanAnalyse(analysis_data, width, height, ...) .run(blobs, masks)
+    core.mv.DepanEstimate(clip, trust, winx, ...)     -> DepanEstimate(width, height, bits, ...) .spectra(frames) .correlate(prev, cur) .finish(results) .run(frames)
     core.mv.DepanCompensate(clip, data, offset, ...)  -> DepanCompensate(width, height, ..., offset=...) .map(n) .transform(motions) .run(frames, transforms)
 
 Argument names, defaults and error strings are the reference's (MVSuper.c:279-291, MVAnalyse.c:639-671,
@@ -187,6 +188,24 @@ class DepanMotion(C.Structure):
     _fields_ = [("dx", C.c_float), ("dy", C.c_float), ("zoom", C.c_float), ("rot", C.c_float), ("iter", C.c_int32), ("error", C.c_float)]
 
 
+class DepanEstimateArgs(C.Structure):
+    _fields_ = [("trust", C.c_double), ("zoommax", C.c_double), ("stab", C.c_double), ("pixaspect", C.c_double)] + [
+        (n, C.c_int32) for n in ("winx", "winy", "wleft", "wtop", "dxmax", "dymax", "fields", "tff", "float_samples")]
+
+
+class DepanEstimateInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("winx", "winy", "wleft", "wtop", "dxmax", "dymax", "windows")] + [("spectrum_bytes", C.c_int64)]
+
+
+class DepanEstimateResult(C.Structure):
+    _fields_ = [("dx", C.c_float), ("dy", C.c_float), ("zoom", C.c_float), ("trust", C.c_float)]
+
+
+class DepanEstimateScan(C.Structure):
+    _fields_ = [("max", C.c_float), ("sum", C.c_float), ("imax", C.c_int32), ("jmax", C.c_int32), ("xp", C.c_float), ("xm", C.c_float),
+                ("yp", C.c_float), ("ym", C.c_float)]
+
+
 _lib = None
 
 
@@ -283,6 +302,15 @@ def lib():
         L.mvx_depan_analyse_destroy.argtypes = [C.c_void_p]
         L.mvx_depan_analyse_frames.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), P(C.c_void_p), C.c_ssize_t, P(C.c_int32), P(DepanMotion), C.c_void_p]
         L.mvx_depan_analyse_host.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), P(C.c_void_p), C.c_ssize_t, P(C.c_int32), P(DepanMotion)]
+        L.mvx_depan_estimate_create.argtypes = [P(DepanEstimateArgs), P(DepanClip), C.c_int, P(C.c_void_p), C.c_char_p]
+        L.mvx_depan_estimate_destroy.argtypes = [C.c_void_p]
+        L.mvx_depan_estimate_get_info.argtypes = [C.c_void_p, P(DepanEstimateInfo)]
+        L.mvx_depan_estimate_get_info.restype = None
+        L.mvx_depan_estimate_spectra.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), C.c_ssize_t, P(C.c_void_p), C.c_void_p]
+        L.mvx_depan_estimate_correlate.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), P(C.c_void_p), P(C.c_int32), P(C.c_int32), P(DepanEstimateResult),
+                                                   P(DepanEstimateScan), C.c_void_p]
+        L.mvx_depan_estimate_host_tail.argtypes = [C.c_void_p, C.c_int, P(DepanEstimateScan), P(C.c_int32), P(C.c_int32), P(DepanEstimateResult)]
+        L.mvx_depan_estimate_finish.argtypes = [C.c_void_p, C.c_int, P(DepanEstimateResult), P(DepanMotion)]
         L.mvx_scale_thscd.argtypes = [P(C.c_int64), P(C.c_int32), P(AnalysisData)]
         L.mvx_vectors_size.argtypes = [P(AnalysisData)]
         L.mvx_vectors_size.restype = C.c_int
@@ -1067,6 +1095,102 @@ class DepanAnalyse:
         out = (DepanMotion * n)()
         _check(lib().mvx_depan_analyse_host(self.h, n, ptrs, mp, mk[0].strides[0] if mk is not None else 0, self._fields(n, top_field), out))
         return self._result(out)
+
+
+class DepanEstimate:
+    """mv.DepanEstimate(clip, trust, winx, winy, wleft, wtop, dxmax, dymax, zoommax, stab, pixaspect, info, show, fields, tff) -- MVDepan.cpp:1271-1503,
+    without `show` and the `info` overlay.  spectra() is the reference's stage 1 (one or two window spectra per frame), correlate() its stage 2
+    (prev against cur: dx, dy, zoom, trust), finish() its stage 3 (host arithmetic); run() does all three for consecutive frames and returns
+    what DepanCompensate.transform() takes.  The transforms are HIP kernels; there is no FFTW and no CPU path."""
+
+    def __init__(self, width, height, bits=8, trust=4.0, winx=None, winy=None, wleft=None, wtop=None, dxmax=None, dymax=None, zoommax=1.0, stab=1.0,
+                 pixaspect=1.0, fields=None, tff=None, num_frames=1 << 30, float_samples=False):
+        a = DepanEstimateArgs(float(trust), float(zoommax), float(stab), float(pixaspect), _u(winx), _u(winy), _u(wleft), _u(wtop), _u(dxmax), _u(dymax),
+                              _u(fields), _u(tff), int(bool(float_samples)))
+        c = DepanClip(int(width), int(height), int(bits), 0, 0, 1)
+        self.h = C.c_void_p()
+        self.num_frames = int(num_frames)
+        err = C.create_string_buffer(ERRLEN)
+        _check(lib().mvx_depan_estimate_create(C.byref(a), C.byref(c), self.num_frames, C.byref(self.h), err), err)
+        self.info = DepanEstimateInfo()
+        lib().mvx_depan_estimate_get_info(self.h, C.byref(self.info))
+        self.windows = self.info.windows
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().mvx_depan_estimate_destroy(self.h)
+        except Exception:
+            pass
+
+    def spectra(self, frames):
+        """frames: device luma planes ([h, pitch] uint8 tensors of one pitch) -> one float32 tensor [windows, winy, winx / 2 + 1, 2] per frame"""
+        n = len(frames)
+        if n == 0:
+            _check(lib().mvx_depan_estimate_spectra(self.h, 0, None, 0, None, None))
+            return []
+        torch = _torch()
+        if any(f.stride(0) != frames[0].stride(0) or f.device != frames[0].device for f in frames):
+            raise MvtoolsError("DepanEstimate.spectra: the planes of one call must share one pitch and one device")
+        i = self.info
+        big = torch.empty((n, self.windows, i.winy, i.winx // 2 + 1, 2), dtype=torch.float32, device=frames[0].device)
+        out = [big[k] for k in range(n)]
+        src = (C.c_void_p * n)(*[f.data_ptr() for f in frames])
+        dst = (C.c_void_p * n)(*[o.data_ptr() for o in out])
+        _check(lib().mvx_depan_estimate_spectra(self.h, n, src, frames[0].stride(0), dst, _stream()))
+        return out
+
+    @staticmethod
+    def _ints(n, values):
+        return None if values is None else (C.c_int32 * max(n, 1))(*[UNSET if v is None else int(v) for v in values])
+
+    def correlate(self, prev, cur, top_field=None, frame_numbers=None, scans=False):
+        """prev / cur: spectra of frames n - 1 and n; -> one dict(dx, dy, zoom, trust) per pair (with scans=True also the per-window scan results)"""
+        n = len(cur)
+        out = (DepanEstimateResult * max(n, 1))()
+        sc = (DepanEstimateScan * max(n * self.windows, 1))()
+        if n == 0:
+            _check(lib().mvx_depan_estimate_correlate(self.h, 0, None, None, None, None, out, None, None))
+            return ([], []) if scans else []
+        _torch()
+        pp = (C.c_void_p * n)(*[p.data_ptr() for p in prev])
+        cp = (C.c_void_p * n)(*[c.data_ptr() for c in cur])
+        _check(lib().mvx_depan_estimate_correlate(self.h, n, pp, cp, self._ints(n, top_field), self._ints(n, frame_numbers), out, sc, _stream()))
+        res = [dict(dx=r.dx, dy=r.dy, zoom=r.zoom, trust=r.trust) for r in out[:n]]
+        if not scans:
+            return res
+        keys = [f[0] for f in DepanEstimateScan._fields_]
+        return res, [{k: getattr(s, k) for k in keys} for s in sc[:n * self.windows]]
+
+    def host_tail(self, scans, top_field=None, frame_numbers=None):
+        """the host tail alone from windows scan results (dicts) per pair; no device"""
+        n = len(scans) // self.windows
+        sc = (DepanEstimateScan * max(len(scans), 1))(*[DepanEstimateScan(**s) for s in scans])
+        out = (DepanEstimateResult * max(n, 1))()
+        _check(lib().mvx_depan_estimate_host_tail(self.h, n, sc, self._ints(n, top_field), self._ints(n, frame_numbers), out))
+        return [dict(dx=r.dx, dy=r.dy, zoom=r.zoom, trust=r.trust) for r in out[:n]]
+
+    def finish(self, results):
+        """stage 3 over the stage-2 results of frames 0 .. len - 1 of a clip of num_frames -> (dx, dy, zoom, rot) per frame; the neighbours of
+        the first and the last frame are clamped as in the reference"""
+        n = len(results)
+        out = []
+        for k in range(n):
+            tri = (DepanEstimateResult * 3)(*[DepanEstimateResult(**{f: float(results[q][f]) for f in ("dx", "dy", "zoom", "trust")})
+                                             for q in (max(0, k - 1), k, min(k + 1, n - 1))])
+            m = DepanMotion()
+            _check(lib().mvx_depan_estimate_finish(self.h, k, tri, C.byref(m)))
+            out.append((m.dx, m.dy, m.zoom, m.rot))
+        return out
+
+    def run(self, frames, top_field=None):
+        """all three stages for frames 0 .. len - 1 of a clip: each frame is transformed once; frame 0 gives zeros by the reference's rule"""
+        n = len(frames)
+        if n == 0:
+            return []
+        sp = self.spectra(frames)
+        res = self.correlate([sp[max(0, k - 1)] for k in range(n)], sp, top_field, list(range(n)))
+        return self.finish(res)
 
 
 class DepanCompensate:
