@@ -654,6 +654,119 @@ int mvx_depan_estimate_host_tail(const mvx_depan_estimate *h, int npairs, const 
  * (iter and error are 0).  Host arithmetic. */
 int mvx_depan_estimate_finish(const mvx_depan_estimate *h, int n, const mvx_depan_estimate_result results_prev_cur_next[3], mvx_depan_motion *motion);
 
+/* ---- mv.DepanStabilise ------------------------------------------------------------------------------
+ * smooths the global motion of a clip (the Depan_* values of DepanAnalyse or DepanEstimate) and warps every frame by the difference
+ * between its smoothed and its own cumulative motion; the border that opens can be filled from a previous and a following frame.
+ * mvx_depan_stabilise_create replaces depanStabiliseCreate, MVDepan.cpp:3909-4163, and touches no device; mvx_depan_stabilise_window
+ * gives the request sets of :3571-3591 (method 0) and :3720-3763 (method 1); mvx_depan_stabilise_plan replaces the host part of
+ * depanStabiliseGetFrame0 / 1, :3567-3666 / :3717-3841 (Inertial :2945-3115, Average :3118-3246, InertialLimit :3249-3329) and the
+ * source selection of fillBorderPrev :3398-3419 and fillBorderNext :3461-3502 (csrc/mvx_depan_stab_host.h: float arithmetic in the
+ * reference's order); mvx_depan_stabilise_frames replaces the up to three painting passes of :3679-3693 (fillBorderPrev, fillBorderNext,
+ * compensateFrame, :3356-3546) with one kernel that selects per sample and stores once (csrc/mvx_depan_stab_sample.h on top of
+ * DepanCompensate's interpolators).  Only the samples of each plane are written.
+ * Per sample the result is: the current frame where its position is inside it; else the next source where that is inside; else what the
+ * first pass wrote, with its mirror, blur or border value.  With prev = next = 0 it is DepanCompensate's pass with the plan's transform.
+ * What the reference does and the library keeps, surprising as it is:
+ *   a. fillBorderPrev always reads clip frame nprev = max(nbase, ndest - prev), with the transform summed over nprev + 1 .. ndest: the
+ *      assignment of :3412 is unconditional, its "most centred and nearest" test selects nothing;
+ *   b. fillBorderNext chooses its frame (the most centred and nearest, :3494-3497) but warps it by the transform accumulated over every
+ *      frame its walk passed, also where it chose an earlier one; a bad frame (dx == 0.0f) ends the walk at the frame before it, which
+ *      may be ndest itself;
+ *   c. data frame 0 is never read: its motion is dx = dy = rot = 0, zoom = 1 from creation (:4075-4078), so frame 0 always counts as bad;
+ *   d. method 1 with fps < 4 * cutoff has radius 0 and Average divides 0 by 0: the transform is NaN, and by divergence 5 of
+ *      DepanCompensate every sample of the current frame's pass takes that pass's border value;
+ *   e. sqrt / fabs of InertialLimit and of the selections are the float overloads (the reference is C++ and includes <math.h>).
+ * The divergences of DepanCompensate hold for each pass (2 to 5 above).  Deliberate divergences of its own:
+ *   1. chroma of the fill passes.  fillBorderPrev and fillBorderNext assign only tr[0] (:3405-3406, :3467-3468) and warp the chroma planes
+ *      by tr[1] and tr[2], which are indeterminate (for 4:4:4 nothing is ever assigned to them).  The library derives the chroma
+ *      transform of each fill pass from that pass's own luma transform, by the rule of compensateFrame (:3366-3379).  Chroma samples that
+ *      come from a fill source therefore have no counterpart in the reference;
+ *   2. `info`: the overlay is the shell's business; mvx_depan_stabilise_plan returns its four numbers and the BASE! flag;
+ *   3. creation rejects what the reference leaves undefined: a clip without frames, a negative frame rate, fps / (4 * cutoff) not below
+ *      1048576 (its (int) conversion and the window tables), a negative or NaN tzoom (winrzsize < 0 writes before winrz, :4155);
+ *   4. (int)(ndest - 10 * fps / cutoff) of method 0 (:3567) is undefined below -2^31; the library takes 0 there as for every
+ *      negative value; fitlast + ndest + 1 (:3654) is summed in 64 bits;
+ *   5. method 1 with next > radius: fillBorderNext reads data frames up to ndest + next which the reference never requested (the loop
+ *      of :3757 is empty); mvx_depan_stabilise_window includes them;
+ *   6. NaN coefficients.  IEEE 754 leaves the sign and payload of a NaN result open, and a compiler may commute the operands of an addition
+ *      or a product, so which NaN the reference's arithmetic ends on depends on its build.  Where a coefficient of a plan is NaN it is
+ *      the positive quiet NaN (0x7FC00000).  Whether a coefficient is NaN is the arithmetic's own outcome, and no finite value depends
+ *      on a NaN's bits. */
+
+typedef struct mvx_depan_stabilise_args {
+    /* float arguments of the reference, passed as doubles and rounded to float; (double)MVX_UNSET -> the default */
+    double cutoff;           /* > 0; -> 1.0 */
+    double damping;          /* -> 0.9 */
+    double initzoom;         /* -> 1.0 */
+    double dxmax, dymax;     /* -> 60 / 30; negative: reset to the base instead of the soft limit */
+    double zoommax, rotmax;  /* -> 1.05 / 1.0 */
+    double pixaspect;        /* > 0; -> 1.0 */
+    double tzoom;            /* >= 0; -> 3.0 */
+    int32_t addzoom;         /* MVX_UNSET -> 0 */
+    int32_t prev, next;      /* >= 0; MVX_UNSET -> 0 */
+    int32_t mirror;          /* bits: 1 top, 2 bottom, 4 left, 8 right; MVX_UNSET -> 0 */
+    int32_t blur;            /* >= 0, MVX_UNSET -> 0; chroma planes of 4:2:0 and 4:2:2 take blur / 2 */
+    int32_t subpixel;        /* 0 nearest, 1 bilinear, 2 bicubic; MVX_UNSET -> 2 */
+    int32_t fitlast;         /* MVX_UNSET -> 0 */
+    int32_t method;          /* 0 inertial, 1 average; MVX_UNSET -> 0 */
+    int32_t fields;          /* MVX_UNSET -> 0 */
+} mvx_depan_stabilise_args;
+
+typedef struct mvx_depan_stabilise_info {
+    int32_t width, height, bits, subsampling_w, subsampling_h, num_planes;
+    int32_t plane_width[3], plane_height[3];
+    int32_t subpixel, mirror, pixel_max, method, prev, next, nfields;
+    int32_t radius;          /* (int)(fps / (4 * cutoff)), :4140 */
+    int32_t wint_size, winrz_size, winfz_size; /* each table has radius + 1 entries; the sizes say where its zeros begin */
+    int32_t border[3], blur[3];
+    float fps, freqnative, initzoom /* 1 / the argument */, zoommax /* after :4061 */, xcenter, ycenter;
+    float nonlinfactor[6];   /* dxc dxx dxy dyc dyx dyy, :4112-4135 */
+} mvx_depan_stabilise_info;
+
+typedef struct mvx_depan_stabilise_source {
+    int32_t used;            /* 0: the filter has no such pass */
+    int32_t frame;           /* the clip frame to read */
+    float tr[6];             /* its luma transform: dxc dxx dxy dyc dyx dyy */
+} mvx_depan_stabilise_source;
+
+typedef struct mvx_depan_stabilise_frame_plan {
+    float tr[6];             /* the luma transform of clip frame n */
+    int32_t nbase;           /* the base after the scan for bad frames, the symmetric cut of method 1 and InertialLimit */
+    int32_t base;            /* nbase == n: "BASE!" in the info string */
+    float motion[4];         /* dx, dy, zoom, rot of the info string (transform2motion of tr, :3700) */
+    mvx_depan_stabilise_source prev, next;
+} mvx_depan_stabilise_frame_plan;
+
+typedef struct mvx_depan_stabilise mvx_depan_stabilise;
+
+/* num_frames / data_frames: the lengths of clip and data; fps_num / fps_den: the clip's frame rate.  The reference's error texts come
+ * first, in its order; then the library's own.  Pitches in bytes, multiples of the sample size */
+int mvx_depan_stabilise_create(const mvx_depan_stabilise_args *args, const mvx_depan_clip *clip, int num_frames, int data_frames,
+                               int64_t fps_num, int64_t fps_den, const ptrdiff_t src_pitch[3], const ptrdiff_t dst_pitch[3],
+                               mvx_depan_stabilise **out, char *err);
+void mvx_depan_stabilise_destroy(mvx_depan_stabilise *h);
+void mvx_depan_stabilise_get_info(const mvx_depan_stabilise *h, mvx_depan_stabilise_info *info);
+/* the cosine windows of :4140-4160, radius + 1 floats each (any may be NULL) */
+void mvx_depan_stabilise_get_windows(const mvx_depan_stabilise *h, float *wint, float *winrz, float *winfz);
+/* output frame n: the data frames *data_first .. *data_last whose motion mvx_depan_stabilise_plan reads, and the clip frames
+ * *clip_first .. *clip_last among which its sources lie (n is one of them) */
+int mvx_depan_stabilise_window(const mvx_depan_stabilise *h, int n, int *data_first, int *data_last, int *clip_first, int *clip_last);
+/* motions: dx, dy, zoom, rot (Depan_dx, Depan_dy, Depan_zoom, Depan_rot) per data frame of the window, data_first first; dx == 0.0f marks
+ * a bad frame.  Host arithmetic, no device. */
+int mvx_depan_stabilise_plan(const mvx_depan_stabilise *h, int n, const float *motions, mvx_depan_stabilise_frame_plan *plan, char *err);
+
+typedef struct mvx_depan_stabilise_job {
+    mvx_depan_stabilise_frame_plan plan;
+    const void *cur[3];      /* planes of clip frame n */
+    const void *prev[3];     /* planes of clip frame plan.prev.frame; read only where plan.prev.used */
+    const void *next[3];     /* planes of clip frame plan.next.frame; read only where plan.next.used */
+    void *dst[3];
+} mvx_depan_stabilise_job;
+
+/* nframes jobs in one batch on `stream`: a small pre-pass for the sources whose rotation form walks its rows (every fill source, and the
+ * current frame with nearest and bilinear), then one launch for all planes of all jobs.  All sources share src_pitch. */
+int mvx_depan_stabilise_frames(mvx_depan_stabilise *h, int nframes, const mvx_depan_stabilise_job *jobs, void *stream);
+
 /* ---- mv.SCDetection -------------------------------------------------------------------------------
  * replaces the decision of mvscdetectionGetFrame, MVSCDetection.c:43-73 (arg string :137-145): scene_change[i] (HOST array) =
  * !usable(blobs[i]) for n device blobs of one vector clip, i.e. the value of _SceneChangePrev (forward vectors) or

@@ -11,6 +11,7 @@
     core.mv.DepanAnalyse(clip, vectors, ...)          -> DepanAnalyse(analysis_data, width, height, ...) .run(blobs, masks)
     core.mv.DepanEstimate(clip, trust, winx, ...)     -> DepanEstimate(width, height, bits, ...) .spectra(frames) .correlate(prev, cur) .finish(results) .run(frames)
     core.mv.DepanCompensate(clip, data, offset, ...)  -> DepanCompensate(width, height, ..., offset=...) .map(n) .transform(motions) .run(frames, transforms)
+    core.mv.DepanStabilise(clip, data, cutoff, ...)   -> DepanStabilise(width, height, ..., fps=(num, den), cutoff=...) .window(n) .plan(n, motions) .run(frames, motions)
 
 Argument names, defaults and error strings are the reference's (MVSuper.c:279-291, MVAnalyse.c:639-671,
 MVDegrains.cpp:813-932, MVCompensate.c:579-592); they are resolved inside the library, not here.
@@ -179,6 +180,32 @@ class DepanCompensateJob(C.Structure):
     _fields_ = [("src", C.c_void_p * 3), ("dst", C.c_void_p * 3), ("tr", C.c_float * 6)]
 
 
+class DepanStabiliseArgs(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("cutoff", "damping", "initzoom", "dxmax", "dymax", "zoommax", "rotmax", "pixaspect", "tzoom")] + [
+        (n, C.c_int32) for n in ("addzoom", "prev", "next", "mirror", "blur", "subpixel", "fitlast", "method", "fields")]
+
+
+class DepanStabiliseInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "bits", "subsampling_w", "subsampling_h", "num_planes")] + [
+        ("plane_width", C.c_int32 * 3), ("plane_height", C.c_int32 * 3)] + [
+        (n, C.c_int32) for n in ("subpixel", "mirror", "pixel_max", "method", "prev", "next", "nfields", "radius", "wint_size", "winrz_size", "winfz_size")] + [
+        ("border", C.c_int32 * 3), ("blur", C.c_int32 * 3)] + [(n, C.c_float) for n in ("fps", "freqnative", "initzoom", "zoommax", "xcenter", "ycenter")] + [
+        ("nonlinfactor", C.c_float * 6)]
+
+
+class DepanStabiliseSource(C.Structure):
+    _fields_ = [("used", C.c_int32), ("frame", C.c_int32), ("tr", C.c_float * 6)]
+
+
+class DepanStabilisePlan(C.Structure):
+    _fields_ = [("tr", C.c_float * 6), ("nbase", C.c_int32), ("base", C.c_int32), ("motion", C.c_float * 4), ("prev", DepanStabiliseSource),
+                ("next", DepanStabiliseSource)]
+
+
+class DepanStabiliseJob(C.Structure):
+    _fields_ = [("plan", DepanStabilisePlan), ("cur", C.c_void_p * 3), ("prev", C.c_void_p * 3), ("next", C.c_void_p * 3), ("dst", C.c_void_p * 3)]
+
+
 class DepanAnalyseArgs(C.Structure):
     _fields_ = [("zoom", C.c_int32), ("rot", C.c_int32), ("pixaspect", C.c_double), ("error", C.c_double), ("wrong", C.c_double), ("zerow", C.c_double),
                 ("thscd1", C.c_int64), ("thscd2", C.c_int32), ("fields", C.c_int32)]
@@ -298,6 +325,16 @@ def lib():
         L.mvx_depan_compensate_map.argtypes = [C.c_void_p, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int)]
         L.mvx_depan_motion_to_transform.argtypes = [C.c_void_p, C.c_int, P(C.c_float), C.c_int, C.c_int, P(C.c_float), P(C.c_float), C.c_char_p]
         L.mvx_depan_compensate_frames.argtypes = [C.c_void_p, C.c_int, P(DepanCompensateJob), C.c_void_p]
+        L.mvx_depan_stabilise_create.argtypes = [P(DepanStabiliseArgs), P(DepanClip), C.c_int, C.c_int, C.c_int64, C.c_int64, P(C.c_ssize_t), P(C.c_ssize_t),
+                                                 P(C.c_void_p), C.c_char_p]
+        L.mvx_depan_stabilise_destroy.argtypes = [C.c_void_p]
+        L.mvx_depan_stabilise_get_info.argtypes = [C.c_void_p, P(DepanStabiliseInfo)]
+        L.mvx_depan_stabilise_get_info.restype = None
+        L.mvx_depan_stabilise_get_windows.argtypes = [C.c_void_p, P(C.c_float), P(C.c_float), P(C.c_float)]
+        L.mvx_depan_stabilise_get_windows.restype = None
+        L.mvx_depan_stabilise_window.argtypes = [C.c_void_p, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_int)]
+        L.mvx_depan_stabilise_plan.argtypes = [C.c_void_p, C.c_int, P(C.c_float), P(DepanStabilisePlan), C.c_char_p]
+        L.mvx_depan_stabilise_frames.argtypes = [C.c_void_p, C.c_int, P(DepanStabiliseJob), C.c_void_p]
         L.mvx_depan_analyse_create.argtypes = [P(DepanAnalyseArgs), P(AnalysisData), P(DepanClip), P(DepanClip), C.c_int, C.c_int, C.c_int, P(C.c_void_p), C.c_char_p]
         L.mvx_depan_analyse_destroy.argtypes = [C.c_void_p]
         L.mvx_depan_analyse_frames.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), P(C.c_void_p), C.c_ssize_t, P(C.c_int32), P(DepanMotion), C.c_void_p]
@@ -1267,6 +1304,110 @@ class DepanCompensate:
             for i in range(6):
                 arr[k].tr[i] = t[i]
         return arr, out
+
+
+class DepanStabilise:
+    """mv.DepanStabilise(clip, data, cutoff, damping, initzoom, addzoom, prev, next, mirror, blur, dxmax, dymax, zoommax, rotmax, subpixel, pixaspect,
+    fitlast, tzoom, info, method, fields) -- MVDepan.cpp:3909-4208.  window(n) names the data frames whose motion plan(n, motions) reads (host
+    arithmetic) and the clip frames its sources lie among; a job is a plan with the planes of the current, prev and next source frames; all jobs
+    of a call are one fused launch.  `src_pitch` / `dst_pitch`: row pitches in bytes of the device planes.  Float arguments: None -> the default."""
+
+    def __init__(self, width, height, bits=8, subsampling=(1, 1), gray=False, src_pitch=None, dst_pitch=None, fps=(25, 1), num_frames=1 << 30, cutoff=None,
+                 damping=None, initzoom=None, addzoom=None, prev=None, next=None, mirror=None, blur=None, dxmax=None, dymax=None, zoommax=None, rotmax=None,
+                 subpixel=None, pixaspect=None, fitlast=None, tzoom=None, method=None, fields=None, data_frames=None):
+        d = lambda v: float(UNSET) if v is None else float(v)
+        a = DepanStabiliseArgs(d(cutoff), d(damping), d(initzoom), d(dxmax), d(dymax), d(zoommax), d(rotmax), d(pixaspect), d(tzoom), _u(addzoom), _u(prev),
+                               _u(next), _u(mirror), _u(blur), _u(subpixel), _u(fitlast), _u(method), _u(fields))
+        c = DepanClip(int(width), int(height), int(bits), int(subsampling[0]), int(subsampling[1]), int(bool(gray)))
+        sw = 0 if gray else subsampling[0]
+        bps = 2 if bits > 8 else 1
+        if dst_pitch is None:
+            dst_pitch = [((max(int(width) >> s, 1) * bps + 255) // 256) * 256 for s in (0, sw, sw)]
+        if src_pitch is None:
+            src_pitch = dst_pitch
+        self.h = C.c_void_p()
+        self.pitch = list(dst_pitch)
+        self.dtype = np.uint16 if bits > 8 else np.uint8
+        self.num_frames = int(num_frames)
+        err = C.create_string_buffer(ERRLEN)
+        _check(lib().mvx_depan_stabilise_create(C.byref(a), C.byref(c), self.num_frames, int(num_frames if data_frames is None else data_frames), int(fps[0]),
+                                                int(fps[1]), _pad3(src_pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
+        self.info = DepanStabiliseInfo()
+        lib().mvx_depan_stabilise_get_info(self.h, C.byref(self.info))
+        self.nplanes = self.info.num_planes
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().mvx_depan_stabilise_destroy(self.h)
+        except Exception:
+            pass
+
+    def windows(self):
+        """the cosine windows wint, winrz, winfz: radius + 1 float32 each"""
+        n = self.info.radius + 1
+        w = [(C.c_float * n)() for _ in range(3)]
+        lib().mvx_depan_stabilise_get_windows(self.h, *w)
+        return [np.array(v, dtype=np.float32) for v in w]
+
+    def window(self, n):
+        """(data_first, data_last, clip_first, clip_last) of output frame n"""
+        v = [C.c_int() for _ in range(4)]
+        _check(lib().mvx_depan_stabilise_window(self.h, int(n), *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    @staticmethod
+    def _motion(m):
+        return (m["dx"], m["dy"], m["zoom"], m["rot"]) if isinstance(m, dict) else tuple(m)
+
+    def plan(self, n, motions):
+        """motions: (dx, dy, zoom, rot) or the dicts of DepanAnalyse.run / DepanEstimate.run, per data frame data_first .. data_last of window(n)"""
+        flat = [float(v) for m in motions for v in self._motion(m)]
+        w = self.window(n)
+        if len(flat) != 4 * (w[1] - w[0] + 1):
+            raise MvtoolsError("DepanStabilise.plan: frame %d needs the motions of data frames %d .. %d" % (n, w[0], w[1]))
+        arr = (C.c_float * len(flat))(*flat)
+        plan = DepanStabilisePlan()
+        err = C.create_string_buffer(ERRLEN)
+        _check(lib().mvx_depan_stabilise_plan(self.h, int(n), arr, C.byref(plan), err), err)
+        return plan
+
+    def alloc(self, n, device="cuda"):
+        return arena_frames(n, [(self.info.plane_height[p], self.pitch[p]) for p in range(self.nplanes)], device, zero=False)
+
+    def jobs(self, plans, cur, prev=None, next=None, out=None):
+        """plans: per job a DepanStabilisePlan; cur / prev / next: per job the device planes of clip frame n, plan.prev.frame, plan.next.frame
+        (prev / next entries may be None where the plan does not use them)"""
+        _torch()
+        n = len(plans)
+        if out is None:
+            out = self.alloc(n, cur[0][0].device if n else "cuda")
+        arr = (DepanStabiliseJob * n)()
+        for k in range(n):
+            arr[k].plan = plans[k]
+            for p in range(self.nplanes):
+                arr[k].cur[p] = cur[k][p].data_ptr()
+                arr[k].dst[p] = out[k][p].data_ptr()
+                if plans[k].prev.used:
+                    arr[k].prev[p] = prev[k][p].data_ptr()
+                if plans[k].next.used:
+                    arr[k].next[p] = next[k][p].data_ptr()
+        return arr, out
+
+    def launch(self, arr):
+        _check(lib().mvx_depan_stabilise_frames(self.h, len(arr), arr, _stream()))
+
+    def run(self, frames, motions, out=None):
+        """a whole clip: frames[n] the device planes of clip frame n, motions[n] the motion of data frame n; every output frame in one call"""
+        n = len(frames)
+        plans = []
+        for k in range(n):
+            w = self.window(k)
+            plans.append(self.plan(k, motions[w[0]:w[1] + 1]))
+        arr, out = self.jobs(plans, frames, [frames[p.prev.frame] if p.prev.used else None for p in plans],
+                             [frames[p.next.frame] if p.next.used else None for p in plans], out)
+        self.launch(arr)
+        return out
 
 
 class Recalculate:
