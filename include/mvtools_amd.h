@@ -606,7 +606,9 @@ int mvx_depan_analyse_host(const mvx_depan_analyse *h, int n, const void *const 
  *      sizes always qualify on a frame of at least 8 x 8 (16 x 8 with zoom).  A window that leaves the frame -- the second window of
  *      zoommax != 1 starts at wleft + width / 2, which the reference does not check -- is refused too;
  *  11. a result with |dx| < 0.01 becomes +0.011f where the reference draws the sign from rand() (:878-879), as in divergence 1;
- *  12. `show` and the `info` overlay are not built; the numbers of `info` are returned. */
+ *  12. the `info` overlay is not built; the numbers of `info` are returned.  `show` is mvx_depan_estimate_correlate_show;
+ *  13. show on a surface whose maximum equals its minimum: the reference multiplies 0 by pixel_max / 0 and converts the NaN to int
+ *      (showcorrelation, :920, :937), which is undefined; the library paints 0 over the whole window. */
 
 typedef struct mvx_depan_estimate_args {
     double trust;            /* 0..100; float arguments in the reference: pass 4.0 / 1.0 / 1.0 / 1.0 for the defaults of trust, zoommax, stab, pixaspect */
@@ -647,6 +649,14 @@ int mvx_depan_estimate_spectra(mvx_depan_estimate *h, int nframes, const void *c
 int mvx_depan_estimate_correlate(mvx_depan_estimate *h, int npairs, const void *const *prev_spectra, const void *const *cur_spectra,
                                  const int32_t *top_field, const int32_t *frame_numbers, mvx_depan_estimate_result *out,
                                  mvx_depan_estimate_scan *scans_out, void *stream);
+/* stage 2 with `show` (showcorrelation, :895-953, as called at :1072-1077 and :1123-1124): the same arguments, results and scan results, bit for
+ * bit, and show_planes[i], a DEVICE luma plane of pair i in the clip's sample type (a copy of frame cur, the caller's; show_pitch in bytes), gets
+ * the correlation surface painted into its window rectangle(s): (int)((c - min) * (pixel_max / (max - min))) at (wleft + i, wtop + j), the
+ * second window of zoommax != 1 at wleft + width / 2.  Nothing else of the plane is touched.  Frame 0 is painted like any other pair.  The scan
+ * reads the kept rows as above; every row of the surface is computed a second time for the paint (four more launches).  Synchronous. */
+int mvx_depan_estimate_correlate_show(mvx_depan_estimate *h, int npairs, const void *const *prev_spectra, const void *const *cur_spectra,
+                                      const int32_t *top_field, const int32_t *frame_numbers, mvx_depan_estimate_result *out,
+                                      mvx_depan_estimate_scan *scans_out, void *const *show_planes, ptrdiff_t show_pitch, void *stream);
 /* the host tail alone, from npairs * windows scan results of the caller; touches no device */
 int mvx_depan_estimate_host_tail(const mvx_depan_estimate *h, int npairs, const mvx_depan_estimate_scan *scans, const int32_t *top_field,
                                  const int32_t *frame_numbers, mvx_depan_estimate_result *out);

@@ -5,6 +5,7 @@
 //   stage 1, mvx_depan_estimate_spectra  : de_rows_kernel (two window rows per complex transform), de_cols_kernel (in place)
 //   stage 2, mvx_depan_estimate_correlate: de_correlate_kernel (conjugate product on load, inverse columns, kept rows only), de_rows_inverse_kernel,
 //                                          de_peak_kernel, then the host tail (mvx_depan_estimate_host.h)
+//            mvx_depan_estimate_correlate_show: the same, then the two inverse passes again with every row kept, de_minmax_kernel, de_paint_kernel
 //   stage 3, mvx_depan_estimate_finish   : host only
 // A batch is one launch per pass: blockIdx.x covers job x window x group of rows or columns.  No atomics: every sum has a fixed order (the mean's
 // is the reference's serial one), so the results are the same from run to run and for any batch size.  A workgroup holds at most 8192 complex values, 64 KiB of LDS.
@@ -54,6 +55,21 @@ __global__ __launch_bounds__(DE_THREADS) void de_peak_kernel(DEParams P, const f
     de_peak(P, corr + (long long)blockIdx.x * P.nrows * P.winx, scans + blockIdx.x, stage, lmax, lidx);
 }
 
+// show.  grid: job x window x groups; full: [job][window][winy][winx]; partial: [job][window][groups][2]
+__global__ __launch_bounds__(DE_THREADS) void de_minmax_kernel(DEParams P, const float *full, int groups, float *partial) {
+    __shared__ float lmin[DE_THREADS];
+    __shared__ float lmax[DE_THREADS];
+    const int g = blockIdx.x % groups, jw = blockIdx.x / groups;
+    de_minmax(P, full + (long long)jw * P.winy * P.winx, g, groups, partial + (long long)jw * groups * 2, lmin, lmax);
+}
+
+__global__ __launch_bounds__(DE_THREADS) void de_paint_kernel(DEParams P, const DEJob *jobs, const float *full, int groups, const float *partial, int pixel_max) {
+    __shared__ float lmin[DE_THREADS];
+    __shared__ float lmax[DE_THREADS];
+    const int g = blockIdx.x % groups, jw = blockIdx.x / groups, win = jw % P.nwin, job = jw / P.nwin;
+    de_paint(P, full + (long long)jw * P.winy * P.winx, partial + (long long)jw * groups * 2, g, groups, jobs[job].out, win, pixel_max, lmin, lmax);
+}
+
 // ------------------------------------------------------------------------------------------------ host object
 
 struct mvx_depan_estimate {
@@ -67,6 +83,8 @@ struct mvx_depan_estimate {
     DevBuf<DEComplex> dHalf;
     DevBuf<float> dCorr;
     DevBuf<DEScan> dScans;
+    DevBuf<DEComplex> dHalfFull;       // show: the surface with every row kept
+    DevBuf<float> dCorrFull, dMinMax;
 };
 
 static_assert(sizeof(DEScan) == sizeof(mvx_depan_estimate_scan) && sizeof(DepanEstimateScan) == sizeof(DEScan), "layouts");
@@ -174,15 +192,22 @@ extern "C" __attribute__((visibility("default"))) int mvx_depan_estimate_host_ta
     return de_tail(h, npairs, (const DepanEstimateScan *)scans, top_field, frame_numbers, out);
 }
 
-// stage 2, :1000-1148.  Synchronous: the scan results come back to the host for the tail.
-extern "C" __attribute__((visibility("default"))) int mvx_depan_estimate_correlate(mvx_depan_estimate *h, int npairs, const void *const *prev_spectra, const void *const *cur_spectra,
-        const int32_t *top_field, const int32_t *frame_numbers, mvx_depan_estimate_result *out, mvx_depan_estimate_scan *scans_out, void *stream) {
+// stage 2, :1000-1148.  Synchronous: the scan results come back to the host for the tail.  With show_planes the correlation surface is painted too
+// (:1072-1077, :1123-1124): the scan above stays on its kept rows, whose pairing in de_rows_inverse decides their floats, and the two inverse passes run
+// once more with every row kept for the minimum, the maximum and the paint alone.
+static int de_correlate(const char *name, mvx_depan_estimate *h, int npairs, const void *const *prev_spectra, const void *const *cur_spectra, const int32_t *top_field,
+        const int32_t *frame_numbers, mvx_depan_estimate_result *out, mvx_depan_estimate_scan *scans_out, void *const *show_planes, ptrdiff_t show_pitch, void *stream) {
     if (npairs <= 0) return MVX_OK;
-    if (npairs > DE_MAX_JOBS) { mvx_set_error("mvx_depan_estimate_correlate: at most %d pairs per call", DE_MAX_JOBS); return MVX_E_ARG; }
+    if (npairs > DE_MAX_JOBS) { mvx_set_error("%s: at most %d pairs per call", name, DE_MAX_JOBS); return MVX_E_ARG; }
+    if (show_planes) {
+        const int bps = h->E.bits > 8 ? 2 : 1;
+        if (show_pitch % bps || show_pitch < (ptrdiff_t)h->E.width * bps) { mvx_set_error("%s: the pitch must hold a row and be a multiple of the sample size", name); return MVX_E_ARG; }
+    }
     std::vector<DEJob> hj(npairs);
     for (int f = 0; f < npairs; f++) {
-        hj[f].a = (const unsigned char *)prev_spectra[f]; hj[f].b = (const unsigned char *)cur_spectra[f]; hj[f].out = nullptr;
-        if (!hj[f].a || !hj[f].b) { mvx_set_error("mvx_depan_estimate_correlate: every pair needs both spectra"); return MVX_E_ARG; }
+        hj[f].a = (const unsigned char *)prev_spectra[f]; hj[f].b = (const unsigned char *)cur_spectra[f]; hj[f].out = show_planes ? (unsigned char *)show_planes[f] : nullptr;
+        if (!hj[f].a || !hj[f].b) { mvx_set_error("%s: every pair needs both spectra", name); return MVX_E_ARG; }
+        if (show_planes && !hj[f].out) { mvx_set_error("%s: every pair needs its luma plane", name); return MVX_E_ARG; }
     }
     const DEParams &P = h->P;
     const size_t nscan = (size_t)npairs * P.nwin;
@@ -200,12 +225,36 @@ extern "C" __attribute__((visibility("default"))) int mvx_depan_estimate_correla
         hipLaunchKernelGGL(de_correlate_kernel, dim3((unsigned)(nscan * cgroups)), dim3(DE_THREADS), (size_t)(P.winy << P.lgcy) * 8, st, P, h->dJobs.p, h->dTwy.p, cgroups, h->dHalf.p);
         hipLaunchKernelGGL(de_rows_inverse_kernel, dim3((unsigned)(nscan * rgroups)), dim3(DE_THREADS), (size_t)(P.winx << P.lgcx) * 8, st, P, h->dTwx.p, rgroups, h->dHalf.p, h->dCorr.p);
         hipLaunchKernelGGL(de_peak_kernel, dim3((unsigned)nscan), dim3(DE_THREADS), 0, st, P, h->dCorr.p, h->dScans.p);
+        if (show_planes) {
+            DEParams F = P;                       // every row of the surface
+            F.nrows = F.winy; F.jshift = 0; F.pitch = show_pitch;
+            const int fgroups = (F.winy / 2 + F.cx - 1) / F.cx, sgroups = de_show_groups(F.winx * F.winy);
+            HIP_CHECK(h->dHalfFull.reserve(nscan * F.winy * F.nx));
+            HIP_CHECK(h->dCorrFull.reserve(nscan * F.winy * F.winx));
+            HIP_CHECK(h->dMinMax.reserve(nscan * sgroups * 2));
+            hipLaunchKernelGGL(de_correlate_kernel, dim3((unsigned)(nscan * cgroups)), dim3(DE_THREADS), (size_t)(F.winy << F.lgcy) * 8, st, F, h->dJobs.p, h->dTwy.p, cgroups, h->dHalfFull.p);
+            hipLaunchKernelGGL(de_rows_inverse_kernel, dim3((unsigned)(nscan * fgroups)), dim3(DE_THREADS), (size_t)(F.winx << F.lgcx) * 8, st, F, h->dTwx.p, fgroups, h->dHalfFull.p, h->dCorrFull.p);
+            hipLaunchKernelGGL(de_minmax_kernel, dim3((unsigned)(nscan * sgroups)), dim3(DE_THREADS), 0, st, F, h->dCorrFull.p, sgroups, h->dMinMax.p);
+            hipLaunchKernelGGL(de_paint_kernel, dim3((unsigned)(nscan * sgroups)), dim3(DE_THREADS), 0, st, F, h->dJobs.p, h->dCorrFull.p, sgroups, h->dMinMax.p, (1 << h->E.bits) - 1);
+        }
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpyAsync(scans.data(), h->dScans.p, sizeof(DEScan) * nscan, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
     }
     if (scans_out) memcpy(scans_out, scans.data(), sizeof(DEScan) * nscan);
     return de_tail(h, npairs, scans.data(), top_field, frame_numbers, out);
+}
+
+extern "C" __attribute__((visibility("default"))) int mvx_depan_estimate_correlate(mvx_depan_estimate *h, int npairs, const void *const *prev_spectra, const void *const *cur_spectra,
+        const int32_t *top_field, const int32_t *frame_numbers, mvx_depan_estimate_result *out, mvx_depan_estimate_scan *scans_out, void *stream) {
+    return de_correlate("mvx_depan_estimate_correlate", h, npairs, prev_spectra, cur_spectra, top_field, frame_numbers, out, scans_out, nullptr, 0, stream);
+}
+
+extern "C" __attribute__((visibility("default"))) int mvx_depan_estimate_correlate_show(mvx_depan_estimate *h, int npairs, const void *const *prev_spectra,
+        const void *const *cur_spectra, const int32_t *top_field, const int32_t *frame_numbers, mvx_depan_estimate_result *out, mvx_depan_estimate_scan *scans_out,
+        void *const *show_planes, ptrdiff_t show_pitch, void *stream) {
+    if (npairs > 0 && !show_planes) { mvx_set_error("mvx_depan_estimate_correlate_show: every pair needs its luma plane"); return MVX_E_ARG; }
+    return de_correlate("mvx_depan_estimate_correlate_show", h, npairs, prev_spectra, cur_spectra, top_field, frame_numbers, out, scans_out, show_planes, show_pitch, stream);
 }
 
 // stage 3, :1154-1243

@@ -12,6 +12,8 @@
 //   columns, inverse: the conjugate product of two spectra is formed on load; only the rows the peak search can read are stored
 //   rows, inverse   : two kept rows ride one complex transform (Z = A + iB of their Hermitian extensions)
 //   peak            : one workgroup per window: the maximum by 256 strided partial results and a fixed tree, the sum by the reference's serial chain
+//   show            : over a surface with every row kept (nrows = winy, jshift = 0): minimum and maximum by strided partial results and fixed trees
+//                     (either is the same in any order), then the surface painted into the window of a luma plane (showcorrelation, MVDepan.cpp:895-953)
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -254,5 +256,58 @@ DE_DEV void de_peak(const DEParams &P, const float *corr, DEScan *out, float *st
         S.xp = corr[row + ip]; S.xm = corr[row + im1];
         S.yp = corr[(long long)de_kept(P, jp) * P.winx + i]; S.ym = corr[(long long)de_kept(P, jm) * P.winx + i];
         *out = S;
+    }
+}
+
+// ---- show, MVDepan.cpp:895-953, on a surface of winy full rows.  Minimum and maximum: `groups` workgroups per window, each over the values
+// group * DE_THREADS + l, stepping groups * DE_THREADS, merged by halving; partial[2 * group] and [2 * group + 1] hold its minimum and maximum.
+#define DE_SHOW_GROUPS DE_THREADS // at most: the paint merges the partial results with one tree of DE_THREADS places
+static inline int de_show_groups(int total) { const int g = (total + 4095) / 4096; return g < 1 ? 1 : g > DE_SHOW_GROUPS ? DE_SHOW_GROUPS : g; }
+
+DE_DEV void de_minmax_tree(float *lmin, float *lmax) {
+    for (int w = DE_THREADS / 2; w > 0; w >>= 1) {
+        DE_FOR(l, w) {
+            if (lmax[l] < lmax[l + w]) lmax[l] = lmax[l + w];
+            if (lmin[l] > lmin[l + w]) lmin[l] = lmin[l + w];
+        }
+        DE_SYNC();
+    }
+}
+
+DE_DEV void de_minmax(const DEParams &P, const float *corr, int group, int groups, float *partial, float *lmin, float *lmax) {
+    const int total = P.winx * P.winy, step = groups * DE_THREADS;
+    DE_FOR(l, DE_THREADS) {
+        float lo = corr[0], hi = corr[0];
+        for (int t = group * DE_THREADS + l; t < total; t += step) {
+            const float cur = corr[t];
+            if (hi < cur) hi = cur;
+            if (lo > cur) lo = cur;
+        }
+        lmin[l] = lo; lmax[l] = hi;
+    }
+    DE_SYNC();
+    de_minmax_tree(lmin, lmax);
+    DE_FOR(l, 1) { partial[2 * group] = lmin[0]; partial[2 * group + 1] = lmax[0]; }
+}
+
+// the same groups paint: (int)((c - min) * norm), norm = pixel_max / (max - min), at (wleft + i, wtop + j) of `plane` (pitch P.pitch), in the clip's
+// sample type.  max == min: the reference multiplies 0 by infinity and converts the NaN; here the window becomes 0.
+DE_DEV void de_paint(const DEParams &P, const float *corr, const float *partial, int group, int groups, unsigned char *plane, int win, int pixel_max,
+                     float *lmin, float *lmax) {
+    DE_FOR(l, DE_THREADS) { const int g = l < groups ? l : 0; lmin[l] = partial[2 * g]; lmax[l] = partial[2 * g + 1]; }
+    DE_SYNC();
+    de_minmax_tree(lmin, lmax);
+    const float cmin = lmin[0], cmax = lmax[0];
+    const float norm = (float)pixel_max / (cmax - cmin);
+    const bool flat = cmax == cmin;
+    const int total = P.winx * P.winy, step = groups * DE_THREADS;
+    DE_FOR(l, DE_THREADS) {
+        for (int t = group * DE_THREADS + l; t < total; t += step) {
+            const int i = t & (P.winx - 1), j = t >> P.lgx;
+            const int v = flat ? 0 : (int)((corr[t] - cmin) * norm);
+            unsigned char *row = plane + (long long)(P.wtop + j) * P.pitch;
+            if (P.bits16) ((unsigned short *)row)[P.wleft[win] + i] = (unsigned short)v;
+            else row[P.wleft[win] + i] = (unsigned char)v;
+        }
     }
 }

@@ -346,6 +346,8 @@ def lib():
         L.mvx_depan_estimate_spectra.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), C.c_ssize_t, P(C.c_void_p), C.c_void_p]
         L.mvx_depan_estimate_correlate.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), P(C.c_void_p), P(C.c_int32), P(C.c_int32), P(DepanEstimateResult),
                                                    P(DepanEstimateScan), C.c_void_p]
+        L.mvx_depan_estimate_correlate_show.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), P(C.c_void_p), P(C.c_int32), P(C.c_int32), P(DepanEstimateResult),
+                                                        P(DepanEstimateScan), P(C.c_void_p), C.c_ssize_t, C.c_void_p]
         L.mvx_depan_estimate_host_tail.argtypes = [C.c_void_p, C.c_int, P(DepanEstimateScan), P(C.c_int32), P(C.c_int32), P(DepanEstimateResult)]
         L.mvx_depan_estimate_finish.argtypes = [C.c_void_p, C.c_int, P(DepanEstimateResult), P(DepanMotion)]
         L.mvx_scale_thscd.argtypes = [P(C.c_int64), P(C.c_int32), P(AnalysisData)]
@@ -1136,7 +1138,7 @@ class DepanAnalyse:
 
 class DepanEstimate:
     """mv.DepanEstimate(clip, trust, winx, winy, wleft, wtop, dxmax, dymax, zoommax, stab, pixaspect, info, show, fields, tff) -- MVDepan.cpp:1271-1503,
-    without `show` and the `info` overlay.  spectra() is the reference's stage 1 (one or two window spectra per frame), correlate() its stage 2
+    without the `info` overlay.  spectra() is the reference's stage 1 (one or two window spectra per frame), correlate() its stage 2
     (prev against cur: dx, dy, zoom, trust), finish() its stage 3 (host arithmetic); run() does all three for consecutive frames and returns
     what DepanCompensate.transform() takes.  The transforms are HIP kernels; there is no FFTW and no CPU path."""
 
@@ -1181,23 +1183,38 @@ class DepanEstimate:
     def _ints(n, values):
         return None if values is None else (C.c_int32 * max(n, 1))(*[UNSET if v is None else int(v) for v in values])
 
-    def correlate(self, prev, cur, top_field=None, frame_numbers=None, scans=False):
-        """prev / cur: spectra of frames n - 1 and n; -> one dict(dx, dy, zoom, trust) per pair (with scans=True also the per-window scan results)"""
+    def correlate(self, prev, cur, top_field=None, frame_numbers=None, scans=False, show=None):
+        """prev / cur: spectra of frames n - 1 and n; -> one dict(dx, dy, zoom, trust) per pair (with scans=True also the per-window scan results).
+        show: the device luma planes of the cur frames ([h, pitch] uint8 tensors of one pitch); copies of them with the correlation surface painted
+        into the window(s) are returned last"""
         n = len(cur)
         out = (DepanEstimateResult * max(n, 1))()
         sc = (DepanEstimateScan * max(n * self.windows, 1))()
         if n == 0:
             _check(lib().mvx_depan_estimate_correlate(self.h, 0, None, None, None, None, out, None, None))
-            return ([], []) if scans else []
+            empty = ([],) * (1 + bool(scans) + (show is not None))
+            return empty if len(empty) > 1 else []
         _torch()
         pp = (C.c_void_p * n)(*[p.data_ptr() for p in prev])
         cp = (C.c_void_p * n)(*[c.data_ptr() for c in cur])
-        _check(lib().mvx_depan_estimate_correlate(self.h, n, pp, cp, self._ints(n, top_field), self._ints(n, frame_numbers), out, sc, _stream()))
+        painted = None
+        if show is None:
+            _check(lib().mvx_depan_estimate_correlate(self.h, n, pp, cp, self._ints(n, top_field), self._ints(n, frame_numbers), out, sc, _stream()))
+        else:
+            if len(show) != n or any(f.stride(0) != show[0].stride(0) or f.device != show[0].device for f in show):
+                raise MvtoolsError("DepanEstimate.correlate: show takes one plane per pair, all of one pitch and one device")
+            painted = [f.clone() for f in show]
+            sp = (C.c_void_p * n)(*[f.data_ptr() for f in painted])
+            _check(lib().mvx_depan_estimate_correlate_show(self.h, n, pp, cp, self._ints(n, top_field), self._ints(n, frame_numbers), out, sc, sp,
+                                                           painted[0].stride(0), _stream()))
         res = [dict(dx=r.dx, dy=r.dy, zoom=r.zoom, trust=r.trust) for r in out[:n]]
-        if not scans:
-            return res
-        keys = [f[0] for f in DepanEstimateScan._fields_]
-        return res, [{k: getattr(s, k) for k in keys} for s in sc[:n * self.windows]]
+        ret = (res,)
+        if scans:
+            keys = [f[0] for f in DepanEstimateScan._fields_]
+            ret += ([{k: getattr(s, k) for k in keys} for s in sc[:n * self.windows]],)
+        if painted is not None:
+            ret += (painted,)
+        return ret if len(ret) > 1 else res
 
     def host_tail(self, scans, top_field=None, frame_numbers=None):
         """the host tail alone from windows scan results (dicts) per pair; no device"""

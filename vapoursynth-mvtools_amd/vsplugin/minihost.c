@@ -19,6 +19,13 @@
  *       out.raw : super      -> every super frame (planes tightly packed) ; props of frame 0 on stdout
  *                 analyse    -> per frame: 84-byte MVTools_MVAnalysisData + MVTools_vectors, backward (isb=1) then forward
  *                 degrainN / compensate -> output frames, planes tightly packed
+ *       pipeline: depananalyse | depanestimate | depancompensate | depanstabilise (the plugin registers these with MVX_VS_DEPAN=1).  Argument prefixes: e.* for
+ *                 DepanEstimate, n.* for DepanAnalyse (on the backward vectors of delta 1, x.vectors=fw: the forward ones; x.mask=path: its mask clip, 8-bit), f.* for the final filter;
+ *                 x.data=analyse|estimate (default estimate): where the data clip of depancompensate / depanstabilise comes from.  With estimate no mv.Super
+ *                 and no mv.Analyse is built.  Per frame the run prints the data clip's Depan_dx / _dy / _zoom / _rot as C hex floats and every Depan*_info
+ *                 string of the output frame; out.raw gets the output frames
+ *   `error` takes DepanAnalyse (on the backward vectors) and DepanEstimate | DepanCompensate | DepanStabilise (data clip: DepanEstimate(clip) with e.*; no mv.Super)
+ *   a stub of com.vapoursynth.text / FrameProps returns its clip unchanged and prints "text.FrameProps props=<name>"; x.notext=1 hides the plugin
  */
 #include <dlfcn.h>
 #include <pthread.h>
@@ -331,7 +338,8 @@ static VSNode *invoke(const char *name, VSMap *in, char *err, size_t errsz) {
                 char pat[80];
                 snprintf(pat, sizeof(pat), "%s:", e->key);
                 const char *hit = strstr(g_funcs[i].args, pat);
-                if (!hit || (hit != g_funcs[i].args && hit[-1] != ';')) { snprintf(err, errsz, "%s: Function does not take argument(s) named %s", name, e->key); return NULL; }
+                while (hit && hit != g_funcs[i].args && hit[-1] != ';') hit = strstr(hit + 1, pat); /* ("tzoom:" also ends "initzoom:") */
+                if (!hit) { snprintf(err, errsz, "%s: Function does not take argument(s) named %s", name, e->key); return NULL; }
             }
             VSMap *out = createMap();
             g_funcs[i].fn(in, out, g_funcs[i].user, NULL, &g_api);
@@ -360,10 +368,24 @@ static const VSFrame *VS_CC assumeGetFrame(int n, int reason, void *inst, void *
     return dst;
 }
 static void VS_CC assumeFree(void *inst, VSCore *core, const VSAPI *vs) { (void)core; AssumeData *d = (AssumeData *)inst; vs->freeNode(d->node); free(d); }
-static struct VSPlugin { int dummy; } *g_std = (struct VSPlugin *)&g_nfuncs;
-static VSPlugin *VS_CC getPluginByID(const char *id, VSCore *core) { (void)core; return strcmp(id, "com.vapoursynth.std") ? NULL : g_std; }
+static struct VSPlugin { int dummy; } *g_std = (struct VSPlugin *)&g_nfuncs, *g_text = (struct VSPlugin *)&g_funcs;
+static int g_notext; /* x.notext=1: the host has no com.vapoursynth.text */
+static VSPlugin *VS_CC getPluginByID(const char *id, VSCore *core) {
+    (void)core;
+    if (!strcmp(id, "com.vapoursynth.text")) return g_notext ? NULL : g_text;
+    return strcmp(id, "com.vapoursynth.std") ? NULL : g_std;
+}
 static VSMap *VS_CC apiInvoke(VSPlugin *plugin, const char *name, const VSMap *args) {
     VSMap *out = createMap();
+    if (plugin == g_text && !strcmp(name, "FrameProps")) { /* the overlay itself is not the shell's: the clip passes through */
+        int e = 0;
+        VSNode *node = mapGetNode(args, "clip", 0, &e);
+        const char *props = mapGetData(args, "props", 0, &e);
+        printf("text.FrameProps props=%s\n", props ? props : "");
+        mapSetNode(out, "clip", node, maReplace);
+        node_free(node);
+        return out;
+    }
     if (plugin != g_std || strcmp(name, "AssumeFPS")) { mapSetError(out, "minihost: only std.AssumeFPS exists"); return out; }
     int e = 0;
     AssumeData *d = (AssumeData *)calloc(1, sizeof(*d));
@@ -459,6 +481,15 @@ static void dump_frame(FILE *fp, const VSFrame *f) {
         for (int y = 0; y < plane_h(f, p); y++) fwrite(f->data[p] + (size_t)y * f->stride[p], 1, (size_t)plane_w(f, p) * f->fmt.bytesPerSample, fp);
 }
 static void die(const char *what, const char *err) { printf("ERROR %s: %s\n", what, err); exit(1); }
+static int has_arg(int argc, char **argv, const char *arg) { for (int i = 0; i < argc; i++) if (!strcmp(argv[i], arg)) return 1; return 0; }
+static VSNode *invoke(const char *name, VSMap *in, char *err, size_t errsz);
+/* DepanEstimate(clip, e.*): the data clip that needs neither mv.Super nor mv.Analyse */
+static VSNode *depan_estimate_clip(VSNode *clip, char extraPrefix, int argc, char **argv, char *err, size_t errsz) {
+    VSMap *m = createMap();
+    mapSetNode(m, "clip", clip, maReplace); add_args(m, 'e', argc, argv);
+    if (extraPrefix) add_args(m, extraPrefix, argc, argv);
+    return invoke("DepanEstimate", m, err, errsz);
+}
 
 /* x.threads=N: request frames 0..count-1 of up to four nodes from N threads at once (results stay in the nodes' frame tables) */
 typedef struct Work { VSNode *nodes[4]; int nnodes, count, next, done; char err[2048]; } Work;
@@ -531,7 +562,15 @@ int main(int argc, char **argv) {
         }
         VSMap *m = createMap();
         VSNode *out = NULL;
-        if (!strcmp(filter, "Super")) {
+        g_notext = has_arg(argc - 7, argv + 7, "x.notext=1");
+        if (!strcmp(filter, "DepanEstimate")) out = depan_estimate_clip(fclip, 'f', argc - 7, argv + 7, err, sizeof(err));
+        else if (!strcmp(filter, "DepanCompensate") || !strcmp(filter, "DepanStabilise")) {
+            VSNode *data = depan_estimate_clip(clip, 0, argc - 7, argv + 7, err, sizeof(err));
+            if (!data) die("DepanEstimate", err);
+            mapSetNode(m, "clip", fclip, maReplace); mapSetNode(m, "data", data, maReplace); add_args(m, 'f', argc - 7, argv + 7);
+            out = invoke(filter, m, err, sizeof(err));
+        }
+        else if (!strcmp(filter, "Super")) {
             mapSetNode(m, "clip", clip, maReplace); add_args(m, 'f', argc - 7, argv + 7);
             VSNode *pc = pelclip_from_args(argc - 7, argv + 7, bits, 4);
             if (pc) mapSetNode(m, "pelclip", pc, maReplace);
@@ -551,9 +590,9 @@ int main(int argc, char **argv) {
                 VSNode *bw = invoke("Analyse", a1, err, sizeof(err)); if (!bw) die("Analyse", err);
                 VSNode *fw = invoke("Analyse", a2, err, sizeof(err)); if (!fw) die("Analyse", err);
                 mapSetNode(m, "clip", fclip, maReplace);
-                if (strcmp(filter, "Mask")) mapSetNode(m, "super", sup, maReplace); /* (mv.Mask takes no super clip) */
+                if (strcmp(filter, "Mask") && strcmp(filter, "DepanAnalyse")) mapSetNode(m, "super", sup, maReplace); /* (mv.Mask and mv.DepanAnalyse take no super clip) */
                 add_args(m, 'f', argc - 7, argv + 7);
-                if (!strcmp(filter, "Compensate") || !strcmp(filter, "Flow") || !strcmp(filter, "Mask")) { mapSetNode(m, "vectors", bw, maReplace); out = invoke(filter, m, err, sizeof(err)); }
+                if (!strcmp(filter, "Compensate") || !strcmp(filter, "Flow") || !strcmp(filter, "Mask") || !strcmp(filter, "DepanAnalyse")) { mapSetNode(m, "vectors", bw, maReplace); out = invoke(filter, m, err, sizeof(err)); }
                 else if (!strcmp(filter, "Degrain1Swapped")) { mapSetNode(m, "mvbw", fw, maReplace); mapSetNode(m, "mvfw", bw, maReplace); out = invoke("Degrain1", m, err, sizeof(err)); }
                 else { mapSetNode(m, "mvbw", bw, maReplace); mapSetNode(m, "mvfw", fw, maReplace); out = invoke(filter, m, err, sizeof(err)); }
             }
@@ -576,6 +615,61 @@ int main(int argc, char **argv) {
     if (!fo) { fprintf(stderr, "cannot write %s\n", outPath); return 2; }
     if (getenv("MVX_HOST_TIMES")) fprintf(stderr, "minihost: clip loaded at %.2f s after start\n", now_s() - g_start); /* (graph construction starts here) */
 
+    g_notext = has_arg(nextra, extra, "x.notext=1");
+    if (!strncmp(pipeline, "depan", 5)) { /* the Depan family: data clip (DepanAnalyse on mv.Analyse's vectors, or DepanEstimate) -> DepanCompensate | DepanStabilise */
+        const char *final = !strcmp(pipeline, "depananalyse") ? "DepanAnalyse" : !strcmp(pipeline, "depanestimate") ? "DepanEstimate" : !strcmp(pipeline, "depancompensate") ? "DepanCompensate" :
+                            !strcmp(pipeline, "depanstabilise") ? "DepanStabilise" : NULL;
+        if (!final) { fprintf(stderr, "bad pipeline\n"); return 2; }
+        const int isData = !strcmp(final, "DepanAnalyse") || !strcmp(final, "DepanEstimate");
+        const int fromAnalyse = !strcmp(final, "DepanAnalyse") || (!isData && has_arg(nextra, extra, "x.data=analyse"));
+        VSNode *data;
+        if (fromAnalyse) {
+            VSMap *sm = createMap(); mapSetNode(sm, "clip", clip, maReplace); add_args(sm, 's', nextra, extra);
+            VSNode *sup = invoke("Super", sm, err, sizeof(err));
+            if (!sup) die("Super", err);
+            VSMap *am = createMap(); mapSetNode(am, "super", sup, maReplace); add_args(am, 'a', nextra, extra);
+            mapSetInt(am, "isb", has_arg(nextra, extra, "x.vectors=fw") ? 0 : 1, maReplace); mapSetInt(am, "delta", 1, maReplace);
+            VSNode *vectors = invoke("Analyse", am, err, sizeof(err));
+            if (!vectors) die("Analyse", err);
+            VSMap *nm = createMap(); mapSetNode(nm, "clip", clip, maReplace); mapSetNode(nm, "vectors", vectors, maReplace); add_args(nm, 'n', nextra, extra);
+            for (int i = 0; i < nextra; i++) /* x.mask=path: DepanAnalyse's mask clip, 8-bit, in the source clip's layout */
+                if (!strncmp(extra[i], "x.mask=", 7)) mapSetNode(nm, "mask", source_clip(extra[i] + 7, w, hh, 8, nframes), maReplace);
+            if (isData) add_args(nm, 'f', nextra, extra);
+            data = invoke("DepanAnalyse", nm, err, sizeof(err));
+            if (!data) die("DepanAnalyse", err);
+        } else {
+            data = depan_estimate_clip(clip, isData ? 'f' : 0, nextra, extra, err, sizeof(err));
+            if (!data) die("DepanEstimate", err);
+        }
+        VSNode *out = data;
+        if (!isData) {
+            VSMap *m = createMap(); mapSetNode(m, "clip", clip, maReplace); mapSetNode(m, "data", data, maReplace); add_args(m, 'f', nextra, extra);
+            out = invoke(final, m, err, sizeof(err));
+            if (!out) die(pipeline, err);
+        }
+        g_uncapped = out;
+        prefetch_parallel(threads, nframes, &out, 1); /* (output frames only: every upstream request is the filters') */
+        for (int n = 0; n < nframes; n++) {
+            const VSFrame *f = eval_frame(n, out, err, sizeof(err));
+            if (!f) die("output frame", err);
+            const VSFrame *df = out == data ? frame_addref(f) : eval_frame(n, data, err, sizeof(err));
+            if (!df) die("data frame", err);
+            int e[4];
+            const float dx = (float)mapGetFloat(df->props, "Depan_dx", 0, &e[0]), dy = (float)mapGetFloat(df->props, "Depan_dy", 0, &e[1]);
+            const float zoom = (float)mapGetFloat(df->props, "Depan_zoom", 0, &e[2]), rot = (float)mapGetFloat(df->props, "Depan_rot", 0, &e[3]);
+            if (e[0] || e[1] || e[2] || e[3]) die("data frame", "Depan_* properties missing");
+            printf("frame %d Depan_dx=%a Depan_dy=%a Depan_zoom=%a Depan_rot=%a\n", n, (double)dx, (double)dy, (double)zoom, (double)rot);
+            static const char *const infos[4] = { "DepanAnalyse_info", "DepanEstimate_info", "DepanCompensate_info", "DepanStabilise_info" };
+            for (int k = 0; k < 4; k++) {
+                int ie = 0;
+                const char *text = mapGetData(f->props, infos[k], 0, &ie);
+                if (!ie) printf("frame %d %s=%s\n", n, infos[k], text);
+            }
+            dump_frame(fo, f);
+            freeFrame(df); freeFrame(f);
+        }
+        fclose(fo); printf("DONE\n"); return 0;
+    }
     VSMap *sm = createMap(); mapSetNode(sm, "clip", clip, maReplace); add_args(sm, 's', nextra, extra);
     VSNode *pelclip = pelclip_from_args(nextra, extra, bits, nframes);
     if (pelclip) mapSetNode(sm, "pelclip", pelclip, maReplace);
@@ -707,7 +801,7 @@ int main(int argc, char **argv) {
         static const char *vn[] = { "mvbw", "mvfw", "mvbw2", "mvfw2", "mvbw3", "mvfw3", "mvbw4", "mvfw4", "mvbw5", "mvfw5", "mvbw6", "mvfw6" };
         for (int r = 0; r < 2 * R; r++) mapSetNode(m, vn[r], vec[r], maReplace);
         add_args(m, 'd', nextra, extra);
-        char fn[16]; snprintf(fn, sizeof(fn), "Degrain%d", R);
+        char fn[24]; snprintf(fn, sizeof(fn), "Degrain%d", R);
         out = invoke(fn, m, err, sizeof(err));
     }
     if (!out) die(pipeline, err);

@@ -9,7 +9,11 @@
  * and, when the host's environment has MVX_VS_FLOW=1 as the plugin is loaded, the per-sample filters
  *     FlowInter (src/MVFlowInter.c:700-710)   FlowFPS (src/MVFlowFPS.c:913-925)   Flow (src/MVFlow.cpp:597-607)
  *     FlowBlur  (src/MVFlowBlur.c:555-565)    Mask    (src/MVMask.c:350-360)
- * and keeps the reference's inter-filter data layout: super-frame geometry + Super_* props on frame 0
+ * and, with MVX_VS_DEPAN=1, the global-motion filters (src/MVDepan.cpp:4211-4288)
+ *     DepanAnalyse   DepanEstimate   DepanCompensate   DepanStabilise
+ * DepanEstimate is ONE node where the reference chains three: its temporary DepanEstimateFFT / FFT2 and DepanEstimateX / Y / Zoom / Trust frame properties do not
+ * exist here (the spectra stay on the device, the stage-2 results in a table of the instance); info=1 sets Depan*_info and invokes text.FrameProps as the reference does.
+ * The shell keeps the reference's inter-filter data layout: super-frame geometry + Super_* props on frame 0
  * (src/MVSuper.c:111-120), vector clips = copyFrame(super[n]) + binary props MVTools_MVAnalysisData / MVTools_vectors
  * (src/MVAnalyse.c:224-239).  This file is the only code that touches VSAPI; all arithmetic happens on the GPU behind
  * the C ABI, and every compute failure surfaces through setFilterError (there is no CPU path).
@@ -2624,6 +2628,511 @@ static void VS_CC maskCreate(const VSMap *in, VSMap *out, void *user, VSCore *co
     vs->createVideoFilter(out, "Mask", &d->vi, consumerGetFrame, consumerFree, fmParallel, deps, 2, d, core);
 }
 
+/* ------------------------------------------------------------------------------------------------ the Depan family (MVX_VS_DEPAN=1)
+ * mv.DepanAnalyse / mv.DepanEstimate write Depan_dx / _dy / _zoom / _rot on copies of the clip's frames, mv.DepanCompensate / mv.DepanStabilise read them from
+ * their data clip and warp.  All four sit on the Consumer skeleton (none takes a super clip; DepanEstimate takes no vectors either).  The library's creation
+ * functions give the reference's error texts in the reference's order; what only the host can see (a format that is not constant, the sample type, the
+ * colour family) reaches them as a bit depth of 0, which draws the reference's format message at its place in that order.  info=1 sets the Depan*_info
+ * string with the reference's format from the numbers the library returns and puts text.FrameProps behind the filter (MVDepan.cpp:446-470). */
+ENGINE_DESTROY(mvx_depan_analyse) ENGINE_DESTROY(mvx_depan_compensate) ENGINE_DESTROY(mvx_depan_stabilise)
+
+/* a clip's format as the library takes it.  floatSamples NULL: integer clips only (DepanAnalyse, DepanCompensate :2811-2820, DepanStabilise :4025-4034); else DepanEstimate's
+ * rule (:1340-1344), a float clip reaching the library as float_samples.  Anything else the reference's format test refuses becomes a bit depth of 0 */
+static void depan_clip_of(mvx_depan_clip *c, const VSVideoInfo *vi, int *floatSamples) {
+    const VSVideoFormat *f = &vi->format;
+    const int isFloat = f->sampleType == stFloat;
+    const int known = mvx_vsh_is_constant_video_format(vi) && (f->colorFamily == cfYUV || f->colorFamily == cfGray) && (floatSamples ? 1 : !isFloat);
+    c->width = vi->width; c->height = vi->height; c->bits = known ? f->bitsPerSample : 0;
+    c->subsampling_w = f->subSamplingW; c->subsampling_h = f->subSamplingH; c->gray = f->colorFamily == cfGray;
+    if (floatSamples) *floatSamples = known && isFloat;
+}
+/* (double)MVX_UNSET where the argument is absent: mvx_depan_stabilise_args */
+static double opt_float_unset(const VSMap *in, const char *key, const VSAPI *vs) { return opt_float(in, key, (double)MVX_UNSET, vs); }
+
+/* Depan_dx, _dy, _zoom, _rot of a data frame -> m[0..3] (the library's order); 0 when one is missing */
+static int depan_read_motion(float m[4], const VSFrame *f, const VSAPI *vs) {
+    static const char *const keys[4] = { "Depan_dx", "Depan_dy", "Depan_zoom", "Depan_rot" };
+    const VSMap *props = vs->getFramePropertiesRO(f);
+    int ok = 1;
+    for (int k = 0; k < 4; k++) { int e = 0; m[k] = (float)vs->mapGetFloat(props, keys[k], 0, &e); if (e) ok = 0; }
+    return ok;
+}
+static void depan_write_motion(VSFrame *dst, const mvx_depan_motion *m, const VSAPI *vs) {
+    VSMap *props = vs->getFramePropertiesRW(dst);
+    vs->mapSetFloat(props, "Depan_dx", m->dx, maReplace);
+    vs->mapSetFloat(props, "Depan_dy", m->dy, maReplace);
+    vs->mapSetFloat(props, "Depan_zoom", m->zoom, maReplace);
+    vs->mapSetFloat(props, "Depan_rot", m->rot, maReplace);
+}
+static void depan_set_info(VSFrame *dst, const char *prop, const char *text, const VSAPI *vs) {
+    vs->mapSetData(vs->getFramePropertiesRW(dst), prop, text, -1, dtUtf8, maReplace);
+}
+/* invokeFrameProps, :446-470, and the message its callers put in front.  A host without the text plugin fails creation (the reference hands invoke a NULL plugin) */
+static void depan_info_overlay(const char *filter, const char *prop, VSMap *out, VSCore *core, const VSAPI *vs) {
+    char msg[700];
+    VSPlugin *text = vs->getPluginByID("com.vapoursynth.text", core);
+    if (!text) {
+        snprintf(msg, sizeof(msg), "%s: failed to invoke text.FrameProps: the host has no plugin com.vapoursynth.text.", filter);
+        vs->mapSetError(out, msg);
+        return;
+    }
+    VSNode *node = vs->mapGetNode(out, "clip", 0, NULL);
+    VSMap *args = vs->createMap();
+    vs->mapSetNode(args, "clip", node, maReplace);
+    vs->freeNode(node);
+    vs->mapSetData(args, "props", prop, -1, dtUtf8, maReplace);
+    VSMap *ret = vs->invoke(text, "FrameProps", args);
+    vs->freeMap(args);
+    if (vs->mapGetError(ret)) {
+        snprintf(msg, sizeof(msg), "%s: failed to invoke text.FrameProps: %s", filter, vs->mapGetError(ret));
+        vs->mapSetError(out, msg);
+        vs->freeMap(ret);
+        return;
+    }
+    node = vs->mapGetNode(ret, "clip", 0, NULL);
+    vs->freeMap(ret);
+    vs->mapSetNode(out, "clip", node, maReplace);
+    vs->freeNode(node);
+}
+/* errors of a Depan frame: the library's text as it is (it carries the filter's name where the reference's does) */
+static void depan_frame_error(const char *name, int rc, VSFrameContext *ctx, const VSAPI *vs) {
+    char msg[MVX_ERRLEN + 64];
+    if (rc == MVX_E_NOMEM) { snprintf(msg, sizeof(msg), "%s: out of memory.", name); vs->setFilterError(msg, ctx); }
+    else vs->setFilterError(mvx_last_error(), ctx);
+}
+
+/* ---- mv.DepanAnalyse, MVDepan.cpp:237-430 / :473-615 */
+
+typedef struct DepanAnalyseData { Consumer c; VSNode *node, *vectors, *mask; const VSVideoInfo *vi; mvx_depan_analyse *da; mvx_analysis_data ad; ptrdiff_t maskPitch[3]; FieldOpt fo; int info; } DepanAnalyseData;
+
+static const VSFrame *VS_CC depanAnalyseGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    (void)fd;
+    DepanAnalyseData *d = (DepanAnalyseData *)inst;
+    const int nmv = d->ad.isBackward ? (n > 0 ? n - 1 : 0) : n; /* :287 */
+    if (reason == arInitial) { /* :243-247 */
+        vs->requestFrameFilter(nmv, d->vectors, ctx);
+        vs->requestFrameFilter(n, d->node, ctx);
+        if (d->mask) vs->requestFrameFilter(n, d->mask, ctx);
+        return NULL;
+    }
+    if (reason != arAllFramesReady) return NULL;
+    const VSFrame *src = vs->getFrameFilter(n, d->node, ctx);
+    void *dblob = NULL, *maskArena = NULL, *dmask[3] = { NULL, NULL, NULL };
+    int rc = clip_blob_to_device(&dblob, nmv, d->vectors, &d->ad, ctx, vs);
+    if (rc == MVX_E_ARG) rc = 0; /* an unusable blob: NULL, a frame without a result */
+    if (!rc && d->mask) {
+        const VSFrame *mf = vs->getFrameFilter(n, d->mask, ctx);
+        rc = upload_plane_set(dmask, &maskArena, mf, d->maskPitch, 1, 1, vs);
+        vs->freeFrame(mf);
+    }
+    int missing = 0;
+    const int32_t top = d->fo.fields ? frame_top_field(&d->fo, src, n, &missing, vs) : 0;
+    mvx_depan_motion m;
+    memset(&m, 0, sizeof(m));
+    const void *blobs[1] = { dblob }, *masks[1] = { dmask[0] };
+    if (!rc) rc = mvx_depan_analyse_frames(d->da, 1, blobs, d->mask ? masks : NULL, d->maskPitch[0], &top, &m, thread_stream());
+    shell_quiesce(rc);
+    if (dblob) mvx_dev_free(dblob);
+    if (maskArena) mvx_dev_free(maskArena);
+    if (!rc && missing && m.dx != 0.0f) { /* :371-383: the parity is read for a frame with a result only */
+        vs->freeFrame(src);
+        vs->setFilterError("DepanAnalyse: _Field property not found in input frame. Therefore, you must pass tff argument.", ctx);
+        return NULL;
+    }
+    if (rc) { vs->freeFrame(src); depan_frame_error("DepanAnalyse", rc, ctx, vs); return NULL; }
+    VSFrame *dst = vs->copyFrame(src, core);
+    vs->freeFrame(src);
+    if (d->info) { /* :405 */
+        char info[129];
+        snprintf(info, 128, "fn=%d iter=%d error=%.3f dx=%.2f dy=%.2f rot=%.3f zoom=%.5f", n, m.iter, m.error, m.dx, m.dy, m.rot, m.zoom);
+        depan_set_info(dst, "DepanAnalyse_info", info, vs);
+    }
+    depan_write_motion(dst, &m, vs);
+    return dst;
+}
+
+static void VS_CC depanAnalyseCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
+    warm_barrier();
+    (void)user;
+    DepanAnalyseData *d = (DepanAnalyseData *)consumer_new(sizeof(*d), "DepanAnalyse", depanAnalyseGetFrameUngated, mvx_depan_analyse_destroy_engine);
+    char err[1400] = "", aerr[1400] = "", lerr[MVX_ERRLEN] = "";
+    int e = 0;
+    mvx_depan_analyse_args a;
+    a.zoom = opt_int(in, "zoom", vs); a.rot = opt_int(in, "rot", vs);
+    if (a.zoom != MVX_UNSET) a.zoom = !!a.zoom;
+    if (a.rot != MVX_UNSET) a.rot = !!a.rot;
+    a.pixaspect = opt_float(in, "pixaspect", 1.0, vs); a.error = opt_float(in, "error", 15.0, vs); a.wrong = opt_float(in, "wrong", 10.0, vs); a.zerow = opt_float(in, "zerow", 0.05, vs);
+    a.thscd1 = opt_int64(in, "thscd1", vs); a.thscd2 = opt_int(in, "thscd2", vs);
+    d->info = !!vs->mapGetInt(in, "info", 0, &e);
+    field_opt(&d->fo, in, vs);
+    a.fields = d->fo.fields;
+    d->node = consumer_node(&d->c, in, "clip", vs);
+    d->vi = vs->getVideoInfo(d->node);
+    d->vectors = consumer_node(&d->c, in, "vectors", vs);
+    d->mask = vs->mapGetNode(in, "mask", 0, &e);
+    if (d->mask) d->c.nodes[d->c.nnodes++] = d->mask;
+    mvx_depan_clip clip, mclip;
+    depan_clip_of(&clip, d->vi, NULL);
+    const VSVideoInfo *mvi = d->mask ? vs->getVideoInfo(d->mask) : NULL;
+    if (mvi) {
+        depan_clip_of(&mclip, mvi, NULL);
+        mclip.bits = mvx_vsh_is_constant_video_format(mvi) ? mvi->format.bitsPerSample : 99; /* :558-562: not constant fails as more than 8 bits does */
+        clip_pitches(d->maskPitch, mvi, 1);
+    }
+    /* the reference's order: pixaspect, the clip's format, the lengths, the mask (all from the library but the second), then the vector clip's data (:575), then
+     * delta and thscd (the library).  A vector clip without data is tried with a blank one: whatever fails before :575 is reported first */
+    const int noData = adata_from_clip(&d->ad, d->vectors, "DepanAnalyse", "vectors", aerr, sizeof(aerr), vs) != 0;
+    if (noData) { memset(&d->ad, 0, sizeof(d->ad)); d->ad.nDeltaFrame = 1; }
+    if ((float)a.pixaspect > 0.0f && !mvx_vsh_is_constant_video_format(d->vi)) snprintf(err, sizeof(err), "DepanAnalyse: clip must have constant format and dimensions.");
+    else if (mvx_depan_analyse_create(&a, &d->ad, &clip, mvi ? &mclip : NULL, d->vi->numFrames, vs->getVideoInfo(d->vectors)->numFrames, mvi ? mvi->numFrames : 0, &d->da, lerr)) {
+        static const char *const early[3] = { "DepanAnalyse: pixaspect", "DepanAnalyse: vectors must", "DepanStabilise: mask" };
+        int isEarly = 0;
+        for (int k = 0; k < 3; k++) if (!strncmp(lerr, early[k], strlen(early[k]))) isEarly = 1;
+        snprintf(err, sizeof(err), "%s", noData && !isEarly ? aerr : lerr);
+    }
+    else if (noData) snprintf(err, sizeof(err), "%s", aerr);
+    d->c.engine = d->da;
+    if (err[0]) { consumer_fail(&d->c, err, out, vs); return; }
+    VSFilterDependency deps[3] = { { d->node, rpStrictSpatial }, { d->vectors, rpGeneral }, { d->mask, rpStrictSpatial } };
+    vs->createVideoFilter(out, "DepanAnalyse", d->vi, consumerGetFrame, consumerFree, fmParallel, deps, d->mask ? 3 : 2, d, core);
+    if (d->info && !vs->mapGetError(out)) depan_info_overlay("DepanAnalyse", "DepanAnalyse_info", out, core, vs);
+}
+
+/* ---- mv.DepanEstimate, MVDepan.cpp:956-1243 / :1271-1503.  ONE node where the reference chains three: the spectra the reference hands from stage 1 to stage 2
+ * as DepanEstimateFFT / FFT2 properties stay on the device in a small per-instance table of recently used frames, and the stage-2 results it hands to stage 3 as
+ * DepanEstimateX / Y / Zoom / Trust properties live in a per-instance table by frame number (16 bytes a frame, each filled once).  Neither kind of property
+ * exists here.  The library's results depend on neither batch size nor order, so the output does not depend on the order of the requests.  show=1: the
+ * correlate of pair n always runs through mvx_depan_estimate_correlate_show on a device copy of frame n's luma, and the window rows come back. */
+
+#define DE_SPECTRA_SLOTS 8
+typedef struct DepanEstimateData {
+    Consumer c; VSNode *node; const VSVideoInfo *vi; mvx_depan_estimate *de; mvx_depan_estimate_info ei; ptrdiff_t pitch[3]; int info, show;
+    pthread_mutex_t mu;                    /* the two tables, and the device work that fills them */
+    mvx_depan_estimate_result *res; unsigned char *have;
+    struct { int frame; void *buf; uint64_t stamp; } slot[DE_SPECTRA_SLOTS]; uint64_t clock;
+} DepanEstimateData;
+
+static void depan_estimate_destroy_engine(void *e) {
+    DepanEstimateData *d = (DepanEstimateData *)e;
+    for (int i = 0; i < DE_SPECTRA_SLOTS; i++) if (d->slot[i].buf) mvx_dev_free(d->slot[i].buf);
+    free(d->res); free(d->have);
+    if (d->de) mvx_depan_estimate_destroy(d->de);
+    pthread_mutex_destroy(&d->mu);
+}
+/* the device spectra of clip frame `frame` (mu held); `keep`: a frame whose slot must survive */
+static int depan_estimate_spectra_of(DepanEstimateData *d, int frame, int keep, void **out, VSFrameContext *ctx, const VSAPI *vs) {
+    int lru = -1;
+    for (int i = 0; i < DE_SPECTRA_SLOTS; i++) {
+        if (d->slot[i].buf && d->slot[i].frame == frame) { d->slot[i].stamp = ++d->clock; *out = d->slot[i].buf; return 0; }
+        if (d->slot[i].buf && d->slot[i].frame == keep) continue;
+        if (lru < 0 || !d->slot[i].buf || (d->slot[lru].buf && d->slot[i].stamp < d->slot[lru].stamp)) lru = i;
+    }
+    if (!d->slot[lru].buf) d->slot[lru].buf = shell_alloc((size_t)d->ei.windows * (size_t)d->ei.spectrum_bytes);
+    if (!d->slot[lru].buf) return MVX_E_NOMEM;
+    d->slot[lru].frame = -1;
+    const VSFrame *f = vs->getFrameFilter(frame, d->node, ctx);
+    void *arena = NULL, *plane[3];
+    int rc = upload_plane_set(plane, &arena, f, d->pitch, 1, d->vi->format.bytesPerSample, vs);
+    vs->freeFrame(f);
+    const void *planes[1] = { plane[0] };
+    void *spectra[1] = { d->slot[lru].buf };
+    if (!rc) rc = mvx_depan_estimate_spectra(d->de, 1, planes, d->pitch[0], spectra, thread_stream());
+    if (!rc) rc = mvx_stream_sync(thread_stream()); /* another thread's stream reads them next */
+    shell_quiesce(rc);
+    if (arena) mvx_dev_free(arena);
+    if (rc) return rc;
+    d->slot[lru].frame = frame; d->slot[lru].stamp = ++d->clock;
+    *out = d->slot[lru].buf;
+    return 0;
+}
+
+static const VSFrame *VS_CC depanEstimateGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    (void)fd;
+    DepanEstimateData *d = (DepanEstimateData *)inst;
+    const int last = d->vi->numFrames - 1;
+    const int lo = n - 2 > 0 ? n - 2 : 0, hi = n + 1 < last ? n + 1 : last;
+    if (reason == arInitial) { /* stage 3 reads the results of n - 1 .. n + 1 (:1160-1162), stage 2 of a frame reads the frame before it too (:1005-1006) */
+        for (int k = lo; k <= hi; k++) vs->requestFrameFilter(k, d->node, ctx);
+        return NULL;
+    }
+    if (reason != arAllFramesReady) return NULL;
+    const VSFrame *src = vs->getFrameFilter(n, d->node, ctx);
+    VSFrame *dst = vs->copyFrame(src, core);
+    vs->freeFrame(src);
+    const int want[3] = { n > 0 ? n - 1 : 0, n, n < last ? n + 1 : last };
+    const int bps = d->vi->format.bytesPerSample;
+    int rc = 0;
+    pthread_mutex_lock(&d->mu);
+    for (int k = 0; k < 3 && !rc; k++) {
+        const int r = want[k], paint = d->show && r == n && k == 1;
+        if (d->have[r] && !paint) continue;
+        const int p = r > 0 ? r - 1 : 0; /* frame 0 is its own predecessor, :1009 */
+        void *sprev = NULL, *scur = NULL;
+        rc = depan_estimate_spectra_of(d, p, r, &sprev, ctx, vs);
+        if (!rc) rc = depan_estimate_spectra_of(d, r, p, &scur, ctx, vs);
+        if (rc) break;
+        const VSFrame *fr = vs->getFrameFilter(r, d->node, ctx);
+        int e = 0;
+        const int field = !!vs->mapGetInt(vs->getFramePropertiesRO(fr), "_Field", 0, &e);
+        const int32_t top = e ? MVX_UNSET : field, num = r;
+        const void *pp[1] = { sprev }, *cp[1] = { scur };
+        mvx_depan_estimate_result res;
+        if (!paint) rc = mvx_depan_estimate_correlate(d->de, 1, pp, cp, &top, &num, &res, NULL, thread_stream());
+        else {
+            void *arena = NULL, *plane[3];
+            rc = upload_plane_set(plane, &arena, fr, d->pitch, 1, bps, vs);
+            void *planes[1] = { plane[0] };
+            if (!rc) rc = mvx_depan_estimate_correlate_show(d->de, 1, pp, cp, &top, &num, &res, NULL, planes, d->pitch[0], thread_stream());
+            if (!rc) rc = timed_download(vs->getWritePtr(dst, 0) + (size_t)d->ei.wtop * vs->getStride(dst, 0), vs->getStride(dst, 0),
+                                         (char *)plane[0] + (size_t)d->ei.wtop * d->pitch[0], d->pitch[0], (size_t)d->vi->width * bps, (size_t)d->ei.winy);
+            if (!rc) rc = mvx_stream_sync(thread_stream());
+            shell_quiesce(rc);
+            if (arena) mvx_dev_free(arena);
+        }
+        vs->freeFrame(fr);
+        if (!rc) { d->res[r] = res; d->have[r] = 1; }
+    }
+    mvx_depan_estimate_result tri[3];
+    if (!rc) for (int k = 0; k < 3; k++) tri[k] = d->res[want[k]];
+    pthread_mutex_unlock(&d->mu);
+    shell_quiesce(rc);
+    mvx_depan_motion m;
+    if (!rc) rc = mvx_depan_estimate_finish(d->de, n, tri, &m);
+    if (rc) { vs->freeFrame(dst); depan_frame_error("DepanEstimate", rc, ctx, vs); return NULL; }
+    depan_write_motion(dst, &m, vs);
+    if (d->info) { /* :1233 */
+        char info[129];
+        snprintf(info, 128, "fn=%d dx=%.2f dy=%.2f zoom=%.5f trust=%.2f", n, m.dx, m.dy, m.zoom, tri[1].trust);
+        depan_set_info(dst, "DepanEstimate_info", info, vs);
+    }
+    return dst;
+}
+
+static void VS_CC depanEstimateCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
+    warm_barrier();
+    (void)user;
+    DepanEstimateData *d = (DepanEstimateData *)consumer_new(sizeof(*d), "DepanEstimate", depanEstimateGetFrameUngated, depan_estimate_destroy_engine);
+    pthread_mutex_init(&d->mu, NULL);
+    d->c.engine = d;
+    char lerr[MVX_ERRLEN] = "";
+    int e = 0, floatSamples = 0;
+    mvx_depan_estimate_args a;
+    a.trust = opt_float(in, "trust", 4.0, vs); a.zoommax = opt_float(in, "zoommax", 1.0, vs); a.stab = opt_float(in, "stab", 1.0, vs); a.pixaspect = opt_float(in, "pixaspect", 1.0, vs);
+    a.winx = opt_int(in, "winx", vs); a.winy = opt_int(in, "winy", vs); a.wleft = opt_int(in, "wleft", vs); a.wtop = opt_int(in, "wtop", vs);
+    a.dxmax = opt_int(in, "dxmax", vs); a.dymax = opt_int(in, "dymax", vs);
+    FieldOpt fo;
+    field_opt(&fo, in, vs);
+    a.fields = fo.fields; a.tff = fo.tffExists ? fo.tff : MVX_UNSET;
+    d->info = !!vs->mapGetInt(in, "info", 0, &e);
+    d->show = !!vs->mapGetInt(in, "show", 0, &e);
+    d->node = consumer_node(&d->c, in, "clip", vs);
+    d->vi = vs->getVideoInfo(d->node);
+    mvx_depan_clip clip;
+    depan_clip_of(&clip, d->vi, &floatSamples);
+    a.float_samples = floatSamples;
+    if (mvx_depan_estimate_create(&a, &clip, d->vi->numFrames, &d->de, lerr)) { consumer_fail(&d->c, lerr, out, vs); return; }
+    mvx_depan_estimate_get_info(d->de, &d->ei);
+    clip_pitches(d->pitch, d->vi, d->vi->format.bytesPerSample);
+    d->res = (mvx_depan_estimate_result *)calloc((size_t)d->vi->numFrames, sizeof(*d->res));
+    d->have = (unsigned char *)calloc((size_t)d->vi->numFrames, 1);
+    if (!d->res || !d->have) { consumer_fail(&d->c, "DepanEstimate: out of memory.", out, vs); return; }
+    VSFilterDependency deps[1] = { { d->node, rpGeneral } };
+    vs->createVideoFilter(out, "DepanEstimate", d->vi, consumerGetFrame, consumerFree, fmParallel, deps, 1, d, core);
+    if (d->info && !vs->mapGetError(out)) depan_info_overlay("DepanEstimate", "DepanEstimate_info", out, core, vs);
+}
+
+/* ---- mv.DepanCompensate, MVDepan.cpp:2588-2735 / :2750-2881 */
+
+typedef struct DepanCompData { Consumer c; VSNode *node, *data; const VSVideoInfo *vi; mvx_depan_compensate *dc; mvx_depan_compensate_info ci; ptrdiff_t pitch[3]; int info; } DepanCompData;
+
+static const VSFrame *VS_CC depanCompGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    (void)fd;
+    DepanCompData *d = (DepanCompData *)inst;
+    int nsrc = n, start = n, end = n;
+    const int warp = mvx_depan_compensate_map(d->dc, n, &nsrc, &start, &end);
+    if (reason == arInitial) { /* :2594-2609 */
+        if (warp) {
+            vs->requestFrameFilter(nsrc, d->node, ctx);
+            for (int k = start + 1; k <= end; k++) vs->requestFrameFilter(k, d->data, ctx);
+        }
+        vs->requestFrameFilter(n, d->node, ctx);
+        return NULL;
+    }
+    if (reason != arAllFramesReady) return NULL;
+    if (!warp) return vs->getFrameFilter(n, d->node, ctx); /* :2613-2614 */
+    float motions[4 * 24], trsum[6], motion[4];
+    int count = 0;
+    for (int k = start + 1; k <= end && count < 24; k++, count++) {
+        const VSFrame *df = vs->getFrameFilter(k, d->data, ctx);
+        const int ok = depan_read_motion(motions + 4 * count, df, vs);
+        vs->freeFrame(df);
+        if (!ok) { vs->setFilterError("DepanCompensate: required frame properties not found in data clip. Did data clip really come from DepanAnalyse or DepanEstimate?", ctx); return NULL; }
+    }
+    const VSFrame *cur = vs->getFrameFilter(n, d->node, ctx);
+    int e = 0;
+    const int field = !!vs->mapGetInt(vs->getFramePropertiesRO(cur), "_Field", 0, &e);
+    vs->freeFrame(cur);
+    char lerr[MVX_ERRLEN] = "";
+    if (mvx_depan_motion_to_transform(d->dc, count, motions, n, e ? MVX_UNSET : field, trsum, motion, lerr)) { vs->setFilterError(lerr, ctx); return NULL; }
+    const VSFrame *src = vs->getFrameFilter(nsrc, d->node, ctx);
+    const int np = d->vi->format.numPlanes, bps = d->vi->format.bytesPerSample;
+    mvx_depan_compensate_job job;
+    memset(&job, 0, sizeof(job));
+    void *srcArena = NULL, *dstArena = NULL, *dsrc[3], *ddst[3];
+    int rc = upload_plane_set(dsrc, &srcArena, src, d->pitch, np, bps, vs);
+    if (!rc) rc = dst_plane_set(ddst, &dstArena, d->pitch, d->ci.plane_height, np);
+    for (int p = 0; p < np && !rc; p++) { job.src[p] = dsrc[p]; job.dst[p] = ddst[p]; }
+    memcpy(job.tr, trsum, sizeof(job.tr));
+    if (!rc) rc = mvx_depan_compensate_frames(d->dc, 1, &job, thread_stream());
+    VSFrame *dst = NULL;
+    if (!rc) {
+        dst = vs->newVideoFrame(&d->vi->format, d->vi->width, d->vi->height, src, core);
+        rc = download_plane_set(dst, ddst, d->pitch, np, bps, vs);
+    }
+    shell_quiesce(rc);
+    if (srcArena) mvx_dev_free(srcArena);
+    if (dstArena) mvx_dev_free(dstArena);
+    vs->freeFrame(src);
+    if (rc) { if (dst) vs->freeFrame(dst); depan_frame_error("DepanCompensate", rc, ctx, vs); return NULL; }
+    if (d->info) { /* :2724 */
+        char info[129];
+        snprintf(info, 128, "offset=%.2f, %d to %d, dx=%.2f, dy=%.2f, rot=%.3f zoom=%.5f", d->ci.offset, nsrc, n, motion[0], motion[1], motion[3], motion[2]);
+        depan_set_info(dst, "DepanCompensate_info", info, vs);
+    }
+    return dst;
+}
+
+static void VS_CC depanCompCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
+    warm_barrier();
+    (void)user;
+    DepanCompData *d = (DepanCompData *)consumer_new(sizeof(*d), "DepanCompensate", depanCompGetFrameUngated, mvx_depan_compensate_destroy_engine);
+    char lerr[MVX_ERRLEN] = "";
+    int e = 0;
+    mvx_depan_compensate_args a;
+    a.offset = opt_float(in, "offset", 0.0, vs); a.subpixel = opt_int(in, "subpixel", vs); a.pixaspect = opt_float(in, "pixaspect", 1.0, vs);
+    a.matchfields = opt_int(in, "matchfields", vs); a.mirror = opt_int(in, "mirror", vs); a.blur = opt_int(in, "blur", vs);
+    FieldOpt fo;
+    field_opt(&fo, in, vs);
+    a.fields = fo.fields; a.tff = fo.tffExists ? fo.tff : MVX_UNSET;
+    d->info = !!vs->mapGetInt(in, "info", 0, &e);
+    d->node = consumer_node(&d->c, in, "clip", vs);
+    d->vi = vs->getVideoInfo(d->node);
+    d->data = consumer_node(&d->c, in, "data", vs);
+    mvx_depan_clip clip;
+    depan_clip_of(&clip, d->vi, NULL);
+    clip_pitches(d->pitch, d->vi, d->vi->format.bytesPerSample > 0 ? d->vi->format.bytesPerSample : 1);
+    if (mvx_depan_compensate_create(&a, &clip, d->vi->numFrames, vs->getVideoInfo(d->data)->numFrames, d->pitch, d->pitch, &d->dc, lerr)) { consumer_fail(&d->c, lerr, out, vs); return; }
+    d->c.engine = d->dc;
+    mvx_depan_compensate_get_info(d->dc, &d->ci);
+    VSFilterDependency deps[2] = { { d->node, rpGeneral }, { d->data, rpGeneral } };
+    vs->createVideoFilter(out, "DepanCompensate", d->vi, consumerGetFrame, consumerFree, fmParallel, deps, 2, d, core);
+    if (d->info && !vs->mapGetError(out)) depan_info_overlay("DepanCompensate", "DepanCompensate_info", out, core, vs);
+}
+
+/* ---- mv.DepanStabilise, MVDepan.cpp:3562-3885 / :3909-4208 */
+
+typedef struct DepanStabData { Consumer c; VSNode *node, *data; const VSVideoInfo *vi; mvx_depan_stabilise *ds; mvx_depan_stabilise_info si; ptrdiff_t pitch[3]; int info; } DepanStabData;
+
+static const VSFrame *VS_CC depanStabGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    (void)fd;
+    DepanStabData *d = (DepanStabData *)inst;
+    int df = n, dl = n, cf = n, cl = n;
+    int rc = mvx_depan_stabilise_window(d->ds, n, &df, &dl, &cf, &cl);
+    if (rc) { if (reason == arInitial || reason == arAllFramesReady) depan_frame_error("DepanStabilise", rc, ctx, vs); return NULL; }
+    if (reason == arInitial) { /* :3571-3591, :3720-3763, and the data frames of the library's divergence 5 */
+        for (int k = df; k <= dl; k++) vs->requestFrameFilter(k, d->data, ctx);
+        for (int k = cf; k <= cl; k++) vs->requestFrameFilter(k, d->node, ctx);
+        return NULL;
+    }
+    if (reason != arAllFramesReady) return NULL;
+    float *motions = (float *)malloc(sizeof(float) * 4 * (size_t)(dl - df + 1));
+    if (!motions) { vs->setFilterError("DepanStabilise: out of memory.", ctx); return NULL; }
+    for (int k = df; k <= dl; k++) {
+        const VSFrame *f = vs->getFrameFilter(k, d->data, ctx);
+        const int ok = depan_read_motion(motions + 4 * (size_t)(k - df), f, vs);
+        vs->freeFrame(f);
+        if (!ok && k != 0) { /* (data frame 0 is never read, :4075-4078) */
+            free(motions);
+            vs->setFilterError("DepanStabilise: required frame properties not found in data clip.", ctx); /* :3343 */
+            return NULL;
+        }
+    }
+    char lerr[MVX_ERRLEN] = "";
+    mvx_depan_stabilise_job job;
+    memset(&job, 0, sizeof(job));
+    rc = mvx_depan_stabilise_plan(d->ds, n, motions, &job.plan, lerr);
+    free(motions);
+    if (rc) { vs->setFilterError(lerr, ctx); return NULL; }
+    const int np = d->vi->format.numPlanes, bps = d->vi->format.bytesPerSample;
+    const VSFrame *src = vs->getFrameFilter(n, d->node, ctx);
+    void *arena[3] = { NULL, NULL, NULL }, *dstArena = NULL, *dcur[3], *dprev[3], *dnext[3], *ddst[3];
+    rc = upload_plane_set(dcur, &arena[0], src, d->pitch, np, bps, vs);
+    if (!rc && job.plan.prev.used) {
+        const VSFrame *f = vs->getFrameFilter(job.plan.prev.frame, d->node, ctx);
+        rc = f ? upload_plane_set(dprev, &arena[1], f, d->pitch, np, bps, vs) : MVX_E_ARG;
+        vs->freeFrame(f);
+    }
+    if (!rc && job.plan.next.used) {
+        const VSFrame *f = vs->getFrameFilter(job.plan.next.frame, d->node, ctx);
+        rc = f ? upload_plane_set(dnext, &arena[2], f, d->pitch, np, bps, vs) : MVX_E_ARG;
+        vs->freeFrame(f);
+    }
+    if (!rc) rc = dst_plane_set(ddst, &dstArena, d->pitch, d->si.plane_height, np);
+    for (int p = 0; p < np && !rc; p++) {
+        job.cur[p] = dcur[p]; job.dst[p] = ddst[p];
+        if (job.plan.prev.used) job.prev[p] = dprev[p];
+        if (job.plan.next.used) job.next[p] = dnext[p];
+    }
+    if (!rc) rc = mvx_depan_stabilise_frames(d->ds, 1, &job, thread_stream());
+    VSFrame *dst = NULL;
+    if (!rc) {
+        dst = vs->newVideoFrame(&d->vi->format, d->vi->width, d->vi->height, src, core);
+        rc = download_plane_set(dst, ddst, d->pitch, np, bps, vs);
+    }
+    shell_quiesce(rc);
+    for (int k = 0; k < 3; k++) if (arena[k]) mvx_dev_free(arena[k]);
+    if (dstArena) mvx_dev_free(dstArena);
+    vs->freeFrame(src);
+    if (rc) { if (dst) vs->freeFrame(dst); depan_frame_error("DepanStabilise", rc, ctx, vs); return NULL; }
+    if (d->info) { /* :3554 */
+        char info[129];
+        snprintf(info, 128, "frame=%d %s=%d dx=%.2f dy=%.2f rot=%.3f zoom=%.5f", n, job.plan.base ? "BASE!" : "base ", job.plan.nbase, job.plan.motion[0], job.plan.motion[1],
+                 job.plan.motion[3], job.plan.motion[2]);
+        depan_set_info(dst, "DepanStabilise_info", info, vs);
+    }
+    return dst;
+}
+
+static void VS_CC depanStabCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
+    warm_barrier();
+    (void)user;
+    DepanStabData *d = (DepanStabData *)consumer_new(sizeof(*d), "DepanStabilise", depanStabGetFrameUngated, mvx_depan_stabilise_destroy_engine);
+    char lerr[MVX_ERRLEN] = "";
+    int e = 0;
+    mvx_depan_stabilise_args a;
+    a.cutoff = opt_float_unset(in, "cutoff", vs); a.damping = opt_float_unset(in, "damping", vs); a.initzoom = opt_float_unset(in, "initzoom", vs);
+    a.dxmax = opt_float_unset(in, "dxmax", vs); a.dymax = opt_float_unset(in, "dymax", vs); a.zoommax = opt_float_unset(in, "zoommax", vs); a.rotmax = opt_float_unset(in, "rotmax", vs);
+    a.pixaspect = opt_float_unset(in, "pixaspect", vs); a.tzoom = opt_float_unset(in, "tzoom", vs);
+    a.addzoom = opt_int(in, "addzoom", vs); a.prev = opt_int(in, "prev", vs); a.next = opt_int(in, "next", vs); a.mirror = opt_int(in, "mirror", vs); a.blur = opt_int(in, "blur", vs);
+    a.subpixel = opt_int(in, "subpixel", vs); a.fitlast = opt_int(in, "fitlast", vs); a.method = opt_int(in, "method", vs); a.fields = opt_int(in, "fields", vs);
+    d->info = !!vs->mapGetInt(in, "info", 0, &e);
+    d->node = consumer_node(&d->c, in, "clip", vs);
+    d->vi = vs->getVideoInfo(d->node);
+    d->data = consumer_node(&d->c, in, "data", vs);
+    mvx_depan_clip clip;
+    depan_clip_of(&clip, d->vi, NULL);
+    clip_pitches(d->pitch, d->vi, d->vi->format.bytesPerSample > 0 ? d->vi->format.bytesPerSample : 1);
+    if (mvx_depan_stabilise_create(&a, &clip, d->vi->numFrames, vs->getVideoInfo(d->data)->numFrames, d->vi->fpsNum, d->vi->fpsDen, d->pitch, d->pitch, &d->ds, lerr)) {
+        consumer_fail(&d->c, lerr, out, vs);
+        return;
+    }
+    d->c.engine = d->ds;
+    mvx_depan_stabilise_get_info(d->ds, &d->si);
+    VSFilterDependency deps[2] = { { d->node, rpGeneral }, { d->data, rpGeneral } };
+    vs->createVideoFilter(out, "DepanStabilise", d->vi, consumerGetFrame, consumerFree, fmParallel, deps, 2, d, core);
+    if (d->info && !vs->mapGetError(out)) depan_info_overlay("DepanStabilise", "DepanStabilise_info", out, core, vs);
+}
+
 /* ------------------------------------------------------------------------------------------------ entry point */
 
 #define DEGRAIN_TAIL "thsad:int:opt;thsadc:int:opt;plane:int:opt;limit:int:opt;limitc:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;"
@@ -2680,20 +3189,40 @@ VS_EXTERNAL_API(void) VapourSynthPluginInit2(VSPlugin *plugin, const VSPLUGINAPI
                              "clip:vnode;", compCreate, NULL, plugin);
     /* The per-sample filters are opt-in for now: MVX_VS_FLOW=1 in the host's environment when the plugin is loaded (read here, once).  Without it the
      * plugin registers exactly the functions above.   */
-    if (!env_long("MVX_VS_FLOW", 0)) return;
-    vspapi->registerFunction("FlowInter",
-                             "clip:vnode;super:vnode;mvbw:vnode;mvfw:vnode;time:float:opt;ml:float:opt;blend:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;",
-                             "clip:vnode;", flowCreate, NULL, plugin);
-    vspapi->registerFunction("FlowFPS",
-                             "clip:vnode;super:vnode;mvbw:vnode;mvfw:vnode;num:int:opt;den:int:opt;mask:int:opt;ml:float:opt;blend:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;",
-                             "clip:vnode;", flowCreate, (void *)(intptr_t)1, plugin);
-    vspapi->registerFunction("Flow",
-                             "clip:vnode;super:vnode;vectors:vnode;time:float:opt;mode:int:opt;fields:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;tff:int:opt;",
-                             "clip:vnode;", flowCompCreate, NULL, plugin);
-    vspapi->registerFunction("FlowBlur",
-                             "clip:vnode;super:vnode;mvbw:vnode;mvfw:vnode;blur:float:opt;prec:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;",
-                             "clip:vnode;", blurCreate, NULL, plugin);
-    vspapi->registerFunction("Mask",
-                             "clip:vnode;vectors:vnode;ml:float:opt;gamma:float:opt;kind:int:opt;time:float:opt;ysc:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;",
-                             "clip:vnode;", maskCreate, NULL, plugin);
+    if (env_long("MVX_VS_FLOW", 0)) {
+        vspapi->registerFunction("FlowInter",
+                                 "clip:vnode;super:vnode;mvbw:vnode;mvfw:vnode;time:float:opt;ml:float:opt;blend:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;",
+                                 "clip:vnode;", flowCreate, NULL, plugin);
+        vspapi->registerFunction("FlowFPS",
+                                 "clip:vnode;super:vnode;mvbw:vnode;mvfw:vnode;num:int:opt;den:int:opt;mask:int:opt;ml:float:opt;blend:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;",
+                                 "clip:vnode;", flowCreate, (void *)(intptr_t)1, plugin);
+        vspapi->registerFunction("Flow",
+                                 "clip:vnode;super:vnode;vectors:vnode;time:float:opt;mode:int:opt;fields:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;tff:int:opt;",
+                                 "clip:vnode;", flowCompCreate, NULL, plugin);
+        vspapi->registerFunction("FlowBlur",
+                                 "clip:vnode;super:vnode;mvbw:vnode;mvfw:vnode;blur:float:opt;prec:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;",
+                                 "clip:vnode;", blurCreate, NULL, plugin);
+        vspapi->registerFunction("Mask",
+                                 "clip:vnode;vectors:vnode;ml:float:opt;gamma:float:opt;kind:int:opt;time:float:opt;ysc:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;",
+                                 "clip:vnode;", maskCreate, NULL, plugin);
+    }
+    /* The Depan family is opt-in by a switch of its own, read the same way: MVX_VS_DEPAN=1.  (src/MVDepan.cpp:4211-4288) */
+    if (!env_long("MVX_VS_DEPAN", 0)) return;
+    vspapi->registerFunction("DepanAnalyse",
+                             "clip:vnode;vectors:vnode;mask:vnode:opt;zoom:int:opt;rot:int:opt;pixaspect:float:opt;error:float:opt;info:int:opt;wrong:float:opt;zerow:float:opt;"
+                             "thscd1:int:opt;thscd2:int:opt;fields:int:opt;tff:int:opt;",
+                             "clip:vnode;", depanAnalyseCreate, NULL, plugin);
+    vspapi->registerFunction("DepanEstimate",
+                             "clip:vnode;trust:float:opt;winx:int:opt;winy:int:opt;wleft:int:opt;wtop:int:opt;dxmax:int:opt;dymax:int:opt;zoommax:float:opt;stab:float:opt;"
+                             "pixaspect:float:opt;info:int:opt;show:int:opt;fields:int:opt;tff:int:opt;",
+                             "clip:vnode;", depanEstimateCreate, NULL, plugin);
+    vspapi->registerFunction("DepanCompensate",
+                             "clip:vnode;data:vnode;offset:float:opt;subpixel:int:opt;pixaspect:float:opt;matchfields:int:opt;mirror:int:opt;blur:int:opt;info:int:opt;fields:int:opt;"
+                             "tff:int:opt;",
+                             "clip:vnode;", depanCompCreate, NULL, plugin);
+    vspapi->registerFunction("DepanStabilise",
+                             "clip:vnode;data:vnode;cutoff:float:opt;damping:float:opt;initzoom:float:opt;addzoom:int:opt;prev:int:opt;next:int:opt;mirror:int:opt;blur:int:opt;"
+                             "dxmax:float:opt;dymax:float:opt;zoommax:float:opt;rotmax:float:opt;subpixel:int:opt;pixaspect:float:opt;fitlast:int:opt;tzoom:float:opt;info:int:opt;"
+                             "method:int:opt;fields:int:opt;",
+                             "clip:vnode;", depanStabCreate, NULL, plugin);
 }
