@@ -34,7 +34,9 @@ extern "C" {
 #define MVO_ERR 256
 
 /* wire types: MVAnalysisData.h:40-44, :83-134 */
-typedef struct mvo_vector { int x, y; int64_t sad; } mvo_vector;
+/* (a blob's vectors follow headers of ints: they lie at multiples of 4, not of 8.  The reference reads and writes them in place the same way,
+ * which x86 tolerates; here the struct declares it -- same 16 bytes, same offsets, alignment 4 -- so that the access is defined) */
+typedef struct __attribute__((packed, aligned(4))) mvo_vector { int x, y; int64_t sad; } mvo_vector;
 
 typedef struct mvo_analysis_data {
     int nMagicKey, nVersion, nBlkSizeX, nBlkSizeY, nPel, nLvCount, nDeltaFrame, isBackward, nCPUFlags,

@@ -62,7 +62,12 @@ SUPER_CASES = [
 
 @pytest.mark.parametrize("w,h,bits,sub,kw", SUPER_CASES)
 def test_super_parity(oracle, mv, w, h, bits, sub, kw):
-    frames = pl.moving_clip(w, h, bits, 2, seed=3, sub=sub)
+    _super_case(oracle, mv, w, h, bits, sub, kw)
+
+
+def _super_case(oracle, mv, w, h, bits, sub, kw, frames=None):
+    """frames: two frames of another clip than the default (tests/test_gpu_sample_range.py)"""
+    frames = frames or pl.moving_clip(w, h, bits, 2, seed=3, sub=sub)
     osup = oracle.Super(w, h, bits, subsampling=sub, **kw)
     gsup = mv.Super(w, h, bits, subsampling=sub, **kw)
     assert (gsup.info.super_width, gsup.info.super_height, gsup.info.levels) == (osup.s.superWidth, osup.s.superHeight, osup.s.levels)
@@ -126,7 +131,11 @@ def _behind(frame, p, offset, nbytes):
 def test_super_fused_shadow_planes(mv, w, h, bits, sub, kw):
     """mvx_super_frames_shadow (level-0 kernels write the shadow data themselves) against mvx_super_shadow_frames (derives it from
     the finished planes) on every shadow byte a search can read"""
-    frames = pl.moving_clip(w, h, bits, 2, seed=4, sub=sub)
+    _shadow_case(mv, w, h, bits, sub, kw)
+
+
+def _shadow_case(mv, w, h, bits, sub, kw, frames=None):
+    frames = frames or pl.moving_clip(w, h, bits, 2, seed=4, sub=sub)
     gsup = mv.Super(w, h, bits, subsampling=sub, **kw)
     if not gsup.shadow:
         pytest.skip("no shadow planes for this format")
@@ -248,11 +257,15 @@ ANALYSE_CASES = [
 
 @pytest.mark.parametrize("w,h,bits,skw,akw", ANALYSE_CASES)
 def test_analyse_parity(oracle, mv, w, h, bits, skw, akw):
+    _analyse_case(oracle, mv, w, h, bits, skw, akw)
+
+
+def _analyse_case(oracle, mv, w, h, bits, skw, akw, frames=None):
     import torch
     akw = dict(akw)
     noise = akw.pop("_noise", 3)
     ramp = akw.pop("_lumaramp", 0)
-    frames = pl.moving_clip(w, h, bits, 2, seed=11, noise=noise)
+    frames = frames or pl.moving_clip(w, h, bits, 2, seed=11, noise=noise)
     if ramp:  # brightness change between the two frames (8-bit scale), stronger to the right: the luma-gated SATD modes fire
         f1 = frames[1]
         y = f1[0].astype(np.int64) + (np.linspace(0, ramp, w)[None, :] * (1 << (bits - 8))).astype(np.int64)
@@ -288,10 +301,11 @@ def test_analyse_parity(oracle, mv, w, h, bits, skw, akw):
             pytest.fail("job %d blob differs: %s | %s" % (i, hdr, " ; ".join(msg[:4])))
 
 
-def _pipeline(oracle, mv, w, h, bits, radius, skw, akw, nframes=None, seed=21):
+def _pipeline(oracle, mv, w, h, bits, radius, skw, akw, nframes=None, seed=21, frames=None):
     import torch
     nframes = nframes or (2 * radius + 1)
-    frames = pl.moving_clip(w, h, bits, nframes, seed=seed, noise=3)
+    frames = frames or pl.moving_clip(w, h, bits, nframes, seed=seed, noise=3)
+    assert len(frames) == nframes
     osup = oracle.Super(w, h, bits, **skw)
     gsup = mv.Super(w, h, bits, **skw)
     osf = [osup.frame(f) for f in frames]
@@ -342,8 +356,12 @@ DEGRAIN_CASES = [
 
 @pytest.mark.parametrize("w,h,bits,radius,skw,akw,dkw", DEGRAIN_CASES)
 def test_degrain_parity(oracle, mv, w, h, bits, radius, skw, akw, dkw):
+    _degrain_case(oracle, mv, w, h, bits, radius, skw, akw, dkw)
+
+
+def _degrain_case(oracle, mv, w, h, bits, radius, skw, akw, dkw, frames=None):
     import torch
-    frames, osup, gsup, osf, gsrc, gsf = _pipeline(oracle, mv, w, h, bits, radius, skw, akw)
+    frames, osup, gsup, osf, gsrc, gsf = _pipeline(oracle, mv, w, h, bits, radius, skw, akw, frames=frames)
     n = len(frames)
     mid = radius  # output frame; also test the clip edge (frame 0: forward refs missing)
     for target in (mid, 0):
@@ -387,8 +405,12 @@ COMP_CASES = [
 
 @pytest.mark.parametrize("w,h,bits,skw,akw,ckw", COMP_CASES)
 def test_compensate_parity(oracle, mv, w, h, bits, skw, akw, ckw):
+    _compensate_case(oracle, mv, w, h, bits, skw, akw, ckw)
+
+
+def _compensate_case(oracle, mv, w, h, bits, skw, akw, ckw, frames=None):
     import torch
-    frames, osup, gsup, osf, gsrc, gsf = _pipeline(oracle, mv, w, h, bits, 1, skw, akw, nframes=2)
+    frames, osup, gsup, osf, gsrc, gsf = _pipeline(oracle, mv, w, h, bits, 1, skw, akw, nframes=2, frames=frames)
     oan = oracle.Analyse(osup, isb=1, **akw)
     gan = mv.Analyse(gsup, isb=1, **akw)
     for (src, ref) in ((0, 1), (1, None)):
@@ -486,6 +508,10 @@ def test_analyse_two_chains_per_simd(oracle, mv, dbg, kernel, bits, akw):
 ])
 @pytest.mark.parametrize("variant", ["general", "plain-layout", "serial", "spec-off", "spec-everywhere"])
 def test_analyse_default_search_other_kernels(oracle, mv, dbg, variant, w, h, bits, skw, akw):
+    _other_kernels_case(oracle, mv, dbg, variant, w, h, bits, skw, akw)
+
+
+def _other_kernels_case(oracle, mv, dbg, variant, w, h, bits, skw, akw, frames=None):
     """The default search normally runs in the speculative kernel (mvx_analyse_spec.h) on super frames that carry shadow copies.
     The same cases through the general kernel ("general" = 1), through the speculative kernel on the plain layout (no shadow
     copies: unaligned loads), through the serial lean kernel (mvx_analyse_fast.h, "spec" = 0) and through the speculative kernel's
@@ -501,7 +527,7 @@ def test_analyse_default_search_other_kernels(oracle, mv, dbg, variant, w, h, bi
         dbg("spec", 2)
     if variant == "spec-everywhere":
         dbg("spec", 5)
-    frames = pl.moving_clip(w, h, bits, 3, seed=13, noise=noise)
+    frames = frames or pl.moving_clip(w, h, bits, 3, seed=13, noise=noise)
     osup = oracle.Super(w, h, bits, **skw)
     gsup = mv.Super(w, h, bits, shadow=(variant != "plain-layout"), **skw)
     osf = [osup.frame(f) for f in frames]
@@ -620,7 +646,7 @@ def test_analyse_team_is_the_librarys_choice_for_small_launches(oracle, mv, dbg,
     assert info[4] == 3 and info[1] == 4, list(info)
 
 
-def _speculative_case(oracle, mv, dbg, mode, w, h, bits, skw, akw):
+def _speculative_case(oracle, mv, dbg, mode, w, h, bits, skw, akw, frames=None):
     """The speculative kernel of the default search (mvx_analyse_spec.h): groups of 32 blocks evaluated ahead of the serial walk under
     the hypothesis left == up (row passes over windows of seven blocks, strip or block form), verified block by block, everything else
     searched live.  Same blobs as the oracle -- forward, backward, with a field shift, with a missing reference; noisy clips (most
@@ -640,7 +666,7 @@ def _speculative_case(oracle, mv, dbg, mode, w, h, bits, skw, akw):
         dbg("team", 0)
     blk, ov = akw.get("blksize", 8), akw.get("overlap", 0)  # row passes: 16-bit 16x16 overlapping by half; 8-bit 8x8 overlapping by half or not at all
     rows_apply = (blk == 16 and ov in (8, 0)) or (akw.get("chroma", 1) != 0 and (bits, blk) == (8, 8) and ov in (4, 0))  # (16x16: luma-only searches too, r5)
-    frames = pl.moving_clip(w, h, bits, 3, seed=17, noise=noise, motion=(5, -2))
+    frames = frames or pl.moving_clip(w, h, bits, 3, seed=17, noise=noise, motion=(5, -2))
     osup = oracle.Super(w, h, bits, **skw)
     gsup = mv.Super(w, h, bits, **skw)
     osf = [osup.frame(f) for f in frames]
@@ -1000,11 +1026,15 @@ BLOCKFPS_CASES = [
 @pytest.mark.gpu
 @pytest.mark.parametrize("w,h,bits,akw,bkw", BLOCKFPS_CASES)
 def test_blockfps_parity(oracle, mv, w, h, bits, akw, bkw):
+    _blockfps_case(oracle, mv, w, h, bits, akw, bkw)
+
+
+def _blockfps_case(oracle, mv, w, h, bits, akw, bkw, frames=None):
     import torch
     nf = 6
     akw = dict(akw)
     delta = akw.pop("delta", 1)
-    frames, osup, gsup, osf, gsrc, gsf = _pipeline(oracle, mv, w, h, bits, 1, {}, akw, nframes=nf, seed=41)
+    frames, osup, gsup, osf, gsrc, gsf = _pipeline(oracle, mv, w, h, bits, 1, {}, akw, nframes=nf, seed=41, frames=frames)
     oabw = oracle.Analyse(osup, num_frames=nf, isb=1, delta=delta, **akw)
     oafw = oracle.Analyse(osup, num_frames=nf, isb=0, delta=delta, **akw)
     obbw = [oabw.frame(osf[n], osf[n + delta] if n + delta < nf else None) for n in range(nf)]
@@ -1085,9 +1115,13 @@ RECALC_CASES = [
 @pytest.mark.gpu
 @pytest.mark.parametrize("bits,akw,rkw", RECALC_CASES)
 def test_recalculate_parity(oracle, mv, bits, akw, rkw):
+    _recalculate_case(oracle, mv, bits, akw, rkw)
+
+
+def _recalculate_case(oracle, mv, bits, akw, rkw, frames=None):
     import torch
     w, h, nf = 192, 128, 3
-    frames, osup, gsup, osf, gsrc, gsf = _pipeline(oracle, mv, w, h, bits, 1, dict(pel=2), {}, nframes=nf, seed=53)
+    frames, osup, gsup, osf, gsrc, gsf = _pipeline(oracle, mv, w, h, bits, 1, dict(pel=2), {}, nframes=nf, seed=53, frames=frames)
     oan = oracle.Analyse(osup, num_frames=nf, isb=1, **akw)
     gan = mv.Analyse(gsup, num_frames=nf, isb=1, **akw)
     oold = [oan.frame(osf[n], osf[n + 1] if n + 1 < nf else None) for n in range(nf)]

@@ -17,7 +17,8 @@
 //     blocks are collected in four registers (v_writelane) and stored with one coalesced store.  Per block that removes
 //     three loads, two stores and ~25 address / exec-mask / readfirstlane instructions;
 //   * all per-block control state is scalar and small (no candidate generators, no pattern program counter), costs are
-//     32-bit (block SADs are < 2^27, the motion term saturates);
+//     32-bit (block SADs are < 2^27, so a cost's sum is < 2^29, and the motion term saturates; the product penalty * sad would
+//     pass 2^31 and is never formed in 32 bits: mvx_penalty_new, mvx_analyse_kernel.h);
 //   * the rescue is a loop over passes of eight candidates (eight lanes each) around one evaluation site.
 #pragma once
 // Tuning constants of the candidate evaluation.  Their alternatives (and the forms this file had before: group sums through the
@@ -348,8 +349,8 @@ template <int BPS, int BW, bool UV, int STREAM_MAX = MVX_STREAM_MAX> struct Fast
     }
     // cost of a refinement candidate: pobCheckMV (:219-261, penalty for new vectors); saturating -- a saturated cost never wins
     __device__ __forceinline__ int cost_new(int vx, int vy, unsigned aL, unsigned aC) const {
-        int cc = (int)aL + ((penaltyNew * (int)aL) >> 8);
-        if (chroma) cc += (int)aC + ((penaltyNew * (int)aC) >> 8);
+        int cc = (int)aL + mvx_penalty_new(penaltyNew, aL);
+        if (chroma) cc += (int)aC + mvx_penalty_new(penaltyNew, aC);
         return sat_add(motion_distortion(vx, vy), cc);
     }
 

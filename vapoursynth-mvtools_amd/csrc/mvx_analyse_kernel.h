@@ -27,6 +27,18 @@ enum { SearchOnetime, SearchNstep, SearchLogarithmic, SearchExhaustive, SearchHe
 #define MOTION_IS_BACKWARD 2
 #define MOTION_USE_CHROMA_MOTION 8
 
+// (pnew * sad) >> 8 of pobCheckMV (PlaneOfBlocks.cpp:238,247: a 64-bit product there) in 32 bits, exact for EVERY sad: with
+// sad = 256 q + r it is pnew * q + ((pnew * r) >> 8).  The plain 32-bit product is not enough: sad < 2^27 bounds the sum, but
+// pnew * sad passes 2^31 from sad = 2^31 / pnew on (pnew 50, the truemotion default: a 32x32 block at 16 bits whose samples
+// differ by 41 944 on average -- a fade; pnew 256: an eighth of the range) and the wrapped, negative penalty lets every new
+// candidate undercut the predictor.  pnew <= 256 (validated on the host) and sad < 2^27: both terms stay below 2^27, and every
+// factor fits 24 bits, so both products are the full-rate 24-bit multiply.  (A plain 32-bit multiply runs at a quarter of the rate:
+// with two of them the headline benchmark lost 1.8 % against the parent, with the 64-bit product 1.5 %, with this form 0.4 %, inside
+// the parent's run-to-run spread of 1.2 % -- profiles/penalty_product_fix.txt.)
+__device__ __forceinline__ static int mvx_penalty_new(int pnew, unsigned sad) {
+    return (int)(__umul24(sad >> 8, (unsigned)pnew) + (__umul24(sad & 255u, (unsigned)pnew) >> 8));
+}
+
 struct ALevel {
     int nBlkX, nBlkY;
     int pel, logPel;
@@ -950,8 +962,9 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
     // reference's square refinement runs around the unchanged centre against the unchanged nMinCost, which is exactly
     // what was evaluated; otherwise they are discarded and the square is redone around the moved centre.
     enum { FR_A, FR_HEX6, FR_SQUARE, FR_EXH2, FR_HEXSQ };
-    // block SADs bounded by 2^27 -> costs fit 32 bits once the (already int) motion distortion is added with saturation:
-    // a saturated cost can never beat nMinCost, which is at most the zero candidate's cost.
+    // block SADs bounded by 2^27 -> the SUM of a cost (sad + penalty, luma + chroma: < 2^29) fits 32 bits once the (already int) motion
+    // distortion is added with saturation: a saturated cost can never beat nMinCost, which is at most the zero candidate's cost.
+    // The PRODUCT penalty * sad inside it does not (up to 2^35): 64-bit for the predictors, mvx_penalty_new for new vectors.
     static constexpr bool COST32 = GEO::BW != 0 && GEO::BW * GEO::BH <= 1024;
 
     // the predictor set of pobPseudoEPZSearch (:832-915): zero, global, hierarchical predictor, median, left, up, ahead
@@ -1025,8 +1038,8 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
                 cc = tot + (int)(((long long)pen * tot) >> 8);
                 cc = sat_add(md, cc);
             } else {
-                cc = (int)aL + ((penaltyNew * (int)aL) >> 8);
-                if (chroma) cc += (int)aC + ((penaltyNew * (int)aC) >> 8);
+                cc = (int)aL + mvx_penalty_new(penaltyNew, aL);
+                if (chroma) cc += (int)aC + mvx_penalty_new(penaltyNew, aC);
                 cc = sat_add(motion_distortion(vx, vy), cc);
             }
             const int lim = nMinCost > 0x7fffffffLL ? 0x7fffffff : (int)nMinCost;

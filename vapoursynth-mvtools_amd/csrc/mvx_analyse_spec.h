@@ -550,8 +550,8 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                         auto a2_refine = [&](int wx, int wy, int &best, int &bx, int &by, int &bs) {
                             auto vok = [&](int vx, int vy) { return vx >= dxMin && vy >= nDyMin && vx <= dxMax1 && vy < nDyMax; };
                             auto cnew = [&](int vx, int vy, const v2u &t) { // pobCheckMV: penalty for new vectors, saturating
-                                int cc = (int)t[0] + ((penaltyNew * (int)t[0]) >> 8);
-                                if (chroma) cc += (int)t[1] + ((penaltyNew * (int)t[1]) >> 8);
+                                int cc = (int)t[0] + mvx_penalty_new(penaltyNew, t[0]);
+                                if (chroma) cc += (int)t[1] + mvx_penalty_new(penaltyNew, t[1]);
                                 return F::sat_add(md(vx, vy), cc);
                             };
                             bool won = false;
