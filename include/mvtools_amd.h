@@ -157,6 +157,11 @@ int mvx_analyse_set_ref_shadow(mvx_analyse *a, const ptrdiff_t copy_stride[3]);
  * geometry (MVAnalyse.c:229, :615-624), which is what readers of the vector clip must use. */
 int mvx_analyse_frames(mvx_analyse *a, int njobs, const mvx_analyse_job *jobs, void *stream);
 
+/* dct = 1..4 of mv.Analyse / mv.Recalculate (the reference's FFTW block-DCT cost, DCTFFTW.cpp, PlaneOfBlocks.cpp:117-163) run as a float32
+ * block DCT in HIP.  Opt-in for now: process-wide, off by default; while it is off both creates refuse these modes.
+ * Call it once, before creating the filters.  Returns MVX_OK.  (Blocks up to 32x32.) */
+int mvx_enable_dct_float(int on);
+
 /* ---- mv.Recalculate ------------------------------------------------------------------------------
  * replaces mvrecalculateCreate / mvrecalculateGetFrame, MVRecalculate.c:263-545 / :68-254 (arg string :549-572);
  * the per-block refinement is PlaneOfBlocks.cpp:1158-1424, `divide` GroupOfPlanes.c:177-302.           */
@@ -802,6 +807,10 @@ int mvx_debug_option(const char *name, int value);
  * 0 the serial lean kernel (or the general one), 2 the speculative kernel with one wave per chain, 3 its team form (the waves of a workgroup walk one
  * chain; the library's choice for launches that leave wave slots empty).  Tests use it to assert which build a batch took. */
 void mvx_debug_last_launch(int out[5]);
+/* test hook of the dct 1..4 modes: the device transform and quantiser alone.  `a` was created with dct 1..4; `plane` is a device luma plane, block i
+ * starts at sample xs[i] of row ys[i] (HOST arrays; the caller keeps the blocks inside the plane); out_bytes (device) receives blksize * blksizev
+ * quantised coefficients per block, row-major, in the sample type.  Synchronises the stream. */
+int mvx_analyse_dct_blocks(mvx_analyse *a, const void *plane, ptrdiff_t pitch, int n, const int32_t *xs, const int32_t *ys, void *out_bytes, void *stream);
 
 /* ---- small device-memory helpers so that a C host (e.g. the VapourSynth shell) needs no HIP headers */
 void *mvx_dev_alloc(size_t bytes);            /* zero-filled */

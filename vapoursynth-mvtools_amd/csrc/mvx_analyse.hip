@@ -7,6 +7,7 @@
 #include "mvx_analyse_kernel.h"
 #include "mvx_analyse_fast.h"
 #include "mvx_analyse_spec.h"
+#include "mvx_dct_host.h"
 int mvx_analyse_launch_spec_u8(const AParams &P, const ASpecLaunch &S);
 int mvx_analyse_launch_spec_u16(const AParams &P, const ASpecLaunch &S);
 
@@ -47,6 +48,24 @@ extern "C" __attribute__((visibility("default"))) void mvx_debug_last_launch(int
 }
 
 static int A(int v, int d) { return v == MVX_UNSET ? d : v; }
+
+// ---- dct 1..4 (the float block DCT, mvx_dct_block.h) are opt-in for now: process-wide, off by default.  Not a debug option: the library
+// never reads the environment, and a production host that wants these modes needs this call.
+static std::atomic<int> g_dctFloat{0};
+extern "C" __attribute__((visibility("default"))) int mvx_enable_dct_float(int on) {
+    g_dctFloat.store(on ? 1 : 0);
+    return MVX_OK;
+}
+static bool mvx_is_fdct(const AParams &P) { return P.dctmode >= 1 && P.dctmode <= 4; }
+// device copy of the basis tables, made on first use like the parameter block
+static int mvx_dct_upload(AParams &P, float **dTab) {
+    if (!mvx_is_fdct(P) || *dTab) return MVX_OK;
+    const std::vector<float> t = mvx_dct_tables(P.blkX, P.blkY);
+    HIP_CHECK(hipMalloc((void **)dTab, t.size() * sizeof(float)));
+    HIP_CHECK(hipMemcpy(*dTab, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+    P.dctTab = *dTab;
+    return MVX_OK;
+}
 
 // MVAnalyse.c:267-635 mvanalyseCreate
 // MVAnalyse.c:615-624 / MVRecalculate.c:533-543: the geometry readers see when divide > 0
@@ -140,7 +159,8 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_create(const m
     if (P.searchTypeCoarse < 0 || P.searchTypeCoarse > 7) MVX_FAIL("Analyse: search_coarse must be between 0 and 7 (inclusive).");
     if (P.dctmode < 0 || P.dctmode > 10) MVX_FAIL("Analyse: dct must be between 0 and 10 (inclusive).");
     if (P.dctmode >= 5 && ad.nBlkSizeX == 16 && ad.nBlkSizeY == 2) MVX_FAIL("Analyse: dct 5..10 cannot work with 16x2 blocks.");
-    if (P.dctmode >= 1 && P.dctmode <= 4) MVX_FAIL("Analyse: dct 1..4 (FFTW3 DCT cost) are not implemented on the GPU path.");
+    if (P.dctmode >= 1 && P.dctmode <= 4 && !g_dctFloat.load()) MVX_FAIL("Analyse: dct 1..4 (FFTW3 DCT cost) are not implemented on the GPU path.");
+    if (P.dctmode >= 1 && P.dctmode <= 4 && ad.nBlkSizeX * ad.nBlkSizeY > MVX_DCT_MAX_SAMPLES) MVX_FAIL("Analyse: dct 1..4 are implemented for blocks up to 32x32.");
     if (divide < 0 || divide > 2) MVX_FAIL("Analyse: divide must be between 0 and 2 (inclusive).");
     {
         static const int okb[12][2] = { { 4, 4 }, { 8, 4 }, { 8, 8 }, { 16, 2 }, { 16, 8 }, { 16, 16 }, { 32, 16 }, { 32, 32 }, { 64, 32 }, { 64, 64 }, { 128, 64 }, { 128, 128 } };
@@ -227,6 +247,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_create(const m
         L.blobOff = blobOff;
         blobOff += 4 + L.nBlkX * L.nBlkY * 16;
     }
+    P.dctShift = mvx_dct_shift(P.blkX, P.blkY);
     P.divide = divide;
     if (divide) blobOff += 4 + P.lv[0].nBlkX * P.lv[0].nBlkY * 16 * 4; // PlaneOfBlocks.cpp:1517-1526
     P.blobSize = blobOff;
@@ -243,6 +264,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_create(const m
 extern "C" __attribute__((visibility("default"))) void mvx_analyse_destroy(mvx_analyse *a) {
     if (!a) return;
     if (a->dP) (void)hipFree(a->dP);
+    if (a->dTab) (void)hipFree(a->dTab);
     for (auto &sl : a->slot) if (sl.d) (void)hipFree(sl.d);
     delete a;
 }
@@ -276,18 +298,44 @@ static int mvx_team_default(int njobs, int simds, bool strips, int bps) {
     return 0;
 }
 
+// the device copy of the parameter block (and, for dct 1..4, of the basis tables it points to), made on first use
+static int mvx_analyse_device_state(mvx_analyse *a) {
+    std::lock_guard<std::mutex> lk(a->guard.mu);
+    if (!a->dP) {
+        HIP_CHECK(hipGetDevice(&a->device));
+        if (int rc = mvx_dct_upload(a->P, &a->dTab)) return rc;
+        HIP_CHECK(hipMalloc((void **)&a->dP, sizeof(AParams)));
+        HIP_CHECK(hipMemcpy(a->dP, &a->P, sizeof(AParams), hipMemcpyHostToDevice));
+    }
+    return MVX_OK;
+}
+
+// test hook: the device transform and quantiser of the dct 1..4 modes on n blocks of a device luma plane (block i at sample xs[i], row ys[i];
+// xs / ys are HOST arrays); out_bytes (device) receives blkX * blkY coefficients per block in the sample type
+extern "C" __attribute__((visibility("default"))) int mvx_analyse_dct_blocks(mvx_analyse *a, const void *plane, ptrdiff_t pitch, int n, const int32_t *xs, const int32_t *ys,
+                                                                             void *out_bytes, void *stream) {
+    if (!mvx_is_fdct(a->P)) { mvx_set_error("mvx_analyse_dct_blocks: the handle was not created with dct 1..4"); return MVX_E_ARG; }
+    if (n <= 0) return MVX_OK;
+    if (int rc = mvx_analyse_device_state(a)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    int *dXY = nullptr;
+    HIP_CHECK(hipMalloc((void **)&dXY, sizeof(int) * 2 * (size_t)n));
+    int rc = MVX_OK;
+    if (hipMemcpyAsync(dXY, xs, sizeof(int) * n, hipMemcpyHostToDevice, st) != hipSuccess || hipMemcpyAsync(dXY + n, ys, sizeof(int) * n, hipMemcpyHostToDevice, st) != hipSuccess) {
+        mvx_set_error("mvx_analyse_dct_blocks: copying the block positions failed");
+        rc = MVX_E_DEVICE;
+    }
+    if (rc == MVX_OK) rc = mvx_dct_blocks_launch(a->P, plane, (long long)pitch, n, dXY, dXY + n, out_bytes, st);
+    if (hipStreamSynchronize(st) != hipSuccess && rc == MVX_OK) { mvx_set_error("mvx_analyse_dct_blocks: the kernel failed"); rc = MVX_E_DEVICE; }
+    (void)hipFree(dXY);
+    return rc;
+}
+
 extern "C" __attribute__((visibility("default"))) int mvx_analyse_frames(mvx_analyse *a, int njobs, const mvx_analyse_job *jobs, void *stream) {
     if (njobs <= 0) return MVX_OK;
     hipStream_t st = (hipStream_t)stream;
+    if (int rc0 = mvx_analyse_device_state(a)) return rc0;
     const AParams &P = a->P;
-    {
-        std::lock_guard<std::mutex> lk(a->guard.mu);
-        if (!a->dP) {
-            HIP_CHECK(hipGetDevice(&a->device));
-            HIP_CHECK(hipMalloc((void **)&a->dP, sizeof(AParams)));
-            HIP_CHECK(hipMemcpy(a->dP, &P, sizeof(AParams), hipMemcpyHostToDevice));
-        }
-    }
     mvx_analyse::JobSlot &S = a->slot[a->nextSlot.fetch_add(1) % mvx_analyse::kSlots];
     CallGuard::Scope scope(S.guard, st);
     if ((size_t)njobs > S.cap) {
@@ -448,6 +496,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_frames(mvx_ana
     // LDS of a chain: [source block | previous block row's results, 16 B per block | histogram of the global-motion estimate]
     const int ldsHist = ldsRow + maxBlkX * 16;
     int ldsBytes = ldsHist + histBins * 4;
+    if (mvx_is_fdct(P)) ldsBytes += mvx_dct_lds_bytes(P.blkX, P.blkY); // dct 1..4: [dctSrc | two float copies of a block | basis tables] behind the histogram
     if (ldsBytes > 160 * 1024) { mvx_set_error("mvx_analyse_frames: frame too wide for the LDS row buffer"); return MVX_E_ARG; }
     // One-chain-per-workgroup launches (generic kernels, MVX_CPW=1, window / tile modes): asking for a little more than a fifth of
     // the CU's 160 KiB of LDS makes the dispatcher spread the chains four per CU instead of stacking some CUs (+5 % at 1008 chains).
@@ -470,7 +519,8 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_frames(mvx_ana
     for (int i = 0; i < P.nLevels; i++)
         if ((long long)P.lv[i].pel * P.lv[i].pel * P.lv[i].pstride[0] >= 0xffffffffLL || (long long)P.lv[i].pel * P.lv[i].pel * P.lv[i].pstride[1] >= 0xffffffffLL) off32 = false;
     int rc = (P.dctmode != 0 || !off32) ? 1 : P.bps == 1 ? mvx_analyse_launch_u8(P, L) : mvx_analyse_launch_u16(P, L); // specialised 4:2:0 geometries (SAD cost only)
-    if (rc == 1) rc = mvx_analyse_launch_any(P, L);                                     // everything else
+    if (rc == 1 && mvx_is_fdct(P)) rc = mvx_analyse_launch_fdct(P, L);               // dct 1..4: their own generic build
+    else if (rc == 1) rc = mvx_analyse_launch_any(P, L);                                // everything else
     if (rc) return rc;
     return finish(0, cpw, syncEvery, 0);
 }
@@ -486,6 +536,7 @@ struct mvx_recalculate {
     RParams *dR = nullptr;
     AJob *dJobs = nullptr;
     size_t jobsCap = 0;
+    float *dTab = nullptr; // dct 1..4: basis tables
     CallGuard guard;
 };
 
@@ -519,7 +570,8 @@ extern "C" __attribute__((visibility("default"))) int mvx_recalculate_create(con
     if (P.searchType < 0 || P.searchType > 7) MVX_FAIL("Recalculate: search must be between 0 and 7 (inclusive).");
     if (P.dctmode < 0 || P.dctmode > 10) MVX_FAIL("Recalculate: dct must be between 0 and 10 (inclusive).");
     if (P.dctmode >= 5 && ad.nBlkSizeX == 16 && ad.nBlkSizeY == 2) MVX_FAIL("Recalculate: dct 5..10 cannot work with 16x2 blocks.");
-    if (P.dctmode >= 1 && P.dctmode <= 4) MVX_FAIL("Recalculate: dct 1..4 (FFTW3 DCT cost) are not implemented on the GPU path.");
+    if (P.dctmode >= 1 && P.dctmode <= 4 && !g_dctFloat.load()) MVX_FAIL("Recalculate: dct 1..4 (FFTW3 DCT cost) are not implemented on the GPU path.");
+    if (P.dctmode >= 1 && P.dctmode <= 4 && ad.nBlkSizeX * ad.nBlkSizeY > MVX_DCT_MAX_SAMPLES) MVX_FAIL("Recalculate: dct 1..4 are implemented for blocks up to 32x32.");
     if (divide < 0 || divide > 2) MVX_FAIL("Recalculate: divide must be between 0 and 2 (inclusive).");
     {
         static const int okb[12][2] = { { 4, 4 }, { 8, 4 }, { 8, 8 }, { 16, 2 }, { 16, 8 }, { 16, 16 }, { 32, 16 }, { 32, 32 }, { 64, 32 }, { 64, 64 }, { 128, 64 }, { 128, 128 } };
@@ -582,6 +634,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_recalculate_create(con
         }
         L.blobOff = 8;
     }
+    P.dctShift = mvx_dct_shift(P.blkX, P.blkY);
     P.divide = divide;
     P.blobSize = 8 + 4 + ad.nBlkX * ad.nBlkY * 16 + (divide ? 4 + ad.nBlkX * ad.nBlkY * 64 : 0);
     mvx_recalculate *h = new mvx_recalculate();
@@ -600,6 +653,7 @@ extern "C" __attribute__((visibility("default"))) void mvx_recalculate_destroy(m
     if (!r) return;
     if (r->dP) (void)hipFree(r->dP);
     if (r->dR) (void)hipFree(r->dR);
+    if (r->dTab) (void)hipFree(r->dTab);
     if (r->dJobs) (void)hipFree(r->dJobs);
     delete r;
 }
@@ -612,6 +666,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_recalculate_frames(mvx
     CallGuard::Scope scope(r->guard, st);
     const AParams &P = r->P;
     if (!r->dP) {
+        if (int rc0 = mvx_dct_upload(r->P, &r->dTab)) return rc0;
         HIP_CHECK(hipMalloc((void **)&r->dP, sizeof(AParams)));
         HIP_CHECK(hipMemcpy(r->dP, &P, sizeof(AParams), hipMemcpyHostToDevice));
         HIP_CHECK(hipMalloc((void **)&r->dR, sizeof(RParams)));
@@ -637,7 +692,8 @@ extern "C" __attribute__((visibility("default"))) int mvx_recalculate_frames(mvx
     if (P.chroma) srcBytes += 2 * (P.blkX / P.xr) * (P.blkY / P.yr) * P.bps;
     const int ldsRow = (srcBytes + 15) & ~15; // only the source block lives in LDS here
     RLaunch L = { njobs, P.lv[0].nBlkX * P.lv[0].nBlkY, ldsRow + 64, ldsRow, ldsRow, 0, st, r->dP, r->dR, r->dJobs };
-    int rc = mvx_recalc_launch(P, L);
+    if (mvx_is_fdct(P)) L.ldsBytes += mvx_dct_lds_bytes(P.blkX, P.blkY); // (behind the 64 bytes of slack: recalc_block)
+    int rc = mvx_is_fdct(P) ? mvx_recalc_launch_fdct(P, L) : mvx_recalc_launch(P, L);
     if (rc) return rc;
     if (P.divide) hipLaunchKernelGGL(analyse_divide_kernel, dim3((L.nBlk + 255) / 256, njobs), dim3(256), 0, st, r->dP, r->dJobs);
     HIP_CHECK(hipGetLastError());

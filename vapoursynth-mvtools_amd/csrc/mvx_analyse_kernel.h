@@ -21,6 +21,7 @@
 #pragma once
 #include <atomic>
 #include "mvx_common.h"
+#include "mvx_dct_block.h"
 
 enum { SearchOnetime, SearchNstep, SearchLogarithmic, SearchExhaustive, SearchHex2, SearchUMH, SearchHorizontal, SearchVertical };
 #define MOTION_USE_SIMD 1
@@ -63,6 +64,8 @@ struct AParams {
     int superHPad, superVPad;
     long long shadow[3]; // byte distance between the shifted copies of a reference plane (mvx_analyse_set_ref_shadow), 0 = none
     ALevel lv[MVX_MAX_LEVELS];
+    const float *dctTab; // dct 1..4: device copy of mvx_dct_tables(blkX, blkY) (mvx_dct_host.h), else null
+    int dctShift;        // dct 1..4: mvx_dct_shift(blkX, blkY)
 };
 
 struct AJob {
@@ -94,6 +97,7 @@ struct mvx_analyse {
     std::atomic<unsigned> nextSlot{0};
     int ldsBytes = 0;
     int device = 0;
+    float *dTab = nullptr; // dct 1..4: device copy of the basis tables (P.dctTab)
     CallGuard guard; // creation of dP, mvx_analyse_set_ref_shadow
 };
 
@@ -343,9 +347,15 @@ template <int BW_, int BH_, int XR_, int YR_, bool DCT_ = false> struct Geo {
 };
 typedef Geo<0, 0, 0, 0> GeoAny;
 typedef Geo<0, 0, 0, 0, true> GeoAnyDct;
+// dct 1..4 (the float block DCT of mvx_dct_block.h) get a generic build of their own, for the same reason; a type beside Geo<> so that
+// the kernels built from Geo<> keep their names.  DCT is true: the scan keeps the block-luma bookkeeping the SATD modes share with them.
+struct GeoAnyFdct { static constexpr int BW = 0, BH = 0, XR = 0, YR = 0; static constexpr bool DCT = true; };
+template <typename GEO> struct GeoIsFdct { static constexpr bool value = false; };
+template <> struct GeoIsFdct<GeoAnyFdct> { static constexpr bool value = true; };
 
 // WPE: chains per SIMD the enclosing kernel is built for (register budget; picks register-saving variants below)
 template <int BPS, typename GEO, int WPE = 1> struct Searcher {
+    static constexpr bool FDCT = GeoIsFdct<GEO>::value;
     const AParams &P;
     const AJob &J;
     lds_u8 *lds;          // [srcblock | rowbuf | hist]
@@ -835,6 +845,59 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
         return luma_cost(aL, sd, hit);
     }
 
+    // ---- dct 1..4: the float block DCT (mvx_dct_block.h), one block at a time by the whole wave.  LDS behind the chain's ordinary
+    // regions (ldsDct): [dctSrc | A | B | cxT | cy], mvx_dct_lds_*.
+    int ldsDct;
+    __device__ __forceinline__ void fdct_load_tables() const { // once per level / block kernel: the basis tables into LDS
+        MVX_DCT_LDS float *t = (MVX_DCT_LDS float *)(lds + ldsDct + mvx_dct_lds_cx(blkW, blkH));
+        const int n = blkW * blkW + blkH * blkH;
+        for (int i = lane_id(); i < n; i += WAVE) t[i] = P.dctTab[i];
+        mvx_dct_wave_sync();
+    }
+    __device__ __forceinline__ int fdct_log_bw() const { return 31 - __builtin_clz((unsigned)blkW); }
+    template <typename LOAD, typename SINK> __device__ __forceinline__ void fdct_block(LOAD load, SINK sink) const {
+        lds_u8 *base = lds + ldsDct;
+        mvx_dct_wave(lane_id(), blkW, fdct_log_bw(), blkH, P.bits, P.dctShift, load, (MVX_DCT_LDS float *)(base + mvx_dct_lds_a(blkW, blkH)),
+                     (MVX_DCT_LDS float *)(base + mvx_dct_lds_b(blkW, blkH)), (const MVX_DCT_LDS float *)(base + mvx_dct_lds_cx(blkW, blkH)),
+                     (const MVX_DCT_LDS float *)(base + mvx_dct_lds_cy(blkW, blkH)), sink);
+    }
+    // the staged source block's quantised DCT, once per block (PlaneOfBlocks.cpp:824-827, :1335-1338)
+    __device__ __forceinline__ void fdct_source() const {
+        LDS_AS unsigned short *dsrc = (LDS_AS unsigned short *)(lds + ldsDct);
+        const lds_u8 *src = lds; const int rowB = lumaRowB;
+        fdct_block([=](int y, int x) { return BPS == 1 ? (int)*(const LDS_AS unsigned char *)(src + y * rowB + x) : (int)*(const LDS_AS unsigned short *)(src + y * rowB + 2 * x); },
+                   [=](int t, int q) { dsrc[t] = (unsigned short)q; });
+    }
+    // The luma term of a round's candidates (group totals aL) under dct 1..4.  The candidates that need the reference block's DCT --
+    // mvx_dct_wanted -- are taken one after the other by the whole wave: G lanes cannot hold a transform, 64 can.
+    __device__ __forceinline__ unsigned fdct_apply(bool ok, int s, int logG, int vx, int vy, unsigned aL) const {
+        bool hit = false;
+        if (dctmode == 3 || dctmode == 4) {
+            unsigned rl = 0;
+            if (ok) rl = eval_luma_ref(s, logG, vx, vy);
+            rl = group_sum(rl, logG);
+            hit = mvx_dct_luma_hit(srcLuma, (int)rl);
+        }
+        const bool want = ok && mvx_dct_wanted(dctmode, dctweight16, hit);
+        unsigned long long todo = __ballot(want);
+        const int lane = lane_id();
+        const LDS_AS unsigned short *dsrc = (const LDS_AS unsigned short *)(lds + ldsDct);
+        unsigned myDct = 0; int myDc = 0;
+        while (todo) {
+            const int first = __ffsll((long long)todo) - 1; // first lane of the candidate's group
+            todo &= ~((logG == 6 ? ~0ULL : ((1ULL << (1 << logG)) - 1)) << first);
+            gl_u8 *ref = ref_luma(bcast_i(vx, first), bcast_i(vy, first));
+            const long long rp = pitchY;
+            int sum = 0, dc = 0;
+            fdct_block([=](int y, int x) { return BPS == 1 ? (int)*(GL_AS const unsigned char *)(ref + (long long)y * rp + x) : (int)*(GL_AS const uh1 *)(ref + (long long)y * rp + 2 * x); },
+                       [&](int t, int q) { const int d = abs((int)dsrc[t] - q); sum += d; if (t == 0) dc = d; });
+            const int tot = wave_sum_i32(sum);
+            const int dc0 = bcast_i(dc, 0); // coefficient 0 belongs to lane 0
+            if ((lane >> logG) == (first >> logG)) { myDct = (unsigned)tot; myDc = dc0; }
+        }
+        return (unsigned)mvx_dct_cost(dctmode, (long long)aL, myDct, myDc, blkW, hit, dctweight16);
+    }
+
     // partial SADs of this lane's share (items s, s+G, ...) of one candidate
     __device__ __forceinline__ void eval_cand(int s, int logG, int vx, int vy, int vyc, unsigned &aL, unsigned &aC) const {
         if (GEO::BW != 0) {
@@ -897,7 +960,8 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
             const long long pt1 = PROF_T();
             aL = group_sum(aL, logG);
             aC = group_sum(aC, logG);
-            if (GEO::DCT && dctmode != 0) aL = apply_dct(ok, s, logG, vx, vy, aL);
+            if constexpr (FDCT) aL = fdct_apply(ok, s, logG, vx, vy, aL);
+            else if (GEO::DCT && dctmode != 0) aL = apply_dct(ok, s, logG, vx, vy, aL);
             const long long pt2 = PROF_T();
             PROF_ADD(4, pt1 - pt0); PROF_ADD(5, pt2 - pt1); PROF_ADD(8, 1);
             const long long tot = (long long)aL + (chroma ? (long long)aC : 0);
@@ -1487,6 +1551,7 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
         penaltyNew = P.pnew; LSAD = P.lsad;
         dctmode = GEO::DCT ? P.dctmode : 0; sumLumaChange = 0; srcLuma = 0;
         dctweight16 = min(16, abs(*meanLumaChange) / (blkW * blkH)); // PlaneOfBlocks.cpp:981
+        if constexpr (FDCT) fdct_load_tables();
 
         LDS_AS Vec *rowbuf = (LDS_AS Vec *)(lds + ldsRow);
         const int stepX = P.blkX - P.ovX, stepY = P.blkY - P.ovY;
@@ -1626,7 +1691,8 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
             scale_lambda();
 
             __builtin_amdgcn_wave_barrier(); // single wave: DS ops are in order; keep the compiler from moving LDS reads above the staging writes
-            if (GEO::DCT && (dctmode == 7 || dctmode == 8 || dctmode == 10)) srcLuma = src_luma(); // :829-830 (only these modes read it)
+            if (GEO::DCT && (dctmode == 7 || dctmode == 8 || dctmode == 10 || (FDCT && dctmode >= 3))) srcLuma = src_luma(); // :829-830 (only these modes read it)
+            if constexpr (FDCT) fdct_source();
             const long long bt1 = PROF_T();
             // (the hints matter: the general state machine is an inner loop, which the register allocator would otherwise favour
             // over the straight-line path that actually runs; measured +2 % at 4K16)
@@ -1642,7 +1708,7 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
             const long long bt2 = PROF_T();
             __builtin_amdgcn_wave_barrier();
 
-            if (GEO::DCT && smallestPlane && (dctmode == 6 || dctmode == 9)) // :1109-1110 (feeds dctweight16 of the finer levels)
+            if (GEO::DCT && smallestPlane && (dctmode == 6 || dctmode == 9 || (FDCT && dctmode == 2))) // :1109-1110 (feeds dctweight16 of the finer levels)
                 sumLumaChange += uni(wave_sum_i32((int)eval_luma_ref(l, 6, 0, 0))) - src_luma();
             // results: vectors[blkIdx] (:967) == blob row (:1106); the row also stays in LDS for the next row's predictors
             if (l == 0) { st_vec(&vectors[blkIdx], bestMV); st_vec_lds(&rowbuf[blkx], bestMV); }
@@ -1746,6 +1812,7 @@ __global__ __launch_bounds__(64 * CPW, WPE) void analyse_kernel(const AParams *P
     Searcher<BPS, GEO, WPE> S(P, J);
     S.lds = (lds_u8 *)smem + (CPW == 1 ? 0 : uni((int)(threadIdx.x >> 6)) * ldsChain);
     S.ldsRow = ldsRow; S.ldsHist = ldsHist; S.histBins = histBins;
+    if constexpr (GeoIsFdct<GEO>::value) S.ldsDct = ldsHist + histBins * 4;
     S.blockSync = CPW > 1 ? syncEvery : 0;
 #ifdef MVX_PROFILE
     for (int i = 0; i < 16; i++) S.prof[i] = 0;
@@ -1782,85 +1849,16 @@ extern "C" __attribute__((visibility("default"))) int mvx_debug_prof(unsigned lo
 template <int BPS>
 __global__ __launch_bounds__(64, 1) void recalc_kernel(const AParams *Pp, const RParams *Rp, const AJob *jobs, int ldsRow, int ldsHist, int histBins) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const AParams &P = *Pp;
-    const RParams &R = *Rp;
-    const AJob &J = jobs[blockIdx.y];
-    typedef Searcher<BPS, GeoAnyDct> S_t;
-    S_t S(P, J);
-    S.lds = (lds_u8 *)smem; S.ldsRow = ldsRow; S.ldsHist = ldsHist; S.histBins = histBins;
-    S.blockSync = 0;
-    for (int i = 0; i < 16; i++) S.prof[i] = 0;
-    const int l = lane_id();
-    S.setup_geometry(0);
-    const int nBlk = S.nBlkX * S.nBlkY, b = blockIdx.x;
-    const int valid = J.valid && ((const int *)J.oldBlob)[1] == 1; // MVRecalculate.c:152 fgopIsValid && reference frame inside the clip
-    if (b == 0 && l == 0) { int *hdr = (int *)J.blob; hdr[0] = P.blobSize; hdr[1] = valid; }
-    if (!valid) { // gopWriteDefaultToArray
-        if (l == 0) { Vec d; d.x = 0; d.y = 0; d.sad = P.verybigSAD; S_t::st_vec(&S.vectors[b], d); }
-        return;
-    }
-    S.smallestPlane = 0;
-    S.blky = b / S.nBlkX; S.blkx = b - S.blky * S.nBlkX; S.blkIdx = b; S.blkScanDir = 1;
-    const int stepX = P.blkX - P.ovX, stepY = P.blkY - P.ovY;
-    S.x0 = S.hpad + stepX * S.blkx; S.y0 = S.vpad + stepY * S.blky;
-    S.cx0 = S.chpad + (stepX >> S.logxr) * S.blkx; S.cy0 = S.cvpad + (stepY >> S.logyr) * S.blky;
-    for (int t = l; t < S.TT; t += WAVE) { // source block -> LDS
-        int loff, cb;
-        gl_u8 *g = S.src_item_ptr(t, S.blkx, S.blky, stepX, stepY, loff, cb);
-        A4x32 a = ld_chunk_g(g, cb);
-        st_chunk_l(S.lds + loff, a, cb);
-    }
-    __builtin_amdgcn_wave_barrier();
-    S.searchType = P.searchType; S.nSearchParam = P.nSearchParam; S.tryMany = 0;
-    S.penaltyNew = P.pnew; S.penaltyZero = 0; S.pglobal = 0; S.badcount = 0; S.badrange = 0; S.badSAD = 0; S.LSAD = 0;
-    S.dctmode = P.dctmode; S.dctweight16 = 8; S.sumLumaChange = 0; S.srcLuma = 0; // :1167
-    S.zeroMVfieldShifted.x = 0; S.zeroMVfieldShifted.y = 0; S.zeroMVfieldShifted.sad = 0;
-    S.globalMVPredictor.x = 0; S.globalMVPredictor.y = 0; S.globalMVPredictor.sad = 9999999;
-    const int nLambdaLevel = P.lambda / (S.pel * S.pel);
-    S.nLambda = S.blky == 0 ? 0 : nLambdaLevel;
-    S.nDxMax = (S.pw - S.x0 - S.blkW) << S.logPel; // :1262-1265
-    S.nDyMax = (S.ph - S.y0 - S.blkH) << S.logPel;
-    S.nDxMin = -(S.x0 << S.logPel);
-    S.nDyMin = -(S.y0 << S.logPel);
-    // old vectors around the new block's centre (:1268-1321); plane headers walked like fgopUpdate
-    const unsigned char *po = J.oldBlob + 8;
-    for (int i = R.nLvCount - 1; i >= 1; i--) po += *(const int *)po;
-    GL_AS const GVec *ov = (GL_AS const GVec *)(po + 4);
-    const int centerX = P.blkX / 2 + stepX * S.blkx, blkxold = (centerX - R.blkX / 2) / R.stepX;
-    const int centerY = P.blkY / 2 + stepY * S.blky, blkyold = (centerY - R.blkY / 2) / R.stepY;
-    const int deltaX = max(0, centerX - (R.blkX / 2 + R.stepX * blkxold)), deltaY = max(0, centerY - (R.blkY / 2 + R.stepY * blkyold));
-    const int x1 = min(R.nBlkX - 1, max(0, blkxold)), x2 = min(R.nBlkX - 1, max(0, blkxold + 1));
-    const int y1 = min(R.nBlkY - 1, max(0, blkyold)), y2 = min(R.nBlkY - 1, max(0, blkyold + 1));
-    Vec vo;
-    if (R.smooth == 1) {
-        const Vec v1 = S_t::ld_vec(&ov[x1 + y1 * R.nBlkX]), v2 = S_t::ld_vec(&ov[x2 + y1 * R.nBlkX]), v3 = S_t::ld_vec(&ov[x1 + y2 * R.nBlkX]), v4 = S_t::ld_vec(&ov[x2 + y2 * R.nBlkX]);
-        const int ax = v1.x * R.stepX + deltaX * (v2.x - v1.x), ay = v1.y * R.stepX + deltaX * (v2.y - v1.y);
-        const long long as = v1.sad * R.stepX + deltaX * (v2.sad - v1.sad);
-        const int bx = v3.x * R.stepX + deltaX * (v4.x - v3.x), by = v3.y * R.stepX + deltaX * (v4.y - v3.y);
-        const long long bs = v3.sad * R.stepX + deltaX * (v4.sad - v3.sad);
-        vo.x = (ax + deltaY * (bx - ax) / R.stepY) / R.stepX;
-        vo.y = (ay + deltaY * (by - ay) / R.stepY) / R.stepX;
-        vo.sad = (as + deltaY * (bs - as) / R.stepY) / R.stepX;
-    } else {
-        const bool rx = deltaX * 2 >= R.stepX, ry = deltaY * 2 >= R.stepY;
-        vo = S_t::ld_vec(&ov[(rx ? x2 : x1) + (ry ? y2 : y1) * R.nBlkX]);
-    }
-    vo = uni(vo);
-    vo.x = (vo.x << S.logPel) >> R.logPel;
-    vo.y = (vo.y << S.logPel) >> R.logPel;
-    S.predictor = S.clip_mv(vo);
-    S.predictor.sad = vo.sad * (P.blkX * P.blkY) / (R.blkX * R.blkY);
-    S.bestMV = S.predictor;
-    if (S.dctmode == 7 || S.dctmode == 8 || S.dctmode == 10) S.srcLuma = S.src_luma();
-    unsigned aL = 0, aC = 0;
-    S.eval_cand(l, 6, S.predictor.x, S.predictor.y, S.predictor.y, aL, aC);
-    aL = group_sum(aL, 6); aC = group_sum(aC, 6);
-    if (S.dctmode != 0) aL = S.apply_dct(true, l, 6, S.predictor.x, S.predictor.y, aL);
-    const long long sad = uni((long long)aL + (S.chroma ? (long long)aC : 0));
-    S.bestMV.sad = sad;
-    S.nMinCost = sad;
-    if (sad > R.thSAD) S.search_block(2);
-    if (l == 0) S_t::st_vec(&S.vectors[b], S.bestMV);
+#define MVX_RECALC_GEO GeoAnyDct
+#include "mvx_analyse_recalc_body.h"
+#undef MVX_RECALC_GEO
+}
+template <int BPS> // dct 1..4 (mvx_analyse_fdct.hip)
+__global__ __launch_bounds__(64, 1) void recalc_fdct_kernel(const AParams *Pp, const RParams *Rp, const AJob *jobs, int ldsRow, int ldsHist, int histBins) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+#define MVX_RECALC_GEO GeoAnyFdct
+#include "mvx_analyse_recalc_body.h"
+#undef MVX_RECALC_GEO
 }
 
 struct RLaunch { int njobs, nBlk, ldsBytes, ldsRow, ldsHist, histBins; hipStream_t st; const AParams *dP; const RParams *dR; const AJob *dJobs; };
@@ -1894,3 +1892,7 @@ int mvx_analyse_launch_u8(const AParams &P, const ALaunch &L);
 int mvx_analyse_launch_u16(const AParams &P, const ALaunch &L);
 int mvx_analyse_launch_fast_u8(const AParams &P, const ALaunch &L);
 int mvx_analyse_launch_fast_u16(const AParams &P, const ALaunch &L);
+// dct 1..4 (mvx_analyse_fdct.hip)
+int mvx_analyse_launch_fdct(const AParams &P, const ALaunch &L);
+int mvx_recalc_launch_fdct(const AParams &P, const RLaunch &L);
+int mvx_dct_blocks_launch(const AParams &P, const void *plane, long long pitch, int n, const int *dXs, const int *dYs, void *out, hipStream_t st);

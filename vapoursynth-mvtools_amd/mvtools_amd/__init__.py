@@ -274,6 +274,8 @@ def lib():
         L.mvx_analyse_get_data.argtypes = [C.c_void_p, P(AnalysisData)]
         L.mvx_analyse_blob_size.argtypes = [C.c_void_p]
         L.mvx_analyse_frames.argtypes = [C.c_void_p, C.c_int, P(AnalyseJob), C.c_void_p]
+        L.mvx_enable_dct_float.argtypes = [C.c_int]
+        L.mvx_analyse_dct_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_ssize_t, C.c_int, P(C.c_int32), P(C.c_int32), C.c_void_p, C.c_void_p]
         L.mvx_degrain_create.argtypes = [P(DegrainArgs), P(AnalysisData), C.c_void_p, P(C.c_ssize_t), P(C.c_ssize_t), P(C.c_ssize_t),
                                          P(C.c_void_p), C.c_char_p]
         L.mvx_degrain_destroy.argtypes = [C.c_void_p]
@@ -367,6 +369,19 @@ def lib():
 def debug_option(name, value):
     """kernel-variant selection for tests / measurements (never changes results): see mvx_debug_option in mvtools_amd.h"""
     _check(lib().mvx_debug_option(name.encode(), int(value)))
+
+
+_dct_float = False
+
+
+def enable_dct_float(on=True):
+    """dct = 1..4 of Analyse / Recalculate (the float block DCT as luma cost) are opt-in for now: process-wide, off by default
+    (mvx_enable_dct_float in mvtools_amd.h).  Returns the previous setting."""
+    global _dct_float
+    was = _dct_float
+    _check(lib().mvx_enable_dct_float(1 if on else 0))
+    _dct_float = bool(on)
+    return was
 
 
 def _u(v):
@@ -641,6 +656,19 @@ class Analyse:
         stride = (self.blob_size + 255) // 256 * 256
         buf = torch.zeros((n, stride), dtype=torch.uint8, device=device)
         return [buf[i, :self.blob_size] for i in range(n)]
+
+    def dct_blocks(self, plane, xs, ys):
+        """test hook (dct 1..4): the device transform and quantiser on the blocks at sample xs[i], row ys[i] of a device luma plane (a uint8
+        [rows, pitch] tensor, as frame_to_device / Super.build give them) -> numpy [n, blksizev, blksize] in the sample type"""
+        torch = _torch()
+        bw, bh, n, item = self.ad.nBlkSizeX, self.ad.nBlkSizeY, len(xs), np.dtype(self.sup.dtype).itemsize
+        for x, y in zip(xs, ys):
+            if not (0 <= x and (x + bw) * item <= plane.shape[1] and 0 <= y and y + bh <= plane.shape[0]):
+                raise ValueError("dct_blocks: block (%d, %d) leaves the plane" % (x, y))
+        out = torch.zeros((max(n, 1), bh, bw * item), dtype=torch.uint8, device=plane.device)
+        ax, ay = (C.c_int32 * max(n, 1))(*xs), (C.c_int32 * max(n, 1))(*ys)
+        _check(lib().mvx_analyse_dct_blocks(self.h, plane.data_ptr(), plane.stride(0), n, ax, ay, out.data_ptr(), _stream()))
+        return out[:n].cpu().numpy().view(self.sup.dtype).reshape(n, bh, bw)
 
     def run(self, jobs, blobs=None, field_shift=0):
         """jobs: list of (src_super_frame, ref_super_frame_or_None) -> list of device blobs (MVTools_vectors)."""

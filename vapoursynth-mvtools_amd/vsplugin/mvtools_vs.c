@@ -26,7 +26,8 @@
  * instance on the instance's own stream -- the search is a serial chain per frame whose throughput comes from the number
  * of chains in flight.  The other filters make one C-ABI call per frame; all handles are thread-safe.
  *
- * Not supported (fail loudly at creation, like the C ABI): dct 1..4.
+ * dct 1..4 of Analyse / Recalculate (the float block DCT as luma cost) are opt-in: with MVX_VS_DCT=1 in the host's environment as the
+ * plugin is loaded the shell calls mvx_enable_dct_float(1) once; without it they fail loudly at creation, like the C ABI's default, and nothing here changes.
  */
 #include <errno.h>
 #include <pthread.h>
@@ -3187,6 +3188,8 @@ VS_EXTERNAL_API(void) VapourSynthPluginInit2(VSPlugin *plugin, const VSPLUGINAPI
     vspapi->registerFunction("Compensate",
                              "clip:vnode;super:vnode;vectors:vnode;scbehavior:int:opt;thsad:int:opt;fields:int:opt;time:float:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;tff:int:opt;",
                              "clip:vnode;", compCreate, NULL, plugin);
+    /* dct 1..4 are opt-in in the library (mvx_enable_dct_float): MVX_VS_DCT=1, read here, once, switches them on for this process.   */
+    if (env_long("MVX_VS_DCT", 0)) (void)mvx_enable_dct_float(1);
     /* The per-sample filters are opt-in for now: MVX_VS_FLOW=1 in the host's environment when the plugin is loaded (read here, once).  Without it the
      * plugin registers exactly the functions above.   */
     if (env_long("MVX_VS_FLOW", 0)) {
