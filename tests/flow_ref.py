@@ -143,9 +143,11 @@ def take(fin, rows, cols):
     return fin[rows, cols]
 
 
-def flow_inter(kind, t, fin_b, fin_f, off, pel, vb, vf, mb, mf, w, h, dtype, vbb=None, vff=None):
+def flow_inter(kind, t, fin_b, fin_f, off, pel, vb, vf, mb, mf, w, h, dtype, vbb=None, vff=None, probe=None):
     """kind 'simple' / 'regular' / 'extra': MaskFun.cpp:493-551 / :374-414 / :417-490 over one plane.  fin_b = the right Finest plane
-    (prefB), fin_f = the left one (prefF); off = (row, column) of the unpadded sample (0, 0) in them; v* = (VX, VY) full planes."""
+    (prefB), fin_f = the left one (prefF); off = (row, column) of the unpadded sample (0, 0) in them; v* = (VX, VY) full planes.
+    probe (a dict of lists) collects intermediates for the tests that show what a case reaches: the fetched samples "dF" / "dB", the
+    masks "MF" / "MB" and, for 'regular', the two inner products "inner" (int64: what a 32-bit kernel must hold without wrapping)."""
     lp = {1: 0, 2: 1, 4: 2}[pel]
     Y = (np.arange(h, dtype=np.int64) << lp)[:, None] + off[0]
     X = (np.arange(w, dtype=np.int64) << lp)[None, :] + off[1]
@@ -156,6 +158,9 @@ def flow_inter(kind, t, fin_b, fin_f, off, pel, vb, vf, mb, mf, w, h, dtype, vbb
         return take(fin, Y + ((cut(v[1]) * tt) >> 8), X + ((cut(v[0]) * tt) >> 8)).astype(np.int64)
 
     dF, dB = fetch(fin_f, vf, t), fetch(fin_b, vb, 256 - t)
+    if probe is not None:
+        for k, v in (("dF", dF), ("dB", dB), ("MF", MF), ("MB", MB)):
+            probe.setdefault(k, []).append(v)
     if kind == "simple":
         if t == 128:
             out = (((dF + dB) << 8) + (dB - dF) * (MF - MB)) >> 9
@@ -163,8 +168,11 @@ def flow_inter(kind, t, fin_b, fin_f, off, pel, vb, vf, mb, mf, w, h, dtype, vbb
             out = ((((dF * (255 - MF) + dB * MF + 255) >> 8) * (256 - t) + ((dB * (255 - MB) + dF * MB + 255) >> 8) * t) >> 8)
     elif kind == "regular":
         dF0, dB0 = take(fin_f, Y, X).astype(np.int64), take(fin_b, Y, X).astype(np.int64)
-        a = (dF * (255 - MF) + ((MF * (dB * (255 - MB) + MB * dF0) + 255) >> 8) + 255) >> 8
-        b = (dB * (255 - MB) + ((MB * (dF * (255 - MF) + MF * dB0) + 255) >> 8) + 255) >> 8
+        inner_a, inner_b = MF * (dB * (255 - MB) + MB * dF0) + 255, MB * (dF * (255 - MF) + MF * dB0) + 255
+        a = (dF * (255 - MF) + (inner_a >> 8) + 255) >> 8
+        b = (dB * (255 - MB) + (inner_b >> 8) + 255) >> 8
+        if probe is not None:
+            probe.setdefault("inner", []).extend([inner_a, inner_b])
         out = (a * (256 - t) + b * t) >> 8
     else:
         dFF, dBB = fetch(fin_f, vff, t), fetch(fin_b, vbb, 256 - t)
@@ -224,10 +232,10 @@ class Flow:
         b = np.ascontiguousarray(np.asarray(blob, np.uint8))
         return bool(_lib().mvo_blob_is_usable(C.byref(ad), C.c_void_p(b.ctypes.data), self.thscd1, self.thscd2))
 
-    def frame(self, n, clip, finest, blobs_bw, blobs_fw):
+    def frame(self, n, clip, finest, blobs_bw, blobs_fw, probe=None):
         """clip: input frames (lists of numpy planes); finest: Finest frames (mvoracle.Super.finest) per input frame, or a callable
         n -> Finest frame; blobs_*: per input frame blobs of the two vector clips.  Sets last_kind: "copy", "blend", "left", or the
-        formula "simple" / "regular" / "extra", with "128" appended at time256 128."""
+        formula "simple" / "regular" / "extra", with "128" appended at time256 128.  probe: see flow_inter."""
         nl, nr, t = self.map(n)
         last = self.in_frames - 1
         L, R = clip[min(nl, last)], clip[min(nr, last)]
@@ -277,5 +285,5 @@ class Flow:
 
             off = ((self.vpad // yr) * a.nPel, (self.hpad // xr) * a.nPel)     # nOffsetY / nOffsetUV, MVFlowInter.c:218-219
             out.append(flow_inter(kind, t, finR[p], finL[p], off, a.nPel, full(SB), full(SF), upsize_u8(MB, dw, dh), upsize_u8(MF, dw, dh),
-                                  lw, lh, dtype, full(SBB), full(SFF)))
+                                  lw, lh, dtype, full(SBB), full(SFF), probe))
         return out

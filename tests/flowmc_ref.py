@@ -96,10 +96,11 @@ def shift_loop(src, vx, vy, t, pel, bits):
     return np.array(dst, np.int64)
 
 
-def blur(fin, off, vb, vf, blur256, prec, pel, w, h, dtype, stats=None):
+def blur(fin, off, vb, vf, blur256, prec, pel, w, h, dtype, stats=None, probe=None):
     """MVFlowBlur.c:72-130 RealFlowBlur over one plane (fin = the Finest plane of frame n): per sample and for F then B, m = (max(|vx0|, |vy0|)
     / prec) >> 8 with v0 = V * blur256; if m > 0, v0 /= m (truncating) and m taps at ((i + 1) * v0) >> 8; the mean of the sample and the
-    taps.  stats counts samples with taps ("taps"), samples without ("notaps") and negative v0 with a remainder ("trunc")."""
+    taps.  stats counts samples with taps ("taps"), samples without ("notaps") and negative v0 with a remainder ("trunc").  probe (a dict)
+    keeps the largest sum of a sample and its taps ("max_sum") and the largest divisor ("max_count")."""
     Y, X, _ = _grid(h, w, pel, off)
     total = take(fin, Y, X).astype(np.int64)
     count = np.ones((h, w), np.int64)
@@ -122,6 +123,8 @@ def blur(fin, off, vb, vf, blur256, prec, pel, w, h, dtype, stats=None):
     if stats is not None:
         stats["taps"] = stats.get("taps", 0) + int(np.count_nonzero(count > 1))
         stats["notaps"] = stats.get("notaps", 0) + int(np.count_nonzero(count == 1))
+    if probe is not None:
+        probe["max_sum"], probe["max_count"] = max(probe.get("max_sum", 0), int(total.max())), max(probe.get("max_count", 0), int(count.max()))
     return (total // count).astype(dtype)                               # non-negative operands
 
 
@@ -202,8 +205,8 @@ class FlowBlur(_Base):
         self.prec = prec
         self.blur256 = int(np.float32(blur) * np.float32(256.0) / np.float32(200.0))
 
-    def frame(self, n, clip, finest, blobs_bw, blobs_fw, stats=None):
-        """blobs_*: per input frame blobs of the two vector clips.  Sets last_kind "copy" or "blur"."""
+    def frame(self, n, clip, finest, blobs_bw, blobs_fw, stats=None, probe=None):
+        """blobs_*: per input frame blobs of the two vector clips.  Sets last_kind "copy" or "blur".  probe: see blur."""
         d = self.delta
         self.last_kind = "copy"
         ok = n - d >= 0 and n + d < self.in_frames                                                  # :158-178
@@ -223,5 +226,5 @@ class FlowBlur(_Base):
                 if p:
                     sx, sy = half_uv(sx, xr), half_uv(sy, yr)                                      # :251-257
                 full.append((upsize_i16(sx, lw, lh, lw, lh, a.nPel, True), upsize_i16(sy, lw, lh, lw, lh, a.nPel, False)))
-            out.append(blur(fin[p], off, full[0], full[1], self.blur256, self.prec, a.nPel, lw, lh, clip[n][p].dtype, stats))
+            out.append(blur(fin[p], off, full[0], full[1], self.blur256, self.prec, a.nPel, lw, lh, clip[n][p].dtype, stats, probe))
         return out

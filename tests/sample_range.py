@@ -11,12 +11,16 @@ generators close that gap; each returns the same `frames[f][p]` layout as `movin
                  search still follows
   checker        3x3 cells of 0 and pm moving by (2, 1) per frame: the bicubic and Wiener taps overshoot on both sides of every edge
 
+The per-pixel Flow filters (FlowInter / FlowFPS, Flow, FlowBlur) have case lists of their own at the end of this file, on the same three
+clips, with the vectors the search finds and with crafted fields (tests/vector_fields.py).
+
 tests/test_sample_range.py proves through the oracle alone that each case reaches what it claims; tests/test_gpu_sample_range.py
 runs the cases on the GPU.  tests/sample_range_oracle_main.c repeats `step` and `checker` in C (same arithmetic, same LCG).
 """
 import numpy as np
 
 import pipeline as pl
+import vector_fields
 
 DEPTHS = (8, 10, 12, 14, 16)
 
@@ -228,3 +232,105 @@ BLOCKFPS_CASES = [("rails", 128, 96, (10, 16)[m & 1], dict(blksize=8, overlap=4)
     ("step", 128, 96, 16, dict(blksize=8, overlap=4), dict(num=60, den=1)),
     ("step", 128, 96, 16, dict(blksize=8, overlap=4), dict(num=60, den=1, blend=0)),
 ]
+
+# ---------------------------------------------------------------------------------------- FlowInter / FlowFPS, Flow, FlowBlur
+# (gen, fmt, w, h, bits, super kwargs, analyse kwargs, filter kwargs, recipe or None, kinds): the case shape of tests/test_gpu_flow.py and
+# tests/test_gpu_flowmc.py with the clip's generator in front, a vector_fields.Recipe where the vectors are crafted (None: the vectors the
+# search finds) and at the end what the restatement reports the output frames took.  Every case runs FLOW_NF input frames.
+#
+# Searched vectors on rails or checker never reach a formula at the default thresholds: the block SADs of a clip with a fifth of its samples
+# on each rail are above thscd1 = 400 in more than thscd2 = 130 of 256 blocks, the blobs count as scene changes and every job is Blend.  T
+# (both thresholds at their maxima) keeps them usable; the crafted fields carry SADs of 64 at most and need no T.
+FLOW_NF = 4
+FLOW_FORMATS = {"420": (1, 1), "444": (0, 0), "422": (1, 0), "gray": (1, 1)}
+T = dict(thscd1=16320, thscd2=255)
+_B84 = dict(blksize=8, overlap=4)
+_BW, _FW = dict(_B84, isb=1), dict(_B84, isb=0)
+
+
+def flow_clip(gen, fmt, w, h, bits, nframes=FLOW_NF):
+    """the clip of a Flow case: rails with moving_clip's noise of the Flow suites (3), step from end to end of the range (STEP_SPAN), checker;
+    luma only for gray"""
+    sub = FLOW_FORMATS[fmt]
+    if gen == "rails":
+        frames = rails(w, h, bits, nframes, sub=sub, noise=3)
+    elif gen == "step":
+        frames = step(w, h, bits, nframes, *STEP_SPAN[bits], sub=sub)
+    else:
+        frames = make(gen, w, h, bits, nframes, sub=sub)
+    return [[f[0]] for f in frames] if fmt == "gray" else frames
+
+
+def _flowinter_range_cases():
+    R = vector_fields.Recipe
+    out = []
+    for bits in (10, 12, 14, 16):          # searched vectors, T: the formulas on samples of 0 and pm with the masks the search's vectors give
+        for fkw, kinds in ((dict(fps=1, num=60, mask=2), "copy,extra,simple"), (dict(fps=1, num=48, mask=2), "copy,extra128,simple128"),
+                           (dict(fps=1, num=48, mask=0), "copy,simple128"), (dict(fps=1, num=60, mask=1), "copy,regular"),
+                           (dict(time=50.0), "blend,extra128,regular128"), (dict(time=33.0, ml=20.0), "blend,extra,regular")):
+            out.append(("rails", "420", 128, 96, bits, {}, _B84, dict(fkw, **T), None, kinds))
+    out += [
+        ("rails", "444", 128, 96, 10, {}, _B84, dict(fps=1, num=60, mask=2, **T), None, "copy,extra,simple"),
+        ("rails", "422", 160, 96, 12, {}, _B84, dict(time=50.0, **T), None, "blend,extra128,regular128"),
+        ("rails", "gray", 128, 96, 14, {}, _B84, dict(fps=1, num=48, mask=2, **T), None, "copy,extra128,simple128"),
+        ("rails", "420", 206, 118, 10, {}, _B84, dict(fps=1, num=60, mask=1, **T), None, "copy,regular"),     # nBlkXP > nBlkX and nBlkYP > nBlkY
+    ]
+    seed = 2000                            # crafted occlusion fields: saturated masks; at 16 bits the regular formula's 32-bit product on its bound
+    for fkw, kinds in ((dict(fps=1, num=48, mask=1), "copy,regular128"), (dict(fps=1, num=60, mask=1), "copy,regular")):
+        for gen in ("rails", "checker", "step"):
+            out.append((gen, "420", 128, 96, 16, {}, _B84, fkw, R("occlusion", seed), kinds))
+            seed += 20
+    for bits in (10, 12, 14):              # 255-masks on samples that are all 0 or pm, through Extra and Simple
+        out.append(("checker", "420", 128, 96, bits, {}, _B84, dict(fps=1, num=60, mask=2), R("occlusion", seed), "copy,extra,simple"))
+        out.append(("checker", "420", 128, 96, bits, {}, _B84, dict(fps=1, num=48, mask=0), R("occlusion", seed + 20), "copy,simple128"))
+        seed += 40
+    for bits in (10, 16):                  # the cut: Blend and the left frame between a frame near 0 and a frame near pm, default thresholds
+        out += [
+            ("step", "420", 128, 96, bits, {}, _B84, dict(fps=1, num=60, mask=2), None, "blend,copy"),
+            ("step", "420", 128, 96, bits, {}, _B84, dict(fps=1, num=60, mask=2, blend=0), None, "copy,left"),
+            ("step", "420", 128, 96, bits, {}, _B84, dict(time=33.0), None, "blend"),
+            ("step", "420", 128, 96, bits, {}, _B84, dict(time=33.0, blend=0), None, "left"),
+        ]
+    return out
+
+
+def _flow_range_cases():
+    R = vector_fields.Recipe
+    SH, FE = "collide,copy,hole,shift", "copy,fetch"
+    out, seed = [], 2300
+    for gen, bits in (("rails", 10), ("rails", 12), ("rails", 14), ("checker", 10)):   # crafted limits fields: the hole value of every depth
+        for akw, fkw, kinds in ((_BW, dict(time=100.0, mode=1), SH), (_FW, dict(time=100.0, mode=1), SH), (_BW, dict(time=37.5, mode=1), SH),
+                                (_FW, dict(time=37.5, mode=1), SH), (_BW, dict(time=100.0), FE)):
+            out.append((gen, "420", 128, 96, bits, {}, akw, fkw, R("limits", seed), kinds))
+            seed += 20
+    out += [
+        ("rails", "420", 128, 96, 16, {}, _BW, dict(time=100.0, mode=1), R("limits", seed), SH),
+        ("rails", "420", 128, 96, 16, {}, _FW, dict(time=100.0), R("limits", seed + 20), FE),
+        ("rails", "gray", 128, 96, 12, {}, _FW, dict(time=100.0, mode=1), R("limits", seed + 40), SH),
+        ("rails", "420", 128, 96, 10, {}, _BW, dict(time=100.0, mode=1, **T), None, SH),                       # the vectors the search finds
+        ("rails", "420", 128, 96, 14, {}, _FW, dict(time=100.0, mode=1, **T), None, SH),
+    ]
+    return out
+
+
+def _blur_range_cases():
+    R = vector_fields.Recipe
+    K = "blur,copy,taps,trunc"
+    out = [("rails", "420", 128, 96, bits, {}, _B84, dict(blur=200.0), R("limits", 2800 + 20 * i), K) for i, bits in enumerate((10, 12, 14, 16))]
+    out += [
+        ("rails", "420", 128, 96, 12, {}, _B84, dict(blur=200.0, prec=3), R("limits", 2880), "blur,copy,notaps,taps,trunc"),
+        ("step", "420", 128, 96, 16, {}, _B84, dict(blur=200.0), R("limits", 2900), K),                           # the largest tap sums there are
+        ("checker", "420", 128, 96, 16, {}, _B84, dict(blur=200.0), R("limits", 2920), K),
+        ("checker", "420", 128, 96, 10, {}, _B84, dict(blur=200.0), R("limits", 2940), K),
+    ]
+    return out
+
+
+FLOWINTER_RANGE_CASES = _flowinter_range_cases()
+FLOW_RANGE_CASES = _flow_range_cases()
+BLUR_RANGE_CASES = _blur_range_cases()
+
+
+def flow_case_id(c):
+    kw = ",".join("%s=%s" % kv for kv in c[7].items() if kv[0] not in T) + (",T" if "thscd1" in c[7] else "")
+    return "%s-%s-%dx%d-%dbit-%s%s-%s" % (c[0], c[1], c[2], c[3], c[4], "isb%d-" % c[6]["isb"] if "isb" in c[6] else "", kw, c[8] if c[8] is not None else "searched")

@@ -55,12 +55,15 @@ CASES = [
 ]
 
 
-def _run(mv, oracle, fmt, w, h, bits, skw, akw, fkw, nf, seed, outs=None, edit=None, ml_double=None):
+def _run(mv, oracle, fmt, w, h, bits, skw, akw, fkw, nf, seed, outs=None, edit=None, ml_double=None, frames=None):
+    """frames: the clip instead of moving_clip's (luma only for gray)"""
     import torch
     f = FORMATS[fmt]
-    frames = pl.moving_clip(w, h, bits, nf, seed=seed, noise=3, sub=f.get("subsampling", (1, 1)))
-    if f.get("gray"):
-        frames = [[fr[0]] for fr in frames]
+    if frames is None:
+        frames = pl.moving_clip(w, h, bits, nf, seed=seed, noise=3, sub=f.get("subsampling", (1, 1)))
+        if f.get("gray"):
+            frames = [[fr[0]] for fr in frames]
+    assert len(frames) == nf and len(frames[0]) == (1 if f.get("gray") else 3)
     kw = dict(f, **skw)
     osup, gsup = oracle.Super(w, h, bits, **kw), mv.Super(w, h, bits, **kw)
     gsrc = [mv.frame_to_device(fr) for fr in frames]

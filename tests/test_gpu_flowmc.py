@@ -77,11 +77,14 @@ BLUR_CASES = [
 ]
 
 
-def _clip(mv, oracle, fmt, w, h, bits, skw, nf, seed):
+def _clip(mv, oracle, fmt, w, h, bits, skw, nf, seed, frames=None):
+    """frames: the clip instead of moving_clip's (luma only for gray)"""
     f = FORMATS[fmt]
-    frames = pl.moving_clip(w, h, bits, nf, seed=seed, noise=3, sub=f.get("subsampling", (1, 1)))
-    if f.get("gray"):
-        frames = [[fr[0]] for fr in frames]
+    if frames is None:
+        frames = pl.moving_clip(w, h, bits, nf, seed=seed, noise=3, sub=f.get("subsampling", (1, 1)))
+        if f.get("gray"):
+            frames = [[fr[0]] for fr in frames]
+    assert len(frames) == nf and len(frames[0]) == (1 if f.get("gray") else 3)
     kw = dict(f, **skw)
     osup, gsup = oracle.Super(w, h, bits, **kw), mv.Super(w, h, bits, **kw)
     gsrc = [mv.frame_to_device(fr) for fr in frames]
@@ -106,9 +109,9 @@ def _compare(mv, out, want, k, n, kind):
         assert np.array_equal(got, want[p]), "frame %d plane %d (%s): %s" % (n, p, kind, pl.first_diff(got, want[p]))
 
 
-def _run_flow(mv, oracle, fmt, w, h, bits, skw, akw, fkw, nf, seed, outs=None, edit=None):
+def _run_flow(mv, oracle, fmt, w, h, bits, skw, akw, fkw, nf, seed, outs=None, edit=None, frames=None):
     import torch
-    frames, gsup, gsrc, gsf, fin = _clip(mv, oracle, fmt, w, h, bits, skw, nf, seed)
+    frames, gsup, gsrc, gsf, fin = _clip(mv, oracle, fmt, w, h, bits, skw, nf, seed, frames=frames)
     akw, fkw = dict(akw), dict(fkw)
     isb, delta, fs = akw.pop("isb"), akw.pop("delta", 1), fkw.pop("fs", 0)
     ga = mv.Analyse(gsup, num_frames=nf, isb=isb, delta=delta, **akw)
@@ -131,9 +134,9 @@ def _run_flow(mv, oracle, fmt, w, h, bits, skw, akw, fkw, nf, seed, outs=None, e
     return _kinds(kinds, stats)
 
 
-def _run_blur(mv, oracle, fmt, w, h, bits, skw, akw, fkw, nf, seed, outs=None, edit=None):
+def _run_blur(mv, oracle, fmt, w, h, bits, skw, akw, fkw, nf, seed, outs=None, edit=None, frames=None):
     import torch
-    frames, gsup, gsrc, gsf, fin = _clip(mv, oracle, fmt, w, h, bits, skw, nf, seed)
+    frames, gsup, gsrc, gsf, fin = _clip(mv, oracle, fmt, w, h, bits, skw, nf, seed, frames=frames)
     akw = dict(akw)
     delta = akw.pop("delta", 1)
     gabw = mv.Analyse(gsup, num_frames=nf, isb=1, delta=delta, **akw)

@@ -1,12 +1,17 @@
-"""The block pipeline at the ENDS of the sample range: the HIP path against the CPU oracle, bit-exact, on the clips of
-tests/sample_range.py (tests/test_sample_range.py shows on the CPU that each of them reaches what it is here for).  The runners are
-those of tests/test_gpu_parity.py, given other frames."""
+"""The block pipeline and the per-pixel Flow filters at the ENDS of the sample range: the HIP path against the CPU oracle (the Flow
+filters: against the restatements tests/flow_ref.py and tests/flowmc_ref.py), bit-exact, on the clips of tests/sample_range.py
+(tests/test_sample_range.py shows on the CPU that each of them reaches what it is here for).  The runners are those of
+tests/test_gpu_parity.py, tests/test_gpu_flow.py and tests/test_gpu_flowmc.py, given other frames."""
 import ctypes as C
+import itertools
 
 import pytest
 
 import sample_range as sr
+import test_gpu_flow as gflow
+import test_gpu_flowmc as gflowmc
 import test_gpu_parity as gp
+import vector_fields as vf
 from test_gpu_parity import dbg  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
@@ -130,3 +135,37 @@ def test_compensate_at_the_rails(oracle, mv, gen, w, h, bits, akw, ckw):
 @pytest.mark.parametrize("gen,w,h,bits,akw,bkw", sr.BLOCKFPS_CASES, ids=_id)
 def test_blockfps_at_the_rails(oracle, mv, gen, w, h, bits, akw, bkw):
     gp._blockfps_case(oracle, mv, w, h, bits, akw, bkw, frames=_consumer_clip(gen, w, h, bits, 6))
+
+
+# ---------------------------------------------------------------------------------------- FlowInter / FlowFPS, Flow, FlowBlur
+def _flow_case(runner, consumer, mv, oracle, case):
+    """one case of the Flow lists through a runner of tests/test_gpu_flow.py / tests/test_gpu_flowmc.py (byte equality of every plane of every
+    output frame is the runner's); the crafted fields are built as tests/test_gpu_vector_fields.py builds them: the i-th blob the runner
+    edits (the backward clip's first, then the forward clip's) gets index i"""
+    gen, fmt, w, h, bits, skw, akw, fkw, recipe, kinds = case
+    edit = None
+    if recipe is not None:
+        count, ed = itertools.count(), vf.case_editor(consumer, recipe, fkw)
+        edit = lambda blob, ad: ed(blob, ad, next(count))
+    got = runner(mv, oracle, fmt, w, h, bits, skw, akw, fkw, nf=sr.FLOW_NF, seed=0, edit=edit, frames=sr.flow_clip(gen, fmt, w, h, bits))
+    assert got == kinds, "the case did not take what it is listed for"
+
+
+@pytest.mark.parametrize("case", sr.FLOWINTER_RANGE_CASES, ids=sr.flow_case_id)
+def test_flowinter_flowfps_at_the_rails(oracle, mv, case):
+    """Simple, regular and Extra (at time256 128 and elsewhere), Blend and the left frame on samples of 0 and pm at 10, 12, 14 and 16 bits;
+    at 16 bits on saturated masks the regular formula's 32-bit product MF * (dB * (255 - MB) + MB * dF0) + 255 on its bound, 0.992 * 2^32"""
+    _flow_case(gflow._run, "flowinter", mv, oracle, case)
+
+
+@pytest.mark.parametrize("case", sr.FLOW_RANGE_CASES, ids=sr.flow_case_id)
+def test_flow_at_the_rails(oracle, mv, case):
+    """fetch and shift; the holes of a shift are painted with the DEPTH's maximum, (1 << bits) - 1, which 10, 12 and 14 bits tell apart
+    from the two-byte container's 65535"""
+    _flow_case(gflowmc._run_flow, "flow", mv, oracle, case)
+
+
+@pytest.mark.parametrize("case", sr.BLUR_RANGE_CASES, ids=sr.flow_case_id)
+def test_flowblur_at_the_rails(oracle, mv, case):
+    """sums of up to 511 samples of 0 and pm divided by their count; at 16 bits sums above 2^24"""
+    _flow_case(gflowmc._run_blur, "flowblur", mv, oracle, case)

@@ -2,6 +2,7 @@
 
 A GPU case that never clamps, never saturates a limit or never brings the penalty product past 2^31 proves nothing about those
 paths however bit-exact it is; these are the conditions (not measurements) that make tests/test_gpu_sample_range.py worth its time."""
+import functools
 import os
 import subprocess
 
@@ -238,6 +239,232 @@ def test_blockfps_occlusion_mask_is_mixed(oracle):
     masks = [ob.frame(n, frames, osf, obbw, obfw)[0] >> (bits - 8) for n in range(ob.num_frames) if ob.map(n)[2] not in (0, 256)]
     m = np.concatenate([x.ravel() for x in masks])
     assert (m > 0).any() and (m < 255).any() and len(np.unique(m)) > 2, np.unique(m)[:8]
+
+
+# ---------------------------------------------------------------------------------------- FlowInter / FlowFPS, Flow, FlowBlur
+# The runners below do on the CPU what those of tests/test_gpu_flow.py and tests/test_gpu_flowmc.py do on the GPU: the oracle's Super and
+# Analyse (which the GPU's are pinned to, byte for byte) feed the restatements, the crafted fields are built through the same
+# vector_fields.case_editor with the same blob indices.  What they report is therefore what the GPU case compares.
+FORMATS = {"420": dict(subsampling=(1, 1)), "444": dict(subsampling=(0, 0)), "422": dict(subsampling=(1, 0)), "gray": dict(gray=True)}
+
+
+def _flow_pipeline(oracle, gen, fmt, w, h, bits, skw, akw, isbs):
+    """(frames, super, Finest frames by number, [analysis data, blobs per input frame] per direction); the cases that share it follow one another"""
+    return _flow_pipeline_of(gen, fmt, w, h, bits, tuple(sorted(skw.items())), tuple(sorted(akw.items())), isbs)
+
+
+@functools.lru_cache(maxsize=8)
+def _flow_pipeline_of(gen, fmt, w, h, bits, skw, akw, isbs):
+    import mvoracle as oracle
+    nf = sr.FLOW_NF
+    frames = sr.flow_clip(gen, fmt, w, h, bits)
+    osup = oracle.Super(w, h, bits, **dict(FORMATS[fmt], **dict(skw)))
+    osf = [osup.frame(f) for f in frames]
+    fin = [osup.finest(f) for f in osf]
+    akw = dict(akw)
+    delta = akw.pop("delta", 1)
+    vecs = []
+    for isb in isbs:
+        an = oracle.Analyse(osup, num_frames=nf, isb=isb, delta=delta, **akw)
+        refs = [n + delta if isb else n - delta for n in range(nf)]
+        vecs.append((an.ad, [an.frame(osf[n], osf[r] if 0 <= r < nf else None) for n, r in enumerate(refs)]))
+    return frames, osup, fin, vecs
+
+
+def _edited(consumer, recipe, fkw, vecs):
+    """the blobs after the case's editor, numbered as the GPU runners number them: the backward clip's first, then the forward clip's"""
+    if recipe is None:
+        return [b for _, b in vecs]
+    import vector_fields as vf
+    edit, out, i = vf.case_editor(consumer, recipe, fkw), [], 0
+    for ad, blobs in vecs:
+        out.append([edit(b, ad, i + k) for k, b in enumerate(blobs)])
+        i += len(blobs)
+    return out
+
+
+def _cpu_flowinter(oracle, case, probe=None, **override):
+    import flow_ref
+    gen, fmt, w, h, bits, skw, akw, fkw, recipe, _ = case
+    fkw = dict(fkw, **override)
+    frames, osup, fin, vecs = _flow_pipeline(oracle, gen, fmt, w, h, bits, skw, akw, (1, 0))
+    bbw, bfw = _edited("flowinter", recipe, fkw, vecs)
+    fkw = dict(fkw)
+    fps = (24, 1) if fkw.pop("fps", None) else None
+    ref = flow_ref.Flow(vecs[0][0], vecs[1][0], sr.FLOW_NF, osup.nplanes, osup.s.hpad, osup.s.vpad, fps=fps, **fkw)
+    kinds, outs = set(), []
+    for n in range(ref.num_frames):
+        outs.append(ref.frame(n, frames, fin, bbw, bfw, probe))
+        kinds.add(ref.last_kind)
+    return ",".join(sorted(kinds)), frames, outs
+
+
+def _cpu_flow(oracle, case, bits_of_the_hole=None):
+    import flowmc_ref
+    gen, fmt, w, h, bits, skw, akw, fkw, recipe, _ = case
+    akw = dict(akw)
+    isb = akw.pop("isb")
+    frames, osup, fin, vecs = _flow_pipeline(oracle, gen, fmt, w, h, bits, skw, akw, (isb,))
+    blobs, = _edited("flow", recipe, fkw, vecs)
+    ref = flowmc_ref.Flow(vecs[0][0], sr.FLOW_NF, osup.nplanes, osup.s.hpad, osup.s.vpad, bits_of_the_hole or bits, **fkw)
+    kinds, stats, outs = set(), {}, []
+    for n in range(sr.FLOW_NF):
+        outs.append(ref.frame(n, frames, lambda k: fin[k], blobs[n], 0, stats))
+        kinds.add(ref.last_kind)
+    return ",".join(sorted(kinds | {k for k, v in stats.items() if v > 0})), stats, outs
+
+
+def _cpu_blur(oracle, case):
+    import flowmc_ref
+    gen, fmt, w, h, bits, skw, akw, fkw, recipe, _ = case
+    frames, osup, fin, vecs = _flow_pipeline(oracle, gen, fmt, w, h, bits, skw, akw, (1, 0))
+    bbw, bfw = _edited("flowblur", recipe, fkw, vecs)
+    ref = flowmc_ref.FlowBlur(vecs[0][0], vecs[1][0], sr.FLOW_NF, osup.nplanes, osup.s.hpad, osup.s.vpad, bits, **fkw)
+    kinds, stats, probe = set(), {}, {}
+    for n in range(sr.FLOW_NF):
+        ref.frame(n, frames, lambda k: fin[k], bbw, bfw, stats, probe)
+        kinds.add(ref.last_kind)
+    return ",".join(sorted(kinds | {k for k, v in stats.items() if v > 0})), stats, probe
+
+
+def _cases(cases, cond=lambda c: True):
+    return [pytest.param(c, id=sr.flow_case_id(c)) for c in cases if cond(c)]
+
+
+def test_flow_range_lists_are_well_formed():
+    """new recipe seeds start at 2000 and lie 20 apart (a case edits 2 * FLOW_NF blobs with seed + index); the geometry is the issue's"""
+    import vector_fields as vf
+    cases = sr.FLOWINTER_RANGE_CASES + sr.FLOW_RANGE_CASES + sr.BLUR_RANGE_CASES
+    seeds = sorted(c[8].seed for c in cases if c[8] is not None)
+    assert seeds[0] >= 2000 and all(b - a >= 20 for a, b in zip(seeds, seeds[1:])) and 2 * sr.FLOW_NF <= 20
+    old = [k[-1].seed for lst in (vf.DEGRAIN_CASES, vf.COMPENSATE_CASES, vf.BLOCKFPS_CASES, vf.RECALC_CASES, vf.FLOWINTER_CASES, vf.FLOW_CASES, vf.BLUR_CASES,
+                                  [vf.FULL_DEGRAIN, vf.FULL_FLOWFPS]) for k in lst]
+    assert max(old) + 20 <= seeds[0]
+    for c in cases:
+        assert c[4] in (10, 12, 14, 16) and c[5] == {} and c[6]["blksize"] == 8 and c[6]["overlap"] == 4 and (c[8] is None or isinstance(c[8], vf.Recipe))
+        assert c[8] is None or "thscd1" not in c[7], "the crafted fields are usable at the default thresholds"
+    assert len(set(sr.flow_case_id(c) for c in cases)) == len(cases)
+
+
+def test_flow_range_cases_cover_every_formula_below_16_bits():
+    """together, at 10, 12 and 14 bits alone, the cases reach each formula and fallback of FlowInter / FlowFPS, Flow's fetch and shift with
+    colliding sources and holes, and FlowBlur's taps with truncating divisions (tests/test_gpu_flow.py and tests/test_gpu_flowmc.py hold the
+    same sets over their 8 and 16-bit cases)"""
+    seen = lambda cases: set(k for c in cases if c[4] in (10, 12, 14) for k in c[-1].split(","))
+    assert seen(sr.FLOWINTER_RANGE_CASES) == {"simple", "simple128", "regular", "regular128", "extra", "extra128", "blend", "left", "copy"}
+    assert seen(sr.FLOW_RANGE_CASES) == {"copy", "fetch", "shift", "collide", "hole"}
+    assert seen(sr.BLUR_RANGE_CASES) == {"copy", "blur", "taps", "trunc", "notaps"}   # (notaps: the prec=3 case only)
+    for bits in (10, 12, 14):   # every depth on its own reaches the hole value and a formula of each family
+        assert {"hole", "fetch"} <= set(k for c in sr.FLOW_RANGE_CASES if c[4] == bits for k in c[-1].split(","))
+        assert {"simple", "regular", "extra"} <= set(k for c in sr.FLOWINTER_RANGE_CASES if c[4] == bits for k in c[-1].split(","))
+
+
+@pytest.mark.parametrize("case", _cases(sr.FLOWINTER_RANGE_CASES, lambda c: c[0] != "step" or c[8] is not None))
+def test_flowinter_range_cases_reach_their_kinds(oracle, case):
+    """the pinned kinds, from the restatement; searched vectors (T): a twentieth at least of the fetched dF and of the fetched dB are 0 and
+    a twentieth are pm; crafted occlusion fields: both masks reach 255, and on the checker most fetched samples are 0 or pm"""
+    gen, bits, recipe = case[0], case[4], case[8]
+    pm = (1 << bits) - 1
+    probe = {}
+    kinds, _, _ = _cpu_flowinter(oracle, case, probe)
+    assert kinds == case[-1]
+    dF, dB = (np.concatenate([a.ravel() for a in probe[k]]) for k in ("dF", "dB"))
+    MF, MB = (np.concatenate([a.ravel() for a in probe[k]]) for k in ("MF", "MB"))
+    if recipe is None:
+        for d in (dF, dB):
+            assert (d == 0).mean() >= 0.05 and (d == pm).mean() >= 0.05, ((d == 0).mean(), (d == pm).mean())
+        if case[7].get("ml") == 20.0:
+            assert MF.max() == 255 and MB.max() == 255, "ml 20 is there to let the search's own vectors saturate the masks"
+    else:
+        assert MF.max() == 255 and MB.max() == 255 and (MF == 255).mean() > 0.02 and (MB == 255).mean() > 0.02
+        assert ((MF > 0) & (MF < 255)).any() and (MF == 0).any()
+        if gen == "checker":
+            assert ((dF == 0) | (dF == pm)).mean() > 0.5 and ((dB == 0) | (dB == pm)).mean() > 0.5   # (the sub-pel planes hold values between)
+        for d in (dF, dB):   # a mask of 255 on a sample of 0 and on a sample of pm, both ways round
+            for m in (MF, MB):
+                assert ((m == 255) & (d == 0)).any() and ((m == 255) & (d >= pm - (pm + 1) // 32)).any()
+
+
+def test_searched_vectors_on_rails_need_the_thresholds_raised(oracle):
+    """the trap: at the default thscd1 / thscd2 the search's vectors on rails are scene changes, every job is Blend (or FlowFPS's copy) and a
+    GPU case would compare the fallback alone"""
+    for case in (sr.FLOWINTER_RANGE_CASES[0], [c for c in sr.FLOWINTER_RANGE_CASES if c[0] == "rails" and c[4] == 16 and "time" in c[7]][0]):
+        assert case[8] is None and case[7]["thscd1"] == 16320 and case[7]["thscd2"] == 255
+        kinds, _, _ = _cpu_flowinter(oracle, case, thscd1=400, thscd2=130)
+        assert set(kinds.split(",")) <= {"blend", "copy"} and "blend" in kinds, kinds
+        assert set(case[-1].split(",")) & {"extra", "extra128", "simple", "regular"}
+
+
+OCC16 = [c for c in sr.FLOWINTER_RANGE_CASES if c[4] == 16 and c[8] is not None and c[7] == dict(fps=1, num=48, mask=1)]
+BOUND = 65535 * 255 * 255 + 255   # MF * (dB * (255 - MB) + MB * dF0) + 255 at MF = 255 and samples of 65535: 0.992 * 2^32
+
+
+@pytest.mark.parametrize("case", _cases(OCC16))
+def test_regular_product_reaches_its_bound_at_16_bits(oracle, case):
+    """MaskFun.cpp:374-414 forms MF * (dB * (255 - MB) + MB * dF0) + 255 in 64 bits, the kernel in 32 unsigned: a tenth of the products
+    at least lie at or above 2^31 (where a signed 32-bit product would wrap) and the largest IS the bound, 4 261 413 630 < 2^32"""
+    probe = {}
+    kinds, _, _ = _cpu_flowinter(oracle, case, probe)
+    assert kinds == "copy,regular128"
+    inner = np.concatenate([a.ravel() for a in probe["inner"]])
+    assert inner.dtype == np.int64 and inner.min() >= 255
+    assert (inner >= 1 << 31).mean() >= 0.1, (inner >= 1 << 31).mean()
+    assert int(inner.max()) == BOUND == 4261413630 and BOUND < 1 << 32
+
+
+def test_regular_product_control_at_14_bits(oracle):
+    """the same field on the same clip at 14 bits: the largest product is 16383 * 255 * 255 + 255, below 2^31 -- only 16 bits reach the bound"""
+    assert len(OCC16) == 3 and sorted(c[0] for c in OCC16) == ["checker", "rails", "step"]
+    case = [c for c in OCC16 if c[0] == "rails"][0]
+    probe = {}
+    _cpu_flowinter(oracle, case[:4] + (14,) + case[5:], probe)
+    assert max(int(a.max()) for a in probe["inner"]) == 16383 * 255 * 255 + 255 < 1 << 31
+
+
+@pytest.mark.parametrize("case", _cases(sr.FLOWINTER_RANGE_CASES, lambda c: c[0] == "step" and c[8] is None))
+def test_the_cut_is_blended_or_left(oracle, case):
+    """between a frame near 0 and a frame near pm every job falls back: Blend (FlowFPS: and the copies), or the left frame with blend=0"""
+    pm = (1 << case[4]) - 1
+    kinds, frames, outs = _cpu_flowinter(oracle, case)
+    assert kinds == case[-1] and set(kinds.split(",")) - {"copy"} == ({"blend"} if case[7].get("blend", 1) else {"left"})
+    for n, fr in enumerate(frames):
+        for p in fr:
+            assert (p.mean() > 15 * pm / 16) if n & 1 else (p.mean() < pm / 16), (n, p.mean())
+    if case[7].get("blend", 1):   # a blend of the two levels: an output frame far from both
+        assert any(pm / 8 < o[0].mean() < 7 * pm / 8 for o in outs)
+
+
+@pytest.mark.parametrize("case", _cases(sr.FLOW_RANGE_CASES))
+def test_flow_range_cases_reach_their_kinds(oracle, case):
+    """the pinned kinds; shift at time 100 on the crafted fields below 16 bits: a tenth at least of the destinations are holes and a tenth
+    are not, sources collide, and the same run with the hole value of 16 bits gives other planes (so a kernel that painted 65535, or took
+    the depth from the two-byte container, fails the GPU case); fetch: the output holds 0 and pm"""
+    bits, fkw, recipe = case[4], case[7], case[8]
+    pm = (1 << bits) - 1
+    kinds, stats, outs = _cpu_flow(oracle, case)
+    assert kinds == case[-1]
+    if fkw.get("mode"):
+        total = (sr.FLOW_NF - 1) * sum(p.size for p in outs[0])   # all frames but one have a reference (the last with isb=1, the first with isb=0)
+        assert stats["hole"] > 0 and stats["collide"] > 0
+        if recipe is not None and fkw["time"] == 100.0:
+            assert 0.1 * total <= stats["hole"] <= 0.9 * total, (stats, total)
+        if bits < 16:
+            _, _, wide = _cpu_flow(oracle, case, bits_of_the_hole=16)
+            assert any(not np.array_equal(a, b) for o, v in zip(outs, wide) for a, b in zip(o, v))
+            assert all(int(p.max()) <= pm for o in outs for p in o) and any(int(p.max()) == 65535 for v in wide for p in v)
+    else:
+        assert min(int(p.min()) for o in outs for p in o) == 0 and max(int(p.max()) for o in outs for p in o) == pm
+
+
+@pytest.mark.parametrize("case", _cases(sr.BLUR_RANGE_CASES))
+def test_blur_range_cases_reach_their_kinds(oracle, case):
+    """the pinned kinds, taps and truncating divisions; at 16 bits the largest sum of a sample and its taps is above 2^24 (hundreds of taps
+    of 65535: no float32 accumulator holds it exactly)"""
+    kinds, stats, probe = _cpu_blur(oracle, case)
+    assert kinds == case[-1] and stats["taps"] > 0 and stats["trunc"] > 0
+    if case[4] == 16 and case[7].get("prec", 1) == 1:
+        assert probe["max_sum"] > 1 << 24 and probe["max_count"] > 256, probe
+    assert probe["max_sum"] <= probe["max_count"] * ((1 << case[4]) - 1) < 1 << 31
 
 
 # ------------------------------------------------------------------------------------------- the oracle under sanitizers

@@ -34,6 +34,7 @@
 #include <string.h>
 #include <sys/mman.h>
 #include <time.h>
+#include <unistd.h>
 
 #include "vs4_api.h"
 
@@ -87,6 +88,18 @@ static int64_t VS_CC mapGetInt(const VSMap *m, const char *k, int i, int *err) {
 static int VS_CC mapGetIntSaturated(const VSMap *m, const char *k, int i, int *err) {
     int64_t v = mapGetInt(m, k, i, err);
     return v > 2147483647LL ? 2147483647 : v < -2147483647LL - 1 ? -2147483647 - 1 : (int)v;
+}
+/* Every way out of the process goes through leave().  The plugin brings the HIP runtime up on a thread of its own (mvtools_vs.c, warmup_thread), and exit()
+ * under a thread that is inside the runtime's initialisation is, now and then, a segmentation fault after the complete output.  The plugin's filter-creation
+ * functions wait for the runtime, and from then on its own exit handler covers exit().  For a run that reaches none of them: `list` and `error` turn the
+ * warm-up off before the plugin is loaded (host_main: they have nothing to overlap it with; an `error` whose function is not registered creates nothing); a
+ * `run` that fails before its first filter (a missing or short input file, a bad pipeline) flushes and ends without exit handlers */
+static int g_created; /* a creation function of the plugin has returned */
+static void leave(int rc) {
+    const char *warm = getenv("MVX_VS_WARMUP");
+    if (g_created || (warm && atol(warm) == 0)) exit(rc); /* no thread of the plugin's can be inside the runtime's initialisation */
+    fflush(NULL);
+    _exit(rc);
 }
 static int VS_CC mapSetInt(VSMap *m, const char *k, int64_t v, int append) { put(m, k, ptInt, append)->i = v; return 0; }
 static double VS_CC mapGetFloat(const VSMap *m, const char *k, int i, int *err) { const Item *it = get(m, k, i, ptFloat, err); return it ? it->f : 0; }
@@ -343,6 +356,7 @@ static VSNode *invoke(const char *name, VSMap *in, char *err, size_t errsz) {
             }
             VSMap *out = createMap();
             g_funcs[i].fn(in, out, g_funcs[i].user, NULL, &g_api);
+            g_created = 1;
             VSNode *n = NULL;
             if (mapGetError(out)) snprintf(err, errsz, "%s", mapGetError(out));
             else { int e = 0; n = mapGetNode(out, "clip", 0, &e); if (e) snprintf(err, errsz, "%s: no clip returned", name); }
@@ -434,14 +448,14 @@ static VSNode *source_clip(const char *path, int w, int h, int bits, int nframes
     n->vi.fpsNum = 24; n->vi.fpsDen = 1; n->vi.width = w; n->vi.height = h; n->vi.numFrames = nframes;
     n->cache = (const VSFrame **)calloc((size_t)nframes, sizeof(VSFrame *));
     FILE *fp = path ? fopen(path, "rb") : NULL;
-    if (path && !fp) { fprintf(stderr, "cannot open %s\n", path); exit(2); }
+    if (path && !fp) { fprintf(stderr, "cannot open %s\n", path); leave(2); }
     for (int f = 0; f < nframes; f++) {
         VSFrame *fr = newVideoFrame(&n->vi.format, w, h, NULL, NULL);
         for (int p = 0; p < n->vi.format.numPlanes; p++)
             for (int y = 0; y < plane_h(fr, p); y++) {
                 uint8_t *row = fr->data[p] + (size_t)y * fr->stride[p];
                 const size_t rb = (size_t)plane_w(fr, p) * n->vi.format.bytesPerSample;
-                if (fp) { if (fread(row, 1, rb, fp) != rb) { fprintf(stderr, "short read\n"); exit(2); } }
+                if (fp) { if (fread(row, 1, rb, fp) != rb) { fprintf(stderr, "short read\n"); leave(2); } }
                 else memset(row, 0, rb);
             }
         if (g_field_order >= 0) mapSetInt(fr->props, "_Field", g_field_order ^ (f % 2), maReplace);
@@ -480,7 +494,7 @@ static void dump_frame(FILE *fp, const VSFrame *f) {
     for (int p = 0; p < f->fmt.numPlanes; p++)
         for (int y = 0; y < plane_h(f, p); y++) fwrite(f->data[p] + (size_t)y * f->stride[p], 1, (size_t)plane_w(f, p) * f->fmt.bytesPerSample, fp);
 }
-static void die(const char *what, const char *err) { printf("ERROR %s: %s\n", what, err); exit(1); }
+static void die(const char *what, const char *err) { printf("ERROR %s: %s\n", what, err); leave(1); }
 static int has_arg(int argc, char **argv, const char *arg) { for (int i = 0; i < argc; i++) if (!strcmp(argv[i], arg)) return 1; return 0; }
 static VSNode *invoke(const char *name, VSMap *in, char *err, size_t errsz);
 /* DepanEstimate(clip, e.*): the data clip that needs neither mv.Super nor mv.Analyse */
@@ -531,13 +545,14 @@ static void prefetch_parallel(int threads, int count, VSNode **nodes, int nnodes
 static double now_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
 static double g_start;
 
-int main(int argc, char **argv) {
+static int host_main(int argc, char **argv) {
     if (argc < 3) { fprintf(stderr, "usage: see minihost.c\n"); return 2; }
     g_start = now_s();
     init_api();
     /* host-side setting: the plugin hands its search launches to a pool of 12 streams, and the HIP runtime maps streams onto
      * GPU_MAX_HW_QUEUES hardware queues (read once, when the runtime initialises).  The host owns its environment, so it is set here */
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
+    if (strcmp(argv[2], "run")) setenv("MVX_VS_WARMUP", "0", 1); /* (see leave) */
     void *h = dlopen(argv[1], RTLD_NOW | RTLD_GLOBAL);
     if (!h) { fprintf(stderr, "dlopen: %s\n", dlerror()); return 2; }
     VSInitPlugin init = (VSInitPlugin)dlsym(h, "VapourSynthPluginInit2");
@@ -846,3 +861,5 @@ int main(int argc, char **argv) {
     printf("DONE\n");
     return 0;
 }
+
+int main(int argc, char **argv) { leave(host_main(argc, argv)); return 0; }

@@ -808,7 +808,9 @@ static void VS_CC superFree(void *inst, VSCore *core, const VSAPI *vs) {
  * plugin is loaded, while the host is still reading its script / opening its clips.  Two rules keep that safe: (1) every filter-creation function first waits until the RUNTIME
  * is up (what a synchronous start would have cost it anyway) -- so a host that exits after a creation error never tears the process down under a thread that is inside the
  * runtime's initialisation (the runtime's own exit handlers run before any handler registered earlier: measured, a segmentation fault at exit with the error message still in the
- * stdio buffer); (2) once the runtime is up the thread registers an exit handler -- which therefore runs BEFORE the runtime's -- that waits for the rest of the warm-up.
+ * stdio buffer); (2) as soon as the runtime is up, and BEFORE it lets the waiting creation functions go on, the thread registers an exit handler -- which therefore runs before the
+ * runtime's -- that waits for the rest of the warm-up.  What the rules do not cover is a host that calls exit() without having called a creation function and without freeing its
+ * core (freeing it unloads the plugin, whose destructor joins the thread): such a host sets MVX_VS_WARMUP=0, as the mini host does for `list` and `error` (minihost.c, leave).
  * MVX_VS_WARMUP=0 turns the thread off, MVX_VS_WARM_STAGES = staging buffers to page-lock (default 48 = 768 MiB: what a 4K session allocates within its first second). */
 static pthread_t g_warm_thread;
 static int g_warm_started, g_warm_runtime_up, g_warm_done; /* (atomics: __atomic_*) */
@@ -818,8 +820,8 @@ static void warm_join(void) {
 static void *warmup_thread(void *arg) {
     (void)arg;
     (void)mvx_warmup(-1);         /* the runtime (no device: the filters report that when they are used) */
+    atexit(warm_join);            /* (registered after the runtime's own handlers, so it runs before them; and before a creation function may go on and exit) */
     __atomic_store_n(&g_warm_runtime_up, 1, __ATOMIC_RELEASE);
-    atexit(warm_join);            /* (registered after the runtime's own handlers, so it runs before them) */
     const char *e = getenv("MVX_VS_WARM_STAGES");
     (void)mvx_warmup(e ? atoi(e) : 48); /* code objects, staging buffers */
     __atomic_store_n(&g_warm_done, 1, __ATOMIC_RELEASE);
