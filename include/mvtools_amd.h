@@ -222,6 +222,50 @@ typedef struct mvx_degrain_job {
 
 int mvx_degrain_frames(mvx_degrain *d, int nframes, const mvx_degrain_job *jobs, void *stream);
 
+/* ---- mv.DegrainN: temporal radius 1..24 ------------------------------------------------------------
+ * No reference counterpart by name: the reference registers Degrain1..6 only, but its arithmetic is a template over the radius
+ * (Degrain_C<radius> MVDegrains.h:30-53, useBlock :192-206, DegrainWeight :184-189, normaliseWeights<radius> :208-223), and this is that
+ * template read at any radius, with the frame loop of mvdegrainGetFrame (MVDegrains.cpp:85-330).  Reference r (order mvbw, mvfw, mvbw2,
+ * mvfw2, ...) has temporal distance d = r / 2 + 1 and is weighed against the threshold of ITS distance: thsad at d = 1, thsad2 at
+ * d = radius, t_d = floor(thsad2 + (thsad - thsad2) * (1 + cos(pi * (d - 1) / (radius - 1))) / 2 + 0.5) in between (MDegrainN's thSAD2;
+ * radius 1 or thsad2 == thsad: thsad everywhere), each then scaled like thsad (MVDegrains.cpp:658-661).  With thsad2 / thsadc2 unset and
+ * radius <= 6 the output bytes are those of mvx_degrain_frames.  Messages are mvx_degrain_create's with the name DegrainN, in the same order. */
+
+#define MVX_DEGRAIN_N_MAX_RADIUS 24
+
+typedef struct mvx_degrain_n_args {
+    int32_t radius;           /* 1..MVX_DEGRAIN_N_MAX_RADIUS */
+    int64_t thsad, thsadc;    /* MVX_UNSET -> 400 / thsad, as Degrain */
+    int64_t thsad2, thsadc2;  /* threshold at distance `radius`; MVX_UNSET -> thsad / thsadc (no fall-off) */
+    int32_t plane, limit, limitc;
+    int64_t thscd1; int32_t thscd2;
+} mvx_degrain_n_args;
+
+typedef struct mvx_degrain_n_info { /* what creation resolved */
+    int32_t radius, nrefs;
+    int64_t thsad_d[MVX_DEGRAIN_N_MAX_RADIUS], thsadc_d[MVX_DEGRAIN_N_MAX_RADIUS]; /* per distance 1..radius, AFTER the block-size scaling */
+} mvx_degrain_n_info;
+
+typedef struct mvx_degrain_n mvx_degrain_n;
+
+/* touches no device */
+int mvx_degrain_n_create(const mvx_degrain_n_args *args, const mvx_analysis_data *vectors_data /* of mvbw */,
+                         const mvx_super *super_clip, const ptrdiff_t src_pitch[3], const ptrdiff_t super_pitch[3],
+                         const ptrdiff_t dst_pitch[3], mvx_degrain_n **out, char *err);
+void mvx_degrain_n_get_info(const mvx_degrain_n *d, mvx_degrain_n_info *info);
+void mvx_degrain_n_destroy(mvx_degrain_n *d);
+
+typedef struct mvx_degrain_n_job {
+    const void *src[3];              /* clip frame n */
+    const void *const (*refs)[3];    /* HOST array of 2 * radius entries: super frame n+1 (mvbw), n-1 (mvfw), n+2, n-2, ...;
+                                        refs[r][0] NULL = that frame is outside the clip */
+    const void *const *blobs;        /* HOST array of 2 * radius device pointers: MVTools_vectors of vector clip r at frame n */
+    void *dst[3];
+} mvx_degrain_n_job;
+
+/* the host arrays behind refs and blobs are read before the call returns */
+int mvx_degrain_n_frames(mvx_degrain_n *d, int nframes, const mvx_degrain_n_job *jobs, void *stream);
+
 /* ---- mv.Compensate -------------------------------------------------------------------------------
  * replaces mvcompensateCreate / mvcompensateGetFrame, MVCompensate.c:419-575 / :73-374 (arg string :579-592) */
 

@@ -1,0 +1,420 @@
+// mvx_degrain_n.hip -- mv.DegrainN on gfx950: the block filter of mvx_degrain.hip at a temporal radius of 1..24 (2..48 references), each
+// reference weighed against the threshold of its own temporal distance.
+//
+// The reference's arithmetic is a template over the radius -- Degrain_C<radius> (MVDegrains.h:30-53), useBlock (:192-206), DegrainWeight
+// (:184-189), normaliseWeights<radius> (:208-223) -- and only its six registerFunction calls stop at 6.  This file is that template read at
+// any radius, inside the frame loop of mvdegrainGetFrame (MVDegrains.cpp:85-330) with overlaps_c / ToPixels (Overlap.cpp:143-158,335-356) in
+// the gather form of mvx_degrain.hip: one thread per row of a cell of W samples, which visits the <= 4 blocks covering the cell.
+//
+// What differs from mvx_degrain.hip is that nothing is sized by the reference count at compile time:
+//   plan    per (frame, plane class, block) a LIST of the references whose weight is not 0 -- a 16-byte head (WSrc, count) and then
+//           count entries (byte offset of the compensated block in the reference's super plane, normalised weight, reference index) in a
+//           slot of fixed stride.  A reference with weight 0 adds nothing to WSum or to a sum (MVDegrains.h:40-48,212-221), so leaving it
+//           out changes no result; far references are mostly such, and only the entries that exist are written and read.
+//   gather  takes a block's list in chunks of DN_K entries: DN_K rows requested, then multiply-added into sum[W]; window and
+//           normalisation once per block after the last chunk.  The reference planes' base pointers (up to 48 per frame and plane) sit in
+//           LDS, the per-distance thresholds and the job tables in global memory.
+#include "mvx_fps_shared.h"
+#include "mvx_degrain_n_weights.h"
+
+static_assert(DN_MAX_RADIUS == MVX_DEGRAIN_N_MAX_RADIUS, "radius limit");
+
+#define DN_K 4 // entries per chunk: DN_K loads of one cell row in flight (W = 8 samples of 16 bits: 4 registers each)
+
+// ------------------------------------------------------------------------------------------------ device structs
+
+struct DNParams {
+    int nRefs, nBlkX, nBlkY, nBlk, pel, logPel, bits, bps, nplanes, overlap;
+    int nLvCount;
+    int recBytes;            // stride of a plan slot: 16 + 8 * (nRefs rounded up to a multiple of DN_K)
+    long long thscd1; int thscd2;
+    PlaneG pl[3];
+    const int16_t *win[3];
+    long long thSAD[2][DN_MAX_RADIUS]; // [luma / chroma][distance - 1]
+};
+
+struct DNJob { const unsigned char *src[3]; unsigned char *dst[3]; };
+
+struct __attribute__((aligned(16))) DNHead { int wsrc, count, pad[2]; };
+struct __attribute__((aligned(8))) DNEntry { unsigned off; short w; unsigned short r; };
+static_assert(sizeof(DNHead) == 16 && sizeof(DNEntry) == 8, "plan slot layout");
+static int dn_rec_bytes(int nrefs) { return 16 + 8 * ((nrefs + DN_K - 1) / DN_K * DN_K); }
+
+// ------------------------------------------------------------------------------------------------ kernels
+
+// per (job, reference): 0 when the reference's vectors are not usable (fgopIsUsable, or a reference frame outside the clip, which may have
+// no blob at all), else the byte offset of level 0 inside the blob (a walk over the per-level size headers, done once here)
+__global__ __launch_bounds__(256) void dn_usable_kernel(const DNParams *Pp, const unsigned char *const *refs, const unsigned char *const *blobs, unsigned *lv0) {
+    const DNParams &P = *Pp;
+    const int k = blockIdx.y * P.nRefs + blockIdx.x;
+    const unsigned char *blob = blobs[k];
+    const bool ok = fps_block_usable(blob, refs[(size_t)k * 3] != nullptr, P.nLvCount, P.nBlk, P.thscd1, P.thscd2);
+    if (threadIdx.x == 0) lv0[k] = ok ? (unsigned)((const unsigned char *)mvx_level0(blob, P.nLvCount) - blob) : 0u;
+}
+
+// one thread per (job, block): both plane classes' lists.  The references are walked DN_K at a time so that DN_K vector loads are in flight;
+// raw weights go into the slot as they are found, and are normalised in place once WSum is known.
+__global__ __launch_bounds__(256) void dn_plan_kernel(const DNParams *Pp, const unsigned char *const *blobs, const unsigned *lv0, unsigned char *plan) {
+    const DNParams &P = *Pp;
+    const int f = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= P.nBlk) return;
+    const int by = i / P.nBlkX, bx = i - by * P.nBlkX;
+    const int n = P.nRefs, ncls = P.nplanes > 1 ? 2 : 1;
+    typedef unsigned pl_v4 __attribute__((ext_vector_type(4), aligned(4)));
+    unsigned char *slot[2];
+    int count[2] = { 0, 0 }, WSum[2] = { dn_wsum_begin(), dn_wsum_begin() };
+    for (int c = 0; c < 2; c++) slot[c] = plan + ((size_t)f * 2 + c) * P.nBlk * P.recBytes + (size_t)i * P.recBytes;
+    for (int r0 = 0; r0 < n; r0 += DN_K) {
+        pl_v4 vv[DN_K]; bool us[DN_K];
+#pragma unroll
+        for (int k = 0; k < DN_K; k++) {
+            const int r = r0 + k;
+            const unsigned l0 = r < n ? lv0[f * n + r] : 0u;
+            us[k] = l0 != 0u;
+            vv[k] = pl_v4{0, 0, 0, 0};
+            if (us[k]) vv[k] = *(DG_GL const pl_v4 *)(dg_gl(blobs[f * n + r]) + l0 + (size_t)i * sizeof(GVecD));
+        }
+#pragma unroll
+        for (int k = 0; k < DN_K; k++) {
+            if (!us[k]) continue; // MVDegrains.h:192-206 useBlock: weight 0
+            const int r = r0 + k;
+            const int vx = (int)vv[k][0], vy = (int)vv[k][1];
+            const long long sad = (long long)(((unsigned long long)vv[k][3] << 32) | vv[k][2]);
+            const int blx = ((bx * P.pl[0].stepX) << P.logPel) + vx, bly = ((by * P.pl[0].stepY) << P.logPel) + vy; // block origin Fakery.c:31-32
+            for (int c = 0; c < ncls; c++) {
+                const PlaneG &g = P.pl[c];
+                const int w = dn_weight(P.thSAD[c][dn_distance(r) - 1], sad);
+                if (w == 0) continue;
+                DNEntry e;
+                e.off = sup_offset(g, P.pel, P.logPel, P.bps, c ? blx >> g.subX : blx, c ? bly >> g.subY : bly);
+                e.w = (short)w; e.r = (unsigned short)r;
+                ((DNEntry *)(slot[c] + sizeof(DNHead)))[count[c]++] = e;
+                WSum[c] += w;
+            }
+        }
+    }
+    for (int c = 0; c < ncls; c++) { // MVDegrains.h:208-223 normaliseWeights
+        const double scale = dn_scale(WSum[c]);
+        DNEntry *e = (DNEntry *)(slot[c] + sizeof(DNHead));
+        int WSrc = 256;
+        for (int k = 0; k < count[c]; k++) { const int w = dn_scaled(e[k].w, scale); WSrc -= w; e[k].w = (short)w; }
+        DNHead h; h.wsrc = WSrc; h.count = count[c]; h.pad[0] = h.pad[1] = 0;
+        *(DNHead *)slot[c] = h;
+    }
+}
+
+// BYTES consecutive bytes from an arbitrarily aligned address, as dwords
+template <int BYTES> struct DnRaw { unsigned d[(BYTES + 3) / 4]; };
+template <int BYTES> __device__ __forceinline__ DnRaw<BYTES> dn_load_raw(DG_GL const unsigned char *p) {
+    DnRaw<BYTES> r;
+    if constexpr (BYTES == 16) { const dg_uv4 t = *(DG_GL const dg_uv4 *)p; r.d[0] = t[0]; r.d[1] = t[1]; r.d[2] = t[2]; r.d[3] = t[3]; }
+    else if constexpr (BYTES == 8) { const dg_uv2 t = *(DG_GL const dg_uv2 *)p; r.d[0] = t[0]; r.d[1] = t[1]; }
+    else if constexpr (BYTES == 4) r.d[0] = *(DG_GL const dg_uv1 *)p;
+    else if constexpr (BYTES == 2) r.d[0] = *(DG_GL const dg_uh1 *)p;
+    else r.d[0] = *p;
+    return r;
+}
+template <typename T, int BYTES> __device__ __forceinline__ int dn_sample(const DnRaw<BYTES> &r, int i) {
+    return sizeof(T) == 2 ? (int)((r.d[i >> 1] >> (16 * (i & 1))) & 0xffffu) : (int)((r.d[i >> 2] >> (8 * (i & 3))) & 0xffu);
+}
+// W samples of type T to an arbitrarily aligned address (dg_store's widths start at two bytes; a cell here can be one 8-bit sample)
+template <typename T, int W> __device__ __forceinline__ void dn_store(DG_GL unsigned char *p, const int *v) {
+    constexpr int BYTES = W * (int)sizeof(T);
+    unsigned d[(BYTES + 3) / 4];
+#pragma unroll
+    for (int k = 0; k < (BYTES + 3) / 4; k++) d[k] = 0;
+#pragma unroll
+    for (int i = 0; i < W; i++) {
+        if (sizeof(T) == 2) d[i >> 1] |= (unsigned)v[i] << (16 * (i & 1));
+        else d[i >> 2] |= (unsigned)v[i] << (8 * (i & 3));
+    }
+    if constexpr (BYTES == 16) { const dg_uv4 t = { d[0], d[1], d[2], d[3] }; *(DG_GL dg_uv4 *)p = t; }
+    else if constexpr (BYTES == 8) { const dg_uv2 t = { d[0], d[1] }; *(DG_GL dg_uv2 *)p = t; }
+    else if constexpr (BYTES == 4) *(DG_GL dg_uv1 *)p = d[0];
+    else if constexpr (BYTES == 2) *(DG_GL dg_uh1 *)p = (unsigned short)d[0];
+    else *p = (unsigned char)d[0];
+}
+typedef unsigned dn_v4 __attribute__((ext_vector_type(4), aligned(16)));
+
+// the cell's row inside one block: Degrain_C (MVDegrains.h:30-53) over the block's list, DN_K entries at a time.  slot: the block's plan slot
+// (16-byte aligned), refB: the frame's reference planes in LDS.  The head and the first chunk of entries are requested together (a slot has
+// room for at least DN_K entries), and every later chunk before the rows of the one before it are used, so a visit is two dependent round
+// trips (list -> rows) whatever the length of the list.  An entry slot past the list's end repeats the chunk's first entry with weight 0, so
+// every load goes to an address that a listed reference owns.
+template <typename T, int W>
+__device__ __forceinline__ void dn_block_sum(DG_GL const unsigned char *slot, const unsigned long long *refB, long long rowOff, const int *s, int *sum) {
+    const dn_v4 head = *(DG_GL const dn_v4 *)slot;
+    dn_v4 ent[DN_K / 2];
+#pragma unroll
+    for (int k = 0; k < DN_K / 2; k++) ent[k] = *(DG_GL const dn_v4 *)(slot + sizeof(DNHead) + 16 * k);
+    const int wsrc = (int)head[0], count = (int)head[1]; // DNHead
+#pragma unroll
+    for (int i = 0; i < W; i++) sum[i] = 128 + s[i] * wsrc;
+    for (int e = 0; e < count; e += DN_K) {
+        unsigned off[DN_K], wr[DN_K]; // DNEntry: offset, weight | reference << 16
+#pragma unroll
+        for (int k = 0; k < DN_K; k += 2) { off[k] = ent[k / 2][0]; wr[k] = ent[k / 2][1]; off[k + 1] = ent[k / 2][2]; wr[k + 1] = ent[k / 2][3]; }
+        DnRaw<W * (int)sizeof(T)> raw[DN_K];
+        int w[DN_K];
+#pragma unroll
+        for (int k = 0; k < DN_K; k++) {
+            const bool valid = e + k < count; // (k == 0 always is)
+            const unsigned o = valid ? off[k] : off[0], r = (valid ? wr[k] : wr[0]) >> 16;
+            w[k] = valid ? (int)(short)(wr[k] & 0xffffu) : 0;
+            raw[k] = dn_load_raw<W * (int)sizeof(T)>(dg_gl((const unsigned char *)refB[r]) + o + rowOff);
+        }
+        if (e + DN_K < count) {
+#pragma unroll
+            for (int k = 0; k < DN_K / 2; k++) ent[k] = *(DG_GL const dn_v4 *)(slot + sizeof(DNHead) + (size_t)(e + DN_K) * sizeof(DNEntry) + 16 * k);
+        }
+#pragma unroll
+        for (int k = 0; k < DN_K; k++) {
+#pragma unroll
+            for (int i = 0; i < W; i++) sum[i] += dn_sample<T>(raw[k], i) * w[k];
+        }
+    }
+}
+
+// One thread per row of a cell: W consecutive samples starting at a multiple of W, where W divides the block width and the block step, so
+// that the same blocks cover all of them (blocks side by side: one block).  256 threads = 32 cells x 8 rows of one plane of one job.
+template <typename T, int W>
+__global__ __launch_bounds__(256) void dn_cell_kernel(const DNParams *Pp, const DNJob *jobs, const unsigned char *const *refs, const unsigned char *plan, int planeFirst, int planesPerFrame) {
+    const DNParams &P = *Pp;
+    const int z = blockIdx.z, f = z / planesPerFrame, p = planeFirst + z % planesPerFrame;
+    const PlaneG &g = P.pl[p];
+    __shared__ unsigned long long refB[DN_MAX_REFS];
+    if ((int)threadIdx.x < P.nRefs) refB[threadIdx.x] = (unsigned long long)refs[((size_t)f * P.nRefs + threadIdx.x) * 3 + p];
+    __syncthreads();
+    const int c = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
+    const int x0 = c * W;
+    if (x0 >= g.W || y >= g.H) return;
+    const DNJob &J = jobs[f];
+    const unsigned char *srow = J.src[p] + (long long)y * g.srcPitch + (long long)x0 * sizeof(T);
+    unsigned char *drow = J.dst[p] + (long long)y * g.dstPitch + (long long)x0 * sizeof(T);
+    const bool fullW = x0 + W <= g.W;
+    int s[W];
+    if (fullW) {
+        const DnRaw<W * (int)sizeof(T)> raw = dn_load_raw<W * (int)sizeof(T)>(dg_gl(srow));
+#pragma unroll
+        for (int i = 0; i < W; i++) s[i] = dn_sample<T>(raw, i);
+    } else {
+#pragma unroll
+        for (int i = 0; i < W; i++) s[i] = x0 + i < g.W ? (int)((const T *)srow)[i] : 0;
+    }
+    int out[W];
+#pragma unroll
+    for (int i = 0; i < W; i++) out[i] = s[i];
+    // MVDegrains.cpp:211-214,238-249,290-298: a plane that is not processed and the strips no block covers keep the source.  The covered
+    // width is a multiple of W, so a cell that starts inside it lies inside it (and inside the frame)
+    if (g.process && x0 < g.WB && y < g.HB) {
+        DG_GL const unsigned char *pl = dg_gl(plan + ((size_t)f * 2 + (p ? 1 : 0)) * P.nBlk * P.recBytes);
+        const int pm = (1 << P.bits) - 1;
+        int sum[W];
+        if (!P.overlap) { // MVDegrains.cpp:238-249: Degrain_C straight into the frame
+            const int bx = x0 / g.blkW, by = y / g.blkH;
+            const int px = x0 - bx * g.blkW, py = y - by * g.blkH;
+            DG_GL const unsigned char *slot = pl + (size_t)(by * P.nBlkX + bx) * P.recBytes;
+            dn_block_sum<T, W>(slot, refB, (long long)py * g.supPitch + (long long)px * sizeof(T), s, sum);
+#pragma unroll
+            for (int i = 0; i < W; i++) out[i] = (T)(sum[i] >> 8);
+        } else {
+            // blocks covering this cell: bx in [bx0, bx1], by in [by0, by1]
+            int bx1 = x0 / g.stepX; if (bx1 > P.nBlkX - 1) bx1 = P.nBlkX - 1;
+            const int bx0 = x0 - g.blkW + 1 <= 0 ? 0 : (x0 - g.blkW + g.stepX) / g.stepX;
+            int by1 = y / g.stepY; if (by1 > P.nBlkY - 1) by1 = P.nBlkY - 1;
+            const int by0 = y - g.blkH + 1 <= 0 ? 0 : (y - g.blkH + g.stepY) / g.stepY;
+            unsigned acc[W];
+#pragma unroll
+            for (int i = 0; i < W; i++) acc[i] = 0;
+            const int16_t *win = P.win[p];
+            for (int by = by0; by <= by1; by++) {
+                const int py = y - by * g.stepY;
+                const int wby = by == 0 ? 0 : (by == P.nBlkY - 1 ? 6 : 3); // ((by + nBlkY - 3) / (nBlkY - 2)) * 3, MVDegrains.cpp:256
+                for (int bx = bx0; bx <= bx1; bx++) {
+                    const int px = x0 - bx * g.stepX; // 0 <= px <= blkW - W
+                    const int wbx = bx == P.nBlkX - 1 ? 2 : (bx == 0 ? 0 : 1); // :260-262,285
+                    DG_GL const unsigned char *slot = pl + (size_t)(by * P.nBlkX + bx) * P.recBytes;
+                    const DnRaw<W * 2> wr = dn_load_raw<W * 2>(dg_gl((const unsigned char *)(win + (wby + wbx) * g.blkW * g.blkH + py * g.blkW + px)));
+                    dn_block_sum<T, W>(slot, refB, (long long)py * g.supPitch + (long long)px * sizeof(T), s, sum);
+#pragma unroll
+                    for (int i = 0; i < W; i++) { // overlaps_c, Overlap.cpp:143-158
+                        const int val = (T)(sum[i] >> 8);
+                        acc[i] += (unsigned)((val * dn_sample<unsigned short>(wr, i)) >> 6);
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < W; i++) {
+                unsigned a0 = acc[i];
+                if (sizeof(T) == 1) a0 &= 0xffffu; // 16-bit accumulator of the 8-bit path (Overlap.cpp:254-256)
+                const int a = (int)((a0 + 16) >> 5); // ToPixels, Overlap.cpp:335-356
+                out[i] = a > pm ? pm : a;
+            }
+        }
+        if (g.limit < pm) { // LimitChanges, MVDegrains.h:163-181
+#pragma unroll
+            for (int i = 0; i < W; i++) {
+                const int lo = s[i] - g.limit, hi = s[i] + g.limit;
+                out[i] = out[i] < lo ? lo : out[i];
+                out[i] = out[i] > hi ? hi : out[i];
+            }
+        }
+    }
+    if (fullW) dn_store<T, W>(dg_glw(drow), out);
+    else {
+#pragma unroll
+        for (int i = 0; i < W; i++) if (x0 + i < g.W) ((T *)drow)[i] = (T)out[i];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host object
+
+struct mvx_degrain_n {
+    CallGuard guard;
+    DNParams P;
+    mvx_degrain_n_info info;
+    DevBuf<DNParams> dP;
+    DevBuf<unsigned char> dTables;   // per call: the jobs, then the reference planes [job][reference][plane], then the blobs [job][reference]
+    DevBuf<unsigned> dLv0;
+    DevBuf<unsigned char> dPlan;
+    DevBuf<int16_t> dWin[2];
+    int nWinClasses = 1;
+};
+
+// the scaled thresholds of one plane class over the distances; 0, or which argument reaches INT_MAX (MVDegrains.cpp:660-661): 1 the near
+// threshold (thsad / thsadc), 2 the far one (thsad2 / thsadc2) -- the entries in between lie between the two
+static int dn_thresholds(int64_t t1, int64_t t2, int radius, int64_t nSCD1, int64_t nSCD1_old, int64_t *table) {
+    dn_threshold_table(t1, t2, radius, nSCD1, nSCD1_old, table);
+    if (table[0] >= 2147483647LL) return 1;
+    for (int d = 1; d < radius; d++) if (table[d] >= 2147483647LL) return 2;
+    return 0;
+}
+
+extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_create(const mvx_degrain_n_args *a, const mvx_analysis_data *ad, const mvx_super *sup, const ptrdiff_t src_pitch[3],
+                                    const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_degrain_n **out, char *err) {
+    MVX_CREATE_BEGIN(out);
+    const mvx_super_info &si = sup->info;
+    const int radius = a->radius;
+    const char *name = "DegrainN";
+    if (radius < 1 || radius > MVX_DEGRAIN_N_MAX_RADIUS) MVX_FAIL("%s: radius must be between 1 and %d.", name, MVX_DEGRAIN_N_MAX_RADIUS);
+    const int64_t t1 = a->thsad == MVX_UNSET ? 400 : a->thsad, t1c = a->thsadc == MVX_UNSET ? t1 : a->thsadc;
+    const int64_t t2 = a->thsad2 == MVX_UNSET ? t1 : a->thsad2, t2c = a->thsadc2 == MVX_UNSET ? t1c : a->thsadc2;
+    const int plane = a->plane == MVX_UNSET ? 4 : a->plane;
+    if (plane < 0 || plane > 4) MVX_FAIL("%s: plane must be between 0 and 4 (inclusive).", name);
+    static const int planes[5] = { 1, 2, 4, 6, 7 };
+    const int YUVplanes = planes[plane];
+    int64_t nSCD1, nSCD1_old; int32_t nSCD2;
+    if (int rc = mvx_resolve_thscd(name, a->thscd1, a->thscd2, ad, &nSCD1, &nSCD2, err, &nSCD1_old)) return rc;
+    mvx_degrain_n_info info;
+    memset(&info, 0, sizeof(info));
+    info.radius = radius; info.nrefs = 2 * radius;
+    const int overY = dn_thresholds(t1, t2, radius, nSCD1, nSCD1_old, info.thsad_d), overC = dn_thresholds(t1c, t2c, radius, nSCD1, nSCD1_old, info.thsadc_d);
+    if (overY || overC) { // MVDegrains.cpp:660-666: thsad, thsadc, then the far thresholds
+        const char *which = overY == 1 ? "" : overC == 1 ? "c" : overY ? "2" : "c2";
+        MVX_FAIL("%s: with this block size and video format, thsad%s must not exceed %lld or some calculations would overflow.", name, which,
+                 (long long)(2147483647LL * nSCD1_old / nSCD1));
+    }
+    if (!mvx_super_fits(ad, si, true)) MVX_FAIL("%s: wrong source or super clip frame size.", name);
+    const int pixelMax = (1 << si.bits) - 1;
+    const int limit = a->limit == MVX_UNSET ? pixelMax : a->limit;
+    const int limitc = a->limitc == MVX_UNSET ? limit : a->limitc;
+    if (limit < 0 || limit > pixelMax) MVX_FAIL("%s: limit must be between 0 and %d (inclusive).", name, pixelMax);
+    if (limitc < 0 || limitc > pixelMax) MVX_FAIL("%s: limitc must be between 0 and %d (inclusive).", name, pixelMax);
+    const bool overlap = ad->nOverlapX > 0 || ad->nOverlapY > 0;
+    if (overlap && (ad->nBlkX < 3 || ad->nBlkY < 3)) MVX_FAIL("overlap needs at least 3x3 blocks (window selection divides by nBlk-2).");
+    if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) MVX_FAIL("U and V super planes must share one pitch.");
+
+    mvx_degrain_n *h = new mvx_degrain_n();
+    h->info = info;
+    DNParams &P = h->P;
+    memset(&P, 0, sizeof(P));
+    P.nRefs = 2 * radius; P.recBytes = dn_rec_bytes(P.nRefs);
+    P.nBlkX = ad->nBlkX; P.nBlkY = ad->nBlkY; P.nBlk = ad->nBlkX * ad->nBlkY;
+    P.pel = ad->nPel; P.logPel = ad->nPel == 4 ? 2 : ad->nPel == 2 ? 1 : 0;
+    P.bits = si.bits; P.bps = (si.bits + 7) / 8; P.nplanes = si.num_planes;
+    P.overlap = overlap;
+    P.nLvCount = ad->nLvCount;
+    fps_fill_planes(P.pl, ad, si, src_pitch, super_pitch, dst_pitch);
+    h->nWinClasses = si.num_planes > 1 ? 2 : 1;
+    for (int d = 0; d < radius; d++) { P.thSAD[0][d] = info.thsad_d[d]; P.thSAD[1][d] = info.thsadc_d[d]; }
+    P.thscd1 = nSCD1; P.thscd2 = nSCD2;
+    P.pl[0].process = !!(YUVplanes & 1);
+    P.pl[1].process = !!(YUVplanes & 2 & si.modeYUV);
+    P.pl[2].process = !!(YUVplanes & 4 & si.modeYUV);
+    P.pl[0].limit = limit; P.pl[1].limit = P.pl[2].limit = limitc;
+    *out = h;
+    return MVX_OK;
+}
+
+extern "C" __attribute__((visibility("default"))) void mvx_degrain_n_get_info(const mvx_degrain_n *d, mvx_degrain_n_info *info) { *info = d->info; }
+extern "C" __attribute__((visibility("default"))) void mvx_degrain_n_destroy(mvx_degrain_n *d) { delete d; }
+
+// device state is created on first use so that argument validation works without a GPU
+static int dn_finish(mvx_degrain_n *h) {
+    if (h->dP.p) return MVX_OK;
+    DNParams &P = h->P;
+    if (P.overlap) {
+        for (int c = 0; c < h->nWinClasses; c++) {
+            const PlaneG &g = P.pl[c];
+            std::vector<int16_t> w(9 * g.blkW * g.blkH);
+            mvx_over_windows(w.data(), g.blkW, g.blkH, g.ovX, g.ovY);
+            HIP_CHECK(h->dWin[c].reserve(w.size()));
+            HIP_CHECK(hipMemcpy(h->dWin[c].p, w.data(), w.size() * 2, hipMemcpyHostToDevice));
+        }
+        P.win[0] = h->dWin[0].p; P.win[1] = P.win[2] = h->dWin[1].p;
+    }
+    return fps_upload_params(h->dP, P);
+}
+
+// samples per cell of plane p: the largest power of two up to 8 that divides the block width and the block step
+static int dn_cell_width(const PlaneG &g) {
+    int w = 8;
+    while (w > 1 && (g.blkW % w || g.stepX % w)) w >>= 1;
+    return w;
+}
+
+template <typename T> static void dn_launch_cells(int W, dim3 grid, hipStream_t st, const DNParams *dP, const DNJob *dJ, const unsigned char *const *dRefs, const unsigned char *plan, int p0, int npl) {
+#define DNC(N) hipLaunchKernelGGL((dn_cell_kernel<T, N>), grid, dim3(256), 0, st, dP, dJ, dRefs, plan, p0, npl)
+    switch (W) { case 1: DNC(1); break; case 2: DNC(2); break; case 4: DNC(4); break; default: DNC(8); break; }
+#undef DNC
+}
+
+extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_frames(mvx_degrain_n *d, int nframes, const mvx_degrain_n_job *jobs, void *stream) {
+    if (nframes <= 0) return MVX_OK;
+    hipStream_t st = (hipStream_t)stream;
+    CallGuard::Scope scope(d->guard, st);
+    int rc = dn_finish(d);
+    if (rc) return rc;
+    const DNParams &P = d->P;
+    const size_t n = (size_t)nframes, nr = (size_t)P.nRefs;
+    // one host block, one copy: jobs | reference planes | blobs (each part a multiple of 8 bytes)
+    const size_t offRefs = sizeof(DNJob) * n, offBlobs = offRefs + sizeof(void *) * 3 * nr * n, total = offBlobs + sizeof(void *) * nr * n;
+    std::vector<unsigned char> host(total, 0);
+    DNJob *hj = (DNJob *)host.data();
+    const unsigned char **hr = (const unsigned char **)(host.data() + offRefs), **hb = (const unsigned char **)(host.data() + offBlobs);
+    for (size_t f = 0; f < n; f++) {
+        for (int p = 0; p < 3; p++) { hj[f].src[p] = (const unsigned char *)jobs[f].src[p]; hj[f].dst[p] = (unsigned char *)jobs[f].dst[p]; }
+        for (size_t r = 0; r < nr; r++) {
+            for (int p = 0; p < 3; p++) hr[(f * nr + r) * 3 + p] = (const unsigned char *)jobs[f].refs[r][p];
+            hb[f * nr + r] = (const unsigned char *)jobs[f].blobs[r];
+        }
+    }
+    const size_t planBytes = (size_t)P.recBytes * 2 * P.nBlk * n;
+    HIP_CHECK(d->dTables.reserve(total, total));
+    HIP_CHECK(d->dLv0.reserve(nr * n, nr * n));
+    HIP_CHECK(d->dPlan.reserve(planBytes, planBytes / 2));
+    HIP_CHECK(hipMemcpyAsync(d->dTables.p, host.data(), total, hipMemcpyHostToDevice, st));
+    const DNJob *dJ = (const DNJob *)d->dTables.p;
+    const unsigned char *const *dRefs = (const unsigned char *const *)(d->dTables.p + offRefs), *const *dBlobs = (const unsigned char *const *)(d->dTables.p + offBlobs);
+    hipLaunchKernelGGL(dn_usable_kernel, dim3(P.nRefs, nframes), dim3(256), 0, st, d->dP.p, dRefs, dBlobs, d->dLv0.p);
+    hipLaunchKernelGGL(dn_plan_kernel, dim3((P.nBlk + 255) / 256, nframes), dim3(256), 0, st, d->dP.p, dBlobs, d->dLv0.p, d->dPlan.p);
+    for (int cls = 0; cls < (P.nplanes > 1 ? 2 : 1); cls++) { // one launch for the luma planes of all jobs, one for both chroma planes
+        const int p0 = cls, npl = cls ? 2 : 1, W = dn_cell_width(P.pl[p0]);
+        const dim3 grid(((P.pl[p0].W + W - 1) / W + 31) / 32, (P.pl[p0].H + 7) / 8, nframes * npl);
+        if (P.bps == 1) dn_launch_cells<uint8_t>(W, grid, st, d->dP.p, dJ, dRefs, d->dPlan.p, p0, npl);
+        else dn_launch_cells<uint16_t>(W, grid, st, d->dP.p, dJ, dRefs, d->dPlan.p, p0, npl);
+    }
+    HIP_CHECK(hipGetLastError());
+    return MVX_OK;
+}

@@ -3,6 +3,7 @@
     core.mv.Super(clip, ...)            -> Super(width, height, bits, ...)       .build(frames)
     core.mv.Analyse(super, ...)         -> Analyse(super, num_frames, ...)       .run(jobs)
     core.mv.Degrain1..6(clip, super, mvbw, mvfw, ...) -> Degrain(radius, super, analysis_data, ...) .run(jobs)
+    (no reference name: radius 1..24)                 -> DegrainN(radius, super, analysis_data, ..., thsad2=...) .info() .run(jobs)
     core.mv.Compensate(clip, super, vectors, ...)     -> Compensate(super, analysis_data, ...)      .run(jobs)
     core.mv.FlowInter / FlowFPS(clip, super, mvbw, mvfw, ...) -> FlowInter / FlowFPS(super, bw_data, fw_data, ...) .run(ns, ...)
     core.mv.Flow(clip, super, vectors, ...)           -> Flow(super, analysis_data, ...)          .run(jobs)
@@ -72,6 +73,22 @@ class DegrainArgs(C.Structure):
 
 class DegrainJob(C.Structure):
     _fields_ = [("src", C.c_void_p * 3), ("refs", (C.c_void_p * 3) * 12), ("blobs", C.c_void_p * 12), ("dst", C.c_void_p * 3)]
+
+
+DEGRAIN_N_MAX_RADIUS = 24
+
+
+class DegrainNArgs(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("thsad", C.c_int64), ("thsadc", C.c_int64), ("thsad2", C.c_int64), ("thsadc2", C.c_int64), ("plane", C.c_int32),
+                ("limit", C.c_int32), ("limitc", C.c_int32), ("thscd1", C.c_int64), ("thscd2", C.c_int32)]
+
+
+class DegrainNInfo(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("nrefs", C.c_int32), ("thsad_d", C.c_int64 * DEGRAIN_N_MAX_RADIUS), ("thsadc_d", C.c_int64 * DEGRAIN_N_MAX_RADIUS)]
+
+
+class DegrainNJob(C.Structure):
+    _fields_ = [("src", C.c_void_p * 3), ("refs", C.POINTER(C.c_void_p * 3)), ("blobs", C.POINTER(C.c_void_p)), ("dst", C.c_void_p * 3)]
 
 
 class CompensateArgs(C.Structure):
@@ -280,6 +297,12 @@ def lib():
                                          P(C.c_void_p), C.c_char_p]
         L.mvx_degrain_destroy.argtypes = [C.c_void_p]
         L.mvx_degrain_frames.argtypes = [C.c_void_p, C.c_int, P(DegrainJob), C.c_void_p]
+        L.mvx_degrain_n_create.argtypes = [P(DegrainNArgs), P(AnalysisData), C.c_void_p, P(C.c_ssize_t), P(C.c_ssize_t), P(C.c_ssize_t),
+                                           P(C.c_void_p), C.c_char_p]
+        L.mvx_degrain_n_get_info.argtypes = [C.c_void_p, P(DegrainNInfo)]
+        L.mvx_degrain_n_get_info.restype = None
+        L.mvx_degrain_n_destroy.argtypes = [C.c_void_p]
+        L.mvx_degrain_n_frames.argtypes = [C.c_void_p, C.c_int, P(DegrainNJob), C.c_void_p]
         L.mvx_compensate_create.argtypes = [P(CompensateArgs), P(AnalysisData), C.c_void_p, P(C.c_ssize_t), P(C.c_ssize_t),
                                             P(C.c_void_p), C.c_char_p]
         L.mvx_compensate_destroy.argtypes = [C.c_void_p]
@@ -734,6 +757,63 @@ class Degrain:
                         arr[i].refs[r][p] = refs[r][p].data_ptr()
                 arr[i].blobs[r] = blobs[r].data_ptr()
         _check(lib().mvx_degrain_frames(self.h, n, arr, _stream()))
+        return out
+
+
+class DegrainN:
+    """Degrain at a temporal radius of 1..24 (include/mvtools_amd.h, mv.DegrainN): the reference's templates over the radius (MVDegrains.h:30-53,184-223)
+    read at any radius, each reference weighed against the threshold of its temporal distance -- thsad at distance 1 falling to thsad2 at distance
+    `radius` (thsad2 / thsadc2 None: no fall-off).  analysis_data = the vector clips' MVTools_MVAnalysisData."""
+
+    def __init__(self, radius, sup, analysis_data, src_pitch, dst_pitch=None, thsad=None, thsadc=None, thsad2=None, thsadc2=None, plane=None, limit=None,
+                 limitc=None, thscd1=None, thscd2=None):
+        self.sup = sup
+        self.radius = radius
+        a = DegrainNArgs(radius, _u(thsad), _u(thsadc), _u(thsad2), _u(thsadc2), _u(plane), _u(limit), _u(limitc), _u(thscd1), _u(thscd2))
+        ad = AnalysisData.from_buffer_copy(bytes(analysis_data))
+        dst_pitch = dst_pitch or src_pitch
+        pad = lambda l: (C.c_ssize_t * 3)(*(list(l) + [0] * (3 - len(l))))
+        self.h = C.c_void_p()
+        err = C.create_string_buffer(ERRLEN)
+        _check(lib().mvx_degrain_n_create(C.byref(a), C.byref(ad), sup.h, pad(src_pitch), pad(sup.pitch), pad(dst_pitch), C.byref(self.h), err), err)
+        self.src_pitch, self.dst_pitch = list(src_pitch), list(dst_pitch)
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().mvx_degrain_n_destroy(self.h)
+        except Exception:
+            pass
+
+    def info(self):
+        """what creation resolved: dict(radius, nrefs, thsad_d, thsadc_d) -- the thresholds per distance 1..radius after the block-size scaling"""
+        i = DegrainNInfo()
+        lib().mvx_degrain_n_get_info(self.h, C.byref(i))
+        return dict(radius=i.radius, nrefs=i.nrefs, thsad_d=list(i.thsad_d[:i.radius]), thsadc_d=list(i.thsadc_d[:i.radius]))
+
+    def run(self, jobs, out=None):
+        """jobs: list of (src_frame, [ref_super or None]*2r, [blob]*2r) ordered mvbw, mvfw, mvbw2, mvfw2, ..."""
+        torch = _torch()
+        n, nr = len(jobs), 2 * self.radius
+        if out is None:
+            out = [[torch.empty_like(p) for p in j[0]] for j in jobs]
+        arr = (DegrainNJob * n)()
+        refs_all, blobs_all = ((C.c_void_p * 3) * (nr * n))(), (C.c_void_p * (nr * n))()  # the host tables behind the jobs' pointers
+        for i, (src, refs, blobs) in enumerate(jobs):
+            if len(refs) != nr or len(blobs) != nr:
+                raise ValueError("DegrainN: a job needs %d references and blobs" % nr)
+            for p in range(self.sup.nplanes):
+                assert src[p].stride(0) == self.src_pitch[p] and out[i][p].stride(0) == self.dst_pitch[p]
+                arr[i].src[p] = src[p].data_ptr()
+                arr[i].dst[p] = out[i][p].data_ptr()
+            for r in range(nr):
+                if refs[r] is not None:
+                    for p in range(self.sup.nplanes):
+                        refs_all[i * nr + r][p] = refs[r][p].data_ptr()
+                blobs_all[i * nr + r] = blobs[r].data_ptr() if blobs[r] is not None else None
+            arr[i].refs = C.cast(C.byref(refs_all, i * nr * C.sizeof(C.c_void_p * 3)), C.POINTER(C.c_void_p * 3))
+            arr[i].blobs = C.cast(C.byref(blobs_all, i * nr * C.sizeof(C.c_void_p)), C.POINTER(C.c_void_p))
+        _check(lib().mvx_degrain_n_frames(self.h, n, arr, _stream()))
         return out
 
 
