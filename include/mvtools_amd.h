@@ -252,6 +252,23 @@ typedef struct mvx_degrain_n mvx_degrain_n;
 int mvx_degrain_n_create(const mvx_degrain_n_args *args, const mvx_analysis_data *vectors_data /* of mvbw */,
                          const mvx_super *super_clip, const ptrdiff_t src_pitch[3], const ptrdiff_t super_pitch[3],
                          const ptrdiff_t dst_pitch[3], mvx_degrain_n **out, char *err);
+/* out16 (pinterf's MVTools2 has it as out16=true on MDegrain and MDegrainN; no counterpart in the reference): an 8-bit clip, an 8-bit
+ * super clip and vectors analysed on 8-bit samples -- SADs, thsad, thsad2, thscd1 and thscd2 in 8-bit units, the weights those of
+ * mvx_degrain_n_create -- written as 16-bit planes; dst_pitch is THEIR pitch.  The output is byte for byte what the 16-bit arithmetic above
+ * gives when every source and super sample is shifted left by 8 and every block carries the weights of the 8-bit run:
+ *   block value      S = WSrc * src + sum of W_r * ref_r, 0..65280: no + 128, no shift ((128 + 256 * S) >> 8 = S)
+ *   overlap 0        out = S
+ *   overlap > 0      acc += (S * win) >> 6 in 32 bits (NOT the 16-bit wrap of the 8-bit path); out = min(65535, (acc + 16) >> 5)
+ *   limit / limitc   in units of the output: 0..65535, MVX_UNSET -> 65535 (none) / limit; below 65535 out is clamped to
+ *                    [(src << 8) - limit, (src << 8) + limit]
+ *   passed through   a plane that `plane` leaves out, the strips no block covers, a job without a usable reference: out = src << 8
+ * Messages are mvx_degrain_n_create's, and after the frame-size check "DegrainN: out16 needs an 8 bit clip." for any other super clip.
+ * Touches no device.  The object is used and destroyed like one of mvx_degrain_n_create. */
+int mvx_degrain_n_create_out16(const mvx_degrain_n_args *args, const mvx_analysis_data *vectors_data /* of mvbw */,
+                               const mvx_super *super_clip, const ptrdiff_t src_pitch[3], const ptrdiff_t super_pitch[3],
+                               const ptrdiff_t dst_pitch[3] /* of the 16-bit planes */, mvx_degrain_n **out, char *err);
+/* bits per sample of the planes mvx_degrain_n_frames writes: 16 for an out16 object, else the clip's depth */
+int mvx_degrain_n_out_bits(const mvx_degrain_n *d);
 void mvx_degrain_n_get_info(const mvx_degrain_n *d, mvx_degrain_n_info *info);
 void mvx_degrain_n_destroy(mvx_degrain_n *d);
 
@@ -263,7 +280,7 @@ typedef struct mvx_degrain_n_job {
     void *dst[3];
 } mvx_degrain_n_job;
 
-/* the host arrays behind refs and blobs are read before the call returns */
+/* the host arrays behind refs and blobs are read before the call returns; serves objects of both create functions */
 int mvx_degrain_n_frames(mvx_degrain_n *d, int nframes, const mvx_degrain_n_job *jobs, void *stream);
 
 /* ---- mv.Compensate -------------------------------------------------------------------------------

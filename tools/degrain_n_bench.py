@@ -2,6 +2,7 @@
 input resident: clip frames, super frames, vector blobs and the output frames.
 
     python tools/degrain_n_bench.py [--configs 1080p8,4k16] [--seconds S] [--jobs N]
+    python tools/degrain_n_bench.py --out16 [--radii 3,8] [--repeats 3] [--seconds S] [--jobs N]
 
 Workloads: 1920 x 1080 8-bit and 3840 x 2160 16-bit, 4:2:0, blocks of 16 overlapping by 8, pel 2.  Rows: Degrain at radius 3 and 6 (the existing kernels,
 whose code this tool leaves alone: what the new ones are read against) and DegrainN at radius 3, 6, 12 and 24, defaults otherwise (thsad 400, no fall-off).
@@ -12,7 +13,12 @@ DegrainN are as long as they get, and the times are its worst case (on real foot
 writing its own output frame; the job tables are built once and the C entry point is called directly, so the host's share of a call is the library's
 own (DegrainN copies its reference tables per call).  The call is repeated until about S seconds lie between the two events, after a warm-up call of the
 same shape.  Reported: ms per frame = ms per call / jobs, and the mean number of references with a weight per block.  Kernel times and counters come from
-separate profiler runs."""
+separate profiler runs.
+
+--out16: the 1080p 8-bit clip only, DegrainN at each of --radii, --repeats timings of each of three lines: (a) the 8-bit DegrainN, (b) DegrainN with out16
+(8-bit clip, super frames and vectors, 16-bit output planes), (c) what gives 16-bit output without out16 -- the same clip shifted left by 8 as a 16-bit clip,
+its own 16-bit super frames and vectors, the 16-bit DegrainN.  The repeats of a line are taken in turn with the other lines (a, b, c, a, b, c, ...), so a drift
+of the clock reaches all three alike; the spread of a line is max - min over its repeats."""
 import argparse
 import ctypes as C
 import os
@@ -86,13 +92,69 @@ def call_of(kind, g, src, refs, blobs, out):
     return run
 
 
+def prepared(w, h, bits, clip):
+    """-> (device frames, super clip, analysis data, {(isb, delta 1..3): (reference super frame, blob)}) for the job TARGET"""
+    sup = mv.Super(w, h, bits)
+    src = [mv.frame_to_device(f) for f in clip]
+    sf = sup.build(src)
+    near = {}
+    for d in (1, 2, 3):
+        for isb in (1, 0):
+            an = mv.Analyse(sup, num_frames=POOL, isb=isb, delta=d, **AKW)
+            nref = TARGET + (d if isb else -d)
+            near[(isb, d)] = (sf[nref], an.run([(sf[TARGET], sf[nref])])[0])
+    return src, sup, an.ad, near
+
+
+def main_out16(a):
+    import torch
+    w, h, _ = CONFIGS["1080p8"]
+    njobs = a.jobs or 64
+    clip8 = pl.moving_clip(w, h, 8, POOL, seed=5, motion=(1, 0))
+    clip16 = [[p.astype(np.uint16) << 8 for p in f] for f in clip8]
+    src8, sup8, ad8, near8 = prepared(w, h, 8, clip8)
+    src16, sup16, ad16, near16 = prepared(w, h, 16, clip16)
+    pitch8, pitch16 = [p.stride(0) for p in src8[0]], [p.stride(0) for p in src16[0]]
+    out8 = [[torch.empty_like(p) for p in src8[TARGET]] for _ in range(njobs)]
+    out16 = [[torch.empty_like(p) for p in src16[TARGET]] for _ in range(njobs)]
+    print("out16: %dx%d 4:2:0, blocks 16/8 (%d x %d), pel 2, %d jobs per call, %d repeats in turn; ms per frame" % (w, h, ad8.nBlkX, ad8.nBlkY, njobs, a.repeats), flush=True)
+    for radius in [int(r) for r in a.radii.split(",")]:
+        def listed(near):
+            picks = [near[(isb, (d - 1) % 3 + 1)] for d in range(1, radius + 1) for isb in (1, 0)]
+            return [r for r, _ in picks], [b for _, b in picks]
+        refs8, blobs8 = listed(near8)
+        refs16, blobs16 = listed(near16)
+        ga = mv.DegrainN(radius, sup8, ad8, pitch8)
+        gb = mv.DegrainN(radius, sup8, ad8, pitch8, dst_pitch=pitch16, out16=True)
+        gc = mv.DegrainN(radius, sup16, ad16, pitch16)
+        assert (ga.out_bits, gb.out_bits, gc.out_bits) == (8, 16, 16)
+        lines = [("(a) 8-bit clip, 8-bit output", call_of("DegrainN", ga, src8[TARGET], refs8, blobs8, out8)),
+                 ("(b) 8-bit clip, out16", call_of("DegrainN", gb, src8[TARGET], refs8, blobs8, out16)),
+                 ("(c) clip shifted to 16 bits, 16-bit DegrainN", call_of("DegrainN", gc, src16[TARGET], refs16, blobs16, out16))]
+        ms = [[] for _ in lines]
+        for _ in range(a.repeats):
+            for i, (_, run) in enumerate(lines):
+                ms[i].append(timed(run, a.seconds)[0] / njobs)
+        for (name, _), m in zip(lines, ms):
+            print("  radius %2d  %-46s %s  min %.4f  spread %.4f  (%.0f fps)" % (radius, name, "  ".join("%.4f" % v for v in m), min(m), max(m) - min(m), 1e3 / min(m)), flush=True)
+        b, c = ms[1], ms[2]
+        print("  radius %2d  (b) - (c) = %+.4f ms per frame at the minima; spread of (c) %.4f: %s" % (
+            radius, min(b) - min(c), max(c) - min(c), "(b) is not slower than (c) by more than (c)'s spread" if min(b) - min(c) <= max(c) - min(c) else "(b) IS SLOWER than (c) by more than (c)'s spread"),
+            flush=True)
+
+
 def main():
     import torch
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="1080p8,4k16")
     ap.add_argument("--seconds", type=float, default=0.5)
     ap.add_argument("--jobs", type=int, default=0, help="jobs per call (default: 64 at 1080p, 16 at 4K)")
+    ap.add_argument("--out16", action="store_true", help="1080p 8-bit: DegrainN, DegrainN with out16, and the 16-bit DegrainN on the clip shifted up")
+    ap.add_argument("--radii", default="3,8", help="with --out16")
+    ap.add_argument("--repeats", type=int, default=3, help="with --out16")
     a = ap.parse_args()
+    if a.out16:
+        return main_out16(a)
     for name in a.configs.split(","):
         w, h, bits = CONFIGS[name]
         njobs = a.jobs or (64 if w < 3000 else 16)

@@ -14,6 +14,9 @@
 //   gather  takes a block's list in chunks of DN_K entries: DN_K rows requested, then multiply-added into sum[W]; window and
 //           normalisation once per block after the last chunk.  The reference planes' base pointers (up to 48 per frame and plane) sit in
 //           LDS, the per-distance thresholds and the job tables in global memory.
+//   out16   (mvx_degrain_n_create_out16) an 8-bit clip written as 16-bit planes: the cell kernel with an output sample type TO of its own.
+//           A block's value is the sum before its >> 8, S = WSrc * src + sum of W_r * ref_r (0..65280), which is what the 16-bit arithmetic
+//           gives on samples shifted left by 8: (128 + 256 * S) >> 8 = S.  Loads, plan and lists are those of the 8-bit clip.
 #include "mvx_fps_shared.h"
 #include "mvx_degrain_n_weights.h"
 
@@ -142,7 +145,7 @@ typedef unsigned dn_v4 __attribute__((ext_vector_type(4), aligned(16)));
 // room for at least DN_K entries), and every later chunk before the rows of the one before it are used, so a visit is two dependent round
 // trips (list -> rows) whatever the length of the list.  An entry slot past the list's end repeats the chunk's first entry with weight 0, so
 // every load goes to an address that a listed reference owns.
-template <typename T, int W>
+template <typename T, int W, int ROUND = 128>
 __device__ __forceinline__ void dn_block_sum(DG_GL const unsigned char *slot, const unsigned long long *refB, long long rowOff, const int *s, int *sum) {
     const dn_v4 head = *(DG_GL const dn_v4 *)slot;
     dn_v4 ent[DN_K / 2];
@@ -150,7 +153,7 @@ __device__ __forceinline__ void dn_block_sum(DG_GL const unsigned char *slot, co
     for (int k = 0; k < DN_K / 2; k++) ent[k] = *(DG_GL const dn_v4 *)(slot + sizeof(DNHead) + 16 * k);
     const int wsrc = (int)head[0], count = (int)head[1]; // DNHead
 #pragma unroll
-    for (int i = 0; i < W; i++) sum[i] = 128 + s[i] * wsrc;
+    for (int i = 0; i < W; i++) sum[i] = ROUND + s[i] * wsrc;
     for (int e = 0; e < count; e += DN_K) {
         unsigned off[DN_K], wr[DN_K]; // DNEntry: offset, weight | reference << 16
 #pragma unroll
@@ -178,11 +181,17 @@ __device__ __forceinline__ void dn_block_sum(DG_GL const unsigned char *slot, co
 
 // One thread per row of a cell: W consecutive samples starting at a multiple of W, where W divides the block width and the block step, so
 // that the same blocks cover all of them (blocks side by side: one block).  256 threads = 32 cells x 8 rows of one plane of one job.
-template <typename T, int W>
+// TO: the sample type of the output planes.  TO = T is the reference's filter.  T 8-bit and TO 16-bit is out16: a block's value is its sum S
+// without rounding term and shift, the accumulator of the overlap keeps all its 32 bits (S * win <= 65280 * 2048 < 2^31, and the <= 4 terms
+// of a sample, whose window weights total 2047..2049, add up to <= 65280 * 2049 / 64 < 2^21), the clamp is at 65535, and the source enters
+// the limits and the samples that are passed through as s << 8.
+template <typename T, typename TO, int W>
 __global__ __launch_bounds__(256) void dn_cell_kernel(const DNParams *Pp, const DNJob *jobs, const unsigned char *const *refs, const unsigned char *plan, int planeFirst, int planesPerFrame) {
     const DNParams &P = *Pp;
     const int z = blockIdx.z, f = z / planesPerFrame, p = planeFirst + z % planesPerFrame;
     const PlaneG &g = P.pl[p];
+    constexpr bool OUT16 = sizeof(TO) > sizeof(T);
+    constexpr int UP = OUT16 ? 8 : 0; // source sample -> output scale
     __shared__ unsigned long long refB[DN_MAX_REFS];
     if ((int)threadIdx.x < P.nRefs) refB[threadIdx.x] = (unsigned long long)refs[((size_t)f * P.nRefs + threadIdx.x) * 3 + p];
     __syncthreads();
@@ -191,7 +200,7 @@ __global__ __launch_bounds__(256) void dn_cell_kernel(const DNParams *Pp, const 
     if (x0 >= g.W || y >= g.H) return;
     const DNJob &J = jobs[f];
     const unsigned char *srow = J.src[p] + (long long)y * g.srcPitch + (long long)x0 * sizeof(T);
-    unsigned char *drow = J.dst[p] + (long long)y * g.dstPitch + (long long)x0 * sizeof(T);
+    unsigned char *drow = J.dst[p] + (long long)y * g.dstPitch + (long long)x0 * sizeof(TO);
     const bool fullW = x0 + W <= g.W;
     int s[W];
     if (fullW) {
@@ -204,20 +213,20 @@ __global__ __launch_bounds__(256) void dn_cell_kernel(const DNParams *Pp, const 
     }
     int out[W];
 #pragma unroll
-    for (int i = 0; i < W; i++) out[i] = s[i];
+    for (int i = 0; i < W; i++) out[i] = s[i] << UP;
     // MVDegrains.cpp:211-214,238-249,290-298: a plane that is not processed and the strips no block covers keep the source.  The covered
     // width is a multiple of W, so a cell that starts inside it lies inside it (and inside the frame)
     if (g.process && x0 < g.WB && y < g.HB) {
         DG_GL const unsigned char *pl = dg_gl(plan + ((size_t)f * 2 + (p ? 1 : 0)) * P.nBlk * P.recBytes);
-        const int pm = (1 << P.bits) - 1;
+        const int pm = OUT16 ? 65535 : (1 << P.bits) - 1;
         int sum[W];
         if (!P.overlap) { // MVDegrains.cpp:238-249: Degrain_C straight into the frame
             const int bx = x0 / g.blkW, by = y / g.blkH;
             const int px = x0 - bx * g.blkW, py = y - by * g.blkH;
             DG_GL const unsigned char *slot = pl + (size_t)(by * P.nBlkX + bx) * P.recBytes;
-            dn_block_sum<T, W>(slot, refB, (long long)py * g.supPitch + (long long)px * sizeof(T), s, sum);
+            dn_block_sum<T, W, OUT16 ? 0 : 128>(slot, refB, (long long)py * g.supPitch + (long long)px * sizeof(T), s, sum);
 #pragma unroll
-            for (int i = 0; i < W; i++) out[i] = (T)(sum[i] >> 8);
+            for (int i = 0; i < W; i++) out[i] = OUT16 ? sum[i] : (int)(T)(sum[i] >> 8);
         } else {
             // blocks covering this cell: bx in [bx0, bx1], by in [by0, by1]
             int bx1 = x0 / g.stepX; if (bx1 > P.nBlkX - 1) bx1 = P.nBlkX - 1;
@@ -236,10 +245,10 @@ __global__ __launch_bounds__(256) void dn_cell_kernel(const DNParams *Pp, const 
                     const int wbx = bx == P.nBlkX - 1 ? 2 : (bx == 0 ? 0 : 1); // :260-262,285
                     DG_GL const unsigned char *slot = pl + (size_t)(by * P.nBlkX + bx) * P.recBytes;
                     const DnRaw<W * 2> wr = dn_load_raw<W * 2>(dg_gl((const unsigned char *)(win + (wby + wbx) * g.blkW * g.blkH + py * g.blkW + px)));
-                    dn_block_sum<T, W>(slot, refB, (long long)py * g.supPitch + (long long)px * sizeof(T), s, sum);
+                    dn_block_sum<T, W, OUT16 ? 0 : 128>(slot, refB, (long long)py * g.supPitch + (long long)px * sizeof(T), s, sum);
 #pragma unroll
                     for (int i = 0; i < W; i++) { // overlaps_c, Overlap.cpp:143-158
-                        const int val = (T)(sum[i] >> 8);
+                        const int val = OUT16 ? sum[i] : (int)(T)(sum[i] >> 8);
                         acc[i] += (unsigned)((val * dn_sample<unsigned short>(wr, i)) >> 6);
                     }
                 }
@@ -247,7 +256,7 @@ __global__ __launch_bounds__(256) void dn_cell_kernel(const DNParams *Pp, const 
 #pragma unroll
             for (int i = 0; i < W; i++) {
                 unsigned a0 = acc[i];
-                if (sizeof(T) == 1) a0 &= 0xffffu; // 16-bit accumulator of the 8-bit path (Overlap.cpp:254-256)
+                if (sizeof(T) == 1 && !OUT16) a0 &= 0xffffu; // 16-bit accumulator of the 8-bit path (Overlap.cpp:254-256)
                 const int a = (int)((a0 + 16) >> 5); // ToPixels, Overlap.cpp:335-356
                 out[i] = a > pm ? pm : a;
             }
@@ -255,16 +264,16 @@ __global__ __launch_bounds__(256) void dn_cell_kernel(const DNParams *Pp, const 
         if (g.limit < pm) { // LimitChanges, MVDegrains.h:163-181
 #pragma unroll
             for (int i = 0; i < W; i++) {
-                const int lo = s[i] - g.limit, hi = s[i] + g.limit;
+                const int lo = (s[i] << UP) - g.limit, hi = (s[i] << UP) + g.limit;
                 out[i] = out[i] < lo ? lo : out[i];
                 out[i] = out[i] > hi ? hi : out[i];
             }
         }
     }
-    if (fullW) dn_store<T, W>(dg_glw(drow), out);
+    if (fullW) dn_store<TO, W>(dg_glw(drow), out);
     else {
 #pragma unroll
-        for (int i = 0; i < W; i++) if (x0 + i < g.W) ((T *)drow)[i] = (T)out[i];
+        for (int i = 0; i < W; i++) if (x0 + i < g.W) ((TO *)drow)[i] = (TO)out[i];
     }
 }
 
@@ -280,6 +289,7 @@ struct mvx_degrain_n {
     DevBuf<unsigned char> dPlan;
     DevBuf<int16_t> dWin[2];
     int nWinClasses = 1;
+    bool out16 = false;              // 8-bit clip, 16-bit output planes
 };
 
 // the scaled thresholds of one plane class over the distances; 0, or which argument reaches INT_MAX (MVDegrains.cpp:660-661): 1 the near
@@ -291,8 +301,8 @@ static int dn_thresholds(int64_t t1, int64_t t2, int radius, int64_t nSCD1, int6
     return 0;
 }
 
-extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_create(const mvx_degrain_n_args *a, const mvx_analysis_data *ad, const mvx_super *sup, const ptrdiff_t src_pitch[3],
-                                    const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_degrain_n **out, char *err) {
+static int dn_create(const mvx_degrain_n_args *a, const mvx_analysis_data *ad, const mvx_super *sup, const ptrdiff_t src_pitch[3], const ptrdiff_t super_pitch[3],
+                     const ptrdiff_t dst_pitch[3], bool out16, mvx_degrain_n **out, char *err) {
     MVX_CREATE_BEGIN(out);
     const mvx_super_info &si = sup->info;
     const int radius = a->radius;
@@ -316,7 +326,8 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_create(const
                  (long long)(2147483647LL * nSCD1_old / nSCD1));
     }
     if (!mvx_super_fits(ad, si, true)) MVX_FAIL("%s: wrong source or super clip frame size.", name);
-    const int pixelMax = (1 << si.bits) - 1;
+    if (out16 && si.bits != 8) MVX_FAIL("%s: out16 needs an 8 bit clip.", name);
+    const int pixelMax = out16 ? 65535 : (1 << si.bits) - 1; // the limits are in units of the output
     const int limit = a->limit == MVX_UNSET ? pixelMax : a->limit;
     const int limitc = a->limitc == MVX_UNSET ? limit : a->limitc;
     if (limit < 0 || limit > pixelMax) MVX_FAIL("%s: limit must be between 0 and %d (inclusive).", name, pixelMax);
@@ -327,6 +338,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_create(const
 
     mvx_degrain_n *h = new mvx_degrain_n();
     h->info = info;
+    h->out16 = out16;
     DNParams &P = h->P;
     memset(&P, 0, sizeof(P));
     P.nRefs = 2 * radius; P.recBytes = dn_rec_bytes(P.nRefs);
@@ -346,6 +358,16 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_create(const
     *out = h;
     return MVX_OK;
 }
+
+extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_create(const mvx_degrain_n_args *a, const mvx_analysis_data *ad, const mvx_super *sup, const ptrdiff_t src_pitch[3],
+                                    const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_degrain_n **out, char *err) {
+    return dn_create(a, ad, sup, src_pitch, super_pitch, dst_pitch, false, out, err);
+}
+extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_create_out16(const mvx_degrain_n_args *a, const mvx_analysis_data *ad, const mvx_super *sup, const ptrdiff_t src_pitch[3],
+                                    const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_degrain_n **out, char *err) {
+    return dn_create(a, ad, sup, src_pitch, super_pitch, dst_pitch, true, out, err);
+}
+extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_out_bits(const mvx_degrain_n *d) { return d->out16 ? 16 : d->P.bits; }
 
 extern "C" __attribute__((visibility("default"))) void mvx_degrain_n_get_info(const mvx_degrain_n *d, mvx_degrain_n_info *info) { *info = d->info; }
 extern "C" __attribute__((visibility("default"))) void mvx_degrain_n_destroy(mvx_degrain_n *d) { delete d; }
@@ -374,8 +396,8 @@ static int dn_cell_width(const PlaneG &g) {
     return w;
 }
 
-template <typename T> static void dn_launch_cells(int W, dim3 grid, hipStream_t st, const DNParams *dP, const DNJob *dJ, const unsigned char *const *dRefs, const unsigned char *plan, int p0, int npl) {
-#define DNC(N) hipLaunchKernelGGL((dn_cell_kernel<T, N>), grid, dim3(256), 0, st, dP, dJ, dRefs, plan, p0, npl)
+template <typename T, typename TO> static void dn_launch_cells(int W, dim3 grid, hipStream_t st, const DNParams *dP, const DNJob *dJ, const unsigned char *const *dRefs, const unsigned char *plan, int p0, int npl) {
+#define DNC(N) hipLaunchKernelGGL((dn_cell_kernel<T, TO, N>), grid, dim3(256), 0, st, dP, dJ, dRefs, plan, p0, npl)
     switch (W) { case 1: DNC(1); break; case 2: DNC(2); break; case 4: DNC(4); break; default: DNC(8); break; }
 #undef DNC
 }
@@ -412,8 +434,9 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_frames(mvx_d
     for (int cls = 0; cls < (P.nplanes > 1 ? 2 : 1); cls++) { // one launch for the luma planes of all jobs, one for both chroma planes
         const int p0 = cls, npl = cls ? 2 : 1, W = dn_cell_width(P.pl[p0]);
         const dim3 grid(((P.pl[p0].W + W - 1) / W + 31) / 32, (P.pl[p0].H + 7) / 8, nframes * npl);
-        if (P.bps == 1) dn_launch_cells<uint8_t>(W, grid, st, d->dP.p, dJ, dRefs, d->dPlan.p, p0, npl);
-        else dn_launch_cells<uint16_t>(W, grid, st, d->dP.p, dJ, dRefs, d->dPlan.p, p0, npl);
+        if (d->out16) dn_launch_cells<uint8_t, uint16_t>(W, grid, st, d->dP.p, dJ, dRefs, d->dPlan.p, p0, npl);
+        else if (P.bps == 1) dn_launch_cells<uint8_t, uint8_t>(W, grid, st, d->dP.p, dJ, dRefs, d->dPlan.p, p0, npl);
+        else dn_launch_cells<uint16_t, uint16_t>(W, grid, st, d->dP.p, dJ, dRefs, d->dPlan.p, p0, npl);
     }
     HIP_CHECK(hipGetLastError());
     return MVX_OK;

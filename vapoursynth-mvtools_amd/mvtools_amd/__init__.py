@@ -299,6 +299,8 @@ def lib():
         L.mvx_degrain_frames.argtypes = [C.c_void_p, C.c_int, P(DegrainJob), C.c_void_p]
         L.mvx_degrain_n_create.argtypes = [P(DegrainNArgs), P(AnalysisData), C.c_void_p, P(C.c_ssize_t), P(C.c_ssize_t), P(C.c_ssize_t),
                                            P(C.c_void_p), C.c_char_p]
+        L.mvx_degrain_n_create_out16.argtypes = L.mvx_degrain_n_create.argtypes
+        L.mvx_degrain_n_out_bits.argtypes = [C.c_void_p]
         L.mvx_degrain_n_get_info.argtypes = [C.c_void_p, P(DegrainNInfo)]
         L.mvx_degrain_n_get_info.restype = None
         L.mvx_degrain_n_destroy.argtypes = [C.c_void_p]
@@ -763,19 +765,25 @@ class Degrain:
 class DegrainN:
     """Degrain at a temporal radius of 1..24 (include/mvtools_amd.h, mv.DegrainN): the reference's templates over the radius (MVDegrains.h:30-53,184-223)
     read at any radius, each reference weighed against the threshold of its temporal distance -- thsad at distance 1 falling to thsad2 at distance
-    `radius` (thsad2 / thsadc2 None: no fall-off).  analysis_data = the vector clips' MVTools_MVAnalysisData."""
+    `radius` (thsad2 / thsadc2 None: no fall-off).  analysis_data = the vector clips' MVTools_MVAnalysisData.
+    out16: an 8-bit clip (8-bit super clip and vectors, thresholds in 8-bit units) written as 16-bit planes -- a block's weighted sum before its
+    >> 8, see mvx_degrain_n_create_out16; limit / limitc are then 0..65535, and dst_pitch defaults to rows of 16-bit samples rounded up to 256 bytes."""
 
     def __init__(self, radius, sup, analysis_data, src_pitch, dst_pitch=None, thsad=None, thsadc=None, thsad2=None, thsadc2=None, plane=None, limit=None,
-                 limitc=None, thscd1=None, thscd2=None):
+                 limitc=None, thscd1=None, thscd2=None, out16=False):
         self.sup = sup
         self.radius = radius
+        self.out16 = bool(out16)
         a = DegrainNArgs(radius, _u(thsad), _u(thsadc), _u(thsad2), _u(thsadc2), _u(plane), _u(limit), _u(limitc), _u(thscd1), _u(thscd2))
         ad = AnalysisData.from_buffer_copy(bytes(analysis_data))
+        if self.out16:
+            dst_pitch = dst_pitch or [(sup.info.plane_width[p] * 2 + 255) // 256 * 256 for p in range(len(src_pitch))]
         dst_pitch = dst_pitch or src_pitch
         pad = lambda l: (C.c_ssize_t * 3)(*(list(l) + [0] * (3 - len(l))))
         self.h = C.c_void_p()
         err = C.create_string_buffer(ERRLEN)
-        _check(lib().mvx_degrain_n_create(C.byref(a), C.byref(ad), sup.h, pad(src_pitch), pad(sup.pitch), pad(dst_pitch), C.byref(self.h), err), err)
+        create = lib().mvx_degrain_n_create_out16 if self.out16 else lib().mvx_degrain_n_create
+        _check(create(C.byref(a), C.byref(ad), sup.h, pad(src_pitch), pad(sup.pitch), pad(dst_pitch), C.byref(self.h), err), err)
         self.src_pitch, self.dst_pitch = list(src_pitch), list(dst_pitch)
 
     def __del__(self):
@@ -784,6 +792,11 @@ class DegrainN:
                 lib().mvx_degrain_n_destroy(self.h)
         except Exception:
             pass
+
+    @property
+    def out_bits(self):
+        """bits per sample of the planes run() writes: 16 with out16, else the clip's depth"""
+        return lib().mvx_degrain_n_out_bits(self.h)
 
     def info(self):
         """what creation resolved: dict(radius, nrefs, thsad_d, thsadc_d) -- the thresholds per distance 1..radius after the block-size scaling"""
@@ -795,6 +808,8 @@ class DegrainN:
         """jobs: list of (src_frame, [ref_super or None]*2r, [blob]*2r) ordered mvbw, mvfw, mvbw2, mvfw2, ..."""
         torch = _torch()
         n, nr = len(jobs), 2 * self.radius
+        if out is None and self.out16:
+            out = [[torch.empty((p.shape[0], self.dst_pitch[i]), dtype=torch.uint8, device=p.device) for i, p in enumerate(j[0])] for j in jobs]
         if out is None:
             out = [[torch.empty_like(p) for p in j[0]] for j in jobs]
         arr = (DegrainNJob * n)()
