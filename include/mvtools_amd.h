@@ -312,6 +312,72 @@ typedef struct mvx_compensate_job {
 
 int mvx_compensate_frames(mvx_compensate *c, int nframes, const mvx_compensate_job *jobs, void *stream);
 
+/* ---- the multi blob, mv.AnalyseN and mv.CompensateN: one source frame against a temporal radius ------
+ * No reference counterpart: pinterf's MAnalyse(multi=true, delta=tr) / MCompensate(tr=...) and mvtools-sf's Analyze(radius=...) /
+ * Compensate(tr=...) are the models.  Nothing new is computed: every field is one mvx_analyse_frames result and every compensated frame
+ * one mvx_compensate_frames result, byte for byte.
+ *
+ * The multi blob: ONE device buffer per source frame with 2 * radius fields.  Field r has isb = (r % 2 == 0) and delta = r / 2 + 1 --
+ * mvbw1, mvfw1, mvbw2, mvfw2, ..., the order of mvx_degrain_n_job -- and starts at byte r * field_stride, where field_stride is
+ * mvx_analyse_blob_size rounded up to 256.  Each field is a complete MVTools_vectors blob: blob + r * field_stride can be handed to any
+ * consumer of this header unchanged.  The bytes between a field's end and the next field are never written. */
+
+typedef struct mvx_analyse_n mvx_analyse_n;
+
+/* radius 1..MVX_DEGRAIN_N_MAX_RADIUS ("AnalyseN: radius must be between 1 and 24."); args->isb and args->delta must be MVX_UNSET ("AnalyseN:
+ * isb and delta are set by the radius."); every other message is mvx_analyse_create's with the name AnalyseN, in the same order, and
+ * dct 1..4 stay behind mvx_enable_dct_float.  Touches no device. */
+int mvx_analyse_n_create(const mvx_analyse_args *args, int radius, const mvx_super *super_clip, int num_frames,
+                         const ptrdiff_t super_pitch[3], mvx_analyse_n **out, char *err);
+void mvx_analyse_n_destroy(mvx_analyse_n *a);
+/* the MVTools_MVAnalysisData of field r: what an mvx_analyse created with that field's isb and delta reports; MVX_E_ARG for r outside 0..2 * radius - 1 */
+int mvx_analyse_n_get_data(const mvx_analyse_n *a, int r, mvx_analysis_data *out);
+size_t mvx_analyse_n_field_size(const mvx_analyse_n *a);   /* bytes of one field: mvx_analyse_blob_size */
+size_t mvx_analyse_n_field_stride(const mvx_analyse_n *a); /* field_size rounded up to 256 */
+size_t mvx_analyse_n_blob_size(const mvx_analyse_n *a);   /* 2 * radius * field_stride */
+int mvx_analyse_n_set_ref_shadow(mvx_analyse_n *a, const ptrdiff_t copy_stride[3]); /* as mvx_analyse_set_ref_shadow */
+
+typedef struct mvx_analyse_n_job {
+    const void *src[3];              /* super frame n (device) */
+    const void *const (*refs)[3];    /* HOST array of 2 * radius entries: super frame n+1, n-1, n+2, n-2, ...; refs[r][0] NULL = that frame is
+                                        outside the clip: field r is the invalid blob mvx_analyse_frames writes for a NULL reference */
+    void *blob;                      /* device, mvx_analyse_n_blob_size() bytes, 16-byte aligned */
+    const int32_t *field_shift;      /* HOST array of 2 * radius values (mvx_analyse_job.field_shift per field), or NULL: field_shift_all everywhere */
+    int32_t field_shift_all;
+    int32_t reserved;
+} mvx_analyse_n_job;
+
+/* All 2 * radius * njobs searches of the call go to the device as ONE mvx_analyse_frames batch (the search picks its launch form from the
+ * number of chains in a launch).  `jobs` and the arrays behind refs and field_shift are HOST arrays, read before the call returns. */
+int mvx_analyse_n_frames(mvx_analyse_n *a, int njobs, const mvx_analyse_n_job *jobs, void *stream);
+
+typedef struct mvx_compensate_n mvx_compensate_n;
+
+/* tr 1..MVX_DEGRAIN_N_MAX_RADIUS ("CompensateN: tr must be between 1 and 24."); then mvx_compensate_create's messages with the name
+ * CompensateN, in the same order; fields = 1 is refused last with "CompensateN: fields is not supported.".  vectors_data: of field 0
+ * (every field shares its geometry).  Touches no device. */
+int mvx_compensate_n_create(const mvx_compensate_args *args, int tr, const mvx_analysis_data *vectors_data /* of field 0 */,
+                            const mvx_super *super_clip, const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3],
+                            mvx_compensate_n **out, char *err);
+void mvx_compensate_n_destroy(mvx_compensate_n *c);
+/* output k (0..2 * tr) of a job in temporal order: *offset = k - tr (the frame n + offset), *field = the field of the multi blob that
+ * compensates it -- mvfw of distance tr - k before the centre, mvbw of distance k - tr behind it --, -1 for the centre.  MVX_E_ARG for k outside. */
+int mvx_compensate_n_map(const mvx_compensate_n *c, int k, int *offset, int *field);
+
+typedef struct mvx_compensate_n_job {
+    const void *src_super[3];        /* super frame n */
+    const void *const (*refs)[3];    /* HOST array of 2 * tr entries in the order of mvx_analyse_n_job; refs[r][0] NULL = outside the clip */
+    const void *blob;                /* the multi blob of frame n (device) */
+    size_t field_stride;             /* mvx_analyse_n_field_stride of the object that wrote it */
+    void *const (*dst)[3];           /* HOST array of 2 * tr + 1 frames, output k in temporal order */
+} mvx_compensate_n_job;
+
+/* Output k != tr is byte for byte what mvx_compensate_frames writes for (src_super, refs[field], blob + field * field_stride) with the same
+ * scbehavior, thsad, time, thscd1 and thscd2 -- a reference outside the clip and a scene change per scbehavior included.  Output tr is the
+ * source: the unpadded pel-0 window of the finest level of src_super, copied.  One usable pass and one plan pass over all fields of all
+ * jobs, then one output kernel per plane class whose grid covers the 2 * tr + 1 planes of every job (csrc/mvx_compensate_n.hip). */
+int mvx_compensate_n_frames(mvx_compensate_n *c, int njobs, const mvx_compensate_n_job *jobs, void *stream);
+
 /* ---- mv.BlockFPS ---------------------------------------------------------------------------------
  * replaces mvblockfpsCreate / mvblockfpsGetFrame, MVBlockFPS.c:741-1014 / :229-676 (arg string :1017-1033);
  * masks MaskFun.cpp:63-166, mask upsizer SimpleResize.cpp:27-121.                                     */

@@ -1,4 +1,4 @@
-// mvx_api.hip -- device/runtime helpers of the C ABI (no pixel work here).
+// mvx_api.hip -- device/runtime helpers of the C ABI, and mv.AnalyseN, which is host code over mvx_analyse_* (no pixel work here).
 #include "mvx_common.h"
 
 extern "C" __attribute__((visibility("default"))) const char *mvx_version(void) { return "mvtools_amd 0.1 (gfx950; mvtools v24 hot path)"; }
@@ -288,3 +288,78 @@ extern "C" __attribute__((visibility("default"))) int mvx_dev_memset(void *dev, 
 }
 
 extern "C" __attribute__((visibility("default"))) int mvx_stream_sync(void *stream) { HIP_CHECK(hipStreamSynchronize((hipStream_t)stream)); return MVX_OK; }
+
+// ================================================================================================ mv.AnalyseN
+// One source frame against a temporal radius (mvtools_amd.h, "the multi blob").  A field's isb and delta reach neither the search's parameter
+// block nor a byte of its blob -- they only label the MVTools_MVAnalysisData -- so ONE mvx_analyse serves every field, and a call is one
+// mvx_analyse_frames batch of 2 * radius * njobs chains: the search kernels, their launch choice and their build are untouched.
+struct mvx_analyse_n {
+    mvx_analyse *an = nullptr;
+    int radius = 0;
+    size_t stride = 0;
+    mvx_analysis_data ad;      // of field 0 (isb = 1, delta = 1)
+};
+#define MVX_MOTION_IS_BACKWARD 2
+
+extern "C" __attribute__((visibility("default"))) int mvx_analyse_n_create(const mvx_analyse_args *a, int radius, const mvx_super *sup, int num_frames,
+                                                                           const ptrdiff_t super_pitch[3], mvx_analyse_n **out, char *err) {
+    MVX_CREATE_BEGIN(out);
+    if (radius < 1 || radius > MVX_DEGRAIN_N_MAX_RADIUS) MVX_FAIL("AnalyseN: radius must be between 1 and %d.", MVX_DEGRAIN_N_MAX_RADIUS);
+    if (a->isb != MVX_UNSET || a->delta != MVX_UNSET) MVX_FAIL("AnalyseN: isb and delta are set by the radius.");
+    mvx_analyse_args args = *a;
+    args.isb = 1; args.delta = 1;
+    mvx_analyse *an = nullptr;
+    char msg[MVX_ERRLEN];
+    if (int rc = mvx_analyse_create(&args, sup, num_frames, super_pitch, &an, msg)) {
+        // mvx_analyse_create's message under this filter's name (the library's own messages carry no name and pass as they are)
+        if (!strncmp(msg, "Analyse:", 8)) snprintf(err, MVX_ERRLEN, "AnalyseN:%s", msg + 8);
+        else snprintf(err, MVX_ERRLEN, "%s", msg);
+        mvx_set_error("%s", err);
+        return rc;
+    }
+    mvx_analyse_n *h = new mvx_analyse_n();
+    h->an = an;
+    h->radius = radius;
+    h->stride = ((size_t)mvx_analyse_blob_size(an) + 255) / 256 * 256;
+    mvx_analyse_get_data(an, &h->ad);
+    *out = h;
+    return MVX_OK;
+}
+extern "C" __attribute__((visibility("default"))) void mvx_analyse_n_destroy(mvx_analyse_n *a) {
+    if (!a) return;
+    mvx_analyse_destroy(a->an);
+    delete a;
+}
+extern "C" __attribute__((visibility("default"))) int mvx_analyse_n_get_data(const mvx_analyse_n *a, int r, mvx_analysis_data *out) {
+    if (r < 0 || r >= 2 * a->radius) { mvx_set_error("mvx_analyse_n_get_data: field %d of %d", r, 2 * a->radius); return MVX_E_ARG; }
+    *out = a->ad;
+    out->isBackward = r % 2 == 0;
+    out->nDeltaFrame = r / 2 + 1;
+    out->nMotionFlags = (a->ad.nMotionFlags & ~MVX_MOTION_IS_BACKWARD) | (out->isBackward ? MVX_MOTION_IS_BACKWARD : 0); // MVAnalyse.c:489
+    return MVX_OK;
+}
+extern "C" __attribute__((visibility("default"))) size_t mvx_analyse_n_field_size(const mvx_analyse_n *a) { return (size_t)mvx_analyse_blob_size(a->an); }
+extern "C" __attribute__((visibility("default"))) size_t mvx_analyse_n_field_stride(const mvx_analyse_n *a) { return a->stride; }
+extern "C" __attribute__((visibility("default"))) size_t mvx_analyse_n_blob_size(const mvx_analyse_n *a) { return 2 * (size_t)a->radius * a->stride; }
+extern "C" __attribute__((visibility("default"))) int mvx_analyse_n_set_ref_shadow(mvx_analyse_n *a, const ptrdiff_t copy_stride[3]) {
+    return mvx_analyse_set_ref_shadow(a->an, copy_stride);
+}
+
+extern "C" __attribute__((visibility("default"))) int mvx_analyse_n_frames(mvx_analyse_n *a, int njobs, const mvx_analyse_n_job *jobs, void *stream) {
+    if (njobs <= 0) return MVX_OK;
+    const int nf = 2 * a->radius;
+    std::vector<mvx_analyse_job> all((size_t)njobs * nf);
+    for (int j = 0; j < njobs; j++) {
+        const mvx_analyse_n_job &J = jobs[j];
+        if (!J.refs || !J.blob) { mvx_set_error("mvx_analyse_n_frames: a job needs its reference table and its blob"); return MVX_E_ARG; }
+        if (((uintptr_t)J.blob) & 15) { mvx_set_error("mvx_analyse_n_frames: blob must be 16-byte aligned"); return MVX_E_ARG; }
+        for (int r = 0; r < nf; r++) {
+            mvx_analyse_job &o = all[(size_t)j * nf + r];
+            for (int p = 0; p < 3; p++) { o.src[p] = J.src[p]; o.ref[p] = J.refs[r][0] ? J.refs[r][p] : nullptr; }
+            o.blob = (unsigned char *)J.blob + (size_t)r * a->stride;
+            o.field_shift = J.field_shift ? J.field_shift[r] : J.field_shift_all;
+            o.reserved = 0;
+        }
+    }
+    return mvx_analyse_frames(a->an, (int)all.size(), all.data(), stream);
+}

@@ -1,0 +1,324 @@
+// mvx_compensate_n.hip -- mv.CompensateN on gfx950: the frames n - tr .. n + tr compensated onto frame n from one multi blob
+// (mvtools_amd.h, "the multi blob"), in temporal order, the source in the middle.
+//
+// Every compensated output is one mv.Compensate result (MVCompensate.c:73-374 as mvx_degrain.hip restates it): fgopIsUsable per field, the
+// block origin from the vector scaled by time or the block's own place when its SAD reaches thsad, overlaps_c / ToPixels
+// (Overlap.cpp:143-158,335-356) in gather form, the uncovered strips and the scene-change fallback per scbehavior.  What this file adds is
+// the shape of the work: a job is 2 * tr fields and 2 * tr + 1 output frames, so
+//   usable  one launch over (field, job): 0, or the byte offset of level 0 inside the field's blob
+//   plan    one launch over (block, field x job): where the block comes from in the chosen super frame, luma and chroma
+//   output  one launch per plane class over (cell, row, plane x output x job): a thread produces one row of a cell of W samples -- W
+//           divides the block width and the block step, so the same <= 2 x 2 blocks cover all of them and each costs one vector load.
+//           Blocks side by side, the uncovered strips, an unusable field and the centre are a single load and store of the same cell.
+// Nothing is sized by tr at compile time: the tables (source planes, reference planes, field blobs, output planes) live in global memory,
+// and what a workgroup needs of them -- it serves ONE plane of ONE output -- is uniform, so it arrives in scalar registers.
+#include "mvx_fps_shared.h"
+
+// ------------------------------------------------------------------------------------------------ device structs
+
+struct CNParams {
+    int tr, nFields, nOut, nBlkX, nBlkY, nBlk, pel, logPel, bits, bps, nplanes, overlap;
+    int nLvCount;
+    int time256, scBehavior;
+    long long thSAD;
+    long long thscd1; int thscd2;
+    PlaneG pl[3];
+    const int16_t *win[3];
+};
+
+struct __attribute__((aligned(16))) CNRec { unsigned off[2]; int fromRef; int pad; }; // off[0] luma, off[1] chroma
+static_assert(sizeof(CNRec) == 16, "plan record layout");
+
+// the tables of a call, all in one device block: [job][plane] | [job][field][plane] | [job][field] | [job][output][plane]
+struct CNTables {
+    const unsigned char *const *src;
+    const unsigned char *const *refs;
+    const unsigned char *const *blobs;
+    unsigned char *const *dst;
+};
+
+// output k of a job -> the field that compensates it, -1 for the centre: mvfw (odd fields) of distance tr - k before it, mvbw (even fields) of
+// distance k - tr behind it
+__host__ __device__ __forceinline__ int cn_field(int tr, int k) { return k == tr ? -1 : k < tr ? 2 * (tr - k - 1) + 1 : 2 * (k - tr - 1); }
+
+// ------------------------------------------------------------------------------------------------ kernels
+
+// per (job, field): 0 when the field's vectors are not usable (fgopIsUsable, or a reference frame outside the clip), else the byte offset of
+// level 0 inside the field's blob
+__global__ __launch_bounds__(256) void cn_usable_kernel(const CNParams *Pp, CNTables T, unsigned *lv0) {
+    const CNParams &P = *Pp;
+    const int k = blockIdx.y * P.nFields + blockIdx.x;
+    const unsigned char *blob = T.blobs[k];
+    const bool ok = fps_block_usable(blob, T.refs[(size_t)k * 3] != nullptr, P.nLvCount, P.nBlk, P.thscd1, P.thscd2);
+    if (threadIdx.x == 0) lv0[k] = ok ? (unsigned)((const unsigned char *)mvx_level0(blob, P.nLvCount) - blob) : 0u;
+}
+
+// one thread per (job x field, block): compensate_plan_kernel's record (MVCompensate.c:238-247,286-295) without a field shift
+__global__ __launch_bounds__(256) void cn_plan_kernel(const CNParams *Pp, CNTables T, const unsigned *lv0, CNRec *plan) {
+    const CNParams &P = *Pp;
+    const int k = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const unsigned l0 = lv0[k];
+    if (i >= P.nBlk || !l0) return; // (the output kernel does not read the plan of a field that is not usable)
+    const int by = i / P.nBlkX, bx = i - by * P.nBlkX;
+    typedef unsigned pl_v4 __attribute__((ext_vector_type(4), aligned(4)));
+    const pl_v4 v = *(DG_GL const pl_v4 *)(dg_gl(T.blobs[k]) + l0 + (size_t)i * sizeof(GVecD));
+    const int vx = (int)v[0], vy = (int)v[1];
+    const long long sad = (long long)(((unsigned long long)v[3] << 32) | v[2]);
+    int blx = bx * P.pl[0].stepX * P.pel, bly = by * P.pl[0].stepY * P.pel;
+    CNRec rec;
+    rec.fromRef = sad < P.thSAD;
+    if (rec.fromRef) { blx += vx * P.time256 / 256; bly += vy * P.time256 / 256; }
+    rec.off[0] = sup_offset(P.pl[0], P.pel, P.logPel, P.bps, blx, bly);
+    rec.off[1] = P.nplanes > 1 ? sup_offset(P.pl[1], P.pel, P.logPel, P.bps, blx >> P.pl[1].subX, bly >> P.pl[1].subY) : 0;
+    rec.pad = 0;
+    plan[(size_t)k * P.nBlk + i] = rec;
+}
+
+// W samples of type T at an arbitrarily aligned address (dg_load / dg_store start at two bytes; a cell can be one 8-bit sample)
+template <typename T, int W> __device__ __forceinline__ void cn_load(DG_GL const unsigned char *p, int *o) {
+    if constexpr (W * sizeof(T) == 1) o[0] = *p; else dg_load<T, W>(p, o);
+}
+template <typename T, int W> __device__ __forceinline__ void cn_store(DG_GL unsigned char *p, const int *v) {
+    if constexpr (W * sizeof(T) == 1) *p = (unsigned char)v[0]; else dg_store<T, W>(p, v);
+}
+
+// One thread per row of a cell; 256 threads = 32 cells x 8 rows of one plane of one output of one job.  z = (job, output, plane of the class).
+template <typename T, int W>
+__global__ __launch_bounds__(256) void cn_cell_kernel(const CNParams *Pp, CNTables Tb, const unsigned *lv0, const CNRec *plan, int planeFirst, int planesPerFrame) {
+    const CNParams &P = *Pp;
+    const int z = blockIdx.z, p = planeFirst + z % planesPerFrame, zo = z / planesPerFrame;
+    const int k = zo % P.nOut, f = zo / P.nOut;
+    const PlaneG &g = P.pl[p];
+    const int c = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
+    const int x0 = c * W;
+    if (x0 >= g.W || y >= g.H) return;
+    // uniform over the workgroup
+    const int field = cn_field(P.tr, k);
+    const unsigned char *srcSup = Tb.src[(size_t)f * 3 + p];
+    const unsigned char *refSup = field >= 0 ? Tb.refs[((size_t)f * P.nFields + field) * 3 + p] : nullptr;
+    const bool usable = field >= 0 && lv0[f * P.nFields + field] != 0u;
+    unsigned char *drow = Tb.dst[((size_t)f * P.nOut + k) * 3 + p] + (long long)y * g.dstPitch + (long long)x0 * (long long)sizeof(T);
+    // interior (pel plane 0) sample of a super frame
+    const long long inner = (long long)(g.vpadPel / P.pel + y) * g.supPitch + (long long)(g.hpadPel / P.pel + x0) * (long long)sizeof(T);
+    const bool covered = x0 < g.WB && y < g.HB; // (the covered width is a multiple of W: a cell that starts inside it lies inside it, and inside the frame)
+    int out[W];
+    const unsigned char *sp = nullptr; // where a cell that is a plain copy comes from
+    if (field < 0) sp = srcSup + inner;                                                         // the centre: the source
+    else if (!usable) sp = ((!P.scBehavior && refSup) ? refSup : srcSup) + inner;               // MVCompensate.c:348-364
+    else if (!covered) sp = (P.scBehavior ? srcSup : refSup) + inner;                           // :319-342
+    else if (!P.overlap) {                                                                      // :227-258: plain block copies (block sizes are powers of two)
+        const int lbw = __ffs(g.blkW) - 1, lbh = __ffs(g.blkH) - 1;
+        const int bx = x0 >> lbw, by = y >> lbh, px = x0 & (g.blkW - 1), py = y & (g.blkH - 1);
+        const dg_iv4 R = *(DG_GL const dg_iv4 *)dg_gl(plan + ((size_t)f * P.nFields + field) * P.nBlk + by * P.nBlkX + bx);
+        sp = (R[2] ? refSup : srcSup) + (unsigned)R[p ? 1 : 0] + (long long)py * g.supPitch + (long long)px * (long long)sizeof(T);
+    }
+    if (sp) {
+        if (x0 + W <= g.W) {
+            cn_load<T, W>(dg_gl(sp), out);
+            cn_store<T, W>(dg_glw(drow), out);
+        } else {
+#pragma unroll
+            for (int i = 0; i < W; i++) if (x0 + i < g.W) ((T *)drow)[i] = ((const T *)sp)[i];
+        }
+        return;
+    }
+    // overlapped blocks (:260-317): the blocks bx0..bx1 x by0..by1 cover the cell, at most two each way (the overlap is at most half a block).
+    // All four slots are loaded -- one that does not exist repeats the first and adds nothing -- so that the four plan records, and then the
+    // four rows and window rows, are in flight together.
+    int bx1 = x0 / g.stepX; if (bx1 > P.nBlkX - 1) bx1 = P.nBlkX - 1;
+    const int bx0 = x0 - g.blkW + 1 <= 0 ? 0 : (x0 - g.blkW + g.stepX) / g.stepX;
+    int by1 = y / g.stepY; if (by1 > P.nBlkY - 1) by1 = P.nBlkY - 1;
+    const int by0 = y - g.blkH + 1 <= 0 ? 0 : (y - g.blkH + g.stepY) / g.stepY;
+    DG_GL const unsigned char *pl = dg_gl(plan + ((size_t)f * P.nFields + field) * P.nBlk);
+    DG_GL const unsigned char *win = dg_gl(P.win[p]);
+    bool have[4];
+    dg_iv4 R[4];
+    int px[4], py[4], wsel[4];
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const int by = by0 + (s >> 1), bx = bx0 + (s & 1);
+        have[s] = by <= by1 && bx <= bx1;
+        const int byc = have[s] ? by : by0, bxc = have[s] ? bx : bx0;
+        R[s] = *(DG_GL const dg_iv4 *)(pl + (size_t)(byc * P.nBlkX + bxc) * sizeof(CNRec));
+        px[s] = x0 - bxc * g.stepX; py[s] = y - byc * g.stepY; // 0 <= px <= blkW - W
+        const int wby = byc == 0 ? 0 : (byc == P.nBlkY - 1 ? 6 : 3); // ((by + nBlkY - 3) / (nBlkY - 2)) * 3, MVCompensate.c:263
+        const int wbx = bxc == P.nBlkX - 1 ? 2 : (bxc == 0 ? 0 : 1); // :267-269,297
+        wsel[s] = (wby + wbx) * g.blkW * g.blkH + py[s] * g.blkW + px[s];
+    }
+    int val[4][W], wv[4][W];
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const unsigned char *base = (R[s][2] ? refSup : srcSup) + (unsigned)R[s][p ? 1 : 0] + (long long)py[s] * g.supPitch + (long long)px[s] * (long long)sizeof(T);
+        cn_load<T, W>(dg_gl(base), val[s]);
+        cn_load<unsigned short, W>(win + (size_t)wsel[s] * 2, wv[s]);
+    }
+    const int pm = (1 << P.bits) - 1;
+#pragma unroll
+    for (int i = 0; i < W; i++) {
+        unsigned acc = 0;
+#pragma unroll
+        for (int s = 0; s < 4; s++) acc += have[s] ? (unsigned)((val[s][i] * wv[s][i]) >> 6) : 0u; // overlaps_c, Overlap.cpp:143-158
+        if (sizeof(T) == 1) acc &= 0xffffu; // 16-bit accumulator of the 8-bit path (Overlap.cpp:254-256)
+        const int a = (int)((acc + 16) >> 5); // ToPixels, Overlap.cpp:335-356
+        out[i] = a > pm ? pm : a;
+    }
+    cn_store<T, W>(dg_glw(drow), out);
+}
+
+// ------------------------------------------------------------------------------------------------ host object
+
+struct mvx_compensate_n {
+    CallGuard guard;
+    CNParams P;
+    int minStride = 0;               // bytes of a field's blob
+    DevBuf<CNParams> dP;
+    DevBuf<unsigned char> dTables;   // per call: see CNTables
+    DevBuf<unsigned> dLv0;
+    DevBuf<CNRec> dPlan;
+    DevBuf<int16_t> dWin[2];
+    int nWinClasses = 1;
+};
+
+// MVCompensate.c:419-575 mvcompensateCreate under the name CompensateN
+extern "C" __attribute__((visibility("default"))) int mvx_compensate_n_create(const mvx_compensate_args *a, int tr, const mvx_analysis_data *ad, const mvx_super *sup,
+                                                                              const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_compensate_n **out, char *err) {
+    MVX_CREATE_BEGIN(out);
+    const mvx_super_info &si = sup->info;
+    const char *name = "CompensateN";
+    if (tr < 1 || tr > MVX_DEGRAIN_N_MAX_RADIUS) MVX_FAIL("%s: tr must be between 1 and %d.", name, MVX_DEGRAIN_N_MAX_RADIUS);
+    const int scBehavior = a->scbehavior == MVX_UNSET ? 1 : !!a->scbehavior;
+    long long thSAD = a->thsad == MVX_UNSET ? 10000 : a->thsad;
+    const double time = a->time;
+    if (time < 0.0 || time > 100.0) MVX_FAIL("%s: time must be between 0.0 and 100.0 (inclusive).", name);
+    int64_t nSCD1, nSCD1_old; int32_t nSCD2;
+    if (int rc = mvx_resolve_thscd(name, a->thscd1, a->thscd2, ad, &nSCD1, &nSCD2, err, &nSCD1_old)) return rc;
+    thSAD = thSAD * nSCD1 / nSCD1_old; // :521
+    if (!mvx_super_fits(ad, si, true)) MVX_FAIL("%s: wrong source or super clip frame size.", name);
+    const bool fields = a->fields != MVX_UNSET && a->fields;
+    if (fields && ad->nPel < 2) MVX_FAIL("%s: fields option requires pel > 1.", name); // :514-517
+    if (fields) MVX_FAIL("%s: fields is not supported.", name);
+    const bool overlap = ad->nOverlapX > 0 || ad->nOverlapY > 0;
+    if (overlap && (ad->nBlkX < 3 || ad->nBlkY < 3)) MVX_FAIL("overlap needs at least 3x3 blocks (window selection divides by nBlk-2).");
+    if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) MVX_FAIL("U and V super planes must share one pitch.");
+
+    mvx_compensate_n *h = new mvx_compensate_n();
+    CNParams &P = h->P;
+    memset(&P, 0, sizeof(P));
+    P.tr = tr; P.nFields = 2 * tr; P.nOut = 2 * tr + 1;
+    P.nBlkX = ad->nBlkX; P.nBlkY = ad->nBlkY; P.nBlk = ad->nBlkX * ad->nBlkY;
+    P.pel = ad->nPel; P.logPel = ad->nPel == 4 ? 2 : ad->nPel == 2 ? 1 : 0;
+    P.bits = si.bits; P.bps = (si.bits + 7) / 8; P.nplanes = si.num_planes;
+    P.overlap = overlap;
+    P.nLvCount = ad->nLvCount;
+    fps_fill_planes(P.pl, ad, si, nullptr, super_pitch, dst_pitch);
+    h->nWinClasses = si.num_planes > 1 ? 2 : 1;
+    P.thscd1 = nSCD1; P.thscd2 = nSCD2; P.thSAD = thSAD;
+    P.time256 = (int)(time * 256 / 100); // :560
+    P.scBehavior = scBehavior;
+    if (!(si.modeYUV & 6)) P.nplanes = 1; // num_planes :147-149
+    h->minStride = mvx_vectors_size(ad);
+    *out = h;
+    return MVX_OK;
+}
+
+extern "C" __attribute__((visibility("default"))) void mvx_compensate_n_destroy(mvx_compensate_n *c) { delete c; }
+
+extern "C" __attribute__((visibility("default"))) int mvx_compensate_n_map(const mvx_compensate_n *c, int k, int *offset, int *field) {
+    if (k < 0 || k > 2 * c->P.tr) { mvx_set_error("mvx_compensate_n_map: output %d of %d", k, 2 * c->P.tr + 1); return MVX_E_ARG; }
+    if (offset) *offset = k - c->P.tr;
+    if (field) *field = cn_field(c->P.tr, k);
+    return MVX_OK;
+}
+
+// device state is created on first use so that argument validation works without a GPU
+static int cn_finish(mvx_compensate_n *h) {
+    if (h->dP.p) return MVX_OK;
+    CNParams &P = h->P;
+    if (P.overlap) {
+        for (int c = 0; c < h->nWinClasses; c++) {
+            const PlaneG &g = P.pl[c];
+            std::vector<int16_t> w(9 * g.blkW * g.blkH);
+            mvx_over_windows(w.data(), g.blkW, g.blkH, g.ovX, g.ovY);
+            HIP_CHECK(h->dWin[c].reserve(w.size()));
+            HIP_CHECK(hipMemcpy(h->dWin[c].p, w.data(), w.size() * 2, hipMemcpyHostToDevice));
+        }
+        P.win[0] = h->dWin[0].p; P.win[1] = P.win[2] = h->dWin[1].p;
+    }
+    return fps_upload_params(h->dP, P);
+}
+
+// samples per cell of a plane: the widest power of two up to 16 bytes that divides the block width and the block step
+static int cn_cell_width(const PlaneG &g, int bps) {
+    int w = 16 / bps;
+    while (w > 1 && (g.blkW % w || g.stepX % w)) w >>= 1;
+    return w;
+}
+
+template <typename T> static void cn_launch_cells(int W, dim3 grid, hipStream_t st, const CNParams *dP, const CNTables &tables, const unsigned *lv0, const CNRec *plan, int p0, int npl) {
+#define CNC(N) hipLaunchKernelGGL((cn_cell_kernel<T, N>), grid, dim3(256), 0, st, dP, tables, lv0, plan, p0, npl)
+    switch (W) {
+    case 1: CNC(1); break;
+    case 2: CNC(2); break;
+    case 4: CNC(4); break;
+    case 8: CNC(8); break;
+    default: if constexpr (sizeof(T) == 1) CNC(16); break; // (16 bytes: 8-bit samples only)
+    }
+#undef CNC
+}
+
+extern "C" __attribute__((visibility("default"))) int mvx_compensate_n_frames(mvx_compensate_n *c, int njobs, const mvx_compensate_n_job *jobs, void *stream) {
+    if (njobs <= 0) return MVX_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const CNParams &P = c->P;
+    const size_t n = (size_t)njobs, nf = (size_t)P.nFields, no = (size_t)P.nOut;
+    // a grid's y and z hold 65535: the output kernel's z is (job, output, chroma plane), the plan kernel's y (job, field)
+    if (njobs > 65535 / (P.nOut * 2)) { mvx_set_error("mvx_compensate_n_frames: at most %d jobs per call at tr %d", 65535 / (P.nOut * 2), P.tr); return MVX_E_ARG; }
+    for (size_t f = 0; f < n; f++) {
+        const mvx_compensate_n_job &J = jobs[f];
+        if (!J.refs || !J.dst || !J.blob || !J.src_super[0]) { mvx_set_error("mvx_compensate_n_frames: a job needs its source, its reference table, its blob and its output table"); return MVX_E_ARG; }
+        if (J.field_stride < (size_t)c->minStride || J.field_stride % 16) { mvx_set_error("mvx_compensate_n_frames: field_stride must be a multiple of 16 and hold a field's %d bytes", c->minStride); return MVX_E_ARG; }
+        for (size_t k = 0; k < no; k++)
+            for (int p = 0; p < P.nplanes; p++)
+                if (!J.dst[k][p]) { mvx_set_error("mvx_compensate_n_frames: output %d lacks plane %d", (int)k, p); return MVX_E_ARG; }
+    }
+    CallGuard::Scope scope(c->guard, st);
+    int rc = cn_finish(c);
+    if (rc) return rc;
+    // one host block, one copy (each part a multiple of 8 bytes)
+    const size_t offRefs = sizeof(void *) * 3 * n, offBlobs = offRefs + sizeof(void *) * 3 * nf * n, offDst = offBlobs + sizeof(void *) * nf * n,
+                 total = offDst + sizeof(void *) * 3 * no * n;
+    std::vector<unsigned char> host(total, 0);
+    const unsigned char **hs = (const unsigned char **)host.data(), **hr = (const unsigned char **)(host.data() + offRefs),
+                        **hb = (const unsigned char **)(host.data() + offBlobs);
+    unsigned char **hd = (unsigned char **)(host.data() + offDst);
+    for (size_t f = 0; f < n; f++) {
+        const mvx_compensate_n_job &J = jobs[f];
+        for (int p = 0; p < P.nplanes; p++) hs[f * 3 + p] = (const unsigned char *)J.src_super[p];
+        for (size_t r = 0; r < nf; r++) {
+            if (J.refs[r][0]) for (int p = 0; p < P.nplanes; p++) hr[(f * nf + r) * 3 + p] = (const unsigned char *)J.refs[r][p];
+            hb[f * nf + r] = (const unsigned char *)J.blob + r * J.field_stride;
+        }
+        for (size_t k = 0; k < no; k++)
+            for (int p = 0; p < P.nplanes; p++) hd[(f * no + k) * 3 + p] = (unsigned char *)J.dst[k][p];
+    }
+    HIP_CHECK(c->dTables.reserve(total, total));
+    HIP_CHECK(c->dLv0.reserve(nf * n, nf * n));
+    HIP_CHECK(c->dPlan.reserve((size_t)P.nBlk * nf * n, (size_t)P.nBlk * nf * n / 2));
+    HIP_CHECK(hipMemcpyAsync(c->dTables.p, host.data(), total, hipMemcpyHostToDevice, st));
+    CNTables T;
+    T.src = (const unsigned char *const *)c->dTables.p;
+    T.refs = (const unsigned char *const *)(c->dTables.p + offRefs);
+    T.blobs = (const unsigned char *const *)(c->dTables.p + offBlobs);
+    T.dst = (unsigned char *const *)(c->dTables.p + offDst);
+    hipLaunchKernelGGL(cn_usable_kernel, dim3(P.nFields, njobs), dim3(256), 0, st, c->dP.p, T, c->dLv0.p);
+    hipLaunchKernelGGL(cn_plan_kernel, dim3((P.nBlk + 255) / 256, njobs * P.nFields), dim3(256), 0, st, c->dP.p, T, c->dLv0.p, c->dPlan.p);
+    for (int cls = 0; cls < (P.nplanes > 1 ? 2 : 1); cls++) { // one launch for the luma planes of all outputs of all jobs, one for both chroma planes
+        const int p0 = cls, npl = cls ? 2 : 1, W = cn_cell_width(P.pl[p0], P.bps);
+        const dim3 grid(((P.pl[p0].W + W - 1) / W + 31) / 32, (P.pl[p0].H + 7) / 8, njobs * P.nOut * npl);
+        if (P.bps == 1) cn_launch_cells<uint8_t>(W, grid, st, c->dP.p, T, c->dLv0.p, c->dPlan.p, p0, npl);
+        else cn_launch_cells<uint16_t>(W, grid, st, c->dP.p, T, c->dLv0.p, c->dPlan.p, p0, npl);
+    }
+    HIP_CHECK(hipGetLastError());
+    return MVX_OK;
+}

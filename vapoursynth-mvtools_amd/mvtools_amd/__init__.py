@@ -5,6 +5,8 @@
     core.mv.Degrain1..6(clip, super, mvbw, mvfw, ...) -> Degrain(radius, super, analysis_data, ...) .run(jobs)
     (no reference name: radius 1..24)                 -> DegrainN(radius, super, analysis_data, ..., thsad2=...) .info() .run(jobs)
     core.mv.Compensate(clip, super, vectors, ...)     -> Compensate(super, analysis_data, ...)      .run(jobs)
+    (no reference name: one frame against a radius)   -> AnalyseN(super, radius, num_frames, ...)  .ad(r) .fields(multi_blob) .run(jobs)
+                                                         CompensateN(tr, super, analysis_data, ...) .map(k) .run(jobs)
     core.mv.FlowInter / FlowFPS(clip, super, mvbw, mvfw, ...) -> FlowInter / FlowFPS(super, bw_data, fw_data, ...) .run(ns, ...)
     core.mv.Flow(clip, super, vectors, ...)           -> Flow(super, analysis_data, ...)          .run(jobs)
     core.mv.FlowBlur(clip, super, mvbw, mvfw, ...)    -> FlowBlur(super, bw_data, fw_data, ...)   .run(ns, ...)
@@ -99,6 +101,16 @@ class CompensateArgs(C.Structure):
 class CompensateJob(C.Structure):
     _fields_ = [("src_super", C.c_void_p * 3), ("ref_super", C.c_void_p * 3), ("blob", C.c_void_p), ("dst", C.c_void_p * 3),
                 ("field_shift", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AnalyseNJob(C.Structure):
+    _fields_ = [("src", C.c_void_p * 3), ("refs", C.POINTER(C.c_void_p * 3)), ("blob", C.c_void_p), ("field_shift", C.POINTER(C.c_int32)),
+                ("field_shift_all", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CompensateNJob(C.Structure):
+    _fields_ = [("src_super", C.c_void_p * 3), ("refs", C.POINTER(C.c_void_p * 3)), ("blob", C.c_void_p), ("field_stride", C.c_size_t),
+                ("dst", C.POINTER(C.c_void_p * 3))]
 
 
 RECALC_ARGS = ("thsad", "smooth", "blksize", "blksizev", "search", "searchparam", "lambda_", "chroma", "truemotion", "pnew", "overlap", "overlapv", "divide",
@@ -309,6 +321,22 @@ def lib():
                                             P(C.c_void_p), C.c_char_p]
         L.mvx_compensate_destroy.argtypes = [C.c_void_p]
         L.mvx_compensate_frames.argtypes = [C.c_void_p, C.c_int, P(CompensateJob), C.c_void_p]
+        L.mvx_analyse_n_create.argtypes = [P(AnalyseArgs), C.c_int, C.c_void_p, C.c_int, P(C.c_ssize_t), P(C.c_void_p), C.c_char_p]
+        L.mvx_analyse_n_destroy.argtypes = [C.c_void_p]
+        L.mvx_analyse_n_get_data.argtypes = [C.c_void_p, C.c_int, P(AnalysisData)]
+        L.mvx_analyse_n_field_size.argtypes = [C.c_void_p]
+        L.mvx_analyse_n_field_size.restype = C.c_size_t
+        L.mvx_analyse_n_field_stride.argtypes = [C.c_void_p]
+        L.mvx_analyse_n_field_stride.restype = C.c_size_t
+        L.mvx_analyse_n_blob_size.argtypes = [C.c_void_p]
+        L.mvx_analyse_n_blob_size.restype = C.c_size_t
+        L.mvx_analyse_n_set_ref_shadow.argtypes = [C.c_void_p, P(C.c_ssize_t)]
+        L.mvx_analyse_n_frames.argtypes = [C.c_void_p, C.c_int, P(AnalyseNJob), C.c_void_p]
+        L.mvx_compensate_n_create.argtypes = [P(CompensateArgs), C.c_int, P(AnalysisData), C.c_void_p, P(C.c_ssize_t), P(C.c_ssize_t),
+                                              P(C.c_void_p), C.c_char_p]
+        L.mvx_compensate_n_destroy.argtypes = [C.c_void_p]
+        L.mvx_compensate_n_map.argtypes = [C.c_void_p, C.c_int, P(C.c_int), P(C.c_int)]
+        L.mvx_compensate_n_frames.argtypes = [C.c_void_p, C.c_int, P(CompensateNJob), C.c_void_p]
         L.mvx_finest_size.argtypes = [C.c_void_p, P(C.c_int32), P(C.c_int32)]
         L.mvx_finest_frames.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), P(C.c_ssize_t), P(C.c_void_p), P(C.c_ssize_t), C.c_void_p]
         L.mvx_scdetect.argtypes = [P(AnalysisData), C.c_int64, C.c_int32, C.c_int, P(C.c_void_p), P(C.c_int32), C.c_void_p, C.c_char_p]
@@ -713,6 +741,101 @@ class Analyse:
         return blobs
 
 
+def multi_refs(n, radius, num_frames):
+    """the frames behind the 2 * radius fields of frame n's multi blob, in field order: n+1, n-1, n+2, n-2, ...; None outside the clip"""
+    out = []
+    for d in range(1, radius + 1):
+        out += [m if 0 <= m < num_frames else None for m in (n + d, n - d)]
+    return out
+
+
+def _ref_table(jobs_refs, nr, nplanes, what):
+    """the HOST table [job * nr + r][plane] behind the refs pointers of the *N jobs; a None reference stays NULL"""
+    table = ((C.c_void_p * 3) * (nr * max(len(jobs_refs), 1)))()
+    for i, refs in enumerate(jobs_refs):
+        if len(refs) != nr:
+            raise ValueError("%s: a job needs %d references" % (what, nr))
+        for r, ref in enumerate(refs):
+            if ref is not None:
+                for p in range(nplanes):
+                    table[i * nr + r][p] = ref[p].data_ptr()
+    return table
+
+
+class AnalyseN:
+    """One source frame against a temporal radius (include/mvtools_amd.h, "the multi blob"): field r of a multi blob is the MVTools_vectors of
+    Analyse(isb = r % 2 == 0, delta = r // 2 + 1), byte for byte, at byte r * field_stride.  Keyword names are Analyse's; isb and delta are
+    set by the radius."""
+
+    def __init__(self, sup, radius, num_frames=1 << 30, **kw):
+        self.sup = sup
+        a = AnalyseArgs(*([UNSET] * len(ANALYSE_ARGS)))
+        for k, v in kw.items():
+            k2 = {"lambda": "lambda_", "global": "global_"}.get(k, k)
+            if k2 not in ANALYSE_ARGS:
+                raise TypeError("AnalyseN: unknown argument " + k)
+            if v is not None:
+                setattr(a, k2, int(v))
+        pitch = (C.c_ssize_t * 3)(*(sup.pitch + [0] * (3 - len(sup.pitch))))
+        self.h = C.c_void_p()
+        err = C.create_string_buffer(ERRLEN)
+        _check(lib().mvx_analyse_n_create(C.byref(a), int(radius), sup.h, int(num_frames), pitch, C.byref(self.h), err), err)
+        self.radius = int(radius)
+        self.field_size = lib().mvx_analyse_n_field_size(self.h)
+        self.field_stride = lib().mvx_analyse_n_field_stride(self.h)
+        self.blob_size = lib().mvx_analyse_n_blob_size(self.h)
+        if sup.shadow:  # super frames from sup.alloc / sup.build carry their shifted copies
+            _check(lib().mvx_analyse_n_set_ref_shadow(self.h, (C.c_ssize_t * 3)(*(sup.shadow_stride + [0] * (3 - len(sup.shadow_stride))))))
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().mvx_analyse_n_destroy(self.h)
+        except Exception:
+            pass
+
+    def ad(self, r):
+        """the MVTools_MVAnalysisData of field r"""
+        out = AnalysisData()
+        _check(lib().mvx_analyse_n_get_data(self.h, int(r), C.byref(out)))
+        return out
+
+    def alloc_blobs(self, n, device="cuda"):
+        torch = _torch()
+        buf = torch.zeros((n, self.blob_size), dtype=torch.uint8, device=device)
+        return [buf[i] for i in range(n)]
+
+    def fields(self, multi_blob):
+        """the 2 * radius fields of a multi blob as tensor views: each is a blob any consumer takes"""
+        return [multi_blob[r * self.field_stride:r * self.field_stride + self.field_size] for r in range(2 * self.radius)]
+
+    def run(self, jobs, blobs=None, field_shift=0):
+        """jobs: list of (src_super_frame, [ref_super_frame or None] * 2r in the order of multi_refs) -> list of multi blobs on the device.
+        field_shift: one value, or per job a list of 2r."""
+        n, nr = len(jobs), 2 * self.radius
+        if blobs is None:
+            blobs = self.alloc_blobs(n, device=jobs[0][0][0].device)
+        self.sup.check_room([f for s, refs in jobs for f in [s] + list(refs)], "AnalyseN input")  # (the search reads the shadow planes behind every plane)
+        arr = (AnalyseNJob * n)()
+        table = _ref_table([refs for _, refs in jobs], nr, self.sup.nplanes, "AnalyseN")
+        shifts = (C.c_int32 * (nr * n))()
+        for i, (s, refs) in enumerate(jobs):
+            for p in range(self.sup.nplanes):
+                assert s[p].stride(0) == self.sup.pitch[p]
+                arr[i].src[p] = s[p].data_ptr()
+            arr[i].refs = C.cast(C.byref(table, i * nr * C.sizeof(C.c_void_p * 3)), C.POINTER(C.c_void_p * 3))
+            if blobs[i].numel() < self.blob_size:
+                raise ValueError("AnalyseN: a multi blob holds %d bytes" % self.blob_size)
+            arr[i].blob = blobs[i].data_ptr()
+            if isinstance(field_shift, int):
+                arr[i].field_shift_all = field_shift
+            else:
+                shifts[i * nr:(i + 1) * nr] = [int(v) for v in field_shift[i]]
+                arr[i].field_shift = C.cast(C.byref(shifts, i * nr * 4), C.POINTER(C.c_int32))
+        _check(lib().mvx_analyse_n_frames(self.h, n, arr, _stream()))
+        return blobs
+
+
 class Degrain:
     """mv.Degrain1..6 -- MVDegrains.cpp:511-809.  analysis_data = the vector clips' MVTools_MVAnalysisData."""
 
@@ -805,7 +928,8 @@ class DegrainN:
         return dict(radius=i.radius, nrefs=i.nrefs, thsad_d=list(i.thsad_d[:i.radius]), thsadc_d=list(i.thsadc_d[:i.radius]))
 
     def run(self, jobs, out=None):
-        """jobs: list of (src_frame, [ref_super or None]*2r, [blob]*2r) ordered mvbw, mvfw, mvbw2, mvfw2, ..."""
+        """jobs: list of (src_frame, [ref_super or None]*2r, [blob]*2r) ordered mvbw, mvfw, mvbw2, mvfw2, ...; in place of the list of blobs a job
+        may carry ONE multi blob (AnalyseN.run): a tensor of 2r * field_stride bytes whose field r is blob r"""
         torch = _torch()
         n, nr = len(jobs), 2 * self.radius
         if out is None and self.out16:
@@ -815,6 +939,11 @@ class DegrainN:
         arr = (DegrainNJob * n)()
         refs_all, blobs_all = ((C.c_void_p * 3) * (nr * n))(), (C.c_void_p * (nr * n))()  # the host tables behind the jobs' pointers
         for i, (src, refs, blobs) in enumerate(jobs):
+            multi = blobs if hasattr(blobs, "data_ptr") else None
+            if multi is not None:  # the fields of a multi blob: base + r * stride
+                if multi.dim() != 1 or multi.numel() % (256 * nr):
+                    raise ValueError("DegrainN: a multi blob is a one-dimensional tensor of %d fields, each a multiple of 256 bytes" % nr)
+                blobs = [multi[r * (multi.numel() // nr):] for r in range(nr)]
             if len(refs) != nr or len(blobs) != nr:
                 raise ValueError("DegrainN: a job needs %d references and blobs" % nr)
             for p in range(self.sup.nplanes):
@@ -875,6 +1004,69 @@ class Compensate:
             arr[k].blob = blob.data_ptr()
             arr[k].field_shift = int(job[3]) if len(job) > 3 else 0
         _check(lib().mvx_compensate_frames(self.h, n, arr, _stream()))
+        return out
+
+
+class CompensateN:
+    """The frames n - tr .. n + tr compensated onto frame n from frame n's multi blob (include/mvtools_amd.h, mv.CompensateN): 2 * tr + 1 frames
+    per job in temporal order, each compensated one byte for byte what Compensate writes for that pair, the source in the middle.
+    analysis_data: of field 0 (AnalyseN.ad(0))."""
+
+    def __init__(self, tr, sup, analysis_data, dst_pitch=None, scbehavior=None, thsad=None, time=100.0, thscd1=None, thscd2=None, fields=None):
+        self.sup = sup
+        a = CompensateArgs(_u(scbehavior), _u(thsad), float(time), _u(thscd1), _u(thscd2), _u(fields))
+        ad = AnalysisData.from_buffer_copy(bytes(analysis_data))
+        i = sup.info
+        if dst_pitch is None:
+            w = [i.width] + [i.width // i.xRatioUV] * 2
+            dst_pitch = [((w[p] * sup.bps + 255) // 256) * 256 for p in range(sup.nplanes)]
+        pad = lambda l: (C.c_ssize_t * 3)(*(list(l) + [0] * (3 - len(l))))
+        self.h = C.c_void_p()
+        err = C.create_string_buffer(ERRLEN)
+        _check(lib().mvx_compensate_n_create(C.byref(a), int(tr), C.byref(ad), sup.h, pad(sup.pitch), pad(dst_pitch), C.byref(self.h), err), err)
+        self.tr = int(tr)
+        self.dst_pitch = list(dst_pitch)
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().mvx_compensate_n_destroy(self.h)
+        except Exception:
+            pass
+
+    def map(self, k):
+        """output k of a job -> (offset of its frame from n, field of the multi blob that compensates it or -1 for the centre)"""
+        off, field = C.c_int(), C.c_int()
+        _check(lib().mvx_compensate_n_map(self.h, int(k), C.byref(off), C.byref(field)))
+        return off.value, field.value
+
+    def run(self, jobs, out=None):
+        """jobs: list of (src_super, [ref_super or None] * 2tr in the order of multi_refs, multi blob[, field_stride]) -> per job 2tr + 1 frames.
+        field_stride defaults to the blob's bytes / 2tr (a blob of AnalyseN.alloc_blobs)."""
+        torch = _torch()
+        i = self.sup.info
+        n, nr, no, npl = len(jobs), 2 * self.tr, 2 * self.tr + 1, self.sup.nplanes
+        hs = [i.height] + [i.height // i.yRatioUV] * 2
+        if out is None:
+            dev = jobs[0][0][0].device
+            out = [[[torch.zeros((hs[p], self.dst_pitch[p]), dtype=torch.uint8, device=dev) for p in range(npl)] for _ in range(no)] for _ in range(n)]
+        arr = (CompensateNJob * n)()
+        table = _ref_table([job[1] for job in jobs], nr, npl, "CompensateN")
+        dst = ((C.c_void_p * 3) * (no * n))()
+        for j, job in enumerate(jobs):
+            s, blob = job[0], job[2]
+            if len(out[j]) != no:
+                raise ValueError("CompensateN: a job writes %d frames" % no)
+            for p in range(npl):
+                arr[j].src_super[p] = s[p].data_ptr()
+                for k in range(no):
+                    assert out[j][k][p].stride(0) == self.dst_pitch[p]
+                    dst[j * no + k][p] = out[j][k][p].data_ptr()
+            arr[j].refs = C.cast(C.byref(table, j * nr * C.sizeof(C.c_void_p * 3)), C.POINTER(C.c_void_p * 3))
+            arr[j].dst = C.cast(C.byref(dst, j * no * C.sizeof(C.c_void_p * 3)), C.POINTER(C.c_void_p * 3))
+            arr[j].blob = blob.data_ptr()
+            arr[j].field_stride = int(job[3]) if len(job) > 3 else blob.numel() // nr
+        _check(lib().mvx_compensate_n_frames(self.h, n, arr, _stream()))
         return out
 
 
