@@ -10,13 +10,14 @@ import vector_fields
 W, H = 96, 64
 B84 = ("p2", dict(pel=2), dict(blksize=8, overlap=4))     # overlapped blocks: 23 x 15 of them; cells of 4 luma / 2 chroma samples (4:4:4: 4 / 4)
 B160 = ("p1", dict(pel=1), dict(blksize=16, overlap=0))   # blocks side by side: 6 x 4; cells of 16 / 8 samples (16 bits: 8 / 8)
+B42 = ("p2b4", dict(pel=2), dict(blksize=4, overlap=2))   # the smallest blocks: 47 x 31 of them; at 4:2:0 chroma blocks of 2 stepping by 1 -- cells of ONE sample
 RADII = (1, 2, 3, 7)
 
 # fmt, bits, (tag, super kwargs, analyse kwargs)
-GEOS = [("420", 8, B84), ("420", 8, B160), ("420", 16, B84), ("420", 16, B160), ("444", 8, B84), ("gray", 8, B160)]
+GEOS = [("420", 8, B84), ("420", 8, B160), ("420", 16, B84), ("420", 16, B160), ("444", 8, B84), ("gray", 8, B160), ("420", 8, B42), ("420", 16, B42)]
 
 # thsad of every CompensateN case: chosen on the CPU (tests/test_multi_cases.py) so that beyond distance 1 at least half of the (block, field)
-# pairs are compensated and at least a fiftieth fall back on the source block (the shares it leaves: 0.64 .. 0.93 and 0.07 .. 0.36)
+# pairs are compensated and at least a fiftieth fall back on the source block (the shares it leaves: 0.64 .. 0.96 and 0.04 .. 0.36; the blocks of 4: 0.88 .. 0.96 and 0.04 .. 0.12)
 THSAD = 250
 USED, UNUSED = 0.5, 0.02
 

@@ -1,29 +1,26 @@
 // mvx_compensate_n.hip -- mv.CompensateN on gfx950: the frames n - tr .. n + tr compensated onto frame n from one multi blob
 // (mvtools_amd.h, "the multi blob"), in temporal order, the source in the middle.
 //
-// Every compensated output is one mv.Compensate result (MVCompensate.c:73-374 as mvx_degrain.hip restates it): fgopIsUsable per field, the
+// Every compensated output is one mv.Compensate result (MVCompensate.c:73-374; what the two filters share -- geometry, windows, creation
+// arguments, the usable kernel, block cover, loads -- is in mvx_block_shared.h): fgopIsUsable per field, the
 // block origin from the vector scaled by time or the block's own place when its SAD reaches thsad, overlaps_c / ToPixels
 // (Overlap.cpp:143-158,335-356) in gather form, the uncovered strips and the scene-change fallback per scbehavior.  What this file adds is
 // the shape of the work: a job is 2 * tr fields and 2 * tr + 1 output frames, so
-//   usable  one launch over (field, job): 0, or the byte offset of level 0 inside the field's blob
+//   usable  one launch over (field, job): 0, or the byte offset of level 0 inside the field's blob (blk_usable_kernel)
 //   plan    one launch over (block, field x job): where the block comes from in the chosen super frame, luma and chroma
 //   output  one launch per plane class over (cell, row, plane x output x job): a thread produces one row of a cell of W samples -- W
 //           divides the block width and the block step, so the same <= 2 x 2 blocks cover all of them and each costs one vector load.
 //           Blocks side by side, the uncovered strips, an unusable field and the centre are a single load and store of the same cell.
 // Nothing is sized by tr at compile time: the tables (source planes, reference planes, field blobs, output planes) live in global memory,
 // and what a workgroup needs of them -- it serves ONE plane of ONE output -- is uniform, so it arrives in scalar registers.
-#include "mvx_fps_shared.h"
+#include "mvx_block_shared.h"
 
 // ------------------------------------------------------------------------------------------------ device structs
 
-struct CNParams {
-    int tr, nFields, nOut, nBlkX, nBlkY, nBlk, pel, logPel, bits, bps, nplanes, overlap;
-    int nLvCount;
+struct CNParams : BlkGeom {
+    int tr, nFields, nOut;
     int time256, scBehavior;
     long long thSAD;
-    long long thscd1; int thscd2;
-    PlaneG pl[3];
-    const int16_t *win[3];
 };
 
 struct __attribute__((aligned(16))) CNRec { unsigned off[2]; int fromRef; int pad; }; // off[0] luma, off[1] chroma
@@ -42,16 +39,6 @@ struct CNTables {
 __host__ __device__ __forceinline__ int cn_field(int tr, int k) { return k == tr ? -1 : k < tr ? 2 * (tr - k - 1) + 1 : 2 * (k - tr - 1); }
 
 // ------------------------------------------------------------------------------------------------ kernels
-
-// per (job, field): 0 when the field's vectors are not usable (fgopIsUsable, or a reference frame outside the clip), else the byte offset of
-// level 0 inside the field's blob
-__global__ __launch_bounds__(256) void cn_usable_kernel(const CNParams *Pp, CNTables T, unsigned *lv0) {
-    const CNParams &P = *Pp;
-    const int k = blockIdx.y * P.nFields + blockIdx.x;
-    const unsigned char *blob = T.blobs[k];
-    const bool ok = fps_block_usable(blob, T.refs[(size_t)k * 3] != nullptr, P.nLvCount, P.nBlk, P.thscd1, P.thscd2);
-    if (threadIdx.x == 0) lv0[k] = ok ? (unsigned)((const unsigned char *)mvx_level0(blob, P.nLvCount) - blob) : 0u;
-}
 
 // one thread per (job x field, block): compensate_plan_kernel's record (MVCompensate.c:238-247,286-295) without a field shift
 __global__ __launch_bounds__(256) void cn_plan_kernel(const CNParams *Pp, CNTables T, const unsigned *lv0, CNRec *plan) {
@@ -73,14 +60,6 @@ __global__ __launch_bounds__(256) void cn_plan_kernel(const CNParams *Pp, CNTabl
     rec.off[1] = P.nplanes > 1 ? sup_offset(P.pl[1], P.pel, P.logPel, P.bps, blx >> P.pl[1].subX, bly >> P.pl[1].subY) : 0;
     rec.pad = 0;
     plan[(size_t)k * P.nBlk + i] = rec;
-}
-
-// W samples of type T at an arbitrarily aligned address (dg_load / dg_store start at two bytes; a cell can be one 8-bit sample)
-template <typename T, int W> __device__ __forceinline__ void cn_load(DG_GL const unsigned char *p, int *o) {
-    if constexpr (W * sizeof(T) == 1) o[0] = *p; else dg_load<T, W>(p, o);
-}
-template <typename T, int W> __device__ __forceinline__ void cn_store(DG_GL unsigned char *p, const int *v) {
-    if constexpr (W * sizeof(T) == 1) *p = (unsigned char)v[0]; else dg_store<T, W>(p, v);
 }
 
 // One thread per row of a cell; 256 threads = 32 cells x 8 rows of one plane of one output of one job.  z = (job, output, plane of the class).
@@ -115,8 +94,8 @@ __global__ __launch_bounds__(256) void cn_cell_kernel(const CNParams *Pp, CNTabl
     }
     if (sp) {
         if (x0 + W <= g.W) {
-            cn_load<T, W>(dg_gl(sp), out);
-            cn_store<T, W>(dg_glw(drow), out);
+            dg_load<T, W>(dg_gl(sp), out);
+            dg_store<T, W>(dg_glw(drow), out);
         } else {
 #pragma unroll
             for (int i = 0; i < W; i++) if (x0 + i < g.W) ((T *)drow)[i] = ((const T *)sp)[i];
@@ -126,10 +105,9 @@ __global__ __launch_bounds__(256) void cn_cell_kernel(const CNParams *Pp, CNTabl
     // overlapped blocks (:260-317): the blocks bx0..bx1 x by0..by1 cover the cell, at most two each way (the overlap is at most half a block).
     // All four slots are loaded -- one that does not exist repeats the first and adds nothing -- so that the four plan records, and then the
     // four rows and window rows, are in flight together.
-    int bx1 = x0 / g.stepX; if (bx1 > P.nBlkX - 1) bx1 = P.nBlkX - 1;
-    const int bx0 = x0 - g.blkW + 1 <= 0 ? 0 : (x0 - g.blkW + g.stepX) / g.stepX;
-    int by1 = y / g.stepY; if (by1 > P.nBlkY - 1) by1 = P.nBlkY - 1;
-    const int by0 = y - g.blkH + 1 <= 0 ? 0 : (y - g.blkH + g.stepY) / g.stepY;
+    int bx0, bx1, by0, by1;
+    blk_cover(x0, g.blkW, g.stepX, P.nBlkX, bx0, bx1);
+    blk_cover(y, g.blkH, g.stepY, P.nBlkY, by0, by1);
     DG_GL const unsigned char *pl = dg_gl(plan + ((size_t)f * P.nFields + field) * P.nBlk);
     DG_GL const unsigned char *win = dg_gl(P.win[p]);
     bool have[4];
@@ -142,16 +120,14 @@ __global__ __launch_bounds__(256) void cn_cell_kernel(const CNParams *Pp, CNTabl
         const int byc = have[s] ? by : by0, bxc = have[s] ? bx : bx0;
         R[s] = *(DG_GL const dg_iv4 *)(pl + (size_t)(byc * P.nBlkX + bxc) * sizeof(CNRec));
         px[s] = x0 - bxc * g.stepX; py[s] = y - byc * g.stepY; // 0 <= px <= blkW - W
-        const int wby = byc == 0 ? 0 : (byc == P.nBlkY - 1 ? 6 : 3); // ((by + nBlkY - 3) / (nBlkY - 2)) * 3, MVCompensate.c:263
-        const int wbx = bxc == P.nBlkX - 1 ? 2 : (bxc == 0 ? 0 : 1); // :267-269,297
-        wsel[s] = (wby + wbx) * g.blkW * g.blkH + py[s] * g.blkW + px[s];
+        wsel[s] = (BLK_WIN_ROW(byc, P.nBlkY) + BLK_WIN_COL(bxc, P.nBlkX)) * g.blkW * g.blkH + py[s] * g.blkW + px[s];
     }
     int val[4][W], wv[4][W];
 #pragma unroll
     for (int s = 0; s < 4; s++) {
         const unsigned char *base = (R[s][2] ? refSup : srcSup) + (unsigned)R[s][p ? 1 : 0] + (long long)py[s] * g.supPitch + (long long)px[s] * (long long)sizeof(T);
-        cn_load<T, W>(dg_gl(base), val[s]);
-        cn_load<unsigned short, W>(win + (size_t)wsel[s] * 2, wv[s]);
+        dg_load<T, W>(dg_gl(base), val[s]);
+        dg_load<unsigned short, W>(win + (size_t)wsel[s] * 2, wv[s]);
     }
     const int pm = (1 << P.bits) - 1;
 #pragma unroll
@@ -163,7 +139,7 @@ __global__ __launch_bounds__(256) void cn_cell_kernel(const CNParams *Pp, CNTabl
         const int a = (int)((acc + 16) >> 5); // ToPixels, Overlap.cpp:335-356
         out[i] = a > pm ? pm : a;
     }
-    cn_store<T, W>(dg_glw(drow), out);
+    dg_store<T, W>(dg_glw(drow), out);
 }
 
 // ------------------------------------------------------------------------------------------------ host object
@@ -176,8 +152,7 @@ struct mvx_compensate_n {
     DevBuf<unsigned char> dTables;   // per call: see CNTables
     DevBuf<unsigned> dLv0;
     DevBuf<CNRec> dPlan;
-    DevBuf<int16_t> dWin[2];
-    int nWinClasses = 1;
+    BlkWin win;
 };
 
 // MVCompensate.c:419-575 mvcompensateCreate under the name CompensateN
@@ -187,36 +162,15 @@ extern "C" __attribute__((visibility("default"))) int mvx_compensate_n_create(co
     const mvx_super_info &si = sup->info;
     const char *name = "CompensateN";
     if (tr < 1 || tr > MVX_DEGRAIN_N_MAX_RADIUS) MVX_FAIL("%s: tr must be between 1 and %d.", name, MVX_DEGRAIN_N_MAX_RADIUS);
-    const int scBehavior = a->scbehavior == MVX_UNSET ? 1 : !!a->scbehavior;
-    long long thSAD = a->thsad == MVX_UNSET ? 10000 : a->thsad;
-    const double time = a->time;
-    if (time < 0.0 || time > 100.0) MVX_FAIL("%s: time must be between 0.0 and 100.0 (inclusive).", name);
-    int64_t nSCD1, nSCD1_old; int32_t nSCD2;
-    if (int rc = mvx_resolve_thscd(name, a->thscd1, a->thscd2, ad, &nSCD1, &nSCD2, err, &nSCD1_old)) return rc;
-    thSAD = thSAD * nSCD1 / nSCD1_old; // :521
-    if (!mvx_super_fits(ad, si, true)) MVX_FAIL("%s: wrong source or super clip frame size.", name);
-    const bool fields = a->fields != MVX_UNSET && a->fields;
-    if (fields && ad->nPel < 2) MVX_FAIL("%s: fields option requires pel > 1.", name); // :514-517
-    if (fields) MVX_FAIL("%s: fields is not supported.", name);
-    const bool overlap = ad->nOverlapX > 0 || ad->nOverlapY > 0;
-    if (overlap && (ad->nBlkX < 3 || ad->nBlkY < 3)) MVX_FAIL("overlap needs at least 3x3 blocks (window selection divides by nBlk-2).");
-    if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) MVX_FAIL("U and V super planes must share one pitch.");
-
-    mvx_compensate_n *h = new mvx_compensate_n();
+    CompResolved r;
+    if (int rc = comp_resolve(name, a, ad, si, &r, err)) return rc;
+    if (r.fields) MVX_FAIL("%s: fields is not supported.", name);
+    mvx_compensate_n *h;
+    if (int rc = blk_new(&h, ad, si, nullptr, super_pitch, dst_pitch, err)) return rc;
     CNParams &P = h->P;
-    memset(&P, 0, sizeof(P));
     P.tr = tr; P.nFields = 2 * tr; P.nOut = 2 * tr + 1;
-    P.nBlkX = ad->nBlkX; P.nBlkY = ad->nBlkY; P.nBlk = ad->nBlkX * ad->nBlkY;
-    P.pel = ad->nPel; P.logPel = ad->nPel == 4 ? 2 : ad->nPel == 2 ? 1 : 0;
-    P.bits = si.bits; P.bps = (si.bits + 7) / 8; P.nplanes = si.num_planes;
-    P.overlap = overlap;
-    P.nLvCount = ad->nLvCount;
-    fps_fill_planes(P.pl, ad, si, nullptr, super_pitch, dst_pitch);
-    h->nWinClasses = si.num_planes > 1 ? 2 : 1;
-    P.thscd1 = nSCD1; P.thscd2 = nSCD2; P.thSAD = thSAD;
-    P.time256 = (int)(time * 256 / 100); // :560
-    P.scBehavior = scBehavior;
-    if (!(si.modeYUV & 6)) P.nplanes = 1; // num_planes :147-149
+    P.thSAD = r.thSAD; P.time256 = r.time256; P.scBehavior = r.scBehavior;
+    comp_apply(P, r, si);
     h->minStride = mvx_vectors_size(ad);
     *out = h;
     return MVX_OK;
@@ -229,30 +183,6 @@ extern "C" __attribute__((visibility("default"))) int mvx_compensate_n_map(const
     if (offset) *offset = k - c->P.tr;
     if (field) *field = cn_field(c->P.tr, k);
     return MVX_OK;
-}
-
-// device state is created on first use so that argument validation works without a GPU
-static int cn_finish(mvx_compensate_n *h) {
-    if (h->dP.p) return MVX_OK;
-    CNParams &P = h->P;
-    if (P.overlap) {
-        for (int c = 0; c < h->nWinClasses; c++) {
-            const PlaneG &g = P.pl[c];
-            std::vector<int16_t> w(9 * g.blkW * g.blkH);
-            mvx_over_windows(w.data(), g.blkW, g.blkH, g.ovX, g.ovY);
-            HIP_CHECK(h->dWin[c].reserve(w.size()));
-            HIP_CHECK(hipMemcpy(h->dWin[c].p, w.data(), w.size() * 2, hipMemcpyHostToDevice));
-        }
-        P.win[0] = h->dWin[0].p; P.win[1] = P.win[2] = h->dWin[1].p;
-    }
-    return fps_upload_params(h->dP, P);
-}
-
-// samples per cell of a plane: the widest power of two up to 16 bytes that divides the block width and the block step
-static int cn_cell_width(const PlaneG &g, int bps) {
-    int w = 16 / bps;
-    while (w > 1 && (g.blkW % w || g.stepX % w)) w >>= 1;
-    return w;
 }
 
 template <typename T> static void cn_launch_cells(int W, dim3 grid, hipStream_t st, const CNParams *dP, const CNTables &tables, const unsigned *lv0, const CNRec *plan, int p0, int npl) {
@@ -283,7 +213,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_compensate_n_frames(mv
                 if (!J.dst[k][p]) { mvx_set_error("mvx_compensate_n_frames: output %d lacks plane %d", (int)k, p); return MVX_E_ARG; }
     }
     CallGuard::Scope scope(c->guard, st);
-    int rc = cn_finish(c);
+    int rc = blk_upload(c->dP, c->P, c->win);
     if (rc) return rc;
     // one host block, one copy (each part a multiple of 8 bytes)
     const size_t offRefs = sizeof(void *) * 3 * n, offBlobs = offRefs + sizeof(void *) * 3 * nf * n, offDst = offBlobs + sizeof(void *) * nf * n,
@@ -311,10 +241,10 @@ extern "C" __attribute__((visibility("default"))) int mvx_compensate_n_frames(mv
     T.refs = (const unsigned char *const *)(c->dTables.p + offRefs);
     T.blobs = (const unsigned char *const *)(c->dTables.p + offBlobs);
     T.dst = (unsigned char *const *)(c->dTables.p + offDst);
-    hipLaunchKernelGGL(cn_usable_kernel, dim3(P.nFields, njobs), dim3(256), 0, st, c->dP.p, T, c->dLv0.p);
+    hipLaunchKernelGGL(blk_usable_kernel<CNParams>, dim3(P.nFields, njobs), dim3(256), 0, st, c->dP.p, P.nFields, BlkTables{T.refs, T.blobs}, c->dLv0.p);
     hipLaunchKernelGGL(cn_plan_kernel, dim3((P.nBlk + 255) / 256, njobs * P.nFields), dim3(256), 0, st, c->dP.p, T, c->dLv0.p, c->dPlan.p);
     for (int cls = 0; cls < (P.nplanes > 1 ? 2 : 1); cls++) { // one launch for the luma planes of all outputs of all jobs, one for both chroma planes
-        const int p0 = cls, npl = cls ? 2 : 1, W = cn_cell_width(P.pl[p0], P.bps);
+        const int p0 = cls, npl = cls ? 2 : 1, W = blk_cell_width(P.pl[p0], 16 / P.bps);
         const dim3 grid(((P.pl[p0].W + W - 1) / W + 31) / 32, (P.pl[p0].H + 7) / 8, njobs * P.nOut * npl);
         if (P.bps == 1) cn_launch_cells<uint8_t>(W, grid, st, c->dP.p, T, c->dLv0.p, c->dPlan.p, p0, npl);
         else cn_launch_cells<uint16_t>(W, grid, st, c->dP.p, T, c->dLv0.p, c->dPlan.p, p0, npl);

@@ -1,5 +1,6 @@
 // mvx_degrain.hip -- the block filters on gfx950: mv.Degrain1..6 and mv.Compensate (first half), mv.BlockFPS and mv.SCDetection (second half,
-// each under its own heading).  What they share with the flow filters and mv.Mask is in mvx_fps_shared.h.
+// each under its own heading).  What they share with DegrainN and CompensateN is in mvx_block_shared.h, what they share with the flow filters
+// and mv.Mask in mvx_fps_shared.h.
 //
 // The reference walks blocks, blends each block into a temp (Degrain_C, MVDegrains.h:30-53), scatters it times a
 // raised-cosine window into a 16/32-bit accumulator (overlaps_c, Overlap.cpp:143-158) and finally normalises
@@ -9,7 +10,7 @@
 //   plan kernel   : per (frame, block) -> per-reference weights (fp64 exactly as MVDegrains.h:184-223) and the byte
 //                   offset of the motion-compensated block inside the reference super frame (MVDegrains.h:192-206)
 //   gather kernel : per output sample  -> blend + window + normalise + uncovered strips + LimitChanges.
-#include "mvx_fps_shared.h"
+#include "mvx_block_shared.h"
 
 #define MOTION_USE_CHROMA_MOTION 8
 
@@ -66,13 +67,9 @@ extern "C" __attribute__((visibility("default"))) void mvx_scale_thscd(int64_t *
 
 // ------------------------------------------------------------------------------------------------ shared device structs
 
-struct DGParams {
-    int nRefs, nBlkX, nBlkY, nBlk, pel, logPel, bits, bps, nplanes, overlap;
-    int nLvCount;            // levels in a blob; the level-0 record is found by walking the per-plane size headers like fgopUpdate (Fakery.c:112-123)
+struct DGParams : BlkGeom {
+    int nRefs;
     long long thSAD[2];
-    long long thscd1; int thscd2;
-    PlaneG pl[3];
-    const int16_t *win[3];
     // compensate only
     long long cthSAD; int time256, scBehavior;
 };
@@ -104,12 +101,6 @@ __global__ __launch_bounds__(256) void usable_kernel(const DGParams *Pp, const D
     const int f = blockIdx.y, r = blockIdx.x;
     const bool ok = fps_block_usable(jobs[f].blobs[r], jobs[f].refs[r][0] != nullptr, P.nLvCount, P.nBlk, P.thscd1, P.thscd2);
     if (threadIdx.x == 0) usable[f * 12 + r] = ok;
-}
-
-// MVDegrains.h:184-189
-__device__ __forceinline__ int degrain_weight(long long thSAD, long long blockSAD) {
-    if (blockSAD >= thSAD) return 0;
-    return (int)((double)((thSAD - blockSAD) * (thSAD + blockSAD) * 256) / (double)(thSAD * thSAD + blockSAD * blockSAD));
 }
 
 // (r6: left alone the register allocator takes 162 registers for six references -- three waves per SIMD; asked for six it needs 71 and spills nothing:
@@ -155,7 +146,7 @@ __global__ __launch_bounds__(256, dg_plan_waves(NR)) void degrain_plan_kernel(co
                 // wave's 16-byte loads at 2-byte-aligned addresses cost the texture addresser 64 cycles instead of 16 (tools/micro/ta_pattern.hip, patterns
                 // 21 / 22), and these loads keep it busy 78 % of the kernel's run time (profiles/r4_stream_kernel_counters.txt)
                 if (g.shadow && (rec.off[r] & 2u)) rec.off[r] = (rec.off[r] & ~3u) + (unsigned)g.shadow;
-                W[r] = degrain_weight(P.thSAD[g.thIdx], sad[r]);
+                W[r] = dn_weight(P.thSAD[g.thIdx], sad[r]); // MVDegrains.h:184-189
             }
             WSum += W[r];
         }
@@ -196,18 +187,17 @@ __global__ __launch_bounds__(256) void degrain_kernel(const DGParams *Pp, const 
         out = (T)(sum >> 8);
     } else {
         // blocks covering this sample: bx in [bx0, bx1], by in [by0, by1]
-        int bx1 = x / g.stepX; if (bx1 > P.nBlkX - 1) bx1 = P.nBlkX - 1;
-        int bx0 = x - g.blkW + 1 <= 0 ? 0 : (x - g.blkW + g.stepX) / g.stepX;
-        int by1 = y / g.stepY; if (by1 > P.nBlkY - 1) by1 = P.nBlkY - 1;
-        int by0 = y - g.blkH + 1 <= 0 ? 0 : (y - g.blkH + g.stepY) / g.stepY;
+        int bx0, bx1, by0, by1;
+        blk_cover(x, g.blkW, g.stepX, P.nBlkX, bx0, bx1);
+        blk_cover(y, g.blkH, g.stepY, P.nBlkY, by0, by1);
         unsigned acc = 0;
         const int16_t *win = P.win[p];
         for (int by = by0; by <= by1; by++) {
             const int py = y - by * g.stepY;
-            const int wby = by == 0 ? 0 : (by == P.nBlkY - 1 ? 6 : 3); // ((by + nBlkY - 3) / (nBlkY - 2)) * 3, MVDegrains.cpp:256
+            const int wby = BLK_WIN_ROW(by, P.nBlkY);
             for (int bx = bx0; bx <= bx1; bx++) {
                 const int px = x - bx * g.stepX;
-                const int wbx = bx == P.nBlkX - 1 ? 2 : (bx == 0 ? 0 : 1); // :260-262,285
+                const int wbx = BLK_WIN_COL(bx, P.nBlkX);
                 const PlanRec &R = pl[by * P.nBlkX + bx];
                 int sum = 128 + s * R.wsrc;
 #pragma unroll
@@ -239,22 +229,6 @@ __global__ __launch_bounds__(256) void degrain_kernel(const DGParams *Pp, const 
 // Same arithmetic per sample as degrain_kernel (Degrain_C + overlaps_c + ToPixels + LimitChanges).
 // Pointers that come out of the job tables are generic ("flat") to the compiler; flat loads are slower and every one of them is waited
 // for with vmcnt(0) lgkmcnt(0).  The vector helpers therefore take global-address-space pointers (dg_gl casts).
-// the same in two steps, so that several loads can be in flight before the first one is unpacked
-template <typename T, int W> struct DgRaw { unsigned d[(W * (int)sizeof(T) + 3) / 4]; };
-template <typename T, int W> __device__ __forceinline__ DgRaw<T, W> dg_load_raw(DG_GL const unsigned char *p) {
-    constexpr int BYTES = W * (int)sizeof(T);
-    DgRaw<T, W> r;
-    if (BYTES >= 16) {
-#pragma unroll
-        for (int k = 0; k < BYTES / 16; k++) { dg_uv4 t = *(DG_GL const dg_uv4 *)(p + 16 * k); r.d[4 * k] = t[0]; r.d[4 * k + 1] = t[1]; r.d[4 * k + 2] = t[2]; r.d[4 * k + 3] = t[3]; }
-    } else if (BYTES == 8) { dg_uv2 t = *(DG_GL const dg_uv2 *)p; r.d[0] = t[0]; r.d[1] = t[1]; }
-    else if (BYTES == 4) r.d[0] = *(DG_GL const dg_uv1 *)p;
-    else r.d[0] = *(DG_GL const dg_uh1 *)p;
-    return r;
-}
-template <typename T, int W> __device__ __forceinline__ int dg_sample(const DgRaw<T, W> &r, int i) {
-    return sizeof(T) == 2 ? (int)((r.d[i >> 1] >> (16 * (i & 1))) & 0xffffu) : (int)((r.d[i >> 2] >> (8 * (i & 3))) & 0xffu);
-}
 // r5: the weighted sum of TWO references per instruction for 16-bit samples (MVDegrains.h:31-53: sum += ref * W, all terms non-negative and < 2^24):
 // v_perm_b32 pairs sample i of reference a with sample i of reference b, v_dot2_u32_u16 multiplies the pair by the two weights and adds.  Per sample and pair of
 // references 2 instructions instead of 4 (two shifts / masks + two multiply-adds); same integers.
@@ -320,8 +294,8 @@ __global__ __launch_bounds__(256, (dg_cell_waves<NR, W>())) void degrain_cell_ke
     // profiles/r6_degrain_window_plan_ab.txt)
     if (TILED && g.process && P.overlap) { // (uniform over the workgroup; the host launches this kernel only when the tile fits: dg_tile_fits)
         const int xt = bxi * 32 * W, yt = byi * 8;
-        tBx = __builtin_amdgcn_readfirstlane(xt - g.blkW + 1 <= 0 ? 0 : (xt - g.blkW + g.stepX) / g.stepX);
-        tBy = __builtin_amdgcn_readfirstlane(yt - g.blkH + 1 <= 0 ? 0 : (yt - g.blkH + g.stepY) / g.stepY);
+        tBx = __builtin_amdgcn_readfirstlane(BLK_FIRST(xt, g.blkW, g.stepX));
+        tBy = __builtin_amdgcn_readfirstlane(BLK_FIRST(yt, g.blkH, g.stepY));
         const int bxHi = min(bxi * 32 + 31, P.nBlkX - 1), byHi = min((yt + 7) / g.stepY, P.nBlkY - 1);
         tNbx = __builtin_amdgcn_readfirstlane(bxHi - tBx + 1);
         const int nby = __builtin_amdgcn_readfirstlane(byHi - tBy + 1);
@@ -378,10 +352,10 @@ __global__ __launch_bounds__(256, (dg_cell_waves<NR, W>())) void degrain_cell_ke
         }
     } else if (g.process && x0 < g.WB && y < g.HB) { // MVDegrains.cpp:211-214,238-249,290-298: uncovered strips keep the source
         const PlanRec *pl = plan + ((size_t)f * 2 + (p ? 1 : 0)) * P.nBlk;
-        int bx1 = c; if (bx1 > P.nBlkX - 1) bx1 = P.nBlkX - 1;
-        const int bx0 = x0 - g.blkW + 1 <= 0 ? 0 : (x0 - g.blkW + g.stepX) / g.stepX;
-        int by1 = y / g.stepY; if (by1 > P.nBlkY - 1) by1 = P.nBlkY - 1;
-        const int by0 = y - g.blkH + 1 <= 0 ? 0 : (y - g.blkH + g.stepY) / g.stepY;
+        int bx1 = c; if (bx1 > P.nBlkX - 1) bx1 = P.nBlkX - 1; // (the step is the cell: no division)
+        const int bx0 = BLK_FIRST(x0, g.blkW, g.stepX);
+        int by0, by1;
+        blk_cover(y, g.blkH, g.stepY, P.nBlkY, by0, by1);
         unsigned acc[W];
 #pragma unroll
         for (int i = 0; i < W; i++) acc[i] = 0;
@@ -395,12 +369,12 @@ __global__ __launch_bounds__(256, (dg_cell_waves<NR, W>())) void degrain_cell_ke
         for (int r = 0; r < NR; r++) refp[r] = J.refs[r][p] ? J.refs[r][p] : (safe ? safe : J.src[p]);
         for (int by = by0; by <= by1; by++) {
             const int py = y - by * g.stepY;
-            const int wby = by == 0 ? 0 : (by == P.nBlkY - 1 ? 6 : 3);
+            const int wby = BLK_WIN_ROW(by, P.nBlkY);
             for (int bx = bx0; bx <= bx1; bx++) {
                 const int px = x0 - bx * g.stepX;   // >= 0; the block covers samples i < blkW - px of this cell
                 const int nv = g.blkW - px;
                 if (nv <= 0) continue;
-                const int wbx = bx == P.nBlkX - 1 ? 2 : (bx == 0 ? 0 : 1);
+                const int wbx = BLK_WIN_COL(bx, P.nBlkX);
                 PlanRec R;
                 if (TILED) __builtin_memcpy(&R, &tileD[((by - tBy) * tNbx + (bx - tBx)) * RD], sizeof(PlanRec));
                 else R = pl[by * P.nBlkX + bx];
@@ -526,18 +500,17 @@ __global__ __launch_bounds__(256) void compensate_kernel(const DGParams *Pp, con
         drow[x] = ((const T *)((R.fromRef ? refSup : srcSup) + R.off[c] + (long long)py * g.supPitch))[px];
         return;
     }
-    int bx1 = x / g.stepX; if (bx1 > P.nBlkX - 1) bx1 = P.nBlkX - 1;
-    int bx0 = x - g.blkW + 1 <= 0 ? 0 : (x - g.blkW + g.stepX) / g.stepX;
-    int by1 = y / g.stepY; if (by1 > P.nBlkY - 1) by1 = P.nBlkY - 1;
-    int by0 = y - g.blkH + 1 <= 0 ? 0 : (y - g.blkH + g.stepY) / g.stepY;
+    int bx0, bx1, by0, by1;
+    blk_cover(x, g.blkW, g.stepX, P.nBlkX, bx0, bx1);
+    blk_cover(y, g.blkH, g.stepY, P.nBlkY, by0, by1);
     unsigned acc = 0;
     const int16_t *win = P.win[p];
     for (int by = by0; by <= by1; by++) {
         const int py = y - by * g.stepY;
-        const int wby = by == 0 ? 0 : (by == P.nBlkY - 1 ? 6 : 3);
+        const int wby = BLK_WIN_ROW(by, P.nBlkY);
         for (int bx = bx0; bx <= bx1; bx++) {
             const int px = x - bx * g.stepX;
-            const int wbx = bx == P.nBlkX - 1 ? 2 : (bx == 0 ? 0 : 1);
+            const int wbx = BLK_WIN_COL(bx, P.nBlkX);
             const CPlanRec R = pl[by * P.nBlkX + bx];
             const int val = ((const T *)((R.fromRef ? refSup : srcSup) + R.off[c] + (long long)py * g.supPitch))[px];
             acc += (unsigned)((val * (int)win[(wby + wbx) * g.blkW * g.blkH + py * g.blkW + px]) >> 6);
@@ -586,44 +559,10 @@ struct DGCommon {
     DevBuf<DGJob> dJobs;          // these two grow to twice the call's jobs
     DevBuf<int> dUsable;
     DevBuf<unsigned char> dPlan;  // grows to one and a half times the call's plan
-    DevBuf<int16_t> dWin[2];
-    int nWinClasses = 1;
+    BlkWin win;
 };
 struct mvx_degrain : DGCommon { int radius; };
 struct mvx_compensate : DGCommon {};
-
-static int fill_common(DGCommon *h, const mvx_analysis_data *ad, const mvx_super_info &si, const ptrdiff_t src_pitch[3],
-                       const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], char *err) {
-    DGParams &P = h->P;
-    memset(&P, 0, sizeof(P));
-    P.nBlkX = ad->nBlkX; P.nBlkY = ad->nBlkY; P.nBlk = ad->nBlkX * ad->nBlkY;
-    P.pel = ad->nPel; P.logPel = ad->nPel == 4 ? 2 : ad->nPel == 2 ? 1 : 0;
-    P.bits = si.bits; P.bps = (si.bits + 7) / 8; P.nplanes = si.num_planes;
-    P.overlap = ad->nOverlapX > 0 || ad->nOverlapY > 0;
-    if (P.overlap && (ad->nBlkX < 3 || ad->nBlkY < 3)) MVX_FAIL("overlap needs at least 3x3 blocks (window selection divides by nBlk-2).");
-    P.nLvCount = ad->nLvCount;
-    fps_fill_planes(P.pl, ad, si, src_pitch, super_pitch, dst_pitch);
-    if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) MVX_FAIL("U and V super planes must share one pitch.");
-    h->nWinClasses = si.num_planes > 1 ? 2 : 1;
-    return MVX_OK;
-}
-
-// device state is created on first use so that argument validation works without a GPU
-static int finish_common(DGCommon *h) {
-    if (h->dP.p) return MVX_OK;
-    DGParams &P = h->P;
-    if (P.overlap) {
-        for (int c = 0; c < h->nWinClasses; c++) {
-            const PlaneG &g = P.pl[c];
-            std::vector<int16_t> w(9 * g.blkW * g.blkH);
-            mvx_over_windows(w.data(), g.blkW, g.blkH, g.ovX, g.ovY);
-            HIP_CHECK(h->dWin[c].reserve(w.size()));
-            HIP_CHECK(hipMemcpy(h->dWin[c].p, w.data(), w.size() * 2, hipMemcpyHostToDevice));
-        }
-        P.win[0] = h->dWin[0].p; P.win[1] = P.win[2] = h->dWin[1].p;
-    }
-    return fps_upload_params(h->dP, P);
-}
 
 static int ensure_jobs(DGCommon *h, int nframes, size_t planBytesPerFrame) {
     const size_t n = (size_t)nframes, need = planBytesPerFrame * n;
@@ -653,39 +592,18 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_create(const m
     if (radius < 1 || radius > 6) MVX_FAIL("Degrain: radius must be between 1 and 6.");
     char name[16]; // the reference's filter name carries the radius
     snprintf(name, sizeof(name), "Degrain%d", radius);
-    long long thSAD0 = a->thsad == MVX_UNSET ? 400 : a->thsad;
-    long long thSAD1 = a->thsadc == MVX_UNSET ? thSAD0 : a->thsadc;
-    int plane = a->plane == MVX_UNSET ? 4 : a->plane;
-    if (plane < 0 || plane > 4) MVX_FAIL("%s: plane must be between 0 and 4 (inclusive).", name);
-    static const int planes[5] = { 1, 2, 4, 6, 7 };
-    const int YUVplanes = planes[plane];
-    int64_t nSCD1, nSCD1_old; int32_t nSCD2;
-    if (int rc = mvx_resolve_thscd(name, a->thscd1, a->thscd2, ad, &nSCD1, &nSCD2, err, &nSCD1_old)) return rc;
-    thSAD0 = thSAD0 * nSCD1 / nSCD1_old; // :658-659
-    thSAD1 = thSAD1 * nSCD1 / nSCD1_old;
-    if (thSAD0 >= 2147483647LL || thSAD1 >= 2147483647LL) {
-        const bool c = thSAD0 < 2147483647LL;
-        MVX_FAIL("%s: with this block size and video format, thsad%s must not exceed %lld or some calculations would overflow.", name, c ? "c" : "",
-                 (long long)(2147483647LL * nSCD1_old / nSCD1));
-    }
-    if (!mvx_super_fits(ad, si, true)) MVX_FAIL("%s: wrong source or super clip frame size.", name);
-    const int pixelMax = (1 << si.bits) - 1;
-    int limit = a->limit == MVX_UNSET ? pixelMax : a->limit;
-    int limitc = a->limitc == MVX_UNSET ? limit : a->limitc;
-    if (limit < 0 || limit > pixelMax) MVX_FAIL("%s: limit must be between 0 and %d (inclusive).", name, pixelMax);
-    if (limitc < 0 || limitc > pixelMax) MVX_FAIL("%s: limitc must be between 0 and %d (inclusive).", name, pixelMax);
-
-    mvx_degrain *h = new mvx_degrain();
+    mvx_degrain_n_args an; // (DegrainN without far thresholds: dg_resolve)
+    an.radius = radius; an.thsad = a->thsad; an.thsadc = a->thsadc; an.thsad2 = an.thsadc2 = MVX_UNSET;
+    an.plane = a->plane; an.limit = a->limit; an.limitc = a->limitc; an.thscd1 = a->thscd1; an.thscd2 = a->thscd2;
+    DgResolved r;
+    if (int rc = dg_resolve(name, &an, false, ad, si, &r, err)) return rc;
+    mvx_degrain *h;
+    if (int rc = blk_new(&h, ad, si, src_pitch, super_pitch, dst_pitch, err)) return rc;
     h->radius = radius;
-    int rc = fill_common(h, ad, si, src_pitch, super_pitch, dst_pitch, err);
-    if (rc) { delete h; return rc; }
     DGParams &P = h->P;
     P.nRefs = 2 * radius;
-    P.thSAD[0] = thSAD0; P.thSAD[1] = thSAD1; P.thscd1 = nSCD1; P.thscd2 = nSCD2;
-    P.pl[0].process = !!(YUVplanes & 1);
-    P.pl[1].process = !!(YUVplanes & 2 & si.modeYUV);
-    P.pl[2].process = !!(YUVplanes & 4 & si.modeYUV);
-    P.pl[0].limit = limit; P.pl[1].limit = P.pl[2].limit = limitc;
+    P.thSAD[0] = r.info.thsad_d[0]; P.thSAD[1] = r.info.thsadc_d[0];
+    dg_apply(P, r, si);
     *out = h;
     return MVX_OK;
 }
@@ -730,7 +648,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_frames(mvx_deg
     if (nframes <= 0) return MVX_OK;
     hipStream_t st = (hipStream_t)stream;
     CallGuard::Scope scope(d->guard, st);
-    int rc = finish_common(d);
+    int rc = blk_upload(d->dP, d->P, d->win);
     if (rc) return rc;
     const DGParams &P = d->P;
     if ((rc = ensure_jobs(d, nframes, plan_rec_bytes(P.nRefs) * 2 * (size_t)P.nBlk))) return rc;
@@ -778,24 +696,14 @@ extern "C" __attribute__((visibility("default"))) int mvx_compensate_create(cons
                                      const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_compensate **out, char *err) {
     MVX_CREATE_BEGIN(out);
     const mvx_super_info &si = sup->info;
-    const int scBehavior = a->scbehavior == MVX_UNSET ? 1 : !!a->scbehavior;
-    long long thSAD = a->thsad == MVX_UNSET ? 10000 : a->thsad;
-    const double time = a->time;
-    if (time < 0.0 || time > 100.0) MVX_FAIL("Compensate: time must be between 0.0 and 100.0 (inclusive).");
-    int64_t nSCD1, nSCD1_old; int32_t nSCD2;
-    if (int rc = mvx_resolve_thscd("Compensate", a->thscd1, a->thscd2, ad, &nSCD1, &nSCD2, err, &nSCD1_old)) return rc;
-    thSAD = thSAD * nSCD1 / nSCD1_old; // :521
-    if (!mvx_super_fits(ad, si, true)) MVX_FAIL("Compensate: wrong source or super clip frame size.");
-    if (a->fields != MVX_UNSET && a->fields && ad->nPel < 2) MVX_FAIL("Compensate: fields option requires pel > 1."); // :514-517
-    mvx_compensate *h = new mvx_compensate();
-    int rc = fill_common(h, ad, si, nullptr, super_pitch, dst_pitch, err);
-    if (rc) { delete h; return rc; }
+    CompResolved r;
+    if (int rc = comp_resolve("Compensate", a, ad, si, &r, err)) return rc;
+    mvx_compensate *h;
+    if (int rc = blk_new(&h, ad, si, nullptr, super_pitch, dst_pitch, err)) return rc;
     DGParams &P = h->P;
     P.nRefs = 1;
-    P.thscd1 = nSCD1; P.thscd2 = nSCD2; P.cthSAD = thSAD;
-    P.time256 = (int)(time * 256 / 100); // :560
-    P.scBehavior = scBehavior;
-    if (!(si.modeYUV & 6)) P.nplanes = 1; // num_planes :147-149
+    P.cthSAD = r.thSAD; P.time256 = r.time256; P.scBehavior = r.scBehavior;
+    comp_apply(P, r, si);
     *out = h;
     return MVX_OK;
 }
@@ -806,7 +714,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_compensate_frames(mvx_
     if (nframes <= 0) return MVX_OK;
     hipStream_t st = (hipStream_t)stream;
     CallGuard::Scope scope(c->guard, st);
-    int rc = finish_common(c);
+    int rc = blk_upload(c->dP, c->P, c->win);
     if (rc) return rc;
     const DGParams &P = c->P;
     if ((rc = ensure_jobs(c, nframes, sizeof(CPlanRec) * (size_t)P.nBlk))) return rc;
@@ -997,18 +905,17 @@ __global__ __launch_bounds__(256) void blockfps_kernel(const DGParams *Pp, const
         const int bx = x / g.blkW, by = y / g.blkH;
         out = (T)result(pl[by * P.nBlkX + bx], x - bx * g.blkW, y - by * g.blkH);
     } else {
-        int bx1 = x / g.stepX; if (bx1 > P.nBlkX - 1) bx1 = P.nBlkX - 1;
-        const int bx0 = x - g.blkW + 1 <= 0 ? 0 : (x - g.blkW + g.stepX) / g.stepX;
-        int by1 = y / g.stepY; if (by1 > P.nBlkY - 1) by1 = P.nBlkY - 1;
-        const int by0 = y - g.blkH + 1 <= 0 ? 0 : (y - g.blkH + g.stepY) / g.stepY;
+        int bx0, bx1, by0, by1;
+        blk_cover(x, g.blkW, g.stepX, P.nBlkX, bx0, bx1);
+        blk_cover(y, g.blkH, g.stepY, P.nBlkY, by0, by1);
         unsigned acc = 0;
         const int16_t *win = P.win[p];
         for (int by = by0; by <= by1; by++) {
             const int py = y - by * g.stepY;
-            const int wby = by == 0 ? 0 : (by == P.nBlkY - 1 ? 6 : 3);
+            const int wby = BLK_WIN_ROW(by, P.nBlkY);
             for (int bx = bx0; bx <= bx1; bx++) {
                 const int px = x - bx * g.stepX;
-                const int wbx = bx == P.nBlkX - 1 ? 2 : (bx == 0 ? 0 : 1);
+                const int wbx = BLK_WIN_COL(bx, P.nBlkX);
                 const int val = (T)result(pl[by * P.nBlkX + bx], px, py);
                 acc += (unsigned)((val * (int)win[(wby + wbx) * g.blkW * g.blkH + py * g.blkW + px]) >> 6);
             }
@@ -1154,9 +1061,8 @@ extern "C" __attribute__((visibility("default"))) int mvx_blockfps_create(const 
     if (int rc = mvx_pair_checks("BlockFPS", bw, fw, err)) return rc;
     if (fps_num == 0 || fps_den == 0) MVX_FAIL("BlockFPS: The input clip must have a frame rate. Invoke AssumeFPS if necessary.");
     if (!mvx_super_fits(bw, si, true)) MVX_FAIL("BlockFPS: wrong source or super clip frame size.");
-    mvx_blockfps *h = new mvx_blockfps();
-    int rc = fill_common(h, bw, si, clip_pitch, super_pitch, dst_pitch, err);
-    if (rc) { delete h; return rc; }
+    mvx_blockfps *h;
+    if (int rc = blk_new(&h, bw, si, clip_pitch, super_pitch, dst_pitch, err)) return rc;
     DGParams &P = h->P;
     if (!(si.modeYUV & 6)) P.nplanes = 1;
     P.nRefs = 2; P.thscd1 = thscd1; P.thscd2 = thscd2;
@@ -1185,7 +1091,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_blockfps_frames(mvx_bl
     if (nframes <= 0) return MVX_OK;
     hipStream_t st = (hipStream_t)stream;
     CallGuard::Scope scope(b->guard, st);
-    int rc = finish_common(b);
+    int rc = blk_upload(b->dP, b->P, b->win);
     if (rc) return rc;
     const DGParams &P = b->P;
     BFParams &B = b->B;

@@ -1,5 +1,6 @@
 // mvx_degrain_n.hip -- mv.DegrainN on gfx950: the block filter of mvx_degrain.hip at a temporal radius of 1..24 (2..48 references), each
-// reference weighed against the threshold of its own temporal distance.
+// reference weighed against the threshold of its own temporal distance.  What the two share (geometry, windows, creation arguments, the usable
+// kernel, block cover, loads) is in mvx_block_shared.h.
 //
 // The reference's arithmetic is a template over the radius -- Degrain_C<radius> (MVDegrains.h:30-53), useBlock (:192-206), DegrainWeight
 // (:184-189), normaliseWeights<radius> (:208-223) -- and only its six registerFunction calls stop at 6.  This file is that template read at
@@ -17,8 +18,7 @@
 //   out16   (mvx_degrain_n_create_out16) an 8-bit clip written as 16-bit planes: the cell kernel with an output sample type TO of its own.
 //           A block's value is the sum before its >> 8, S = WSrc * src + sum of W_r * ref_r (0..65280), which is what the 16-bit arithmetic
 //           gives on samples shifted left by 8: (128 + 256 * S) >> 8 = S.  Loads, plan and lists are those of the 8-bit clip.
-#include "mvx_fps_shared.h"
-#include "mvx_degrain_n_weights.h"
+#include "mvx_block_shared.h"
 
 static_assert(DN_MAX_RADIUS == MVX_DEGRAIN_N_MAX_RADIUS, "radius limit");
 
@@ -26,13 +26,9 @@ static_assert(DN_MAX_RADIUS == MVX_DEGRAIN_N_MAX_RADIUS, "radius limit");
 
 // ------------------------------------------------------------------------------------------------ device structs
 
-struct DNParams {
-    int nRefs, nBlkX, nBlkY, nBlk, pel, logPel, bits, bps, nplanes, overlap;
-    int nLvCount;
+struct DNParams : BlkGeom {
+    int nRefs;
     int recBytes;            // stride of a plan slot: 16 + 8 * (nRefs rounded up to a multiple of DN_K)
-    long long thscd1; int thscd2;
-    PlaneG pl[3];
-    const int16_t *win[3];
     long long thSAD[2][DN_MAX_RADIUS]; // [luma / chroma][distance - 1]
 };
 
@@ -44,16 +40,6 @@ static_assert(sizeof(DNHead) == 16 && sizeof(DNEntry) == 8, "plan slot layout");
 static int dn_rec_bytes(int nrefs) { return 16 + 8 * ((nrefs + DN_K - 1) / DN_K * DN_K); }
 
 // ------------------------------------------------------------------------------------------------ kernels
-
-// per (job, reference): 0 when the reference's vectors are not usable (fgopIsUsable, or a reference frame outside the clip, which may have
-// no blob at all), else the byte offset of level 0 inside the blob (a walk over the per-level size headers, done once here)
-__global__ __launch_bounds__(256) void dn_usable_kernel(const DNParams *Pp, const unsigned char *const *refs, const unsigned char *const *blobs, unsigned *lv0) {
-    const DNParams &P = *Pp;
-    const int k = blockIdx.y * P.nRefs + blockIdx.x;
-    const unsigned char *blob = blobs[k];
-    const bool ok = fps_block_usable(blob, refs[(size_t)k * 3] != nullptr, P.nLvCount, P.nBlk, P.thscd1, P.thscd2);
-    if (threadIdx.x == 0) lv0[k] = ok ? (unsigned)((const unsigned char *)mvx_level0(blob, P.nLvCount) - blob) : 0u;
-}
 
 // one thread per (job, block): both plane classes' lists.  The references are walked DN_K at a time so that DN_K vector loads are in flight;
 // raw weights go into the slot as they are found, and are normalised in place once WSum is known.
@@ -107,37 +93,6 @@ __global__ __launch_bounds__(256) void dn_plan_kernel(const DNParams *Pp, const 
     }
 }
 
-// BYTES consecutive bytes from an arbitrarily aligned address, as dwords
-template <int BYTES> struct DnRaw { unsigned d[(BYTES + 3) / 4]; };
-template <int BYTES> __device__ __forceinline__ DnRaw<BYTES> dn_load_raw(DG_GL const unsigned char *p) {
-    DnRaw<BYTES> r;
-    if constexpr (BYTES == 16) { const dg_uv4 t = *(DG_GL const dg_uv4 *)p; r.d[0] = t[0]; r.d[1] = t[1]; r.d[2] = t[2]; r.d[3] = t[3]; }
-    else if constexpr (BYTES == 8) { const dg_uv2 t = *(DG_GL const dg_uv2 *)p; r.d[0] = t[0]; r.d[1] = t[1]; }
-    else if constexpr (BYTES == 4) r.d[0] = *(DG_GL const dg_uv1 *)p;
-    else if constexpr (BYTES == 2) r.d[0] = *(DG_GL const dg_uh1 *)p;
-    else r.d[0] = *p;
-    return r;
-}
-template <typename T, int BYTES> __device__ __forceinline__ int dn_sample(const DnRaw<BYTES> &r, int i) {
-    return sizeof(T) == 2 ? (int)((r.d[i >> 1] >> (16 * (i & 1))) & 0xffffu) : (int)((r.d[i >> 2] >> (8 * (i & 3))) & 0xffu);
-}
-// W samples of type T to an arbitrarily aligned address (dg_store's widths start at two bytes; a cell here can be one 8-bit sample)
-template <typename T, int W> __device__ __forceinline__ void dn_store(DG_GL unsigned char *p, const int *v) {
-    constexpr int BYTES = W * (int)sizeof(T);
-    unsigned d[(BYTES + 3) / 4];
-#pragma unroll
-    for (int k = 0; k < (BYTES + 3) / 4; k++) d[k] = 0;
-#pragma unroll
-    for (int i = 0; i < W; i++) {
-        if (sizeof(T) == 2) d[i >> 1] |= (unsigned)v[i] << (16 * (i & 1));
-        else d[i >> 2] |= (unsigned)v[i] << (8 * (i & 3));
-    }
-    if constexpr (BYTES == 16) { const dg_uv4 t = { d[0], d[1], d[2], d[3] }; *(DG_GL dg_uv4 *)p = t; }
-    else if constexpr (BYTES == 8) { const dg_uv2 t = { d[0], d[1] }; *(DG_GL dg_uv2 *)p = t; }
-    else if constexpr (BYTES == 4) *(DG_GL dg_uv1 *)p = d[0];
-    else if constexpr (BYTES == 2) *(DG_GL dg_uh1 *)p = (unsigned short)d[0];
-    else *p = (unsigned char)d[0];
-}
 typedef unsigned dn_v4 __attribute__((ext_vector_type(4), aligned(16)));
 
 // the cell's row inside one block: Degrain_C (MVDegrains.h:30-53) over the block's list, DN_K entries at a time.  slot: the block's plan slot
@@ -158,14 +113,14 @@ __device__ __forceinline__ void dn_block_sum(DG_GL const unsigned char *slot, co
         unsigned off[DN_K], wr[DN_K]; // DNEntry: offset, weight | reference << 16
 #pragma unroll
         for (int k = 0; k < DN_K; k += 2) { off[k] = ent[k / 2][0]; wr[k] = ent[k / 2][1]; off[k + 1] = ent[k / 2][2]; wr[k + 1] = ent[k / 2][3]; }
-        DnRaw<W * (int)sizeof(T)> raw[DN_K];
+        DgRaw<T, W> raw[DN_K];
         int w[DN_K];
 #pragma unroll
         for (int k = 0; k < DN_K; k++) {
             const bool valid = e + k < count; // (k == 0 always is)
             const unsigned o = valid ? off[k] : off[0], r = (valid ? wr[k] : wr[0]) >> 16;
             w[k] = valid ? (int)(short)(wr[k] & 0xffffu) : 0;
-            raw[k] = dn_load_raw<W * (int)sizeof(T)>(dg_gl((const unsigned char *)refB[r]) + o + rowOff);
+            raw[k] = dg_load_raw<T, W>(dg_gl((const unsigned char *)refB[r]) + o + rowOff);
         }
         if (e + DN_K < count) {
 #pragma unroll
@@ -174,7 +129,7 @@ __device__ __forceinline__ void dn_block_sum(DG_GL const unsigned char *slot, co
 #pragma unroll
         for (int k = 0; k < DN_K; k++) {
 #pragma unroll
-            for (int i = 0; i < W; i++) sum[i] += dn_sample<T>(raw[k], i) * w[k];
+            for (int i = 0; i < W; i++) sum[i] += dg_sample(raw[k], i) * w[k];
         }
     }
 }
@@ -203,11 +158,8 @@ __global__ __launch_bounds__(256) void dn_cell_kernel(const DNParams *Pp, const 
     unsigned char *drow = J.dst[p] + (long long)y * g.dstPitch + (long long)x0 * sizeof(TO);
     const bool fullW = x0 + W <= g.W;
     int s[W];
-    if (fullW) {
-        const DnRaw<W * (int)sizeof(T)> raw = dn_load_raw<W * (int)sizeof(T)>(dg_gl(srow));
-#pragma unroll
-        for (int i = 0; i < W; i++) s[i] = dn_sample<T>(raw, i);
-    } else {
+    if (fullW) dg_load<T, W>(dg_gl(srow), s);
+    else {
 #pragma unroll
         for (int i = 0; i < W; i++) s[i] = x0 + i < g.W ? (int)((const T *)srow)[i] : 0;
     }
@@ -229,27 +181,26 @@ __global__ __launch_bounds__(256) void dn_cell_kernel(const DNParams *Pp, const 
             for (int i = 0; i < W; i++) out[i] = OUT16 ? sum[i] : (int)(T)(sum[i] >> 8);
         } else {
             // blocks covering this cell: bx in [bx0, bx1], by in [by0, by1]
-            int bx1 = x0 / g.stepX; if (bx1 > P.nBlkX - 1) bx1 = P.nBlkX - 1;
-            const int bx0 = x0 - g.blkW + 1 <= 0 ? 0 : (x0 - g.blkW + g.stepX) / g.stepX;
-            int by1 = y / g.stepY; if (by1 > P.nBlkY - 1) by1 = P.nBlkY - 1;
-            const int by0 = y - g.blkH + 1 <= 0 ? 0 : (y - g.blkH + g.stepY) / g.stepY;
+            int bx0, bx1, by0, by1;
+            blk_cover(x0, g.blkW, g.stepX, P.nBlkX, bx0, bx1);
+            blk_cover(y, g.blkH, g.stepY, P.nBlkY, by0, by1);
             unsigned acc[W];
 #pragma unroll
             for (int i = 0; i < W; i++) acc[i] = 0;
             const int16_t *win = P.win[p];
             for (int by = by0; by <= by1; by++) {
                 const int py = y - by * g.stepY;
-                const int wby = by == 0 ? 0 : (by == P.nBlkY - 1 ? 6 : 3); // ((by + nBlkY - 3) / (nBlkY - 2)) * 3, MVDegrains.cpp:256
+                const int wby = BLK_WIN_ROW(by, P.nBlkY);
                 for (int bx = bx0; bx <= bx1; bx++) {
                     const int px = x0 - bx * g.stepX; // 0 <= px <= blkW - W
-                    const int wbx = bx == P.nBlkX - 1 ? 2 : (bx == 0 ? 0 : 1); // :260-262,285
+                    const int wbx = BLK_WIN_COL(bx, P.nBlkX);
                     DG_GL const unsigned char *slot = pl + (size_t)(by * P.nBlkX + bx) * P.recBytes;
-                    const DnRaw<W * 2> wr = dn_load_raw<W * 2>(dg_gl((const unsigned char *)(win + (wby + wbx) * g.blkW * g.blkH + py * g.blkW + px)));
+                    const DgRaw<unsigned short, W> wr = dg_load_raw<unsigned short, W>(dg_gl((const unsigned char *)(win + (wby + wbx) * g.blkW * g.blkH + py * g.blkW + px)));
                     dn_block_sum<T, W, OUT16 ? 0 : 128>(slot, refB, (long long)py * g.supPitch + (long long)px * sizeof(T), s, sum);
 #pragma unroll
                     for (int i = 0; i < W; i++) { // overlaps_c, Overlap.cpp:143-158
                         const int val = OUT16 ? sum[i] : (int)(T)(sum[i] >> 8);
-                        acc[i] += (unsigned)((val * dn_sample<unsigned short>(wr, i)) >> 6);
+                        acc[i] += (unsigned)((val * dg_sample(wr, i)) >> 6);
                     }
                 }
             }
@@ -270,7 +221,7 @@ __global__ __launch_bounds__(256) void dn_cell_kernel(const DNParams *Pp, const 
             }
         }
     }
-    if (fullW) dn_store<TO, W>(dg_glw(drow), out);
+    if (fullW) dg_store<TO, W>(dg_glw(drow), out);
     else {
 #pragma unroll
         for (int i = 0; i < W; i++) if (x0 + i < g.W) ((TO *)drow)[i] = (TO)out[i];
@@ -287,19 +238,9 @@ struct mvx_degrain_n {
     DevBuf<unsigned char> dTables;   // per call: the jobs, then the reference planes [job][reference][plane], then the blobs [job][reference]
     DevBuf<unsigned> dLv0;
     DevBuf<unsigned char> dPlan;
-    DevBuf<int16_t> dWin[2];
-    int nWinClasses = 1;
+    BlkWin win;
     bool out16 = false;              // 8-bit clip, 16-bit output planes
 };
-
-// the scaled thresholds of one plane class over the distances; 0, or which argument reaches INT_MAX (MVDegrains.cpp:660-661): 1 the near
-// threshold (thsad / thsadc), 2 the far one (thsad2 / thsadc2) -- the entries in between lie between the two
-static int dn_thresholds(int64_t t1, int64_t t2, int radius, int64_t nSCD1, int64_t nSCD1_old, int64_t *table) {
-    dn_threshold_table(t1, t2, radius, nSCD1, nSCD1_old, table);
-    if (table[0] >= 2147483647LL) return 1;
-    for (int d = 1; d < radius; d++) if (table[d] >= 2147483647LL) return 2;
-    return 0;
-}
 
 static int dn_create(const mvx_degrain_n_args *a, const mvx_analysis_data *ad, const mvx_super *sup, const ptrdiff_t src_pitch[3], const ptrdiff_t super_pitch[3],
                      const ptrdiff_t dst_pitch[3], bool out16, mvx_degrain_n **out, char *err) {
@@ -308,53 +249,16 @@ static int dn_create(const mvx_degrain_n_args *a, const mvx_analysis_data *ad, c
     const int radius = a->radius;
     const char *name = "DegrainN";
     if (radius < 1 || radius > MVX_DEGRAIN_N_MAX_RADIUS) MVX_FAIL("%s: radius must be between 1 and %d.", name, MVX_DEGRAIN_N_MAX_RADIUS);
-    const int64_t t1 = a->thsad == MVX_UNSET ? 400 : a->thsad, t1c = a->thsadc == MVX_UNSET ? t1 : a->thsadc;
-    const int64_t t2 = a->thsad2 == MVX_UNSET ? t1 : a->thsad2, t2c = a->thsadc2 == MVX_UNSET ? t1c : a->thsadc2;
-    const int plane = a->plane == MVX_UNSET ? 4 : a->plane;
-    if (plane < 0 || plane > 4) MVX_FAIL("%s: plane must be between 0 and 4 (inclusive).", name);
-    static const int planes[5] = { 1, 2, 4, 6, 7 };
-    const int YUVplanes = planes[plane];
-    int64_t nSCD1, nSCD1_old; int32_t nSCD2;
-    if (int rc = mvx_resolve_thscd(name, a->thscd1, a->thscd2, ad, &nSCD1, &nSCD2, err, &nSCD1_old)) return rc;
-    mvx_degrain_n_info info;
-    memset(&info, 0, sizeof(info));
-    info.radius = radius; info.nrefs = 2 * radius;
-    const int overY = dn_thresholds(t1, t2, radius, nSCD1, nSCD1_old, info.thsad_d), overC = dn_thresholds(t1c, t2c, radius, nSCD1, nSCD1_old, info.thsadc_d);
-    if (overY || overC) { // MVDegrains.cpp:660-666: thsad, thsadc, then the far thresholds
-        const char *which = overY == 1 ? "" : overC == 1 ? "c" : overY ? "2" : "c2";
-        MVX_FAIL("%s: with this block size and video format, thsad%s must not exceed %lld or some calculations would overflow.", name, which,
-                 (long long)(2147483647LL * nSCD1_old / nSCD1));
-    }
-    if (!mvx_super_fits(ad, si, true)) MVX_FAIL("%s: wrong source or super clip frame size.", name);
-    if (out16 && si.bits != 8) MVX_FAIL("%s: out16 needs an 8 bit clip.", name);
-    const int pixelMax = out16 ? 65535 : (1 << si.bits) - 1; // the limits are in units of the output
-    const int limit = a->limit == MVX_UNSET ? pixelMax : a->limit;
-    const int limitc = a->limitc == MVX_UNSET ? limit : a->limitc;
-    if (limit < 0 || limit > pixelMax) MVX_FAIL("%s: limit must be between 0 and %d (inclusive).", name, pixelMax);
-    if (limitc < 0 || limitc > pixelMax) MVX_FAIL("%s: limitc must be between 0 and %d (inclusive).", name, pixelMax);
-    const bool overlap = ad->nOverlapX > 0 || ad->nOverlapY > 0;
-    if (overlap && (ad->nBlkX < 3 || ad->nBlkY < 3)) MVX_FAIL("overlap needs at least 3x3 blocks (window selection divides by nBlk-2).");
-    if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) MVX_FAIL("U and V super planes must share one pitch.");
-
-    mvx_degrain_n *h = new mvx_degrain_n();
-    h->info = info;
+    DgResolved r;
+    if (int rc = dg_resolve(name, a, out16, ad, si, &r, err)) return rc;
+    mvx_degrain_n *h;
+    if (int rc = blk_new(&h, ad, si, src_pitch, super_pitch, dst_pitch, err)) return rc;
+    h->info = r.info;
     h->out16 = out16;
     DNParams &P = h->P;
-    memset(&P, 0, sizeof(P));
     P.nRefs = 2 * radius; P.recBytes = dn_rec_bytes(P.nRefs);
-    P.nBlkX = ad->nBlkX; P.nBlkY = ad->nBlkY; P.nBlk = ad->nBlkX * ad->nBlkY;
-    P.pel = ad->nPel; P.logPel = ad->nPel == 4 ? 2 : ad->nPel == 2 ? 1 : 0;
-    P.bits = si.bits; P.bps = (si.bits + 7) / 8; P.nplanes = si.num_planes;
-    P.overlap = overlap;
-    P.nLvCount = ad->nLvCount;
-    fps_fill_planes(P.pl, ad, si, src_pitch, super_pitch, dst_pitch);
-    h->nWinClasses = si.num_planes > 1 ? 2 : 1;
-    for (int d = 0; d < radius; d++) { P.thSAD[0][d] = info.thsad_d[d]; P.thSAD[1][d] = info.thsadc_d[d]; }
-    P.thscd1 = nSCD1; P.thscd2 = nSCD2;
-    P.pl[0].process = !!(YUVplanes & 1);
-    P.pl[1].process = !!(YUVplanes & 2 & si.modeYUV);
-    P.pl[2].process = !!(YUVplanes & 4 & si.modeYUV);
-    P.pl[0].limit = limit; P.pl[1].limit = P.pl[2].limit = limitc;
+    for (int d = 0; d < radius; d++) { P.thSAD[0][d] = r.info.thsad_d[d]; P.thSAD[1][d] = r.info.thsadc_d[d]; }
+    dg_apply(P, r, si);
     *out = h;
     return MVX_OK;
 }
@@ -372,30 +276,6 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_out_bits(con
 extern "C" __attribute__((visibility("default"))) void mvx_degrain_n_get_info(const mvx_degrain_n *d, mvx_degrain_n_info *info) { *info = d->info; }
 extern "C" __attribute__((visibility("default"))) void mvx_degrain_n_destroy(mvx_degrain_n *d) { delete d; }
 
-// device state is created on first use so that argument validation works without a GPU
-static int dn_finish(mvx_degrain_n *h) {
-    if (h->dP.p) return MVX_OK;
-    DNParams &P = h->P;
-    if (P.overlap) {
-        for (int c = 0; c < h->nWinClasses; c++) {
-            const PlaneG &g = P.pl[c];
-            std::vector<int16_t> w(9 * g.blkW * g.blkH);
-            mvx_over_windows(w.data(), g.blkW, g.blkH, g.ovX, g.ovY);
-            HIP_CHECK(h->dWin[c].reserve(w.size()));
-            HIP_CHECK(hipMemcpy(h->dWin[c].p, w.data(), w.size() * 2, hipMemcpyHostToDevice));
-        }
-        P.win[0] = h->dWin[0].p; P.win[1] = P.win[2] = h->dWin[1].p;
-    }
-    return fps_upload_params(h->dP, P);
-}
-
-// samples per cell of plane p: the largest power of two up to 8 that divides the block width and the block step
-static int dn_cell_width(const PlaneG &g) {
-    int w = 8;
-    while (w > 1 && (g.blkW % w || g.stepX % w)) w >>= 1;
-    return w;
-}
-
 template <typename T, typename TO> static void dn_launch_cells(int W, dim3 grid, hipStream_t st, const DNParams *dP, const DNJob *dJ, const unsigned char *const *dRefs, const unsigned char *plan, int p0, int npl) {
 #define DNC(N) hipLaunchKernelGGL((dn_cell_kernel<T, TO, N>), grid, dim3(256), 0, st, dP, dJ, dRefs, plan, p0, npl)
     switch (W) { case 1: DNC(1); break; case 2: DNC(2); break; case 4: DNC(4); break; default: DNC(8); break; }
@@ -406,7 +286,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_frames(mvx_d
     if (nframes <= 0) return MVX_OK;
     hipStream_t st = (hipStream_t)stream;
     CallGuard::Scope scope(d->guard, st);
-    int rc = dn_finish(d);
+    int rc = blk_upload(d->dP, d->P, d->win);
     if (rc) return rc;
     const DNParams &P = d->P;
     const size_t n = (size_t)nframes, nr = (size_t)P.nRefs;
@@ -429,10 +309,10 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_frames(mvx_d
     HIP_CHECK(hipMemcpyAsync(d->dTables.p, host.data(), total, hipMemcpyHostToDevice, st));
     const DNJob *dJ = (const DNJob *)d->dTables.p;
     const unsigned char *const *dRefs = (const unsigned char *const *)(d->dTables.p + offRefs), *const *dBlobs = (const unsigned char *const *)(d->dTables.p + offBlobs);
-    hipLaunchKernelGGL(dn_usable_kernel, dim3(P.nRefs, nframes), dim3(256), 0, st, d->dP.p, dRefs, dBlobs, d->dLv0.p);
+    hipLaunchKernelGGL(blk_usable_kernel<DNParams>, dim3(P.nRefs, nframes), dim3(256), 0, st, d->dP.p, P.nRefs, BlkTables{dRefs, dBlobs}, d->dLv0.p);
     hipLaunchKernelGGL(dn_plan_kernel, dim3((P.nBlk + 255) / 256, nframes), dim3(256), 0, st, d->dP.p, dBlobs, d->dLv0.p, d->dPlan.p);
     for (int cls = 0; cls < (P.nplanes > 1 ? 2 : 1); cls++) { // one launch for the luma planes of all jobs, one for both chroma planes
-        const int p0 = cls, npl = cls ? 2 : 1, W = dn_cell_width(P.pl[p0]);
+        const int p0 = cls, npl = cls ? 2 : 1, W = blk_cell_width(P.pl[p0], 8);
         const dim3 grid(((P.pl[p0].W + W - 1) / W + 31) / 32, (P.pl[p0].H + 7) / 8, nframes * npl);
         if (d->out16) dn_launch_cells<uint8_t, uint16_t>(W, grid, st, d->dP.p, dJ, dRefs, d->dPlan.p, p0, npl);
         else if (P.bps == 1) dn_launch_cells<uint8_t, uint8_t>(W, grid, st, d->dP.p, dJ, dRefs, d->dPlan.p, p0, npl);

@@ -1,5 +1,6 @@
 // mvx_degrain_n_weights.h -- the arithmetic of mv.DegrainN that decides a block's weights, in one place for the device code
-// (mvx_degrain_n.hip) and for the stand-alone host program of the tests (tests/degrain_n_host_main.cpp).  It is the reference's
+// (mvx_degrain_n.hip; mvx_degrain.hip takes dn_weight and, at creation, the threshold table from here too: mvx_block_shared.h) and for the
+// stand-alone host program of the tests (tests/degrain_n_host_main.cpp).  It is the reference's
 // template read at any radius: DegrainWeight (MVDegrains.h:184-189), normaliseWeights<radius> (MVDegrains.h:208-223), and the table of
 // thresholds per temporal distance with its block-size normalisation (MVDegrains.cpp:658-661).  fp64 throughout; build with
 // -ffp-contract=off.  Internal; not part of the ABI.

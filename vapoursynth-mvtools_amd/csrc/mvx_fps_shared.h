@@ -1,7 +1,8 @@
 // mvx_fps_shared.h -- what the filters that consume vectors share (mvx_degrain.hip, mvx_flow.hip, mvx_mask.hip).  Device side: the level-0
 // vector reader, fgopIsUsable, the super-plane addressing, the wide sample loads / stores, the reference's bilinear upsizer and the occlusion
 // mask of MaskFun.cpp.  Host side: the scene-change thresholds, the checks on a pair of vector clips, the frame-rate conversion, the padded
-// small-field grid with its upsizer tables, the plane geometry and the launch dispatch by sample type and width.  Internal; not part of the ABI.
+// small-field grid with its upsizer tables, the plane geometry and the launch dispatch by sample type and width.  What only the block filters
+// share is in mvx_block_shared.h, on top of this.  Internal; not part of the ABI.
 #pragma once
 #include <algorithm>
 #include <type_traits>
@@ -48,21 +49,30 @@ typedef unsigned dg_uv2 __attribute__((ext_vector_type(2), aligned(1)));
 typedef unsigned dg_uv1 __attribute__((aligned(1)));
 typedef unsigned short dg_uh1 __attribute__((aligned(1)));
 
-// W samples of type T from an arbitrarily aligned address, widened to int
-template <typename T, int W> __device__ __forceinline__ void dg_load(DG_GL const unsigned char *p, int *o) {
+// ---- W samples of type T (1, 2, 4, 8, 16 or 32 bytes) at an arbitrarily aligned address: the one family of wide sample loads and stores.
+// The bytes as dwords first and the samples out of them later, so that several loads can be in flight before the first one is unpacked
+template <typename T, int W> struct DgRaw { unsigned d[(W * (int)sizeof(T) + 3) / 4]; };
+template <typename T, int W> __device__ __forceinline__ DgRaw<T, W> dg_load_raw(DG_GL const unsigned char *p) {
     constexpr int BYTES = W * (int)sizeof(T);
-    unsigned d[(BYTES + 3) / 4];
-    if (BYTES >= 16) {
+    static_assert(BYTES == 1 || BYTES == 2 || BYTES == 4 || BYTES == 8 || BYTES == 16 || BYTES == 32, "1, 2, 4, 8, 16 or 32 bytes");
+    DgRaw<T, W> r;
+    if constexpr (BYTES >= 16) {
 #pragma unroll
-        for (int k = 0; k < BYTES / 16; k++) { dg_uv4 t = *(DG_GL const dg_uv4 *)(p + 16 * k); d[4 * k] = t[0]; d[4 * k + 1] = t[1]; d[4 * k + 2] = t[2]; d[4 * k + 3] = t[3]; }
-    } else if (BYTES == 8) { dg_uv2 t = *(DG_GL const dg_uv2 *)p; d[0] = t[0]; d[1] = t[1]; }
-    else if (BYTES == 4) d[0] = *(DG_GL const dg_uv1 *)p;
-    else d[0] = *(DG_GL const dg_uh1 *)p;
+        for (int k = 0; k < BYTES / 16; k++) { dg_uv4 t = *(DG_GL const dg_uv4 *)(p + 16 * k); r.d[4 * k] = t[0]; r.d[4 * k + 1] = t[1]; r.d[4 * k + 2] = t[2]; r.d[4 * k + 3] = t[3]; }
+    } else if constexpr (BYTES == 8) { dg_uv2 t = *(DG_GL const dg_uv2 *)p; r.d[0] = t[0]; r.d[1] = t[1]; }
+    else if constexpr (BYTES == 4) r.d[0] = *(DG_GL const dg_uv1 *)p;
+    else if constexpr (BYTES == 2) r.d[0] = *(DG_GL const dg_uh1 *)p;
+    else r.d[0] = *p;
+    return r;
+}
+template <typename T, int W> __device__ __forceinline__ int dg_sample(const DgRaw<T, W> &r, int i) {
+    return sizeof(T) == 2 ? (int)((r.d[i >> 1] >> (16 * (i & 1))) & 0xffffu) : (int)((r.d[i >> 2] >> (8 * (i & 3))) & 0xffu);
+}
+// both steps at once: the samples widened to int
+template <typename T, int W> __device__ __forceinline__ void dg_load(DG_GL const unsigned char *p, int *o) {
+    const DgRaw<T, W> r = dg_load_raw<T, W>(p);
 #pragma unroll
-    for (int i = 0; i < W; i++) {
-        if (sizeof(T) == 2) o[i] = (int)((d[i >> 1] >> (16 * (i & 1))) & 0xffffu);
-        else o[i] = (int)((d[i >> 2] >> (8 * (i & 3))) & 0xffu);
-    }
+    for (int i = 0; i < W; i++) o[i] = dg_sample(r, i);
 }
 // N consecutive ints (dword-aligned address)
 typedef int dg_iv4 __attribute__((ext_vector_type(4), aligned(4)));
@@ -74,22 +84,24 @@ template <int N> __device__ __forceinline__ void dg_load_ints(DG_GL const unsign
     } else if (N == 2) { const dg_iv2 t = *(DG_GL const dg_iv2 *)p; o[0] = t[0]; o[1] = t[1]; }
     else o[0] = *(DG_GL const int *)p;
 }
+// W ints packed to samples of type T and stored
 template <typename T, int W> __device__ __forceinline__ void dg_store(DG_GL unsigned char *p, const int *v) {
     constexpr int BYTES = W * (int)sizeof(T);
-    unsigned d[(BYTES + 3) / 4];
+    DgRaw<T, W> r;
 #pragma unroll
-    for (int k = 0; k < (BYTES + 3) / 4; k++) d[k] = 0;
+    for (int k = 0; k < (BYTES + 3) / 4; k++) r.d[k] = 0;
 #pragma unroll
     for (int i = 0; i < W; i++) {
-        if (sizeof(T) == 2) d[i >> 1] |= (unsigned)v[i] << (16 * (i & 1));
-        else d[i >> 2] |= (unsigned)v[i] << (8 * (i & 3));
+        if (sizeof(T) == 2) r.d[i >> 1] |= (unsigned)v[i] << (16 * (i & 1));
+        else r.d[i >> 2] |= (unsigned)v[i] << (8 * (i & 3));
     }
-    if (BYTES >= 16) {
+    if constexpr (BYTES >= 16) {
 #pragma unroll
-        for (int k = 0; k < BYTES / 16; k++) { dg_uv4 t = { d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3] }; *(DG_GL dg_uv4 *)(p + 16 * k) = t; }
-    } else if (BYTES == 8) { dg_uv2 t = { d[0], d[1] }; *(DG_GL dg_uv2 *)p = t; }
-    else if (BYTES == 4) *(DG_GL dg_uv1 *)p = d[0];
-    else *(DG_GL dg_uh1 *)p = (unsigned short)d[0];
+        for (int k = 0; k < BYTES / 16; k++) { dg_uv4 t = { r.d[4 * k], r.d[4 * k + 1], r.d[4 * k + 2], r.d[4 * k + 3] }; *(DG_GL dg_uv4 *)(p + 16 * k) = t; }
+    } else if constexpr (BYTES == 8) { dg_uv2 t = { r.d[0], r.d[1] }; *(DG_GL dg_uv2 *)p = t; }
+    else if constexpr (BYTES == 4) *(DG_GL dg_uv1 *)p = r.d[0];
+    else if constexpr (BYTES == 2) *(DG_GL dg_uh1 *)p = (unsigned short)r.d[0];
+    else *p = (unsigned char)r.d[0];
 }
 
 // SimpleResize.cpp:62-121, uint8_t form, at one output sample whose table values are at hand: rows r0 / r1 (byte offsets), column o,

@@ -484,6 +484,29 @@ def _pitches(planes):
     return a
 
 
+def _pad3(l):
+    return (C.c_ssize_t * 3)(*(list(l) + [0] * (3 - len(l))))
+
+
+def _frame_pitch(sup):
+    """the default row pitch of frames of the clip's size (not the super clip's): rows rounded up to 256 bytes"""
+    i = sup.info
+    w = [i.width] + [i.width // i.xRatioUV] * 2
+    return [((w[p] * sup.bps + 255) // 256) * 256 for p in range(sup.nplanes)]
+
+
+class _Handle:
+    """A library object behind self.h, destroyed with the Python object (if its creation got as far as a handle)."""
+    _destroy = None  # the name of the library's destroy function
+
+    def __del__(self):
+        try:
+            if self.h:
+                getattr(lib(), self._destroy)(self.h)
+        except Exception:
+            pass
+
+
 # ---------------------------------------------------------------------------------------------- frame helpers
 
 def plane_to_device(arr, pitch_align=256, device="cuda"):
@@ -508,8 +531,9 @@ def plane_to_numpy(t, width, dtype):
     return a.view(dtype).reshape(t.shape[0], width)
 
 
-class Super:
+class Super(_Handle):
     """mv.Super -- MVSuper.c:140-275."""
+    _destroy = "mvx_super_destroy"
 
     def __init__(self, width, height, bits=8, subsampling=(1, 1), gray=False, hpad=None, vpad=None, pel=None, levels=None,
                  chroma=None, sharp=None, rfilter=None, shadow=None):
@@ -547,13 +571,6 @@ class Super:
             lib().mvx_super_shadow_bytes(self.h, (C.c_ssize_t * 3)(*(self.pitch + [0] * (3 - len(self.pitch)))), extra)
         self.shadow = any(extra)
         self.slots = [1 + (extra[p] + self.shadow_stride[p] - 1) // self.shadow_stride[p] for p in range(self.nplanes)]  # areas per plane: the plane + its shadow data
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().mvx_super_destroy(self.h)
-        except Exception:
-            pass
 
     def alloc(self, n=1, device="cuda"):
         """n zero-filled super frames (the library only ever writes the defined rectangles)."""
@@ -607,8 +624,7 @@ class Super:
         for f in range(n):
             for p in range(self.nplanes):
                 pl[f * 3 + p] = out[f][p].data_ptr()
-        pad = lambda l: (C.c_ssize_t * 3)(*(list(l) + [0] * (3 - len(l))))
-        _check(lib().mvx_super_shadow_frames(self.h, n, pl, pad(self.pitch), pad(self.shadow_stride), _stream()))
+        _check(lib().mvx_super_shadow_frames(self.h, n, pl, _pad3(self.pitch), _pad3(self.shadow_stride), _stream()))
 
     def finest(self, super_frames, out=None):
         """mv.Finest(super) -- MVFinest.c: interleaved sub-pel planes of level 0, one output frame per super frame."""
@@ -627,8 +643,7 @@ class Super:
             for p in range(self.nplanes):
                 src[f * 3 + p] = super_frames[f][p].data_ptr()
                 dst[f * 3 + p] = out[f][p].data_ptr()
-        pad = lambda l: (C.c_ssize_t * 3)(*(list(l) + [0] * (3 - len(l))))
-        _check(lib().mvx_finest_frames(self.h, n, src, pad(self.pitch), dst, pad(pitch), _stream()))
+        _check(lib().mvx_finest_frames(self.h, n, src, _pad3(self.pitch), dst, _pad3(pitch), _stream()))
         return out
 
     def pelclip_mode(self, pel_width, pel_height):
@@ -668,15 +683,15 @@ class Super:
                 assert frames[f][p].stride(0) == frames[0][p].stride(0) and out[f][p].stride(0) == out[0][p].stride(0)
         if self.shadow:  # one call: the level-0 kernels write the shadow data of level 0 themselves
             self.check_room(out, "output super frame")
-            pad = lambda l: (C.c_ssize_t * 3)(*(list(l) + [0] * (3 - len(l))))
-            _check(lib().mvx_super_frames_shadow(self.h, n, src, _pitches(frames[0]), dst, _pitches(out[0]), pad(self.shadow_stride), _stream()))
+            _check(lib().mvx_super_frames_shadow(self.h, n, src, _pitches(frames[0]), dst, _pitches(out[0]), _pad3(self.shadow_stride), _stream()))
         else:
             _check(lib().mvx_super_frames(self.h, n, src, _pitches(frames[0]), dst, _pitches(out[0]), _stream()))
         return out
 
 
-class Analyse:
+class Analyse(_Handle):
     """mv.Analyse -- MVAnalyse.c:267-635; keyword names are the reference's argument names."""
+    _destroy = "mvx_analyse_destroy"
 
     def __init__(self, sup, num_frames=1 << 30, **kw):
         self.sup = sup
@@ -696,13 +711,6 @@ class Analyse:
         self.blob_size = lib().mvx_analyse_blob_size(self.h)
         if sup.shadow:  # super frames from sup.alloc / sup.build carry their shifted copies
             _check(lib().mvx_analyse_set_ref_shadow(self.h, (C.c_ssize_t * 3)(*(sup.shadow_stride + [0] * (3 - len(sup.shadow_stride))))))
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().mvx_analyse_destroy(self.h)
-        except Exception:
-            pass
 
     def alloc_blobs(self, n, device="cuda"):
         torch = _torch()
@@ -762,10 +770,11 @@ def _ref_table(jobs_refs, nr, nplanes, what):
     return table
 
 
-class AnalyseN:
+class AnalyseN(_Handle):
     """One source frame against a temporal radius (include/mvtools_amd.h, "the multi blob"): field r of a multi blob is the MVTools_vectors of
     Analyse(isb = r % 2 == 0, delta = r // 2 + 1), byte for byte, at byte r * field_stride.  Keyword names are Analyse's; isb and delta are
     set by the radius."""
+    _destroy = "mvx_analyse_n_destroy"
 
     def __init__(self, sup, radius, num_frames=1 << 30, **kw):
         self.sup = sup
@@ -786,13 +795,6 @@ class AnalyseN:
         self.blob_size = lib().mvx_analyse_n_blob_size(self.h)
         if sup.shadow:  # super frames from sup.alloc / sup.build carry their shifted copies
             _check(lib().mvx_analyse_n_set_ref_shadow(self.h, (C.c_ssize_t * 3)(*(sup.shadow_stride + [0] * (3 - len(sup.shadow_stride))))))
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().mvx_analyse_n_destroy(self.h)
-        except Exception:
-            pass
 
     def ad(self, r):
         """the MVTools_MVAnalysisData of field r"""
@@ -836,8 +838,9 @@ class AnalyseN:
         return blobs
 
 
-class Degrain:
+class Degrain(_Handle):
     """mv.Degrain1..6 -- MVDegrains.cpp:511-809.  analysis_data = the vector clips' MVTools_MVAnalysisData."""
+    _destroy = "mvx_degrain_destroy"
 
     def __init__(self, radius, sup, analysis_data, src_pitch, dst_pitch=None, thsad=None, thsadc=None, plane=None, limit=None,
                  limitc=None, thscd1=None, thscd2=None):
@@ -846,21 +849,13 @@ class Degrain:
         a = DegrainArgs(radius, _u(thsad), _u(thsadc), _u(plane), _u(limit), _u(limitc), _u(thscd1), _u(thscd2))
         ad = AnalysisData.from_buffer_copy(bytes(analysis_data))
         dst_pitch = dst_pitch or src_pitch
-        pad = lambda l: (C.c_ssize_t * 3)(*(list(l) + [0] * (3 - len(l))))
         self.h = C.c_void_p()
         err = C.create_string_buffer(ERRLEN)
-        _check(lib().mvx_degrain_create(C.byref(a), C.byref(ad), sup.h, pad(src_pitch), pad(sup.pitch), pad(dst_pitch), C.byref(self.h), err), err)
+        _check(lib().mvx_degrain_create(C.byref(a), C.byref(ad), sup.h, _pad3(src_pitch), _pad3(sup.pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
         self.src_pitch, self.dst_pitch = list(src_pitch), list(dst_pitch)
         self.ref_shadow = bool(sup.shadow and sup.slots[0] > 1)
         if self.ref_shadow:  # super frames from sup.alloc / sup.build carry the shifted copy of their luma plane (clips of more than 8 bits)
             _check(lib().mvx_degrain_set_ref_shadow(self.h, (C.c_ssize_t * 3)(*(sup.shadow_stride + [0] * (3 - len(sup.shadow_stride))))))
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().mvx_degrain_destroy(self.h)
-        except Exception:
-            pass
 
     def run(self, jobs, out=None):
         """jobs: list of (src_frame, [ref_super or None]*2r, [blob]*2r) ordered mvbw, mvfw, mvbw2, mvfw2, ..."""
@@ -885,12 +880,13 @@ class Degrain:
         return out
 
 
-class DegrainN:
+class DegrainN(_Handle):
     """Degrain at a temporal radius of 1..24 (include/mvtools_amd.h, mv.DegrainN): the reference's templates over the radius (MVDegrains.h:30-53,184-223)
     read at any radius, each reference weighed against the threshold of its temporal distance -- thsad at distance 1 falling to thsad2 at distance
     `radius` (thsad2 / thsadc2 None: no fall-off).  analysis_data = the vector clips' MVTools_MVAnalysisData.
     out16: an 8-bit clip (8-bit super clip and vectors, thresholds in 8-bit units) written as 16-bit planes -- a block's weighted sum before its
     >> 8, see mvx_degrain_n_create_out16; limit / limitc are then 0..65535, and dst_pitch defaults to rows of 16-bit samples rounded up to 256 bytes."""
+    _destroy = "mvx_degrain_n_destroy"
 
     def __init__(self, radius, sup, analysis_data, src_pitch, dst_pitch=None, thsad=None, thsadc=None, thsad2=None, thsadc2=None, plane=None, limit=None,
                  limitc=None, thscd1=None, thscd2=None, out16=False):
@@ -902,19 +898,11 @@ class DegrainN:
         if self.out16:
             dst_pitch = dst_pitch or [(sup.info.plane_width[p] * 2 + 255) // 256 * 256 for p in range(len(src_pitch))]
         dst_pitch = dst_pitch or src_pitch
-        pad = lambda l: (C.c_ssize_t * 3)(*(list(l) + [0] * (3 - len(l))))
         self.h = C.c_void_p()
         err = C.create_string_buffer(ERRLEN)
         create = lib().mvx_degrain_n_create_out16 if self.out16 else lib().mvx_degrain_n_create
-        _check(create(C.byref(a), C.byref(ad), sup.h, pad(src_pitch), pad(sup.pitch), pad(dst_pitch), C.byref(self.h), err), err)
+        _check(create(C.byref(a), C.byref(ad), sup.h, _pad3(src_pitch), _pad3(sup.pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
         self.src_pitch, self.dst_pitch = list(src_pitch), list(dst_pitch)
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().mvx_degrain_n_destroy(self.h)
-        except Exception:
-            pass
 
     @property
     def out_bits(self):
@@ -961,29 +949,20 @@ class DegrainN:
         return out
 
 
-class Compensate:
+class Compensate(_Handle):
     """mv.Compensate -- MVCompensate.c:419-575."""
+    _destroy = "mvx_compensate_destroy"
 
     def __init__(self, sup, analysis_data, dst_pitch=None, scbehavior=None, thsad=None, time=100.0, thscd1=None, thscd2=None, fields=None):
         self.sup = sup
         a = CompensateArgs(_u(scbehavior), _u(thsad), float(time), _u(thscd1), _u(thscd2), _u(fields))
         ad = AnalysisData.from_buffer_copy(bytes(analysis_data))
-        i = sup.info
         if dst_pitch is None:
-            w = [i.width] + [i.width // i.xRatioUV] * 2
-            dst_pitch = [((w[p] * sup.bps + 255) // 256) * 256 for p in range(sup.nplanes)]
-        pad = lambda l: (C.c_ssize_t * 3)(*(list(l) + [0] * (3 - len(l))))
+            dst_pitch = _frame_pitch(sup)
         self.h = C.c_void_p()
         err = C.create_string_buffer(ERRLEN)
-        _check(lib().mvx_compensate_create(C.byref(a), C.byref(ad), sup.h, pad(sup.pitch), pad(dst_pitch), C.byref(self.h), err), err)
+        _check(lib().mvx_compensate_create(C.byref(a), C.byref(ad), sup.h, _pad3(sup.pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
         self.dst_pitch = list(dst_pitch)
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().mvx_compensate_destroy(self.h)
-        except Exception:
-            pass
 
     def run(self, jobs, out=None):
         """jobs: list of (src_super, ref_super_or_None, blob[, field_shift])."""
@@ -1007,32 +986,23 @@ class Compensate:
         return out
 
 
-class CompensateN:
+class CompensateN(_Handle):
     """The frames n - tr .. n + tr compensated onto frame n from frame n's multi blob (include/mvtools_amd.h, mv.CompensateN): 2 * tr + 1 frames
     per job in temporal order, each compensated one byte for byte what Compensate writes for that pair, the source in the middle.
     analysis_data: of field 0 (AnalyseN.ad(0))."""
+    _destroy = "mvx_compensate_n_destroy"
 
     def __init__(self, tr, sup, analysis_data, dst_pitch=None, scbehavior=None, thsad=None, time=100.0, thscd1=None, thscd2=None, fields=None):
         self.sup = sup
         a = CompensateArgs(_u(scbehavior), _u(thsad), float(time), _u(thscd1), _u(thscd2), _u(fields))
         ad = AnalysisData.from_buffer_copy(bytes(analysis_data))
-        i = sup.info
         if dst_pitch is None:
-            w = [i.width] + [i.width // i.xRatioUV] * 2
-            dst_pitch = [((w[p] * sup.bps + 255) // 256) * 256 for p in range(sup.nplanes)]
-        pad = lambda l: (C.c_ssize_t * 3)(*(list(l) + [0] * (3 - len(l))))
+            dst_pitch = _frame_pitch(sup)
         self.h = C.c_void_p()
         err = C.create_string_buffer(ERRLEN)
-        _check(lib().mvx_compensate_n_create(C.byref(a), int(tr), C.byref(ad), sup.h, pad(sup.pitch), pad(dst_pitch), C.byref(self.h), err), err)
+        _check(lib().mvx_compensate_n_create(C.byref(a), int(tr), C.byref(ad), sup.h, _pad3(sup.pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
         self.tr = int(tr)
         self.dst_pitch = list(dst_pitch)
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().mvx_compensate_n_destroy(self.h)
-        except Exception:
-            pass
 
     def map(self, k):
         """output k of a job -> (offset of its frame from n, field of the multi blob that compensates it or -1 for the centre)"""
@@ -1070,9 +1040,10 @@ class CompensateN:
         return out
 
 
-class BlockFPS:
+class BlockFPS(_Handle):
     """mv.BlockFPS(clip, super, mvbw, mvfw, num, den, mode, ml, blend, thscd1, thscd2) -- MVBlockFPS.c:741-1014.
     `fps_num / fps_den` is the input clip's frame rate; `clip_pitch` the row pitch of its device planes."""
+    _destroy = "mvx_blockfps_destroy"
 
     def __init__(self, sup, ad_bw, ad_fw, num_frames, clip_pitch, fps_num=24, fps_den=1, num=None, den=None, mode=None, ml=100.0, blend=None, thscd1=None,
                  thscd2=None):
@@ -1080,23 +1051,15 @@ class BlockFPS:
         a = BlockFPSArgs(_u(num), _u(den), _u(mode), float(ml), _u(blend), _u(thscd1), _u(thscd2))
         bw = AnalysisData.from_buffer_copy(bytes(ad_bw))
         fw = AnalysisData.from_buffer_copy(bytes(ad_fw))
-        pad = lambda l: (C.c_ssize_t * 3)(*(list(l) + [0] * (3 - len(l))))
         self.h = C.c_void_p()
         self.pitch = list(clip_pitch)
         err = C.create_string_buffer(ERRLEN)
-        _check(lib().mvx_blockfps_create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, int(num_frames), int(fps_num), int(fps_den), pad(sup.pitch), pad(clip_pitch),
-                                         pad(clip_pitch), C.byref(self.h), err), err)
+        _check(lib().mvx_blockfps_create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, int(num_frames), int(fps_num), int(fps_den), _pad3(sup.pitch), _pad3(clip_pitch),
+                                         _pad3(clip_pitch), C.byref(self.h), err), err)
         self.in_frames = int(num_frames)
         info = BlockFPSInfo()
         lib().mvx_blockfps_get_info(self.h, C.byref(info))
         self.num_frames, self.fps_num, self.fps_den = info.num_frames, info.fps_num, info.fps_den
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().mvx_blockfps_destroy(self.h)
-        except Exception:
-            pass
 
     def map(self, n):
         a, b, c = C.c_int(), C.c_int(), C.c_int()
@@ -1131,8 +1094,9 @@ class BlockFPS:
         return out
 
 
-class _Flow:
+class _Flow(_Handle):
     """the engine both flow filters share (mvx_flow_*); subclasses create the handle"""
+    _destroy = "mvx_flow_destroy"
 
     def __init__(self, sup, num_frames, create):
         self.sup = sup
@@ -1143,13 +1107,6 @@ class _Flow:
         info = BlockFPSInfo()
         lib().mvx_flow_get_info(self.h, C.byref(info))
         self.num_frames, self.fps_num, self.fps_den = info.num_frames, info.fps_num, info.fps_den
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().mvx_flow_destroy(self.h)
-        except Exception:
-            pass
 
     def map(self, n):
         a, b, c = C.c_int(), C.c_int(), C.c_int()
@@ -1195,10 +1152,6 @@ class _Flow:
         return arr, out
 
 
-def _pad3(l):
-    return (C.c_ssize_t * 3)(*(list(l) + [0] * (3 - len(l))))
-
-
 class FlowInter(_Flow):
     """mv.FlowInter(clip, super, mvbw, mvfw, time, ml, blend, thscd1, thscd2) -- MVFlowInter.c:473-678.  Output frame n lies `time` percent
     of the way from input frame n to n + delta; `clip_pitch` is the row pitch of the clip's device planes (and of the output)."""
@@ -1224,9 +1177,10 @@ class FlowFPS(_Flow):
                                                                                    int(fps_den), _pad3(sup.pitch), _pad3(clip_pitch), _pad3(clip_pitch), h, err))
 
 
-class Flow:
+class Flow(_Handle):
     """mv.Flow(clip, super, vectors, time, mode, fields, thscd1, thscd2, tff) -- MVFlow.cpp:391-593.  Output frame n is clip frame n compensated
     per sample from the Finest frame of ref(n); `clip_pitch` is the row pitch of the clip's device planes (and of the output)."""
+    _destroy = "mvx_flowcomp_destroy"
 
     def __init__(self, sup, ad, num_frames, clip_pitch, time=100.0, mode=None, fields=None, thscd1=None, thscd2=None):
         self.sup = sup
@@ -1238,13 +1192,6 @@ class Flow:
         err = C.create_string_buffer(ERRLEN)
         _check(lib().mvx_flowcomp_create(C.byref(a), C.byref(ad), sup.h, self.num_frames, _pad3(sup.pitch), _pad3(clip_pitch), _pad3(clip_pitch),
                                          C.byref(self.h), err), err)
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().mvx_flowcomp_destroy(self.h)
-        except Exception:
-            pass
 
     def ref(self, n):
         """the reference frame of output frame n (MVFlow.cpp:170-176); outside the clip the job passes no super frame"""
@@ -1274,9 +1221,10 @@ class Flow:
         _check(lib().mvx_flowcomp_frames(self.h, len(arr), arr, _stream()))
 
 
-class FlowBlur:
+class FlowBlur(_Handle):
     """mv.FlowBlur(clip, super, mvbw, mvfw, blur, prec, thscd1, thscd2) -- MVFlowBlur.c:346-552.  `clip_pitch` is the row pitch of the clip's
     device planes (and of the output)."""
+    _destroy = "mvx_flowblur_destroy"
 
     def __init__(self, sup, ad_bw, ad_fw, num_frames, clip_pitch, blur=50.0, prec=None, thscd1=None, thscd2=None):
         self.sup = sup
@@ -1290,13 +1238,6 @@ class FlowBlur:
         err = C.create_string_buffer(ERRLEN)
         _check(lib().mvx_flowblur_create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, self.num_frames, _pad3(sup.pitch), _pad3(clip_pitch),
                                          _pad3(clip_pitch), C.byref(self.h), err), err)
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().mvx_flowblur_destroy(self.h)
-        except Exception:
-            pass
 
     def run(self, ns, clip, supers, blobs_bw, blobs_fw, out=None):
         """ns: output frame numbers, one job each, all in one call; clip / supers: device frames of the input clip and its super clip;
@@ -1330,11 +1271,12 @@ class FlowBlur:
         return arr, out
 
 
-class Mask:
+class Mask(_Handle):
     """mv.Mask(clip, vectors, ml, gamma, kind, time, ysc, thscd1, thscd2) -- MVMask.c:227-346.  `width` / `height` / `subsampling` / `gray` /
     `bits` describe the clip argument (which must have the vector clip's geometry); the output is always three 8-bit planes, 4:4:4 for a
     Gray clip.  `clip_pitch` is the row pitch of the clip's device planes (only the luma plane is read, by kind 5); `dst_pitch` the row
     pitches of the output planes (multiples of 16 bytes; default: the plane widths rounded up to 256)."""
+    _destroy = "mvx_mask_destroy"
 
     def __init__(self, vectors_ad, width, height, subsampling=(1, 1), gray=False, clip_pitch=None, dst_pitch=None, bits=8, ml=100.0, gamma=1.0,
                  kind=None, time=100.0, ysc=None, thscd1=None, thscd2=None):
@@ -1353,13 +1295,6 @@ class Mask:
         _check(lib().mvx_mask_create(C.byref(a), C.byref(ad), C.byref(c), _pad3(clip_pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
         self.info = MaskInfo()
         lib().mvx_mask_get_info(self.h, C.byref(self.info))
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().mvx_mask_destroy(self.h)
-        except Exception:
-            pass
 
     def alloc(self, n, device="cuda"):
         """n output frames of three planes with this filter's pitches (contents undefined)"""
@@ -1392,11 +1327,12 @@ class Mask:
         return arr, out
 
 
-class DepanAnalyse:
+class DepanAnalyse(_Handle):
     """mv.DepanAnalyse(clip, vectors, mask, zoom, rot, pixaspect, error, info, wrong, zerow, thscd1, thscd2, fields, tff) -- MVDepan.cpp:473-615.
     `width` / `height` describe the clip; `mask` = (bits,) or (bits, width, height) of the optional mask clip.  The vectors come from a delta-1
     Analyse; for backward vectors the caller passes the blob of frame max(0, n - 1) for frame n (MVDepan.cpp:287).  The estimator runs on the
     host in block order; run() gathers what it reads with one kernel, run_host() takes numpy blobs and mask planes and touches no device."""
+    _destroy = "mvx_depan_analyse_destroy"
 
     def __init__(self, vectors_ad, width, height, bits=8, subsampling=(1, 1), gray=False, mask=None, zoom=None, rot=None, pixaspect=1.0, error=15.0,
                  wrong=10.0, zerow=0.05, thscd1=None, thscd2=None, fields=None, num_frames=1, vector_frames=None, mask_frames=None):
@@ -1414,13 +1350,6 @@ class DepanAnalyse:
         nf = int(num_frames)
         _check(lib().mvx_depan_analyse_create(C.byref(a), C.byref(ad), C.byref(c), m, nf, nf if vector_frames is None else int(vector_frames),
                                               nf if mask_frames is None else int(mask_frames), C.byref(self.h), err), err)
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().mvx_depan_analyse_destroy(self.h)
-        except Exception:
-            pass
 
     @staticmethod
     def _result(out):
@@ -1451,11 +1380,12 @@ class DepanAnalyse:
         return self._result(out)
 
 
-class DepanEstimate:
+class DepanEstimate(_Handle):
     """mv.DepanEstimate(clip, trust, winx, winy, wleft, wtop, dxmax, dymax, zoommax, stab, pixaspect, info, show, fields, tff) -- MVDepan.cpp:1271-1503,
     without the `info` overlay.  spectra() is the reference's stage 1 (one or two window spectra per frame), correlate() its stage 2
     (prev against cur: dx, dy, zoom, trust), finish() its stage 3 (host arithmetic); run() does all three for consecutive frames and returns
     what DepanCompensate.transform() takes.  The transforms are HIP kernels; there is no FFTW and no CPU path."""
+    _destroy = "mvx_depan_estimate_destroy"
 
     def __init__(self, width, height, bits=8, trust=4.0, winx=None, winy=None, wleft=None, wtop=None, dxmax=None, dymax=None, zoommax=1.0, stab=1.0,
                  pixaspect=1.0, fields=None, tff=None, num_frames=1 << 30, float_samples=False):
@@ -1469,13 +1399,6 @@ class DepanEstimate:
         self.info = DepanEstimateInfo()
         lib().mvx_depan_estimate_get_info(self.h, C.byref(self.info))
         self.windows = self.info.windows
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().mvx_depan_estimate_destroy(self.h)
-        except Exception:
-            pass
 
     def spectra(self, frames):
         """frames: device luma planes ([h, pitch] uint8 tensors of one pitch) -> one float32 tensor [windows, winy, winx / 2 + 1, 2] per frame"""
@@ -1562,10 +1485,11 @@ class DepanEstimate:
         return self.finish(res)
 
 
-class DepanCompensate:
+class DepanCompensate(_Handle):
     """mv.DepanCompensate(clip, data, offset, subpixel, pixaspect, matchfields, mirror, blur, info, fields, tff) -- MVDepan.cpp:2750-2881.
     map(n) says which clip frame to warp and which data frames' motions to sum, transform(motions, ...) sums them (host arithmetic), and a
     job is (src planes, summed transform).  `src_pitch` / `dst_pitch`: row pitches in bytes of the device planes."""
+    _destroy = "mvx_depan_compensate_destroy"
 
     def __init__(self, width, height, bits=8, subsampling=(1, 1), gray=False, src_pitch=None, dst_pitch=None, offset=0.0, subpixel=None, pixaspect=1.0,
                  matchfields=None, mirror=None, blur=None, fields=None, tff=None, num_frames=1 << 30, data_frames=None):
@@ -1586,13 +1510,6 @@ class DepanCompensate:
         self.info = DepanCompensateInfo()
         lib().mvx_depan_compensate_get_info(self.h, C.byref(self.info))
         self.nplanes = self.info.num_planes
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().mvx_depan_compensate_destroy(self.h)
-        except Exception:
-            pass
 
     def map(self, n):
         """(nsrc, start, end) of output frame n: warp clip frame nsrc by the motions of data frames start + 1 .. end; None: return clip frame n"""
@@ -1638,11 +1555,12 @@ class DepanCompensate:
         return arr, out
 
 
-class DepanStabilise:
+class DepanStabilise(_Handle):
     """mv.DepanStabilise(clip, data, cutoff, damping, initzoom, addzoom, prev, next, mirror, blur, dxmax, dymax, zoommax, rotmax, subpixel, pixaspect,
     fitlast, tzoom, info, method, fields) -- MVDepan.cpp:3909-4208.  window(n) names the data frames whose motion plan(n, motions) reads (host
     arithmetic) and the clip frames its sources lie among; a job is a plan with the planes of the current, prev and next source frames; all jobs
     of a call are one fused launch.  `src_pitch` / `dst_pitch`: row pitches in bytes of the device planes.  Float arguments: None -> the default."""
+    _destroy = "mvx_depan_stabilise_destroy"
 
     def __init__(self, width, height, bits=8, subsampling=(1, 1), gray=False, src_pitch=None, dst_pitch=None, fps=(25, 1), num_frames=1 << 30, cutoff=None,
                  damping=None, initzoom=None, addzoom=None, prev=None, next=None, mirror=None, blur=None, dxmax=None, dymax=None, zoommax=None, rotmax=None,
@@ -1667,13 +1585,6 @@ class DepanStabilise:
         self.info = DepanStabiliseInfo()
         lib().mvx_depan_stabilise_get_info(self.h, C.byref(self.info))
         self.nplanes = self.info.num_planes
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().mvx_depan_stabilise_destroy(self.h)
-        except Exception:
-            pass
 
     def windows(self):
         """the cosine windows wint, winrz, winfz: radius + 1 float32 each"""
@@ -1742,8 +1653,9 @@ class DepanStabilise:
         return out
 
 
-class Recalculate:
+class Recalculate(_Handle):
     """mv.Recalculate(super, vectors, thsad, smooth, blksize, ...) -- MVRecalculate.c:263-545."""
+    _destroy = "mvx_recalculate_destroy"
 
     def __init__(self, sup, vectors_ad, **kw):
         self.sup = sup
@@ -1755,20 +1667,12 @@ class Recalculate:
             if v is not None:
                 setattr(a, k2, int(v))
         old = AnalysisData.from_buffer_copy(bytes(vectors_ad))
-        pad = lambda l: (C.c_ssize_t * 3)(*(list(l) + [0] * (3 - len(l))))
         self.h = C.c_void_p()
         err = C.create_string_buffer(ERRLEN)
-        _check(lib().mvx_recalculate_create(C.byref(a), sup.h, C.byref(old), pad(sup.pitch), C.byref(self.h), err), err)
+        _check(lib().mvx_recalculate_create(C.byref(a), sup.h, C.byref(old), _pad3(sup.pitch), C.byref(self.h), err), err)
         self.ad = AnalysisData()
         lib().mvx_recalculate_get_data(self.h, C.byref(self.ad))
         self.blob_size = lib().mvx_recalculate_blob_size(self.h)
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().mvx_recalculate_destroy(self.h)
-        except Exception:
-            pass
 
     def run(self, jobs, blobs=None):
         """jobs: list of (src_super, ref_super_or_None, old_blob) -> list of device blobs."""
