@@ -804,7 +804,7 @@ int mvx_depan_estimate_finish(const mvx_depan_estimate *h, int n, const mvx_depa
  * depanStabiliseGetFrame0 / 1, :3567-3666 / :3717-3841 (Inertial :2945-3115, Average :3118-3246, InertialLimit :3249-3329) and the
  * source selection of fillBorderPrev :3398-3419 and fillBorderNext :3461-3502 (csrc/mvx_depan_stab_host.h: float arithmetic in the
  * reference's order); mvx_depan_stabilise_frames replaces the up to three painting passes of :3679-3693 (fillBorderPrev, fillBorderNext,
- * compensateFrame, :3356-3546) with one kernel that selects per sample and stores once (csrc/mvx_depan_stab_sample.h on top of
+ * compensateFrame, :3356-3546) with one kernel that selects per sample and stores once (csrc/mvx_depan_sample.h: ds_sample on top of
  * DepanCompensate's interpolators).  Only the samples of each plane are written.
  * Per sample the result is: the current frame where its position is inside it; else the next source where that is inside; else what the
  * first pass wrote, with its mirror, blur or border value.  With prev = next = 0 it is DepanCompensate's pass with the plan's transform.

@@ -133,3 +133,24 @@ def expected(c):
 
 def missing(c, stats):
     return [k for k in c["need"] if not stats.get(k)]
+
+
+# ---- what the GPU tests of DepanCompensate and DepanStabilise share
+
+def guarded(g, n):
+    """n output frames, each plane inside a buffer with one guard row either side, all 0xA5"""
+    import torch
+    full = [[torch.full((g.info.plane_height[p] + 2, g.pitch[p]), 0xA5, dtype=torch.uint8, device="cuda") for p in range(g.nplanes)] for _ in range(n)]
+    return full, [[t[1:-1] for t in fr] for fr in full]
+
+
+def check(full, want, dtype):
+    import pipeline as pl
+    item = np.dtype(dtype).itemsize
+    for k, planes in enumerate(want):
+        for p, wp in enumerate(planes):
+            buf = full[k][p].cpu().numpy()
+            got = np.ascontiguousarray(buf[1:-1, :wp.shape[1] * item]).view(dtype)
+            assert np.array_equal(got, wp), "job %d plane %d: %s" % (k, p, pl.first_diff(got, wp))
+            assert np.all(buf[0] == 0xA5) and np.all(buf[-1] == 0xA5), "job %d plane %d: a guard row was written" % (k, p)
+            assert np.all(buf[1:-1, wp.shape[1] * item:] == 0xA5), "job %d plane %d: bytes beyond the width were written" % (k, p)

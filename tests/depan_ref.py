@@ -1,4 +1,4 @@
-"""CPU restatement of mv.DepanCompensate and mv.DepanAnalyse (test infrastructure; the GPU parity tests compare the HIP path, mvx_depan.hip,
+"""CPU restatement of mv.DepanCompensate and mv.DepanAnalyse (test infrastructure; the GPU parity tests compare the HIP path, mvx_depan.hip and mvx_depan_warp.hip,
 and the host estimator, mvx_depan_host.h, against it).
 
 It follows the reference literally.  Citations are to dubhater/vapoursynth-mvtools src/MVDepan.cpp:

@@ -1,5 +1,5 @@
 """CPU restatement of mv.DepanStabilise (test infrastructure; tests/test_depan_stab_host.py holds the host planner, csrc/mvx_depan_stab_host.h,
-to it, and tests/test_depan_stab_ref.py / tests/test_gpu_depan_stabilise.py the fused per-sample selection, csrc/mvx_depan_stab_sample.h).
+to it, and tests/test_depan_stab_ref.py / tests/test_gpu_depan_stabilise.py the fused per-sample selection, csrc/mvx_depan_sample.h).
 
 It follows the reference literally.  Citations are to dubhater/vapoursynth-mvtools src/MVDepan.cpp:
   creation      :3909-4163          Inertial      :2945-3115      Average   :3118-3246      InertialLimit :3249-3329

@@ -123,11 +123,11 @@ def test_full_size_cases_take_seconds():
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    """csrc/mvx_depan_sample.h compiled for the host (tests/depan_sample_emu.cpp)"""
+    """csrc/mvx_depan_sample.h compiled for the host (tests/depan_warp_emu.cpp)"""
     here = os.path.dirname(os.path.abspath(__file__))
     so = str(tmp_path_factory.mktemp("depan_emu") / "libdepan_emu.so")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-I" + os.path.join(os.path.dirname(here), "vapoursynth-mvtools_amd", "csrc"),
-                           os.path.join(here, "depan_sample_emu.cpp"), "-o", so])
+                           os.path.join(here, "depan_warp_emu.cpp"), "-o", so])
     return C.CDLL(so)
 
 
@@ -161,9 +161,9 @@ def test_the_kernel_text_under_the_sanitizers_on_the_library_cases(tmp_path):
     if not shutil.which("g++") or subprocess.run(["g++"] + flags + [str(one), "-o", str(tmp_path / "one")], capture_output=True).returncode or \
             subprocess.run([str(tmp_path / "one")]).returncode:
         pytest.skip("g++ does not link -fsanitize=address,undefined here")
-    exe = str(tmp_path / "depan_sample_emu")
+    exe = str(tmp_path / "depan_warp_emu")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-DDEPAN_EMU_MAIN"] + flags + [
-        "-I" + os.path.join(os.path.dirname(here), "vapoursynth-mvtools_amd", "csrc"), os.path.join(here, "depan_sample_emu.cpp"), "-o", exe])
+        "-I" + os.path.join(os.path.dirname(here), "vapoursynth-mvtools_amd", "csrc"), os.path.join(here, "depan_warp_emu.cpp"), "-o", exe])
     runs = 0
     for case in dc.LIBRARY_CASES + [c for c in dc.CASES if c["name"] in ("small_s0_8", "small_s1_16", "small_s2_8", "gray_s2", "f444_s1")]:
         src, want, _ = dc.expected(case)
@@ -177,7 +177,7 @@ def test_the_kernel_text_under_the_sanitizers_on_the_library_cases(tmp_path):
                     fh.write(struct.pack("<8i", w, h, bps, case["sub"], case["mirror"], (1 << case["bits"]) - 1, 0 if p == 0 else 1 << (case["bits"] - 1), blur))
                     fh.write(np.ascontiguousarray(tp, dtype=f32).tobytes())
                     fh.write(np.ascontiguousarray(src[p]).tobytes())
-                r = subprocess.run([exe, fin, fout], capture_output=True, text=True)
+                r = subprocess.run([exe, "compensate", fin, fout], capture_output=True, text=True)
                 assert r.returncode == 0, (case["name"], k, p, r.stderr[-2000:])
                 got = np.fromfile(fout, dtype=src[p].dtype).reshape(h, w)
                 assert np.array_equal(got, want[k][p]), (case["name"], k, p)

@@ -1,6 +1,6 @@
 """CPU tests of DepanStabilise's painting: the restatement tests/depan_stab_ref.py against what follows from the reference's source alone, the
 condition on the cases of tests/depan_stab_cases.py -- each reaches the sources and branches it names -- and the kernel's own per-sample text
-(csrc/mvx_depan_stab_sample.h) compiled for the host and held to the restatement's sequential painting on every case, so that the fused
+(csrc/mvx_depan_sample.h) compiled for the host and held to the restatement's sequential painting on every case, so that the fused
 selection is proven before a GPU sees it.  The same text and the host planner run as a stand-alone program under AddressSanitizer and UBSan;
 nothing loaded into python runs under a sanitizer."""
 import ctypes as C
@@ -92,9 +92,9 @@ def test_full_size_cases_take_seconds():
 
 @pytest.fixture(scope="module")
 def emu(tmp_path_factory):
-    """csrc/mvx_depan_stab_sample.h and csrc/mvx_depan_stab_host.h compiled for the host (tests/depan_stab_emu.cpp)"""
+    """csrc/mvx_depan_sample.h and csrc/mvx_depan_stab_host.h compiled for the host (tests/depan_warp_emu.cpp)"""
     so = str(tmp_path_factory.mktemp("depan_stab_emu") / "libdepan_stab_emu.so")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-I" + CSRC, os.path.join(HERE, "depan_stab_emu.cpp"), "-o", so])
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-fPIC", "-shared", "-I" + CSRC, os.path.join(HERE, "depan_warp_emu.cpp"), "-o", so])
     return C.CDLL(so)
 
 
@@ -135,7 +135,7 @@ def test_the_kernel_text_on_the_host_equals_the_sequential_painting(emu, case):
 
 
 def plan_input(e, fps, ndest, motions):
-    """the input of `depan_stab_host_main plan` / depan_stab_emu_plan for the restatement object e, whose arguments are kept in e.args"""
+    """the input of `depan_warp_emu plan` / depan_stab_emu_plan for the restatement object e, whose arguments are kept in e.args"""
     a = e.args
     ints = [e.width, e.height, e.num_frames, int(a["addzoom"]), a["prev"], a["next"], a["mirror"], a["blur"], a["subpixel"], a["fitlast"], a["method"], int(a["fields"])]
     floats = [a[k] for k in ("cutoff", "damping", "initzoom", "dxmax", "dymax", "zoommax", "rotmax", "pixaspect", "tzoom")]
@@ -152,8 +152,8 @@ def test_the_planner_and_the_kernel_text_under_the_sanitizers(tmp_path):
     if not shutil.which("g++") or subprocess.run(["g++"] + flags + [str(one), "-o", str(tmp_path / "one")], capture_output=True).returncode or \
             subprocess.run([str(tmp_path / "one")]).returncode:
         pytest.skip("g++ does not link -fsanitize=address,undefined here")
-    exe = str(tmp_path / "depan_stab_host_main")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off"] + flags + ["-I" + CSRC, os.path.join(HERE, "depan_stab_host_main.cpp"), "-o", exe])
+    exe = str(tmp_path / "depan_warp_emu")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-DDEPAN_EMU_MAIN"] + flags + ["-I" + CSRC, os.path.join(HERE, "depan_warp_emu.cpp"), "-o", exe])
     runs = 0
     fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
     names = ("small_s0_8", "small_s1_16", "small_s2_8", "gray_s2", "f444_s1", "undef_s0", "undef_s1", "undef_s2", "self_s2", "covers_s2")

@@ -1,4 +1,4 @@
-"""GPU parity of mv.DepanCompensate and mv.DepanAnalyse (mvx_depan.hip) against the CPU restatement tests/depan_ref.py, through the Python
+"""GPU parity of mv.DepanCompensate (mvx_depan_warp.hip) and mv.DepanAnalyse (mvx_depan.hip) against the CPU restatement tests/depan_ref.py, through the Python
 package.  Bit-exact on every sample of every plane; all frames of a case in ONE mvx_depan_compensate_frames call.  Every destination plane
 is allocated with a guard row before and after it and filled with 0xA5: nothing but the samples may change.
 
@@ -18,24 +18,6 @@ f32 = np.float32
 W, H = 206, 118
 
 
-def _guarded(g, n):
-    """n output frames, each plane inside a buffer with one guard row either side, all 0xA5"""
-    import torch
-    full = [[torch.full((g.info.plane_height[p] + 2, g.pitch[p]), 0xA5, dtype=torch.uint8, device="cuda") for p in range(g.nplanes)] for _ in range(n)]
-    return full, [[t[1:-1] for t in fr] for fr in full]
-
-
-def _check(mv, g, full, want, dtype):
-    item = np.dtype(dtype).itemsize
-    for k, planes in enumerate(want):
-        for p, wp in enumerate(planes):
-            buf = full[k][p].cpu().numpy()
-            got = np.ascontiguousarray(buf[1:-1, :wp.shape[1] * item]).view(dtype)
-            assert np.array_equal(got, wp), "job %d plane %d: %s" % (k, p, pl.first_diff(got, wp))
-            assert np.all(buf[0] == 0xA5) and np.all(buf[-1] == 0xA5), "job %d plane %d: a guard row was written" % (k, p)
-            assert np.all(buf[1:-1, wp.shape[1] * item:] == 0xA5), "job %d plane %d: bytes beyond the width were written" % (k, p)
-
-
 def _run(mv, case):
     import torch
     src, want, stats = dc.expected(case)
@@ -43,10 +25,10 @@ def _run(mv, case):
     dev = [mv.plane_to_device(p) for p in src]
     g = mv.DepanCompensate(case["w"], case["h"], case["bits"], f["subsampling"], f.get("gray", False), src_pitch=[d.stride(0) for d in dev], offset=1.0,
                            subpixel=case["sub"], mirror=case["mirror"], blur=case["blur"])
-    full, out = _guarded(g, len(case["trs"]))
+    full, out = dc.guarded(g, len(case["trs"]))
     g.run([dev] * len(case["trs"]), case["trs"], out=out)
     torch.cuda.synchronize()
-    _check(mv, g, full, want, g.dtype)
+    dc.check(full, want, g.dtype)
     return stats
 
 
@@ -95,7 +77,7 @@ def test_the_rotation_chain_is_not_the_direct_product(mv):
 def test_no_frames_is_a_no_op(mv):
     import torch
     g = mv.DepanCompensate(W, H, offset=1.0)
-    full, out = _guarded(g, 1)
+    full, out = dc.guarded(g, 1)
     g.launch((mv.DepanCompensateJob * 0)())
     torch.cuda.synchronize()
     assert all(bool((t == 0xA5).all()) for t in full[0])
@@ -184,9 +166,9 @@ def test_end_to_end_on_a_planted_pan(mv):
                 trs.append(t)
                 want.append(dr.compensate_frame(frames[m[0]], t_ref, 2, 8, (1, 1), False, 15, 0, "strict"))
             assert len(src) == nf - 1
-            full, out = _guarded(g, len(src))
+            full, out = dc.guarded(g, len(src))
             g.run(src, trs, out=out)
             torch.cuda.synchronize()
-            _check(mv, g, full, want, np.uint8)
+            dc.check(full, want, np.uint8)
         # the planted pan of (3, -1) per frame comes back from real vectors; backward vectors give the inverse motion
         assert abs(abs(motions[2]["dx"]) - 3) < 0.5 and abs(abs(motions[2]["dy"]) - 1) < 0.5

@@ -1,4 +1,4 @@
-"""GPU parity of mv.DepanStabilise (mvx_depan_stab.hip) against the sequential painting of the CPU restatement tests/depan_stab_ref.py, through the
+"""GPU parity of mv.DepanStabilise (mvx_depan_warp.hip) against the sequential painting of the CPU restatement tests/depan_stab_ref.py, through the
 Python package.  Bit-exact on every sample of every plane; all jobs of a case in ONE mvx_depan_stabilise_frames call.  Every destination plane
 sits in a buffer with a guard row before and after it, filled with 0xA5: nothing but the samples may change.
 
@@ -12,28 +12,9 @@ import pytest
 import depan_cases as dc
 import depan_stab_cases as sc
 import depan_stab_ref as sr
-import pipeline as pl
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-
-
-def _guarded(g, n):
-    """n output frames, each plane inside a buffer with one guard row either side, all 0xA5"""
-    import torch
-    full = [[torch.full((g.info.plane_height[p] + 2, g.pitch[p]), 0xA5, dtype=torch.uint8, device="cuda") for p in range(g.nplanes)] for _ in range(n)]
-    return full, [[t[1:-1] for t in fr] for fr in full]
-
-
-def _check(full, want, dtype):
-    item = np.dtype(dtype).itemsize
-    for k, planes in enumerate(want):
-        for p, wp in enumerate(planes):
-            buf = full[k][p].cpu().numpy()
-            got = np.ascontiguousarray(buf[1:-1, :wp.shape[1] * item]).view(dtype)
-            assert np.array_equal(got, wp), "job %d plane %d: %s" % (k, p, pl.first_diff(got, wp))
-            assert np.all(buf[0] == 0xA5) and np.all(buf[-1] == 0xA5), "job %d plane %d: a guard row was written" % (k, p)
-            assert np.all(buf[1:-1, wp.shape[1] * item:] == 0xA5), "job %d plane %d: bytes beyond the width were written" % (k, p)
 
 
 def _plan(mv, cur, nxt, prev):
@@ -56,11 +37,11 @@ def _run(mv, case):
                           mirror=case["mirror"], blur=case["blur"], prev=1, next=1, num_frames=3)
     plans = [_plan(mv, *j) for j in case["jobs"]]
     n = len(plans)
-    full, out = _guarded(g, n)
+    full, out = dc.guarded(g, n)
     arr, _ = g.jobs(plans, [dev[0]] * n, [dev[j[2][0]] if j[2] else None for j in case["jobs"]], [dev[j[1][0]] if j[1] else None for j in case["jobs"]], out=out)
     g.launch(arr)
     torch.cuda.synchronize()
-    _check(full, want, g.dtype)
+    dc.check(full, want, g.dtype)
     return stats
 
 
@@ -102,11 +83,11 @@ def test_a_whole_clip(mv, size, method):
         p = e.plan(k, motions)
         want.append(e.paint(frames[k], p["tr"], (frames[p["prev"]["frame"]], p["prev"]["tr"]), (frames[p["next"]["frame"]], p["next"]["tr"]), stats))
     assert stats["from_cur"] and stats["from_next"] and stats["from_prev"] and stats["passes"] == 9 * n
-    full, out = _guarded(g, n)
+    full, out = dc.guarded(g, n)
     as_dicts = [dict(dx=m[0], dy=m[1], zoom=m[2], rot=m[3]) for m in motions]      # what DepanAnalyse.run and DepanEstimate.run return
     g.run(dev, as_dicts, out=out)
     torch.cuda.synchronize()
-    _check(full, want, np.uint8)
+    dc.check(full, want, np.uint8)
 
     g0 = mv.DepanStabilise(w, h, src_pitch=pitch, num_frames=n, **kw)
     plans = [g0.plan(k, motions[g0.window(k)[0]:g0.window(k)[1] + 1]) for k in range(n)]
@@ -139,10 +120,10 @@ def test_radius_zero_takes_the_border_value_and_the_fill_sources(mv):
             assert np.isnan(p["tr"]).all()
             src = lambda s: None if s is None else (frames[s["frame"]], s["tr"])
             want.append(e.paint(frames[k], p["tr"], src(p["prev"]), src(p["next"]), stats))
-        full, out = _guarded(g, n)
+        full, out = dc.guarded(g, n)
         g.run(dev, motions, out=out)
         torch.cuda.synchronize()
-        _check(full, want, np.uint8)
+        dc.check(full, want, np.uint8)
         assert stats["undef"] > 0
         if not fill:
             assert all(np.all(fr[0] == 0) and np.all(fr[1] == 128) and np.all(fr[2] == 128) for fr in want)
@@ -151,7 +132,7 @@ def test_radius_zero_takes_the_border_value_and_the_fill_sources(mv):
 def test_no_frames_is_a_no_op(mv):
     import torch
     g = mv.DepanStabilise(206, 118, num_frames=4, prev=1, next=1)
-    full, out = _guarded(g, 1)
+    full, out = dc.guarded(g, 1)
     g.launch((mv.DepanStabiliseJob * 0)())
     assert g.run([], []) == []
     torch.cuda.synchronize()

@@ -1,10 +1,14 @@
-// mvx_depan_sample.h -- DepanCompensate's arithmetic for one output sample (compensate_plane_nearest / _bilinear / _bicubic,
-// MVDepan.cpp:1626-2585): what depan_plane_kernel of mvx_depan.hip runs per thread.  It is a header without HIP so that
-// tests/test_depan_ref.py can compile the same text for the host and hold it to the restatement on a machine without a GPU.  Build with
-// -ffp-contract=off.
+// mvx_depan_sample.h -- the warp of DepanCompensate and DepanStabilise for one output sample, and the host side of the records it reads:
+// what depan_warp_kernel of mvx_depan_warp.hip runs per thread and what the two *_frames functions put into its table.
+//   dc_nearest / dc_bilinear / dc_bicubic : compensate_plane_nearest / _bilinear / _bicubic, MVDepan.cpp:1626-2585, one DCPlane record.
+//   ds_sample                             : DepanStabilise's selection among the up to three records of a plane (below).
+//   dc_plane_transform, dc_fill, ds_borders (host) : a record from (plane, source, luma transform).
+// It is a header without HIP so that tests/test_depan_ref.py and tests/test_depan_stab_ref.py can compile the same text for the host
+// (tests/depan_warp_emu.cpp) and hold it to the restatements on a machine without a GPU.  Build with -ffp-contract=off.
 #pragma once
 #include <math.h>
 #include <stddef.h>
+#include <string.h>
 #ifdef __HIPCC__
 #define DC_FN __device__ __forceinline__
 #else
@@ -33,9 +37,10 @@ DC_FN bool dc_ok(float v) { return fabsf(v) < DC_LIMIT; } // false for NaN
 DC_FN void dc_chain_row(const DCPlane &P, int h) {
     float xsrc = P.dxc + P.dxy * h, ysrc = P.dyc + P.dyy * h;
     float *c = P.chain + (size_t)h * P.segs * 2;
+    const float dxx = P.dxx, dyx = P.dyx; // read once: the stores through c could alias P, and the walk would wait for two loads per column
     for (int row = 0; row < P.W; row++) {
         if ((row & (DC_SEG - 1)) == 0) { c[0] = xsrc; c[1] = ysrc; c += 2; }
-        xsrc += P.dxx; ysrc += P.dyx;
+        xsrc += dxx; ysrc += dyx;
     }
 }
 
@@ -266,4 +271,70 @@ template <typename T> DC_FN int dc_bicubic(const DCPlane &P, const DCCommon &C, 
         if (rowleft >= W && (C.mirror & 8)) return dc_right<T>(P, hlow, rowleft, 0, 1);
     }
     return P.border;
+}
+
+template <typename T, int SUB> DC_FN int dc_sample(const DCPlane &P, const DCCommon &C, int h, int row) {
+    return SUB == 0 ? dc_nearest<T>(P, C, h, row) : SUB == 1 ? dc_bilinear<T>(P, C, h, row) : dc_bicubic<T>(P, C, h, row);
+}
+
+// ------------------------------------------------------------------------------------------------ DepanStabilise's selection
+// The reference paints one destination up to three times (MVDepan.cpp:3679-3693): fillBorderPrev (nearest, the filter's mirror, the border
+// value), fillBorderNext (nearest; border -1 and no mirror once prev has painted), compensateFrame (the subpixel interpolator; border -1 and
+// no mirror once anything has painted).  A pass with border -1 leaves a sample alone where its position is outside its source, and every
+// pass writes a pure function of its own source, so the last pass that holds a sample decides it: the current frame, else next, else prev.
+// A plane's three sources lie side by side, S[DS_CUR], S[DS_NEXT], S[DS_PREV]; an unused one has src == nullptr.  Exactly the first pass
+// painted carries a border value >= 0 and the mirror bits, so the selection always ends on a value >= 0.
+enum { DS_CUR = 0, DS_NEXT = 1, DS_PREV = 2, DS_SOURCES = 3 };
+
+template <typename T, int SUB> DC_FN int ds_sample(const DCPlane *S, const DCCommon &C, int h, int row) {
+    const DCCommon none = { 0, C.pixel_max, C.nplanes };
+    int v = dc_sample<T, SUB>(S[DS_CUR], S[DS_CUR].border >= 0 ? C : none, h, row);
+    if (v < 0 && S[DS_NEXT].src) v = dc_nearest<T>(S[DS_NEXT], S[DS_NEXT].border >= 0 ? C : none, h, row);
+    if (v < 0 && S[DS_PREV].src) v = dc_nearest<T>(S[DS_PREV], C, h, row);
+    return v;
+}
+
+// one output sample of a plane with NSRC records: 1 DepanCompensate, DS_SOURCES DepanStabilise
+template <typename T, int SUB, int NSRC> DC_FN void dc_store(const DCPlane *S, const DCCommon &C, int h, int row) {
+    const int v = NSRC == 1 ? dc_sample<T, SUB>(S[0], C, h, row) : ds_sample<T, SUB>(S, C, h, row);
+    ((T *)(S[DS_CUR].dst + (long long)h * S[DS_CUR].dpitch))[row] = (T)v;
+}
+
+// ------------------------------------------------------------------------------------------------ the host side of a record
+// what a filter's records share: the clip's geometry per plane, the pitches, and the arguments that both filters take
+struct DCClip {
+    int bits, np, ssw, ssh, subpixel, mirror, pixel_max;
+    int W[3], H[3], border[3], blur[3];
+    long long spitch[3], dpitch[3];
+};
+
+// plane p's transform from the pass's luma transform, MVDepan.cpp:2687-2700 / :3366-3379, and its form, the comparisons of :1666,1733 (the
+// same in all three interpolators); tr: dxc dxx dxy dyc dyx dyy
+static inline void dc_plane_transform(int ssw, int ssh, int p, const float *tr, DCPlane *P) {
+    float dxc = tr[0], dxx = tr[1], dxy = tr[2], dyc = tr[3], dyx = tr[4], dyy = tr[5];
+    if (p && ssw == 1 && ssh == 1) { dxc /= 2; dyc /= 2; }
+    else if (p && ssw == 1 && ssh == 0) { dxc /= 2; dxy /= 2; dyx *= 2; }
+    P->dxc = dxc; P->dxx = dxx; P->dxy = dxy; P->dyc = dyc; P->dyx = dyx; P->dyy = dyy;
+    P->cls = (dxy == 0.0f && dyx == 0.0f && dxx == 1.0f && dyy == 1.0f) ? 0 : (dxy == 0.0f && dyx == 0.0f) ? 1 : 2;
+}
+
+// the record of plane p read from src by the luma transform tr, with the border value of a first pass.  fill: a fill source of
+// DepanStabilise, nearest whatever subpixel is.  Returns the number of floats of the chain the record needs (the rotation form of nearest
+// and bilinear) and leaves P->chain to the caller.
+static inline size_t dc_fill(const DCClip &G, int p, const void *src, void *dst, const float *tr, bool fill, DCPlane *P) {
+    memset(P, 0, sizeof(*P));
+    P->src = (const unsigned char *)src; P->dst = (unsigned char *)dst;
+    P->spitch = G.spitch[p]; P->dpitch = G.dpitch[p];
+    P->W = G.W[p]; P->H = G.H[p];
+    P->border = G.border[p]; P->blur = G.blur[p];
+    dc_plane_transform(G.ssw, G.ssh, p, tr, P);
+    P->segs = (P->W + DC_SEG - 1) / DC_SEG;
+    return P->cls == 2 && (fill || G.subpixel < 2) ? (size_t)P->H * P->segs * 2 : 0;
+}
+
+// border values of the passes of one plane: `border` for the first pass painted (prev, else next, else the current frame), -1 for the others
+static inline void ds_borders(DCPlane *S, int border) {
+    S[DS_PREV].border = border;
+    S[DS_NEXT].border = S[DS_PREV].src ? -1 : border;
+    S[DS_CUR].border = S[DS_PREV].src || S[DS_NEXT].src ? -1 : border;
 }

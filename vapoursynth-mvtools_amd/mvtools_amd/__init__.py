@@ -1485,15 +1485,13 @@ class DepanEstimate(_Handle):
         return self.finish(res)
 
 
-class DepanCompensate(_Handle):
-    """mv.DepanCompensate(clip, data, offset, subpixel, pixaspect, matchfields, mirror, blur, info, fields, tff) -- MVDepan.cpp:2750-2881.
-    map(n) says which clip frame to warp and which data frames' motions to sum, transform(motions, ...) sums them (host arithmetic), and a
-    job is (src planes, summed transform).  `src_pitch` / `dst_pitch`: row pitches in bytes of the device planes."""
-    _destroy = "mvx_depan_compensate_destroy"
+class _DepanWarp(_Handle):
+    """What DepanCompensate and DepanStabilise share: the clip's format, the default pitches (rows rounded up to 256 bytes), the handle and its
+    info struct, the output arena and the launch of a job array.  _name: the stem of the library's functions; _info: the info struct's class."""
+    _name = _info = None
 
-    def __init__(self, width, height, bits=8, subsampling=(1, 1), gray=False, src_pitch=None, dst_pitch=None, offset=0.0, subpixel=None, pixaspect=1.0,
-                 matchfields=None, mirror=None, blur=None, fields=None, tff=None, num_frames=1 << 30, data_frames=None):
-        a = DepanCompensateArgs(float(offset), _u(subpixel), float(pixaspect), _u(matchfields), _u(mirror), _u(blur), _u(fields), _u(tff))
+    def _create(self, args, width, height, bits, subsampling, gray, src_pitch, dst_pitch, num_frames, data_frames, *extra):
+        """extra: the arguments of the creation function between data_frames and the pitches"""
         c = DepanClip(int(width), int(height), int(bits), int(subsampling[0]), int(subsampling[1]), int(bool(gray)))
         sw = 0 if gray else subsampling[0]
         bps = 2 if bits > 8 else 1
@@ -1505,11 +1503,29 @@ class DepanCompensate(_Handle):
         self.pitch = list(dst_pitch)
         self.dtype = np.uint16 if bits > 8 else np.uint8
         err = C.create_string_buffer(ERRLEN)
-        _check(lib().mvx_depan_compensate_create(C.byref(a), C.byref(c), int(num_frames), int(num_frames if data_frames is None else data_frames),
-                                                 _pad3(src_pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
-        self.info = DepanCompensateInfo()
-        lib().mvx_depan_compensate_get_info(self.h, C.byref(self.info))
+        _check(getattr(lib(), self._name + "_create")(C.byref(args), C.byref(c), int(num_frames), int(num_frames if data_frames is None else data_frames), *extra,
+                                                      _pad3(src_pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
+        self.info = self._info()
+        getattr(lib(), self._name + "_get_info")(self.h, C.byref(self.info))
         self.nplanes = self.info.num_planes
+
+    def alloc(self, n, device="cuda"):
+        return arena_frames(n, [(self.info.plane_height[p], self.pitch[p]) for p in range(self.nplanes)], device, zero=False)
+
+    def launch(self, arr):
+        _check(getattr(lib(), self._name + "_frames")(self.h, len(arr), arr, _stream()))
+
+
+class DepanCompensate(_DepanWarp):
+    """mv.DepanCompensate(clip, data, offset, subpixel, pixaspect, matchfields, mirror, blur, info, fields, tff) -- MVDepan.cpp:2750-2881.
+    map(n) says which clip frame to warp and which data frames' motions to sum, transform(motions, ...) sums them (host arithmetic), and a
+    job is (src planes, summed transform).  `src_pitch` / `dst_pitch`: row pitches in bytes of the device planes."""
+    _destroy, _name, _info = "mvx_depan_compensate_destroy", "mvx_depan_compensate", DepanCompensateInfo
+
+    def __init__(self, width, height, bits=8, subsampling=(1, 1), gray=False, src_pitch=None, dst_pitch=None, offset=0.0, subpixel=None, pixaspect=1.0,
+                 matchfields=None, mirror=None, blur=None, fields=None, tff=None, num_frames=1 << 30, data_frames=None):
+        a = DepanCompensateArgs(float(offset), _u(subpixel), float(pixaspect), _u(matchfields), _u(mirror), _u(blur), _u(fields), _u(tff))
+        self._create(a, width, height, bits, subsampling, gray, src_pitch, dst_pitch, num_frames, data_frames)
 
     def map(self, n):
         """(nsrc, start, end) of output frame n: warp clip frame nsrc by the motions of data frames start + 1 .. end; None: return clip frame n"""
@@ -1527,17 +1543,11 @@ class DepanCompensate(_Handle):
         _check(lib().mvx_depan_motion_to_transform(self.h, len(motions), arr, int(ndest), UNSET if top_field is None else int(bool(top_field)), tr, mo, err), err)
         return np.array(tr, dtype=np.float32), np.array(mo, dtype=np.float32)
 
-    def alloc(self, n, device="cuda"):
-        return arena_frames(n, [(self.info.plane_height[p], self.pitch[p]) for p in range(self.nplanes)], device, zero=False)
-
     def run(self, frames, transforms, out=None):
         """frames: per job the device planes of clip frame nsrc; transforms: per job trsum; all jobs in one call"""
         arr, out = self.jobs(frames, transforms, out)
         self.launch(arr)
         return out
-
-    def launch(self, arr):
-        _check(lib().mvx_depan_compensate_frames(self.h, len(arr), arr, _stream()))
 
     def jobs(self, frames, transforms, out=None):
         _torch()
@@ -1555,12 +1565,12 @@ class DepanCompensate(_Handle):
         return arr, out
 
 
-class DepanStabilise(_Handle):
+class DepanStabilise(_DepanWarp):
     """mv.DepanStabilise(clip, data, cutoff, damping, initzoom, addzoom, prev, next, mirror, blur, dxmax, dymax, zoommax, rotmax, subpixel, pixaspect,
     fitlast, tzoom, info, method, fields) -- MVDepan.cpp:3909-4208.  window(n) names the data frames whose motion plan(n, motions) reads (host
     arithmetic) and the clip frames its sources lie among; a job is a plan with the planes of the current, prev and next source frames; all jobs
     of a call are one fused launch.  `src_pitch` / `dst_pitch`: row pitches in bytes of the device planes.  Float arguments: None -> the default."""
-    _destroy = "mvx_depan_stabilise_destroy"
+    _destroy, _name, _info = "mvx_depan_stabilise_destroy", "mvx_depan_stabilise", DepanStabiliseInfo
 
     def __init__(self, width, height, bits=8, subsampling=(1, 1), gray=False, src_pitch=None, dst_pitch=None, fps=(25, 1), num_frames=1 << 30, cutoff=None,
                  damping=None, initzoom=None, addzoom=None, prev=None, next=None, mirror=None, blur=None, dxmax=None, dymax=None, zoommax=None, rotmax=None,
@@ -1568,23 +1578,8 @@ class DepanStabilise(_Handle):
         d = lambda v: float(UNSET) if v is None else float(v)
         a = DepanStabiliseArgs(d(cutoff), d(damping), d(initzoom), d(dxmax), d(dymax), d(zoommax), d(rotmax), d(pixaspect), d(tzoom), _u(addzoom), _u(prev),
                                _u(next), _u(mirror), _u(blur), _u(subpixel), _u(fitlast), _u(method), _u(fields))
-        c = DepanClip(int(width), int(height), int(bits), int(subsampling[0]), int(subsampling[1]), int(bool(gray)))
-        sw = 0 if gray else subsampling[0]
-        bps = 2 if bits > 8 else 1
-        if dst_pitch is None:
-            dst_pitch = [((max(int(width) >> s, 1) * bps + 255) // 256) * 256 for s in (0, sw, sw)]
-        if src_pitch is None:
-            src_pitch = dst_pitch
-        self.h = C.c_void_p()
-        self.pitch = list(dst_pitch)
-        self.dtype = np.uint16 if bits > 8 else np.uint8
         self.num_frames = int(num_frames)
-        err = C.create_string_buffer(ERRLEN)
-        _check(lib().mvx_depan_stabilise_create(C.byref(a), C.byref(c), self.num_frames, int(num_frames if data_frames is None else data_frames), int(fps[0]),
-                                                int(fps[1]), _pad3(src_pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
-        self.info = DepanStabiliseInfo()
-        lib().mvx_depan_stabilise_get_info(self.h, C.byref(self.info))
-        self.nplanes = self.info.num_planes
+        self._create(a, width, height, bits, subsampling, gray, src_pitch, dst_pitch, num_frames, data_frames, int(fps[0]), int(fps[1]))
 
     def windows(self):
         """the cosine windows wint, winrz, winfz: radius + 1 float32 each"""
@@ -1615,9 +1610,6 @@ class DepanStabilise(_Handle):
         _check(lib().mvx_depan_stabilise_plan(self.h, int(n), arr, C.byref(plan), err), err)
         return plan
 
-    def alloc(self, n, device="cuda"):
-        return arena_frames(n, [(self.info.plane_height[p], self.pitch[p]) for p in range(self.nplanes)], device, zero=False)
-
     def jobs(self, plans, cur, prev=None, next=None, out=None):
         """plans: per job a DepanStabilisePlan; cur / prev / next: per job the device planes of clip frame n, plan.prev.frame, plan.next.frame
         (prev / next entries may be None where the plan does not use them)"""
@@ -1636,9 +1628,6 @@ class DepanStabilise(_Handle):
                 if plans[k].next.used:
                     arr[k].next[p] = next[k][p].data_ptr()
         return arr, out
-
-    def launch(self, arr):
-        _check(lib().mvx_depan_stabilise_frames(self.h, len(arr), arr, _stream()))
 
     def run(self, frames, motions, out=None):
         """a whole clip: frames[n] the device planes of clip frame n, motions[n] the motion of data frame n; every output frame in one call"""

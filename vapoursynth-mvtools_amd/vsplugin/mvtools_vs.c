@@ -2944,13 +2944,57 @@ static void VS_CC depanEstimateCreate(const VSMap *in, VSMap *out, void *user, V
     if (d->info && !vs->mapGetError(out)) depan_info_overlay("DepanEstimate", "DepanEstimate_info", out, core, vs);
 }
 
-/* ---- mv.DepanCompensate, MVDepan.cpp:2588-2735 / :2750-2881 */
+/* ---- what mv.DepanCompensate (dc, ci) and mv.DepanStabilise (ds) share: the instance, the opening and the end of creation, the tail of a frame */
+typedef struct DepanWarpData { Consumer c; VSNode *node, *data; const VSVideoInfo *vi; ptrdiff_t pitch[3]; int height[3], info; mvx_depan_compensate *dc; mvx_depan_compensate_info ci; mvx_depan_stabilise *ds; } DepanWarpData;
 
-typedef struct DepanCompData { Consumer c; VSNode *node, *data; const VSVideoInfo *vi; mvx_depan_compensate *dc; mvx_depan_compensate_info ci; ptrdiff_t pitch[3]; int info; } DepanCompData;
+/* the instance with its clip and data nodes, the clip's format as the library takes it, and the pitches and heights of the device planes */
+static DepanWarpData *depan_warp_open(const char *name, VSFilterGetFrame body, void (*destroy)(void *), const VSMap *in, mvx_depan_clip *clip, const VSAPI *vs) {
+    DepanWarpData *d = (DepanWarpData *)consumer_new(sizeof(*d), name, body, destroy);
+    int e = 0;
+    d->info = !!vs->mapGetInt(in, "info", 0, &e);
+    d->node = consumer_node(&d->c, in, "clip", vs);
+    d->vi = vs->getVideoInfo(d->node);
+    d->data = consumer_node(&d->c, in, "data", vs);
+    depan_clip_of(clip, d->vi, NULL);
+    clip_pitches(d->pitch, d->vi, d->vi->format.bytesPerSample > 0 ? d->vi->format.bytesPerSample : 1);
+    for (int p = 0; p < 3; p++) d->height[p] = p ? d->vi->height >> d->vi->format.subSamplingH : d->vi->height;
+    return d;
+}
+/* after the library's creation: the engine handed to the skeleton, the filter, and with info=1 text.FrameProps behind it */
+static void depan_warp_register(DepanWarpData *d, const char *name, const char *prop, void *engine, VSMap *out, VSCore *core, const VSAPI *vs) {
+    d->c.engine = engine;
+    VSFilterDependency deps[2] = { { d->node, rpGeneral }, { d->data, rpGeneral } };
+    vs->createVideoFilter(out, name, d->vi, consumerGetFrame, consumerFree, fmParallel, deps, 2, d, core);
+    if (d->info && !vs->mapGetError(out)) depan_info_overlay(name, prop, out, core, vs);
+}
+/* rc: what the uploads of the job's sources gave.  Allocates the destination planes into jobDst (the job's dst member), launches the one job, downloads into a new
+ * frame with src's properties, and frees the arenas and src.  NULL, with the filter error set, when any step failed */
+static VSFrame *depan_warp_finish(DepanWarpData *d, const char *name, int rc, const void *job, void *jobDst[3], void *const *arena, int narena, const VSFrame *src,
+        VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    const int np = d->vi->format.numPlanes, bps = d->vi->format.bytesPerSample;
+    void *dstArena = NULL, *ddst[3];
+    if (!rc) rc = dst_plane_set(ddst, &dstArena, d->pitch, d->height, np);
+    for (int p = 0; p < np && !rc; p++) jobDst[p] = ddst[p];
+    if (!rc) rc = d->ds ? mvx_depan_stabilise_frames(d->ds, 1, (const mvx_depan_stabilise_job *)job, thread_stream())
+                        : mvx_depan_compensate_frames(d->dc, 1, (const mvx_depan_compensate_job *)job, thread_stream());
+    VSFrame *dst = NULL;
+    if (!rc) {
+        dst = vs->newVideoFrame(&d->vi->format, d->vi->width, d->vi->height, src, core);
+        rc = download_plane_set(dst, ddst, d->pitch, np, bps, vs);
+    }
+    shell_quiesce(rc);
+    for (int k = 0; k < narena; k++) if (arena[k]) mvx_dev_free(arena[k]);
+    if (dstArena) mvx_dev_free(dstArena);
+    vs->freeFrame(src);
+    if (rc) { if (dst) vs->freeFrame(dst); depan_frame_error(name, rc, ctx, vs); return NULL; }
+    return dst;
+}
+
+/* ---- mv.DepanCompensate, MVDepan.cpp:2588-2735 / :2750-2881 */
 
 static const VSFrame *VS_CC depanCompGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
     (void)fd;
-    DepanCompData *d = (DepanCompData *)inst;
+    DepanWarpData *d = (DepanWarpData *)inst;
     int nsrc = n, start = n, end = n;
     const int warp = mvx_depan_compensate_map(d->dc, n, &nsrc, &start, &end);
     if (reason == arInitial) { /* :2594-2609 */
@@ -2978,26 +3022,15 @@ static const VSFrame *VS_CC depanCompGetFrameUngated(int n, int reason, void *in
     char lerr[MVX_ERRLEN] = "";
     if (mvx_depan_motion_to_transform(d->dc, count, motions, n, e ? MVX_UNSET : field, trsum, motion, lerr)) { vs->setFilterError(lerr, ctx); return NULL; }
     const VSFrame *src = vs->getFrameFilter(nsrc, d->node, ctx);
-    const int np = d->vi->format.numPlanes, bps = d->vi->format.bytesPerSample;
+    const int np = d->vi->format.numPlanes;
     mvx_depan_compensate_job job;
     memset(&job, 0, sizeof(job));
-    void *srcArena = NULL, *dstArena = NULL, *dsrc[3], *ddst[3];
-    int rc = upload_plane_set(dsrc, &srcArena, src, d->pitch, np, bps, vs);
-    if (!rc) rc = dst_plane_set(ddst, &dstArena, d->pitch, d->ci.plane_height, np);
-    for (int p = 0; p < np && !rc; p++) { job.src[p] = dsrc[p]; job.dst[p] = ddst[p]; }
+    void *srcArena = NULL, *dsrc[3];
+    const int rc = upload_plane_set(dsrc, &srcArena, src, d->pitch, np, d->vi->format.bytesPerSample, vs);
+    for (int p = 0; p < np && !rc; p++) job.src[p] = dsrc[p];
     memcpy(job.tr, trsum, sizeof(job.tr));
-    if (!rc) rc = mvx_depan_compensate_frames(d->dc, 1, &job, thread_stream());
-    VSFrame *dst = NULL;
-    if (!rc) {
-        dst = vs->newVideoFrame(&d->vi->format, d->vi->width, d->vi->height, src, core);
-        rc = download_plane_set(dst, ddst, d->pitch, np, bps, vs);
-    }
-    shell_quiesce(rc);
-    if (srcArena) mvx_dev_free(srcArena);
-    if (dstArena) mvx_dev_free(dstArena);
-    vs->freeFrame(src);
-    if (rc) { if (dst) vs->freeFrame(dst); depan_frame_error("DepanCompensate", rc, ctx, vs); return NULL; }
-    if (d->info) { /* :2724 */
+    VSFrame *dst = depan_warp_finish(d, "DepanCompensate", rc, &job, job.dst, &srcArena, 1, src, ctx, core, vs);
+    if (dst && d->info) { /* :2724 */
         char info[129];
         snprintf(info, 128, "offset=%.2f, %d to %d, dx=%.2f, dy=%.2f, rot=%.3f zoom=%.5f", d->ci.offset, nsrc, n, motion[0], motion[1], motion[3], motion[2]);
         depan_set_info(dst, "DepanCompensate_info", info, vs);
@@ -3008,37 +3041,25 @@ static const VSFrame *VS_CC depanCompGetFrameUngated(int n, int reason, void *in
 static void VS_CC depanCompCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
     warm_barrier();
     (void)user;
-    DepanCompData *d = (DepanCompData *)consumer_new(sizeof(*d), "DepanCompensate", depanCompGetFrameUngated, mvx_depan_compensate_destroy_engine);
+    mvx_depan_clip clip;
+    DepanWarpData *d = depan_warp_open("DepanCompensate", depanCompGetFrameUngated, mvx_depan_compensate_destroy_engine, in, &clip, vs);
     char lerr[MVX_ERRLEN] = "";
-    int e = 0;
     mvx_depan_compensate_args a;
     a.offset = opt_float(in, "offset", 0.0, vs); a.subpixel = opt_int(in, "subpixel", vs); a.pixaspect = opt_float(in, "pixaspect", 1.0, vs);
     a.matchfields = opt_int(in, "matchfields", vs); a.mirror = opt_int(in, "mirror", vs); a.blur = opt_int(in, "blur", vs);
     FieldOpt fo;
     field_opt(&fo, in, vs);
     a.fields = fo.fields; a.tff = fo.tffExists ? fo.tff : MVX_UNSET;
-    d->info = !!vs->mapGetInt(in, "info", 0, &e);
-    d->node = consumer_node(&d->c, in, "clip", vs);
-    d->vi = vs->getVideoInfo(d->node);
-    d->data = consumer_node(&d->c, in, "data", vs);
-    mvx_depan_clip clip;
-    depan_clip_of(&clip, d->vi, NULL);
-    clip_pitches(d->pitch, d->vi, d->vi->format.bytesPerSample > 0 ? d->vi->format.bytesPerSample : 1);
     if (mvx_depan_compensate_create(&a, &clip, d->vi->numFrames, vs->getVideoInfo(d->data)->numFrames, d->pitch, d->pitch, &d->dc, lerr)) { consumer_fail(&d->c, lerr, out, vs); return; }
-    d->c.engine = d->dc;
     mvx_depan_compensate_get_info(d->dc, &d->ci);
-    VSFilterDependency deps[2] = { { d->node, rpGeneral }, { d->data, rpGeneral } };
-    vs->createVideoFilter(out, "DepanCompensate", d->vi, consumerGetFrame, consumerFree, fmParallel, deps, 2, d, core);
-    if (d->info && !vs->mapGetError(out)) depan_info_overlay("DepanCompensate", "DepanCompensate_info", out, core, vs);
+    depan_warp_register(d, "DepanCompensate", "DepanCompensate_info", d->dc, out, core, vs);
 }
 
 /* ---- mv.DepanStabilise, MVDepan.cpp:3562-3885 / :3909-4208 */
 
-typedef struct DepanStabData { Consumer c; VSNode *node, *data; const VSVideoInfo *vi; mvx_depan_stabilise *ds; mvx_depan_stabilise_info si; ptrdiff_t pitch[3]; int info; } DepanStabData;
-
 static const VSFrame *VS_CC depanStabGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
     (void)fd;
-    DepanStabData *d = (DepanStabData *)inst;
+    DepanWarpData *d = (DepanWarpData *)inst;
     int df = n, dl = n, cf = n, cl = n;
     int rc = mvx_depan_stabilise_window(d->ds, n, &df, &dl, &cf, &cl);
     if (rc) { if (reason == arInitial || reason == arAllFramesReady) depan_frame_error("DepanStabilise", rc, ctx, vs); return NULL; }
@@ -3068,7 +3089,7 @@ static const VSFrame *VS_CC depanStabGetFrameUngated(int n, int reason, void *in
     if (rc) { vs->setFilterError(lerr, ctx); return NULL; }
     const int np = d->vi->format.numPlanes, bps = d->vi->format.bytesPerSample;
     const VSFrame *src = vs->getFrameFilter(n, d->node, ctx);
-    void *arena[3] = { NULL, NULL, NULL }, *dstArena = NULL, *dcur[3], *dprev[3], *dnext[3], *ddst[3];
+    void *arena[3] = { NULL, NULL, NULL }, *dcur[3], *dprev[3], *dnext[3];
     rc = upload_plane_set(dcur, &arena[0], src, d->pitch, np, bps, vs);
     if (!rc && job.plan.prev.used) {
         const VSFrame *f = vs->getFrameFilter(job.plan.prev.frame, d->node, ctx);
@@ -3080,24 +3101,13 @@ static const VSFrame *VS_CC depanStabGetFrameUngated(int n, int reason, void *in
         rc = f ? upload_plane_set(dnext, &arena[2], f, d->pitch, np, bps, vs) : MVX_E_ARG;
         vs->freeFrame(f);
     }
-    if (!rc) rc = dst_plane_set(ddst, &dstArena, d->pitch, d->si.plane_height, np);
     for (int p = 0; p < np && !rc; p++) {
-        job.cur[p] = dcur[p]; job.dst[p] = ddst[p];
+        job.cur[p] = dcur[p];
         if (job.plan.prev.used) job.prev[p] = dprev[p];
         if (job.plan.next.used) job.next[p] = dnext[p];
     }
-    if (!rc) rc = mvx_depan_stabilise_frames(d->ds, 1, &job, thread_stream());
-    VSFrame *dst = NULL;
-    if (!rc) {
-        dst = vs->newVideoFrame(&d->vi->format, d->vi->width, d->vi->height, src, core);
-        rc = download_plane_set(dst, ddst, d->pitch, np, bps, vs);
-    }
-    shell_quiesce(rc);
-    for (int k = 0; k < 3; k++) if (arena[k]) mvx_dev_free(arena[k]);
-    if (dstArena) mvx_dev_free(dstArena);
-    vs->freeFrame(src);
-    if (rc) { if (dst) vs->freeFrame(dst); depan_frame_error("DepanStabilise", rc, ctx, vs); return NULL; }
-    if (d->info) { /* :3554 */
+    VSFrame *dst = depan_warp_finish(d, "DepanStabilise", rc, &job, job.dst, arena, 3, src, ctx, core, vs);
+    if (dst && d->info) { /* :3554 */
         char info[129];
         snprintf(info, 128, "frame=%d %s=%d dx=%.2f dy=%.2f rot=%.3f zoom=%.5f", n, job.plan.base ? "BASE!" : "base ", job.plan.nbase, job.plan.motion[0], job.plan.motion[1],
                  job.plan.motion[3], job.plan.motion[2]);
@@ -3109,31 +3119,17 @@ static const VSFrame *VS_CC depanStabGetFrameUngated(int n, int reason, void *in
 static void VS_CC depanStabCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
     warm_barrier();
     (void)user;
-    DepanStabData *d = (DepanStabData *)consumer_new(sizeof(*d), "DepanStabilise", depanStabGetFrameUngated, mvx_depan_stabilise_destroy_engine);
+    mvx_depan_clip clip;
+    DepanWarpData *d = depan_warp_open("DepanStabilise", depanStabGetFrameUngated, mvx_depan_stabilise_destroy_engine, in, &clip, vs);
     char lerr[MVX_ERRLEN] = "";
-    int e = 0;
     mvx_depan_stabilise_args a;
     a.cutoff = opt_float_unset(in, "cutoff", vs); a.damping = opt_float_unset(in, "damping", vs); a.initzoom = opt_float_unset(in, "initzoom", vs);
     a.dxmax = opt_float_unset(in, "dxmax", vs); a.dymax = opt_float_unset(in, "dymax", vs); a.zoommax = opt_float_unset(in, "zoommax", vs); a.rotmax = opt_float_unset(in, "rotmax", vs);
     a.pixaspect = opt_float_unset(in, "pixaspect", vs); a.tzoom = opt_float_unset(in, "tzoom", vs);
     a.addzoom = opt_int(in, "addzoom", vs); a.prev = opt_int(in, "prev", vs); a.next = opt_int(in, "next", vs); a.mirror = opt_int(in, "mirror", vs); a.blur = opt_int(in, "blur", vs);
     a.subpixel = opt_int(in, "subpixel", vs); a.fitlast = opt_int(in, "fitlast", vs); a.method = opt_int(in, "method", vs); a.fields = opt_int(in, "fields", vs);
-    d->info = !!vs->mapGetInt(in, "info", 0, &e);
-    d->node = consumer_node(&d->c, in, "clip", vs);
-    d->vi = vs->getVideoInfo(d->node);
-    d->data = consumer_node(&d->c, in, "data", vs);
-    mvx_depan_clip clip;
-    depan_clip_of(&clip, d->vi, NULL);
-    clip_pitches(d->pitch, d->vi, d->vi->format.bytesPerSample > 0 ? d->vi->format.bytesPerSample : 1);
-    if (mvx_depan_stabilise_create(&a, &clip, d->vi->numFrames, vs->getVideoInfo(d->data)->numFrames, d->vi->fpsNum, d->vi->fpsDen, d->pitch, d->pitch, &d->ds, lerr)) {
-        consumer_fail(&d->c, lerr, out, vs);
-        return;
-    }
-    d->c.engine = d->ds;
-    mvx_depan_stabilise_get_info(d->ds, &d->si);
-    VSFilterDependency deps[2] = { { d->node, rpGeneral }, { d->data, rpGeneral } };
-    vs->createVideoFilter(out, "DepanStabilise", d->vi, consumerGetFrame, consumerFree, fmParallel, deps, 2, d, core);
-    if (d->info && !vs->mapGetError(out)) depan_info_overlay("DepanStabilise", "DepanStabilise_info", out, core, vs);
+    if (mvx_depan_stabilise_create(&a, &clip, d->vi->numFrames, vs->getVideoInfo(d->data)->numFrames, d->vi->fpsNum, d->vi->fpsDen, d->pitch, d->pitch, &d->ds, lerr)) { consumer_fail(&d->c, lerr, out, vs); return; }
+    depan_warp_register(d, "DepanStabilise", "DepanStabilise_info", d->ds, out, core, vs);
 }
 
 /* ------------------------------------------------------------------------------------------------ entry point */
