@@ -378,6 +378,39 @@ typedef struct mvx_compensate_n_job {
  * jobs, then one output kernel per plane class whose grid covers the 2 * tr + 1 planes of every job (csrc/mvx_compensate_n.hip). */
 int mvx_compensate_n_frames(mvx_compensate_n *c, int njobs, const mvx_compensate_n_job *jobs, void *stream);
 
+/* ---- mv.RecalculateN: a multi blob refined field by field -------------------------------------------
+ * No reference counterpart: pinterf's MRecalculate(tr=...) is the model.  Field r of the new multi blob is one mvx_recalculate_frames result
+ * on field r of the old one, byte for byte.  As in AnalyseN a field's isb and delta only label its MVTools_MVAnalysisData, so ONE
+ * mvx_recalculate serves every field. */
+
+typedef struct mvx_recalculate_n mvx_recalculate_n;
+
+/* radius 1..MVX_DEGRAIN_N_MAX_RADIUS ("RecalculateN: radius must be between 1 and 24."); vectors_data: of field 0 of the old multi blob, so
+ * backward with delta 1 ("RecalculateN: vectors_data must be field 0 of a multi blob."); every other message is mvx_recalculate_create's with
+ * the name RecalculateN, in the same order, and dct 1..4 stay behind mvx_enable_dct_float.  Touches no device. */
+int mvx_recalculate_n_create(const mvx_recalculate_args *args, int radius, const mvx_super *super_clip, const mvx_analysis_data *vectors_data,
+                             const ptrdiff_t super_pitch[3], mvx_recalculate_n **out, char *err);
+void mvx_recalculate_n_destroy(mvx_recalculate_n *r);
+/* the MVTools_MVAnalysisData of field r of the result: what an mvx_recalculate created on field r's old data reports; MVX_E_ARG for r
+ * outside 0..2 * radius - 1 */
+int mvx_recalculate_n_get_data(const mvx_recalculate_n *rn, int r, mvx_analysis_data *out);
+size_t mvx_recalculate_n_field_size(const mvx_recalculate_n *r);   /* bytes of one field: mvx_recalculate_blob_size */
+size_t mvx_recalculate_n_field_stride(const mvx_recalculate_n *r); /* field_size rounded up to 256 */
+size_t mvx_recalculate_n_blob_size(const mvx_recalculate_n *r);    /* 2 * radius * field_stride */
+
+typedef struct mvx_recalculate_n_job {
+    const void *src[3];              /* super frame n (device) */
+    const void *const (*refs)[3];    /* HOST array of 2 * radius entries in the order of mvx_analyse_n_job; refs[r][0] NULL = that frame is
+                                        outside the clip: field r is the invalid blob mvx_recalculate_frames writes for a NULL reference */
+    const void *old_blob;            /* the old multi blob of frame n (device, 16-byte aligned) */
+    size_t old_field_stride;         /* field stride of the object that wrote it (a multiple of 16) */
+    void *blob;                      /* device, mvx_recalculate_n_blob_size() bytes, 16-byte aligned */
+} mvx_recalculate_n_job;
+
+/* All 2 * radius * njobs refinements of the call go to the device as ONE mvx_recalculate_frames call.  `jobs` and the arrays behind refs are
+ * HOST arrays, read before the call returns.  The bytes between a field's end and the next field are never written. */
+int mvx_recalculate_n_frames(mvx_recalculate_n *r, int njobs, const mvx_recalculate_n_job *jobs, void *stream);
+
 /* ---- mv.BlockFPS ---------------------------------------------------------------------------------
  * replaces mvblockfpsCreate / mvblockfpsGetFrame, MVBlockFPS.c:741-1014 / :229-676 (arg string :1017-1033);
  * masks MaskFun.cpp:63-166, mask upsizer SimpleResize.cpp:27-121.                                     */

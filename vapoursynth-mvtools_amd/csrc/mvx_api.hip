@@ -363,3 +363,71 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_n_frames(mvx_a
     }
     return mvx_analyse_frames(a->an, (int)all.size(), all.data(), stream);
 }
+
+// ================================================================================================ mv.RecalculateN
+// A multi blob refined field by field (mvtools_amd.h).  As above, isb and delta only label the MVTools_MVAnalysisData: ONE mvx_recalculate
+// serves every field and a call is one mvx_recalculate_frames batch of 2 * radius * njobs jobs; the refinement kernels are untouched.
+struct mvx_recalculate_n {
+    mvx_recalculate *rc = nullptr;
+    int radius = 0;
+    size_t stride = 0;
+    mvx_analysis_data ad;      // of field 0
+};
+
+extern "C" __attribute__((visibility("default"))) int mvx_recalculate_n_create(const mvx_recalculate_args *a, int radius, const mvx_super *sup, const mvx_analysis_data *vectors,
+                                                                               const ptrdiff_t super_pitch[3], mvx_recalculate_n **out, char *err) {
+    MVX_CREATE_BEGIN(out);
+    if (radius < 1 || radius > MVX_DEGRAIN_N_MAX_RADIUS) MVX_FAIL("RecalculateN: radius must be between 1 and %d.", MVX_DEGRAIN_N_MAX_RADIUS);
+    if (!vectors->isBackward || vectors->nDeltaFrame != 1) MVX_FAIL("RecalculateN: vectors_data must be field 0 of a multi blob.");
+    mvx_recalculate *rc = nullptr;
+    char msg[MVX_ERRLEN];
+    if (int e = mvx_recalculate_create(a, sup, vectors, super_pitch, &rc, msg)) {
+        // mvx_recalculate_create's message under this filter's name (the library's own messages carry no name and pass as they are)
+        if (!strncmp(msg, "Recalculate:", 12)) snprintf(err, MVX_ERRLEN, "RecalculateN:%s", msg + 12);
+        else snprintf(err, MVX_ERRLEN, "%s", msg);
+        mvx_set_error("%s", err);
+        return e;
+    }
+    mvx_recalculate_n *h = new mvx_recalculate_n();
+    h->rc = rc;
+    h->radius = radius;
+    h->stride = ((size_t)mvx_recalculate_blob_size(rc) + 255) / 256 * 256;
+    mvx_recalculate_get_data(rc, &h->ad);
+    *out = h;
+    return MVX_OK;
+}
+extern "C" __attribute__((visibility("default"))) void mvx_recalculate_n_destroy(mvx_recalculate_n *r) {
+    if (!r) return;
+    mvx_recalculate_destroy(r->rc);
+    delete r;
+}
+extern "C" __attribute__((visibility("default"))) int mvx_recalculate_n_get_data(const mvx_recalculate_n *rn, int r, mvx_analysis_data *out) {
+    if (r < 0 || r >= 2 * rn->radius) { mvx_set_error("mvx_recalculate_n_get_data: field %d of %d", r, 2 * rn->radius); return MVX_E_ARG; }
+    *out = rn->ad;
+    out->isBackward = r % 2 == 0;
+    out->nDeltaFrame = r / 2 + 1;
+    out->nMotionFlags = (rn->ad.nMotionFlags & ~MVX_MOTION_IS_BACKWARD) | (out->isBackward ? MVX_MOTION_IS_BACKWARD : 0); // MVRecalculate.c:501
+    return MVX_OK;
+}
+extern "C" __attribute__((visibility("default"))) size_t mvx_recalculate_n_field_size(const mvx_recalculate_n *r) { return (size_t)mvx_recalculate_blob_size(r->rc); }
+extern "C" __attribute__((visibility("default"))) size_t mvx_recalculate_n_field_stride(const mvx_recalculate_n *r) { return r->stride; }
+extern "C" __attribute__((visibility("default"))) size_t mvx_recalculate_n_blob_size(const mvx_recalculate_n *r) { return 2 * (size_t)r->radius * r->stride; }
+
+extern "C" __attribute__((visibility("default"))) int mvx_recalculate_n_frames(mvx_recalculate_n *rn, int njobs, const mvx_recalculate_n_job *jobs, void *stream) {
+    if (njobs <= 0) return MVX_OK;
+    const int nf = 2 * rn->radius;
+    std::vector<mvx_recalculate_job> all((size_t)njobs * nf);
+    for (int j = 0; j < njobs; j++) {
+        const mvx_recalculate_n_job &J = jobs[j];
+        if (!J.refs || !J.blob) { mvx_set_error("mvx_recalculate_n_frames: a job needs its reference table and its blob"); return MVX_E_ARG; }
+        if (!J.old_blob) { mvx_set_error("mvx_recalculate_n_frames: old_blob is required"); return MVX_E_ARG; }
+        if ((((uintptr_t)J.blob) & 15) || (((uintptr_t)J.old_blob) & 15) || (J.old_field_stride & 15)) { mvx_set_error("mvx_recalculate_n_frames: blobs must be 16-byte aligned"); return MVX_E_ARG; }
+        for (int r = 0; r < nf; r++) {
+            mvx_recalculate_job &o = all[(size_t)j * nf + r];
+            for (int p = 0; p < 3; p++) { o.src[p] = J.src[p]; o.ref[p] = J.refs[r][0] ? J.refs[r][p] : nullptr; }
+            o.old_blob = (const unsigned char *)J.old_blob + (size_t)r * J.old_field_stride;
+            o.blob = (unsigned char *)J.blob + (size_t)r * rn->stride;
+        }
+    }
+    return mvx_recalculate_frames(rn->rc, (int)all.size(), all.data(), stream);
+}

@@ -7,6 +7,7 @@
     core.mv.Compensate(clip, super, vectors, ...)     -> Compensate(super, analysis_data, ...)      .run(jobs)
     (no reference name: one frame against a radius)   -> AnalyseN(super, radius, num_frames, ...)  .ad(r) .fields(multi_blob) .run(jobs)
                                                          CompensateN(tr, super, analysis_data, ...) .map(k) .run(jobs)
+                                                         RecalculateN(super, analysis_data, radius, ...) .get_data(r) .run(jobs)
     core.mv.FlowInter / FlowFPS(clip, super, mvbw, mvfw, ...) -> FlowInter / FlowFPS(super, bw_data, fw_data, ...) .run(ns, ...)
     core.mv.Flow(clip, super, vectors, ...)           -> Flow(super, analysis_data, ...)          .run(jobs)
     core.mv.FlowBlur(clip, super, mvbw, mvfw, ...)    -> FlowBlur(super, bw_data, fw_data, ...)   .run(ns, ...)
@@ -123,6 +124,11 @@ class RecalculateArgs(C.Structure):
 
 class RecalculateJob(C.Structure):
     _fields_ = [("src", C.c_void_p * 3), ("ref", C.c_void_p * 3), ("old_blob", C.c_void_p), ("blob", C.c_void_p)]
+
+
+class RecalculateNJob(C.Structure):
+    _fields_ = [("src", C.c_void_p * 3), ("refs", C.POINTER(C.c_void_p * 3)), ("old_blob", C.c_void_p), ("old_field_stride", C.c_size_t),
+                ("blob", C.c_void_p)]
 
 
 class BlockFPSArgs(C.Structure):
@@ -345,6 +351,13 @@ def lib():
         L.mvx_recalculate_get_data.argtypes = [C.c_void_p, P(AnalysisData)]
         L.mvx_recalculate_blob_size.argtypes = [C.c_void_p]
         L.mvx_recalculate_frames.argtypes = [C.c_void_p, C.c_int, P(RecalculateJob), C.c_void_p]
+        L.mvx_recalculate_n_create.argtypes = [P(RecalculateArgs), C.c_int, C.c_void_p, P(AnalysisData), P(C.c_ssize_t), P(C.c_void_p), C.c_char_p]
+        L.mvx_recalculate_n_destroy.argtypes = [C.c_void_p]
+        L.mvx_recalculate_n_get_data.argtypes = [C.c_void_p, C.c_int, P(AnalysisData)]
+        for f in (L.mvx_recalculate_n_field_size, L.mvx_recalculate_n_field_stride, L.mvx_recalculate_n_blob_size):
+            f.argtypes = [C.c_void_p]
+            f.restype = C.c_size_t
+        L.mvx_recalculate_n_frames.argtypes = [C.c_void_p, C.c_int, P(RecalculateNJob), C.c_void_p]
         L.mvx_blockfps_create.argtypes = [P(BlockFPSArgs), P(AnalysisData), P(AnalysisData), C.c_void_p, C.c_int, C.c_int64, C.c_int64, P(C.c_ssize_t),
                                           P(C.c_ssize_t), P(C.c_ssize_t), P(C.c_void_p), C.c_char_p]
         L.mvx_blockfps_destroy.argtypes = [C.c_void_p]
@@ -1679,6 +1692,69 @@ class Recalculate(_Handle):
             arr[i].old_blob = ob.data_ptr()
             arr[i].blob = blobs[i].data_ptr()
         _check(lib().mvx_recalculate_frames(self.h, n, arr, _stream()))
+        return blobs
+
+
+class RecalculateN(_Handle):
+    """A multi blob refined field by field (include/mvtools_amd.h, mv.RecalculateN): field r of the result is the MVTools_vectors of
+    Recalculate on field r of the old blob, byte for byte, at byte r * field_stride.  vectors_ad: of field 0 of the old blob (AnalyseN.ad(0));
+    keyword names are Recalculate's."""
+    _destroy = "mvx_recalculate_n_destroy"
+
+    def __init__(self, sup, vectors_ad, radius, **kw):
+        self.sup = sup
+        a = RecalculateArgs(*([UNSET] * len(RECALC_ARGS)))
+        for k, v in kw.items():
+            k2 = {"lambda": "lambda_"}.get(k, k)
+            if k2 not in RECALC_ARGS:
+                raise TypeError("RecalculateN: unknown argument " + k)
+            if v is not None:
+                setattr(a, k2, int(v))
+        old = AnalysisData.from_buffer_copy(bytes(vectors_ad))
+        self.h = C.c_void_p()
+        err = C.create_string_buffer(ERRLEN)
+        _check(lib().mvx_recalculate_n_create(C.byref(a), int(radius), sup.h, C.byref(old), _pad3(sup.pitch), C.byref(self.h), err), err)
+        self.radius = int(radius)
+        self.field_size = lib().mvx_recalculate_n_field_size(self.h)
+        self.field_stride = lib().mvx_recalculate_n_field_stride(self.h)
+        self.blob_size = lib().mvx_recalculate_n_blob_size(self.h)
+
+    def get_data(self, r):
+        """the MVTools_MVAnalysisData of field r of the result"""
+        out = AnalysisData()
+        _check(lib().mvx_recalculate_n_get_data(self.h, int(r), C.byref(out)))
+        return out
+
+    def alloc_blobs(self, n, device="cuda"):
+        torch = _torch()
+        buf = torch.zeros((n, self.blob_size), dtype=torch.uint8, device=device)
+        return [buf[i] for i in range(n)]
+
+    def fields(self, multi_blob):
+        """the 2 * radius fields of a multi blob as tensor views: each is a blob any consumer takes"""
+        return [multi_blob[r * self.field_stride:r * self.field_stride + self.field_size] for r in range(2 * self.radius)]
+
+    def run(self, jobs, blobs=None, old_field_stride=None):
+        """jobs: list of (src_super_frame, [ref_super_frame or None] * 2r in the order of multi_refs, old_multi_blob) -> list of multi blobs
+        on the device.  old_field_stride defaults to the old blob's bytes / 2r (a blob of AnalyseN.alloc_blobs)."""
+        n, nr = len(jobs), 2 * self.radius
+        if blobs is None:
+            blobs = self.alloc_blobs(n, device=jobs[0][0][0].device)
+        arr = (RecalculateNJob * n)()
+        table = _ref_table([refs for _, refs, _ in jobs], nr, self.sup.nplanes, "RecalculateN")
+        for i, (s, refs, ob) in enumerate(jobs):
+            for p in range(self.sup.nplanes):
+                assert s[p].stride(0) == self.sup.pitch[p]
+                arr[i].src[p] = s[p].data_ptr()
+            arr[i].refs = C.cast(C.byref(table, i * nr * C.sizeof(C.c_void_p * 3)), C.POINTER(C.c_void_p * 3))
+            if ob is None:
+                raise ValueError("RecalculateN: a job needs its old multi blob")
+            arr[i].old_blob = ob.data_ptr()
+            arr[i].old_field_stride = int(old_field_stride) if old_field_stride is not None else ob.numel() // nr
+            if blobs[i].numel() < self.blob_size:
+                raise ValueError("RecalculateN: a multi blob holds %d bytes" % self.blob_size)
+            arr[i].blob = blobs[i].data_ptr()
+        _check(lib().mvx_recalculate_n_frames(self.h, n, arr, _stream()))
         return blobs
 
 

@@ -24,6 +24,14 @@
  *                 x.data=analyse|estimate (default estimate): where the data clip of depancompensate / depanstabilise comes from.  With estimate no mv.Super
  *                 and no mv.Analyse is built.  Per frame the run prints the data clip's Depan_dx / _dy / _zoom / _rot as C hex floats and every Depan*_info
  *                 string of the output frame; out.raw gets the output frames
+ *       pipeline: multianalyse | multirecalculate | multifield | multidegrain | multicompensate (the plugin registers their filters with MVX_VS_MULTI=1).  Argument prefixes:
+ *                 m.* for AnalyseN (m.radius is required), r.* for RecalculateN (multirecalculate always; the others put it between AnalyseN and the final filter when
+ *                 any r.* argument is given), f.* for the final filter (MultiField, DegrainN, CompensateN).  multianalyse / multirecalculate write, per frame and field, the
+ *                 field's 84-byte MVTools_MVAnalysisData (derived from field 0's) and the field's blob, and print "multi radius=R stride=S"; with x.dump=prop they write
+ *                 the frame's whole MVTools_multi_vectors property instead.  multifield writes what `analyse` writes for one clip.  multicompensate prints its frame
+ *                 count, rate and the _Duration* of frame 1; x.order=reverse asks for the output frames last to first before they are written
+ *   `error` takes AnalyseN (f.*), and RecalculateN | DegrainN | CompensateN | MultiField (f.*) on AnalyseN(m.*); x.vectors=single hands them mv.Analyse's backward clip
+ *       instead, and x.vectors=multi hands the AnalyseN clip to any of the single-field filters below
  *   `error` takes DepanAnalyse (on the backward vectors) and DepanEstimate | DepanCompensate | DepanStabilise (data clip: DepanEstimate(clip) with e.*; no mv.Super)
  *   a stub of com.vapoursynth.text / FrameProps returns its clip unchanged and prints "text.FrameProps props=<name>"; x.notext=1 hides the plugin
  */
@@ -83,6 +91,17 @@ static const Item *get(const VSMap *m, const char *key, int index, int type, int
 }
 static void VS_CC mapSetError(VSMap *m, const char *msg) { clearMap(m); m->error = strdup(msg ? msg : "Error: no error specified"); }
 static const char *VS_CC mapGetError(const VSMap *m) { return m->error; }
+static int VS_CC mapDeleteKey(VSMap *m, const char *key) {
+    for (Entry **pe = &m->head; *pe; pe = &(*pe)->next)
+        if (!strcmp((*pe)->key, key)) {
+            Entry *e = *pe;
+            *pe = e->next;
+            for (int i = 0; i < e->n; i++) { free(e->v[i].data); if (e->v[i].node) node_free(e->v[i].node); }
+            free(e->v); free(e->key); free(e);
+            return 1;
+        }
+    return 0;
+}
 static int VS_CC mapNumElements(const VSMap *m, const char *key) { Entry *e = find(m, key); return e ? e->n : -1; }
 static int64_t VS_CC mapGetInt(const VSMap *m, const char *k, int i, int *err) { const Item *it = get(m, k, i, ptInt, err); return it ? it->i : 0; }
 static int VS_CC mapGetIntSaturated(const VSMap *m, const char *k, int i, int *err) {
@@ -420,7 +439,7 @@ static void init_api(void) {
     g_api.getFrameWidth = getFrameWidth; g_api.getFrameHeight = getFrameHeight;
     g_api.getFrame = getFrame; g_api.getFrameFilter = getFrameFilter; g_api.requestFrameFilter = requestFrameFilter; g_api.setFilterError = setFilterError;
     g_api.createMap = createMap; g_api.freeMap = freeMap; g_api.clearMap = clearMap; g_api.mapSetError = mapSetError; g_api.mapGetError = mapGetError;
-    g_api.mapNumElements = mapNumElements; g_api.mapGetInt = mapGetInt; g_api.mapGetIntSaturated = mapGetIntSaturated; g_api.mapSetInt = mapSetInt;
+    g_api.mapNumElements = mapNumElements; g_api.mapDeleteKey = mapDeleteKey; g_api.mapGetInt = mapGetInt; g_api.mapGetIntSaturated = mapGetIntSaturated; g_api.mapSetInt = mapSetInt;
     g_api.mapGetFloat = mapGetFloat; g_api.mapSetFloat = mapSetFloat; g_api.mapGetData = mapGetData; g_api.mapGetDataSize = mapGetDataSize; g_api.mapSetData = mapSetData;
     g_api.mapGetNode = mapGetNode; g_api.mapSetNode = mapSetNode; g_api.logMessage = logMessage;
     g_api.getPluginByID = getPluginByID; g_api.invoke = apiInvoke;
@@ -542,6 +561,46 @@ static void prefetch_parallel(int threads, int count, VSNode **nodes, int nnodes
     if (w.err[0]) die("parallel request", w.err);
 }
 
+/* the temporal-radius filters: AnalyseN(super, m.*), and RecalculateN(super, vectors, r.*) behind it when asked for */
+static VSNode *multi_clip(VSNode *sup, int withRecalc, int argc, char **argv, char *err, size_t errsz) {
+    VSMap *am = createMap(); mapSetNode(am, "super", sup, maReplace); add_args(am, 'm', argc, argv);
+    VSNode *v = invoke("AnalyseN", am, err, errsz);
+    if (!v) die("AnalyseN", err);
+    if (withRecalc) {
+        VSMap *rm = createMap(); mapSetNode(rm, "super", sup, maReplace); mapSetNode(rm, "vectors", v, maReplace); add_args(rm, 'r', argc, argv);
+        v = invoke("RecalculateN", rm, err, errsz);
+        if (!v) die("RecalculateN", err);
+    }
+    return v;
+}
+static int has_prefix_arg(int argc, char **argv, char prefix) { for (int i = 0; i < argc; i++) if (argv[i][0] == prefix && argv[i][1] == '.') return 1; return 0; }
+static void dump_vector_props(FILE *fo, const VSFrame *f) {
+    int e;
+    fwrite(mapGetData(f->props, "MVTools_MVAnalysisData", 0, &e), 1, (size_t)mapGetDataSize(f->props, "MVTools_MVAnalysisData", 0, &e), fo);
+    fwrite(mapGetData(f->props, "MVTools_vectors", 0, &e), 1, (size_t)mapGetDataSize(f->props, "MVTools_vectors", 0, &e), fo);
+}
+/* a frame of a multi vector clip: per field the 84 bytes derived from field 0's (int 6 nDeltaFrame, 7 isBackward, 9 nMotionFlags with MOTION_IS_BACKWARD = 2) and the blob */
+static void dump_multi_props(FILE *fo, const VSFrame *f, int whole) {
+    int e[4];
+    const char *ad = mapGetData(f->props, "MVTools_multi_MVAnalysisData", 0, &e[0]);
+    const int radius = (int)mapGetInt(f->props, "MVTools_multi_radius", 0, &e[1]);
+    const long long stride = (long long)mapGetInt(f->props, "MVTools_multi_stride", 0, &e[2]);
+    const char *blob = mapGetData(f->props, "MVTools_multi_vectors", 0, &e[3]);
+    if (e[0] || e[1] || e[2] || e[3] || mapGetDataSize(f->props, "MVTools_multi_MVAnalysisData", 0, NULL) != 84) die("multi frame", "MVTools_multi_* properties missing");
+    const int size = mapGetDataSize(f->props, "MVTools_multi_vectors", 0, NULL);
+    if ((long long)size != 2LL * radius * stride) die("multi frame", "MVTools_multi_vectors has the wrong size");
+    if (whole) { fwrite(blob, 1, (size_t)size, fo); return; }
+    for (int r = 0; r < 2 * radius; r++) {
+        int32_t d[21], fsize = 0;
+        memcpy(d, ad, 84);
+        d[7] = r % 2 == 0; d[6] = r / 2 + 1; d[9] = (d[9] & ~2) | (d[7] ? 2 : 0);
+        memcpy(&fsize, blob + (size_t)r * (size_t)stride, 4);
+        if (fsize < 8 || fsize > stride) die("multi frame", "a field states an impossible size");
+        fwrite(d, 1, 84, fo);
+        fwrite(blob + (size_t)r * (size_t)stride, 1, (size_t)fsize, fo);
+    }
+}
+
 static double now_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
 static double g_start;
 
@@ -596,6 +655,14 @@ static int host_main(int argc, char **argv) {
             VSNode *sup = invoke("Super", sm, err, sizeof(err));
             if (!sup) die("Super", err);
             if (!strcmp(filter, "Analyse")) { mapSetNode(m, "super", sup, maReplace); add_args(m, 'f', argc - 7, argv + 7); out = invoke("Analyse", m, err, sizeof(err)); }
+            else if (!strcmp(filter, "AnalyseN")) { mapSetNode(m, "super", sup, maReplace); add_args(m, 'f', argc - 7, argv + 7); out = invoke("AnalyseN", m, err, sizeof(err)); }
+            else if ((!strcmp(filter, "RecalculateN") || !strcmp(filter, "DegrainN") || !strcmp(filter, "CompensateN") || !strcmp(filter, "MultiField")) && !has_arg(argc - 7, argv + 7, "x.vectors=single")) {
+                mapSetNode(m, "vectors", multi_clip(sup, 0, argc - 7, argv + 7, err, sizeof(err)), maReplace);
+                if (strcmp(filter, "MultiField")) mapSetNode(m, "super", sup, maReplace);
+                if (!strcmp(filter, "DegrainN") || !strcmp(filter, "CompensateN")) mapSetNode(m, "clip", fclip, maReplace);
+                add_args(m, 'f', argc - 7, argv + 7);
+                out = invoke(filter, m, err, sizeof(err));
+            }
             else if (!strcmp(filter, "AnalyseOnClip")) { mapSetNode(m, "super", clip, maReplace); out = invoke("Analyse", m, err, sizeof(err)); }
             else { /* DegrainN / Compensate with deliberately swapped or plain vector clips: a.* args go to both analyses */
                 VSMap *a1 = createMap(), *a2 = createMap();
@@ -604,10 +671,12 @@ static int host_main(int argc, char **argv) {
                 mapSetInt(a1, "isb", 1, maReplace); mapSetInt(a2, "isb", 0, maReplace);
                 VSNode *bw = invoke("Analyse", a1, err, sizeof(err)); if (!bw) die("Analyse", err);
                 VSNode *fw = invoke("Analyse", a2, err, sizeof(err)); if (!fw) die("Analyse", err);
-                mapSetNode(m, "clip", fclip, maReplace);
-                if (strcmp(filter, "Mask") && strcmp(filter, "DepanAnalyse")) mapSetNode(m, "super", sup, maReplace); /* (mv.Mask and mv.DepanAnalyse take no super clip) */
+                if (has_arg(argc - 7, argv + 7, "x.vectors=multi")) bw = fw = multi_clip(sup, 0, argc - 7, argv + 7, err, sizeof(err)); /* a multi vector clip where a single-field one belongs */
+                if (strcmp(filter, "RecalculateN") && strcmp(filter, "MultiField")) mapSetNode(m, "clip", fclip, maReplace);
+                if (strcmp(filter, "Mask") && strcmp(filter, "DepanAnalyse") && strcmp(filter, "MultiField")) mapSetNode(m, "super", sup, maReplace); /* (mv.Mask and mv.DepanAnalyse take no super clip) */
                 add_args(m, 'f', argc - 7, argv + 7);
-                if (!strcmp(filter, "Compensate") || !strcmp(filter, "Flow") || !strcmp(filter, "Mask") || !strcmp(filter, "DepanAnalyse")) { mapSetNode(m, "vectors", bw, maReplace); out = invoke(filter, m, err, sizeof(err)); }
+                if (!strcmp(filter, "RecalculateN") || !strcmp(filter, "DegrainN") || !strcmp(filter, "CompensateN") || !strcmp(filter, "MultiField") ||
+                    !strcmp(filter, "Compensate") || !strcmp(filter, "Flow") || !strcmp(filter, "Mask") || !strcmp(filter, "DepanAnalyse")) { mapSetNode(m, "vectors", bw, maReplace); out = invoke(filter, m, err, sizeof(err)); }
                 else if (!strcmp(filter, "Degrain1Swapped")) { mapSetNode(m, "mvbw", fw, maReplace); mapSetNode(m, "mvfw", bw, maReplace); out = invoke("Degrain1", m, err, sizeof(err)); }
                 else { mapSetNode(m, "mvbw", bw, maReplace); mapSetNode(m, "mvfw", fw, maReplace); out = invoke(filter, m, err, sizeof(err)); }
             }
@@ -710,6 +779,8 @@ static int host_main(int argc, char **argv) {
     int R = 1, delta0 = 1;
     for (int i = 0; i < nextra; i++) if (!strncmp(extra[i], "x.delta=", 8)) delta0 = atoi(extra[i] + 8);
     if (!strncmp(pipeline, "degrain", 7)) R = atoi(pipeline + 7);
+    const int isMulti = !strncmp(pipeline, "multi", 5);
+    if (isMulti) R = 0; /* (their vectors come from AnalyseN: no mv.Analyse node) */
     VSNode *vec[12];
     VSMap *amaps[12] = { NULL };
     for (int r = 0; r < R; r++)
@@ -798,7 +869,39 @@ static int host_main(int argc, char **argv) {
     const char *flowFilter = NULL;
     int flowPair = 0;
     for (int i = 0; i < 5; i++) if (!strcmp(pipeline, flowFilters[i].pipeline)) { flowFilter = flowFilters[i].filter; flowPair = flowFilters[i].pair; }
-    if (!strcmp(pipeline, "compensate")) { mapSetNode(m, "vectors", vec[0], maReplace); add_args(m, 'c', nextra, extra); out = invoke("Compensate", m, err, sizeof(err)); }
+    if (isMulti) {
+        const int final = !strcmp(pipeline, "multianalyse") ? 0 : !strcmp(pipeline, "multirecalculate") ? 1 : !strcmp(pipeline, "multifield") ? 2 : !strcmp(pipeline, "multidegrain") ? 3 :
+                          !strcmp(pipeline, "multicompensate") ? 4 : -1;
+        if (final < 0) { fprintf(stderr, "bad pipeline\n"); return 2; }
+        VSNode *mv = multi_clip(sup, final == 1 || has_prefix_arg(nextra, extra, 'r'), nextra, extra, err, sizeof(err));
+        if (final <= 2) { /* the vector pipelines */
+            if (final == 2) {
+                VSMap *fm = createMap(); mapSetNode(fm, "vectors", mv, maReplace); add_args(fm, 'f', nextra, extra);
+                mv = invoke("MultiField", fm, err, sizeof(err));
+                if (!mv) die(pipeline, err);
+            }
+            prefetch_parallel(threads, nframes, &mv, 1);
+            for (int n = 0; n < nframes; n++) {
+                const VSFrame *f = eval_frame(n, mv, err, sizeof(err));
+                if (!f) die("output frame", err);
+                if (final == 2) dump_vector_props(fo, f);
+                else {
+                    int e;
+                    if (n == 0) printf("multi radius=%lld stride=%lld\n", (long long)mapGetInt(f->props, "MVTools_multi_radius", 0, &e), (long long)mapGetInt(f->props, "MVTools_multi_stride", 0, &e));
+                    dump_multi_props(fo, f, has_arg(nextra, extra, "x.dump=prop"));
+                }
+                freeFrame(f);
+            }
+            fclose(fo); printf("DONE\n"); return 0;
+        }
+        mapSetNode(m, "vectors", mv, maReplace); add_args(m, 'f', nextra, extra);
+        out = invoke(final == 3 ? "DegrainN" : "CompensateN", m, err, sizeof(err));
+        if (out && final == 4) {
+            isFlowFps = 1; outFrames = out->vi.numFrames; /* (the _Duration* line of frame 1, like flowfps) */
+            printf("multicompensate frames=%d fps=%lld/%lld\n", out->vi.numFrames, (long long)out->vi.fpsNum, (long long)out->vi.fpsDen);
+        }
+    }
+    else if (!strcmp(pipeline, "compensate")) { mapSetNode(m, "vectors", vec[0], maReplace); add_args(m, 'c', nextra, extra); out = invoke("Compensate", m, err, sizeof(err)); }
     else if (flowFilter) { /* the per-sample filters (f.*): both vector clips, or one as `vectors` (x.vectors=fw: the forward one) */
         int fwd = 0;
         for (int i = 0; i < nextra; i++) if (!strcmp(extra[i], "x.vectors=fw")) fwd = 1;
@@ -837,6 +940,8 @@ static int host_main(int argc, char **argv) {
         prefetch_parallel(threads, outFrames, &out, 1);
         if (times) { fprintf(stderr, "minihost: output clip %.2f s\n", now_s() - t0); t0 = now_s(); }
     }
+    if (has_arg(nextra, extra, "x.order=reverse")) /* the output frames last to first; they stay in the node's frame table for the loop below */
+        for (int n = outFrames - 1; n >= 0; n--) { const VSFrame *f = eval_frame(n, out, err, sizeof(err)); if (!f) die("output frame", err); freeFrame(f); }
     int failed = 0; /* (with x.free=1 a failed output frame is reported after the teardown: the free callbacks of a graph whose request ended in an error run too) */
     for (int n = 0; n < outFrames; n++) {
         const VSFrame *f = eval_frame(n, out, err, sizeof(err));

@@ -11,6 +11,8 @@
  *     FlowBlur  (src/MVFlowBlur.c:555-565)    Mask    (src/MVMask.c:350-360)
  * and, with MVX_VS_DEPAN=1, the global-motion filters (src/MVDepan.cpp:4211-4288)
  *     DepanAnalyse   DepanEstimate   DepanCompensate   DepanStabilise
+ * and, with MVX_VS_MULTI=1, the temporal-radius filters over the multi vector clip (no reference counterpart; see their section)
+ *     AnalyseN   RecalculateN   DegrainN   CompensateN   MultiField
  * DepanEstimate is ONE node where the reference chains three: its temporary DepanEstimateFFT / FFT2 and DepanEstimateX / Y / Zoom / Trust frame properties do not
  * exist here (the spectra stay on the device, the stage-2 results in a table of the instance); info=1 sets Depan*_info and invokes text.FrameProps as the reference does.
  * The shell keeps the reference's inter-filter data layout: super-frame geometry + Super_* props on frame 0
@@ -478,14 +480,9 @@ static int adata_similar(const mvx_analysis_data *a, const mvx_analysis_data *b,
 }
 
 /* MVTools_vectors of a vector-clip frame -> device.  The array states its own size in its first int (gopGetArraySize,
- * GroupOfPlanes.c:167-174); clips made with divide carry an extra array the level formula does not describe. */
-static int blob_to_device(void **dblob, int *size, const mvx_analysis_data *ad, const VSFrame *vf, const VSAPI *vs) {
-    int e = 0;
-    const VSMap *props = vs->getFramePropertiesRO(vf);
-    const char *blob = vs->mapGetData(props, PROP_VECTORS, 0, &e);
-    *dblob = NULL;
-    if (e) return MVX_E_ARG;
-    const int n = vs->mapGetDataSize(props, PROP_VECTORS, 0, NULL);
+ * GroupOfPlanes.c:167-174); clips made with divide carry an extra array the level formula does not describe.  blob_check is the validation alone (the fields of a
+ * multi vector clip go through it too). */
+static int blob_check(const char *blob, int n, const mvx_analysis_data *ad) {
     int stated = 0;
     if (n >= 8) memcpy(&stated, blob, sizeof(stated));
     if (n < 8 || stated != n) return MVX_E_ARG;
@@ -505,6 +502,16 @@ static int blob_to_device(void **dblob, int *size, const mvx_analysis_data *ad, 
         for (int i = ad->nLvCount - 1; i >= 1 && off < n; i--) { int psz; memcpy(&psz, blob + off, sizeof(psz)); off += psz; }
         if (planes < ad->nLvCount || off > lastOff || n - off < 4 + ad->nBlkX * ad->nBlkY * 16) return MVX_E_ARG;
     }
+    return 0;
+}
+static int blob_to_device(void **dblob, int *size, const mvx_analysis_data *ad, const VSFrame *vf, const VSAPI *vs) {
+    int e = 0;
+    const VSMap *props = vs->getFramePropertiesRO(vf);
+    const char *blob = vs->mapGetData(props, PROP_VECTORS, 0, &e);
+    *dblob = NULL;
+    if (e) return MVX_E_ARG;
+    const int n = vs->mapGetDataSize(props, PROP_VECTORS, 0, NULL);
+    if (blob_check(blob, n, ad)) return MVX_E_ARG;
     *dblob = shell_alloc((size_t)n);
     if (!*dblob) return MVX_E_NOMEM;
     if (timed_upload(*dblob, n, blob, n, (size_t)n, 1)) return MVX_E_DEVICE; /* complete on return: the prop memory goes away with the frame */
@@ -3132,6 +3139,625 @@ static void VS_CC depanStabCreate(const VSMap *in, VSMap *out, void *user, VSCor
     depan_warp_register(d, "DepanStabilise", "DepanStabilise_info", d->ds, out, core, vs);
 }
 
+/* ------------------------------------------------------------------------------------------------ the temporal-radius filters (MVX_VS_MULTI=1)
+ * mv.AnalyseN / mv.RecalculateN / mv.DegrainN / mv.CompensateN / mv.MultiField over the multi blob of include/mvtools_amd.h.  A MULTI VECTOR CLIP is, like mv.Analyse's
+ * vector clip, copyFrame(super[n]) with binary properties -- but its own:
+ *     MVTools_multi_MVAnalysisData  the 84 bytes of field 0 (backward, delta 1)
+ *     MVTools_multi_radius          int
+ *     MVTools_multi_stride          int: bytes from one field to the next (a field's size rounded up to 256)
+ *     MVTools_multi_vectors         2 * radius * stride bytes; field r at r * stride, every pad byte 0
+ * It carries neither MVTools_MVAnalysisData nor MVTools_vectors, so a single-field filter refuses it at creation with its own "Property ... not found" message;
+ * mv.MultiField turns one field into an ordinary vector clip.  The property is uploaded per request (no device-side hand-over between these nodes yet). */
+#define PROP_MULTI_ADATA "MVTools_multi_MVAnalysisData"
+#define PROP_MULTI_RADIUS "MVTools_multi_radius"
+#define PROP_MULTI_STRIDE "MVTools_multi_stride"
+#define PROP_MULTI_VECTORS "MVTools_multi_vectors"
+#define MULTI_MAX_FIELDS (2 * MVX_DEGRAIN_N_MAX_RADIUS)
+
+typedef struct MultiInfo { mvx_analysis_data ad0; int radius; int64_t stride; } MultiInfo;
+
+/* the analysis data of field r, from field 0's: the one place that knows the order of the fields (mvbw1, mvfw1, mvbw2, mvfw2, ...) */
+static void multi_field_data(mvx_analysis_data *out, const mvx_analysis_data *ad0, int r) {
+    *out = *ad0;
+    out->isBackward = r % 2 == 0;
+    out->nDeltaFrame = r / 2 + 1;
+    out->nMotionFlags = (ad0->nMotionFlags & ~2) | (out->isBackward ? 2 : 0); /* MOTION_IS_BACKWARD, src/MVAnalyse.c:489 */
+}
+/* frame n + multi_offset(r) is the reference of field r */
+static int multi_offset(int r) { return r % 2 == 0 ? r / 2 + 1 : -(r / 2 + 1); }
+
+static int multi_from_clip(MultiInfo *mi, VSNode *clip, const char *filter, const char *name, char *error, size_t esz, const VSAPI *vs) {
+    char msg[1024];
+    const VSFrame *f0 = vs->getFrame(0, clip, msg, sizeof(msg));
+    if (!f0) { snprintf(error, esz, "%s: Failed to retrieve first frame from %s. Error message: %s", filter, name, msg); return -1; }
+    const VSMap *props = vs->getFramePropertiesRO(f0);
+    int err = 0, e1 = 0, e2 = 0, rc = 0;
+    const char *data = vs->mapGetData(props, PROP_MULTI_ADATA, 0, &err);
+    if (err) { snprintf(error, esz, "%s: Property '%s' not found in first frame of %s.", filter, PROP_MULTI_ADATA, name); rc = -1; }
+    else {
+        const int size = vs->mapGetDataSize(props, PROP_MULTI_ADATA, 0, NULL);
+        mi->radius = vs->mapGetIntSaturated(props, PROP_MULTI_RADIUS, 0, &e1);
+        mi->stride = vs->mapGetInt(props, PROP_MULTI_STRIDE, 0, &e2);
+        if (size != (int)sizeof(mi->ad0)) { snprintf(error, esz, "%s: Property '%s' in first frame of %s has wrong size (%d instead of %d).", filter, PROP_MULTI_ADATA, name, size, (int)sizeof(mi->ad0)); rc = -1; }
+        else if (e1 || e2 || mi->radius < 1 || mi->radius > MVX_DEGRAIN_N_MAX_RADIUS || mi->stride < 256 || mi->stride % 256 || mi->stride > (1 << 30)) {
+            snprintf(error, esz, "%s: the multi vector clip properties in first frame of %s appear to be wrong.", filter, name); rc = -1;
+        } else memcpy(&mi->ad0, data, sizeof(mi->ad0));
+    }
+    vs->freeFrame(f0);
+    return rc;
+}
+
+/* the first `nfields` fields of MVTools_multi_vectors of a frame, each validated like a MVTools_vectors property (blob_check: its stated size, here also against the
+ * stride, and plane headers that tile it exactly) -> host pointer, or NULL */
+static const char *multi_fields_checked(const MultiInfo *mi, int nfields, const VSFrame *vf, const VSAPI *vs) {
+    int e = 0;
+    const VSMap *props = vs->getFramePropertiesRO(vf);
+    const char *blob = vs->mapGetData(props, PROP_MULTI_VECTORS, 0, &e);
+    if (e) return NULL;
+    const int64_t n = vs->mapGetDataSize(props, PROP_MULTI_VECTORS, 0, NULL);
+    if (n != 2 * (int64_t)mi->radius * mi->stride || nfields > 2 * mi->radius) return NULL;
+    for (int r = 0; r < nfields; r++) {
+        const char *f = blob + (size_t)r * (size_t)mi->stride;
+        int stated = 0;
+        memcpy(&stated, f, sizeof(stated));
+        if (stated < 8 || ((int64_t)stated + 255) / 256 * 256 != mi->stride || blob_check(f, stated, &mi->ad0)) return NULL;
+    }
+    return blob;
+}
+static int multi_to_device(void **dblob, const MultiInfo *mi, int nfields, const VSFrame *vf, const VSAPI *vs) {
+    *dblob = NULL;
+    const char *blob = multi_fields_checked(mi, nfields, vf, vs);
+    if (!blob) return MVX_E_ARG;
+    const size_t n = (size_t)nfields * (size_t)mi->stride;
+    *dblob = shell_alloc(n);
+    if (!*dblob) return MVX_E_NOMEM;
+    return timed_upload(*dblob, (ptrdiff_t)n, blob, (ptrdiff_t)n, n, 1) ? MVX_E_DEVICE : 0; /* complete on return: the prop memory goes away with the frame */
+}
+/* a finished multi blob on the device -> the properties of a frame.  Field by field: the device never writes the pad bytes, the property's are 0 */
+static int multi_set_props(VSFrame *dst, const void *dblob, const MultiInfo *mi, size_t fieldSize, const VSAPI *vs) {
+    const size_t n = 2 * (size_t)mi->radius * (size_t)mi->stride;
+    char *host = (char *)calloc(1, n);
+    if (!host) return MVX_E_NOMEM;
+    int rc = timed_download(host, (ptrdiff_t)mi->stride, dblob, (ptrdiff_t)mi->stride, fieldSize, 2 * (size_t)mi->radius);
+    if (!rc) rc = mvx_stream_sync(thread_stream());
+    if (!rc) {
+        VSMap *props = vs->getFramePropertiesRW(dst);
+        vs->mapSetData(props, PROP_MULTI_ADATA, (const char *)&mi->ad0, sizeof(mi->ad0), dtBinary, maReplace);
+        vs->mapSetInt(props, PROP_MULTI_RADIUS, mi->radius, maReplace);
+        vs->mapSetInt(props, PROP_MULTI_STRIDE, mi->stride, maReplace);
+        vs->mapSetData(props, PROP_MULTI_VECTORS, host, (int)n, dtBinary, maReplace);
+    }
+    free(host);
+    return rc;
+}
+/* the super frames n + multi_offset(r), r < nfields, that lie inside the clip: requested (arInitial) ... */
+static void multi_request_refs(int n, int nfields, int numFrames, VSNode *super, VSFrameContext *ctx, const VSAPI *vs) {
+    for (int r = 0; r < nfields; r++) {
+        const int m = n + multi_offset(r);
+        if (m >= 0 && m < numFrames) vs->requestFrameFilter(m, super, ctx);
+    }
+}
+/* ... and brought to the device as the HOST table the *_n jobs take (an entry outside the clip stays NULL) */
+static int multi_refs_to_device(DevRef *refs, const void *table[][3], int n, int nfields, int numFrames, VSNode *super, const SuperGeo *g, VSFrameContext *ctx, const VSAPI *vs) {
+    int rc = 0;
+    for (int r = 0; r < nfields && !rc; r++) {
+        const int m = n + multi_offset(r);
+        if (m < 0 || m >= numFrames) continue;
+        rc = clip_super_to_device(&refs[r], m, super, g, ctx, vs);
+        for (int p = 0; p < 3 && !rc; p++) table[r][p] = refs[r].plane[p];
+    }
+    return rc;
+}
+
+ENGINE_DESTROY(mvx_analyse_n) ENGINE_DESTROY(mvx_recalculate_n) ENGINE_DESTROY(mvx_degrain_n) ENGINE_DESTROY(mvx_compensate_n)
+
+/* ---- mv.AnalyseN(super, radius, ...): one mvx_analyse_n_frames call per frame (no combining queue, no look-ahead windows yet) */
+typedef struct AnalyseNData { Consumer c; VSNode *super; const VSVideoInfo *vi; mvx_analyse_n *an; MultiInfo mi; size_t fieldSize; FieldOpt fo; } AnalyseNData;
+
+static const VSFrame *VS_CC analyseNGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    (void)fd;
+    AnalyseNData *d = (AnalyseNData *)inst;
+    const int nf = 2 * d->mi.radius;
+    if (reason == arInitial) {
+        vs->requestFrameFilter(n, d->super, ctx);
+        multi_request_refs(n, nf, d->vi->numFrames, d->super, ctx, vs);
+        return NULL;
+    }
+    if (reason != arAllFramesReady) return NULL;
+    const VSFrame *src = vs->getFrameFilter(n, d->super, ctx);
+    int32_t shift[MULTI_MAX_FIELDS];
+    memset(shift, 0, sizeof(shift));
+    if (d->fo.fields) { /* src/MVAnalyse.c:135-179, per field */
+        int missing = 0;
+        const int srcTop = frame_top_field(&d->fo, src, n, &missing, vs);
+        for (int r = 0; r < nf; r++) {
+            const int m = n + multi_offset(r);
+            if (m < 0 || m >= d->vi->numFrames) continue;
+            const VSFrame *ref = vs->getFrameFilter(m, d->super, ctx);
+            const int refTop = frame_top_field(&d->fo, ref, m, &missing, vs);
+            vs->freeFrame(ref);
+            if (d->mi.ad0.nPel > 1 && (r / 2 + 1) % 2) shift[r] = field_shift_of(srcTop, refTop, d->mi.ad0.nPel);
+        }
+        if (missing) {
+            vs->setFilterError("AnalyseN: _Field property not found in input frame. Therefore, you must pass tff argument.", ctx);
+            vs->freeFrame(src);
+            return NULL;
+        }
+    }
+    DevRef ds, refs[MULTI_MAX_FIELDS];
+    const void *table[MULTI_MAX_FIELDS][3];
+    memset(refs, 0, sizeof(refs)); memset(table, 0, sizeof(table));
+    int rc = super_to_device(&ds, src, &d->c.geo, vs);
+    if (!rc) rc = multi_refs_to_device(refs, table, n, nf, d->vi->numFrames, d->super, &d->c.geo, ctx, vs);
+    void *dblob = rc ? NULL : shell_alloc(2 * (size_t)d->mi.radius * (size_t)d->mi.stride);
+    if (!rc && !dblob) rc = MVX_E_NOMEM;
+    VSFrame *dst = NULL;
+    if (!rc) {
+        mvx_analyse_n_job job;
+        memset(&job, 0, sizeof(job));
+        for (int p = 0; p < 3; p++) job.src[p] = ds.plane[p];
+        job.refs = table; job.blob = dblob; job.field_shift = shift;
+        rc = mvx_analyse_n_frames(d->an, 1, &job, thread_stream());
+        if (!rc) { dst = vs->copyFrame(src, core); rc = multi_set_props(dst, dblob, &d->mi, d->fieldSize, vs); }
+    }
+    shell_quiesce(rc);
+    dev_release(&ds);
+    for (int r = 0; r < nf; r++) dev_release(&refs[r]);
+    if (dblob) mvx_dev_free(dblob);
+    vs->freeFrame(src);
+    if (rc) {
+        if (dst) vs->freeFrame(dst);
+        consumer_frame_error(d->c.name, rc, 0, ctx, vs);
+        return NULL;
+    }
+    return dst;
+}
+
+static int video_format_ok(const VSVideoInfo *vi) {
+    return mvx_vsh_is_constant_video_format(vi) && vi->format.bitsPerSample <= 16 && vi->format.sampleType == stInteger && vi->format.subSamplingW <= 1 &&
+           vi->format.subSamplingH <= 1 && (vi->format.colorFamily == cfYUV || vi->format.colorFamily == cfGray);
+}
+
+static void VS_CC analyseNCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
+    warm_barrier();
+    (void)user;
+    static const char *keys[] = { "blksize", "blksizev", "levels", "search", "searchparam", "pelsearch", "isb", "lambda", "chroma", "delta", "truemotion",
+                                  "lsad", "plevel", "global", "pnew", "pzero", "pglobal", "overlap", "overlapv", "divide", "badsad", "badrange", "opt",
+                                  "meander", "trymany", "fields", "tff", "search_coarse", "dct" };
+    mvx_analyse_args a;
+    int32_t *av = (int32_t *)&a;
+    for (size_t i = 0; i < sizeof(keys) / sizeof(keys[0]); i++) av[i] = opt_int(in, keys[i], vs); /* (isb and delta are not in the argument string: unset) */
+    AnalyseNData *d = (AnalyseNData *)consumer_new(sizeof(*d), "AnalyseN", analyseNGetFrameUngated, mvx_analyse_n_destroy_engine);
+    char err[1400] = "";
+    field_opt(&d->fo, in, vs);
+    {
+        VSNode *node = vs->mapGetNode(in, "super", 0, NULL);
+        const int ok = video_format_ok(vs->getVideoInfo(node));
+        vs->freeNode(node);
+        if (!ok) snprintf(err, sizeof(err), "AnalyseN: super clip must be GRAY, 420, 422, 440, or 444, up to 16 bits, with constant dimensions.");
+    }
+    if (!err[0]) d->super = consumer_super(&d->c, in, err, sizeof(err), vs);
+    if (!err[0]) {
+        d->vi = vs->getVideoInfo(d->super);
+        char lerr[MVX_ERRLEN];
+        if (mvx_analyse_n_create(&a, (int)vs->mapGetIntSaturated(in, "radius", 0, NULL), d->c.sup, d->vi->numFrames, d->c.geo.pitch, &d->an, lerr)) snprintf(err, sizeof(err), "%s", lerr);
+        d->c.engine = d->an;
+    }
+    if (err[0]) { consumer_fail(&d->c, err, out, vs); return; }
+    d->mi.radius = (int)vs->mapGetIntSaturated(in, "radius", 0, NULL);
+    d->mi.stride = (int64_t)mvx_analyse_n_field_stride(d->an);
+    d->fieldSize = mvx_analyse_n_field_size(d->an);
+    mvx_analyse_n_get_data(d->an, 0, &d->mi.ad0);
+    if (d->c.geo.copies > 1) mvx_analyse_n_set_ref_shadow(d->an, d->c.geo.shadowStride); /* every device super frame of this shell carries its copies */
+    pthread_mutex_lock(&g_lock); g_stat_instances++; pthread_mutex_unlock(&g_lock); /* (MVX_VS_STATS=1 reports the shell's thread-seconds for graphs with a searching instance) */
+    VSFilterDependency deps[1] = { { d->super, rpGeneral } };
+    vs->createVideoFilter(out, "AnalyseN", d->vi, consumerGetFrame, consumerFree, fmParallel, deps, 1, d, core);
+}
+
+/* ---- mv.RecalculateN(super, vectors, ...): the radius is the clip's; one mvx_recalculate_n_frames call per frame */
+typedef struct RecalcNData { Consumer c; VSNode *super, *vectors; const VSVideoInfo *vi; mvx_recalculate_n *rn; MultiInfo old, mi; size_t fieldSize; FieldOpt fo; } RecalcNData;
+
+static const VSFrame *VS_CC recalcNGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    (void)fd;
+    RecalcNData *d = (RecalcNData *)inst;
+    const int nf = 2 * d->mi.radius;
+    if (reason == arInitial) {
+        vs->requestFrameFilter(n, d->vectors, ctx);
+        vs->requestFrameFilter(n, d->super, ctx);
+        multi_request_refs(n, nf, d->vi->numFrames, d->super, ctx, vs);
+        return NULL;
+    }
+    if (reason != arAllFramesReady) return NULL;
+    const VSFrame *src = vs->getFrameFilter(n, d->super, ctx);
+    if (d->fo.fields) { /* src/MVRecalculate.c:121-163: only the error survives, the shift itself never reaches a result */
+        int missing = 0;
+        frame_top_field(&d->fo, src, n, &missing, vs);
+        for (int r = 0; r < nf; r++) {
+            const int m = n + multi_offset(r);
+            if (m < 0 || m >= d->vi->numFrames) continue;
+            const VSFrame *ref = vs->getFrameFilter(m, d->super, ctx);
+            frame_top_field(&d->fo, ref, m, &missing, vs);
+            vs->freeFrame(ref);
+        }
+        if (missing) {
+            vs->setFilterError("RecalculateN: _Field property not found in input frame. Therefore, you must pass tff argument.", ctx);
+            vs->freeFrame(src);
+            return NULL;
+        }
+    }
+    const VSFrame *mvn = vs->getFrameFilter(n, d->vectors, ctx);
+    void *oldBlob = NULL;
+    int rc = multi_to_device(&oldBlob, &d->old, nf, mvn, vs);
+    vs->freeFrame(mvn);
+    DevRef ds, refs[MULTI_MAX_FIELDS];
+    const void *table[MULTI_MAX_FIELDS][3];
+    memset(&ds, 0, sizeof(ds)); memset(refs, 0, sizeof(refs)); memset(table, 0, sizeof(table));
+    if (!rc) rc = super_to_device(&ds, src, &d->c.geo, vs);
+    if (!rc) rc = multi_refs_to_device(refs, table, n, nf, d->vi->numFrames, d->super, &d->c.geo, ctx, vs);
+    void *dblob = rc ? NULL : mvx_dev_alloc(2 * (size_t)d->mi.radius * (size_t)d->mi.stride);
+    if (!rc && !dblob) rc = MVX_E_NOMEM;
+    VSFrame *dst = NULL;
+    if (!rc) {
+        mvx_recalculate_n_job job;
+        memset(&job, 0, sizeof(job));
+        for (int p = 0; p < 3; p++) job.src[p] = ds.plane[p];
+        job.refs = table; job.old_blob = oldBlob; job.old_field_stride = (size_t)d->old.stride; job.blob = dblob;
+        rc = mvx_recalculate_n_frames(d->rn, 1, &job, thread_stream());
+        if (!rc) { dst = vs->copyFrame(src, core); rc = multi_set_props(dst, dblob, &d->mi, d->fieldSize, vs); }
+    }
+    shell_quiesce(rc);
+    dev_release(&ds);
+    for (int r = 0; r < nf; r++) dev_release(&refs[r]);
+    if (dblob) mvx_dev_free(dblob);
+    if (oldBlob) mvx_dev_free(oldBlob);
+    vs->freeFrame(src);
+    if (rc) {
+        if (dst) vs->freeFrame(dst);
+        consumer_frame_error(d->c.name, rc, 0, ctx, vs);
+        return NULL;
+    }
+    return dst;
+}
+
+static void VS_CC recalcNCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
+    warm_barrier();
+    (void)user;
+    static const char *keys[] = { "thsad", "smooth", "blksize", "blksizev", "search", "searchparam", "lambda", "chroma", "truemotion", "pnew", "overlap", "overlapv",
+                                  "divide", "meander", "fields", "dct" };
+    mvx_recalculate_args a;
+    int64_t *av = (int64_t *)&a;
+    for (size_t i = 0; i < sizeof(keys) / sizeof(keys[0]); i++) av[i] = opt_int64(in, keys[i], vs);
+    RecalcNData *d = (RecalcNData *)consumer_new(sizeof(*d), "RecalculateN", recalcNGetFrameUngated, mvx_recalculate_n_destroy_engine);
+    char err[1400] = "";
+    field_opt(&d->fo, in, vs);
+    d->super = consumer_super(&d->c, in, err, sizeof(err), vs);
+    if (!err[0]) { d->vectors = consumer_node(&d->c, in, "vectors", vs); multi_from_clip(&d->old, d->vectors, "RecalculateN", "vectors", err, sizeof(err), vs); }
+    if (!err[0]) {
+        d->vi = vs->getVideoInfo(d->super);
+        char lerr[MVX_ERRLEN];
+        if (mvx_recalculate_n_create(&a, d->old.radius, d->c.sup, &d->old.ad0, d->c.geo.pitch, &d->rn, lerr)) snprintf(err, sizeof(err), "%s", lerr);
+        d->c.engine = d->rn;
+    }
+    if (err[0]) { consumer_fail(&d->c, err, out, vs); return; }
+    d->mi.radius = d->old.radius;
+    d->mi.stride = (int64_t)mvx_recalculate_n_field_stride(d->rn);
+    d->fieldSize = mvx_recalculate_n_field_size(d->rn);
+    mvx_recalculate_n_get_data(d->rn, 0, &d->mi.ad0);
+    VSFilterDependency deps[2] = { { d->super, rpGeneral }, { d->vectors, rpStrictSpatial } };
+    vs->createVideoFilter(out, "RecalculateN", d->vi, consumerGetFrame, consumerFree, fmParallel, deps, 2, d, core);
+}
+
+/* ---- mv.MultiField(vectors, field): one field as an ordinary vector clip (a host copy) */
+typedef struct MultiFieldData { Consumer c; VSNode *vectors; MultiInfo mi; mvx_analysis_data ad; int field; } MultiFieldData;
+
+static const VSFrame *VS_CC multiFieldGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    (void)fd;
+    MultiFieldData *d = (MultiFieldData *)inst;
+    if (reason == arInitial) { vs->requestFrameFilter(n, d->vectors, ctx); return NULL; }
+    if (reason != arAllFramesReady) return NULL;
+    const VSFrame *src = vs->getFrameFilter(n, d->vectors, ctx);
+    const char *blob = multi_fields_checked(&d->mi, d->field + 1, src, vs);
+    VSFrame *dst = NULL;
+    if (blob) {
+        const char *f = blob + (size_t)d->field * (size_t)d->mi.stride;
+        int size = 0;
+        memcpy(&size, f, sizeof(size));
+        dst = vs->copyFrame(src, core);
+        VSMap *props = vs->getFramePropertiesRW(dst);
+        vs->mapSetData(props, PROP_ADATA, (const char *)&d->ad, sizeof(d->ad), dtBinary, maReplace);
+        vs->mapSetData(props, PROP_VECTORS, f, size, dtBinary, maReplace);
+        vs->mapDeleteKey(props, PROP_MULTI_ADATA); vs->mapDeleteKey(props, PROP_MULTI_RADIUS); vs->mapDeleteKey(props, PROP_MULTI_STRIDE); vs->mapDeleteKey(props, PROP_MULTI_VECTORS);
+    } else consumer_frame_error(d->c.name, MVX_E_ARG, 0, ctx, vs);
+    vs->freeFrame(src);
+    return dst;
+}
+
+static void VS_CC multiFieldCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
+    warm_barrier();
+    (void)user;
+    MultiFieldData *d = (MultiFieldData *)consumer_new(sizeof(*d), "MultiField", multiFieldGetFrameUngated, NULL);
+    char err[1400] = "";
+    d->vectors = consumer_node(&d->c, in, "vectors", vs);
+    multi_from_clip(&d->mi, d->vectors, "MultiField", "vectors", err, sizeof(err), vs);
+    d->field = (int)vs->mapGetIntSaturated(in, "field", 0, NULL);
+    if (!err[0] && (d->field < 0 || d->field >= 2 * d->mi.radius)) snprintf(err, sizeof(err), "MultiField: field must be between 0 and %d.", 2 * d->mi.radius - 1);
+    if (err[0]) { consumer_fail(&d->c, err, out, vs); return; }
+    multi_field_data(&d->ad, &d->mi.ad0, d->field);
+    VSFilterDependency deps[1] = { { d->vectors, rpStrictSpatial } };
+    vs->createVideoFilter(out, "MultiField", vs->getVideoInfo(d->vectors), consumerGetFrame, consumerFree, fmParallel, deps, 1, d, core);
+}
+
+/* ---- mv.DegrainN(clip, super, vectors, radius, ..., thsad2, thsadc2, ..., out16) */
+typedef struct DegrainNData { Consumer c; VSNode *node, *super, *vectors; const VSVideoInfo *vi; VSVideoInfo outvi; int radius; mvx_degrain_n *dg; MultiInfo mi; ptrdiff_t pitch[3], dstPitch[3]; } DegrainNData;
+
+static const VSFrame *VS_CC degrainNGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    (void)fd;
+    DegrainNData *d = (DegrainNData *)inst;
+    const int nr = 2 * d->radius;
+    if (reason == arInitial) {
+        vs->requestFrameFilter(n, d->vectors, ctx);
+        multi_request_refs(n, nr, d->vi->numFrames, d->super, ctx, vs);
+        vs->requestFrameFilter(n, d->node, ctx);
+        return NULL;
+    }
+    if (reason != arAllFramesReady) return NULL;
+    const VSFrame *src = vs->getFrameFilter(n, d->node, ctx);
+    const int np = d->vi->format.numPlanes;
+    DevRef refs[MULTI_MAX_FIELDS];
+    const void *table[MULTI_MAX_FIELDS][3], *blobs[MULTI_MAX_FIELDS];
+    memset(refs, 0, sizeof(refs)); memset(table, 0, sizeof(table));
+    void *srcArena = NULL, *dstArena = NULL, *dmulti = NULL, *dsrc[3], *ddst[3];
+    int height[3] = { 0, 0, 0 };
+    for (int p = 0; p < np; p++) height[p] = vs->getFrameHeight(src, p);
+    int rc = upload_plane_set(dsrc, &srcArena, src, d->pitch, np, d->vi->format.bytesPerSample, vs);
+    if (!rc) rc = dst_plane_set(ddst, &dstArena, d->dstPitch, height, np);
+    if (!rc) {
+        const VSFrame *vf = vs->getFrameFilter(n, d->vectors, ctx);
+        rc = multi_to_device(&dmulti, &d->mi, nr, vf, vs);
+        vs->freeFrame(vf);
+    }
+    if (!rc) rc = multi_refs_to_device(refs, table, n, nr, d->vi->numFrames, d->super, &d->c.geo, ctx, vs);
+    if (!rc) {
+        mvx_degrain_n_job job;
+        memset(&job, 0, sizeof(job));
+        for (int p = 0; p < np; p++) { job.src[p] = dsrc[p]; job.dst[p] = ddst[p]; }
+        for (int r = 0; r < nr; r++) blobs[r] = (const char *)dmulti + (size_t)r * (size_t)d->mi.stride;
+        job.refs = table; job.blobs = blobs;
+        rc = mvx_degrain_n_frames(d->dg, 1, &job, thread_stream());
+    }
+    VSFrame *dst = NULL;
+    if (!rc) {
+        dst = vs->newVideoFrame(&d->outvi.format, d->outvi.width, d->outvi.height, src, core);
+        rc = download_plane_set(dst, ddst, d->dstPitch, np, d->outvi.format.bytesPerSample, vs);
+    }
+    shell_quiesce(rc);
+    for (int r = 0; r < nr; r++) dev_release(&refs[r]);
+    if (dmulti) mvx_dev_free(dmulti);
+    if (srcArena) mvx_dev_free(srcArena);
+    if (dstArena) mvx_dev_free(dstArena);
+    vs->freeFrame(src);
+    if (rc) {
+        if (dst) vs->freeFrame(dst);
+        consumer_frame_error(d->c.name, rc, 0, ctx, vs);
+        return NULL;
+    }
+    return dst;
+}
+
+static void VS_CC degrainNCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
+    warm_barrier();
+    (void)user;
+    DegrainNData *d = (DegrainNData *)consumer_new(sizeof(*d), "DegrainN", degrainNGetFrameUngated, mvx_degrain_n_destroy_engine);
+    char err[1400] = "";
+    mvx_degrain_n_args a;
+    a.radius = opt_int(in, "radius", vs);
+    a.thsad = opt_int64(in, "thsad", vs); a.thsadc = opt_int64(in, "thsadc", vs); a.thsad2 = opt_int64(in, "thsad2", vs); a.thsadc2 = opt_int64(in, "thsadc2", vs);
+    a.plane = opt_int(in, "plane", vs); a.limit = opt_int(in, "limit", vs); a.limitc = opt_int(in, "limitc", vs); a.thscd1 = opt_int64(in, "thscd1", vs); a.thscd2 = opt_int(in, "thscd2", vs);
+    const int out16 = opt_int(in, "out16", vs) != MVX_UNSET && opt_int(in, "out16", vs) != 0;
+    d->super = consumer_super(&d->c, in, err, sizeof(err), vs);
+    if (!err[0]) { d->vectors = consumer_node(&d->c, in, "vectors", vs); multi_from_clip(&d->mi, d->vectors, "DegrainN", "vectors", err, sizeof(err), vs); }
+    if (!err[0]) {
+        if (a.radius == MVX_UNSET) a.radius = d->mi.radius;
+        if (a.radius > d->mi.radius) snprintf(err, sizeof(err), "DegrainN: radius is greater than the radius of the vector clip.");
+    }
+    if (!err[0]) {
+        d->node = consumer_node(&d->c, in, "clip", vs);
+        d->vi = vs->getVideoInfo(d->node);
+        consumer_check_clip(&d->c, d->vi, vs->getVideoInfo(d->super), 0, err, sizeof(err));
+    }
+    if (!err[0]) {
+        d->outvi = *d->vi;
+        if (out16 && !vs->queryVideoFormat(&d->outvi.format, d->vi->format.colorFamily, stInteger, 16, d->vi->format.subSamplingW, d->vi->format.subSamplingH, core))
+            snprintf(err, sizeof(err), "DegrainN: the host has no 16 bit format for out16.");
+    }
+    if (!err[0]) {
+        clip_pitches(d->pitch, d->vi, d->vi->format.bytesPerSample);
+        clip_pitches(d->dstPitch, &d->outvi, d->outvi.format.bytesPerSample);
+        char lerr[MVX_ERRLEN];
+        if ((out16 ? mvx_degrain_n_create_out16 : mvx_degrain_n_create)(&a, &d->mi.ad0, d->c.sup, d->pitch, d->c.geo.pitch, d->dstPitch, &d->dg, lerr)) snprintf(err, sizeof(err), "%s", lerr);
+        d->c.engine = d->dg;
+    }
+    if (err[0]) { consumer_fail(&d->c, err, out, vs); return; }
+    d->radius = a.radius;
+    VSFilterDependency deps[3] = { { d->node, rpStrictSpatial }, { d->super, rpGeneral }, { d->vectors, rpStrictSpatial } };
+    vs->createVideoFilter(out, "DegrainN", &d->outvi, consumerGetFrame, consumerFree, fmParallel, deps, 3, d, core);
+}
+
+/* ---- mv.CompensateN(clip, super, vectors, tr, ...): 2 * tr + 1 output frames per source frame, in temporal order (mvx_compensate_n_map)
+ * The first request for any output of source frame n runs ONE mvx_compensate_n_frames job and keeps all 2 * tr + 1 plane sets on the device in a table of the
+ * instance; requests for other outputs of the same n wait for it and download their own plane set.  The table is bounded (MVX_VS_MULTI_SETS, default 8 sets),
+ * its bytes count against the device cache's budget, and the least recently used idle set makes room; an evicted set is computed again.  What a frame holds never
+ * depends on which request computed its set. */
+enum { CS_EMPTY, CS_BUILDING, CS_READY };
+typedef struct CompSet { int n, state, users; uint64_t stamp; void *arena; } CompSet;
+#define COMP_SETS_MAX 64
+typedef struct CompNData {
+    Consumer c; VSNode *node, *super, *vectors; const VSVideoInfo *clipvi; VSVideoInfo vi; mvx_compensate_n *cn; MultiInfo mi; int tr, no;
+    ptrdiff_t pitch[3]; int height[3]; size_t planeOff[3], frameBytes;
+    pthread_mutex_t mu; pthread_cond_t cv; CompSet sets[COMP_SETS_MAX]; int nsets; uint64_t stamp;
+} CompNData;
+
+static void comp_sets_account(size_t bytes, int add) { /* the table shares the device budget of the frame cache */
+    pthread_mutex_lock(&g_lock);
+    if (add) g_cache_bytes += bytes; else g_cache_bytes -= bytes;
+    pthread_mutex_unlock(&g_lock);
+}
+/* all outputs of source frame n into `arena` */
+static int comp_n_build(CompNData *d, int n, void *arena, VSFrameContext *ctx, const VSAPI *vs) {
+    const int nf = 2 * d->tr, np = d->clipvi->format.numPlanes;
+    DevRef ds, refs[MULTI_MAX_FIELDS];
+    const void *table[MULTI_MAX_FIELDS][3];
+    void *dst[MULTI_MAX_FIELDS + 1][3];
+    memset(&ds, 0, sizeof(ds)); memset(refs, 0, sizeof(refs)); memset(table, 0, sizeof(table)); memset(dst, 0, sizeof(dst));
+    void *dmulti = NULL;
+    const VSFrame *vf = vs->getFrameFilter(n, d->vectors, ctx);
+    int rc = multi_to_device(&dmulti, &d->mi, nf, vf, vs);
+    vs->freeFrame(vf);
+    if (!rc) rc = clip_super_to_device(&ds, n, d->super, &d->c.geo, ctx, vs);
+    if (!rc) rc = multi_refs_to_device(refs, table, n, nf, d->clipvi->numFrames, d->super, &d->c.geo, ctx, vs);
+    if (!rc) {
+        for (int k = 0; k < d->no; k++) for (int p = 0; p < np; p++) dst[k][p] = (char *)arena + (size_t)k * d->frameBytes + d->planeOff[p];
+        mvx_compensate_n_job job;
+        memset(&job, 0, sizeof(job));
+        for (int p = 0; p < 3; p++) job.src_super[p] = ds.plane[p];
+        job.refs = table; job.blob = dmulti; job.field_stride = (size_t)d->mi.stride; job.dst = dst;
+        rc = mvx_compensate_n_frames(d->cn, 1, &job, thread_stream());
+        if (!rc) rc = mvx_stream_sync(thread_stream()); /* the other requests of this set download on their own streams */
+    }
+    shell_quiesce(rc);
+    dev_release(&ds);
+    for (int r = 0; r < nf; r++) dev_release(&refs[r]);
+    if (dmulti) mvx_dev_free(dmulti);
+    return rc;
+}
+/* the set of source frame n, computed if the table does not hold it: *held is the table's entry (give it back with comp_set_release) or NULL with *own an arena of the
+ * caller's (every entry was in use) */
+static int comp_set_acquire(CompNData *d, int n, CompSet **held, void **own, VSFrameContext *ctx, const VSAPI *vs) {
+    *held = NULL; *own = NULL;
+    CompSet *s = NULL;
+    pthread_mutex_lock(&d->mu);
+    for (;;) {
+        s = NULL;
+        for (int i = 0; i < d->nsets; i++) if (d->sets[i].state != CS_EMPTY && d->sets[i].n == n) s = &d->sets[i];
+        if (!s) break;
+        if (s->state == CS_READY) { s->users++; s->stamp = ++d->stamp; pthread_mutex_unlock(&d->mu); *held = s; return 0; }
+        pthread_cond_wait(&d->cv, &d->mu); /* being built: GPU work only, nothing it waits for needs a host worker thread */
+    }
+    for (int i = 0; i < d->nsets && !s; i++) if (d->sets[i].state == CS_EMPTY) s = &d->sets[i];
+    if (!s) for (int i = 0; i < d->nsets; i++) if (d->sets[i].state == CS_READY && d->sets[i].users == 0 && (!s || d->sets[i].stamp < s->stamp)) s = &d->sets[i];
+    if (s) { s->state = CS_BUILDING; s->n = n; s->users = 1; s->stamp = ++d->stamp; }
+    pthread_mutex_unlock(&d->mu);
+    const size_t bytes = (size_t)d->no * d->frameBytes;
+    void *arena = s ? s->arena : NULL;
+    if (!arena) {
+        arena = shell_alloc(bytes);
+        if (arena && s) { s->arena = arena; comp_sets_account(bytes, 1); }
+    }
+    const int rc = arena ? comp_n_build(d, n, arena, ctx, vs) : MVX_E_NOMEM;
+    if (s) {
+        pthread_mutex_lock(&d->mu);
+        if (rc) { s->state = CS_EMPTY; s->users = 0; } else s->state = CS_READY; /* (a failed set is nobody's: whoever waited for it computes it itself and reports its own error) */
+        pthread_cond_broadcast(&d->cv);
+        pthread_mutex_unlock(&d->mu);
+        if (!rc) *held = s;
+    } else if (rc) { if (arena) mvx_dev_free(arena); }
+    else *own = arena;
+    return rc;
+}
+static void comp_set_release(CompNData *d, CompSet *held, void *own) {
+    if (held) { pthread_mutex_lock(&d->mu); held->users--; pthread_mutex_unlock(&d->mu); }
+    if (own) mvx_dev_free(own);
+}
+
+static const VSFrame *VS_CC compNGetFrameUngated(int m, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    (void)fd;
+    CompNData *d = (CompNData *)inst;
+    const int n = m / d->no, k = m % d->no;
+    if (reason == arInitial) { /* everything the set needs: whichever request of source frame n comes first computes all of its outputs */
+        vs->requestFrameFilter(n, d->vectors, ctx);
+        vs->requestFrameFilter(n, d->super, ctx);
+        multi_request_refs(n, 2 * d->tr, d->clipvi->numFrames, d->super, ctx, vs);
+        vs->requestFrameFilter(n, d->node, ctx);
+        return NULL;
+    }
+    if (reason != arAllFramesReady) return NULL;
+    const int np = d->clipvi->format.numPlanes;
+    CompSet *held = NULL;
+    void *own = NULL;
+    int rc = comp_set_acquire(d, n, &held, &own, ctx, vs);
+    VSFrame *dst = NULL;
+    if (!rc) {
+        const VSFrame *src = vs->getFrameFilter(n, d->node, ctx);
+        dst = vs->newVideoFrame(&d->vi.format, d->vi.width, d->vi.height, src, core);
+        vs->freeFrame(src);
+        void *planes[3] = { NULL, NULL, NULL };
+        for (int p = 0; p < np; p++) planes[p] = (char *)(held ? held->arena : own) + (size_t)k * d->frameBytes + d->planeOff[p];
+        rc = download_plane_set(dst, planes, d->pitch, np, d->vi.format.bytesPerSample, vs);
+        shell_quiesce(rc);
+    }
+    comp_set_release(d, held, own);
+    if (rc) {
+        if (dst) vs->freeFrame(dst);
+        consumer_frame_error(d->c.name, rc, 0, ctx, vs);
+        return NULL;
+    }
+    return dst;
+}
+
+static void VS_CC compNFree(void *inst, VSCore *core, const VSAPI *vs) {
+    CompNData *d = (CompNData *)inst;
+    for (int i = 0; i < d->nsets; i++) if (d->sets[i].arena) { comp_sets_account((size_t)d->no * d->frameBytes, 0); mvx_dev_free(d->sets[i].arena); }
+    pthread_mutex_destroy(&d->mu); pthread_cond_destroy(&d->cv);
+    consumerFree(inst, core, vs);
+}
+
+static void VS_CC compNCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
+    warm_barrier();
+    (void)user;
+    CompNData *d = (CompNData *)consumer_new(sizeof(*d), "CompensateN", compNGetFrameUngated, mvx_compensate_n_destroy_engine);
+    char err[1400] = "";
+    mvx_compensate_args a;
+    a.scbehavior = opt_int(in, "scbehavior", vs); a.thsad = opt_int64(in, "thsad", vs); a.thscd1 = opt_int64(in, "thscd1", vs); a.thscd2 = opt_int(in, "thscd2", vs);
+    a.time = opt_float(in, "time", 100.0, vs);
+    { FieldOpt fo; field_opt(&fo, in, vs); a.fields = fo.fields; } /* (fields = 1 is the library's to refuse; tff has nothing to act on) */
+    int tr = opt_int(in, "tr", vs);
+    d->super = consumer_super(&d->c, in, err, sizeof(err), vs);
+    if (!err[0]) { d->vectors = consumer_node(&d->c, in, "vectors", vs); multi_from_clip(&d->mi, d->vectors, "CompensateN", "vectors", err, sizeof(err), vs); }
+    if (!err[0]) {
+        if (tr == MVX_UNSET) tr = d->mi.radius;
+        if (tr > d->mi.radius) snprintf(err, sizeof(err), "CompensateN: tr is greater than the radius of the vector clip.");
+    }
+    if (!err[0]) {
+        d->node = consumer_node(&d->c, in, "clip", vs);
+        d->clipvi = vs->getVideoInfo(d->node);
+        consumer_check_clip(&d->c, d->clipvi, vs->getVideoInfo(d->super), 1, err, sizeof(err));
+    }
+    if (!err[0]) {
+        clip_pitches(d->pitch, d->clipvi, d->clipvi->format.bytesPerSample);
+        char lerr[MVX_ERRLEN];
+        if (mvx_compensate_n_create(&a, tr, &d->mi.ad0, d->c.sup, d->c.geo.pitch, d->pitch, &d->cn, lerr)) snprintf(err, sizeof(err), "%s", lerr);
+        d->c.engine = d->cn;
+    }
+    if (!err[0] && (int64_t)d->clipvi->numFrames * (2 * tr + 1) > 2147483647LL) snprintf(err, sizeof(err), "CompensateN: the output clip would have too many frames.");
+    if (err[0]) { consumer_fail(&d->c, err, out, vs); return; }
+    d->tr = tr; d->no = 2 * tr + 1;
+    for (int p = 0; p < d->clipvi->format.numPlanes; p++) {
+        d->height[p] = p ? d->clipvi->height >> d->clipvi->format.subSamplingH : d->clipvi->height;
+        d->planeOff[p] = d->frameBytes;
+        d->frameBytes += (size_t)d->pitch[p] * (size_t)d->height[p];
+    }
+    pthread_mutex_init(&d->mu, NULL); pthread_cond_init(&d->cv, NULL);
+    d->nsets = (int)env_long("MVX_VS_MULTI_SETS", 8);
+    if (d->nsets < 1) d->nsets = 1;
+    if (d->nsets > COMP_SETS_MAX) d->nsets = COMP_SETS_MAX;
+    d->vi = *d->clipvi;
+    d->vi.numFrames = d->clipvi->numFrames * d->no;
+    d->vi.fpsNum = d->clipvi->fpsNum * d->no;
+    VSFilterDependency deps[3] = { { d->node, rpGeneral }, { d->super, rpGeneral }, { d->vectors, rpGeneral } };
+    vs->createVideoFilter(out, "CompensateN", &d->vi, consumerGetFrame, compNFree, fmParallel, deps, 3, d, core);
+    if (d->vi.fpsNum > 0 && d->vi.fpsDen > 0) assume_fps(out, "CompensateN", d->vi.fpsNum, d->vi.fpsDen, core, vs);
+}
+
 /* ------------------------------------------------------------------------------------------------ entry point */
 
 #define DEGRAIN_TAIL "thsad:int:opt;thsadc:int:opt;plane:int:opt;limit:int:opt;limitc:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;"
@@ -3208,22 +3834,45 @@ VS_EXTERNAL_API(void) VapourSynthPluginInit2(VSPlugin *plugin, const VSPLUGINAPI
                                  "clip:vnode;", maskCreate, NULL, plugin);
     }
     /* The Depan family is opt-in by a switch of its own, read the same way: MVX_VS_DEPAN=1.  (src/MVDepan.cpp:4211-4288) */
-    if (!env_long("MVX_VS_DEPAN", 0)) return;
-    vspapi->registerFunction("DepanAnalyse",
-                             "clip:vnode;vectors:vnode;mask:vnode:opt;zoom:int:opt;rot:int:opt;pixaspect:float:opt;error:float:opt;info:int:opt;wrong:float:opt;zerow:float:opt;"
-                             "thscd1:int:opt;thscd2:int:opt;fields:int:opt;tff:int:opt;",
-                             "clip:vnode;", depanAnalyseCreate, NULL, plugin);
-    vspapi->registerFunction("DepanEstimate",
-                             "clip:vnode;trust:float:opt;winx:int:opt;winy:int:opt;wleft:int:opt;wtop:int:opt;dxmax:int:opt;dymax:int:opt;zoommax:float:opt;stab:float:opt;"
-                             "pixaspect:float:opt;info:int:opt;show:int:opt;fields:int:opt;tff:int:opt;",
-                             "clip:vnode;", depanEstimateCreate, NULL, plugin);
-    vspapi->registerFunction("DepanCompensate",
-                             "clip:vnode;data:vnode;offset:float:opt;subpixel:int:opt;pixaspect:float:opt;matchfields:int:opt;mirror:int:opt;blur:int:opt;info:int:opt;fields:int:opt;"
-                             "tff:int:opt;",
-                             "clip:vnode;", depanCompCreate, NULL, plugin);
-    vspapi->registerFunction("DepanStabilise",
-                             "clip:vnode;data:vnode;cutoff:float:opt;damping:float:opt;initzoom:float:opt;addzoom:int:opt;prev:int:opt;next:int:opt;mirror:int:opt;blur:int:opt;"
-                             "dxmax:float:opt;dymax:float:opt;zoommax:float:opt;rotmax:float:opt;subpixel:int:opt;pixaspect:float:opt;fitlast:int:opt;tzoom:float:opt;info:int:opt;"
-                             "method:int:opt;fields:int:opt;",
-                             "clip:vnode;", depanStabCreate, NULL, plugin);
+    if (env_long("MVX_VS_DEPAN", 0)) {
+        vspapi->registerFunction("DepanAnalyse",
+                                 "clip:vnode;vectors:vnode;mask:vnode:opt;zoom:int:opt;rot:int:opt;pixaspect:float:opt;error:float:opt;info:int:opt;wrong:float:opt;zerow:float:opt;"
+                                 "thscd1:int:opt;thscd2:int:opt;fields:int:opt;tff:int:opt;",
+                                 "clip:vnode;", depanAnalyseCreate, NULL, plugin);
+        vspapi->registerFunction("DepanEstimate",
+                                 "clip:vnode;trust:float:opt;winx:int:opt;winy:int:opt;wleft:int:opt;wtop:int:opt;dxmax:int:opt;dymax:int:opt;zoommax:float:opt;stab:float:opt;"
+                                 "pixaspect:float:opt;info:int:opt;show:int:opt;fields:int:opt;tff:int:opt;",
+                                 "clip:vnode;", depanEstimateCreate, NULL, plugin);
+        vspapi->registerFunction("DepanCompensate",
+                                 "clip:vnode;data:vnode;offset:float:opt;subpixel:int:opt;pixaspect:float:opt;matchfields:int:opt;mirror:int:opt;blur:int:opt;info:int:opt;fields:int:opt;"
+                                 "tff:int:opt;",
+                                 "clip:vnode;", depanCompCreate, NULL, plugin);
+        vspapi->registerFunction("DepanStabilise",
+                                 "clip:vnode;data:vnode;cutoff:float:opt;damping:float:opt;initzoom:float:opt;addzoom:int:opt;prev:int:opt;next:int:opt;mirror:int:opt;blur:int:opt;"
+                                 "dxmax:float:opt;dymax:float:opt;zoommax:float:opt;rotmax:float:opt;subpixel:int:opt;pixaspect:float:opt;fitlast:int:opt;tzoom:float:opt;info:int:opt;"
+                                 "method:int:opt;fields:int:opt;",
+                                 "clip:vnode;", depanStabCreate, NULL, plugin);
+    }
+    /* The temporal-radius filters over the multi vector clip, by a switch of their own, read the same way: MVX_VS_MULTI=1.   */
+    if (env_long("MVX_VS_MULTI", 0)) {
+        vspapi->registerFunction("AnalyseN",
+                                 "super:vnode;radius:int;blksize:int:opt;blksizev:int:opt;levels:int:opt;search:int:opt;searchparam:int:opt;pelsearch:int:opt;lambda:int:opt;"
+                                 "chroma:int:opt;truemotion:int:opt;lsad:int:opt;plevel:int:opt;global:int:opt;pnew:int:opt;pzero:int:opt;pglobal:int:opt;"
+                                 "overlap:int:opt;overlapv:int:opt;divide:int:opt;badsad:int:opt;badrange:int:opt;opt:int:opt;meander:int:opt;trymany:int:opt;fields:int:opt;"
+                                 "tff:int:opt;search_coarse:int:opt;dct:int:opt;",
+                                 "clip:vnode;", analyseNCreate, NULL, plugin);
+        vspapi->registerFunction("RecalculateN",
+                                 "super:vnode;vectors:vnode;thsad:int:opt;smooth:int:opt;blksize:int:opt;blksizev:int:opt;search:int:opt;searchparam:int:opt;lambda:int:opt;"
+                                 "chroma:int:opt;truemotion:int:opt;pnew:int:opt;overlap:int:opt;overlapv:int:opt;divide:int:opt;opt:int:opt;meander:int:opt;fields:int:opt;"
+                                 "tff:int:opt;dct:int:opt;",
+                                 "clip:vnode;", recalcNCreate, NULL, plugin);
+        vspapi->registerFunction("DegrainN",
+                                 "clip:vnode;super:vnode;vectors:vnode;radius:int:opt;thsad:int:opt;thsadc:int:opt;thsad2:int:opt;thsadc2:int:opt;plane:int:opt;limit:int:opt;limitc:int:opt;"
+                                 "thscd1:int:opt;thscd2:int:opt;out16:int:opt;",
+                                 "clip:vnode;", degrainNCreate, NULL, plugin);
+        vspapi->registerFunction("CompensateN",
+                                 "clip:vnode;super:vnode;vectors:vnode;tr:int:opt;scbehavior:int:opt;thsad:int:opt;fields:int:opt;time:float:opt;thscd1:int:opt;thscd2:int:opt;tff:int:opt;",
+                                 "clip:vnode;", compNCreate, NULL, plugin);
+        vspapi->registerFunction("MultiField", "vectors:vnode;field:int;", "clip:vnode;", multiFieldCreate, NULL, plugin);
+    }
 }

@@ -143,7 +143,8 @@ struct VSAPI {
     mvx_vs_slot copyMap;
     void (VS_CC *mapSetError)(VSMap *map, const char *errorMessage);
     const char *(VS_CC *mapGetError)(const VSMap *map);
-    mvx_vs_slot mapNumKeys, mapGetKey, mapDeleteKey;
+    mvx_vs_slot mapNumKeys, mapGetKey;
+    int (VS_CC *mapDeleteKey)(VSMap *map, const char *key); /* 0 if the key was not in the map */
     int (VS_CC *mapNumElements)(const VSMap *map, const char *key);
     mvx_vs_slot mapGetType, mapSetEmpty;
     int64_t (VS_CC *mapGetInt)(const VSMap *map, const char *key, int index, int *error);

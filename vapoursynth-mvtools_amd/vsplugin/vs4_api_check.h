@@ -30,6 +30,7 @@ MVX_VSAPI_SLOT(getStride, 21);
 MVX_VSAPI_SLOT(getVideoInfo, 10);
 MVX_VSAPI_SLOT(getWritePtr, 23);
 MVX_VSAPI_SLOT(invoke, 96);
+MVX_VSAPI_SLOT(mapDeleteKey, 55);
 MVX_VSAPI_SLOT(mapGetData, 69);
 MVX_VSAPI_SLOT(mapGetDataSize, 70);
 MVX_VSAPI_SLOT(mapGetError, 52);
