@@ -29,7 +29,8 @@
  *                 any r.* argument is given), f.* for the final filter (MultiField, DegrainN, CompensateN).  multianalyse / multirecalculate write, per frame and field, the
  *                 field's 84-byte MVTools_MVAnalysisData (derived from field 0's) and the field's blob, and print "multi radius=R stride=S"; with x.dump=prop they write
  *                 the frame's whole MVTools_multi_vectors property instead.  multifield writes what `analyse` writes for one clip.  multicompensate prints its frame
- *                 count, rate and the _Duration* of frame 1; x.order=reverse asks for the output frames last to first before they are written
+ *                 count, rate and the _Duration* of frame 1; x.order=reverse asks for the output frames last to first before they are written (also in the
+ *                 vector pipelines)
  *   `error` takes AnalyseN (f.*), and RecalculateN | DegrainN | CompensateN | MultiField (f.*) on AnalyseN(m.*); x.vectors=single hands them mv.Analyse's backward clip
  *       instead, and x.vectors=multi hands the AnalyseN clip to any of the single-field filters below
  *   `error` takes DepanAnalyse (on the backward vectors) and DepanEstimate | DepanCompensate | DepanStabilise (data clip: DepanEstimate(clip) with e.*; no mv.Super)
@@ -573,6 +574,12 @@ static VSNode *multi_clip(VSNode *sup, int withRecalc, int argc, char **argv, ch
     }
     return v;
 }
+/* x.order=reverse: the frames of the output are asked for last to first before the loop that writes them first to last (they stay in the node's frame table for it) */
+static void ask_out_of_order(VSNode *node, int count, int argc, char **argv) {
+    char err[2048] = "";
+    if (has_arg(argc, argv, "x.order=reverse"))
+        for (int n = count - 1; n >= 0; n--) { const VSFrame *f = eval_frame(n, node, err, sizeof(err)); if (!f) die("output frame", err); freeFrame(f); }
+}
 static int has_prefix_arg(int argc, char **argv, char prefix) { for (int i = 0; i < argc; i++) if (argv[i][0] == prefix && argv[i][1] == '.') return 1; return 0; }
 static void dump_vector_props(FILE *fo, const VSFrame *f) {
     int e;
@@ -880,7 +887,11 @@ static int host_main(int argc, char **argv) {
                 mv = invoke("MultiField", fm, err, sizeof(err));
                 if (!mv) die(pipeline, err);
             }
+            const double tb = now_s(); /* (MVX_HOST_TIMES: the two marks of the picture pipelines, for tools/multi_shell_bench.py) */
+            if (getenv("MVX_HOST_TIMES")) fprintf(stderr, "minihost: graph built at %.2f s after start\n", tb - g_start);
             prefetch_parallel(threads, nframes, &mv, 1);
+            if (getenv("MVX_HOST_TIMES")) fprintf(stderr, "minihost: output clip (frame order) %.2f s\n", now_s() - tb);
+            ask_out_of_order(mv, nframes, nextra, extra);
             for (int n = 0; n < nframes; n++) {
                 const VSFrame *f = eval_frame(n, mv, err, sizeof(err));
                 if (!f) die("output frame", err);
@@ -940,8 +951,7 @@ static int host_main(int argc, char **argv) {
         prefetch_parallel(threads, outFrames, &out, 1);
         if (times) { fprintf(stderr, "minihost: output clip %.2f s\n", now_s() - t0); t0 = now_s(); }
     }
-    if (has_arg(nextra, extra, "x.order=reverse")) /* the output frames last to first; they stay in the node's frame table for the loop below */
-        for (int n = outFrames - 1; n >= 0; n--) { const VSFrame *f = eval_frame(n, out, err, sizeof(err)); if (!f) die("output frame", err); freeFrame(f); }
+    ask_out_of_order(out, outFrames, nextra, extra);
     int failed = 0; /* (with x.free=1 a failed output frame is reported after the teardown: the free callbacks of a graph whose request ended in an error run too) */
     for (int n = 0; n < outFrames; n++) {
         const VSFrame *f = eval_frame(n, out, err, sizeof(err));

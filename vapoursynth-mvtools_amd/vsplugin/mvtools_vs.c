@@ -41,6 +41,7 @@
 #include "vs4_api.h"
 #include "vs4_api_check.h"
 #include "../../include/mvtools_amd.h"
+#include "mvx_vs_window.h"
 
 #define PROP_ADATA "MVTools_MVAnalysisData"
 #define PROP_VECTORS "MVTools_vectors"
@@ -931,9 +932,17 @@ typedef struct Combiner {
 #define LA_SLOTS 6
 enum { LW_EMPTY, LW_BUILDING, LW_LAUNCHED, LW_SYNCING, LW_READY, LW_FAILED };
 typedef struct LaWindow { int w, state, first, count, users, rc; void *dblobs; size_t dstride; DevFrame **pins; int npins; void *stream; } LaWindow; /* dblobs: the window's vectors, on the device until the slot is recycled */
-typedef struct LookAhead { int on, B, depth; volatile int started; /* a window of this instance has been launched (r6: the request that starts the FIRST one starts no window ahead) */ volatile int degraded; /* a window ran out of device memory: new requests take the per-frame path */ VSNode *srcNode; SuperData *sd; pthread_mutex_t mu; pthread_cond_t cv; LaWindow win[LA_SLOTS]; } LookAhead;
+/* The engine has two users, mv.Analyse and mv.AnalyseN.  What differs between them is below the line: how many frames a window needs before and after its own (the
+ * arithmetic is mvx_vs_window.h's), how many bytes of vectors a frame has, and the launch itself.  A launch callback gets the window's inputs on the device -- pins[i] is
+ * source frame lo + i, the last of the nn entries the fixed frame where there is one outside [lo, hi], top[i] its parity -- and `count` frames' room at dblobs; it enqueues
+ * ONE library call on `stream` and does not wait for it. */
+typedef struct LaLaunch { int first, count, lo, hi, nn; const int *top; DevFrame *const *pins; void *dblobs; void *stream; } LaLaunch;
+typedef struct LookAhead { int on, B, depth; volatile int started; /* a window of this instance has been launched (r6: the request that starts the FIRST one starts no window ahead) */ volatile int degraded; /* a window ran out of device memory: new requests take the per-frame path */ VSNode *srcNode; SuperData *sd; pthread_mutex_t mu; pthread_cond_t cv; LaWindow win[LA_SLOTS];
+    /* ---- the user's */
+    void *owner; int numFrames, before, after, fixed; /* fixed: a static reference frame every window needs (mv.Analyse with delta <= 0), else -1 */
+    size_t frameBytes; const FieldOpt *fo; int (*enqueue)(void *owner, const LaLaunch *l); } LookAhead;
 #define LA_DEPTH_MAX 3
-typedef struct LaReq { int legacy, w, hold[1 + LA_DEPTH_MAX], want[1 + LA_DEPTH_MAX]; } LaReq;
+typedef struct LaReq { int w, hold[1 + LA_DEPTH_MAX], want[1 + LA_DEPTH_MAX]; } LaReq; /* the frame data of a request that goes through the windows (one that does not has none) */
 
 typedef struct AnalyseData { VSNode *node; const VSVideoInfo *vi; mvx_super *sup; SuperGeo geo; mvx_analyse *an; mvx_analysis_data ad; int blobSize; FieldOpt fo; Combiner cb; LookAhead la; } AnalyseData;
 
@@ -941,6 +950,8 @@ static long env_long(const char *name, long def) { const char *e = getenv(name);
 
 /* totals over all instances, printed when the plugin is unloaded (MVX_VS_STATS=1): a host need not free its nodes before it exits */
 static long g_stat_launches, g_stat_jobs, g_stat_largest, g_stat_instances;
+/* ... and of mv.AnalyseN's windows: a line of their own, only when a window was launched */
+static long g_statn_windows, g_statn_frames, g_statn_chains, g_statn_largest;
 __attribute__((destructor)) static void print_stats(void) {
     if (env_long("MVX_VS_STATS", 0) && g_stat_instances)
     {
@@ -951,6 +962,8 @@ __attribute__((destructor)) static void print_stats(void) {
         for (int k = 0; k < PF_N; k++) fprintf(stderr, " %s=%.2f/%ld", nm[k], g_prof[k], g_prof_n[k]);
         fprintf(stderr, "\n");
     }
+    if (env_long("MVX_VS_STATS", 0) && g_statn_windows)
+        fprintf(stderr, "mvtools_vs: AnalyseN windows=%ld frames=%ld chains=%ld largest_window=%ld\n", g_statn_windows, g_statn_frames, g_statn_chains, g_statn_largest);
 }
 
 /* Streams of the search launches, shared by every mv.Analyse instance and handed out round robin.  The runtime maps streams onto a few
@@ -1063,77 +1076,61 @@ static void la_window_release(LaWindow *s) { /* frees what a finished / failed w
     s->state = LW_EMPTY; s->count = 0; s->rc = 0;
 }
 /* the slot of window w, recycled from an older finished window if nobody uses it; NULL if it is taken.  mu held. */
-static LaWindow *la_slot(AnalyseData *d, int w) {
-    LaWindow *s = &d->la.win[w % LA_SLOTS];
+static LaWindow *la_slot(LookAhead *la, int w) {
+    LaWindow *s = &la->win[mvx_win_slot(w, LA_SLOTS)];
     if (s->w == w) return s;
     if (s->users || s->state == LW_BUILDING || s->state == LW_LAUNCHED || s->state == LW_SYNCING) return NULL;
     la_window_release(s);
     s->w = w;
     return s;
 }
-/* source frames window v needs: [*lo, *hi] and, for a static reference (delta <= 0), the frame *fixed (else -1) */
-static void la_inputs(const AnalyseData *d, int v, int *lo, int *hi, int *fixed) {
-    const int first = v * d->la.B, last = (first + d->la.B < d->vi->numFrames ? first + d->la.B : d->vi->numFrames) - 1;
-    *lo = first; *hi = last; *fixed = -1;
-    if (d->ad.nDeltaFrame > 0) {
-        if (d->ad.isBackward) { const int h = last + d->ad.nDeltaFrame; *hi = h < d->vi->numFrames ? h : d->vi->numFrames - 1; }
-        else { const int l = first - d->ad.nDeltaFrame; *lo = l > 0 ? l : 0; }
-    } else if (-d->ad.nDeltaFrame < d->vi->numFrames) *fixed = -d->ad.nDeltaFrame;
+/* source frames window v needs: [*lo, *hi] and, for a static reference, the frame *fixed (else -1) */
+static void la_inputs(const LookAhead *la, int v, int *lo, int *hi, int *fixed) {
+    int first, count;
+    mvx_win_inputs(v, la->B, la->numFrames, la->before, la->after, &first, &count, lo, hi);
+    *fixed = la->fixed;
 }
-static void la_request_inputs(const AnalyseData *d, int v, VSFrameContext *ctx, const VSAPI *vs) {
+static void la_request_inputs(const LookAhead *la, int v, VSFrameContext *ctx, const VSAPI *vs) {
     int lo, hi, fixed;
-    la_inputs(d, v, &lo, &hi, &fixed);
-    for (int k = lo; k <= hi; k++) vs->requestFrameFilter(k, d->la.srcNode, ctx);
-    if (fixed >= 0 && (fixed < lo || fixed > hi)) vs->requestFrameFilter(fixed, d->la.srcNode, ctx);
+    la_inputs(la, v, &lo, &hi, &fixed);
+    for (int k = lo; k <= hi; k++) vs->requestFrameFilter(k, la->srcNode, ctx);
+    if (fixed >= 0 && (fixed < lo || fixed > hi)) vs->requestFrameFilter(fixed, la->srcNode, ctx);
 }
-static int analyse_nref(const AnalyseData *d, int n);
 /* builds the super frames of window v on the device and enqueues its search (does not wait for it) */
-static int la_launch(AnalyseData *d, LaWindow *s, int v, VSFrameContext *ctx, const VSAPI *vs) {
-    int lo, hi, fixed;
-    la_inputs(d, v, &lo, &hi, &fixed);
+static int la_launch(LookAhead *la, LaWindow *s, int v, VSFrameContext *ctx, const VSAPI *vs) {
+    int first, count, lo, hi;
+    mvx_win_inputs(v, la->B, la->numFrames, la->before, la->after, &first, &count, &lo, &hi);
+    const int fixed = la->fixed;
     const double tl0 = prof_now();
-    const int first = v * d->la.B, count = (first + d->la.B < d->vi->numFrames ? first + d->la.B : d->vi->numFrames) - first;
     const int extra = fixed >= 0 && (fixed < lo || fixed > hi);
     const int nn = hi - lo + 1 + extra;
     int *nums = (int *)malloc(sizeof(int) * (size_t)nn), *top = (int *)calloc((size_t)nn, sizeof(int));
     const VSFrame **srcs = (const VSFrame **)calloc((size_t)nn, sizeof(VSFrame *));
     DevFrame **pins = (DevFrame **)calloc((size_t)nn, sizeof(DevFrame *));
-    mvx_analyse_job *jobs = (mvx_analyse_job *)calloc((size_t)count, sizeof(mvx_analyse_job));
-    int rc = (!nums || !top || !srcs || !pins || !jobs) ? MVX_E_NOMEM : 0, missing = 0;
+    int rc = (!nums || !top || !srcs || !pins) ? MVX_E_NOMEM : 0, missing = 0;
     for (int i = 0; i < nn && !rc; i++) {
         nums[i] = i < hi - lo + 1 ? lo + i : fixed;
-        srcs[i] = vs->getFrameFilter(nums[i], d->la.srcNode, ctx);
+        srcs[i] = vs->getFrameFilter(nums[i], la->srcNode, ctx);
         if (!srcs[i]) { rc = MVX_E_ARG; break; }
-        top[i] = frame_top_field(&d->fo, srcs[i], nums[i], &missing, vs); /* mv.Super copies the props of its source frame (MVSuper.c:104) */
+        top[i] = frame_top_field(la->fo, srcs[i], nums[i], &missing, vs); /* mv.Super copies the props of its source frame (MVSuper.c:104) */
     }
-    if (!rc && missing && d->fo.fields) rc = -1000; /* reported by the caller with the reference's message */
-    la_trace(d, v, "source frames fetched", prof_now() - tl0);
-    { const double tq = prof_now(); if (!rc) rc = super_build_device(d->la.sd, nn, nums, srcs, pins, vs); prof_add(PF_LA_BUILD, tq); la_trace(d, v, "super frames on the device", prof_now() - tq); }
+    if (!rc && missing && la->fo->fields) rc = -1000; /* reported by the caller with the reference's message */
+    la_trace(la->owner, v, "source frames fetched", prof_now() - tl0);
+    { const double tq = prof_now(); if (!rc) rc = super_build_device(la->sd, nn, nums, srcs, pins, vs); prof_add(PF_LA_BUILD, tq); la_trace(la->owner, v, "super frames on the device", prof_now() - tq); }
     for (int i = 0; i < nn; i++) if (srcs && srcs[i]) vs->freeFrame(srcs[i]);
-    const size_t stride = ((size_t)d->blobSize + 255) / 256 * 256;
-    void *dblobs = rc ? NULL : shell_alloc(stride * (size_t)count);
+    void *dblobs = rc ? NULL : shell_alloc(la->frameBytes * (size_t)count);
     /* the window's vectors stay on the device; every request downloads its own 2.7 MB when it is served.  (Bringing a whole window to the
      * host at once was tried both ways: a synchronous 350 MB download by the first waiter stalled all request threads six times per window,
      * and page-locked per-slot arrays for an asynchronous copy cost 0.4 s of hipHostMalloc each, during which every HIP call of the process
      * waits.) */
     if (!rc && !dblobs) rc = MVX_E_NOMEM;
     if (!rc) {
-        for (int i = 0; i < count; i++) {
-            const int k = first + i, nref = analyse_nref(d, k);
-            const int haveRef = nref >= 0 && nref < d->vi->numFrames;
-            const int is = k - lo, ir = !haveRef ? -1 : (nref >= lo && nref <= hi) ? nref - lo : nn - 1;
-            for (int p = 0; p < 3; p++) { jobs[i].src[p] = pins[is]->plane[p]; jobs[i].ref[p] = haveRef ? pins[ir]->plane[p] : NULL; }
-            jobs[i].blob = (char *)dblobs + stride * (size_t)i;
-            jobs[i].field_shift = (haveRef && d->fo.fields && d->ad.nPel > 1 && (d->ad.nDeltaFrame % 2)) ? field_shift_of(top[is], top[ir], d->ad.nPel) : 0;
-        }
         s->stream = search_stream_next();
+        const LaLaunch l = { first, count, lo, hi, nn, top, pins, dblobs, s->stream };
         const double tq = prof_now();
-        rc = mvx_analyse_frames(d->an, count, jobs, s->stream);
+        rc = la->enqueue(la->owner, &l);
         prof_add(PF_LA_LAUNCH, tq);
-        la_trace(d, v, "search enqueued", prof_now() - tl0);
-        pthread_mutex_lock(&g_lock);
-        g_stat_launches++; g_stat_jobs += count; if (count > g_stat_largest) g_stat_largest = count;
-        pthread_mutex_unlock(&g_lock);
+        la_trace(la->owner, v, "search enqueued", prof_now() - tl0);
     }
     if (rc) {
         shell_quiesce(rc);
@@ -1141,43 +1138,123 @@ static int la_launch(AnalyseData *d, LaWindow *s, int v, VSFrameContext *ctx, co
         for (int i = 0; i < nn; i++) if (pins && pins[i]) cache_unpin(pins[i]);
         free(pins);
         if (dblobs) mvx_dev_free(dblobs);
-    } else { s->pins = pins; s->npins = nn; s->dblobs = dblobs; s->dstride = stride; s->first = first; s->count = count; }
-    free(nums); free(top); free(srcs); free(jobs);
+    } else { s->pins = pins; s->npins = nn; s->dblobs = dblobs; s->dstride = la->frameBytes; s->first = first; s->count = count; }
+    free(nums); free(top); free(srcs);
     return rc;
 }
 /* waits until window s is READY (or FAILED): the first waiter synchronises the window's stream */
-static int la_wait(AnalyseData *d, LaWindow *s) {
-    pthread_mutex_lock(&d->la.mu);
+static int la_wait(LookAhead *la, LaWindow *s) {
+    pthread_mutex_lock(&la->mu);
     for (;;) {
         if (s->state == LW_READY || s->state == LW_FAILED || s->state == LW_EMPTY) break;
         if (s->state == LW_LAUNCHED) {
             s->state = LW_SYNCING;
-            pthread_mutex_unlock(&d->la.mu);
+            pthread_mutex_unlock(&la->mu);
             const double t0 = prof_now();
             const int rc = mvx_stream_sync(s->stream);
             prof_add(PF_SEARCH_WAIT, t0);
-            la_trace(d, s->w, "first waiter saw the search finish", prof_now() - t0);
-            pthread_mutex_lock(&d->la.mu);
+            la_trace(la->owner, s->w, "first waiter saw the search finish", prof_now() - t0);
+            pthread_mutex_lock(&la->mu);
             for (int i = 0; i < s->npins; i++) cache_unpin(s->pins[i]);
             free(s->pins); s->pins = NULL; s->npins = 0;
             s->rc = rc; s->state = rc ? LW_FAILED : LW_READY;
-            pthread_cond_broadcast(&d->la.cv);
+            pthread_cond_broadcast(&la->cv);
             continue;
         }
-        { const double tb = prof_now(); pthread_cond_wait(&d->la.cv, &d->la.mu); prof_add(PF_LA_BLOCKED, tb); } /* BUILDING / SYNCING: somebody is on it */
+        { const double tb = prof_now(); pthread_cond_wait(&la->cv, &la->mu); prof_add(PF_LA_BLOCKED, tb); } /* BUILDING / SYNCING: somebody is on it */
     }
     const int rc = s->state == LW_READY ? 0 : (s->rc ? s->rc : MVX_E_DEVICE);
-    pthread_mutex_unlock(&d->la.mu);
+    pthread_mutex_unlock(&la->mu);
     return rc;
 }
-static void la_release_req(AnalyseData *d, LaReq *r) {
+static void la_release_req(LookAhead *la, LaReq *r) {
     if (!r) return;
-    if (!r->legacy) {
-        pthread_mutex_lock(&d->la.mu);
-        for (int i = 0; i <= LA_DEPTH_MAX; i++) if (r->hold[i]) d->la.win[(r->w + i) % LA_SLOTS].users--;
-        pthread_mutex_unlock(&d->la.mu);
-    }
+    pthread_mutex_lock(&la->mu);
+    for (int i = 0; i <= LA_DEPTH_MAX; i++) if (r->hold[i]) la->win[mvx_win_slot(r->w + i, LA_SLOTS)].users--;
+    pthread_mutex_unlock(&la->mu);
     free(r);
+}
+/* arInitial of the request for frame n of a clip with windows: its frame data, and what it asks for -- frame n of `self` (the vector clip's frame is a copy of the super
+ * frame, MVAnalyse.c:224) and the source frames of the windows it will start.  0: no slot / no memory, this request takes the per-frame path and *fd stays NULL */
+static int la_request(LookAhead *la, int n, VSNode *self, void **fd, VSFrameContext *ctx, const VSAPI *vs) {
+    LaReq *r = (LaReq *)calloc(1, sizeof(LaReq));
+    if (!r) return 0;
+    r->w = mvx_win_of(n, la->B);
+    pthread_mutex_lock(&la->mu);
+    LaWindow *s0 = la->degraded ? NULL : la_slot(la, r->w);
+    if (s0) {
+        s0->users++; r->hold[0] = 1; r->want[0] = s0->state == LW_EMPTY;
+        /* (r6: not the request that starts an instance's FIRST window -- mv.DegrainN's creation reads frame 0 of every vector clip, and the windows ahead of
+         * the first instances' frame 0 kept the GPU from the later instances' first windows: 0.8 s of graph construction for six clips; the windows ahead are
+         * started by the next request, a moment later) */
+        for (int i = 1; la->started && i <= la->depth && (r->w + i) * la->B < la->numFrames; i++) { /* the windows ahead: whoever sees them empty first starts them */
+            LaWindow *s1 = la_slot(la, r->w + i);
+            if (s1 && s1->state == LW_EMPTY) { s1->users++; r->hold[i] = 1; r->want[i] = 1; }
+        }
+    }
+    pthread_mutex_unlock(&la->mu);
+    if (!s0) { free(r); return 0; }
+    *fd = r;
+    vs->requestFrameFilter(n, self, ctx);
+    /* one source frame of the window that will be started next: by the time some request sees that window empty and asks
+     * for all of its frames, the requests of this window have had the host produce them, in parallel */
+    { const int ahead = n + (la->depth + 1) * la->B; if (ahead < la->numFrames) vs->requestFrameFilter(ahead, la->srcNode, ctx); }
+    for (int i = 0; i <= LA_DEPTH_MAX; i++) if (r->want[i]) { la_trace(la->owner, r->w + i, "source frames requested", 0.0); la_request_inputs(la, r->w + i, ctx, vs); }
+    return 1;
+}
+/* arAllFramesReady of such a request: starts the windows whose frames it asked for and waits for its own, *win (READY when this returns 0) */
+static int la_serve(LookAhead *la, const LaReq *r, LaWindow **win, VSFrameContext *ctx, const VSAPI *vs) {
+    int rc = 0;
+    for (int i = 0; i <= LA_DEPTH_MAX && !rc; i++) {
+        if (!r->want[i]) continue;
+        LaWindow *s = &la->win[mvx_win_slot(r->w + i, LA_SLOTS)];
+        int mine = 0;
+        pthread_mutex_lock(&la->mu);
+        if (s->state == LW_EMPTY) { s->state = LW_BUILDING; mine = 1; }
+        pthread_mutex_unlock(&la->mu);
+        if (!mine) continue;
+        const int lrc = la_launch(la, s, r->w + i, ctx, vs);
+        pthread_mutex_lock(&la->mu);
+        s->rc = lrc; s->state = lrc ? LW_FAILED : LW_LAUNCHED;
+        la->started = 1;
+        if (lrc == MVX_E_NOMEM) la->degraded = 1; /* (the requests already waiting for this window fail -- their reference frames were never asked for -- but nothing after them does) */
+        pthread_cond_broadcast(&la->cv);
+        pthread_mutex_unlock(&la->mu);
+        if (lrc && i == 0) rc = lrc;
+    }
+    *win = &la->win[mvx_win_slot(r->w, LA_SLOTS)];
+    if (!rc) rc = la_wait(la, *win);
+    return rc;
+}
+/* what creation decides: on with windows of B frames and `depth` of them ahead, unless what they hold would not fit the device (MVX_VS_LOOKAHEAD_AUTOSIZE=0: not asked).
+ * superBytes / blobBytes / slots: see mvx_win_bytes; half of the free memory is left to the other vector clips' share, the consumers' frames and the allocator's pool */
+static void la_size(LookAhead *la, long B, double superBytes, double blobBytes, int slots) {
+    la->on = 1; la->B = (int)(B > 512 ? 512 : B);
+    /* windows started ahead of the one being consumed.  Two: gathering a window's source frames and building its super frames
+     * takes a host about as long as consuming a window does, and the search itself another ~0.5 s */
+    la->depth = (int)env_long("MVX_VS_LOOKAHEAD_DEPTH", 2);
+    if (la->depth < 0) la->depth = 0;
+    if (la->depth > LA_DEPTH_MAX) la->depth = LA_DEPTH_MAX;
+    size_t fr = 0, tot = 0;
+    if (env_long("MVX_VS_LOOKAHEAD_AUTOSIZE", 1) && mvx_dev_mem_info(&fr, &tot) == 0 && fr)
+        la->on = mvx_win_fit(&la->B, &la->depth, la->before + la->after > 0 ? la->before + la->after : 1, superBytes, blobBytes, slots, 0.5 * (double)fr); /* (0: not even one small window: the per-frame path) */
+}
+static void la_open(LookAhead *la, VSNode *srcNode, const VSAPI *vs) {
+    la->srcNode = vs->addNodeRef(srcNode);
+    pthread_mutex_init(&la->mu, NULL); pthread_cond_init(&la->cv, NULL);
+    for (int i = 0; i < LA_SLOTS; i++) la->win[i].w = -1;
+}
+/* the windows' pins go before the nodes: freeing the super node may run mv.Super's free callback, which drops its unpinned frames from the cache */
+static void la_drain(LookAhead *la) {
+    for (int i = 0; i < LA_SLOTS; i++) {
+        LaWindow *s = &la->win[i];
+        if (s->state == LW_LAUNCHED) (void)mvx_stream_sync(s->stream); /* nobody came for it */
+        la_window_release(s);
+    }
+}
+static void la_close(LookAhead *la, const VSAPI *vs) {
+    vs->freeNode(la->srcNode);
+    pthread_mutex_destroy(&la->mu); pthread_cond_destroy(&la->cv);
 }
 
 /* r6: the vectors of a look-ahead window stay on the device until its slot is recycled; a consumer of this plugin (mv.DegrainN) that finds the window of frame n still there
@@ -1204,24 +1281,44 @@ static AnalyseData *analyse_lookup(VSNode *out) {
     return d;
 }
 /* the device copy of frame n's vectors, its window pinned (la_device_blob_release), or NULL */
-static const void *la_device_blob(AnalyseData *d, int n, LaWindow **held) {
+static const void *la_device_blob(LookAhead *la, int n, LaWindow **held) {
     *held = NULL;
-    if (!d || !d->la.on) return NULL;
+    if (!la || !la->on) return NULL;
     const void *p = NULL;
-    pthread_mutex_lock(&d->la.mu);
-    LaWindow *s = &d->la.win[(n / d->la.B) % LA_SLOTS];
-    if (s->w == n / d->la.B && s->state == LW_READY && s->dblobs && n >= s->first && n < s->first + s->count) {
+    pthread_mutex_lock(&la->mu);
+    LaWindow *s = &la->win[mvx_win_slot(mvx_win_of(n, la->B), LA_SLOTS)];
+    if (s->w == mvx_win_of(n, la->B) && s->state == LW_READY && s->dblobs && n >= s->first && n < s->first + s->count) {
         s->users++; *held = s;
         p = (const char *)s->dblobs + s->dstride * (size_t)(n - s->first);
     }
-    pthread_mutex_unlock(&d->la.mu);
+    pthread_mutex_unlock(&la->mu);
     return p;
 }
-static void la_device_blob_release(AnalyseData *d, LaWindow *held) {
+static void la_device_blob_release(LookAhead *la, LaWindow *held) {
     if (!held) return;
-    pthread_mutex_lock(&d->la.mu);
+    pthread_mutex_lock(&la->mu);
     held->users--;
-    pthread_mutex_unlock(&d->la.mu);
+    pthread_mutex_unlock(&la->mu);
+}
+/* mv.Analyse's launch: one job per frame of the window */
+static int analyse_enqueue(void *owner, const LaLaunch *l) {
+    AnalyseData *d = (AnalyseData *)owner;
+    mvx_analyse_job *jobs = (mvx_analyse_job *)calloc((size_t)l->count, sizeof(mvx_analyse_job));
+    if (!jobs) return MVX_E_NOMEM;
+    for (int i = 0; i < l->count; i++) {
+        const int k = l->first + i, nref = analyse_nref(d, k);
+        const int haveRef = nref >= 0 && nref < d->vi->numFrames;
+        const int is = k - l->lo, ir = !haveRef ? -1 : (nref >= l->lo && nref <= l->hi) ? nref - l->lo : l->nn - 1;
+        for (int p = 0; p < 3; p++) { jobs[i].src[p] = l->pins[is]->plane[p]; jobs[i].ref[p] = haveRef ? l->pins[ir]->plane[p] : NULL; }
+        jobs[i].blob = (char *)l->dblobs + d->la.frameBytes * (size_t)i;
+        jobs[i].field_shift = (haveRef && d->fo.fields && d->ad.nPel > 1 && (d->ad.nDeltaFrame % 2)) ? field_shift_of(l->top[is], l->top[ir], d->ad.nPel) : 0;
+    }
+    const int rc = mvx_analyse_frames(d->an, l->count, jobs, l->stream);
+    free(jobs);
+    pthread_mutex_lock(&g_lock);
+    g_stat_launches++; g_stat_jobs += l->count; if (l->count > g_stat_largest) g_stat_largest = l->count;
+    pthread_mutex_unlock(&g_lock);
+    return rc;
 }
 
 static const VSFrame *VS_CC analyseGetFrame(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
@@ -1230,59 +1327,15 @@ static const VSFrame *VS_CC analyseGetFrame(int n, int reason, void *inst, void 
     const int haveRef = nref >= 0 && nref < d->vi->numFrames;
     if (d->la.on) {
         if (reason == arInitial) {
-            LaReq *r = (LaReq *)calloc(1, sizeof(LaReq));
-            *fd = r;
-            if (r) {
-                r->w = n / d->la.B;
-                pthread_mutex_lock(&d->la.mu);
-                LaWindow *s0 = d->la.degraded ? NULL : la_slot(d, r->w);
-                if (!s0) r->legacy = 1;
-                else {
-                    s0->users++; r->hold[0] = 1; r->want[0] = s0->state == LW_EMPTY;
-                    /* (r6: not the request that starts an instance's FIRST window -- mv.DegrainN's creation reads frame 0 of every vector clip, and the windows ahead of
-                     * the first instances' frame 0 kept the GPU from the later instances' first windows: 0.8 s of graph construction for six clips; the windows ahead are
-                     * started by the next request, a moment later) */
-                    for (int i = 1; d->la.started && i <= d->la.depth && (r->w + i) * d->la.B < d->vi->numFrames; i++) { /* the windows ahead: whoever sees them empty first starts them */
-                        LaWindow *s1 = la_slot(d, r->w + i);
-                        if (s1 && s1->state == LW_EMPTY) { s1->users++; r->hold[i] = 1; r->want[i] = 1; }
-                    }
-                }
-                pthread_mutex_unlock(&d->la.mu);
-                if (!r->legacy) {
-                    vs->requestFrameFilter(n, d->node, ctx); /* the vector clip's frame is a copy of the super frame (MVAnalyse.c:224) */
-                    /* one source frame of the window that will be started next: by the time some request sees that window empty and asks
-                     * for all of its frames, the requests of this window have had the host produce them, in parallel */
-                    { const int ahead = n + (d->la.depth + 1) * d->la.B; if (ahead < d->vi->numFrames) vs->requestFrameFilter(ahead, d->la.srcNode, ctx); }
-                    for (int i = 0; i <= LA_DEPTH_MAX; i++) if (r->want[i]) { la_trace(d, r->w + i, "source frames requested", 0.0); la_request_inputs(d, r->w + i, ctx, vs); }
-                    return NULL;
-                }
-            }
+            if (la_request(&d->la, n, d->node, fd, ctx, vs)) return NULL;
             /* (no slot / no memory: this request takes the per-frame path below) */
-        } else if (*fd && !((LaReq *)*fd)->legacy) {
+        } else if (*fd) {
             LaReq *r = (LaReq *)*fd;
             *fd = NULL;
-            if (reason != arAllFramesReady) { la_release_req(d, r); return NULL; } /* arError */
+            if (reason != arAllFramesReady) { la_release_req(&d->la, r); return NULL; } /* arError */
             const double tgf = prof_now();
-            int rc = 0;
-            for (int i = 0; i <= LA_DEPTH_MAX && !rc; i++) {
-                if (!r->want[i]) continue;
-                LaWindow *s = &d->la.win[(r->w + i) % LA_SLOTS];
-                int mine = 0;
-                pthread_mutex_lock(&d->la.mu);
-                if (s->state == LW_EMPTY) { s->state = LW_BUILDING; mine = 1; }
-                pthread_mutex_unlock(&d->la.mu);
-                if (!mine) continue;
-                const int lrc = la_launch(d, s, r->w + i, ctx, vs);
-                pthread_mutex_lock(&d->la.mu);
-                s->rc = lrc; s->state = lrc ? LW_FAILED : LW_LAUNCHED;
-                d->la.started = 1;
-                if (lrc == MVX_E_NOMEM) d->la.degraded = 1; /* (the requests already waiting for this window fail -- their reference frames were never asked for -- but nothing after them does) */
-                pthread_cond_broadcast(&d->la.cv);
-                pthread_mutex_unlock(&d->la.mu);
-                if (lrc && i == 0) rc = lrc;
-            }
-            LaWindow *s = &d->la.win[r->w % LA_SLOTS];
-            if (!rc) rc = la_wait(d, s);
+            LaWindow *s = NULL;
+            int rc = la_serve(&d->la, r, &s, ctx, vs);
             const VSFrame *src = vs->getFrameFilter(n, d->node, ctx);
             VSFrame *dst = NULL;
             char *blob = rc ? NULL : (char *)malloc((size_t)d->blobSize);
@@ -1299,10 +1352,10 @@ static const VSFrame *VS_CC analyseGetFrame(int n, int reason, void *inst, void 
                                    rc == MVX_E_NOMEM ? "Analyse: out of memory." : mvx_last_error(), ctx);
             free(blob);
             if (src) vs->freeFrame(src);
-            la_release_req(d, r);
+            la_release_req(&d->la, r);
             prof_add(PF_GF_ANALYSE, tgf);
             return dst;
-        } else if (*fd) { free(*fd); *fd = NULL; }
+        }
     }
     if (reason == arInitial) {
         if (haveRef && nref < n) vs->requestFrameFilter(nref, d->node, ctx);
@@ -1366,18 +1419,9 @@ static void VS_CC analyseFree(void *inst, VSCore *core, const VSAPI *vs) {
     (void)core;
     AnalyseData *d = (AnalyseData *)inst;
     analyse_unregister(d);
-    if (d->la.on) { /* the windows' pins go first: freeing the super node may run mv.Super's free callback, which drops its unpinned frames from the cache */
-        for (int i = 0; i < LA_SLOTS; i++) {
-            LaWindow *s = &d->la.win[i];
-            if (s->state == LW_LAUNCHED) (void)mvx_stream_sync(s->stream); /* nobody came for it */
-            la_window_release(s);
-        }
-    }
+    if (d->la.on) la_drain(&d->la);
     vs->freeNode(d->node);
-    if (d->la.on) {
-        vs->freeNode(d->la.srcNode);
-        pthread_mutex_destroy(&d->la.mu); pthread_cond_destroy(&d->la.cv);
-    }
+    if (d->la.on) la_close(&d->la, vs);
     combiner_free(&d->cb, "Analyse");
     mvx_analyse_destroy(d->an);
     mvx_super_destroy(d->sup);
@@ -1426,28 +1470,16 @@ static void VS_CC analyseCreate(const VSMap *in, VSMap *out, void *user, VSCore 
         SuperData *sd = super_lookup(node);
         const long B = env_long("MVX_VS_LOOKAHEAD", 128);
         if (sd && !sd->pelMode && B > 0 && vi->numFrames > 1 && cache_cap() > 0) { /* (no device cache, no windows: they live in it) */
-            d->la.on = 1; d->la.B = (int)(B > 512 ? 512 : B); d->la.sd = sd;
-            /* windows started ahead of the one being consumed.  Two: gathering a window's source frames and building its super frames
-             * takes a host about as long as consuming a window does, and the search itself another ~0.5 s */
-            d->la.depth = (int)env_long("MVX_VS_LOOKAHEAD_DEPTH", 2);
-            if (d->la.depth < 0) d->la.depth = 0;
-            if (d->la.depth > LA_DEPTH_MAX) d->la.depth = LA_DEPTH_MAX;
-            { /* what the windows in flight pin must fit the device: every window holds B + delta super frames (with their shadow planes)
-               * and B blobs; half of the free memory is left to the other vector clips' share, Degrain's frames and the allocator's pool */
-                size_t fr = 0, tot = 0;
-                if (env_long("MVX_VS_LOOKAHEAD_AUTOSIZE", 1) && mvx_dev_mem_info(&fr, &tot) == 0 && fr) {
-                    const int delta = d->ad.nDeltaFrame > 0 ? d->ad.nDeltaFrame : 1;
-                    const double per = (double)sd->geo.bytes * 1.2 + (double)d->blobSize, avail = 0.5 * (double)fr;
-                    while (d->la.depth > 0 && (double)(d->la.depth + 1) * (d->la.B + delta) * per > avail) d->la.depth--;
-                    while (d->la.B > 8 && (double)(d->la.depth + 1) * (d->la.B + delta) * per > avail) d->la.B /= 2;
-                    if ((double)(d->la.depth + 1) * (d->la.B + delta) * per > avail) d->la.on = 0; /* not even one small window: the per-frame path */
-                }
-            }
+            const int delta = d->ad.nDeltaFrame;
+            d->la.sd = sd; d->la.owner = d; d->la.numFrames = vi->numFrames; d->la.fo = &d->fo; d->la.enqueue = analyse_enqueue;
+            d->la.before = delta > 0 && !d->ad.isBackward ? delta : 0; d->la.after = delta > 0 && d->ad.isBackward ? delta : 0;
+            d->la.fixed = delta <= 0 && -delta < vi->numFrames ? -delta : -1;
+            d->la.frameBytes = ((size_t)d->blobSize + 255) / 256 * 256;
+            /* what the windows in flight pin must fit the device: every window holds B + delta super frames (with their shadow planes) and B blobs */
+            la_size(&d->la, B, (double)sd->geo.bytes * 1.2 + (double)d->blobSize, 0.0, 0);
         }
         if (d->la.on) {
-            d->la.srcNode = vs->addNodeRef(sd->node);
-            pthread_mutex_init(&d->la.mu, NULL); pthread_cond_init(&d->la.cv, NULL);
-            for (int i = 0; i < LA_SLOTS; i++) d->la.win[i].w = -1;
+            la_open(&d->la, sd->node, vs);
             deps[1].source = d->la.srcNode; ndeps = 2;
         }
     }
@@ -1948,7 +1980,7 @@ static const VSFrame *VS_CC degrainGetFrameUngated(int n, int reason, void *inst
     if (!rc) rc = dst_plane_set(ddst, &dstArena, d->pitch, height, np);
     for (int p = 0; p < np && !rc; p++) { job.src[p] = dsrc[p]; job.dst[p] = ddst[p]; }
     for (int r = 0; r < nr && !rc; r++) {
-        const void *onDevice = la_device_blob(d->an[r], n, &blobHeld[r]);
+        const void *onDevice = la_device_blob(d->an[r] ? &d->an[r]->la : NULL, n, &blobHeld[r]);
         if (onDevice) job.blobs[r] = (void *)onDevice; /* (the window that made the frame's property: the same bytes) */
         else {
             rc = clip_blob_to_device(&blobArena[r], n, d->vectors[r], &d->ad[r], ctx, vs);
@@ -1971,7 +2003,7 @@ static const VSFrame *VS_CC degrainGetFrameUngated(int n, int reason, void *inst
             rc = timed_download_on(download_stream(), vs->getWritePtr(dst, p), vs->getStride(dst, p), job.dst[p], d->pitch[p], (size_t)vs->getFrameWidth(dst, p) * bps, (size_t)vs->getFrameHeight(dst, p));
     }
     shell_quiesce(rc);
-    for (int r = 0; r < nr; r++) { dev_release(&refs[r]); if (blobArena[r]) mvx_dev_free(blobArena[r]); la_device_blob_release(d->an[r], blobHeld[r]); }
+    for (int r = 0; r < nr; r++) { dev_release(&refs[r]); if (blobArena[r]) mvx_dev_free(blobArena[r]); if (blobHeld[r]) la_device_blob_release(&d->an[r]->la, blobHeld[r]); }
     if (srcArena) mvx_dev_free(srcArena);
     if (dstArena) mvx_dev_free(dstArena);
     vs->freeFrame(src);
@@ -3147,7 +3179,8 @@ static void VS_CC depanStabCreate(const VSMap *in, VSMap *out, void *user, VSCor
  *     MVTools_multi_stride          int: bytes from one field to the next (a field's size rounded up to 256)
  *     MVTools_multi_vectors         2 * radius * stride bytes; field r at r * stride, every pad byte 0
  * It carries neither MVTools_MVAnalysisData nor MVTools_vectors, so a single-field filter refuses it at creation with its own "Property ... not found" message;
- * mv.MultiField turns one field into an ordinary vector clip.  The property is uploaded per request (no device-side hand-over between these nodes yet). */
+ * mv.MultiField turns one field into an ordinary vector clip.  The property is uploaded per request: handing the blob from mv.AnalyseN's windows to this plugin's consumers on the device was built and
+ * measured, and gained nothing beyond the spread of the rates (profiles/multi_lookahead_bench.txt), so it is not here. */
 #define PROP_MULTI_ADATA "MVTools_multi_MVAnalysisData"
 #define PROP_MULTI_RADIUS "MVTools_multi_radius"
 #define PROP_MULTI_STRIDE "MVTools_multi_stride"
@@ -3164,7 +3197,7 @@ static void multi_field_data(mvx_analysis_data *out, const mvx_analysis_data *ad
     out->nMotionFlags = (ad0->nMotionFlags & ~2) | (out->isBackward ? 2 : 0); /* MOTION_IS_BACKWARD, src/MVAnalyse.c:489 */
 }
 /* frame n + multi_offset(r) is the reference of field r */
-static int multi_offset(int r) { return r % 2 == 0 ? r / 2 + 1 : -(r / 2 + 1); }
+static int multi_offset(int r) { return mvx_win_field_offset(r); }
 
 static int multi_from_clip(MultiInfo *mi, VSNode *clip, const char *filter, const char *name, char *error, size_t esz, const VSAPI *vs) {
     char msg[1024];
@@ -3251,8 +3284,10 @@ static int multi_refs_to_device(DevRef *refs, const void *table[][3], int n, int
 
 ENGINE_DESTROY(mvx_analyse_n) ENGINE_DESTROY(mvx_recalculate_n) ENGINE_DESTROY(mvx_degrain_n) ENGINE_DESTROY(mvx_compensate_n)
 
-/* ---- mv.AnalyseN(super, radius, ...): one mvx_analyse_n_frames call per frame (no combining queue, no look-ahead windows yet) */
-typedef struct AnalyseNData { Consumer c; VSNode *super; const VSVideoInfo *vi; mvx_analyse_n *an; MultiInfo mi; size_t fieldSize; FieldOpt fo; } AnalyseNData;
+/* ---- mv.AnalyseN(super, radius, ...).  Under mv.Analyse's conditions it computes its clip in look-ahead windows (the engine above): ONE mvx_analyse_n_frames call per
+ * window of MVX_VS_MULTI_LOOKAHEAD frames (unset: mvx_win_default_length; 0: off), whose multi blobs stay on the device until the slot is recycled; a request
+ * downloads its frame's fields from there.  Else, and for a request that finds no slot, one call per frame (no combining queue). */
+typedef struct AnalyseNData { Consumer c; VSNode *super; const VSVideoInfo *vi; mvx_analyse_n *an; MultiInfo mi; size_t fieldSize; FieldOpt fo; LookAhead la; } AnalyseNData;
 
 static const VSFrame *VS_CC analyseNGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
     (void)fd;
@@ -3313,6 +3348,74 @@ static const VSFrame *VS_CC analyseNGetFrameUngated(int n, int reason, void *ins
     return dst;
 }
 
+/* mv.AnalyseN's launch: one job per frame of the window, its 2 * radius references from a HOST table of count x 2 * radius entries (outside the clip: NULL) */
+static int analyse_n_enqueue(void *owner, const LaLaunch *l) {
+    AnalyseNData *d = (AnalyseNData *)owner;
+    const int nf = 2 * d->mi.radius;
+    const size_t cells = (size_t)l->count * (size_t)nf;
+    const void *(*table)[3] = (const void *(*)[3])calloc(cells, sizeof(*table));
+    int32_t *shift = (int32_t *)calloc(cells, sizeof(int32_t));
+    mvx_analyse_n_job *jobs = (mvx_analyse_n_job *)calloc((size_t)l->count, sizeof(mvx_analyse_n_job));
+    int rc = (!table || !shift || !jobs) ? MVX_E_NOMEM : 0;
+    for (int i = 0; i < l->count && !rc; i++) {
+        const int n = l->first + i, is = n - l->lo;
+        for (int r = 0; r < nf; r++) {
+            const int ir = mvx_win_field_input(n, r, l->lo, l->hi);
+            if (ir < 0) continue;
+            for (int p = 0; p < 3; p++) table[(size_t)i * nf + r][p] = l->pins[ir]->plane[p];
+            if (d->fo.fields && d->mi.ad0.nPel > 1 && (r / 2 + 1) % 2) shift[(size_t)i * nf + r] = field_shift_of(l->top[is], l->top[ir], d->mi.ad0.nPel); /* src/MVAnalyse.c:135-179, per field */
+        }
+        for (int p = 0; p < 3; p++) jobs[i].src[p] = l->pins[is]->plane[p];
+        jobs[i].refs = table + (size_t)i * nf; jobs[i].field_shift = shift + (size_t)i * nf;
+        jobs[i].blob = (char *)l->dblobs + d->la.frameBytes * (size_t)i;
+    }
+    if (!rc) rc = mvx_analyse_n_frames(d->an, l->count, jobs, l->stream); /* (the host arrays are read before it returns) */
+    free(table); free(shift); free(jobs);
+    if (rc) return rc; /* (the AnalyseN line counts windows that were launched) */
+    pthread_mutex_lock(&g_lock);
+    g_statn_windows++; g_statn_frames += l->count; g_statn_chains += (long)l->count * nf; if (l->count > g_statn_largest) g_statn_largest = l->count;
+    pthread_mutex_unlock(&g_lock);
+    return 0;
+}
+
+/* the node's getFrame when the instance has windows.  A request in a window is ungated, like mv.Analyse's: it waits for GPU work or for a thread that is already running.
+ * One that finds no slot, or comes after the instance ran out of device memory, is the per-frame request it always was, behind the admission gate: the frame data of a
+ * window request is its LaReq, of a per-frame request the gate's permit (NULL with the gate off) */
+static const VSFrame *VS_CC analyseNGetFrameWindows(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
+    AnalyseNData *d = (AnalyseNData *)inst;
+    if (reason == arInitial) {
+        if (la_request(&d->la, n, d->super, fd, ctx, vs)) return NULL;
+        /* (no slot / no memory: this request takes the per-frame path below) */
+    } else if (*fd && *fd != (void *)&d->c.gate) {
+        LaReq *r = (LaReq *)*fd;
+        *fd = NULL;
+        if (reason != arAllFramesReady) { la_release_req(&d->la, r); return NULL; } /* arError */
+        LaWindow *s = NULL;
+        int rc = la_serve(&d->la, r, &s, ctx, vs);
+        const VSFrame *src = vs->getFrameFilter(n, d->super, ctx);
+        VSFrame *dst = NULL;
+        if (!rc && !src) rc = MVX_E_DEVICE;
+        if (!rc) { dst = vs->copyFrame(src, core); rc = multi_set_props(dst, (const char *)s->dblobs + s->dstride * (size_t)(n - s->first), &d->mi, d->fieldSize, vs); }
+        shell_quiesce(rc);
+        if (src) vs->freeFrame(src);
+        la_release_req(&d->la, r);
+        if (rc) {
+            if (dst) vs->freeFrame(dst);
+            if (rc == -1000) vs->setFilterError("AnalyseN: _Field property not found in input frame. Therefore, you must pass tff argument.", ctx);
+            else consumer_frame_error(d->c.name, rc, 0, ctx, vs);
+            return NULL;
+        }
+        return dst;
+    }
+    return consumerGetFrame(n, reason, inst, fd, ctx, core, vs);
+}
+
+static void VS_CC analyseNFree(void *inst, VSCore *core, const VSAPI *vs) {
+    AnalyseNData *d = (AnalyseNData *)inst;
+    if (d->la.on) { la_drain(&d->la); la_close(&d->la, vs); } /* (windows nobody came for are waited for) */
+    consumerFree(inst, core, vs);
+}
+
 static int video_format_ok(const VSVideoInfo *vi) {
     return mvx_vsh_is_constant_video_format(vi) && vi->format.bitsPerSample <= 16 && vi->format.sampleType == stInteger && vi->format.subSamplingW <= 1 &&
            vi->format.subSamplingH <= 1 && (vi->format.colorFamily == cfYUV || vi->format.colorFamily == cfGray);
@@ -3350,8 +3453,26 @@ static void VS_CC analyseNCreate(const VSMap *in, VSMap *out, void *user, VSCore
     mvx_analyse_n_get_data(d->an, 0, &d->mi.ad0);
     if (d->c.geo.copies > 1) mvx_analyse_n_set_ref_shadow(d->an, d->c.geo.shadowStride); /* every device super frame of this shell carries its copies */
     pthread_mutex_lock(&g_lock); g_stat_instances++; pthread_mutex_unlock(&g_lock); /* (MVX_VS_STATS=1 reports the shell's thread-seconds for graphs with a searching instance) */
-    VSFilterDependency deps[1] = { { d->super, rpGeneral } };
-    vs->createVideoFilter(out, "AnalyseN", d->vi, consumerGetFrame, consumerFree, fmParallel, deps, 1, d, core);
+    VSFilterDependency deps[2] = { { d->super, rpGeneral }, { NULL, rpGeneral } };
+    int ndeps = 1;
+    { /* windows under mv.Analyse's conditions; their length is MVX_VS_MULTI_LOOKAHEAD frames (0 = off), unset the one that puts a Degrain3 graph's chains in flight */
+        SuperData *sd = super_lookup(d->super);
+        long A = env_long("MVX_VS_LOOKAHEAD", 128);
+        if (A > 512) A = 512;
+        const long B = getenv("MVX_VS_MULTI_LOOKAHEAD") ? env_long("MVX_VS_MULTI_LOOKAHEAD", 0) : mvx_win_default_length(d->mi.radius, A);
+        if (sd && !sd->pelMode && A > 0 && B > 0 && d->vi->numFrames > 1 && cache_cap() > 0) {
+            d->la.sd = sd; d->la.owner = d; d->la.numFrames = d->vi->numFrames; d->la.fo = &d->fo; d->la.enqueue = analyse_n_enqueue;
+            d->la.before = d->la.after = d->mi.radius; d->la.fixed = -1;
+            d->la.frameBytes = 2 * (size_t)d->mi.radius * (size_t)d->mi.stride;
+            /* a window pins its frames' and 2 * radius more super frames while it is searched, and its blobs stay in every slot that may be READY */
+            la_size(&d->la, B, (double)sd->geo.bytes * 1.2, (double)d->la.frameBytes, LA_SLOTS);
+        }
+        if (d->la.on) {
+            la_open(&d->la, sd->node, vs);
+            deps[1].source = d->la.srcNode; ndeps = 2;
+        }
+    }
+    vs->createVideoFilter(out, "AnalyseN", d->vi, d->la.on ? analyseNGetFrameWindows : consumerGetFrame, analyseNFree, fmParallel, deps, ndeps, d, core);
 }
 
 /* ---- mv.RecalculateN(super, vectors, ...): the radius is the clip's; one mvx_recalculate_n_frames call per frame */
