@@ -411,6 +411,54 @@ typedef struct mvx_recalculate_n_job {
  * HOST arrays, read before the call returns.  The bytes between a field's end and the next field are never written. */
 int mvx_recalculate_n_frames(mvx_recalculate_n *r, int njobs, const mvx_recalculate_n_job *jobs, void *stream);
 
+/* ---- mv.ScaleVect: the vectors of a small clip rewritten for a clip 1, 2 or 4 times its size --------------
+ * No reference counterpart: pinterf's MScaleVect is the model (search on a small clip, or on an 8-bit copy of a 16-bit clip, and use the
+ * vectors at full size).  The target clip is named by its mvx_super, so no consumer can be handed a vector that points outside that super
+ * clip's padding.  With s = scale, `in` the vectors' MVTools_MVAnalysisData and si the target's mvx_super_info, creation refuses, in this
+ * order:
+ *   "ScaleVect: scale must be 1, 2 or 4."
+ *   "ScaleVect: the target super clip must be scale times the size of the vectors' clip."    si.width != s * nWidth, si.height != s * nHeight or
+ *                                                                                            si.super_width - 2 * si.hpad != s * nWidth
+ *   "ScaleVect: the target super clip's chroma subsampling or colour data is not that of the vectors."   xRatioUV / yRatioUV differ, or the SADs
+ *                                                                                            include chroma (nMotionFlags) and the super clip carries none
+ *   "ScaleVect: the scaled block size must be 4x4, 8x4, ..."                                 s * nBlkSizeX x s * nBlkSizeY is not in mvx_recalculate_create's list
+ *   "ScaleVect: scale times the target's pel must be a multiple of the vectors' pel."        the vector factor m = s * si.pel / nPel is no positive integer
+ * The data of the scaled clip (mvx_scale_vect_get_data): nBlkSizeX/Y, nOverlapX/Y, nWidth and nHeight times s; nPel = si.pel; bitsPerSample =
+ * si.bits; nHPadding / nVPadding = si.hpad / si.vpad; every other field copied (magic key, version, nLvCount, nDeltaFrame, isBackward, both
+ * flag words, nBlkX/Y, the ratios).  It is what mvx_analyse_create reports on the target super clip with blksize * s, overlap * s and the
+ * same levels, isb and delta.  The block grid of EVERY level is that of `in`, so mvx_vectors_size is unchanged and a scaled blob has the
+ * layout of its input byte for byte (checked at creation).
+ * A blob whose validity word is 0 is copied.  In a valid blob the two header words and the per-level size words are copied and every
+ * record of every level becomes
+ *   x' = x * m, y' = y * m                     (in 64 bits)
+ *   sad' = sad * s * s << (si.bits - bitsPerSample)   (64-bit two's complement; an arithmetic shift to the right where the difference is negative)
+ * and on level 0 x' and y' are then clamped into the block's legal rectangle on the target super clip, -(pos + pad) * pel ..
+ * (size + pad - pos - blk) * pel - 1 per axis (PlaneOfBlocks.cpp's nDxMin .. nDxMax - 1).  The clamp changes nothing when the target's
+ * padding is at least s times the small clip's; when it is not it is what keeps Degrain, Compensate and Flow inside the super frame.
+ * Coarser levels are scaled and not clamped: no consumer of this header reads them.  The scaled SADs are ESTIMATES (a SAD of the small clip
+ * times the area ratio and the depth ratio): mvx_recalculate_frames at full size replaces them with true SADs and refines the vectors, which
+ * is the usual chain.  Vector clips made with divide > 0 are not supported: their level sizes are not those of the level formula.
+ * Touches no device at creation. */
+
+typedef struct mvx_scale_vect mvx_scale_vect;
+
+int mvx_scale_vect_create(const mvx_analysis_data *in, int scale, const mvx_super *target, mvx_scale_vect **out, char *err);
+void mvx_scale_vect_destroy(mvx_scale_vect *h);
+void mvx_scale_vect_get_data(const mvx_scale_vect *h, mvx_analysis_data *out); /* MVTools_MVAnalysisData of the scaled clip */
+
+typedef struct mvx_scale_vect_job {
+    const void *in;       /* device: a blob of mvx_vectors_size(in) bytes, or a multi blob; 4-byte aligned */
+    void *out;            /* device, as large as in; out == in scales in place, any other overlap is not allowed */
+    int32_t fields;       /* 1: an ordinary blob; 2 * radius: every field of a multi blob */
+    size_t field_stride;  /* of the multi blob, the same on both sides (a multiple of 4; unused when fields is 1); the bytes between a
+                             field's end and the next field are neither read nor written */
+} mvx_scale_vect_job;
+
+/* ONE launch for all fields of all jobs (csrc/mvx_scale_vect.hip), asynchronous on `stream`; `jobs` is a HOST array, read before the call
+ * returns.  As in RecalculateN a field's isBackward and nDeltaFrame only label its MVTools_MVAnalysisData: ONE object serves every field of
+ * a multi blob, and the caller reads the labels off the object that produced the field (mvx_analyse_n_get_data). */
+int mvx_scale_vect_frames(mvx_scale_vect *h, int njobs, const mvx_scale_vect_job *jobs, void *stream);
+
 /* ---- mv.BlockFPS ---------------------------------------------------------------------------------
  * replaces mvblockfpsCreate / mvblockfpsGetFrame, MVBlockFPS.c:741-1014 / :229-676 (arg string :1017-1033);
  * masks MaskFun.cpp:63-166, mask upsizer SimpleResize.cpp:27-121.                                     */

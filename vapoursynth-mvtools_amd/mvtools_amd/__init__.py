@@ -8,6 +8,7 @@
     (no reference name: one frame against a radius)   -> AnalyseN(super, radius, num_frames, ...)  .ad(r) .fields(multi_blob) .run(jobs)
                                                          CompensateN(tr, super, analysis_data, ...) .map(k) .run(jobs)
                                                          RecalculateN(super, analysis_data, radius, ...) .get_data(r) .run(jobs)
+    (no reference name: vectors of a small clip at full size) -> ScaleVect(analysis_data, super, scale) .ad .run(blobs)
     core.mv.FlowInter / FlowFPS(clip, super, mvbw, mvfw, ...) -> FlowInter / FlowFPS(super, bw_data, fw_data, ...) .run(ns, ...)
     core.mv.Flow(clip, super, vectors, ...)           -> Flow(super, analysis_data, ...)          .run(jobs)
     core.mv.FlowBlur(clip, super, mvbw, mvfw, ...)    -> FlowBlur(super, bw_data, fw_data, ...)   .run(ns, ...)
@@ -129,6 +130,10 @@ class RecalculateJob(C.Structure):
 class RecalculateNJob(C.Structure):
     _fields_ = [("src", C.c_void_p * 3), ("refs", C.POINTER(C.c_void_p * 3)), ("old_blob", C.c_void_p), ("old_field_stride", C.c_size_t),
                 ("blob", C.c_void_p)]
+
+
+class ScaleVectJob(C.Structure):
+    _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p), ("fields", C.c_int32), ("field_stride", C.c_size_t)]
 
 
 class BlockFPSArgs(C.Structure):
@@ -358,6 +363,11 @@ def lib():
             f.argtypes = [C.c_void_p]
             f.restype = C.c_size_t
         L.mvx_recalculate_n_frames.argtypes = [C.c_void_p, C.c_int, P(RecalculateNJob), C.c_void_p]
+        L.mvx_scale_vect_create.argtypes = [P(AnalysisData), C.c_int, C.c_void_p, P(C.c_void_p), C.c_char_p]
+        L.mvx_scale_vect_destroy.argtypes = [C.c_void_p]
+        L.mvx_scale_vect_get_data.argtypes = [C.c_void_p, P(AnalysisData)]
+        L.mvx_scale_vect_get_data.restype = None
+        L.mvx_scale_vect_frames.argtypes = [C.c_void_p, C.c_int, P(ScaleVectJob), C.c_void_p]
         L.mvx_blockfps_create.argtypes = [P(BlockFPSArgs), P(AnalysisData), P(AnalysisData), C.c_void_p, C.c_int, C.c_int64, C.c_int64, P(C.c_ssize_t),
                                           P(C.c_ssize_t), P(C.c_ssize_t), P(C.c_void_p), C.c_char_p]
         L.mvx_blockfps_destroy.argtypes = [C.c_void_p]
@@ -1756,6 +1766,50 @@ class RecalculateN(_Handle):
             arr[i].blob = blobs[i].data_ptr()
         _check(lib().mvx_recalculate_n_frames(self.h, n, arr, _stream()))
         return blobs
+
+
+class ScaleVect(_Handle):
+    """The blobs of a vector clip rewritten for a clip `scale` (1, 2 or 4) times its size (include/mvtools_amd.h, mv.ScaleVect): search on a small
+    or 8-bit clip, use the vectors on super_clip's.  vectors_data: the small clip's MVTools_MVAnalysisData; .ad: the scaled clip's, which is
+    what the consumers (Recalculate, Degrain, Compensate, ...) on super_clip are created with.  The SADs are estimates until a Recalculate."""
+    _destroy = "mvx_scale_vect_destroy"
+
+    def __init__(self, vectors_data, super_clip, scale=2):
+        self.sup = super_clip
+        self.scale = int(scale)
+        ad = AnalysisData.from_buffer_copy(bytes(vectors_data))
+        self.h = C.c_void_p()
+        err = C.create_string_buffer(ERRLEN)
+        _check(lib().mvx_scale_vect_create(C.byref(ad), self.scale, super_clip.h, C.byref(self.h), err), err)
+        self.ad = AnalysisData()
+        lib().mvx_scale_vect_get_data(self.h, C.byref(self.ad))
+        self.blob_size = lib().mvx_vectors_size(C.byref(self.ad))
+
+    def run(self, blobs, out=None, fields=1, field_stride=None):
+        """blobs: device blobs of the small clip, a list of tensors or the rows of one tensor; all of them in one launch -> the scaled blobs
+        (out: the tensors to write, which may be the inputs themselves; default: new ones, laid out like Analyse.alloc_blobs).  fields = 2 *
+        radius scales whole multi blobs: field_stride defaults to a blob's bytes / fields, and the bytes between the fields are not touched."""
+        torch = _torch()
+        blobs = list(blobs)
+        n, fields = len(blobs), int(fields)
+        if fields < 1:
+            raise ValueError("ScaleVect: fields must be at least 1")
+        stride = 0 if fields == 1 else int(field_stride) if field_stride is not None else blobs[0].numel() // fields
+        need = self.blob_size if fields == 1 else (fields - 1) * stride + self.blob_size
+        if out is None:
+            row = (self.blob_size + 255) // 256 * 256 if fields == 1 else fields * stride
+            buf = torch.zeros((n, row), dtype=torch.uint8, device=blobs[0].device)
+            out = [buf[i, :need] for i in range(n)]
+        out = list(out)
+        if len(out) != n:
+            raise ValueError("ScaleVect: %d blobs, %d outputs" % (n, len(out)))
+        arr = (ScaleVectJob * max(n, 1))()
+        for i, (b, o) in enumerate(zip(blobs, out)):
+            if b.numel() < need or o.numel() < need or not b.is_contiguous() or not o.is_contiguous():
+                raise ValueError("ScaleVect: a blob is a contiguous tensor of at least %d bytes" % need)
+            arr[i].in_, arr[i].out, arr[i].fields, arr[i].field_stride = b.data_ptr(), o.data_ptr(), fields, stride
+        _check(lib().mvx_scale_vect_frames(self.h, n, arr, _stream()))
+        return out
 
 
 def scdetect(analysis_data, blobs, thscd1=None, thscd2=None):
