@@ -641,7 +641,23 @@ int mvx_flowblur_frames(mvx_flowblur *h, int nframes, const mvx_flowblur_job *jo
  *   2. a clip whose size or chroma ratios differ from the vector clip's nWidth / nHeight / xRatioUV / yRatioUV (Gray counts as
  *      1 / 1): the reference does not check this, and then writes planes of the wrong size;
  *   3. (not rejected) where 255 * pow(...) of the occlusion mask exceeds the int range the reference's cast is undefined -- on
- *      x86 it yields INT_MIN, so the cell keeps its old value; the library saturates: the cell becomes 255. */
+ *      x86 it yields INT_MIN, so the cell keeps its old value; the library saturates: the cell becomes 255.
+ *
+ * Deep masks (mvx_mask_create_deep): a clip of B = 9..16 bits gives three planes of B bits in 16-bit containers, so that a mask can be
+ * merged by at the depth of the clip it was made for.  The semantics are the library's own; the reference refuses such clips
+ * (MVMask.c:321), and no parity with any other MVTools is claimed.  With s = B - 8:
+ *   - the block-resolution masks stay bytes, computed as above, except that kind 1 shifts the int64 SAD right by s (arithmetic) before
+ *     it becomes a double: MakeSADMaskTime's own `sad >> (bitsPerSample - 8)`, MaskFun.cpp:162, which the reference's format check
+ *     keeps from ever seeing anything but 0.  s comes from the clip argument; the vector clip's depth is not consulted (nor is it by
+ *     mvx_mask_create, which never shifts: a 16-bit vector clip's SADs saturate an 8-bit mask);
+ *   - the upsizer, its tables, the edge replication and the usability test work on bytes and give an 8-bit value m per sample;
+ *   - each sample is stored as E(m).  Kinds 0-2 are weights, full at the clip's peak as merging filters read them, so they replicate
+ *     their bits: E(m) = m << s | m >> (8 - s), monotone, 0 -> 0, 255 -> 2^B - 1.  Kinds 3-4 and kind 5's U and V are offsets from a
+ *     neutral value, so they scale: E(m) = m << s, 128 -> 2^(B-1).  Two rules, because a replicated 128 would no longer be neutral and a
+ *     scaled 255 would no longer be full.  Kind 5's luma is the clip's own, two bytes a sample;
+ *   - ysc stays 0..255, in 8-bit units: an unusable frame is filled with E(ysc) by the rule of the plane filled.
+ * Pitches are in bytes (clip_pitch[0] too), dst planes 16-byte aligned; only the samples are written, two bytes each.  At B = 8 a deep
+ * object behaves byte for byte like mvx_mask_create's. */
 
 typedef struct mvx_mask_args {
     double ml, gamma;        /* pass 100.0 / 1.0 for the defaults; float arguments in the reference: every factor is formed in float */
@@ -654,7 +670,7 @@ typedef struct mvx_mask_args {
 /* the format of the clip argument (VSVideoInfo) */
 typedef struct mvx_mask_clip { int32_t width, height, bits, subsampling_w, subsampling_h, gray; } mvx_mask_clip;
 
-/* the output clip: always 3 planes of 8 bits; a Gray input gives 4:4:4 (MVMask.c:328-329).  The remaining fields are what creation
+/* the output clip: always 3 planes, of 8 bits (of mvx_mask_out_bits for a deep object); a Gray input gives 4:4:4 (MVMask.c:328-329).  The remaining fields are what creation
  * derived from the arguments (MVMask.c:304-307,334), for hosts and tests that want to see the rounding. */
 typedef struct mvx_mask_info {
     int32_t width, height, subsampling_w, subsampling_h, num_planes;
@@ -668,12 +684,19 @@ typedef struct mvx_mask mvx_mask;
 /* clip_pitch[0]: row pitch of the clip's luma plane (read by kind 5 only); dst_pitch: multiples of 16 bytes, U and V alike */
 int mvx_mask_create(const mvx_mask_args *args, const mvx_analysis_data *vectors, const mvx_mask_clip *clip, const ptrdiff_t clip_pitch[3],
                     const ptrdiff_t dst_pitch[3], mvx_mask **out, char *err);
+/* the same checks in the same order with the same messages, except the format check: 8 to 16 bits, subsampling 0..1 on each axis, else
+ * "Mask: input clip must be Gray or YUV (4:2:0, 4:2:2, 4:4:0, 4:4:4) of 8 to 16 bits, with constant dimensions."  The output has the
+ * clip's depth (see "Deep masks" above); mvx_mask_info keeps its layout and describes the planes in samples. */
+int mvx_mask_create_deep(const mvx_mask_args *args, const mvx_analysis_data *vectors, const mvx_mask_clip *clip, const ptrdiff_t clip_pitch[3],
+                         const ptrdiff_t dst_pitch[3], mvx_mask **out, char *err);
+/* bits per sample of the planes mvx_mask_frames writes: 8, or a deep object's clip depth (above 8: 16-bit containers) */
+int mvx_mask_out_bits(const mvx_mask *m);
 void mvx_mask_destroy(mvx_mask *m);
 void mvx_mask_get_info(const mvx_mask *m, mvx_mask_info *info);
 
 typedef struct mvx_mask_job {
     const void *blob;        /* vectors at n; NULL = unusable */
-    const void *clip_luma;   /* luma plane of clip frame n; read by kind 5 only */
+    const void *clip_luma;   /* luma plane of clip frame n; read by kind 5 only (a deep object above 8 bits: 16-bit samples) */
     void *dst[3];            /* 16-byte aligned */
 } mvx_mask_job;
 

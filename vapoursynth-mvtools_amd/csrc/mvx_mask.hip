@@ -11,6 +11,9 @@
 //                        (row-by-row vsh_bitblt semantics: every row below nHeightB - 1 equals it, after its right fill); V = U, the
 //                        scene-change fill and kind 5's luma copy are cases of the same kernel.  One launch for the luma planes of all
 //                        jobs, one for both chroma planes of all jobs.
+// Deep objects (mvx_mask_create_deep, 9 to 16 bits; include/mvtools_amd.h has the semantics): the small masks stay bytes, kind 1 from the SAD >> (bits - 8)
+// (mask_small_kernel<4, true>); mask_planes_kernel<CLS, 1> does a lane's work unchanged up to its 16 bytes and stores them as 16 samples of 16 bits.
+// The instantiations <.., false> and <.., 0> are the 8-bit kernels, instruction for instruction what they were before the deep forms existed.
 // pow: the device's double-precision pow where the exponent is not exactly 1; at exponent 1 the base itself (mvx_degrain.hip's SAD mask
 // does the same), so kinds 1 and 2 at the default gamma 1 (and kind 0 at gamma 2) are exact whatever the two pow implementations do in the
 // last place.  Kind 0 at gamma 1 is pow(x, 0.5): see DESIGN.md 4.9 for what that means for a byte.
@@ -29,6 +32,7 @@ struct MKParams {
     int W[2], H[2], segs[2];              // luma / chroma plane size, 16-byte segments per row
     long long dstPitch[3], clipPitch;
     const unsigned *hTab[2], *vTab[2];    // per output column / row: small-mask offset << 16 | weight of the second cell (0..16384)
+    int shift;                            // deep objects: the output depth - 8 (0..8); 0 otherwise.  Last, so that every earlier field keeps its offset
 };
 struct MKJob { const unsigned char *blob, *clip; unsigned char *dst[3]; };
 
@@ -72,7 +76,8 @@ __device__ __forceinline__ unsigned char mk_component(int v, float f) { return (
 // store); the four 16-byte vector records are loaded together.  NB = 1 is kind 2's form: it stores nothing here, and four scatters per lane
 // only lengthen the chain of atomics (measured: 0.152 -> 0.179 ms per 64 frames).  A plane holds P.stride bytes, nBlk rounded up to 16, so
 // every job's planes are aligned.
-template <int NB>
+// SH: the deep form of kind 1, MaskFun.cpp:162 with bitsPerSample the clip argument's: the int64 SAD >> P.shift (arithmetic) before it becomes a double
+template <int NB, bool SH>
 __global__ __launch_bounds__(256) void mask_small_kernel(const MKParams *Pp, const MKJob *jobs, const int *over, unsigned char *small, int *occ) {
     const MKParams &P = *Pp;
     const int f = blockIdx.y;
@@ -99,7 +104,7 @@ __global__ __launch_bounds__(256) void mask_small_kernel(const MKParams *Pp, con
             const int tX = (256 - P.time256) * 16 / (P.stepX * P.pel), tY = (256 - P.time256) * 16 / (P.stepY * P.pel);
             int bxi = bx - vx[k] * tX / 4096, byi = by - vy[k] * tY / 4096;
             if (bxi < 0 || bxi >= nBlkX || byi < 0 || byi >= nBlkY) { bxi = bx; byi = by; }
-            const long long sad = vec[bxi + byi * nBlkX].sad;
+            const long long sad = SH ? vec[bxi + byi * nBlkX].sad >> P.shift : vec[bxi + byi * nBlkX].sad;
             c = mk_cut(255 * mk_pow(sad * P.sadFactor, P.gamma));
         } else if (P.kind == 2) {
             fps_occlusion_block(vec, i, bx, by, nBlkX, nBlkY, P.isb, P.time256, P.stepX, P.stepY, P.pel, P.occDivider, occ + (size_t)f * P.stride, nBlkX, P.gamma);
@@ -135,6 +140,37 @@ __device__ __forceinline__ void mk_store(DG_GL unsigned char *d, unsigned long l
     if (n & 4) { *(DG_GL unsigned *)(d + o) = (unsigned)r; r >>= 32; o += 4; }
     if (n & 2) { *(DG_GL unsigned short *)(d + o) = (unsigned short)r; r >>= 16; o += 2; }
     if (n & 1) d[o] = (unsigned char)r;
+}
+
+// The deep forms.  mk_widen: four bytes of w as four 16-bit samples E(m) in two dwords, E(m) = m << shl | m >> shr on every 16-bit lane.  A weight
+// (kinds 0-2) replicates its bits, shr = 8 - shl: 0 stays 0 and 255 becomes the peak; an offset (kinds 3-5) passes shr = 8, m >> 8 = 0: 128 becomes half
+// the range.  m << shl stays inside its lane (255 << 8 < 65536); m >> shr lets bits of the upper lane into the lower one, which the mask removes.
+__device__ __forceinline__ void mk_widen(unsigned w, int shl, int shr, unsigned &a, unsigned &b) {
+    const unsigned p = __builtin_amdgcn_perm(0u, w, 0x0c010c00u), q = __builtin_amdgcn_perm(0u, w, 0x0c030c02u);
+    a = (p << shl) | ((p >> shr) & 0x00ff00ffu);
+    b = (q << shl) | ((q >> shr) & 0x00ff00ffu);
+}
+// n (1..16) 16-bit samples, four per q, to the 16-byte aligned address d: two adjacent vector stores, or for a row's tail the pieces 8 / 4 / 2 / 1 of
+// n, each aligned
+__device__ __forceinline__ void mk_store16(DG_GL unsigned char *d, unsigned long long q0, unsigned long long q1, unsigned long long q2, unsigned long long q3, int n) {
+    if (n == 16) {
+        const dg_iv4 t = { (int)q0, (int)(q0 >> 32), (int)q1, (int)(q1 >> 32) }, u = { (int)q2, (int)(q2 >> 32), (int)q3, (int)(q3 >> 32) };
+        *(DG_GL dg_iv4 *)d = t; *(DG_GL dg_iv4 *)(d + 16) = u;
+        return;
+    }
+    unsigned long long a = q0, b = q1; // the samples not yet stored: the next four, and the four after them
+    int o = 0;
+    if (n & 8) { const dg_iv4 t = { (int)q0, (int)(q0 >> 32), (int)q1, (int)(q1 >> 32) }; *(DG_GL dg_iv4 *)d = t; a = q2; b = q3; o = 16; }
+    if (n & 4) { const dg_iv2 t = { (int)a, (int)(a >> 32) }; *(DG_GL dg_iv2 *)(d + o) = t; a = b; o += 8; }
+    if (n & 2) { *(DG_GL unsigned *)(d + o) = (unsigned)a; a >>= 32; o += 4; }
+    if (n & 1) *(DG_GL unsigned short *)(d + o) = (unsigned short)a;
+}
+// the 16 bytes w of one segment of a row, widened to n samples at d
+__device__ __forceinline__ void mk_store_wide(DG_GL unsigned char *d, const unsigned *w, int n, int shl, int shr) {
+    unsigned e[8];
+#pragma unroll
+    for (int k = 0; k < 4; k++) mk_widen(w[k], shl, shr, e[2 * k], e[2 * k + 1]);
+    mk_store16(d, e[0] | (unsigned long long)e[1] << 32, e[2] | (unsigned long long)e[3] << 32, e[4] | (unsigned long long)e[5] << 32, e[6] | (unsigned long long)e[7] << 32, n);
 }
 
 // 16 bytes from any address as four dwords: aligned dword loads (gfx950 serves vector loads at odd addresses several times slower) and a
@@ -185,8 +221,10 @@ __device__ __forceinline__ unsigned mk_sample(unsigned lo, unsigned hi, int c, u
 // A lane produces the same 16-byte segment of MK_ROWS consecutive rows.  With one row per lane the kernel is bound by latency, not by the
 // stores: a wave lives for four dependent memory round trips (job, usable, tables, cells) and moves 1 KB.  The rows of a lane share the
 // horizontal table entries and the usable test, and their cell loads are all in flight together.
+// DEEP: the form for 16-bit samples.  A lane's work is the same up to the 16 bytes it would store; they leave as 16 samples E(m), two adjacent
+// 16-byte stores per row (a wave: 2 KB contiguous), the fill as E(ysc), and kind 5's luma is copied two bytes a sample.
 #define MK_ROWS 4
-template <int CLS>
+template <int CLS, int DEEP>
 __global__ __launch_bounds__(256) void mask_planes_kernel(const MKParams *Pp, const MKJob *jobs, const int *over, const unsigned char *small) {
     const MKParams &P = *Pp;
     const int f = CLS ? blockIdx.y >> 1 : blockIdx.y, pl = CLS ? 1 + (blockIdx.y & 1) : 0;
@@ -197,8 +235,33 @@ __global__ __launch_bounds__(256) void mask_planes_kernel(const MKParams *Pp, co
     const MKJob &J = jobs[f];
     const int x0 = 16 * s, n = min(16, P.W[CLS] - x0);
     const long long pitch = P.dstPitch[pl];
-    DG_GL unsigned char *d = dg_glw(J.dst[pl]) + (long long)y0 * pitch + x0;
-    if (CLS == 0 && P.kind == 5) { // MVMask.c:160-161,194-195: the clip's luma, usable or not
+    DG_GL unsigned char *d = dg_glw(J.dst[pl]) + (long long)y0 * pitch + (DEEP ? 2 * x0 : x0);
+    const int shl = DEEP ? P.shift : 0, shr = DEEP && P.kind <= 2 ? 8 - shl : 8; // mk_widen: a weight for kinds 0-2, an offset for kinds 3-5
+    if (DEEP && CLS == 0 && P.kind == 5) { // the clip's luma at its own depth
+        DG_GL const unsigned char *c = dg_gl(J.clip) + (long long)y0 * P.clipPitch + 2 * x0;
+        unsigned w[MK_ROWS][8];
+#pragma unroll
+        for (int r = 0; r < MK_ROWS; r++) {
+#pragma unroll
+            for (int k = 0; k < 8; k++) w[r][k] = 0;
+            if (y0 + r >= H) continue;
+            DG_GL const unsigned char *cr = c + r * P.clipPitch;
+            if (n == 16) {
+                const dg_uv4 t = *(DG_GL const dg_uv4 *)cr, u = *(DG_GL const dg_uv4 *)(cr + 16);
+#pragma unroll
+                for (int k = 0; k < 4; k++) { w[r][k] = t[k]; w[r][4 + k] = u[k]; }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 15; i++) if (i < n) w[r][i >> 1] |= (unsigned)*(DG_GL const dg_uh1 *)(cr + 2 * i) << (16 * (i & 1));
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < MK_ROWS; r++)
+            if (y0 + r < H) mk_store16(d + r * pitch, w[r][0] | (unsigned long long)w[r][1] << 32, w[r][2] | (unsigned long long)w[r][3] << 32,
+                                       w[r][4] | (unsigned long long)w[r][5] << 32, w[r][6] | (unsigned long long)w[r][7] << 32, n);
+        return;
+    }
+    if (!DEEP && CLS == 0 && P.kind == 5) { // MVMask.c:160-161,194-195: the clip's luma, usable or not
         DG_GL const unsigned char *c = dg_gl(J.clip) + (long long)y0 * P.clipPitch + x0;
         unsigned w[MK_ROWS][4];
 #pragma unroll
@@ -219,6 +282,13 @@ __global__ __launch_bounds__(256) void mask_planes_kernel(const MKParams *Pp, co
     }
     if (!mk_usable(P, J.blob, over + f * MK_SLICES)) { // MVMask.c:197-200
         const unsigned long long fill = (unsigned)P.ysc * 0x0101010101010101ull;
+        if (DEEP) { // E(ysc) by the plane's rule
+            const unsigned long long fill16 = (unsigned long long)((unsigned)P.ysc << shl | (unsigned)P.ysc >> shr) * 0x0001000100010001ull;
+#pragma unroll
+            for (int r = 0; r < MK_ROWS; r++)
+                if (y0 + r < H) mk_store16(d + r * pitch, fill16, fill16, fill16, fill16, n);
+            return;
+        }
 #pragma unroll
         for (int r = 0; r < MK_ROWS; r++)
             if (y0 + r < H) mk_store(d + r * pitch, fill, fill, n);
@@ -253,7 +323,8 @@ __global__ __launch_bounds__(256) void mask_planes_kernel(const MKParams *Pp, co
             mk_vertical<2>(t[r], u[r], wv[r], v);
 #pragma unroll
             for (int i = 0; i < 16; i++) w[i >> 2] |= mk_sample(v[0], v[1], (int)(e[i] >> 16) - oF, e[i] & 0xffffu) << (8 * (i & 3));
-            if (y0 + r < H) mk_store(d + r * pitch, w[0] | (unsigned long long)w[1] << 32, w[2] | (unsigned long long)w[3] << 32, n);
+            if (DEEP) { if (y0 + r < H) mk_store_wide(d + r * pitch, w, n, shl, shr); }
+            else if (y0 + r < H) mk_store(d + r * pitch, w[0] | (unsigned long long)w[1] << 32, w[2] | (unsigned long long)w[3] << 32, n);
         }
     } else if (o7 - oF <= 6 && oL - o8 <= 6 && o8 - oF <= 8) { // at most 16 cells, each half at most 8: a window per half
         unsigned t[MK_ROWS][4], u[MK_ROWS][4];
@@ -270,7 +341,8 @@ __global__ __launch_bounds__(256) void mask_planes_kernel(const MKParams *Pp, co
             for (int i = 0; i < 8; i++) w[i >> 2] |= mk_sample(v[0], v[1], (int)(e[i] >> 16) - oF, e[i] & 0xffffu) << (8 * (i & 3));
 #pragma unroll
             for (int i = 8; i < 16; i++) w[i >> 2] |= mk_sample(x0w, x1w, (int)(e[i] >> 16) - o8, e[i] & 0xffffu) << (8 * (i & 3));
-            if (y0 + r < H) mk_store(d + r * pitch, w[0] | (unsigned long long)w[1] << 32, w[2] | (unsigned long long)w[3] << 32, n);
+            if (DEEP) { if (y0 + r < H) mk_store_wide(d + r * pitch, w, n, shl, shr); }
+            else if (y0 + r < H) mk_store(d + r * pitch, w[0] | (unsigned long long)w[1] << 32, w[2] | (unsigned long long)w[3] << 32, n);
         }
     } else {
         // SimpleResize.cpp:62-121 at any geometry: the vertical pass rounded to a byte per small-mask column, then the horizontal pass; a
@@ -290,10 +362,12 @@ __global__ __launch_bounds__(256) void mask_planes_kernel(const MKParams *Pp, co
                 }
                 w[i >> 2] |= (unsigned)(unsigned char)((a * (16384 - wr) + b * wr + 8192) >> 14) << (8 * (i & 3));
             }
-            mk_store(d + r * pitch, w[0] | (unsigned long long)w[1] << 32, w[2] | (unsigned long long)w[3] << 32, n);
+            if (DEEP) mk_store_wide(d + r * pitch, w, n, shl, shr);
+            else mk_store(d + r * pitch, w[0] | (unsigned long long)w[1] << 32, w[2] | (unsigned long long)w[3] << 32, n);
         }
     }
 }
+
 
 // ------------------------------------------------------------------------------------------------ host object
 
@@ -301,7 +375,8 @@ struct mvx_mask {
     CallGuard guard;
     MKParams P;
     mvx_mask_info info;
-    std::vector<unsigned> tables;        // hTab luma, vTab luma, hTab chroma, vTab chroma
+    int bits;                            // of the output samples: 8, or a deep object's 9..16 (two bytes a sample)
+    std::vector<unsigned> tables;       // hTab luma, vTab luma, hTab chroma, vTab chroma
     size_t tabOff[4];
     DevBuf<MKParams> dP;
     DevBuf<unsigned> dTables;
@@ -321,9 +396,9 @@ static void mask_table(unsigned *t, int padded, int size, int covered, int in) {
     }
 }
 
-// MVMask.c:227-346 mvmaskCreate
-extern "C" __attribute__((visibility("default"))) int mvx_mask_create(const mvx_mask_args *a, const mvx_analysis_data *ad, const mvx_mask_clip *clip,
-        const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_mask **out, char *err) {
+// MVMask.c:227-346 mvmaskCreate.  deep: the format check of mvx_mask_create_deep, and an output of the clip's depth
+static int mask_create(const mvx_mask_args *a, const mvx_analysis_data *ad, const mvx_mask_clip *clip, const ptrdiff_t clip_pitch[3],
+        const ptrdiff_t dst_pitch[3], mvx_mask **out, char *err, bool deep) {
     MVX_CREATE_BEGIN(out);
     const float ml = (float)a->ml, fGamma = (float)a->gamma;   // float arguments (MVMask.c:235-241)
     const int kind = a->kind == MVX_UNSET ? 0 : a->kind;
@@ -335,7 +410,10 @@ extern "C" __attribute__((visibility("default"))) int mvx_mask_create(const mvx_
     if (time < 0.0 || time > 100.0) MVX_FAIL("Mask: time must be between 0.0 and 100.0 (inclusive).");
     if (ysc < 0 || ysc > 255) MVX_FAIL("Mask: ysc must be between 0 and 255 (inclusive).");
     if (int rc = mvx_resolve_thscd("Mask", a->thscd1, a->thscd2, ad, &thscd1, &thscd2, err)) return rc;
-    if (clip->bits > 8 || clip->subsampling_w > 1 || clip->subsampling_h > 1 || clip->subsampling_w < 0 || clip->subsampling_h < 0)
+    const bool subOk = clip->subsampling_w >= 0 && clip->subsampling_w <= 1 && clip->subsampling_h >= 0 && clip->subsampling_h <= 1;
+    if (deep && (clip->bits < 8 || clip->bits > 16 || !subOk))
+        MVX_FAIL("Mask: input clip must be Gray or YUV (4:2:0, 4:2:2, 4:4:0, 4:4:4) of 8 to 16 bits, with constant dimensions.");
+    if (!deep && (clip->bits > 8 || !subOk))
         MVX_FAIL("Mask: input clip must be GRAY8, YUV420P8, YUV422P8, YUV440P8, or YUV444P8, with constant dimensions.");
     // the library's own checks (divergences 1 and 2 of mvtools_amd.h)
     if (ad->nBlkX < 2 || ad->nBlkY < 2) MVX_FAIL("Mask: the frame must be at least two blocks wide and two blocks high.");
@@ -381,9 +459,20 @@ extern "C" __attribute__((visibility("default"))) int mvx_mask_create(const mvx_
     I.subsampling_w = clip->gray ? 0 : clip->subsampling_w; I.subsampling_h = clip->gray ? 0 : clip->subsampling_h;
     for (int p = 0; p < 3; p++) { I.plane_width[p] = P.W[p ? 1 : 0]; I.plane_height[p] = P.H[p ? 1 : 0]; }
     I.time256 = P.time256; I.fMaskNormFactor = P.fNorm; I.fMaskNormFactor2 = P.fNorm2; I.fHalfGamma = P.fHalfGamma;
+    h->bits = deep ? clip->bits : 8;
+    P.shift = h->bits - 8;
     *out = h;
     return MVX_OK;
 }
+extern "C" __attribute__((visibility("default"))) int mvx_mask_create(const mvx_mask_args *a, const mvx_analysis_data *ad, const mvx_mask_clip *clip,
+        const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_mask **out, char *err) {
+    return mask_create(a, ad, clip, clip_pitch, dst_pitch, out, err, false);
+}
+extern "C" __attribute__((visibility("default"))) int mvx_mask_create_deep(const mvx_mask_args *a, const mvx_analysis_data *ad, const mvx_mask_clip *clip,
+        const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_mask **out, char *err) {
+    return mask_create(a, ad, clip, clip_pitch, dst_pitch, out, err, true);
+}
+extern "C" __attribute__((visibility("default"))) int mvx_mask_out_bits(const mvx_mask *h) { return h->bits; }
 extern "C" __attribute__((visibility("default"))) void mvx_mask_destroy(mvx_mask *h) { delete h; }
 extern "C" __attribute__((visibility("default"))) void mvx_mask_get_info(const mvx_mask *h, mvx_mask_info *info) { *info = h->info; }
 
@@ -421,13 +510,19 @@ extern "C" __attribute__((visibility("default"))) int mvx_mask_frames(mvx_mask *
     const dim3 perBlock((unsigned)(((P.nBlk + 3) / 4 + 255) / 256), (unsigned)nframes); // four blocks per lane
     hipLaunchKernelGGL(mask_usable_kernel, dim3(MK_SLICES, (unsigned)nframes), dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dOver.p);
     if (P.kind == 2) HIP_CHECK(hipMemsetAsync(h->dOcc.p, 0, n * P.stride * sizeof(int), st));
-    if (P.kind == 2) hipLaunchKernelGGL((mask_small_kernel<1>), dim3((unsigned)((P.nBlk + 255) / 256), (unsigned)nframes), dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dOver.p, h->dSmall.p, h->dOcc.p);
-    else hipLaunchKernelGGL((mask_small_kernel<4>), perBlock, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dOver.p, h->dSmall.p, h->dOcc.p);
+    if (P.kind == 2) hipLaunchKernelGGL((mask_small_kernel<1, false>), dim3((unsigned)((P.nBlk + 255) / 256), (unsigned)nframes), dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dOver.p, h->dSmall.p, h->dOcc.p);
+    else if (P.kind == 1 && P.shift) hipLaunchKernelGGL((mask_small_kernel<4, true>), perBlock, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dOver.p, h->dSmall.p, h->dOcc.p);
+    else hipLaunchKernelGGL((mask_small_kernel<4, false>), perBlock, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dOver.p, h->dSmall.p, h->dOcc.p);
     if (P.kind == 2) hipLaunchKernelGGL(mask_occ_finish_kernel, perBlock, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dOver.p, h->dOcc.p, h->dSmall.p);
-    hipLaunchKernelGGL((mask_planes_kernel<0>), dim3((unsigned)(((long long)P.segs[0] * ((P.H[0] + MK_ROWS - 1) / MK_ROWS) + 255) / 256), (unsigned)nframes), dim3(256), 0, st,
-                       h->dP.p, h->dJobs.p, h->dOver.p, h->dSmall.p);
-    hipLaunchKernelGGL((mask_planes_kernel<1>), dim3((unsigned)(((long long)P.segs[1] * ((P.H[1] + MK_ROWS - 1) / MK_ROWS) + 255) / 256), (unsigned)nframes * 2), dim3(256), 0, st,
-                       h->dP.p, h->dJobs.p, h->dOver.p, h->dSmall.p);
+    const dim3 lumaGrid((unsigned)(((long long)P.segs[0] * ((P.H[0] + MK_ROWS - 1) / MK_ROWS) + 255) / 256), (unsigned)nframes);
+    const dim3 chromaGrid((unsigned)(((long long)P.segs[1] * ((P.H[1] + MK_ROWS - 1) / MK_ROWS) + 255) / 256), (unsigned)nframes * 2);
+    if (h->bits > 8) { // a lane's segment is 16 samples in either form: the same grids
+        hipLaunchKernelGGL((mask_planes_kernel<0, 1>), lumaGrid, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dOver.p, h->dSmall.p);
+        hipLaunchKernelGGL((mask_planes_kernel<1, 1>), chromaGrid, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dOver.p, h->dSmall.p);
+    } else {
+        hipLaunchKernelGGL((mask_planes_kernel<0, 0>), lumaGrid, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dOver.p, h->dSmall.p);
+        hipLaunchKernelGGL((mask_planes_kernel<1, 0>), chromaGrid, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dOver.p, h->dSmall.p);
+    }
     HIP_CHECK(hipGetLastError());
     return MVX_OK;
 }

@@ -392,6 +392,8 @@ def lib():
         L.mvx_flowblur_destroy.argtypes = [C.c_void_p]
         L.mvx_flowblur_frames.argtypes = [C.c_void_p, C.c_int, P(FlowBlurJob), C.c_void_p]
         L.mvx_mask_create.argtypes = [P(MaskArgs), P(AnalysisData), P(MaskClip), P(C.c_ssize_t), P(C.c_ssize_t), P(C.c_void_p), C.c_char_p]
+        L.mvx_mask_create_deep.argtypes = L.mvx_mask_create.argtypes
+        L.mvx_mask_out_bits.argtypes = [C.c_void_p]
         L.mvx_mask_destroy.argtypes = [C.c_void_p]
         L.mvx_mask_get_info.argtypes = [C.c_void_p, P(MaskInfo)]
         L.mvx_mask_get_info.restype = None
@@ -1298,26 +1300,38 @@ class Mask(_Handle):
     """mv.Mask(clip, vectors, ml, gamma, kind, time, ysc, thscd1, thscd2) -- MVMask.c:227-346.  `width` / `height` / `subsampling` / `gray` /
     `bits` describe the clip argument (which must have the vector clip's geometry); the output is always three 8-bit planes, 4:4:4 for a
     Gray clip.  `clip_pitch` is the row pitch of the clip's device planes (only the luma plane is read, by kind 5); `dst_pitch` the row
-    pitches of the output planes (multiples of 16 bytes; default: the plane widths rounded up to 256)."""
+    pitches of the output planes (multiples of 16 bytes; default: the plane widths rounded up to 256).
+    deep: mvx_mask_create_deep -- a clip of 8 to 16 bits gives planes of its own depth (`out_bits`): above 8 bits run() returns planes of uint16
+    samples (byte tensors with rows of 16-bit samples, as everywhere in this package: plane_to_numpy(plane, width, np.uint16)) and kind 5 takes
+    the clip's 16-bit luma; all pitches are in bytes, and the defaults are rows of 16-bit samples rounded up to 256 bytes.  ysc stays 0..255.
+    include/mvtools_amd.h has the semantics: kinds 0-2 replicate their bits up to the clip's peak, kinds 3-5 scale around the neutral value, and
+    kind 1 shifts the SAD right by bits - 8."""
     _destroy = "mvx_mask_destroy"
 
     def __init__(self, vectors_ad, width, height, subsampling=(1, 1), gray=False, clip_pitch=None, dst_pitch=None, bits=8, ml=100.0, gamma=1.0,
-                 kind=None, time=100.0, ysc=None, thscd1=None, thscd2=None):
+                 kind=None, time=100.0, ysc=None, thscd1=None, thscd2=None, deep=False):
         a = MaskArgs(float(ml), float(gamma), _u(kind), float(time), _u(ysc), _u(thscd1), _u(thscd2))
         ad = AnalysisData.from_buffer_copy(bytes(vectors_ad))
         c = MaskClip(int(width), int(height), int(bits), int(subsampling[0]), int(subsampling[1]), int(bool(gray)))
         sw, sh = (0, 0) if gray else subsampling
         if dst_pitch is None:
-            dst_pitch = [((max(int(width) >> s, 1) + 255) // 256) * 256 for s in (0, sw, sw)]
+            bps = 2 if deep and int(bits) > 8 else 1
+            dst_pitch = [((max(int(width) >> s, 1) * bps + 255) // 256) * 256 for s in (0, sw, sw)]
         if clip_pitch is None:
             clip_pitch = [dst_pitch[0]]
         self.h = C.c_void_p()
         self.kind = 0 if kind is None else int(kind)
         self.pitch = list(dst_pitch)
         err = C.create_string_buffer(ERRLEN)
-        _check(lib().mvx_mask_create(C.byref(a), C.byref(ad), C.byref(c), _pad3(clip_pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
+        create = lib().mvx_mask_create_deep if deep else lib().mvx_mask_create
+        _check(create(C.byref(a), C.byref(ad), C.byref(c), _pad3(clip_pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
         self.info = MaskInfo()
         lib().mvx_mask_get_info(self.h, C.byref(self.info))
+
+    @property
+    def out_bits(self):
+        """bits per sample of the planes run() writes: 8, or with deep the clip's depth"""
+        return lib().mvx_mask_out_bits(self.h)
 
     def alloc(self, n, device="cuda"):
         """n output frames of three planes with this filter's pitches (contents undefined)"""

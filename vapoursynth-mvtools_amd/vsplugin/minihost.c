@@ -925,6 +925,9 @@ static int host_main(int argc, char **argv) {
             isFlowFps = 1; outFrames = out->vi.numFrames;
             printf("flowfps frames=%d fps=%lld/%lld\n", out->vi.numFrames, (long long)out->vi.fpsNum, (long long)out->vi.fpsDen);
         }
+        if (out && !strcmp(flowFilter, "Mask")) /* the mask clip's own format: with MVX_VS_MASK_DEEP=1 it has the clip's depth */
+            printf("mask format family=%s bits=%d bytes=%d ssw=%d ssh=%d planes=%d\n", out->vi.format.colorFamily == cfYUV ? "yuv" : "other", out->vi.format.bitsPerSample,
+                   out->vi.format.bytesPerSample, out->vi.format.subSamplingW, out->vi.format.subSamplingH, out->vi.format.numPlanes);
     }
     else {
         static const char *vn[] = { "mvbw", "mvfw", "mvbw2", "mvfw2", "mvbw3", "mvfw3", "mvbw4", "mvfw4", "mvbw5", "mvfw5", "mvbw6", "mvfw6" };

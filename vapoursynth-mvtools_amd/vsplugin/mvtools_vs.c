@@ -8,7 +8,7 @@
  *     Recalculate (src/MVRecalculate.c:549-572)   Finest (src/MVFinest.c:213-218)   SCDetection (src/MVSCDetection.c:137-145)
  * and, when the host's environment has MVX_VS_FLOW=1 as the plugin is loaded, the per-sample filters
  *     FlowInter (src/MVFlowInter.c:700-710)   FlowFPS (src/MVFlowFPS.c:913-925)   Flow (src/MVFlow.cpp:597-607)
- *     FlowBlur  (src/MVFlowBlur.c:555-565)    Mask    (src/MVMask.c:350-360)
+ *     FlowBlur  (src/MVFlowBlur.c:555-565)    Mask    (src/MVMask.c:350-360; with MVX_VS_MASK_DEEP=1 as well: clips of 9 to 16 bits, masks of the clip's depth)
  * and, with MVX_VS_DEPAN=1, the global-motion filters (src/MVDepan.cpp:4211-4288)
  *     DepanAnalyse   DepanEstimate   DepanCompensate   DepanStabilise
  * and, with MVX_VS_MULTI=1, the temporal-radius filters over the multi vector clip (no reference counterpart; see their section)
@@ -2595,7 +2595,11 @@ static void VS_CC blurCreate(const VSMap *in, VSMap *out, void *user, VSCore *co
 
 /* ------------------------------------------------------------------------------------------------ mv.Mask */
 
-typedef struct MaskData { Consumer c; VSNode *node, *vectors; const VSVideoInfo *clipvi; VSVideoInfo vi; mvx_mask *mk; mvx_mask_info info; mvx_analysis_data ad; ptrdiff_t pitch[3]; int kind; } MaskData;
+typedef struct MaskData { Consumer c; VSNode *node, *vectors; const VSVideoInfo *clipvi; VSVideoInfo vi; mvx_mask *mk; mvx_mask_info info; mvx_analysis_data ad; ptrdiff_t pitch[3]; int kind, bps; } MaskData;
+/* MVX_VS_MASK_DEEP=1 (read once, at the entry point): mv.Mask goes through mvx_mask_create_deep, takes clips of 8 to 16 bits and gives a mask of the clip's depth */
+static int g_mask_deep;
+#define MASK_FORMAT_MSG "Mask: input clip must be GRAY8, YUV420P8, YUV422P8, YUV440P8, or YUV444P8, with constant dimensions."
+#define MASK_FORMAT_MSG_DEEP "Mask: input clip must be Gray or YUV (4:2:0, 4:2:2, 4:4:0, 4:4:4) of 8 to 16 bits, with constant dimensions."
 
 static const VSFrame *VS_CC maskGetFrameUngated(int n, int reason, void *inst, void **fd, VSFrameContext *ctx, VSCore *core, const VSAPI *vs) {
     (void)fd;
@@ -2611,7 +2615,7 @@ static const VSFrame *VS_CC maskGetFrameUngated(int n, int reason, void *inst, v
     memset(&job, 0, sizeof(job));
     void *lumaArena = NULL, *dstArena = NULL, *dluma[3], *ddst[3], *dblob = NULL;
     int rc = 0;
-    if (d->kind == 5) rc = upload_plane_set(dluma, &lumaArena, src, d->pitch, 1, 1, vs); /* (the clip is 8-bit: creation) */
+    if (d->kind == 5) rc = upload_plane_set(dluma, &lumaArena, src, d->pitch, 1, d->bps, vs); /* (the clip has the mask's depth: creation) */
     if (!rc) rc = dst_plane_set(ddst, &dstArena, d->pitch, d->info.plane_height, 3);
     if (!rc) rc = clip_blob_to_device(&dblob, n, d->vectors, &d->ad, ctx, vs);
     for (int p = 0; p < 3 && !rc; p++) job.dst[p] = ddst[p];
@@ -2621,7 +2625,7 @@ static const VSFrame *VS_CC maskGetFrameUngated(int n, int reason, void *inst, v
     VSFrame *dst = NULL;
     if (!rc) {
         dst = vs->newVideoFrame(&d->vi.format, d->vi.width, d->vi.height, src, core);
-        rc = download_plane_set(dst, ddst, d->pitch, 3, 1, vs);
+        rc = download_plane_set(dst, ddst, d->pitch, 3, d->bps, vs);
     }
     shell_quiesce(rc);
     if (dblob) mvx_dev_free(dblob);
@@ -2654,16 +2658,19 @@ static void VS_CC maskCreate(const VSMap *in, VSMap *out, void *user, VSCore *co
         d->vi = *d->clipvi;
         const VSVideoFormat *f = &d->clipvi->format;
         const mvx_mask_clip mc = { d->clipvi->width, d->clipvi->height, f->bitsPerSample, f->subSamplingW, f->subSamplingH, f->colorFamily == cfGray };
-        clip_pitches(d->pitch, d->clipvi, 1); /* of the clip's luma and of the mask's planes alike: 8-bit, the clip's subsampling (Gray: none, three full-size planes) */
+        d->bps = g_mask_deep && f->bitsPerSample > 8 ? 2 : 1;
+        clip_pitches(d->pitch, d->clipvi, d->bps); /* of the clip's luma and of the mask's planes alike: the same depth, the clip's subsampling (Gray: none, three full-size planes) */
         char lerr[MVX_ERRLEN];
-        if (mvx_mask_create(&a, &d->ad, &mc, d->pitch, d->pitch, &d->mk, lerr)) snprintf(err, sizeof(err), "%s", lerr);
+        if ((g_mask_deep ? mvx_mask_create_deep : mvx_mask_create)(&a, &d->ad, &mc, d->pitch, d->pitch, &d->mk, lerr)) snprintf(err, sizeof(err), "%s", lerr);
         else if (!mvx_vsh_is_constant_video_format(d->clipvi) || f->sampleType != stInteger || (f->colorFamily != cfYUV && f->colorFamily != cfGray))
-            snprintf(err, sizeof(err), "Mask: input clip must be GRAY8, YUV420P8, YUV422P8, YUV440P8, or YUV444P8, with constant dimensions.");
+            snprintf(err, sizeof(err), "%s", g_mask_deep ? MASK_FORMAT_MSG_DEEP : MASK_FORMAT_MSG);
         d->c.engine = d->mk;
     }
-    if (!err[0]) { /* three 8-bit planes with the clip's subsampling; Gray -> 4:4:4 (src/MVMask.c:328-329) */
+    if (!err[0]) { /* three planes with the clip's subsampling, 8-bit (deep: of the clip's depth); Gray -> 4:4:4 (src/MVMask.c:328-329) */
         mvx_mask_get_info(d->mk, &d->info);
-        if (!vs->queryVideoFormat(&d->vi.format, cfYUV, stInteger, 8, d->info.subsampling_w, d->info.subsampling_h, core)) snprintf(err, sizeof(err), "Mask: the host has no 8-bit YUV format for the mask clip.");
+        const int obits = mvx_mask_out_bits(d->mk);
+        if (!vs->queryVideoFormat(&d->vi.format, cfYUV, stInteger, obits, d->info.subsampling_w, d->info.subsampling_h, core))
+            snprintf(err, sizeof(err), "Mask: the host has no %d-bit YUV format for the mask clip.", obits);
     }
     if (err[0]) { consumer_fail(&d->c, err, out, vs); return; }
     VSFilterDependency deps[2] = { { d->node, rpStrictSpatial }, { d->vectors, rpStrictSpatial } };
@@ -3953,6 +3960,8 @@ VS_EXTERNAL_API(void) VapourSynthPluginInit2(VSPlugin *plugin, const VSPLUGINAPI
         vspapi->registerFunction("Mask",
                                  "clip:vnode;vectors:vnode;ml:float:opt;gamma:float:opt;kind:int:opt;time:float:opt;ysc:int:opt;thscd1:int:opt;thscd2:int:opt;opt:int:opt;",
                                  "clip:vnode;", maskCreate, NULL, plugin);
+        /* mv.Mask for clips of 9 to 16 bits is a switch of its own beside this one, read the same way: MVX_VS_MASK_DEEP=1.   */
+        g_mask_deep = env_long("MVX_VS_MASK_DEEP", 0) != 0;
     }
     /* The Depan family is opt-in by a switch of its own, read the same way: MVX_VS_DEPAN=1.  (src/MVDepan.cpp:4211-4288) */
     if (env_long("MVX_VS_DEPAN", 0)) {
