@@ -1,7 +1,10 @@
 """developer tool: how many blocks of the speculative search kernel (mvx_analyse_spec.h) verify, per level, from a library built with
 -DMVX_SPEC_STATS (python tools/build_variant.py specstats "MVX_SPEC_STATS" mvx_analyse_spec_u16.hip):
 
-    MVX_LIB=tools/variants/specstats.so python tools/specstats.py [cfg] [batch]"""
+    MVX_LIB=tools/variants/specstats.so python tools/specstats.py [cfg] [batch]
+
+Also per level: the windows of stage 2 by form, the stage-2 passes that ran and the passes that packing saved (add MVX_SPEC_NOPACK to the switches
+for the unpacked count)."""
 import ctypes as C
 import os
 import sys
@@ -17,7 +20,8 @@ batch = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 blk, ov = cfg[4].get("blksize", 8), cfg[4].get("overlap", 0)
 nblkx0 = (cfg[0] - ov) // (blk - ov)  # blocks per row of the finest level
 p = bench.Pipeline(mv, torch, cfg, batch, torch.device("cuda", 0), 1)
-out = (C.c_ulonglong * (24 * 8))()  # MVX_MAX_LEVELS x 8
+NCOL = 10
+out = (C.c_ulonglong * (24 * NCOL))()  # MVX_MAX_LEVELS x NCOL
 p.step()
 torch.cuda.synchronize()
 assert mv.lib().mvx_debug_specstats(out, 1) == 0
@@ -27,7 +31,7 @@ assert mv.lib().mvx_debug_specstats(out, 1) == 0
 print("batch %d: search launch %.1f ms (counting build)" % (batch, p.ev[0][0].elapsed_time(p.ev[0][1])))
 print("level: blocks in speculated rows, searched live (share), of them flag clear (hexagon won / rescue), accepted after redoing the predictor phase with the true left / median")
 for lv in range(16):
-    b, live, flag, resc, ws, wb, dev, lim = (int(out[lv * 8 + i]) for i in range(8))
+    b, live, flag, resc, ws, wb, dev, lim, p2, saved = (int(out[lv * NCOL + i]) for i in range(NCOL))
     if b:
         print("%5d: %12d %12d (%5.2f %%) %12d %10d" % (lv, b, live, 100.0 * live / b, flag, resc))
         if ws + wb:
@@ -36,3 +40,7 @@ for lv in range(16):
             # a group is a whole number of windows (mvx_analyse_spec.h: GT): every window but the last one of a block row is full
             bpw = b / (ws + wb)
             print("       %.2f blocks per stage-2 window" % bpw + (" = %.1f windows per block row of %d blocks" % (nblkx0 / bpw, nblkx0) if lv == 0 else ""))
+            # stage 2 in packed passes (mvx_analyse_spec.h: PACK): four strip-form windows in a row take seven passes, not eight; stage 1 is one pass per window
+            print("       stage-2 passes run %d, saved by packing %d (%.1f %% of stage 2, %.1f %% of all row passes)" % (
+                p2, saved, 100.0 * saved / max(p2 + saved, 1), 100.0 * saved / max(p2 + saved + ws + wb, 1))
+                + (" = %.1f saved per block row of %d blocks (all groups packed: %d)" % (saved * (nblkx0 / bpw) / (ws + wb), nblkx0, nblkx0 // 28) if lv == 0 and blk - ov == 8 else ""))

@@ -35,6 +35,19 @@
 #define MVX_FAST_NOSTRIP 8                // flags: no runs in pass A (every block's candidates loaded on their own)
 #define MVX_FAST_NOSPEC 4                 // flags: verify nothing, search every block live (developer switch: the same kernel as a plain serial walk)
 
+// -DMVX_SPEC_NOPACK (tools/build_variant.py: the A/B and the counting build): stage 2 of the 16x16 row passes window by window, two passes of eight slots per
+// strip-form window whatever its neighbours (SpecSearcher::PACK)
+#ifdef MVX_SPEC_NOPACK
+#define MVX_SPEC_PACK 0
+#else
+#define MVX_SPEC_PACK 1
+#endif
+// MVX_SPEC_PLANEORDER: the order in which the strip-form passes of a Hex2 level take the 14 pattern points (slots stay reference indices): 1 = by sub-pel
+// plane -- at pel 2 the first eight are the six points with an odd x and an even y and the two with both even, the last six those with an odd y --, 0 = the
+// reference's own order (-DMVX_SPEC_PLANEORDER=0: the A/B build)
+#ifndef MVX_SPEC_PLANEORDER
+#define MVX_SPEC_PLANEORDER 1
+#endif
 constexpr int SPEC_SW3 = 12; // row loads in flight per lane in the builds for three or more chains per SIMD (168 registers)
 // -DMVX_SPEC_PROF (tools/specprof.py): cycles of ONE chain per phase of the group loop (s_memtime; a stamp waits for the scalar counter only)
 #ifdef MVX_SPEC_PROF
@@ -50,7 +63,7 @@ static __device__ unsigned long long g_specprof[SPROF_N];
 #define SPEC_PROF_DUMP_() ((void)0)
 #endif
 #ifdef MVX_SPEC_STATS
-static __device__ unsigned long long g_specstat[MVX_MAX_LEVELS][8]; // per level: blocks in speculated rows, of them searched live, live because the flag was clear, rescues; 16x16 row passes: windows of stage 2 in strip form, in block form, blocks of block-form windows whose centre differs from the window's first block, block-form windows because of the limits alone
+static __device__ unsigned long long g_specstat[MVX_MAX_LEVELS][10]; // per level: blocks in speculated rows, of them searched live, live because the flag was clear, rescues; 16x16 row passes: windows of stage 2 in strip form, in block form, blocks of block-form windows whose centre differs from the window's first block, block-form windows because of the limits alone; passes of stage 2 that ran, passes that packing saved
 #endif
 
 // SWIN: row loads a lane keeps in flight in the row passes (12 = half a pass; 24 = a whole pass: the builds with 256 registers)
@@ -236,6 +249,19 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
     static constexpr int HC = STRIP_OK ? BW / 16 : 1, SW_BLOCKS = 8 / HC - 1, LPB = 2 * HC, LPC = SW_BLOCKS * LPB;
     static constexpr int pickSW(int nt, int w) { return w <= 1 ? 1 : (w <= nt && nt % w == 0) ? w : pickSW(nt, w - 1); } // rows in flight: a divisor of the rows of a pass
     static constexpr int SNA = BW, SNB = UV ? BW / 2 : 0, SNT = SNA + SNB, SW = pickSW(SNT, (BW == 32 && SWIN > 12) ? 12 : SWIN), S_UV = SNA * ROWB, SSTG = SNT / 8; // (32x32: 12 in flight -- 24 plus the six staging pieces spill) // rows of a pass, loads in flight, LDS offset of the UV rows, staging pieces per lane
+    // SDMA (r6): the source strip of a window goes straight to LDS (global_load_lds_dwordx4), into one of two buffers.  What orders a strip before the passes that
+    // read it is a COUNT: a strip is requested in front of the SW row loads of one pass and awaited with vmcnt(SW) -- so a pass must refill exactly SW rows (a whole
+    // pass in flight: SW == SNT) and a strip is the SSTG == 3 loads stage_issue makes of it
+    static constexpr bool SDMA = STRIP_OK && COLB == 16 && HC == 1 && SW == 24 && SNT == 24;
+    static_assert(!SDMA || (SW == SNT && SSTG == 3), "SDMA: strip_run<true> issues exactly SW loads per pass, a strip is three loads per lane");
+    static_assert(SW <= 63, "the wait for a strip is s_waitcnt vmcnt(SW)");
+    // PACK: stage 2 of four consecutive strip-form windows of a Hex2 level in seven passes, not eight (search_level_spec); needs both strip buffers
+    static constexpr bool PACK = SDMA && MVX_SPEC_PACK;
+    // the reference pattern index of the i-th point a strip-form window of a Hex2 level evaluates: 1, 2, 4, 5, 8, 9, 0, 3 | 6, 7, 10, 11, 12, 13
+    __device__ __forceinline__ static int hex_ord(int i) {
+        if constexpr (MVX_SPEC_PLANEORDER != 0) return (int)(0xDCBA7630985421ull >> (4 * i)) & 15;
+        else return i;
+    }
     struct StripPass { v4u r[SW]; unsigned curA, curB, aL, aC; };
     __device__ __forceinline__ v4u strip_issue(StripPass &T, int piece) const {
         v4u v;
@@ -417,14 +443,18 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
             const int gb = side8 ? l >> 3 : STRIP8_OK ? (l >= 45 ? 3 : l >= 30 ? 2 : l >= 15 ? 1 : 0) : side16 ? min(l >> 3, 3) : min(l / LPC, 3);
             for (int q = 0; q < 8; q++) {
                 int dx, dy;
-                if (q < 4) { pat_delta(hexLevel, STRIP8_OK ? q * 16 + (l >> 2) : q * 8 + (l >> 3), dx, dy); sPat |= (unsigned)((dx & 15) | ((dy & 15) << 4)) << (8 * q); }
+                // (PACK, Hex2 levels: byte 0 = points 0-7, the full pass of a window; bytes 1-3 = the points 8-13 of the packed passes 0-2 of four windows -- lane
+                // group g of packed pass j holds pair 8 j + g of the 24 (window, point) pairs that are left.  Byte 1 is also the second pass of a window on its own:
+                // its groups 0-5 hold the points 8-13 either way, groups 6 and 7 write nothing there)
+                const int sIdx = STRIP8_OK ? q * 16 + (l >> 2) : (PACK && hexLevel && q >= 1) ? 8 + (8 * (q - 1) + (l >> 3)) % 6 : q * 8 + (l >> 3);
+                if (q < 4) { pat_delta(hexLevel, (STRIP_OK && hexLevel) ? hex_ord(min(sIdx, 13)) : sIdx, dx, dy); sPat |= (unsigned)((dx & 15) | ((dy & 15) << 4)) << (8 * q); }
                 pat_delta(hexLevel, q * (side8 ? 8 : 4) + gb, dx, dy);
                 const unsigned b = (unsigned)((dx & 15) | ((dy & 15) << 4)) << (8 * (q & 3));
                 if (q < 4) bPat0 |= b; else bPat1 |= b;
             }
         }
 #ifdef MVX_SPEC_STATS
-        unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0, st4 = 0, st5 = 0, st6 = 0, st7 = 0;
+        unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0, st4 = 0, st5 = 0, st6 = 0, st7 = 0, st8 = 0, st9 = 0;
 #endif
 
         int prevX = 0, prevY = 0, prevSad = 0;
@@ -632,6 +662,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                     pbMask = 0;
                                     staged2 = true;
                                     unsigned stripW = 0; // stage 2: windows in strip form
+                                    unsigned packS = 0;  // stage 2: walk positions at which four strip-form windows in a row start (PACK: seven passes for the four)
                                     int pkW = 0;         // this lane's block: the refinement centre
                                     // lane roles: strip form (candidate l >> 3, column l & 7); block form (candidate l / 14, block (l % 14) >> 1, half l & 1);
                                     // recomputed from an opaque lane number in every pass (values derived from the lane number are loop invariants: the
@@ -651,9 +682,16 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                     roles();
                                     // this lane's share of pass q of window w in stage st: table slot (-1: nothing to write), the column it writes, whether its
                                     // block sum is "column + next column" (strip) or "half + other half" (block), source column, first reference piece
-                                    auto w_cand = [&](int st, int w, int q, int &slot, int &colW, bool &stripLane, int &srcCol, unsigned &oA, unsigned &oB) {
+                                    // PACK: rj >= 0 is PACKED pass rj (0..2) of four strip-form windows in a row; w is then the window at position rj of the four, and the lane groups
+                                    // from 6 - 2 rj on belong to the window after it in walk order: what is one value per wave elsewhere (the window's first block, its length, its
+                                    // centre, its strip buffer) is one of two per lane.  Table slots stay reference pattern indices, so A2 reads what it always read.
+                                    // srcOff: byte offset of the lane's source column in the chain's LDS (SDMA: the window at walk position i has its strip in buffer i & 1)
+                                    constexpr int SBUF = SNT * ROWB; // bytes of one strip buffer (the host sizes the chain's LDS for two)
+                                    auto widx = [&](int i) { return fwd ? i : nw - 1 - i; }; // windows in walk order (its own inverse)
+                                    auto w_cand = [&](int st, int w, int q, int rj, int &slot, int &colW, bool &stripLane, int &srcOff, unsigned &oA, unsigned &oB) {
                                         const int f = lo + SWB * w, L = min(SWB, hiE - f);
                                         const int bxf = hpad + stepX * (c0 + f);
+                                        const int bufW = SDMA ? (widx(w) & 1) * SBUF : 0;
                                         const bool stripWin = st == 2 && ((stripW >> w) & 1);
                                         // the block lanes' vectors come from the lanes that own the blocks: fetched HERE, with every lane active (ds_bpermute returns 0
                                         // for a source lane that is masked off, and in stage 1 lanes 56-63 take the other branch below)
@@ -666,19 +704,29 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                         if (stripWin || (st == 1 && tail)) { // strip lanes: one vector for the whole window
                                             const int p = st == 1 ? pS : pS, g = gS;
                                             int vx, vy, vyc;
+                                            int fV = f, LV = L, bxV = bxf, bufV = bufW; // (per lane in a packed pass)
                                             if (st == 1) { vx = 0; vy = fieldShift; vyc = 0; slot = slotZ; } // (the zero candidate's chroma ignores fieldShift, :836-839)
                                             else {
-                                                const int sW = __builtin_amdgcn_readlane(pkW, f);
-                                                const int idx = q * 8 + g;
-                                                const int dd = (int)(sPat >> (8 * q)), dx = (dd << 28) >> 28, dy = (dd << 24) >> 28;
+                                                int sW = __builtin_amdgcn_readlane(pkW, f);
+                                                int idx = q * 8 + g, sh = 8 * q;
+                                                if constexpr (PACK) {
+                                                    if (rj >= 0) {
+                                                        const int w2 = widx(widx(w) + 1), f2 = lo + SWB * w2, L2 = min(SWB, hiE - f2);
+                                                        const int sW2 = __builtin_amdgcn_readlane(pkW, f2);
+                                                        const bool hi = g >= 6 - 2 * rj; // pair 8 rj + g of the four windows' 24: window (8 rj + g) / 6, point 8 + (8 rj + g) % 6
+                                                        fV = hi ? f2 : f; LV = hi ? L2 : L; bxV = hpad + stepX * (c0 + fV); sW = hi ? sW2 : sW; bufV = hi ? SBUF - bufW : bufW;
+                                                        idx = 8 + 2 * rj + g - (hi ? 6 : 0); sh = 8 * (1 + rj);
+                                                    }
+                                                }
+                                                const int dd = (int)(sPat >> sh), dx = (dd << 28) >> 28, dy = (dd << 24) >> 28;
                                                 vx = upx(sW) + dx; vy = upy(sW) + dy; vyc = vy;
-                                                slot = idx < npat ? idx : -1;
+                                                slot = idx < npat ? (hexLevel ? hex_ord(idx) : idx) : -1;
                                             }
-                                            const int pe = min(p, TC * (L - 1) + 2 * HC - 1) * COLB; // (columns beyond the run re-read its last one)
-                                            if ((p % TC != 0) | (p / TC >= L)) slot = -1;  // (block m is written by the lane of its first column)
-                                            colW = f + p / TC; stripLane = true; srcCol = p;
-                                            oA = luma_off_at(bxf, vx, vy) + (unsigned)pe;
-                                            oB = 2 * chroma_off_at(bxf, vx, vyc) + (unsigned)pe;
+                                            const int pe = min(p, TC * (LV - 1) + 2 * HC - 1) * COLB; // (columns beyond the run re-read its last one)
+                                            if ((p % TC != 0) | (p / TC >= LV)) slot = -1;  // (block m is written by the lane of its first column)
+                                            colW = fV + p / TC; stripLane = true; srcOff = bufV + p * COLB;
+                                            oA = luma_off_at(bxV, vx, vy) + (unsigned)pe;
+                                            oB = 2 * chroma_off_at(bxV, vx, vyc) + (unsigned)pe;
                                         } else { // block lanes: every block its own vector
                                             const int me = meB, col = colB;
                                             int base, dx = 0, dy = 0;
@@ -698,7 +746,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                             const bool ok = (tx >= xMin) & (ty >= nDyMin) & (tx < xMax) & (ty < nDyMax); // (outside the block's limits: the centre instead; A2 never reads the entry)
                                             const int vx = ok ? tx : cxv, vy = ok ? ty : cyv;
                                             if ((hB != 0) | (mB >= L) | idleB) slot = -1;
-                                            colW = f + me; stripLane = false; srcCol = TC * me + hB;
+                                            colW = f + me; stripLane = false; srcOff = bufW + (TC * me + hB) * COLB;
                                             oA = luma_off_at(bx0, vx, vy) + (unsigned)(hB * COLB);
                                             oB = 2 * chroma_off_at(bx0, vx, vy) + (unsigned)(hB * COLB);
                                         }
@@ -707,13 +755,12 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                     // r6, SDMA: sixteen-byte columns, 16x16 blocks -- lane l's piece of rows 8k .. 8k + 7 belongs at byte 16 l of that kilobyte of the strip, which is where
                                     // global_load_lds_dwordx4 puts it: the strip never passes through registers (twelve fewer live across the passes, no ds_write).  Two buffers: the next
                                     // window's strip arrives while this window's passes read theirs.  A strip is requested BEFORE the 24 row loads that follow it (the prime, or a pass's
-                                    // refills), so "all but the 24 newest loads have returned" (vmcnt is in order) means it is there
-                                    constexpr bool SDMA = COLB == 16 && HC == 1 && SW == 24 && SNT == 24;
-                                    constexpr int SBUF = SNT * ROWB; // bytes of one strip buffer (the host sizes the chain's LDS for two)
-                                    int sbuf = 0;                    // the buffer of the window whose passes run
+                                    // refills), so "all but the SW newest loads have returned" (vmcnt is in order) means it is there.  A request overwrites the buffer that the passes
+                                    // before it read: it waits for their ds_reads first (lgkmcnt(0))
                                     A4x32 stg[SDMA ? 1 : SSTG]; // (rows gS, gS + 8, ...: the luma rows first, then the rows of the UV plane)
                                     auto stage_issue = [&](int w, int buf) {
                                         const int f = lo + SWB * w, L = min(SWB, hiE - f), bx0 = hpad + stepX * (c0 + f), pe = min(pS, TC * (L - 1) + 2 * HC - 1) * COLB;
+                                        if constexpr (SDMA) asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory");
 #pragma unroll
                                         for (int k = 0; k < SSTG; k++) {
                                             const int row = gS + 8 * k;
@@ -726,7 +773,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                         }
                                     };
                                     auto stage_store = [&]() {
-                                        if constexpr (SDMA) asm volatile("s_waitcnt vmcnt(24)" : : : "memory");
+                                        if constexpr (SDMA) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(SW) : "memory");
                                         else {
 #pragma unroll
                                             for (int k = 0; k < SSTG; k++) st_chunk_l(lds + (gS + 8 * k) * ROWB + pS * COLB, stg[k], COLB); // (S_UV = SNA * ROWB: the UV rows follow the luma rows)
@@ -737,34 +784,46 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                     // On a clip whose vectors are whole pels stage 1 reads the integer-pel plane and stage 2 mostly the three others: little to share)
                                     // (a leading-edge prefetch -- one dword of every line a window two ahead will need, four scattered loads per window --
                                     // was measured and removed: 493 -> 544 ms per 2046-chain launch, profiles/r4_spec_prefetch.txt)
-                                    auto widx = [&](int i) { return fwd ? i : nw - 1 - i; }; // windows in walk order
                                     auto npass = [&](int st, int w) { return st == 1 ? 1 : ((stripW >> w) & 1) ? (npat + 7) / 8 : (npat + 3) / 4; };
                                     // one stage: a stream of passes whose loads stay in flight across passes and windows
                                     auto run_stage = [&](int st, int wFrom, int wTo) { // the windows wFrom .. wTo - 1 in walk order
-                                        int wi = wFrom, w = widx(wFrom), q = 0;
+                                        // PACK, four strip-form windows in a row (ci = the window's position among them, -1 elsewhere): F0 R0 F1 R1 F2 R2 F3 -- F = a window's full
+                                        // pass (points 0-7, q = 0), R = packed pass rj (q = 1): the 4 x 6 pairs that are left, eight to a pass.  Rj reads the strips of the windows
+                                        // at positions j and j + 1: the second was requested in front of Fj's refills and is awaited before Rj; F(j + 1) then requests the strip of
+                                        // position j + 2 into the buffer of position j, which no later pass reads
+                                        int wi = wFrom, w = widx(wFrom), q = 0, rj = -1, ci = -1;
+                                        if constexpr (PACK) ci = (st == 2 && ((packS >> wi) & 1)) ? 0 : -1;
                                         StripPass T;
-                                        int slot, colW, srcCol; bool stripLane; unsigned oA, oB;
+                                        int slot, colW, srcOff; bool stripLane; unsigned oA, oB;
                                         roles();
-                                        w_cand(st, w, q, slot, colW, stripLane, srcCol, oA, oB);
-                                        if constexpr (SDMA) { sbuf = 0; stage_issue(w, 0); strip_prime(T, oA, oB); } // (the strip first: see above)
+                                        w_cand(st, w, q, rj, slot, colW, stripLane, srcOff, oA, oB);
+                                        if constexpr (SDMA) { stage_issue(w, wi & 1); strip_prime(T, oA, oB); } // (the strip first: see above)
                                         else { strip_prime(T, oA, oB); stage_issue(w, 0); }
                                         for (;;) {
                                             roles();
-                                            int wn = w, qn = q + 1, win = wi;
-                                            if (qn >= npass(st, w)) { qn = 0; win = wi + 1; wn = widx(win); }
+                                            int wn = w, qn = q + 1, win = wi, rjn = -1, cin = ci;
+                                            bool nextWin;
+                                            if (PACK && ci >= 0) {
+                                                if (rj < 0 && ci < 3) { rjn = ci; nextWin = false; } // F(ci) -> R(ci)
+                                                else { cin = ci < 3 ? ci + 1 : -1; nextWin = true; } // R(ci) -> F(ci + 1); F3: the four are done
+                                            } else nextWin = qn >= npass(st, w);
+                                            if (nextWin) {
+                                                qn = 0; win = wi + 1; wn = widx(win);
+                                                if constexpr (PACK) { if (st == 2 && cin < 0 && win < wTo && ((packS >> win) & 1)) cin = 0; }
+                                            }
                                             const bool more = win < wTo;
                                             int slotN = -1, colN = 0, srcN = 0; bool stripN = false; unsigned nA = 0, nB = 0;
                                             SPROF(2);
-                                            if (more) w_cand(st, wn, qn, slotN, colN, stripN, srcN, nA, nB); // the pass after this one (its loads refill the window of loads while this one is consumed)
+                                            if (more) w_cand(st, wn, qn, rjn, slotN, colN, stripN, srcN, nA, nB); // the pass after this one (its loads refill the window of loads while this one is consumed)
                                             SPROF(11);
-                                            if (q == 0) { // a new window: its source strip (requested one window ahead)
+                                            if (q == 0 || (PACK && rj >= 0)) { // a new window: its source strip (requested one window ahead); a packed pass: the strip of its second window
                                                 __builtin_amdgcn_wave_barrier();
                                                 stage_store();
-                                                if (wi + 1 < wTo) stage_issue(widx(wi + 1), sbuf ^ 1);
+                                                if (q == 0 && wi + 1 < wTo) stage_issue(widx(wi + 1), (wi + 1) & 1);
                                                 __builtin_amdgcn_wave_barrier();
                                             }
                                             SPROF(12);
-                                            if (more) strip_run<true>(T, srcCol, nA, nB, SDMA ? sbuf * SBUF : 0); else strip_run<false>(T, srcCol, 0, 0, SDMA ? sbuf * SBUF : 0);
+                                            if (more) strip_run<true>(T, 0, nA, nB, srcOff); else strip_run<false>(T, 0, 0, 0, srcOff);
                                             SPROF(13);
                                             // strip lanes: block m = columns m and m + 1; block lanes: the two halves of a block sit in neighbouring lanes
                                             unsigned sL = T.aL + (unsigned)__builtin_amdgcn_update_dpp(0, (int)T.aL, 0x101, 0xf, 0xf, true), sC = T.aC + (unsigned)__builtin_amdgcn_update_dpp(0, (int)T.aC, 0x101, 0xf, 0xf, true);
@@ -778,9 +837,11 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
 #ifdef MVX_SPEC_PROF
                                             sprof[15] += 1;
 #endif
+#ifdef MVX_SPEC_STATS
+                                            if (st == 2) st8 += 1;
+#endif
                                             if (!more) break;
-                                            if (SDMA && win != wi) sbuf ^= 1;
-                                            w = wn; wi = win; q = qn; slot = slotN; colW = colN; stripLane = stripN; srcCol = srcN;
+                                            w = wn; wi = win; q = qn; rj = rjn; ci = cin; slot = slotN; colW = colN; stripLane = stripN; srcOff = srcN;
                                         }
                                         __builtin_amdgcn_wave_barrier();
                                     };
@@ -797,6 +858,18 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
 #ifdef MVX_SPEC_STATS
                                             if ((stripW >> w) & 1) st4 += 1;
                                             else { st5 += 1; st6 += __builtin_popcountll(__ballot(inw & (pkW != w0))); if (__ballot(inw & (pkW != w0)) == 0) st7 += 1; }
+#endif
+                                        }
+                                        if constexpr (PACK) { // four strip-form windows in a row, in walk order: their 4 x 14 points fill seven passes of eight exactly
+                                            if (hexLevel) {
+                                                for (int i = 0; i + 4 <= nw;) {
+                                                    bool all4 = true;
+                                                    for (int k = 0; k < 4; k++) all4 = all4 && ((stripW >> widx(i + k)) & 1);
+                                                    if (all4) { packS |= 1u << i; i += 4; } else i++;
+                                                }
+                                            }
+#if defined(MVX_SPEC_STATS)
+                                            st9 += __builtin_popcount(packS);
 #endif
                                         }
                                     }
@@ -1328,7 +1401,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
             }
         }
 #ifdef MVX_SPEC_STATS
-        if (l == 0) { atomicAdd(&g_specstat[lvl][0], st0); atomicAdd(&g_specstat[lvl][1], st1); atomicAdd(&g_specstat[lvl][2], st2); atomicAdd(&g_specstat[lvl][3], st3); atomicAdd(&g_specstat[lvl][4], st4); atomicAdd(&g_specstat[lvl][5], st5); atomicAdd(&g_specstat[lvl][6], st6); atomicAdd(&g_specstat[lvl][7], st7); }
+        if (l == 0) { atomicAdd(&g_specstat[lvl][0], st0); atomicAdd(&g_specstat[lvl][1], st1); atomicAdd(&g_specstat[lvl][2], st2); atomicAdd(&g_specstat[lvl][3], st3); atomicAdd(&g_specstat[lvl][4], st4); atomicAdd(&g_specstat[lvl][5], st5); atomicAdd(&g_specstat[lvl][6], st6); atomicAdd(&g_specstat[lvl][7], st7); atomicAdd(&g_specstat[lvl][8], st8); atomicAdd(&g_specstat[lvl][9], st9); }
 #endif
         SPROF(7);
         // vectors[] of this level feed the next level's interpolation / global-MV estimate (other lanes read them)
@@ -1402,8 +1475,8 @@ extern "C" __attribute__((visibility("default"))) int mvx_debug_specprof(unsigne
 #endif
 #if defined(MVX_SPEC_STATS) && defined(MVX_PROF_EXPORT)
 extern "C" __attribute__((visibility("default"))) int mvx_debug_specstats(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_specstat), sizeof(unsigned long long) * MVX_MAX_LEVELS * 8) != hipSuccess) return -1;
-    if (reset) { static unsigned long long z[MVX_MAX_LEVELS * 8]; if (hipMemcpyToSymbol(HIP_SYMBOL(g_specstat), z, sizeof(z)) != hipSuccess) return -1; }
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_specstat), sizeof(unsigned long long) * MVX_MAX_LEVELS * 10) != hipSuccess) return -1;
+    if (reset) { static unsigned long long z[MVX_MAX_LEVELS * 10]; if (hipMemcpyToSymbol(HIP_SYMBOL(g_specstat), z, sizeof(z)) != hipSuccess) return -1; }
     return 0;
 }
 #endif
