@@ -74,6 +74,24 @@ int mvx_super_create(const mvx_super_args *args, mvx_super **out, char *err /* M
 void mvx_super_destroy(mvx_super *s);
 void mvx_super_get_info(const mvx_super *s, mvx_super_info *info);
 
+/* A super clip of a 32-bit float clip (pinterf's MVTools2 takes float clips in MSuper and MDegrain as long as the vectors come from an integer
+ * search; no counterpart in the reference).  It has ONE level: args->bits must be 32 ("Super: a float clip has 32 bits per sample.") and
+ * args->levels MVX_UNSET or 1 ("Super: a float super clip has one level (levels=1)."); these two checks come first, every other message is
+ * mvx_super_create's in its order.  rfilter is range-checked and then unused.  mvx_super_info.bits is 32, the geometry is what mvx_super_create
+ * gives for the same arguments with levels=1, samples are 4 bytes.  mvx_super_frames serves the object (src pitch a multiple of 4 bytes, planes
+ * aligned alike) and fills level 0 -- padding, the pel-2 planes, the twelve averaged planes of pel 4 -- with the integer rules operation for
+ * operation on float32: no rounding term, every shift a multiplication by the exact power of two, no clamp (samples may overshoot, chroma is
+ * centred on 0), nothing fused:
+ *   sharp 0   (a + b) * 0.5f; diagonal (((a + b) + c) + d) * 0.25f with the integer code's edge cases
+ *   sharp 1   ((s(X) + s(X+1)) * 9.0f - (s(X-1) + s(X+2))) * 0.0625f
+ *   sharp 2   m2 = (m2 + m3) * 4; m2 -= (m1 + m4); m2 *= 5; m0 = (m0 + m5) + m2; m0 * 0.03125f
+ *   the diagonal plane of sharp 1 and 2 is the horizontal rule on the UNROUNDED vertical plane; pel 4: (a + b) * 0.5f
+ * (csrc/mvx_super_float_rule.h).  Samples are assumed finite.  Only mvx_degrain_n_create_float consumes such an object: mvx_super_shadow_copies
+ * returns 0, the shadow, pelclip and Finest entries return MVX_E_ARG, and every other *_create that takes an mvx_super refuses it before any
+ * other check with "<Name>: float super clips are not supported.".  Touches no device. */
+int mvx_super_create_float(const mvx_super_args *args, mvx_super **out, char *err);
+int mvx_super_is_float(const mvx_super *s);
+
 /* Builds `nframes` super frames.  src[f*3+p] / dst[f*3+p] are device pointers to plane p of frame f
  * (p >= num_planes ignored); pitches in bytes, shared by all frames.  dst planes must have been
  * zero-filled once by the caller when allocated: only the defined rectangles (every level's padded
@@ -267,7 +285,25 @@ int mvx_degrain_n_create(const mvx_degrain_n_args *args, const mvx_analysis_data
 int mvx_degrain_n_create_out16(const mvx_degrain_n_args *args, const mvx_analysis_data *vectors_data /* of mvbw */,
                                const mvx_super *super_clip, const ptrdiff_t src_pitch[3], const ptrdiff_t super_pitch[3],
                                const ptrdiff_t dst_pitch[3] /* of the 16-bit planes */, mvx_degrain_n **out, char *err);
-/* bits per sample of the planes mvx_degrain_n_frames writes: 16 for an out16 object, else the clip's depth */
+/* DegrainN on a 32-bit float clip: the clip, the super clip (mvx_super_create_float) and the output are float32 planes; the vectors come from
+ * a search on ANY 8..16 bit clip of the same width, height, pel, padding and subsampling (Analyse / AnalyseN / RecalculateN, or a result of
+ * ScaleVect).  thsad, thsad2, thscd1 and thscd2 are in the units of that search and resolved from vectors_data; usable blocks, weights,
+ * normalisation and lists are exactly those of mvx_degrain_n_create for these blobs.  Arithmetic of a sample, float32, every operation rounded
+ * on its own, s the source sample, the list in its stored order:
+ *   block value      S = (float)WSrc * s; for each entry S = S + (float)w_k * ref_k; V = S * (1/256.0f)
+ *   overlap 0        out = V
+ *   overlap > 0      acc = 0; over the covering blocks (by outer, bx inner, ascending) acc = acc + V * (float)win; out = acc / (float)wsum with
+ *                    wsum the integer sum of those same window weights (2047..2049: dividing by it keeps a flat area flat)
+ *   limit / limitc   on the 8-bit scale 0..255, MVX_UNSET -> 255 (none) / limit; below 255: L = (float)limit / 255.0f,
+ *                    out = max(s - L, min(s + L, out))
+ *   passed through   bit for bit: a plane that `plane` leaves out, the strips no block covers, a job without a usable reference
+ * Inputs are assumed finite (no NaN, no infinity).  Messages are mvx_degrain_n_create's in its order, and after the frame-size check
+ * "DegrainN: the float entry needs a float super clip."; the limits' messages name 255.  Planes and pitches must be multiples of 4 bytes.
+ * Touches no device.  The object is used and destroyed like one of mvx_degrain_n_create; mvx_degrain_n_out_bits returns 32. */
+int mvx_degrain_n_create_float(const mvx_degrain_n_args *args, const mvx_analysis_data *vectors_data /* of mvbw */,
+                               const mvx_super *super_clip /* float */, const ptrdiff_t src_pitch[3], const ptrdiff_t super_pitch[3],
+                               const ptrdiff_t dst_pitch[3], mvx_degrain_n **out, char *err);
+/* bits per sample of the planes mvx_degrain_n_frames writes: 16 for an out16 object, 32 for a float one, else the clip's depth */
 int mvx_degrain_n_out_bits(const mvx_degrain_n *d);
 void mvx_degrain_n_get_info(const mvx_degrain_n *d, mvx_degrain_n_info *info);
 void mvx_degrain_n_destroy(mvx_degrain_n *d);
@@ -837,7 +873,7 @@ int mvx_depan_analyse_host(const mvx_depan_analyse *h, int n, const void *const 
  *      and 32 (:657-668), so every clip goes through its uint16_t branch: right for 9..16 bits, but an 8-bit clip is read as pairs of
  *      bytes over 2 * winx bytes per row, past the window and on the last rows past the frame.  The library reads bytes for 8 bits and
  *      words for 9..16 bits;
- *   9. float clips are refused at creation (no filter of this library has a float path);
+ *   9. float clips are refused at creation (only mv.Super's and mv.DegrainN's float entries have a float path);
  *  10. winx (after the halving for zoom) and winy must be powers of two from 8 to 8192, refused at creation otherwise; the automatic
  *      sizes always qualify on a frame of at least 8 x 8 (16 x 8 with zoom).  A window that leaves the frame -- the second window of
  *      zoommax != 1 starts at wleft + width / 2, which the reference does not check -- is refused too;

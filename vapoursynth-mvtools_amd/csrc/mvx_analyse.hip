@@ -122,6 +122,7 @@ __global__ __launch_bounds__(256) void analyse_divide_kernel(const AParams *Pp, 
 extern "C" __attribute__((visibility("default"))) int mvx_analyse_create(const mvx_analyse_args *a, const mvx_super *sup, int num_frames, const ptrdiff_t super_pitch[3],
                                   mvx_analyse **out, char *err) {
     MVX_CREATE_BEGIN(out);
+    MVX_REFUSE_FLOAT(sup, "Analyse");
     const mvx_super_info &si = sup->info;
     mvx_analysis_data ad;
     memset(&ad, 0, sizeof(ad));
@@ -544,6 +545,7 @@ struct mvx_recalculate {
 extern "C" __attribute__((visibility("default"))) int mvx_recalculate_create(const mvx_recalculate_args *a, const mvx_super *sup, const mvx_analysis_data *vectors,
                                                                              const ptrdiff_t super_pitch[3], mvx_recalculate **out, char *err) {
     MVX_CREATE_BEGIN(out);
+    MVX_REFUSE_FLOAT(sup, "Recalculate");
     const mvx_super_info &si = sup->info;
     auto A64 = [](int64_t v, int64_t d) { return v == MVX_UNSET ? d : v; };
     mvx_analysis_data ad;

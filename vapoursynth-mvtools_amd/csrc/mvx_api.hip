@@ -304,6 +304,7 @@ struct mvx_analyse_n {
 extern "C" __attribute__((visibility("default"))) int mvx_analyse_n_create(const mvx_analyse_args *a, int radius, const mvx_super *sup, int num_frames,
                                                                            const ptrdiff_t super_pitch[3], mvx_analyse_n **out, char *err) {
     MVX_CREATE_BEGIN(out);
+    MVX_REFUSE_FLOAT(sup, "AnalyseN");
     if (radius < 1 || radius > MVX_DEGRAIN_N_MAX_RADIUS) MVX_FAIL("AnalyseN: radius must be between 1 and %d.", MVX_DEGRAIN_N_MAX_RADIUS);
     if (a->isb != MVX_UNSET || a->delta != MVX_UNSET) MVX_FAIL("AnalyseN: isb and delta are set by the radius.");
     mvx_analyse_args args = *a;
@@ -377,6 +378,7 @@ struct mvx_recalculate_n {
 extern "C" __attribute__((visibility("default"))) int mvx_recalculate_n_create(const mvx_recalculate_args *a, int radius, const mvx_super *sup, const mvx_analysis_data *vectors,
                                                                                const ptrdiff_t super_pitch[3], mvx_recalculate_n **out, char *err) {
     MVX_CREATE_BEGIN(out);
+    MVX_REFUSE_FLOAT(sup, "RecalculateN");
     if (radius < 1 || radius > MVX_DEGRAIN_N_MAX_RADIUS) MVX_FAIL("RecalculateN: radius must be between 1 and %d.", MVX_DEGRAIN_N_MAX_RADIUS);
     if (!vectors->isBackward || vectors->nDeltaFrame != 1) MVX_FAIL("RecalculateN: vectors_data must be field 0 of a multi blob.");
     mvx_recalculate *rc = nullptr;

@@ -107,8 +107,9 @@ template <typename PARAMS> static int blk_upload(DevBuf<PARAMS> &dP, PARAMS &P, 
 
 // Degrain1..6 (MVDegrains.cpp:511-809) and DegrainN.  Degrain is DegrainN without far thresholds: every distance then has the threshold of
 // the first (dn_threshold), which is Degrain's thsad * nSCD1 / nSCD1_old.  out16: the limits are in units of the 16-bit output
+enum { DG_PLAIN = 0, DG_OUT16 = 1, DG_FLOAT = 2 }; // kind: the clip's depth out / out16 / mvx_degrain_n_create_float (limits on the 8-bit scale)
 struct DgResolved { mvx_degrain_n_info info; int YUVplanes, limit, limitc; int64_t thscd1; int32_t thscd2; };
-static int dg_resolve(const char *name, const mvx_degrain_n_args *a, bool out16, const mvx_analysis_data *ad, const mvx_super_info &si, DgResolved *r, char *err) {
+static int dg_resolve(const char *name, const mvx_degrain_n_args *a, int kind, const mvx_analysis_data *ad, const mvx_super_info &si, DgResolved *r, char *err) {
     const int radius = a->radius;
     const int64_t t1 = a->thsad == MVX_UNSET ? 400 : a->thsad, t1c = a->thsadc == MVX_UNSET ? t1 : a->thsadc;
     const int64_t t2 = a->thsad2 == MVX_UNSET ? t1 : a->thsad2, t2c = a->thsadc2 == MVX_UNSET ? t1c : a->thsadc2;
@@ -130,8 +131,10 @@ static int dg_resolve(const char *name, const mvx_degrain_n_args *a, bool out16,
     if (which) MVX_FAIL("%s: with this block size and video format, thsad%s must not exceed %lld or some calculations would overflow.", name, which,
                         (long long)(2147483647LL * nSCD1_old / r->thscd1));
     if (!mvx_super_fits(ad, si, true)) MVX_FAIL("%s: wrong source or super clip frame size.", name);
+    const bool out16 = kind == DG_OUT16;
     if (out16 && si.bits != 8) MVX_FAIL("%s: out16 needs an 8 bit clip.", name);
-    const int pixelMax = out16 ? 65535 : (1 << si.bits) - 1;
+    if (kind == DG_FLOAT && si.bits != 32) MVX_FAIL("%s: the float entry needs a float super clip.", name);
+    const int pixelMax = out16 ? 65535 : kind == DG_FLOAT ? 255 : (1 << si.bits) - 1;
     r->limit = a->limit == MVX_UNSET ? pixelMax : a->limit;
     r->limitc = a->limitc == MVX_UNSET ? r->limit : a->limitc;
     if (r->limit < 0 || r->limit > pixelMax) MVX_FAIL("%s: limit must be between 0 and %d (inclusive).", name, pixelMax);

@@ -159,6 +159,7 @@ struct mvx_compensate_n {
 extern "C" __attribute__((visibility("default"))) int mvx_compensate_n_create(const mvx_compensate_args *a, int tr, const mvx_analysis_data *ad, const mvx_super *sup,
                                                                               const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_compensate_n **out, char *err) {
     MVX_CREATE_BEGIN(out);
+    MVX_REFUSE_FLOAT(sup, "CompensateN");
     const mvx_super_info &si = sup->info;
     const char *name = "CompensateN";
     if (tr < 1 || tr > MVX_DEGRAIN_N_MAX_RADIUS) MVX_FAIL("%s: tr must be between 1 and %d.", name, MVX_DEGRAIN_N_MAX_RADIUS);

@@ -587,6 +587,7 @@ static int dg_rows_cw(const DGParams &P, int p, bool covered) {
 extern "C" __attribute__((visibility("default"))) int mvx_degrain_create(const mvx_degrain_args *a, const mvx_analysis_data *ad, const mvx_super *sup, const ptrdiff_t src_pitch[3],
                                   const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_degrain **out, char *err) {
     MVX_CREATE_BEGIN(out);
+    MVX_REFUSE_FLOAT(sup, "Degrain");
     const mvx_super_info &si = sup->info;
     const int radius = a->radius;
     if (radius < 1 || radius > 6) MVX_FAIL("Degrain: radius must be between 1 and 6.");
@@ -596,7 +597,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_create(const m
     an.radius = radius; an.thsad = a->thsad; an.thsadc = a->thsadc; an.thsad2 = an.thsadc2 = MVX_UNSET;
     an.plane = a->plane; an.limit = a->limit; an.limitc = a->limitc; an.thscd1 = a->thscd1; an.thscd2 = a->thscd2;
     DgResolved r;
-    if (int rc = dg_resolve(name, &an, false, ad, si, &r, err)) return rc;
+    if (int rc = dg_resolve(name, &an, DG_PLAIN, ad, si, &r, err)) return rc;
     mvx_degrain *h;
     if (int rc = blk_new(&h, ad, si, src_pitch, super_pitch, dst_pitch, err)) return rc;
     h->radius = radius;
@@ -695,6 +696,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_frames(mvx_deg
 extern "C" __attribute__((visibility("default"))) int mvx_compensate_create(const mvx_compensate_args *a, const mvx_analysis_data *ad, const mvx_super *sup,
                                      const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_compensate **out, char *err) {
     MVX_CREATE_BEGIN(out);
+    MVX_REFUSE_FLOAT(sup, "Compensate");
     const mvx_super_info &si = sup->info;
     CompResolved r;
     if (int rc = comp_resolve("Compensate", a, ad, si, &r, err)) return rc;
@@ -1046,6 +1048,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_blockfps_create(const 
         const mvx_super *sup, int num_frames, int64_t fps_num, int64_t fps_den, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3],
         const ptrdiff_t dst_pitch[3], mvx_blockfps **out, char *err) {
     MVX_CREATE_BEGIN(out);
+    MVX_REFUSE_FLOAT(sup, "BlockFPS");
     const mvx_super_info &si = sup->info;
     const int mode = a->mode == MVX_UNSET ? 3 : a->mode;
     const int blend = a->blend == MVX_UNSET ? 1 : !!a->blend;

@@ -228,6 +228,147 @@ __global__ __launch_bounds__(256) void dn_cell_kernel(const DNParams *Pp, const 
     }
 }
 
+// ---- float clips (mvx_degrain_n_create_float): the cell kernel with a float accumulator.  Plan, lists, usable pass and the structure of the
+// gather are those above; the arithmetic is float32, every operation rounded on its own (include/mvtools_amd.h).
+
+// a block's value at the cell's row: V = (WSrc * s + w_1 * ref_1 + ... in list order) * (1 / 256).  An entry slot past the list's end is
+// loaded like dn_block_sum's (the chunk's first entry) and then left out by a select: nothing is added for it.
+template <int W>
+__device__ __forceinline__ void dn_block_value_float(DG_GL const unsigned char *slot, const unsigned long long *refB, long long rowOff, const float *s, float *V) {
+    const dn_v4 head = *(DG_GL const dn_v4 *)slot;
+    dn_v4 ent[DN_K / 2];
+#pragma unroll
+    for (int k = 0; k < DN_K / 2; k++) ent[k] = *(DG_GL const dn_v4 *)(slot + sizeof(DNHead) + 16 * k);
+    const int wsrc = (int)head[0], count = (int)head[1]; // DNHead
+    float S[W];
+#pragma unroll
+    for (int i = 0; i < W; i++) S[i] = (float)wsrc * s[i];
+    for (int e = 0; e < count; e += DN_K) {
+        unsigned off[DN_K], wr[DN_K];
+#pragma unroll
+        for (int k = 0; k < DN_K; k += 2) { off[k] = ent[k / 2][0]; wr[k] = ent[k / 2][1]; off[k + 1] = ent[k / 2][2]; wr[k + 1] = ent[k / 2][3]; }
+        DgRaw<float, W> raw[DN_K];
+        float w[DN_K];
+        bool valid[DN_K];
+#pragma unroll
+        for (int k = 0; k < DN_K; k++) {
+            valid[k] = e + k < count; // (k == 0 always is)
+            const unsigned o = valid[k] ? off[k] : off[0], r = (valid[k] ? wr[k] : wr[0]) >> 16;
+            w[k] = (float)(int)(short)(wr[k] & 0xffffu);
+            raw[k] = dg_load_raw<float, W>(dg_gl((const unsigned char *)refB[r]) + o + rowOff);
+        }
+        if (e + DN_K < count) {
+#pragma unroll
+            for (int k = 0; k < DN_K / 2; k++) ent[k] = *(DG_GL const dn_v4 *)(slot + sizeof(DNHead) + (size_t)(e + DN_K) * sizeof(DNEntry) + 16 * k);
+        }
+#pragma unroll
+        for (int k = 0; k < DN_K; k++) {
+#pragma unroll
+            for (int i = 0; i < W; i++) {
+                const float t = S[i] + w[k] * __uint_as_float(raw[k].d[i]);
+                S[i] = valid[k] ? t : S[i];
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < W; i++) V[i] = S[i] * (1.0f / 256.0f);
+}
+
+// dn_cell_kernel's cells and threads.  overlap > 0: acc = acc + V * win over the covering blocks (by outer, bx inner, ascending), divided by the
+// integer sum of those window weights (2047..2049), so that a flat area stays flat.  limit is on the 8-bit scale: L = limit / 255.  lv0: the
+// usable pass's result; a job none of whose references is usable keeps its source bit for bit (with overlap acc / wsum would not).
+template <int W>
+__global__ __launch_bounds__(256) void dn_cell_float_kernel(const DNParams *Pp, const DNJob *jobs, const unsigned char *const *refs, const unsigned *lv0, const unsigned char *plan,
+                                                            int planeFirst, int planesPerFrame) {
+    const DNParams &P = *Pp;
+    const int z = blockIdx.z, f = z / planesPerFrame, p = planeFirst + z % planesPerFrame;
+    const PlaneG &g = P.pl[p];
+    __shared__ unsigned long long refB[DN_MAX_REFS];
+    __shared__ int anyUsable;
+    if (threadIdx.x == 0) anyUsable = 0;
+    __syncthreads();
+    if ((int)threadIdx.x < P.nRefs) {
+        refB[threadIdx.x] = (unsigned long long)refs[((size_t)f * P.nRefs + threadIdx.x) * 3 + p];
+        if (lv0[f * P.nRefs + threadIdx.x] != 0u) anyUsable = 1;
+    }
+    __syncthreads();
+    const int c = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
+    const int x0 = c * W;
+    if (x0 >= g.W || y >= g.H) return;
+    const DNJob &J = jobs[f];
+    const unsigned char *srow = J.src[p] + (long long)y * g.srcPitch + (long long)x0 * sizeof(float);
+    unsigned char *drow = J.dst[p] + (long long)y * g.dstPitch + (long long)x0 * sizeof(float);
+    const bool fullW = x0 + W <= g.W;
+    float s[W];
+    if (fullW) {
+        const DgRaw<float, W> r = dg_load_raw<float, W>(dg_gl(srow));
+#pragma unroll
+        for (int i = 0; i < W; i++) s[i] = __uint_as_float(r.d[i]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < W; i++) s[i] = x0 + i < g.W ? ((const float *)srow)[i] : 0.0f;
+    }
+    float out[W];
+#pragma unroll
+    for (int i = 0; i < W; i++) out[i] = s[i];
+    if (g.process && anyUsable && x0 < g.WB && y < g.HB) { // the covered width is a multiple of W: a cell that starts inside it lies inside it
+        DG_GL const unsigned char *pl = dg_gl(plan + ((size_t)f * 2 + (p ? 1 : 0)) * P.nBlk * P.recBytes);
+        float V[W];
+        if (!P.overlap) {
+            const int bx = x0 / g.blkW, by = y / g.blkH;
+            const int px = x0 - bx * g.blkW, py = y - by * g.blkH;
+            DG_GL const unsigned char *slot = pl + (size_t)(by * P.nBlkX + bx) * P.recBytes;
+            dn_block_value_float<W>(slot, refB, (long long)py * g.supPitch + (long long)px * sizeof(float), s, V);
+#pragma unroll
+            for (int i = 0; i < W; i++) out[i] = V[i];
+        } else {
+            int bx0, bx1, by0, by1;
+            blk_cover(x0, g.blkW, g.stepX, P.nBlkX, bx0, bx1);
+            blk_cover(y, g.blkH, g.stepY, P.nBlkY, by0, by1);
+            float acc[W];
+            int wsum[W];
+#pragma unroll
+            for (int i = 0; i < W; i++) { acc[i] = 0.0f; wsum[i] = 0; }
+            const int16_t *win = P.win[p];
+            for (int by = by0; by <= by1; by++) {
+                const int py = y - by * g.stepY;
+                const int wby = BLK_WIN_ROW(by, P.nBlkY);
+                for (int bx = bx0; bx <= bx1; bx++) {
+                    const int px = x0 - bx * g.stepX; // 0 <= px <= blkW - W
+                    const int wbx = BLK_WIN_COL(bx, P.nBlkX);
+                    DG_GL const unsigned char *slot = pl + (size_t)(by * P.nBlkX + bx) * P.recBytes;
+                    const DgRaw<unsigned short, W> wr = dg_load_raw<unsigned short, W>(dg_gl((const unsigned char *)(win + (wby + wbx) * g.blkW * g.blkH + py * g.blkW + px)));
+                    dn_block_value_float<W>(slot, refB, (long long)py * g.supPitch + (long long)px * sizeof(float), s, V);
+#pragma unroll
+                    for (int i = 0; i < W; i++) {
+                        const int wi = dg_sample(wr, i);
+                        acc[i] = acc[i] + V[i] * (float)wi;
+                        wsum[i] += wi;
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < W; i++) out[i] = acc[i] / (float)wsum[i];
+        }
+        if (g.limit < 255) {
+            const float L = (float)g.limit / 255.0f;
+#pragma unroll
+            for (int i = 0; i < W; i++) out[i] = fmaxf(s[i] - L, fminf(s[i] + L, out[i]));
+        }
+    }
+    if (fullW) {
+        DG_GL unsigned char *d = dg_glw(drow);
+        if constexpr (W >= 4) {
+#pragma unroll
+            for (int k = 0; k < W / 4; k++) { dg_uv4 t = { __float_as_uint(out[4 * k]), __float_as_uint(out[4 * k + 1]), __float_as_uint(out[4 * k + 2]), __float_as_uint(out[4 * k + 3]) }; *(DG_GL dg_uv4 *)(d + 16 * k) = t; }
+        } else if constexpr (W == 2) { dg_uv2 t = { __float_as_uint(out[0]), __float_as_uint(out[1]) }; *(DG_GL dg_uv2 *)d = t; }
+        else *(DG_GL dg_uv1 *)d = __float_as_uint(out[0]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < W; i++) if (x0 + i < g.W) ((float *)drow)[i] = out[i];
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host object
 
 struct mvx_degrain_n {
@@ -240,21 +381,24 @@ struct mvx_degrain_n {
     DevBuf<unsigned char> dPlan;
     BlkWin win;
     bool out16 = false;              // 8-bit clip, 16-bit output planes
+    bool flt = false;                // float clip, float super clip, float output planes
 };
 
 static int dn_create(const mvx_degrain_n_args *a, const mvx_analysis_data *ad, const mvx_super *sup, const ptrdiff_t src_pitch[3], const ptrdiff_t super_pitch[3],
-                     const ptrdiff_t dst_pitch[3], bool out16, mvx_degrain_n **out, char *err) {
+                     const ptrdiff_t dst_pitch[3], int kind, mvx_degrain_n **out, char *err) {
     MVX_CREATE_BEGIN(out);
+    if (kind != DG_FLOAT) MVX_REFUSE_FLOAT(sup, "DegrainN");
     const mvx_super_info &si = sup->info;
     const int radius = a->radius;
     const char *name = "DegrainN";
     if (radius < 1 || radius > MVX_DEGRAIN_N_MAX_RADIUS) MVX_FAIL("%s: radius must be between 1 and %d.", name, MVX_DEGRAIN_N_MAX_RADIUS);
     DgResolved r;
-    if (int rc = dg_resolve(name, a, out16, ad, si, &r, err)) return rc;
+    if (int rc = dg_resolve(name, a, kind, ad, si, &r, err)) return rc;
     mvx_degrain_n *h;
     if (int rc = blk_new(&h, ad, si, src_pitch, super_pitch, dst_pitch, err)) return rc;
     h->info = r.info;
-    h->out16 = out16;
+    h->out16 = kind == DG_OUT16;
+    h->flt = kind == DG_FLOAT;
     DNParams &P = h->P;
     P.nRefs = 2 * radius; P.recBytes = dn_rec_bytes(P.nRefs);
     for (int d = 0; d < radius; d++) { P.thSAD[0][d] = r.info.thsad_d[d]; P.thSAD[1][d] = r.info.thsadc_d[d]; }
@@ -265,13 +409,17 @@ static int dn_create(const mvx_degrain_n_args *a, const mvx_analysis_data *ad, c
 
 extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_create(const mvx_degrain_n_args *a, const mvx_analysis_data *ad, const mvx_super *sup, const ptrdiff_t src_pitch[3],
                                     const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_degrain_n **out, char *err) {
-    return dn_create(a, ad, sup, src_pitch, super_pitch, dst_pitch, false, out, err);
+    return dn_create(a, ad, sup, src_pitch, super_pitch, dst_pitch, DG_PLAIN, out, err);
 }
 extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_create_out16(const mvx_degrain_n_args *a, const mvx_analysis_data *ad, const mvx_super *sup, const ptrdiff_t src_pitch[3],
                                     const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_degrain_n **out, char *err) {
-    return dn_create(a, ad, sup, src_pitch, super_pitch, dst_pitch, true, out, err);
+    return dn_create(a, ad, sup, src_pitch, super_pitch, dst_pitch, DG_OUT16, out, err);
 }
-extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_out_bits(const mvx_degrain_n *d) { return d->out16 ? 16 : d->P.bits; }
+extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_create_float(const mvx_degrain_n_args *a, const mvx_analysis_data *ad, const mvx_super *sup, const ptrdiff_t src_pitch[3],
+                                    const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_degrain_n **out, char *err) {
+    return dn_create(a, ad, sup, src_pitch, super_pitch, dst_pitch, DG_FLOAT, out, err);
+}
+extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_out_bits(const mvx_degrain_n *d) { return d->flt ? 32 : d->out16 ? 16 : d->P.bits; }
 
 extern "C" __attribute__((visibility("default"))) void mvx_degrain_n_get_info(const mvx_degrain_n *d, mvx_degrain_n_info *info) { *info = d->info; }
 extern "C" __attribute__((visibility("default"))) void mvx_degrain_n_destroy(mvx_degrain_n *d) { delete d; }
@@ -314,7 +462,11 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_frames(mvx_d
     for (int cls = 0; cls < (P.nplanes > 1 ? 2 : 1); cls++) { // one launch for the luma planes of all jobs, one for both chroma planes
         const int p0 = cls, npl = cls ? 2 : 1, W = blk_cell_width(P.pl[p0], 8);
         const dim3 grid(((P.pl[p0].W + W - 1) / W + 31) / 32, (P.pl[p0].H + 7) / 8, nframes * npl);
-        if (d->out16) dn_launch_cells<uint8_t, uint16_t>(W, grid, st, d->dP.p, dJ, dRefs, d->dPlan.p, p0, npl);
+        if (d->flt) {
+#define DNF(N) hipLaunchKernelGGL((dn_cell_float_kernel<N>), grid, dim3(256), 0, st, d->dP.p, dJ, dRefs, d->dLv0.p, d->dPlan.p, p0, npl)
+            switch (W) { case 1: DNF(1); break; case 2: DNF(2); break; case 4: DNF(4); break; default: DNF(8); break; }
+#undef DNF
+        } else if (d->out16) dn_launch_cells<uint8_t, uint16_t>(W, grid, st, d->dP.p, dJ, dRefs, d->dPlan.p, p0, npl);
         else if (P.bps == 1) dn_launch_cells<uint8_t, uint8_t>(W, grid, st, d->dP.p, dJ, dRefs, d->dPlan.p, p0, npl);
         else dn_launch_cells<uint16_t, uint16_t>(W, grid, st, d->dP.p, dJ, dRefs, d->dPlan.p, p0, npl);
     }

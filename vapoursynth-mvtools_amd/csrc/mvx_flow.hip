@@ -305,6 +305,7 @@ template <typename F> static void flow_launches(const FLParams &P, int nframes, 
 extern "C" __attribute__((visibility("default"))) int mvx_flowinter_create(const mvx_flowinter_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
         const mvx_super *sup, int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flow **out, char *err) {
     MVX_CREATE_BEGIN(out);
+    MVX_REFUSE_FLOAT(sup, "FlowInter");
     const mvx_super_info &si = sup->info;
     const float time = (float)a->time, ml = (float)a->ml;
     const int blend = a->blend == MVX_UNSET ? 1 : !!a->blend;
@@ -332,6 +333,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_flowfps_create(const m
         const mvx_super *sup, int num_frames, int64_t fps_num, int64_t fps_den, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3],
         const ptrdiff_t dst_pitch[3], mvx_flow **out, char *err) {
     MVX_CREATE_BEGIN(out);
+    MVX_REFUSE_FLOAT(sup, "FlowFPS");
     const mvx_super_info &si = sup->info;
     const int mask = a->mask == MVX_UNSET ? 2 : a->mask;
     const int blend = a->blend == MVX_UNSET ? 1 : !!a->blend;
@@ -680,6 +682,7 @@ static int fm_create(FMEngine *h, const char *name, int64_t thscd1, int32_t thsc
 extern "C" __attribute__((visibility("default"))) int mvx_flowcomp_create(const mvx_flowcomp_args *a, const mvx_analysis_data *vectors, const mvx_super *sup,
         int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flowcomp **out, char *err) {
     MVX_CREATE_BEGIN(out);
+    MVX_REFUSE_FLOAT(sup, "Flow");
     const double time = a->time;
     const int mode = a->mode == MVX_UNSET ? 0 : a->mode;
     int64_t thscd1; int32_t thscd2;
@@ -744,6 +747,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_flowblur_create(const 
         const mvx_super *sup, int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flowblur **out,
         char *err) {
     MVX_CREATE_BEGIN(out);
+    MVX_REFUSE_FLOAT(sup, "FlowBlur");
     const float blur = (float)a->blur;
     const int prec = a->prec == MVX_UNSET ? 1 : a->prec;
     int64_t thscd1; int32_t thscd2;

@@ -308,7 +308,7 @@ static void fps_fill_planes(PlaneG pl[3], const mvx_analysis_data *ad, const mvx
         g.dstPitch = dst_pitch[q];
         g.supPlaneStride = g.supPitch * (long long)((si.height >> sy) + 2 * (si.vpad >> sy));
         g.thIdx = p ? 1 : 0;
-        g.process = 1; g.limit = (1 << si.bits) - 1;
+        g.process = 1; g.limit = si.bits > 16 ? 255 : (1 << si.bits) - 1; // (a float clip's limits are on the 8-bit scale)
         g.shadow = 0;
     }
 }

@@ -83,6 +83,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_vectors_size(const mvx
 
 extern "C" __attribute__((visibility("default"))) int mvx_scale_vect_create(const mvx_analysis_data *in, int scale, const mvx_super *target, mvx_scale_vect **out, char *err) {
     MVX_CREATE_BEGIN(out);
+    MVX_REFUSE_FLOAT(target, "ScaleVect");
     const mvx_super_info &si = target->info;
     const int s = scale;
     if (s != 1 && s != 2 && s != 4) MVX_FAIL("ScaleVect: scale must be 1, 2 or 4.");

@@ -54,10 +54,13 @@ void mvx_level_plane(const mvx_super_info &si, int level, int plane, long long p
 
 static int argdef(int v, int d) { return v == MVX_UNSET ? d : v; }
 
-extern "C" __attribute__((visibility("default"))) int mvx_super_create(const mvx_super_args *a, mvx_super **out, char *err) { // MVSuper.c:140-264
+// flt: mvx_super_create_float -- 32-bit float samples, one level; its two messages come first, every other check is the integer create's
+static int super_create(const mvx_super_args *a, bool flt, mvx_super **out, char *err) { // MVSuper.c:140-264
     MVX_CREATE_BEGIN(out);
     mvx_super_info si;
     memset(&si, 0, sizeof(si));
+    if (flt && a->bits != 32) MVX_FAIL("Super: a float clip has 32 bits per sample.");
+    if (flt && a->levels != MVX_UNSET && a->levels != 1) MVX_FAIL("Super: a float super clip has one level (levels=1).");
     si.hpad = argdef(a->hpad, 16);
     si.vpad = argdef(a->vpad, 16);
     si.pel = argdef(a->pel, 2);
@@ -68,7 +71,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_super_create(const mvx
     if (si.pel != 1 && si.pel != 2 && si.pel != 4) MVX_FAIL("Super: pel must be 1, 2, or 4.");
     if (si.sharp < 0 || si.sharp > 2) MVX_FAIL("Super: sharp must be between 0 and 2 (inclusive).");
     if (si.rfilter < 0 || si.rfilter > 4) MVX_FAIL("Super: rfilter must be between 0 and 4 (inclusive).");
-    if (a->bits < 8 || a->bits > 16 || a->subsampling_w < 0 || a->subsampling_w > 1 || a->subsampling_h < 0 || a->subsampling_h > 1 ||
+    if ((!flt && (a->bits < 8 || a->bits > 16)) || a->subsampling_w < 0 || a->subsampling_w > 1 || a->subsampling_h < 0 || a->subsampling_h > 1 ||
         a->width <= 0 || a->height <= 0)
         MVX_FAIL("Super: input clip must be GRAY, 420, 422, 440, or 444, up to 16 bits, with constant dimensions.");
     if (si.hpad < 0 || si.vpad < 0) MVX_FAIL("Super: hpad and vpad must not be negative.");
@@ -77,6 +80,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_super_create(const mvx
     si.modeYUV = si.chroma ? 7 : 1;
     si.xRatioUV = 1 << a->subsampling_w;
     si.yRatioUV = 1 << a->subsampling_h;
+    if (flt) si.levels = 1;
     int nLevelsMax = 0; // :220-227
     while (mvx_plane_height_luma(si.height, nLevelsMax, si.yRatioUV, si.vpad) >= si.yRatioUV * 2 &&
            mvx_plane_width_luma(si.width, nLevelsMax, si.xRatioUV, si.hpad) >= si.xRatioUV * 2)
@@ -94,9 +98,14 @@ extern "C" __attribute__((visibility("default"))) int mvx_super_create(const mvx
     }
     mvx_super *s = new mvx_super();
     s->info = si;
+    s->is_float = flt;
     *out = s;
     return MVX_OK;
 }
+
+extern "C" __attribute__((visibility("default"))) int mvx_super_create(const mvx_super_args *a, mvx_super **out, char *err) { return super_create(a, false, out, err); }
+extern "C" __attribute__((visibility("default"))) int mvx_super_create_float(const mvx_super_args *a, mvx_super **out, char *err) { return super_create(a, true, out, err); }
+extern "C" __attribute__((visibility("default"))) int mvx_super_is_float(const mvx_super *s) { return s->is_float ? 1 : 0; }
 
 extern "C" __attribute__((visibility("default"))) void mvx_super_destroy(mvx_super *s) { delete s; }
 extern "C" __attribute__((visibility("default"))) void mvx_super_get_info(const mvx_super *s, mvx_super_info *info) { *info = s->info; }
@@ -256,6 +265,108 @@ template <typename T> __global__ __launch_bounds__(256) void super_avg_kernel(Su
             v = (a[X + o.ax] + b[X] + 1) >> 1;
         }
         d[X] = (T)v;
+    }
+}
+
+// ---- float super clips (mvx_super_create_float): level 0 only.  Siblings of super_level0_kernel and super_avg_kernel with float tiles and the
+// arithmetic of mvx_super_float_rule.h; the same tile, halo, clamped coordinates and defined rectangles.  No super_rows_kernel share (XA == XB).
+#include "mvx_super_float_rule.h"
+
+typedef float sf_v4 __attribute__((ext_vector_type(4), aligned(16)));
+
+template <int SHARP, int PEL>
+__global__ __launch_bounds__(256) void super_level0_float_kernel(SuperL0Args A) {
+    __shared__ float sp0[L0_LH][L0_LW + 1];
+    __shared__ float sv[L0_TH][L0_LW + 1];
+    const int z = blockIdx.z, f = z / 3, p = z % 3;
+    if (p >= A.nplanes || !(A.modeYUV & (1 << p))) return;
+    const SuperPlaneGeom g = A.g[p];
+    const int X0 = blockIdx.x * L0_TW, Y0 = blockIdx.y * L0_TH;
+    if (X0 >= g.pw || Y0 >= g.ph) return;
+    const unsigned char *src = (const unsigned char *)A.src[f * 3 + p];
+    unsigned char *dst = (unsigned char *)A.dst[f * 3 + p];
+    const int tid = threadIdx.x;
+
+    for (int i = tid; i < L0_LH * L0_LW; i += 256) { // phase 1: the padded tile (+halo), coordinates clamped
+        int ly = i / L0_LW, lx = i - ly * L0_LW;
+        int X = iclamp(X0 - L0_HL + lx, 0, g.pw - 1), Y = iclamp(Y0 - L0_HL + ly, 0, g.ph - 1);
+        int sx = iclamp(X - g.hpad, 0, g.w - 1), sy = iclamp(Y - g.vpad, 0, g.h - 1);
+        sp0[ly][lx] = ((const float *)(src + (long long)sy * g.src_pitch))[sx];
+    }
+    __syncthreads();
+    if (PEL > 1) { // phase 2: the (unrounded) vertical half-pel plane for the tile rows, all tile columns incl. halo
+        for (int i = tid; i < L0_TH * L0_LW; i += 256) {
+            int ty = i / L0_LW, lx = i - ty * L0_LW;
+            int Y = Y0 + ty;
+            float v = 0.0f;
+            if (Y < g.ph) v = mvx_sf_half<SHARP>([&](int yy) { return sp0[yy - Y0 + L0_HL][lx]; }, Y, g.ph);
+            sv[ty][lx] = v;
+        }
+        __syncthreads();
+    }
+    // phase 3: 8 consecutive samples per thread
+    const int ty = tid >> 4, tx8 = (tid & 15) * 8;
+    const int Y = Y0 + ty;
+    if (Y >= g.ph) return;
+    const long long planeStride = g.dst_pitch * g.ph;
+    const int idxH = PEL == 2 ? 1 : 2, idxV = PEL == 2 ? 2 : 8, idxHV = PEL == 2 ? 3 : 10;
+    float *r0 = (float *)(dst + (long long)Y * g.dst_pitch);
+    float *rH = (float *)(dst + idxH * planeStride + (long long)Y * g.dst_pitch);
+    float *rV = (float *)(dst + idxV * planeStride + (long long)Y * g.dst_pitch);
+    float *rHV = (float *)(dst + idxHV * planeStride + (long long)Y * g.dst_pitch);
+    float o0[8], oH[8], oV[8], oHV[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        int X = X0 + tx8 + k;
+        int lx = tx8 + k + L0_HL;
+        o0[k] = sp0[ty + L0_HL][lx];
+        if (PEL > 1) {
+            int Xc = min(X, g.pw - 1); // keeps LDS indices in range for the (unstored) overhang of the last tile
+            oH[k] = mvx_sf_half<SHARP>([&](int xx) { return sp0[ty + L0_HL][xx - X0 + L0_HL]; }, Xc, g.pw);
+            oV[k] = sv[ty][lx];
+            if (SHARP == 0)
+                oHV[k] = mvx_sf_diagonal(sp0[ty + L0_HL][lx], sp0[ty + L0_HL][lx + 1], sp0[ty + L0_HL + 1][lx], sp0[ty + L0_HL + 1][lx + 1], Y >= g.ph - 1, Xc >= g.pw - 1);
+            else
+                oHV[k] = mvx_sf_half<SHARP>([&](int xx) { return sv[ty][xx - X0 + L0_HL]; }, Xc, g.pw);
+        }
+    }
+    const int Xs = X0 + tx8;
+    if (Xs + 8 <= g.pw) { // rows start at multiples of 16 bytes (pitch and plane pointers are checked), Xs is a multiple of 8 samples
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            *(sf_v4 *)(r0 + Xs + 4 * h) = sf_v4{ o0[4 * h], o0[4 * h + 1], o0[4 * h + 2], o0[4 * h + 3] };
+            if (PEL > 1) {
+                *(sf_v4 *)(rH + Xs + 4 * h) = sf_v4{ oH[4 * h], oH[4 * h + 1], oH[4 * h + 2], oH[4 * h + 3] };
+                *(sf_v4 *)(rV + Xs + 4 * h) = sf_v4{ oV[4 * h], oV[4 * h + 1], oV[4 * h + 2], oV[4 * h + 3] };
+                *(sf_v4 *)(rHV + Xs + 4 * h) = sf_v4{ oHV[4 * h], oHV[4 * h + 1], oHV[4 * h + 2], oHV[4 * h + 3] };
+            }
+        }
+    } else {
+        for (int k = 0; k < 8 && Xs + k < g.pw; k++) {
+            r0[Xs + k] = o0[k];
+            if (PEL > 1) { rH[Xs + k] = oH[k]; rV[Xs + k] = oV[k]; rHV[Xs + k] = oHV[k]; }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void super_avg_float_kernel(SuperAvgArgs A) {
+    const int z = blockIdx.z, f = z / 3, p = z % 3;
+    if (p >= A.nplanes || !(A.modeYUV & (1 << p))) return;
+    const SuperPlaneGeom g = A.g[p];
+    const int X = blockIdx.x * 256 + threadIdx.x, Y = blockIdx.y;
+    if (X >= g.pw || Y >= g.ph) return;
+    unsigned char *dst = (unsigned char *)A.dst[f * 3 + p];
+    const long long ps = g.dst_pitch * g.ph;
+    for (int k = 0; k < A.nops; k++) {
+        const AvgOp o = A.ops[k];
+        float *d = (float *)(dst + o.d * ps + (long long)Y * g.dst_pitch);
+        float v = 0.0f;
+        if (X < g.pw - o.ax && Y < g.ph - o.ay) {
+            const float *a = (const float *)(dst + o.a * ps + (long long)(Y + o.ay) * g.dst_pitch);
+            const float *b = (const float *)(dst + o.b * ps + (long long)Y * g.dst_pitch);
+            v = mvx_sf_avg(a[X + o.ax], b[X]);
+        }
+        d[X] = v;
     }
 }
 
@@ -465,7 +576,7 @@ __global__ __launch_bounds__(256) void super_shadow_kernel(ShadowArgs A) {
 // without); the search then simply loads from the planes themselves.  Measured again r6 (cfg2): the search -12 %, but the whole step +5.6 %.
 // r3: 8-bit 4:2:x clips get the UV-interleaved plane too (U and V of a chroma block in ONE row of twice the width: half the load
 // instructions and cache lines per candidate), still no luma copy.
-extern "C" __attribute__((visibility("default"))) int mvx_super_shadow_copies(const mvx_super *s) { return s->info.bits <= 8 ? (s->info.num_planes >= 3 ? 1 : 0) : 1; }
+extern "C" __attribute__((visibility("default"))) int mvx_super_shadow_copies(const mvx_super *s) { return s->is_float ? 0 : s->info.bits <= 8 ? (s->info.num_planes >= 3 ? 1 : 0) : 1; }
 // bytes of shadow data a caller must provide behind plane p: the luma plane's shifted copy, and -- behind the U plane -- ONE plane
 // of twice the chroma size holding U and V interleaved (every chroma position is dword-aligned there, no shifted copy needed)
 extern "C" __attribute__((visibility("default"))) void mvx_super_shadow_bytes(const mvx_super *s, const ptrdiff_t pitch[3], size_t extra[3]) {
@@ -500,6 +611,7 @@ static int shadow_launch(const mvx_super_info &si, int nframes, void *const *dpl
 }
 extern "C" __attribute__((visibility("default"))) int mvx_super_shadow_frames(const mvx_super *s, int nframes, void *const *planes, const ptrdiff_t pitch[3],
                                                                               const ptrdiff_t copy_stride[3], void *stream) {
+    if (s->is_float) { mvx_set_error("mvx_super_shadow_frames: float super clips are not supported."); return MVX_E_ARG; }
     if (nframes <= 0 || !mvx_super_shadow_copies(s)) return MVX_OK;
     const mvx_super_info &si = s->info;
     hipStream_t st = (hipStream_t)stream;
@@ -528,6 +640,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_super_pelclip_mode(con
     const mvx_super_info &si = s->info;
     if (err) err[0] = 0;
     *mode = 0;
+    if (s->is_float) { if (err) snprintf(err, MVX_ERRLEN, "Super: float super clips take no pelclip."); mvx_set_error("Super: float super clips take no pelclip."); return MVX_E_ARG; }
     if (si.pel < 2) return MVX_OK;
     if (pelclip_width == si.width * si.pel && pelclip_height == si.height * si.pel) { *mode = 1; return MVX_OK; }
     if (pelclip_width == (si.width + si.hpad * 2) * si.pel && pelclip_height == (si.height + si.vpad * 2) * si.pel) { *mode = 2; return MVX_OK; }
@@ -539,6 +652,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_super_pelclip_mode(con
 extern "C" __attribute__((visibility("default"))) int mvx_super_frames_pelclip(mvx_super *s, int nframes, const void *const *src, const ptrdiff_t src_pitch[3],
                                 const void *const *pelclip, const ptrdiff_t pelclip_pitch[3], int pelclip_mode, void *const *dst,
                                 const ptrdiff_t dst_pitch[3], void *stream) {
+    if (s->is_float) { mvx_set_error("mvx_super_frames_pelclip: float super clips are not supported."); return MVX_E_ARG; }
     if (pelclip_mode < 0 || pelclip_mode > 2 || (pelclip_mode && s->info.pel < 2)) { mvx_set_error("mvx_super_frames_pelclip: bad pelclip mode"); return MVX_E_ARG; }
     if (pelclip_mode) {
         if (!pelclip || !pelclip_pitch) { mvx_set_error("mvx_super_frames_pelclip: no pelclip frames"); return MVX_E_ARG; }
@@ -552,10 +666,61 @@ extern "C" __attribute__((visibility("default"))) int mvx_super_frames_pelclip(m
     return super_frames_impl(s, nframes, src, src_pitch, pelclip, pelclip_pitch, pelclip_mode, dst, dst_pitch, nullptr, stream);
 }
 
+// level 0 of a float super clip: one tiled kernel, and for pel 4 the two dependent passes of averages
+static int super_frames_float(mvx_super *s, int nframes, const void *const *src, const ptrdiff_t src_pitch[3], void *const *dst, const ptrdiff_t dst_pitch[3], void *stream) {
+    const mvx_super_info &si = s->info;
+    hipStream_t st = (hipStream_t)stream;
+    CallGuard::Scope scope(g_scratch_guard, st);
+    for (int p = 0; p < si.num_planes; p++) {
+        if (dst_pitch[p] % 16 || src_pitch[p] % 4) { mvx_set_error("mvx_super_frames: float planes need a dst pitch that is a multiple of 16 bytes and a src pitch that is a multiple of 4"); return MVX_E_ARG; }
+        for (int f = 0; f < nframes; f++)
+            if (((uintptr_t)dst[f * 3 + p] % 16) || ((uintptr_t)src[f * 3 + p] % 4)) { mvx_set_error("mvx_super_frames: float planes must be aligned (dst to 16 bytes, src to 4)"); return MVX_E_ARG; }
+    }
+    void *dsrc = nullptr, *ddst = nullptr;
+    int rc;
+    if ((rc = upload_ptrs(0, src, (size_t)nframes * 3, st, &dsrc))) return rc;
+    if ((rc = upload_ptrs(1, (const void *const *)dst, (size_t)nframes * 3, st, &ddst))) return rc;
+    SuperL0Args A;
+    memset(&A, 0, sizeof(A)); // XA == XB: every column is the tiled kernel's
+    A.src = (const void *const *)dsrc; A.dst = (void *const *)ddst;
+    A.pel = si.pel; A.bits = si.bits; A.modeYUV = si.modeYUV; A.nplanes = si.num_planes;
+    int maxpw = 0, maxph = 0;
+    for (int p = 0; p < si.num_planes; p++) {
+        LevelPlane lp;
+        mvx_level_plane(si, 0, p, dst_pitch[p], &lp);
+        A.g[p] = { lp.w, lp.h, lp.hpad, lp.vpad, lp.pw, lp.ph, (long long)src_pitch[p], (long long)dst_pitch[p] };
+        if (lp.pw > maxpw) maxpw = lp.pw;
+        if (lp.ph > maxph) maxph = lp.ph;
+    }
+    dim3 grid((maxpw + L0_TW - 1) / L0_TW, (maxph + L0_TH - 1) / L0_TH, nframes * 3);
+#define L0F(S, P) hipLaunchKernelGGL((super_level0_float_kernel<S, P>), grid, dim3(256), 0, st, A)
+    if (si.pel == 1) L0F(2, 1);
+    else if (si.pel == 2) { if (si.sharp == 0) L0F(0, 2); else if (si.sharp == 1) L0F(1, 2); else L0F(2, 2); }
+    else { if (si.sharp == 0) L0F(0, 4); else if (si.sharp == 1) L0F(1, 4); else L0F(2, 4); }
+#undef L0F
+    if (si.pel == 4) {
+        SuperAvgArgs B;
+        memset(&B, 0, sizeof(B));
+        B.dst = (void *const *)ddst; B.modeYUV = si.modeYUV; B.nplanes = si.num_planes;
+        for (int p = 0; p < 3; p++) B.g[p] = A.g[p];
+        dim3 g2((maxpw + 255) / 256, maxph, nframes * 3);
+        const AvgOp pass1[8] = { { 1, 0, 2, 0, 0 }, { 9, 8, 10, 0, 0 }, { 4, 0, 8, 0, 0 }, { 6, 2, 10, 0, 0 },
+                                 { 3, 0, 2, 1, 0 }, { 11, 8, 10, 1, 0 }, { 12, 0, 8, 0, 1 }, { 14, 2, 10, 0, 1 } };
+        const AvgOp pass2[4] = { { 5, 4, 6, 0, 0 }, { 13, 12, 14, 0, 0 }, { 7, 4, 6, 1, 0 }, { 15, 12, 14, 1, 0 } };
+        memcpy(B.ops, pass1, sizeof(pass1)); B.nops = 8;
+        hipLaunchKernelGGL(super_avg_float_kernel, g2, dim3(256), 0, st, B);
+        memcpy(B.ops, pass2, sizeof(pass2)); B.nops = 4;
+        hipLaunchKernelGGL(super_avg_float_kernel, g2, dim3(256), 0, st, B);
+    }
+    HIP_CHECK(hipGetLastError());
+    return MVX_OK;
+}
+
 static int super_frames_impl(mvx_super *s, int nframes, const void *const *src, const ptrdiff_t src_pitch[3], const void *const *pelclip,
                              const ptrdiff_t pelclip_pitch[3], int pelMode, void *const *dst, const ptrdiff_t dst_pitch[3], const ptrdiff_t *shadow_stride,
                              void *stream) {
     if (nframes <= 0) return MVX_OK;
+    if (s->is_float) return super_frames_float(s, nframes, src, src_pitch, dst, dst_pitch, stream);
     if (shadow_stride && !mvx_super_shadow_copies(s)) shadow_stride = nullptr;
     if (shadow_stride) { int rc = shadow_check(s->info, dst_pitch, shadow_stride); if (rc) return rc; }
     const mvx_super_info &si = s->info;
@@ -779,6 +944,7 @@ extern "C" __attribute__((visibility("default"))) void mvx_finest_size(const mvx
 
 extern "C" __attribute__((visibility("default"))) int mvx_finest_frames(const mvx_super *s, int nframes, const void *const *super_frames, const ptrdiff_t super_pitch[3],
                                                                         void *const *dst, const ptrdiff_t dst_pitch[3], void *stream) {
+    if (s->is_float) { mvx_set_error("Finest: float super clips are not supported."); return MVX_E_ARG; }
     hipStream_t st = (hipStream_t)stream;
     const mvx_super_info &si = s->info;
     const int logPel = si.pel == 4 ? 2 : si.pel == 2 ? 1 : 0;

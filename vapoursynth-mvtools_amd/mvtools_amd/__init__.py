@@ -295,6 +295,8 @@ def lib():
         L.mvx_last_error.restype = C.c_char_p
         L.mvx_version.restype = C.c_char_p
         L.mvx_super_create.argtypes = [P(SuperArgs), P(C.c_void_p), C.c_char_p]
+        L.mvx_super_create_float.argtypes = L.mvx_super_create.argtypes
+        L.mvx_super_is_float.argtypes = [C.c_void_p]
         L.mvx_super_destroy.argtypes = [C.c_void_p]
         L.mvx_super_get_info.argtypes = [C.c_void_p, P(SuperInfo)]
         L.mvx_super_frames.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), P(C.c_ssize_t), P(C.c_void_p), P(C.c_ssize_t), C.c_void_p]
@@ -323,6 +325,7 @@ def lib():
         L.mvx_degrain_n_create.argtypes = [P(DegrainNArgs), P(AnalysisData), C.c_void_p, P(C.c_ssize_t), P(C.c_ssize_t), P(C.c_ssize_t),
                                            P(C.c_void_p), C.c_char_p]
         L.mvx_degrain_n_create_out16.argtypes = L.mvx_degrain_n_create.argtypes
+        L.mvx_degrain_n_create_float.argtypes = L.mvx_degrain_n_create.argtypes
         L.mvx_degrain_n_out_bits.argtypes = [C.c_void_p]
         L.mvx_degrain_n_get_info.argtypes = [C.c_void_p, P(DegrainNInfo)]
         L.mvx_degrain_n_get_info.restype = None
@@ -505,7 +508,7 @@ def _stream():
 def _pitches(planes):
     a = (C.c_ssize_t * 3)()
     for i, p in enumerate(planes):
-        a[i] = p.stride(0)
+        a[i] = p.stride(0) * p.element_size()  # bytes (planes are byte tensors everywhere but in a float clip, whose planes may be float32)
     return a
 
 
@@ -557,20 +560,25 @@ def plane_to_numpy(t, width, dtype):
 
 
 class Super(_Handle):
-    """mv.Super -- MVSuper.c:140-275."""
+    """mv.Super -- MVSuper.c:140-275.  sample_float=True with bits=32: the super clip of a float32 clip (mvx_super_create_float) -- one level, no
+    shadow planes, planes of float32; only DegrainN consumes it."""
     _destroy = "mvx_super_destroy"
 
     def __init__(self, width, height, bits=8, subsampling=(1, 1), gray=False, hpad=None, vpad=None, pel=None, levels=None,
-                 chroma=None, sharp=None, rfilter=None, shadow=None):
+                 chroma=None, sharp=None, rfilter=None, shadow=None, sample_float=False):
         a = SuperArgs(width, height, bits, subsampling[0], subsampling[1], int(gray), _u(hpad), _u(vpad), _u(pel), _u(levels),
                       _u(chroma), _u(sharp), _u(rfilter))
         self.h = C.c_void_p()
         err = C.create_string_buffer(ERRLEN)
-        _check(lib().mvx_super_create(C.byref(a), C.byref(self.h), err), err)
+        self.is_float = bool(sample_float)
+        create = lib().mvx_super_create_float if self.is_float else lib().mvx_super_create
+        _check(create(C.byref(a), C.byref(self.h), err), err)
         self.info = SuperInfo()
         lib().mvx_super_get_info(self.h, C.byref(self.info))
-        self.dtype = np.uint8 if bits <= 8 else np.uint16
-        self.bps = 1 if bits <= 8 else 2
+        self.dtype = np.float32 if self.is_float else np.uint8 if bits <= 8 else np.uint16
+        self.bps = 4 if self.is_float else 1 if bits <= 8 else 2
+        if self.is_float:
+            shadow = False
         self.nplanes = self.info.num_planes
         self.pitch = [((self.info.plane_width[p] * self.bps + 255) // 256) * 256 for p in range(self.nplanes)]
         # developer experiment (r4): row pitch as a number of 128-byte lines that is odd / a given residue -- how the rows of a block and the
@@ -910,7 +918,9 @@ class DegrainN(_Handle):
     read at any radius, each reference weighed against the threshold of its temporal distance -- thsad at distance 1 falling to thsad2 at distance
     `radius` (thsad2 / thsadc2 None: no fall-off).  analysis_data = the vector clips' MVTools_MVAnalysisData.
     out16: an 8-bit clip (8-bit super clip and vectors, thresholds in 8-bit units) written as 16-bit planes -- a block's weighted sum before its
-    >> 8, see mvx_degrain_n_create_out16; limit / limitc are then 0..65535, and dst_pitch defaults to rows of 16-bit samples rounded up to 256 bytes."""
+    >> 8, see mvx_degrain_n_create_out16; limit / limitc are then 0..65535, and dst_pitch defaults to rows of 16-bit samples rounded up to 256 bytes.
+    A float super clip (Super(..., bits=32, sample_float=True)) selects mvx_degrain_n_create_float: float32 clip, super clip and output, vectors and
+    thresholds from a search on an 8..16 bit copy, limit / limitc on the 8-bit scale 0..255; out16 with it is refused by the library."""
     _destroy = "mvx_degrain_n_destroy"
 
     def __init__(self, radius, sup, analysis_data, src_pitch, dst_pitch=None, thsad=None, thsadc=None, thsad2=None, thsadc2=None, plane=None, limit=None,
@@ -918,6 +928,7 @@ class DegrainN(_Handle):
         self.sup = sup
         self.radius = radius
         self.out16 = bool(out16)
+        self.is_float = bool(getattr(sup, "is_float", False))
         a = DegrainNArgs(radius, _u(thsad), _u(thsadc), _u(thsad2), _u(thsadc2), _u(plane), _u(limit), _u(limitc), _u(thscd1), _u(thscd2))
         ad = AnalysisData.from_buffer_copy(bytes(analysis_data))
         if self.out16:
@@ -925,13 +936,13 @@ class DegrainN(_Handle):
         dst_pitch = dst_pitch or src_pitch
         self.h = C.c_void_p()
         err = C.create_string_buffer(ERRLEN)
-        create = lib().mvx_degrain_n_create_out16 if self.out16 else lib().mvx_degrain_n_create
+        create = lib().mvx_degrain_n_create_out16 if self.out16 else lib().mvx_degrain_n_create_float if self.is_float else lib().mvx_degrain_n_create
         _check(create(C.byref(a), C.byref(ad), sup.h, _pad3(src_pitch), _pad3(sup.pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
         self.src_pitch, self.dst_pitch = list(src_pitch), list(dst_pitch)
 
     @property
     def out_bits(self):
-        """bits per sample of the planes run() writes: 16 with out16, else the clip's depth"""
+        """bits per sample of the planes run() writes: 16 with out16, 32 for a float clip, else the clip's depth"""
         return lib().mvx_degrain_n_out_bits(self.h)
 
     def info(self):
@@ -960,7 +971,7 @@ class DegrainN(_Handle):
             if len(refs) != nr or len(blobs) != nr:
                 raise ValueError("DegrainN: a job needs %d references and blobs" % nr)
             for p in range(self.sup.nplanes):
-                assert src[p].stride(0) == self.src_pitch[p] and out[i][p].stride(0) == self.dst_pitch[p]
+                assert src[p].stride(0) * src[p].element_size() == self.src_pitch[p] and out[i][p].stride(0) * out[i][p].element_size() == self.dst_pitch[p]
                 arr[i].src[p] = src[p].data_ptr()
                 arr[i].dst[p] = out[i][p].data_ptr()
             for r in range(nr):
