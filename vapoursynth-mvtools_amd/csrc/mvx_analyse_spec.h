@@ -42,6 +42,16 @@
 #else
 #define MVX_SPEC_PACK 1
 #endif
+// -DMVX_SPEC_NORUN (tools/build_variant.py: the A/B build): no run form -- a stage-2 window of the overlapping 16x16 row passes whose blocks end on two or three
+// centres takes block form like any other window that is not in strip form (SpecSearcher::RUN).  -DMVX_SPEC_RUNMAX=2: run form for two runs only
+#ifdef MVX_SPEC_NORUN
+#define MVX_SPEC_RUN 0
+#else
+#define MVX_SPEC_RUN 1
+#endif
+#ifndef MVX_SPEC_RUNMAX
+#define MVX_SPEC_RUNMAX 3
+#endif
 // MVX_SPEC_PLANEORDER: the order in which the strip-form passes of a Hex2 level take the 14 pattern points (slots stay reference indices): 1 = by sub-pel
 // plane -- at pel 2 the first eight are the six points with an odd x and an even y and the two with both even, the last six those with an odd y --, 0 = the
 // reference's own order (-DMVX_SPEC_PLANEORDER=0: the A/B build)
@@ -63,7 +73,8 @@ static __device__ unsigned long long g_specprof[SPROF_N];
 #define SPEC_PROF_DUMP_() ((void)0)
 #endif
 #ifdef MVX_SPEC_STATS
-static __device__ unsigned long long g_specstat[MVX_MAX_LEVELS][10]; // per level: blocks in speculated rows, of them searched live, live because the flag was clear, rescues; 16x16 row passes: windows of stage 2 in strip form, in block form, blocks of block-form windows whose centre differs from the window's first block, block-form windows because of the limits alone; passes of stage 2 that ran, passes that packing saved
+#define SPEC_NSTAT 17
+static __device__ unsigned long long g_specstat[MVX_MAX_LEVELS][SPEC_NSTAT]; // (10-14: windows of stage 2 that are not in strip form by their runs of equal centres -- one, two, three, four or more, a run that fails the limits test; 15: run-form passes that ran, 16: passes run form saved against block form) per level: blocks in speculated rows, of them searched live, live because the flag was clear, rescues; 16x16 row passes: windows of stage 2 in strip form, in block form, blocks of block-form windows whose centre differs from the window's first block, block-form windows because of the limits alone; passes of stage 2 that ran, passes that packing saved
 #endif
 
 // SWIN: row loads a lane keeps in flight in the row passes (12 = half a pass; 24 = a whole pass: the builds with 256 registers)
@@ -257,6 +268,10 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
     static_assert(SW <= 63, "the wait for a strip is s_waitcnt vmcnt(SW)");
     // PACK: stage 2 of four consecutive strip-form windows of a Hex2 level in seven passes, not eight (search_level_spec); needs both strip buffers
     static constexpr bool PACK = SDMA && MVX_SPEC_PACK;
+    // RUN: stage 2 of a window whose blocks end on two or three centres, in runs of consecutive blocks, in RUN FORM (search_level_spec): every run a strip of its own
+    // around its centre, 7 + R column lanes per candidate -- the overlapping 16x16 builds, with one strip buffer or two
+    static constexpr bool RUN = STRIP_OK && !SIDE && HC == 1 && MVX_SPEC_RUN;
+    static_assert(!RUN || SPEC_TB / SW_BLOCKS <= 4, "run form keeps one byte per window of a group");
     // the reference pattern index of the i-th point a strip-form window of a Hex2 level evaluates: 1, 2, 4, 5, 8, 9, 0, 3 | 6, 7, 10, 11, 12, 13
     __device__ __forceinline__ static int hex_ord(int i) {
         if constexpr (MVX_SPEC_PLANEORDER != 0) return (int)(0xDCBA7630985421ull >> (4 * i)) & 15;
@@ -454,7 +469,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
             }
         }
 #ifdef MVX_SPEC_STATS
-        unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0, st4 = 0, st5 = 0, st6 = 0, st7 = 0, st8 = 0, st9 = 0;
+        unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0, st4 = 0, st5 = 0, st6 = 0, st7 = 0, st8 = 0, st9 = 0, stR[7] = {0, 0, 0, 0, 0, 0, 0};
 #endif
 
         int prevX = 0, prevY = 0, prevSad = 0;
@@ -646,8 +661,9 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                             //     vector in strip form (lanes 56-63 = the window's eight 16-byte columns);
                             //   A2a, one lane per block: the predictor phase -> the block's refinement centre W (under the hypothesis left == up);
                             //   stage 2: the pattern around W.  Strip form where the window's blocks share W and keep the pattern inside their limits
-                            //     (lane = (candidate, column), eight candidates per pass: 2 passes on Hex2 levels, 3 on exhaustive ones); block form
-                            //     elsewhere (four candidates per pass: 4 / 6 passes).
+                            //     (lane = (candidate, column), eight candidates per pass: 2 passes on Hex2 levels, 3 on exhaustive ones); run form where
+                            //     they end on two or three centres, in runs of consecutive blocks (RUN: a strip per run, seven or six candidates per pass:
+                            //     2 or 3 / 4 passes); block form elsewhere (four candidates per pass: 4 / 6 passes).
                             // (the first form evaluated the pattern around UP and gave every block whose predictor phase ended elsewhere to the live
                             // search: one block in eight one level up from the finest, most blocks of the chains with an odd frame distance there)
                             if constexpr (STRIP_OK) {
@@ -663,6 +679,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                     staged2 = true;
                                     unsigned stripW = 0; // stage 2: windows in strip form
                                     unsigned packS = 0;  // stage 2: walk positions at which four strip-form windows in a row start (PACK: seven passes for the four)
+                                    unsigned runW = 0;   // stage 2: windows in run form, a byte each: the block at which the second run starts (1-6) | that of the third run << 3 (0: two runs)
                                     int pkW = 0;         // this lane's block: the refinement centre
                                     // lane roles: strip form (candidate l >> 3, column l & 7); block form (candidate l / 14, block (l % 14) >> 1, half l & 1);
                                     // recomputed from an opaque lane number in every pass (values derived from the lane number are loop invariants: the
@@ -693,6 +710,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                         const int bxf = hpad + stepX * (c0 + f);
                                         const int bufW = SDMA ? (widx(w) & 1) * SBUF : 0;
                                         const bool stripWin = st == 2 && ((stripW >> w) & 1);
+                                        const int rb = (RUN && st == 2) ? (int)((runW >> (8 * w)) & 63) : 0;
                                         // the block lanes' vectors come from the lanes that own the blocks: fetched HERE, with every lane active (ds_bpermute returns 0
                                         // for a source lane that is masked off, and in stage 1 lanes 56-63 take the other branch below)
                                         const int meB = min(mB, L - 1), colB = f + meB; // (lanes beyond the window repeat its last block)
@@ -700,6 +718,30 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                         if (st == 1) {
                                             bU = __builtin_amdgcn_ds_bpermute(colB << 2, pkU); bAh = __builtin_amdgcn_ds_bpermute(colB << 2, pkAh);
                                             bG = __builtin_amdgcn_ds_bpermute(colB << 2, pkG); bH = __builtin_amdgcn_ds_bpermute(colB << 2, pkH);
+                                        } else if (RUN && rb != 0) {
+                                            // RUN FORM: R = 2 (3) runs of blocks, each with one centre, are R strips side by side: a run of k blocks is k + 1 columns, the window 7 + R
+                                            // column lanes per candidate and 7 (6) candidates per pass.  Lane = (candidate lq / NL, position lq % NL); run r holds the positions
+                                            // (its first block) + r .. (its end) + r, so position - r is the lane's column of the window's one source strip, and block m is the sum of
+                                            // the lanes of its columns m and m + 1 as in strip form.  The points go in the reference's order: slot = point.
+                                            const int c1 = rb & 7, c2 = rb >> 3;
+                                            const bool r3 = c2 != 0;
+                                            const int g = r3 ? lq / 10 : lq / 9, pos = lq - g * (r3 ? 10 : 9), NC = r3 ? 6 : 7;
+                                            const int idx = q * NC + g, ic = min(idx, npat - 1);
+                                            // the pattern offset of point ic is byte ic / 4 of the block-form table of the lanes whose candidate group is ic % 4
+                                            const int pl = ((ic & 3) * LPC) << 2;
+                                            const unsigned b0 = (unsigned)__builtin_amdgcn_ds_bpermute(pl, (int)bPat0), b1 = (unsigned)__builtin_amdgcn_ds_bpermute(pl, (int)bPat1);
+                                            const int dd = (int)(((ic & 16) ? b1 : b0) >> (8 * ((ic >> 2) & 3))), dx = (dd << 28) >> 28, dy = (dd << 24) >> 28;
+                                            const int r = (pos > c1 ? 1 : 0) + ((r3 & (pos > c2 + 1)) ? 1 : 0);
+                                            const int col = pos - r, colc = min(col, L);                 // (positions beyond the last run re-read its last column)
+                                            const int eB = r == 0 ? c1 : (r == 1 && r3) ? c2 : L;       // the run's end: its last column, the first block of the next run
+                                            const int s0 = __builtin_amdgcn_readlane(pkW, f), s1 = __builtin_amdgcn_readlane(pkW, f + c1), s2 = __builtin_amdgcn_readlane(pkW, f + c2);
+                                            const int sW = r == 0 ? s0 : r == 1 ? s1 : s2;
+                                            const int vx = upx(sW) + dx, vy = upy(sW) + dy;
+                                            slot = ((g < NC) & (idx < npat) & (col < eB)) ? idx : -1; // (block m is written by the lane of its first column)
+                                            colW = f + colc; stripLane = true; srcOff = bufW + colc * COLB;
+                                            oA = luma_off_at(bxf, vx, vy) + (unsigned)(colc * COLB);
+                                            oB = 2 * chroma_off_at(bxf, vx, vy) + (unsigned)(colc * COLB);
+                                            return;
                                         } else if (!stripWin) bW = __builtin_amdgcn_ds_bpermute(colB << 2, pkW);
                                         if (stripWin || (st == 1 && tail)) { // strip lanes: one vector for the whole window
                                             const int p = st == 1 ? pS : pS, g = gS;
@@ -784,7 +826,10 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                     // On a clip whose vectors are whole pels stage 1 reads the integer-pel plane and stage 2 mostly the three others: little to share)
                                     // (a leading-edge prefetch -- one dword of every line a window two ahead will need, four scattered loads per window --
                                     // was measured and removed: 493 -> 544 ms per 2046-chain launch, profiles/r4_spec_prefetch.txt)
-                                    auto npass = [&](int st, int w) { return st == 1 ? 1 : ((stripW >> w) & 1) ? (npat + 7) / 8 : (npat + 3) / 4; };
+                                    auto npass = [&](int st, int w) {
+                                        if (RUN && st == 2 && ((runW >> (8 * w)) & 63)) return (hexLevel && ((runW >> (8 * w)) & 56)) ? 3 : hexLevel ? 2 : 4; // 14 (24) points, 7 or 6 to a pass
+                                        return st == 1 ? 1 : ((stripW >> w) & 1) ? (npat + 7) / 8 : (npat + 3) / 4;
+                                    };
                                     // one stage: a stream of passes whose loads stay in flight across passes and windows
                                     auto run_stage = [&](int st, int wFrom, int wTo) { // the windows wFrom .. wTo - 1 in walk order
                                         // PACK, four strip-form windows in a row (ci = the window's position among them, -1 elsewhere): F0 R0 F1 R1 F2 R2 F3 -- F = a window's full
@@ -826,7 +871,10 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                             if (more) strip_run<true>(T, 0, nA, nB, srcOff); else strip_run<false>(T, 0, 0, 0, srcOff);
                                             SPROF(13);
                                             // strip lanes: block m = columns m and m + 1; block lanes: the two halves of a block sit in neighbouring lanes
-                                            unsigned sL = T.aL + (unsigned)__builtin_amdgcn_update_dpp(0, (int)T.aL, 0x101, 0xf, 0xf, true), sC = T.aC + (unsigned)__builtin_amdgcn_update_dpp(0, (int)T.aC, 0x101, 0xf, 0xf, true);
+                                            // (RUN: a candidate's 9 or 10 lanes cross the rows of 16 lanes: the next lane of the WAVE, wave_shl:1, not of the row, row_shl:1 -- the same
+                                            // lane for every strip lane that writes, whose column is never the last of eight)
+                                            constexpr int NEXT = RUN ? 0x130 : 0x101;
+                                            unsigned sL = T.aL + (unsigned)__builtin_amdgcn_update_dpp(0, (int)T.aL, NEXT, 0xf, 0xf, true), sC = T.aC + (unsigned)__builtin_amdgcn_update_dpp(0, (int)T.aC, NEXT, 0xf, 0xf, true);
                                             unsigned hL = T.aL + (unsigned)__builtin_amdgcn_update_dpp(0, (int)T.aL, 0xB1, 0xf, 0xf, true), hC = T.aC + (unsigned)__builtin_amdgcn_update_dpp(0, (int)T.aC, 0xB1, 0xf, 0xf, true);
                                             if (HC == 2) { // a 32x32 block: four columns / four lanes
                                                 sL += (unsigned)__builtin_amdgcn_update_dpp(0, (int)sL, 0x102, 0xf, 0xf, true); sC += (unsigned)__builtin_amdgcn_update_dpp(0, (int)sC, 0x102, 0xf, 0xf, true);
@@ -839,6 +887,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
 #endif
 #ifdef MVX_SPEC_STATS
                                             if (st == 2) st8 += 1;
+                                            if (RUN && st == 2 && ((runW >> (8 * w)) & 63)) stR[5] += 1;
 #endif
                                             if (!more) break;
                                             w = wn; wi = win; q = qn; rj = rjn; ci = cin; slot = slotN; colW = colN; stripLane = stripN; srcOff = srcN;
@@ -850,11 +899,27 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
                                     pkW = pk(pX_, pY_);
                                     { // windows whose blocks share the centre and keep the whole pattern inside their limits
                                         const bool ok2 = (pX_ - 2 >= dxMin) & (pX_ + 2 <= dxMax1) & (pY_ - 2 >= nDyMin) & (pY_ + 2 < nDyMax);
+                                        const int pkWl = __builtin_amdgcn_ds_bpermute((l - 1) << 2, pkW); // (RUN) the centre of the block to the left
                                         for (int w = 0; w < nw; w++) {
                                             const int f = lo + SWB * w, e = min(f + SWB, hiE);
                                             const bool inw = (l >= f) & (l < e);
                                             const int w0 = __builtin_amdgcn_readlane(pkW, f);
                                             if (e - f >= 2 && __ballot(inw & ((pkW != w0) | !ok2)) == 0) stripW |= 1u << w;
+                                            if constexpr (RUN) { // run form: two or three maximal runs of equal centres, every block with the whole pattern inside its limits
+                                                const unsigned cuts = (unsigned)(__ballot(inw & (l > f) & (pkW != pkWl)) >> f); // bit m: a run starts at block m of the window
+                                                const int R = 1 + __builtin_popcount(cuts);
+                                                const bool lim = __ballot(inw & !ok2) != 0;
+                                                if (!lim && R >= 2 && R <= MVX_SPEC_RUNMAX) {
+                                                    const unsigned rest = cuts & (cuts - 1);
+                                                    runW |= (unsigned)(__builtin_ctz(cuts) | (rest ? __builtin_ctz(rest) << 3 : 0)) << (8 * w);
+                                                }
+#ifdef MVX_SPEC_STATS
+                                                if (!((stripW >> w) & 1)) {
+                                                    stR[lim ? 4 : min(R, 4) - 1] += 1;
+                                                    if ((runW >> (8 * w)) & 63) stR[6] += (npat + 3) / 4 - (hexLevel ? R : 4);
+                                                }
+#endif
+                                            }
 #ifdef MVX_SPEC_STATS
                                             if ((stripW >> w) & 1) st4 += 1;
                                             else { st5 += 1; st6 += __builtin_popcountll(__ballot(inw & (pkW != w0))); if (__ballot(inw & (pkW != w0)) == 0) st7 += 1; }
@@ -1401,7 +1466,7 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
             }
         }
 #ifdef MVX_SPEC_STATS
-        if (l == 0) { atomicAdd(&g_specstat[lvl][0], st0); atomicAdd(&g_specstat[lvl][1], st1); atomicAdd(&g_specstat[lvl][2], st2); atomicAdd(&g_specstat[lvl][3], st3); atomicAdd(&g_specstat[lvl][4], st4); atomicAdd(&g_specstat[lvl][5], st5); atomicAdd(&g_specstat[lvl][6], st6); atomicAdd(&g_specstat[lvl][7], st7); atomicAdd(&g_specstat[lvl][8], st8); atomicAdd(&g_specstat[lvl][9], st9); }
+        if (l == 0) { atomicAdd(&g_specstat[lvl][0], st0); atomicAdd(&g_specstat[lvl][1], st1); atomicAdd(&g_specstat[lvl][2], st2); atomicAdd(&g_specstat[lvl][3], st3); atomicAdd(&g_specstat[lvl][4], st4); atomicAdd(&g_specstat[lvl][5], st5); atomicAdd(&g_specstat[lvl][6], st6); atomicAdd(&g_specstat[lvl][7], st7); atomicAdd(&g_specstat[lvl][8], st8); atomicAdd(&g_specstat[lvl][9], st9); for (int i = 0; i < 7; i++) atomicAdd(&g_specstat[lvl][10 + i], stR[i]); }
 #endif
         SPROF(7);
         // vectors[] of this level feed the next level's interpolation / global-MV estimate (other lanes read them)
@@ -1475,8 +1540,8 @@ extern "C" __attribute__((visibility("default"))) int mvx_debug_specprof(unsigne
 #endif
 #if defined(MVX_SPEC_STATS) && defined(MVX_PROF_EXPORT)
 extern "C" __attribute__((visibility("default"))) int mvx_debug_specstats(unsigned long long *out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_specstat), sizeof(unsigned long long) * MVX_MAX_LEVELS * 10) != hipSuccess) return -1;
-    if (reset) { static unsigned long long z[MVX_MAX_LEVELS * 10]; if (hipMemcpyToSymbol(HIP_SYMBOL(g_specstat), z, sizeof(z)) != hipSuccess) return -1; }
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_specstat), sizeof(unsigned long long) * MVX_MAX_LEVELS * SPEC_NSTAT) != hipSuccess) return -1;
+    if (reset) { static unsigned long long z[MVX_MAX_LEVELS * SPEC_NSTAT]; if (hipMemcpyToSymbol(HIP_SYMBOL(g_specstat), z, sizeof(z)) != hipSuccess) return -1; }
     return 0;
 }
 #endif
