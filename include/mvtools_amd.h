@@ -14,6 +14,22 @@
  *   - functions return 0 on success, a negative code on failure; mvx_*_create additionally write the
  *     reference's user-visible error string (e.g. "Super: pel must be 1, 2, or 4.") into `err`.
  *   - there is NO CPU fallback: if no gfx950 device / kernel image is available the call fails.
+ *
+ * Plane layouts (checked: *_create refuses a pitch, *_frames an address, with MVX_E_ARG and before anything is uploaded or launched)
+ *   - Clip-side planes -- src / clip / dst of mvx_degrain, mvx_degrain_n in all its three entries, mvx_compensate, mvx_compensate_n,
+ *     mvx_blockfps, mvx_flowinter / mvx_flowfps, mvx_flowcomp and mvx_flowblur: any pitch that holds a row of its plane and is a multiple of
+ *     the sample size (1, 2, or 4 bytes for a float clip; out16 writes 2-byte samples), and any plane address that is a multiple of the
+ *     sample size.  A tight pitch, an odd pitch for 8-bit samples, a plane inside a wider frame, U and V of different pitch, src and dst of
+ *     different pitch are all legal.  A shorter pitch, a pitch or address that is no multiple of the sample size, and a missing plane where
+ *     the filter needs one are refused: "<src|clip|dst> pitch of plane P must hold a row of N bytes and be a multiple of the sample size."
+ *     (the flow filters put their name in front), "<entry>: <what> plane P must be aligned to N bytes" / "... is required".
+ *   - Super planes, for every consumer and for mvx_analyse / mvx_recalculate: what mvx_super_frames writes -- pitches that hold a row of the
+ *     super plane and are multiples of 16 bytes, U and V alike, plane addresses that are multiples of 16 bytes ("super pitch of plane P must
+ *     hold a row of N bytes and be a multiple of 16 bytes.", with "Analyse: " / "Recalculate: " in front there).
+ *   - Only samples are written: the bytes between a plane's width and its pitch, and every byte of a super frame outside the defined
+ *     rectangles, are neither written nor read (tests/test_gpu_layouts.py: planes carved out of arenas of two fills).
+ *   mvx_super_frames (src: as clip-side planes; dst: super planes) and mvx_finest_frames (both sides as clip-side planes) check the same at their
+ *   entries; mv.Mask and the Depan filters state their own rules at theirs.
  */
 #ifndef MVTOOLS_AMD_H
 #define MVTOOLS_AMD_H
@@ -93,10 +109,18 @@ int mvx_super_create_float(const mvx_super_args *args, mvx_super **out, char *er
 int mvx_super_is_float(const mvx_super *s);
 
 /* Builds `nframes` super frames.  src[f*3+p] / dst[f*3+p] are device pointers to plane p of frame f
- * (p >= num_planes ignored); pitches in bytes, shared by all frames.  dst planes must have been
- * zero-filled once by the caller when allocated: only the defined rectangles (every level's padded
- * plane, every sub-pel plane) are written, bytes outside them are never touched.
- * dst pitch must be a multiple of 16 bytes. */
+ * (p >= num_planes ignored); pitches in bytes, shared by all frames.  Only the defined rectangles (every
+ * level's padded plane, every sub-pel plane) are written; bytes outside them are never touched, and no
+ * entry of this library reads them, so dst planes need no initialisation (a caller that compares or
+ * stores whole super frames zero-fills them once when it allocates them).
+ * Layouts: dst pitch a multiple of 16 bytes that holds a row of the super plane ("mvx_super_frames: dst
+ * pitch must be a multiple of 16 bytes"); src any pitch that holds a row, src and dst planes at any
+ * address, all multiples of the sample size ("... src pitch must hold a row and be a multiple of the
+ * sample size", "... planes must be aligned to the sample size"; a float clip: src 4, dst 16).  The
+ * consumers and the search want dst planes on 16-byte boundaries (head of this file).  Results never
+ * depend on the layout, speed does: at pel 2 the rows-in-registers kernels serve a call whose src pitches
+ * are multiples of 4 with src planes on 4-byte and dst planes on 16-byte boundaries, the slower tile
+ * kernels any other call. */
 int mvx_super_frames(mvx_super *s, int nframes, const void *const *src, const ptrdiff_t src_pitch[3],
                      void *const *dst, const ptrdiff_t dst_pitch[3], void *stream);
 
@@ -133,7 +157,10 @@ int mvx_super_frames_pelclip(mvx_super *s, int nframes, const void *const *src, 
 /* ---- mv.Finest -----------------------------------------------------------------------------------
  * replaces mvfinestGetFrame, MVFinest.c:48-140 (arg string :213-218): the pel^2 sub-pel planes of level 0 of a super frame
  * interleaved into one plane of (width + 2 hpad) * pel x (height + 2 vpad) * pel samples (chroma planes subsampled like
- * the clip).  Planes the super clip does not carry (chroma=0) are not written. */
+ * the clip).  Planes the super clip does not carry (chroma=0) are not written.  Layouts: super and dst pitches that hold a row of
+ * their plane, super and dst planes at any address, all multiples of the sample size; U and V may differ ("mvx_finest_frames: pitches
+ * must hold a row of their plane and be multiples of the sample size", "... planes are required and must be aligned to the sample
+ * size", MVX_E_ARG before anything is launched).  Only the samples of dst are written. */
 void mvx_finest_size(const mvx_super *s, int32_t *width, int32_t *height);
 int mvx_finest_frames(const mvx_super *s, int nframes, const void *const *super_frames /* [f*3+p] */, const ptrdiff_t super_pitch[3],
                       void *const *dst /* [f*3+p] */, const ptrdiff_t dst_pitch[3], void *stream);

@@ -213,3 +213,155 @@ def test_scdetect_argument_check(mv):
     assert L.mvx_last_error().decode() == "SCDetection: thscd1 can be at most 16320."
     assert L.mvx_scdetect(C.byref(ad), 16321, mv.UNSET, 0, blobs, out, None, err) == 0
     assert err.value == b""
+
+
+# ------------------------------------------------------------------------------------------------ plane layouts (include/mvtools_amd.h, "Plane layouts")
+
+def _pitch_msg(what, plane, row):
+    return "%s pitch of plane %d must hold a row of %d bytes and be a multiple of the sample size." % (what, plane, row)
+
+
+def _super_msg(plane, row, name=""):
+    return "%ssuper pitch of plane %d must hold a row of %d bytes and be a multiple of 16 bytes." % (name, plane, row)
+
+
+def _with_pitch(sup, pitch):
+    sup.pitch = list(pitch)
+    return sup
+
+
+def test_clip_side_pitches_the_legal_edges_and_the_refusals(mv):
+    """320 x 192, 4:2:0: rows of 320 / 160 / 160 samples.  Legal: a tight pitch, one sample more than a row (odd at 8 bits, 2 mod 4 at 16), U
+    and V of different pitch, src and dst of different pitch.  Refused: a pitch shorter than a row, a pitch that is no multiple of the sample."""
+    sup, bw, fw = _clips(mv)
+    sup16, bw16, fw16 = _clips(mv, bits=16)
+    for src, dst in (([320, 160, 160], None), ([321, 161, 161], [320, 160, 160]), ([512, 256, 512], [320, 160, 416]), ([320, 160, 160], [1024, 161, 160])):
+        mv.Degrain(1, sup, bw, src, dst)
+        mv.DegrainN(7, sup, bw, src, dst)
+        mv.BlockFPS(sup, bw, fw, 10, src, dst_pitch=dst)
+        mv.Compensate(sup, bw, dst or src)
+        mv.CompensateN(2, sup, bw, dst or src)
+    mv.Degrain(1, sup16, bw16, [642, 322, 322], [640, 320, 324])           # 16 bit: 2 mod 4
+    mv.DegrainN(2, sup, bw, [320, 160, 160], [640, 322, 320], out16=True)  # out16: the dst rows are 16-bit samples
+    for make in (lambda s, d: mv.Degrain(1, sup, bw, s, d), lambda s, d: mv.DegrainN(3, sup, bw, s, d)):
+        assert _err(lambda: make([319, 160, 160], [320, 160, 160])) == _pitch_msg("src", 0, 320)
+        assert _err(lambda: make([320, 160, 159], [320, 160, 160])) == _pitch_msg("src", 2, 160)
+        assert _err(lambda: make([320, 160, 160], [320, 100, 160])) == _pitch_msg("dst", 1, 160)
+        assert _err(lambda: make([0, 160, 160], [320, 160, 160])) == _pitch_msg("src", 0, 320)
+        assert _err(lambda: make([-320, 160, 160], [320, 160, 160])) == _pitch_msg("src", 0, 320)
+    assert _err(lambda: mv.Degrain(1, sup16, bw16, [641, 320, 320])) == _pitch_msg("src", 0, 640)      # odd for 16-bit samples
+    assert _err(lambda: mv.Degrain(1, sup16, bw16, [640, 320, 320], [640, 321, 320])) == _pitch_msg("dst", 1, 320)
+    assert _err(lambda: mv.Degrain(1, sup16, bw16, [320, 320, 320])) == _pitch_msg("src", 0, 640)      # an 8-bit row's pitch
+    assert _err(lambda: mv.DegrainN(2, sup, bw, [320, 160, 160], [320, 160, 160], out16=True)) == _pitch_msg("dst", 0, 640)
+    assert _err(lambda: mv.DegrainN(2, sup, bw, [320, 160, 160], [640, 321, 320], out16=True)) == _pitch_msg("dst", 1, 320)
+    assert _err(lambda: mv.Compensate(sup, bw, [320, 159, 160])) == _pitch_msg("dst", 1, 160)
+    assert _err(lambda: mv.CompensateN(1, sup16, bw16, [640, 320, 323])) == _pitch_msg("dst", 2, 320)
+    assert _err(lambda: mv.BlockFPS(sup, bw, fw, 10, [320, 160, 100])) == _pitch_msg("clip", 2, 160)
+    assert _err(lambda: mv.BlockFPS(sup, bw, fw, 10, [320, 160, 160], dst_pitch=[300, 160, 160])) == _pitch_msg("dst", 0, 320)
+    # after the filter's own checks and the two older checks of the library
+    assert _err(lambda: mv.Degrain(1, sup, bw, [1, 1, 1], limit=999)) == "Degrain1: limit must be between 0 and 255 (inclusive)."
+    assert _err(lambda: mv.Degrain(1, _split_uv_pitch(mv.Super(320, 192, 8)), bw, [1, 1, 1])) == "U and V super planes must share one pitch."
+
+
+def test_super_pitches_what_mvx_super_frames_writes(mv):
+    """the consumers and the search take super planes as mvx_super_frames writes them: a pitch that holds a row and is a multiple of 16"""
+    sup, bw, fw = _clips(mv)
+    row = [sup.info.plane_width[p] for p in range(3)]
+    ok = [(r + 15) // 16 * 16 + 16 for r in row]
+    for pitch in (ok, [(r + 15) // 16 * 16 for r in row]):
+        s = _with_pitch(mv.Super(320, 192, 8), pitch)
+        mv.Analyse(s, isb=1)
+        mv.Recalculate(s, bw, blksize=8)
+        mv.Degrain(1, s, bw, PITCH)
+        mv.Compensate(s, bw, PITCH)
+        mv.BlockFPS(s, bw, fw, 10, PITCH)
+    bad8, short = [ok[0] + 8, ok[1], ok[2]], [ok[0], row[1] // 16 * 16 - 16, row[1] // 16 * 16 - 16]
+    assert _err(lambda: mv.Analyse(_with_pitch(mv.Super(320, 192, 8), bad8))) == _super_msg(0, row[0], "Analyse: ")
+    assert _err(lambda: mv.Analyse(_with_pitch(mv.Super(320, 192, 8), short))) == _super_msg(1, row[1], "Analyse: ")
+    assert _err(lambda: mv.Recalculate(_with_pitch(mv.Super(320, 192, 8), bad8), bw, blksize=8)) == _super_msg(0, row[0], "Recalculate: ")
+    assert _err(lambda: mv.Degrain(1, _with_pitch(mv.Super(320, 192, 8), bad8), bw, PITCH)) == _super_msg(0, row[0])
+    assert _err(lambda: mv.DegrainN(9, _with_pitch(mv.Super(320, 192, 8), short), bw, PITCH)) == _super_msg(1, row[1])
+    assert _err(lambda: mv.Compensate(_with_pitch(mv.Super(320, 192, 8), bad8), bw, PITCH)) == _super_msg(0, row[0])
+    assert _err(lambda: mv.BlockFPS(_with_pitch(mv.Super(320, 192, 8), short), bw, fw, 10, PITCH)) == _super_msg(1, row[1])
+    with pytest.raises(ValueError):
+        mv.Super(320, 192, 8, pitch=bad8)
+    assert mv.Super(320, 192, 8, pitch=ok).pitch == ok and mv.Super(320, 192, 8).pitch == [(r + 255) // 256 * 256 for r in row]
+
+
+def test_plane_addresses_are_checked_before_anything_is_launched(mv):
+    """*_frames refuses a missing plane and an address that is no multiple of the sample size (clip side) or of 16 (super side) with
+    MVX_E_ARG before it touches a device: this runs without one"""
+    L = mv.lib()
+    sup16, bw16, fw16 = _clips(mv, bits=16)
+    A = 0x10000  # never dereferenced
+
+    def refused(call, msg):
+        assert call() == -1 and L.mvx_last_error().decode() == msg
+
+    dg = mv.Degrain(1, sup16, bw16, [640, 320, 320])
+    job = (mv.DegrainJob * 1)()
+
+    def fill(src=(A, A, A), dst=(A, A, A), ref=(A, A, A)):
+        for p in range(3):
+            job[0].src[p], job[0].dst[p], job[0].refs[0][p], job[0].refs[1][p] = src[p], dst[p], ref[p], None
+        return lambda: L.mvx_degrain_frames(dg.h, 1, job, None)
+    refused(fill(src=(A + 1, A, A)), "mvx_degrain_frames: src plane 0 must be aligned to 2 bytes")
+    refused(fill(src=(A, A, None)), "mvx_degrain_frames: src plane 2 is required")
+    refused(fill(dst=(A, A + 3, A)), "mvx_degrain_frames: dst plane 1 must be aligned to 2 bytes")
+    refused(fill(dst=(None, A, A)), "mvx_degrain_frames: dst plane 0 is required")
+    refused(fill(ref=(A + 8, A, A)), "mvx_degrain_frames: reference super plane 0 must be aligned to 16 bytes")
+
+    comp = mv.Compensate(sup16, bw16, [640, 320, 320])
+    cj = (mv.CompensateJob * 1)()
+
+    def cfill(src=(A, A, A), dst=(A, A, A)):
+        for p in range(3):
+            cj[0].src_super[p], cj[0].dst[p], cj[0].ref_super[p] = src[p], dst[p], None
+        return lambda: L.mvx_compensate_frames(comp.h, 1, cj, None)
+    refused(cfill(src=(A, A + 4, A)), "mvx_compensate_frames: source super plane 1 must be aligned to 16 bytes")
+    refused(cfill(src=(None, A, A)), "mvx_compensate_frames: source super plane 0 is required")
+    refused(cfill(dst=(A, A, A + 1)), "mvx_compensate_frames: dst plane 2 must be aligned to 2 bytes")
+
+    bf = mv.BlockFPS(sup16, bw16, fw16, 10, [640, 320, 320])
+    bj = (mv.BlockFPSJob * 1)()
+
+    def bfill(left=(A, A, A), dst=(A, A, A)):
+        bj[0].time256 = 0
+        for p in range(3):
+            bj[0].clip_left[p], bj[0].dst[p] = left[p], dst[p]
+        return lambda: L.mvx_blockfps_frames(bf.h, 1, bj, None)
+    refused(bfill(left=(None, A, A)), "mvx_blockfps_frames: clip_left / clip_right are required")
+    refused(bfill(left=(A, A + 1, A)), "mvx_blockfps_frames: clip_left plane 1 must be aligned to 2 bytes")
+    refused(bfill(dst=(A, A, None)), "mvx_blockfps_frames: dst plane 2 is required")
+    # an 8-bit clip has no alignment to miss: the same odd addresses pass these checks (and then need a device)
+    sup, bw, _ = _clips(mv)
+    c8 = mv.Compensate(sup, bw, PITCH)
+    for p in range(3):
+        cj[0].src_super[p], cj[0].dst[p] = A, None
+    refused(lambda: L.mvx_compensate_frames(c8.h, 1, cj, None), "mvx_compensate_frames: dst plane 0 is required")
+
+
+def test_finest_layouts_are_checked_before_anything_is_launched(mv):
+    """mvx_finest_frames: pitches that hold a row, planes that are there, all multiples of the sample size; U and V may differ"""
+    L = mv.lib()
+    sup = mv.Super(320, 192, 16)
+    w, h = C.c_int32(), C.c_int32()
+    L.mvx_finest_size(sup.h, C.byref(w), C.byref(h))
+    rows = [w.value * 2, w.value, w.value]
+    A = 0x10000  # never dereferenced
+    three = lambda l: (C.c_ssize_t * 3)(*l)
+    ptrs = lambda l: (C.c_void_p * 3)(*l)
+
+    def call(src=(A, A, A), dst=(A, A, A), spitch=None, dpitch=None):
+        rc = L.mvx_finest_frames(sup.h, 1, ptrs(src), three(spitch or sup.pitch), ptrs(dst), three(dpitch or rows), None)
+        return rc, L.mvx_last_error().decode()
+    pitches = "mvx_finest_frames: pitches must hold a row of their plane and be multiples of the sample size"
+    planes = "mvx_finest_frames: planes are required and must be aligned to the sample size"
+    assert call(dpitch=[rows[0] - 2, rows[1], rows[2]]) == (-1, pitches)
+    assert call(dpitch=[rows[0], rows[1] + 1, rows[2]]) == (-1, pitches)
+    assert call(spitch=[sup.pitch[0], sup.pitch[1], 64]) == (-1, pitches)
+    assert call(dst=(A, A + 1, A)) == (-1, planes)
+    assert call(src=(A + 1, A, A)) == (-1, planes)
+    assert call(dst=(A, A, None)) == (-1, planes)
+    # legal: a tight pitch (rows), one sample more, U != V -- these pass the checks; a tight 16-bit row of 2 mod 4 bytes needs no more
+    assert call(dst=(A, A, None), dpitch=[rows[0] + 2, rows[1], rows[2] + 256])[1] == planes

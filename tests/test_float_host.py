@@ -209,3 +209,34 @@ def test_rule_header_on_the_host_is_the_restatement(rule_exe, sharp, n):
     assert np.array_equal(out[0], sf.half_rows(a, sharp))
     assert np.array_equal(out[1], sf.diagonal(a))
     assert np.array_equal(out[2], (np.roll(a, -1, axis=0) + a) * np.float32(0.5))
+
+
+# ------------------------------------------------------------------------------------------------ plane layouts of the float entries
+
+def test_float_degrain_n_planes_and_pitches_are_multiples_of_4(mv):
+    """include/mvtools_amd.h, mvx_degrain_n_create_float: "Planes and pitches must be multiples of 4 bytes" -- the clip-side contract of the block
+    filters at a sample size of 4; refused with MVX_E_ARG at creation (pitches) and at the head of mvx_degrain_n_frames (addresses)"""
+    _, bw, _ = _clips(mv)
+    fsup = _fsup(mv)
+    w = fsup.info.width
+    rows = [w * 4, w * 2, w * 2]
+    msg = lambda what, p: "%s pitch of plane %d must hold a row of %d bytes and be a multiple of the sample size." % (what, p, rows[p])
+    mv.DegrainN(1, fsup, bw, rows)                                    # tight
+    mv.DegrainN(1, fsup, bw, [r + 4 for r in rows], rows)             # one sample more
+    mv.DegrainN(1, fsup, bw, [rows[0], rows[1], rows[2] + 256], rows)  # U != V
+    assert _err(lambda: mv.DegrainN(1, fsup, bw, [rows[0] + 2, rows[1], rows[2]])) == msg("src", 0)
+    assert _err(lambda: mv.DegrainN(1, fsup, bw, rows, [rows[0], rows[1] + 2, rows[2]])) == msg("dst", 1)
+    assert _err(lambda: mv.DegrainN(1, fsup, bw, [rows[0] - 4, rows[1], rows[2]])) == msg("src", 0)
+    dn = mv.DegrainN(1, fsup, bw, rows)
+    L, A = mv.lib(), 0x10000  # never dereferenced
+    job = (mv.DegrainNJob * 1)()
+    refs, blobs = ((C.c_void_p * 3) * 2)(), (C.c_void_p * 2)()
+    job[0].refs = C.cast(refs, C.POINTER(C.c_void_p * 3))
+    job[0].blobs = C.cast(blobs, C.POINTER(C.c_void_p))
+    for src, dst, ref, want in (((A + 2, A, A), (A, A, A), A, "mvx_degrain_n_frames: src plane 0 must be aligned to 4 bytes"),
+                                ((A, A, A), (A, A + 2, A), A, "mvx_degrain_n_frames: dst plane 1 must be aligned to 4 bytes"),
+                                ((A, A, A), (A, A, None), A, "mvx_degrain_n_frames: dst plane 2 is required"),
+                                ((A, A, A), (A, A, A), A + 4, "mvx_degrain_n_frames: reference super plane 0 must be aligned to 16 bytes")):
+        for p in range(3):
+            job[0].src[p], job[0].dst[p], refs[0][p] = src[p], dst[p], ref
+        assert L.mvx_degrain_n_frames(dn.h, 1, job, None) == -1 and L.mvx_last_error().decode() == want

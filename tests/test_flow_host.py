@@ -99,3 +99,64 @@ def test_flowinter_time256_is_formed_in_float(mv):
         assert flow_ref.Flow(bw, fw, 10, 3, 16, 16, time=time).map(5) == (5, 7, want)
         assert g.num_frames == 10
     assert int(0.39062499 * 256.0 / 100.0) == 0  # the same argument in double would give time256 0
+
+
+# ------------------------------------------------------------------------------------------------ plane layouts (include/mvtools_amd.h, "Plane layouts")
+
+def _makers(mv, sup, bw, fw):
+    return {"FlowInter": lambda c, d=None: mv.FlowInter(sup, bw, fw, 10, c, dst_pitch=d), "FlowFPS": lambda c, d=None: mv.FlowFPS(sup, bw, fw, 10, c, 24, 1, dst_pitch=d),
+            "Flow": lambda c, d=None: mv.Flow(sup, bw, 10, c, dst_pitch=d), "FlowBlur": lambda c, d=None: mv.FlowBlur(sup, bw, fw, 10, c, dst_pitch=d)}
+
+
+@pytest.mark.parametrize("name", ["FlowInter", "FlowFPS", "Flow", "FlowBlur"])
+def test_flow_filters_plane_layouts_at_creation(mv, name):
+    """the contract of the block filters (tests/test_block_host.py), with the filter's name in front as in every message of the flow filters"""
+    sup, bw, fw = _pair(mv)
+    make = _makers(mv, sup, bw, fw)[name]
+    msg = lambda what, p, row: "%s: %s pitch of plane %d must hold a row of %d bytes and be a multiple of the sample size." % (name, what, p, row)
+    make([320, 160, 160])                           # tight
+    make([321, 161, 161], [320, 160, 160])          # one sample more than a row; clip and dst differ
+    make([512, 256, 512], [320, 160, 416])          # U != V
+    assert _err(lambda: make([319, 160, 160])) == msg("clip", 0, 320)
+    assert _err(lambda: make([320, 160, 100])) == msg("clip", 2, 160)
+    assert _err(lambda: make([320, 160, 160], [320, 159, 160])) == msg("dst", 1, 160)
+    sup16, bw16, fw16 = _pair(mv, bits=16)
+    make16 = _makers(mv, sup16, bw16, fw16)[name]
+    make16([642, 322, 322], [640, 320, 324])        # 2 mod 4
+    assert _err(lambda: make16([641, 320, 320])) == msg("clip", 0, 640)
+    assert _err(lambda: make16([640, 320, 320], [640, 320, 321])) == msg("dst", 2, 320)
+    row = sup.info.plane_width[0]
+    s = mv.Super(320, 192, 8)
+    s.pitch = [s.pitch[0] + 8, s.pitch[1], s.pitch[2]]
+    assert _err(lambda: _makers(mv, s, bw, fw)[name]([320, 160, 160])) == \
+        "%s: super pitch of plane 0 must hold a row of %d bytes and be a multiple of 16 bytes." % (name, row)
+
+
+def test_flow_plane_addresses_are_checked_before_anything_is_launched(mv):
+    L = mv.lib()
+    sup16, bw16, fw16 = _pair(mv, bits=16)
+    A = 0x10000  # never dereferenced
+    g = mv.FlowInter(sup16, bw16, fw16, 10, [640, 320, 320])
+    job = (mv.FlowJob * 1)()
+
+    def fill(left=(A, A, A), right=(A, A, A), dst=(A, A, A), sup=(None, None, None)):
+        job[0].time256 = 128
+        for p in range(3):
+            job[0].clip_left[p], job[0].clip_right[p], job[0].dst[p], job[0].super_left[p] = left[p], right[p], dst[p], sup[p]
+        return L.mvx_flow_frames(g.h, 1, job, None), L.mvx_last_error().decode()
+    assert fill(left=(None, A, A)) == (-1, "mvx_flow_frames: dst / clip_left / clip_right are required")
+    assert fill(left=(A, None, A)) == (-1, "mvx_flow_frames: clip_left plane 1 is required")
+    assert fill(left=(A + 1, A, A)) == (-1, "mvx_flow_frames: clip_left plane 0 must be aligned to 2 bytes")
+    assert fill(right=(A, A, A + 1)) == (-1, "mvx_flow_frames: clip_right plane 2 must be aligned to 2 bytes")
+    assert fill(dst=(A, A + 1, A)) == (-1, "mvx_flow_frames: dst plane 1 must be aligned to 2 bytes")
+    assert fill(sup=(A + 2, A, A)) == (-1, "mvx_flow_frames: super_left plane 0 must be aligned to 16 bytes")
+    fc = mv.Flow(sup16, bw16, 10, [640, 320, 320])
+    cj = (mv.FlowCompJob * 1)()
+    for p in range(3):
+        cj[0].clip[p], cj[0].dst[p] = A, A + (1 if p == 2 else 0)
+    assert L.mvx_flowcomp_frames(fc.h, 1, cj, None) == -1 and L.mvx_last_error().decode() == "mvx_flowcomp_frames: dst plane 2 must be aligned to 2 bytes"
+    fb = mv.FlowBlur(sup16, bw16, fw16, 10, [640, 320, 320])
+    bj = (mv.FlowBlurJob * 1)()
+    for p in range(3):
+        bj[0].clip[p], bj[0].dst[p] = A + (1 if p == 0 else 0), A
+    assert L.mvx_flowblur_frames(fb.h, 1, bj, None) == -1 and L.mvx_last_error().decode() == "mvx_flowblur_frames: clip plane 0 must be aligned to 2 bytes"

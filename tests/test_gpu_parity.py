@@ -322,7 +322,7 @@ DEGRAIN_CASES = [
     (256, 160, 16, 6, {}, dict(blksize=32, overlap=16), {}),          # cfg5 shape (tr=6)
     (196, 116, 16, 1, {}, dict(blksize=16, overlap=8), {}),           # width not a multiple of the cell: partial cell rows
     (196, 116, 8, 2, {}, dict(blksize=8, overlap=4), {}),
-    (200, 120, 8, 1, {}, dict(blksize=8, overlap=0), {}),             # no overlap + uncovered strips
+    (200, 120, 8, 1, {}, dict(blksize=8, overlap=0), {}),             # no overlap; 25 x 15 blocks cover the frame exactly
     (200, 120, 8, 1, dict(pel=1), dict(blksize=8, overlap=2), {}),
     (200, 120, 8, 1, dict(pel=4), dict(blksize=8, overlap=4), {}),
     (128, 96, 8, 1, {}, dict(blksize=8, overlap=4), dict(limit=3, limitc=5)),
@@ -351,6 +351,8 @@ DEGRAIN_CASES = [
     (400, 200, 16, 6, {}, dict(blksize=16, overlap=8), dict(thscd1=20, thscd2=10)),  # twelve references, all unusable: every load goes to the `safe` plane
     (400, 200, 8, 4, {}, dict(blksize=16, overlap=8), dict(plane=0)),
     (576, 160, 16, 3, {}, dict(blksize=32, blksizev=16, overlap=16, overlapv=8), {}),  # 16-sample cells, block rows of 8
+    # (new cases go at the end: the ids of the cases above carry their position in this list)
+    (206, 118, 8, 1, {}, dict(blksize=8, overlap=0), {}),             # no overlap + uncovered strips: 6 columns right, 6 rows below
 ]
 
 
@@ -400,6 +402,8 @@ COMP_CASES = [
     (128, 96, 8, {}, dict(blksize=8, overlap=4), dict(thsad=60)),
     (128, 96, 8, {}, dict(blksize=8, overlap=4), dict(time=40.0)),
     (128, 96, 8, {}, dict(blksize=8, overlap=4), dict(thscd1=20, thscd2=10)),
+    # (new cases go at the end: the ids of the cases above carry their position in this list)
+    (206, 118, 8, {}, dict(blksize=8, overlap=0), {}),                # side by side with uncovered strips on both edges
 ]
 
 
@@ -1009,7 +1013,7 @@ BLOCKFPS_CASES = [
     (128, 96, 8, dict(blksize=8, overlap=4), dict(num=60, den=1)),                       # BASELINE cfg4: 24 -> 60
     (128, 96, 8, dict(blksize=8, overlap=0), dict(num=60, den=1)),
     (192, 112, 16, dict(blksize=16, overlap=8), dict(num=48, den=1, mode=0)),
-    (200, 120, 8, dict(blksize=8, overlap=4), dict(num=60, den=1, mode=1)),              # uncovered strips
+    (200, 120, 8, dict(blksize=8, overlap=4), dict(num=60, den=1, mode=1)),              # 49 x 29 overlapped blocks cover the frame exactly
     (200, 120, 8, dict(blksize=8, overlap=0), dict(num=60, den=1, mode=2)),
     (128, 96, 16, dict(blksize=8, overlap=4), dict(num=60, den=1, mode=4, ml=40.0)),
     (128, 96, 8, dict(blksize=8, overlap=4), dict(num=60, den=1, mode=5, ml=20.0)),
@@ -1020,6 +1024,8 @@ BLOCKFPS_CASES = [
     (128, 96, 8, dict(blksize=8, overlap=4), dict(num=60, den=1, thscd1=20, thscd2=10)), # scene change -> blend fallback
     (128, 96, 8, dict(blksize=8, overlap=4), dict(num=60, den=1, thscd1=20, thscd2=10, blend=0)),
     (128, 96, 8, dict(blksize=8, overlap=4, delta=2), dict(num=36, den=1)),               # delta 2
+    # (new cases go at the end: the ids of the cases above carry their position in this list)
+    (206, 118, 8, dict(blksize=8, overlap=0), dict(num=60, den=1, mode=2)),              # side by side with uncovered strips on both edges
 ]
 
 

@@ -227,6 +227,8 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_create(const m
     P.superHPad = si.hpad; P.superVPad = si.vpad;
     for (int p = 0; p < 3; p++) P.pitch[p] = p < si.num_planes ? super_pitch[p] : 0;
     if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) MVX_FAIL("Analyse: the U and V planes of the super clip must share one pitch.");
+    for (int p = 0; p < si.num_planes; p++) // the search loads dwords and 16-byte vectors from rows of the super planes: what mvx_super_frames requires of its dst
+        if (super_pitch[p] < (ptrdiff_t)si.plane_width[p] * P.bps || super_pitch[p] % 16) MVX_FAIL("Analyse: super pitch of plane %d must hold a row of %d bytes and be a multiple of 16 bytes.", p, si.plane_width[p] * P.bps);
     int blobOff = 8;
     for (int i = ad.nLvCount - 1; i >= 0; i--) { // GroupOfPlanes.c:25-56 (block grid per level), :167-174 (blob layout)
         ALevel &L = P.lv[i];
@@ -351,6 +353,8 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_frames(mvx_ana
         hj[i].fieldShift = jobs[i].field_shift;
         hj[i].valid = jobs[i].ref[0] != nullptr;
         if (((uintptr_t)jobs[i].blob) & 15) { mvx_set_error("mvx_analyse_frames: blob must be 16-byte aligned"); return MVX_E_ARG; }
+        for (int p = 0; p < 3; p++)
+            if ((((uintptr_t)jobs[i].src[p]) | ((uintptr_t)jobs[i].ref[p])) & 15) { mvx_set_error("mvx_analyse_frames: super planes must be 16-byte aligned"); return MVX_E_ARG; }
     }
     // Chain placement.  Chains that search the same reference frame read the same lines at about the same time (they start
     // together and advance at the same pace).  The specialised kernels run FOUR (or eight) chains per workgroup, one (two) per
@@ -620,6 +624,8 @@ extern "C" __attribute__((visibility("default"))) int mvx_recalculate_create(con
     P.superHPad = si.hpad; P.superVPad = si.vpad;
     for (int p = 0; p < 3; p++) P.pitch[p] = p < si.num_planes ? super_pitch[p] : 0;
     if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) MVX_FAIL("Recalculate: the U and V planes of the super clip must share one pitch.");
+    for (int p = 0; p < si.num_planes; p++) // as Analyse
+        if (super_pitch[p] < (ptrdiff_t)si.plane_width[p] * P.bps || super_pitch[p] % 16) MVX_FAIL("Recalculate: super pitch of plane %d must hold a row of %d bytes and be a multiple of 16 bytes.", p, si.plane_width[p] * P.bps);
     {
         ALevel &L = P.lv[0];
         L.nBlkX = ad.nBlkX; L.nBlkY = ad.nBlkY; L.pel = ad.nPel; L.logPel = mvx_ilog2(L.pel);
@@ -688,6 +694,8 @@ extern "C" __attribute__((visibility("default"))) int mvx_recalculate_frames(mvx
         hj[i].valid = jobs[i].ref[0] != nullptr;
         if (!hj[i].oldBlob) { mvx_set_error("mvx_recalculate_frames: old_blob is required"); return MVX_E_ARG; }
         if ((((uintptr_t)jobs[i].blob) & 15) || (((uintptr_t)jobs[i].old_blob) & 15)) { mvx_set_error("mvx_recalculate_frames: blobs must be 16-byte aligned"); return MVX_E_ARG; }
+        for (int p = 0; p < 3; p++)
+            if ((((uintptr_t)jobs[i].src[p]) | ((uintptr_t)jobs[i].ref[p])) & 15) { mvx_set_error("mvx_recalculate_frames: super planes must be 16-byte aligned"); return MVX_E_ARG; }
     }
     HIP_CHECK(hipMemcpyAsync(r->dJobs, hj.data(), sizeof(AJob) * njobs, hipMemcpyHostToDevice, st));
     int srcBytes = P.blkX * P.blkY * P.bps;

@@ -60,9 +60,11 @@ static int blk_cell_width(const PlaneG &g, int widest) {
 
 struct BlkWin { DevBuf<int16_t> d[2]; int classes = 1; }; // a handle's overlap windows on the device: luma, chroma
 
-// the geometry of a filter whose parameter block was zeroed, and the two checks that are the library's own
+// the geometry of a filter whose parameter block was zeroed, and the checks that are the library's own: the block grid, then the plane
+// layouts (mvx_fps_shared.h).  src_what: what the filter calls the planes behind src_pitch; dst_bps: the sample size of the planes it writes
+// where that is not the clip's (out16)
 static int blk_fill(BlkGeom &G, BlkWin &win, const mvx_analysis_data *ad, const mvx_super_info &si, const ptrdiff_t src_pitch[3], const ptrdiff_t super_pitch[3],
-                    const ptrdiff_t dst_pitch[3], char *err) {
+                    const ptrdiff_t dst_pitch[3], char *err, const char *src_what = "src", int dst_bps = 0) {
     G.nBlkX = ad->nBlkX; G.nBlkY = ad->nBlkY; G.nBlk = ad->nBlkX * ad->nBlkY;
     G.pel = ad->nPel; G.logPel = ad->nPel == 4 ? 2 : ad->nPel == 2 ? 1 : 0;
     G.bits = si.bits; G.bps = (si.bits + 7) / 8; G.nplanes = si.num_planes;
@@ -71,16 +73,19 @@ static int blk_fill(BlkGeom &G, BlkWin &win, const mvx_analysis_data *ad, const 
     G.nLvCount = ad->nLvCount;
     fps_fill_planes(G.pl, ad, si, src_pitch, super_pitch, dst_pitch);
     if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) MVX_FAIL("U and V super planes must share one pitch.");
+    if (int rc = fps_check_super_pitches(si, super_pitch, err)) return rc;
+    if (src_pitch) if (int rc = fps_check_pitches(src_what, G.pl, si.num_planes, src_pitch, G.bps, err)) return rc;
+    if (int rc = fps_check_pitches("dst", G.pl, si.num_planes, dst_pitch, dst_bps ? dst_bps : G.bps, err)) return rc;
     win.classes = si.num_planes > 1 ? 2 : 1;
     return MVX_OK;
 }
 
 // a new handle H (members P, derived from BlkGeom, and win) with its geometry filled, or none
 template <typename H> static int blk_new(H **h, const mvx_analysis_data *ad, const mvx_super_info &si, const ptrdiff_t src_pitch[3], const ptrdiff_t super_pitch[3],
-                                         const ptrdiff_t dst_pitch[3], char *err) {
+                                         const ptrdiff_t dst_pitch[3], char *err, const char *src_what = "src", int dst_bps = 0) {
     *h = new H();
     memset(&(*h)->P, 0, sizeof((*h)->P));
-    const int rc = blk_fill((*h)->P, (*h)->win, ad, si, src_pitch, super_pitch, dst_pitch, err);
+    const int rc = blk_fill((*h)->P, (*h)->win, ad, si, src_pitch, super_pitch, dst_pitch, err, src_what, dst_bps);
     if (rc) { delete *h; *h = nullptr; }
     return rc;
 }

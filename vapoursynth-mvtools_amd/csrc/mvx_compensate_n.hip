@@ -212,6 +212,11 @@ extern "C" __attribute__((visibility("default"))) int mvx_compensate_n_frames(mv
         for (size_t k = 0; k < no; k++)
             for (int p = 0; p < P.nplanes; p++)
                 if (!J.dst[k][p]) { mvx_set_error("mvx_compensate_n_frames: output %d lacks plane %d", (int)k, p); return MVX_E_ARG; }
+        for (size_t k = 0; k < no; k++)
+            if (int rc = fps_check_planes("mvx_compensate_n_frames", "dst", J.dst[k], P.nplanes, P.bps, true)) return rc;
+        if (int rc = fps_check_planes("mvx_compensate_n_frames", "source super", J.src_super, P.nplanes, 16, true)) return rc;
+        for (size_t r = 0; r < nf; r++)
+            if (int rc = fps_check_planes("mvx_compensate_n_frames", "reference super", J.refs[r], P.nplanes, 16, false)) return rc;
     }
     CallGuard::Scope scope(c->guard, st);
     int rc = blk_upload(c->dP, c->P, c->win);

@@ -648,10 +648,16 @@ template <typename T> static void launch_degrain_cells(int nr, int W, dim3 grid,
 extern "C" __attribute__((visibility("default"))) int mvx_degrain_frames(mvx_degrain *d, int nframes, const mvx_degrain_job *jobs, void *stream) {
     if (nframes <= 0) return MVX_OK;
     hipStream_t st = (hipStream_t)stream;
+    const DGParams &P = d->P;
+    for (int f = 0; f < nframes; f++) {
+        if (int rc = fps_check_planes("mvx_degrain_frames", "src", jobs[f].src, P.nplanes, P.bps, true)) return rc;
+        if (int rc = fps_check_planes("mvx_degrain_frames", "dst", jobs[f].dst, P.nplanes, P.bps, true)) return rc;
+        for (int r = 0; r < P.nRefs; r++)
+            if (int rc = fps_check_planes("mvx_degrain_frames", "reference super", jobs[f].refs[r], P.nplanes, 16, false)) return rc;
+    }
     CallGuard::Scope scope(d->guard, st);
     int rc = blk_upload(d->dP, d->P, d->win);
     if (rc) return rc;
-    const DGParams &P = d->P;
     if ((rc = ensure_jobs(d, nframes, plan_rec_bytes(P.nRefs) * 2 * (size_t)P.nBlk))) return rc;
     std::vector<DGJob> hj(nframes);
     for (int f = 0; f < nframes; f++) {
@@ -715,10 +721,15 @@ extern "C" __attribute__((visibility("default"))) void mvx_compensate_destroy(mv
 extern "C" __attribute__((visibility("default"))) int mvx_compensate_frames(mvx_compensate *c, int nframes, const mvx_compensate_job *jobs, void *stream) {
     if (nframes <= 0) return MVX_OK;
     hipStream_t st = (hipStream_t)stream;
+    const DGParams &P = c->P;
+    for (int f = 0; f < nframes; f++) {
+        if (int rc = fps_check_planes("mvx_compensate_frames", "source super", jobs[f].src_super, P.nplanes, 16, true)) return rc;
+        if (int rc = fps_check_planes("mvx_compensate_frames", "reference super", jobs[f].ref_super, P.nplanes, 16, false)) return rc;
+        if (int rc = fps_check_planes("mvx_compensate_frames", "dst", jobs[f].dst, P.nplanes, P.bps, true)) return rc;
+    }
     CallGuard::Scope scope(c->guard, st);
     int rc = blk_upload(c->dP, c->P, c->win);
     if (rc) return rc;
-    const DGParams &P = c->P;
     if ((rc = ensure_jobs(c, nframes, sizeof(CPlanRec) * (size_t)P.nBlk))) return rc;
     std::vector<DGJob> hj(nframes);
     for (int f = 0; f < nframes; f++) {
@@ -1065,7 +1076,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_blockfps_create(const 
     if (fps_num == 0 || fps_den == 0) MVX_FAIL("BlockFPS: The input clip must have a frame rate. Invoke AssumeFPS if necessary.");
     if (!mvx_super_fits(bw, si, true)) MVX_FAIL("BlockFPS: wrong source or super clip frame size.");
     mvx_blockfps *h;
-    if (int rc = blk_new(&h, bw, si, clip_pitch, super_pitch, dst_pitch, err)) return rc;
+    if (int rc = blk_new(&h, bw, si, clip_pitch, super_pitch, dst_pitch, err, "clip")) return rc;
     DGParams &P = h->P;
     if (!(si.modeYUV & 6)) P.nplanes = 1;
     P.nRefs = 2; P.thscd1 = thscd1; P.thscd2 = thscd2;
@@ -1093,11 +1104,20 @@ extern "C" __attribute__((visibility("default"))) void mvx_blockfps_map(const mv
 extern "C" __attribute__((visibility("default"))) int mvx_blockfps_frames(mvx_blockfps *b, int nframes, const mvx_blockfps_job *jobs, void *stream) {
     if (nframes <= 0) return MVX_OK;
     hipStream_t st = (hipStream_t)stream;
+    const DGParams &P = b->P;
+    BFParams &B = b->B;
+    for (int f = 0; f < nframes; f++) {
+        const mvx_blockfps_job &J = jobs[f];
+        if (!J.clip_left[0] || (J.time256 > 0 && !J.clip_right[0])) { mvx_set_error("mvx_blockfps_frames: clip_left / clip_right are required"); return MVX_E_ARG; }
+        if (int rc = fps_check_planes("mvx_blockfps_frames", "clip_left", J.clip_left, P.nplanes, P.bps, true)) return rc;
+        if (int rc = fps_check_planes("mvx_blockfps_frames", "clip_right", J.clip_right, P.nplanes, P.bps, false)) return rc;
+        if (int rc = fps_check_planes("mvx_blockfps_frames", "dst", J.dst, P.nplanes, P.bps, true)) return rc;
+        if (int rc = fps_check_planes("mvx_blockfps_frames", "source super", J.src_super, P.nplanes, 16, false)) return rc;
+        if (int rc = fps_check_planes("mvx_blockfps_frames", "reference super", J.ref_super, P.nplanes, 16, false)) return rc;
+    }
     CallGuard::Scope scope(b->guard, st);
     int rc = blk_upload(b->dP, b->P, b->win);
     if (rc) return rc;
-    const DGParams &P = b->P;
-    BFParams &B = b->B;
     if (!b->dB.p && (rc = fps_upload_tables(b->dTables, b->dB, B, B.nWidthP, B.nHeightP))) return rc;
     if ((rc = ensure_jobs(b, nframes, sizeof(BFPlan) * (size_t)P.nBlk))) return rc;
     const size_t n = (size_t)nframes, cells = (size_t)B.XP * B.YP;
@@ -1116,7 +1136,6 @@ extern "C" __attribute__((visibility("default"))) int mvx_blockfps_frames(mvx_bl
         j.blobF = (const unsigned char *)jobs[f].blob_fw; j.blobB = (const unsigned char *)jobs[f].blob_bw;
         j.time256 = jobs[f].time256;
         j.good = j.srcSup[0] && j.refSup[0] && j.blobF && j.blobB;
-        if (!j.clipL[0] || (j.time256 > 0 && !j.clipR[0])) { mvx_set_error("mvx_blockfps_frames: clip_left / clip_right are required"); return MVX_E_ARG; }
     }
     HIP_CHECK(hipMemcpyAsync(b->dBJobs.p, hj.data(), sizeof(BFJob) * nframes, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(bf_usable_kernel, dim3(nframes), dim3(256), 0, st, b->dP.p, b->dB.p, b->dBJobs.p, b->dUsable.p);

@@ -395,7 +395,7 @@ static int dn_create(const mvx_degrain_n_args *a, const mvx_analysis_data *ad, c
     DgResolved r;
     if (int rc = dg_resolve(name, a, kind, ad, si, &r, err)) return rc;
     mvx_degrain_n *h;
-    if (int rc = blk_new(&h, ad, si, src_pitch, super_pitch, dst_pitch, err)) return rc;
+    if (int rc = blk_new(&h, ad, si, src_pitch, super_pitch, dst_pitch, err, "src", kind == DG_OUT16 ? 2 : 0)) return rc;
     h->info = r.info;
     h->out16 = kind == DG_OUT16;
     h->flt = kind == DG_FLOAT;
@@ -433,11 +433,19 @@ template <typename T, typename TO> static void dn_launch_cells(int W, dim3 grid,
 extern "C" __attribute__((visibility("default"))) int mvx_degrain_n_frames(mvx_degrain_n *d, int nframes, const mvx_degrain_n_job *jobs, void *stream) {
     if (nframes <= 0) return MVX_OK;
     hipStream_t st = (hipStream_t)stream;
+    const DNParams &P = d->P;
+    const size_t n = (size_t)nframes, nr = (size_t)P.nRefs;
+    for (size_t f = 0; f < n; f++) {
+        const mvx_degrain_n_job &J = jobs[f];
+        if (!J.refs || !J.blobs) { mvx_set_error("mvx_degrain_n_frames: a job needs its reference table and its blob table"); return MVX_E_ARG; }
+        if (int rc = fps_check_planes("mvx_degrain_n_frames", "src", J.src, P.nplanes, P.bps, true)) return rc;
+        if (int rc = fps_check_planes("mvx_degrain_n_frames", "dst", J.dst, P.nplanes, d->out16 ? 2 : P.bps, true)) return rc;
+        for (size_t r = 0; r < nr; r++)
+            if (int rc = fps_check_planes("mvx_degrain_n_frames", "reference super", J.refs[r], P.nplanes, 16, false)) return rc;
+    }
     CallGuard::Scope scope(d->guard, st);
     int rc = blk_upload(d->dP, d->P, d->win);
     if (rc) return rc;
-    const DNParams &P = d->P;
-    const size_t n = (size_t)nframes, nr = (size_t)P.nRefs;
     // one host block, one copy: jobs | reference planes | blobs (each part a multiple of 8 bytes)
     const size_t offRefs = sizeof(DNJob) * n, offBlobs = offRefs + sizeof(void *) * 3 * nr * n, total = offBlobs + sizeof(void *) * nr * n;
     std::vector<unsigned char> host(total, 0);

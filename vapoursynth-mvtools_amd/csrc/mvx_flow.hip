@@ -279,6 +279,10 @@ static int flow_geometry(FLParams &P, int nWidthP[2], int nHeightP[2], const cha
     if (P.XP < 2 || P.YP < 2) MVX_FAIL("%s: the frame must be at least two blocks wide and two blocks high.", name);
     if (si.num_planes > 1 && super_pitch[1] != super_pitch[2]) MVX_FAIL("%s: U and V super planes must share one pitch.", name);
     fps_fill_planes(P.pl, bw, si, nullptr, super_pitch, dst_pitch);
+    // the plane layouts (mvx_fps_shared.h), prefixed with the filter's name like every message of the flow filters
+    char msg[MVX_ERRLEN];
+    if (fps_check_super_pitches(si, super_pitch, msg) || fps_check_pitches("clip", P.pl, P.nplanes, clip_pitch, P.bps, msg) ||
+        fps_check_pitches("dst", P.pl, P.nplanes, dst_pitch, P.bps, msg)) MVX_FAIL("%s: %s", name, msg);
     for (int p = 0; p < 3; p++) P.clipPitch[p] = clip_pitch[p < si.num_planes ? p : 0];
     return MVX_OK;
 }
@@ -369,8 +373,20 @@ extern "C" __attribute__((visibility("default"))) void mvx_flow_map(const mvx_fl
 extern "C" __attribute__((visibility("default"))) int mvx_flow_frames(mvx_flow *h, int nframes, const mvx_flow_job *jobs, void *stream) {
     if (nframes <= 0) return MVX_OK;
     hipStream_t st = (hipStream_t)stream;
-    CallGuard::Scope scope(h->guard, st);
     FLParams &P = h->P;
+    for (int f = 0; f < nframes; f++) { // the jobs' checks, before anything is uploaded or launched
+        const mvx_flow_job &s = jobs[f];
+        if (s.time256 < 0 || s.time256 > 256) { mvx_set_error("mvx_flow_frames: time256 must be between 0 and 256"); return MVX_E_ARG; }
+        const int copy = P.isFPS && s.time256 <= 0 ? 1 : P.isFPS && s.time256 >= 256 ? 2 : 0;
+        const bool right = copy == 2 || (!copy && P.blend);
+        if (!s.dst[0] || !s.clip_left[0] || (right && !s.clip_right[0])) { mvx_set_error("mvx_flow_frames: dst / clip_left / clip_right are required"); return MVX_E_ARG; }
+        if (int rc = fps_check_planes("mvx_flow_frames", "dst", s.dst, P.nplanes, P.bps, true)) return rc;
+        if (int rc = fps_check_planes("mvx_flow_frames", "clip_left", s.clip_left, P.nplanes, P.bps, true)) return rc;
+        if (int rc = fps_check_planes("mvx_flow_frames", "clip_right", s.clip_right, P.nplanes, P.bps, right)) return rc;
+        if (int rc = fps_check_planes("mvx_flow_frames", "super_left", s.super_left, P.nplanes, 16, false)) return rc;
+        if (int rc = fps_check_planes("mvx_flow_frames", "super_right", s.super_right, P.nplanes, 16, false)) return rc;
+    }
+    CallGuard::Scope scope(h->guard, st);
     if (!h->dP.p) // MVFlowInter.c:677-679
         if (int rc = fps_upload_tables(h->dTables, h->dP, P, h->nWidthP, h->nHeightP)) return rc;
     const size_t n = (size_t)nframes, cellsN = (size_t)P.XP * P.YP;
@@ -394,10 +410,6 @@ extern "C" __attribute__((visibility("default"))) int mvx_flow_frames(mvx_flow *
         j.time256 = s.time256;
         if (P.isFPS && s.time256 <= 0) j.copy = 1;
         else if (P.isFPS && s.time256 >= 256) j.copy = 2;
-        if (s.time256 < 0 || s.time256 > 256) { mvx_set_error("mvx_flow_frames: time256 must be between 0 and 256"); return MVX_E_ARG; }
-        if (!j.dst[0] || !j.clipL[0] || ((j.copy == 2 || (!j.copy && P.blend)) && !j.clipR[0])) {
-            mvx_set_error("mvx_flow_frames: dst / clip_left / clip_right are required"); return MVX_E_ARG;
-        }
     }
     HIP_CHECK(hipMemcpyAsync(h->dJobs.p, hj.data(), sizeof(FLJob) * nframes, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(flow_usable_kernel, dim3(nframes, 4), dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p);
@@ -707,8 +719,15 @@ extern "C" __attribute__((visibility("default"))) int mvx_flowcomp_ref(const mvx
 extern "C" __attribute__((visibility("default"))) int mvx_flowcomp_frames(mvx_flowcomp *h, int nframes, const mvx_flowcomp_job *jobs, void *stream) {
     if (nframes <= 0) return MVX_OK;
     hipStream_t st = (hipStream_t)stream;
-    CallGuard::Scope scope(h->guard, st);
     FLParams &P = h->P;
+    for (int f = 0; f < nframes; f++) { // the jobs' checks, before the call takes the handle's guard
+        const mvx_flowcomp_job &s = jobs[f];
+        if (!s.dst[0] || !s.clip[0]) { mvx_set_error("mvx_flowcomp_frames: dst / clip are required"); return MVX_E_ARG; }
+        if (int rc = fps_check_planes("mvx_flowcomp_frames", "dst", s.dst, P.nplanes, P.bps, true)) return rc;
+        if (int rc = fps_check_planes("mvx_flowcomp_frames", "clip", s.clip, P.nplanes, P.bps, true)) return rc;
+        if (int rc = fps_check_planes("mvx_flowcomp_frames", "ref_super", s.ref_super, P.nplanes, 16, false)) return rc;
+    }
+    CallGuard::Scope scope(h->guard, st);
     std::vector<FMJob> hj(nframes);
     for (int f = 0; f < nframes; f++) {
         FMJob &j = hj[f];
@@ -721,7 +740,6 @@ extern "C" __attribute__((visibility("default"))) int mvx_flowcomp_frames(mvx_fl
         }
         j.blob[0] = comp ? (const unsigned char *)s.blob : nullptr;
         j.fieldShift = s.field_shift;
-        if (!j.dst[0] || !j.clip[0]) { mvx_set_error("mvx_flowcomp_frames: dst / clip are required"); return MVX_E_ARG; }
     }
     if (int rc = fm_prologue(h, nframes, hj, st)) return rc;
     if (h->mode == 0) {
@@ -767,8 +785,15 @@ extern "C" __attribute__((visibility("default"))) void mvx_flowblur_destroy(mvx_
 extern "C" __attribute__((visibility("default"))) int mvx_flowblur_frames(mvx_flowblur *h, int nframes, const mvx_flowblur_job *jobs, void *stream) {
     if (nframes <= 0) return MVX_OK;
     hipStream_t st = (hipStream_t)stream;
-    CallGuard::Scope scope(h->guard, st);
     FLParams &P = h->P;
+    for (int f = 0; f < nframes; f++) { // the jobs' checks, before the call takes the handle's guard
+        const mvx_flowblur_job &s = jobs[f];
+        if (!s.dst[0] || !s.clip[0]) { mvx_set_error("mvx_flowblur_frames: dst / clip are required"); return MVX_E_ARG; }
+        if (int rc = fps_check_planes("mvx_flowblur_frames", "dst", s.dst, P.nplanes, P.bps, true)) return rc;
+        if (int rc = fps_check_planes("mvx_flowblur_frames", "clip", s.clip, P.nplanes, P.bps, true)) return rc;
+        if (int rc = fps_check_planes("mvx_flowblur_frames", "super", s.super, P.nplanes, 16, false)) return rc;
+    }
+    CallGuard::Scope scope(h->guard, st);
     std::vector<FMJob> hj(nframes);
     for (int f = 0; f < nframes; f++) {
         FMJob &j = hj[f];
@@ -781,7 +806,6 @@ extern "C" __attribute__((visibility("default"))) int mvx_flowblur_frames(mvx_fl
         }
         j.blob[0] = comp ? (const unsigned char *)s.blob_bw : nullptr;
         j.blob[1] = comp ? (const unsigned char *)s.blob_fw : nullptr;
-        if (!j.dst[0] || !j.clip[0]) { mvx_set_error("mvx_flowblur_frames: dst / clip are required"); return MVX_E_ARG; }
     }
     if (int rc = fm_prologue(h, nframes, hj, st)) return rc;
     fps_classes(P.pl, P.nplanes, nframes, [](int) { return 1; }, [&](dim3 grid, int, int p0, int npl) { // one sample per thread

@@ -313,6 +313,37 @@ static void fps_fill_planes(PlaneG pl[3], const mvx_analysis_data *ad, const mvx
     }
 }
 
+// ---- the layout contract of the vector consumers (include/mvtools_amd.h, "Plane layouts").  Clip-side planes -- the clip planes a filter
+// reads and the planes it writes: a pitch holds a row of its plane and is a multiple of the sample size, and so is every plane address; U and
+// V may differ.  Super planes: what mvx_super_frames writes -- pitches that hold a row and are multiples of 16 bytes, U and V alike, planes on
+// 16-byte boundaries.  *_create checks the pitches, *_frames the addresses, before anything is uploaded or launched.
+// the pitches of the planes `what` ("src", "clip", "dst") of pl[0..nplanes), sample size bps
+static int fps_check_pitches(const char *what, const PlaneG pl[3], int nplanes, const ptrdiff_t pitch[3], int bps, char *err) {
+    for (int p = 0; p < nplanes; p++) {
+        const long long row = (long long)pl[p].W * bps;
+        if (pitch[p] < row || pitch[p] % bps) MVX_FAIL("%s pitch of plane %d must hold a row of %lld bytes and be a multiple of the sample size.", what, p, row);
+    }
+    return MVX_OK;
+}
+// the pitches of the super planes
+static int fps_check_super_pitches(const mvx_super_info &si, const ptrdiff_t super_pitch[3], char *err) {
+    const int bps = (si.bits + 7) / 8;
+    for (int p = 0; p < si.num_planes; p++) {
+        const long long row = (long long)si.plane_width[p] * bps;
+        if (super_pitch[p] < row || super_pitch[p] % 16) MVX_FAIL("super pitch of plane %d must hold a row of %lld bytes and be a multiple of 16 bytes.", p, row);
+    }
+    return MVX_OK;
+}
+// the addresses of one job's planes `what`: each a multiple of `align` bytes, and all there when `required` (planes a job may leave out --
+// a reference outside the clip, the chroma of a super clip without chroma -- are NULL and pass)
+static int fps_check_planes(const char *fn, const char *what, const void *const *planes, int nplanes, int align, bool required) {
+    for (int p = 0; p < nplanes; p++) {
+        if (!planes[p] && required) { mvx_set_error("%s: %s plane %d is required", fn, what, p); return MVX_E_ARG; }
+        if ((uintptr_t)planes[p] % (uintptr_t)align) { mvx_set_error("%s: %s plane %d must be aligned to %d bytes", fn, what, p, align); return MVX_E_ARG; }
+    }
+    return MVX_OK;
+}
+
 // ---- launches of the kernels that produce CW consecutive samples per thread, 64 x 4 threads per workgroup
 // the widest segment of at most 16 bytes that divides a plane of W samples
 static int fps_segment(int bps, int W) { int cw = 16 / bps; while (cw > 1 && W % cw) cw >>= 1; return cw; }

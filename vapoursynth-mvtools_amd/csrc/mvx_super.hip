@@ -728,6 +728,15 @@ static int super_frames_impl(mvx_super *s, int nframes, const void *const *src, 
     CallGuard::Scope scope(g_scratch_guard, st);
     for (int p = 0; p < si.num_planes; p++)
         if (dst_pitch[p] % 16) { mvx_set_error("mvx_super_frames: dst pitch must be a multiple of 16 bytes"); return MVX_E_ARG; }
+    for (int p = 0; p < si.num_planes; p++) { // the source: any pitch that holds a row and any address, both multiples of the sample size
+        if (!(si.modeYUV & (1 << p))) continue;
+        const int sb = si.bits <= 8 ? 1 : 2;
+        LevelPlane lp;
+        mvx_level_plane(si, 0, p, dst_pitch[p], &lp);
+        if (src_pitch[p] < (ptrdiff_t)lp.w * sb || src_pitch[p] % sb) { mvx_set_error("mvx_super_frames: src pitch must hold a row and be a multiple of the sample size"); return MVX_E_ARG; }
+        for (int f = 0; f < nframes; f++)
+            if ((uintptr_t)src[f * 3 + p] % sb || (uintptr_t)dst[f * 3 + p] % sb) { mvx_set_error("mvx_super_frames: planes must be aligned to the sample size"); return MVX_E_ARG; }
+    }
     void *dsrc = nullptr, *ddst = nullptr;
     int rc;
     if ((rc = upload_ptrs(0, src, (size_t)nframes * 3, st, &dsrc))) return rc;
@@ -948,6 +957,21 @@ extern "C" __attribute__((visibility("default"))) int mvx_finest_frames(const mv
     hipStream_t st = (hipStream_t)stream;
     const mvx_super_info &si = s->info;
     const int logPel = si.pel == 4 ? 2 : si.pel == 2 ? 1 : 0;
+    // the layouts, before anything is launched: the kernel loads and stores single samples, so pitches that hold a row and addresses need
+    // no more than the sample's alignment
+    const int bps = si.bits <= 8 ? 1 : 2;
+    for (int p = 0; p < si.num_planes; p++) {
+        if (!(si.modeYUV & (1 << p))) continue;
+        LevelPlane lp;
+        mvx_level_plane(si, 0, p, super_pitch[p], &lp);
+        if (super_pitch[p] < (ptrdiff_t)lp.pw * bps || super_pitch[p] % bps || dst_pitch[p] < (ptrdiff_t)lp.pw * si.pel * bps || dst_pitch[p] % bps) {
+            mvx_set_error("mvx_finest_frames: pitches must hold a row of their plane and be multiples of the sample size"); return MVX_E_ARG;
+        }
+        for (int f = 0; f < nframes; f++)
+            if (!super_frames[f * 3 + p] || !dst[f * 3 + p] || (uintptr_t)super_frames[f * 3 + p] % bps || (uintptr_t)dst[f * 3 + p] % bps) {
+                mvx_set_error("mvx_finest_frames: planes are required and must be aligned to the sample size"); return MVX_E_ARG;
+            }
+    }
     for (int f = 0; f < nframes; f++)
         for (int p = 0; p < si.num_planes; p++) {
             if (!(si.modeYUV & (1 << p))) continue; // planes the super clip does not carry stay untouched (MVFinest.c:87 pPlanes[i] == NULL)

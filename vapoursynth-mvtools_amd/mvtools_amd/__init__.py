@@ -565,7 +565,7 @@ class Super(_Handle):
     _destroy = "mvx_super_destroy"
 
     def __init__(self, width, height, bits=8, subsampling=(1, 1), gray=False, hpad=None, vpad=None, pel=None, levels=None,
-                 chroma=None, sharp=None, rfilter=None, shadow=None, sample_float=False):
+                 chroma=None, sharp=None, rfilter=None, shadow=None, sample_float=False, pitch=None):
         a = SuperArgs(width, height, bits, subsampling[0], subsampling[1], int(gray), _u(hpad), _u(vpad), _u(pel), _u(levels),
                       _u(chroma), _u(sharp), _u(rfilter))
         self.h = C.c_void_p()
@@ -581,6 +581,10 @@ class Super(_Handle):
             shadow = False
         self.nplanes = self.info.num_planes
         self.pitch = [((self.info.plane_width[p] * self.bps + 255) // 256) * 256 for p in range(self.nplanes)]
+        if pitch is not None:  # a caller's row pitches (bytes per plane; mvx_super_frames wants multiples of 16): alloc, the shadow planes and every consumer follow
+            if len(pitch) != self.nplanes or any(q % 16 or q < self.info.plane_width[p] * self.bps for p, q in enumerate(pitch)):
+                raise ValueError("Super: pitch needs %d multiples of 16 that hold a row of their plane" % self.nplanes)
+            self.pitch = [int(q) for q in pitch]
         # developer experiment (r4): row pitch as a number of 128-byte lines that is odd / a given residue -- how the rows of a block and the
         # sub-pel planes spread over the sets of the CU's L1.  MVX_PITCH_LINES="odd" | "<k>" (pitch = smallest number of lines >= the row that is == k mod 64)
         _pl = os.environ.get("MVX_PITCH_LINES")
@@ -670,6 +674,9 @@ class Super(_Handle):
         pitch = [((dims[p][1] * self.bps + 255) // 256) * 256 for p in range(self.nplanes)]
         if out is None:
             out = arena_frames(n, [(dims[p][0], pitch[p]) for p in range(self.nplanes)], super_frames[0][0].device)
+        else:  # the caller's planes, at their pitch
+            pitch = [out[0][p].stride(0) for p in range(self.nplanes)]
+            assert all(o[p].stride(0) == pitch[p] for o in out for p in range(self.nplanes))
         src = (C.c_void_p * (3 * n))()
         dst = (C.c_void_p * (3 * n))()
         for f in range(n):
@@ -1082,7 +1089,7 @@ class BlockFPS(_Handle):
     _destroy = "mvx_blockfps_destroy"
 
     def __init__(self, sup, ad_bw, ad_fw, num_frames, clip_pitch, fps_num=24, fps_den=1, num=None, den=None, mode=None, ml=100.0, blend=None, thscd1=None,
-                 thscd2=None):
+                 thscd2=None, dst_pitch=None):
         self.sup = sup
         a = BlockFPSArgs(_u(num), _u(den), _u(mode), float(ml), _u(blend), _u(thscd1), _u(thscd2))
         bw = AnalysisData.from_buffer_copy(bytes(ad_bw))
@@ -1091,7 +1098,7 @@ class BlockFPS(_Handle):
         self.pitch = list(clip_pitch)
         err = C.create_string_buffer(ERRLEN)
         _check(lib().mvx_blockfps_create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, int(num_frames), int(fps_num), int(fps_den), _pad3(sup.pitch), _pad3(clip_pitch),
-                                         _pad3(clip_pitch), C.byref(self.h), err), err)
+                                         _pad3(dst_pitch or clip_pitch), C.byref(self.h), err), err)
         self.in_frames = int(num_frames)
         info = BlockFPSInfo()
         lib().mvx_blockfps_get_info(self.h, C.byref(info))
@@ -1192,12 +1199,12 @@ class FlowInter(_Flow):
     """mv.FlowInter(clip, super, mvbw, mvfw, time, ml, blend, thscd1, thscd2) -- MVFlowInter.c:473-678.  Output frame n lies `time` percent
     of the way from input frame n to n + delta; `clip_pitch` is the row pitch of the clip's device planes (and of the output)."""
 
-    def __init__(self, sup, ad_bw, ad_fw, num_frames, clip_pitch, time=50.0, ml=100.0, blend=None, thscd1=None, thscd2=None):
+    def __init__(self, sup, ad_bw, ad_fw, num_frames, clip_pitch, time=50.0, ml=100.0, blend=None, thscd1=None, thscd2=None, dst_pitch=None):
         a = FlowInterArgs(float(time), float(ml), _u(blend), _u(thscd1), _u(thscd2))
         bw = AnalysisData.from_buffer_copy(bytes(ad_bw))
         fw = AnalysisData.from_buffer_copy(bytes(ad_fw))
         super().__init__(sup, num_frames, lambda h, err: lib().mvx_flowinter_create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, int(num_frames), _pad3(sup.pitch),
-                                                                                     _pad3(clip_pitch), _pad3(clip_pitch), h, err))
+                                                                                     _pad3(clip_pitch), _pad3(dst_pitch or clip_pitch), h, err))
 
 
 class FlowFPS(_Flow):
@@ -1205,12 +1212,12 @@ class FlowFPS(_Flow):
     input clip's frame rate; `clip_pitch` the row pitch of its device planes (and of the output)."""
 
     def __init__(self, sup, ad_bw, ad_fw, num_frames, clip_pitch, fps_num=24, fps_den=1, num=None, den=None, mask=None, ml=100.0, blend=None, thscd1=None,
-                 thscd2=None):
+                 thscd2=None, dst_pitch=None):
         a = FlowFPSArgs(_u(num), _u(den), _u(mask), float(ml), _u(blend), _u(thscd1), _u(thscd2))
         bw = AnalysisData.from_buffer_copy(bytes(ad_bw))
         fw = AnalysisData.from_buffer_copy(bytes(ad_fw))
         super().__init__(sup, num_frames, lambda h, err: lib().mvx_flowfps_create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, int(num_frames), int(fps_num),
-                                                                                   int(fps_den), _pad3(sup.pitch), _pad3(clip_pitch), _pad3(clip_pitch), h, err))
+                                                                                   int(fps_den), _pad3(sup.pitch), _pad3(clip_pitch), _pad3(dst_pitch or clip_pitch), h, err))
 
 
 class Flow(_Handle):
@@ -1218,7 +1225,7 @@ class Flow(_Handle):
     per sample from the Finest frame of ref(n); `clip_pitch` is the row pitch of the clip's device planes (and of the output)."""
     _destroy = "mvx_flowcomp_destroy"
 
-    def __init__(self, sup, ad, num_frames, clip_pitch, time=100.0, mode=None, fields=None, thscd1=None, thscd2=None):
+    def __init__(self, sup, ad, num_frames, clip_pitch, time=100.0, mode=None, fields=None, thscd1=None, thscd2=None, dst_pitch=None):
         self.sup = sup
         a = FlowCompArgs(float(time), _u(mode), _u(fields), _u(thscd1), _u(thscd2))
         ad = AnalysisData.from_buffer_copy(bytes(ad))
@@ -1226,7 +1233,7 @@ class Flow(_Handle):
         self.pitch = list(clip_pitch)
         self.num_frames = int(num_frames)
         err = C.create_string_buffer(ERRLEN)
-        _check(lib().mvx_flowcomp_create(C.byref(a), C.byref(ad), sup.h, self.num_frames, _pad3(sup.pitch), _pad3(clip_pitch), _pad3(clip_pitch),
+        _check(lib().mvx_flowcomp_create(C.byref(a), C.byref(ad), sup.h, self.num_frames, _pad3(sup.pitch), _pad3(clip_pitch), _pad3(dst_pitch or clip_pitch),
                                          C.byref(self.h), err), err)
 
     def ref(self, n):
@@ -1262,7 +1269,7 @@ class FlowBlur(_Handle):
     device planes (and of the output)."""
     _destroy = "mvx_flowblur_destroy"
 
-    def __init__(self, sup, ad_bw, ad_fw, num_frames, clip_pitch, blur=50.0, prec=None, thscd1=None, thscd2=None):
+    def __init__(self, sup, ad_bw, ad_fw, num_frames, clip_pitch, blur=50.0, prec=None, thscd1=None, thscd2=None, dst_pitch=None):
         self.sup = sup
         a = FlowBlurArgs(float(blur), _u(prec), _u(thscd1), _u(thscd2))
         bw = AnalysisData.from_buffer_copy(bytes(ad_bw))
@@ -1273,7 +1280,7 @@ class FlowBlur(_Handle):
         self.delta = bw.nDeltaFrame
         err = C.create_string_buffer(ERRLEN)
         _check(lib().mvx_flowblur_create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, self.num_frames, _pad3(sup.pitch), _pad3(clip_pitch),
-                                         _pad3(clip_pitch), C.byref(self.h), err), err)
+                                         _pad3(dst_pitch or clip_pitch), C.byref(self.h), err), err)
 
     def run(self, ns, clip, supers, blobs_bw, blobs_fw, out=None):
         """ns: output frame numbers, one job each, all in one call; clip / supers: device frames of the input clip and its super clip;
