@@ -16,7 +16,8 @@
  *   - there is NO CPU fallback: if no gfx950 device / kernel image is available the call fails.
  *
  * Plane layouts (checked: *_create refuses a pitch, *_frames an address, with MVX_E_ARG and before anything is uploaded or launched)
- *   - Clip-side planes -- src / clip / dst of mvx_degrain, mvx_degrain_n in all its three entries, mvx_compensate, mvx_compensate_n,
+ *   - Clip-side planes -- src / clip / dst of mvx_degrain, mvx_degrain_n in all its three entries, mvx_compensate and mvx_compensate_n with
+ *     their float entries,
  *     mvx_blockfps, mvx_flowinter / mvx_flowfps, mvx_flowcomp and mvx_flowblur: any pitch that holds a row of its plane and is a multiple of
  *     the sample size (1, 2, or 4 bytes for a float clip; out16 writes 2-byte samples), and any plane address that is a multiple of the
  *     sample size.  A tight pitch, an odd pitch for 8-bit samples, a plane inside a wider frame, U and V of different pitch, src and dst of
@@ -102,7 +103,8 @@ void mvx_super_get_info(const mvx_super *s, mvx_super_info *info);
  *   sharp 1   ((s(X) + s(X+1)) * 9.0f - (s(X-1) + s(X+2))) * 0.0625f
  *   sharp 2   m2 = (m2 + m3) * 4; m2 -= (m1 + m4); m2 *= 5; m0 = (m0 + m5) + m2; m0 * 0.03125f
  *   the diagonal plane of sharp 1 and 2 is the horizontal rule on the UNROUNDED vertical plane; pel 4: (a + b) * 0.5f
- * (csrc/mvx_super_float_rule.h).  Samples are assumed finite.  Only mvx_degrain_n_create_float consumes such an object: mvx_super_shadow_copies
+ * (csrc/mvx_super_float_rule.h).  Samples are assumed finite.  Only the float entries -- mvx_degrain_n_create_float, mvx_compensate_create_float and
+ * mvx_compensate_n_create_float -- consume such an object: mvx_super_shadow_copies
  * returns 0, the shadow, pelclip and Finest entries return MVX_E_ARG, and every other *_create that takes an mvx_super refuses it before any
  * other check with "<Name>: float super clips are not supported.".  Touches no device. */
 int mvx_super_create_float(const mvx_super_args *args, mvx_super **out, char *err);
@@ -375,6 +377,17 @@ typedef struct mvx_compensate_job {
 
 int mvx_compensate_frames(mvx_compensate *c, int nframes, const mvx_compensate_job *jobs, void *stream);
 
+/* Compensate on a 32-bit float clip, for ONE vector clip of any isb and delta: the single-field form of mvx_compensate_n_create_float (below),
+ * whose arithmetic table, layout rules and notes on the vectors hold here word for word -- one field and one output per job, no centre; the
+ * output is bit for bit output k of mvx_compensate_n_frames for the same (source, reference, field).  Messages are mvx_compensate_create's in
+ * their order, after the frame-size check "Compensate: the float entry needs a float super clip."; fields = 1 is refused last with
+ * "Compensate: fields is not supported on float clips.".  Touches no device.  mvx_compensate_frames and mvx_compensate_destroy serve the
+ * object; for it mvx_compensate_frames refuses a job whose field_shift is not 0 ("mvx_compensate_frames: field_shift is not supported on
+ * float clips"), a job without a blob, and more than 32767 jobs per call. */
+int mvx_compensate_create_float(const mvx_compensate_args *args, const mvx_analysis_data *vectors_data,
+                                const mvx_super *super_clip /* float */, const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3],
+                                mvx_compensate **out, char *err);
+
 /* ---- the multi blob, mv.AnalyseN and mv.CompensateN: one source frame against a temporal radius ------
  * No reference counterpart: pinterf's MAnalyse(multi=true, delta=tr) / MCompensate(tr=...) and mvtools-sf's Analyze(radius=...) /
  * Compensate(tr=...) are the models.  Nothing new is computed: every field is one mvx_analyse_frames result and every compensated frame
@@ -440,6 +453,29 @@ typedef struct mvx_compensate_n_job {
  * source: the unpadded pel-0 window of the finest level of src_super, copied.  One usable pass and one plan pass over all fields of all
  * jobs, then one output kernel per plane class whose grid covers the 2 * tr + 1 planes of every job (csrc/mvx_compensate_n.hip). */
 int mvx_compensate_n_frames(mvx_compensate_n *c, int njobs, const mvx_compensate_n_job *jobs, void *stream);
+
+/* CompensateN on a 32-bit float clip: the super clip (mvx_super_create_float) and the outputs are float32 planes; vectors_data and the multi
+ * blob come from a search on ANY 8..16 bit clip of the same width, height, pel, padding and subsampling (AnalyseN / RecalculateN, or fields
+ * that ScaleVect wrote).  thsad, thscd1 and thscd2 are in the units of that search and resolved from vectors_data; which fields are usable,
+ * where a block comes from (its vector scaled by time, or its own place at sad >= thsad) and the output -> field map are exactly those of
+ * mvx_compensate_n_create for the same blob.  A sample, float32, every operation rounded on its own:
+ *   centre output                a plain load and store of the unpadded pel-0 window of src_super, bit for bit
+ *   unusable field               (scene change per thscd1 / thscd2, invalid blob, reference outside the clip) the same plain copy: the
+ *                                reference at scbehavior 0 where there is one, else the source
+ *   strips no block covers       the same plain copy: the source at scbehavior 1, the reference at 0
+ *   blocks side by side          (overlap 0) the same plain copy of the block's samples from where its vector points
+ *   overlapped blocks            acc = 0; over the covering blocks (by outer, bx inner, ascending) acc = acc + v * (float)win; out = acc /
+ *                                (float)wsum with wsum the integer sum of those same window weights (2047..2049), as in
+ *                                mvx_degrain_n_create_float: no >> 6 per term, no rounding term, no clamp, no 16-bit wrap
+ *   a cell cut by the frame's edge   sample by sample, the same values
+ * Copies move bytes and never look at them; samples may be negative or overshoot.  Inputs of overlapped blocks are assumed finite.
+ * Messages are mvx_compensate_n_create's in their order, after the frame-size check "CompensateN: the float entry needs a float super clip.",
+ * and "CompensateN: fields is not supported." stays last.  Touches no device.  mvx_compensate_n_map, mvx_compensate_n_frames and
+ * mvx_compensate_n_destroy serve the object.  Layouts in mvx_compensate_n_frames: dst planes at any pitch that holds a row and any address,
+ * both multiples of 4; super planes with pitches and addresses that are multiples of 16; everything else is refused before a launch. */
+int mvx_compensate_n_create_float(const mvx_compensate_args *args, int tr, const mvx_analysis_data *vectors_data /* of field 0 */,
+                                  const mvx_super *super_clip /* float */, const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3],
+                                  mvx_compensate_n **out, char *err);
 
 /* ---- mv.RecalculateN: a multi blob refined field by field -------------------------------------------
  * No reference counterpart: pinterf's MRecalculate(tr=...) is the model.  Field r of the new multi blob is one mvx_recalculate_frames result

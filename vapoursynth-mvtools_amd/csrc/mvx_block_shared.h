@@ -157,7 +157,9 @@ static void dg_apply(BlkGeom &G, const DgResolved &r, const mvx_super_info &si) 
 
 // Compensate (MVCompensate.c:419-575) and CompensateN
 struct CompResolved { int scBehavior, time256, fields; long long thSAD; int64_t thscd1; int32_t thscd2; };
-static int comp_resolve(const char *name, const mvx_compensate_args *a, const mvx_analysis_data *ad, const mvx_super_info &si, CompResolved *r, char *err) {
+// not_float: a float entry was handed an integer super clip (said after the frame-size check)
+static int comp_resolve(const char *name, const mvx_compensate_args *a, const mvx_analysis_data *ad, const mvx_super_info &si, CompResolved *r, char *err,
+                        bool not_float = false) {
     r->scBehavior = a->scbehavior == MVX_UNSET ? 1 : !!a->scbehavior;
     r->thSAD = a->thsad == MVX_UNSET ? 10000 : a->thsad;
     const double time = a->time;
@@ -166,11 +168,19 @@ static int comp_resolve(const char *name, const mvx_compensate_args *a, const mv
     if (int rc = mvx_resolve_thscd(name, a->thscd1, a->thscd2, ad, &r->thscd1, &r->thscd2, err, &nSCD1_old)) return rc;
     r->thSAD = r->thSAD * r->thscd1 / nSCD1_old; // :521
     if (!mvx_super_fits(ad, si, true)) MVX_FAIL("%s: wrong source or super clip frame size.", name);
+    if (not_float) MVX_FAIL("%s: the float entry needs a float super clip.", name);
     r->fields = a->fields != MVX_UNSET && a->fields;
     if (r->fields && ad->nPel < 2) MVX_FAIL("%s: fields option requires pel > 1.", name); // :514-517
     r->time256 = (int)(time * 256 / 100); // :560
     return MVX_OK;
 }
+// mvx_compensate_create_float's object is a single-field object of the float engine in mvx_compensate_n.hip; mvx_compensate (mvx_degrain.hip)
+// holds it and forwards mvx_compensate_frames and mvx_compensate_destroy
+struct mvx_compensate_n;
+int cn_single_create(const mvx_compensate_args *a, const mvx_analysis_data *ad, const mvx_super *sup, const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3],
+                     mvx_compensate_n **out, char *err);
+int cn_single_frames(mvx_compensate_n *c, int nframes, const mvx_compensate_job *jobs, void *stream);
+void cn_single_destroy(mvx_compensate_n *c);
 // ... into a geometry that blk_fill has filled
 static void comp_apply(BlkGeom &G, const CompResolved &r, const mvx_super_info &si) {
     G.thscd1 = r.thscd1; G.thscd2 = r.thscd2;

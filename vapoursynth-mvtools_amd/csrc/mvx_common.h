@@ -88,7 +88,7 @@ struct mvx_super {
     mvx_super_info info;
     // per level / plane dims (pitch independent part)
     int lw[MVX_MAX_LEVELS][3], lh[MVX_MAX_LEVELS][3];
-    bool is_float = false; // mvx_super_create_float: float32 samples, one level; only mvx_super_frames and mvx_degrain_n_create_float take it
+    bool is_float = false; // mvx_super_create_float: float32 samples, one level; only mvx_super_frames and the *_create_float entries take it
 };
 // the first line after MVX_CREATE_BEGIN of every create that takes a super clip and has no float path
 #define MVX_REFUSE_FLOAT(sup, name) do { if ((sup)->is_float) MVX_FAIL("%s: float super clips are not supported.", name); } while (0)

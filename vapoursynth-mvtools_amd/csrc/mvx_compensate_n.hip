@@ -21,6 +21,7 @@ struct CNParams : BlkGeom {
     int tr, nFields, nOut;
     int time256, scBehavior;
     long long thSAD;
+    int single;              // the float kernel's output -> field map: 0 cn_field(tr, k); 1 output k is field k (mvx_compensate_create_float: one field, no centre)
 };
 
 struct __attribute__((aligned(16))) CNRec { unsigned off[2]; int fromRef; int pad; }; // off[0] luma, off[1] chroma
@@ -142,6 +143,97 @@ __global__ __launch_bounds__(256) void cn_cell_kernel(const CNParams *Pp, CNTabl
     dg_store<T, W>(dg_glw(drow), out);
 }
 
+// ---- float clips (mvx_compensate_n_create_float, mvx_compensate_create_float): cn_cell_kernel's cells and threads on float32 samples.  Usable
+// pass, plan and tables are those above (none of them touches a sample).  Every case but overlapped blocks moves the cell's bytes and never
+// looks at them; overlapped blocks are DegrainN-float's rule (include/mvtools_amd.h): acc = acc + v * (float)win over the
+// covering blocks, by outer and bx inner, then acc / (float)wsum -- every operation rounded on its own, no shift, no rounding term, no clamp.
+// W * 4 bytes, 16 at most.
+template <int W> __device__ __forceinline__ void cn_store_raw(DG_GL unsigned char *p, const DgRaw<float, W> &r) {
+    if constexpr (W == 4) { dg_uv4 t = { r.d[0], r.d[1], r.d[2], r.d[3] }; *(DG_GL dg_uv4 *)p = t; }
+    else if constexpr (W == 2) { dg_uv2 t = { r.d[0], r.d[1] }; *(DG_GL dg_uv2 *)p = t; }
+    else *(DG_GL dg_uv1 *)p = r.d[0];
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void cn_cell_float_kernel(const CNParams *Pp, CNTables Tb, const unsigned *lv0, const CNRec *plan, int planeFirst, int planesPerFrame) {
+    static_assert(W == 1 || W == 2 || W == 4, "cells of 16 bytes at most");
+    const CNParams &P = *Pp;
+    const int z = blockIdx.z, p = planeFirst + z % planesPerFrame, zo = z / planesPerFrame;
+    const int k = zo % P.nOut, f = zo / P.nOut;
+    const PlaneG &g = P.pl[p];
+    const int c = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
+    const int x0 = c * W;
+    if (x0 >= g.W || y >= g.H) return;
+    // uniform over the workgroup
+    const int field = P.single ? k : cn_field(P.tr, k);
+    const unsigned char *srcSup = Tb.src[(size_t)f * 3 + p];
+    const unsigned char *refSup = field >= 0 ? Tb.refs[((size_t)f * P.nFields + field) * 3 + p] : nullptr;
+    const bool usable = field >= 0 && lv0[f * P.nFields + field] != 0u;
+    unsigned char *drow = Tb.dst[((size_t)f * P.nOut + k) * 3 + p] + (long long)y * g.dstPitch + (long long)x0 * 4;
+    const long long inner = (long long)(g.vpadPel / P.pel + y) * g.supPitch + (long long)(g.hpadPel / P.pel + x0) * 4;
+    const bool covered = x0 < g.WB && y < g.HB; // (as in cn_cell_kernel: a cell that starts inside the covered width lies inside it)
+    const unsigned char *sp = nullptr; // where a cell that is a plain copy comes from
+    if (field < 0) sp = srcSup + inner;
+    else if (!usable) sp = ((!P.scBehavior && refSup) ? refSup : srcSup) + inner;
+    else if (!covered) sp = (P.scBehavior ? srcSup : refSup) + inner;
+    else if (!P.overlap) {
+        const int lbw = __ffs(g.blkW) - 1, lbh = __ffs(g.blkH) - 1;
+        const int bx = x0 >> lbw, by = y >> lbh, px = x0 & (g.blkW - 1), py = y & (g.blkH - 1);
+        const dg_iv4 R = *(DG_GL const dg_iv4 *)dg_gl(plan + ((size_t)f * P.nFields + field) * P.nBlk + by * P.nBlkX + bx);
+        sp = (R[2] ? refSup : srcSup) + (unsigned)R[p ? 1 : 0] + (long long)py * g.supPitch + (long long)px * 4;
+    }
+    if (sp) { // the bytes as they are: no float operation sees them
+        if (x0 + W <= g.W) cn_store_raw<W>(dg_glw(drow), dg_load_raw<float, W>(dg_gl(sp)));
+        else {
+#pragma unroll
+            for (int i = 0; i < W; i++) if (x0 + i < g.W) ((unsigned *)drow)[i] = ((const unsigned *)sp)[i];
+        }
+        return;
+    }
+    // overlapped blocks: the four slots of cn_cell_kernel, all loaded; one that does not exist repeats the first and is left out by a select
+    // (never added with weight 0: 0 * x is not 0 for the non-finite bytes that may lie behind a plane)
+    int bx0, bx1, by0, by1;
+    blk_cover(x0, g.blkW, g.stepX, P.nBlkX, bx0, bx1);
+    blk_cover(y, g.blkH, g.stepY, P.nBlkY, by0, by1);
+    DG_GL const unsigned char *pl = dg_gl(plan + ((size_t)f * P.nFields + field) * P.nBlk);
+    DG_GL const unsigned char *win = dg_gl(P.win[p]);
+    bool have[4];
+    dg_iv4 R[4];
+    int px[4], py[4], wsel[4];
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const int by = by0 + (s >> 1), bx = bx0 + (s & 1);
+        have[s] = by <= by1 && bx <= bx1;
+        const int byc = have[s] ? by : by0, bxc = have[s] ? bx : bx0;
+        R[s] = *(DG_GL const dg_iv4 *)(pl + (size_t)(byc * P.nBlkX + bxc) * sizeof(CNRec));
+        px[s] = x0 - bxc * g.stepX; py[s] = y - byc * g.stepY; // 0 <= px <= blkW - W
+        wsel[s] = (BLK_WIN_ROW(byc, P.nBlkY) + BLK_WIN_COL(bxc, P.nBlkX)) * g.blkW * g.blkH + py[s] * g.blkW + px[s];
+    }
+    DgRaw<float, W> val[4];
+    DgRaw<unsigned short, W> wv[4];
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const unsigned char *base = (R[s][2] ? refSup : srcSup) + (unsigned)R[s][p ? 1 : 0] + (long long)py[s] * g.supPitch + (long long)px[s] * 4;
+        val[s] = dg_load_raw<float, W>(dg_gl(base));
+        wv[s] = dg_load_raw<unsigned short, W>(win + (size_t)wsel[s] * 2);
+    }
+    DgRaw<float, W> out;
+#pragma unroll
+    for (int i = 0; i < W; i++) {
+        float acc = 0.0f;
+        int wsum = 0;
+#pragma unroll
+        for (int s = 0; s < 4; s++) { // slot order: (by0, bx0), (by0, bx1), (by1, bx0), (by1, bx1)
+            const int wi = dg_sample(wv[s], i);
+            const float t = acc + __uint_as_float(val[s].d[i]) * (float)wi;
+            acc = have[s] ? t : acc;
+            wsum += have[s] ? wi : 0;
+        }
+        out.d[i] = __float_as_uint(acc / (float)wsum);
+    }
+    cn_store_raw<W>(dg_glw(drow), out);
+}
+
 // ------------------------------------------------------------------------------------------------ host object
 
 struct mvx_compensate_n {
@@ -153,28 +245,41 @@ struct mvx_compensate_n {
     DevBuf<unsigned> dLv0;
     DevBuf<CNRec> dPlan;
     BlkWin win;
+    bool flt = false;                // float super clip, float output planes (cn_cell_float_kernel)
 };
 
-// MVCompensate.c:419-575 mvcompensateCreate under the name CompensateN
-extern "C" __attribute__((visibility("default"))) int mvx_compensate_n_create(const mvx_compensate_args *a, int tr, const mvx_analysis_data *ad, const mvx_super *sup,
-                                                                              const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_compensate_n **out, char *err) {
+// MVCompensate.c:419-575 mvcompensateCreate under the name CompensateN.  flt: the float entries (the super clip must be a float one; said after
+// the frame-size check); single: mvx_compensate_create_float's object -- one field, one output per job, no centre, under the name Compensate
+static int cn_create(const mvx_compensate_args *a, int tr, bool flt, bool single, const mvx_analysis_data *ad, const mvx_super *sup, const ptrdiff_t super_pitch[3],
+                     const ptrdiff_t dst_pitch[3], mvx_compensate_n **out, char *err) {
     MVX_CREATE_BEGIN(out);
-    MVX_REFUSE_FLOAT(sup, "CompensateN");
+    const char *name = single ? "Compensate" : "CompensateN";
+    if (!flt) MVX_REFUSE_FLOAT(sup, name);
     const mvx_super_info &si = sup->info;
-    const char *name = "CompensateN";
-    if (tr < 1 || tr > MVX_DEGRAIN_N_MAX_RADIUS) MVX_FAIL("%s: tr must be between 1 and %d.", name, MVX_DEGRAIN_N_MAX_RADIUS);
+    if (!single && (tr < 1 || tr > MVX_DEGRAIN_N_MAX_RADIUS)) MVX_FAIL("%s: tr must be between 1 and %d.", name, MVX_DEGRAIN_N_MAX_RADIUS);
     CompResolved r;
-    if (int rc = comp_resolve(name, a, ad, si, &r, err)) return rc;
-    if (r.fields) MVX_FAIL("%s: fields is not supported.", name);
+    if (int rc = comp_resolve(name, a, ad, si, &r, err, flt && !sup->is_float)) return rc;
+    if (r.fields) { if (single) MVX_FAIL("%s: fields is not supported on float clips.", name); MVX_FAIL("%s: fields is not supported.", name); }
     mvx_compensate_n *h;
     if (int rc = blk_new(&h, ad, si, nullptr, super_pitch, dst_pitch, err)) return rc;
     CNParams &P = h->P;
-    P.tr = tr; P.nFields = 2 * tr; P.nOut = 2 * tr + 1;
+    P.tr = single ? 0 : tr; P.nFields = single ? 1 : 2 * tr; P.nOut = single ? 1 : 2 * tr + 1;
+    P.single = single;
     P.thSAD = r.thSAD; P.time256 = r.time256; P.scBehavior = r.scBehavior;
     comp_apply(P, r, si);
     h->minStride = mvx_vectors_size(ad);
+    h->flt = flt;
     *out = h;
     return MVX_OK;
+}
+
+extern "C" __attribute__((visibility("default"))) int mvx_compensate_n_create(const mvx_compensate_args *a, int tr, const mvx_analysis_data *ad, const mvx_super *sup,
+                                                                              const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_compensate_n **out, char *err) {
+    return cn_create(a, tr, false, false, ad, sup, super_pitch, dst_pitch, out, err);
+}
+extern "C" __attribute__((visibility("default"))) int mvx_compensate_n_create_float(const mvx_compensate_args *a, int tr, const mvx_analysis_data *ad, const mvx_super *sup,
+                                                                                    const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_compensate_n **out, char *err) {
+    return cn_create(a, tr, true, false, ad, sup, super_pitch, dst_pitch, out, err);
 }
 
 extern "C" __attribute__((visibility("default"))) void mvx_compensate_n_destroy(mvx_compensate_n *c) { delete c; }
@@ -198,6 +303,8 @@ template <typename T> static void cn_launch_cells(int W, dim3 grid, hipStream_t 
 #undef CNC
 }
 
+static int cn_run(mvx_compensate_n *c, int njobs, const mvx_compensate_n_job *jobs, hipStream_t st);
+
 extern "C" __attribute__((visibility("default"))) int mvx_compensate_n_frames(mvx_compensate_n *c, int njobs, const mvx_compensate_n_job *jobs, void *stream) {
     if (njobs <= 0) return MVX_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -218,6 +325,13 @@ extern "C" __attribute__((visibility("default"))) int mvx_compensate_n_frames(mv
         for (size_t r = 0; r < nf; r++)
             if (int rc = fps_check_planes("mvx_compensate_n_frames", "reference super", J.refs[r], P.nplanes, 16, false)) return rc;
     }
+    return cn_run(c, njobs, jobs, st);
+}
+
+// the launches of a call whose jobs have been checked
+static int cn_run(mvx_compensate_n *c, int njobs, const mvx_compensate_n_job *jobs, hipStream_t st) {
+    const CNParams &P = c->P;
+    const size_t n = (size_t)njobs, nf = (size_t)P.nFields, no = (size_t)P.nOut;
     CallGuard::Scope scope(c->guard, st);
     int rc = blk_upload(c->dP, c->P, c->win);
     if (rc) return rc;
@@ -252,9 +366,51 @@ extern "C" __attribute__((visibility("default"))) int mvx_compensate_n_frames(mv
     for (int cls = 0; cls < (P.nplanes > 1 ? 2 : 1); cls++) { // one launch for the luma planes of all outputs of all jobs, one for both chroma planes
         const int p0 = cls, npl = cls ? 2 : 1, W = blk_cell_width(P.pl[p0], 16 / P.bps);
         const dim3 grid(((P.pl[p0].W + W - 1) / W + 31) / 32, (P.pl[p0].H + 7) / 8, njobs * P.nOut * npl);
-        if (P.bps == 1) cn_launch_cells<uint8_t>(W, grid, st, c->dP.p, T, c->dLv0.p, c->dPlan.p, p0, npl);
+        if (c->flt) {
+#define CNF(N) hipLaunchKernelGGL((cn_cell_float_kernel<N>), grid, dim3(256), 0, st, c->dP.p, T, c->dLv0.p, c->dPlan.p, p0, npl)
+            switch (W) { case 1: CNF(1); break; case 2: CNF(2); break; default: CNF(4); break; }
+#undef CNF
+        } else if (P.bps == 1) cn_launch_cells<uint8_t>(W, grid, st, c->dP.p, T, c->dLv0.p, c->dPlan.p, p0, npl);
         else cn_launch_cells<uint16_t>(W, grid, st, c->dP.p, T, c->dLv0.p, c->dPlan.p, p0, npl);
     }
     HIP_CHECK(hipGetLastError());
     return MVX_OK;
+}
+
+// ---- mvx_compensate_create_float: the single-field form of the float engine (mvx_degrain.hip holds mvx_compensate and forwards here).  One
+// field and one output per job, no centre: a job of mvx_compensate_frames becomes a job of cn_run with tables of one row each.
+int cn_single_create(const mvx_compensate_args *a, const mvx_analysis_data *ad, const mvx_super *sup, const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3],
+                     mvx_compensate_n **out, char *err) {
+    return cn_create(a, 0, true, true, ad, sup, super_pitch, dst_pitch, out, err);
+}
+void cn_single_destroy(mvx_compensate_n *c) { delete c; }
+
+int cn_single_frames(mvx_compensate_n *c, int nframes, const mvx_compensate_job *jobs, void *stream) {
+    if (nframes <= 0) return MVX_OK;
+    const CNParams &P = c->P;
+    if (nframes > 65535 / 2) { mvx_set_error("mvx_compensate_frames: at most %d jobs per call on float clips", 65535 / 2); return MVX_E_ARG; }
+    for (int f = 0; f < nframes; f++) {
+        if (jobs[f].field_shift) { mvx_set_error("mvx_compensate_frames: field_shift is not supported on float clips"); return MVX_E_ARG; }
+        if (!jobs[f].blob) { mvx_set_error("mvx_compensate_frames: a job needs its blob"); return MVX_E_ARG; }
+        if (int rc = fps_check_planes("mvx_compensate_frames", "source super", jobs[f].src_super, P.nplanes, 16, true)) return rc;
+        if (int rc = fps_check_planes("mvx_compensate_frames", "reference super", jobs[f].ref_super, P.nplanes, 16, false)) return rc;
+        if (int rc = fps_check_planes("mvx_compensate_frames", "dst", jobs[f].dst, P.nplanes, P.bps, true)) return rc;
+    }
+    typedef const void *cplanes[3];
+    typedef void *planes[3];
+    std::vector<mvx_compensate_n_job> nj((size_t)nframes);
+    std::vector<const void *> refs((size_t)nframes * 3);
+    std::vector<void *> dst((size_t)nframes * 3);
+    for (int f = 0; f < nframes; f++) {
+        for (int p = 0; p < 3; p++) {
+            nj[f].src_super[p] = jobs[f].src_super[p];
+            refs[(size_t)f * 3 + p] = jobs[f].ref_super[0] ? jobs[f].ref_super[p] : nullptr;
+            dst[(size_t)f * 3 + p] = jobs[f].dst[p];
+        }
+        nj[f].refs = (const cplanes *)(refs.data() + (size_t)f * 3);
+        nj[f].dst = (const planes *)(dst.data() + (size_t)f * 3);
+        nj[f].blob = jobs[f].blob;
+        nj[f].field_stride = ((size_t)c->minStride + 15) / 16 * 16;
+    }
+    return cn_run(c, nframes, nj.data(), (hipStream_t)stream);
 }

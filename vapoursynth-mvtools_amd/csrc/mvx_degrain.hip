@@ -562,7 +562,10 @@ struct DGCommon {
     BlkWin win;
 };
 struct mvx_degrain : DGCommon { int radius; };
-struct mvx_compensate : DGCommon {};
+struct mvx_compensate : DGCommon {
+    mvx_compensate_n *flt = nullptr; // mvx_compensate_create_float: the object of the float engine (mvx_compensate_n.hip) that does all the work
+    ~mvx_compensate() { if (flt) cn_single_destroy(flt); }
+};
 
 static int ensure_jobs(DGCommon *h, int nframes, size_t planBytesPerFrame) {
     const size_t n = (size_t)nframes, need = planBytesPerFrame * n;
@@ -716,9 +719,22 @@ extern "C" __attribute__((visibility("default"))) int mvx_compensate_create(cons
     return MVX_OK;
 }
 
+// Compensate on a float clip: host code over the float engine of CompensateN, one field and one output per job
+extern "C" __attribute__((visibility("default"))) int mvx_compensate_create_float(const mvx_compensate_args *a, const mvx_analysis_data *ad, const mvx_super *sup,
+                                     const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_compensate **out, char *err) {
+    MVX_CREATE_BEGIN(out);
+    mvx_compensate_n *n;
+    if (int rc = cn_single_create(a, ad, sup, super_pitch, dst_pitch, &n, err)) return rc;
+    mvx_compensate *h = new mvx_compensate();
+    h->flt = n;
+    *out = h;
+    return MVX_OK;
+}
+
 extern "C" __attribute__((visibility("default"))) void mvx_compensate_destroy(mvx_compensate *c) { delete c; }
 
 extern "C" __attribute__((visibility("default"))) int mvx_compensate_frames(mvx_compensate *c, int nframes, const mvx_compensate_job *jobs, void *stream) {
+    if (c->flt) return cn_single_frames(c->flt, nframes, jobs, stream);
     if (nframes <= 0) return MVX_OK;
     hipStream_t st = (hipStream_t)stream;
     const DGParams &P = c->P;

@@ -333,6 +333,7 @@ def lib():
         L.mvx_degrain_n_frames.argtypes = [C.c_void_p, C.c_int, P(DegrainNJob), C.c_void_p]
         L.mvx_compensate_create.argtypes = [P(CompensateArgs), P(AnalysisData), C.c_void_p, P(C.c_ssize_t), P(C.c_ssize_t),
                                             P(C.c_void_p), C.c_char_p]
+        L.mvx_compensate_create_float.argtypes = L.mvx_compensate_create.argtypes
         L.mvx_compensate_destroy.argtypes = [C.c_void_p]
         L.mvx_compensate_frames.argtypes = [C.c_void_p, C.c_int, P(CompensateJob), C.c_void_p]
         L.mvx_analyse_n_create.argtypes = [P(AnalyseArgs), C.c_int, C.c_void_p, C.c_int, P(C.c_ssize_t), P(C.c_void_p), C.c_char_p]
@@ -348,6 +349,7 @@ def lib():
         L.mvx_analyse_n_frames.argtypes = [C.c_void_p, C.c_int, P(AnalyseNJob), C.c_void_p]
         L.mvx_compensate_n_create.argtypes = [P(CompensateArgs), C.c_int, P(AnalysisData), C.c_void_p, P(C.c_ssize_t), P(C.c_ssize_t),
                                               P(C.c_void_p), C.c_char_p]
+        L.mvx_compensate_n_create_float.argtypes = L.mvx_compensate_n_create.argtypes
         L.mvx_compensate_n_destroy.argtypes = [C.c_void_p]
         L.mvx_compensate_n_map.argtypes = [C.c_void_p, C.c_int, P(C.c_int), P(C.c_int)]
         L.mvx_compensate_n_frames.argtypes = [C.c_void_p, C.c_int, P(CompensateNJob), C.c_void_p]
@@ -561,7 +563,7 @@ def plane_to_numpy(t, width, dtype):
 
 class Super(_Handle):
     """mv.Super -- MVSuper.c:140-275.  sample_float=True with bits=32: the super clip of a float32 clip (mvx_super_create_float) -- one level, no
-    shadow planes, planes of float32; only DegrainN consumes it."""
+    shadow planes, planes of float32; DegrainN, and Compensate / CompensateN with sample_float=True, consume it."""
     _destroy = "mvx_super_destroy"
 
     def __init__(self, width, height, bits=8, subsampling=(1, 1), gray=False, hpad=None, vpad=None, pel=None, levels=None,
@@ -992,19 +994,30 @@ class DegrainN(_Handle):
         return out
 
 
+def _out_plane(torch, rows, pitch, is_float, device):
+    """a zeroed output plane of `rows` rows of `pitch` bytes: bytes, or float32 samples for a float filter (whose pitches are multiples of 4)"""
+    if is_float:
+        return torch.zeros((rows, pitch // 4), dtype=torch.float32, device=device)
+    return torch.zeros((rows, pitch), dtype=torch.uint8, device=device)
+
+
 class Compensate(_Handle):
-    """mv.Compensate -- MVCompensate.c:419-575."""
+    """mv.Compensate -- MVCompensate.c:419-575.  sample_float=True selects mvx_compensate_create_float: a float super clip
+    (Super(..., bits=32, sample_float=True)), float32 output planes, vectors and thresholds from a search on an 8..16 bit copy; fields is refused.
+    The keyword is explicit: a float super clip without it is refused like by every filter that has no float path."""
     _destroy = "mvx_compensate_destroy"
 
-    def __init__(self, sup, analysis_data, dst_pitch=None, scbehavior=None, thsad=None, time=100.0, thscd1=None, thscd2=None, fields=None):
+    def __init__(self, sup, analysis_data, dst_pitch=None, scbehavior=None, thsad=None, time=100.0, thscd1=None, thscd2=None, fields=None, sample_float=False):
         self.sup = sup
+        self.is_float = bool(sample_float)
         a = CompensateArgs(_u(scbehavior), _u(thsad), float(time), _u(thscd1), _u(thscd2), _u(fields))
         ad = AnalysisData.from_buffer_copy(bytes(analysis_data))
         if dst_pitch is None:
             dst_pitch = _frame_pitch(sup)
         self.h = C.c_void_p()
         err = C.create_string_buffer(ERRLEN)
-        _check(lib().mvx_compensate_create(C.byref(a), C.byref(ad), sup.h, _pad3(sup.pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
+        create = lib().mvx_compensate_create_float if self.is_float else lib().mvx_compensate_create
+        _check(create(C.byref(a), C.byref(ad), sup.h, _pad3(sup.pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
         self.dst_pitch = list(dst_pitch)
 
     def run(self, jobs, out=None):
@@ -1015,7 +1028,7 @@ class Compensate(_Handle):
         hs = [i.height] + [i.height // i.yRatioUV] * 2
         if out is None:
             dev = jobs[0][0][0].device
-            out = [[torch.zeros((hs[p], self.dst_pitch[p]), dtype=torch.uint8, device=dev) for p in range(self.sup.nplanes)] for _ in range(n)]
+            out = [[_out_plane(torch, hs[p], self.dst_pitch[p], self.is_float, dev) for p in range(self.sup.nplanes)] for _ in range(n)]
         arr = (CompensateJob * n)()
         for k, job in enumerate(jobs):
             s, r, blob = job[:3]
@@ -1032,18 +1045,21 @@ class Compensate(_Handle):
 class CompensateN(_Handle):
     """The frames n - tr .. n + tr compensated onto frame n from frame n's multi blob (include/mvtools_amd.h, mv.CompensateN): 2 * tr + 1 frames
     per job in temporal order, each compensated one byte for byte what Compensate writes for that pair, the source in the middle.
-    analysis_data: of field 0 (AnalyseN.ad(0))."""
+    analysis_data: of field 0 (AnalyseN.ad(0)).  sample_float=True selects mvx_compensate_n_create_float, as in Compensate: float super clip,
+    float32 output planes, the multi blob of a search on an 8..16 bit copy."""
     _destroy = "mvx_compensate_n_destroy"
 
-    def __init__(self, tr, sup, analysis_data, dst_pitch=None, scbehavior=None, thsad=None, time=100.0, thscd1=None, thscd2=None, fields=None):
+    def __init__(self, tr, sup, analysis_data, dst_pitch=None, scbehavior=None, thsad=None, time=100.0, thscd1=None, thscd2=None, fields=None, sample_float=False):
         self.sup = sup
+        self.is_float = bool(sample_float)
         a = CompensateArgs(_u(scbehavior), _u(thsad), float(time), _u(thscd1), _u(thscd2), _u(fields))
         ad = AnalysisData.from_buffer_copy(bytes(analysis_data))
         if dst_pitch is None:
             dst_pitch = _frame_pitch(sup)
         self.h = C.c_void_p()
         err = C.create_string_buffer(ERRLEN)
-        _check(lib().mvx_compensate_n_create(C.byref(a), int(tr), C.byref(ad), sup.h, _pad3(sup.pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
+        create = lib().mvx_compensate_n_create_float if self.is_float else lib().mvx_compensate_n_create
+        _check(create(C.byref(a), int(tr), C.byref(ad), sup.h, _pad3(sup.pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
         self.tr = int(tr)
         self.dst_pitch = list(dst_pitch)
 
@@ -1062,7 +1078,7 @@ class CompensateN(_Handle):
         hs = [i.height] + [i.height // i.yRatioUV] * 2
         if out is None:
             dev = jobs[0][0][0].device
-            out = [[[torch.zeros((hs[p], self.dst_pitch[p]), dtype=torch.uint8, device=dev) for p in range(npl)] for _ in range(no)] for _ in range(n)]
+            out = [[[_out_plane(torch, hs[p], self.dst_pitch[p], self.is_float, dev) for p in range(npl)] for _ in range(no)] for _ in range(n)]
         arr = (CompensateNJob * n)()
         table = _ref_table([job[1] for job in jobs], nr, npl, "CompensateN")
         dst = ((C.c_void_p * 3) * (no * n))()
@@ -1073,7 +1089,7 @@ class CompensateN(_Handle):
             for p in range(npl):
                 arr[j].src_super[p] = s[p].data_ptr()
                 for k in range(no):
-                    assert out[j][k][p].stride(0) == self.dst_pitch[p]
+                    assert out[j][k][p].stride(0) * out[j][k][p].element_size() == self.dst_pitch[p]
                     dst[j * no + k][p] = out[j][k][p].data_ptr()
             arr[j].refs = C.cast(C.byref(table, j * nr * C.sizeof(C.c_void_p * 3)), C.POINTER(C.c_void_p * 3))
             arr[j].dst = C.cast(C.byref(dst, j * no * C.sizeof(C.c_void_p * 3)), C.POINTER(C.c_void_p * 3))
