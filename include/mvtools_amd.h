@@ -598,6 +598,41 @@ typedef struct mvx_blockfps_job {
 
 int mvx_blockfps_frames(mvx_blockfps *b, int nframes, const mvx_blockfps_job *jobs, void *stream);
 
+/* BlockFPS on a 32-bit float clip: the clip, the super clip (mvx_super_create_float) and the outputs are float32 planes; mvbw, mvfw and the
+ * blobs come from a search on ANY 8..16 bit clip of the same width, height, pel, padding and subsampling.  thscd1, thscd2 and ml are in the
+ * units of that search: which jobs are usable, the plan (the vectors scaled by the time position, divided by the subsampling ratio) and the
+ * occlusion / SAD masks -- 8-bit integers, SADs shifted by mvbw's bitsPerSample - 8, upsized with the reference's integer tables -- are
+ * exactly those of mvx_blockfps_create for the same blobs.  A sample, float32, nothing fused, every operation rounded on its own
+ * (csrc/mvx_blockfps_float_rule.h), with t = time256, ft = (float)t, fu = (float)(256 - t), K = 1 / 256, sVal / rVal the level-0 samples of
+ * the left / right super frame at the output position, b the fetch from the right super frame along the backward vector, fw the fetch from
+ * the left one along the forward vector, mF, mB, mO the upsized masks (0..255), med(a, b, c) = max(min(a, b), min(max(a, b), c)) and
+ * mix(m, p, q) = ((float)m * p + (float)(255 - m) * q) / 255, bb = mix(mB, fw, b), ff = mix(mF, b, fw):
+ *   mode 0                       (b * ft + fw * fu) * K
+ *   mode 1                       med(rVal, sVal, (b * ft + fw * fu) * K)
+ *   mode 2                       med((rVal * ft + sVal * fu) * K, b, fw)
+ *   mode 3, 6                    (bb * ft + ff * fu) * K
+ *   mode 4, 7                    mix(mO, (rVal * ft + sVal * fu) * K, (bb * ft + ff * fu) * K)
+ *   mode 5, 8                    (float)mO / 255 on every plane (the integer path writes mO << (bits - 8) to every plane too)
+ *   blocks side by side          (overlap 0) the value itself
+ *   overlapped blocks            acc = 0; over the covering blocks (by outer, bx inner, ascending) acc = acc + V * (float)win; out = acc /
+ *                                (float)wsum with wsum the integer sum of those same window weights, as in mvx_degrain_n_create_float: no
+ *                                >> 6 per term, no rounding term, no clamp, no 16-bit wrap
+ *   strips no block covers       (sVal * fu + rVal * ft) * K
+ *   job not usable               (time256 0 or 256, a scene change per thscd1 / thscd2, an invalid blob, a frame outside the clip) t <= 0, or
+ *                                t < 256 at blend 0: clip_left, a plain load and store, bit for bit (NaN payloads survive); t >= 256:
+ *                                clip_right likewise; otherwise (l * fu + r * ft) * K
+ * The mask mixes divide by 255, the weights' own sum, where the reference's (... + 255) >> 8 is 8-bit arithmetic.  Minimum and maximum are
+ * comparisons that return their second operand when neither is smaller / larger.  Inputs are assumed finite; samples may be negative or
+ * overshoot.  Messages are mvx_blockfps_create's in their order; after the frame-size check "BlockFPS: the float entry needs a float super
+ * clip."; then the library's own geometry and pitch checks.  mvx_blockfps_create itself keeps refusing a float super clip first of all.
+ * Touches no device.  mvx_blockfps_get_info, mvx_blockfps_map, mvx_blockfps_frames and mvx_blockfps_destroy serve the object.  Layouts:
+ * clip_left, clip_right and dst planes at any pitch that holds a row and any address, both multiples of 4; super planes with pitches and
+ * addresses that are multiples of 16; mvx_blockfps_frames refuses everything else before a launch. */
+int mvx_blockfps_create_float(const mvx_blockfps_args *args, const mvx_analysis_data *mvbw, const mvx_analysis_data *mvfw,
+                              const mvx_super *super_clip /* float */, int num_frames, int64_t fps_num, int64_t fps_den,
+                              const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3],
+                              mvx_blockfps **out, char *err);
+
 /* ---- mv.FlowInter / mv.FlowFPS -------------------------------------------------------------------
  * per-sample ("flow") interpolation between two frames; both filters share one handle type and one engine.
  * mvx_flowinter_create replaces mvflowinterCreate, MVFlowInter.c:473-678 (arg string :697-710);

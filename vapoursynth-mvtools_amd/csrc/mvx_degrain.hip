@@ -1061,6 +1061,163 @@ __global__ __launch_bounds__(256) void blockfps_rows_kernel(const DGParams *Pp, 
     dg_store<T, CW>(dg_glw(dptr), out);
 }
 
+#include "mvx_blockfps_float_rule.h"
+
+// ---- float clips (mvx_blockfps_create_float): one kernel of cn_cell_float_kernel's shape for every case.  A thread produces one row of a cell
+// of W float32 samples; W divides the block width and the block step, so the same <= 2 x 2 blocks cover all of a cell and each costs one
+// vector load per fetch.  The usable pass, the masks, the plan and the resize tables are those above (none of them touches a sample; the plan's
+// offsets are in bytes of 4 per sample because P.bps is 4).  The arithmetic is mvx_blockfps_float_rule.h; the copies of an unusable job move
+// bytes and never look at them.  Job, plane, geometry and tables are uniform over the workgroup and arrive through scalar loads.  The
+// motion-compensated fetches are 4-byte aligned and no more, as are the clip and the output planes.
+// n: the samples of the cell inside the plane (W or more: all of them); a cell cut by the plane's edge is read and written sample by sample
+template <int W> __device__ __forceinline__ DgRaw<float, W> bff_load(DG_GL const unsigned char *p, int n) {
+    if (n >= W) return dg_load_raw<float, W>(p);
+    DgRaw<float, W> r;
+#pragma unroll
+    for (int i = 0; i < W; i++) r.d[i] = i < n ? *(DG_GL const dg_uv1 *)(p + 4 * i) : 0u;
+    return r;
+}
+template <int W> __device__ __forceinline__ void bff_store(DG_GL unsigned char *p, const DgRaw<float, W> &r, int n) {
+    if (n >= W) {
+        if constexpr (W == 4) { dg_uv4 t = { r.d[0], r.d[1], r.d[2], r.d[3] }; *(DG_GL dg_uv4 *)p = t; }
+        else if constexpr (W == 2) { dg_uv2 t = { r.d[0], r.d[1] }; *(DG_GL dg_uv2 *)p = t; }
+        else *(DG_GL dg_uv1 *)p = r.d[0];
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < W; i++) if (i < n) *(DG_GL dg_uv1 *)(p + 4 * i) = r.d[i];
+}
+
+// MODE: 0..5, the arithmetic of the mode (6, 7 and 8 compute like 3, 4 and 5: they differ in how the masks are made).  A template argument so
+// that a mode keeps in registers only what it reads: 0..2 no mask, 3 F and B, 4 all three, 5 O alone and no fetch.  The masks of a sample
+// travel packed in one register: F | B << 8 | O << 16
+// The mask modes divide two or three times per sample, and an IEEE division is a dozen instructions with half a dozen values in flight.  Left
+// alone the scheduler interleaves the divisions of all W samples (109 and 112 VGPRs at W = 4 in modes 3 and 4, occupancy 4); a scheduling
+// barrier after each sample keeps one sample's temporaries live at a time
+#define BFF_ONE_AT_A_TIME() do { if constexpr (MODE == 3 || MODE == 4) __builtin_amdgcn_sched_barrier(0); } while (0)
+template <int W, int MODE>
+__global__ __launch_bounds__(256) void bf_cell_float_kernel(const DGParams *Pp, const BFParams *Bp, const BFJob *jobs, const int *usable, const BFPlan *plan, const unsigned char *masks,
+                                                            int planeFirst, int planesPerFrame) {
+    static_assert(W == 1 || W == 2 || W == 4, "cells of 16 bytes at most");
+    const DGParams &P = *Pp; const BFParams &B = *Bp;
+    const int z = blockIdx.z, f = z / planesPerFrame, p = planeFirst + z % planesPerFrame;
+    const PlaneG &g = P.pl[p];
+    const int x0 = (blockIdx.x * 32 + (threadIdx.x & 31)) * W, y = blockIdx.y * 8 + (threadIdx.x >> 5);
+    if (x0 >= g.W || y >= g.H) return;
+    const int n = g.W - x0;
+    const BFJob &J = jobs[f];
+    DG_GL unsigned char *dptr = dg_glw(J.dst[p]) + (long long)y * g.dstPitch + (long long)x0 * 4;
+    const int t = J.time256;
+    DgRaw<float, W> out;
+    if (!usable[f]) { // time256 0 / 256, vectors unusable or frames outside the clip: a copy, bit for bit, or the blend of the two clip frames
+        const long long co = (long long)y * B.clipPitch[p] + (long long)x0 * 4;
+        const bool left = t <= 0 || (t < 256 && !B.blend);
+        if (left || t >= 256) { bff_store<W>(dptr, bff_load<W>(dg_gl(left ? J.clipL[p] : J.clipR[p]) + co, n), n); return; }
+        const DgRaw<float, W> l = bff_load<W>(dg_gl(J.clipL[p]) + co, n), r = bff_load<W>(dg_gl(J.clipR[p]) + co, n);
+#pragma unroll
+        for (int i = 0; i < W; i++) out.d[i] = __float_as_uint(mvx_bff_time(__uint_as_float(r.d[i]), __uint_as_float(l.d[i]), t));
+        bff_store<W>(dptr, out, n);
+        return;
+    }
+    const long long inner = B.supInterior[p] + (long long)y * g.supPitch + (long long)x0 * 4;
+    const DgRaw<float, W> sVal = bff_load<W>(dg_gl(J.srcSup[p]) + inner, n), rVal = bff_load<W>(dg_gl(J.refSup[p]) + inner, n);
+    const int covW = P.overlap ? g.WB : g.blkW * P.nBlkX, covH = P.overlap ? g.HB : g.blkH * P.nBlkY;
+    if (x0 >= covW || y >= covH) { // the strips no block covers
+#pragma unroll
+        for (int i = 0; i < W; i++) out.d[i] = __float_as_uint(mvx_bff_time(__uint_as_float(rVal.d[i]), __uint_as_float(sVal.d[i]), t));
+        bff_store<W>(dptr, out, n);
+        return;
+    }
+    // from here on the cell lies inside the covered width (a multiple of W), so inside the plane
+    const int c = p ? 1 : 0;
+    unsigned mk[W];
+#pragma unroll
+    for (int i = 0; i < W; i++) mk[i] = 0u;
+    if constexpr (MODE >= 3) { // the upsizer of blockfps_rows_kernel: the integer tables, the masks stay bytes
+        DG_GL const unsigned char *m = dg_gl(masks + (size_t)f * 3 * B.XP * B.YP);
+        const int wb = *(DG_GL const int *)dg_gl(B.vW[c] + y), wt = 16384 - wb;
+        const int rowOff = *(DG_GL const int *)dg_gl(B.vOff[c] + y) * B.XP;
+        int hO[W], hWr[W];
+        dg_load_ints<W>(dg_gl(B.hOff[c] + x0), hO);
+        dg_load_ints<W>(dg_gl(B.hW[c] + x0), hWr);
+        const int o0 = hO[0];
+        auto vcol = [&](DG_GL const unsigned char *mm, int o) { return (int)(unsigned char)((mm[rowOff + o] * wt + mm[rowOff + B.XP + o] * wb + 8192) >> 14); };
+        auto upsize = [&](DG_GL const unsigned char *mm, int shift) {
+            // the bytes o0 .. o0 + 3 of the two mask rows as one unaligned dword each (the mask buffer has slack behind its last row)
+            const unsigned r0 = *(DG_GL const dg_uv1 *)(mm + rowOff + o0), r1 = *(DG_GL const dg_uv1 *)(mm + rowOff + B.XP + o0);
+            auto vc = [&](int k) { return (int)(unsigned char)((((r0 >> (8 * k)) & 0xffu) * wt + ((r1 >> (8 * k)) & 0xffu) * wb + 8192) >> 14); };
+            const int a0 = vc(0), a1 = vc(1), a2 = o0 + 2 < B.XP ? vc(2) : a1;
+#pragma unroll
+            for (int i = 0; i < W; i++) {
+                const int o = hO[i], wr = hWr[i], wl = 16384 - wr, k = o - o0;
+                int a, b;
+                if (k == 0) { a = a0; b = a1; } else if (k == 1) { a = a1; b = a2; } else { a = vcol(mm, o); b = vcol(mm, o + 1); }
+                mk[i] |= (unsigned)(unsigned char)((a * wl + b * wr + 8192) >> 14) << shift;
+            }
+        };
+        if constexpr (MODE != 5) { upsize(m, 0); upsize(m + B.XP * B.YP, 8); }
+        if constexpr (MODE >= 4) upsize(m + 2 * B.XP * B.YP, 16);
+    }
+    // one sample of a block from its two fetches
+    auto value = [&](int i, unsigned b, unsigned fw) {
+        return mvx_bff_value(MODE, t, __uint_as_float(sVal.d[i]), __uint_as_float(rVal.d[i]), __uint_as_float(b), __uint_as_float(fw), (int)(mk[i] & 0xffu),
+                             (int)((mk[i] >> 8) & 0xffu), (int)(mk[i] >> 16));
+    };
+    DG_GL const unsigned char *pl = dg_gl(plan + (size_t)f * P.nBlk);
+    DG_GL const unsigned char *refSup = dg_gl(J.refSup[p]), *srcSup = dg_gl(J.srcSup[p]);
+    if (!P.overlap) { // blocks side by side (their sizes are powers of two): the value itself
+        DgRaw<float, W> bv = sVal, fv = sVal; // (mode 5 reads neither)
+        if constexpr (MODE != 5) {
+            const int lbw = __ffs(g.blkW) - 1, lbh = __ffs(g.blkH) - 1;
+            const int bx = x0 >> lbw, by = y >> lbh, px = x0 & (g.blkW - 1), py = y & (g.blkH - 1);
+            const dg_iv4 R = *(DG_GL const dg_iv4 *)(pl + (size_t)(by * P.nBlkX + bx) * sizeof(BFPlan));
+            const long long bo = (long long)py * g.supPitch + (long long)px * 4;
+            bv = dg_load_raw<float, W>(refSup + (unsigned)R[c] + bo);
+            fv = dg_load_raw<float, W>(srcSup + (unsigned)R[2 + c] + bo);
+        }
+#pragma unroll
+        for (int i = 0; i < W; i++) { out.d[i] = __float_as_uint(value(i, bv.d[i], fv.d[i])); BFF_ONE_AT_A_TIME(); }
+        bff_store<W>(dptr, out, W);
+        return;
+    }
+    // overlapped blocks: the blocks bx0..bx1 x by0..by1 cover the cell, at most two each way, by outer and bx inner.  One block at a time: its
+    // two fetches and its window row are all that is live beside the cell's own state, which keeps the kernel at cn_cell_float_kernel's occupancy
+    int bx0, bx1, by0, by1;
+    blk_cover(x0, g.blkW, g.stepX, P.nBlkX, bx0, bx1);
+    blk_cover(y, g.blkH, g.stepY, P.nBlkY, by0, by1);
+    DG_GL const unsigned char *win = dg_gl(P.win[p]);
+    float acc[W];
+    int wsum[W];
+#pragma unroll
+    for (int i = 0; i < W; i++) { acc[i] = 0.0f; wsum[i] = 0; }
+#pragma unroll 1
+    for (int by = by0; by <= by1; by++) {
+        const int py = y - by * g.stepY, wrow = BLK_WIN_ROW(by, P.nBlkY);
+#pragma unroll 1
+        for (int bx = bx0; bx <= bx1; bx++) {
+            const int px = x0 - bx * g.stepX; // 0 <= px <= blkW - W
+            DgRaw<float, W> bv = sVal, fv = sVal; // (mode 5 reads neither)
+            if constexpr (MODE != 5) {
+                const dg_iv4 R = *(DG_GL const dg_iv4 *)(pl + (size_t)(by * P.nBlkX + bx) * sizeof(BFPlan));
+                const long long bo = (long long)py * g.supPitch + (long long)px * 4;
+                bv = dg_load_raw<float, W>(refSup + (unsigned)R[c] + bo);
+                fv = dg_load_raw<float, W>(srcSup + (unsigned)R[2 + c] + bo);
+            }
+            const DgRaw<unsigned short, W> wv = dg_load_raw<unsigned short, W>(win + (size_t)((wrow + BLK_WIN_COL(bx, P.nBlkX)) * g.blkW * g.blkH + py * g.blkW + px) * 2);
+#pragma unroll
+            for (int i = 0; i < W; i++) {
+                const int wi = dg_sample(wv, i);
+                acc[i] = mvx_bff_add(acc[i], value(i, bv.d[i], fv.d[i]), wi);
+                wsum[i] += wi;
+                BFF_ONE_AT_A_TIME();
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < W; i++) out.d[i] = __float_as_uint(mvx_bff_out(acc[i], wsum[i]));
+    bff_store<W>(dptr, out, W);
+}
+
 struct mvx_blockfps : DGCommon {
     BFParams B;
     DevBuf<BFParams> dB;
@@ -1069,13 +1226,15 @@ struct mvx_blockfps : DGCommon {
     DevBuf<unsigned char> dMasks;
     FpsRate rate;
     int delta;
+    bool flt = false;             // float super clip, float clip and output planes (bf_cell_float_kernel)
 };
 
-extern "C" __attribute__((visibility("default"))) int mvx_blockfps_create(const mvx_blockfps_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
+// MVBlockFPS.c:741-1014 mvblockfpsCreate.  flt: the float entry (the super clip must be a float one; said after the frame-size check)
+static int bf_create(bool flt, const mvx_blockfps_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
         const mvx_super *sup, int num_frames, int64_t fps_num, int64_t fps_den, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3],
         const ptrdiff_t dst_pitch[3], mvx_blockfps **out, char *err) {
     MVX_CREATE_BEGIN(out);
-    MVX_REFUSE_FLOAT(sup, "BlockFPS");
+    if (!flt) MVX_REFUSE_FLOAT(sup, "BlockFPS");
     const mvx_super_info &si = sup->info;
     const int mode = a->mode == MVX_UNSET ? 3 : a->mode;
     const int blend = a->blend == MVX_UNSET ? 1 : !!a->blend;
@@ -1091,9 +1250,14 @@ extern "C" __attribute__((visibility("default"))) int mvx_blockfps_create(const 
     if (int rc = mvx_pair_checks("BlockFPS", bw, fw, err)) return rc;
     if (fps_num == 0 || fps_den == 0) MVX_FAIL("BlockFPS: The input clip must have a frame rate. Invoke AssumeFPS if necessary.");
     if (!mvx_super_fits(bw, si, true)) MVX_FAIL("BlockFPS: wrong source or super clip frame size.");
+    if (flt && !sup->is_float) MVX_FAIL("BlockFPS: the float entry needs a float super clip.");
     mvx_blockfps *h;
     if (int rc = blk_new(&h, bw, si, clip_pitch, super_pitch, dst_pitch, err, "clip")) return rc;
     DGParams &P = h->P;
+    h->flt = flt;
+    // P.bps stays the sample size (4: pitches, the plan's offsets, supInterior).  P.bits is read by bf_mask_kernel alone on this path, as the
+    // depth of the SADs (sad >> (bits - 8)): that of the search, not the super clip's 32
+    if (flt) P.bits = bw->bitsPerSample;
     if (!(si.modeYUV & 6)) P.nplanes = 1;
     P.nRefs = 2; P.thscd1 = thscd1; P.thscd2 = thscd2;
     fps_rate_init(h->rate, a->num, a->den, fps_num, fps_den, num_frames);
@@ -1108,6 +1272,16 @@ extern "C" __attribute__((visibility("default"))) int mvx_blockfps_create(const 
     for (int p = 0; p < 3; p++) B.clipPitch[p] = clip_pitch[p < si.num_planes ? p : 0];
     *out = h;
     return MVX_OK;
+}
+extern "C" __attribute__((visibility("default"))) int mvx_blockfps_create(const mvx_blockfps_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
+        const mvx_super *sup, int num_frames, int64_t fps_num, int64_t fps_den, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3],
+        const ptrdiff_t dst_pitch[3], mvx_blockfps **out, char *err) {
+    return bf_create(false, a, bw, fw, sup, num_frames, fps_num, fps_den, super_pitch, clip_pitch, dst_pitch, out, err);
+}
+extern "C" __attribute__((visibility("default"))) int mvx_blockfps_create_float(const mvx_blockfps_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
+        const mvx_super *sup, int num_frames, int64_t fps_num, int64_t fps_den, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3],
+        const ptrdiff_t dst_pitch[3], mvx_blockfps **out, char *err) {
+    return bf_create(true, a, bw, fw, sup, num_frames, fps_num, fps_den, super_pitch, clip_pitch, dst_pitch, out, err);
 }
 extern "C" __attribute__((visibility("default"))) void mvx_blockfps_destroy(mvx_blockfps *b) { delete b; }
 extern "C" __attribute__((visibility("default"))) void mvx_blockfps_get_info(const mvx_blockfps *b, mvx_blockfps_info *info) {
@@ -1162,6 +1336,24 @@ extern "C" __attribute__((visibility("default"))) int mvx_blockfps_frames(mvx_bl
     }
     const BFPlan *plan = (const BFPlan *)b->dPlan.p;
     hipLaunchKernelGGL(bf_plan_kernel, dim3((P.nBlk + 255) / 256, nframes), dim3(256), 0, st, b->dP.p, b->dBJobs.p, b->dUsable.p, (BFPlan *)b->dPlan.p);
+    if (b->flt) { // one launch for the luma planes of all jobs, one for both chroma planes
+        // the widest cell at which the mode's kernel keeps occupancy 8: 16 bytes in modes 0, 5 and 8, 8 bytes in modes 1, 2, 3 and 6, one sample in
+        // modes 4 and 7 (profiles/blockfps_float_isa.txt)
+        const int m = B.mode < 6 ? B.mode : B.mode - 3, mw = m == 0 || m == 5 ? 4 : m == 4 ? 1 : 2;
+        for (int cls = 0; cls < (P.nplanes > 1 ? 2 : 1); cls++) {
+            const int p0 = cls, npl = cls ? 2 : 1, W = blk_cell_width(P.pl[p0], mw);
+            const dim3 grid(((P.pl[p0].W + W - 1) / W + 31) / 32, (P.pl[p0].H + 7) / 8, nframes * npl);
+#define BFF(N, M) hipLaunchKernelGGL((bf_cell_float_kernel<N, M>), grid, dim3(256), 0, st, b->dP.p, b->dB.p, b->dBJobs.p, b->dUsable.p, plan, b->dMasks.p, p0, npl)
+#define BFW(M) switch (W) { case 1: BFF(1, M); break; case 2: BFF(2, M); break; default: BFF(4, M); break; }
+#define BFN(M) switch (W) { case 1: BFF(1, M); break; default: BFF(2, M); break; }
+            switch (m) { case 0: BFW(0); break; case 1: BFN(1); break; case 2: BFN(2); break; case 3: BFN(3); break; case 4: BFF(1, 4); break; default: BFW(5); break; }
+#undef BFN
+#undef BFW
+#undef BFF
+        }
+        HIP_CHECK(hipGetLastError());
+        return MVX_OK;
+    }
     const int cwY = dg_rows_cw(P, 0, false), cwC = P.nplanes > 1 ? dg_rows_cw(P, 1, false) : 1;
     if (cwY && cwC && (P.nplanes == 1 || P.pl[1].W == P.pl[2].W)) {
         fps_classes(P.pl, P.nplanes, nframes, [&](int p) { return p ? cwC : cwY; }, [&](dim3 grid, int cw, int p0, int npl) {

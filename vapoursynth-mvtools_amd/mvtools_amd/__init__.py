@@ -375,6 +375,7 @@ def lib():
         L.mvx_scale_vect_frames.argtypes = [C.c_void_p, C.c_int, P(ScaleVectJob), C.c_void_p]
         L.mvx_blockfps_create.argtypes = [P(BlockFPSArgs), P(AnalysisData), P(AnalysisData), C.c_void_p, C.c_int, C.c_int64, C.c_int64, P(C.c_ssize_t),
                                           P(C.c_ssize_t), P(C.c_ssize_t), P(C.c_void_p), C.c_char_p]
+        L.mvx_blockfps_create_float.argtypes = L.mvx_blockfps_create.argtypes
         L.mvx_blockfps_destroy.argtypes = [C.c_void_p]
         L.mvx_blockfps_get_info.argtypes = [C.c_void_p, P(BlockFPSInfo)]
         L.mvx_blockfps_map.argtypes = [C.c_void_p, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int)]
@@ -563,7 +564,7 @@ def plane_to_numpy(t, width, dtype):
 
 class Super(_Handle):
     """mv.Super -- MVSuper.c:140-275.  sample_float=True with bits=32: the super clip of a float32 clip (mvx_super_create_float) -- one level, no
-    shadow planes, planes of float32; DegrainN, and Compensate / CompensateN with sample_float=True, consume it."""
+    shadow planes, planes of float32; DegrainN, and Compensate / CompensateN / BlockFPS with sample_float=True, consume it."""
     _destroy = "mvx_super_destroy"
 
     def __init__(self, width, height, bits=8, subsampling=(1, 1), gray=False, hpad=None, vpad=None, pel=None, levels=None,
@@ -1101,20 +1102,25 @@ class CompensateN(_Handle):
 
 class BlockFPS(_Handle):
     """mv.BlockFPS(clip, super, mvbw, mvfw, num, den, mode, ml, blend, thscd1, thscd2) -- MVBlockFPS.c:741-1014.
-    `fps_num / fps_den` is the input clip's frame rate; `clip_pitch` the row pitch of its device planes."""
+    `fps_num / fps_den` is the input clip's frame rate; `clip_pitch` the row pitch of its device planes.  sample_float=True selects
+    mvx_blockfps_create_float: a float super clip (Super(..., bits=32, sample_float=True)), float32 clip and output planes, vectors, thresholds
+    and ml from a search on an 8..16 bit copy.  The keyword is explicit: a float super clip without it is refused."""
     _destroy = "mvx_blockfps_destroy"
 
     def __init__(self, sup, ad_bw, ad_fw, num_frames, clip_pitch, fps_num=24, fps_den=1, num=None, den=None, mode=None, ml=100.0, blend=None, thscd1=None,
-                 thscd2=None, dst_pitch=None):
+                 thscd2=None, dst_pitch=None, sample_float=False):
         self.sup = sup
+        self.is_float = bool(sample_float)
         a = BlockFPSArgs(_u(num), _u(den), _u(mode), float(ml), _u(blend), _u(thscd1), _u(thscd2))
         bw = AnalysisData.from_buffer_copy(bytes(ad_bw))
         fw = AnalysisData.from_buffer_copy(bytes(ad_fw))
         self.h = C.c_void_p()
         self.pitch = list(clip_pitch)
         err = C.create_string_buffer(ERRLEN)
-        _check(lib().mvx_blockfps_create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, int(num_frames), int(fps_num), int(fps_den), _pad3(sup.pitch), _pad3(clip_pitch),
-                                         _pad3(dst_pitch or clip_pitch), C.byref(self.h), err), err)
+        create = lib().mvx_blockfps_create_float if self.is_float else lib().mvx_blockfps_create
+        self.dst_pitch = list(dst_pitch or clip_pitch)
+        _check(create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, int(num_frames), int(fps_num), int(fps_den), _pad3(sup.pitch), _pad3(clip_pitch),
+                      _pad3(self.dst_pitch), C.byref(self.h), err), err)
         self.in_frames = int(num_frames)
         info = BlockFPSInfo()
         lib().mvx_blockfps_get_info(self.h, C.byref(info))
@@ -1130,7 +1136,9 @@ class BlockFPS(_Handle):
         input frame device blobs of the two vector clips (mvbw at n, mvfw at n)."""
         torch = _torch()
         n = len(frames_out)
-        if out is None:
+        if out is None and self.is_float:
+            out = [[_out_plane(torch, clip[0][p].shape[0], self.dst_pitch[p], True, clip[0][0].device) for p in range(self.sup.nplanes)] for _ in range(n)]
+        elif out is None:
             out = arena_frames(n, [tuple(p.shape) for p in clip[0]], clip[0][0].device, zero=False)
         arr = (BlockFPSJob * n)()
         last = self.in_frames - 1
