@@ -1164,7 +1164,8 @@ int mvx_vectors_size(const mvx_analysis_data *ad);
  * through each of them.  Options: "general" = 1 keeps the default search out of its lean and speculative kernels; "cpw1" = 1
  * runs the general kernels one chain per workgroup; "spec" picks the default search's kernel (0 the lean serial one, 1 the
  * library's choice, 2 speculative with every block live, 3 speculative without runs, 5 speculative wherever it can run);
- * "team" = waves per chain of the speculative kernel's team form (0 never, 2..8 always, -1 the library's choice).  The
+ * "team" = waves per chain of the speculative kernel's team form (0 never, 2..8 always, -1 the library's choice);
+ * "scratch_poison" = 0 off, 1..255 the byte every fresh allocation of handle-owned device scratch is filled with (headroom included).  The
  * library never reads the environment; a production host never needs this call. */
 int mvx_debug_option(const char *name, int value);
 /* the last search launch of this process: out[0] = chains per SIMD of the default-search kernel (0: the general kernel ran), out[1] = chains

@@ -29,15 +29,18 @@ struct MvxDebug {
     int general = 0;   // 1: never use the lean kernel of the default search (mvx_analyse_fast.h)
     int cpw1 = 0;      // one chain per workgroup (general kernels)
     int spec = 1;      // default search: 1 = the speculative kernel (mvx_analyse_spec.h), 0 = the lean serial kernel (mvx_analyse_fast.h), 2 = the speculative kernel's code with speculation off (every block live), 3 = speculative without runs (every block's candidates loaded on their own), 5 = speculative for every shape it can run (by default only where its row passes apply)
+    int scratch_poison = 0; // 1..255: fill every fresh allocation of handle-owned scratch with this byte (mvx_common.h: mvx_poison_fresh)
     int team = -1;     // waves per chain of the speculative kernel's team form (mvx_analyse_spec.h: TEAM): 0 = never, 2..8 = always that many, -1 = the library's choice
 };
 static MvxDebug g_dbg;
 extern "C" __attribute__((visibility("default"))) int mvx_debug_option(const char *name, int value) {
-    struct { const char *n; int *p; } tab[] = { { "general", &g_dbg.general }, { "cpw1", &g_dbg.cpw1 }, { "spec", &g_dbg.spec }, { "team", &g_dbg.team } };
+    struct { const char *n; int *p; } tab[] = { { "general", &g_dbg.general }, { "cpw1", &g_dbg.cpw1 }, { "spec", &g_dbg.spec }, { "team", &g_dbg.team }, { "scratch_poison", &g_dbg.scratch_poison } };
+    if (!strcmp(name, "scratch_poison") && (value < 0 || value > 255)) { mvx_set_error("mvx_debug_option: scratch_poison is 0 (off) or a byte 1..255"); return MVX_E_ARG; }
     for (auto &t : tab) if (!strcmp(t.n, name)) { *t.p = value; return MVX_OK; }
     mvx_set_error("mvx_debug_option: unknown option %s", name);
     return MVX_E_ARG;
 }
+int mvx_scratch_poison(void) { return g_dbg.scratch_poison; }
 
 // what the last search launch of this process looked like (tests assert that a batch really took the build they mean to cover):
 // out[0] = chains per SIMD of the lean kernel (0: the general kernel ran), out[1] = chains per workgroup, out[2] = barrier interval in
@@ -345,6 +348,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_frames(mvx_ana
         if (S.d) (void)hipFree(S.d);
         S.cap = (size_t)njobs * 2;
         HIP_CHECK(hipMalloc((void **)&S.d, S.cap * sizeof(AJob)));
+        HIP_CHECK(mvx_poison_fresh(S.d, S.cap * sizeof(AJob)));
     }
     std::vector<AJob> hj(njobs);
     for (int i = 0; i < njobs; i++) {
@@ -684,6 +688,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_recalculate_frames(mvx
         if (r->dJobs) (void)hipFree(r->dJobs);
         r->jobsCap = (size_t)njobs * 2;
         HIP_CHECK(hipMalloc((void **)&r->dJobs, r->jobsCap * sizeof(AJob)));
+        HIP_CHECK(mvx_poison_fresh(r->dJobs, r->jobsCap * sizeof(AJob)));
     }
     std::vector<AJob> hj(njobs);
     for (int i = 0; i < njobs; i++) {

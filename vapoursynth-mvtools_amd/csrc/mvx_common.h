@@ -30,6 +30,18 @@ void mvx_divided_data(const mvx_analysis_data *in, mvx_analysis_data *out);
 #define MVX_CREATE_BEGIN(out) MVX_ERR_BEGIN(); *(out) = nullptr
 #define MVX_FAIL(...) do { snprintf(err, MVX_ERRLEN, __VA_ARGS__); mvx_set_error("%s", err); return MVX_E_ARG; } while (0)
 
+// ---- test option scratch_poison (mvx_debug_option; defined in mvx_analyse.hip): 0 = off, 1..255 = the byte that every FRESH allocation
+// of handle-owned scratch is filled with over its whole capacity, headroom included, before anyone uses it.  A kernel that reads a record
+// this call did not write then reads that byte instead of the zeros a new allocation usually holds.  Changes no result.
+int mvx_scratch_poison(void);
+// after every hipMalloc of scratch: on the null stream and waited for, as mvx_dev_alloc does (the callers' streams may be non-blocking)
+static inline hipError_t mvx_poison_fresh(void *p, size_t bytes) {
+    const int v = mvx_scratch_poison();
+    if (!v || !p || !bytes) return hipSuccess;
+    const hipError_t e = hipMemset(p, v, bytes);
+    return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
+}
+
 // ---- device scratch that a handle owns: count elements of T, freed with the handle.  reserve() leaves a buffer that is large enough
 // alone; one that is too small is freed FIRST (hipFree synchronises the device: no earlier kernel still reads it) and replaced by one of
 // count + headroom elements.  On failure p == nullptr and cap == 0, so the next call starts over.
@@ -45,8 +57,9 @@ template <typename T> struct DevBuf {
         if (count <= cap) return hipSuccess;
         release();
         const hipError_t e = hipMalloc((void **)&p, (count + headroom) * sizeof(T));
-        if (e == hipSuccess) cap = count + headroom; else p = nullptr;
-        return e;
+        if (e != hipSuccess) { p = nullptr; return e; }
+        cap = count + headroom;
+        return mvx_poison_fresh(p, cap * sizeof(T));
     }
 };
 

@@ -462,6 +462,7 @@ static int upload_ptrs(int which, const void *const *host, size_t n, hipStream_t
         if (s.d) (void)hipFree(s.d);
         s.cap = bytes < 4096 ? 4096 : bytes * 2;
         HIP_CHECK(hipMalloc(&s.d, s.cap));
+        HIP_CHECK(mvx_poison_fresh(s.d, s.cap));
         s.dev = dev;
     }
     HIP_CHECK(hipMemcpyAsync(s.d, host, bytes, hipMemcpyHostToDevice, st));
