@@ -375,6 +375,9 @@ typedef struct mvx_compensate_job {
     int32_t reserved;
 } mvx_compensate_job;
 
+/* At most 32767 jobs per call ("mvx_compensate_frames: at most 32767 jobs per call", for a float object with " on float clips" behind it as
+ * before; MVX_E_ARG, before a job is looked at): a launch holds
+ * (job, chroma plane) in one grid dimension of 65535.  A job whose ref_super[0] is NULL needs no blob. */
 int mvx_compensate_frames(mvx_compensate *c, int nframes, const mvx_compensate_job *jobs, void *stream);
 
 /* Compensate on a 32-bit float clip, for ONE vector clip of any isb and delta: the single-field form of mvx_compensate_n_create_float (below),
@@ -382,8 +385,8 @@ int mvx_compensate_frames(mvx_compensate *c, int nframes, const mvx_compensate_j
  * output is bit for bit output k of mvx_compensate_n_frames for the same (source, reference, field).  Messages are mvx_compensate_create's in
  * their order, after the frame-size check "Compensate: the float entry needs a float super clip."; fields = 1 is refused last with
  * "Compensate: fields is not supported on float clips.".  Touches no device.  mvx_compensate_frames and mvx_compensate_destroy serve the
- * object; for it mvx_compensate_frames refuses a job whose field_shift is not 0 ("mvx_compensate_frames: field_shift is not supported on
- * float clips"), a job without a blob, and more than 32767 jobs per call. */
+ * object; for it mvx_compensate_frames also refuses a job whose field_shift is not 0 ("mvx_compensate_frames: field_shift is not supported
+ * on float clips") and a job without a blob. */
 int mvx_compensate_create_float(const mvx_compensate_args *args, const mvx_analysis_data *vectors_data,
                                 const mvx_super *super_clip /* float */, const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3],
                                 mvx_compensate **out, char *err);
@@ -451,7 +454,8 @@ typedef struct mvx_compensate_n_job {
 /* Output k != tr is byte for byte what mvx_compensate_frames writes for (src_super, refs[field], blob + field * field_stride) with the same
  * scbehavior, thsad, time, thscd1 and thscd2 -- a reference outside the clip and a scene change per scbehavior included.  Output tr is the
  * source: the unpadded pel-0 window of the finest level of src_super, copied.  One usable pass and one plan pass over all fields of all
- * jobs, then one output kernel per plane class whose grid covers the 2 * tr + 1 planes of every job (csrc/mvx_compensate_n.hip). */
+ * jobs, then one output kernel per plane class whose grid covers the 2 * tr + 1 planes of every job (csrc/mvx_compensate.hip, the engine
+ * of mvx_compensate_frames too). */
 int mvx_compensate_n_frames(mvx_compensate_n *c, int njobs, const mvx_compensate_n_job *jobs, void *stream);
 
 /* CompensateN on a 32-bit float clip: the super clip (mvx_super_create_float) and the outputs are float32 planes; vectors_data and the multi

@@ -341,6 +341,21 @@ def test_plane_addresses_are_checked_before_anything_is_launched(mv):
     refused(lambda: L.mvx_compensate_frames(c8.h, 1, cj, None), "mvx_compensate_frames: dst plane 0 is required")
 
 
+def test_compensate_frames_limits_the_jobs_of_a_call_before_it_looks_at_one(mv):
+    """The output kernel's grid holds (job, chroma plane) in z, 65535 at most: an integer handle refuses 32768 jobs with MVX_E_ARG before it
+    looks at any of them (these are all zero: no plane, no blob) or at a device; a call of no jobs is a no-op"""
+    L = mv.lib()
+    sup, bw, _ = _clips(mv)
+    comp = mv.Compensate(sup, bw, PITCH)
+    many = (mv.CompensateJob * 32768)()
+    assert L.mvx_compensate_frames(comp.h, 32768, many, None) == -1
+    assert L.mvx_last_error().decode() == "mvx_compensate_frames: at most 32767 jobs per call"
+    assert L.mvx_compensate_frames(comp.h, 32767, many, None) == -1  # inside the limit the jobs are looked at
+    assert L.mvx_last_error().decode() == "mvx_compensate_frames: source super plane 0 is required"
+    assert L.mvx_compensate_frames(comp.h, 0, many, None) == 0
+    assert L.mvx_compensate_frames(comp.h, 0, None, None) == 0
+
+
 def test_finest_layouts_are_checked_before_anything_is_launched(mv):
     """mvx_finest_frames: pitches that hold a row, planes that are there, all multiples of the sample size; U and V may differ"""
     L = mv.lib()

@@ -497,10 +497,10 @@ COMP_CASES = [
     # w, h, bits, analyse kwargs, compensate kwargs
     (206, 118, 8, dict(blksize=8, overlap=4), {}),                 # overlapped: the gather
     (206, 118, 16, dict(blksize=16, overlap=8), {}),
-    (208, 120, 8, dict(blksize=8, overlap=0), {}),                 # side by side: the rows kernel
+    (208, 120, 8, dict(blksize=8, overlap=0), {}),                 # side by side: cells that are plain copies
     (208, 120, 16, dict(blksize=16, overlap=0), {}),
     (208, 120, 8, dict(blksize=4, overlap=0), {}),                 # the smallest segment: chroma blocks of 2
-    (206, 118, 8, dict(blksize=8, overlap=0), {}),                 # segments of 2 and an uncovered strip: dg_rows_cw's `covered` term
+    (206, 118, 8, dict(blksize=8, overlap=0), {}),                 # chroma cells of 2 and an uncovered strip: a cell that starts inside the covered width must lie inside it
     (206, 118, 8, dict(blksize=8, overlap=0), dict(thscd1=20, thscd2=10)),                 # a scene change, scbehavior 1
     (206, 118, 8, dict(blksize=8, overlap=0), dict(thscd1=20, thscd2=10, scbehavior=0)),
     (206, 118, 16, dict(blksize=8, overlap=4), dict(time=40.0)),

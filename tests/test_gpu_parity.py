@@ -463,6 +463,55 @@ def test_fields_shift_parity(oracle, mv, w, h, bits, pel, akw, shift):
     assert not all(np.array_equal(a, b) for a, b in zip(want, oc.frame(osf[0], osf[1], ob)))
 
 
+class _NoBlob:
+    """what Compensate.run takes for the blob of a job that has none"""
+    data_ptr = staticmethod(lambda: None)
+
+
+@pytest.mark.parametrize("scbehavior", [0, 1])
+@pytest.mark.parametrize("w,h,bits,akw", [
+    (206, 118, 8, dict(blksize=8, overlap=0)),    # chroma cells of 2, strips no block covers
+    (72, 56, 16, dict(blksize=16, overlap=8)),    # 8 x 6 blocks: four covering blocks, first / middle / last windows both ways
+])
+def test_unlike_jobs_in_one_compensate_call(oracle, mv, w, h, bits, akw, scbehavior):
+    """One mvx_compensate_frames call whose jobs differ in everything that is per-job table data of the engine: field shifts +pel/2, 0 and
+    -pel/2 (on SADs around thsad, so that blocks read from the reference and from the source both meet the shift), a reference outside the
+    clip (and then no blob), and a blob over the scene-change count.  Every output is the oracle's, and the output of the job in a call of
+    its own."""
+    import torch
+    import vector_fields as vf
+    pel = 2
+    frames, osup, gsup, osf, gsrc, gsf = _pipeline(oracle, mv, w, h, bits, 1, dict(pel=pel), akw, nframes=3, seed=31)
+    gan = mv.Analyse(gsup, isb=1, fields=1, **akw)
+    pairs = [(0, 1), (1, 2), (2, 0)]
+    found = [b.cpu().numpy() for b in gan.run([(gsf[s], gsf[r]) for s, r in pairs])]
+    ckw = dict(thsad=200, scbehavior=scbehavior)  # (a thsad below thscd1: SADs around it leave the scene-change count alone)
+    thsad, nscd1, nscd2 = vf.scaled_thresholds(gan.ad, ckw["thsad"])
+    edges = [vf.sad_edges(b, gan.ad, 7 + i, thsad) for i, b in enumerate(found)]
+    scene = vf.scene_count(found[0], gan.ad, 11, nscd1, nscd2 + 1, thsad)
+    # (source, reference or None, blob or None, field shift)
+    jobs = [(0, 1, edges[0], pel // 2), (1, 2, edges[1], 0), (2, 0, edges[2], -(pel // 2)), (1, None, None, pel // 2), (0, 1, scene, -(pel // 2))]
+    oc = oracle.Compensate(osup, gan.ad, **ckw)
+    gc = mv.Compensate(gsup, gan.ad, fields=1, **ckw)
+    dev = gsf[0][0].device
+    gjobs = [(gsf[s], gsf[r] if r is not None else None, torch.from_numpy(b).to(dev) if b is not None else _NoBlob, shift) for s, r, b, shift in jobs]
+    got = gc.run(gjobs)
+    alone = [gc.run([j])[0] for j in gjobs]
+    torch.cuda.synchronize()
+    for k, (s, r, b, shift) in enumerate(jobs):
+        want = oc.frame(osf[s], osf[r] if r is not None else None, b if b is not None else found[0], field_shift=shift)
+        for p in range(3):
+            g = mv.plane_to_numpy(got[k][p], want[p].shape[1], want[p].dtype)
+            assert np.array_equal(g, want[p]), "job %d plane %d differs from the oracle (%d samples)" % (k, p, int((g != want[p]).sum()))
+            assert torch.equal(got[k][p], alone[k][p]), "job %d plane %d differs from the job run alone" % (k, p)
+    # the shifts reach the output, through blocks of both kinds
+    for k in (0, 2):
+        s, r, b, shift = jobs[k]
+        _, sad = vf.records(b, gan.ad)
+        assert (sad < thsad).any() and (sad >= thsad).any()
+        assert not all(np.array_equal(x, y) for x, y in zip(oc.frame(osf[s], osf[r], b, field_shift=shift), oc.frame(osf[s], osf[r], b)))
+
+
 @pytest.mark.parametrize("bits,akw", [(8, dict(blksize=8, overlap=4)), (16, dict(blksize=16, overlap=8)), (16, dict(blksize=32, overlap=16))])
 def test_analyse_one_chain_per_workgroup(oracle, mv, dbg, bits, akw):
     """MVX_CPW=1 keeps the one-chain-per-workgroup builds of the specialised kernels reachable (A/B timing uses them): same vectors"""

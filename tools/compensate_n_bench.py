@@ -4,6 +4,7 @@ input resident: super frames, the multi blob and the output frames.
 
     python tools/compensate_n_bench.py [--trs 3,8] [--repeats 3] [--seconds S] [--jobs N] [--overlap 8]
     python tools/compensate_n_bench.py --float [--trs 3] [--repeats 3] [--seconds S] [--jobs N]
+    python tools/compensate_n_bench.py --single [--repeats 3] [--seconds S] [--jobs 8,256] [--shapes 8:8:0,8:16:8,16:16:8]
 
 Workload: 1920 x 1080 8-bit 4:2:0, blocks of 16 overlapping by 8 (--overlap 0: side by side), pel 2, defaults otherwise.  The clip has 2 * tr + 1 frames
 moving by one sample per frame; the job is the middle frame against all the others, with the vectors AnalyseN finds.  A call takes --jobs copies of that
@@ -16,7 +17,12 @@ its repeats.  Reported: ms per job (2 * tr + 1 frames).
 16-bit clip; the float clip is that clip scaled to 0..1): 1920 x 1080 4:2:0, pel 2, blocks 16/8 and 16/0, the lines timed in turn as above.  Reported
 per line: ms per job and the rate of the algorithm's bytes -- every output sample written once and one sample read for it, 2 * (2 * tr + 1) frames of
 1.5 * 1920 * 1080 samples of 2 or 4 bytes per job (overlapped blocks read up to four samples and window weights per output sample: those extra
-reads are the implementation's, not the algorithm's, and are not counted)."""
+reads are the implementation's, not the algorithm's, and are not counted).
+
+--single: mvx_compensate_frames by itself -- no CompensateN line, no copy of the source -- at 1920 x 1080 4:2:0, pel 2: 8-bit blocks 8/0, 8-bit 16/8 and
+16-bit 16/8, each at every --jobs count (at 256 jobs the outputs of a call exceed the last-level cache).  A job is the middle frame of three against
+the frame after it or, every other job, the frame before it, with the vectors Analyse finds; every job writes its own output frame.  Reported: ms per
+job (one frame), --repeats times; to compare two builds of the library run one process per build (MVX_LIB selects the library) in turn."""
 import argparse
 import ctypes as C
 import os
@@ -119,16 +125,53 @@ def main_float(a):
                 "the float path's byte rate is LOWER by more than the spread" if gbs[1] / gbs[0] < 1 - rel else "the float path's byte rate is not lower by more than the spread"), flush=True)
 
 
+def main_single(a):
+    import torch
+    L = mv.lib()
+    for bits, blk, overlap in [tuple(int(v) for v in t.split(":")) for t in a.shapes.split(",")]:
+        sup = mv.Super(W, H, bits)
+        sf = sup.build([mv.frame_to_device(f) for f in pl.moving_clip(W, H, bits, 3, seed=5, motion=(1, 0))])
+        blobs, ad = [], None
+        for isb, ref in ((1, 2), (0, 0)):
+            an = mv.Analyse(sup, isb=isb, blksize=blk, overlap=overlap)
+            blobs.append(an.run([(sf[1], sf[ref])])[0])
+            ad = an.ad
+        refs = [sf[2], sf[0]]
+        comp = mv.Compensate(sup, ad)
+        i = sup.info
+        hs = [i.height] + [i.height // i.yRatioUV] * 2
+        for jobs in [int(j) for j in a.jobs.split(",")]:
+            outs = [[torch.zeros((hs[p], comp.dst_pitch[p]), dtype=torch.uint8, device="cuda") for p in range(3)] for _ in range(jobs)]
+            arr = (mv.CompensateJob * jobs)()
+            for j in range(jobs):
+                for p in range(3):
+                    arr[j].src_super[p], arr[j].ref_super[p], arr[j].dst[p] = sf[1][p].data_ptr(), refs[j & 1][p].data_ptr(), outs[j][p].data_ptr()
+                arr[j].blob = blobs[j & 1].data_ptr()
+
+            def run():
+                if L.mvx_compensate_frames(comp.h, jobs, arr, stream()):
+                    raise SystemExit(L.mvx_last_error().decode())
+            ms = [timed(run, a.seconds) / jobs for _ in range(a.repeats)]
+            print("single  %2d-bit blocks %2d/%d (%d x %d)  %3d jobs per call  ms per job  %s  min %.4f  spread %.4f" % (
+                bits, blk, overlap, ad.nBlkX, ad.nBlkY, jobs, "  ".join("%.4f" % v for v in ms), min(ms), max(ms) - min(ms)), flush=True)
+            del outs, arr
+
+
 def main():
     import torch
     ap = argparse.ArgumentParser()
+    ap.add_argument("--single", action="store_true", help="mvx_compensate_frames by itself (see the head of this file)")
+    ap.add_argument("--shapes", default="8:8:0,8:16:8,16:16:8", help="--single: bits:blksize:overlap of every shape")
     ap.add_argument("--float", dest="flt", action="store_true", help="the float CompensateN beside the 16-bit one (see the head of this file)")
     ap.add_argument("--trs", default="3,8")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--seconds", type=float, default=0.5)
-    ap.add_argument("--jobs", type=int, default=8, help="jobs (source frames) per call")
+    ap.add_argument("--jobs", default="8", help="jobs (source frames) per call; --single: a list, e.g. 8,256")
     ap.add_argument("--overlap", type=int, default=8)
     a = ap.parse_args()
+    if a.single:
+        return main_single(a)
+    a.jobs = int(a.jobs)
     if a.flt:
         if a.trs == "3,8":
             a.trs = "3"

@@ -115,8 +115,8 @@ def main():
         r = res.get(k, {})
         c = mix(body)
         print(k)
-        print("   VGPRs %s  AGPRs %s  spillV %s  spillS %s  scratch %s  occupancy %s  LDS %s" % (
-            r.get("VGPRs"), r.get("AGPRs"), r.get("VGPRs Spill"), r.get("SGPRs Spill"), r.get("ScratchSize"), r.get("Occupancy"), r.get("LDS Size")))
+        print("   VGPRs %s  AGPRs %s  SGPRs %s  spillV %s  spillS %s  scratch %s  occupancy %s  LDS %s" % (
+            r.get("VGPRs"), r.get("AGPRs"), r.get("TotalSGPRs"), r.get("VGPRs Spill"), r.get("SGPRs Spill"), r.get("ScratchSize"), r.get("Occupancy"), r.get("LDS Size")))
         print("   static instr: total %d  %s" % (sum(c.values()), "  ".join("%s %d" % kv for kv in sorted(c.items()))))
     if not keep:
         os.unlink(out)

@@ -1,4 +1,4 @@
-// mvx_block_shared.h -- what the block filters share (mvx_degrain.hip: Degrain, Compensate, BlockFPS; mvx_degrain_n.hip; mvx_compensate_n.hip).
+// mvx_block_shared.h -- what the block filters share (mvx_degrain.hip: Degrain, BlockFPS; mvx_degrain_n.hip; mvx_compensate.hip: Compensate, CompensateN).
 // All five read level-0 vectors, turn every block into an offset into a super plane, gather the up to 2 x 2 overlapped blocks that cover a
 // cell, weigh them with the overlap windows and store.  Device side: which blocks cover a sample or a cell and which of the nine windows a
 // block takes, and fgopIsUsable with the level-0 offset as its result (the N filters).  Host side: the geometry that opens every parameter
@@ -174,13 +174,6 @@ static int comp_resolve(const char *name, const mvx_compensate_args *a, const mv
     r->time256 = (int)(time * 256 / 100); // :560
     return MVX_OK;
 }
-// mvx_compensate_create_float's object is a single-field object of the float engine in mvx_compensate_n.hip; mvx_compensate (mvx_degrain.hip)
-// holds it and forwards mvx_compensate_frames and mvx_compensate_destroy
-struct mvx_compensate_n;
-int cn_single_create(const mvx_compensate_args *a, const mvx_analysis_data *ad, const mvx_super *sup, const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3],
-                     mvx_compensate_n **out, char *err);
-int cn_single_frames(mvx_compensate_n *c, int nframes, const mvx_compensate_job *jobs, void *stream);
-void cn_single_destroy(mvx_compensate_n *c);
 // ... into a geometry that blk_fill has filled
 static void comp_apply(BlkGeom &G, const CompResolved &r, const mvx_super_info &si) {
     G.thscd1 = r.thscd1; G.thscd2 = r.thscd2;

@@ -1,6 +1,6 @@
-// mvx_degrain.hip -- the block filters on gfx950: mv.Degrain1..6 and mv.Compensate (first half), mv.BlockFPS and mv.SCDetection (second half,
-// each under its own heading).  What they share with DegrainN and CompensateN is in mvx_block_shared.h, what they share with the flow filters
-// and mv.Mask in mvx_fps_shared.h.
+// mvx_degrain.hip -- the block filters on gfx950: mv.Degrain1..6 (first half), mv.BlockFPS and mv.SCDetection (second half, each under its own
+// heading).  What they share with DegrainN, Compensate and CompensateN (mvx_degrain_n.hip, mvx_compensate.hip) is in mvx_block_shared.h, what
+// they share with the flow filters and mv.Mask in mvx_fps_shared.h.
 //
 // The reference walks blocks, blends each block into a temp (Degrain_C, MVDegrains.h:30-53), scatters it times a
 // raised-cosine window into a 16/32-bit accumulator (overlaps_c, Overlap.cpp:143-158) and finally normalises
@@ -70,8 +70,6 @@ extern "C" __attribute__((visibility("default"))) void mvx_scale_thscd(int64_t *
 struct DGParams : BlkGeom {
     int nRefs;
     long long thSAD[2];
-    // compensate only
-    long long cthSAD; int time256, scBehavior;
 };
 
 struct DGJob {
@@ -79,7 +77,6 @@ struct DGJob {
     const unsigned char *refs[12][3];
     const unsigned char *blobs[12];
     unsigned char *dst[3];
-    int fieldShift;          // compensate only (MVCompensate.c:188-225)
 };
 
 // plan record: one per (frame, plane class luma/chroma, block), sized for the filter's 2 * radius references (Degrain3: 40 bytes; a fixed
@@ -439,117 +436,6 @@ __global__ __launch_bounds__(256, (dg_cell_waves<NR, W>())) void degrain_cell_ke
     }
 }
 
-// ---- compensate
-
-struct CPlanRec { unsigned off[2]; int fromRef; }; // off[0] luma, off[1] chroma
-
-__global__ __launch_bounds__(256) void compensate_plan_kernel(const DGParams *Pp, const DGJob *jobs, const int *usable, CPlanRec *plan) {
-    const DGParams &P = *Pp;
-    const int f = blockIdx.y;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= P.nBlk || !usable[f * 12]) return;
-    const int by = i / P.nBlkX, bx = i - by * P.nBlkX;
-    const GVecD *v = mvx_level0(jobs[f].blobs[0], P.nLvCount);
-    const GVecD b = v[i];
-    int blx, bly;
-    CPlanRec rec;
-    if (b.sad < P.cthSAD) { // MVCompensate.c:238-242,286-290
-        blx = bx * P.pl[0].stepX * P.pel + b.x * P.time256 / 256;
-        bly = by * P.pl[0].stepY * P.pel + b.y * P.time256 / 256 + jobs[f].fieldShift;
-        rec.fromRef = 1;
-    } else { // :243-247,291-295 (no-overlap: stepX == blkW)
-        blx = bx * P.pl[0].stepX * P.pel;
-        bly = by * P.pl[0].stepY * P.pel + jobs[f].fieldShift;
-        rec.fromRef = 0;
-    }
-    rec.off[0] = sup_offset(P.pl[0], P.pel, P.logPel, P.bps, blx, bly);
-    rec.off[1] = P.nplanes > 1 ? sup_offset(P.pl[1], P.pel, P.logPel, P.bps, blx >> P.pl[1].subX, bly >> P.pl[1].subY) : 0;
-    plan[(size_t)f * P.nBlk + i] = rec;
-}
-
-// job layout for compensate: src[] = super frame n, refs[0][] = super frame nref (may be null), blobs[0], dst[]
-template <typename T>
-__global__ __launch_bounds__(256) void compensate_kernel(const DGParams *Pp, const DGJob *jobs, const int *usable, const CPlanRec *plan) {
-    const DGParams &P = *Pp;
-    const int z = blockIdx.z, f = z / 3, p = z % 3;
-    if (p >= P.nplanes) return;
-    const PlaneG &g = P.pl[p];
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= g.W || y >= g.H) return;
-    const DGJob &J = jobs[f];
-    T *drow = (T *)(J.dst[p] + (long long)y * g.dstPitch);
-    const unsigned char *srcSup = J.src[p], *refSup = J.refs[0][p];
-    // interior (pel plane 0) sample of a super frame
-    const long long inner = (long long)(g.vpadPel / P.pel + y) * g.supPitch + (long long)(g.hpadPel / P.pel + x) * (long long)sizeof(T);
-    if (!usable[f * 12]) { // MVCompensate.c:348-364
-        const unsigned char *s = (!P.scBehavior && refSup) ? refSup : srcSup;
-        drow[x] = *(const T *)(s + inner);
-        return;
-    }
-    if (x >= g.WB || y >= g.HB) { // :319-342
-        const unsigned char *s = P.scBehavior ? srcSup : refSup;
-        drow[x] = *(const T *)(s + inner);
-        return;
-    }
-    const CPlanRec *pl = plan + (size_t)f * P.nBlk;
-    const int c = p ? 1 : 0;
-    if (!P.overlap) {
-        const int bx = x / g.blkW, by = y / g.blkH;
-        const int px = x - bx * g.blkW, py = y - by * g.blkH;
-        const CPlanRec R = pl[by * P.nBlkX + bx];
-        drow[x] = ((const T *)((R.fromRef ? refSup : srcSup) + R.off[c] + (long long)py * g.supPitch))[px];
-        return;
-    }
-    int bx0, bx1, by0, by1;
-    blk_cover(x, g.blkW, g.stepX, P.nBlkX, bx0, bx1);
-    blk_cover(y, g.blkH, g.stepY, P.nBlkY, by0, by1);
-    unsigned acc = 0;
-    const int16_t *win = P.win[p];
-    for (int by = by0; by <= by1; by++) {
-        const int py = y - by * g.stepY;
-        const int wby = BLK_WIN_ROW(by, P.nBlkY);
-        for (int bx = bx0; bx <= bx1; bx++) {
-            const int px = x - bx * g.stepX;
-            const int wbx = BLK_WIN_COL(bx, P.nBlkX);
-            const CPlanRec R = pl[by * P.nBlkX + bx];
-            const int val = ((const T *)((R.fromRef ? refSup : srcSup) + R.off[c] + (long long)py * g.supPitch))[px];
-            acc += (unsigned)((val * (int)win[(wby + wbx) * g.blkW * g.blkH + py * g.blkW + px]) >> 6);
-        }
-    }
-    if (sizeof(T) == 1) acc &= 0xffffu;
-    const int a = (int)((acc + 16) >> 5);
-    const int pm = (1 << P.bits) - 1;
-    drow[x] = (T)(a > pm ? pm : a);
-}
-
-
-// ---- blocks without overlap (MVCompensate.c:227-258,286-306: plain block copies): one thread per CW consecutive samples of one
-// block row -- one vector load from the chosen super frame, one vector store.  CW divides the block width, the covered width and
-// the frame width (the host checks), so a segment is never split between cases; block sizes are powers of two.
-template <typename T, int CW>
-__global__ __launch_bounds__(256) void compensate_rows_kernel(const DGParams *Pp, const DGJob *jobs, const int *usable, const CPlanRec *plan, int planeFirst, int planesPerFrame) {
-    const DGParams &P = *Pp;
-    const int z = blockIdx.z, f = z / planesPerFrame, p = planeFirst + z % planesPerFrame;
-    const PlaneG &g = P.pl[p];
-    const int x = (blockIdx.x * 64 + (threadIdx.x & 63)) * CW, y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= g.W || y >= g.H) return;
-    const DGJob &J = jobs[f];
-    const unsigned char *srcSup = J.src[p], *refSup = J.refs[0][p];
-    const long long inner = (long long)(g.vpadPel / P.pel + y) * g.supPitch + (long long)(g.hpadPel / P.pel + x) * (long long)sizeof(T);
-    const unsigned char *sp;
-    if (!usable[f * 12]) sp = ((!P.scBehavior && refSup) ? refSup : srcSup) + inner;            // MVCompensate.c:348-364
-    else if (x >= g.WB || y >= g.HB) sp = (P.scBehavior ? srcSup : refSup) + inner;             // :319-342
-    else {
-        const int lbw = __ffs(g.blkW) - 1, lbh = __ffs(g.blkH) - 1;
-        const int bx = x >> lbw, by = y >> lbh, px = x & (g.blkW - 1), py = y & (g.blkH - 1);
-        const CPlanRec R = plan[(size_t)f * P.nBlk + by * P.nBlkX + bx];
-        sp = (R.fromRef ? refSup : srcSup) + R.off[p ? 1 : 0] + (long long)py * g.supPitch + (long long)px * (long long)sizeof(T);
-    }
-    int v[CW];
-    dg_load<T, CW>(dg_gl(sp), v);
-    dg_store<T, CW>(dg_glw(J.dst[p] + (long long)y * g.dstPitch + (long long)x * (long long)sizeof(T)), v);
-}
-
 // ------------------------------------------------------------------------------------------------ host objects
 
 struct DGCommon {
@@ -562,10 +448,6 @@ struct DGCommon {
     BlkWin win;
 };
 struct mvx_degrain : DGCommon { int radius; };
-struct mvx_compensate : DGCommon {
-    mvx_compensate_n *flt = nullptr; // mvx_compensate_create_float: the object of the float engine (mvx_compensate_n.hip) that does all the work
-    ~mvx_compensate() { if (flt) cn_single_destroy(flt); }
-};
 
 static int ensure_jobs(DGCommon *h, int nframes, size_t planBytesPerFrame) {
     const size_t n = (size_t)nframes, need = planBytesPerFrame * n;
@@ -575,14 +457,13 @@ static int ensure_jobs(DGCommon *h, int nframes, size_t planBytesPerFrame) {
     return MVX_OK;
 }
 
-// samples per thread of the row kernels of Compensate and BlockFPS: up to 16 bytes, dividing the block width and the frame width, so that a
-// segment is never split between cases (`covered`: and the covered width, where Compensate's uncovered strip starts; BlockFPS's starts at
-// nBlkX * blkW).  0: the blocks overlap or are not powers of two -- the per-sample gather
-static int dg_rows_cw(const DGParams &P, int p, bool covered) {
+// samples per thread of BlockFPS's row kernel: up to 16 bytes, dividing the block width and the frame width, so that a segment is never split
+// between cases (the uncovered strip starts at nBlkX * blkW).  0: the blocks overlap or are not powers of two -- the per-sample gather
+static int dg_rows_cw(const DGParams &P, int p) {
     if (P.overlap) return 0;
     const PlaneG &g = P.pl[p];
     int cw = 16 / P.bps;
-    while (cw > 1 && (g.blkW % cw || g.W % cw || (covered && g.WB % cw))) cw >>= 1;
+    while (cw > 1 && (g.blkW % cw || g.W % cw)) cw >>= 1;
     return (cw >= 2 && (g.blkW & (g.blkW - 1)) == 0 && (g.blkH & (g.blkH - 1)) == 0) ? cw : 0;
 }
 
@@ -696,84 +577,6 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_frames(mvx_deg
         dim3 grid((P.pl[0].W + 63) / 64, (P.pl[0].H + 3) / 4, nframes * 3);
         if (P.bps == 1) launch_degrain<uint8_t>(P.nRefs, grid, st, d->dP.p, d->dJobs.p, d->dPlan.p);
         else launch_degrain<uint16_t>(P.nRefs, grid, st, d->dP.p, d->dJobs.p, d->dPlan.p);
-    }
-    HIP_CHECK(hipGetLastError());
-    return MVX_OK;
-}
-
-// MVCompensate.c:419-575 mvcompensateCreate
-extern "C" __attribute__((visibility("default"))) int mvx_compensate_create(const mvx_compensate_args *a, const mvx_analysis_data *ad, const mvx_super *sup,
-                                     const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_compensate **out, char *err) {
-    MVX_CREATE_BEGIN(out);
-    MVX_REFUSE_FLOAT(sup, "Compensate");
-    const mvx_super_info &si = sup->info;
-    CompResolved r;
-    if (int rc = comp_resolve("Compensate", a, ad, si, &r, err)) return rc;
-    mvx_compensate *h;
-    if (int rc = blk_new(&h, ad, si, nullptr, super_pitch, dst_pitch, err)) return rc;
-    DGParams &P = h->P;
-    P.nRefs = 1;
-    P.cthSAD = r.thSAD; P.time256 = r.time256; P.scBehavior = r.scBehavior;
-    comp_apply(P, r, si);
-    *out = h;
-    return MVX_OK;
-}
-
-// Compensate on a float clip: host code over the float engine of CompensateN, one field and one output per job
-extern "C" __attribute__((visibility("default"))) int mvx_compensate_create_float(const mvx_compensate_args *a, const mvx_analysis_data *ad, const mvx_super *sup,
-                                     const ptrdiff_t super_pitch[3], const ptrdiff_t dst_pitch[3], mvx_compensate **out, char *err) {
-    MVX_CREATE_BEGIN(out);
-    mvx_compensate_n *n;
-    if (int rc = cn_single_create(a, ad, sup, super_pitch, dst_pitch, &n, err)) return rc;
-    mvx_compensate *h = new mvx_compensate();
-    h->flt = n;
-    *out = h;
-    return MVX_OK;
-}
-
-extern "C" __attribute__((visibility("default"))) void mvx_compensate_destroy(mvx_compensate *c) { delete c; }
-
-extern "C" __attribute__((visibility("default"))) int mvx_compensate_frames(mvx_compensate *c, int nframes, const mvx_compensate_job *jobs, void *stream) {
-    if (c->flt) return cn_single_frames(c->flt, nframes, jobs, stream);
-    if (nframes <= 0) return MVX_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const DGParams &P = c->P;
-    for (int f = 0; f < nframes; f++) {
-        if (int rc = fps_check_planes("mvx_compensate_frames", "source super", jobs[f].src_super, P.nplanes, 16, true)) return rc;
-        if (int rc = fps_check_planes("mvx_compensate_frames", "reference super", jobs[f].ref_super, P.nplanes, 16, false)) return rc;
-        if (int rc = fps_check_planes("mvx_compensate_frames", "dst", jobs[f].dst, P.nplanes, P.bps, true)) return rc;
-    }
-    CallGuard::Scope scope(c->guard, st);
-    int rc = blk_upload(c->dP, c->P, c->win);
-    if (rc) return rc;
-    if ((rc = ensure_jobs(c, nframes, sizeof(CPlanRec) * (size_t)P.nBlk))) return rc;
-    std::vector<DGJob> hj(nframes);
-    for (int f = 0; f < nframes; f++) {
-        memset(&hj[f], 0, sizeof(DGJob));
-        for (int p = 0; p < 3; p++) {
-            hj[f].src[p] = (const unsigned char *)jobs[f].src_super[p];
-            hj[f].refs[0][p] = (const unsigned char *)jobs[f].ref_super[p];
-            hj[f].dst[p] = (unsigned char *)jobs[f].dst[p];
-        }
-        hj[f].blobs[0] = (const unsigned char *)jobs[f].blob;
-        hj[f].fieldShift = jobs[f].field_shift;
-    }
-    HIP_CHECK(hipMemcpyAsync(c->dJobs.p, hj.data(), sizeof(DGJob) * nframes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(usable_kernel, dim3(1, nframes), dim3(256), 0, st, c->dP.p, c->dJobs.p, c->dUsable.p);
-    const CPlanRec *plan = (const CPlanRec *)c->dPlan.p;
-    hipLaunchKernelGGL(compensate_plan_kernel, dim3((P.nBlk + 255) / 256, nframes), dim3(256), 0, st, c->dP.p, c->dJobs.p, c->dUsable.p, (CPlanRec *)c->dPlan.p);
-    // blocks without overlap: the vectorised row kernel (one launch per plane class); otherwise the per-sample gather
-    const int cwY = dg_rows_cw(P, 0, true), cwC = P.nplanes > 1 ? dg_rows_cw(P, 1, true) : 1;
-    if (cwY && cwC && (P.nplanes == 1 || P.pl[1].W == P.pl[2].W)) {
-        fps_classes(P.pl, P.nplanes, nframes, [&](int p) { return p ? cwC : cwY; }, [&](dim3 grid, int cw, int p0, int npl) {
-            fps_dispatch<2>(P.bps, cw, [&](auto t, auto w) {
-                hipLaunchKernelGGL((compensate_rows_kernel<typename decltype(t)::type, decltype(w)::value>), grid, dim3(256), 0, st, c->dP.p, c->dJobs.p, c->dUsable.p, plan, p0, npl);
-            });
-        });
-    } else {
-        dim3 grid((P.pl[0].W + 63) / 64, (P.pl[0].H + 3) / 4, nframes * 3);
-        if (P.bps == 1) hipLaunchKernelGGL(compensate_kernel<uint8_t>, grid, dim3(256), 0, st, c->dP.p, c->dJobs.p, c->dUsable.p, plan);
-        else hipLaunchKernelGGL(compensate_kernel<uint16_t>, grid, dim3(256), 0, st, c->dP.p, c->dJobs.p, c->dUsable.p, plan);
     }
     HIP_CHECK(hipGetLastError());
     return MVX_OK;
@@ -958,7 +761,7 @@ __global__ __launch_bounds__(256) void blockfps_kernel(const DGParams *Pp, const
 }
 
 
-// ---- blocks without overlap: one thread per CW consecutive samples of one block row (same conditions as compensate_rows_kernel).
+// ---- blocks without overlap: one thread per CW consecutive samples of one block row (the host checks dg_rows_cw's conditions).
 // The four vector loads (left / right frame at the sample, the two motion-compensated fetches) and the plan record are per segment;
 // the mask upsizer (SimpleResize.cpp:62-121) interpolates vertically once per mask column the segment touches.
 template <typename T, int CW>
@@ -1063,7 +866,7 @@ __global__ __launch_bounds__(256) void blockfps_rows_kernel(const DGParams *Pp, 
 
 #include "mvx_blockfps_float_rule.h"
 
-// ---- float clips (mvx_blockfps_create_float): one kernel of cn_cell_float_kernel's shape for every case.  A thread produces one row of a cell
+// ---- float clips (mvx_blockfps_create_float): one kernel of cn_cell_kernel<float, W>'s shape for every case.  A thread produces one row of a cell
 // of W float32 samples; W divides the block width and the block step, so the same <= 2 x 2 blocks cover all of a cell and each costs one
 // vector load per fetch.  The usable pass, the masks, the plan and the resize tables are those above (none of them touches a sample; the plan's
 // offsets are in bytes of 4 per sample because P.bps is 4).  The arithmetic is mvx_blockfps_float_rule.h; the copies of an unusable job move
@@ -1181,7 +984,7 @@ __global__ __launch_bounds__(256) void bf_cell_float_kernel(const DGParams *Pp, 
         return;
     }
     // overlapped blocks: the blocks bx0..bx1 x by0..by1 cover the cell, at most two each way, by outer and bx inner.  One block at a time: its
-    // two fetches and its window row are all that is live beside the cell's own state, which keeps the kernel at cn_cell_float_kernel's occupancy
+    // two fetches and its window row are all that is live beside the cell's own state, which keeps the kernel at cn_cell_kernel<float, W>'s occupancy
     int bx0, bx1, by0, by1;
     blk_cover(x0, g.blkW, g.stepX, P.nBlkX, bx0, bx1);
     blk_cover(y, g.blkH, g.stepY, P.nBlkY, by0, by1);
@@ -1354,7 +1157,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_blockfps_frames(mvx_bl
         HIP_CHECK(hipGetLastError());
         return MVX_OK;
     }
-    const int cwY = dg_rows_cw(P, 0, false), cwC = P.nplanes > 1 ? dg_rows_cw(P, 1, false) : 1;
+    const int cwY = dg_rows_cw(P, 0), cwC = P.nplanes > 1 ? dg_rows_cw(P, 1) : 1;
     if (cwY && cwC && (P.nplanes == 1 || P.pl[1].W == P.pl[2].W)) {
         fps_classes(P.pl, P.nplanes, nframes, [&](int p) { return p ? cwC : cwY; }, [&](dim3 grid, int cw, int p0, int npl) {
             fps_dispatch<2>(P.bps, cw, [&](auto t, auto w) {
