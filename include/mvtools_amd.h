@@ -18,7 +18,7 @@
  * Plane layouts (checked: *_create refuses a pitch, *_frames an address, with MVX_E_ARG and before anything is uploaded or launched)
  *   - Clip-side planes -- src / clip / dst of mvx_degrain, mvx_degrain_n in all its three entries, mvx_compensate and mvx_compensate_n with
  *     their float entries,
- *     mvx_blockfps, mvx_flowinter / mvx_flowfps, mvx_flowcomp and mvx_flowblur: any pitch that holds a row of its plane and is a multiple of
+ *     mvx_blockfps, mvx_flowinter / mvx_flowfps, mvx_flowcomp and mvx_flowblur, the last two with their float entries: any pitch that holds a row of its plane and is a multiple of
  *     the sample size (1, 2, or 4 bytes for a float clip; out16 writes 2-byte samples), and any plane address that is a multiple of the
  *     sample size.  A tight pitch, an odd pitch for 8-bit samples, a plane inside a wider frame, U and V of different pitch, src and dst of
  *     different pitch are all legal.  A shorter pitch, a pitch or address that is no multiple of the sample size, and a missing plane where
@@ -103,8 +103,9 @@ void mvx_super_get_info(const mvx_super *s, mvx_super_info *info);
  *   sharp 1   ((s(X) + s(X+1)) * 9.0f - (s(X-1) + s(X+2))) * 0.0625f
  *   sharp 2   m2 = (m2 + m3) * 4; m2 -= (m1 + m4); m2 *= 5; m0 = (m0 + m5) + m2; m0 * 0.03125f
  *   the diagonal plane of sharp 1 and 2 is the horizontal rule on the UNROUNDED vertical plane; pel 4: (a + b) * 0.5f
- * (csrc/mvx_super_float_rule.h).  Samples are assumed finite.  Only the float entries -- mvx_degrain_n_create_float, mvx_compensate_create_float and
- * mvx_compensate_n_create_float -- consume such an object: mvx_super_shadow_copies
+ * (csrc/mvx_super_float_rule.h).  Samples are assumed finite.  Only the float entries -- mvx_degrain_n_create_float, mvx_compensate_create_float,
+ * mvx_compensate_n_create_float, mvx_blockfps_create_float, mvx_flowcomp_create_float and mvx_flowblur_create_float -- consume such an object
+ * (FlowInter and FlowFPS have no float entry): mvx_super_shadow_copies
  * returns 0, the shadow, pelclip and Finest entries return MVX_E_ARG, and every other *_create that takes an mvx_super refuses it before any
  * other check with "<Name>: float super clips are not supported.".  Touches no device. */
 int mvx_super_create_float(const mvx_super_args *args, mvx_super **out, char *err);
@@ -760,6 +761,38 @@ typedef struct mvx_flowblur_job {
 
 /* nframes jobs in one batch on `stream`: two small per-job kernels, then one launch for the luma planes and one for both chroma planes */
 int mvx_flowblur_frames(mvx_flowblur *h, int nframes, const mvx_flowblur_job *jobs, void *stream);
+
+/* Flow and FlowBlur on a 32-bit float clip: the clip, the super clip (mvx_super_create_float) and the outputs are float32 planes; the vector
+ * clips and the blobs come from a search on ANY 8..16 bit clip of the same width, height, pel, padding and subsampling, and thscd1 / thscd2
+ * are in the units of that search.  The reference has no float path; the arithmetic is the library's own.  Everything on the vector side is
+ * the integer filter's, value for value, for the same blobs: which jobs are usable, the int16 cells, field_shift, the upsized vx / vy with
+ * the resizer's limits, time256, blur256, prec, the tap count m and the tap positions.  Only how a sample is fetched, carried and averaged
+ * differs, with s(X, Y) the float super sample at pel position (X, Y) (the super frame read as the Finest frame) and lp = log2(pel):
+ *   Flow mode 0 (fetch)          out(x, y) = s((x << lp) + ((vx * time256 + 128) >> 8), (y << lp) + ((vy * time256 + 128) >> 8)), the 32 bits
+ *                                copied as they are: no arithmetic at all
+ *   Flow mode 1 (shift)          source sample s(x << lp, y << lp) goes to the integer filter's destination, and the last writer in raster
+ *                                order wins as there: an atomic maximum of the key ((raster index + 1) << 32) | bits of the sample (the
+ *                                index fits 32 bits: a legal plane has fewer than 2^32 samples).  The winner's bits are stored as they are;
+ *                                where no source landed, the top of the plane's nominal range -- 1.0f on luma, 0.5f on chroma (centred on
+ *                                0, as in mvx_super_create_float) -- stands where the integer filter writes pixel_max
+ *   FlowBlur                     sum = s(X, Y); for the F taps, then the B taps, in the integer kernel's order: sum = sum + tap, float32,
+ *                                each addition rounded on its own; out = sum / (float)(mF + mB + 1): one division, no reciprocal, nothing
+ *                                fused, no clamp.  mF + mB == 0 gives the sample itself bit for bit (x / 1.0f)
+ *   job not usable               (a scene change per thscd1 / thscd2, an invalid blob, a NULL super frame or blob) the clip frame, a plain
+ *                                load and store, bit for bit: NaN payloads survive
+ * Messages are mvx_flowcomp_create's / mvx_flowblur_create's in their order; after the frame-size check "Flow: the float entry needs a float
+ * super clip." / "FlowBlur: the float entry needs a float super clip."; then the library's own geometry and pitch checks; fields = 1 is
+ * refused last with "Flow: fields is not supported on float clips.".  mvx_flowcomp_create and mvx_flowblur_create themselves keep refusing a
+ * float super clip first of all.  Touch no device.  mvx_flowcomp_frames / _ref / _destroy and mvx_flowblur_frames / _destroy serve the
+ * objects; the job structs are the same.  Layouts: clip and dst planes at any pitch that holds a row and any address, both multiples of 4;
+ * super planes with pitches and addresses that are multiples of 16; *_frames refuses everything else before a launch.  Samples are moved in
+ * segments of 4, 2 or 1 (the widest that divides the plane width).  Not registered in the VapourSynth shell. */
+int mvx_flowcomp_create_float(const mvx_flowcomp_args *args, const mvx_analysis_data *vectors, const mvx_super *super_clip /* float */,
+                              int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3],
+                              mvx_flowcomp **out, char *err);
+int mvx_flowblur_create_float(const mvx_flowblur_args *args, const mvx_analysis_data *mvbw, const mvx_analysis_data *mvfw,
+                              const mvx_super *super_clip /* float */, int num_frames, const ptrdiff_t super_pitch[3],
+                              const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flowblur **out, char *err);
 
 /* ---- mv.Mask --------------------------------------------------------------------------------------
  * motion, SAD and occlusion masks from one vector clip, as an 8-bit three-plane clip.

@@ -2,6 +2,7 @@
 the super frames and vector blobs resident.
 
     python tools/flow_bench.py [--frames N] [--warmup W] [--only 1080p8|4k16] [--filters flowfps,fetch,shift,blur]
+    python tools/flow_bench.py --float [--frames N] [--repeats R] [--filters fetch,shift,blur]
 
 Workloads at 1080p 8-bit and 4K 16-bit 4:2:0: FlowFPS 2x and 24 -> 60, mask=2; Flow fetch and Flow shift at time 100; FlowBlur at blur 50,
 prec 1.  Per workload: output fps, ms per output frame, algorithmic bytes per output frame and frac = those bytes per second over 8.0 TB/s.
@@ -9,6 +10,11 @@ FlowFPS: 3 x the output frame (its write plus one read of each of the two input 
 plus one read of the frame they sample).  FlowBlur also reports its mean taps per sample (F + B, all planes).  Flow shift launches at most 64
 jobs at once (its winner buffer takes 8 bytes per sample and job).  Kernel times come from a separate rocprofv3 --kernel-trace --stats run
 of this script.
+
+--float: Flow fetch, Flow shift and FlowBlur (blur 50) at 1080p 4:2:0, pel 2, blocks 16/8, on a 16-bit clip and on its float clip
+(sample_float=True) with the SAME vectors, searched once on the 16-bit clip.  The two paths alternate R times in one process; per path the
+median, the fastest and the slowest ms per frame, the spread (slowest - fastest) / median, and the algorithm's bytes per second at the median
+(2 x the output frame: 2-byte samples against 4-byte samples).
 """
 import argparse
 import os
@@ -139,14 +145,70 @@ def workload_mc(w, h, bits, kind, frames, warmup, nin=4):
     print("%-44s frames=%d  %.1f fps  %.4f ms/frame  alg_bytes/frame=%d  frac=%.3f%s" % (name, frames, 1000.0 / per, per, alg, frac, extra), flush=True)
 
 
+def float_workloads(kinds, frames, warmup, repeats, w=1920, h=1080, nin=4):
+    """the 16-bit path and the float path of Flow fetch / Flow shift / FlowBlur on the same vectors, alternating"""
+    import torch
+    import degrain_float_cases as fc
+    q = pl.moving_clip(w, h, 16, nin, seed=5)
+    floats = fc.float_clip(q, 16, seed=9)
+    akw = dict(blksize=16, overlap=8)
+    sides = {}
+    isup = mv.Super(w, h, 16, pel=2)
+    isrc = [mv.frame_to_device(f) for f in q]
+    isf = isup.build(isrc)
+    abw, afw = mv.Analyse(isup, num_frames=nin, isb=1, **akw), mv.Analyse(isup, num_frames=nin, isb=0, **akw)
+    bbw = abw.run([(isf[n], isf[n + 1] if n + 1 < nin else None) for n in range(nin)])
+    bfw = afw.run([(isf[n], isf[n - 1] if n >= 1 else None) for n in range(nin)])
+    fsup = mv.Super(w, h, 32, pel=2, sample_float=True)
+    fsrc = [mv.frame_to_device(f) for f in floats]
+    sides["16-bit"] = (isup, isrc, isf, {}, 2)
+    sides["float"] = (fsup, fsrc, fsup.build(fsrc), dict(sample_float=True), 4)
+    for kind in kinds:
+        n = min(frames, 64) if kind == "shift" else frames
+        runs = {}
+        for tag, (sup, src, sf, kw, bps) in sides.items():
+            pitch = [p.stride(0) for p in src[0]]
+            out = mv.arena_frames(n, [tuple(p.shape) for p in src[0]], src[0][0].device, zero=False)
+            if kind == "blur":
+                fl = mv.FlowBlur(sup, abw.ad, afw.ad, nin, pitch, blur=50.0, prec=1, **kw)
+                ns = [1 + k % (nin - 2) for k in range(n)]
+                fl.run(ns[:warmup], src, sf, bbw, bfw)
+                arr, _ = fl.jobs(ns, src, sf, bbw, bfw, out=out)
+            else:
+                fl = mv.Flow(sup, abw.ad, nin, pitch, time=100.0, mode=1 if kind == "shift" else 0, **kw)
+                jobs = [(src[k % (nin - 1)], sf[k % (nin - 1) + 1], bbw[k % (nin - 1)]) for k in range(n)]
+                fl.run(jobs[:warmup])
+                arr = (mv.FlowCompJob * n)()
+                for k, (c, r, b) in enumerate(jobs):
+                    for p in range(sup.nplanes):
+                        arr[k].clip[p], arr[k].ref_super[p], arr[k].dst[p] = c[p].data_ptr(), r[p].data_ptr(), out[k][p].data_ptr()
+                    arr[k].blob = b.data_ptr()
+            runs[tag] = (fl, arr, out, 2 * (w * h * bps * 3 // 2), [])
+        torch.cuda.synchronize()
+        for _ in range(repeats):
+            for tag in runs:  # alternating, each timed launch after a warm-up launch of its own shape
+                fl, arr, _, _, ms = runs[tag]
+                ms.append(_timed(fl.launch, arr) / n)
+        for tag, (_, _, _, alg, ms) in runs.items():
+            med, lo_, hi = float(np.median(ms)), min(ms), max(ms)
+            print("%-7s %-6s 1080p 4:2:0 pel 2 16/8  frames=%d repeats=%d  median %.4f ms/frame (fastest %.4f, slowest %.4f, spread %.1f %%)  "
+                  "alg_bytes/frame=%d  %.3f TB/s  frac=%.3f" % (kind, tag, n, repeats, med, lo_, hi, 100.0 * (hi - lo_) / med, alg, alg / (med * 1e-3) / 1e12,
+                                                                alg / (med * 1e-3) / PEAK), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--only", default=None, help="run one workload: 1080p8 or 4k16 (counter passes)")
     ap.add_argument("--filters", default="flowfps,fetch,shift,blur", help="comma-separated subset of flowfps, fetch, shift, blur")
+    ap.add_argument("--float", dest="float_", action="store_true", help="the float path against the 16-bit path on the same vectors (1080p, pel 2, 16/8)")
+    ap.add_argument("--repeats", type=int, default=7, help="--float: timed launches per path, alternating")
     a = ap.parse_args()
     filters = a.filters.split(",")
+    if a.float_:
+        float_workloads([k for k in ("fetch", "shift", "blur") if k in filters], a.frames, a.warmup, a.repeats)
+        return
     for (w, h, bits, tag) in ((1920, 1080, 8, "1080p8"), (3840, 2160, 16, "4k16")):
         if "flowfps" in filters:
             for num in (48, 60):

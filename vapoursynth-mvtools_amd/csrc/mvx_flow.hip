@@ -44,12 +44,23 @@ static_assert(sizeof(FLCell) == 16, "cell layout");
 __device__ __forceinline__ int fl_lo(int w) { return (int)(short)(w & 0xffff); }
 __device__ __forceinline__ int fl_hi(int w) { return w >> 16; }
 
-// the wide helpers move at least two bytes: a single 8-bit sample goes on its own
+// the wide helpers move at least two bytes: a single 8-bit sample goes on its own.  T = float (Flow and FlowBlur on float clips, second half
+// of the file): the int holds the sample's 32 bits as they are -- no float operation sees a sample that is only moved, so NaN payloads and
+// signed zeros survive -- and W of them are one store of 4, 8 or 16 bytes
 template <typename T, int W> __device__ __forceinline__ void fl_load(DG_GL const unsigned char *p, int *o) {
-    if constexpr (W * sizeof(T) == 1) o[0] = *p; else dg_load<T, W>(p, o);
+    if constexpr (sizeof(T) == 4) {
+        const DgRaw<T, W> r = dg_load_raw<T, W>(p);
+#pragma unroll
+        for (int i = 0; i < W; i++) o[i] = (int)r.d[i];
+    } else if constexpr (W * sizeof(T) == 1) o[0] = *p; else dg_load<T, W>(p, o);
 }
 template <typename T, int W> __device__ __forceinline__ void fl_store(DG_GL unsigned char *p, const int *v) {
-    if constexpr (W * sizeof(T) == 1) *p = (unsigned char)v[0]; else dg_store<T, W>(p, v);
+    if constexpr (sizeof(T) == 4) {
+        static_assert(W == 1 || W == 2 || W == 4, "4, 8 or 16 bytes");
+        if constexpr (W == 4) { const dg_uv4 t = { (unsigned)v[0], (unsigned)v[1], (unsigned)v[2], (unsigned)v[3] }; *(DG_GL dg_uv4 *)p = t; }
+        else if constexpr (W == 2) { const dg_uv2 t = { (unsigned)v[0], (unsigned)v[1] }; *(DG_GL dg_uv2 *)p = t; }
+        else *(DG_GL dg_uv1 *)p = (unsigned)v[0];
+    } else if constexpr (W * sizeof(T) == 1) *p = (unsigned char)v[0]; else dg_store<T, W>(p, v);
 }
 
 // per (job, blob): Fakery.c:52-58,103-107,144-146 fgopIsUsable of mvfw at nright, mvbw at nleft, mvfw at nleft, mvbw at nright -> flags[job][4];
@@ -129,7 +140,8 @@ __device__ __forceinline__ int fl_vup(int s1a, int s2a, int s1b, int s2b, int wt
 
 template <typename T>
 __device__ __forceinline__ int fl_fetch(const FLParams &P, const PlaneG &g, const unsigned char *sup, int X, int Y) {
-    return *(DG_GL const T *)dg_gl(sup + sup_offset(g, P.pel, P.logPel, (int)sizeof(T), X, Y));
+    if constexpr (sizeof(T) == 4) return (int)*(DG_GL const unsigned *)dg_gl(sup + sup_offset(g, P.pel, P.logPel, 4, X, Y)); // the bits of a float sample
+    else return *(DG_GL const T *)dg_gl(sup + sup_offset(g, P.pel, P.logPel, (int)sizeof(T), X, Y));
 }
 
 // one thread per CW consecutive samples of one row of plane class p0 .. p0 + npl - 1
@@ -305,6 +317,14 @@ template <typename F> static void flow_launches(const FLParams &P, int nframes, 
     });
 }
 
+// the same for Flow's kernels, which also run on float32 samples (T = float: segments of 4, 2 or 1 samples)
+template <typename F> static void fm_launches(const FLParams &P, int nframes, F &&go) {
+    fps_classes(P.pl, P.nplanes, nframes, [&](int p) { return fps_segment(P.bps, P.pl[p].W); }, [&](dim3 grid, int cw, int p0, int npl) {
+        auto one = [&](auto t, auto w) { go(grid, p0, npl, t, w); };
+        if (P.bps == 4) fps_dispatch_float<1>(cw, one); else fps_dispatch<1>(P.bps, cw, one);
+    });
+}
+
 // MVFlowInter.c:473-678 mvflowinterCreate.  time and ml are float arguments there: time256 is formed in float, ml reaches the mask as (double)(float)ml.
 extern "C" __attribute__((visibility("default"))) int mvx_flowinter_create(const mvx_flowinter_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
         const mvx_super *sup, int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flow **out, char *err) {
@@ -437,6 +457,12 @@ extern "C" __attribute__((visibility("default"))) int mvx_flow_frames(mvx_flow *
 //   flowshift_resolve  : per CW samples -> the winner's sample, or pixel_max where nobody wrote (the reference's memset)
 //   flowblur_kernel    : per sample -> the data-dependent F and B tap loops of RealFlowBlur
 // Each of the last four runs as one launch for the luma planes of all jobs and one for both chroma planes of all jobs.
+//
+// T = float (mvx_flowcomp_create_float, mvx_flowblur_create_float; the rules are in include/mvtools_amd.h): everything above the sample is the
+// integer filter's -- usability, cells, the upsizer, time256 / blur256 / prec, tap counts and positions.  Flow only moves samples, so its
+// kernels carry the 32 bits of each (fl_load / fl_fetch / fl_store) in segments of 4, 2 or 1 samples; the shift's key holds them whole, as
+// ((raster index + 1) << 32) | bits, and a hole becomes 1.0f on luma and 0.5f on chroma.  FlowBlur adds the taps to a float32 sum one by one
+// in the integer kernel's order and divides once.
 struct FMJob {
     const unsigned char *sup[3];   // Flow: super frame nref; FlowBlur: super frame n; NULL = copy the clip frame
     const unsigned char *blob[2];  // Flow: vectors at n; FlowBlur: mvbw at n - delta, mvfw at n + delta
@@ -561,14 +587,25 @@ __global__ __launch_bounds__(256) void flowshift_scatter(const FLParams *Pp, con
         at.vec(cl, 1, 0, hO[i], 16384 - hWr[i], hWr[i], -xi * P.pel, (P.limW[c] - xi) * P.pel - 1, vx, vy);
         const int dx = xi + ((-vx * time256 + rounding) >> shift), dy = y + ((-vy * time256 + rounding) >> shift);
         if (dx >= 0 && dx < g.W && dy >= 0 && dy < g.H) {
-            const unsigned long long key = ((unsigned long long)((long long)y * g.W + xi + 1) << 16) | (unsigned)s[i];
+            // float: the payload takes the low 32 bits and the index the high ones.  It fits them for every legal frame: a plane has
+            // fewer than 2^32 samples, or the 32-bit byte offsets of sup_offset could not address its super plane
+            unsigned long long key;
+            if constexpr (sizeof(T) == 4) key = ((unsigned long long)((long long)y * g.W + xi + 1) << 32) | (unsigned)s[i];
+            else key = ((unsigned long long)((long long)y * g.W + xi + 1) << 16) | (unsigned)s[i];
             __hip_atomic_fetch_max(win + (long long)dy * g.W + dx, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
 
-// MVFlow.cpp:312,336-337 + the scatter's result: the low 16 bits of the winner, pixel_max where no source landed
+// MVFlow.cpp:312,336-337 + the scatter's result: the low 16 bits of the winner, pixel_max where no source landed.  Float: the low 32 bits,
+// and the top of the plane's nominal range where no source landed -- 1.0f on luma, 0.5f on chroma, which is centred on 0
 typedef unsigned long long fm_u64x2 __attribute__((ext_vector_type(2), aligned(8)));
+template <typename T> __device__ __forceinline__ int fm_payload(unsigned long long k) {
+    if constexpr (sizeof(T) == 4) return (int)(unsigned)k; else return (int)(k & 0xffff);
+}
+template <typename T> __device__ __forceinline__ int fm_hole(const FLParams &P, int p) {
+    if constexpr (sizeof(T) == 4) return p ? 0x3f000000 : 0x3f800000; else return (1 << P.bits) - 1;
+}
 template <typename T, int CW>
 __global__ __launch_bounds__(256) void flowshift_resolve(const FLParams *Pp, const FMJob *jobs, const int *flags, FMWin w, int planeFirst, int planesPerFrame) {
     const FLParams &P = *Pp;
@@ -580,17 +617,17 @@ __global__ __launch_bounds__(256) void flowshift_resolve(const FLParams *Pp, con
     DG_GL unsigned char *dptr = dg_glw(J.dst[p] + (long long)y * g.dstPitch + (long long)x * (long long)sizeof(T));
     if (fm_copy<T, CW>(P, J, flags, f, p, x, y, dptr)) return;
     DG_GL const unsigned long long *win = (DG_GL const unsigned long long *)(unsigned long long)(w.win + f * w.job + w.off[p] + (long long)y * g.W + x);
-    const int pixel_max = (1 << P.bits) - 1;
+    const int pixel_max = fm_hole<T>(P, p);
     int out[CW];
     if constexpr (CW == 1) {
         const unsigned long long k = *win;
-        out[0] = k ? (int)(k & 0xffff) : pixel_max;
+        out[0] = k ? fm_payload<T>(k) : pixel_max;
     } else {
 #pragma unroll
         for (int i = 0; i < CW; i += 2) {
             const fm_u64x2 k = *(DG_GL const fm_u64x2 *)(win + i);
-            out[i] = k[0] ? (int)(k[0] & 0xffff) : pixel_max;
-            out[i + 1] = k[1] ? (int)(k[1] & 0xffff) : pixel_max;
+            out[i] = k[0] ? fm_payload<T>(k[0]) : pixel_max;
+            out[i + 1] = k[1] ? fm_payload<T>(k[1]) : pixel_max;
         }
     }
     fl_store<T, CW>(dptr, out);
@@ -600,16 +637,20 @@ __global__ __launch_bounds__(256) void flowshift_resolve(const FLParams *Pp, con
 // v0 = V * blur256 / m (C's truncating division; >> is arithmetic), the mean of the sample and the taps.  Every tap lies inside the
 // frame: the upsizer limits |V| to the frame, and |(i + 1) * v0| <= |V * blur256| with blur256 <= 256.  The sum stays int32 as in the
 // reference: it holds 16-bit samples while mF + mB < 32767.
+// Float: sum = s(X, Y), then sum = sum + tap in float32 for the F taps and the B taps in this order, each addition rounded on its own, and
+// sum / (float)(mF + mB + 1) -- one division, no reciprocal, nothing to fuse, no clamp; without taps it is x / 1.0f, the sample itself.
+template <typename T> struct fb_sum { typedef int type; static __device__ __forceinline__ int of(int s) { return s; } };
+template <> struct fb_sum<float> { typedef float type; static __device__ __forceinline__ float of(int s) { return __int_as_float(s); } };
 template <typename T>
 __device__ __forceinline__ int fb_taps(const FLParams &P, const PlaneG &g, const unsigned char *sup, int X, int Y, int vx, int vy, int blur256, int prec,
-                                       int &sum) {
+                                       typename fb_sum<T>::type &sum) {
     int vx0 = vx * blur256, vy0 = vy * blur256;
     const int m = (max(abs(vx0), abs(vy0)) / prec) >> 8;
     if (m > 0) {
         vx0 /= m; vy0 /= m;
         int ax = vx0, ay = vy0;
         for (int i = 0; i < m; i++) {
-            sum += fl_fetch<T>(P, g, sup, X + (ax >> 8), Y + (ay >> 8));
+            sum = sum + fb_sum<T>::of(fl_fetch<T>(P, g, sup, X + (ax >> 8), Y + (ay >> 8)));
             ax += vx0; ay += vy0;
         }
     }
@@ -635,10 +676,11 @@ __global__ __launch_bounds__(256) void flowblur_kernel(const FLParams *Pp, const
     at.vec(cl, 2, 0, o, 16384 - wr, wr, xLo, xHi, vxB, vyB);
     at.vec(cl, 2, 1, o, 16384 - wr, wr, xLo, xHi, vxF, vyF);
     const int X = x << P.logPel, Y = y << P.logPel;
-    int sum = fl_fetch<T>(P, g, J.sup[p], X, Y);
+    typename fb_sum<T>::type sum = fb_sum<T>::of(fl_fetch<T>(P, g, J.sup[p], X, Y));
     const int mF = fb_taps<T>(P, g, J.sup[p], X, Y, vxF, vyF, blur256, prec, sum);
     const int mB = fb_taps<T>(P, g, J.sup[p], X, Y, vxB, vyB, blur256, prec, sum);
-    const int out = sum / (mF + mB + 1);
+    int out;
+    if constexpr (sizeof(T) == 4) out = __float_as_int(sum / (float)(mF + mB + 1)); else out = sum / (mF + mB + 1);
     fl_store<T, 1>(dptr, &out);
 }
 
@@ -675,10 +717,12 @@ static int fm_prologue(FMEngine *h, int nframes, const std::vector<FMJob> &hj, h
     return MVX_OK;
 }
 
-// the geometry part of creation (after each filter's own checks): the size check, then the grid
+// the geometry part of creation (after each filter's own checks): the size check, then the grid.  not_float: a float entry was handed an
+// integer super clip (said after the size check)
 static int fm_create(FMEngine *h, const char *name, int64_t thscd1, int32_t thscd2, const mvx_analysis_data *ad, const mvx_super_info &si,
-                     const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], bool padded, char *err) {
+                     const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], bool padded, bool not_float, char *err) {
     if (!mvx_super_fits(ad, si, false)) MVX_FAIL("%s: wrong source or super clip frame size.", name);
+    if (not_float) MVX_FAIL("%s: the float entry needs a float super clip.", name);
     if (int rc = flow_geometry(h->P, h->nWidthP, h->nHeightP, name, thscd1, thscd2, ad, si, super_pitch, clip_pitch, dst_pitch, padded, err)) return rc;
     long long o = 0;
     for (int p = 0; p < 3; p++) {
@@ -691,10 +735,11 @@ static int fm_create(FMEngine *h, const char *name, int64_t thscd1, int32_t thsc
 }
 
 // MVFlow.cpp:391-593 mvflowCreate.  time is a double argument there: time256 is formed in double (FlowInter forms it in float).
-extern "C" __attribute__((visibility("default"))) int mvx_flowcomp_create(const mvx_flowcomp_args *a, const mvx_analysis_data *vectors, const mvx_super *sup,
-        int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flowcomp **out, char *err) {
+// flt: the float entry (the super clip must be a float one; said after the frame-size check.  fields = 1 is refused last)
+static int flowcomp_create(const mvx_flowcomp_args *a, const mvx_analysis_data *vectors, const mvx_super *sup, int num_frames, const ptrdiff_t super_pitch[3],
+                           const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flowcomp **out, char *err, bool flt) {
     MVX_CREATE_BEGIN(out);
-    MVX_REFUSE_FLOAT(sup, "Flow");
+    if (!flt) MVX_REFUSE_FLOAT(sup, "Flow");
     const double time = a->time;
     const int mode = a->mode == MVX_UNSET ? 0 : a->mode;
     int64_t thscd1; int32_t thscd2;
@@ -702,13 +747,22 @@ extern "C" __attribute__((visibility("default"))) int mvx_flowcomp_create(const 
     if (mode < 0 || mode > 1) MVX_FAIL("Flow: mode must be 0 or 1.");
     if (int rc = mvx_resolve_thscd("Flow", a->thscd1, a->thscd2, vectors, &thscd1, &thscd2, err)) return rc;
     mvx_flowcomp *h = new mvx_flowcomp();
-    if (int rc = fm_create(h, "Flow", thscd1, thscd2, vectors, sup->info, super_pitch, clip_pitch, dst_pitch, true, err)) { delete h; return rc; }
+    if (int rc = fm_create(h, "Flow", thscd1, thscd2, vectors, sup->info, super_pitch, clip_pitch, dst_pitch, true, flt && !sup->is_float, err)) { delete h; return rc; }
     h->nb = 1; h->mode = mode;
     h->fields = a->fields == MVX_UNSET ? 0 : !!a->fields;
+    if (flt && h->fields) { delete h; MVX_FAIL("Flow: fields is not supported on float clips."); }
     h->time256 = (int)(time * 256.0 / 100.0);
     h->numFrames = num_frames;
     *out = h;
     return MVX_OK;
+}
+extern "C" __attribute__((visibility("default"))) int mvx_flowcomp_create(const mvx_flowcomp_args *a, const mvx_analysis_data *vectors, const mvx_super *sup,
+        int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flowcomp **out, char *err) {
+    return flowcomp_create(a, vectors, sup, num_frames, super_pitch, clip_pitch, dst_pitch, out, err, false);
+}
+extern "C" __attribute__((visibility("default"))) int mvx_flowcomp_create_float(const mvx_flowcomp_args *a, const mvx_analysis_data *vectors, const mvx_super *sup,
+        int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flowcomp **out, char *err) {
+    return flowcomp_create(a, vectors, sup, num_frames, super_pitch, clip_pitch, dst_pitch, out, err, true);
 }
 extern "C" __attribute__((visibility("default"))) void mvx_flowcomp_destroy(mvx_flowcomp *h) { delete h; }
 // MVFlow.cpp:170-176: the reference frame of output frame n
@@ -743,16 +797,16 @@ extern "C" __attribute__((visibility("default"))) int mvx_flowcomp_frames(mvx_fl
     }
     if (int rc = fm_prologue(h, nframes, hj, st)) return rc;
     if (h->mode == 0) {
-        flow_launches(P, nframes, [&](dim3 grid, int p0, int npl, auto t, auto w) {
+        fm_launches(P, nframes, [&](dim3 grid, int p0, int npl, auto t, auto w) {
             hipLaunchKernelGGL((flowcomp_kernel<typename decltype(t)::type, decltype(w)::value>), grid, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p, h->dCells.p, h->time256, p0, npl);
         });
     } else {
         const FMWin win = { h->dWin.p, h->winJob, { h->winOff[0], h->winOff[1], h->winOff[2] } };
         HIP_CHECK(hipMemsetAsync(h->dWin.p, 0, (size_t)nframes * h->winJob * sizeof(unsigned long long), st));
-        flow_launches(P, nframes, [&](dim3 grid, int p0, int npl, auto t, auto w) {
+        fm_launches(P, nframes, [&](dim3 grid, int p0, int npl, auto t, auto w) {
             hipLaunchKernelGGL((flowshift_scatter<typename decltype(t)::type, decltype(w)::value>), grid, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p, h->dCells.p, h->time256, win, p0, npl);
         });
-        flow_launches(P, nframes, [&](dim3 grid, int p0, int npl, auto t, auto w) {
+        fm_launches(P, nframes, [&](dim3 grid, int p0, int npl, auto t, auto w) {
             hipLaunchKernelGGL((flowshift_resolve<typename decltype(t)::type, decltype(w)::value>), grid, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p, win, p0, npl);
         });
     }
@@ -761,11 +815,11 @@ extern "C" __attribute__((visibility("default"))) int mvx_flowcomp_frames(mvx_fl
 }
 
 // MVFlowBlur.c:346-552 mvflowblurCreate.  blur is a float argument there: blur256 is formed in float.
-extern "C" __attribute__((visibility("default"))) int mvx_flowblur_create(const mvx_flowblur_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
-        const mvx_super *sup, int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flowblur **out,
-        char *err) {
+// flt: the float entry (the super clip must be a float one; said after the frame-size check)
+static int flowblur_create(const mvx_flowblur_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw, const mvx_super *sup, int num_frames,
+                           const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flowblur **out, char *err, bool flt) {
     MVX_CREATE_BEGIN(out);
-    MVX_REFUSE_FLOAT(sup, "FlowBlur");
+    if (!flt) MVX_REFUSE_FLOAT(sup, "FlowBlur");
     const float blur = (float)a->blur;
     const int prec = a->prec == MVX_UNSET ? 1 : a->prec;
     int64_t thscd1; int32_t thscd2;
@@ -773,12 +827,22 @@ extern "C" __attribute__((visibility("default"))) int mvx_flowblur_create(const 
     if (prec < 1) MVX_FAIL("FlowBlur: prec must be at least 1.");
     if (int rc = flow_pair_checks("FlowBlur", a->thscd1, a->thscd2, &thscd1, &thscd2, bw, fw, err)) return rc;
     mvx_flowblur *h = new mvx_flowblur();
-    if (int rc = fm_create(h, "FlowBlur", thscd1, thscd2, bw, sup->info, super_pitch, clip_pitch, dst_pitch, false, err)) { delete h; return rc; }
+    if (int rc = fm_create(h, "FlowBlur", thscd1, thscd2, bw, sup->info, super_pitch, clip_pitch, dst_pitch, false, flt && !sup->is_float, err)) { delete h; return rc; }
     h->nb = 2; h->prec = prec;
     h->blur256 = (int)(blur * 256.0f / 200.0f);
     h->numFrames = num_frames;
     *out = h;
     return MVX_OK;
+}
+extern "C" __attribute__((visibility("default"))) int mvx_flowblur_create(const mvx_flowblur_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
+        const mvx_super *sup, int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flowblur **out,
+        char *err) {
+    return flowblur_create(a, bw, fw, sup, num_frames, super_pitch, clip_pitch, dst_pitch, out, err, false);
+}
+extern "C" __attribute__((visibility("default"))) int mvx_flowblur_create_float(const mvx_flowblur_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
+        const mvx_super *sup, int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flowblur **out,
+        char *err) {
+    return flowblur_create(a, bw, fw, sup, num_frames, super_pitch, clip_pitch, dst_pitch, out, err, true);
 }
 extern "C" __attribute__((visibility("default"))) void mvx_flowblur_destroy(mvx_flowblur *h) { delete h; }
 
@@ -809,7 +873,8 @@ extern "C" __attribute__((visibility("default"))) int mvx_flowblur_frames(mvx_fl
     }
     if (int rc = fm_prologue(h, nframes, hj, st)) return rc;
     fps_classes(P.pl, P.nplanes, nframes, [](int) { return 1; }, [&](dim3 grid, int, int p0, int npl) { // one sample per thread
-        if (P.bps == 1) hipLaunchKernelGGL((flowblur_kernel<uint8_t>), grid, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p, h->dCells.p, h->blur256, h->prec, p0, npl);
+        if (P.bps == 4) hipLaunchKernelGGL((flowblur_kernel<float>), grid, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p, h->dCells.p, h->blur256, h->prec, p0, npl);
+        else if (P.bps == 1) hipLaunchKernelGGL((flowblur_kernel<uint8_t>), grid, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p, h->dCells.p, h->blur256, h->prec, p0, npl);
         else hipLaunchKernelGGL((flowblur_kernel<uint16_t>), grid, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p, h->dCells.p, h->blur256, h->prec, p0, npl);
     });
     HIP_CHECK(hipGetLastError());

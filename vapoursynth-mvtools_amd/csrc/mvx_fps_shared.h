@@ -365,3 +365,6 @@ template <int MINW, typename T, int W, typename F> static void fps_dispatch_widt
 template <int MINW, typename F> static void fps_dispatch(int bps, int cw, F &&f) {
     if (bps == 1) fps_dispatch_width<MINW, uint8_t, 16>(cw, f); else fps_dispatch_width<MINW, uint16_t, 8>(cw, f);
 }
+// the segments MINW .. 4 of float32 samples (16 bytes at most, like the others).  On its own, so that a kernel gets a float form only where
+// its caller asks for one
+template <int MINW, typename F> static void fps_dispatch_float(int cw, F &&f) { fps_dispatch_width<MINW, float, 4>(cw, f); }

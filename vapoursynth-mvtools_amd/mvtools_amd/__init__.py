@@ -390,11 +390,13 @@ def lib():
         L.mvx_flow_frames.argtypes = [C.c_void_p, C.c_int, P(FlowJob), C.c_void_p]
         L.mvx_flowcomp_create.argtypes = [P(FlowCompArgs), P(AnalysisData), C.c_void_p, C.c_int, P(C.c_ssize_t), P(C.c_ssize_t), P(C.c_ssize_t),
                                           P(C.c_void_p), C.c_char_p]
+        L.mvx_flowcomp_create_float.argtypes = L.mvx_flowcomp_create.argtypes
         L.mvx_flowcomp_destroy.argtypes = [C.c_void_p]
         L.mvx_flowcomp_ref.argtypes = [C.c_void_p, C.c_int]
         L.mvx_flowcomp_frames.argtypes = [C.c_void_p, C.c_int, P(FlowCompJob), C.c_void_p]
         L.mvx_flowblur_create.argtypes = [P(FlowBlurArgs), P(AnalysisData), P(AnalysisData), C.c_void_p, C.c_int, P(C.c_ssize_t), P(C.c_ssize_t),
                                           P(C.c_ssize_t), P(C.c_void_p), C.c_char_p]
+        L.mvx_flowblur_create_float.argtypes = L.mvx_flowblur_create.argtypes
         L.mvx_flowblur_destroy.argtypes = [C.c_void_p]
         L.mvx_flowblur_frames.argtypes = [C.c_void_p, C.c_int, P(FlowBlurJob), C.c_void_p]
         L.mvx_mask_create.argtypes = [P(MaskArgs), P(AnalysisData), P(MaskClip), P(C.c_ssize_t), P(C.c_ssize_t), P(C.c_void_p), C.c_char_p]
@@ -564,7 +566,7 @@ def plane_to_numpy(t, width, dtype):
 
 class Super(_Handle):
     """mv.Super -- MVSuper.c:140-275.  sample_float=True with bits=32: the super clip of a float32 clip (mvx_super_create_float) -- one level, no
-    shadow planes, planes of float32; DegrainN, and Compensate / CompensateN / BlockFPS with sample_float=True, consume it."""
+    shadow planes, planes of float32; DegrainN, and Compensate / CompensateN / BlockFPS / Flow / FlowBlur with sample_float=True, consume it."""
     _destroy = "mvx_super_destroy"
 
     def __init__(self, width, height, bits=8, subsampling=(1, 1), gray=False, hpad=None, vpad=None, pel=None, levels=None,
@@ -1244,21 +1246,33 @@ class FlowFPS(_Flow):
                                                                                    int(fps_den), _pad3(sup.pitch), _pad3(clip_pitch), _pad3(dst_pitch or clip_pitch), h, err))
 
 
+def _flow_out(torch, flt, n, frame):
+    """n output frames like the clip frame `frame` for Flow / FlowBlur: float32 planes of the filter's dst pitch for a float filter"""
+    if flt.is_float:
+        return [[_out_plane(torch, frame[p].shape[0], flt.dst_pitch[p], True, frame[0].device) for p in range(flt.sup.nplanes)] for _ in range(n)]
+    return arena_frames(n, [tuple(p.shape) for p in frame], frame[0].device, zero=False)
+
+
 class Flow(_Handle):
     """mv.Flow(clip, super, vectors, time, mode, fields, thscd1, thscd2, tff) -- MVFlow.cpp:391-593.  Output frame n is clip frame n compensated
-    per sample from the Finest frame of ref(n); `clip_pitch` is the row pitch of the clip's device planes (and of the output)."""
+    per sample from the Finest frame of ref(n); `clip_pitch` is the row pitch of the clip's device planes (and of the output).  sample_float=True
+    selects mvx_flowcomp_create_float: a float super clip (Super(..., bits=32, sample_float=True)), float32 clip and output planes, vectors and
+    thresholds from a search on an 8..16 bit copy; samples are moved bit for bit, fields is refused.  The keyword is explicit: a float super
+    clip without it is refused."""
     _destroy = "mvx_flowcomp_destroy"
 
-    def __init__(self, sup, ad, num_frames, clip_pitch, time=100.0, mode=None, fields=None, thscd1=None, thscd2=None, dst_pitch=None):
+    def __init__(self, sup, ad, num_frames, clip_pitch, time=100.0, mode=None, fields=None, thscd1=None, thscd2=None, dst_pitch=None, sample_float=False):
         self.sup = sup
+        self.is_float = bool(sample_float)
         a = FlowCompArgs(float(time), _u(mode), _u(fields), _u(thscd1), _u(thscd2))
         ad = AnalysisData.from_buffer_copy(bytes(ad))
         self.h = C.c_void_p()
         self.pitch = list(clip_pitch)
         self.num_frames = int(num_frames)
         err = C.create_string_buffer(ERRLEN)
-        _check(lib().mvx_flowcomp_create(C.byref(a), C.byref(ad), sup.h, self.num_frames, _pad3(sup.pitch), _pad3(clip_pitch), _pad3(dst_pitch or clip_pitch),
-                                         C.byref(self.h), err), err)
+        create = lib().mvx_flowcomp_create_float if self.is_float else lib().mvx_flowcomp_create
+        self.dst_pitch = list(dst_pitch or clip_pitch)
+        _check(create(C.byref(a), C.byref(ad), sup.h, self.num_frames, _pad3(sup.pitch), _pad3(clip_pitch), _pad3(self.dst_pitch), C.byref(self.h), err), err)
 
     def ref(self, n):
         """the reference frame of output frame n (MVFlow.cpp:170-176); outside the clip the job passes no super frame"""
@@ -1266,11 +1280,10 @@ class Flow(_Handle):
 
     def run(self, jobs, out=None):
         """jobs: list of (clip_frame, ref_super_or_None, blob[, field_shift]); None or a blob of None copies the clip frame"""
-        _torch()
+        torch = _torch()
         n = len(jobs)
         if out is None:
-            c = jobs[0][0]
-            out = arena_frames(n, [tuple(p.shape) for p in c], c[0].device, zero=False)
+            out = _flow_out(torch, self, n, jobs[0][0])
         arr = (FlowCompJob * n)()
         for k, job in enumerate(jobs):
             clip, r, blob = job[:3]
@@ -1290,11 +1303,13 @@ class Flow(_Handle):
 
 class FlowBlur(_Handle):
     """mv.FlowBlur(clip, super, mvbw, mvfw, blur, prec, thscd1, thscd2) -- MVFlowBlur.c:346-552.  `clip_pitch` is the row pitch of the clip's
-    device planes (and of the output)."""
+    device planes (and of the output).  sample_float=True selects mvx_flowblur_create_float, as in Flow: float super clip, float32 clip and
+    output planes, the taps summed in float32 one by one and divided once."""
     _destroy = "mvx_flowblur_destroy"
 
-    def __init__(self, sup, ad_bw, ad_fw, num_frames, clip_pitch, blur=50.0, prec=None, thscd1=None, thscd2=None, dst_pitch=None):
+    def __init__(self, sup, ad_bw, ad_fw, num_frames, clip_pitch, blur=50.0, prec=None, thscd1=None, thscd2=None, dst_pitch=None, sample_float=False):
         self.sup = sup
+        self.is_float = bool(sample_float)
         a = FlowBlurArgs(float(blur), _u(prec), _u(thscd1), _u(thscd2))
         bw = AnalysisData.from_buffer_copy(bytes(ad_bw))
         fw = AnalysisData.from_buffer_copy(bytes(ad_fw))
@@ -1303,8 +1318,9 @@ class FlowBlur(_Handle):
         self.num_frames = int(num_frames)
         self.delta = bw.nDeltaFrame
         err = C.create_string_buffer(ERRLEN)
-        _check(lib().mvx_flowblur_create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, self.num_frames, _pad3(sup.pitch), _pad3(clip_pitch),
-                                         _pad3(dst_pitch or clip_pitch), C.byref(self.h), err), err)
+        create = lib().mvx_flowblur_create_float if self.is_float else lib().mvx_flowblur_create
+        self.dst_pitch = list(dst_pitch or clip_pitch)
+        _check(create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, self.num_frames, _pad3(sup.pitch), _pad3(clip_pitch), _pad3(self.dst_pitch), C.byref(self.h), err), err)
 
     def run(self, ns, clip, supers, blobs_bw, blobs_fw, out=None):
         """ns: output frame numbers, one job each, all in one call; clip / supers: device frames of the input clip and its super clip;
@@ -1320,10 +1336,10 @@ class FlowBlur(_Handle):
 
     def jobs(self, ns, clip, supers, blobs_bw, blobs_fw, out=None):
         """the job table of run() and its output frames, without launching"""
-        _torch()
+        torch = _torch()
         n = len(ns)
         if out is None:
-            out = arena_frames(n, [tuple(p.shape) for p in clip[0]], clip[0][0].device, zero=False)
+            out = _flow_out(torch, self, n, clip[0])
         arr = (FlowBlurJob * n)()
         d = self.delta
         for k, fo in enumerate(ns):
