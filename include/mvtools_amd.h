@@ -18,7 +18,7 @@
  * Plane layouts (checked: *_create refuses a pitch, *_frames an address, with MVX_E_ARG and before anything is uploaded or launched)
  *   - Clip-side planes -- src / clip / dst of mvx_degrain, mvx_degrain_n in all its three entries, mvx_compensate and mvx_compensate_n with
  *     their float entries,
- *     mvx_blockfps, mvx_flowinter / mvx_flowfps, mvx_flowcomp and mvx_flowblur, the last two with their float entries: any pitch that holds a row of its plane and is a multiple of
+ *     mvx_blockfps, mvx_flowinter / mvx_flowfps, mvx_flowcomp and mvx_flowblur, all of these with their float entries: any pitch that holds a row of its plane and is a multiple of
  *     the sample size (1, 2, or 4 bytes for a float clip; out16 writes 2-byte samples), and any plane address that is a multiple of the
  *     sample size.  A tight pitch, an odd pitch for 8-bit samples, a plane inside a wider frame, U and V of different pitch, src and dst of
  *     different pitch are all legal.  A shorter pitch, a pitch or address that is no multiple of the sample size, and a missing plane where
@@ -104,8 +104,8 @@ void mvx_super_get_info(const mvx_super *s, mvx_super_info *info);
  *   sharp 2   m2 = (m2 + m3) * 4; m2 -= (m1 + m4); m2 *= 5; m0 = (m0 + m5) + m2; m0 * 0.03125f
  *   the diagonal plane of sharp 1 and 2 is the horizontal rule on the UNROUNDED vertical plane; pel 4: (a + b) * 0.5f
  * (csrc/mvx_super_float_rule.h).  Samples are assumed finite.  Only the float entries -- mvx_degrain_n_create_float, mvx_compensate_create_float,
- * mvx_compensate_n_create_float, mvx_blockfps_create_float, mvx_flowcomp_create_float and mvx_flowblur_create_float -- consume such an object
- * (FlowInter and FlowFPS have no float entry): mvx_super_shadow_copies
+ * mvx_compensate_n_create_float, mvx_blockfps_create_float, mvx_flowinter_create_float, mvx_flowfps_create_float, mvx_flowcomp_create_float and
+ * mvx_flowblur_create_float -- consume such an object: mvx_super_shadow_copies
  * returns 0, the shadow, pelclip and Finest entries return MVX_E_ARG, and every other *_create that takes an mvx_super refuses it before any
  * other check with "<Name>: float super clips are not supported.".  Touches no device. */
 int mvx_super_create_float(const mvx_super_args *args, mvx_super **out, char *err);
@@ -699,6 +699,47 @@ typedef struct mvx_flow_job {
 /* nframes jobs of one handle in one batch on `stream`: three small per-job kernels and a memset, then two gather launches that cover
  * all jobs: one for the luma planes, one for both chroma planes (Gray: the luma launch only) */
 int mvx_flow_frames(mvx_flow *h, int nframes, const mvx_flow_job *jobs, void *stream);
+
+/* FlowInter and FlowFPS on a 32-bit float clip: clip_left, clip_right and dst are float32 planes, super_left / super_right frames of a
+ * mvx_super_create_float clip; mvbw, mvfw and the blobs come from a search on ANY 8..16 bit clip of the same width, height, pel, padding and
+ * subsampling.  thscd1, thscd2 and ml are in the units of that search.  The reference has no float path; the arithmetic is the library's own.
+ * Everything above the sample is the integer filter's, value for value, for the same blobs: which jobs are usable and which formula a job
+ * takes (fl_state: FlowInter Regular or Extra; FlowFPS Simple at mask 0, Regular at mask 1, Extra at mask 2 and Simple where the extra vectors
+ * are not usable), the occlusion masks, the padded cells, the int16 upsizer and the 8-bit mask upsizer at each sample, the fetch positions,
+ * time256 and the FlowFPS rate map.  A sample, float32, nothing fused, every operation rounded on its own (csrc/mvx_flow_float_rule.h), with
+ * t = time256, dF the fetch from the LEFT super frame along the forward vector scaled by t, dB the fetch from the RIGHT one along the backward
+ * vector scaled by 256 - t, dF0 / dB0 the left / right super sample at the output position, dFF / dBB the Extra fetches (the forward vectors
+ * at nleft on the left frame, the backward vectors at nright on the right one), mF / mB the upsized masks (0..255),
+ * time(r, l, t) = (r * (float)t + l * (float)(256 - t)) * (1 / 256) and mix(m, p, q) = ((float)m * p + (float)(255 - m) * q) / 255:
+ *   Simple  (MaskFun.cpp:493-551) time(mix(mB, dF, dB), mix(mF, dB, dF), t) at EVERY t.  There is no special formula at t = 128: the
+ *                                reference's own, ((dF + dB) * 256 + (dB - dF) * (mF - mB)) >> 9, is the general one with its shifts merged
+ *                                and 256 for the masks' 255 -- within peak / 512 of it before rounding -- and float32 has no shift to save
+ *   Regular (:374-414)           a = mix(mF, mix(mB, dF0, dB), dF); b = mix(mB, mix(mF, dB0, dF), dB); time(b, a, t)
+ *   Extra   (:417-490)           lo = min(dB, dF), hi = max(dB, dF), medBB = max(lo, min(dBB, hi)), medFF = max(lo, min(dFF, hi));
+ *                                time(mix(mB, medFF, dB), mix(mF, medBB, dF), t)
+ *   job not usable, blend 1      (a scene change per thscd1 / thscd2, an invalid blob, a frame outside the clip) time(r, l, t) on the clip
+ *                                frames
+ *   job not usable, blend 0      clip_left, a plain load and store of the 32 bits: NaN payloads and signed zeros survive
+ *   FlowFPS t <= 0 / t >= 256    clip_left / clip_right likewise, bit for bit
+ * The mask mixes divide by 255, the weights' own sum, where the reference's (... + 255) >> 8 is 8-bit arithmetic; there is no rounding term
+ * and no clamp to a sample range.  Minimum and maximum are comparisons that return their second operand when neither is smaller / larger.
+ * Inputs are assumed finite; samples may be negative or overshoot.  Messages are mvx_flowinter_create's / mvx_flowfps_create's, the
+ * reference's, in their order -- arguments, thscd1, the two vector clips, for FlowFPS the frame rate and the two frame-size checks, "wrong
+ * source or super clip frame size", for FlowFPS "inconsistent clips frame size" --; then "FlowInter: the float entry needs a float super
+ * clip." / "FlowFPS: the float entry needs a float super clip."; then the library's own geometry and pitch checks ("at least two blocks
+ * wide", U and V super pitch, super / clip / dst pitches with 4-byte samples), which the integer entries say before their frame-size checks.
+ * mvx_flowinter_create and mvx_flowfps_create themselves keep refusing a float super clip first of all.  Touch no device.
+ * mvx_flow_frames, mvx_flow_map, mvx_flow_get_info and mvx_flow_destroy serve the objects; the job struct is the same.  Layouts: clip_left,
+ * clip_right and dst planes at any pitch that holds a row and any address, both multiples of 4; super planes with pitches and addresses that
+ * are multiples of 16; mvx_flow_frames refuses everything else before a launch.  Samples are produced in segments of 4, 2 or 1 (the widest
+ * that divides the plane width).  Not registered in the VapourSynth shell. */
+int mvx_flowinter_create_float(const mvx_flowinter_args *args, const mvx_analysis_data *mvbw, const mvx_analysis_data *mvfw,
+                               const mvx_super *super_clip /* float */, int num_frames, const ptrdiff_t super_pitch[3],
+                               const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flow **out, char *err);
+int mvx_flowfps_create_float(const mvx_flowfps_args *args, const mvx_analysis_data *mvbw, const mvx_analysis_data *mvfw,
+                             const mvx_super *super_clip /* float */, int num_frames, int64_t fps_num, int64_t fps_den,
+                             const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3],
+                             mvx_flow **out, char *err);
 
 /* ---- mv.Flow / mv.FlowBlur ------------------------------------------------------------------------
  * per-sample motion compensation and motion blur on the flow machinery above (int16 vector upsizing per sample, the super clip

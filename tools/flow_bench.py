@@ -2,7 +2,7 @@
 the super frames and vector blobs resident.
 
     python tools/flow_bench.py [--frames N] [--warmup W] [--only 1080p8|4k16] [--filters flowfps,fetch,shift,blur]
-    python tools/flow_bench.py --float [--frames N] [--repeats R] [--filters fetch,shift,blur]
+    python tools/flow_bench.py --float [--frames N] [--repeats R] [--filters fetch,shift,blur,flowinter,flowfps]
 
 Workloads at 1080p 8-bit and 4K 16-bit 4:2:0: FlowFPS 2x and 24 -> 60, mask=2; Flow fetch and Flow shift at time 100; FlowBlur at blur 50,
 prec 1.  Per workload: output fps, ms per output frame, algorithmic bytes per output frame and frac = those bytes per second over 8.0 TB/s.
@@ -11,10 +11,11 @@ plus one read of the frame they sample).  FlowBlur also reports its mean taps pe
 jobs at once (its winner buffer takes 8 bytes per sample and job).  Kernel times come from a separate rocprofv3 --kernel-trace --stats run
 of this script.
 
---float: Flow fetch, Flow shift and FlowBlur (blur 50) at 1080p 4:2:0, pel 2, blocks 16/8, on a 16-bit clip and on its float clip
-(sample_float=True) with the SAME vectors, searched once on the 16-bit clip.  The two paths alternate R times in one process; per path the
-median, the fastest and the slowest ms per frame, the spread (slowest - fastest) / median, and the algorithm's bytes per second at the median
-(2 x the output frame: 2-byte samples against 4-byte samples).
+--float: Flow fetch, Flow shift and FlowBlur (blur 50), and with --filters flowinter,flowfps FlowInter (time 50) and FlowFPS (24 -> 60, mask 2;
+both on the Extra formula), at 1080p 4:2:0, pel 2, blocks 16/8, on a 16-bit clip and on its float clip (sample_float=True) with the SAME
+vectors, searched once on the 16-bit clip.  The two paths alternate R times in one process; per path the median, the fastest and the slowest ms
+per frame, the spread (slowest - fastest) / median, and the algorithm's bytes per second at the median (2 x the output frame, 3 x for FlowInter
+and FlowFPS: 2-byte samples against 4-byte samples).
 """
 import argparse
 import os
@@ -146,7 +147,7 @@ def workload_mc(w, h, bits, kind, frames, warmup, nin=4):
 
 
 def float_workloads(kinds, frames, warmup, repeats, w=1920, h=1080, nin=4):
-    """the 16-bit path and the float path of Flow fetch / Flow shift / FlowBlur on the same vectors, alternating"""
+    """the 16-bit path and the float path of Flow fetch / Flow shift / FlowBlur / FlowInter / FlowFPS on the same vectors, alternating"""
     import torch
     import degrain_float_cases as fc
     q = pl.moving_clip(w, h, 16, nin, seed=5)
@@ -169,7 +170,20 @@ def float_workloads(kinds, frames, warmup, repeats, w=1920, h=1080, nin=4):
         for tag, (sup, src, sf, kw, bps) in sides.items():
             pitch = [p.stride(0) for p in src[0]]
             out = mv.arena_frames(n, [tuple(p.shape) for p in src[0]], src[0][0].device, zero=False)
-            if kind == "blur":
+            reads = 1
+            if kind in ("flowinter", "flowfps"):
+                if kind == "flowinter":
+                    fl = mv.FlowInter(sup, abw.ad, afw.ad, nin, pitch, time=50.0, **kw)
+                    inner = [1]
+                else:
+                    fl = mv.FlowFPS(sup, abw.ad, afw.ad, nin, pitch, 24, 1, num=60, den=1, mask=2, **kw)
+                    inner = [k for k in range(fl.num_frames) if fl.map(k)[0] == 1 and fl.map(k)[2] not in (0, 256)]
+                # output frames inside the middle input interval (1, 2): both extra blobs usable -> the Extra formula, no copies
+                ns = [inner[k % len(inner)] for k in range(n)]
+                fl.run(ns[:warmup], src, sf, bbw, bfw)
+                arr, _ = fl.jobs(ns, src, sf, bbw, bfw, out=out)
+                reads = 2
+            elif kind == "blur":
                 fl = mv.FlowBlur(sup, abw.ad, afw.ad, nin, pitch, blur=50.0, prec=1, **kw)
                 ns = [1 + k % (nin - 2) for k in range(n)]
                 fl.run(ns[:warmup], src, sf, bbw, bfw)
@@ -183,7 +197,7 @@ def float_workloads(kinds, frames, warmup, repeats, w=1920, h=1080, nin=4):
                     for p in range(sup.nplanes):
                         arr[k].clip[p], arr[k].ref_super[p], arr[k].dst[p] = c[p].data_ptr(), r[p].data_ptr(), out[k][p].data_ptr()
                     arr[k].blob = b.data_ptr()
-            runs[tag] = (fl, arr, out, 2 * (w * h * bps * 3 // 2), [])
+            runs[tag] = (fl, arr, out, (1 + reads) * (w * h * bps * 3 // 2), [])
         torch.cuda.synchronize()
         for _ in range(repeats):
             for tag in runs:  # alternating, each timed launch after a warm-up launch of its own shape
@@ -201,13 +215,13 @@ def main():
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--only", default=None, help="run one workload: 1080p8 or 4k16 (counter passes)")
-    ap.add_argument("--filters", default="flowfps,fetch,shift,blur", help="comma-separated subset of flowfps, fetch, shift, blur")
+    ap.add_argument("--filters", default="flowfps,fetch,shift,blur", help="comma-separated subset of flowfps, fetch, shift, blur (--float: and flowinter)")
     ap.add_argument("--float", dest="float_", action="store_true", help="the float path against the 16-bit path on the same vectors (1080p, pel 2, 16/8)")
     ap.add_argument("--repeats", type=int, default=7, help="--float: timed launches per path, alternating")
     a = ap.parse_args()
     filters = a.filters.split(",")
     if a.float_:
-        float_workloads([k for k in ("fetch", "shift", "blur") if k in filters], a.frames, a.warmup, a.repeats)
+        float_workloads([k for k in ("fetch", "shift", "blur", "flowinter", "flowfps") if k in filters], a.frames, a.warmup, a.repeats)
         return
     for (w, h, bits, tag) in ((1920, 1080, 8, "1080p8"), (3840, 2160, 16, "4k16")):
         if "flowfps" in filters:

@@ -14,6 +14,7 @@
 //   flow_kernel        : per CW consecutive output samples -> the interpolated samples, one wide store; one launch for the luma planes
 //                        of all jobs and one for both chroma planes of all jobs (the two classes differ in CW and in the upsizer tables)
 #include "mvx_fps_shared.h"
+#include "mvx_flow_float_rule.h"
 
 enum { FL_SIMPLE = 0, FL_REGULAR = 1, FL_EXTRA = 2, FL_FALLBACK = -1 };
 
@@ -144,7 +145,9 @@ __device__ __forceinline__ int fl_fetch(const FLParams &P, const PlaneG &g, cons
     else return *(DG_GL const T *)dg_gl(sup + sup_offset(g, P.pel, P.logPel, (int)sizeof(T), X, Y));
 }
 
-// one thread per CW consecutive samples of one row of plane class p0 .. p0 + npl - 1
+// one thread per CW consecutive samples of one row of plane class p0 .. p0 + npl - 1.  T = float (mvx_flowinter_create_float,
+// mvx_flowfps_create_float; the rules are in include/mvtools_amd.h and mvx_flow_float_rule.h): the vectors, the masks and the fetch positions
+// are the integer filter's, the fetched 32 bits go through the rule header as float32, a copy moves them untouched
 template <typename T, int CW>
 __global__ __launch_bounds__(256) void flow_kernel(const FLParams *Pp, const FLJob *jobs, const int *flags, const FLCell *cells, const unsigned char *masks,
                                                    int planeFirst, int planesPerFrame) {
@@ -166,7 +169,10 @@ __global__ __launch_bounds__(256) void flow_kernel(const FLParams *Pp, const FLJ
         int r[CW];
         fl_load<T, CW>(dg_gl(J.clipR[p] + co), r);
 #pragma unroll
-        for (int i = 0; i < CW; i++) out[i] = (int)(T)((l[i] * (256 - t) + r[i] * t) >> 8);
+        for (int i = 0; i < CW; i++) {
+            if constexpr (sizeof(T) == 4) out[i] = __float_as_int(mvx_flf_blend(t, __int_as_float(l[i]), __int_as_float(r[i])));
+            else out[i] = (int)(T)((l[i] * (256 - t) + r[i] * t) >> 8);
+        }
         fl_store<T, CW>(dptr, out);
         return;
     }
@@ -200,14 +206,19 @@ __global__ __launch_bounds__(256) void flow_kernel(const FLParams *Pp, const FLJ
         const int dB = fl_fetch<T>(P, g, J.supR[p], X + ((vxB * (256 - t)) >> 8), Y + ((vyB * (256 - t)) >> 8));
         int v;
         if (st == FL_SIMPLE) { // MaskFun.cpp:493-551 (time256 == 128 has its own formula; its vectors v >> 1 equal (v * 128) >> 8)
-            if (t == 128) v = (((dF + dB) << 8) + (dB - dF) * (mF - mB)) >> 9;
+            if constexpr (sizeof(T) == 4) v = __float_as_int(mvx_flf_simple(t, __int_as_float(dF), __int_as_float(dB), mF, mB)); // one formula at every t
+            else if (t == 128) v = (((dF + dB) << 8) + (dB - dF) * (mF - mB)) >> 9;
             else v = (((dF * (255 - mF) + dB * mF + 255) >> 8) * (256 - t) + ((dB * (255 - mB) + dF * mB + 255) >> 8) * t) >> 8;
         } else if (st == FL_REGULAR) { // MaskFun.cpp:374-414: the int64 products are non-negative and below 2^32
             const unsigned dF0 = (unsigned)fl_fetch<T>(P, g, J.supL[p], X, Y), dB0 = (unsigned)fl_fetch<T>(P, g, J.supR[p], X, Y);
-            const unsigned uF = (unsigned)dF, uB = (unsigned)dB, kF = (unsigned)mF, kB = (unsigned)mB;
-            const unsigned a = (uF * (255 - kF) + ((kF * (uB * (255 - kB) + kB * dF0) + 255) >> 8) + 255) >> 8;
-            const unsigned b = (uB * (255 - kB) + ((kB * (uF * (255 - kF) + kF * dB0) + 255) >> 8) + 255) >> 8;
-            v = (int)((a * (unsigned)(256 - t) + b * (unsigned)t) >> 8);
+            if constexpr (sizeof(T) == 4) {
+                v = __float_as_int(mvx_flf_regular(t, __int_as_float(dF), __int_as_float(dB), __uint_as_float(dF0), __uint_as_float(dB0), mF, mB));
+            } else {
+                const unsigned uF = (unsigned)dF, uB = (unsigned)dB, kF = (unsigned)mF, kB = (unsigned)mB;
+                const unsigned a = (uF * (255 - kF) + ((kF * (uB * (255 - kB) + kB * dF0) + 255) >> 8) + 255) >> 8;
+                const unsigned b = (uB * (255 - kB) + ((kB * (uF * (255 - kF) + kF * dB0) + 255) >> 8) + 255) >> 8;
+                v = (int)((a * (unsigned)(256 - t) + b * (unsigned)t) >> 8);
+            }
         } else { // MaskFun.cpp:417-490
             const dg_iv2 c0 = *(DG_GL const dg_iv2 *)(cl + 16 * (r0 + o) + 8), d0 = *(DG_GL const dg_iv2 *)(cl + 16 * (r0 + o + 1) + 8);
             const dg_iv2 c1 = *(DG_GL const dg_iv2 *)(cl + 16 * (r1 + o) + 8), d1 = *(DG_GL const dg_iv2 *)(cl + 16 * (r1 + o + 1) + 8);
@@ -217,11 +228,15 @@ __global__ __launch_bounds__(256) void flow_kernel(const FLParams *Pp, const FLJ
             const int vyFF = fl_vup(fl_hi(c0[1]) >> hy, fl_hi(c1[1]) >> hy, fl_hi(d0[1]) >> hy, fl_hi(d1[1]) >> hy, wt, wb, wl, wr, yLo, yHi);
             const int dFF = fl_fetch<T>(P, g, J.supL[p], X + ((vxFF * t) >> 8), Y + ((vyFF * t) >> 8));
             const int dBB = fl_fetch<T>(P, g, J.supR[p], X + ((vxBB * (256 - t)) >> 8), Y + ((vyBB * (256 - t)) >> 8));
-            const int mn = min(dB, dF), mx = max(dB, dF);
-            const int medBB = max(mn, min(dBB, mx)), medFF = max(mn, min(dFF, mx));
-            v = (((medBB * mF + dF * (255 - mF) + 255) >> 8) * (256 - t) + ((medFF * mB + dB * (255 - mB) + 255) >> 8) * t) >> 8;
+            if constexpr (sizeof(T) == 4) {
+                v = __float_as_int(mvx_flf_extra(t, __int_as_float(dF), __int_as_float(dB), __int_as_float(dFF), __int_as_float(dBB), mF, mB));
+            } else {
+                const int mn = min(dB, dF), mx = max(dB, dF);
+                const int medBB = max(mn, min(dBB, mx)), medFF = max(mn, min(dFF, mx));
+                v = (((medBB * mF + dF * (255 - mF) + 255) >> 8) * (256 - t) + ((medFF * mB + dB * (255 - mB) + 255) >> 8) * t) >> 8;
+            }
         }
-        out[i] = (int)(T)v;
+        if constexpr (sizeof(T) == 4) out[i] = v; else out[i] = (int)(T)v; // float: v holds the result's 32 bits
     }
     fl_store<T, CW>(dptr, out);
 }
@@ -299,25 +314,29 @@ static int flow_geometry(FLParams &P, int nWidthP[2], int nHeightP[2], const cha
     return MVX_OK;
 }
 
-// FlowInter / FlowFPS: the two-clip checks, then the padded geometry
-static int flow_common(mvx_flow *h, const char *name, int64_t arg1, int32_t arg2, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
-                       const mvx_super_info &si, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], char *err) {
+// FlowInter / FlowFPS: the two-clip checks, then the padded geometry.  The integer entries say the geometry's and the pitches' messages before
+// their frame-size checks (`sizes`); the float entries (flt) say the reference's messages in the reference's order first, then that the
+// super clip is no float one, then the library's own
+template <typename SIZES>
+static int flow_common(mvx_flow *h, const char *name, int64_t arg1, int32_t arg2, const mvx_analysis_data *bw, const mvx_analysis_data *fw, const mvx_super *sup,
+                       const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], bool flt, char *err, SIZES &&sizes) {
+    const mvx_super_info &si = sup->info;
     int64_t thscd1; int32_t thscd2;
     if (int rc = flow_pair_checks(name, arg1, arg2, &thscd1, &thscd2, bw, fw, err)) return rc;
+    if (flt) {
+        if (int rc = sizes()) return rc;
+        if (!sup->is_float) MVX_FAIL("%s: the float entry needs a float super clip.", name);
+    }
     if (int rc = flow_geometry(h->P, h->nWidthP, h->nHeightP, name, thscd1, thscd2, bw, si, super_pitch, clip_pitch, dst_pitch, true, err)) return rc;
+    if (!flt)
+        if (int rc = sizes()) return rc;
     h->delta = bw->nDeltaFrame;
     return MVX_OK;
 }
 
 // the luma / chroma launches of a kernel that produces CW consecutive samples per thread, the widest segment that divides the plane width (the
-// tables cover nWidthP >= the width): go(grid, first plane, planes per job, fps_type<T>, integral constant CW)
-template <typename F> static void flow_launches(const FLParams &P, int nframes, F &&go) {
-    fps_classes(P.pl, P.nplanes, nframes, [&](int p) { return fps_segment(P.bps, P.pl[p].W); }, [&](dim3 grid, int cw, int p0, int npl) {
-        fps_dispatch<1>(P.bps, cw, [&](auto t, auto w) { go(grid, p0, npl, t, w); });
-    });
-}
-
-// the same for Flow's kernels, which also run on float32 samples (T = float: segments of 4, 2 or 1 samples)
+// tables cover nWidthP >= the width): go(grid, first plane, planes per job, fps_type<T>, integral constant CW).  Every kernel of this file
+// that takes it also runs on float32 samples (T = float: segments of 4, 2 or 1 samples)
 template <typename F> static void fm_launches(const FLParams &P, int nframes, F &&go) {
     fps_classes(P.pl, P.nplanes, nframes, [&](int p) { return fps_segment(P.bps, P.pl[p].W); }, [&](dim3 grid, int cw, int p0, int npl) {
         auto one = [&](auto t, auto w) { go(grid, p0, npl, t, w); };
@@ -326,22 +345,21 @@ template <typename F> static void fm_launches(const FLParams &P, int nframes, F 
 }
 
 // MVFlowInter.c:473-678 mvflowinterCreate.  time and ml are float arguments there: time256 is formed in float, ml reaches the mask as (double)(float)ml.
-extern "C" __attribute__((visibility("default"))) int mvx_flowinter_create(const mvx_flowinter_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
-        const mvx_super *sup, int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flow **out, char *err) {
+// flt: the float entry (the super clip must be a float one; said after the frame-size check)
+static int flowinter_create(const mvx_flowinter_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw, const mvx_super *sup, int num_frames,
+                            const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flow **out, char *err, bool flt) {
     MVX_CREATE_BEGIN(out);
-    MVX_REFUSE_FLOAT(sup, "FlowInter");
+    if (!flt) MVX_REFUSE_FLOAT(sup, "FlowInter");
     const mvx_super_info &si = sup->info;
     const float time = (float)a->time, ml = (float)a->ml;
     const int blend = a->blend == MVX_UNSET ? 1 : !!a->blend;
     if (time < 0.0f || time > 100.0f) MVX_FAIL("FlowInter: time must be between 0 and 100 %% (inclusive).");
     if (ml <= 0.0f) MVX_FAIL("FlowInter: ml must be greater than 0.");
     mvx_flow *h = new mvx_flow();
-    int rc = flow_common(h, "FlowInter", a->thscd1, a->thscd2, bw, fw, si, super_pitch, clip_pitch, dst_pitch, err);
-    if (!rc && !mvx_super_fits(bw, si, false)) {
-        snprintf(err, MVX_ERRLEN, "FlowInter: wrong source or super clip frame size.");
-        mvx_set_error("%s", err);
-        rc = MVX_E_ARG;
-    }
+    const int rc = flow_common(h, "FlowInter", a->thscd1, a->thscd2, bw, fw, sup, super_pitch, clip_pitch, dst_pitch, flt, err, [&]() -> int {
+        if (!mvx_super_fits(bw, si, false)) MVX_FAIL("FlowInter: wrong source or super clip frame size.");
+        return MVX_OK;
+    });
     if (rc) { delete h; return rc; }
     FLParams &P = h->P;
     P.isFPS = 0; P.blend = blend; P.ml = (double)ml;
@@ -351,26 +369,35 @@ extern "C" __attribute__((visibility("default"))) int mvx_flowinter_create(const
     *out = h;
     return MVX_OK;
 }
+extern "C" __attribute__((visibility("default"))) int mvx_flowinter_create(const mvx_flowinter_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
+        const mvx_super *sup, int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flow **out, char *err) {
+    return flowinter_create(a, bw, fw, sup, num_frames, super_pitch, clip_pitch, dst_pitch, out, err, false);
+}
+extern "C" __attribute__((visibility("default"))) int mvx_flowinter_create_float(const mvx_flowinter_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
+        const mvx_super *sup, int num_frames, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3], mvx_flow **out, char *err) {
+    return flowinter_create(a, bw, fw, sup, num_frames, super_pitch, clip_pitch, dst_pitch, out, err, true);
+}
 
-// MVFlowFPS.c:565-802 mvflowfpsCreate
-extern "C" __attribute__((visibility("default"))) int mvx_flowfps_create(const mvx_flowfps_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
-        const mvx_super *sup, int num_frames, int64_t fps_num, int64_t fps_den, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3],
-        const ptrdiff_t dst_pitch[3], mvx_flow **out, char *err) {
+// MVFlowFPS.c:565-802 mvflowfpsCreate.  flt: the float entry, as above
+static int flowfps_create(const mvx_flowfps_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw, const mvx_super *sup, int num_frames,
+                          int64_t fps_num, int64_t fps_den, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3], const ptrdiff_t dst_pitch[3],
+                          mvx_flow **out, char *err, bool flt) {
     MVX_CREATE_BEGIN(out);
-    MVX_REFUSE_FLOAT(sup, "FlowFPS");
+    if (!flt) MVX_REFUSE_FLOAT(sup, "FlowFPS");
     const mvx_super_info &si = sup->info;
     const int mask = a->mask == MVX_UNSET ? 2 : a->mask;
     const int blend = a->blend == MVX_UNSET ? 1 : !!a->blend;
     if (mask < 0 || mask > 2) MVX_FAIL("FlowFPS: mask must be 0, 1, or 2.");
     if (a->ml <= 0.0) MVX_FAIL("FlowFPS: ml must be greater than 0.");
     mvx_flow *h = new mvx_flow();
-    int rc = flow_common(h, "FlowFPS", a->thscd1, a->thscd2, bw, fw, si, super_pitch, clip_pitch, dst_pitch, err);
-    auto fail = [&](const char *m) { snprintf(err, MVX_ERRLEN, "%s", m); mvx_set_error("%s", err); rc = MVX_E_ARG; };
-    if (!rc && (fps_num == 0 || fps_den == 0)) fail("FlowFPS: The input clip must have a frame rate. Invoke AssumeFPS if necessary.");
-    if (!rc && (bw->nWidth != si.width || bw->nHeight != si.height)) fail("FlowFPS: inconsistent source and vector frame size.");
-    if (!rc && !mvx_super_fits(bw, si, false)) fail("FlowFPS: wrong source or super clip frame size.");
-    if (!rc && !(bw->nWidth + bw->nHPadding * 2 == si.super_width && bw->nHeight + bw->nVPadding * 2 <= si.super_height))
-        fail("FlowFPS: inconsistent clips frame size! Incomprehensible error messages are the best, right?");
+    const int rc = flow_common(h, "FlowFPS", a->thscd1, a->thscd2, bw, fw, sup, super_pitch, clip_pitch, dst_pitch, flt, err, [&]() -> int {
+        if (fps_num == 0 || fps_den == 0) MVX_FAIL("FlowFPS: The input clip must have a frame rate. Invoke AssumeFPS if necessary.");
+        if (bw->nWidth != si.width || bw->nHeight != si.height) MVX_FAIL("FlowFPS: inconsistent source and vector frame size.");
+        if (!mvx_super_fits(bw, si, false)) MVX_FAIL("FlowFPS: wrong source or super clip frame size.");
+        if (!(bw->nWidth + bw->nHPadding * 2 == si.super_width && bw->nHeight + bw->nVPadding * 2 <= si.super_height))
+            MVX_FAIL("FlowFPS: inconsistent clips frame size! Incomprehensible error messages are the best, right?");
+        return MVX_OK;
+    });
     if (rc) { delete h; return rc; }
     FLParams &P = h->P;
     P.isFPS = 1; P.maskmode = mask; P.blend = blend; P.ml = a->ml;
@@ -378,6 +405,16 @@ extern "C" __attribute__((visibility("default"))) int mvx_flowfps_create(const m
     h->time256 = 0;
     *out = h;
     return MVX_OK;
+}
+extern "C" __attribute__((visibility("default"))) int mvx_flowfps_create(const mvx_flowfps_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
+        const mvx_super *sup, int num_frames, int64_t fps_num, int64_t fps_den, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3],
+        const ptrdiff_t dst_pitch[3], mvx_flow **out, char *err) {
+    return flowfps_create(a, bw, fw, sup, num_frames, fps_num, fps_den, super_pitch, clip_pitch, dst_pitch, out, err, false);
+}
+extern "C" __attribute__((visibility("default"))) int mvx_flowfps_create_float(const mvx_flowfps_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
+        const mvx_super *sup, int num_frames, int64_t fps_num, int64_t fps_den, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3],
+        const ptrdiff_t dst_pitch[3], mvx_flow **out, char *err) {
+    return flowfps_create(a, bw, fw, sup, num_frames, fps_num, fps_den, super_pitch, clip_pitch, dst_pitch, out, err, true);
 }
 
 extern "C" __attribute__((visibility("default"))) void mvx_flow_destroy(mvx_flow *h) { delete h; }
@@ -436,7 +473,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_flow_frames(mvx_flow *
     HIP_CHECK(hipMemsetAsync(h->dSmall.p, 0, n * 2 * cellsN * sizeof(int), st));
     hipLaunchKernelGGL(flow_occ_kernel, dim3((P.nBlk + 255) / 256, 2, nframes), dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p, h->dSmall.p);
     hipLaunchKernelGGL(flow_cells_kernel, dim3((unsigned)((cellsN + 255) / 256), nframes), dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p, h->dSmall.p, h->dCells.p, h->dMasks.p);
-    flow_launches(P, nframes, [&](dim3 grid, int p0, int npl, auto t, auto w) {
+    fm_launches(P, nframes, [&](dim3 grid, int p0, int npl, auto t, auto w) { // (float32 planes as well)
         hipLaunchKernelGGL((flow_kernel<typename decltype(t)::type, decltype(w)::value>), grid, dim3(256), 0, st, h->dP.p, h->dJobs.p, h->dFlags.p, h->dCells.p, h->dMasks.p, p0, npl);
     });
     HIP_CHECK(hipGetLastError());

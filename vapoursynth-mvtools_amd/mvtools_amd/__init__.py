@@ -384,6 +384,8 @@ def lib():
                                            P(C.c_ssize_t), P(C.c_void_p), C.c_char_p]
         L.mvx_flowfps_create.argtypes = [P(FlowFPSArgs), P(AnalysisData), P(AnalysisData), C.c_void_p, C.c_int, C.c_int64, C.c_int64, P(C.c_ssize_t),
                                          P(C.c_ssize_t), P(C.c_ssize_t), P(C.c_void_p), C.c_char_p]
+        L.mvx_flowinter_create_float.argtypes = L.mvx_flowinter_create.argtypes
+        L.mvx_flowfps_create_float.argtypes = L.mvx_flowfps_create.argtypes
         L.mvx_flow_destroy.argtypes = [C.c_void_p]
         L.mvx_flow_get_info.argtypes = [C.c_void_p, P(BlockFPSInfo)]
         L.mvx_flow_map.argtypes = [C.c_void_p, C.c_int, P(C.c_int), P(C.c_int), P(C.c_int)]
@@ -566,7 +568,7 @@ def plane_to_numpy(t, width, dtype):
 
 class Super(_Handle):
     """mv.Super -- MVSuper.c:140-275.  sample_float=True with bits=32: the super clip of a float32 clip (mvx_super_create_float) -- one level, no
-    shadow planes, planes of float32; DegrainN, and Compensate / CompensateN / BlockFPS / Flow / FlowBlur with sample_float=True, consume it."""
+    shadow planes, planes of float32; DegrainN, and Compensate / CompensateN / BlockFPS / Flow / FlowBlur / FlowInter / FlowFPS with sample_float=True, consume it."""
     _destroy = "mvx_super_destroy"
 
     def __init__(self, width, height, bits=8, subsampling=(1, 1), gray=False, hpad=None, vpad=None, pel=None, levels=None,
@@ -1167,8 +1169,10 @@ class _Flow(_Handle):
     """the engine both flow filters share (mvx_flow_*); subclasses create the handle"""
     _destroy = "mvx_flow_destroy"
 
-    def __init__(self, sup, num_frames, create):
+    def __init__(self, sup, num_frames, create, dst_pitch, sample_float):
         self.sup = sup
+        self.is_float = bool(sample_float)
+        self.dst_pitch = list(dst_pitch)
         self.h = C.c_void_p()
         err = C.create_string_buffer(ERRLEN)
         _check(create(C.byref(self.h), err), err)
@@ -1196,10 +1200,10 @@ class _Flow(_Handle):
 
     def jobs(self, ns, clip, supers, blobs_bw, blobs_fw, out=None):
         """the job table of run() and its output frames, without launching"""
-        _torch()
+        torch = _torch()
         n = len(ns)
         if out is None:
-            out = arena_frames(n, [tuple(p.shape) for p in clip[0]], clip[0][0].device, zero=False)
+            out = _flow_out(torch, self, n, clip[0])
         arr = (FlowJob * n)()
         last = self.in_frames - 1
         for k, fo in enumerate(ns):
@@ -1223,31 +1227,40 @@ class _Flow(_Handle):
 
 class FlowInter(_Flow):
     """mv.FlowInter(clip, super, mvbw, mvfw, time, ml, blend, thscd1, thscd2) -- MVFlowInter.c:473-678.  Output frame n lies `time` percent
-    of the way from input frame n to n + delta; `clip_pitch` is the row pitch of the clip's device planes (and of the output)."""
+    of the way from input frame n to n + delta; `clip_pitch` is the row pitch of the clip's device planes (and of the output).  sample_float=True
+    selects mvx_flowinter_create_float: a float super clip (Super(..., bits=32, sample_float=True)), float32 clip and output planes, vectors,
+    thresholds and ml from a search on an 8..16 bit copy; the vectors, masks and fetch positions are the integer filter's, the samples are
+    mixed in float32.  The keyword is explicit: a float super clip without it is refused."""
 
-    def __init__(self, sup, ad_bw, ad_fw, num_frames, clip_pitch, time=50.0, ml=100.0, blend=None, thscd1=None, thscd2=None, dst_pitch=None):
+    def __init__(self, sup, ad_bw, ad_fw, num_frames, clip_pitch, time=50.0, ml=100.0, blend=None, thscd1=None, thscd2=None, dst_pitch=None,
+                 sample_float=False):
         a = FlowInterArgs(float(time), float(ml), _u(blend), _u(thscd1), _u(thscd2))
         bw = AnalysisData.from_buffer_copy(bytes(ad_bw))
         fw = AnalysisData.from_buffer_copy(bytes(ad_fw))
-        super().__init__(sup, num_frames, lambda h, err: lib().mvx_flowinter_create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, int(num_frames), _pad3(sup.pitch),
-                                                                                     _pad3(clip_pitch), _pad3(dst_pitch or clip_pitch), h, err))
+        dst_pitch = list(dst_pitch or clip_pitch)
+        create = lib().mvx_flowinter_create_float if sample_float else lib().mvx_flowinter_create
+        super().__init__(sup, num_frames, lambda h, err: create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, int(num_frames), _pad3(sup.pitch),
+                                                                _pad3(clip_pitch), _pad3(dst_pitch), h, err), dst_pitch, sample_float)
 
 
 class FlowFPS(_Flow):
     """mv.FlowFPS(clip, super, mvbw, mvfw, num, den, mask, ml, blend, thscd1, thscd2) -- MVFlowFPS.c:565-878.  `fps_num / fps_den` is the
-    input clip's frame rate; `clip_pitch` the row pitch of its device planes (and of the output)."""
+    input clip's frame rate; `clip_pitch` the row pitch of its device planes (and of the output).  sample_float=True selects
+    mvx_flowfps_create_float, as in FlowInter: float super clip, float32 clip and output planes; frames at time256 0 / 256 are copied bit for bit."""
 
     def __init__(self, sup, ad_bw, ad_fw, num_frames, clip_pitch, fps_num=24, fps_den=1, num=None, den=None, mask=None, ml=100.0, blend=None, thscd1=None,
-                 thscd2=None, dst_pitch=None):
+                 thscd2=None, dst_pitch=None, sample_float=False):
         a = FlowFPSArgs(_u(num), _u(den), _u(mask), float(ml), _u(blend), _u(thscd1), _u(thscd2))
         bw = AnalysisData.from_buffer_copy(bytes(ad_bw))
         fw = AnalysisData.from_buffer_copy(bytes(ad_fw))
-        super().__init__(sup, num_frames, lambda h, err: lib().mvx_flowfps_create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, int(num_frames), int(fps_num),
-                                                                                   int(fps_den), _pad3(sup.pitch), _pad3(clip_pitch), _pad3(dst_pitch or clip_pitch), h, err))
+        dst_pitch = list(dst_pitch or clip_pitch)
+        create = lib().mvx_flowfps_create_float if sample_float else lib().mvx_flowfps_create
+        super().__init__(sup, num_frames, lambda h, err: create(C.byref(a), C.byref(bw), C.byref(fw), sup.h, int(num_frames), int(fps_num), int(fps_den),
+                                                                _pad3(sup.pitch), _pad3(clip_pitch), _pad3(dst_pitch), h, err), dst_pitch, sample_float)
 
 
 def _flow_out(torch, flt, n, frame):
-    """n output frames like the clip frame `frame` for Flow / FlowBlur: float32 planes of the filter's dst pitch for a float filter"""
+    """n output frames like the clip frame `frame` for the flow filters: float32 planes of the filter's dst pitch for a float filter"""
     if flt.is_float:
         return [[_out_plane(torch, frame[p].shape[0], flt.dst_pitch[p], True, frame[0].device) for p in range(flt.sup.nplanes)] for _ in range(n)]
     return arena_frames(n, [tuple(p.shape) for p in frame], frame[0].device, zero=False)
