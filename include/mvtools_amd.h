@@ -1251,6 +1251,13 @@ int mvx_debug_option(const char *name, int value);
  * 0 the serial lean kernel (or the general one), 2 the speculative kernel with one wave per chain, 3 its team form (the waves of a workgroup walk one
  * chain; the library's choice for launches that leave wave slots empty).  Tests use it to assert which build a batch took. */
 void mvx_debug_last_launch(int out[5]);
+/* test hook: the search's own table of level `level` (0 = finest) of a created mv.Analyse, no device involved.  out[0..10] = nBlkX, nBlkY, pel,
+ * padded width, padded height, hpad, vpad and the chroma plane's padded width, padded height, hpad, vpad; out[11..13] = byte offset of the level's
+ * first sub-pel plane inside super plane 0 / 1 / 2; out[14..16] = byte distance between its sub-pel planes; out[17..19] = the row pitches;
+ * out[20..22] = the shadow strides set by mvx_analyse_set_ref_shadow (the 8-bit layout has none for luma); out[23] = which search takes the
+ * default launch: 2 the lean / speculative kernels can, 1 the specialised general kernels, 0 the generic kernel (64-bit addresses).  Returns
+ * the number of levels, or MVX_E_ARG.  tests/test_search_addressing.py audits the kernels' 32-bit reference offsets against it. */
+int mvx_analyse_debug_level(const mvx_analyse *a, int level, int64_t out[24]);
 /* test hook of the dct 1..4 modes: the device transform and quantiser alone.  `a` was created with dct 1..4; `plane` is a device luma plane, block i
  * starts at sample xs[i] of row ys[i] (HOST arrays; the caller keeps the blocks inside the plane); out_bytes (device) receives blksize * blksizev
  * quantised coefficients per block, row-major, in the sample type.  Synchronises the stream. */

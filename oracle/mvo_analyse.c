@@ -1018,6 +1018,10 @@ int mvo_analyse_init(mvo_analyse *d, const mvo_analyse_args *a, const mvo_super 
     ad->nLvCount = levels > 0 ? levels : nLevelsMax + levels;
     if (ad->nLvCount < 1 || ad->nLvCount > nLevelsMax) FAIL("Analyse: invalid number of levels.");
     if (ad->nLvCount > d->nSuperLevels) FAIL("Analyse: super clip has %d levels. Analyse needs %d levels.", d->nSuperLevels, ad->nLvCount);
+    /* not the reference's: a block as large as the padded frame has an empty legal rectangle on the finest level, and the clipped predictors are
+     * then read in front of the plane itself (the reference does).  Refused here and by the library with the same words. */
+    if (ad->nWidth + 2 * ad->nHPadding <= ad->nBlkSizeX || ad->nHeight + 2 * ad->nVPadding <= ad->nBlkSizeY)
+        FAIL("Analyse: the padded frame must be larger than a block (no vector is legal otherwise).");
     if (d->nPelSearch <= 0) d->nPelSearch = ad->nPel;
     return 0;
 }

@@ -4,8 +4,8 @@ NaN payloads and signed zeros count.
 
 The rig is that of the other float filters: the float clip is float_clip of the integer clip, the vectors are searched on the integer copy and
 never on the float samples, crafted cases rewrite them on the host, and the float super frames are built on the GPU and asserted to be the Super
-restatement's (tests/super_float_ref.py) before the restatement runs on them.  The search is the oracle's, on the host, in every case: the same
-blobs as mv.Analyse's, and these tests are about what consumes them -- the only other GPU code they run is the float Super.  Every output frame
+restatement's (tests/super_float_ref.py) before the restatement runs on them.  The search is mv.Analyse's on the GPU, in every case, and is
+asserted to give the oracle's blobs -- the tiny unpadded clips included, whose search once faulted (tests/test_gpu_small_geometry.py).  Every output frame
 of a case is a job of ONE call, so copied and blended frames (FlowFPS at time256 0, clip ends, scene changes, invalid blobs) stand beside
 interpolated ones in every batch; tests/test_flow_float_cases.py holds the cases to their conditions on the CPU, and the same conditions are
 asserted here."""
@@ -33,7 +33,17 @@ class Rig:
         self.mv, self.c = mv, c
         self.q, self.floats = fx.clips(c)
         kw = fx.super_kwargs(c)
-        self.vectors = fx.edited(c, fx.search_oracle(oracle, c, self.q))
+        # the search runs on the GPU, on the integer copy (mv.Super + mv.Analyse), and must give the oracle's blobs
+        isup = mv.Super(c.w, c.h, c.bits, **kw)
+        isf = isup.build([mv.frame_to_device(f) for f in self.q])
+        searched = []
+        for (isb, delta), (oad, oblobs) in zip(fx.fields(c), fx.search_oracle(oracle, c, self.q)):
+            an = mv.Analyse(isup, num_frames=fx.NF, isb=isb, delta=delta, **fx.mc.analyse_kwargs(c))
+            refs = [fx.mc.reference(isb, delta, n) for n in range(fx.NF)]
+            blobs = [b.cpu().numpy() for b in an.run([(isf[n], isf[r] if r is not None else None) for n, r in enumerate(refs)])]
+            assert all(np.array_equal(b, o) for b, o in zip(blobs, oblobs)), "mv.Analyse differs from the oracle (isb %d, delta %d)" % (isb, delta)
+            searched.append((an.ad, blobs))
+        self.vectors = fx.edited(c, searched)
         self.blobs = [[torch.from_numpy(b).to("cuda") for b in blobs] for _, blobs in self.vectors]
         self.fsup = mv.Super(c.w, c.h, 32, sample_float=True, **kw)
         self.src = [mv.frame_to_device(f) for f in self.floats]

@@ -4,9 +4,9 @@ NaN payloads and signed zeros count.
 
 The rig is that of the other float filters: the float clip is float_clip of the integer clip, the vectors are searched on the integer copy and
 never on the float samples, crafted cases rewrite them on the host, and the float super frames are built on the GPU and asserted to be the Super
-restatement's (tests/super_float_ref.py) before the restatement runs on them.  The search is mv.Analyse's on the sizes the suite searches on the
-GPU elsewhere (96x64, 70x54) and the oracle's, on the host, for the two tiny clips (36x36 without padding, 35x30): the same blobs, and these
-tests are about what consumes them.  Every frame of a case's clip is a job of ONE call, so copied
+restatement's (tests/super_float_ref.py) before the restatement runs on them.  The search is mv.Analyse's on the GPU at every size, the two tiny clips
+(36x36 without padding, 35x30) included: the unpadded 36x36 search once ended in a memory fault, tests/test_gpu_small_geometry.py has what
+it was.  Every frame of a case's clip is a job of ONE call, so copied
 frames (clip ends, scene changes, invalid blobs) stand beside compensated ones in every batch; tests/test_flowmc_float_cases.py holds the cases
 to their conditions on the CPU, and the same conditions are asserted here from the vectors the GPU searched."""
 import numpy as np
@@ -21,7 +21,7 @@ from test_gpu_parity import dbg  # noqa: F401  (the fixture that puts a debug op
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-HOST_SEARCH = ((36, 36), (35, 30))
+HOST_SEARCH = ()  # (sizes searched by the oracle on the host instead: none -- the fault of the unpadded 36x36 search is fixed, tests/test_gpu_small_geometry.py)
 _rigs = {}
 
 

@@ -218,6 +218,10 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_create(const m
     if (ad.nLvCount < 1 || ad.nLvCount > nLevelsMax) MVX_FAIL("Analyse: invalid number of levels.");
     if (ad.nLvCount > si.levels) MVX_FAIL("Analyse: super clip has %d levels. Analyse needs %d levels.", si.levels, ad.nLvCount);
     if (ad.nLvCount > MVX_MAX_LEVELS) MVX_FAIL("Analyse: too many levels.");
+    // A block as large as the padded frame has an EMPTY legal rectangle on the finest level ((pw - blksize) << logPel vectors wide): the clipped predictors
+    // would then be read in front of the caller's plane itself.  The reference does read there; this library and its oracle refuse.
+    if (ad.nWidth + 2 * si.hpad <= ad.nBlkSizeX || ad.nHeight + 2 * si.vpad <= ad.nBlkSizeY)
+        MVX_FAIL("Analyse: the padded frame must be larger than a block (no vector is legal otherwise).");
     if (P.nPelSearch <= 0) P.nPelSearch = ad.nPel;
 
     // ---- device parameter block
@@ -286,6 +290,18 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_set_ref_shadow
 }
 extern "C" __attribute__((visibility("default"))) void mvx_analyse_get_data(const mvx_analyse *a, mvx_analysis_data *out) { *out = a->adOut; }
 extern "C" __attribute__((visibility("default"))) int mvx_analyse_blob_size(const mvx_analyse *a) { return a->P.blobSize; }
+// test hook: the level table the kernels read, as numbers (no device; creation touches none either)
+extern "C" __attribute__((visibility("default"))) int mvx_analyse_debug_level(const mvx_analyse *a, int level, int64_t out[24]) {
+    const AParams &P = a->P;
+    if (level < 0 || level >= P.nLevels) { mvx_set_error("mvx_analyse_debug_level: no such level"); return MVX_E_ARG; }
+    const ALevel &L = P.lv[level];
+    const int v[11] = { L.nBlkX, L.nBlkY, L.pel, L.pw, L.ph, L.hpad, L.vpad, L.cpw, L.cph, L.chpad, L.cvpad };
+    for (int i = 0; i < 11; i++) out[i] = v[i];
+    for (int p = 0; p < 3; p++) { out[11 + p] = L.off[p]; out[14 + p] = L.pstride[p]; out[17 + p] = P.pitch[p]; out[20 + p] = P.shadow[p]; }
+    const bool specialised = P.dctmode == 0 && P.xr == 2 && P.yr == 2 && P.blkX == P.blkY && (P.blkX == 16 || P.blkX == 8 || (P.blkX == 32 && P.bps == 2));
+    out[23] = mvx_fast_eligible(P) ? 2 : specialised ? 1 : 0;
+    return P.nLevels;
+}
 
 // Waves per chain the speculative kernel is launched with when the caller does not say (mvx_debug_option "team"): 0 = one wave per chain.
 // Measured r5 on cfg3 (profiles/r5_team_first_bench.txt, r5_team_batch_sweep.txt; ms per launch, one wave / team of 2 / 4 / 8):
@@ -523,10 +539,12 @@ extern "C" __attribute__((visibility("default"))) int mvx_analyse_frames(mvx_ana
     // 8-bit); with one chain per SIMD it costs 1 %
     const int syncEvery = wpe >= 2 ? 256 : 0;
     const ALaunch L = { njobs, ldsBytes, ldsRow, ldsHist, histBins, ldsNeed, simds, cpw, wpe, syncEvery, 0, 0, st, a->dP, S.d };
-    // the specialised kernels address the reference as "64-bit base + 32-bit offset inside the level's plane set" (all sub-pel planes)
+    // the specialised kernels address the reference as "64-bit base + 32-bit offset inside the level's plane set" (all sub-pel planes);
+    // the offsets count from mvx_ref_bias_bytes in front of the level (mvx_analyse_addr.h)
     bool off32 = true;
     for (int i = 0; i < P.nLevels; i++)
-        if ((long long)P.lv[i].pel * P.lv[i].pel * P.lv[i].pstride[0] >= 0xffffffffLL || (long long)P.lv[i].pel * P.lv[i].pel * P.lv[i].pstride[1] >= 0xffffffffLL) off32 = false;
+        if ((long long)P.lv[i].pel * P.lv[i].pel * P.lv[i].pstride[0] + mvx_ref_bias_bytes(P.pitch[0], P.bps) >= 0xffffffffLL ||
+            (long long)P.lv[i].pel * P.lv[i].pel * P.lv[i].pstride[1] + mvx_ref_bias_bytes(P.pitch[1], P.bps) >= 0xffffffffLL) off32 = false;
     int rc = (P.dctmode != 0 || !off32) ? 1 : P.bps == 1 ? mvx_analyse_launch_u8(P, L) : mvx_analyse_launch_u16(P, L); // specialised 4:2:0 geometries (SAD cost only)
     if (rc == 1 && mvx_is_fdct(P)) rc = mvx_analyse_launch_fdct(P, L);               // dct 1..4: their own generic build
     else if (rc == 1) rc = mvx_analyse_launch_any(P, L);                                // everything else

@@ -98,8 +98,9 @@ static inline bool mvx_fast_eligible(const AParams &P) {
             if (P.plevel == 1) v *= sc; else if (P.plevel == 2) v *= sc * sc;
             if (v < 0 || v > 0x7fffffffLL) return false;
         }
-        if ((long long)L.pel * L.pel * L.pstride[0] >= 0xffffffffLL || (long long)L.pel * L.pel * L.pstride[1] >= 0xffffffffLL) return false; // 32-bit plane offsets
-        if ((long long)L.pel * L.pel * L.pstride[0] + (P.bps == 1 ? 3 : 1) * P.shadow[0] >= 0xffffffffLL || 2 * (long long)L.pel * L.pel * L.pstride[1] + P.shadow[1] >= 0xffffffffLL) return false;
+        const long long biasY = mvx_ref_bias_bytes(P.pitch[0], P.bps), biasC = mvx_ref_bias_bytes(P.pitch[1], P.bps); // (offsets count from that far in front of the level)
+        if ((long long)L.pel * L.pel * L.pstride[0] + biasY >= 0xffffffffLL || (long long)L.pel * L.pel * L.pstride[1] + biasC >= 0xffffffffLL) return false; // 32-bit plane offsets
+        if ((long long)L.pel * L.pel * L.pstride[0] + biasY + (P.bps == 1 ? 3 : 1) * P.shadow[0] >= 0xffffffffLL || 2 * ((long long)L.pel * L.pel * L.pstride[1] + biasC) + P.shadow[1] >= 0xffffffffLL) return false;
         if ((L.pw << L.logPel) >= 30000 || (L.ph << L.logPel) >= 30000) return false; // vectors and their squared distances stay well inside int
     }
     return true;
@@ -157,21 +158,15 @@ template <int BPS, int BW, bool UV, int STREAM_MAX = MVX_STREAM_MAX> struct Fast
     // byte offsets of a candidate's reference block inside the level's plane set (PlaneOfBlocks.cpp:35-101, MVFrame.cpp:1707-1729)
     // With shadow copies the block at sample position x is read from copy k = x % (4 / BPS), where it starts at a dword-aligned
     // address (copy k = the plane shifted left by k samples): same samples, ~3.7x cheaper for the CU's texture path.
-    __device__ __forceinline__ static unsigned shadow_off(unsigned off, unsigned shadow) {
-        if (!shadow) return off;
-        const unsigned k = BPS == 2 ? (off >> 1) & 1u : off & 3u;
-        return (off & ~3u) + k * shadow;
-    }
+    // The arithmetic is mvx_analyse_addr.h's (one text with the host audit): offsets count from the level bases moved back by mvx_ref_bias_bytes
+    // (search_level), so the clipped predictors of an empty legal rectangle -- which lie left of / above the level's first sample -- have
+    // offsets that do not wrap.
+    __device__ __forceinline__ static unsigned shadow_off(unsigned off, unsigned shadow) { return mvx_shadow_off<BPS>(off, shadow); }
     __device__ __forceinline__ unsigned ref_luma_off(int vx, int vy) const {
-        const int ax = (x0 << logPel) + vx, ay = (y0 << logPel) + vy, m = pel - 1;
-        const unsigned idx = (unsigned)((ax & m) | ((ay & m) << logPel));
-        return shadow_off(idx * pstrideY + (unsigned)(ay >> logPel) * pitchY + (unsigned)(ax >> logPel) * BPS, shadowY);
+        return shadow_off(mvx_luma_off32<BPS>(x0, y0, vx, vy, pel, logPel, pstrideY, pitchY), shadowY);
     }
     __device__ __forceinline__ unsigned ref_chroma_off(int vx, int vy) const { // 4:2:0; block origins are even (even hpad/vpad/steps: checked by the host)
-        const int xb = vx < 0 ? 1 : 0, yb = vy < 0 ? 1 : 0;
-        const int ax = ((x0 >> 1) << logPel) + ((vx + xb) >> 1), ay = ((y0 >> 1) << logPel) + ((vy + yb) >> 1), m = pel - 1;
-        const unsigned idx = (unsigned)((ax & m) | ((ay & m) << logPel));
-        return idx * pstrideC + (unsigned)(ay >> logPel) * pitchC + (unsigned)(ax >> logPel) * BPS; // (in the UV plane: twice this, always dword-aligned)
+        return mvx_chroma_off32<BPS>(x0 >> 1, y0 >> 1, vx, vy, 1, 1, pel, logPel, pstrideC, pitchC); // (in the UV plane: twice this, always dword-aligned)
     }
 
     // ---- SAD of this lane's share of one plane region (T pieces of CB bytes, 1 << LOGC pieces per row) for a candidate that
@@ -204,16 +199,16 @@ template <int BPS, int BW, bool UV, int STREAM_MAX = MVX_STREAM_MAX> struct Fast
         if (T < GG) { // fewer pieces than lanes in the group: lanes s < T own one piece each
             if (s < T) {
                 const int row = s >> LOGC, xb = (s & (C - 1)) * CB;
-                acc = sad_piece<CB>(src + row * ROWB + xb, ld_ref<CB>(base + (off + (unsigned)row * refPitch + (unsigned)xb)), acc);
+                acc = sad_piece<CB>(src + row * ROWB + xb, ld_ref<CB>(base + mvx_piece_off32(off, row, refPitch, xb)), acc);
             }
             return acc;
         }
         constexpr int N = T >= GG ? T / GG : 1, NB = N < 4 ? N : 4; // pieces per lane, loads in flight
         if (GG >= C) { // the piece column is fixed per lane, rows advance by GG / C per piece
             const int row0 = s >> LOGC, xb = (s & (C - 1)) * CB;
-            unsigned po = off + (unsigned)row0 * refPitch + (unsigned)xb;
+            unsigned po = mvx_piece_off32(off, row0, refPitch, xb);
             const lds_u8 *sp = src + row0 * ROWB + xb;
-            const unsigned step = (unsigned)(GG >> LOGC) * refPitch;
+            const unsigned step = mvx_rows_step32(GG >> LOGC, refPitch);
             constexpr int lstep = (GG >> LOGC) * ROWB;
             // rolling window: NB loads in flight, the register of a consumed piece is reloaded at once (issuing NB, consuming NB,
             // issuing the next NB costs one memory round trip per batch)
@@ -255,7 +250,7 @@ template <int BPS, int BW, bool UV, int STREAM_MAX = MVX_STREAM_MAX> struct Fast
 #pragma unroll
                 for (int k = 0; k < NB; k++) {
                     const int t = s + (k0 + k) * GG, row = t >> LOGC, xb = (t & (C - 1)) * CB;
-                    r[k] = ld_ref<CB>(base + (off + (unsigned)row * refPitch + (unsigned)xb));
+                    r[k] = ld_ref<CB>(base + mvx_piece_off32(off, row, refPitch, xb));
                 }
 #pragma unroll
                 for (int k = 0; k < NB; k++) {
@@ -274,9 +269,9 @@ template <int BPS, int BW, bool UV, int STREAM_MAX = MVX_STREAM_MAX> struct Fast
         constexpr int GG = 1 << LOGG, CA = 1 << LOGCA, CB_ = 1 << LOGCB;
         constexpr int NA = TA / GG, NBB = TB / GG, NT = NA + NBB, W = NT < FAST_INFLIGHT ? NT : FAST_INFLIGHT;
         const int rowA = s >> LOGCA, xbA = (s & (CA - 1)) * CBA, rowB = s >> LOGCB, xbB = (s & (CB_ - 1)) * CBB;
-        unsigned poA = offA + (unsigned)rowA * pitchA + (unsigned)xbA, poB = offB + (unsigned)rowB * pitchB + (unsigned)xbB;
+        unsigned poA = mvx_piece_off32(offA, rowA, pitchA, xbA), poB = mvx_piece_off32(offB, rowB, pitchB, xbB);
         const lds_u8 *spA = srcA + rowA * ROWBA + xbA, *spB = srcB + rowB * ROWBB + xbB;
-        const unsigned stepA = (unsigned)(GG >> LOGCA) * pitchA, stepB = (unsigned)(GG >> LOGCB) * pitchB;
+        const unsigned stepA = mvx_rows_step32(GG >> LOGCA, pitchA), stepB = mvx_rows_step32(GG >> LOGCB, pitchB);
         constexpr int lstepA = (GG >> LOGCA) * ROWBA, lstepB = (GG >> LOGCB) * ROWBB;
         v4u r[W];
         // (the memory clobber keeps the loads in program order: the scheduler otherwise likes to issue the FIRST piece's load last,
@@ -745,13 +740,15 @@ template <int BPS, int BW, bool UV, int STREAM_MAX = MVX_STREAM_MAX> struct Fast
         // compiler cannot prove them invariant -- and a value that arrives in a vector register drags every address computed from
         // it into vector registers too)
         auto uptr = [](const unsigned char *p) { return (gl_u8 *)(unsigned long long)uni((long long)(unsigned long long)p); };
-        srcY = uptr(J.src[0] + L.off[0]); refY = uptr(J.ref[0] + L.off[0]);
-        srcU = uptr(J.src[1] + L.off[1]); refU = uptr(J.ref[1] + L.off[1]);
-        srcV = uptr(J.src[2] + L.off[2]); refV = uptr(J.ref[2] + L.off[2]);
+        // the reference bases lie mvx_ref_bias_bytes in front of the level: ref_luma_off / ref_chroma_off count from there (mvx_analyse_addr.h)
+        const long long biasY = mvx_ref_bias_bytes(P.pitch[0], BPS), biasC = mvx_ref_bias_bytes(P.pitch[1], BPS);
+        srcY = uptr(J.src[0] + L.off[0]); refY = uptr(J.ref[0] + L.off[0] - biasY);
+        srcU = uptr(J.src[1] + L.off[1]); refU = uptr(J.ref[1] + L.off[1] - biasC);
+        srcV = uptr(J.src[2] + L.off[2]); refV = uptr(J.ref[2] + L.off[2] - biasC);
         pitchY = (unsigned)uni((int)P.pitch[0]); pitchC = (unsigned)uni((int)P.pitch[1]); pstrideY = (unsigned)uni((int)L.pstride[0]); pstrideC = (unsigned)uni((int)L.pstride[1]);
         shadowY = (unsigned)uni((int)P.shadow[0]);
         // the UV plane mirrors the whole U / V buffers sample for sample: U byte offset o <-> UV byte offset 2 * o
-        srcUV = uptr(J.src[1] + P.shadow[1] + 2 * L.off[1]); refUV = uptr((J.ref[1] ? J.ref[1] : J.src[1]) + P.shadow[1] + 2 * L.off[1]);
+        srcUV = uptr(J.src[1] + P.shadow[1] + 2 * L.off[1]); refUV = uptr((J.ref[1] ? J.ref[1] : J.src[1]) + P.shadow[1] + 2 * L.off[1] - 2 * biasC);
         unsigned char *rec = (unsigned char *)(unsigned long long)uni((long long)(unsigned long long)(J.blob + L.blobOff));
         vectors = (GL_AS GVec *)(rec + 4);
         if (l == 0) *(int *)rec = 4 + nBlkX * nBlkY * 16; // pobWriteHeaderToArray :413-416

@@ -22,6 +22,7 @@
 #include <atomic>
 #include "mvx_common.h"
 #include "mvx_dct_block.h"
+#include "mvx_analyse_addr.h"
 
 enum { SearchOnetime, SearchNstep, SearchLogarithmic, SearchExhaustive, SearchHex2, SearchUMH, SearchHorizontal, SearchVertical };
 #define MOTION_USE_SIMD 1
@@ -423,20 +424,17 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
         return idx * pstrideC + (long long)(ay >> logPel) * pitchC + (long long)(ax >> logPel) * BPS;
     }
 
-    // 32-bit forms for the specialised kernels (the host checks that a level's plane set is smaller than 2 GiB): the loads then
-    // address "uniform 64-bit base + per-lane 32-bit offset" directly, which saves ~40 vector instructions of 64-bit address
-    // arithmetic per search round.  Offsets of inadmissible candidates may wrap; their lanes never load.
+    // 32-bit forms for the specialised kernels (the host checks that a level's plane set and the bias are smaller than 4 GiB): the loads
+    // then address "uniform 64-bit base + per-lane 32-bit offset" directly, which saves ~40 vector instructions of 64-bit address
+    // arithmetic per search round.  The offsets count from mvx_ref_bias_bytes in front of the level bases (eval_fixed; mvx_analyse_addr.h).  Offsets of candidates that fail
+    // vector_ok may wrap; their lanes never load.  CLIPPED predictors do load, legal or not: on a level whose legal rectangle is empty the
+    // clip lands a few samples left of / rows above the level's first sample -- the bias is what keeps those offsets from wrapping.
     __device__ __forceinline__ unsigned ref_luma_off32(int vx, int vy) const {
-        const int ax = (x0 << logPel) + vx, ay = (y0 << logPel) + vy, m = pel - 1;
-        const unsigned idx = (unsigned)((ax & m) | ((ay & m) << logPel));
-        return idx * (unsigned)pstrideY + (unsigned)(ay >> logPel) * (unsigned)pitchY + (unsigned)(ax >> logPel) * BPS;
+        return mvx_luma_off32<BPS>(x0, y0, vx, vy, pel, logPel, (unsigned)pstrideY, (unsigned)pitchY);
     }
     __device__ __forceinline__ unsigned ref_chroma_off32(int vx, int vy) const {
         const int lxr = GEO::BW ? (GEO::XR == 2 ? 1 : 0) : logxr, lyr = GEO::BW ? (GEO::YR == 2 ? 1 : 0) : logyr; // compile-time in the specialised kernels
-        const int xbias = (vx < 0) ? ((1 << lxr) - 1) : 0, ybias = (vy < 0) ? ((1 << lyr) - 1) : 0;
-        const int ax = (cx0 << logPel) + ((vx + xbias) >> lxr), ay = (cy0 << logPel) + ((vy + ybias) >> lyr), m = pel - 1;
-        const unsigned idx = (unsigned)((ax & m) | ((ay & m) << logPel));
-        return idx * (unsigned)pstrideC + (unsigned)(ay >> logPel) * (unsigned)pitchC + (unsigned)(ax >> logPel) * BPS;
+        return mvx_chroma_off32<BPS>(cx0, cy0, vx, vy, lxr, lyr, pel, logPel, (unsigned)pstrideC, (unsigned)pitchC);
     }
 
     // item t of the block -> LDS offset and (plane, row, byte offset in row)
@@ -596,7 +594,7 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
         if (T < G) { // fewer items than lanes in the group: lanes s < T own one item each
             if (s < T) {
                 const int row = s >> LOGC, xb = (s & (C - 1)) * CB;
-                acc = sad_chunk<BPS>(src + row * ROWB + xb, base + (off + (unsigned)row * refPitch + (unsigned)xb), CB, acc);
+                acc = sad_chunk<BPS>(src + row * ROWB + xb, base + mvx_piece_off32(off, row, refPitch, xb), CB, acc);
             }
             return acc;
         }
@@ -604,9 +602,9 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
         constexpr int NB = N < EV_NB ? N : EV_NB;  // loads in flight per batch
         if (G >= C) { // the chunk column is fixed per lane, rows advance by G / C per item
             const int row0 = s >> LOGC, xb = (s & (C - 1)) * CB;
-            const unsigned p = off + (unsigned)row0 * refPitch + (unsigned)xb;
+            const unsigned p = mvx_piece_off32(off, row0, refPitch, xb);
             const lds_u8 *sp = src + row0 * ROWB + xb;
-            const unsigned step = (unsigned)(G >> LOGC) * refPitch;
+            const unsigned step = mvx_rows_step32(G >> LOGC, refPitch);
             constexpr int lstep = (G >> LOGC) * ROWB;
             unsigned po = p; // running offset: one add per chunk (kept as a chain: as p + k * step the compiler multiplies per chunk)
 #pragma unroll 2
@@ -643,7 +641,7 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
 #pragma unroll
                 for (int k = 0; k < NB; k++) {
                     const int t = s + (k0 + k) * G, row = t >> LOGC, xb = (t & (C - 1)) * CB;
-                    gl_u8 *q = base + (off + (unsigned)row * refPitch + (unsigned)xb);
+                    gl_u8 *q = base + mvx_piece_off32(off, row, refPitch, xb);
                     if (CB == 16) { uv4 v = LDREF((GL_AS const uv4 *)q); r[k] = v4u{v[0], v[1], v[2], v[3]}; }
                     else if (CB == 8) { uv2 v = LDREF((GL_AS const uv2 *)q); r[k] = v4u{v[0], v[1], 0, 0}; }
                     else if (CB == 4) r[k] = v4u{LDREF((GL_AS const uv1 *)q), 0, 0, 0};
@@ -675,11 +673,12 @@ template <int BPS, typename GEO, int WPE = 1> struct Searcher {
         constexpr int LROWB = BW * BPS, LCB = LROWB < 16 ? LROWB : 16, LLOGC = ilog2c(LROWB / LCB), LT = BH * (LROWB / LCB);
         constexpr int CROWB = (BW / XR) * BPS, CCB = CROWB < 16 ? CROWB : 16, CLOGC = ilog2c(CROWB / CCB), CT = (BH / YR) * (CROWB / CCB);
         constexpr int UOFF = BH * LROWB, VOFF = UOFF + (BH / YR) * CROWB;
-        aL = region_fixed32<LOGG, LT, LLOGC, LCB, LROWB>(s, lds, refY, ref_luma_off32(vx, vy), (unsigned)pitchY, aL);
+        aL = region_fixed32<LOGG, LT, LLOGC, LCB, LROWB>(s, lds, refY - mvx_ref_bias_bytes(pitchY, BPS), ref_luma_off32(vx, vy), (unsigned)pitchY, aL);
         if (chroma) {
             const unsigned co = ref_chroma_off32(vx, vyc);
-            aC = region_fixed32<LOGG, CT, CLOGC, CCB, CROWB>(s, lds + UOFF, refU, co, (unsigned)pitchC, aC);
-            aC = region_fixed32<LOGG, CT, CLOGC, CCB, CROWB>(s, lds + VOFF, refV, co, (unsigned)pitchC, aC);
+            const long long biasC = mvx_ref_bias_bytes(pitchC, BPS);
+            aC = region_fixed32<LOGG, CT, CLOGC, CCB, CROWB>(s, lds + UOFF, refU - biasC, co, (unsigned)pitchC, aC);
+            aC = region_fixed32<LOGG, CT, CLOGC, CCB, CROWB>(s, lds + VOFF, refV - biasC, co, (unsigned)pitchC, aC);
         }
     }
 

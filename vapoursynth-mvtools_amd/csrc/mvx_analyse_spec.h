@@ -180,28 +180,23 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
     static constexpr bool STREAM_HEX = PG<2, 12>::OK && PG<LOGGP, 4>::OK, STREAM_EXH = PG<1, 12>::OK;
 
     __device__ __forceinline__ unsigned luma_off_at(int bx0, int vx, int vy) const { // ref_luma_off for a block at bx0 of this row
-        const int ax = (bx0 << logPel) + vx, ay = (y0 << logPel) + vy, m = pel - 1;
-        const unsigned idx = (unsigned)((ax & m) | ((ay & m) << logPel));
-        return F::shadow_off(idx * pstrideY + (unsigned)(ay >> logPel) * pitchY + (unsigned)(ax >> logPel) * BPS, shadowY);
+        return F::shadow_off(mvx_luma_off32<BPS>(bx0, y0, vx, vy, pel, logPel, pstrideY, pitchY), shadowY);
     }
     __device__ __forceinline__ unsigned chroma_off_at(int bx0, int vx, int vy) const {
-        const int xb = vx < 0 ? 1 : 0, yb = vy < 0 ? 1 : 0;
-        const int ax = ((bx0 >> 1) << logPel) + ((vx + xb) >> 1), ay = ((y0 >> 1) << logPel) + ((vy + yb) >> 1), m = pel - 1;
-        const unsigned idx = (unsigned)((ax & m) | ((ay & m) << logPel));
-        return idx * pstrideC + (unsigned)(ay >> logPel) * pitchC + (unsigned)(ax >> logPel) * BPS;
+        return mvx_chroma_off32<BPS>(bx0 >> 1, y0 >> 1, vx, vy, 1, 1, pel, logPel, pstrideC, pitchC);
     }
     // this lane's first luma / UV piece of candidate (vx, vy; chroma rows from vyc) of the block at bx0
     template <int LOGG, int WMAX> __device__ __forceinline__ void pass_start(int s, int bx0, int vx, int vy, int vyc, unsigned &oA, unsigned &oB) const {
         typedef PG<LOGG, WMAX> Q;
         const int rowA = s >> G::LLOGC, xbA = (s & (Q::CA - 1)) * G::LCB, rowB = s >> G::UVLOGC, xbB = (s & (Q::CB - 1)) * G::UVCB;
-        oA = luma_off_at(bx0, vx, vy) + (unsigned)rowA * pitchY + (unsigned)xbA;
-        oB = 2 * chroma_off_at(bx0, vx, vyc) + (unsigned)rowB * 2 * pitchC + (unsigned)xbB;
+        oA = mvx_piece_off32(luma_off_at(bx0, vx, vy), rowA, pitchY, xbA);
+        oB = mvx_piece_off32(2 * chroma_off_at(bx0, vx, vyc), rowB, 2 * pitchC, xbB);
     }
     template <int LOGG, int WMAX> __device__ __forceinline__ v4u pass_issue(Pass<LOGG, WMAX> &T, int piece) const {
         typedef PG<LOGG, WMAX> Q;
         v4u v;
-        if (piece < Q::NA) { v = F::template ld_ref<G::LCB>(refY + T.curA); T.curA += (unsigned)(Q::GG >> G::LLOGC) * pitchY; asm volatile("" : "+v"(T.curA) : : "memory"); }
-        else { v = F::template ld_ref<G::UVCB>(refUV + T.curB); T.curB += (unsigned)(Q::GG >> G::UVLOGC) * 2 * pitchC; asm volatile("" : "+v"(T.curB) : : "memory"); }
+        if (piece < Q::NA) { v = F::template ld_ref<G::LCB>(refY + T.curA); T.curA += mvx_rows_step32(Q::GG >> G::LLOGC, pitchY); asm volatile("" : "+v"(T.curA) : : "memory"); }
+        else { v = F::template ld_ref<G::UVCB>(refUV + T.curB); T.curB += mvx_rows_step32(Q::GG >> G::UVLOGC, 2 * pitchC); asm volatile("" : "+v"(T.curB) : : "memory"); }
         return v;
     }
     template <int LOGG, int WMAX> __device__ __forceinline__ void pass_prime(Pass<LOGG, WMAX> &T, unsigned oA, unsigned oB) const {
@@ -280,8 +275,8 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
     struct StripPass { v4u r[SW]; unsigned curA, curB, aL, aC; };
     __device__ __forceinline__ v4u strip_issue(StripPass &T, int piece) const {
         v4u v;
-        if (piece < SNA) { v = F::template ld_ref<COLB>(refY + T.curA); T.curA += pitchY; asm volatile("" : "+v"(T.curA) : : "memory"); }
-        else { v = F::template ld_ref<COLB>(refUV + T.curB); T.curB += 2 * pitchC; asm volatile("" : "+v"(T.curB) : : "memory"); }
+        if (piece < SNA) { v = F::template ld_ref<COLB>(refY + T.curA); T.curA += mvx_rows_step32(1, pitchY); asm volatile("" : "+v"(T.curA) : : "memory"); }
+        else { v = F::template ld_ref<COLB>(refUV + T.curB); T.curB += mvx_rows_step32(1, 2 * pitchC); asm volatile("" : "+v"(T.curB) : : "memory"); }
         return v;
     }
     __device__ __forceinline__ void strip_prime(StripPass &T, unsigned oA, unsigned oB) const {
@@ -328,8 +323,8 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
     struct Strip8 { v4u r[R8T]; unsigned curA, curB; unsigned aL[4], aC[4]; };
     __device__ __forceinline__ v4u strip8_issue(Strip8 &T, int piece) const { // (byte-aligned 16-byte loads: 8-bit samples sit anywhere)
         v4u v;
-        if (piece < R8A) { v = F::template ld_ref<16>(refY + T.curA); T.curA += pitchY; asm volatile("" : "+v"(T.curA) : : "memory"); }
-        else { v = F::template ld_ref<16>(refUV + T.curB); T.curB += 2 * pitchC; asm volatile("" : "+v"(T.curB) : : "memory"); }
+        if (piece < R8A) { v = F::template ld_ref<16>(refY + T.curA); T.curA += mvx_rows_step32(1, pitchY); asm volatile("" : "+v"(T.curA) : : "memory"); }
+        else { v = F::template ld_ref<16>(refUV + T.curB); T.curB += mvx_rows_step32(1, 2 * pitchC); asm volatile("" : "+v"(T.curB) : : "memory"); }
         return v;
     }
     __device__ __forceinline__ void strip8_prime(Strip8 &T, unsigned oA, unsigned oB) const {
@@ -389,12 +384,14 @@ template <int BPS, int BW, bool UV, int SWIN = 12, bool TEAM = false, bool SIDE 
         chroma = uni(P.chroma);
         pw = uni(L.pw); ph = uni(L.ph); hpad = uni(L.hpad); vpad = uni(L.vpad);
         auto uptr = [](const unsigned char *p) { return (gl_u8 *)(unsigned long long)uni((long long)(unsigned long long)p); };
-        srcY = uptr(J.src[0] + L.off[0]); refY = uptr(J.ref[0] + L.off[0]);
-        srcU = uptr(J.src[1] + L.off[1]); refU = uptr(J.ref[1] + L.off[1]);
-        srcV = uptr(J.src[2] + L.off[2]); refV = uptr(J.ref[2] + L.off[2]);
+        // the reference bases lie mvx_ref_bias_bytes in front of the level: luma_off_at / chroma_off_at count from there (mvx_analyse_addr.h)
+        const long long biasY = mvx_ref_bias_bytes(P.pitch[0], BPS), biasC = mvx_ref_bias_bytes(P.pitch[1], BPS);
+        srcY = uptr(J.src[0] + L.off[0]); refY = uptr(J.ref[0] + L.off[0] - biasY);
+        srcU = uptr(J.src[1] + L.off[1]); refU = uptr(J.ref[1] + L.off[1] - biasC);
+        srcV = uptr(J.src[2] + L.off[2]); refV = uptr(J.ref[2] + L.off[2] - biasC);
         pitchY = (unsigned)uni((int)P.pitch[0]); pitchC = (unsigned)uni((int)P.pitch[1]); pstrideY = (unsigned)uni((int)L.pstride[0]); pstrideC = (unsigned)uni((int)L.pstride[1]);
         shadowY = (unsigned)uni((int)P.shadow[0]);
-        srcUV = uptr(J.src[1] + P.shadow[1] + 2 * L.off[1]); refUV = uptr((J.ref[1] ? J.ref[1] : J.src[1]) + P.shadow[1] + 2 * L.off[1]);
+        srcUV = uptr(J.src[1] + P.shadow[1] + 2 * L.off[1]); refUV = uptr((J.ref[1] ? J.ref[1] : J.src[1]) + P.shadow[1] + 2 * L.off[1] - 2 * biasC);
         unsigned char *rec = (unsigned char *)(unsigned long long)uni((long long)(unsigned long long)(J.blob + L.blobOff));
         vectors = (GL_AS GVec *)(rec + 4);
         if (l == 0 && (!TEAM || role == 0)) *(int *)rec = 4 + nBlkX * nBlkY * 16; // pobWriteHeaderToArray :413-416

@@ -776,6 +776,10 @@ static int super_frames_impl(mvx_super *s, int nframes, const void *const *src, 
             const SuperPlaneGeom &g = A.g[p];
             Q.g[p] = g;
             int xa = (g.hpad + 4 + NS - 1) / NS * NS, last = g.w + g.hpad - NS - 4; // last: the largest X whose window ends inside the row
+            // The thread also produces sample X + NS, for the shifted copy (KIND 1), with the interior filter: that column must lie left of the
+            // last four of the padded row, where the sharp filters give way to the bilinear rule.  A padding of its own puts it there; without
+            // one (w + hpad - 4 == pw - 4) the last thread column is left to the tile kernel and the strip kernel's copy of what it wrote.
+            if (g.hpad == 0) last -= 1;
             int xb = last >= xa ? last / NS * NS + NS : xa;
             Q.XA[p] = A.XA[p] = xa; Q.XB[p] = A.XB[p] = xb;
             if (shadow_stride && p < 2) Q.shadow[p] = shadow_stride[p];

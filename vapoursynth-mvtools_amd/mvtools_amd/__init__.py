@@ -315,6 +315,7 @@ def lib():
         L.mvx_analyse_destroy.argtypes = [C.c_void_p]
         L.mvx_analyse_get_data.argtypes = [C.c_void_p, P(AnalysisData)]
         L.mvx_analyse_blob_size.argtypes = [C.c_void_p]
+        L.mvx_analyse_debug_level.argtypes = [C.c_void_p, C.c_int, P(C.c_int64)]
         L.mvx_analyse_frames.argtypes = [C.c_void_p, C.c_int, P(AnalyseJob), C.c_void_p]
         L.mvx_enable_dct_float.argtypes = [C.c_int]
         L.mvx_analyse_dct_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_ssize_t, C.c_int, P(C.c_int32), P(C.c_int32), C.c_void_p, C.c_void_p]
@@ -764,6 +765,17 @@ class Analyse(_Handle):
         stride = (self.blob_size + 255) // 256 * 256
         buf = torch.zeros((n, stride), dtype=torch.uint8, device=device)
         return [buf[i, :self.blob_size] for i in range(n)]
+
+    def levels(self):
+        """test hook (mvx_analyse_debug_level; no device): the search's level table, one list of 24 numbers per level, finest first"""
+        out = (C.c_int64 * 24)()
+        n = lib().mvx_analyse_debug_level(self.h, 0, out)
+        _check(min(n, 0))
+        rows = [list(out)]
+        for i in range(1, n):
+            _check(min(lib().mvx_analyse_debug_level(self.h, i, out), 0))
+            rows.append(list(out))
+        return rows
 
     def dct_blocks(self, plane, xs, ys):
         """test hook (dct 1..4): the device transform and quantiser on the blocks at sample xs[i], row ys[i] of a device luma plane (a uint8
