@@ -982,6 +982,24 @@ typedef struct mvx_depan_compensate mvx_depan_compensate;
 /* num_frames / data_frames: the lengths of clip and data.  Pitches in bytes, multiples of the sample size */
 int mvx_depan_compensate_create(const mvx_depan_compensate_args *args, const mvx_depan_clip *clip, int num_frames, int data_frames,
                                 const ptrdiff_t src_pitch[3], const ptrdiff_t dst_pitch[3], mvx_depan_compensate **out, char *err);
+/* DepanCompensate on a 32-bit float clip: the same arguments, checks and messages in the same order, but clip->bits must be 32 ("...: the
+ * float path takes a 32-bit float clip; ..." where the format message sits; the format message itself remains for the subsampling) and the
+ * pitches multiples of 4.  Touches no device.  The object is served by every mvx_depan_compensate_* function and
+ * mvx_depan_motion_to_transform, which are host arithmetic and the same for it; mvx_depan_compensate_frames reads and writes planes of
+ * float32.  info.bits is 32; info.pixel_max and info.border[] are 0: the border value is 0.0f for luma and 0.5f for chroma (the float
+ * Flow's hole values), and nothing is clamped.
+ * The float rule (csrc/mvx_depan_sample_float.h).  Where a sample comes from is the integer path's decision, value for
+ * value: the form, the chain, rowleft / hlow, the 32nds of bilinear and the 256ths of bicubic, mirror bits, blur runs, edge rows and
+ * columns, and divergences 2 and 5 above.  What is written there: a copy moves the sample's 32 bits (nearest, an unblurred mirror column,
+ * bicubic's edge columns, the bottom-row copies: NaN payloads, denormals and -0.0f survive); a blur run is the float32 sum in index order
+ * divided by its length; bilinear is ((32 - ky) * ((32 - kx) * a + kx * b) + ky * ((32 - kx) * c + kx * d)) * (1.0f / 1024) in all three
+ * forms; bicubic is four row sums and their column sum over the integer table, divided once by the product of the two coefficient totals,
+ * in all three forms (the translation form's sixteen truncated products are not restated); its near-edge rows are the reference's
+ * expression in float32 and the zoom form's bottom row is (a + b) * 0.5f.  Nothing is fused.
+ * The motion side has no float path and needs none: DepanAnalyse reads vectors, which come from the integer search on an 8..16 bit copy
+ * of the clip as everywhere in the float family, and DepanEstimate is given the same copy (its entries refuse a float clip). */
+int mvx_depan_compensate_create_float(const mvx_depan_compensate_args *args, const mvx_depan_clip *clip, int num_frames, int data_frames,
+                                      const ptrdiff_t src_pitch[3], const ptrdiff_t dst_pitch[3], mvx_depan_compensate **out, char *err);
 void mvx_depan_compensate_destroy(mvx_depan_compensate *h);
 void mvx_depan_compensate_get_info(const mvx_depan_compensate *h, mvx_depan_compensate_info *info);
 /* output frame ndest: returns 1 with *nsrc = ndest - intoffset, the clip frame to warp, and the motions of data frames *start + 1 ..
@@ -1049,7 +1067,9 @@ int mvx_depan_analyse_host(const mvx_depan_analyse *h, int n, const void *const 
  *      and 32 (:657-668), so every clip goes through its uint16_t branch: right for 9..16 bits, but an 8-bit clip is read as pairs of
  *      bytes over 2 * winx bytes per row, past the window and on the last rows past the frame.  The library reads bytes for 8 bits and
  *      words for 9..16 bits;
- *   9. float clips are refused at creation (only mv.Super's and mv.DegrainN's float entries have a float path);
+ *   9. float clips are refused at creation.  Of the Depan family only the two warps have float entries (mvx_depan_compensate_create_float,
+ *      mvx_depan_stabilise_create_float): a float pipeline estimates on the 8..16 bit copy its search reads -- the transform here is
+ *      single precision anyway -- and warps the float clip by the result;
  *  10. winx (after the halving for zoom) and winy must be powers of two from 8 to 8192, refused at creation otherwise; the automatic
  *      sizes always qualify on a frame of at least 8 x 8 (16 x 8 with zoom).  A window that leaves the frame -- the second window of
  *      zoommax != 1 starts at wleft + width / 2, which the reference does not check -- is refused too;
@@ -1202,6 +1222,14 @@ typedef struct mvx_depan_stabilise mvx_depan_stabilise;
 int mvx_depan_stabilise_create(const mvx_depan_stabilise_args *args, const mvx_depan_clip *clip, int num_frames, int data_frames,
                                int64_t fps_num, int64_t fps_den, const ptrdiff_t src_pitch[3], const ptrdiff_t dst_pitch[3],
                                mvx_depan_stabilise **out, char *err);
+/* DepanStabilise on a 32-bit float clip, as mvx_depan_compensate_create_float: the same arguments, checks and messages in the same order,
+ * clip->bits must be 32, pitches multiples of 4, no device touched; window, plan, get_info and get_windows serve the object unchanged and
+ * mvx_depan_stabilise_frames paints planes of float32 by the float rule.  info.bits is 32, info.pixel_max and info.border[] are 0 (the
+ * border value is 0.0f luma, 0.5f chroma).  A float sample may be negative, so the selection carries a painted flag per pass where the
+ * integer path reads "negative" as "not painted": a negative sample of the current frame is never overpainted by a fill source. */
+int mvx_depan_stabilise_create_float(const mvx_depan_stabilise_args *args, const mvx_depan_clip *clip, int num_frames, int data_frames,
+                                     int64_t fps_num, int64_t fps_den, const ptrdiff_t src_pitch[3], const ptrdiff_t dst_pitch[3],
+                                     mvx_depan_stabilise **out, char *err);
 void mvx_depan_stabilise_destroy(mvx_depan_stabilise *h);
 void mvx_depan_stabilise_get_info(const mvx_depan_stabilise *h, mvx_depan_stabilise_info *info);
 /* the cosine windows of :4140-4160, radius + 1 floats each (any may be NULL) */

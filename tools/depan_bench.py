@@ -11,6 +11,12 @@ the "fill, linear 16 B/thread" line of tools/micro/write_bw.hip's output in FILE
 recorded in profiles/r2_write_bw_microbench.txt.  The rotation form of nearest and bilinear includes its pre-pass.
 The estimator: milliseconds per frame of mvx_depan_analyse_host (no device) on real vectors of the 1080p clip at 8/4 and 16/8 blocks.
 Kernel times come from a separate rocprofv3 --kernel-trace --stats run of this script.
+
+    python tools/depan_bench.py --float [--jobs N] [--seconds S] [--rounds R] [--out FILE]
+
+The float path (sample_float=True) beside the 16-bit path at 1920 x 1080 4:2:0, in one process on the same transforms -- rotation for nearest
+and bilinear, zoom for bicubic -- alternating the two filters round by round: ms per frame and GB/s of the algorithm's bytes (one read and
+one write of every plane; the float path moves twice the 16-bit path's), median with the smallest and largest round.
 """
 import argparse
 import os
@@ -44,14 +50,65 @@ def ceiling(path):
     raise SystemExit("no 'fill, linear 16 B/thread' line in " + src)
 
 
+def timed(launch, seconds):
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    launch()
+    e1.record()
+    torch.cuda.synchronize()
+    reps = max(5, int(seconds * 1e3 / max(e0.elapsed_time(e1), 1e-3)))
+    e0.record()
+    for _ in range(reps):
+        launch()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def float_beside_16(a):
+    """mvx_depan_compensate_frames on a float clip and on a 16-bit clip, alternating"""
+    import torch
+    w, h = 1920, 1080
+    rng = np.random.default_rng(5)
+    shapes = ((h, w), (h // 2, w // 2), (h // 2, w // 2))
+    clips = {"16-bit": (mv.frame_to_device([rng.integers(0, 1 << 16, s).astype(np.uint16) for s in shapes]), dict(bits=16), 2),
+             "float ": (mv.frame_to_device([(rng.random(s, dtype=np.float32) * 1.5 - 0.25).astype(np.float32) for s in shapes]), dict(bits=32, sample_float=True), 4)}
+    lines = []
+    for sub, name, form in ((0, "nearest", "rotation"), (1, "bilinear", "rotation"), (2, "bicubic", "zoom")):
+        side = {}
+        for key, (src, kw, bps) in clips.items():
+            g = mv.DepanCompensate(w, h, src_pitch=[t.stride(0) for t in src], offset=1.0, subpixel=sub, mirror=15, **kw)
+            arr, out = g.jobs([src] * a.jobs, [FORMS[form]] * a.jobs)
+            g.launch(arr)  # warm-up of the timed shape: code objects and the handle's buffers
+            torch.cuda.synchronize()
+            side[key] = (g, arr, out, 2 * (w * h * 3 // 2) * bps, [])
+        for _ in range(a.rounds):
+            for key, (g, arr, out, moved, ms) in side.items():
+                ms.append(timed(lambda: g.launch(arr), a.seconds) / a.jobs)
+        for key, (g, arr, out, moved, ms) in side.items():
+            lo, med, hi = min(ms), float(np.median(ms)), max(ms)
+            lines.append("depan %-8s %-8s %s %dx%d 4:2:0  jobs/call=%d rounds=%d  %.4f ms/frame (%.4f .. %.4f)  moved=%d B/frame  %.1f GB/s (%.1f .. %.1f)" % (
+                name, form, key, w, h, a.jobs, a.rounds, med, lo, hi, moved, moved / med / 1e6, moved / hi / 1e6, moved / lo / 1e6))
+            print(lines[-1], flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     import torch
     ap = argparse.ArgumentParser()
     ap.add_argument("--jobs", type=int, default=16)
     ap.add_argument("--seconds", type=float, default=0.3)
+    ap.add_argument("--float", dest="float_", action="store_true", help="the float path beside the 16-bit path at 1080p, alternating")
+    ap.add_argument("--rounds", type=int, default=5, help="--float: rounds per filter")
+    ap.add_argument("--out", default=None, help="--float: also write the lines to this file")
     ap.add_argument("--write-bw", default=None, help="output of tools/micro/write_bw.hip from the same session")
     ap.add_argument("--shapes", default="1080p8,4k16")
     a = ap.parse_args()
+    if a.float_:
+        return float_beside_16(a)
     peak, origin = ceiling(a.write_bw)
     print("ceiling: %.2f TB/s (linear 16-byte fill, %s)" % (peak / 1e12, origin), flush=True)
     for shape in a.shapes.split(","):

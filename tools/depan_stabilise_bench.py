@@ -12,6 +12,13 @@ Per line: output frames per second, ms per call, and the share of output samples
 repeated until about S seconds have passed between the two events.  The rotation form includes its pre-pass.  Kernel times come from a
 separate rocprofv3 --kernel-trace --stats run of this script.
 The planner: microseconds per output frame of mvx_depan_stabilise_plan (no device) over a 200-frame track, both methods.
+
+    python tools/depan_stabilise_bench.py --float [--jobs N] [--seconds S] [--rounds R] [--out FILE]
+
+The float path (sample_float=True) beside the 16-bit path at 1920 x 1080 4:2:0 with prev = next = 1 (the border filled from both sources), in
+one process on the same plans -- rotation for nearest and bilinear, zoom for bicubic -- alternating the two filters round by round: ms per
+frame and GB/s of the algorithm's bytes (the current frame read once, the output written once; the fill sources' few per cent are not
+counted), median with the smallest and largest round.
 """
 import argparse
 import os
@@ -56,13 +63,54 @@ def timed(launch, seconds):
     return e0.elapsed_time(e1) / reps, reps
 
 
+def float_beside_16(a):
+    import torch
+    w, h = 1920, 1080
+    rng = np.random.default_rng(5)
+    shapes = ((h, w), (h // 2, w // 2), (h // 2, w // 2))
+    clips = {"16-bit": ([mv.frame_to_device([rng.integers(0, 1 << 16, s).astype(np.uint16) for s in shapes]) for _ in range(3)], dict(bits=16), 2),
+             "float ": ([mv.frame_to_device([(rng.random(s, dtype=np.float32) * 1.5 - 0.25).astype(np.float32) for s in shapes]) for _ in range(3)],
+                        dict(bits=32, sample_float=True), 4)}
+    lines = []
+    for sub, name, form in ((0, "nearest", "rotation"), (1, "bilinear", "rotation"), (2, "bicubic", "zoom")):
+        base = FORMS[form]
+        plan = mv.DepanStabilisePlan()
+        plan.tr[:] = shifted(base, 0.015 * w, 0.02 * h)
+        plan.next.used, plan.next.frame = 1, 1
+        plan.next.tr[:] = shifted(base, -0.01 * w, 0.01 * h)
+        plan.prev.used, plan.prev.frame = 1, 2
+        plan.prev.tr[:] = shifted(base, 0.0, -0.01 * h)
+        side = {}
+        for key, (src, kw, bps) in clips.items():
+            g = mv.DepanStabilise(w, h, src_pitch=[t.stride(0) for t in src[0]], subpixel=sub, mirror=15, prev=1, next=1, num_frames=3, **kw)
+            arr, out = g.jobs([plan] * a.jobs, [src[0]] * a.jobs, [src[2]] * a.jobs, [src[1]] * a.jobs)
+            g.launch(arr)  # warm-up of the timed shape
+            torch.cuda.synchronize()
+            side[key] = (g, arr, out, 2 * (w * h * 3 // 2) * bps, [])
+        for _ in range(a.rounds):
+            for key, (g, arr, out, moved, ms) in side.items():
+                ms.append(timed(lambda: g.launch(arr), a.seconds)[0] / a.jobs)
+        for key, (g, arr, out, moved, ms) in side.items():
+            lo, med, hi = min(ms), float(np.median(ms)), max(ms)
+            lines.append("stabilise %-8s %-8s prev=next=1 %s %dx%d 4:2:0  jobs/call=%d rounds=%d  %.4f ms/frame (%.4f .. %.4f)  moved=%d B/frame  %.1f GB/s (%.1f .. %.1f)" % (
+                name, form, key, w, h, a.jobs, a.rounds, med, lo, hi, moved, moved / med / 1e6, moved / hi / 1e6, moved / lo / 1e6))
+            print(lines[-1], flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--jobs", type=int, default=16)
     ap.add_argument("--seconds", type=float, default=0.3)
     ap.add_argument("--shapes", default="1080p8,4k16")
     ap.add_argument("--out", default=None, help="also write the lines to this file")
+    ap.add_argument("--float", dest="float_", action="store_true", help="the float path beside the 16-bit path at 1080p, alternating")
+    ap.add_argument("--rounds", type=int, default=5, help="--float: rounds per filter")
     a = ap.parse_args()
+    if a.float_:
+        return float_beside_16(a)
     lines = []
 
     def say(s):

@@ -22,6 +22,7 @@
 #include "mvx_depan_host.h"
 #include "mvx_depan_stab_host.h"
 #include "mvx_depan_sample.h"
+#include "mvx_depan_sample_float.h"
 
 __global__ __launch_bounds__(64) void depan_chain_kernel(const DCPlane *planes) {
     const DCPlane &P = planes[blockIdx.x];   // up to 16384 jobs x 3 planes x 3 sources: more than a grid's y extent holds
@@ -34,7 +35,8 @@ __global__ __launch_bounds__(256) void depan_warp_kernel(const DCPlane *planes, 
     const DCPlane *S = planes + (size_t)blockIdx.z * NSRC;
     const int row = blockIdx.x * 256 + threadIdx.x, h = blockIdx.y;
     if (row >= S[DS_CUR].W || h >= S[DS_CUR].H) return;
-    dc_store<T, SUB, NSRC>(S, C, h, row);
+    if constexpr (sizeof(T) == 4) dcf_store<SUB, NSRC>(S, C, h, row);   // a float clip: mvx_depan_sample_float.h
+    else dc_store<T, SUB, NSRC>(S, C, h, row);
 }
 
 // ------------------------------------------------------------------------------------------------ the engine both filters derive from
@@ -71,7 +73,8 @@ struct DepanWarp {
         if (T.chain) hipLaunchKernelGGL(depan_chain_kernel, dim3((unsigned)T.rec.size(), (unsigned)((G.H[0] + 63) / 64)), dim3(64), 0, st, dPlanes.p);
         const DCCommon C = { G.mirror, G.pixel_max, G.np };
         const dim3 grid((unsigned)((G.W[0] + 255) / 256), (unsigned)G.H[0], (unsigned)(T.rec.size() / NSRC)); // luma is the largest plane
-        if (G.bits > 8) dispatch<unsigned short, NSRC>(grid, st, C);
+        if (G.bits == 32) dispatch<float, NSRC>(grid, st, C);
+        else if (G.bits > 8) dispatch<unsigned short, NSRC>(grid, st, C);
         else dispatch<unsigned char, NSRC>(grid, st, C);
         HIP_CHECK(hipGetLastError());
         return MVX_OK;
@@ -81,17 +84,20 @@ struct DepanWarp {
 // The checks and fields the two creation functions share, at their place in each filter's order of messages: the reference's format
 // message; `refusal`, the filter's own message that the reference places next (nullptr: none applies); then the library's own checks
 // (divergences 3 and 4 of DepanCompensate in mvtools_amd.h).  Info: mvx_depan_compensate_info or mvx_depan_stabilise_info, zeroed but for
-// the shared fields.
-template <typename Info> static int depan_warp_create(const char *name, const mvx_depan_clip *clip, const char *refusal, const ptrdiff_t src_pitch[3],
+// the shared fields.  is_float: the *_create_float entries -- a 32-bit float clip; where the format message sits, one more for a clip that
+// is not 32-bit; samples of 4 bytes; info.pixel_max and info.border[] are 0 (the border is 0.0f luma and 0.5f chroma: G->border holds it in
+// halves for mvx_depan_sample_float.h).
+template <typename Info> static int depan_warp_create(const char *name, bool is_float, const mvx_depan_clip *clip, const char *refusal, const ptrdiff_t src_pitch[3],
         const ptrdiff_t dst_pitch[3], int subpixel, int mirror, int blur, DCClip *G, Info *I, char *err) {
-    if (clip->bits > 16 || clip->bits < 8 || clip->subsampling_w > 1 || clip->subsampling_h > 1 || clip->subsampling_w < 0 || clip->subsampling_h < 0 ||
+    if (is_float && clip->bits != 32) MVX_FAIL("%s: the float path takes a 32-bit float clip; create an 8..16 bit clip's filter with the integer entry.", name);
+    if ((!is_float && (clip->bits > 16 || clip->bits < 8)) || clip->subsampling_w > 1 || clip->subsampling_h > 1 || clip->subsampling_w < 0 || clip->subsampling_h < 0 ||
         (clip->subsampling_w == 0 && clip->subsampling_h == 1))
         MVX_FAIL("%s: clip must have constant format and dimensions, integer sample type, bit depth up to 16, and it must be Gray, 420, 422, or 444, and not RGB.", name);
     if (refusal) MVX_FAIL("%s", refusal);
     const int ssw = clip->gray ? 0 : clip->subsampling_w, ssh = clip->gray ? 0 : clip->subsampling_h;
     if (clip->width < (2 << ssw) || clip->height < (2 << ssh) || clip->width > 32767 || clip->height > 32767)
         MVX_FAIL("%s: every plane must be at least 2 samples wide and 2 high, and the frame at most 32767 x 32767.", name);
-    const int np = clip->gray ? 1 : 3, bps = clip->bits > 8 ? 2 : 1;
+    const int np = clip->gray ? 1 : 3, bps = is_float ? 4 : clip->bits > 8 ? 2 : 1;
     for (int p = 0; p < np; p++)
         if (src_pitch[p] % bps || dst_pitch[p] % bps || src_pitch[p] < (clip->width >> (p ? ssw : 0)) * bps || dst_pitch[p] < (clip->width >> (p ? ssw : 0)) * bps)
             MVX_FAIL("%s: pitches must hold a row of their plane and be multiples of the sample size.", name);
@@ -99,10 +105,11 @@ template <typename Info> static int depan_warp_create(const char *name, const mv
     memset(I, 0, sizeof(*I));
     I->width = clip->width; I->height = clip->height;
     I->bits = G->bits = clip->bits; I->num_planes = G->np = np; I->subsampling_w = G->ssw = ssw; I->subsampling_h = G->ssh = ssh;
-    I->subpixel = G->subpixel = subpixel; I->mirror = G->mirror = mirror; I->pixel_max = G->pixel_max = (1 << clip->bits) - 1;
+    I->subpixel = G->subpixel = subpixel; I->mirror = G->mirror = mirror; I->pixel_max = G->pixel_max = is_float ? 0 : (1 << clip->bits) - 1;
     for (int p = 0; p < 3; p++) {
         I->plane_width[p] = G->W[p] = clip->width >> (p ? ssw : 0); I->plane_height[p] = G->H[p] = clip->height >> (p ? ssh : 0);
-        I->border[p] = G->border[p] = p ? 1 << (clip->bits - 1) : 0;             // :2683 / :3362-3363, :3424
+        I->border[p] = is_float ? 0 : p ? 1 << (clip->bits - 1) : 0;             // :2683 / :3362-3363, :3424
+        G->border[p] = is_float ? (p ? 1 : 0) : I->border[p];
         I->blur[p] = G->blur[p] = p && ssw == 1 ? blur / 2 : blur;                // :2684,2692,2698 / :3371,3377
         G->spitch[p] = p < np ? src_pitch[p] : 0; G->dpitch[p] = p < np ? dst_pitch[p] : 0;
     }
@@ -118,7 +125,7 @@ struct mvx_depan_compensate : DepanWarp {
 };
 
 // MVDepan.cpp:2750-2881 depanCompensateCreate
-extern "C" __attribute__((visibility("default"))) int mvx_depan_compensate_create(const mvx_depan_compensate_args *a, const mvx_depan_clip *clip, int num_frames, int data_frames,
+static int depan_compensate_create(bool is_float, const mvx_depan_compensate_args *a, const mvx_depan_clip *clip, int num_frames, int data_frames,
         const ptrdiff_t src_pitch[3], const ptrdiff_t dst_pitch[3], mvx_depan_compensate **out, char *err) {
     MVX_CREATE_BEGIN(out);
     const float offset = (float)a->offset, pixaspect = (float)a->pixaspect;
@@ -133,7 +140,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_depan_compensate_creat
     if (blur < 0) MVX_FAIL("DepanCompensate: blur must not be negative.");
     DCClip G;
     mvx_depan_compensate_info I;
-    if (int rc = depan_warp_create("DepanCompensate", clip, num_frames > data_frames ? "DepanCompensate: data must have at least as many frames as clip." : nullptr,
+    if (int rc = depan_warp_create("DepanCompensate", is_float, clip, num_frames > data_frames ? "DepanCompensate: data must have at least as many frames as clip." : nullptr,
                                    src_pitch, dst_pitch, subpixel, mirror, blur, &G, &I, err)) return rc;
 
     mvx_depan_compensate *h = new mvx_depan_compensate();
@@ -146,6 +153,15 @@ extern "C" __attribute__((visibility("default"))) int mvx_depan_compensate_creat
     h->info = I;
     *out = h;
     return MVX_OK;
+}
+extern "C" __attribute__((visibility("default"))) int mvx_depan_compensate_create(const mvx_depan_compensate_args *a, const mvx_depan_clip *clip, int num_frames, int data_frames,
+        const ptrdiff_t src_pitch[3], const ptrdiff_t dst_pitch[3], mvx_depan_compensate **out, char *err) {
+    return depan_compensate_create(false, a, clip, num_frames, data_frames, src_pitch, dst_pitch, out, err);
+}
+// the same filter on a 32-bit float clip (mvx_depan_sample_float.h); no device is touched
+extern "C" __attribute__((visibility("default"))) int mvx_depan_compensate_create_float(const mvx_depan_compensate_args *a, const mvx_depan_clip *clip, int num_frames, int data_frames,
+        const ptrdiff_t src_pitch[3], const ptrdiff_t dst_pitch[3], mvx_depan_compensate **out, char *err) {
+    return depan_compensate_create(true, a, clip, num_frames, data_frames, src_pitch, dst_pitch, out, err);
 }
 extern "C" __attribute__((visibility("default"))) void mvx_depan_compensate_destroy(mvx_depan_compensate *h) { delete h; }
 extern "C" __attribute__((visibility("default"))) void mvx_depan_compensate_get_info(const mvx_depan_compensate *h, mvx_depan_compensate_info *info) { *info = h->info; }
@@ -201,7 +217,7 @@ static float ds_arg(double v, float dflt) { return v == (double)MVX_UNSET ? dflt
 static int ds_arg(int32_t v, int dflt) { return v == MVX_UNSET ? dflt : v; }
 
 // MVDepan.cpp:3909-4163 depanStabiliseCreate
-extern "C" __attribute__((visibility("default"))) int mvx_depan_stabilise_create(const mvx_depan_stabilise_args *a, const mvx_depan_clip *clip, int num_frames, int data_frames,
+static int depan_stabilise_create(bool is_float, const mvx_depan_stabilise_args *a, const mvx_depan_clip *clip, int num_frames, int data_frames,
         int64_t fps_num, int64_t fps_den, const ptrdiff_t src_pitch[3], const ptrdiff_t dst_pitch[3], mvx_depan_stabilise **out, char *err) {
     MVX_CREATE_BEGIN(out);
     DepanStabParams P;
@@ -220,7 +236,7 @@ extern "C" __attribute__((visibility("default"))) int mvx_depan_stabilise_create
     if (P.method < 0 || P.method > 1) MVX_FAIL("DepanStabilise: method must be between 0 and 1 (inclusive).");
     DCClip G;
     mvx_depan_stabilise_info I;
-    if (int rc = depan_warp_create("DepanStabilise", clip, fps_num == 0 || fps_den == 0 ? "DepanStabilise: clip must have known frame rate."
+    if (int rc = depan_warp_create("DepanStabilise", is_float, clip, fps_num == 0 || fps_den == 0 ? "DepanStabilise: clip must have known frame rate."
                                    : num_frames > data_frames ? "DepanStabilise: data must have at least as many frames as clip." : nullptr,
                                    src_pitch, dst_pitch, P.subpixel, P.mirror, P.blur, &G, &I, err)) return rc;
     // the library's own checks (divergence 3 of DepanStabilise in mvtools_amd.h)
@@ -241,6 +257,15 @@ extern "C" __attribute__((visibility("default"))) int mvx_depan_stabilise_create
     h->info = I;
     *out = h;
     return MVX_OK;
+}
+extern "C" __attribute__((visibility("default"))) int mvx_depan_stabilise_create(const mvx_depan_stabilise_args *a, const mvx_depan_clip *clip, int num_frames, int data_frames,
+        int64_t fps_num, int64_t fps_den, const ptrdiff_t src_pitch[3], const ptrdiff_t dst_pitch[3], mvx_depan_stabilise **out, char *err) {
+    return depan_stabilise_create(false, a, clip, num_frames, data_frames, fps_num, fps_den, src_pitch, dst_pitch, out, err);
+}
+// the same filter on a 32-bit float clip (mvx_depan_sample_float.h); no device is touched
+extern "C" __attribute__((visibility("default"))) int mvx_depan_stabilise_create_float(const mvx_depan_stabilise_args *a, const mvx_depan_clip *clip, int num_frames, int data_frames,
+        int64_t fps_num, int64_t fps_den, const ptrdiff_t src_pitch[3], const ptrdiff_t dst_pitch[3], mvx_depan_stabilise **out, char *err) {
+    return depan_stabilise_create(true, a, clip, num_frames, data_frames, fps_num, fps_den, src_pitch, dst_pitch, out, err);
 }
 extern "C" __attribute__((visibility("default"))) void mvx_depan_stabilise_destroy(mvx_depan_stabilise *h) { delete h; }
 extern "C" __attribute__((visibility("default"))) void mvx_depan_stabilise_get_info(const mvx_depan_stabilise *h, mvx_depan_stabilise_info *info) { *info = h->info; }

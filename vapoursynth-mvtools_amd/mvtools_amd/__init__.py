@@ -410,6 +410,7 @@ def lib():
         L.mvx_mask_get_info.restype = None
         L.mvx_mask_frames.argtypes = [C.c_void_p, C.c_int, P(MaskJob), C.c_void_p]
         L.mvx_depan_compensate_create.argtypes = [P(DepanCompensateArgs), P(DepanClip), C.c_int, C.c_int, P(C.c_ssize_t), P(C.c_ssize_t), P(C.c_void_p), C.c_char_p]
+        L.mvx_depan_compensate_create_float.argtypes = L.mvx_depan_compensate_create.argtypes
         L.mvx_depan_compensate_destroy.argtypes = [C.c_void_p]
         L.mvx_depan_compensate_get_info.argtypes = [C.c_void_p, P(DepanCompensateInfo)]
         L.mvx_depan_compensate_get_info.restype = None
@@ -418,6 +419,7 @@ def lib():
         L.mvx_depan_compensate_frames.argtypes = [C.c_void_p, C.c_int, P(DepanCompensateJob), C.c_void_p]
         L.mvx_depan_stabilise_create.argtypes = [P(DepanStabiliseArgs), P(DepanClip), C.c_int, C.c_int, C.c_int64, C.c_int64, P(C.c_ssize_t), P(C.c_ssize_t),
                                                  P(C.c_void_p), C.c_char_p]
+        L.mvx_depan_stabilise_create_float.argtypes = L.mvx_depan_stabilise_create.argtypes
         L.mvx_depan_stabilise_destroy.argtypes = [C.c_void_p]
         L.mvx_depan_stabilise_get_info.argtypes = [C.c_void_p, P(DepanStabiliseInfo)]
         L.mvx_depan_stabilise_get_info.restype = None
@@ -1607,23 +1609,26 @@ class DepanEstimate(_Handle):
 
 class _DepanWarp(_Handle):
     """What DepanCompensate and DepanStabilise share: the clip's format, the default pitches (rows rounded up to 256 bytes), the handle and its
-    info struct, the output arena and the launch of a job array.  _name: the stem of the library's functions; _info: the info struct's class."""
+    info struct, the output arena and the launch of a job array.  _name: the stem of the library's functions; _info: the info struct's class.
+    sample_float=True with bits=32 selects the *_create_float entry: planes of float32 (4-byte samples in the default pitches), the border
+    0.0f luma / 0.5f chroma, nothing clamped; transforms, plans and jobs are the same host arithmetic."""
     _name = _info = None
 
-    def _create(self, args, width, height, bits, subsampling, gray, src_pitch, dst_pitch, num_frames, data_frames, *extra):
+    def _create(self, sample_float, args, width, height, bits, subsampling, gray, src_pitch, dst_pitch, num_frames, data_frames, *extra):
         """extra: the arguments of the creation function between data_frames and the pitches"""
         c = DepanClip(int(width), int(height), int(bits), int(subsampling[0]), int(subsampling[1]), int(bool(gray)))
         sw = 0 if gray else subsampling[0]
-        bps = 2 if bits > 8 else 1
+        self.is_float = bool(sample_float)
+        bps = 4 if self.is_float else 2 if bits > 8 else 1
         if dst_pitch is None:
             dst_pitch = [((max(int(width) >> s, 1) * bps + 255) // 256) * 256 for s in (0, sw, sw)]
         if src_pitch is None:
             src_pitch = dst_pitch
         self.h = C.c_void_p()
         self.pitch = list(dst_pitch)
-        self.dtype = np.uint16 if bits > 8 else np.uint8
+        self.dtype = np.float32 if self.is_float else np.uint16 if bits > 8 else np.uint8
         err = C.create_string_buffer(ERRLEN)
-        _check(getattr(lib(), self._name + "_create")(C.byref(args), C.byref(c), int(num_frames), int(num_frames if data_frames is None else data_frames), *extra,
+        _check(getattr(lib(), self._name + ("_create_float" if self.is_float else "_create"))(C.byref(args), C.byref(c), int(num_frames), int(num_frames if data_frames is None else data_frames), *extra,
                                                       _pad3(src_pitch), _pad3(dst_pitch), C.byref(self.h), err), err)
         self.info = self._info()
         getattr(lib(), self._name + "_get_info")(self.h, C.byref(self.info))
@@ -1639,13 +1644,14 @@ class _DepanWarp(_Handle):
 class DepanCompensate(_DepanWarp):
     """mv.DepanCompensate(clip, data, offset, subpixel, pixaspect, matchfields, mirror, blur, info, fields, tff) -- MVDepan.cpp:2750-2881.
     map(n) says which clip frame to warp and which data frames' motions to sum, transform(motions, ...) sums them (host arithmetic), and a
-    job is (src planes, summed transform).  `src_pitch` / `dst_pitch`: row pitches in bytes of the device planes."""
+    job is (src planes, summed transform).  `src_pitch` / `dst_pitch`: row pitches in bytes of the device planes.  sample_float=True with bits=32
+    selects mvx_depan_compensate_create_float: float32 planes in and out; the transforms come from motion found on an 8..16 bit copy."""
     _destroy, _name, _info = "mvx_depan_compensate_destroy", "mvx_depan_compensate", DepanCompensateInfo
 
     def __init__(self, width, height, bits=8, subsampling=(1, 1), gray=False, src_pitch=None, dst_pitch=None, offset=0.0, subpixel=None, pixaspect=1.0,
-                 matchfields=None, mirror=None, blur=None, fields=None, tff=None, num_frames=1 << 30, data_frames=None):
+                 matchfields=None, mirror=None, blur=None, fields=None, tff=None, num_frames=1 << 30, data_frames=None, sample_float=False):
         a = DepanCompensateArgs(float(offset), _u(subpixel), float(pixaspect), _u(matchfields), _u(mirror), _u(blur), _u(fields), _u(tff))
-        self._create(a, width, height, bits, subsampling, gray, src_pitch, dst_pitch, num_frames, data_frames)
+        self._create(sample_float, a, width, height, bits, subsampling, gray, src_pitch, dst_pitch, num_frames, data_frames)
 
     def map(self, n):
         """(nsrc, start, end) of output frame n: warp clip frame nsrc by the motions of data frames start + 1 .. end; None: return clip frame n"""
@@ -1689,17 +1695,18 @@ class DepanStabilise(_DepanWarp):
     """mv.DepanStabilise(clip, data, cutoff, damping, initzoom, addzoom, prev, next, mirror, blur, dxmax, dymax, zoommax, rotmax, subpixel, pixaspect,
     fitlast, tzoom, info, method, fields) -- MVDepan.cpp:3909-4208.  window(n) names the data frames whose motion plan(n, motions) reads (host
     arithmetic) and the clip frames its sources lie among; a job is a plan with the planes of the current, prev and next source frames; all jobs
-    of a call are one fused launch.  `src_pitch` / `dst_pitch`: row pitches in bytes of the device planes.  Float arguments: None -> the default."""
+    of a call are one fused launch.  `src_pitch` / `dst_pitch`: row pitches in bytes of the device planes.  Float arguments: None -> the default.
+    sample_float=True with bits=32 selects mvx_depan_stabilise_create_float: float32 planes in and out; the motions come from an 8..16 bit copy."""
     _destroy, _name, _info = "mvx_depan_stabilise_destroy", "mvx_depan_stabilise", DepanStabiliseInfo
 
     def __init__(self, width, height, bits=8, subsampling=(1, 1), gray=False, src_pitch=None, dst_pitch=None, fps=(25, 1), num_frames=1 << 30, cutoff=None,
                  damping=None, initzoom=None, addzoom=None, prev=None, next=None, mirror=None, blur=None, dxmax=None, dymax=None, zoommax=None, rotmax=None,
-                 subpixel=None, pixaspect=None, fitlast=None, tzoom=None, method=None, fields=None, data_frames=None):
+                 subpixel=None, pixaspect=None, fitlast=None, tzoom=None, method=None, fields=None, data_frames=None, sample_float=False):
         d = lambda v: float(UNSET) if v is None else float(v)
         a = DepanStabiliseArgs(d(cutoff), d(damping), d(initzoom), d(dxmax), d(dymax), d(zoommax), d(rotmax), d(pixaspect), d(tzoom), _u(addzoom), _u(prev),
                                _u(next), _u(mirror), _u(blur), _u(subpixel), _u(fitlast), _u(method), _u(fields))
         self.num_frames = int(num_frames)
-        self._create(a, width, height, bits, subsampling, gray, src_pitch, dst_pitch, num_frames, data_frames, int(fps[0]), int(fps[1]))
+        self._create(sample_float, a, width, height, bits, subsampling, gray, src_pitch, dst_pitch, num_frames, data_frames, int(fps[0]), int(fps[1]))
 
     def windows(self):
         """the cosine windows wint, winrz, winfz: radius + 1 float32 each"""
