@@ -3,7 +3,7 @@
 The reference accepts them in every filter (MVAnalyse.c:463-517, MVDegrains.cpp:161-162,342,693,776, MVCompensate.c:128-129,543,
 MVBlockFPS.c:326-327, MVRecalculate.c:370-400): the chroma block is blk / xRatioUV by blk / yRatioUV, a Gray clip has one plane and
 searches luma only.  In the library these formats take the general search kernel (mvx_fast_eligible wants xr == yr == 2) and the
-run-time chroma ratios of degrain_kernel / cn_cell_kernel (Compensate) / blockfps_kernel; round 5's suite exercised them through mv.Super only
+run-time chroma ratios of degrain_kernel / cn_cell_kernel (Compensate) / bf_cell_kernel (BlockFPS); round 5's suite exercised them through mv.Super only
 ("format gap").  Bit-exact, through the C ABI, against the oracle on the same seeded clips."""
 import numpy as np
 import pytest

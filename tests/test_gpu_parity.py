@@ -1075,13 +1075,36 @@ BLOCKFPS_CASES = [
     (128, 96, 8, dict(blksize=8, overlap=4, delta=2), dict(num=36, den=1)),               # delta 2
     # (new cases go at the end: the ids of the cases above carry their position in this list)
     (206, 118, 8, dict(blksize=8, overlap=0), dict(num=60, den=1, mode=2)),              # side by side with uncovered strips on both edges
+    # one cell kernel serves every sample type and block layout: the combinations the two integer kernels it replaced had split between them
+    (128, 96, 16, dict(blksize=16, overlap=0), dict(num=60, den=1, mode=3)),             # side by side at the widest 16-bit cell (8 samples)
+    (128, 96, 8, dict(blksize=16, overlap=0), dict(num=60, den=1, mode=4, ml=40.0)),     # side by side, widest 8-bit cell of the mode, all three masks
+    (128, 96, 16, dict(blksize=8, overlap=0), dict(num=60, den=1, mode=5)),              # side by side, mask-only mode: no fetch
+    (206, 118, 8, dict(blksize=8, overlap=4), dict(num=60, den=1, mode=3)),              # overlap, uncovered strips on both edges; chroma 103 wide: cut cells in the strip
+    (206, 118, 16, dict(blksize=8, overlap=4), dict(num=60, den=1, thscd1=20, thscd2=10)),            # fallback blend through cut cells
+    (206, 118, 16, dict(blksize=8, overlap=4), dict(num=60, den=1, thscd1=20, thscd2=10, blend=0)),   # fallback copy through cut cells
+    (128, 96, 8, dict(blksize=8, overlap=2), dict(num=60, den=1, mode=1)),               # luma cells of 2 samples, chroma cells of 1 on 8-bit
+    (128, 96, 8, dict(blksize=4, overlap=2), dict(num=60, den=1, mode=0)),               # chroma blocks 2 wide, the narrowest blocks, overlapped
+    (128, 96, 8, dict(blksize=4, overlap=0), dict(num=60, den=1, mode=2)),               # ... and side by side
+    # the 8-bit overlap sum (the 16-bit wrap of its accumulator, the clamp) on samples at the maximum: tests/sample_range.py's rails clip, a fifth
+    # of whose samples are 255 (it has no clip that is all maximum, and the search could not follow one); test_blockfps_at_the_rails runs
+    # this clip at 10 and 16 bits on blocks 8/4 only
+    (128, 96, 8, dict(blksize=16, overlap=8), dict(num=60, den=1, mode=0, clip="rails")),
+    # cells of 16 8-bit samples, which modes 4 and 7 do not take: side by side and overlapped
+    (128, 96, 8, dict(blksize=16, overlap=0), dict(num=60, den=1, mode=3)),
+    (128, 96, 8, dict(blksize=32, overlap=16), dict(num=60, den=1, mode=3)),
 ]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("w,h,bits,akw,bkw", BLOCKFPS_CASES)
 def test_blockfps_parity(oracle, mv, w, h, bits, akw, bkw):
-    _blockfps_case(oracle, mv, w, h, bits, akw, bkw)
+    bkw = dict(bkw)
+    clip = bkw.pop("clip", None)  # a generator of tests/sample_range.py in place of the moving clip
+    frames = None
+    if clip:
+        import sample_range
+        frames = sample_range.make(clip, w, h, bits, 6)
+    _blockfps_case(oracle, mv, w, h, bits, akw, bkw, frames=frames)
 
 
 def _blockfps_case(oracle, mv, w, h, bits, akw, bkw, frames=None):

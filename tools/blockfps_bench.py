@@ -1,11 +1,12 @@
 """Times mvx_blockfps_frames (mv.BlockFPS) on the GPU with device events, every input resident: clip frames, super frames, both vector clips and
 the output frames.
 
-    python tools/blockfps_bench.py [--repeats 3] [--seconds S] [--mode 3]
+    python tools/blockfps_bench.py [--bits 16] [--blksize 16] [--repeats 3] [--seconds S] [--mode 3]
     python tools/blockfps_bench.py --float [--repeats 3] [--seconds S] [--mode 3]
 
-Workload: 1920 x 1080 4:2:0 16-bit, pel 2, blocks of 16 overlapping by 8 and blocks of 16 side by side, mode 3, 24 -> 60 fps over a clip of five
-frames moving by one sample per frame, with the vectors Analyse finds.  A call is the eight interpolated output frames of that conversion (outputs
+Workload: 1920 x 1080 4:2:0 at --bits 8 or 16, pel 2, blocks of --blksize overlapping by half and the same blocks side by side, mode 3, 24 -> 60 fps
+over a clip of five frames moving by one sample per frame, with the vectors Analyse finds.  MVX_LIB selects the library (the wrapper's rule), so
+two builds are compared by running the tool once per build.  A call is the eight interpolated output frames of that conversion (outputs
 1-4 and 6-9: time256 102, 205, 51, 154 between frames 0-1, 1-2, 2-3, 3-4), each into its own output frame; the job table is built once and the C
 entry point is called directly.  Each line is timed --repeats times in turn with the other (a, b, a, b, ...), a call repeated until about S
 seconds lie between the two events after a warm-up call; the spread of a line is max - min over its repeats.  Reported: ms per output frame.
@@ -77,20 +78,24 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--seconds", type=float, default=0.5)
     ap.add_argument("--mode", type=int, default=3)
+    ap.add_argument("--bits", type=int, default=16, choices=(8, 16), help="the integer clip's depth (--float: 16, the depth of the search it shares)")
+    ap.add_argument("--blksize", type=int, default=16)
     a = ap.parse_args()
+    if a.flt and a.bits != 16:
+        ap.error("--float compares with the 16-bit clip")
     L = mv.lib()
-    q = pl.moving_clip(W, H, 16, NFRAMES, seed=5, motion=(1, 0))
-    isup = mv.Super(W, H, 16)
+    q = pl.moving_clip(W, H, a.bits, NFRAMES, seed=5, motion=(1, 0))
+    isup = mv.Super(W, H, a.bits)
     iclip = [mv.frame_to_device(f) for f in q]
     isf = isup.build(iclip)
-    kinds = [("16-bit mvx_blockfps_frames", isup, iclip, isf, {})]
+    kinds = [("%d-bit mvx_blockfps_frames" % a.bits, isup, iclip, isf, {})]
     if a.flt:
         fsup = mv.Super(W, H, 32, sample_float=True)
         fclip = [mv.frame_to_device([(x.astype(np.float32) / np.float32(65535) - np.float32(0.5 if p else 0.0)) for p, x in enumerate(f)]) for f in q]
         kinds.append(("float  mvx_blockfps_frames", fsup, fclip, fsup.build(fclip), dict(sample_float=True)))
-    for overlap in (8, 0):
-        abw = mv.Analyse(isup, num_frames=NFRAMES, isb=1, blksize=16, overlap=overlap)
-        afw = mv.Analyse(isup, num_frames=NFRAMES, isb=0, blksize=16, overlap=overlap)
+    for overlap in (a.blksize // 2, 0):
+        abw = mv.Analyse(isup, num_frames=NFRAMES, isb=1, blksize=a.blksize, overlap=overlap)
+        afw = mv.Analyse(isup, num_frames=NFRAMES, isb=0, blksize=a.blksize, overlap=overlap)
         bw = abw.run([(isf[m], isf[m + 1] if m + 1 < NFRAMES else None) for m in range(NFRAMES)])
         fw = afw.run([(isf[m], isf[m - 1] if m >= 1 else None) for m in range(NFRAMES)])
         ad = abw.ad

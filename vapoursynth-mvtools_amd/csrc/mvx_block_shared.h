@@ -1,4 +1,5 @@
-// mvx_block_shared.h -- what the block filters share (mvx_degrain.hip: Degrain, BlockFPS; mvx_degrain_n.hip; mvx_compensate.hip: Compensate, CompensateN).
+// mvx_block_shared.h -- what the block filters share (mvx_degrain.hip: Degrain; mvx_degrain_n.hip: DegrainN; mvx_compensate.hip: Compensate,
+// CompensateN; mvx_blockfps.hip: BlockFPS).
 // All five read level-0 vectors, turn every block into an offset into a super plane, gather the up to 2 x 2 overlapped blocks that cover a
 // cell, weigh them with the overlap windows and store.  Device side: which blocks cover a sample or a cell and which of the nine windows a
 // block takes, and fgopIsUsable with the level-0 offset as its result (the N filters).  Host side: the geometry that opens every parameter
@@ -11,7 +12,7 @@
 
 // ------------------------------------------------------------------------------------------------ device
 
-// what DGParams, DNParams and CNParams open with (they derive from it, so the kernels read P.nBlkX as before)
+// what DGParams, DNParams, CNParams and BFParams open with (they derive from it, so the kernels read P.nBlkX as before)
 struct BlkGeom {
     int nBlkX, nBlkY, nBlk, pel, logPel, bits, bps, nplanes, overlap;
     int nLvCount;            // levels in a blob; the level-0 record is found by walking the per-plane size headers like fgopUpdate (Fakery.c:112-123)
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(256) void blk_usable_kernel(const PARAMS *Pp, int n
 
 // ------------------------------------------------------------------------------------------------ host
 
-// samples per cell of a plane for the N filters' cell kernels: the largest power of two up to `widest` that divides the block width and the block step
+// samples per cell of a plane for the cell kernels of the N filters and of BlockFPS: the largest power of two up to `widest` that divides the block width and the block step
 static int blk_cell_width(const PlaneG &g, int widest) {
     int w = widest;
     while (w > 1 && (g.blkW % w || g.stepX % w)) w >>= 1;
@@ -91,9 +92,8 @@ template <typename H> static int blk_new(H **h, const mvx_analysis_data *ad, con
 }
 
 // device state is created on first use so that argument validation works without a GPU: the windows per plane class, then the parameter
-// block, which points at them
-template <typename PARAMS> static int blk_upload(DevBuf<PARAMS> &dP, PARAMS &P, BlkWin &win) {
-    if (dP.p) return MVX_OK;
+// block, which points at them (BlockFPS, whose block points at its upsizer tables too, uploads it itself)
+static int blk_upload_windows(BlkGeom &P, BlkWin &win) {
     if (P.overlap) {
         for (int c = 0; c < win.classes; c++) {
             const PlaneG &g = P.pl[c];
@@ -104,6 +104,11 @@ template <typename PARAMS> static int blk_upload(DevBuf<PARAMS> &dP, PARAMS &P, 
         }
         P.win[0] = win.d[0].p; P.win[1] = P.win[2] = win.d[1].p;
     }
+    return MVX_OK;
+}
+template <typename PARAMS> static int blk_upload(DevBuf<PARAMS> &dP, PARAMS &P, BlkWin &win) {
+    if (dP.p) return MVX_OK;
+    if (int rc = blk_upload_windows(P, win)) return rc;
     return fps_upload_params(dP, P);
 }
 

@@ -1,6 +1,6 @@
-// mvx_degrain.hip -- the block filters on gfx950: mv.Degrain1..6 (first half), mv.BlockFPS and mv.SCDetection (second half, each under its own
-// heading).  What they share with DegrainN, Compensate and CompensateN (mvx_degrain_n.hip, mvx_compensate.hip) is in mvx_block_shared.h, what
-// they share with the flow filters and mv.Mask in mvx_fps_shared.h.
+// mvx_degrain.hip -- mv.Degrain1..6 on gfx950, with the overlap windows, mvx_vectors_size and mvx_scale_thscd that every vector consumer uses, and
+// mv.SCDetection at the end under its own heading.  What Degrain shares with DegrainN, Compensate, CompensateN and BlockFPS (mvx_degrain_n.hip,
+// mvx_compensate.hip, mvx_blockfps.hip) is in mvx_block_shared.h, what they share with the flow filters and mv.Mask in mvx_fps_shared.h.
 //
 // The reference walks blocks, blends each block into a temp (Degrain_C, MVDegrains.h:30-53), scatters it times a
 // raised-cosine window into a 16/32-bit accumulator (overlaps_c, Overlap.cpp:143-158) and finally normalises
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(256, (dg_cell_waves<NR, W>())) void degrain_cell_ke
 
 // ------------------------------------------------------------------------------------------------ host objects
 
-struct DGCommon {
+struct mvx_degrain {
     CallGuard guard;
     DGParams P;
     DevBuf<DGParams> dP;
@@ -446,25 +446,15 @@ struct DGCommon {
     DevBuf<int> dUsable;
     DevBuf<unsigned char> dPlan;  // grows to one and a half times the call's plan
     BlkWin win;
+    int radius;
 };
-struct mvx_degrain : DGCommon { int radius; };
 
-static int ensure_jobs(DGCommon *h, int nframes, size_t planBytesPerFrame) {
+static int ensure_jobs(mvx_degrain *h, int nframes, size_t planBytesPerFrame) {
     const size_t n = (size_t)nframes, need = planBytesPerFrame * n;
     HIP_CHECK(h->dJobs.reserve(n, n));
     HIP_CHECK(h->dUsable.reserve(n * 12, n * 12));
     HIP_CHECK(h->dPlan.reserve(need, need / 2));
     return MVX_OK;
-}
-
-// samples per thread of BlockFPS's row kernel: up to 16 bytes, dividing the block width and the frame width, so that a segment is never split
-// between cases (the uncovered strip starts at nBlkX * blkW).  0: the blocks overlap or are not powers of two -- the per-sample gather
-static int dg_rows_cw(const DGParams &P, int p) {
-    if (P.overlap) return 0;
-    const PlaneG &g = P.pl[p];
-    int cw = 16 / P.bps;
-    while (cw > 1 && (g.blkW % cw || g.W % cw)) cw >>= 1;
-    return (cw >= 2 && (g.blkW & (g.blkW - 1)) == 0 && (g.blkH & (g.blkH - 1)) == 0) ? cw : 0;
 }
 
 // MVDegrains.cpp:511-809 mvdegrainCreate
@@ -577,598 +567,6 @@ extern "C" __attribute__((visibility("default"))) int mvx_degrain_frames(mvx_deg
         dim3 grid((P.pl[0].W + 63) / 64, (P.pl[0].H + 3) / 4, nframes * 3);
         if (P.bps == 1) launch_degrain<uint8_t>(P.nRefs, grid, st, d->dP.p, d->dJobs.p, d->dPlan.p);
         else launch_degrain<uint16_t>(P.nRefs, grid, st, d->dP.p, d->dJobs.p, d->dPlan.p);
-    }
-    HIP_CHECK(hipGetLastError());
-    return MVX_OK;
-}
-
-// ================================================================================================ mv.BlockFPS
-// MVBlockFPS.c:229-676 (frame), :741-1014 (creation); MaskFun.cpp:63-166,349-371; SimpleResize.cpp:27-121.
-// One gather pass per output sample like Degrain / Compensate: the two motion-compensated fetches (backward vectors at
-// the left frame into the right super frame, forward vectors at the right frame into the left one, both scaled by the
-// time position), the per-mode blend, the overlap window sum and ToPixels.  The occlusion / SAD masks live at block
-// resolution (three small byte planes per frame pair) and are upsized bilinearly ON THE FLY per sample with the
-// reference's integer tables, so no full-size mask planes exist.
-
-struct BFParams {
-    int mode, blend, XP, YP;            // padded small-mask grid
-    int nWidthP[2], nHeightP[2];        // luma / chroma upsizer output sizes
-    double ml;
-    long long thscd1; int thscd2;
-    int supInterior[3];                 // byte offset of the un-padded level-0 sample (0,0) inside each super plane (:455-464)
-    const int *hOff[2], *hW[2], *vOff[2], *vW[2]; // SimpleResize tables, luma / chroma
-    long long clipPitch[3];
-};
-struct BFJob {
-    const unsigned char *srcSup[3], *refSup[3]; // super frame nleft / nright
-    const unsigned char *blobF, *blobB;         // mvfw vectors at nright, mvbw vectors at nleft
-    const unsigned char *clipL[3], *clipR[3];
-    unsigned char *dst[3];
-    int time256, good;
-};
-struct BFPlan { unsigned offB[2], offF[2]; };    // luma / chroma offsets of the two compensated blocks
-
-// per job: usable = both vector fields valid and no scene change (Fakery.c:144-146); 0 -> fallback
-__global__ __launch_bounds__(256) void bf_usable_kernel(const DGParams *Pp, const BFParams *Bp, const BFJob *jobs, int *usable) {
-    const DGParams &P = *Pp; const BFParams &B = *Bp;
-    const BFJob &J = jobs[blockIdx.x];
-    const unsigned char *const blobs[2] = { J.blobF, J.blobB };
-    const bool ok = fps_block_usable(blobs, J.good && J.time256 > 0 && J.time256 < 256, P.nLvCount, P.nBlk, B.thscd1, B.thscd2);
-    if (threadIdx.x == 0) usable[blockIdx.x] = ok;
-}
-
-// small masks, pass 1: scatter-max (occlusion, MaskFun.cpp:91-130) or direct (SAD mask, :139-166) into int planes
-// [job][F,B][YP*XP]; the scatter only ever takes maxima, so the order of the reference's loops does not matter.
-__global__ __launch_bounds__(256) void bf_mask_kernel(const DGParams *Pp, const BFParams *Bp, const BFJob *jobs, const int *usable, int *small) {
-    const DGParams &P = *Pp; const BFParams &B = *Bp;
-    const int f = blockIdx.z, dir = blockIdx.y; // dir 0 = forward mask, 1 = backward mask
-    if (!usable[f] || B.mode < 3) return;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= P.nBlk) return;
-    const BFJob &J = jobs[f];
-    const GVecD *vec = mvx_level0((dir ? J.blobB : J.blobF), P.nLvCount);
-    const int nBlkX = P.nBlkX, nBlkY = P.nBlkY, by = i / nBlkX, bx = i - by * nBlkX;
-    const int time256 = dir ? 256 - J.time256 : J.time256;
-    const int stepX = P.pl[0].stepX, stepY = P.pl[0].stepY, nPel = P.pel;
-    int *m = small + ((size_t)f * 2 + dir) * B.XP * B.YP;
-    if (B.mode <= 5) {
-        fps_occlusion_block(vec, i, bx, by, nBlkX, nBlkY, dir, time256, stepX, stepY, nPel, B.ml, m, B.XP);
-    } else {
-        const int tX = (256 - time256) * 16 / (stepX * nPel), tY = (256 - time256) * 16 / (stepY * nPel);
-        int bxi = bx - vec[i].x * tX / 4096, byi = by - vec[i].y * tY / 4096;
-        if (bxi < 0 || bxi >= nBlkX || byi < 0 || byi >= nBlkY) { bxi = bx; byi = by; }
-        const long long sad = vec[bxi + byi * nBlkX].sad >> (P.bits - 8);
-        const double factor = 4.0 / (B.ml * P.pl[0].blkW * P.pl[0].blkH);
-        const double l = 255 * ((double)sad * factor); // pow(x, 1.0) == x
-        m[bx + by * B.XP] = (int)(unsigned char)((l > 255) ? 255 : l);
-    }
-}
-// pass 2: byte planes [job][F,B,O][YP*XP] with the right / bottom padding clones (MaskFun.cpp:63-80) and O = F*B/255 (:93-101)
-__global__ __launch_bounds__(256) void bf_mask_finish_kernel(const DGParams *Pp, const BFParams *Bp, const int *usable, const int *small, unsigned char *masks) {
-    const DGParams &P = *Pp; const BFParams &B = *Bp;
-    const int f = blockIdx.y;
-    if (!usable[f] || B.mode < 3) return;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= B.XP * B.YP) return;
-    const int y = i / B.XP, x = i - y * B.XP;
-    const int s = fps_pad_source(x, y, P.nBlkX, P.nBlkY, B.XP);
-    const int *mF = small + ((size_t)f * 2 + 0) * B.XP * B.YP, *mB = small + ((size_t)f * 2 + 1) * B.XP * B.YP;
-    const int vF = mF[s], vB = mB[s];
-    unsigned char *o = masks + (size_t)f * 3 * B.XP * B.YP;
-    o[i] = (unsigned char)vF;
-    o[B.XP * B.YP + i] = (unsigned char)vB;
-    o[2 * B.XP * B.YP + i] = (unsigned char)((vF * vB) / 255);
-}
-
-__global__ __launch_bounds__(256) void bf_plan_kernel(const DGParams *Pp, const BFJob *jobs, const int *usable, BFPlan *plan) {
-    const DGParams &P = *Pp;
-    const int f = blockIdx.y;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= P.nBlk || !usable[f]) return;
-    const BFJob &J = jobs[f];
-    const int by = i / P.nBlkX, bx = i - by * P.nBlkX;
-    const GVecD *vB = mvx_level0(J.blobB, P.nLvCount), *vF = mvx_level0(J.blobF, P.nLvCount);
-    const int x = bx * P.pl[0].stepX, y = by * P.pl[0].stepY, t = J.time256; // FakeBlockData x / y, Fakery.c:31-32
-    const int bX = x * P.pel + ((vB[i].x * (256 - t)) >> 8), bY = y * P.pel + ((vB[i].y * (256 - t)) >> 8);
-    const int fX = x * P.pel + ((vF[i].x * t) >> 8), fY = y * P.pel + ((vF[i].y * t) >> 8);
-    BFPlan r;
-    for (int c = 0; c < 2; c++) { // the reference DIVIDES by the subsampling ratio here (:482-488), it does not shift
-        const PlaneG &g = P.pl[c];
-        const int xr = 1 << g.subX, yr = 1 << g.subY;
-        r.offB[c] = sup_offset(g, P.pel, P.logPel, P.bps, bX / xr, bY / yr);
-        r.offF[c] = sup_offset(g, P.pel, P.logPel, P.bps, fX / xr, fY / yr);
-    }
-    plan[(size_t)f * P.nBlk + i] = r;
-}
-
-__device__ __forceinline__ int bf_median(int a, int b, int c) { const int mn = min(a, b), mx = max(a, b); return max(mn, min(mx, c)); }
-
-template <typename T>
-__global__ __launch_bounds__(256) void blockfps_kernel(const DGParams *Pp, const BFParams *Bp, const BFJob *jobs, const int *usable, const BFPlan *plan, const unsigned char *masks) {
-    const DGParams &P = *Pp; const BFParams &B = *Bp;
-    const int z = blockIdx.z, f = z / 3, p = z % 3;
-    if (p >= P.nplanes) return;
-    const PlaneG &g = P.pl[p];
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= g.W || y >= g.H) return;
-    const BFJob &J = jobs[f];
-    T *drow = (T *)(J.dst[p] + (long long)y * g.dstPitch);
-    const int t = J.time256;
-    if (!usable[f]) { // time256 0 / 256, vectors unusable or frames outside the clip (:285-288, :640-673)
-        const int l = ((const T *)(J.clipL[p] + (long long)y * B.clipPitch[p]))[x];
-        if (t <= 0 || (t < 256 && !B.blend)) { drow[x] = (T)l; return; }
-        const int r = ((const T *)(J.clipR[p] + (long long)y * B.clipPitch[p]))[x];
-        drow[x] = t >= 256 ? (T)r : (T)((l * (256 - t) + r * t) >> 8);
-        return;
-    }
-    const int sVal = ((const T *)(J.srcSup[p] + B.supInterior[p] + (long long)y * g.supPitch))[x];
-    const int rVal = ((const T *)(J.refSup[p] + B.supInterior[p] + (long long)y * g.supPitch))[x];
-    const int covW = P.overlap ? g.WB : g.blkW * P.nBlkX, covH = P.overlap ? g.HB : g.blkH * P.nBlkY;
-    if (x >= covW || y >= covH) { drow[x] = (T)((sVal * (256 - t) + rVal * t) >> 8); return; } // Blend of the uncovered strips
-    const int mode = B.mode, c = p ? 1 : 0;
-    int mF = 0, mB = 0, mO = 0;
-    if (mode >= 3) {
-        const unsigned char *m = masks + (size_t)f * 3 * B.XP * B.YP;
-        if (mode != 5 && mode != 8) {
-            mF = bf_upsize(m, B.XP, B.hOff[c], B.hW[c], B.vOff[c], B.vW[c], x, y);
-            mB = bf_upsize(m + B.XP * B.YP, B.XP, B.hOff[c], B.hW[c], B.vOff[c], B.vW[c], x, y);
-        }
-        if (mode == 4 || mode == 5 || mode == 7 || mode == 8) mO = bf_upsize(m + 2 * B.XP * B.YP, B.XP, B.hOff[c], B.hW[c], B.vOff[c], B.vW[c], x, y);
-    }
-    const BFPlan *pl = plan + (size_t)f * P.nBlk;
-    auto result = [&](const BFPlan &R, int px, int py) -> int { // RealResultBlock, MVBlockFPS.c:117-227
-        const int b = ((const T *)(J.refSup[p] + R.offB[c] + (long long)py * g.supPitch))[px];
-        const int fw = ((const T *)(J.srcSup[p] + R.offF[c] + (long long)py * g.supPitch))[px];
-        switch (mode) {
-        case 0: return (b * t + fw * (256 - t)) >> 8;
-        case 1: return bf_median(rVal, sVal, (int)(T)((b * t + fw * (256 - t)) >> 8));
-        case 2: return bf_median((int)(T)((rVal * t + sVal * (256 - t)) >> 8), b, fw);
-        case 3: case 6: return (((mB * fw + (255 - mB) * b + 255) >> 8) * t + ((mF * b + (255 - mF) * fw + 255) >> 8) * (256 - t)) >> 8;
-        case 4: case 7: {
-            const int ff = (mF * b + (255 - mF) * fw + 255) >> 8, bb = (mB * fw + (255 - mB) * b + 255) >> 8;
-            const int avg = (rVal * t + sVal * (256 - t) + 255) >> 8, m = (bb * t + ff * (256 - t)) >> 8;
-            return (avg * mO + m * (255 - mO) + 255) >> 8;
-        }
-        default: return mO << (P.bits - 8);
-        }
-    };
-    int out;
-    if (!P.overlap) {
-        const int bx = x / g.blkW, by = y / g.blkH;
-        out = (T)result(pl[by * P.nBlkX + bx], x - bx * g.blkW, y - by * g.blkH);
-    } else {
-        int bx0, bx1, by0, by1;
-        blk_cover(x, g.blkW, g.stepX, P.nBlkX, bx0, bx1);
-        blk_cover(y, g.blkH, g.stepY, P.nBlkY, by0, by1);
-        unsigned acc = 0;
-        const int16_t *win = P.win[p];
-        for (int by = by0; by <= by1; by++) {
-            const int py = y - by * g.stepY;
-            const int wby = BLK_WIN_ROW(by, P.nBlkY);
-            for (int bx = bx0; bx <= bx1; bx++) {
-                const int px = x - bx * g.stepX;
-                const int wbx = BLK_WIN_COL(bx, P.nBlkX);
-                const int val = (T)result(pl[by * P.nBlkX + bx], px, py);
-                acc += (unsigned)((val * (int)win[(wby + wbx) * g.blkW * g.blkH + py * g.blkW + px]) >> 6);
-            }
-        }
-        if (sizeof(T) == 1) acc &= 0xffffu;
-        const int a = (int)((acc + 16) >> 5);
-        const int pm = (1 << P.bits) - 1;
-        out = a > pm ? pm : a;
-    }
-    drow[x] = (T)out;
-}
-
-
-// ---- blocks without overlap: one thread per CW consecutive samples of one block row (the host checks dg_rows_cw's conditions).
-// The four vector loads (left / right frame at the sample, the two motion-compensated fetches) and the plan record are per segment;
-// the mask upsizer (SimpleResize.cpp:62-121) interpolates vertically once per mask column the segment touches.
-template <typename T, int CW>
-__global__ __launch_bounds__(256) void blockfps_rows_kernel(const DGParams *Pp, const BFParams *Bp, const BFJob *jobs, const int *usable, const BFPlan *plan, const unsigned char *masks,
-                                                            int planeFirst, int planesPerFrame) {
-    const DGParams &P = *Pp; const BFParams &B = *Bp;
-    const int z = blockIdx.z, f = z / planesPerFrame, p = planeFirst + z % planesPerFrame;
-    const PlaneG &g = P.pl[p];
-    const int x = (blockIdx.x * 64 + (threadIdx.x & 63)) * CW, y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= g.W || y >= g.H) return;
-    const BFJob &J = jobs[f];
-    unsigned char *dptr = J.dst[p] + (long long)y * g.dstPitch + (long long)x * (long long)sizeof(T);
-    const int t = J.time256;
-    int out[CW];
-    if (!usable[f]) { // time256 0 / 256, vectors unusable or frames outside the clip (:285-288, :640-673)
-        int l[CW];
-        dg_load<T, CW>(dg_gl(J.clipL[p] + (long long)y * B.clipPitch[p] + (long long)x * (long long)sizeof(T)), l);
-        if (t <= 0 || (t < 256 && !B.blend)) { dg_store<T, CW>(dg_glw(dptr), l); return; }
-        int r[CW];
-        dg_load<T, CW>(dg_gl(J.clipR[p] + (long long)y * B.clipPitch[p] + (long long)x * (long long)sizeof(T)), r);
-#pragma unroll
-        for (int i = 0; i < CW; i++) out[i] = t >= 256 ? r[i] : (int)(T)((l[i] * (256 - t) + r[i] * t) >> 8);
-        dg_store<T, CW>(dg_glw(dptr), out);
-        return;
-    }
-    int sVal[CW], rVal[CW];
-    const long long inner = B.supInterior[p] + (long long)y * g.supPitch + (long long)x * (long long)sizeof(T);
-    dg_load<T, CW>(dg_gl(J.srcSup[p] + inner), sVal);
-    dg_load<T, CW>(dg_gl(J.refSup[p] + inner), rVal);
-    const int covW = g.blkW * P.nBlkX, covH = g.blkH * P.nBlkY;
-    if (x >= covW || y >= covH) { // Blend of the uncovered strips
-#pragma unroll
-        for (int i = 0; i < CW; i++) out[i] = (int)(T)((sVal[i] * (256 - t) + rVal[i] * t) >> 8);
-        dg_store<T, CW>(dg_glw(dptr), out);
-        return;
-    }
-    const int mode = B.mode, c = p ? 1 : 0;
-    int mF[CW], mB[CW], mO[CW];
-#pragma unroll
-    for (int i = 0; i < CW; i++) { mF[i] = 0; mB[i] = 0; mO[i] = 0; }
-    if (mode >= 3) {
-        DG_GL const unsigned char *m = dg_gl(masks + (size_t)f * 3 * B.XP * B.YP);
-        // (r4: the resize tables and the mask bytes through global-address-space pointers and as vectors -- the table pointers sit in a struct, so the
-        // compiler emitted one FLAT load per table entry, each waited for on its own, and six byte loads per mask: 45 loads per thread, now 15)
-        const int wb = *(DG_GL const int *)dg_gl(B.vW[c] + y), wt = 16384 - wb;
-        const int rowOff = *(DG_GL const int *)dg_gl(B.vOff[c] + y) * B.XP;
-        int hO[CW], hWr[CW];
-        if (x + CW <= g.W) {
-            dg_load_ints<CW>(dg_gl(B.hOff[c] + x), hO);
-            dg_load_ints<CW>(dg_gl(B.hW[c] + x), hWr);
-        } else {
-#pragma unroll
-            for (int i = 0; i < CW; i++) { const int xi = x + i < g.W ? x + i : g.W - 1; hO[i] = *(DG_GL const int *)dg_gl(B.hOff[c] + xi); hWr[i] = *(DG_GL const int *)dg_gl(B.hW[c] + xi); }
-        }
-        const int o0 = hO[0];
-        // vertically interpolated values of up to three mask columns; columns further right (upsizing by less than CW) are done on demand
-        auto vcol = [&](DG_GL const unsigned char *mm, int o) { return (int)(unsigned char)((mm[rowOff + o] * wt + mm[rowOff + B.XP + o] * wb + 8192) >> 14); };
-        auto upsize = [&](DG_GL const unsigned char *mm, int *dst) {
-            // (the third column is only used when a sample's left neighbour is o0 + 1; at the plane's right edge it does not exist: read o0 + 1 again)
-            // the bytes o0 .. o0 + 3 of the two mask rows as ONE unaligned dword each (the mask buffer has four bytes of slack behind its last row)
-            const unsigned r0 = *(DG_GL const dg_uv1 *)(mm + rowOff + o0), r1 = *(DG_GL const dg_uv1 *)(mm + rowOff + B.XP + o0);
-            auto vc = [&](int k) { return (int)(unsigned char)((((r0 >> (8 * k)) & 0xffu) * wt + ((r1 >> (8 * k)) & 0xffu) * wb + 8192) >> 14); };
-            const int a0 = vc(0), a1 = vc(1), a2 = o0 + 2 < B.XP ? vc(2) : a1;
-#pragma unroll
-            for (int i = 0; i < CW; i++) {
-                const int o = hO[i], wr = hWr[i], wl = 16384 - wr, k = o - o0;
-                int a, b;
-                if (k == 0) { a = a0; b = a1; } else if (k == 1) { a = a1; b = a2; } else { a = vcol(mm, o); b = vcol(mm, o + 1); }
-                dst[i] = (int)(unsigned char)((a * wl + b * wr + 8192) >> 14);
-            }
-        };
-        if (mode != 5 && mode != 8) { upsize(m, mF); upsize(m + B.XP * B.YP, mB); }
-        if (mode == 4 || mode == 5 || mode == 7 || mode == 8) upsize(m + 2 * B.XP * B.YP, mO);
-    }
-    const int lbw = __ffs(g.blkW) - 1, lbh = __ffs(g.blkH) - 1;
-    const int bx = x >> lbw, by = y >> lbh, px = x & (g.blkW - 1), py = y & (g.blkH - 1);
-    const BFPlan R = plan[(size_t)f * P.nBlk + by * P.nBlkX + bx];
-    int bv[CW], fv[CW];
-    const long long bo = (long long)py * g.supPitch + (long long)px * (long long)sizeof(T);
-    dg_load<T, CW>(dg_gl(J.refSup[p] + R.offB[c] + bo), bv);
-    dg_load<T, CW>(dg_gl(J.srcSup[p] + R.offF[c] + bo), fv);
-#pragma unroll
-    for (int i = 0; i < CW; i++) { // RealResultBlock, MVBlockFPS.c:117-227
-        const int b = bv[i], fw = fv[i];
-        int v;
-        switch (mode) {
-        case 0: v = (b * t + fw * (256 - t)) >> 8; break;
-        case 1: v = bf_median(rVal[i], sVal[i], (int)(T)((b * t + fw * (256 - t)) >> 8)); break;
-        case 2: v = bf_median((int)(T)((rVal[i] * t + sVal[i] * (256 - t)) >> 8), b, fw); break;
-        case 3: case 6: v = (((mB[i] * fw + (255 - mB[i]) * b + 255) >> 8) * t + ((mF[i] * b + (255 - mF[i]) * fw + 255) >> 8) * (256 - t)) >> 8; break;
-        case 4: case 7: {
-            const int ff = (mF[i] * b + (255 - mF[i]) * fw + 255) >> 8, bb = (mB[i] * fw + (255 - mB[i]) * b + 255) >> 8;
-            const int avg = (rVal[i] * t + sVal[i] * (256 - t) + 255) >> 8, mm = (bb * t + ff * (256 - t)) >> 8;
-            v = (avg * mO[i] + mm * (255 - mO[i]) + 255) >> 8; break;
-        }
-        default: v = mO[i] << (P.bits - 8); break;
-        }
-        out[i] = (int)(T)v;
-    }
-    dg_store<T, CW>(dg_glw(dptr), out);
-}
-
-#include "mvx_blockfps_float_rule.h"
-
-// ---- float clips (mvx_blockfps_create_float): one kernel of cn_cell_kernel<float, W>'s shape for every case.  A thread produces one row of a cell
-// of W float32 samples; W divides the block width and the block step, so the same <= 2 x 2 blocks cover all of a cell and each costs one
-// vector load per fetch.  The usable pass, the masks, the plan and the resize tables are those above (none of them touches a sample; the plan's
-// offsets are in bytes of 4 per sample because P.bps is 4).  The arithmetic is mvx_blockfps_float_rule.h; the copies of an unusable job move
-// bytes and never look at them.  Job, plane, geometry and tables are uniform over the workgroup and arrive through scalar loads.  The
-// motion-compensated fetches are 4-byte aligned and no more, as are the clip and the output planes.
-// n: the samples of the cell inside the plane (W or more: all of them); a cell cut by the plane's edge is read and written sample by sample
-template <int W> __device__ __forceinline__ DgRaw<float, W> bff_load(DG_GL const unsigned char *p, int n) {
-    if (n >= W) return dg_load_raw<float, W>(p);
-    DgRaw<float, W> r;
-#pragma unroll
-    for (int i = 0; i < W; i++) r.d[i] = i < n ? *(DG_GL const dg_uv1 *)(p + 4 * i) : 0u;
-    return r;
-}
-template <int W> __device__ __forceinline__ void bff_store(DG_GL unsigned char *p, const DgRaw<float, W> &r, int n) {
-    if (n >= W) {
-        if constexpr (W == 4) { dg_uv4 t = { r.d[0], r.d[1], r.d[2], r.d[3] }; *(DG_GL dg_uv4 *)p = t; }
-        else if constexpr (W == 2) { dg_uv2 t = { r.d[0], r.d[1] }; *(DG_GL dg_uv2 *)p = t; }
-        else *(DG_GL dg_uv1 *)p = r.d[0];
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < W; i++) if (i < n) *(DG_GL dg_uv1 *)(p + 4 * i) = r.d[i];
-}
-
-// MODE: 0..5, the arithmetic of the mode (6, 7 and 8 compute like 3, 4 and 5: they differ in how the masks are made).  A template argument so
-// that a mode keeps in registers only what it reads: 0..2 no mask, 3 F and B, 4 all three, 5 O alone and no fetch.  The masks of a sample
-// travel packed in one register: F | B << 8 | O << 16
-// The mask modes divide two or three times per sample, and an IEEE division is a dozen instructions with half a dozen values in flight.  Left
-// alone the scheduler interleaves the divisions of all W samples (109 and 112 VGPRs at W = 4 in modes 3 and 4, occupancy 4); a scheduling
-// barrier after each sample keeps one sample's temporaries live at a time
-#define BFF_ONE_AT_A_TIME() do { if constexpr (MODE == 3 || MODE == 4) __builtin_amdgcn_sched_barrier(0); } while (0)
-template <int W, int MODE>
-__global__ __launch_bounds__(256) void bf_cell_float_kernel(const DGParams *Pp, const BFParams *Bp, const BFJob *jobs, const int *usable, const BFPlan *plan, const unsigned char *masks,
-                                                            int planeFirst, int planesPerFrame) {
-    static_assert(W == 1 || W == 2 || W == 4, "cells of 16 bytes at most");
-    const DGParams &P = *Pp; const BFParams &B = *Bp;
-    const int z = blockIdx.z, f = z / planesPerFrame, p = planeFirst + z % planesPerFrame;
-    const PlaneG &g = P.pl[p];
-    const int x0 = (blockIdx.x * 32 + (threadIdx.x & 31)) * W, y = blockIdx.y * 8 + (threadIdx.x >> 5);
-    if (x0 >= g.W || y >= g.H) return;
-    const int n = g.W - x0;
-    const BFJob &J = jobs[f];
-    DG_GL unsigned char *dptr = dg_glw(J.dst[p]) + (long long)y * g.dstPitch + (long long)x0 * 4;
-    const int t = J.time256;
-    DgRaw<float, W> out;
-    if (!usable[f]) { // time256 0 / 256, vectors unusable or frames outside the clip: a copy, bit for bit, or the blend of the two clip frames
-        const long long co = (long long)y * B.clipPitch[p] + (long long)x0 * 4;
-        const bool left = t <= 0 || (t < 256 && !B.blend);
-        if (left || t >= 256) { bff_store<W>(dptr, bff_load<W>(dg_gl(left ? J.clipL[p] : J.clipR[p]) + co, n), n); return; }
-        const DgRaw<float, W> l = bff_load<W>(dg_gl(J.clipL[p]) + co, n), r = bff_load<W>(dg_gl(J.clipR[p]) + co, n);
-#pragma unroll
-        for (int i = 0; i < W; i++) out.d[i] = __float_as_uint(mvx_bff_time(__uint_as_float(r.d[i]), __uint_as_float(l.d[i]), t));
-        bff_store<W>(dptr, out, n);
-        return;
-    }
-    const long long inner = B.supInterior[p] + (long long)y * g.supPitch + (long long)x0 * 4;
-    const DgRaw<float, W> sVal = bff_load<W>(dg_gl(J.srcSup[p]) + inner, n), rVal = bff_load<W>(dg_gl(J.refSup[p]) + inner, n);
-    const int covW = P.overlap ? g.WB : g.blkW * P.nBlkX, covH = P.overlap ? g.HB : g.blkH * P.nBlkY;
-    if (x0 >= covW || y >= covH) { // the strips no block covers
-#pragma unroll
-        for (int i = 0; i < W; i++) out.d[i] = __float_as_uint(mvx_bff_time(__uint_as_float(rVal.d[i]), __uint_as_float(sVal.d[i]), t));
-        bff_store<W>(dptr, out, n);
-        return;
-    }
-    // from here on the cell lies inside the covered width (a multiple of W), so inside the plane
-    const int c = p ? 1 : 0;
-    unsigned mk[W];
-#pragma unroll
-    for (int i = 0; i < W; i++) mk[i] = 0u;
-    if constexpr (MODE >= 3) { // the upsizer of blockfps_rows_kernel: the integer tables, the masks stay bytes
-        DG_GL const unsigned char *m = dg_gl(masks + (size_t)f * 3 * B.XP * B.YP);
-        const int wb = *(DG_GL const int *)dg_gl(B.vW[c] + y), wt = 16384 - wb;
-        const int rowOff = *(DG_GL const int *)dg_gl(B.vOff[c] + y) * B.XP;
-        int hO[W], hWr[W];
-        dg_load_ints<W>(dg_gl(B.hOff[c] + x0), hO);
-        dg_load_ints<W>(dg_gl(B.hW[c] + x0), hWr);
-        const int o0 = hO[0];
-        auto vcol = [&](DG_GL const unsigned char *mm, int o) { return (int)(unsigned char)((mm[rowOff + o] * wt + mm[rowOff + B.XP + o] * wb + 8192) >> 14); };
-        auto upsize = [&](DG_GL const unsigned char *mm, int shift) {
-            // the bytes o0 .. o0 + 3 of the two mask rows as one unaligned dword each (the mask buffer has slack behind its last row)
-            const unsigned r0 = *(DG_GL const dg_uv1 *)(mm + rowOff + o0), r1 = *(DG_GL const dg_uv1 *)(mm + rowOff + B.XP + o0);
-            auto vc = [&](int k) { return (int)(unsigned char)((((r0 >> (8 * k)) & 0xffu) * wt + ((r1 >> (8 * k)) & 0xffu) * wb + 8192) >> 14); };
-            const int a0 = vc(0), a1 = vc(1), a2 = o0 + 2 < B.XP ? vc(2) : a1;
-#pragma unroll
-            for (int i = 0; i < W; i++) {
-                const int o = hO[i], wr = hWr[i], wl = 16384 - wr, k = o - o0;
-                int a, b;
-                if (k == 0) { a = a0; b = a1; } else if (k == 1) { a = a1; b = a2; } else { a = vcol(mm, o); b = vcol(mm, o + 1); }
-                mk[i] |= (unsigned)(unsigned char)((a * wl + b * wr + 8192) >> 14) << shift;
-            }
-        };
-        if constexpr (MODE != 5) { upsize(m, 0); upsize(m + B.XP * B.YP, 8); }
-        if constexpr (MODE >= 4) upsize(m + 2 * B.XP * B.YP, 16);
-    }
-    // one sample of a block from its two fetches
-    auto value = [&](int i, unsigned b, unsigned fw) {
-        return mvx_bff_value(MODE, t, __uint_as_float(sVal.d[i]), __uint_as_float(rVal.d[i]), __uint_as_float(b), __uint_as_float(fw), (int)(mk[i] & 0xffu),
-                             (int)((mk[i] >> 8) & 0xffu), (int)(mk[i] >> 16));
-    };
-    DG_GL const unsigned char *pl = dg_gl(plan + (size_t)f * P.nBlk);
-    DG_GL const unsigned char *refSup = dg_gl(J.refSup[p]), *srcSup = dg_gl(J.srcSup[p]);
-    if (!P.overlap) { // blocks side by side (their sizes are powers of two): the value itself
-        DgRaw<float, W> bv = sVal, fv = sVal; // (mode 5 reads neither)
-        if constexpr (MODE != 5) {
-            const int lbw = __ffs(g.blkW) - 1, lbh = __ffs(g.blkH) - 1;
-            const int bx = x0 >> lbw, by = y >> lbh, px = x0 & (g.blkW - 1), py = y & (g.blkH - 1);
-            const dg_iv4 R = *(DG_GL const dg_iv4 *)(pl + (size_t)(by * P.nBlkX + bx) * sizeof(BFPlan));
-            const long long bo = (long long)py * g.supPitch + (long long)px * 4;
-            bv = dg_load_raw<float, W>(refSup + (unsigned)R[c] + bo);
-            fv = dg_load_raw<float, W>(srcSup + (unsigned)R[2 + c] + bo);
-        }
-#pragma unroll
-        for (int i = 0; i < W; i++) { out.d[i] = __float_as_uint(value(i, bv.d[i], fv.d[i])); BFF_ONE_AT_A_TIME(); }
-        bff_store<W>(dptr, out, W);
-        return;
-    }
-    // overlapped blocks: the blocks bx0..bx1 x by0..by1 cover the cell, at most two each way, by outer and bx inner.  One block at a time: its
-    // two fetches and its window row are all that is live beside the cell's own state, which keeps the kernel at cn_cell_kernel<float, W>'s occupancy
-    int bx0, bx1, by0, by1;
-    blk_cover(x0, g.blkW, g.stepX, P.nBlkX, bx0, bx1);
-    blk_cover(y, g.blkH, g.stepY, P.nBlkY, by0, by1);
-    DG_GL const unsigned char *win = dg_gl(P.win[p]);
-    float acc[W];
-    int wsum[W];
-#pragma unroll
-    for (int i = 0; i < W; i++) { acc[i] = 0.0f; wsum[i] = 0; }
-#pragma unroll 1
-    for (int by = by0; by <= by1; by++) {
-        const int py = y - by * g.stepY, wrow = BLK_WIN_ROW(by, P.nBlkY);
-#pragma unroll 1
-        for (int bx = bx0; bx <= bx1; bx++) {
-            const int px = x0 - bx * g.stepX; // 0 <= px <= blkW - W
-            DgRaw<float, W> bv = sVal, fv = sVal; // (mode 5 reads neither)
-            if constexpr (MODE != 5) {
-                const dg_iv4 R = *(DG_GL const dg_iv4 *)(pl + (size_t)(by * P.nBlkX + bx) * sizeof(BFPlan));
-                const long long bo = (long long)py * g.supPitch + (long long)px * 4;
-                bv = dg_load_raw<float, W>(refSup + (unsigned)R[c] + bo);
-                fv = dg_load_raw<float, W>(srcSup + (unsigned)R[2 + c] + bo);
-            }
-            const DgRaw<unsigned short, W> wv = dg_load_raw<unsigned short, W>(win + (size_t)((wrow + BLK_WIN_COL(bx, P.nBlkX)) * g.blkW * g.blkH + py * g.blkW + px) * 2);
-#pragma unroll
-            for (int i = 0; i < W; i++) {
-                const int wi = dg_sample(wv, i);
-                acc[i] = mvx_bff_add(acc[i], value(i, bv.d[i], fv.d[i]), wi);
-                wsum[i] += wi;
-                BFF_ONE_AT_A_TIME();
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < W; i++) out.d[i] = __float_as_uint(mvx_bff_out(acc[i], wsum[i]));
-    bff_store<W>(dptr, out, W);
-}
-
-struct mvx_blockfps : DGCommon {
-    BFParams B;
-    DevBuf<BFParams> dB;
-    DevBuf<BFJob> dBJobs;         // grows to twice the call's jobs, as do the masks
-    DevBuf<int> dSmall, dTables;
-    DevBuf<unsigned char> dMasks;
-    FpsRate rate;
-    int delta;
-    bool flt = false;             // float super clip, float clip and output planes (bf_cell_float_kernel)
-};
-
-// MVBlockFPS.c:741-1014 mvblockfpsCreate.  flt: the float entry (the super clip must be a float one; said after the frame-size check)
-static int bf_create(bool flt, const mvx_blockfps_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
-        const mvx_super *sup, int num_frames, int64_t fps_num, int64_t fps_den, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3],
-        const ptrdiff_t dst_pitch[3], mvx_blockfps **out, char *err) {
-    MVX_CREATE_BEGIN(out);
-    if (!flt) MVX_REFUSE_FLOAT(sup, "BlockFPS");
-    const mvx_super_info &si = sup->info;
-    const int mode = a->mode == MVX_UNSET ? 3 : a->mode;
-    const int blend = a->blend == MVX_UNSET ? 1 : !!a->blend;
-    int64_t thscd1; int32_t thscd2;
-    if (mode < 0 || mode > 8) MVX_FAIL("BlockFPS: mode must be between 0 and 8 (inclusive).");
-    if (int rc = mvx_resolve_thscd("BlockFPS", a->thscd1, a->thscd2, bw, &thscd1, &thscd2, err)) return rc;
-    // (the first mismatch is reported, and subsampling and bit depth are not compared: unlike flow_similarity in mvx_flow.hip)
-    if (bw->nWidth != fw->nWidth) MVX_FAIL("BlockFPS: mvbw and mvfw have different widths.");
-    if (bw->nHeight != fw->nHeight) MVX_FAIL("BlockFPS: mvbw and mvfw have different heights.");
-    if (bw->nBlkSizeX != fw->nBlkSizeX || bw->nBlkSizeY != fw->nBlkSizeY) MVX_FAIL("BlockFPS: mvbw and mvfw have different block sizes.");
-    if (bw->nPel != fw->nPel) MVX_FAIL("BlockFPS: mvbw and mvfw have different pel precision.");
-    if (bw->nOverlapX != fw->nOverlapX || bw->nOverlapY != fw->nOverlapY) MVX_FAIL("BlockFPS: mvbw and mvfw have different overlap.");
-    if (int rc = mvx_pair_checks("BlockFPS", bw, fw, err)) return rc;
-    if (fps_num == 0 || fps_den == 0) MVX_FAIL("BlockFPS: The input clip must have a frame rate. Invoke AssumeFPS if necessary.");
-    if (!mvx_super_fits(bw, si, true)) MVX_FAIL("BlockFPS: wrong source or super clip frame size.");
-    if (flt && !sup->is_float) MVX_FAIL("BlockFPS: the float entry needs a float super clip.");
-    mvx_blockfps *h;
-    if (int rc = blk_new(&h, bw, si, clip_pitch, super_pitch, dst_pitch, err, "clip")) return rc;
-    DGParams &P = h->P;
-    h->flt = flt;
-    // P.bps stays the sample size (4: pitches, the plan's offsets, supInterior).  P.bits is read by bf_mask_kernel alone on this path, as the
-    // depth of the SADs (sad >> (bits - 8)): that of the search, not the super clip's 32
-    if (flt) P.bits = bw->bitsPerSample;
-    if (!(si.modeYUV & 6)) P.nplanes = 1;
-    P.nRefs = 2; P.thscd1 = thscd1; P.thscd2 = thscd2;
-    fps_rate_init(h->rate, a->num, a->den, fps_num, fps_den, num_frames);
-    h->delta = bw->nDeltaFrame;
-    BFParams &B = h->B;
-    memset(&B, 0, sizeof(B));
-    B.mode = mode; B.blend = blend; B.ml = a->ml; B.thscd1 = thscd1; B.thscd2 = thscd2;
-    fps_padded_grid(bw, &B.XP, &B.YP, B.nWidthP, B.nHeightP);
-    const int bps = P.bps;
-    B.supInterior[0] = si.hpad * bps + (int)super_pitch[0] * si.vpad;
-    for (int p = 1; p < 3; p++) B.supInterior[p] = (si.hpad >> 1) * bps + (int)super_pitch[p < si.num_planes ? p : 0] * (si.vpad >> 1); // the reference's ">> 1" (:459-463)
-    for (int p = 0; p < 3; p++) B.clipPitch[p] = clip_pitch[p < si.num_planes ? p : 0];
-    *out = h;
-    return MVX_OK;
-}
-extern "C" __attribute__((visibility("default"))) int mvx_blockfps_create(const mvx_blockfps_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
-        const mvx_super *sup, int num_frames, int64_t fps_num, int64_t fps_den, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3],
-        const ptrdiff_t dst_pitch[3], mvx_blockfps **out, char *err) {
-    return bf_create(false, a, bw, fw, sup, num_frames, fps_num, fps_den, super_pitch, clip_pitch, dst_pitch, out, err);
-}
-extern "C" __attribute__((visibility("default"))) int mvx_blockfps_create_float(const mvx_blockfps_args *a, const mvx_analysis_data *bw, const mvx_analysis_data *fw,
-        const mvx_super *sup, int num_frames, int64_t fps_num, int64_t fps_den, const ptrdiff_t super_pitch[3], const ptrdiff_t clip_pitch[3],
-        const ptrdiff_t dst_pitch[3], mvx_blockfps **out, char *err) {
-    return bf_create(true, a, bw, fw, sup, num_frames, fps_num, fps_den, super_pitch, clip_pitch, dst_pitch, out, err);
-}
-extern "C" __attribute__((visibility("default"))) void mvx_blockfps_destroy(mvx_blockfps *b) { delete b; }
-extern "C" __attribute__((visibility("default"))) void mvx_blockfps_get_info(const mvx_blockfps *b, mvx_blockfps_info *info) {
-    info->num_frames = b->rate.outFrames; info->fps_num = b->rate.outNum; info->fps_den = b->rate.outDen;
-}
-extern "C" __attribute__((visibility("default"))) void mvx_blockfps_map(const mvx_blockfps *b, int n, int *nleft, int *nright, int *time256) {
-    fps_rate_map(b->rate, b->delta, n, nleft, nright, time256);
-}
-
-extern "C" __attribute__((visibility("default"))) int mvx_blockfps_frames(mvx_blockfps *b, int nframes, const mvx_blockfps_job *jobs, void *stream) {
-    if (nframes <= 0) return MVX_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const DGParams &P = b->P;
-    BFParams &B = b->B;
-    for (int f = 0; f < nframes; f++) {
-        const mvx_blockfps_job &J = jobs[f];
-        if (!J.clip_left[0] || (J.time256 > 0 && !J.clip_right[0])) { mvx_set_error("mvx_blockfps_frames: clip_left / clip_right are required"); return MVX_E_ARG; }
-        if (int rc = fps_check_planes("mvx_blockfps_frames", "clip_left", J.clip_left, P.nplanes, P.bps, true)) return rc;
-        if (int rc = fps_check_planes("mvx_blockfps_frames", "clip_right", J.clip_right, P.nplanes, P.bps, false)) return rc;
-        if (int rc = fps_check_planes("mvx_blockfps_frames", "dst", J.dst, P.nplanes, P.bps, true)) return rc;
-        if (int rc = fps_check_planes("mvx_blockfps_frames", "source super", J.src_super, P.nplanes, 16, false)) return rc;
-        if (int rc = fps_check_planes("mvx_blockfps_frames", "reference super", J.ref_super, P.nplanes, 16, false)) return rc;
-    }
-    CallGuard::Scope scope(b->guard, st);
-    int rc = blk_upload(b->dP, b->P, b->win);
-    if (rc) return rc;
-    if (!b->dB.p && (rc = fps_upload_tables(b->dTables, b->dB, B, B.nWidthP, B.nHeightP))) return rc;
-    if ((rc = ensure_jobs(b, nframes, sizeof(BFPlan) * (size_t)P.nBlk))) return rc;
-    const size_t n = (size_t)nframes, cells = (size_t)B.XP * B.YP;
-    HIP_CHECK(b->dBJobs.reserve(n, n));
-    HIP_CHECK(b->dSmall.reserve(n * 2 * cells, n * 2 * cells));
-    HIP_CHECK(b->dMasks.reserve(n * 3 * cells + 16, n * 3 * cells)); // (+ slack: the row kernels read mask bytes four at a time)
-    std::vector<BFJob> hj(nframes);
-    for (int f = 0; f < nframes; f++) {
-        BFJob &j = hj[f];
-        memset(&j, 0, sizeof(j));
-        for (int p = 0; p < 3; p++) {
-            j.srcSup[p] = (const unsigned char *)jobs[f].src_super[p]; j.refSup[p] = (const unsigned char *)jobs[f].ref_super[p];
-            j.clipL[p] = (const unsigned char *)jobs[f].clip_left[p]; j.clipR[p] = (const unsigned char *)jobs[f].clip_right[p];
-            j.dst[p] = (unsigned char *)jobs[f].dst[p];
-        }
-        j.blobF = (const unsigned char *)jobs[f].blob_fw; j.blobB = (const unsigned char *)jobs[f].blob_bw;
-        j.time256 = jobs[f].time256;
-        j.good = j.srcSup[0] && j.refSup[0] && j.blobF && j.blobB;
-    }
-    HIP_CHECK(hipMemcpyAsync(b->dBJobs.p, hj.data(), sizeof(BFJob) * nframes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(bf_usable_kernel, dim3(nframes), dim3(256), 0, st, b->dP.p, b->dB.p, b->dBJobs.p, b->dUsable.p);
-    if (B.mode >= 3) {
-        HIP_CHECK(hipMemsetAsync(b->dSmall.p, 0, n * 2 * cells * sizeof(int), st));
-        hipLaunchKernelGGL(bf_mask_kernel, dim3((P.nBlk + 255) / 256, 2, nframes), dim3(256), 0, st, b->dP.p, b->dB.p, b->dBJobs.p, b->dUsable.p, b->dSmall.p);
-        hipLaunchKernelGGL(bf_mask_finish_kernel, dim3((unsigned)((cells + 255) / 256), nframes), dim3(256), 0, st, b->dP.p, b->dB.p, b->dUsable.p, b->dSmall.p, b->dMasks.p);
-    }
-    const BFPlan *plan = (const BFPlan *)b->dPlan.p;
-    hipLaunchKernelGGL(bf_plan_kernel, dim3((P.nBlk + 255) / 256, nframes), dim3(256), 0, st, b->dP.p, b->dBJobs.p, b->dUsable.p, (BFPlan *)b->dPlan.p);
-    if (b->flt) { // one launch for the luma planes of all jobs, one for both chroma planes
-        // the widest cell at which the mode's kernel keeps occupancy 8: 16 bytes in modes 0, 5 and 8, 8 bytes in modes 1, 2, 3 and 6, one sample in
-        // modes 4 and 7 (profiles/blockfps_float_isa.txt)
-        const int m = B.mode < 6 ? B.mode : B.mode - 3, mw = m == 0 || m == 5 ? 4 : m == 4 ? 1 : 2;
-        for (int cls = 0; cls < (P.nplanes > 1 ? 2 : 1); cls++) {
-            const int p0 = cls, npl = cls ? 2 : 1, W = blk_cell_width(P.pl[p0], mw);
-            const dim3 grid(((P.pl[p0].W + W - 1) / W + 31) / 32, (P.pl[p0].H + 7) / 8, nframes * npl);
-#define BFF(N, M) hipLaunchKernelGGL((bf_cell_float_kernel<N, M>), grid, dim3(256), 0, st, b->dP.p, b->dB.p, b->dBJobs.p, b->dUsable.p, plan, b->dMasks.p, p0, npl)
-#define BFW(M) switch (W) { case 1: BFF(1, M); break; case 2: BFF(2, M); break; default: BFF(4, M); break; }
-#define BFN(M) switch (W) { case 1: BFF(1, M); break; default: BFF(2, M); break; }
-            switch (m) { case 0: BFW(0); break; case 1: BFN(1); break; case 2: BFN(2); break; case 3: BFN(3); break; case 4: BFF(1, 4); break; default: BFW(5); break; }
-#undef BFN
-#undef BFW
-#undef BFF
-        }
-        HIP_CHECK(hipGetLastError());
-        return MVX_OK;
-    }
-    const int cwY = dg_rows_cw(P, 0), cwC = P.nplanes > 1 ? dg_rows_cw(P, 1) : 1;
-    if (cwY && cwC && (P.nplanes == 1 || P.pl[1].W == P.pl[2].W)) {
-        fps_classes(P.pl, P.nplanes, nframes, [&](int p) { return p ? cwC : cwY; }, [&](dim3 grid, int cw, int p0, int npl) {
-            fps_dispatch<2>(P.bps, cw, [&](auto t, auto w) {
-                hipLaunchKernelGGL((blockfps_rows_kernel<typename decltype(t)::type, decltype(w)::value>), grid, dim3(256), 0, st, b->dP.p, b->dB.p, b->dBJobs.p, b->dUsable.p, plan,
-                                   b->dMasks.p, p0, npl);
-            });
-        });
-    } else {
-        dim3 grid((P.pl[0].W + 63) / 64, (P.pl[0].H + 3) / 4, nframes * 3);
-        if (P.bps == 1) hipLaunchKernelGGL(blockfps_kernel<uint8_t>, grid, dim3(256), 0, st, b->dP.p, b->dB.p, b->dBJobs.p, b->dUsable.p, plan, b->dMasks.p);
-        else hipLaunchKernelGGL(blockfps_kernel<uint16_t>, grid, dim3(256), 0, st, b->dP.p, b->dB.p, b->dBJobs.p, b->dUsable.p, plan, b->dMasks.p);
     }
     HIP_CHECK(hipGetLastError());
     return MVX_OK;

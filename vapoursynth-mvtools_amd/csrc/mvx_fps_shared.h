@@ -1,4 +1,5 @@
-// mvx_fps_shared.h -- what the filters that consume vectors share (mvx_degrain.hip, mvx_flow.hip, mvx_mask.hip).  Device side: the level-0
+// mvx_fps_shared.h -- what the filters that consume vectors share (the block filters through mvx_block_shared.h: mvx_degrain.hip, mvx_degrain_n.hip,
+// mvx_compensate.hip, mvx_blockfps.hip; mvx_flow.hip, mvx_mask.hip).  Device side: the level-0
 // vector reader, fgopIsUsable, the super-plane addressing, the wide sample loads / stores, the reference's bilinear upsizer and the occlusion
 // mask of MaskFun.cpp.  Host side: the scene-change thresholds, the checks on a pair of vector clips, the frame-rate conversion, the padded
 // small-field grid with its upsizer tables, the plane geometry and the launch dispatch by sample type and width.  What only the block filters
@@ -109,11 +110,6 @@ template <typename T, int W> __device__ __forceinline__ void dg_store(DG_GL unsi
 template <typename PTR> __device__ __forceinline__ int fps_upsize_u8(PTR m, int r0, int r1, int o, int wt, int wb, int wl, int wr) {
     const int a = (unsigned char)((m[r0 + o] * wt + m[r1 + o] * wb + 8192) >> 14), b = (unsigned char)((m[r0 + o + 1] * wt + m[r1 + o + 1] * wb + 8192) >> 14);
     return (unsigned char)((a * wl + b * wr + 8192) >> 14);
-}
-// the same with the table lookups
-__device__ __forceinline__ int bf_upsize(const unsigned char *m, int XP, const int *hOff, const int *hW, const int *vOff, const int *vW, int x, int y) {
-    const int wb = vW[y], wr = hW[x], r0 = vOff[y] * XP;
-    return fps_upsize_u8(m, r0, r0 + XP, hOff[x], 16384 - wb, wb, 16384 - wr, wr);
 }
 
 // Fakery.c:52-58,103-107,144-146 fgopIsUsable, the count part: this thread's share (stride 256) of the n level-0 blocks from `first` on whose SAD
