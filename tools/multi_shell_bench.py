@@ -15,7 +15,11 @@ mv.Degrain3 reads frame 0 of its vector clips and so runs the first look-ahead w
 requests for the output clip alone, the shell's upload / download thread-seconds (MVX_VS_STATS) and its AnalyseN counters.  Every mini-host process runs under its own
 time limit and the first one that fails ends the session.  Recorded, not gated.
 
-    usage (GPU box):  python tools/multi_shell_bench.py [frames] [threads] [repeats] [--against DIR]"""
+With --float the session is another one: multidegrain at radius 3 on a 1080p 16-bit clip, and the same graph with the float switch (MVX_VS_FLOAT=1) on the float clip whose
+quantised copy that 16-bit clip is -- mv.Super and mv.DegrainN on float samples, mv.AnalyseN on the 16-bit clip, so both graphs use the same vectors -- turn and turn about.
+The float graph moves twice the bytes per frame over PCIe in each direction.
+
+    usage (GPU box):  python tools/multi_shell_bench.py [frames] [threads] [repeats] [--against DIR | --float]"""
 import os
 import re
 import statistics
@@ -34,11 +38,14 @@ if "--against" in argv:
     i = argv.index("--against")
     AGAINST = os.path.abspath(argv[i + 1])
     del argv[i:i + 2]
+FLOAT = "--float" in argv
+if FLOAT:
+    argv.remove("--float")
 N = int(argv[0]) if len(argv) > 0 else 160
 T = int(argv[1]) if len(argv) > 1 else 16
 REPEATS = int(argv[2]) if len(argv) > 2 else 3
 LIMIT = 180  # seconds a mini-host process may take
-w, h, bits = 1920, 1080, 8
+w, h, bits = 1920, 1080, 16 if FLOAT else 8
 tmp = os.environ.get("TMPDIR", "/tmp")
 src, out = os.path.join(tmp, "multi_bench_in.raw"), os.path.join(tmp, "multi_bench_out.raw")
 frames = pl.moving_clip(w, h, bits, N, seed=3, noise=2)
@@ -46,6 +53,12 @@ with open(src, "wb") as f:
     for fr in frames:
         for p in fr:
             f.write(np.ascontiguousarray(p).tobytes())
+fsrc = os.path.join(tmp, "multi_bench_in_float.raw")
+if FLOAT:   # luma in [0, 1], chroma in [-0.5, 0.5]: round(x * 65535) (chroma: of x + 0.5) is the 16-bit clip
+    with open(fsrc, "wb") as f:
+        for fr in frames:
+            for p, a in enumerate(fr):
+                f.write((a.astype(np.float64) / 65535.0 - (0.5 if p else 0.0)).astype(np.float32).tobytes())
 host = os.path.join(ROOT, "vapoursynth-mvtools_amd", "mvx_vs_host")
 PLUGINS = {"this": os.path.join(ROOT, "vapoursynth-mvtools_amd", "libmvtools_vs.so")}
 if AGAINST:
@@ -61,6 +74,9 @@ PIPELINES = [
     ("multirecalculate radius 3", "multirecalculate", M3 + ["r.blksize=8", "r.overlap=4", "r.thsad=200"], 1, None),
 ]
 RUNS = []          # (plugin, name, pipeline, args, per, lookahead)
+if FLOAT:
+    RUNS = [("this", "multidegrain radius 3, 16-bit", "multidegrain", M3, 1, "-"), ("this", "multidegrain radius 3, float", "multidegrain", M3 + ["x.float=" + fsrc], 1, "-")]
+    PIPELINES = []
 for name, pipeline, args, per, default in PIPELINES:
     if AGAINST:
         RUNS.append(("other", name, pipeline, args, per, "-"))
@@ -72,7 +88,7 @@ print("%dx%d P%d, %d frames, %d request threads, %d repeats; blksize 16, overlap
 results = {i: dict(rates=[], req=[], moved="", counters="") for i in range(len(RUNS))}
 for _ in range(REPEATS):      # repeats outermost: the two plugins, and the settings of a pipeline, take turns
     for i, (plugin, name, pipeline, args, per, la) in enumerate(RUNS):
-        env = dict(os.environ, MVX_VS_STATS="1", MVX_HOST_TIMES="1", MVX_VS_MULTI="1")
+        env = dict(os.environ, MVX_VS_STATS="1", MVX_HOST_TIMES="1", MVX_VS_MULTI="1", **({"MVX_VS_FLOAT": "1"} if FLOAT else {}))
         env.pop("MVX_VS_MULTI_LOOKAHEAD", None)
         if la != "-":
             env["MVX_VS_MULTI_LOOKAHEAD"] = la

@@ -15,7 +15,7 @@
  *       pipeline: super | finest | analyse | scdetection (d.*) | recalculate (r.*) | degrainN | compensate | blockfps (b.*)
  *                 | flowinter | flowfps | flow | flowblur | mask (f.*; the plugin registers these with MVX_VS_FLOW=1): on the vector pair of delta 1, or
  *                 of x.delta=N; flow and mask take the backward clip as `vectors`, x.vectors=fw the forward one
- *       in.raw  : nframes x (Y, U, V planes, 4:2:0, tightly packed, little endian); x.format=422 | 444 | gray (one plane): other chroma formats
+ *       in.raw  : nframes x (Y, U, V planes, 4:2:0, tightly packed, little endian); x.format=422 | 444 | gray (one plane) | 410 (subsampling 2: refused by the plugin): other chroma formats
  *       out.raw : super      -> every super frame (planes tightly packed) ; props of frame 0 on stdout
  *                 analyse    -> per frame: 84-byte MVTools_MVAnalysisData + MVTools_vectors, backward (isb=1) then forward
  *                 degrainN / compensate -> output frames, planes tightly packed
@@ -34,6 +34,15 @@
  *   `error` takes AnalyseN (f.*), and RecalculateN | DegrainN | CompensateN | MultiField (f.*) on AnalyseN(m.*); x.vectors=single hands them mv.Analyse's backward clip
  *       instead, and x.vectors=multi hands the AnalyseN clip to any of the single-field filters below
  *   `error` takes DepanAnalyse (on the backward vectors) and DepanEstimate | DepanCompensate | DepanStabilise (data clip: DepanEstimate(clip) with e.*; no mv.Super)
+ *   32-bit float clips (the plugin takes them with MVX_VS_FLOAT=1):
+ *       run ... x.float=<path>: a second source of the same geometry and chroma format, float32 little endian in in.raw's plane order.  The final filter's `clip` comes from
+ *                 it and, where the filter takes one, its `super` from a second mv.Super (s.*) built on it; vectors and Depan data still come from in.raw.  `run super`
+ *                 writes the float super frames.  The run prints "output format sample=float|integer bits=B bytes=N".  multidegrain / multicompensate with x.intout=<path>
+ *                 build the same filter on the integer clip as well, in the same graph, and write its frames there
+ *       error ... x.float=clip | super | both: the filter's `clip` is a blank float clip, its `super` an mv.Super of that clip, or both (mv.Super itself: created on the
+ *                 float clip); the OK line then ends in the output clip's sample type and format.  x.fakesuper=1: instead of the mv.Super node a blank float clip of its
+ *                 size with its Super_* properties on frame 0 (creation then needs no frame of mv.Super).  `error Finest` takes the `super` argument alone
+ *       run ... x.threads=N x.threadorder=reverse: the N threads ask for the frames last to first
  *   a stub of com.vapoursynth.text / FrameProps returns its clip unchanged and prints "text.FrameProps props=<name>"; x.notext=1 hides the plugin
  */
 #include <dlfcn.h>
@@ -239,11 +248,12 @@ static uint8_t *VS_CC getWritePtr(VSFrame *f, int p) {
     return f->data[p];
 }
 static const VSVideoFormat *VS_CC getVideoFrameFormat(const VSFrame *f) { return &f->fmt; }
-static int VS_CC queryVideoFormat(VSVideoFormat *fmt, int colorFamily, int sampleType, int bits, int ssw, int ssh, VSCore *core) { /* integer Gray / YUV of 8..16 bits, like the source clips */
+static int VS_CC queryVideoFormat(VSVideoFormat *fmt, int colorFamily, int sampleType, int bits, int ssw, int ssh, VSCore *core) { /* integer Gray / YUV of 8..16 bits or 32-bit float, like the source clips */
     (void)core;
-    if ((colorFamily != cfGray && colorFamily != cfYUV) || sampleType != stInteger || bits < 8 || bits > 16 || ssw < 0 || ssw > 4 || ssh < 0 || ssh > 4) return 0;
+    const int isFloat = sampleType == stFloat && bits == 32;
+    if ((colorFamily != cfGray && colorFamily != cfYUV) || (!isFloat && (sampleType != stInteger || bits < 8 || bits > 16)) || ssw < 0 || ssw > 4 || ssh < 0 || ssh > 4) return 0;
     if (colorFamily == cfGray && (ssw || ssh)) return 0;
-    fmt->colorFamily = colorFamily; fmt->sampleType = sampleType; fmt->bitsPerSample = bits; fmt->bytesPerSample = bits > 8 ? 2 : 1;
+    fmt->colorFamily = colorFamily; fmt->sampleType = sampleType; fmt->bitsPerSample = bits; fmt->bytesPerSample = isFloat ? 4 : bits > 8 ? 2 : 1;
     fmt->subSamplingW = ssw; fmt->subSamplingH = ssh; fmt->numPlanes = colorFamily == cfGray ? 1 : 3;
     return 1;
 }
@@ -458,12 +468,16 @@ static void format_from_args(int argc, char **argv) {
             g_fmt_gray = !strcmp(f, "gray");
             g_fmt_ssw = (!strcmp(f, "444") || g_fmt_gray) ? 0 : 1;
             g_fmt_ssh = !strcmp(f, "420") ? 1 : 0;
+            if (!strcmp(f, "410")) g_fmt_ssw = g_fmt_ssh = 2; /* (a format the plugin refuses) */
         }
 }
-static VSNode *source_clip(const char *path, int w, int h, int bits, int nframes) {
+/* isFloat: a clip of 32-bit float samples (`bits` is not looked at); a file holds float32, little endian, in the integer clips' plane order */
+static VSNode *source_clip_of(const char *path, int w, int h, int bits, int nframes, int isFloat) {
     VSNode *n = (VSNode *)calloc(1, sizeof(VSNode));
     n->refs = 1;
-    n->vi.format.colorFamily = g_fmt_gray ? cfGray : cfYUV; n->vi.format.sampleType = stInteger; n->vi.format.bitsPerSample = bits; n->vi.format.bytesPerSample = bits > 8 ? 2 : 1;
+    if (isFloat) bits = 32;
+    n->vi.format.colorFamily = g_fmt_gray ? cfGray : cfYUV; n->vi.format.sampleType = isFloat ? stFloat : stInteger; n->vi.format.bitsPerSample = bits;
+    n->vi.format.bytesPerSample = isFloat ? 4 : bits > 8 ? 2 : 1;
     n->vi.format.subSamplingW = g_fmt_ssw; n->vi.format.subSamplingH = g_fmt_ssh; n->vi.format.numPlanes = g_fmt_gray ? 1 : 3;
     n->vi.fpsNum = 24; n->vi.fpsDen = 1; n->vi.width = w; n->vi.height = h; n->vi.numFrames = nframes;
     n->cache = (const VSFrame **)calloc((size_t)nframes, sizeof(VSFrame *));
@@ -482,6 +496,27 @@ static VSNode *source_clip(const char *path, int w, int h, int bits, int nframes
         n->cache[f] = fr;
     }
     if (fp) fclose(fp);
+    return n;
+}
+static VSNode *source_clip(const char *path, int w, int h, int bits, int nframes) { return source_clip_of(path, w, h, bits, nframes, 0); }
+static const char *arg_value(int argc, char **argv, const char *key) { /* the value of "key=value", or NULL */
+    const size_t len = strlen(key);
+    for (int i = 0; i < argc; i++) if (!strncmp(argv[i], key, len) && argv[i][len] == '=') return argv[i] + len + 1;
+    return NULL;
+}
+static const char *sample_name(const VSVideoFormat *f) { return f->sampleType == stFloat ? "float" : "integer"; }
+/* `error` with x.fakesuper=1: a blank float clip of a float super clip's size whose frame 0 carries that clip's Super_* properties (hpad, vpad, pel, chroma from s.*, one
+ * level) -- what a consumer's creation reads of its `super` argument, without a frame of mv.Super, which needs a device */
+static int map_int_or(const VSMap *m, const char *key, int def) { int e = 0; const int64_t v = mapGetInt(m, key, 0, &e); return e ? def : (int)v; }
+static VSNode *fake_float_super(VSNode *real, const VSMap *superArgs, int height) {
+    VSNode *n = source_clip_of(NULL, real->vi.width, real->vi.height, 32, 4, 1);
+    VSMap *p = ((VSFrame *)n->cache[0])->props;
+    mapSetInt(p, "Super_height", height, maReplace);
+    mapSetInt(p, "Super_hpad", map_int_or(superArgs, "hpad", 16), maReplace);
+    mapSetInt(p, "Super_vpad", map_int_or(superArgs, "vpad", 16), maReplace);
+    mapSetInt(p, "Super_pel", map_int_or(superArgs, "pel", 2), maReplace);
+    mapSetInt(p, "Super_modeyuv", g_fmt_gray || !map_int_or(superArgs, "chroma", 1) ? 1 : 7, maReplace);
+    mapSetInt(p, "Super_levels", 1, maReplace);
     return n;
 }
 
@@ -528,6 +563,7 @@ static VSNode *depan_estimate_clip(VSNode *clip, char extraPrefix, int argc, cha
 /* x.threads=N: request frames 0..count-1 of up to four nodes from N threads at once (results stay in the nodes' frame tables) */
 typedef struct Work { VSNode *nodes[4]; int nnodes, count, next, done; char err[2048]; } Work;
 static double g_phase_t0;
+static int g_thread_reverse; /* x.threadorder=reverse: the threads ask for the last frame first */
 static void *worker(void *arg) {
     Work *w = (Work *)arg;
     for (;;) {
@@ -537,7 +573,7 @@ static void *worker(void *arg) {
         if (i < 0) return NULL;
         char err[2048] = "";
         /* node-major order: every thread first asks the first node, so that one filter instance sees all requests at once */
-        const VSFrame *f = eval_frame(i % w->count, w->nodes[i / w->count], err, sizeof(err));
+        const VSFrame *f = eval_frame(g_thread_reverse ? w->count - 1 - i % w->count : i % w->count, w->nodes[i / w->count], err, sizeof(err));
         if (f) freeFrame(f);
         if (getenv("MVX_HOST_TIMES")) { /* progress: when every 64th request completed (the rate of the later part of a run = the steady state) */
             pthread_mutex_lock(&g_host_mu);
@@ -641,6 +677,12 @@ static int host_main(int argc, char **argv) {
             int cw, ch, cb;
             if (!strncmp(argv[i], "x.clip=", 7) && sscanf(argv[i] + 7, "%dx%dx%d", &cw, &ch, &cb) == 3) fclip = source_clip(NULL, cw, ch, cb, 4);
         }
+        /* x.float=clip | super | both: the filter's `clip` argument is a blank 32-bit float clip of the first clip's geometry, its `super` argument an mv.Super (s.*) of that
+         * float clip, or both; vector clips and data clips still come from the integer clip.  mv.Super itself is created on the float clip with any of the three */
+        const char *fl = arg_value(argc - 7, argv + 7, "x.float");
+        const int floatClip = fl && (!strcmp(fl, "clip") || !strcmp(fl, "both")), floatSuper = fl && (!strcmp(fl, "super") || !strcmp(fl, "both"));
+        VSNode *flclip = fl ? source_clip_of(NULL, w, hh, 32, 4, 1) : NULL;
+        if (floatClip) fclip = flclip;
         VSMap *m = createMap();
         VSNode *out = NULL;
         g_notext = has_arg(argc - 7, argv + 7, "x.notext=1");
@@ -652,7 +694,7 @@ static int host_main(int argc, char **argv) {
             out = invoke(filter, m, err, sizeof(err));
         }
         else if (!strcmp(filter, "Super")) {
-            mapSetNode(m, "clip", clip, maReplace); add_args(m, 'f', argc - 7, argv + 7);
+            mapSetNode(m, "clip", fl ? flclip : clip, maReplace); add_args(m, 'f', argc - 7, argv + 7);
             VSNode *pc = pelclip_from_args(argc - 7, argv + 7, bits, 4);
             if (pc) mapSetNode(m, "pelclip", pc, maReplace);
             out = invoke("Super", m, err, sizeof(err));
@@ -661,11 +703,19 @@ static int host_main(int argc, char **argv) {
             VSMap *sm = createMap(); mapSetNode(sm, "clip", clip, maReplace); add_args(sm, 's', argc - 7, argv + 7);
             VSNode *sup = invoke("Super", sm, err, sizeof(err));
             if (!sup) die("Super", err);
-            if (!strcmp(filter, "Analyse")) { mapSetNode(m, "super", sup, maReplace); add_args(m, 'f', argc - 7, argv + 7); out = invoke("Analyse", m, err, sizeof(err)); }
-            else if (!strcmp(filter, "AnalyseN")) { mapSetNode(m, "super", sup, maReplace); add_args(m, 'f', argc - 7, argv + 7); out = invoke("AnalyseN", m, err, sizeof(err)); }
+            VSNode *fsup = sup; /* the `super` argument of the filter under test (the vector clips are always searched on `sup`) */
+            if (floatSuper) {
+                VSMap *fm = createMap(); mapSetNode(fm, "clip", flclip, maReplace); add_args(fm, 's', argc - 7, argv + 7);
+                fsup = invoke("Super", fm, err, sizeof(err));
+                if (!fsup) die("Super", err);
+                if (has_arg(argc - 7, argv + 7, "x.fakesuper=1")) fsup = fake_float_super(fsup, fm, hh);
+            }
+            if (!strcmp(filter, "Analyse")) { mapSetNode(m, "super", fsup, maReplace); add_args(m, 'f', argc - 7, argv + 7); out = invoke("Analyse", m, err, sizeof(err)); }
+            else if (!strcmp(filter, "AnalyseN")) { mapSetNode(m, "super", fsup, maReplace); add_args(m, 'f', argc - 7, argv + 7); out = invoke("AnalyseN", m, err, sizeof(err)); }
+            else if (!strcmp(filter, "Finest")) { mapSetNode(m, "super", fsup, maReplace); add_args(m, 'f', argc - 7, argv + 7); out = invoke("Finest", m, err, sizeof(err)); }
             else if ((!strcmp(filter, "RecalculateN") || !strcmp(filter, "DegrainN") || !strcmp(filter, "CompensateN") || !strcmp(filter, "MultiField")) && !has_arg(argc - 7, argv + 7, "x.vectors=single")) {
                 mapSetNode(m, "vectors", multi_clip(sup, 0, argc - 7, argv + 7, err, sizeof(err)), maReplace);
-                if (strcmp(filter, "MultiField")) mapSetNode(m, "super", sup, maReplace);
+                if (strcmp(filter, "MultiField")) mapSetNode(m, "super", fsup, maReplace);
                 if (!strcmp(filter, "DegrainN") || !strcmp(filter, "CompensateN")) mapSetNode(m, "clip", fclip, maReplace);
                 add_args(m, 'f', argc - 7, argv + 7);
                 out = invoke(filter, m, err, sizeof(err));
@@ -680,15 +730,17 @@ static int host_main(int argc, char **argv) {
                 VSNode *fw = invoke("Analyse", a2, err, sizeof(err)); if (!fw) die("Analyse", err);
                 if (has_arg(argc - 7, argv + 7, "x.vectors=multi")) bw = fw = multi_clip(sup, 0, argc - 7, argv + 7, err, sizeof(err)); /* a multi vector clip where a single-field one belongs */
                 if (strcmp(filter, "RecalculateN") && strcmp(filter, "MultiField")) mapSetNode(m, "clip", fclip, maReplace);
-                if (strcmp(filter, "Mask") && strcmp(filter, "DepanAnalyse") && strcmp(filter, "MultiField")) mapSetNode(m, "super", sup, maReplace); /* (mv.Mask and mv.DepanAnalyse take no super clip) */
+                if (strcmp(filter, "Mask") && strcmp(filter, "DepanAnalyse") && strcmp(filter, "MultiField") && strcmp(filter, "SCDetection")) mapSetNode(m, "super", fsup, maReplace); /* (mv.Mask, mv.DepanAnalyse and mv.SCDetection take no super clip) */
                 add_args(m, 'f', argc - 7, argv + 7);
                 if (!strcmp(filter, "RecalculateN") || !strcmp(filter, "DegrainN") || !strcmp(filter, "CompensateN") || !strcmp(filter, "MultiField") ||
-                    !strcmp(filter, "Compensate") || !strcmp(filter, "Flow") || !strcmp(filter, "Mask") || !strcmp(filter, "DepanAnalyse")) { mapSetNode(m, "vectors", bw, maReplace); out = invoke(filter, m, err, sizeof(err)); }
+                    !strcmp(filter, "Compensate") || !strcmp(filter, "Flow") || !strcmp(filter, "Mask") || !strcmp(filter, "DepanAnalyse") || !strcmp(filter, "SCDetection")) { mapSetNode(m, "vectors", bw, maReplace); out = invoke(filter, m, err, sizeof(err)); }
                 else if (!strcmp(filter, "Degrain1Swapped")) { mapSetNode(m, "mvbw", fw, maReplace); mapSetNode(m, "mvfw", bw, maReplace); out = invoke("Degrain1", m, err, sizeof(err)); }
                 else { mapSetNode(m, "mvbw", bw, maReplace); mapSetNode(m, "mvfw", fw, maReplace); out = invoke(filter, m, err, sizeof(err)); }
             }
         }
-        if (out) printf("OK %dx%d frames=%d\n", out->vi.width, out->vi.height, out->vi.numFrames);
+        if (out && fl) printf("OK %dx%d frames=%d sample=%s bits=%d ssw=%d ssh=%d planes=%d\n", out->vi.width, out->vi.height, out->vi.numFrames, sample_name(&out->vi.format),
+                              out->vi.format.bitsPerSample, out->vi.format.subSamplingW, out->vi.format.subSamplingH, out->vi.format.numPlanes);
+        else if (out) printf("OK %dx%d frames=%d\n", out->vi.width, out->vi.height, out->vi.numFrames);
         else printf("ERROR %s\n", err);
         return 0;
     }
@@ -701,7 +753,12 @@ static int host_main(int argc, char **argv) {
     for (int i = 0; i < nextra; i++) if (!strncmp(extra[i], "x.fieldorder=", 13)) g_field_order = atoi(extra[i] + 13);
     for (int i = 0; i < nextra; i++) if (!strncmp(extra[i], "x.threads=", 10)) threads = atoi(extra[i] + 10);
     for (int i = 0; i < nextra; i++) if (!strncmp(extra[i], "x.cache=", 8)) g_cache_limit = atoi(extra[i] + 8);
+    g_thread_reverse = has_arg(nextra, extra, "x.threadorder=reverse");
     VSNode *clip = source_clip(inPath, w, hh, bits, nframes);
+    /* x.float=<path>: a second source of the same geometry and chroma format, 32-bit float.  The final filter's `clip` is this clip and its `super` a second mv.Super (s.*)
+     * built on it; vectors and Depan data still come from the integer clip.  The run then prints the output clip's sample type */
+    const char *floatPath = arg_value(nextra, extra, "x.float");
+    VSNode *fclip = floatPath ? source_clip_of(floatPath, w, hh, 32, nframes, 1) : NULL;
     FILE *fo = fopen(outPath, "wb"); /* (before the time mark: truncating a previous run's multi-gigabyte result file takes a second) */
     if (!fo) { fprintf(stderr, "cannot write %s\n", outPath); return 2; }
     if (getenv("MVX_HOST_TIMES")) fprintf(stderr, "minihost: clip loaded at %.2f s after start\n", now_s() - g_start); /* (graph construction starts here) */
@@ -722,7 +779,8 @@ static int host_main(int argc, char **argv) {
             mapSetInt(am, "isb", has_arg(nextra, extra, "x.vectors=fw") ? 0 : 1, maReplace); mapSetInt(am, "delta", 1, maReplace);
             VSNode *vectors = invoke("Analyse", am, err, sizeof(err));
             if (!vectors) die("Analyse", err);
-            VSMap *nm = createMap(); mapSetNode(nm, "clip", clip, maReplace); mapSetNode(nm, "vectors", vectors, maReplace); add_args(nm, 'n', nextra, extra);
+            VSMap *nm = createMap(); mapSetNode(nm, "clip", isData && fclip ? fclip : clip, maReplace); /* (depananalyse with x.float: the final filter IS DepanAnalyse) */
+            mapSetNode(nm, "vectors", vectors, maReplace); add_args(nm, 'n', nextra, extra);
             for (int i = 0; i < nextra; i++) /* x.mask=path: DepanAnalyse's mask clip, 8-bit, in the source clip's layout */
                 if (!strncmp(extra[i], "x.mask=", 7)) mapSetNode(nm, "mask", source_clip(extra[i] + 7, w, hh, 8, nframes), maReplace);
             if (isData) add_args(nm, 'f', nextra, extra);
@@ -734,10 +792,11 @@ static int host_main(int argc, char **argv) {
         }
         VSNode *out = data;
         if (!isData) {
-            VSMap *m = createMap(); mapSetNode(m, "clip", clip, maReplace); mapSetNode(m, "data", data, maReplace); add_args(m, 'f', nextra, extra);
+            VSMap *m = createMap(); mapSetNode(m, "clip", fclip ? fclip : clip, maReplace); mapSetNode(m, "data", data, maReplace); add_args(m, 'f', nextra, extra);
             out = invoke(final, m, err, sizeof(err));
             if (!out) die(pipeline, err);
         }
+        if (fclip) printf("output format sample=%s bits=%d bytes=%d\n", sample_name(&out->vi.format), out->vi.format.bitsPerSample, out->vi.format.bytesPerSample);
         g_uncapped = out;
         prefetch_parallel(threads, nframes, &out, 1); /* (output frames only: every upstream request is the filters') */
         for (int n = 0; n < nframes; n++) {
@@ -767,12 +826,20 @@ static int host_main(int argc, char **argv) {
     VSNode *sup = invoke("Super", sm, err, sizeof(err));
     if (!sup) die("Super", err);
     if (getenv("MVX_HOST_TIMES")) fprintf(stderr, "minihost: mv.Super created at %.2f s after start\n", now_s() - g_start);
+    VSNode *fsup = NULL; /* x.float: the float clip's own mv.Super */
+    if (fclip) {
+        VSMap *fsm = createMap(); mapSetNode(fsm, "clip", fclip, maReplace); add_args(fsm, 's', nextra, extra);
+        fsup = invoke("Super", fsm, err, sizeof(err));
+        if (!fsup) die("Super", err);
+    }
+    VSNode *const useClip = fclip ? fclip : clip, *const useSup = fsup ? fsup : sup; /* what the final filter is handed */
     if (!strcmp(pipeline, "super")) {
         for (int n = 0; n < nframes; n++) {
-            const VSFrame *f = eval_frame(n, sup, err, sizeof(err));
+            const VSFrame *f = eval_frame(n, useSup, err, sizeof(err));
             if (!f) die("Super frame", err);
             if (n == 0) {
                 int e;
+                if (fclip) printf("output format sample=%s bits=%d bytes=%d\n", sample_name(&f->fmt), f->fmt.bitsPerSample, f->fmt.bytesPerSample);
                 printf("super %dx%d", f->w, f->h);
                 const char *keys[] = { "Super_height", "Super_hpad", "Super_vpad", "Super_pel", "Super_modeyuv", "Super_levels" };
                 for (int k = 0; k < 6; k++) printf(" %s=%lld", keys[k], (long long)mapGetInt(f->props, keys[k], 0, &e));
@@ -813,10 +880,10 @@ static int host_main(int argc, char **argv) {
         fclose(fo); printf("DONE\n"); return 0;
     }
     VSMap *m = createMap();
-    mapSetNode(m, "clip", clip, maReplace); mapSetNode(m, "super", sup, maReplace);
-    VSNode *out;
+    mapSetNode(m, "clip", useClip, maReplace); mapSetNode(m, "super", useSup, maReplace);
+    VSNode *out, *out2 = NULL; /* out2: the same filter on the integer clip beside the float one (x.intout) */
     if (!strcmp(pipeline, "finest")) {
-        VSMap *fm = createMap(); mapSetNode(fm, "super", sup, maReplace);
+        VSMap *fm = createMap(); mapSetNode(fm, "super", useSup, maReplace);
         VSNode *fin = invoke("Finest", fm, err, sizeof(err));
         if (!fin) die("Finest", err);
         printf("finest %dx%d\n", fin->vi.width, fin->vi.height);
@@ -862,6 +929,7 @@ static int host_main(int argc, char **argv) {
         mapSetNode(m, "mvbw", vec[0], maReplace); mapSetNode(m, "mvfw", vec[1], maReplace); add_args(m, 'b', nextra, extra);
         out = invoke("BlockFPS", m, err, sizeof(err));
         if (!out) die(pipeline, err);
+        if (fclip) printf("output format sample=%s bits=%d bytes=%d\n", sample_name(&out->vi.format), out->vi.format.bitsPerSample, out->vi.format.bytesPerSample);
         printf("blockfps frames=%d fps=%lld/%lld\n", out->vi.numFrames, (long long)out->vi.fpsNum, (long long)out->vi.fpsDen);
         for (int n = 0; n < out->vi.numFrames; n++) {
             const VSFrame *f = eval_frame(n, out, err, sizeof(err));
@@ -907,6 +975,12 @@ static int host_main(int argc, char **argv) {
         }
         mapSetNode(m, "vectors", mv, maReplace); add_args(m, 'f', nextra, extra);
         out = invoke(final == 3 ? "DegrainN" : "CompensateN", m, err, sizeof(err));
+        if (out && fclip && arg_value(nextra, extra, "x.intout")) { /* x.intout=<path>: the same filter on the integer clip and its super clip in the same graph, written there */
+            VSMap *m2 = createMap();
+            mapSetNode(m2, "clip", clip, maReplace); mapSetNode(m2, "super", sup, maReplace); mapSetNode(m2, "vectors", mv, maReplace); add_args(m2, 'f', nextra, extra);
+            out2 = invoke(final == 3 ? "DegrainN" : "CompensateN", m2, err, sizeof(err));
+            if (!out2) die(pipeline, err);
+        }
         if (out && final == 4) {
             isFlowFps = 1; outFrames = out->vi.numFrames; /* (the _Duration* line of frame 1, like flowfps) */
             printf("multicompensate frames=%d fps=%lld/%lld\n", out->vi.numFrames, (long long)out->vi.fpsNum, (long long)out->vi.fpsDen);
@@ -916,7 +990,7 @@ static int host_main(int argc, char **argv) {
     else if (flowFilter) { /* the per-sample filters (f.*): both vector clips, or one as `vectors` (x.vectors=fw: the forward one) */
         int fwd = 0;
         for (int i = 0; i < nextra; i++) if (!strcmp(extra[i], "x.vectors=fw")) fwd = 1;
-        if (!strcmp(flowFilter, "Mask")) { freeMap(m); m = createMap(); mapSetNode(m, "clip", clip, maReplace); } /* (mv.Mask takes no super clip) */
+        if (!strcmp(flowFilter, "Mask")) { freeMap(m); m = createMap(); mapSetNode(m, "clip", useClip, maReplace); } /* (mv.Mask takes no super clip) */
         if (flowPair) { mapSetNode(m, "mvbw", vec[0], maReplace); mapSetNode(m, "mvfw", vec[1], maReplace); }
         else mapSetNode(m, "vectors", vec[fwd], maReplace);
         add_args(m, 'f', nextra, extra);
@@ -937,6 +1011,7 @@ static int host_main(int argc, char **argv) {
         out = invoke(fn, m, err, sizeof(err));
     }
     if (!out) die(pipeline, err);
+    if (fclip) printf("output format sample=%s bits=%d bytes=%d\n", sample_name(&out->vi.format), out->vi.format.bitsPerSample, out->vi.format.bytesPerSample);
     const int times = getenv("MVX_HOST_TIMES") != NULL;
     double t0 = now_s();
     if (times) fprintf(stderr, "minihost: graph built at %.2f s after start\n", t0 - g_start);
@@ -963,6 +1038,16 @@ static int host_main(int argc, char **argv) {
         dump_frame(fo, f); freeFrame(f);
     }
     fclose(fo);
+    if (out2 && !failed) {
+        FILE *fo2 = fopen(arg_value(nextra, extra, "x.intout"), "wb");
+        if (!fo2) { fprintf(stderr, "cannot write %s\n", arg_value(nextra, extra, "x.intout")); return 2; }
+        for (int n = 0; n < outFrames; n++) {
+            const VSFrame *f = eval_frame(n, out2, err, sizeof(err));
+            if (!f) die("output frame of the integer graph", err);
+            dump_frame(fo2, f); freeFrame(f);
+        }
+        fclose(fo2);
+    }
     if (times) fprintf(stderr, "minihost: result file written in %.2f s; threads waited %.2f thread-seconds for frames other threads were producing\n", now_s() - t0, g_wait_s);
     for (int i = 0; i < nextra; i++)
         if (!strcmp(extra[i], "x.free=1")) { /* tear the graph down like a core that is being freed: every filter's free callback runs, consumers before producers */

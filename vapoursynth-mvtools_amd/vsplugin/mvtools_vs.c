@@ -13,6 +13,7 @@
  *     DepanAnalyse   DepanEstimate   DepanCompensate   DepanStabilise
  * and, with MVX_VS_MULTI=1, the temporal-radius filters over the multi vector clip (no reference counterpart; see their section)
  *     AnalyseN   RecalculateN   DegrainN   CompensateN   MultiField
+ * With MVX_VS_FLOAT=1 mv.Super and the filters that have a float entry in the library take 32-bit float clips; the switch registers no function (see g_vs_float).
  * DepanEstimate is ONE node where the reference chains three: its temporary DepanEstimateFFT / FFT2 and DepanEstimateX / Y / Zoom / Trust frame properties do not
  * exist here (the spectra stay on the device, the stage-2 results in a table of the instance); info=1 sets Depan*_info and invokes text.FrameProps as the reference does.
  * The shell keeps the reference's inter-filter data layout: super-frame geometry + Super_* props on frame 0
@@ -46,6 +47,19 @@
 #define PROP_ADATA "MVTools_MVAnalysisData"
 #define PROP_VECTORS "MVTools_vectors"
 #define PROP_SUPER_ID "_MVX_SuperId"
+
+/* MVX_VS_FLOAT=1 (read once, at the entry point): mv.Super and the filters with a float entry in the library take 32-bit float clips.  It registers no
+ * function and changes no argument string; without it every format test and message below is what it was.  A float clip is one the host calls stFloat with 32 bits. */
+static int g_vs_float;
+static int vi_is_float(const VSVideoInfo *vi) { return g_vs_float && vi->format.sampleType == stFloat && vi->format.bitsPerSample == 32; }
+/* the reference's format test of a `super` argument (MVAnalyse.c:506, MVFinest.c:165).  With the switch a float super clip passes it, so that the library's creation function
+ * refuses it with "<Name>: float super clips are not supported." */
+static int format_ok(const VSVideoInfo *vi, int orFloat) {
+    return mvx_vsh_is_constant_video_format(vi) && ((vi->format.bitsPerSample <= 16 && vi->format.sampleType == stInteger) || (orFloat && vi_is_float(vi))) &&
+           vi->format.subSamplingW <= 1 && vi->format.subSamplingH <= 1 && (vi->format.colorFamily == cfYUV || vi->format.colorFamily == cfGray);
+}
+static int super_format_ok(const VSVideoInfo *vi) { return format_ok(vi, 1); }
+static int integer_format_ok(const VSVideoInfo *vi) { return format_ok(vi, 0); }
 
 /* ------------------------------------------------------------------------------------------------ device frame cache */
 
@@ -442,7 +456,8 @@ static mvx_super *super_from_props(VSNode *super, const char *filter, char *erro
     a.hpad = hpad; a.vpad = vpad; a.pel = pel; a.levels = levels; a.chroma = modeyuv != 1; a.sharp = MVX_UNSET; a.rfilter = MVX_UNSET;
     mvx_super *s = NULL;
     char err[MVX_ERRLEN];
-    if (mvx_super_create(&a, &s, err)) { snprintf(error, esz, "%s: parameters from super clip appear to be wrong.", filter); return NULL; }
+    /* a float super clip (MVX_VS_FLOAT=1) gets the float handle: the filters without a float entry then refuse it with the library's own message */
+    if ((vi_is_float(vi) ? mvx_super_create_float : mvx_super_create)(&a, &s, err)) { snprintf(error, esz, "%s: parameters from super clip appear to be wrong.", filter); return NULL; }
     return s;
 }
 
@@ -765,6 +780,8 @@ static const VSFrame *VS_CC superGetFrame(int n, int reason, void *inst, void **
         for (int p = 0; p < g->si.num_planes; p++) ddst[p] = (char *)arena + g->off[p];
         if (!d->pelMode && g->copies > 1) /* the level-0 kernels write their share of the shadow planes themselves */
             rc = mvx_super_frames_shadow(d->sup, 1, (const void *const *)dsrc, d->srcPitch, (void *const *)ddst, g->pitch, g->shadowStride, st);
+        else if (mvx_super_is_float(d->sup)) /* (one level, no shadow copies, never a pelclip: superCreate) */
+            rc = mvx_super_frames(d->sup, 1, (const void *const *)dsrc, d->srcPitch, (void *const *)ddst, g->pitch, st);
         else {
             rc = mvx_super_frames_pelclip(d->sup, 1, (const void *const *)dsrc, d->srcPitch, (const void *const *)dpel, d->pelPitch, d->pelMode, (void *const *)ddst, g->pitch, st);
             if (!rc) rc = super_shadows(g, ddst, st);
@@ -845,8 +862,11 @@ static void VS_CC superCreate(const VSMap *in, VSMap *out, void *user, VSCore *c
     (void)user;
     VSNode *node = vs->mapGetNode(in, "clip", 0, 0);
     const VSVideoInfo *vi = vs->getVideoInfo(node);
-    if (!mvx_vsh_is_constant_video_format(vi) || vi->format.bitsPerSample > 16 || vi->format.sampleType != stInteger || vi->format.subSamplingW > 1 ||
-        vi->format.subSamplingH > 1 || (vi->format.colorFamily != cfYUV && vi->format.colorFamily != cfGray)) {
+    /* a float clip (MVX_VS_FLOAT=1) of a constant Gray or YUV format goes to mvx_super_create_float whatever its subsampling: levels, pel, sharp, rfilter, the format and
+     * the padding are then refused by the library, in the library's order */
+    const int isFloat = vi_is_float(vi) && mvx_vsh_is_constant_video_format(vi) && (vi->format.colorFamily == cfYUV || vi->format.colorFamily == cfGray);
+    if (!isFloat && (!mvx_vsh_is_constant_video_format(vi) || vi->format.bitsPerSample > 16 || vi->format.sampleType != stInteger || vi->format.subSamplingW > 1 ||
+        vi->format.subSamplingH > 1 || (vi->format.colorFamily != cfYUV && vi->format.colorFamily != cfGray))) {
         /* argument-value errors come first in the reference (MVSuper.c:177-192): let the library report them on a dummy format */
         mvx_super_args t = { 64, 64, 8, 1, 1, 0, opt_int(in, "hpad", vs), opt_int(in, "vpad", vs), opt_int(in, "pel", vs), opt_int(in, "levels", vs), opt_int(in, "chroma", vs), opt_int(in, "sharp", vs), opt_int(in, "rfilter", vs) };
         mvx_super *ts = NULL; char terr[MVX_ERRLEN];
@@ -861,12 +881,17 @@ static void VS_CC superCreate(const VSMap *in, VSMap *out, void *user, VSCore *c
     if (a.chroma != MVX_UNSET) a.chroma = !!a.chroma;
     mvx_super *sup = NULL;
     char err[MVX_ERRLEN];
-    if (mvx_super_create(&a, &sup, err)) { vs->mapSetError(out, err); vs->freeNode(node); return; }
+    if ((isFloat ? mvx_super_create_float : mvx_super_create)(&a, &sup, err)) { vs->mapSetError(out, err); vs->freeNode(node); return; }
     /* src/MVSuper.c:229-256 */
     int perr = 0;
     int32_t pelMode = 0;
     VSNode *pelclip = vs->mapGetNode(in, "pelclip", 0, &perr);
     if (perr) pelclip = NULL;
+    if (pelclip && isFloat) { /* (the library's pelclip entry refuses a float super clip: one message here, where the pelclip's own checks sit) */
+        vs->mapSetError(out, "Super: pelclip is not supported on float clips.");
+        mvx_super_destroy(sup); vs->freeNode(node); vs->freeNode(pelclip);
+        return;
+    }
     if (pelclip) {
         const VSVideoInfo *pvi = vs->getVideoInfo(pelclip);
         const int same = pvi->format.colorFamily == vi->format.colorFamily && pvi->format.sampleType == vi->format.sampleType &&
@@ -1440,8 +1465,7 @@ static void VS_CC analyseCreate(const VSMap *in, VSMap *out, void *user, VSCore 
     VSNode *node = vs->mapGetNode(in, "super", 0, 0);
     const VSVideoInfo *vi = vs->getVideoInfo(node);
     char err[1200];
-    if (!mvx_vsh_is_constant_video_format(vi) || vi->format.bitsPerSample > 16 || vi->format.sampleType != stInteger || vi->format.subSamplingW > 1 ||
-        vi->format.subSamplingH > 1 || (vi->format.colorFamily != cfYUV && vi->format.colorFamily != cfGray)) {
+    if (!super_format_ok(vi)) {
         vs->mapSetError(out, "Analyse: super clip must be GRAY, 420, 422, 440, or 444, up to 16 bits, with constant dimensions.");
         vs->freeNode(node);
         return;
@@ -1534,8 +1558,7 @@ static void VS_CC finestCreate(const VSMap *in, VSMap *out, void *user, VSCore *
     (void)user;
     VSNode *super = vs->mapGetNode(in, "super", 0, 0);
     const VSVideoInfo *vi = vs->getVideoInfo(super);
-    if (!mvx_vsh_is_constant_video_format(vi) || vi->format.bitsPerSample > 16 || vi->format.sampleType != stInteger || vi->format.subSamplingW > 1 ||
-        vi->format.subSamplingH > 1 || (vi->format.colorFamily != cfYUV && vi->format.colorFamily != cfGray)) {
+    if (!super_format_ok(vi)) {
         vs->mapSetError(out, "Finest: input clip must be GRAY, 420, 422, 440, or 444, up to 16 bits, with constant dimensions.");
         vs->freeNode(super);
         return;
@@ -1543,6 +1566,12 @@ static void VS_CC finestCreate(const VSMap *in, VSMap *out, void *user, VSCore *
     char err[1400] = "";
     mvx_super *sup = super_from_props(super, "Finest", err, sizeof(err), vs);
     if (!sup) { vs->mapSetError(out, err); vs->freeNode(super); return; }
+    if (mvx_super_is_float(sup)) { /* mvx_finest_frames' refusal (csrc/mvx_super.hip, "Finest: float super clips are not supported."), word for word and at creation: mvx_finest_size has
+                                    * no way to fail.  tests/test_vs_float_shell.py holds the two texts together */
+        vs->mapSetError(out, "Finest: float super clips are not supported.");
+        mvx_super_destroy(sup); vs->freeNode(super);
+        return;
+    }
     FinestData *d = (FinestData *)calloc(1, sizeof(*d));
     d->super = super; d->sup = sup; d->vi = *vi;
     super_geo(&d->geo, sup);
@@ -1793,6 +1822,7 @@ typedef struct Consumer {
     Gate gate;
     VSNode *nodes[14]; int nnodes;         /* every node the instance holds (the filters' own node members point into this) */
     mvx_super *sup; SuperGeo geo;          /* of the super clip (mv.Mask takes none) */
+    int floatEntry;                        /* the library has a *_create_float for this filter, which a float `clip` selects (MVX_VS_FLOAT=1) */
     void *engine; void (*destroy)(void *); /* the library's handle */
     VSFilterGetFrame body;                 /* the filter proper */
 } Consumer;
@@ -1851,10 +1881,15 @@ static void clip_pitches(ptrdiff_t pitch[3], const VSVideoInfo *vi, int bps) {
  * ties to the super clip's, so a clip of another size or format than the one the super clip was made from would be read or written outside its planes. */
 static void consumer_check_clip(const Consumer *c, const VSVideoInfo *vi, const VSVideoInfo *svi, int sizeFirst, char *err, size_t esz) {
     const mvx_super_info *si = &c->geo.si;
-    const int formatOk = mvx_vsh_is_constant_video_format(vi) && vi->format.bitsPerSample <= 16 && vi->format.sampleType == stInteger && vi->format.subSamplingW <= 1 &&
-                         vi->format.subSamplingH <= 1 && (vi->format.colorFamily == cfYUV || vi->format.colorFamily == cfGray);
+    /* MVX_VS_FLOAT=1: a float clip passes the format test of a filter that has a float entry in the library (c->floatEntry; the caller picks the entry by the clip's sample
+     * type); the size test compares the sample types as well.  Where the entry the caller is about to use and the super clip disagree -- the float entry with an integer
+     * super clip, an integer entry with a float one -- both tests are left out: that entry refuses the super clip whatever else it is given ("the float entry needs a float
+     * super clip." / "float super clips are not supported."), so no instance exists whose planes the size test has not tied to the super clip's */
+    const int floatClip = c->floatEntry && vi_is_float(vi);
+    if (floatClip != mvx_super_is_float(c->sup)) return;
+    const int formatOk = floatClip ? super_format_ok(vi) : integer_format_ok(vi);
     const int isSupers = si->width == vi->width && si->height == vi->height && si->super_width == svi->width && si->super_height == svi->height &&
-                         vi->format.bitsPerSample == svi->format.bitsPerSample && vi->format.colorFamily == svi->format.colorFamily &&
+                         vi->format.bitsPerSample == svi->format.bitsPerSample && vi->format.sampleType == svi->format.sampleType && vi->format.colorFamily == svi->format.colorFamily &&
                          vi->format.subSamplingW == svi->format.subSamplingW && vi->format.subSamplingH == svi->format.subSamplingH;
     if (!isSupers && (sizeFirst || formatOk)) snprintf(err, esz, "%s: wrong source or super clip frame size.", c->name);
     else if (!formatOk) snprintf(err, esz, "%s: input clip must be GRAY, 420, 422, 440, or 444, up to 16 bits, with constant dimensions.", c->name);
@@ -2171,12 +2206,13 @@ static void VS_CC compCreate(const VSMap *in, VSMap *out, void *user, VSCore *co
     if (!err[0]) {
         d->node = consumer_node(&d->c, in, "clip", vs);
         d->vi = vs->getVideoInfo(d->node);
+        d->c.floatEntry = 1;
         consumer_check_clip(&d->c, d->vi, vs->getVideoInfo(d->super), 1, err, sizeof(err)); /* (the size first, as MVCompensate.c:535-545) */
     }
     if (!err[0]) {
         clip_pitches(d->pitch, d->vi, d->vi->format.bytesPerSample);
         char lerr[MVX_ERRLEN];
-        if (mvx_compensate_create(&a, &d->ad, d->c.sup, d->c.geo.pitch, d->pitch, &d->cp, lerr)) snprintf(err, sizeof(err), "%s", lerr);
+        if ((vi_is_float(d->vi) ? mvx_compensate_create_float : mvx_compensate_create)(&a, &d->ad, d->c.sup, d->c.geo.pitch, d->pitch, &d->cp, lerr)) snprintf(err, sizeof(err), "%s", lerr);
         d->c.engine = d->cp;
     }
     if (err[0]) { consumer_fail(&d->c, err, out, vs); return; }
@@ -2277,7 +2313,8 @@ static void VS_CC fpsCreate(const VSMap *in, VSMap *out, void *user, VSCore *cor
         d->vi = *d->oldvi;
         clip_pitches(d->pitch, &d->vi, d->vi.format.bytesPerSample);
         char lerr[MVX_ERRLEN];
-        if (mvx_blockfps_create(&a, &d->bw, &d->fw, d->c.sup, d->oldvi->numFrames, d->oldvi->fpsNum, d->oldvi->fpsDen, d->c.geo.pitch, d->pitch, d->pitch, &d->bf, lerr))
+        d->c.floatEntry = 1;
+        if ((vi_is_float(d->oldvi) ? mvx_blockfps_create_float : mvx_blockfps_create)(&a, &d->bw, &d->fw, d->c.sup, d->oldvi->numFrames, d->oldvi->fpsNum, d->oldvi->fpsDen, d->c.geo.pitch, d->pitch, d->pitch, &d->bf, lerr))
             snprintf(err, sizeof(err), "%s", lerr);
         else consumer_check_clip(&d->c, &d->vi, vs->getVideoInfo(d->super), 0, err, sizeof(err));
         d->c.engine = d->bf;
@@ -2390,8 +2427,10 @@ static void VS_CC flowCreate(const VSMap *in, VSMap *out, void *user, VSCore *co
         d->vi = *d->oldvi;
         clip_pitches(d->pitch, &d->vi, d->vi.format.bytesPerSample);
         char lerr[MVX_ERRLEN];
-        const int rc = d->fps ? mvx_flowfps_create(&af, &d->bw, &d->fw, d->c.sup, d->oldvi->numFrames, d->oldvi->fpsNum, d->oldvi->fpsDen, d->c.geo.pitch, d->pitch, d->pitch, &d->fl, lerr)
-                              : mvx_flowinter_create(&ai, &d->bw, &d->fw, d->c.sup, d->oldvi->numFrames, d->c.geo.pitch, d->pitch, d->pitch, &d->fl, lerr);
+        const int flt = vi_is_float(d->oldvi);
+        d->c.floatEntry = 1;
+        const int rc = d->fps ? (flt ? mvx_flowfps_create_float : mvx_flowfps_create)(&af, &d->bw, &d->fw, d->c.sup, d->oldvi->numFrames, d->oldvi->fpsNum, d->oldvi->fpsDen, d->c.geo.pitch, d->pitch, d->pitch, &d->fl, lerr)
+                              : (flt ? mvx_flowinter_create_float : mvx_flowinter_create)(&ai, &d->bw, &d->fw, d->c.sup, d->oldvi->numFrames, d->c.geo.pitch, d->pitch, d->pitch, &d->fl, lerr);
         if (rc) snprintf(err, sizeof(err), "%s", lerr);
         else consumer_check_clip(&d->c, &d->vi, vs->getVideoInfo(d->super), 0, err, sizeof(err));
         d->c.engine = d->fl;
@@ -2501,7 +2540,8 @@ static void VS_CC flowCompCreate(const VSMap *in, VSMap *out, void *user, VSCore
         d->vi = vs->getVideoInfo(d->node);
         clip_pitches(d->pitch, d->vi, d->vi->format.bytesPerSample);
         char lerr[MVX_ERRLEN];
-        if (mvx_flowcomp_create(&a, &d->ad, d->c.sup, d->vi->numFrames, d->c.geo.pitch, d->pitch, d->pitch, &d->fc, lerr)) snprintf(err, sizeof(err), "%s", lerr);
+        d->c.floatEntry = 1;
+        if ((vi_is_float(d->vi) ? mvx_flowcomp_create_float : mvx_flowcomp_create)(&a, &d->ad, d->c.sup, d->vi->numFrames, d->c.geo.pitch, d->pitch, d->pitch, &d->fc, lerr)) snprintf(err, sizeof(err), "%s", lerr);
         else consumer_check_clip(&d->c, d->vi, vs->getVideoInfo(d->super), 0, err, sizeof(err));
         d->c.engine = d->fc;
     }
@@ -2584,7 +2624,8 @@ static void VS_CC blurCreate(const VSMap *in, VSMap *out, void *user, VSCore *co
         d->vi = vs->getVideoInfo(d->node);
         clip_pitches(d->pitch, d->vi, d->vi->format.bytesPerSample);
         char lerr[MVX_ERRLEN];
-        if (mvx_flowblur_create(&a, &d->bw, &d->fw, d->c.sup, d->vi->numFrames, d->c.geo.pitch, d->pitch, d->pitch, &d->fb, lerr)) snprintf(err, sizeof(err), "%s", lerr);
+        d->c.floatEntry = 1;
+        if ((vi_is_float(d->vi) ? mvx_flowblur_create_float : mvx_flowblur_create)(&a, &d->bw, &d->fw, d->c.sup, d->vi->numFrames, d->c.geo.pitch, d->pitch, d->pitch, &d->fb, lerr)) snprintf(err, sizeof(err), "%s", lerr);
         else consumer_check_clip(&d->c, d->vi, vs->getVideoInfo(d->super), 0, err, sizeof(err));
         d->c.engine = d->fb;
     }
@@ -2991,7 +3032,7 @@ static void VS_CC depanEstimateCreate(const VSMap *in, VSMap *out, void *user, V
 }
 
 /* ---- what mv.DepanCompensate (dc, ci) and mv.DepanStabilise (ds) share: the instance, the opening and the end of creation, the tail of a frame */
-typedef struct DepanWarpData { Consumer c; VSNode *node, *data; const VSVideoInfo *vi; ptrdiff_t pitch[3]; int height[3], info; mvx_depan_compensate *dc; mvx_depan_compensate_info ci; mvx_depan_stabilise *ds; } DepanWarpData;
+typedef struct DepanWarpData { Consumer c; VSNode *node, *data; const VSVideoInfo *vi; ptrdiff_t pitch[3]; int height[3], info, flt /* a float clip: the float entries */; mvx_depan_compensate *dc; mvx_depan_compensate_info ci; mvx_depan_stabilise *ds; } DepanWarpData;
 
 /* the instance with its clip and data nodes, the clip's format as the library takes it, and the pitches and heights of the device planes */
 static DepanWarpData *depan_warp_open(const char *name, VSFilterGetFrame body, void (*destroy)(void *), const VSMap *in, mvx_depan_clip *clip, const VSAPI *vs) {
@@ -3002,6 +3043,9 @@ static DepanWarpData *depan_warp_open(const char *name, VSFilterGetFrame body, v
     d->vi = vs->getVideoInfo(d->node);
     d->data = consumer_node(&d->c, in, "data", vs);
     depan_clip_of(clip, d->vi, NULL);
+    /* MVX_VS_FLOAT=1: a float clip of a constant Gray or YUV format goes to the library's float entry with its 32 bits; every other float clip stays a bit depth of 0 */
+    d->flt = vi_is_float(d->vi) && mvx_vsh_is_constant_video_format(d->vi) && (d->vi->format.colorFamily == cfYUV || d->vi->format.colorFamily == cfGray);
+    if (d->flt) clip->bits = 32;
     clip_pitches(d->pitch, d->vi, d->vi->format.bytesPerSample > 0 ? d->vi->format.bytesPerSample : 1);
     for (int p = 0; p < 3; p++) d->height[p] = p ? d->vi->height >> d->vi->format.subSamplingH : d->vi->height;
     return d;
@@ -3096,7 +3140,7 @@ static void VS_CC depanCompCreate(const VSMap *in, VSMap *out, void *user, VSCor
     FieldOpt fo;
     field_opt(&fo, in, vs);
     a.fields = fo.fields; a.tff = fo.tffExists ? fo.tff : MVX_UNSET;
-    if (mvx_depan_compensate_create(&a, &clip, d->vi->numFrames, vs->getVideoInfo(d->data)->numFrames, d->pitch, d->pitch, &d->dc, lerr)) { consumer_fail(&d->c, lerr, out, vs); return; }
+    if ((d->flt ? mvx_depan_compensate_create_float : mvx_depan_compensate_create)(&a, &clip, d->vi->numFrames, vs->getVideoInfo(d->data)->numFrames, d->pitch, d->pitch, &d->dc, lerr)) { consumer_fail(&d->c, lerr, out, vs); return; }
     mvx_depan_compensate_get_info(d->dc, &d->ci);
     depan_warp_register(d, "DepanCompensate", "DepanCompensate_info", d->dc, out, core, vs);
 }
@@ -3174,7 +3218,7 @@ static void VS_CC depanStabCreate(const VSMap *in, VSMap *out, void *user, VSCor
     a.pixaspect = opt_float_unset(in, "pixaspect", vs); a.tzoom = opt_float_unset(in, "tzoom", vs);
     a.addzoom = opt_int(in, "addzoom", vs); a.prev = opt_int(in, "prev", vs); a.next = opt_int(in, "next", vs); a.mirror = opt_int(in, "mirror", vs); a.blur = opt_int(in, "blur", vs);
     a.subpixel = opt_int(in, "subpixel", vs); a.fitlast = opt_int(in, "fitlast", vs); a.method = opt_int(in, "method", vs); a.fields = opt_int(in, "fields", vs);
-    if (mvx_depan_stabilise_create(&a, &clip, d->vi->numFrames, vs->getVideoInfo(d->data)->numFrames, d->vi->fpsNum, d->vi->fpsDen, d->pitch, d->pitch, &d->ds, lerr)) { consumer_fail(&d->c, lerr, out, vs); return; }
+    if ((d->flt ? mvx_depan_stabilise_create_float : mvx_depan_stabilise_create)(&a, &clip, d->vi->numFrames, vs->getVideoInfo(d->data)->numFrames, d->vi->fpsNum, d->vi->fpsDen, d->pitch, d->pitch, &d->ds, lerr)) { consumer_fail(&d->c, lerr, out, vs); return; }
     depan_warp_register(d, "DepanStabilise", "DepanStabilise_info", d->ds, out, core, vs);
 }
 
@@ -3423,11 +3467,6 @@ static void VS_CC analyseNFree(void *inst, VSCore *core, const VSAPI *vs) {
     consumerFree(inst, core, vs);
 }
 
-static int video_format_ok(const VSVideoInfo *vi) {
-    return mvx_vsh_is_constant_video_format(vi) && vi->format.bitsPerSample <= 16 && vi->format.sampleType == stInteger && vi->format.subSamplingW <= 1 &&
-           vi->format.subSamplingH <= 1 && (vi->format.colorFamily == cfYUV || vi->format.colorFamily == cfGray);
-}
-
 static void VS_CC analyseNCreate(const VSMap *in, VSMap *out, void *user, VSCore *core, const VSAPI *vs) {
     warm_barrier();
     (void)user;
@@ -3442,7 +3481,7 @@ static void VS_CC analyseNCreate(const VSMap *in, VSMap *out, void *user, VSCore
     field_opt(&d->fo, in, vs);
     {
         VSNode *node = vs->mapGetNode(in, "super", 0, NULL);
-        const int ok = video_format_ok(vs->getVideoInfo(node));
+        const int ok = super_format_ok(vs->getVideoInfo(node));
         vs->freeNode(node);
         if (!ok) snprintf(err, sizeof(err), "AnalyseN: super clip must be GRAY, 420, 422, 440, or 444, up to 16 bits, with constant dimensions.");
     }
@@ -3691,8 +3730,11 @@ static void VS_CC degrainNCreate(const VSMap *in, VSMap *out, void *user, VSCore
     if (!err[0]) {
         d->node = consumer_node(&d->c, in, "clip", vs);
         d->vi = vs->getVideoInfo(d->node);
+        d->c.floatEntry = 1;
         consumer_check_clip(&d->c, d->vi, vs->getVideoInfo(d->super), 0, err, sizeof(err));
     }
+    const int flt = !err[0] && vi_is_float(d->vi);
+    if (flt && out16) snprintf(err, sizeof(err), "DegrainN: out16 is not supported on float clips.");
     if (!err[0]) {
         d->outvi = *d->vi;
         if (out16 && !vs->queryVideoFormat(&d->outvi.format, d->vi->format.colorFamily, stInteger, 16, d->vi->format.subSamplingW, d->vi->format.subSamplingH, core))
@@ -3702,7 +3744,7 @@ static void VS_CC degrainNCreate(const VSMap *in, VSMap *out, void *user, VSCore
         clip_pitches(d->pitch, d->vi, d->vi->format.bytesPerSample);
         clip_pitches(d->dstPitch, &d->outvi, d->outvi.format.bytesPerSample);
         char lerr[MVX_ERRLEN];
-        if ((out16 ? mvx_degrain_n_create_out16 : mvx_degrain_n_create)(&a, &d->mi.ad0, d->c.sup, d->pitch, d->c.geo.pitch, d->dstPitch, &d->dg, lerr)) snprintf(err, sizeof(err), "%s", lerr);
+        if ((flt ? mvx_degrain_n_create_float : out16 ? mvx_degrain_n_create_out16 : mvx_degrain_n_create)(&a, &d->mi.ad0, d->c.sup, d->pitch, d->c.geo.pitch, d->dstPitch, &d->dg, lerr)) snprintf(err, sizeof(err), "%s", lerr);
         d->c.engine = d->dg;
     }
     if (err[0]) { consumer_fail(&d->c, err, out, vs); return; }
@@ -3858,12 +3900,13 @@ static void VS_CC compNCreate(const VSMap *in, VSMap *out, void *user, VSCore *c
     if (!err[0]) {
         d->node = consumer_node(&d->c, in, "clip", vs);
         d->clipvi = vs->getVideoInfo(d->node);
+        d->c.floatEntry = 1;
         consumer_check_clip(&d->c, d->clipvi, vs->getVideoInfo(d->super), 1, err, sizeof(err));
     }
     if (!err[0]) {
         clip_pitches(d->pitch, d->clipvi, d->clipvi->format.bytesPerSample);
         char lerr[MVX_ERRLEN];
-        if (mvx_compensate_n_create(&a, tr, &d->mi.ad0, d->c.sup, d->c.geo.pitch, d->pitch, &d->cn, lerr)) snprintf(err, sizeof(err), "%s", lerr);
+        if ((vi_is_float(d->clipvi) ? mvx_compensate_n_create_float : mvx_compensate_n_create)(&a, tr, &d->mi.ad0, d->c.sup, d->c.geo.pitch, d->pitch, &d->cn, lerr)) snprintf(err, sizeof(err), "%s", lerr);
         d->c.engine = d->cn;
     }
     if (!err[0] && (int64_t)d->clipvi->numFrames * (2 * tr + 1) > 2147483647LL) snprintf(err, sizeof(err), "CompensateN: the output clip would have too many frames.");
@@ -3942,6 +3985,10 @@ VS_EXTERNAL_API(void) VapourSynthPluginInit2(VSPlugin *plugin, const VSPLUGINAPI
                              "clip:vnode;", compCreate, NULL, plugin);
     /* dct 1..4 are opt-in in the library (mvx_enable_dct_float): MVX_VS_DCT=1, read here, once, switches them on for this process.   */
     if (env_long("MVX_VS_DCT", 0)) (void)mvx_enable_dct_float(1);
+    /* 32-bit float clips, by a switch of its own, read the same way: MVX_VS_FLOAT=1.  It registers nothing: mv.Super and the filters with a float entry in the library
+     * (Compensate, BlockFPS; DegrainN, CompensateN; FlowInter, FlowFPS, Flow, FlowBlur; DepanCompensate, DepanStabilise -- each behind its family's switch) then take a
+     * float clip, and every other filter refuses one.   */
+    g_vs_float = env_long("MVX_VS_FLOAT", 0) != 0;
     /* The per-sample filters are opt-in for now: MVX_VS_FLOW=1 in the host's environment when the plugin is loaded (read here, once).  Without it the
      * plugin registers exactly the functions above.   */
     if (env_long("MVX_VS_FLOW", 0)) {
